@@ -16,6 +16,10 @@ One process per GPU, no data-path collective except the single accumulator reduc
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps, writes the last step's outputs (--dump-outputs DIR) and prints the line:
+metric / value / ms_per_step and the stage timers of the timed steps. --full adds what takes runs of its own after the
+timed region: the roofline and per-kernel figures (sample steps), the host-fed and --files legs and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -51,7 +55,13 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="ecc_4k", choices=sorted(WORKLOADS))
     ap.add_argument("--frames-per-gpu", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also the figures that take runs of their own: roofline and per-kernel sample "
+                         "steps, host-fed leg, --files leg, CPU baseline (a plain run reports the timed steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float32 / float64; the stacked "
+                         "image as a fixed, seeded sample of its rows where it exceeds 48 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-frames", type=int, default=0, help="frames in the CPU baseline sample (0 = cores+1)")
     ap.add_argument("--ecc-slots", type=int, default=0)
     ap.add_argument("--opt", action="append", default=[], help="engine tuning knob name=value (stk_set_option)")
@@ -62,20 +72,25 @@ def main() -> None:
                     help="N > 1 from ONE process: a multi-device context (stk_create_multi) shards, runs one host thread per GPU "
                          "and reduces with RCCL inside the library — the call shape of the Rust drop-in. Launch WITHOUT torchrun.")
     ap.add_argument("--host-fed-steps", type=int, default=2,
-                    help="N = 1: extra steps after the timed region with the stack in PINNED HOST memory (H2D included); 0 = skip")
+                    help="--full, N = 1: extra steps after the timed region with the stack in PINNED HOST memory (H2D included); "
+                         "0 = skip")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N > 1 rehearsal on a one-GPU box: every rank uses cuda:0 and the reduce goes through gloo/CPU "
                          "(checks the sharded code path, not a performance number)")
     ap.add_argument("--files", default="", choices=["", "tiff", "pnm"],
-                    help="N = 1, ecc / keypoint workloads: ALSO time the reference's own call shape (a list of file paths, "
+                    help="--full, N = 1, ecc / keypoint workloads: ALSO time the reference's own call shape (a list of file paths, "
                          "lib.rs:129-137, 702-710): the stack is written once to --files-dir as uncompressed TIFF or binary PNM, "
                          "then stk_*_match_files decodes on host threads into pinned memory while the engine runs; never `value`")
     ap.add_argument("--files-dir", default="/dev/shm", help="where --files writes the stack (tmpfs: the figure is decode + engine, not disk)")
     ap.add_argument("--files-steps", type=int, default=2)
     ap.add_argument("--profile-launches", type=int, default=1,
-                    help="0: no roofline sample; n >= 1: ONE extra step after the timed region (never inside it) with a HIP event "
-                         "pair around every n-th ECC iteration launch (roofline.achieved)")
+                    help="--full; 0: no roofline sample; n >= 1: ONE extra step after the timed region (never inside it) with a "
+                         "HIP event pair around every n-th ECC iteration launch (roofline.achieved)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.files and not args.full:
+        ap.error("--files is a leg of the --full run")
 
     import numpy as np
     import torch
@@ -236,10 +251,13 @@ def main() -> None:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     value = n_global * args.steps / elapsed
+    # what rank 0's caller holds after the last timed step: the stacked image, the counters and its shard's per-frame stats
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, totals, last_stats)
 
-    # ---- after the timed region: ONE step with an event pair around every `stride`-th ECC iteration launch (rank 0) ----
+    # ---- --full, after the timed region: ONE step with an event pair around every `stride`-th ECC iteration launch (rank 0) ----
     sample = None
-    if rank == 0 and api in ("ecc", "hybrid") and args.profile_launches > 0:
+    if args.full and rank == 0 and api in ("ecc", "hybrid") and args.profile_launches > 0:
         st.set_option("profile", 2)
         st.set_option("profile_stride", stride)
         try:
@@ -252,7 +270,7 @@ def main() -> None:
     # bracket those kernels alone: in the timed steps the lanes' launches overlap one another, and a per-lane event pair
     # then measures a kernel that shares the device (its bytes / its time would overstate the rate) ----
     kp_sample = None
-    if rank == 0 and api in ("keypoint", "hybrid") and args.profile_launches > 0:
+    if args.full and rank == 0 and api in ("keypoint", "hybrid") and args.profile_launches > 0:
         lanes_cfg = 3
         for kv in args.opt:
             if kv.split("=", 1)[0] == "kp_lanes":
@@ -267,7 +285,7 @@ def main() -> None:
     # ---- and what a plain float4 stream achieves on this card in this run: the 1/n scale kernel (read 4 B + write 4 B per
     # float of a W x H x 3 image), best of 5 by its own HIP-event timer ----
     stream_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         best = None
         for _ in range(5):
             st.finalize_mean(accs[0], max(totals[0], 1), out)
@@ -320,7 +338,7 @@ def main() -> None:
         wsrc = kp_sample if kp_sample is not None else dict(agg, **{"_steps": args.steps})
         wsteps = 1 if kp_sample is not None else args.steps
         alone = "one extra single-pipeline step (kp_lanes = 1) after the timed region" if kp_sample is not None else "stage timers of the timed steps"
-        if wsrc["warp_ms"] > 0:
+        if args.full and wsrc["warp_ms"] > 0:
             # fused fold: every frame's source read once + the accumulator written once per launch (no read: the launch
             # overwrites); SURVEY 8d's per-frame figure (source + accumulator read + write for EVERY frame) is the unfused cost
             wb = wsrc["warp_frames"] * src_b + wsrc["warp_launches"] * 12 * px
@@ -329,7 +347,7 @@ def main() -> None:
                             "bytes": "frames x %d B/px source + 12 B/px accumulator write per launch" % (src_b // px),
                             "GBps": round(g, 1), "frac": round(g / HBM_PEAK_GBS, 4), "ms_per_step": round(wsrc["warp_ms"] / wsteps, 3),
                             "timing": alone})
-        if api == "ecc" and world == 1:
+        if args.full and api == "ecc" and world == 1:
             # template preparation: in the timed steps it runs on the prep stream under the iteration of the first frames
             # (its time is inside align_ms); its own stage timer needs a step with the overlap switched off, outside the
             # timed region
@@ -345,7 +363,7 @@ def main() -> None:
                             "GBps": round(g, 1), "frac": round(g / HBM_PEAK_GBS, 4), "ms_per_step": round(prep_ms, 3),
                             "note": "one extra step with prep_overlap = 0 (not in the timed region); in the timed steps this runs "
                                     "under the ECC iteration of the first frames"})
-        if wsrc["fast_ms"] > 0:
+        if args.full and wsrc["fast_ms"] > 0:
             # FAST-9/16 + NMS + Harris short list over the 8 pyramid levels: reads each level's u8 pixels once
             g = wsrc["fast_pixels"] / wsrc["fast_ms"] / 1e6
             kernels.append({"kernel": "fast_nms_tiled_all_kernel + threshold + pick + describe (all 8 levels, one launch each per batch)",
@@ -358,7 +376,8 @@ def main() -> None:
                                "unit": "GB/s", "frac": k["frac"], "traffic": None,
                                "peak_achievable": round(stream_gbs, 1) if stream_gbs else None,
                                "timing": "HIP events around the FAST launches of every ORB batch, engine stream; " + alone}
-        res["kernels"] = kernels
+        if args.full:
+            res["kernels"] = kernels
         its = [s["iterations"] for s in (last_stats or [])[1:]]
         res["stages"] = {
             "prep_ms_per_step": round(agg["prep_ms"] / args.steps, 3),
@@ -371,7 +390,7 @@ def main() -> None:
             "ecc_ring_fallbacks_per_step": round(agg["ecc_ring_fallbacks"] / args.steps, 3),
         }
         # ---- host-fed: the same stack in PINNED HOST memory, H2D inside the timed region (SURVEY 8d metric ii) ----
-        if world == 1 and args.host_fed_steps > 0:
+        if args.full and world == 1 and args.host_fed_steps > 0:
             host = frames.cpu().pin_memory()
             run_shard(host, accs[0])                                        # warm-up: staging buffers, first-touch
             torch.cuda.synchronize()
@@ -394,15 +413,45 @@ def main() -> None:
                                "note": "frames in pinned host memory; copy stream -> prep stream -> gated ECC queue; never `value`"}
             del host
         # ---- the reference's own call shape: a list of file paths (decode on host threads inside the call) ----
-        if world == 1 and args.files and api in ("ecc", "keypoint"):
+        if args.full and world == 1 and args.files and api in ("ecc", "keypoint"):
             res["files"] = files_leg(args, st, frames, api, ecc_params, kp_params, n_global, W, H)
         # ---- CPU baseline: the oracle (a port of the reference's OpenCV/Rayon path) on host cores ----
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(args, api, frames, W, H)
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_IMAGE_BYTES = 48 << 20        # the stacked image's share of the --dump-outputs budget (64 MB in all)
+
+
+def dump_outputs(d, image, totals=None, stats=None):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one .npy per array.
+
+    stacked.npy       the stacked image (H x W x C float32), or where that exceeds DUMP_IMAGE_BYTES a fixed sample of its
+                      rows (numpy PCG64 seed 0, ascending): 4K holds 1092 of 2160 rows
+    stacked_rows.npy  the row numbers stacked.npy holds (float64)
+    counts.npy        frames folded, frames dropped (float64; one-process-per-GPU runs)
+    warps.npy         per frame of rank 0's shard: the 3x3 warp (float64), and frame_<field>.npy the other per-frame
+                      statistics (status, iterations, rho, n_keypoints, n_matches, n_inliers), where the path returned them"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    img = image.cpu().numpy() if hasattr(image, "cpu") else np.asarray(image)
+    img = np.asarray(img, np.float32)
+    rows = np.arange(img.shape[0])
+    if img.nbytes > DUMP_IMAGE_BYTES:
+        k = DUMP_IMAGE_BYTES // img[0].nbytes
+        rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(img.shape[0], k, replace=False))
+    np.save(os.path.join(d, "stacked.npy"), np.ascontiguousarray(img[rows]))
+    np.save(os.path.join(d, "stacked_rows.npy"), rows.astype(np.float64))
+    if totals is not None:
+        np.save(os.path.join(d, "counts.npy"), np.asarray(totals, np.float64))
+    if stats:
+        np.save(os.path.join(d, "warps.npy"), np.stack([np.asarray(s["warp"], np.float64) for s in stats]))
+        for key in ("status", "iterations", "rho", "n_keypoints", "n_matches", "n_inliers"):
+            np.save(os.path.join(d, f"frame_{key}.npy"), np.asarray([s[key] for s in stats], np.float64))
 
 
 def result_header(args, value, elapsed, world, scaling, api, W, H, n_global, fpg, reduce_desc, parallelism):
@@ -599,9 +648,11 @@ def single_process(args, torch, np, synth, Stacker, shard_moving_frames, W, H, n
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        image = step()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, image)
     res = result_header(args, n_global * args.steps / elapsed, elapsed, n_dev, scaling, api, W, H, n_global, n_global / n_dev,
                         "RCCL ncclReduce inside the library (stk_create_multi)" if not args.rehearse_on_one_gpu
                         else "members share one GPU: local adds (rehearsal)", f"frame-shard x{n_dev}, ONE process, one host thread per GPU")

@@ -243,6 +243,104 @@ def _write_bmp(path, img, palette=None, top_down=False):
         f.write(pal + b"".join(rows))
 
 
+_JPEG_LUM = [16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+             14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+             49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99]
+_JPEG_CHROM = [17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+               47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32
+_ZIGZAG = sorted(range(64), key=lambda k: (k // 8 + k % 8, k // 8 if (k // 8 + k % 8) % 2 else -(k // 8)))
+
+
+def _write_jpeg(path, img, quality=90, subsampling="420"):
+    """Minimal baseline JPEG writer (JFIF, no restart markers): 8-bit grey (HxW) or colour (HxWx3 given as BGR) with
+    chroma 4:4:4 or 4:2:0 (2 x 2 mean). The Annex K quantisation tables scaled by `quality` as libjpeg scales them;
+    flat Huffman tables (every DC category a 4-bit code, every AC run/size symbol an 8-bit one): valid, if a little
+    larger than the standard ones."""
+    import struct
+    a = np.asarray(img, np.uint8)
+    h, w = a.shape[:2]
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    qt = [np.clip((np.array(t) * scale + 50) // 100, 1, 255) for t in (_JPEG_LUM, _JPEG_CHROM)]
+    if a.ndim == 2:
+        planes, samp, mcu = [a.astype(np.float64)], [1], 8
+    else:
+        b, g, r = (a[..., i].astype(np.float64) for i in range(3))
+        planes = [0.299 * r + 0.587 * g + 0.114 * b, -0.168736 * r - 0.331264 * g + 0.5 * b + 128,
+                  0.5 * r - 0.418688 * g - 0.081312 * b + 128]
+        samp, mcu = ([2, 1, 1], 16) if subsampling == "420" else ([1, 1, 1], 8)
+    H, W = -(-h // mcu) * mcu, -(-w // mcu) * mcu
+    u = np.arange(8)
+    C = np.sqrt(2 / 8) * np.cos((2 * u[None, :] + 1) * u[:, None] * np.pi / 16)
+    C[0] /= np.sqrt(2)
+    coefs = []                                               # per component: (blocks down, blocks across, 64) in zigzag order
+    for c, p in enumerate(planes):
+        p = np.pad(p, ((0, H - h), (0, W - w)), mode="edge")
+        f = mcu // 8 // samp[c]
+        if f > 1:
+            p = p.reshape(H // f, f, W // f, f).mean(axis=(1, 3))
+        blk = p.reshape(p.shape[0] // 8, 8, p.shape[1] // 8, 8).transpose(0, 2, 1, 3) - 128.0
+        q = np.round(C @ blk @ C.T / qt[min(c, 1)].reshape(8, 8)).astype(np.int64)
+        coefs.append(q.reshape(q.shape[0], q.shape[1], 64)[..., _ZIGZAG])
+    ac_syms = [0x00, 0xF0] + [(r << 4) | s for r in range(16) for s in range(1, 11)]
+    ac_code = {s: i for i, s in enumerate(ac_syms)}
+    vals, lens = [], []
+
+    def put(v, n):
+        if n:
+            vals.append(v); lens.append(n)
+
+    def amp(v):
+        s = int(abs(v)).bit_length()
+        return s, (v if v >= 0 else v + (1 << s) - 1)
+
+    pred = [0] * len(planes)
+    for my in range(H // mcu):
+        for mx in range(W // mcu):
+            for c, zz in enumerate(coefs):
+                for dy in range(samp[c]):
+                    for dx in range(samp[c]):
+                        z = zz[my * samp[c] + dy, mx * samp[c] + dx].tolist()
+                        s, v = amp(z[0] - pred[c])
+                        pred[c] = z[0]
+                        put(s, 4); put(v, s)
+                        last = 0
+                        for k in np.flatnonzero(z[1:]).tolist():
+                            run = k - last
+                            while run > 15:
+                                put(ac_code[0xF0], 8); run -= 16
+                            s, v = amp(z[k + 1])
+                            put(ac_code[(run << 4) | s], 8); put(v, s)
+                            last = k + 1
+                        if last != 63:
+                            put(ac_code[0x00], 8)
+    vals, lens = np.array(vals, np.int64), np.array(lens, np.int64)
+    idx = np.repeat(np.arange(len(lens)), lens)
+    pos = np.arange(lens.sum()) - np.repeat(np.cumsum(lens) - lens, lens)
+    bits = (vals[idx] >> (lens[idx] - 1 - pos)) & 1
+    data = np.packbits(np.concatenate([bits, np.ones(-len(bits) % 8, np.int64)]).astype(np.uint8))
+    data = np.insert(data, np.flatnonzero(data == 0xFF) + 1, 0)   # byte stuffing
+
+    def seg(marker, body):
+        return struct.pack(">HH", marker, len(body) + 2) + body
+    nq = 1 if len(planes) == 1 else 2
+    out = b"\xff\xd8" + seg(0xFFE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    out += seg(0xFFDB, b"".join(bytes([i]) + bytes(qt[i].astype(np.uint8)[_ZIGZAG].tolist()) for i in range(nq)))
+    out += seg(0xFFC0, struct.pack(">BHHB", 8, h, w, len(planes)) +
+               b"".join(bytes([c + 1, (samp[c] << 4) | samp[c], min(c, 1)]) for c in range(len(planes))))
+    dc_counts, ac_counts = [0] * 16, [0] * 16
+    dc_counts[3], ac_counts[7] = 12, len(ac_syms)
+    out += seg(0xFFC4, bytes([0x00] + dc_counts + list(range(12))) + bytes([0x10] + ac_counts + ac_syms))
+    out += seg(0xFFDA, bytes([len(planes)]) + b"".join(bytes([c + 1, 0x00]) for c in range(len(planes))) + bytes([0, 63, 0]))
+    with open(path, "wb") as f:
+        f.write(out + data.tobytes() + b"\xff\xd9")
+
+
+@pytest.fixture(scope="session")
+def write_jpeg():
+    """Writer of test JPEGs (baseline, Huffman-coded; no encoder in the main interpreter)."""
+    return _write_jpeg
+
+
 @pytest.fixture(scope="session")
 def write_tiff_tiled():
     return _write_tiff_tiled

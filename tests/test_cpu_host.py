@@ -119,7 +119,8 @@ def test_synthetic_generator_is_seeded_and_sharded_consistently():
 
 def test_orb_bit_pattern_is_pinned():
     """ORB's 256 BRIEF test pairs (OpenCV `bit_pattern_31_`): pinned by hash, and row by row against scikit-image's
-    verbatim copy of the OpenCV table where that package happens to be installed (it is in the build container)."""
+    verbatim copy of the OpenCV table (skimage/feature/orb_descriptor_positions.txt of scikit-image 0.18.3, stored as
+    tests/golden/orb_pattern_skimage.npy)."""
     import hashlib
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -128,9 +129,8 @@ def test_orb_bit_pattern_is_pinned():
     table = np.array([int(v) for v in re.findall(r"-?\d+", body)], dtype=np.int8)
     assert table.size == 1024 and np.abs(table).max() <= 13          # 31x31 patch, rotated radius <= 15*sqrt(2)/... fits
     assert hashlib.sha256(table.tobytes()).hexdigest() == "2164181aea6ff9ac426ca512d5130d15e1f6e3cd47b1cbdd568bbe1e55d49023"
-    sk = "/opt/conda/lib/python3.9/site-packages/skimage/feature/orb_descriptor_positions.txt"
-    if os.path.exists(sk):
-        assert np.array_equal(np.loadtxt(sk).astype(np.int8).reshape(-1), table)
+    sk = np.load(os.path.join(root, "tests", "golden", "orb_pattern_skimage.npy"))
+    assert sk.shape == (256, 4) and np.array_equal(sk.reshape(-1), table)
 
 
 def test_header_is_plain_c_and_a_c_caller_links(tmp_path):
@@ -288,28 +288,21 @@ def test_shard_arithmetic_of_the_library_matches_shard_py():
     assert lib.stk_shard_moving_frames(5, 2, 2, C.byref(f), C.byref(c)) == 2
 
 
-def _conda_pillow_jpegs(tmp_path):
-    """JPEG files written by the Pillow of the image's conda interpreter (the main interpreter has none) and Pillow's own
-    decode of them; None where that interpreter is absent."""
-    import subprocess
-    py = "/opt/conda/bin/python3.9"
-    if not os.path.exists(py):
-        return None
-    code = (
-        "import numpy as np, sys\nfrom PIL import Image\nd = sys.argv[1]\nh, w = 123, 211\n"
-        "yy, xx = np.mgrid[0:h, 0:w]\n"
-        "img = np.stack([xx * 255 // w, yy * 255 // h, (xx + yy) * 3 % 256], -1).astype(np.uint8)\n"
-        "img[30:60, 40:90] = [250, 10, 30]\n"
-        "Image.fromarray(img).save(d + '/c444.jpg', quality=92, subsampling=0)\n"
-        "Image.fromarray(img).save(d + '/c420.jpg', quality=85, subsampling=2)\n"
-        "Image.fromarray(img).save(d + '/prog.jpg', quality=85, progressive=True, subsampling=0)\n"
-        "Image.fromarray(img[..., 0]).save(d + '/grey.jpg', quality=90)\n"
-        "np.save(d + '/src.npy', img)\n"
-        "for n in ('c444', 'c420', 'prog', 'grey'):\n    np.save(d + '/' + n + '.npy', np.asarray(Image.open(d + '/' + n + '.jpg')))\n")
-    r = subprocess.run([py, "-c", code, str(tmp_path)], capture_output=True, text=True)
-    if r.returncode != 0:
-        return None
-    return {n: np.load(tmp_path / (n + ".npy")) for n in ("src", "c444", "c420", "prog", "grey")}
+def _pillow_jpegs(tmp_path):
+    """JPEG files written by Pillow (stored in tests/golden/jpeg_v1.npz by tests/golden/make_jpeg.py), copied into
+    `tmp_path`; the picture they encode (`src`) and Pillow's own decode of them (stored as the difference from `src`)."""
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_v1.npz"))
+    for n in ("c444", "c420", "prog", "grey"):
+        (tmp_path / (n + ".jpg")).write_bytes(gold["host_%s_jpg" % n].tobytes())
+    h, w = 123, 211
+    yy, xx = np.mgrid[0:h, 0:w]
+    src = np.stack([xx * 255 // w, yy * 255 // h, (xx + yy) * 3 % 256], -1).astype(np.uint8)
+    src[30:60, 40:90] = [250, 10, 30]
+    ref = {"src": src}
+    for n in ("c444", "prog", "grey"):
+        base = src[..., 0] if n == "grey" else src
+        ref[n] = (base.astype(np.int16) + gold["host_%s_minus_src" % n]).astype(np.uint8)
+    return ref
 
 
 def test_imread_jpeg_through_runtime_libjpeg(tmp_path):
@@ -318,9 +311,7 @@ def test_imread_jpeg_through_runtime_libjpeg(tmp_path):
     families agree by construction (grey; colour without chroma subsampling: <= 1 level), same content otherwise (4:2:0:
     libjpeg-turbo — OpenCV's decoder — and Pillow's IJG 9 upsample chroma differently)."""
     lib = _ffi.load()
-    ref = _conda_pillow_jpegs(tmp_path)
-    if ref is None:
-        pytest.skip("no Pillow to write test JPEGs with")
+    ref = _pillow_jpegs(tmp_path)
 
     def read(name, expect=0):
         w, h, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()

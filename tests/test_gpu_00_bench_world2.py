@@ -47,7 +47,7 @@ def _check_contract(v, n_gpus):
 @pytest.mark.parametrize("extra", [[], ["--no-reduce-overlap"]], ids=["reduce-overlapped", "reduce-waited"])
 def test_bench_two_ranks_under_torchrun(extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), BENCH] + COMMON + extra
+           "--master-port", str(_free_port()), BENCH] + COMMON + ["--full"] + extra
     r = subprocess.run(cmd, env=dict(os.environ, MASTER_ADDR="127.0.0.1"), capture_output=True, text=True, timeout=840, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     v = _json_line(r.stdout)

@@ -192,12 +192,11 @@ def test_host_fed_pipeline_equals_device_resident(stacker):
         stacker.set_option("upload_batch", 8)
 
 
-def test_files_are_decoded_in_parallel_into_pinned_memory(stacker, tmp_path):
+def test_files_are_decoded_in_parallel_into_pinned_memory(stacker, tmp_path, write_jpeg):
     """*_match_files decodes frames 1..n-1 on a pool of host threads straight into one page-locked block (the reference
     decodes inside its Rayon fold, lib.rs:200, 756): same image as the frame-based call on the same pixels; with several
     unreadable files the one reported is the FIRST in list order, whichever thread met it; a JPEG stack (the reference's
     own data set is JPEG) goes through the same route."""
-    import os, subprocess
     frames, _ = synth.make_stack(24, 320, 240)
     fr = frames.numpy()
     paths = []
@@ -217,19 +216,10 @@ def test_files_are_decoded_in_parallel_into_pinned_memory(stacker, tmp_path):
     with pytest.raises(Exception) as ei:
         stacker.ecc_match_files(paths[:3] + [small] + paths[3:], ecc)
     assert "differs in size" in str(ei.value)
-    py = "/opt/conda/bin/python3.9"
-    if not os.path.exists(py):
-        return
-    np.save(tmp_path / "stack.npy", fr[:6])
-    # (round 4: the snippet used to carry literal backslash-n sequences, was a SyntaxError for the side interpreter, and this
-    # half of the test returned early without ever running)
-    code = ("import numpy as np, sys\nfrom PIL import Image\nd = sys.argv[1]\na = np.load(d + '/stack.npy')\n"
-            "for i, f in enumerate(a):\n    Image.fromarray(f[..., ::-1]).save(d + '/j%02d.jpg' % i, quality=95, subsampling=0)\n")
-    r = subprocess.run([py, "-c", code, str(tmp_path)], capture_output=True)
-    if r.returncode != 0:
-        assert b"No module named" in r.stderr, r.stderr          # no Pillow in that interpreter: nothing to write JPEGs with
-        return
+    # frames 0..5 of the same stack as baseline JPEG files (quality 95, 4:4:4)
     jpaths = [tmp_path / ("j%02d.jpg" % i) for i in range(6)]
+    for i, p in enumerate(jpaths):
+        write_jpeg(p, fr[i], quality=95, subsampling="444")
     decoded = [stacker.imread(p) for p in jpaths]
     assert decoded[0].shape == (240, 320, 3) and np.abs(decoded[1].astype(int) - fr[1].astype(int)).mean() < 3
     assert np.array_equal(stacker.ecc_match_files(jpaths, ecc), stacker.ecc_match(decoded, ecc))

@@ -143,43 +143,31 @@ def test_keypoint_1080p_oracle_and_ground_truth(stacker):
     assert d1 == 0 and torch.equal(out, out1)
 
 
-def _jpeg_roundtrip(frames_u8):
-    """JPEG-encode/decode (quality 90) with the Pillow of the image's conda interpreter, if there is one: the reference's
-    inputs are camera JPEGs (BASELINE configs[0]); returns None where that interpreter is absent."""
-    import os
-    import subprocess
-    import tempfile
-    py = "/opt/conda/bin/python3.9"
-    if not os.path.exists(py):
-        return None
-    with tempfile.TemporaryDirectory() as d:
-        src, dst = os.path.join(d, "in.npy"), os.path.join(d, "out.npy")
-        np.save(src, frames_u8)
-        code = ("import io, sys, numpy as np\nfrom PIL import Image\na = np.load(sys.argv[1])\nout = []\n"
-                "for f in a:\n    b = io.BytesIO(); Image.fromarray(f[..., ::-1]).save(b, format='JPEG', quality=90)\n"
-                "    out.append(np.asarray(Image.open(io.BytesIO(b.getvalue())))[..., ::-1])\n"
-                "np.save(sys.argv[2], np.stack(out))\n")
-        r = subprocess.run([py, "-c", code, src, dst], capture_output=True, timeout=120)
-        if r.returncode != 0 or not os.path.exists(dst):
-            return None
-        return np.ascontiguousarray(np.load(dst))
+def _jpeg_roundtrip(stacker, tmp_path, write_jpeg, frames_u8):
+    """The frames as baseline JPEG files (quality 90, 4:2:0), read back by the engine's imread (libjpeg-turbo, the decoder
+    of OpenCV's imread): the reference's inputs are camera JPEGs (BASELINE configs[0])."""
+    out = []
+    for i, f in enumerate(frames_u8):
+        p = tmp_path / ("f%02d.jpg" % i)
+        write_jpeg(p, f, quality=90, subsampling="420")
+        out.append(stacker.imread(p))
+    return np.ascontiguousarray(np.stack(out))
 
 
-def test_config0_nine_800x600_frames_keypoint_match(stacker):
+def test_config0_nine_800x600_frames_keypoint_match(stacker, tmp_path, write_jpeg):
     # BASELINE configs[0]: the image_stacking_py set (9 JPEGs of about 800x600) is not in the container; SURVEY 8d
-    # substitutes 9 synthetic frames of that size, JPEG round-tripped where a Pillow is available
+    # substitutes 9 synthetic frames of that size, JPEG round-tripped
     frames, G = synth.make_stack(9, 800, 600)
     fr = frames.numpy()
-    jp = _jpeg_roundtrip(fr)
-    if jp is not None:
-        assert jp.shape == fr.shape and np.abs(jp.astype(int) - fr.astype(int)).mean() < 6    # JPEG noise, same content
-        fr = jp
+    jp = _jpeg_roundtrip(stacker, tmp_path, write_jpeg, fr)
+    assert jp.shape == fr.shape and np.abs(jp.astype(int) - fr.astype(int)).mean() < 6        # JPEG noise, same content
+    fr = jp
     dropped, out, stats = stacker.keypoint_match(list(fr), KP, return_stats=True)
     d_o, ref, Hs, status = oracle.keypoint_match(list(fr), details=True)
     assert dropped == d_o == 0
     for i in range(1, 9):
         assert np.allclose(stats[i]["warp"], Hs[i], rtol=H_RTOL, atol=1e-9)
-        assert synth.corner_error(stats[i]["warp"], G[i], 800, 600) <= (1.5 if jp is not None else 1.0)
+        assert synth.corner_error(stats[i]["warp"], G[i], 800, 600) <= 1.5
     assert_stack_close(out, ref, bulk=9e-6)                        # <= 1e-6 per folded frame
     e_out, e_stats = stacker.ecc_match(list(fr), ECC, return_stats=True)
     e_ref, warps, iters = oracle.ecc_match(list(fr), max_count=5000, epsilon=1e-5, gauss_filt_size=5)

@@ -6,7 +6,7 @@ libs=$1; shift
 for r in 1 2; do
   for l in $libs; do
     if [ "$l" = "default" ]; then unset STACKER_AMD_LIB; else export STACKER_AMD_LIB=$GRAFT_REPO_ROOT/libstacker_rs_amd/ab/lib$l.so; fi
-    python3 bench.py --no-cpu-baseline --host-fed-steps 0 "$@" 2>/dev/null | python3 -c "
+    python3 bench.py --full --no-cpu-baseline --host-fed-steps 0 "$@" 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d.get('roofline', {})

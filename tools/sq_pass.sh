@@ -2,7 +2,7 @@
 # Run on the GPU box: tools/sq_pass.sh <tag> [bench args...] — one rocprofv3 pass with the SQ issue / stall counters and a
 # kernel trace of the same command, summarised per kernel (tools/pmc_summary.py).
 tag=${1:-sq}; shift
-args="--steps 2 --warmup 1 --no-cpu-baseline --host-fed-steps 0 --profile-launches 0 $*"
+args="--full --steps 2 --warmup 1 --no-cpu-baseline --host-fed-steps 0 --profile-launches 0 $*"
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
