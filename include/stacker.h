@@ -267,6 +267,44 @@ stk_status stk_keypoint_match_shard(stk_ctx* ctx, const stk_frames* frames,
 stk_status stk_finalize_mean(stk_ctx* ctx, const stk_image_f32* sum, int64_t n_frames,
                              stk_image_f32* out);
 
+/* ---- sigma-clipped stacking: an EXTENSION beyond the reference ---------------------------------------
+ * Kappa-sigma rejection over the same samples the mean adds: per pixel and channel the samples s_i are the warped,
+ * converted frames in fold order (frame 0 through the identity, then the kept frames in ascending index) with the fold's
+ * own warp, border and alpha. Everything is f32, each operation rounded on its own (`/` and sqrt correctly rounded):
+ *   start:  c = the plain mean ((sum of s_i in order) * (float)(1.0 / N)), L = -inf, U = +inf
+ *   passes t = 1 .. iterations + 1, each over the samples in order:
+ *           k = 0, a = 0, b = 0;  for each s: d = s - c; if (L <= s && s <= U) { k += 1; a = a + d; b = b + d*d; }
+ *           last pass: out = k > 0 ? c + a / (float)k : c; counts = k
+ *           otherwise, if k >= 3: ma = a / k; m = c + ma; v = b / k - ma*ma; sigma = sqrt(max(v, 0));
+ *                                 L = max(L, m - kappa_low sigma); U = min(U, m + kappa_high sigma); c = m
+ *                     (k < 3: c, L and U stay)
+ * `counts` (optional) receives k of the last pass: width * height * channels int32 in the location of `out`. `out` must
+ * be tightly packed. stk_timing.finalize_ms of these calls is the device time of the clip passes (warp_ms etc. are the
+ * plain call's). A multi-device context runs them on its first device (like the mixed-size route): the plain mean they
+ * start from is then the single-device one. */
+typedef struct {
+    float   kappa_low, kappa_high;  /* rejection below c - kappa_low sigma / above c + kappa_high sigma: > 0, finite */
+    int32_t iterations;             /* clipping passes T before the final pass, 1 .. 16 */
+    int32_t reserved;               /* 0 */
+} stk_clip_params;
+
+/* ecc_match with the clipped combine: stats, warps, iterations and errors are those of stk_ecc_match on the same input
+ * (every frame is a sample: the reference aborts the stack on any ECC failure). */
+stk_status stk_ecc_match_clipped(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                 const stk_clip_params* clip, stk_image_f32* out, int32_t* counts_or_null,
+                                 stk_frame_stats* stats_or_null);
+/* keypoint_match with the clipped combine: stats and `dropped` as stk_keypoint_match; the samples are frame 0 and the
+ * frames with status 0, folded with the params' border mode and value. */
+stk_status stk_keypoint_match_clipped(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                      float scale_down_width, const stk_clip_params* clip, stk_image_f32* out, int32_t* dropped,
+                                      int32_t* counts_or_null, stk_frame_stats* stats_or_null);
+/* The combine alone, for a caller holding its own warps (e.g. the stats of stk_hybrid_match): M is n x 9 doubles, the
+ * forward matrices exactly as stk_warp_accumulate takes them, frame 0's entry included; include_or_null: n flags (non-zero
+ * = a sample) or NULL = every frame. border_mode as stk_warp_accumulate (CONSTANT, REPLICATE, REFLECT, WRAP, REFLECT_101). */
+stk_status stk_clip_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                          int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                          const stk_clip_params* clip, stk_image_f32* out, int32_t* counts_or_null);
+
 /* ---- stage-level entry points (parity tests bind these) ------------------ */
 /* cvt_color(BGR2GRAY) on the integer image, utils.rs:136-142. out: w*h of the input depth
  * (u8 / u16 / f32), tightly packed, same location as the frame. */

@@ -47,6 +47,10 @@ class FrameStats(C.Structure):
                 ("reserved", C.c_int32), ("warp", C.c_double * 9)]
 
 
+class ClipParams(C.Structure):
+    _fields_ = [("kappa_low", C.c_float), ("kappa_high", C.c_float), ("iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("prep_ms", C.c_double), ("align_ms", C.c_double), ("warp_ms", C.c_double),
                 ("finalize_ms", C.c_double), ("ecc_iter_launches", C.c_int64),
@@ -82,6 +86,13 @@ SIGNATURES = {
                                             C.c_int32, C.POINTER(ImageF32), C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32), C.POINTER(FrameStats)]),
     "stk_finalize_mean": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_int64, C.POINTER(ImageF32)]),
+    "stk_ecc_match_clipped": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float, C.POINTER(ClipParams),
+                                         C.POINTER(ImageF32), C.c_void_p, C.POINTER(FrameStats)]),
+    "stk_keypoint_match_clipped": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                              C.POINTER(ClipParams), C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p,
+                                              C.POINTER(FrameStats)]),
+    "stk_clip_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_double, C.POINTER(ClipParams), C.POINTER(ImageF32), C.c_void_p]),
     "stk_grey": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p]),
     "stk_convert_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_double, C.c_void_p]),
     "stk_hybrid_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.POINTER(EccParams),

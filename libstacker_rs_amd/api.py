@@ -103,6 +103,18 @@ class EccMatchParameters:         # lib.rs:611-623 (no Default in the reference)
         return typ, (self.max_count or 0), (self.epsilon or 0.0)
 
 
+@dataclass
+class SigmaClipParameters:        # extension beyond the reference: include/stacker.h, stk_clip_params
+    """Kappa-sigma rejection for the *_clipped combines: samples below c - kappa_low sigma or above c + kappa_high sigma
+    are left out, `iterations` times, before the final mean of the kept samples."""
+    kappa_low: float = 3.0
+    kappa_high: float = 3.0
+    iterations: int = 2
+
+    def _c(self) -> _ffi.ClipParams:
+        return _ffi.ClipParams(float(self.kappa_low), float(self.kappa_high), int(self.iterations), 0)
+
+
 # ---------------------------------------------------------------------------------------------
 def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
@@ -334,6 +346,76 @@ class Stacker:
                                           C.byref(img), C.byref(dropped), stats)
         self._check(st)
         return (dropped.value, out, self._stats_list(stats, m.n)) if return_stats else (dropped.value, out)
+
+    # -- sigma-clipped combines (extension beyond the reference) -----------------------------------------
+    def _counts_image(self, m: _Marshalled):
+        """int32 HxWxC counts placed where the output lives."""
+        if m.location == DEVICE:
+            import torch
+            cnt = torch.empty((m.h, m.w, m.c), dtype=torch.int32, device=m.torch_device)
+            return cnt, C.c_void_p(cnt.data_ptr())
+        cnt = np.empty((m.h, m.w, m.c), np.int32)
+        return cnt, C.c_void_p(cnt.ctypes.data)
+
+    def ecc_match_clipped(self, files, params: EccMatchParameters, clip: Optional["SigmaClipParameters"] = None,
+                          scale_down_width: Optional[float] = None, return_stats: bool = False, return_counts: bool = False):
+        """ecc_match with kappa-sigma rejection over the aligned frames instead of the plain mean (stk_ecc_match_clipped).
+        Returns the image, then the per-pixel counts of kept samples (return_counts) and the stats (return_stats)."""
+        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
+        stats = (_ffi.FrameStats * m.n)()
+        p, cp = params._c(), (clip or SigmaClipParameters())._c()
+        self._check(self._lib.stk_ecc_match_clipped(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                    C.byref(cp), C.byref(img), cptr, stats))
+        res = (out,) + ((cnt,) if return_counts else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return res if len(res) > 1 else out
+
+    def keypoint_match_clipped(self, files, params: KeyPointMatchParameters, clip: Optional["SigmaClipParameters"] = None,
+                               scale_down_width: Optional[float] = None, return_stats: bool = False, return_counts: bool = False):
+        """keypoint_match with kappa-sigma rejection (stk_keypoint_match_clipped): (dropped, image[, counts][, stats])."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p, cp = params._c(), (clip or SigmaClipParameters())._c()
+        self._check(self._lib.stk_keypoint_match_clipped(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                         C.byref(cp), C.byref(img), C.byref(dropped), cptr, stats))
+        return (dropped.value, out) + ((cnt,) if return_counts else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+
+    def clip_stack(self, files, warps, clip: Optional["SigmaClipParameters"] = None, include=None, *, is_affine=False,
+                   border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_counts: bool = False):
+        """The clipped combine alone over caller-held warps (stk_clip_stack): warps[i] is frame i's forward matrix as
+        warp_accumulate takes it (3x3, or 2x3 for affine), frame 0's included; include: per-frame flags or None = all."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Ms = []
+        for w in warps:
+            Md = np.asarray(w, np.float64).reshape(-1)
+            Ms.append(np.concatenate([Md, [0.0, 0.0, 1.0]]) if Md.size == 6 else Md)
+        if len(Ms) != m.n or any(x.size != 9 for x in Ms):
+            raise InvalidParams("one 3x3 (or 2x3) warp per frame expected")
+        Md = np.ascontiguousarray(np.stack(Ms))
+        inc = None if include is None else np.ascontiguousarray(np.asarray(include, np.int32).reshape(-1))
+        if inc is not None and inc.size != m.n:
+            raise InvalidParams("one include flag per frame expected")
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        out, img = self._out_image(m)
+        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
+        cp = (clip or SigmaClipParameters())._c()
+        self._check(self._lib.stk_clip_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                             None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
+                                             int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(cp),
+                                             C.byref(img), cptr))
+        return (out, cnt) if return_counts else out
 
     # -- shard-level (one process per GPU; frames[0] = reference frame) ------------------------------
     def ecc_match_shard(self, files, params: EccMatchParameters, add_reference: bool, sum_out,

@@ -175,6 +175,21 @@ struct WarpArgs {
     int tune;                    // launch shape of the u8 fast path (option "warp_tune")
 };
 
+// One sigma-clipping pass over the fold's frames (kernels_clip.hip; definition: include/stacker.h, stk_clip_params). The
+// c / L / U planes are tightly packed dw x dh x cn f32; each pass reads them once and writes them once (pass `last`: out and
+// counts instead). first: L = -inf, U = +inf without reading the planes.
+struct ClipArgs {
+    float* c;
+    float* L;
+    float* U;
+    size_t plane_stride;         // floats per row of the c / L / U planes and of counts (dw x cn)
+    float* out;                  // last pass: the clipped mean, row stride out_stride floats
+    size_t out_stride;
+    int* counts;                 // last pass: samples kept, tightly packed; null = not wanted
+    float kappa_low, kappa_high;
+    int first, last;
+};
+
 // ---- kernel launchers (defined in the .hip files) -------------------------------------------
 hipError_t launch_grey(const void* bgr, int depth, int w, int h, size_t stride_bytes, void* out, hipStream_t s,
                        int n_frames = 1, size_t src_frame_bytes = 0, size_t out_frame_elems = 0, int cn = 3 /* 3 BGR, 4 BGRA */);
@@ -203,6 +218,8 @@ hipError_t launch_ecc_init(EccSlot* slots, int n_slots, int* tickets, EccQueue* 
                            const float* init_warps /* n_frames*9 or null */, hipStream_t s, int ready0 = -1 /* -1: all */);
 hipError_t launch_ecc_set_ready(EccQueue* queue, int ready, hipStream_t s);
 hipError_t launch_warp_accumulate(const WarpArgs& a, int depth, hipStream_t s);
+// one clipping pass over the frames of `a` (a.acc unused); same kernel choice as launch_warp_accumulate
+hipError_t launch_clip_pass(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
 // the fold's frame table straight from the ECC results, on the device: entry 0 = the reference frame under the identity
 // (if add_reference), then template k under results[k].warp — what the host loop of ecc_shard_impl builds, bit for bit
 hipError_t launch_warp_frames_from_ecc(const EccFrameResult* results, const void* const* src_ptrs /* n_templates + 1, device */,

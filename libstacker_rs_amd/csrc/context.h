@@ -83,6 +83,7 @@ struct stk_ctx {
     unsigned char* files_block = nullptr; size_t files_block_cap = 0; bool files_block_pinned = false;
     // workspace
     DevBuf frames, ref, blur_tmp, templates, slots, queue, results, partials, warpframes, acc, scratch, init_warps, frameptrs;
+    DevBuf clip;                  // sigma clipping (clip.cpp): the c, L and U planes
     stk::KeypointWorkspace* kp = nullptr;
     stk::geom::HgWorkspace* hg = nullptr;   // findHomography batch workspace (homography.cpp)
     stk::HostPool* host_pool = nullptr;
@@ -124,7 +125,14 @@ size_t image_stride_floats(const stk_image_f32* im);
 void timing_begin(stk_ctx* ctx);
 float ev_ms(hipEvent_t a, hipEvent_t b);
 
-// shared internals of the entry points (stacker.cpp / keypoint.cpp / hybrid.cpp)
+// shared internals of the entry points (stacker.cpp / keypoint.cpp / hybrid.cpp / clip.cpp)
+// stk_ecc_match / stk_keypoint_match on the context's own device: what they run on a plain context
+stk_status ecc_match_single(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                            stk_image_f32* out, stk_frame_stats* stats);
+stk_status keypoint_match_single(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,
+                                 stk_image_f32* out, int32_t* dropped, stk_frame_stats* stats);
+// the frame table of a fold into ctx->warpframes (flags for a w x h destination; asynchronous: `wf` must outlive the copy)
+stk_status warp_table_upload(stk_ctx* ctx, std::vector<WarpFrame>& wf, size_t src_row_bytes, int w, int h, int is_affine);
 stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
                           int32_t add_reference, stk_image_f32* sum, int32_t* n_added, stk_frame_stats* stats,
                           const float* seeds, double alpha, bool allow16);

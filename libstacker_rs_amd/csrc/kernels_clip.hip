@@ -1,0 +1,136 @@
+// kernels_clip.hip — kappa-sigma clipping over the aligned frames (stk_clip_stack and the *_clipped entry points).
+// One pass is one more fold of the same frames: the fold kernels of warp_body.h in their clip mode, the sample of every
+// frame computed by the very instructions the mean fold adds. Per pixel and channel a pass keeps the moments of the
+// samples inside [L, U] about the previous centre c (k, a = sum d, b = sum d^2 with d = s - c), and its epilogue turns them
+// into the next (c, L, U) — or, on the last pass, into the clipped mean and the count of kept samples. Definition (bit for
+// bit, f32, no contraction: the Makefile's -ffp-contract=off; `/` and sqrt are the correctly rounded forms):
+//     pass:      d = s - c; if (L <= s && s <= U) { k += 1; a = a + d; b = b + d*d; }
+//     update:    if (k >= 3) { ma = a / k; m = c + ma; v = b / k - ma*ma; sigma = sqrt(max(v, 0));
+//                              L = max(L, m - kappa_low sigma); U = min(U, m + kappa_high sigma); c = m; }
+//     last pass: out = k > 0 ? c + a / k : c; counts = k
+// The shifted moments keep the variance accurate (the samples sit close to c). Cost over the mean fold's per-sample work:
+// a subtract, a multiply, two adds, two compares and the selects — the c / L / U planes are read once and written once per
+// pass, like the accumulator.
+#include "warp_body.h"
+
+namespace stk {
+
+__device__ __forceinline__ bool clip_in(float s, float L, float U) { return (L <= s) & (s <= U); }
+
+// epilogue of one channel: plane index p, output index o
+__device__ __forceinline__ void clip_end(const ClipArgs& ca, size_t p, size_t o, float c, float L, float U, int k, float a, float b) {
+    if (ca.last) {
+        ca.out[o] = k > 0 ? c + a / (float)k : c;
+        if (ca.counts) ca.counts[p] = k;
+        return;
+    }
+    if (k >= 3) {
+        const float kf = (float)k;
+        const float ma = a / kf;
+        const float m = c + ma;
+        const float v = b / kf - ma * ma;
+        const float sigma = __builtin_sqrtf(__builtin_fmaxf(v, 0.0f));
+        L = __builtin_fmaxf(L, m - ca.kappa_low * sigma);
+        U = __builtin_fminf(U, m + ca.kappa_high * sigma);
+        c = m;
+    }
+    ca.c[p] = c; ca.L[p] = L; ca.U[p] = U;
+}
+
+// generic kernel's state: CN channels, indexed by the (unrolled) channel loop
+template <int CN>
+struct ClipGeneric {
+    float c[CN], L[CN], U[CN], a[CN], b[CN];
+    int k[CN];
+    size_t p;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+        p = (size_t)y * ca.plane_stride + (size_t)x * CN;
+#pragma unroll
+        for (int i = 0; i < CN; i++) {
+            c[i] = ca.c[p + i];
+            L[i] = ca.first ? -__builtin_inff() : ca.L[p + i];
+            U[i] = ca.first ? __builtin_inff() : ca.U[p + i];
+            a[i] = 0.f; b[i] = 0.f; k[i] = 0;
+        }
+    }
+    __device__ __forceinline__ void add(int i, float s) {
+        const float d = s - c[i];
+        const bool in = clip_in(s, L[i], U[i]);
+        k[i] += in ? 1 : 0;
+        a[i] = in ? a[i] + d : a[i];
+        b[i] = in ? b[i] + d * d : b[i];
+    }
+    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
+        const size_t o = (size_t)y * ca.out_stride + (size_t)x * CN;
+#pragma unroll
+        for (int i = 0; i < CN; i++) clip_end(ca, p + i, o + i, c[i], L[i], U[i], k[i], a[i], b[i]);
+    }
+};
+
+// u8 BGR fast kernel's state: (B, G) as register pairs (v_pk_add / v_pk_mul for the moments), R apart
+struct ClipU8C3 {
+    f32x2 c01, L01, U01, a01, b01;
+    float c2, L2, U2, a2, b2;
+    int k0, k1, k2;
+    size_t p;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+        p = (size_t)y * ca.plane_stride + (size_t)x * 3;
+        c01 = f32x2{ca.c[p], ca.c[p + 1]}; c2 = ca.c[p + 2];
+        if (ca.first) {
+            L01 = f32x2{-__builtin_inff(), -__builtin_inff()}; L2 = -__builtin_inff();
+            U01 = f32x2{__builtin_inff(), __builtin_inff()}; U2 = __builtin_inff();
+        } else {
+            L01 = f32x2{ca.L[p], ca.L[p + 1]}; L2 = ca.L[p + 2];
+            U01 = f32x2{ca.U[p], ca.U[p + 1]}; U2 = ca.U[p + 2];
+        }
+        a01 = f32x2{0.f, 0.f}; b01 = f32x2{0.f, 0.f}; a2 = 0.f; b2 = 0.f;
+        k0 = k1 = k2 = 0;
+    }
+    __device__ __forceinline__ void add2(f32x2 s01, float s2) {
+        const f32x2 d = s01 - c01;
+        const f32x2 an = a01 + d, bn = b01 + d * d;
+        const bool i0 = clip_in(s01.x, L01.x, U01.x), i1 = clip_in(s01.y, L01.y, U01.y);
+        k0 += i0 ? 1 : 0; k1 += i1 ? 1 : 0;
+        a01.x = i0 ? an.x : a01.x; a01.y = i1 ? an.y : a01.y;
+        b01.x = i0 ? bn.x : b01.x; b01.y = i1 ? bn.y : b01.y;
+        const float d2 = s2 - c2;
+        const bool i2 = clip_in(s2, L2, U2);
+        k2 += i2 ? 1 : 0;
+        a2 = i2 ? a2 + d2 : a2;
+        b2 = i2 ? b2 + d2 * d2 : b2;
+    }
+    __device__ __forceinline__ void add3(float s0, float s1, float s2) { add2(f32x2{s0, s1}, s2); }
+    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
+        const size_t o = (size_t)y * ca.out_stride + (size_t)x * 3;
+        clip_end(ca, p, o, c01.x, L01.x, U01.x, k0, a01.x, b01.x);
+        clip_end(ca, p + 1, o + 1, c01.y, L01.y, U01.y, k1, a01.y, b01.y);
+        clip_end(ca, p + 2, o + 2, c2, L2, U2, k2, a2, b2);
+    }
+};
+
+hipError_t launch_clip_pass(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
+    if (a.n_frames <= 0) return hipErrorInvalidValue;
+    if (warp_u8c3_applies(a, depth)) {
+        // the mean fold's default launch shape (one wave per row of 64 pixels, four frames in flight)
+        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
+        if (a.is_affine) warp_accumulate_u8c3_kernel<true, 1, 4, true, ClipU8C3><<<g, 256, 0, s>>>(a, c);
+        else warp_accumulate_u8c3_kernel<false, 1, 4, true, ClipU8C3><<<g, 256, 0, s>>>(a, c);
+        return hipGetLastError();
+    }
+    const dim3 grid((a.dw + 63) / 64, (a.dh + 3) / 4);
+#define STK_CLIP_CASE(T, CN) warp_accumulate_kernel<T, CN, true, ClipGeneric<CN>><<<grid, 256, 0, s>>>(a, c)
+    if (depth == 8 && a.cn == 3) STK_CLIP_CASE(uint8_t, 3);
+    else if (depth == 8 && a.cn == 1) STK_CLIP_CASE(uint8_t, 1);
+    else if (depth == 8 && a.cn == 4) STK_CLIP_CASE(uint8_t, 4);
+    else if (depth == 16 && a.cn == 3) STK_CLIP_CASE(uint16_t, 3);
+    else if (depth == 16 && a.cn == 1) STK_CLIP_CASE(uint16_t, 1);
+    else if (depth == 16 && a.cn == 4) STK_CLIP_CASE(uint16_t, 4);
+    else if (depth == 32 && a.cn == 3) STK_CLIP_CASE(float, 3);
+    else if (depth == 32 && a.cn == 1) STK_CLIP_CASE(float, 1);
+    else if (depth == 32 && a.cn == 4) STK_CLIP_CASE(float, 4);
+    else return hipErrorInvalidValue;
+#undef STK_CLIP_CASE
+    return hipGetLastError();
+}
+
+}  // namespace stk

@@ -822,6 +822,32 @@ stk_status keypoint_align_impl(stk_ctx* ctx, const stk_frames* frames, const stk
     return STK_OK;
 }
 
+// stk_keypoint_match on this context's own device (a multi-device context: its first device, alone)
+stk_status keypoint_match_single(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,
+                                 stk_image_f32* out, int32_t* dropped, stk_frame_stats* stats) {
+    stk_status st = check_frames(ctx, frames, true);
+    if (st) return st;
+    if ((st = image_check(ctx, out, frames->width, frames->height, frames->channels))) return st;
+    if (out->row_stride_bytes) return fail(ctx, STK_INVALID_PARAMS, "output must be tightly packed");
+    (void)hipSetDevice(ctx->device);
+    const size_t nel = (size_t)frames->width * frames->height * frames->channels;
+    stk_image_f32 sum = *out;
+    if (out->location != STK_DEVICE) {
+        HIP_TRY(ctx->acc.reserve(nel * sizeof(float)));
+        sum.data = ctx->acc.as<float>(); sum.location = STK_DEVICE;
+    }
+    int32_t added = 0, ndrop = 0;
+    if ((st = stk_keypoint_match_shard(ctx, frames, params, scale_down_width, 1, &sum, &added, &ndrop, stats))) return st;
+    if (dropped) *dropped = ndrop;
+    if (added <= 0)   // lib.rs:324
+        return fail(ctx, STK_INVALID_PARAMS, "All images discarded: try modifying KeyPointMatchParameters::match_distance_threshold");
+    const stk_timing keep = ctx->timing;
+    st = stk_finalize_mean(ctx, &sum, frames->n - ndrop, out);   // lib.rs:342: img / (n - dropped)
+    const double fin = ctx->timing.finalize_ms;
+    ctx->timing = keep; ctx->timing.finalize_ms = fin;
+    return st;
+}
+
 extern "C" {
 
 stk_status stk_keypoint_match_shard(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
@@ -903,27 +929,7 @@ stk_status stk_keypoint_match_shard(stk_ctx* ctx, const stk_frames* frames, cons
 stk_status stk_keypoint_match(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
                               float scale_down_width, stk_image_f32* out, int32_t* dropped, stk_frame_stats* stats) {
     if (ctx && ctx->multi) return multi_match(ctx, 1, frames, params, nullptr, scale_down_width, out, dropped, stats);
-    stk_status st = check_frames(ctx, frames, true);
-    if (st) return st;
-    if ((st = image_check(ctx, out, frames->width, frames->height, frames->channels))) return st;
-    if (out->row_stride_bytes) return fail(ctx, STK_INVALID_PARAMS, "output must be tightly packed");
-    (void)hipSetDevice(ctx->device);
-    const size_t nel = (size_t)frames->width * frames->height * frames->channels;
-    stk_image_f32 sum = *out;
-    if (out->location != STK_DEVICE) {
-        HIP_TRY(ctx->acc.reserve(nel * sizeof(float)));
-        sum.data = ctx->acc.as<float>(); sum.location = STK_DEVICE;
-    }
-    int32_t added = 0, ndrop = 0;
-    if ((st = stk_keypoint_match_shard(ctx, frames, params, scale_down_width, 1, &sum, &added, &ndrop, stats))) return st;
-    if (dropped) *dropped = ndrop;
-    if (added <= 0)   // lib.rs:324
-        return fail(ctx, STK_INVALID_PARAMS, "All images discarded: try modifying KeyPointMatchParameters::match_distance_threshold");
-    const stk_timing keep = ctx->timing;
-    st = stk_finalize_mean(ctx, &sum, frames->n - ndrop, out);   // lib.rs:342: img / (n - dropped)
-    const double fin = ctx->timing.finalize_ms;
-    ctx->timing = keep; ctx->timing.finalize_ms = fin;
-    return st;
+    return keypoint_match_single(ctx, frames, params, scale_down_width, out, dropped, stats);
 }
 
 }  // extern "C"

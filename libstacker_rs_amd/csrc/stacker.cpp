@@ -92,7 +92,7 @@ void stk_destroy(stk_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (DevBuf* b : {&ctx->frames, &ctx->ref, &ctx->blur_tmp, &ctx->templates, &ctx->slots, &ctx->queue, &ctx->results,
-                      &ctx->partials, &ctx->warpframes, &ctx->acc, &ctx->scratch, &ctx->init_warps, &ctx->frameptrs})
+                      &ctx->partials, &ctx->warpframes, &ctx->acc, &ctx->scratch, &ctx->init_warps, &ctx->frameptrs, &ctx->clip})
         b->release();
     keypoint_workspace_destroy(ctx->kp);
     geom::hg_workspace_destroy(ctx->hg);
@@ -445,15 +445,21 @@ stk_status warp_fold(stk_ctx* ctx, std::vector<WarpFrame>& wf, int depth, int w,
                             size_t src_row_bytes, double alpha, int border_mode, const double* border_value,
                             int is_affine, float* acc, size_t acc_stride_floats, int accumulate, int dw, int dh) {
     if (wf.empty()) return STK_OK;
-    // per frame, once: the flags the fast kernels branch on (common.h: warp_frame_flags; the rectangle is the DESTINATION's)
-    for (WarpFrame& f : wf) f.flags = warp_frame_flags(f.src, f.M, src_row_bytes, dw > 0 ? dw : w, dh > 0 ? dh : h, is_affine);
-    HIP_TRY(ctx->warpframes.reserve(sizeof(WarpFrame) * wf.size()));
-    HIP_TRY(hipMemcpyAsync(ctx->warpframes.p, wf.data(), sizeof(WarpFrame) * wf.size(), hipMemcpyHostToDevice, ctx->stream));
-    stk_status st = warp_fold_enqueue(ctx, (int)wf.size(), depth, w, h, cn, src_row_bytes, alpha, border_mode, border_value, is_affine,
+    stk_status st = warp_table_upload(ctx, wf, src_row_bytes, dw > 0 ? dw : w, dh > 0 ? dh : h, is_affine);
+    if (st) return st;
+    st = warp_fold_enqueue(ctx, (int)wf.size(), depth, w, h, cn, src_row_bytes, alpha, border_mode, border_value, is_affine,
                                       acc, acc_stride_floats, accumulate, 0, dw, dh);
     if (st) return st;
     // the host vector may die before the copy above ran if the caller does not synchronise
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return STK_OK;
+}
+
+stk_status warp_table_upload(stk_ctx* ctx, std::vector<WarpFrame>& wf, size_t src_row_bytes, int w, int h, int is_affine) {
+    // per frame, once: the flags the fast kernels branch on (common.h: warp_frame_flags; the rectangle is the DESTINATION's)
+    for (WarpFrame& f : wf) f.flags = warp_frame_flags(f.src, f.M, src_row_bytes, w, h, is_affine);
+    HIP_TRY(ctx->warpframes.reserve(sizeof(WarpFrame) * wf.size()));
+    HIP_TRY(hipMemcpyAsync(ctx->warpframes.p, wf.data(), sizeof(WarpFrame) * wf.size(), hipMemcpyHostToDevice, ctx->stream));
     return STK_OK;
 }
 
@@ -739,6 +745,29 @@ stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_
     return STK_OK;
 }
 
+// stk_ecc_match on this context's own device (a multi-device context: its first device, alone)
+stk_status ecc_match_single(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                            stk_image_f32* out, stk_frame_stats* stats) {
+    stk_status st = check_frames(ctx, frames, true);
+    if (st) return st;
+    if ((st = image_check(ctx, out, frames->width, frames->height, frames->channels))) return st;
+    if (out->row_stride_bytes) return fail(ctx, STK_INVALID_PARAMS, "output must be tightly packed");
+    (void)hipSetDevice(ctx->device);
+    const size_t nel = (size_t)frames->width * frames->height * frames->channels;
+    stk_image_f32 sum = *out;
+    if (out->location != STK_DEVICE) {
+        HIP_TRY(ctx->acc.reserve(nel * sizeof(float)));
+        sum.data = ctx->acc.as<float>(); sum.location = STK_DEVICE;
+    }
+    int32_t added = 0;
+    if ((st = stk_ecc_match_shard(ctx, frames, params, scale_down_width, 1, &sum, &added, stats))) return st;
+    const stk_timing keep = ctx->timing;
+    st = stk_finalize_mean(ctx, &sum, frames->n, out);     // lib.rs:836-839: divide by files_vec.len()
+    const double fin = ctx->timing.finalize_ms;
+    ctx->timing = keep; ctx->timing.finalize_ms = fin;
+    return st;
+}
+
 extern "C" {
 
 stk_status stk_ecc_match_shard(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
@@ -773,24 +802,7 @@ stk_status stk_finalize_mean(stk_ctx* ctx, const stk_image_f32* sum, int64_t n_f
 stk_status stk_ecc_match(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
                          float scale_down_width, stk_image_f32* out, stk_frame_stats* stats) {
     if (ctx && ctx->multi) return multi_match(ctx, 0, frames, nullptr, params, scale_down_width, out, nullptr, stats);
-    stk_status st = check_frames(ctx, frames, true);
-    if (st) return st;
-    if ((st = image_check(ctx, out, frames->width, frames->height, frames->channels))) return st;
-    if (out->row_stride_bytes) return fail(ctx, STK_INVALID_PARAMS, "output must be tightly packed");
-    (void)hipSetDevice(ctx->device);
-    const size_t nel = (size_t)frames->width * frames->height * frames->channels;
-    stk_image_f32 sum = *out;
-    if (out->location != STK_DEVICE) {
-        HIP_TRY(ctx->acc.reserve(nel * sizeof(float)));
-        sum.data = ctx->acc.as<float>(); sum.location = STK_DEVICE;
-    }
-    int32_t added = 0;
-    if ((st = stk_ecc_match_shard(ctx, frames, params, scale_down_width, 1, &sum, &added, stats))) return st;
-    const stk_timing keep = ctx->timing;
-    st = stk_finalize_mean(ctx, &sum, frames->n, out);     // lib.rs:836-839: divide by files_vec.len()
-    const double fin = ctx->timing.finalize_ms;
-    ctx->timing = keep; ctx->timing.finalize_ms = fin;
-    return st;
+    return ecc_match_single(ctx, frames, params, scale_down_width, out, stats);
 }
 
 // ---- stage-level entry points ------------------------------------------------------------------
