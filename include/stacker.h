@@ -216,7 +216,9 @@ void        stk_host_free(void* p);
  *                        prepared on a second stream while the first frames already iterate; 0: all templates first.
  *                        Same bits either way (stk_timing.prep_ms then covers the reference frame only)
  *   "upload_batch"       host-fed stacks: frames per host -> HBM batch (default 8); a batch is the unit the ECC queue
- *                        and the batched ORB wait for */
+ *                        and the batched ORB wait for
+ *   "quantile_band_rows" quantile combines: rows per band of samples. 0 (default): as many as fit a 4 GiB sample buffer;
+ *                        n > 0: at most n. Same bits either way */
 stk_status  stk_set_option(stk_ctx* ctx, const char* name, int64_t value);
 const char* stk_version(void);
 
@@ -304,6 +306,41 @@ stk_status stk_keypoint_match_clipped(stk_ctx* ctx, const stk_frames* frames, co
 stk_status stk_clip_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
                           int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
                           const stk_clip_params* clip, stk_image_f32* out, int32_t* counts_or_null);
+
+/* ---- median and quantile stacking: an EXTENSION beyond the reference ---------------------------------
+ * An order statistic over the same samples the mean adds: per pixel and channel the samples s_1 .. s_N are the warped,
+ * converted frames in fold order (frame 0 through the identity, then the kept frames in ascending index; in
+ * stk_quantile_stack the included frames in index order under the caller's matrices) with the fold's own warp, border
+ * mode and value, alpha and warp_subpixel_bits. Border-constant samples at frame edges count, as in the mean: N is the
+ * same for every pixel. With s_(k) the k-th smallest sample (k from 0), in f32, each operation rounded on its own:
+ *   vi = (float)(N - 1) * quantile;  j = floor(vi);  g = vi - j;
+ *   lo = s_(j);  hi = s_(min(j + 1, N - 1));  d = hi - lo;
+ *   out = g == 0 ? lo : (g >= 0.5 ? hi - d * (1 - g) : lo + d * g)
+ * Apart from the g == 0 rule this is numpy.quantile(samples, quantile, axis=0) with method 'linear', bit for bit (an f32
+ * stack, a Python-float quantile). The rule is deliberate: numpy gives NaN where lo is finite and hi is +-inf, i.e. at the
+ * very pixels (one inf hot pixel) that a median is meant to clean up. Any NaN sample makes the output there NaN. -0 and +0
+ * are equal: either sign may come back. The median is quantile = 0.5; at even N it can differ from numpy.median by 1 ulp
+ * (numpy.median takes (lo + hi) / 2). N is at most 4096 (STK_NOT_IMPLEMENTED beyond).
+ * `out` must be tightly packed. stk_timing.finalize_ms of these calls is the combine's device time (warp_ms etc. are the
+ * plain call's). The samples go through a device buffer band by band (rows [y0, y0 + R) of all N frames at a time; option
+ * "quantile_band_rows"). A multi-device context runs these calls on its first device. */
+typedef struct {
+    float   quantile;               /* 0 <= quantile <= 1: 0 = min, 0.5 = median, 1 = max */
+    int32_t reserved;               /* 0 */
+} stk_quantile_params;
+
+/* ecc_match with the quantile combine: stats, warps, iterations and errors are those of stk_ecc_match on the same input. */
+stk_status stk_ecc_match_quantile(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                  const stk_quantile_params* quantile, stk_image_f32* out, stk_frame_stats* stats_or_null);
+/* keypoint_match with the quantile combine: stats and `dropped` as stk_keypoint_match; the samples are frame 0 and the
+ * frames with status 0, folded with the params' border mode and value. */
+stk_status stk_keypoint_match_quantile(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                       float scale_down_width, const stk_quantile_params* quantile, stk_image_f32* out,
+                                       int32_t* dropped, stk_frame_stats* stats_or_null);
+/* The combine alone over caller-held warps, with the arguments of stk_clip_stack. */
+stk_status stk_quantile_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                              int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                              const stk_quantile_params* quantile, stk_image_f32* out);
 
 /* ---- stage-level entry points (parity tests bind these) ------------------ */
 /* cvt_color(BGR2GRAY) on the integer image, utils.rs:136-142. out: w*h of the input depth

@@ -51,6 +51,10 @@ class ClipParams(C.Structure):
     _fields_ = [("kappa_low", C.c_float), ("kappa_high", C.c_float), ("iterations", C.c_int32), ("reserved", C.c_int32)]
 
 
+class QuantileParams(C.Structure):
+    _fields_ = [("quantile", C.c_float), ("reserved", C.c_int32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("prep_ms", C.c_double), ("align_ms", C.c_double), ("warp_ms", C.c_double),
                 ("finalize_ms", C.c_double), ("ecc_iter_launches", C.c_int64),
@@ -93,6 +97,13 @@ SIGNATURES = {
                                               C.POINTER(FrameStats)]),
     "stk_clip_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_double, C.POINTER(ClipParams), C.POINTER(ImageF32), C.c_void_p]),
+    "stk_ecc_match_quantile": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float, C.POINTER(QuantileParams),
+                                          C.POINTER(ImageF32), C.POINTER(FrameStats)]),
+    "stk_keypoint_match_quantile": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                               C.POINTER(QuantileParams), C.POINTER(ImageF32), C.POINTER(C.c_int32),
+                                               C.POINTER(FrameStats)]),
+    "stk_quantile_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_double, C.POINTER(QuantileParams), C.POINTER(ImageF32)]),
     "stk_grey": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p]),
     "stk_convert_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_double, C.c_void_p]),
     "stk_hybrid_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.POINTER(EccParams),

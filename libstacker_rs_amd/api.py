@@ -115,6 +115,25 @@ class SigmaClipParameters:        # extension beyond the reference: include/stac
         return _ffi.ClipParams(float(self.kappa_low), float(self.kappa_high), int(self.iterations), 0)
 
 
+@dataclass
+class QuantileParameters:         # extension beyond the reference: include/stacker.h, stk_quantile_params
+    """The order statistic for the *_quantile combines: 0 = min, 0.5 = median, 1 = max, linear interpolation between
+    the two nearest samples otherwise (numpy.quantile's default method)."""
+    quantile: float = 0.5
+
+    def _c(self) -> _ffi.QuantileParams:
+        return _ffi.QuantileParams(float(self.quantile), 0)
+
+
+def _quantile_c(q) -> _ffi.QuantileParams:
+    """QuantileParameters, a bare float, or None (the median)."""
+    if q is None:
+        q = QuantileParameters()
+    elif not isinstance(q, QuantileParameters):
+        q = QuantileParameters(float(q))
+    return q._c()
+
+
 # ---------------------------------------------------------------------------------------------
 def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
@@ -416,6 +435,62 @@ class Stacker:
                                              int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(cp),
                                              C.byref(img), cptr))
         return (out, cnt) if return_counts else out
+
+    # -- median / quantile combines (extension beyond the reference) -----------------------------------
+    def ecc_match_quantile(self, files, params: EccMatchParameters, quantile=None, scale_down_width: Optional[float] = None,
+                           return_stats: bool = False):
+        """ecc_match with a per-pixel quantile of the aligned frames instead of the plain mean (stk_ecc_match_quantile).
+        quantile: QuantileParameters or a float in [0, 1]; None = the median."""
+        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        stats = (_ffi.FrameStats * m.n)()
+        p, qp = params._c(), _quantile_c(quantile)
+        self._check(self._lib.stk_ecc_match_quantile(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                     C.byref(qp), C.byref(img), stats))
+        return (out, self._stats_list(stats, m.n)) if return_stats else out
+
+    def keypoint_match_quantile(self, files, params: KeyPointMatchParameters, quantile=None,
+                                scale_down_width: Optional[float] = None, return_stats: bool = False):
+        """keypoint_match with the quantile combine (stk_keypoint_match_quantile): (dropped, image[, stats])."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p, qp = params._c(), _quantile_c(quantile)
+        self._check(self._lib.stk_keypoint_match_quantile(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                          C.byref(qp), C.byref(img), C.byref(dropped), stats))
+        return (dropped.value, out, self._stats_list(stats, m.n)) if return_stats else (dropped.value, out)
+
+    def quantile_stack(self, files, warps, quantile=None, include=None, *, is_affine=False, border_mode=BORDER_CONSTANT,
+                       border_value=(0, 0, 0, 0), alpha=1.0 / 255.0):
+        """The quantile combine alone over caller-held warps (stk_quantile_stack), with the arguments of clip_stack."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Ms = []
+        for w in warps:
+            Md = np.asarray(w, np.float64).reshape(-1)
+            Ms.append(np.concatenate([Md, [0.0, 0.0, 1.0]]) if Md.size == 6 else Md)
+        if len(Ms) != m.n or any(x.size != 9 for x in Ms):
+            raise InvalidParams("one 3x3 (or 2x3) warp per frame expected")
+        Md = np.ascontiguousarray(np.stack(Ms))
+        inc = None if include is None else np.ascontiguousarray(np.asarray(include, np.int32).reshape(-1))
+        if inc is not None and inc.size != m.n:
+            raise InvalidParams("one include flag per frame expected")
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        out, img = self._out_image(m)
+        qp = _quantile_c(quantile)
+        self._check(self._lib.stk_quantile_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                 None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
+                                                 int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(qp),
+                                                 C.byref(img)))
+        return out
 
     # -- shard-level (one process per GPU; frames[0] = reference frame) ------------------------------
     def ecc_match_shard(self, files, params: EccMatchParameters, add_reference: bool, sum_out,

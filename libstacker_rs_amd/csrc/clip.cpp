@@ -31,14 +31,6 @@ stk_status clip_check_out(stk_ctx* ctx, const stk_image_f32* out, const stk_fram
     return STK_OK;
 }
 
-// where the frames of a stack are after a whole-stack call on this context (upload.cpp / keypoint.cpp put host-fed stacks
-// at ctx->frames + i * frame bytes)
-void resident_frames(stk_ctx* ctx, const stk_frames* f, std::vector<const void*>& dev) {
-    const size_t fb = frame_row_bytes(f) * (size_t)f->height;
-    dev.resize(f->n);
-    for (int i = 0; i < f->n; i++) dev[i] = f->location == STK_DEVICE ? f->data[i] : (const void*)(ctx->frames.as<uint8_t>() + fb * (size_t)i);
-}
-
 // The clip passes over the n_frames entries of ctx->warpframes; the c plane (ctx->clip) holds the plain mean. Writes `out`
 // and `counts` (out's location) and sets stk_timing.finalize_ms to the passes' device time.
 stk_status clip_passes(stk_ctx* ctx, int n_frames, int depth, int w, int h, int cn, size_t src_row_bytes, double alpha,

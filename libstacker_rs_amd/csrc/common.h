@@ -188,7 +188,14 @@ struct ClipArgs {
     int* counts;                 // last pass: samples kept, tightly packed; null = not wanted
     float kappa_low, kappa_high;
     int first, last;
+    // the fold's store mode (FoldStore, warp_body.h; kernels_quantile.hip): the samples of destination rows [y0, y0 +
+    // band_rows) go to band[((i * band_rows + y - y0) * dw + x) * cn + c] for entry i of the frame table; plane_stride = dw x cn
+    float* band;
+    int y0, band_rows;
 };
+
+// quantile combines: samples per pixel the selection kernel takes (64 lanes of a wave x 64 keys in registers)
+constexpr int QUANTILE_MAX_SAMPLES = 4096;
 
 // ---- kernel launchers (defined in the .hip files) -------------------------------------------
 hipError_t launch_grey(const void* bgr, int depth, int w, int h, size_t stride_bytes, void* out, hipStream_t s,
@@ -220,6 +227,12 @@ hipError_t launch_ecc_set_ready(EccQueue* queue, int ready, hipStream_t s);
 hipError_t launch_warp_accumulate(const WarpArgs& a, int depth, hipStream_t s);
 // one clipping pass over the frames of `a` (a.acc unused); same kernel choice as launch_warp_accumulate
 hipError_t launch_clip_pass(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
+// the store mode over the frames of `a` for one band (c.band, c.y0, c.band_rows, c.plane_stride; a.acc unused); same kernel
+// choice as launch_clip_pass
+hipError_t launch_quantile_store(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
+// per column k < m of the n x m samples of a band (frame-major: band[i * m + k]): the quantile with lo = s_(j) and the
+// fraction g (include/stacker.h), into out[k]; n <= QUANTILE_MAX_SAMPLES
+hipError_t launch_quantile_select(const float* band, size_t m, int n, int j, float g, float* out, hipStream_t s);
 // the fold's frame table straight from the ECC results, on the device: entry 0 = the reference frame under the identity
 // (if add_reference), then template k under results[k].warp — what the host loop of ecc_shard_impl builds, bit for bit
 hipError_t launch_warp_frames_from_ecc(const EccFrameResult* results, const void* const* src_ptrs /* n_templates + 1, device */,

@@ -70,6 +70,7 @@ struct stk_ctx {
     int opt_ecc_groups = 0;       // ECC slots in this many groups with their own launch sequences on two streams (stacker.cpp: ecc_run); 0 = by frame size
     int opt_ecc_ring_lookahead = 5;   // debug: frame-0 rows the ring keeps ahead (5 = production; less makes the run-time check fire and the strip fall back)
     int opt_ecc_variant = 3;      // ECC iteration kernel: 3 = production (column-walking homography pass / pipelined affine family), 0 = direct cross-check
+    int opt_quantile_band_rows = 0;   // quantile combines: at most this many rows per band of samples; 0 = as many as fit the band budget
     stk_timing timing{};
     hipEvent_t ev[8] = {};
     hipEvent_t poll_ev[2] = {};
@@ -84,6 +85,7 @@ struct stk_ctx {
     // workspace
     DevBuf frames, ref, blur_tmp, templates, slots, queue, results, partials, warpframes, acc, scratch, init_warps, frameptrs;
     DevBuf clip;                  // sigma clipping (clip.cpp): the c, L and U planes
+    DevBuf quantile;              // quantile combines (quantile.cpp): a w x h x cn f32 image, then the band of samples
     stk::KeypointWorkspace* kp = nullptr;
     stk::geom::HgWorkspace* hg = nullptr;   // findHomography batch workspace (homography.cpp)
     stk::HostPool* host_pool = nullptr;
@@ -125,7 +127,10 @@ size_t image_stride_floats(const stk_image_f32* im);
 void timing_begin(stk_ctx* ctx);
 float ev_ms(hipEvent_t a, hipEvent_t b);
 
-// shared internals of the entry points (stacker.cpp / keypoint.cpp / hybrid.cpp / clip.cpp)
+// shared internals of the entry points (stacker.cpp / keypoint.cpp / hybrid.cpp / clip.cpp / quantile.cpp)
+// where the frames of a stack are after a whole-stack call on this context (upload.cpp / keypoint.cpp put host-fed stacks
+// at ctx->frames + i * frame bytes)
+void resident_frames(stk_ctx* ctx, const stk_frames* f, std::vector<const void*>& dev);
 // stk_ecc_match / stk_keypoint_match on the context's own device: what they run on a plain context
 stk_status ecc_match_single(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
                             stk_image_f32* out, stk_frame_stats* stats);

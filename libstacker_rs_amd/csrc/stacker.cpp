@@ -92,7 +92,8 @@ void stk_destroy(stk_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (DevBuf* b : {&ctx->frames, &ctx->ref, &ctx->blur_tmp, &ctx->templates, &ctx->slots, &ctx->queue, &ctx->results,
-                      &ctx->partials, &ctx->warpframes, &ctx->acc, &ctx->scratch, &ctx->init_warps, &ctx->frameptrs, &ctx->clip})
+                      &ctx->partials, &ctx->warpframes, &ctx->acc, &ctx->scratch, &ctx->init_warps, &ctx->frameptrs, &ctx->clip,
+                      &ctx->quantile})
         b->release();
     keypoint_workspace_destroy(ctx->kp);
     geom::hg_workspace_destroy(ctx->hg);
@@ -167,6 +168,7 @@ stk_status set_option_one(stk_ctx* ctx, const char* name, int64_t value) {
     else if (n == "prep_stream") ctx->opt_prep_stream = value != 0;
     else if (n == "prep_overlap") ctx->opt_prep_overlap = value != 0;
     else if (n == "upload_batch") { if (value < 1 || value > 1024) return fail(ctx, STK_INVALID_PARAMS, "upload_batch out of range"); ctx->opt_upload_batch = (int)value; }
+    else if (n == "quantile_band_rows") { if (value < 0 || value > (1 << 24)) return fail(ctx, STK_INVALID_PARAMS, "quantile_band_rows out of range"); ctx->opt_quantile_band_rows = (int)value; }
     else if (n == "ecc_blocks") { if (value != 0 && (value < 8 || value > 65536)) return fail(ctx, STK_INVALID_PARAMS, "ecc_blocks out of range"); ctx->opt_ecc_blocks = (int)value; }
     else return fail(ctx, STK_INVALID_PARAMS, "unknown option " + n);
     return STK_OK;
@@ -484,6 +486,12 @@ stk_status warp_fold_enqueue(stk_ctx* ctx, int n_frames, int depth, int w, int h
 }
 
 void make_warp_frame(WarpFrame& wf, const void* src, const double* M, int is_affine) { warp_frame_make(wf, src, M, is_affine); }
+
+void resident_frames(stk_ctx* ctx, const stk_frames* f, std::vector<const void*>& dev) {
+    const size_t fb = frame_row_bytes(f) * (size_t)f->height;
+    dev.resize(f->n);
+    for (int i = 0; i < f->n; i++) dev[i] = f->location == STK_DEVICE ? f->data[i] : (const void*)(ctx->frames.as<uint8_t>() + fb * (size_t)i);
+}
 
 stk_status image_check(stk_ctx* ctx, const stk_image_f32* im, int w, int h, int c) {
     if (!im || !im->data) return fail(ctx, STK_INVALID_PARAMS, "null output image");

@@ -7,10 +7,17 @@
 //     (rim path).
 // In clip mode ClipState::begin() / finish() are the prologue / epilogue. The mean instantiations (CLIP = false, NoClip)
 // compile to the instructions these kernels had before the clip mode existed.
+// The third mode, store (CLIP = true with ClipState = FoldStore<CN>, below; kernels_quantile.hip), writes every sample to
+// a band buffer instead: the quantile combines' samples, again the mean's by construction. It is the only mode whose rows
+// start at ClipArgs::y0 (a band of the destination); the frame table is the full frame's, unchanged.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace stk {
+
+template <int CN> struct FoldStore;
 
 __device__ __forceinline__ int border_interp(int p, int len, int mode) {
     if ((unsigned)p < (unsigned)len) return p;
@@ -47,7 +54,8 @@ __device__ __forceinline__ int sat_int_d(double v) {
 template <typename T, int CN, bool CLIP, class ClipState>
 __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipArgs ca) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if constexpr (std::is_same_v<ClipState, FoldStore<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
     if (x >= a.dw || y >= a.dh) return;
     float* accp = a.acc + (size_t)y * a.acc_stride + (size_t)x * CN;
     float sum[CN];
@@ -186,6 +194,26 @@ __device__ __forceinline__ f32x2 div2_shared(f32x2 n, float d) {
     return pk_fma(e, r2, q);
 }
 
+// The store mode's state: the sample of table entry i goes to band[((i * band_rows + y - y0) * dw + x) * CN + c]
+// (ClipArgs), so a wave's stores for one frame are contiguous. The hooks run in frame order, so the entry index is a
+// pointer that moves one frame slab per frame: after channel CN - 1 (add) or once per call (add2 / add3).
+template <int CN>
+struct FoldStore {
+    float* p;
+    size_t slab;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+        p = ca.band + (size_t)(y - ca.y0) * ca.plane_stride + (size_t)x * CN;
+        slab = (size_t)ca.band_rows * ca.plane_stride;
+    }
+    __device__ __forceinline__ void add(int c, float v) {
+        p[c] = v;
+        if (c == CN - 1) p += slab;
+    }
+    __device__ __forceinline__ void add2(f32x2 s01, float s2) { p[0] = s01.x; p[1] = s01.y; p[2] = s2; p += slab; }
+    __device__ __forceinline__ void add3(float s0, float s1, float s2) { p[0] = s0; p[1] = s1; p[2] = s2; p += slab; }
+    __device__ __forceinline__ void finish(const ClipArgs&, int, int) {}
+};
+
 // WX: waves of a workgroup side by side along x (tile = 64 WX x 4 / WX pixels); WU: frames in flight per lane
 // CLIP = false: the mean fold (running sums into a.acc); true: one sigma-clipping pass (ClipU8C3, kernels_clip.hip) — the
 // same samples, only the per-sample body and the prologue / epilogue differ
@@ -193,7 +221,8 @@ template <bool AFFINE, int WX, int WU, bool CLIP, class ClipState>
 __global__ __launch_bounds__(256) void warp_accumulate_u8c3_kernel(WarpArgs a, ClipArgs ca) {
     const int wave = threadIdx.x >> 6;
     const int x = (blockIdx.x * WX + (wave % WX)) * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * (4 / WX) + wave / WX;
+    int y = blockIdx.y * (4 / WX) + wave / WX;
+    if constexpr (std::is_same_v<ClipState, FoldStore<3>>) y += ca.y0;      // store mode: a band of rows (a.dh = its end)
     if (x >= a.dw || y >= a.dh) return;
     float* accp = a.acc + (size_t)y * a.acc_stride + (size_t)x * 3;
     f32x2 s01 = {0.f, 0.f};                   // (B, G) running sums as a register pair, R apart
