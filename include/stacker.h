@@ -342,6 +342,85 @@ stk_status stk_quantile_stack(stk_ctx* ctx, const stk_frames* frames, const doub
                               int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
                               const stk_quantile_params* quantile, stk_image_f32* out);
 
+/* ---- weighted, coverage-aware stacking with per-frame normalisation: an EXTENSION beyond the reference ---------
+ * A weighted mean with a per-frame linear map (gain, offset), a per-frame weight and a per-pixel coverage weight, and a
+ * device pass that estimates the gains and offsets from the overlap with frame 0.
+ * Samples. As in the clipped combine: per destination pixel and channel, s_i is the value the mean fold adds for table
+ * entry i. Entry 0 is frame 0 through the identity, then the kept frames in ascending index (in stk_weighted_stack and
+ * stk_overlap_moments: the included frames in index order under the caller's matrices). The fold's warp, border mode and
+ * value, alpha and warp_subpixel_bits apply.
+ * Coverage weight kappa_i(x, y), one per pixel and entry, not per channel. It is the sample the same fold produces for a
+ * frame of the same size whose every value is 1.0f, with alpha = 1, BORDER_CONSTANT and border value 0: the bilinear
+ * weight that falls on in-frame taps, computed by the very lerp chain (or the classic four-weight sum) that computes s_i.
+ * It is exactly 1.0f wherever all four taps are inside and 0 where none is. A non-finite coordinate gives 0. With
+ * coverage = 0, kappa_i = 1 by definition and the border samples count, as in the mean. With coverage = 1 the fold must
+ * run under BORDER_CONSTANT with border value 0 in every channel; anything else is STK_INVALID_PARAMS. Only then is s_i
+ * the premultiplied sum that belongs to kappa_i.
+ * Combine. f32, each operation rounded on its own, `/` correctly rounded, entries in fold order:
+ *   num_c = 0;  den = 0
+ *   for each entry i:   v = s_i,c * g_i,c + o_i,c * kappa_i
+ *                       num_c = num_c + w_i * v
+ *                       den   = den   + w_i * kappa_i
+ *   out_c = den > 0 ? num_c / den : 0;     coverage_out (optional, w x h f32, in the location of `out`) = den
+ * g, o are per frame and channel, w is per frame. w_i must be finite and >= 0, g and o finite; otherwise
+ * STK_INVALID_PARAMS. The same status results if every included w_i is 0.
+ * Overlap moments (the estimator's input). For entry i >= 1 and channel c, take the destination pixels with
+ * x % step == 0, y % step == 0 and kappa_i == 1.0f. kappa_i here is always the BORDER_CONSTANT one, whatever the fold's
+ * border mode. With X = (double)s_i,c and Y = (double)s_0,c, the six f64 values are n, sum X, sum Y, sum X^2, sum Y^2,
+ * sum XY. The products are formed in f64, so each term is exact and only the order of summation is free. The order is
+ * fixed by the geometry and the step alone (per-wave partials written out and reduced in index order, no floating-point
+ * atomics): the same bits on every call, whatever the options.
+ * Estimator, on the host in f64, results rounded to f32. With mx = sum X / n, my = sum Y / n, vx = sum X^2 / n - mx^2 and vy
+ * likewise:
+ *   normalize 0 NONE:    gain 1,              offset 0
+ *             1 OFFSET:  gain 1,              offset my - mx             (sky level)
+ *             2 GAIN:    gain my / mx,        offset 0                   (exposure / transparency)
+ *             3 LINEAR:  gain sqrt(vy / vx),  offset my - g mx           (g: the f64 gain, before rounding)
+ * Entry 0 always has g = 1, o = 0. If n == 0, a denominator is <= 0, or a result is not finite, that frame and channel
+ * fall back to (1, 0) and bit c of stk_frame_weight.flags is set. These are plain moments, not robust ones: a bright
+ * transient inside the overlap biases them.
+ * `out` must be tightly packed. stk_timing.finalize_ms of the whole-stack calls is the device time of the moments pass
+ * plus the weighted fold (warp_ms etc. are the plain call's). A multi-device context runs these calls on its first
+ * device. */
+typedef struct {
+    int32_t normalize;              /* 0 NONE, 1 OFFSET, 2 GAIN, 3 LINEAR */
+    int32_t coverage;               /* 0: border samples count, kappa = 1;  1: divide by the covered weight */
+    int32_t stat_step;              /* moments on every stat_step-th row and column, 1 .. 64; 0 = default (4) */
+    int32_t reserved;               /* 0 */
+} stk_weight_params;
+typedef struct {
+    float   gain[4];
+    float   offset[4];
+    float   weight;
+    int32_t flags;                  /* bit c: channel c fell back to (1, 0) */
+} stk_frame_weight;
+
+/* ecc_match with the weighted combine (definition above): stats, warps, iterations and errors are those of stk_ecc_match
+ * on the same input; the fold runs under BORDER_CONSTANT 0 with alpha = 1/255. weights_or_null: n weights by frame index,
+ * NULL = all 1. coverage_or_null: den, width * height f32 in the location of `out`. applied_or_null: n records by frame
+ * index, what the fold used. */
+stk_status stk_ecc_match_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                  const stk_weight_params* weight, const float* weights_or_null, stk_image_f32* out,
+                                  float* coverage_or_null, stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
+/* keypoint_match with the weighted combine: stats and `dropped` as stk_keypoint_match; the samples are frame 0 and the
+ * frames with status 0, folded with the params' border mode and value (coverage = 1 needs BORDER_CONSTANT 0). In
+ * `applied` a dropped frame has weight 0 and gains 1, offsets 0. */
+stk_status stk_keypoint_match_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                       float scale_down_width, const stk_weight_params* weight, const float* weights_or_null,
+                                       stk_image_f32* out, int32_t* dropped, float* coverage_or_null,
+                                       stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
+/* The combine alone over caller-held warps, with the arguments of stk_clip_stack (definition above). per_frame: n records
+ * by frame index, used as given (flags ignored; excluded frames' records are not read). coverage: 0 or 1. */
+stk_status stk_weighted_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                              int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                              const stk_frame_weight* per_frame, int32_t coverage, stk_image_f32* out, float* coverage_or_null);
+/* The overlap moments alone (definition above) of every included frame i >= 1 against frame 0, which must be included.
+ * stat_step: 1 .. 64. moments: n x channels x 6 doubles on the host, frame index order, per channel n, sum X, sum Y,
+ * sum X^2, sum Y^2, sum XY; frame 0 and excluded frames: zeros. */
+stk_status stk_overlap_moments(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                               int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                               int32_t stat_step, double* moments);
+
 /* ---- stage-level entry points (parity tests bind these) ------------------ */
 /* cvt_color(BGR2GRAY) on the integer image, utils.rs:136-142. out: w*h of the input depth
  * (u8 / u16 / f32), tightly packed, same location as the frame. */

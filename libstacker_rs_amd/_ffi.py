@@ -55,6 +55,14 @@ class QuantileParams(C.Structure):
     _fields_ = [("quantile", C.c_float), ("reserved", C.c_int32)]
 
 
+class WeightParams(C.Structure):
+    _fields_ = [("normalize", C.c_int32), ("coverage", C.c_int32), ("stat_step", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FrameWeight(C.Structure):
+    _fields_ = [("gain", C.c_float * 4), ("offset", C.c_float * 4), ("weight", C.c_float), ("flags", C.c_int32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("prep_ms", C.c_double), ("align_ms", C.c_double), ("warp_ms", C.c_double),
                 ("finalize_ms", C.c_double), ("ecc_iter_launches", C.c_int64),
@@ -104,6 +112,15 @@ SIGNATURES = {
                                                C.POINTER(FrameStats)]),
     "stk_quantile_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                       C.c_double, C.POINTER(QuantileParams), C.POINTER(ImageF32)]),
+    "stk_ecc_match_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float, C.POINTER(WeightParams),
+                                          C.c_void_p, C.POINTER(ImageF32), C.c_void_p, C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
+    "stk_keypoint_match_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                               C.POINTER(WeightParams), C.c_void_p, C.POINTER(ImageF32), C.POINTER(C.c_int32),
+                                               C.c_void_p, C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
+    "stk_weighted_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_double, C.POINTER(FrameWeight), C.c_int32, C.POINTER(ImageF32), C.c_void_p]),
+    "stk_overlap_moments": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_double, C.c_int32, C.c_void_p]),
     "stk_grey": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p]),
     "stk_convert_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_double, C.c_void_p]),
     "stk_hybrid_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.POINTER(EccParams),

@@ -125,6 +125,22 @@ class QuantileParameters:         # extension beyond the reference: include/stac
         return _ffi.QuantileParams(float(self.quantile), 0)
 
 
+NORMALIZE_NONE, NORMALIZE_OFFSET, NORMALIZE_GAIN, NORMALIZE_LINEAR = 0, 1, 2, 3
+
+
+@dataclass
+class WeightParameters:           # extension beyond the reference: include/stacker.h, stk_weight_params
+    """The *_weighted combines: `normalize` maps every frame onto frame 0's level before the mean (0 none, 1 offset = sky
+    level, 2 gain = exposure / transparency, 3 linear), estimated from the overlap on every `stat_step`-th row and column
+    (0 = 4); `coverage` divides each pixel by the weight that actually covered it instead of counting border samples."""
+    normalize: int = NORMALIZE_NONE
+    coverage: bool = True
+    stat_step: int = 0
+
+    def _c(self) -> _ffi.WeightParams:
+        return _ffi.WeightParams(int(self.normalize), int(self.coverage), int(self.stat_step), 0)
+
+
 def _quantile_c(q) -> _ffi.QuantileParams:
     """QuantileParameters, a bare float, or None (the median)."""
     if q is None:
@@ -491,6 +507,137 @@ class Stacker:
                                                  int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(qp),
                                                  C.byref(img)))
         return out
+
+    # -- weighted, coverage-aware combines (extension beyond the reference) ----------------------------
+    def _coverage_image(self, m: _Marshalled):
+        """f32 HxW summed-weight plane placed where the output lives."""
+        if m.location == DEVICE:
+            import torch
+            cov = torch.empty((m.h, m.w), dtype=torch.float32, device=m.torch_device)
+            return cov, C.c_void_p(cov.data_ptr())
+        cov = np.empty((m.h, m.w), np.float32)
+        return cov, C.c_void_p(cov.ctypes.data)
+
+    @staticmethod
+    def _applied_list(applied, n, cn):
+        return [dict(gain=np.array(list(a.gain)[:cn], np.float32), offset=np.array(list(a.offset)[:cn], np.float32),
+                     weight=float(a.weight), flags=int(a.flags)) for a in applied[:n]]
+
+    @staticmethod
+    def _weights_arg(weights, n):
+        if weights is None:
+            return None, None
+        w = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+        if w.size != n:
+            raise InvalidParams("one weight per frame expected")
+        return w, C.c_void_p(w.ctypes.data)
+
+    def ecc_match_weighted(self, files, params: EccMatchParameters, weight: Optional["WeightParameters"] = None, weights=None,
+                           scale_down_width: Optional[float] = None, return_stats: bool = False, return_coverage: bool = False,
+                           return_applied: bool = False):
+        """ecc_match with the weighted, coverage-aware mean and per-frame normalisation instead of the plain mean
+        (stk_ecc_match_weighted). weights: one per frame or None = all 1. Returns the image, then the summed-weight plane
+        (return_coverage), the per-frame records the fold used (return_applied) and the stats (return_stats)."""
+        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
+        wkeep, wptr = self._weights_arg(weights, m.n)
+        applied = (_ffi.FrameWeight * m.n)()
+        stats = (_ffi.FrameStats * m.n)()
+        p, wp = params._c(), (weight or WeightParameters())._c()
+        self._check(self._lib.stk_ecc_match_weighted(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                     C.byref(wp), wptr, C.byref(img), cptr, applied, stats))
+        res = (out,) + ((cov,) if return_coverage else ()) + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) \
+            + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return res if len(res) > 1 else out
+
+    def keypoint_match_weighted(self, files, params: KeyPointMatchParameters, weight: Optional["WeightParameters"] = None,
+                                weights=None, scale_down_width: Optional[float] = None, return_stats: bool = False,
+                                return_coverage: bool = False, return_applied: bool = False):
+        """keypoint_match with the weighted combine (stk_keypoint_match_weighted): (dropped, image[, coverage][, applied]
+        [, stats]). A dropped frame is no sample: weight 0 in `applied`."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
+        wkeep, wptr = self._weights_arg(weights, m.n)
+        applied = (_ffi.FrameWeight * m.n)()
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p, wp = params._c(), (weight or WeightParameters())._c()
+        self._check(self._lib.stk_keypoint_match_weighted(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                          C.byref(wp), wptr, C.byref(img), C.byref(dropped), cptr, applied, stats))
+        return (dropped.value, out) + ((cov,) if return_coverage else ()) \
+            + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+
+    def _warps_arg(self, warps, include, n):
+        Ms = []
+        for w in warps:
+            Md = np.asarray(w, np.float64).reshape(-1)
+            Ms.append(np.concatenate([Md, [0.0, 0.0, 1.0]]) if Md.size == 6 else Md)
+        if len(Ms) != n or any(x.size != 9 for x in Ms):
+            raise InvalidParams("one 3x3 (or 2x3) warp per frame expected")
+        inc = None if include is None else np.ascontiguousarray(np.asarray(include, np.int32).reshape(-1))
+        if inc is not None and inc.size != n:
+            raise InvalidParams("one include flag per frame expected")
+        return np.ascontiguousarray(np.stack(Ms)), inc
+
+    def weighted_stack(self, files, warps, gain=None, offset=None, weights=None, include=None, *, applied=None, coverage: bool = True,
+                       is_affine=False, border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0,
+                       return_coverage: bool = False):
+        """The weighted combine alone over caller-held warps (stk_weighted_stack), with the arguments of clip_stack.
+        gain, offset: n x channels (None = 1 / 0); weights: n (None = 1); or `applied`: the per-frame records another
+        weighted call returned, used as given."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Md, inc = self._warps_arg(warps, include, m.n)
+        rec = (_ffi.FrameWeight * m.n)()
+        if applied is not None:
+            if len(applied) != m.n:
+                raise InvalidParams("one record per frame expected")
+            gain = [a["gain"] for a in applied]
+            offset = [a["offset"] for a in applied]
+            weights = [a["weight"] for a in applied]
+        g = np.ones((m.n, m.c), np.float32) if gain is None else np.asarray(gain, np.float32).reshape(m.n, -1)
+        o = np.zeros((m.n, m.c), np.float32) if offset is None else np.asarray(offset, np.float32).reshape(m.n, -1)
+        w = np.ones(m.n, np.float32) if weights is None else np.asarray(weights, np.float32).reshape(-1)
+        if g.shape != (m.n, m.c) or o.shape != (m.n, m.c) or w.size != m.n:
+            raise InvalidParams("gain and offset: n x channels, weights: n expected")
+        for i in range(m.n):
+            for c in range(4):
+                rec[i].gain[c] = float(g[i, c]) if c < m.c else 1.0
+                rec[i].offset[c] = float(o[i, c]) if c < m.c else 0.0
+            rec[i].weight = float(w[i])
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        out, img = self._out_image(m)
+        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
+        self._check(self._lib.stk_weighted_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                 None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
+                                                 int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), rec, int(coverage),
+                                                 C.byref(img), cptr))
+        return (out, cov) if return_coverage else out
+
+    def overlap_moments(self, files, warps, include=None, *, stat_step: int = 4, is_affine=False, border_mode=BORDER_CONSTANT,
+                        border_value=(0, 0, 0, 0), alpha=1.0 / 255.0):
+        """The overlap moments of every included frame against frame 0 (stk_overlap_moments): an n x channels x 6 float64
+        array (n, sum X, sum Y, sum X^2, sum Y^2, sum XY), zeros for frame 0 and excluded frames."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Md, inc = self._warps_arg(warps, include, m.n)
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        mom = np.zeros((m.n, m.c, 6), np.float64)
+        self._check(self._lib.stk_overlap_moments(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                  None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
+                                                  int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), int(stat_step),
+                                                  C.c_void_p(mom.ctypes.data)))
+        return mom
 
     # -- shard-level (one process per GPU; frames[0] = reference frame) ------------------------------
     def ecc_match_shard(self, files, params: EccMatchParameters, add_reference: bool, sum_out,

@@ -192,6 +192,16 @@ struct ClipArgs {
     // band_rows) go to band[((i * band_rows + y - y0) * dw + x) * cn + c] for entry i of the frame table; plane_stride = dw x cn
     float* band;
     int y0, band_rows;
+    // the fold's weighted mode (FoldWeighted, warp_body.h; kernels_weighted.hip): per-entry gain / offset / weight, indexed
+    // like the frame table; the result goes to out / out_stride, the summed weight den to `den` (dw x dh, optional)
+    const stk_frame_weight* coef;
+    float* den;
+    size_t den_stride;
+    int coverage;                // 0: kappa = 1 (border samples count); 1: kappa = the bilinear weight on in-frame taps
+    // the generic kernel's moments mode (FoldMoments): stepped pixels (step * k), `reps` stepped rows per thread, one
+    // partial of 1 + 5 cn doubles per wave and entry
+    double* partials;
+    int step, reps;
 };
 
 // quantile combines: samples per pixel the selection kernel takes (64 lanes of a wave x 64 keys in registers)
@@ -229,6 +239,15 @@ hipError_t launch_warp_accumulate(const WarpArgs& a, int depth, hipStream_t s);
 hipError_t launch_clip_pass(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
 // the store mode over the frames of `a` for one band (c.band, c.y0, c.band_rows, c.plane_stride; a.acc unused); same kernel
 // choice as launch_clip_pass
+// the weighted fold over the frames of `a` (c.coef, c.coverage, c.out / c.out_stride, c.den / c.den_stride; a.acc unused);
+// same kernel choice as launch_clip_pass
+hipError_t launch_weighted_fold(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
+// stepped grid of the moments pass for a dw x dh destination: columns, rows per thread, workgroups in x and y
+struct MomentsPlan { int gw, gh, reps, bx, by; size_t parts() const { return (size_t)bx * by * 4; } };
+MomentsPlan moments_plan(int dw, int dh, int step);
+// overlap moments of entries 1 .. a.n_frames - 1 against entry 0 (include/stacker.h): per-wave partials into c.partials
+// ((n_frames - 1) x plan.parts() x (1 + 5 cn) doubles), then reduced in index order into moments ((n_frames - 1) x cn x 6)
+hipError_t launch_overlap_moments(const WarpArgs& a, ClipArgs c, int depth, int step, double* moments, hipStream_t s);
 hipError_t launch_quantile_store(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
 // per column k < m of the n x m samples of a band (frame-major: band[i * m + k]): the quantile with lo = s_(j) and the
 // fraction g (include/stacker.h), into out[k]; n <= QUANTILE_MAX_SAMPLES

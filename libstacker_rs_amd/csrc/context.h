@@ -85,6 +85,7 @@ struct stk_ctx {
     // workspace
     DevBuf frames, ref, blur_tmp, templates, slots, queue, results, partials, warpframes, acc, scratch, init_warps, frameptrs;
     DevBuf clip;                  // sigma clipping (clip.cpp): the c, L and U planes
+    DevBuf weighted;              // weighted combine (weighted.cpp): image, den plane, per-entry table, moments and their partials
     DevBuf quantile;              // quantile combines (quantile.cpp): a w x h x cn f32 image, then the band of samples
     stk::KeypointWorkspace* kp = nullptr;
     stk::geom::HgWorkspace* hg = nullptr;   // findHomography batch workspace (homography.cpp)

@@ -1,0 +1,96 @@
+// kernels_weighted.hip — the weighted, coverage-aware mean over the aligned frames and the overlap moments its
+// normalisation is estimated from (stk_weighted_stack, stk_overlap_moments and the *_weighted entry points; definition in
+// include/stacker.h, stk_weight_params). Both are modes of the fold kernels of warp_body.h, so the sample they see is the
+// mean's by construction:
+//   * the weighted fold: FoldWeighted<CN> in the generic kernel and in the u8 BGR fast kernel. Per sample, over the mean's
+//     work: two multiplies and two adds per channel plus one add for den (interior path), and kappa's lerp chain and two
+//     more multiplies on the rim. One launch, the result written once;
+//   * the moments pass: FoldMoments<CN> in the generic kernel (every depth; its samples are the fast kernel's bit for
+//     bit), grid z = entry - 1. A thread walks `reps` stepped rows of one entry privately in f64 before its wave reduces by
+//     lane shuffles and writes one partial; moments_reduce_kernel then adds an entry's partials in index order. The order
+//     of every addition is fixed by the geometry and the step alone: the same bits on every call. No atomics.
+#include "warp_body.h"
+
+namespace stk {
+
+// one workgroup per entry, one thread per moment: partials in index order (four loads in flight, added in order)
+__global__ __launch_bounds__(64) void moments_reduce_kernel(const double* __restrict__ partials, size_t parts, int nm, int cn,
+                                                            double* __restrict__ moments) {
+    const int k = threadIdx.x;
+    if (k >= nm) return;
+    const double* p = partials + (size_t)blockIdx.x * parts * nm + k;
+    double s = 0.0;
+    size_t i = 0;
+    for (; i + 4 <= parts; i += 4) {
+        const double v0 = p[i * nm], v1 = p[(i + 1) * nm], v2 = p[(i + 2) * nm], v3 = p[(i + 3) * nm];
+        s = s + v0; s = s + v1; s = s + v2; s = s + v3;
+    }
+    for (; i < parts; i++) s = s + p[i * nm];
+    // partial layout: n, then per channel (sum X, sum Y, sum X^2, sum Y^2, sum XY); output: per channel (n, the five sums)
+    double* o = moments + (size_t)blockIdx.x * cn * 6;
+    if (k == 0) { for (int c = 0; c < cn; c++) o[c * 6] = s; }
+    else o[((k - 1) / 5) * 6 + 1 + (k - 1) % 5] = s;
+}
+
+hipError_t launch_weighted_fold(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
+    if (a.n_frames <= 0) return hipErrorInvalidValue;
+    if (warp_u8c3_applies(a, depth)) {
+        // the mean fold's default launch shape (one wave per row of 64 pixels, four frames in flight)
+        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
+        if (a.is_affine) warp_accumulate_u8c3_kernel<true, 1, 4, true, FoldWeighted<3>><<<g, 256, 0, s>>>(a, c);
+        else warp_accumulate_u8c3_kernel<false, 1, 4, true, FoldWeighted<3>><<<g, 256, 0, s>>>(a, c);
+        return hipGetLastError();
+    }
+    const dim3 grid((a.dw + 63) / 64, (a.dh + 3) / 4);
+#define STK_WEIGHTED_CASE(T, CN) warp_accumulate_kernel<T, CN, true, FoldWeighted<CN>><<<grid, 256, 0, s>>>(a, c)
+    if (depth == 8 && a.cn == 3) STK_WEIGHTED_CASE(uint8_t, 3);
+    else if (depth == 8 && a.cn == 1) STK_WEIGHTED_CASE(uint8_t, 1);
+    else if (depth == 8 && a.cn == 4) STK_WEIGHTED_CASE(uint8_t, 4);
+    else if (depth == 16 && a.cn == 3) STK_WEIGHTED_CASE(uint16_t, 3);
+    else if (depth == 16 && a.cn == 1) STK_WEIGHTED_CASE(uint16_t, 1);
+    else if (depth == 16 && a.cn == 4) STK_WEIGHTED_CASE(uint16_t, 4);
+    else if (depth == 32 && a.cn == 3) STK_WEIGHTED_CASE(float, 3);
+    else if (depth == 32 && a.cn == 1) STK_WEIGHTED_CASE(float, 1);
+    else if (depth == 32 && a.cn == 4) STK_WEIGHTED_CASE(float, 4);
+    else return hipErrorInvalidValue;
+#undef STK_WEIGHTED_CASE
+    return hipGetLastError();
+}
+
+// rows per thread: at least 8, and enough that an entry has about 1024 partials at most (the second launch adds them one
+// after the other)
+MomentsPlan moments_plan(int dw, int dh, int step) {
+    MomentsPlan p;
+    p.gw = (dw + step - 1) / step;
+    p.gh = (dh + step - 1) / step;
+    p.bx = (p.gw + 63) / 64;
+    const long long want = ((long long)p.bx * p.gh + 1023) / 1024;
+    p.reps = (int)(want < 8 ? 8 : want);
+    p.by = (p.gh + 4 * p.reps - 1) / (4 * p.reps);
+    return p;
+}
+
+hipError_t launch_overlap_moments(const WarpArgs& a, ClipArgs c, int depth, int step, double* moments, hipStream_t s) {
+    if (a.n_frames < 2 || step < 1) return hipErrorInvalidValue;
+    const MomentsPlan p = moments_plan(a.dw, a.dh, step);
+    c.step = step; c.reps = p.reps;
+    const dim3 grid(p.bx, p.by, a.n_frames - 1);
+#define STK_MOMENTS_CASE(T, CN) warp_accumulate_kernel<T, CN, true, FoldMoments<CN>><<<grid, 256, 0, s>>>(a, c)
+    if (depth == 8 && a.cn == 3) STK_MOMENTS_CASE(uint8_t, 3);
+    else if (depth == 8 && a.cn == 1) STK_MOMENTS_CASE(uint8_t, 1);
+    else if (depth == 8 && a.cn == 4) STK_MOMENTS_CASE(uint8_t, 4);
+    else if (depth == 16 && a.cn == 3) STK_MOMENTS_CASE(uint16_t, 3);
+    else if (depth == 16 && a.cn == 1) STK_MOMENTS_CASE(uint16_t, 1);
+    else if (depth == 16 && a.cn == 4) STK_MOMENTS_CASE(uint16_t, 4);
+    else if (depth == 32 && a.cn == 3) STK_MOMENTS_CASE(float, 3);
+    else if (depth == 32 && a.cn == 1) STK_MOMENTS_CASE(float, 1);
+    else if (depth == 32 && a.cn == 4) STK_MOMENTS_CASE(float, 4);
+    else return hipErrorInvalidValue;
+#undef STK_MOMENTS_CASE
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    moments_reduce_kernel<<<a.n_frames - 1, 64, 0, s>>>(c.partials, p.parts(), 1 + 5 * a.cn, a.cn, moments);
+    return hipGetLastError();
+}
+
+}  // namespace stk

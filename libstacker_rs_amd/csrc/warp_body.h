@@ -10,6 +10,11 @@
 // The third mode, store (CLIP = true with ClipState = FoldStore<CN>, below; kernels_quantile.hip), writes every sample to
 // a band buffer instead: the quantile combines' samples, again the mean's by construction. It is the only mode whose rows
 // start at ClipArgs::y0 (a band of the destination); the frame table is the full frame's, unchanged.
+// The fourth mode, weighted (ClipState = FoldWeighted<CN>, below; kernels_weighted.hip), is the weighted, coverage-aware
+// mean: its hooks also get the entry's coverage weight kappa (fold_kappa below: the sample the same lerp chain gives for
+// an all-ones frame), which the rim paths compute and the u8 fast kernel's interior path knows to be 1. The generic kernel
+// has a fifth mode, moments (FoldMoments<CN>): the overlap moments of entry 1 + blockIdx.z against entry 0 over the
+// stepped pixels, a thread walking ClipArgs::reps stepped rows before its wave reduces.
 #pragma once
 #include <type_traits>
 
@@ -18,6 +23,19 @@
 namespace stk {
 
 template <int CN> struct FoldStore;
+template <int CN> struct FoldWeighted;
+template <int CN> struct FoldMoments;
+
+// The coverage weight of one sample: what the fold's interpolation (lerp chain, or the classic four-weight sum) gives for a
+// frame whose every value is 1.0f under alpha = 1 and BORDER_CONSTANT 0; i00 .. i11 say which taps are inside the frame.
+__device__ __forceinline__ float fold_kappa(bool i00, bool i01, bool i10, bool i11, bool classic, float ax, float ay,
+                                            float w00, float w01, float w10, float w11) {
+    const float p00 = i00 ? 1.0f : 0.0f, p01 = i01 ? 1.0f : 0.0f, p10 = i10 ? 1.0f : 0.0f, p11 = i11 ? 1.0f : 0.0f;
+    if (classic) return p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11;
+    const float t0 = __builtin_fmaf(ax, p01 - p00, p00);
+    const float t1 = __builtin_fmaf(ax, p11 - p10, p10);
+    return __builtin_fmaf(ay, t1 - t0, t0);
+}
 
 __device__ __forceinline__ int border_interp(int p, int len, int mode) {
     if ((unsigned)p < (unsigned)len) return p;
@@ -53,10 +71,13 @@ __device__ __forceinline__ int sat_int_d(double v) {
 // reads compiled to flat loads — a different, slower mean kernel.)
 template <typename T, int CN, bool CLIP, class ClipState>
 __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipArgs ca) {
+    constexpr bool WEIGHTED = std::is_same_v<ClipState, FoldWeighted<CN>>;
+    constexpr bool MOMENTS = std::is_same_v<ClipState, FoldMoments<CN>>;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if constexpr (std::is_same_v<ClipState, FoldStore<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
-    if (x >= a.dw || y >= a.dh) return;
+    // (moments mode: (x, y) index the stepped grid and every lane stays for the wave reduction; see the loop below)
+    if constexpr (!MOMENTS) { if (x >= a.dw || y >= a.dh) return; }
     float* accp = a.acc + (size_t)y * a.acc_stride + (size_t)x * CN;
     float sum[CN];
     ClipState cs;
@@ -66,10 +87,17 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
         for (int c = 0; c < CN; c++) sum[c] = a.accumulate ? accp[c] : 0.0f;
     }
 
-    const float fx = (float)x, fy = (float)y;
+    float fx = (float)x, fy = (float)y;
     const int mode = a.border_mode;
-    for (int f = 0; f < a.n_frames; f++) {
-        const WarpFrame* fr = a.frames + f;
+    // moments mode: the thread walks ca.reps stepped rows, each time over entry 0 and entry 1 + blockIdx.z; every other
+    // mode runs the body once. (fx, fy are set before the loop and only the moments mode overwrites them: computing them
+    // inside the loop changed the register allocation of the other modes' instantiations. The body keeps its indentation.)
+    int rep = 0;
+    do {
+    const int px = MOMENTS ? x * ca.step : x, py = MOMENTS ? (y * ca.reps + rep) * ca.step : y;
+    if constexpr (MOMENTS) { cs.live = (px < a.dw) & (py < a.dh); fx = (float)px; fy = (float)py; }
+    for (int f = 0; f < (MOMENTS ? 2 : a.n_frames); f++) {
+        const WarpFrame* fr = a.frames + (MOMENTS ? f * (1 + (int)blockIdx.z) : f);
         const T* __restrict__ src = (const T*)fr->src;
         int ix, iy;
         float ax = 0, ay = 0;
@@ -92,15 +120,15 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
             int Xi, Yi;
             const double* M = fr->Md;
             if (a.is_affine) {
-                const int adx = sat_int_d(M[0] * x * 1024), bdx = sat_int_d(M[3] * x * 1024);
-                const int X0 = sat_int_d((M[1] * y + M[2]) * 1024) + 16;
-                const int Y0 = sat_int_d((M[4] * y + M[5]) * 1024) + 16;
+                const int adx = sat_int_d(M[0] * px * 1024), bdx = sat_int_d(M[3] * px * 1024);
+                const int X0 = sat_int_d((M[1] * py + M[2]) * 1024) + 16;
+                const int Y0 = sat_int_d((M[4] * py + M[5]) * 1024) + 16;
                 Xi = (X0 + adx) >> 5; Yi = (Y0 + bdx) >> 5;
             } else {
-                double W = M[6] * x + M[7] * y + M[8];
+                double W = M[6] * px + M[7] * py + M[8];
                 W = W != 0 ? 32.0 / W : 0;
-                const double Xd = fmax(-2147483648.0, fmin(2147483647.0, (M[0] * x + M[1] * y + M[2]) * W));
-                const double Yd = fmax(-2147483648.0, fmin(2147483647.0, (M[3] * x + M[4] * y + M[5]) * W));
+                const double Xd = fmax(-2147483648.0, fmin(2147483647.0, (M[0] * px + M[1] * py + M[2]) * W));
+                const double Yd = fmax(-2147483648.0, fmin(2147483647.0, (M[3] * px + M[4] * py + M[5]) * W));
                 Xi = sat_int_d(Xd); Yi = sat_int_d(Yd);
             }
             ix = Xi >> 5; iy = Yi >> 5;
@@ -117,6 +145,12 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
         const int cx0 = max(x0, 0), cx1 = max(x1, 0), cy0 = max(y0, 0), cy1 = max(y1, 0);
         const T* r0 = src + (size_t)cy0 * a.src_stride;
         const T* r1 = src + (size_t)cy1 * a.src_stride;
+        if constexpr (WEIGHTED || MOMENTS) {
+            // kappa from the taps that are inside the frame (the BORDER_CONSTANT validity, whatever the fold's border mode)
+            const bool ix0 = (unsigned)ix < (unsigned)a.sw, ix1 = (unsigned)(ix + 1) < (unsigned)a.sw;
+            const bool iy0 = (unsigned)iy < (unsigned)a.sh, iy1 = (unsigned)(iy + 1) < (unsigned)a.sh;
+            cs.entry(fold_kappa(ix0 & iy0, ix1 & iy0, ix0 & iy1, ix1 & iy1, a.subpixel_bits != 0, ax, ay, w00, w01, w10, w11));
+        }
 #pragma unroll
         for (int c = 0; c < CN; c++) {
             const float p00 = v00 ? (float)r0[cx0 * CN + c] * a.alpha : a.bv[c];
@@ -135,6 +169,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
             else sum[c] = sum[c] + v;
         }
     }
+    } while (MOMENTS && ++rep < ca.reps);
     if constexpr (CLIP) cs.finish(ca, x, y);
     else {
 #pragma unroll
@@ -212,6 +247,99 @@ struct FoldStore {
     __device__ __forceinline__ void add2(f32x2 s01, float s2) { p[0] = s01.x; p[1] = s01.y; p[2] = s2; p += slab; }
     __device__ __forceinline__ void add3(float s0, float s1, float s2) { p[0] = s0; p[1] = s1; p[2] = s2; p += slab; }
     __device__ __forceinline__ void finish(const ClipArgs&, int, int) {}
+};
+
+// The weighted mode's state (definition: include/stacker.h, stk_weight_params): per entry i of the frame table
+//     v = s * g_i,c + o_i,c * kappa_i;  num_c = num_c + w_i * v;  den = den + w_i * kappa_i
+// with g, o, w from ClipArgs::coef[i] (indexed like the frame table; the hooks run in frame order, so the entry is a
+// pointer that moves on after channel CN - 1 or once per add2 / add3k call). ClipArgs::coverage == 0: kappa = 1 by
+// definition. kappa = 1 makes o * kappa and w * kappa o and w bit for bit: add2 (the u8 fast kernel's interior path)
+// multiplies neither.
+template <int CN>
+struct FoldWeighted {
+    float num[CN], den, kap;
+    const stk_frame_weight* e;
+    int cov;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int, int) {
+#pragma unroll
+        for (int c = 0; c < CN; c++) num[c] = 0.f;
+        den = 0.f; kap = 1.0f;
+        e = ca.coef; cov = ca.coverage;
+    }
+    __device__ __forceinline__ void entry(float k) { kap = cov ? k : 1.0f; }
+    __device__ __forceinline__ void add(int c, float s) {
+        const float v = s * e->gain[c] + e->offset[c] * kap;
+        num[c] = num[c] + e->weight * v;
+        if (c == CN - 1) { den = den + e->weight * kap; e++; }
+    }
+    __device__ __forceinline__ void add2(f32x2 s01, float s2) {
+        const float w = e->weight;
+        const f32x2 v01 = s01 * f32x2{e->gain[0], e->gain[1]} + f32x2{e->offset[0], e->offset[1]};
+        const f32x2 n01 = f32x2{num[0], num[1]} + f32x2{w, w} * v01;
+        num[0] = n01.x; num[1] = n01.y;
+        num[2] = num[2] + w * (s2 * e->gain[2] + e->offset[2]);
+        den = den + w;
+        e++;
+    }
+    __device__ __forceinline__ void add3k(float s0, float s1, float s2, float k) {
+        entry(k);
+        add(0, s0); add(1, s1); add(2, s2);
+    }
+    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
+        float* o = ca.out + (size_t)y * ca.out_stride + (size_t)x * CN;
+#pragma unroll
+        for (int c = 0; c < CN; c++) o[c] = den > 0.f ? num[c] / den : 0.f;
+        if (ca.den) ca.den[(size_t)y * ca.den_stride + x] = den;
+    }
+};
+
+// The moments mode's state (generic kernel only): the thread's private f64 sums n, and per channel sum X, sum Y, sum X^2,
+// sum Y^2, sum XY with Y = entry 0's sample and X = entry i's over the stepped pixels where kappa_i == 1.0f. X and Y are
+// f32 values, so each product is exact in f64 and only the order of the additions matters: it is fixed — the thread's rows
+// in order, the xor-shuffle tree over the wave, then one partial per wave to ClipArgs::partials, which
+// moments_reduce_kernel (kernels_weighted.hip) adds in index order. No atomics.
+template <int CN>
+struct FoldMoments {
+    static constexpr int NM = 1 + 5 * CN;
+    double S[NM];
+    float Y[CN], kap;
+    int which;
+    bool live;
+    __device__ __forceinline__ void begin(const ClipArgs&, int, int) {
+#pragma unroll
+        for (int k = 0; k < NM; k++) S[k] = 0.0;
+        which = 0; kap = 0.f; live = false;
+    }
+    __device__ __forceinline__ void entry(float k) { kap = k; }
+    __device__ __forceinline__ void add(int c, float v) {
+        if (which == 0) Y[c] = v;
+        else {
+            const bool in = live & (kap == 1.0f);
+            const double X = in ? (double)v : 0.0, Yd = in ? (double)Y[c] : 0.0;    // masked terms add +0
+            if (c == 0) S[0] = S[0] + (in ? 1.0 : 0.0);
+            S[1 + 5 * c] = S[1 + 5 * c] + X;
+            S[2 + 5 * c] = S[2 + 5 * c] + Yd;
+            S[3 + 5 * c] = S[3 + 5 * c] + X * X;
+            S[4 + 5 * c] = S[4 + 5 * c] + Yd * Yd;
+            S[5 + 5 * c] = S[5 + 5 * c] + X * Yd;
+        }
+        if (c == CN - 1) which ^= 1;
+    }
+    __device__ __forceinline__ void finish(const ClipArgs& ca, int, int) {
+#pragma unroll
+        for (int k = 0; k < NM; k++) {
+            double v = S[k];
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+            S[k] = v;
+        }
+        if ((threadIdx.x & 63) == 0) {
+            const size_t part = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6);
+            double* o = ca.partials + ((size_t)blockIdx.z * ((size_t)gridDim.x * gridDim.y * 4) + part) * NM;
+#pragma unroll
+            for (int k = 0; k < NM; k++) o[k] = S[k];
+        }
+    }
 };
 
 // WX: waves of a workgroup side by side along x (tile = 64 WX x 4 / WX pixels); WU: frames in flight per lane
@@ -374,7 +502,9 @@ __global__ __launch_bounds__(256) void warp_accumulate_u8c3_kernel(WarpArgs a, C
                     const float v = STK_LERP(p00, p01, p10, p11);
                     if constexpr (CLIP) vr = v; else s2 = s2 + v;
                 }
-                if constexpr (CLIP) cs.add3(vb, vg, vr);
+                if constexpr (std::is_same_v<ClipState, FoldWeighted<3>>)
+                    cs.add3k(vb, vg, vr, STK_LERP(v00 ? 1.0f : 0.0f, v01 ? 1.0f : 0.0f, v10 ? 1.0f : 0.0f, v11 ? 1.0f : 0.0f));
+                else if constexpr (CLIP) cs.add3(vb, vg, vr);
             }
         }
     }
