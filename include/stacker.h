@@ -77,7 +77,8 @@ typedef struct {
 } stk_ecc_params;
 
 /* A stack of decoded frames (what read_grey_and_f32's imread produced,
- * utils.rs:132): data[0] is the reference frame. All frames share geometry. */
+ * utils.rs:132): data[0] is the reference frame. All frames of a stk_frames share this one geometry; a stack whose
+ * frames differ in size goes through stk_keypoint_match_mixed with one stk_frame_geometry per frame. */
 typedef struct {
     const void* const* data;        /* n pointers */
     int32_t n;
@@ -421,6 +422,80 @@ stk_status stk_overlap_moments(stk_ctx* ctx, const stk_frames* frames, const dou
                                int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
                                int32_t stat_step, double* moments);
 
+/* ---- normalised, coverage-aware sigma-clip and quantile stacking: an EXTENSION beyond the reference -------------
+ * The two rejection combines with the per-frame gain, offset and weight and the coverage of the weighted combine: frames
+ * are compared after each has been mapped onto frame 0's level, and a frame that does not cover a pixel is no sample of
+ * it. Samples s_i, fold order, alpha, warp, border handling and warp_subpixel_bits are the clipped combine's; kappa_i is
+ * the weighted combine's coverage weight (always the BORDER_CONSTANT one, whatever the fold's border mode); g, o are per
+ * frame and channel, w per frame (stk_frame_weight), validated as stk_weighted_stack validates them. All arithmetic is
+ * f32, each operation rounded on its own, `/` and sqrt correctly rounded, entries in fold order; max and min are C's
+ * fmaxf / fminf (a NaN operand gives the other one).
+ * Participation (one flag per pixel and entry, not per channel): entry i is a sample of the pixel iff w_i > 0 and, with
+ * coverage = 1, kappa_i == 1.0f (all taps that carry weight are inside the frame). With coverage = 0 only w_i > 0 is
+ * asked and border samples count. A partly covered sample (0 < kappa < 1) is a dimmed value that cannot be compared or
+ * ranked, so it is left out. coverage = 1 puts no condition on the border mode or value: a border tap never reaches a
+ * participating sample with non-zero weight.
+ * Normalised sample: u = s * g_i,c + o_i,c.
+ * Clip (kappa_low, kappa_high, iterations = T as in stk_clip_params):
+ *   centre pass:  sw = 0; a = 0;  for each participating u: sw = sw + w; a = a + w * u
+ *                 c = sw > 0 ? a / sw : 0;  L = -inf;  U = +inf
+ *   passes t = 1 .. T + 1:  k = 0; sw = 0; a = 0; b = 0
+ *                 for each participating u: d = u - c
+ *                     if (L <= u && u <= U) { k += 1; sw = sw + w; a = a + w * d; b = b + w * (d * d); }
+ *                 last pass: out = k > 0 ? c + a / sw : c;  counts = k;  kept_weight = sw   (per pixel and channel)
+ *                 otherwise, if k >= 3: ma = a / sw; m = c + ma; v = b / sw - ma*ma; sigma = sqrt(max(v, 0));
+ *                                       L = max(L, m - kappa_low sigma); U = min(U, m + kappa_high sigma); c = m
+ * A pixel no entry participates in gives out = 0, counts = 0, kept_weight = 0. The centre is a pass of its own (T + 2
+ * folds in all): the clipped combine's starting centre, the plain mean, counts border samples and un-normalised frames.
+ * With all weights 1 the T + 1 passes are the clipped combine's formulas; only the centre differs (a / sw against
+ * sum * (float)(1.0 / N)), so bit equality with stk_clip_stack is not promised.
+ * Quantile (quantile = q as in stk_quantile_params): with N_p the number of participating entries of the pixel and u_(k)
+ * the k-th smallest participating normalised sample of the pixel and channel (k from 0):
+ *   N_p == 0:  out = 0
+ *   else:      vi = (float)(N_p - 1) * q;  j = floor(vi);  g = vi - j;  lo = u_(j);  hi = u_(min(j + 1, N_p - 1));  d = hi - lo
+ *              out = g == 0 ? lo : (g >= 0.5 ? hi - d * (1 - g) : lo + d * g);   any participating NaN -> NaN
+ *   counts (optional, width * height int32, one per PIXEL) = N_p
+ * w enters only through w_i > 0: an order statistic of the participating samples, not a weighted quantile. With every
+ * entry participating, g = 1 and o = 0 this is stk_quantile_stack bit for bit on a finite stack.
+ * Statuses as in the forms these extend. stk_timing.finalize_ms of the whole-stack calls is the device time of the
+ * moments pass plus the combine. A multi-device context runs these calls on its first device. */
+
+/* stk_clip_stack with stk_weighted_stack's per_frame records and coverage flag. counts_or_null: width * height *
+ * channels int32; kept_weight_or_null: width * height * channels f32; both in the location of `out`. */
+stk_status stk_clip_stack_weighted(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                   int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                   const stk_clip_params* clip, const stk_frame_weight* per_frame, int32_t coverage,
+                                   stk_image_f32* out, int32_t* counts_or_null, float* kept_weight_or_null);
+/* stk_quantile_stack with the per_frame records and the coverage flag. counts_or_null: width * height int32 (N_p). */
+stk_status stk_quantile_stack_weighted(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                       int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                       const stk_quantile_params* quantile, const stk_frame_weight* per_frame, int32_t coverage,
+                                       stk_image_f32* out, int32_t* counts_or_null);
+/* The whole-stack forms: the plain call (its stats, warps and errors), the records as stk_ecc_match_weighted /
+ * stk_keypoint_match_weighted make them (weight: normalize, coverage, stat_step; weights_or_null: n weights by frame
+ * index, NULL = all 1; the moments pass and the estimator when normalize != 0), then the combine above. applied_or_null:
+ * n records by frame index, what the combine used; a dropped frame has weight 0 and gains 1, offsets 0. */
+stk_status stk_ecc_match_clipped_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
+                                          float scale_down_width, const stk_clip_params* clip, const stk_weight_params* weight,
+                                          const float* weights_or_null, stk_image_f32* out, int32_t* counts_or_null,
+                                          float* kept_weight_or_null, stk_frame_weight* applied_or_null,
+                                          stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_clipped_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                               float scale_down_width, const stk_clip_params* clip,
+                                               const stk_weight_params* weight, const float* weights_or_null, stk_image_f32* out,
+                                               int32_t* dropped, int32_t* counts_or_null, float* kept_weight_or_null,
+                                               stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
+stk_status stk_ecc_match_quantile_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
+                                           float scale_down_width, const stk_quantile_params* quantile,
+                                           const stk_weight_params* weight, const float* weights_or_null, stk_image_f32* out,
+                                           int32_t* counts_or_null, stk_frame_weight* applied_or_null,
+                                           stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_quantile_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                                float scale_down_width, const stk_quantile_params* quantile,
+                                                const stk_weight_params* weight, const float* weights_or_null, stk_image_f32* out,
+                                                int32_t* dropped, int32_t* counts_or_null, stk_frame_weight* applied_or_null,
+                                                stk_frame_stats* stats_or_null);
+
 /* ---- stage-level entry points (parity tests bind these) ------------------ */
 /* cvt_color(BGR2GRAY) on the integer image, utils.rs:136-142. out: w*h of the input depth
  * (u8 / u16 / f32), tightly packed, same location as the frame. */
@@ -443,10 +518,10 @@ stk_status stk_hybrid_match_shard(stk_ctx* ctx, const stk_frames* frames, const 
  * imgcodecs::imread(path, IMREAD_UNCHANGED) (utils.rs:110-117, 132) for binary PNM (P5 / P6, 8 or 16 bit), grey / YCbCr / CMYK
  * JPEG (libjpeg-turbo's libjpeg.so.8, OpenCV's decoder family at its default settings), PNG (libpng16.so.16: 8- and 16-bit
  * grey / RGB, palette -> BGR, 1/2/4-bit grey -> 8 bit; anything with alpha — RGBA, grey + alpha, a tRNS chunk — comes out as
- * FOUR channels B G R A, as OpenCV's decoder delivers it under IMREAD_UNCHANGED) and stripped 8/16-bit grey / RGB TIFF
- * (libtiff.so.5 / .6), the libraries loaded at run time: BGR(A) or grey rows, tightly packed, into `data` (capacity_bytes);
+ * FOUR channels B G R A, as OpenCV's decoder delivers it under IMREAD_UNCHANGED) and 8/16-bit grey / RGB TIFF, stripped or
+ * tiled (libtiff.so.5 / .6), the libraries loaded at run time: BGR(A) or grey rows, tightly packed, into `data` (capacity_bytes);
  * data == NULL only reports the geometry. ctx may be NULL. A file that is unreadable or not an image: STK_BACKEND_ERROR (the
- * reference's empty Mat + cvtColor). TIFF may be stripped or tiled, RGBA TIFF gives four channels; BMP (no library:
+ * reference's empty Mat + cvtColor). RGBA TIFF gives four channels; BMP (no library:
  * uncompressed 24-bit, 32-bit -> B G R A, 8-bit palette -> BGR or grey); still WebP (libwebp.so.7: BGR, or B G R A when the
  * bitstream has alpha). CMYK / YCCK JPEG comes out as B G R through
  * OpenCV's own conversion. Flavours no decoder here takes (planar TIFF, RLE / 1- / 4- / 16-bit BMP, animated WebP,

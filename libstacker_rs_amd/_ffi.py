@@ -121,6 +121,26 @@ SIGNATURES = {
                                       C.c_double, C.POINTER(FrameWeight), C.c_int32, C.POINTER(ImageF32), C.c_void_p]),
     "stk_overlap_moments": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_double, C.c_int32, C.c_void_p]),
+    "stk_clip_stack_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_double, C.POINTER(ClipParams), C.POINTER(FrameWeight), C.c_int32, C.POINTER(ImageF32),
+                                           C.c_void_p, C.c_void_p]),
+    "stk_quantile_stack_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                               C.c_double, C.POINTER(QuantileParams), C.POINTER(FrameWeight), C.c_int32,
+                                               C.POINTER(ImageF32), C.c_void_p]),
+    "stk_ecc_match_clipped_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float, C.POINTER(ClipParams),
+                                                  C.POINTER(WeightParams), C.c_void_p, C.POINTER(ImageF32), C.c_void_p, C.c_void_p,
+                                                  C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
+    "stk_keypoint_match_clipped_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                                       C.POINTER(ClipParams), C.POINTER(WeightParams), C.c_void_p, C.POINTER(ImageF32),
+                                                       C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.POINTER(FrameWeight),
+                                                       C.POINTER(FrameStats)]),
+    "stk_ecc_match_quantile_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float,
+                                                   C.POINTER(QuantileParams), C.POINTER(WeightParams), C.c_void_p, C.POINTER(ImageF32),
+                                                   C.c_void_p, C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
+    "stk_keypoint_match_quantile_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                                        C.POINTER(QuantileParams), C.POINTER(WeightParams), C.c_void_p,
+                                                        C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p, C.POINTER(FrameWeight),
+                                                        C.POINTER(FrameStats)]),
     "stk_grey": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p]),
     "stk_convert_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_double, C.c_void_p]),
     "stk_hybrid_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.POINTER(EccParams),

@@ -597,23 +597,7 @@ class Stacker:
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
         Md, inc = self._warps_arg(warps, include, m.n)
-        rec = (_ffi.FrameWeight * m.n)()
-        if applied is not None:
-            if len(applied) != m.n:
-                raise InvalidParams("one record per frame expected")
-            gain = [a["gain"] for a in applied]
-            offset = [a["offset"] for a in applied]
-            weights = [a["weight"] for a in applied]
-        g = np.ones((m.n, m.c), np.float32) if gain is None else np.asarray(gain, np.float32).reshape(m.n, -1)
-        o = np.zeros((m.n, m.c), np.float32) if offset is None else np.asarray(offset, np.float32).reshape(m.n, -1)
-        w = np.ones(m.n, np.float32) if weights is None else np.asarray(weights, np.float32).reshape(-1)
-        if g.shape != (m.n, m.c) or o.shape != (m.n, m.c) or w.size != m.n:
-            raise InvalidParams("gain and offset: n x channels, weights: n expected")
-        for i in range(m.n):
-            for c in range(4):
-                rec[i].gain[c] = float(g[i, c]) if c < m.c else 1.0
-                rec[i].offset[c] = float(o[i, c]) if c < m.c else 0.0
-            rec[i].weight = float(w[i])
+        rec = self._records_arg(m, gain, offset, weights, applied)
         bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
         out, img = self._out_image(m)
         cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
@@ -638,6 +622,160 @@ class Stacker:
                                                   int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), int(stat_step),
                                                   C.c_void_p(mom.ctypes.data)))
         return mom
+
+    # -- normalised, coverage-aware rejection combines (extension beyond the reference) -----------------
+    def _pixel_counts_image(self, m: _Marshalled):
+        """int32 HxW per-pixel counts placed where the output lives."""
+        if m.location == DEVICE:
+            import torch
+            cnt = torch.empty((m.h, m.w), dtype=torch.int32, device=m.torch_device)
+            return cnt, C.c_void_p(cnt.data_ptr())
+        cnt = np.empty((m.h, m.w), np.int32)
+        return cnt, C.c_void_p(cnt.ctypes.data)
+
+    def _kept_image(self, m: _Marshalled):
+        """f32 HxWxC kept-weight planes placed where the output lives."""
+        if m.location == DEVICE:
+            import torch
+            kw = torch.empty((m.h, m.w, m.c), dtype=torch.float32, device=m.torch_device)
+            return kw, C.c_void_p(kw.data_ptr())
+        kw = np.empty((m.h, m.w, m.c), np.float32)
+        return kw, C.c_void_p(kw.ctypes.data)
+
+    @staticmethod
+    def _records_arg(m: _Marshalled, gain, offset, weights, applied):
+        """n stk_frame_weight records from gain / offset (n x channels), weights (n) or another call's `applied`."""
+        rec = (_ffi.FrameWeight * m.n)()
+        if applied is not None:
+            if len(applied) != m.n:
+                raise InvalidParams("one record per frame expected")
+            gain = [a["gain"] for a in applied]
+            offset = [a["offset"] for a in applied]
+            weights = [a["weight"] for a in applied]
+        g = np.ones((m.n, m.c), np.float32) if gain is None else np.asarray(gain, np.float32).reshape(m.n, -1)
+        o = np.zeros((m.n, m.c), np.float32) if offset is None else np.asarray(offset, np.float32).reshape(m.n, -1)
+        w = np.ones(m.n, np.float32) if weights is None else np.asarray(weights, np.float32).reshape(-1)
+        if g.shape != (m.n, m.c) or o.shape != (m.n, m.c) or w.size != m.n:
+            raise InvalidParams("gain and offset: n x channels, weights: n expected")
+        for i in range(m.n):
+            for c in range(4):
+                rec[i].gain[c] = float(g[i, c]) if c < m.c else 1.0
+                rec[i].offset[c] = float(o[i, c]) if c < m.c else 0.0
+            rec[i].weight = float(w[i])
+        return rec
+
+    def clip_stack_weighted(self, files, warps, clip: Optional["SigmaClipParameters"] = None, gain=None, offset=None, weights=None,
+                            include=None, *, applied=None, coverage: bool = True, is_affine=False, border_mode=BORDER_CONSTANT,
+                            border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_counts: bool = False,
+                            return_kept_weight: bool = False):
+        """The normalised, coverage-aware clip alone over caller-held warps (stk_clip_stack_weighted): clip_stack with
+        weighted_stack's gain / offset / weights (or `applied`) and coverage. Returns the image, then the counts of kept
+        samples (return_counts) and the kept weight (return_kept_weight), both per pixel and channel."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Md, inc = self._warps_arg(warps, include, m.n)
+        rec = self._records_arg(m, gain, offset, weights, applied)
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        out, img = self._out_image(m)
+        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
+        kw, kptr = self._kept_image(m) if return_kept_weight else (None, None)
+        cp = (clip or SigmaClipParameters())._c()
+        self._check(self._lib.stk_clip_stack_weighted(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                      None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
+                                                      int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(cp), rec,
+                                                      int(coverage), C.byref(img), cptr, kptr))
+        res = (out,) + ((cnt,) if return_counts else ()) + ((kw,) if return_kept_weight else ())
+        return res if len(res) > 1 else out
+
+    def quantile_stack_weighted(self, files, warps, quantile=None, gain=None, offset=None, weights=None, include=None, *,
+                                applied=None, coverage: bool = True, is_affine=False, border_mode=BORDER_CONSTANT,
+                                border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_counts: bool = False):
+        """The normalised, coverage-aware quantile alone over caller-held warps (stk_quantile_stack_weighted). Returns the
+        image, then the per-pixel number of participating frames (return_counts, HxW)."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Md, inc = self._warps_arg(warps, include, m.n)
+        rec = self._records_arg(m, gain, offset, weights, applied)
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        out, img = self._out_image(m)
+        cnt, cptr = self._pixel_counts_image(m) if return_counts else (None, None)
+        qp = _quantile_c(quantile)
+        self._check(self._lib.stk_quantile_stack_weighted(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                          None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
+                                                          int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(qp), rec,
+                                                          int(coverage), C.byref(img), cptr))
+        return (out, cnt) if return_counts else out
+
+    def _robust_match(self, kind, combine, files, params, cparams, weight, weights, scale_down_width, return_stats, return_counts,
+                      return_kept_weight, return_applied):
+        if kind == "ecc" and isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        if combine == "clipped":
+            cnt, cptr = self._counts_image(m) if return_counts else (None, None)
+            cp = (cparams or SigmaClipParameters())._c()
+        else:
+            cnt, cptr = self._pixel_counts_image(m) if return_counts else (None, None)
+            cp = _quantile_c(cparams)
+        kw, kptr = self._kept_image(m) if return_kept_weight else (None, None)
+        wkeep, wptr = self._weights_arg(weights, m.n)
+        applied = (_ffi.FrameWeight * m.n)()
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p, wp = params._c(), (weight or WeightParameters())._c()
+        fn = getattr(self._lib, f"stk_{kind}_match_{combine}_weighted")
+        args = [self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(cp), C.byref(wp), wptr, C.byref(img)]
+        if kind == "keypoint":
+            args.append(C.byref(dropped))
+        args.append(cptr)
+        if combine == "clipped":
+            args.append(kptr)
+        self._check(fn(*args, applied, stats))
+        res = ((dropped.value,) if kind == "keypoint" else ()) + (out,) + ((cnt,) if return_counts else ()) \
+            + ((kw,) if return_kept_weight else ()) + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) \
+            + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return res if len(res) > 1 else out
+
+    def ecc_match_clipped_weighted(self, files, params: EccMatchParameters, clip: Optional["SigmaClipParameters"] = None,
+                                   weight: Optional["WeightParameters"] = None, weights=None, scale_down_width: Optional[float] = None,
+                                   return_stats: bool = False, return_counts: bool = False, return_kept_weight: bool = False,
+                                   return_applied: bool = False):
+        """ecc_match with the normalised, coverage-aware sigma clip (stk_ecc_match_clipped_weighted): the image, then the
+        counts (return_counts), the kept weight (return_kept_weight), the per-frame records used (return_applied) and the
+        stats (return_stats)."""
+        return self._robust_match("ecc", "clipped", files, params, clip, weight, weights, scale_down_width, return_stats,
+                                  return_counts, return_kept_weight, return_applied)
+
+    def keypoint_match_clipped_weighted(self, files, params: KeyPointMatchParameters, clip: Optional["SigmaClipParameters"] = None,
+                                        weight: Optional["WeightParameters"] = None, weights=None,
+                                        scale_down_width: Optional[float] = None, return_stats: bool = False,
+                                        return_counts: bool = False, return_kept_weight: bool = False, return_applied: bool = False):
+        """keypoint_match with the normalised, coverage-aware sigma clip (stk_keypoint_match_clipped_weighted):
+        (dropped, image[, counts][, kept weight][, applied][, stats])."""
+        return self._robust_match("keypoint", "clipped", files, params, clip, weight, weights, scale_down_width, return_stats,
+                                  return_counts, return_kept_weight, return_applied)
+
+    def ecc_match_quantile_weighted(self, files, params: EccMatchParameters, quantile=None,
+                                    weight: Optional["WeightParameters"] = None, weights=None, scale_down_width: Optional[float] = None,
+                                    return_stats: bool = False, return_counts: bool = False, return_applied: bool = False):
+        """ecc_match with the normalised, coverage-aware quantile (stk_ecc_match_quantile_weighted): the image, then the
+        per-pixel number of participating frames (return_counts), the records (return_applied) and the stats."""
+        return self._robust_match("ecc", "quantile", files, params, quantile, weight, weights, scale_down_width, return_stats,
+                                  return_counts, False, return_applied)
+
+    def keypoint_match_quantile_weighted(self, files, params: KeyPointMatchParameters, quantile=None,
+                                         weight: Optional["WeightParameters"] = None, weights=None,
+                                         scale_down_width: Optional[float] = None, return_stats: bool = False,
+                                         return_counts: bool = False, return_applied: bool = False):
+        """keypoint_match with the normalised, coverage-aware quantile (stk_keypoint_match_quantile_weighted):
+        (dropped, image[, counts][, applied][, stats])."""
+        return self._robust_match("keypoint", "quantile", files, params, quantile, weight, weights, scale_down_width, return_stats,
+                                  return_counts, False, return_applied)
 
     # -- shard-level (one process per GPU; frames[0] = reference frame) ------------------------------
     def ecc_match_shard(self, files, params: EccMatchParameters, add_reference: bool, sum_out,

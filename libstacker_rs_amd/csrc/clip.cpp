@@ -12,8 +12,7 @@
 
 using namespace stk;
 
-namespace {
-
+// (shared with robust.cpp: context.h)
 stk_status clip_validate(stk_ctx* ctx, const stk_clip_params* p) {
     if (!p) return fail(ctx, STK_INVALID_PARAMS, "null clip parameters");
     if (!(p->kappa_low > 0.0f) || !std::isfinite(p->kappa_low) || !(p->kappa_high > 0.0f) || !std::isfinite(p->kappa_high))
@@ -30,6 +29,8 @@ stk_status clip_check_out(stk_ctx* ctx, const stk_image_f32* out, const stk_fram
         return fail(ctx, STK_INVALID_PARAMS, "output must be tightly packed");
     return STK_OK;
 }
+
+namespace {
 
 // The clip passes over the n_frames entries of ctx->warpframes; the c plane (ctx->clip) holds the plain mean. Writes `out`
 // and `counts` (out's location) and sets stk_timing.finalize_ms to the passes' device time.

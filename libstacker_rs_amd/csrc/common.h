@@ -202,10 +202,19 @@ struct ClipArgs {
     // partial of 1 + 5 cn doubles per wave and entry
     double* partials;
     int step, reps;
+    // the weighted clip states (ClipWGeneric / ClipWU8C3, kernels_clip.hip; definition: include/stacker.h, "normalised,
+    // coverage-aware rejection"): coef / coverage as above; centre = 1: the centre pass (c = the weighted mean of the
+    // participating samples, written to the c plane; nothing is read); last pass: the kept weight sw to `kept` (optional)
+    int centre;
+    float* kept;
 };
 
 // quantile combines: samples per pixel the selection kernel takes (64 lanes of a wave x 64 keys in registers)
 constexpr int QUANTILE_MAX_SAMPLES = 4096;
+// the store mode with participation marks an entry that is no sample of a pixel with this bit pattern: a SIGNALLING NaN.
+// A sample is the result of a floating-point add, and an arithmetic result that is NaN is always a quiet one (IEEE 754;
+// the kernels run with the IEEE mode bit set), so no sample, a genuine NaN of any payload included, has these bits
+constexpr unsigned QUANTILE_ABSENT_BITS = 0x7fa00000u;
 
 // ---- kernel launchers (defined in the .hip files) -------------------------------------------
 hipError_t launch_grey(const void* bgr, int depth, int w, int h, size_t stride_bytes, void* out, hipStream_t s,
@@ -249,6 +258,14 @@ MomentsPlan moments_plan(int dw, int dh, int step);
 // ((n_frames - 1) x plan.parts() x (1 + 5 cn) doubles), then reduced in index order into moments ((n_frames - 1) x cn x 6)
 hipError_t launch_overlap_moments(const WarpArgs& a, ClipArgs c, int depth, int step, double* moments, hipStream_t s);
 hipError_t launch_quantile_store(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
+// one pass of the weighted clip (c.coef, c.coverage, c.centre, c.kept besides launch_clip_pass's fields)
+hipError_t launch_clip_pass_weighted(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
+// the store mode with participation (c.coef, c.coverage besides launch_quantile_store's fields): the normalised sample
+// u = s * g + o, QUANTILE_ABSENT_BITS for an entry that is no sample of the pixel
+hipError_t launch_quantile_store_weighted(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
+// the selection with a per-pixel rank over such a band: per column the number N_p of present keys, j and g from N_p and q,
+// the quantile (0 where N_p == 0) into out[k]; counts (optional): N_p of pixel k / cn, written for channel 0
+hipError_t launch_quantile_select_masked(const float* band, size_t m, int n, float q, int cn, float* out, int* counts, hipStream_t s);
 // per column k < m of the n x m samples of a band (frame-major: band[i * m + k]): the quantile with lo = s_(j) and the
 // fraction g (include/stacker.h), into out[k]; n <= QUANTILE_MAX_SAMPLES
 hipError_t launch_quantile_select(const float* band, size_t m, int n, int j, float g, float* out, hipStream_t s);

@@ -86,6 +86,7 @@ struct stk_ctx {
     DevBuf frames, ref, blur_tmp, templates, slots, queue, results, partials, warpframes, acc, scratch, init_warps, frameptrs;
     DevBuf clip;                  // sigma clipping (clip.cpp): the c, L and U planes
     DevBuf weighted;              // weighted combine (weighted.cpp): image, den plane, per-entry table, moments and their partials
+    DevBuf coef;                  // normalised rejection combines (robust.cpp): the per-entry gain / offset / weight table
     DevBuf quantile;              // quantile combines (quantile.cpp): a w x h x cn f32 image, then the band of samples
     stk::KeypointWorkspace* kp = nullptr;
     stk::geom::HgWorkspace* hg = nullptr;   // findHomography batch workspace (homography.cpp)
@@ -139,6 +140,21 @@ stk_status keypoint_match_single(stk_ctx* ctx, const stk_frames* frames, const s
                                  stk_image_f32* out, int32_t* dropped, stk_frame_stats* stats);
 // the frame table of a fold into ctx->warpframes (flags for a w x h destination; asynchronous: `wf` must outlive the copy)
 stk_status warp_table_upload(stk_ctx* ctx, std::vector<WarpFrame>& wf, size_t src_row_bytes, int w, int h, int is_affine);
+// shared by the combines (clip.cpp, quantile.cpp, weighted.cpp; used again by robust.cpp)
+stk_status clip_validate(stk_ctx* ctx, const stk_clip_params* p);
+stk_status clip_check_out(stk_ctx* ctx, const stk_image_f32* out, const stk_frames* f);
+stk_status quantile_validate(stk_ctx* ctx, const stk_quantile_params* p);
+stk_status quantile_check_count(stk_ctx* ctx, int n);
+size_t quantile_image_floats(int w, int h, int cn);
+size_t quantile_band_rows(const stk_ctx* ctx, int n, int w, int h, int cn);
+stk_status quantile_reserve(stk_ctx* ctx, int n, int w, int h, int cn);
+stk_status weighted_validate(stk_ctx* ctx, const stk_weight_params* p);
+stk_status weighted_check_coefs(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, int cn);
+stk::WarpArgs weighted_warp_args(stk_ctx* ctx, int n_entries, int depth, int w, int h, int cn, size_t src_row_bytes, double alpha,
+                                 int border_mode, const double* border_value, int is_affine);
+stk_status weighted_moments(stk_ctx* ctx, int n_entries, int depth, int w, int h, int cn, size_t src_row_bytes, double alpha,
+                            int border_mode, const double* border_value, int is_affine, int step, double* host, double* ms);
+void weighted_estimate(const double* m /* cn x 6 */, int cn, int mode, stk_frame_weight* e);
 stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
                           int32_t add_reference, stk_image_f32* sum, int32_t* n_added, stk_frame_stats* stats,
                           const float* seeds, double alpha, bool allow16);

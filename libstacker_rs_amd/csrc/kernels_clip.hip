@@ -133,4 +133,161 @@ hipError_t launch_clip_pass(const WarpArgs& a, const ClipArgs& c, int depth, hip
     return hipGetLastError();
 }
 
+// ---- the weighted clip: normalised, coverage-aware rejection (stk_clip_stack_weighted and the *_clipped_weighted entry
+// points; definition in include/stacker.h) ---------------------------------------------------------------------------
+// The same fold kernels, a new state. Per sample over the body above: u = s * g + o (one multiply, one add), the
+// participation flag (w > 0, and with coverage kappa == 1.0f; one per pixel and entry) folded into clip_in, the running
+// kept weight sw and two multiplies by w:
+//     pass:      d = u - c; if (participates && L <= u && u <= U) { k += 1; sw = sw + w; a = a + w*d; b = b + w*(d*d); }
+//     update:    as above with sw for k in the divisions (k >= 3 still decides whether there is an update)
+//     last pass: out = k > 0 ? c + a / sw : c; counts = k; kept = sw
+// The centre pass (ClipArgs::centre) is a mode of the same state: c = 0 makes d = u, the interval test is skipped, and the
+// epilogue writes c = sw > 0 ? a / sw : 0 — the weighted mean of the participating samples — to the c plane.
+__device__ __forceinline__ void clip_end_w(const ClipArgs& ca, size_t p, size_t o, float c, float L, float U, int k, float sw, float a, float b) {
+    if (ca.centre) {
+        ca.c[p] = sw > 0.0f ? a / sw : 0.0f;
+        return;
+    }
+    if (ca.last) {
+        ca.out[o] = k > 0 ? c + a / sw : c;
+        if (ca.counts) ca.counts[p] = k;
+        if (ca.kept) ca.kept[p] = sw;
+        return;
+    }
+    if (k >= 3) {
+        const float ma = a / sw;
+        const float m = c + ma;
+        const float v = b / sw - ma * ma;
+        const float sigma = __builtin_sqrtf(__builtin_fmaxf(v, 0.0f));
+        L = __builtin_fmaxf(L, m - ca.kappa_low * sigma);
+        U = __builtin_fminf(U, m + ca.kappa_high * sigma);
+        c = m;
+    }
+    ca.c[p] = c; ca.L[p] = L; ca.U[p] = U;
+}
+
+template <int CN>
+struct ClipWGeneric {
+    float c[CN], L[CN], U[CN], a[CN], b[CN], sw[CN];
+    int k[CN];
+    size_t p;
+    const stk_frame_weight* e;
+    int cov;
+    bool part, centre;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+        p = (size_t)y * ca.plane_stride + (size_t)x * CN;
+        const bool open = ca.first | ca.centre;
+#pragma unroll
+        for (int i = 0; i < CN; i++) {
+            c[i] = ca.centre ? 0.0f : ca.c[p + i];
+            L[i] = open ? -__builtin_inff() : ca.L[p + i];
+            U[i] = open ? __builtin_inff() : ca.U[p + i];
+            a[i] = 0.f; b[i] = 0.f; sw[i] = 0.f; k[i] = 0;
+        }
+        e = ca.coef; cov = ca.coverage; centre = ca.centre != 0; part = true;
+    }
+    __device__ __forceinline__ void entry(float kap) { part = (e->weight > 0.0f) & (cov ? kap == 1.0f : true); }
+    __device__ __forceinline__ void add(int i, float s) {
+        const float w = e->weight;
+        const float u = s * e->gain[i] + e->offset[i];
+        const float d = u - c[i];
+        const bool in = part & (centre | clip_in(u, L[i], U[i]));
+        // a sample that is out adds w = 0 times d = 0: +0 to each sum, whatever u is (two selects instead of three)
+        const float wi = in ? w : 0.0f, di = in ? d : 0.0f;
+        k[i] += in ? 1 : 0;
+        sw[i] = sw[i] + wi;
+        a[i] = a[i] + wi * di;
+        b[i] = b[i] + wi * (di * di);
+        if (i == CN - 1) e++;
+    }
+    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
+        const size_t o = (size_t)y * ca.out_stride + (size_t)x * CN;
+#pragma unroll
+        for (int i = 0; i < CN; i++) clip_end_w(ca, p + i, o + i, c[i], L[i], U[i], k[i], sw[i], a[i], b[i]);
+    }
+};
+
+// u8 BGR fast kernel's state: (B, G) as register pairs, R apart. add2 is the interior path (kappa = 1: the entry
+// participates iff w > 0), add3k the rim path with its kappa.
+struct ClipWU8C3 {
+    f32x2 c01, L01, U01, a01, b01, sw01;
+    float c2, L2, U2, a2, b2, sw2;
+    int k0, k1, k2;
+    size_t p;
+    const stk_frame_weight* e;
+    int cov;
+    bool centre;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+        p = (size_t)y * ca.plane_stride + (size_t)x * 3;
+        if (ca.centre) { c01 = f32x2{0.f, 0.f}; c2 = 0.f; }
+        else { c01 = f32x2{ca.c[p], ca.c[p + 1]}; c2 = ca.c[p + 2]; }
+        if (ca.first | ca.centre) {
+            L01 = f32x2{-__builtin_inff(), -__builtin_inff()}; L2 = -__builtin_inff();
+            U01 = f32x2{__builtin_inff(), __builtin_inff()}; U2 = __builtin_inff();
+        } else {
+            L01 = f32x2{ca.L[p], ca.L[p + 1]}; L2 = ca.L[p + 2];
+            U01 = f32x2{ca.U[p], ca.U[p + 1]}; U2 = ca.U[p + 2];
+        }
+        a01 = f32x2{0.f, 0.f}; b01 = f32x2{0.f, 0.f}; sw01 = f32x2{0.f, 0.f}; a2 = 0.f; b2 = 0.f; sw2 = 0.f;
+        k0 = k1 = k2 = 0;
+        e = ca.coef; cov = ca.coverage; centre = ca.centre != 0;
+    }
+    __device__ __forceinline__ void fold(f32x2 s01, float s2, bool part) {
+        const float w = e->weight;
+        const f32x2 u01 = s01 * f32x2{e->gain[0], e->gain[1]} + f32x2{e->offset[0], e->offset[1]};
+        const f32x2 d = u01 - c01;
+        const bool i0 = part & (centre | clip_in(u01.x, L01.x, U01.x)), i1 = part & (centre | clip_in(u01.y, L01.y, U01.y));
+        // a sample that is out adds w = 0 times d = 0: +0 to each sum, whatever u is (two selects per channel instead of
+        // three, and the sums stay packed)
+        const f32x2 wi = {i0 ? w : 0.0f, i1 ? w : 0.0f}, di = {i0 ? d.x : 0.0f, i1 ? d.y : 0.0f};
+        k0 += i0 ? 1 : 0; k1 += i1 ? 1 : 0;
+        sw01 = sw01 + wi;
+        a01 = a01 + wi * di;
+        b01 = b01 + wi * (di * di);
+        const float u2 = s2 * e->gain[2] + e->offset[2];
+        const float d2 = u2 - c2;
+        const bool i2 = part & (centre | clip_in(u2, L2, U2));
+        const float w2 = i2 ? w : 0.0f, dd2 = i2 ? d2 : 0.0f;
+        k2 += i2 ? 1 : 0;
+        sw2 = sw2 + w2;
+        a2 = a2 + w2 * dd2;
+        b2 = b2 + w2 * (dd2 * dd2);
+        e++;
+    }
+    __device__ __forceinline__ void add2(f32x2 s01, float s2) { fold(s01, s2, e->weight > 0.0f); }
+    __device__ __forceinline__ void add3k(float s0, float s1, float s2, float kap) {
+        fold(f32x2{s0, s1}, s2, (e->weight > 0.0f) & (cov ? kap == 1.0f : true));
+    }
+    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
+        const size_t o = (size_t)y * ca.out_stride + (size_t)x * 3;
+        clip_end_w(ca, p, o, c01.x, L01.x, U01.x, k0, sw01.x, a01.x, b01.x);
+        clip_end_w(ca, p + 1, o + 1, c01.y, L01.y, U01.y, k1, sw01.y, a01.y, b01.y);
+        clip_end_w(ca, p + 2, o + 2, c2, L2, U2, k2, sw2, a2, b2);
+    }
+};
+
+hipError_t launch_clip_pass_weighted(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
+    if (a.n_frames <= 0 || !c.coef) return hipErrorInvalidValue;
+    if (warp_u8c3_applies(a, depth)) {
+        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
+        if (a.is_affine) warp_accumulate_u8c3_kernel<true, 1, 4, true, ClipWU8C3><<<g, 256, 0, s>>>(a, c);
+        else warp_accumulate_u8c3_kernel<false, 1, 4, true, ClipWU8C3><<<g, 256, 0, s>>>(a, c);
+        return hipGetLastError();
+    }
+    const dim3 grid((a.dw + 63) / 64, (a.dh + 3) / 4);
+#define STK_CLIPW_CASE(T, CN) warp_accumulate_kernel<T, CN, true, ClipWGeneric<CN>><<<grid, 256, 0, s>>>(a, c)
+    if (depth == 8 && a.cn == 3) STK_CLIPW_CASE(uint8_t, 3);
+    else if (depth == 8 && a.cn == 1) STK_CLIPW_CASE(uint8_t, 1);
+    else if (depth == 8 && a.cn == 4) STK_CLIPW_CASE(uint8_t, 4);
+    else if (depth == 16 && a.cn == 3) STK_CLIPW_CASE(uint16_t, 3);
+    else if (depth == 16 && a.cn == 1) STK_CLIPW_CASE(uint16_t, 1);
+    else if (depth == 16 && a.cn == 4) STK_CLIPW_CASE(uint16_t, 4);
+    else if (depth == 32 && a.cn == 3) STK_CLIPW_CASE(float, 3);
+    else if (depth == 32 && a.cn == 1) STK_CLIPW_CASE(float, 1);
+    else if (depth == 32 && a.cn == 4) STK_CLIPW_CASE(float, 4);
+    else return hipErrorInvalidValue;
+#undef STK_CLIPW_CASE
+    return hipGetLastError();
+}
+
 }  // namespace stk

@@ -171,4 +171,154 @@ hipError_t launch_quantile_store(const WarpArgs& a, const ClipArgs& c, int depth
     return hipGetLastError();
 }
 
+// ---- the quantile with participation (stk_quantile_stack_weighted and the *_quantile_weighted entry points) ---------
+// The band holds normalised samples and QUANTILE_ABSENT_BITS (a signalling NaN, which no sample is) for an entry that is
+// no sample of the pixel (FoldStoreW, warp_body.h). Keys: an absent entry takes the padding key (all ones), which no
+// bisection candidate with a clear bit counts — except the last one below the NaN key, which is why NaN gets the key
+// below it and is counted like a sample: it ranks last, as in the plain kernel, and makes the output NaN. N_p is one more
+// count round (keys below the padding key); j, g and the bisection threshold j + 1 are per-lane values.
+struct QuantileSelectMaskedArgs {
+    const float* band;       // n x m samples, frame-major
+    float* out;              // m outputs
+    int* counts;             // m / cn pixel counts N_p (optional)
+    size_t m;
+    int n;
+    int log2_splits;
+    int cn;
+    float q;
+};
+
+__device__ __forceinline__ uint32_t quantile_key_masked(float v) {
+    const uint32_t u = __float_as_uint(v);
+    if (u == QUANTILE_ABSENT_BITS) return 0xffffffffu;
+    if (v != v) return 0xfffffffeu;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+template <int G>
+__global__ __launch_bounds__(QSEL_THREADS) void quantile_select_masked_kernel(QuantileSelectMaskedArgs a) {
+    extern __shared__ uint4 keys4[];                    // [G][256], as in quantile_select_kernel
+    constexpr int KPT = 4 * G;
+    const int ls = a.log2_splits, S = 1 << ls, Tw = 64 >> ls, T = QSEL_THREADS >> ls;
+    const int tid = threadIdx.x;
+    {
+        const int c = tid & (T - 1), p = tid >> (8 - ls);
+        const size_t col = (size_t)blockIdx.x * T + c;
+        const int owner = (c / Tw) * 64 + (c % Tw);
+        for (int q = p; q < S * G; q += S) {
+            uint32_t k[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int i = q * 4 + e;
+                k[e] = (col < a.m && i < a.n) ? quantile_key_masked(a.band[(size_t)i * a.m + col]) : 0xffffffffu;
+            }
+            keys4[(q % G) * QSEL_THREADS + owner + (q / G) * Tw] = uint4{k[0], k[1], k[2], k[3]};
+        }
+    }
+    __syncthreads();
+    const int lane = tid & 63, s = lane / Tw, t = (tid >> 6) * Tw + (lane % Tw);
+    const size_t col = (size_t)blockIdx.x * T + t;
+    uint32_t key[KPT];
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        const uint4 v = keys4[g * QSEL_THREADS + tid];
+        key[4 * g] = v.x; key[4 * g + 1] = v.y; key[4 * g + 2] = v.z; key[4 * g + 3] = v.w;
+    }
+    // N_p: the keys below the padding key; NaN samples: the key just below it
+    uint32_t np = 0, nan = 0;
+#pragma unroll
+    for (int e = 0; e < KPT; e++) { np += key[e] != 0xffffffffu; nan += key[e] == 0xfffffffeu; }
+    np = qsel_sum(np, Tw);
+    nan = qsel_sum(nan, Tw);
+    // j and g of this pixel-channel, in f32, each operation rounded on its own (N_p == 0: unused)
+    const float vi = (float)((int)np - 1) * a.q;
+    const float jf = __builtin_floorf(vi);
+    const float gq = vi - jf;
+    const uint32_t need = np ? (uint32_t)(int)jf + 1 : 1;
+
+    uint32_t lo = 0;
+    for (int b = 31; b >= 0; b--) {
+        const uint32_t cand = lo | ((1u << b) - 1u);
+        uint32_t c0 = 0, c1 = 0;
+#pragma unroll
+        for (int e = 0; e < KPT; e += 2) { c0 += key[e] <= cand; c1 += key[e + 1] <= cand; }
+        if (qsel_sum(c0 + c1, Tw) < need) lo |= 1u << b;
+    }
+    // s_(j+1), used where g != 0 (then j + 1 <= N_p - 1: a present key above or equal exists)
+    uint32_t hi;
+    {
+        uint32_t c = 0, above = 0xffffffffu;
+#pragma unroll
+        for (int e = 0; e < KPT; e++) {
+            c += key[e] <= lo;
+            above = min(above, key[e] > lo ? key[e] : 0xffffffffu);
+        }
+        c = qsel_sum(c, Tw);
+        above = qsel_min(above, Tw);
+        hi = c >= need + 1 ? lo : above;
+    }
+    if (s != 0 || col >= a.m) return;
+    float r;
+    if (np == 0) r = 0.0f;
+    else if (nan) r = __builtin_nanf("");
+    else {
+        const float l = quantile_value(lo);
+        if (gq == 0.0f) r = l;
+        else {
+            const float h = quantile_value(hi), d = h - l;
+            r = gq >= 0.5f ? h - d * (1.0f - gq) : l + d * gq;
+        }
+    }
+    a.out[col] = r;
+    if (a.counts && col % (size_t)a.cn == 0) a.counts[col / (size_t)a.cn] = (int)np;
+}
+
+hipError_t launch_quantile_select_masked(const float* band, size_t m, int n, float q, int cn, float* out, int* counts, hipStream_t s) {
+    if (n < 1 || n > QUANTILE_MAX_SAMPLES || m == 0 || cn < 1 || m % (size_t)cn != 0) return hipErrorInvalidValue;
+    QuantileSelectMaskedArgs a{};
+    a.band = band; a.out = out; a.counts = counts; a.m = m; a.n = n; a.cn = cn; a.q = q;
+    // the plain selection's split of a pixel-channel's keys over lanes
+    const int groups = (n + 3) / 4;
+    int ls = 0;
+    while (ls < 6 && (groups + (1 << ls) - 1) >> ls > 8) ls++;
+    const int per = (groups + (1 << ls) - 1) >> ls;
+    const int G = per <= 1 ? 1 : per <= 2 ? 2 : per <= 4 ? 4 : per <= 8 ? 8 : 16;
+    a.log2_splits = ls;
+    const int T = QSEL_THREADS >> ls;
+    const dim3 grid((unsigned)((m + T - 1) / T));
+    const size_t lds = (size_t)QSEL_THREADS * G * sizeof(uint4);
+    switch (G) {
+        case 1: quantile_select_masked_kernel<1><<<grid, QSEL_THREADS, lds, s>>>(a); break;
+        case 2: quantile_select_masked_kernel<2><<<grid, QSEL_THREADS, lds, s>>>(a); break;
+        case 4: quantile_select_masked_kernel<4><<<grid, QSEL_THREADS, lds, s>>>(a); break;
+        case 8: quantile_select_masked_kernel<8><<<grid, QSEL_THREADS, lds, s>>>(a); break;
+        default: quantile_select_masked_kernel<16><<<grid, QSEL_THREADS, lds, s>>>(a); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_quantile_store_weighted(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
+    if (a.n_frames <= 0 || c.band_rows <= 0 || a.dh != c.y0 + c.band_rows || !c.coef) return hipErrorInvalidValue;
+    if (warp_u8c3_applies(a, depth)) {
+        const dim3 g((a.dw + 63) / 64, (c.band_rows + 3) / 4);
+        if (a.is_affine) warp_accumulate_u8c3_kernel<true, 1, 4, true, FoldStoreW<3>><<<g, 256, 0, s>>>(a, c);
+        else warp_accumulate_u8c3_kernel<false, 1, 4, true, FoldStoreW<3>><<<g, 256, 0, s>>>(a, c);
+        return hipGetLastError();
+    }
+    const dim3 grid((a.dw + 63) / 64, (c.band_rows + 3) / 4);
+#define STK_STOREW_CASE(T, CN) warp_accumulate_kernel<T, CN, true, FoldStoreW<CN>><<<grid, 256, 0, s>>>(a, c)
+    if (depth == 8 && a.cn == 3) STK_STOREW_CASE(uint8_t, 3);
+    else if (depth == 8 && a.cn == 1) STK_STOREW_CASE(uint8_t, 1);
+    else if (depth == 8 && a.cn == 4) STK_STOREW_CASE(uint8_t, 4);
+    else if (depth == 16 && a.cn == 3) STK_STOREW_CASE(uint16_t, 3);
+    else if (depth == 16 && a.cn == 1) STK_STOREW_CASE(uint16_t, 1);
+    else if (depth == 16 && a.cn == 4) STK_STOREW_CASE(uint16_t, 4);
+    else if (depth == 32 && a.cn == 3) STK_STOREW_CASE(float, 3);
+    else if (depth == 32 && a.cn == 1) STK_STOREW_CASE(float, 1);
+    else if (depth == 32 && a.cn == 4) STK_STOREW_CASE(float, 4);
+    else return hipErrorInvalidValue;
+#undef STK_STOREW_CASE
+    return hipGetLastError();
+}
+
 }  // namespace stk

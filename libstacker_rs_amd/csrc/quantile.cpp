@@ -18,6 +18,9 @@ namespace {
 
 constexpr size_t QUANTILE_BAND_BYTES = (size_t)4 << 30;
 
+}  // namespace
+
+// (the checks and the band geometry are shared with robust.cpp: context.h)
 stk_status quantile_validate(stk_ctx* ctx, const stk_quantile_params* p) {
     if (!p) return fail(ctx, STK_INVALID_PARAMS, "null quantile parameters");
     if (!(p->quantile >= 0.0f && p->quantile <= 1.0f))
@@ -57,6 +60,8 @@ stk_status quantile_reserve(stk_ctx* ctx, int n, int w, int h, int cn) {
     HIP_TRY(ctx->quantile.reserve((quantile_image_floats(w, h, cn) + R * n * w * cn) * sizeof(float)));
     return STK_OK;
 }
+
+namespace {
 
 // The combine over the n_frames entries of ctx->warpframes (uploaded for the w x h destination): per band a store launch,
 // then a selection launch into `out` (device) or the staging image (host, one copy back at the end). Sets

@@ -1,0 +1,359 @@
+// robust.cpp — normalised, coverage-aware rejection: stk_clip_stack_weighted, stk_quantile_stack_weighted and the
+// *_clipped_weighted / *_quantile_weighted whole-stack forms (an extension beyond the reference; definition in
+// include/stacker.h, kernels in kernels_clip.hip and kernels_quantile.hip).
+// The two rejection combines with the per-entry gain / offset / weight records and the coverage flag of the weighted
+// mean: an entry is a sample of a pixel only if its weight is > 0 and (coverage = 1) the frame covers the pixel, and the
+// samples are compared after each frame has been mapped onto frame 0's level. The workspaces are the plain combines'
+// (ctx->clip: the c, L and U planes; ctx->quantile: an image, then the band); the record table lives in ctx->coef. The
+// whole-stack forms run the plain call first, like clip.cpp, then the moments pass and the estimator of weighted.cpp
+// (both unchanged) when normalize != 0, then the combine.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "context.h"
+
+using namespace stk;
+
+namespace {
+
+stk_status robust_check_border(stk_ctx* ctx, int border_mode, int coverage) {
+    if (border_mode < 0 || border_mode > 4)
+        return fail(ctx, border_mode == STK_BORDER_TRANSPARENT ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS,
+                    "border mode not supported (BORDER_TRANSPARENT leaves the reference's output uninitialised)");
+    if (coverage < 0 || coverage > 1) return fail(ctx, STK_INVALID_PARAMS, "weighted: coverage must be 0 or 1");
+    return STK_OK;
+}
+
+// the record table into ctx->coef (asynchronous: `coef` must outlive the copy)
+stk_status coef_upload(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef) {
+    HIP_TRY(ctx->coef.reserve(coef.size() * sizeof(stk_frame_weight)));
+    HIP_TRY(hipMemcpyAsync(ctx->coef.p, coef.data(), coef.size() * sizeof(stk_frame_weight), hipMemcpyHostToDevice, ctx->stream));
+    return STK_OK;
+}
+
+// The weighted clip over the entries of ctx->warpframes with the records `coef`: the centre pass, then iterations + 1
+// passes. Writes `out`, `counts` and `kept` (out's location); adds its device time to *ms.
+stk_status clip_passes_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, int depth, int w, int h, int cn,
+                                size_t src_row_bytes, double alpha, int border_mode, const double* border_value, int is_affine,
+                                int coverage, const stk_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms) {
+    const size_t nel = (size_t)w * h * cn;
+    HIP_TRY(ctx->clip.reserve(3 * nel * sizeof(float)));
+    float* c = ctx->clip.as<float>();
+    const WarpArgs a = weighted_warp_args(ctx, (int)coef.size(), depth, w, h, cn, src_row_bytes, alpha, border_mode, border_value, is_affine);
+    stk_status st = coef_upload(ctx, coef);
+    if (st) return st;
+    const bool host = out->location != STK_DEVICE;
+    ClipArgs ca{};
+    ca.c = c; ca.L = c + nel; ca.U = c + 2 * nel;
+    ca.plane_stride = (size_t)w * cn;
+    // a host output goes through the planes themselves: each thread reads its c, L, U before it writes out / counts / kept
+    ca.out = host ? c : out->data;
+    ca.out_stride = (size_t)w * cn;
+    ca.counts = counts ? (host ? (int*)ca.L : counts) : nullptr;
+    ca.kept = kept ? (host ? ca.U : kept) : nullptr;
+    ca.kappa_low = p->kappa_low; ca.kappa_high = p->kappa_high;
+    ca.coef = ctx->coef.as<stk_frame_weight>();
+    ca.coverage = coverage;
+    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    ca.centre = 1; ca.first = 1; ca.last = 0;
+    HIP_TRY(launch_clip_pass_weighted(a, ca, depth, ctx->stream));
+    ca.centre = 0;
+    for (int t = 1; t <= p->iterations + 1; t++) {
+        ca.first = t == 1;
+        ca.last = t == p->iterations + 1;
+        HIP_TRY(launch_clip_pass_weighted(a, ca, depth, ctx->stream));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+    if (host) {
+        HIP_TRY(hipMemcpyAsync(out->data, c, nel * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (counts) HIP_TRY(hipMemcpyAsync(counts, ca.L, nel * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (kept) HIP_TRY(hipMemcpyAsync(kept, ca.U, nel * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
+    return STK_OK;
+}
+
+// The quantile with participation over the entries of ctx->warpframes: per band a store launch (normalised samples and
+// absent marks), then the selection with a per-pixel rank. `counts` (w x h, out's location) is optional.
+stk_status quantile_bands_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, int depth, int w, int h, int cn,
+                                   size_t src_row_bytes, double alpha, int border_mode, const double* border_value, int is_affine,
+                                   int coverage, const stk_quantile_params* p, stk_image_f32* out, int32_t* counts, double* ms) {
+    const int n_entries = (int)coef.size();
+    stk_status st = quantile_check_count(ctx, n_entries);
+    if (st) return st;
+    const bool host = out->location != STK_DEVICE;
+    const size_t R = quantile_band_rows(ctx, n_entries, w, h, cn), row = (size_t)w * cn;
+    // the workspace: the image, the band, and behind it the staging copy of a host caller's counts
+    const size_t img_floats = quantile_image_floats(w, h, cn), band_floats = (R * n_entries * row + 63) & ~(size_t)63;
+    HIP_TRY(ctx->quantile.reserve((img_floats + band_floats + (host && counts ? (size_t)w * h : 0)) * sizeof(float)));
+    float* img = ctx->quantile.as<float>();
+    float* band = img + img_floats;
+    float* dst = host ? img : out->data;
+    int* cdst = counts ? (host ? (int*)(band + band_floats) : counts) : nullptr;
+    WarpArgs a = weighted_warp_args(ctx, n_entries, depth, w, h, cn, src_row_bytes, alpha, border_mode, border_value, is_affine);
+    if ((st = coef_upload(ctx, coef))) return st;
+    ClipArgs ca{};
+    ca.band = band;
+    ca.plane_stride = row;
+    ca.coef = ctx->coef.as<stk_frame_weight>();
+    ca.coverage = coverage;
+    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    for (size_t y0 = 0; y0 < (size_t)h; y0 += R) {
+        const size_t rows = std::min(R, (size_t)h - y0);
+        ca.y0 = (int)y0; ca.band_rows = (int)rows;
+        a.dh = (int)(y0 + rows);
+        HIP_TRY(launch_quantile_store_weighted(a, ca, depth, ctx->stream));
+        HIP_TRY(launch_quantile_select_masked(band, rows * row, n_entries, p->quantile, cn, dst + y0 * row,
+                                              cdst ? cdst + y0 * (size_t)w : nullptr, ctx->stream));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+    if (host) {
+        HIP_TRY(hipMemcpyAsync(out->data, img, (size_t)h * row * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (counts) HIP_TRY(hipMemcpyAsync(counts, cdst, (size_t)w * h * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
+    return STK_OK;
+}
+
+// the caller-held-warps forms: argument checks, the records of the included frames, the frame table
+stk_status robust_table(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int is_affine,
+                        const stk_frame_weight* per_frame, const char* what, std::vector<stk_frame_weight>& coef) {
+    if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
+    if (!per_frame) return fail(ctx, STK_INVALID_PARAMS, "null per-frame records");
+    const int n = frames->n, w = frames->width, h = frames->height;
+    std::vector<int> entry_frame;
+    for (int i = 0; i < n; i++) if (!include || include[i]) { entry_frame.push_back(i); coef.push_back(per_frame[i]); }
+    if (coef.empty()) return fail(ctx, STK_INVALID_PARAMS, std::string(what) + ": no frame included");
+    stk_status st = weighted_check_coefs(ctx, coef, frames->channels);
+    if (st) return st;
+    (void)hipSetDevice(ctx->device);
+    timing_begin(ctx);
+    std::vector<const void*> dev;
+    if ((st = resolve_frames(ctx, frames, dev))) return st;
+    std::vector<WarpFrame> wf(entry_frame.size());
+    for (size_t k = 0; k < entry_frame.size(); k++) make_warp_frame(wf[k], dev[entry_frame[k]], M + 9 * (size_t)entry_frame[k], is_affine);
+    if ((st = warp_table_upload(ctx, wf, frame_row_bytes(frames), w, h, is_affine))) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));       // `wf` leaves scope
+    return STK_OK;
+}
+
+// the whole-stack forms: the frame table of the kept frames (entry 0 = frame 0 under the identity) from the plain call's
+// stats, as clip.cpp builds it; `keypoint`: frames with a non-zero status are no entries
+stk_status robust_stack_table(stk_ctx* ctx, const stk_frames* frames, const stk_frame_stats* stats, bool keypoint, int is_affine,
+                              std::vector<int>& entry_frame) {
+    const int n = frames->n;
+    std::vector<const void*> dev;
+    resident_frames(ctx, frames, dev);
+    std::vector<WarpFrame> wf;
+    wf.reserve(n);
+    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int i = 0; i < n; i++) {
+        if (i > 0 && keypoint && stats[i].status != 0) continue;
+        wf.emplace_back();
+        make_warp_frame(wf.back(), dev[i], i == 0 ? I3 : stats[i].warp, is_affine);
+        entry_frame.push_back(i);
+    }
+    stk_status st = warp_table_upload(ctx, wf, frame_row_bytes(frames), frames->width, frames->height, is_affine);
+    if (st) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));       // `wf` leaves scope
+    return STK_OK;
+}
+
+// the records of the table's entries, as stk_*_match_weighted makes them: the moments pass and the estimator when
+// normalize != 0, the caller's weights by frame index; `applied` by frame index (a dropped frame: weight 0, gains 1)
+stk_status robust_coefs(stk_ctx* ctx, const stk_frames* frames, const std::vector<int>& entry_frame, int depth, int border_mode,
+                        const double* border_value, int is_affine, const stk_weight_params* p, const float* weights,
+                        std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms) {
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    const int ne = (int)entry_frame.size();
+    coef.resize(ne);
+    std::vector<double> mom((size_t)std::max(ne - 1, 0) * cn * 6);
+    if (p->normalize != 0 && ne > 1) {
+        const int step = p->stat_step ? p->stat_step : 4;
+        stk_status st = weighted_moments(ctx, ne, depth, w, h, cn, frame_row_bytes(frames), 1.0 / 255.0, border_mode, border_value,
+                                         is_affine, step, mom.data(), ms);
+        if (st) return st;
+    }
+    for (int k = 0; k < ne; k++) {
+        if (k == 0) weighted_estimate(nullptr, cn, 0, &coef[k]);
+        else weighted_estimate(mom.data() + (size_t)(k - 1) * cn * 6, cn, p->normalize, &coef[k]);
+        coef[k].weight = weights ? weights[entry_frame[k]] : 1.0f;
+    }
+    stk_status st = weighted_check_coefs(ctx, coef, cn);
+    if (st) return st;
+    if (applied) {
+        for (int i = 0; i < n; i++) { weighted_estimate(nullptr, cn, 0, &applied[i]); applied[i].weight = 0.0f; }
+        for (int k = 0; k < ne; k++) applied[entry_frame[k]] = coef[k];
+    }
+    return STK_OK;
+}
+
+struct RobustCombine {
+    const stk_clip_params* clip = nullptr;            // exactly one of the two
+    const stk_quantile_params* quantile = nullptr;
+    int32_t* counts = nullptr;
+    float* kept = nullptr;
+};
+
+stk_status robust_validate(stk_ctx* ctx, const RobustCombine& rc, const stk_weight_params* weight, const stk_frames* frames,
+                           const stk_image_f32* out) {
+    stk_status st = rc.clip ? clip_validate(ctx, rc.clip) : quantile_validate(ctx, rc.quantile);
+    if (st) return st;
+    if ((st = weighted_validate(ctx, weight))) return st;
+    if ((st = check_frames(ctx, frames, true))) return st;
+    if ((st = clip_check_out(ctx, out, frames))) return st;
+    if (!rc.clip && (st = quantile_check_count(ctx, frames->n))) return st;
+    return STK_OK;
+}
+
+// the tail of the whole-stack forms, after the plain call: table, records, combine; finalize_ms = moments + combine
+stk_status robust_finish(stk_ctx* ctx, const stk_frames* frames, const stk_frame_stats* stats, bool keypoint, int depth, int border_mode,
+                         const double* border_value, int is_affine, const stk_weight_params* weight, const float* weights,
+                         const RobustCombine& rc, stk_image_f32* out, stk_frame_weight* applied) {
+    const int w = frames->width, h = frames->height, cn = frames->channels;
+    const stk_timing keep = ctx->timing;
+    std::vector<int> entry_frame;
+    std::vector<stk_frame_weight> coef;
+    double ms = 0.0;
+    stk_status st = robust_stack_table(ctx, frames, stats, keypoint, is_affine, entry_frame);
+    if (!st) st = robust_coefs(ctx, frames, entry_frame, depth, border_mode, border_value, is_affine, weight, weights, coef, applied, &ms);
+    const size_t rb = frame_row_bytes(frames);
+    if (!st) {
+        if (rc.clip)
+            st = clip_passes_weighted(ctx, coef, depth, w, h, cn, rb, 1.0 / 255.0, border_mode, border_value, is_affine, weight->coverage,
+                                      rc.clip, out, rc.counts, rc.kept, &ms);
+        else
+            st = quantile_bands_weighted(ctx, coef, depth, w, h, cn, rb, 1.0 / 255.0, border_mode, border_value, is_affine,
+                                         weight->coverage, rc.quantile, out, rc.counts, &ms);
+    }
+    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : ms;
+    return st;
+}
+
+stk_status robust_ecc(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                      const stk_weight_params* weight, const float* weights, const RobustCombine& rc, stk_image_f32* out,
+                      stk_frame_weight* applied, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    stk_status st = robust_validate(ctx, rc, weight, frames, out);
+    if (st) return st;
+    (void)hipSetDevice(ctx->device);
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    std::vector<stk_frame_stats> own;
+    if (!stats) { own.resize(n); stats = own.data(); }
+    // the plain call, on this context's own device, its mean into the combine's workspace image (unused)
+    if (rc.clip) HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
+    else if ((st = quantile_reserve(ctx, 0, w, h, cn))) return st;
+    stk_image_f32 mimg{rc.clip ? ctx->clip.as<float>() : ctx->quantile.as<float>(), w, h, cn, STK_DEVICE, 0};
+    if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
+    const int is_affine = params->motion_type != STK_MOTION_HOMOGRAPHY;
+    return robust_finish(ctx, frames, stats, false, frames->depth, STK_BORDER_CONSTANT, nullptr, is_affine, weight, weights, rc, out, applied);
+}
+
+stk_status robust_keypoint(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,
+                           const stk_weight_params* weight, const float* weights, const RobustCombine& rc, stk_image_f32* out,
+                           int32_t* dropped, stk_frame_weight* applied, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    stk_status st = robust_validate(ctx, rc, weight, frames, out);
+    if (st) return st;
+    if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
+    (void)hipSetDevice(ctx->device);
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    std::vector<stk_frame_stats> own;
+    if (!stats) { own.resize(n); stats = own.data(); }
+    if (rc.clip) HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
+    else if ((st = quantile_reserve(ctx, 0, w, h, cn))) return st;
+    stk_image_f32 mimg{rc.clip ? ctx->clip.as<float>() : ctx->quantile.as<float>(), w, h, cn, STK_DEVICE, 0};
+    if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
+    return robust_finish(ctx, frames, stats, true, 8, params->border_mode, params->border_value, 0, weight, weights, rc, out, applied);
+}
+
+}  // namespace
+
+extern "C" {
+
+stk_status stk_clip_stack_weighted(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                                   int32_t border_mode, const double* border_value, double alpha, const stk_clip_params* clip,
+                                   const stk_frame_weight* per_frame, int32_t coverage, stk_image_f32* out, int32_t* counts,
+                                   float* kept_weight) {
+    stk_status st = check_frames(ctx, frames, false);
+    if (st) return st;
+    if ((st = robust_check_border(ctx, border_mode, coverage))) return st;
+    if ((st = clip_validate(ctx, clip))) return st;
+    if ((st = clip_check_out(ctx, out, frames))) return st;
+    std::vector<stk_frame_weight> coef;
+    if ((st = robust_table(ctx, frames, M, include, is_affine, per_frame, "sigma clipping", coef))) return st;
+    double ms = 0.0;
+    st = clip_passes_weighted(ctx, coef, frames->depth, frames->width, frames->height, frames->channels, frame_row_bytes(frames), alpha,
+                              border_mode, border_value, is_affine, coverage, clip, out, counts, kept_weight, &ms);
+    ctx->timing.finalize_ms = st ? 0.0 : ms;
+    return st;
+}
+
+stk_status stk_quantile_stack_weighted(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include,
+                                       int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                       const stk_quantile_params* quantile, const stk_frame_weight* per_frame, int32_t coverage,
+                                       stk_image_f32* out, int32_t* counts) {
+    stk_status st = check_frames(ctx, frames, false);
+    if (st) return st;
+    if ((st = robust_check_border(ctx, border_mode, coverage))) return st;
+    if ((st = quantile_validate(ctx, quantile))) return st;
+    if ((st = clip_check_out(ctx, out, frames))) return st;
+    int n_in = 0;
+    for (int i = 0; i < frames->n; i++) n_in += (!include || include[i]) ? 1 : 0;
+    if ((st = quantile_check_count(ctx, n_in))) return st;
+    std::vector<stk_frame_weight> coef;
+    if ((st = robust_table(ctx, frames, M, include, is_affine, per_frame, "quantile", coef))) return st;
+    double ms = 0.0;
+    st = quantile_bands_weighted(ctx, coef, frames->depth, frames->width, frames->height, frames->channels, frame_row_bytes(frames), alpha,
+                                 border_mode, border_value, is_affine, coverage, quantile, out, counts, &ms);
+    ctx->timing.finalize_ms = st ? 0.0 : ms;
+    return st;
+}
+
+stk_status stk_ecc_match_clipped_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                          const stk_clip_params* clip, const stk_weight_params* weight, const float* weights,
+                                          stk_image_f32* out, int32_t* counts, float* kept_weight, stk_frame_weight* applied,
+                                          stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    if (!clip) return fail(ctx, STK_INVALID_PARAMS, "null clip parameters");
+    RobustCombine rc;
+    rc.clip = clip; rc.counts = counts; rc.kept = kept_weight;
+    return robust_ecc(ctx, frames, params, scale_down_width, weight, weights, rc, out, applied, stats);
+}
+
+stk_status stk_keypoint_match_clipped_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                               float scale_down_width, const stk_clip_params* clip, const stk_weight_params* weight,
+                                               const float* weights, stk_image_f32* out, int32_t* dropped, int32_t* counts,
+                                               float* kept_weight, stk_frame_weight* applied, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    if (!clip) return fail(ctx, STK_INVALID_PARAMS, "null clip parameters");
+    RobustCombine rc;
+    rc.clip = clip; rc.counts = counts; rc.kept = kept_weight;
+    return robust_keypoint(ctx, frames, params, scale_down_width, weight, weights, rc, out, dropped, applied, stats);
+}
+
+stk_status stk_ecc_match_quantile_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                           const stk_quantile_params* quantile, const stk_weight_params* weight, const float* weights,
+                                           stk_image_f32* out, int32_t* counts, stk_frame_weight* applied, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    if (!quantile) return fail(ctx, STK_INVALID_PARAMS, "null quantile parameters");
+    RobustCombine rc;
+    rc.quantile = quantile; rc.counts = counts;
+    return robust_ecc(ctx, frames, params, scale_down_width, weight, weights, rc, out, applied, stats);
+}
+
+stk_status stk_keypoint_match_quantile_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                                float scale_down_width, const stk_quantile_params* quantile,
+                                                const stk_weight_params* weight, const float* weights, stk_image_f32* out,
+                                                int32_t* dropped, int32_t* counts, stk_frame_weight* applied, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    if (!quantile) return fail(ctx, STK_INVALID_PARAMS, "null quantile parameters");
+    RobustCombine rc;
+    rc.quantile = quantile; rc.counts = counts;
+    return robust_keypoint(ctx, frames, params, scale_down_width, weight, weights, rc, out, dropped, applied, stats);
+}
+
+}  // extern "C"

@@ -93,7 +93,7 @@ void stk_destroy(stk_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (DevBuf* b : {&ctx->frames, &ctx->ref, &ctx->blur_tmp, &ctx->templates, &ctx->slots, &ctx->queue, &ctx->results,
                       &ctx->partials, &ctx->warpframes, &ctx->acc, &ctx->scratch, &ctx->init_warps, &ctx->frameptrs, &ctx->clip,
-                      &ctx->quantile, &ctx->weighted})
+                      &ctx->quantile, &ctx->weighted, &ctx->coef})
         b->release();
     keypoint_workspace_destroy(ctx->kp);
     geom::hg_workspace_destroy(ctx->hg);

@@ -15,6 +15,8 @@
 // an all-ones frame), which the rim paths compute and the u8 fast kernel's interior path knows to be 1. The generic kernel
 // has a fifth mode, moments (FoldMoments<CN>): the overlap moments of entry 1 + blockIdx.z against entry 0 over the
 // stepped pixels, a thread walking ClipArgs::reps stepped rows before its wave reduces.
+// The normalised, coverage-aware rejection combines add two states that take kappa through the same hooks: the weighted
+// clip (ClipWGeneric<CN> / ClipWU8C3, kernels_clip.hip) and the store mode with participation (FoldStoreW<CN>, below).
 #pragma once
 #include <type_traits>
 
@@ -25,6 +27,9 @@ namespace stk {
 template <int CN> struct FoldStore;
 template <int CN> struct FoldWeighted;
 template <int CN> struct FoldMoments;
+template <int CN> struct FoldStoreW;
+template <int CN> struct ClipWGeneric;
+struct ClipWU8C3;
 
 // The coverage weight of one sample: what the fold's interpolation (lerp chain, or the classic four-weight sum) gives for a
 // frame whose every value is 1.0f under alpha = 1 and BORDER_CONSTANT 0; i00 .. i11 say which taps are inside the frame.
@@ -73,9 +78,11 @@ template <typename T, int CN, bool CLIP, class ClipState>
 __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipArgs ca) {
     constexpr bool WEIGHTED = std::is_same_v<ClipState, FoldWeighted<CN>>;
     constexpr bool MOMENTS = std::is_same_v<ClipState, FoldMoments<CN>>;
+    // the normalised, coverage-aware rejection states (kernels_clip.hip, FoldStoreW below) take kappa like the weighted mode
+    constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if constexpr (std::is_same_v<ClipState, FoldStore<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
+    if constexpr (std::is_same_v<ClipState, FoldStore<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
     // (moments mode: (x, y) index the stepped grid and every lane stays for the wave reduction; see the loop below)
     if constexpr (!MOMENTS) { if (x >= a.dw || y >= a.dh) return; }
     float* accp = a.acc + (size_t)y * a.acc_stride + (size_t)x * CN;
@@ -145,7 +152,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
         const int cx0 = max(x0, 0), cx1 = max(x1, 0), cy0 = max(y0, 0), cy1 = max(y1, 0);
         const T* r0 = src + (size_t)cy0 * a.src_stride;
         const T* r1 = src + (size_t)cy1 * a.src_stride;
-        if constexpr (WEIGHTED || MOMENTS) {
+        if constexpr (WEIGHTED || MOMENTS || ROBUST) {
             // kappa from the taps that are inside the frame (the BORDER_CONSTANT validity, whatever the fold's border mode)
             const bool ix0 = (unsigned)ix < (unsigned)a.sw, ix1 = (unsigned)(ix + 1) < (unsigned)a.sw;
             const bool iy0 = (unsigned)iy < (unsigned)a.sh, iy1 = (unsigned)(iy + 1) < (unsigned)a.sh;
@@ -246,6 +253,52 @@ struct FoldStore {
     }
     __device__ __forceinline__ void add2(f32x2 s01, float s2) { p[0] = s01.x; p[1] = s01.y; p[2] = s2; p += slab; }
     __device__ __forceinline__ void add3(float s0, float s1, float s2) { p[0] = s0; p[1] = s1; p[2] = s2; p += slab; }
+    __device__ __forceinline__ void finish(const ClipArgs&, int, int) {}
+};
+
+// The store mode with participation (the normalised, coverage-aware quantile; definition: include/stacker.h): FoldStore's
+// layout, but the value written for entry i is the normalised sample u = s * g_i,c + o_i,c if the entry participates in
+// the pixel (w_i > 0 and, with ClipArgs::coverage, kappa_i == 1.0f) and the bit pattern QUANTILE_ABSENT_BITS if not: a
+// signalling NaN, which u, the result of an add, never is (common.h), so the selection kernel cannot take a genuine NaN
+// for an absent entry. g, o, w from ClipArgs::coef by a pointer that moves once per frame, as in FoldWeighted.
+template <int CN>
+struct FoldStoreW {
+    // The records are read through a constant-address-space pointer: the band's stores (through p) could alias a plain
+    // global pointer as far as the compiler knows, which turned every record read into a vector load behind the previous
+    // frame's stores and kept a pixel's three stores apart. The table is written before the launch only.
+    typedef const stk_frame_weight __attribute__((address_space(4))) * CoefPtr;
+    float* p;
+    size_t slab;
+    CoefPtr e;
+    float v[CN];
+    int cov;
+    bool part;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+        p = ca.band + (size_t)(y - ca.y0) * ca.plane_stride + (size_t)x * CN;
+        slab = (size_t)ca.band_rows * ca.plane_stride;
+        e = (CoefPtr)(uintptr_t)ca.coef; cov = ca.coverage; part = true;
+    }
+    __device__ __forceinline__ float value(int c, float s) const {
+        const float u = s * e->gain[c] + e->offset[c];
+        return part ? u : __uint_as_float(QUANTILE_ABSENT_BITS);
+    }
+    __device__ __forceinline__ void entry(float k) { part = (e->weight > 0.0f) & (cov ? k == 1.0f : true); }
+    // the values of a pixel are stored together, after the last channel's
+    __device__ __forceinline__ void add(int c, float s) {
+        v[c] = value(c, s);
+        if (c == CN - 1) {
+#pragma unroll
+            for (int i = 0; i < CN; i++) p[i] = v[i];
+            p += slab; e++;
+        }
+    }
+    __device__ __forceinline__ void add2(f32x2 s01, float s2) { add3k(s01.x, s01.y, s2, 1.0f); }
+    __device__ __forceinline__ void add3k(float s0, float s1, float s2, float k) {
+        entry(k);
+        const float v0 = value(0, s0), v1 = value(1, s1), v2 = value(2, s2);
+        p[0] = v0; p[1] = v1; p[2] = v2;
+        p += slab; e++;
+    }
     __device__ __forceinline__ void finish(const ClipArgs&, int, int) {}
 };
 
@@ -350,7 +403,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_u8c3_kernel(WarpArgs a, C
     const int wave = threadIdx.x >> 6;
     const int x = (blockIdx.x * WX + (wave % WX)) * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * (4 / WX) + wave / WX;
-    if constexpr (std::is_same_v<ClipState, FoldStore<3>>) y += ca.y0;      // store mode: a band of rows (a.dh = its end)
+    if constexpr (std::is_same_v<ClipState, FoldStore<3>> || std::is_same_v<ClipState, FoldStoreW<3>>) y += ca.y0;      // store mode: a band of rows (a.dh = its end)
     if (x >= a.dw || y >= a.dh) return;
     float* accp = a.acc + (size_t)y * a.acc_stride + (size_t)x * 3;
     f32x2 s01 = {0.f, 0.f};                   // (B, G) running sums as a register pair, R apart
@@ -502,7 +555,8 @@ __global__ __launch_bounds__(256) void warp_accumulate_u8c3_kernel(WarpArgs a, C
                     const float v = STK_LERP(p00, p01, p10, p11);
                     if constexpr (CLIP) vr = v; else s2 = s2 + v;
                 }
-                if constexpr (std::is_same_v<ClipState, FoldWeighted<3>>)
+                if constexpr (std::is_same_v<ClipState, FoldWeighted<3>> || std::is_same_v<ClipState, ClipWU8C3> ||
+                              std::is_same_v<ClipState, FoldStoreW<3>>)
                     cs.add3k(vb, vg, vr, STK_LERP(v00 ? 1.0f : 0.0f, v01 ? 1.0f : 0.0f, v10 ? 1.0f : 0.0f, v11 ? 1.0f : 0.0f));
                 else if constexpr (CLIP) cs.add3(vb, vg, vr);
             }

@@ -34,6 +34,9 @@ WeightedLayout weighted_layout(int n_entries, int w, int h, int cn, int step) {
     return L;
 }
 
+}  // namespace
+
+// (the checks, the moments pass and the estimator are shared with robust.cpp: context.h)
 stk_status weighted_check_out(stk_ctx* ctx, const stk_image_f32* out, const stk_frames* f) {
     stk_status st = image_check(ctx, out, f->width, f->height, f->channels);
     if (st) return st;
@@ -138,6 +141,8 @@ void weighted_estimate(const double* m /* cn x 6 */, int cn, int mode, stk_frame
         e->gain[c] = gf; e->offset[c] = of;
     }
 }
+
+namespace {
 
 // The weighted fold over the n_entries entries of ctx->warpframes with the per-entry records `coef`. Writes `out` and
 // `coverage_out` (out's location); adds its device time to *ms.
