@@ -544,6 +544,62 @@ stk_status stk_hybrid_match_files(stk_ctx* ctx, const char* const* paths, int32_
 enum { STK_SHARPNESS_LAPM = 0, STK_SHARPNESS_LAPV = 1, STK_SHARPNESS_TENG = 2, STK_SHARPNESS_GLVN = 3 };
 stk_status stk_sharpness(stk_ctx* ctx, const void* grey, int32_t depth, int32_t width, int32_t height,
                          int32_t location, int32_t metric, int32_t ksize, double* out);
+
+/* ---- score and rank a whole stack: the first half of the example program (examples/main.rs:35-64) ---------------
+ * All four metrics of every frame of an 8-bit stack in ONE device pass: each frame is read once, its integer grey
+ * (stk_grey's, bit for bit; one-channel frames are taken as they are) exists in on-chip memory only, and one copy behind
+ * one synchronisation brings the sums of all frames back. scores: n x 4 doubles, frame-major, in the order of the
+ * STK_SHARPNESS_* enum; each is the very double stk_sharpness returns for stk_grey of that frame (the sums are exact
+ * integers, so nothing depends on how the pass is cut up). frames: 1, 3 or 4 channels, host or device memory, any
+ * row stride (a frame whose base address or row stride is no multiple of 4 is read byte by byte: same result, slower);
+ * host frames are copied over in batches that fit the context's frame workspace. ksize is TENG's: 1, 3, 5
+ * or 7, else STK_INVALID_PARAMS ("Kernel size must be 1, 3, 5, or 7", lib.rs:1105). 16-bit and f32 frames:
+ * STK_NOT_IMPLEMENTED (the reference scores 8-bit greys, and the int64 sums hold 8-bit input only; for the same reason
+ * frames above 2^27 pixels). stk_timing.prep_ms is the device time of the pass (for host frames with their copies), every
+ * other field 0. A multi-device context scores on its first device. */
+stk_status stk_stack_sharpness(stk_ctx* ctx, const stk_frames* frames, int32_t ksize, double* scores /* n x 4 */);
+
+enum { STK_QUALITY_WEIGHT_NONE = 0, STK_QUALITY_WEIGHT_SCORE = 1 };
+typedef struct {
+    int32_t metric;                 /* STK_SHARPNESS_*: the column the frames are ranked by (the example: TENG) */
+    int32_t ksize;                  /* TENG's kernel size for the scoring pass: 1, 3, 5 or 7 (stk_rank_frames ignores it) */
+    int32_t drop_worst;             /* the example's skip(1): this many of the lowest-ranked frames are dropped; >= 0 */
+    float   keep_fraction;          /* 0 = off; in (0, 1]: keep the best max(1, ceil(keep_fraction * n)) frames (the product in
+                                       double, from the float's own value); not together with drop_worst != 0 */
+    int32_t weight_mode;            /* STK_QUALITY_WEIGHT_* */
+    int32_t reserved;               /* 0 */
+} stk_select_params;
+
+/* The example's sort / skip / reverse (main.rs:53, 64) on scores as stk_stack_sharpness returns them. Host code: no
+ * context, no GPU. A stable ascending sort by the chosen metric, skip the first drop_worst, reverse: order[0 .. n_kept)
+ * are the kept frames' indices, best first — order[0] is the frame the example makes the reference —, and equal scores
+ * come out in DESCENDING frame index. The rest of order holds the dropped frames (best first), so order is always a
+ * permutation of 0 .. n-1. n_kept = n - drop_worst, or max(1, ceil(keep_fraction * n)), at most n; n_kept < 1 (and
+ * n < 1): STK_NOT_ENOUGH_FILES. The example compares with partial_cmp(..).unwrap_or(Equal): a NaN score is equal to every
+ * other, which orders nothing consistently; defined here as what a straight insertion sort (Rust's own on short slices)
+ * makes of it: the NaN frame keeps its place and no frame moves across it (computed run by run: O(n log n) for any n).
+ * weights_or_null: n floats BY POSITION IN order (weights[i] belongs to frame order[i]) for the `weights` of the weighted
+ * combines: STK_QUALITY_WEIGHT_SCORE gives a kept frame (float)(its score / the best kept score), or 1 if that best
+ * score is 0; STK_QUALITY_WEIGHT_NONE, and every dropped frame, 1. */
+stk_status stk_rank_frames(const double* scores /* n x 4 */, int32_t n, const stk_select_params* select,
+                           int32_t* order /* n */, int32_t* n_kept, float* weights_or_null /* n */);
+
+/* stk_ecc_match / stk_keypoint_match behind the ranking: score the stack (stk_stack_sharpness with select->ksize), select
+ * (stk_rank_frames), and run the plain call on the kept frames in ranked order — by definition the plain call's result
+ * on the list {frames->data[order[0]], .., frames->data[order[n_kept - 1]]}, bit for bit; only the pointers are
+ * permuted. out, dropped, stats and errors are the plain call's; stats_or_null has n_kept entries in the order of that
+ * list. order: n entries, n_kept, scores_or_null (n x 4) as above. 8-bit BGR(A) frames; host frames cross to the device
+ * twice, for the scoring pass and again, in ranked order, inside the plain call. stk_timing is the plain call's with the
+ * scoring pass's device time added to prep_ms. The clipped, quantile and weighted combines have no ranked form:
+ * score, rank, permute the list and call them (stk_rank_frames' weights fit their `weights`). */
+stk_status stk_ecc_match_ranked(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                stk_image_f32* out, stk_frame_stats* stats_or_null, const stk_select_params* select,
+                                int32_t* order, int32_t* n_kept, double* scores_or_null);
+stk_status stk_keypoint_match_ranked(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                     float scale_down_width, stk_image_f32* out, int32_t* dropped,
+                                     stk_frame_stats* stats_or_null, const stk_select_params* select, int32_t* order,
+                                     int32_t* n_kept, double* scores_or_null);
+
 /* One frame's whole ECC preparation as ecc_match runs it per frame: cvt_color(BGR2GRAY) (utils.rs:136-142) followed
  * by findTransformECC's own GaussianBlur of the float image (lib.rs:769-777) in one fused pass. `out` is a tightly
  * packed width x height f32 plane in the frame's location. BGR frames, 8-bit or f32. */

@@ -11,8 +11,9 @@ use (api.Stacker / _ffi.load) and there is no CPU fallback.
 from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_WRAP,  # noqa: F401
                   LEAST_SQUARES, LMEDS, RANSAC, RHO, EccMatchParameters, HipError, InvalidParams, IoError,
                   KeyPointMatchParameters, MotionType, NotEnoughFiles, NotImplementedYet, OpenCvError,
-                  ProcessingError, QuantileParameters, SigmaClipParameters, Stacker, StackerError, WeightParameters, default_stacker, ecc_match,
-                  keypoint_match)
+                  ProcessingError, QuantileParameters, SelectParameters, SigmaClipParameters, Stacker, StackerError, WeightParameters,
+                  default_stacker, ecc_match, keypoint_match, rank_frames)
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
-           "StackerError", "Stacker", "SigmaClipParameters", "QuantileParameters", "WeightParameters"]
+           "StackerError", "Stacker", "SigmaClipParameters", "QuantileParameters", "WeightParameters",
+           "SelectParameters", "rank_frames"]

@@ -63,6 +63,11 @@ class FrameWeight(C.Structure):
     _fields_ = [("gain", C.c_float * 4), ("offset", C.c_float * 4), ("weight", C.c_float), ("flags", C.c_int32)]
 
 
+class SelectParams(C.Structure):
+    _fields_ = [("metric", C.c_int32), ("ksize", C.c_int32), ("drop_worst", C.c_int32), ("keep_fraction", C.c_float),
+                ("weight_mode", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("prep_ms", C.c_double), ("align_ms", C.c_double), ("warp_ms", C.c_double),
                 ("finalize_ms", C.c_double), ("ecc_iter_launches", C.c_int64),
@@ -157,6 +162,15 @@ SIGNATURES = {
                                           C.POINTER(EccParams), C.POINTER(ImageF32), C.POINTER(FrameStats)]),
     "stk_sharpness": (c_status, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.POINTER(C.c_double)]),
+    "stk_stack_sharpness": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_int32, C.c_void_p]),
+    "stk_rank_frames": (c_status, [C.c_void_p, C.c_int32, C.POINTER(SelectParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.c_void_p]),
+    "stk_ecc_match_ranked": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float, C.POINTER(ImageF32),
+                                        C.POINTER(FrameStats), C.POINTER(SelectParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.c_void_p]),
+    "stk_keypoint_match_ranked": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                             C.POINTER(ImageF32), C.POINTER(C.c_int32), C.POINTER(FrameStats),
+                                             C.POINTER(SelectParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
     "stk_grey_blur_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_int32, C.c_void_p]),
     "stk_gaussian_blur_f32": (c_status, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p]),

@@ -141,6 +141,44 @@ class WeightParameters:           # extension beyond the reference: include/stac
         return _ffi.WeightParams(int(self.normalize), int(self.coverage), int(self.stat_step), 0)
 
 
+SHARPNESS_LAPM, SHARPNESS_LAPV, SHARPNESS_TENG, SHARPNESS_GLVN = 0, 1, 2, 3
+QUALITY_WEIGHT_NONE, QUALITY_WEIGHT_SCORE = 0, 1
+
+
+@dataclass
+class SelectParameters:           # extension beyond the reference's library: include/stacker.h, stk_select_params
+    """How a scored stack is ranked and cut (the sort / skip(1) / rev() of examples/main.rs:53, 64): by `metric` (TENG with
+    `ksize` in the example), dropping the `drop_worst` lowest frames or keeping the best `keep_fraction` of them (0 = off);
+    `weight_mode` SCORE also gives every kept frame the weight score / best score for the weighted combines."""
+    metric: int = SHARPNESS_TENG
+    ksize: int = 3
+    drop_worst: int = 0
+    keep_fraction: float = 0.0
+    weight_mode: int = QUALITY_WEIGHT_NONE
+
+    def _c(self) -> _ffi.SelectParams:
+        return _ffi.SelectParams(int(self.metric), int(self.ksize), int(self.drop_worst), float(self.keep_fraction),
+                                 int(self.weight_mode), 0)
+
+
+def rank_frames(scores, select: Optional["SelectParameters"] = None):
+    """stk_rank_frames on an n x 4 array of scores (Stacker.stack_sharpness): (order, n_kept, weights). order[:n_kept] are the
+    kept frames, best first; weights[i] belongs to frame order[i]. Host code: needs the library, not a GPU."""
+    sc = np.ascontiguousarray(np.asarray(scores, np.float64))
+    if sc.ndim != 2 or sc.shape[1] != 4:
+        raise InvalidParams("scores: an n x 4 array expected")
+    n = sc.shape[0]
+    order = np.zeros(max(n, 1), np.int32)
+    weights = np.ones(max(n, 1), np.float32)
+    kept = C.c_int32(0)
+    sp = (select or SelectParameters())._c()
+    st = _ffi.load().stk_rank_frames(C.c_void_p(sc.ctypes.data), n, C.byref(sp), order.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     C.byref(kept), C.c_void_p(weights.ctypes.data))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("Not enough files" if st == 1 else "rank_frames: invalid select parameters")
+    return order[:n], kept.value, weights[:n]
+
+
 def _quantile_c(q) -> _ffi.QuantileParams:
     """QuantileParameters, a bare float, or None (the median)."""
     if q is None:
@@ -381,6 +419,56 @@ class Stacker:
                                           C.byref(img), C.byref(dropped), stats)
         self._check(st)
         return (dropped.value, out, self._stats_list(stats, m.n)) if return_stats else (dropped.value, out)
+
+    # -- score and rank a whole stack (the first half of examples/main.rs) ---------------------------------
+    def stack_sharpness(self, files, ksize: int = 3):
+        """LAPM, LAPV, TENG(ksize) and GLVN of every frame of an 8-bit stack in one device pass (stk_stack_sharpness): an
+        n x 4 float64 array, the doubles sharpness_*(grey(frame)) return."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        scores = np.zeros((m.n, 4), np.float64)
+        self._check(self._lib.stk_stack_sharpness(self._h, C.byref(m.c_frames), int(ksize), C.c_void_p(scores.ctypes.data)))
+        return scores
+
+    def rank(self, files, select: Optional["SelectParameters"] = None):
+        """Score the stack and select: (order, n_kept, scores, weights) — stack_sharpness followed by rank_frames."""
+        select = select or SelectParameters()
+        scores = self.stack_sharpness(files, select.ksize)
+        order, n_kept, weights = rank_frames(scores, select)
+        return order, n_kept, scores, weights
+
+    def _ranked_match(self, kind, files, params, select, scale_down_width, return_stats, return_scores):
+        if kind == "ecc" and isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        stats = (_ffi.FrameStats * m.n)()
+        order = (C.c_int32 * m.n)()
+        kept, dropped = C.c_int32(0), C.c_int32(0)
+        scores = np.zeros((m.n, 4), np.float64)
+        p, sp = params._c(), (select or SelectParameters())._c()
+        args = [self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(img)]
+        if kind == "keypoint":
+            args.append(C.byref(dropped))
+        fn = self._lib.stk_keypoint_match_ranked if kind == "keypoint" else self._lib.stk_ecc_match_ranked
+        self._check(fn(*args, stats, C.byref(sp), order, C.byref(kept), C.c_void_p(scores.ctypes.data)))
+        res = ((dropped.value,) if kind == "keypoint" else ()) + (out, np.array(order[:kept.value], np.int32)) \
+            + ((scores,) if return_scores else ()) + ((self._stats_list(stats, kept.value),) if return_stats else ())
+        return res
+
+    def ecc_match_ranked(self, files, params: EccMatchParameters, select: Optional["SelectParameters"] = None,
+                         scale_down_width: Optional[float] = None, return_scores: bool = False, return_stats: bool = False):
+        """Rank the stack on the device, drop what `select` drops, make the sharpest frame the reference and run ecc_match on
+        that list (stk_ecc_match_ranked): (image, order[:n_kept][, scores][, stats]); the stats follow the kept list."""
+        return self._ranked_match("ecc", files, params, select, scale_down_width, return_stats, return_scores)
+
+    def keypoint_match_ranked(self, files, params: KeyPointMatchParameters, select: Optional["SelectParameters"] = None,
+                              scale_down_width: Optional[float] = None, return_scores: bool = False, return_stats: bool = False):
+        """keypoint_match behind the ranking (stk_keypoint_match_ranked): (dropped, image, order[:n_kept][, scores][, stats])."""
+        return self._ranked_match("keypoint", files, params, select, scale_down_width, return_stats, return_scores)
 
     # -- sigma-clipped combines (extension beyond the reference) -----------------------------------------
     def _counts_image(self, m: _Marshalled):

@@ -240,6 +240,12 @@ hipError_t launch_ecc_solve(const EccIterArgs& a, int motion, EccCriteria crit, 
                             EccFrameResult* results, hipStream_t s, const float* init_warps = nullptr);
 hipError_t launch_sharpness(const void* grey, int depth, int w, int h, int metric, int ksize, void* partials, int n_blocks,
                             hipStream_t s);
+// the four sharpness metrics of n 8-bit frames (cn 1, 3 or 4; frames_dev: device array of n frame pointers) in one pass
+// (kernels_quality.hip): per-tile partials (n x quality_tiles(w, h) x 6 int64), reduced to records (n x 6 int64: LAPM x4,
+// LAPV sum and sum of squares, TENG, GLVN sum and sum of squares); n <= 65535
+int quality_tiles(int w, int h);
+hipError_t launch_quality(const void* const* frames_dev, int n, int cn, int w, int h, size_t stride_bytes, int ksize,
+                          long long* partials, long long* records, hipStream_t s);
 hipError_t launch_ecc_init(EccSlot* slots, int n_slots, int* tickets, EccQueue* queue, int n_frames, EccFrameResult* results,
                            const float* init_warps /* n_frames*9 or null */, hipStream_t s, int ready0 = -1 /* -1: all */);
 hipError_t launch_ecc_set_ready(EccQueue* queue, int ready, hipStream_t s);

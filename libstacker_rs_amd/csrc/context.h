@@ -88,6 +88,7 @@ struct stk_ctx {
     DevBuf weighted;              // weighted combine (weighted.cpp): image, den plane, per-entry table, moments and their partials
     DevBuf coef;                  // normalised rejection combines (robust.cpp): the per-entry gain / offset / weight table
     DevBuf quantile;              // quantile combines (quantile.cpp): a w x h x cn f32 image, then the band of samples
+    DevBuf quality;               // whole-stack sharpness (quality.cpp): frame pointers, per-frame records, tile partials
     stk::KeypointWorkspace* kp = nullptr;
     stk::geom::HgWorkspace* hg = nullptr;   // findHomography batch workspace (homography.cpp)
     stk::HostPool* host_pool = nullptr;
@@ -127,6 +128,8 @@ void make_warp_frame(WarpFrame& wf, const void* src, const double* M, int is_aff
 stk_status image_check(stk_ctx* ctx, const stk_image_f32* im, int w, int h, int c);
 size_t image_stride_floats(const stk_image_f32* im);
 void timing_begin(stk_ctx* ctx);
+// closing formula of a sharpness metric from a frame's sums (quality.cpp; shared by stk_sharpness and stk_stack_sharpness)
+double sharpness_finish(int metric, double s, double sq, int width, int height);
 float ev_ms(hipEvent_t a, hipEvent_t b);
 
 // shared internals of the entry points (stacker.cpp / keypoint.cpp / hybrid.cpp / clip.cpp / quantile.cpp)

@@ -7,6 +7,7 @@
 //   ref_planes     blurred frame 0 -> zero-padded I / gx / gy planes    (ECC setup step 5)
 // HBM-bound: grey_blur reads 3 B/px (u8 BGR) and writes 4 B/px.
 #include "common.h"
+#include "grey.h"
 
 namespace stk {
 
@@ -17,9 +18,6 @@ __device__ __forceinline__ int reflect101(int p, int len) {
 }
 
 // ---- grey -------------------------------------------------------------------------------------
-__device__ __forceinline__ uint8_t grey_u8(unsigned b, unsigned g, unsigned r) {
-    return (uint8_t)((b * 3735u + g * 19235u + r * 9798u + (1u << 14)) >> 15);
-}
 __device__ __forceinline__ uint16_t grey_u16(unsigned b, unsigned g, unsigned r) {
     return (uint16_t)((b * 1868u + g * 9617u + r * 4899u + (1u << 13)) >> 14);
 }

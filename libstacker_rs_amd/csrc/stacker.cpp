@@ -93,7 +93,7 @@ void stk_destroy(stk_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (DevBuf* b : {&ctx->frames, &ctx->ref, &ctx->blur_tmp, &ctx->templates, &ctx->slots, &ctx->queue, &ctx->results,
                       &ctx->partials, &ctx->warpframes, &ctx->acc, &ctx->scratch, &ctx->init_warps, &ctx->frameptrs, &ctx->clip,
-                      &ctx->quantile, &ctx->weighted, &ctx->coef})
+                      &ctx->quantile, &ctx->weighted, &ctx->coef, &ctx->quality})
         b->release();
     keypoint_workspace_destroy(ctx->kp);
     geom::hg_workspace_destroy(ctx->hg);
@@ -924,13 +924,7 @@ stk_status stk_sharpness(stk_ctx* ctx, const void* grey, int32_t depth, int32_t 
         const double* p = reinterpret_cast<const double*>(hostp.data());
         for (int b = 0; b < nb; b++) { s += p[2 * b]; sq += p[2 * b + 1]; }
     }
-    const double scale = 1. / ((double)width * height);          // cv::mean / meanStdDev multiply by the reciprocal
-    if (metric == STK_SHARPNESS_LAPM || metric == STK_SHARPNESS_TENG) *out = s * scale;
-    else {
-        const double mean = s * scale;
-        const double sigma = std::sqrt(std::max(sq * scale - mean * mean, 0.));
-        *out = metric == STK_SHARPNESS_LAPV ? sigma * sigma : (sigma * sigma) / std::max(mean, DBL_EPSILON);
-    }
+    *out = sharpness_finish(metric, s, sq, width, height);
     return STK_OK;
 }
 
