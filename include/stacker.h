@@ -89,13 +89,33 @@ typedef struct {
                                        reference's convertTo / warp / add do to it); 1 is accepted by stage-level calls only */
     int32_t depth;                  /* STK_DEPTH_* */
     int32_t location;               /* STK_HOST | STK_DEVICE */
-    size_t  row_stride_bytes;       /* 0 = tightly packed */
+    size_t  row_stride_bytes;       /* 0 = tightly packed; else the bytes from one row to the next: at least width * channels *
+                                       (depth / 8) and a multiple of depth / 8, anything else is STK_INVALID_PARAMS. This is how a
+                                       Mat with padded rows, or a ROI of a larger image, is handed over; the frames need not be
+                                       evenly spaced in memory, and neither data[i] nor the stride need any alignment. The results
+                                       do not depend on the layout: a padded stack gives the bits of its tightly packed copy.
+                                       What the engine reads of frame i, with span = row_stride_bytes * (height - 1) + width *
+                                       channels * (depth / 8), the bytes from its first to its last pixel:
+                                       - STK_HOST: bytes [data[i], data[i] + span) and nothing else: the padding behind the last
+                                         pixel of the last row is not read (a ROI may end on the last byte of its parent buffer);
+                                       - STK_DEVICE: bytes [data[i], data[i] + span) too, but ANY of them, the padding between two
+                                         rows included (it must be readable memory; its values never reach a result): the warp
+                                         kernels' dword-aligned windows reach up to 6 bytes past the last pixel of any row but the
+                                         last (warp_accumulate_u8c3_kernel, warp_body.h: 12 bytes from (offset & ~3)
+                                         for the 6 bytes of a pixel pair that starts at most at 3 * (width - 2); 4 bytes in
+                                         warp_accumulate_u16c3_kernel, kernels_warp.hip; their unaligned forms 2 and 0 bytes), which
+                                         for a tight frame is the next row. No kernel reads before the first pixel — a window's
+                                         aligned start never precedes its row, whose offset is a multiple of 4 whenever windows
+                                         are used — or behind the last one: windows are used on rows 0 .. height - 2 only (the
+                                         interior test keeps a row to spare), and the 8-byte load of the last row's last pixel
+                                         pair backs off by 2 bytes (warp_body.h, the rim path).
+                                         The preparation kernels (kernels_prep.hip, kernels_quality.hip) read pixels only. */
 } stk_frames;
 
 /* Geometry of ONE frame of a stack whose frames differ in size (stk_keypoint_match_mixed). */
 typedef struct {
     int32_t width, height;
-    size_t  row_stride_bytes;       /* 0 = tightly packed */
+    size_t  row_stride_bytes;       /* 0 = tightly packed; else as stk_frames.row_stride_bytes (same rules, same reads) */
 } stk_frame_geometry;
 
 /* Caller-allocated f32 image (the returned CV_32FC3 Mat, lib.rs:98,656; CV_32FC4 — channels = 4 — for BGRA stacks). */

@@ -196,8 +196,22 @@ def _is_torch(x) -> bool:
 _DEPTH = {"uint8": 8, "uint16": 16, "float32": 32}
 
 
+def _row_stride_bytes(shape, strides, el):
+    """The row step in bytes of a frame (h x w or h x w x c, strides in bytes) whose ONLY non-contiguity is that step: pixels
+    and channels packed, rows at least a tight row apart, going forward, on an element boundary. None for anything else."""
+    if len(shape) not in (2, 3):
+        return None
+    c = shape[2] if len(shape) == 3 else 1
+    if (len(shape) == 3 and strides[2] != el) or strides[1] != c * el:
+        return None
+    rs = int(strides[0])
+    return rs if rs >= shape[1] * c * el and rs % el == 0 else None
+
+
 class _Marshalled:
-    """Pointers + geometry of a frame stack, keeping the owners alive."""
+    """Pointers + geometry of a frame stack, keeping the owners alive. A frame that is a row-strided view (a window of a
+    wider image, rows padded: _row_stride_bytes) is handed over where it lies, with stk_frames.row_stride_bytes set, if all
+    frames of the stack share that stride; every other non-contiguous layout is copied into a contiguous frame first."""
 
     def __init__(self, frames):
         if _is_torch(frames) and frames.dim() == 4 and frames.is_contiguous() and frames.shape[0] > 0 \
@@ -229,27 +243,29 @@ class _Marshalled:
         self.devices = set()
         ptrs = []
         geo = None
+        views = []                        # (index, owner as handed in, row stride in bytes) of the frames that are row-strided views
         for f in frames:
-            if _is_torch(f):
-                if f.is_cuda:
-                    self.location = DEVICE
-                    if self.torch_device is None:
-                        self.torch_device = f.device         # outputs go where the reference frame lives
-                    self.devices.add(f.device)
-                    t = f.contiguous()
-                    self.keep.append(t)
-                    ptrs.append(t.data_ptr())
-                    g = (tuple(t.shape), str(t.dtype).replace("torch.", ""))
-                else:
-                    a = np.ascontiguousarray(f.numpy())
-                    self.keep.append(a)
-                    ptrs.append(a.ctypes.data)
-                    g = (a.shape, str(a.dtype))
+            if _is_torch(f) and f.is_cuda:
+                self.location = DEVICE
+                if self.torch_device is None:
+                    self.torch_device = f.device         # outputs go where the reference frame lives
+                self.devices.add(f.device)
+                rs = None if f.is_contiguous() else _row_stride_bytes(tuple(f.shape), [s * f.element_size() for s in f.stride()], f.element_size())
+                t = f if rs else f.contiguous()
+                self.keep.append(t)
+                ptrs.append(t.data_ptr())
+                g = (tuple(t.shape), str(t.dtype).replace("torch.", ""))
             else:
-                a = np.ascontiguousarray(f)
+                v = f.numpy() if _is_torch(f) else f
+                rs = None
+                if isinstance(v, np.ndarray) and not v.flags.c_contiguous:
+                    rs = _row_stride_bytes(v.shape, v.strides, v.itemsize)
+                a = v if rs else np.ascontiguousarray(v)
                 self.keep.append(a)
                 ptrs.append(a.ctypes.data)
                 g = (a.shape, str(a.dtype))
+            if rs:
+                views.append((len(ptrs) - 1, f, rs))
             if len(g[0]) == 2:
                 g = ((g[0][0], g[0][1], 1), g[1])
             if geo is None:
@@ -264,9 +280,36 @@ class _Marshalled:
         else:
             self.h = self.w = self.c = 0
             self.depth = 8
+        # stk_frames has ONE row stride: the views keep their own memory only if every frame of the stack steps its rows
+        # alike (a contiguous frame steps them by the tight row); otherwise they are made contiguous like any other layout
+        stride = 0
+        if views:
+            tight = self.w * self.c * (self.depth // 8)
+            if {rs for _, _, rs in views} | ({tight} if len(views) < self.n else set()) == {views[0][2]}:
+                stride = views[0][2]
+            else:
+                for i, f, _ in views:
+                    if _is_torch(f) and f.is_cuda:
+                        self.keep[i] = f.contiguous()
+                        ptrs[i] = self.keep[i].data_ptr()
+                    else:
+                        self.keep[i] = np.ascontiguousarray(f.numpy() if _is_torch(f) else f)
+                        ptrs[i] = self.keep[i].ctypes.data
         self.ptr_arr = (C.c_void_p * max(self.n, 1))(*ptrs)
         self.c_frames = _ffi.Frames(C.cast(self.ptr_arr, C.POINTER(C.c_void_p)), self.n, self.w, self.h, self.c,
-                                    self.depth, self.location, 0)
+                                    self.depth, self.location, stride)
+
+
+def _image_stride_bytes(img) -> int:
+    """row_stride_bytes of an f32 h x w x c image the caller holds: 0 for a contiguous one, the row step of a row-strided
+    view (a window of a wider image)."""
+    if (img.is_contiguous() if _is_torch(img) else img.flags.c_contiguous):
+        return 0
+    strides = [s * img.element_size() for s in img.stride()] if _is_torch(img) else img.strides
+    rs = _row_stride_bytes(tuple(img.shape), strides, 4)
+    if not rs:
+        raise InvalidParams("the image must be contiguous or a view whose only non-contiguity is its row step")
+    return rs
 
 
 class Stacker:
@@ -872,7 +915,7 @@ class Stacker:
         m = self._marshal(files)
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
-        img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, 0)
+        img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, _image_stride_bytes(sum_out))
         added = C.c_int32(0)
         stats = (_ffi.FrameStats * m.n)()
         p = params._c()
@@ -886,7 +929,7 @@ class Stacker:
         m = self._marshal(files)
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
-        img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, 0)
+        img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, _image_stride_bytes(sum_out))
         added, dropped = C.c_int32(0), C.c_int32(0)
         stats = (_ffi.FrameStats * m.n)()
         p = params._c()
@@ -948,7 +991,7 @@ class Stacker:
         m = self._marshal(files)
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
-        img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, 0)
+        img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, _image_stride_bytes(sum_out))
         added = C.c_int32(0)
         stats = (_ffi.FrameStats * m.n)()
         kp, ep = kp_params._c(), ecc_params._c()
@@ -1094,9 +1137,9 @@ class Stacker:
         if accumulate:
             out = acc
             if _is_torch(out):
-                img = _ffi.ImageF32(out.data_ptr(), m.w, m.h, m.c, DEVICE if out.is_cuda else HOST, 0)
+                img = _ffi.ImageF32(out.data_ptr(), m.w, m.h, m.c, DEVICE if out.is_cuda else HOST, _image_stride_bytes(out))
             else:
-                img = _ffi.ImageF32(out.ctypes.data, m.w, m.h, m.c, HOST, 0)
+                img = _ffi.ImageF32(out.ctypes.data, m.w, m.h, m.c, HOST, _image_stride_bytes(out))
         else:
             out, img = self._out_image(m)
         st = self._lib.stk_warp_accumulate(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), int(is_affine),

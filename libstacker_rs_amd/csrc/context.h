@@ -115,6 +115,16 @@ inline stk_status fail(stk_ctx* ctx, stk_status st, const std::string& msg) {
 
 using stk::WarpFrame;
 size_t frame_row_bytes(const stk_frames* f);
+// the bytes of one frame that a copy out of the CALLER's memory takes: up to the last pixel of the last row. The padding
+// behind that pixel is not the caller's to give (a ROI may end on the last byte of its parent buffer; include/stacker.h,
+// row_stride_bytes). The engine's own buffers keep frames row_bytes * h apart; the bytes the copy leaves out are never used.
+inline size_t frame_copy_bytes(size_t row_bytes, int w, int h, int cn, int depth) {
+    return row_bytes * (size_t)(h - 1) + (size_t)w * cn * (depth / 8);
+}
+inline size_t frame_copy_bytes(const stk_frames* f) {
+    const size_t tight = (size_t)f->width * f->channels * (f->depth / 8);
+    return frame_copy_bytes(f->row_stride_bytes ? f->row_stride_bytes : tight, f->width, f->height, f->channels, f->depth);
+}
 stk_status resolve_frames(stk_ctx* ctx, const stk_frames* f, std::vector<const void*>& dev);
 stk_status check_frames(stk_ctx* ctx, const stk_frames* f, bool need_bgr);
 // (w, h): the SOURCE frames' size; (dw, dh): the accumulator's, 0 = the same (a stack of one geometry)

@@ -916,7 +916,7 @@ stk_status stk_keypoint_match_shard(stk_ctx* ctx, const stk_frames* frames, cons
         }
     }
     HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    if (n_wf == 0) HIP_TRY(hipMemsetAsync(sum->data, 0, image_stride_floats(sum) * h * sizeof(float), ctx->stream));
+    if (n_wf == 0) HIP_TRY(hipMemset2DAsync(sum->data, image_stride_floats(sum) * sizeof(float), 0, (size_t)w * cn * sizeof(float), h, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->timing.align_ms = ev_ms(ctx->ev[0], ctx->ev[1]);       // includes the folds that ran under later lanes
     ctx->timing.warp_ms = 0;

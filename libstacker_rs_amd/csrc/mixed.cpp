@@ -99,7 +99,7 @@ stk_status stk_keypoint_match_mixed(stk_ctx* ctx, const stk_frames* frames, cons
         if (!frames->data[i]) return fail(ctx, STK_INVALID_PARAMS, "frame " + std::to_string(i) + ": null data");
         const void* dev = frames->data[i];
         if (host) {
-            HIP_TRY(hipMemcpyAsync(ctx->frames.p, frames->data[i], rb * (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(ctx->frames.p, frames->data[i], frame_copy_bytes(rb, w, h, cn, 8), hipMemcpyHostToDevice, ctx->stream));
             dev = ctx->frames.p;
         }
         stk_frames one{};

@@ -149,7 +149,7 @@ stk_status multi_match(stk_ctx* ctx, int kind, const stk_frames* frames, const s
                 if (ms->stage[r].reserve(fb * remote.size()) != hipSuccess) { status[r] = fail(c, STK_HIP_ERROR, "staging allocation failed"); return; }
                 for (size_t q = 0; q < remote.size(); q++) {
                     void* d = ms->stage[r].as<uint8_t>() + fb * q;
-                    if (hipMemcpyAsync(d, ptrs[remote[q]], fb, hipMemcpyDefault, c->stream) != hipSuccess) { status[r] = fail(c, STK_HIP_ERROR, "peer copy failed"); return; }
+                    if (hipMemcpyAsync(d, ptrs[remote[q]], frame_copy_bytes(frames), hipMemcpyDefault, c->stream) != hipSuccess) { status[r] = fail(c, STK_HIP_ERROR, "peer copy failed"); return; }
                     ptrs[remote[q]] = d;
                 }
             }

@@ -71,7 +71,7 @@ stk_status quality_scores(stk_ctx* ctx, const stk_frames* f, int ksize, double* 
         const int nb = std::min(batch, n - b0);
         if (host)      // stream order keeps the previous batch's kernels ahead of the copies that overwrite its frames
             for (int i = 0; i < nb; i++)
-                HIP_TRY(hipMemcpyAsync(ctx->frames.as<uint8_t>() + fb * (size_t)i, f->data[b0 + i], fb, hipMemcpyHostToDevice, ctx->stream));
+                HIP_TRY(hipMemcpyAsync(ctx->frames.as<uint8_t>() + fb * (size_t)i, f->data[b0 + i], frame_copy_bytes(f), hipMemcpyHostToDevice, ctx->stream));
         for (int l0 = 0; l0 < nb; l0 += per_launch) {
             const int nl = std::min(per_launch, nb - l0);
             HIP_TRY(launch_quality(ptrs_dev + (host ? l0 : b0 + l0), nl, cn, w, h, rb, ksize, partials, records + (size_t)(b0 + l0) * 6, ctx->stream));

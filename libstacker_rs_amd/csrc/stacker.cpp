@@ -22,13 +22,13 @@ size_t frame_row_bytes(const stk_frames* f) {
 
 // Bring the frames of a stack into HBM (no copy when they already are).
 stk_status resolve_frames(stk_ctx* ctx, const stk_frames* f, std::vector<const void*>& dev) {
-    const size_t rb = frame_row_bytes(f), fb = rb * f->height;
+    const size_t rb = frame_row_bytes(f), fb = rb * f->height, cb = frame_copy_bytes(f);
     dev.resize(f->n);
     if (f->location == STK_DEVICE) { for (int i = 0; i < f->n; i++) dev[i] = f->data[i]; return STK_OK; }
     HIP_TRY(ctx->frames.reserve(fb * f->n));
     for (int i = 0; i < f->n; i++) {
         void* d = ctx->frames.as<uint8_t>() + fb * i;
-        HIP_TRY(hipMemcpyAsync(d, f->data[i], fb, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d, f->data[i], cb, hipMemcpyHostToDevice, ctx->stream));
         dev[i] = d;
     }
     return STK_OK;
@@ -44,6 +44,11 @@ stk_status check_frames(stk_ctx* ctx, const stk_frames* f, bool need_bgr) {
         return fail(ctx, STK_BACKEND_ERROR, "cvtColor(BGR2GRAY): frames must have 3 or 4 channels (utils.rs:136)");
     if (f->channels != 1 && f->channels != 3 && f->channels != 4) return fail(ctx, STK_INVALID_PARAMS, "channels must be 1, 3 or 4");
     if ((size_t)f->width * f->height > (size_t)1 << 30) return fail(ctx, STK_INVALID_PARAMS, "frame too large");
+    if (f->row_stride_bytes) {                            // include/stacker.h: 0 = tightly packed, else whole elements and at least one row
+        const size_t el = (size_t)f->depth / 8;
+        if (f->row_stride_bytes < (size_t)f->width * f->channels * el) return fail(ctx, STK_INVALID_PARAMS, "row stride below the row's bytes");
+        if (f->row_stride_bytes % el) return fail(ctx, STK_INVALID_PARAMS, "row stride must be a multiple of the element size");
+    }
     return STK_OK;
 }
 
@@ -631,7 +636,7 @@ stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_
                                                     sum->data, image_stride_floats(sum), 0);
             if (fs) return fs;
         } else {
-            HIP_TRY(hipMemsetAsync(sum->data, 0, image_stride_floats(sum) * h * sizeof(float), ctx->stream));
+            HIP_TRY(hipMemset2DAsync(sum->data, image_stride_floats(sum) * sizeof(float), 0, (size_t)w * cn * sizeof(float), h, ctx->stream));
         }
         HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
         folded_on_device = true;
@@ -741,7 +746,7 @@ stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_
         wf.emplace_back();
         make_warp_frame(wf.back(), dev[i], M, is_affine);
     }
-    if (wf.empty()) HIP_TRY(hipMemsetAsync(sum->data, 0, image_stride_floats(sum) * h * sizeof(float), ctx->stream));
+    if (wf.empty()) HIP_TRY(hipMemset2DAsync(sum->data, image_stride_floats(sum) * sizeof(float), 0, (size_t)w * cn * sizeof(float), h, ctx->stream));
     if ((st = warp_fold(ctx, wf, frames->depth, w, h, cn, rb, alpha, STK_BORDER_CONSTANT, nullptr, is_affine,
                         sum->data, image_stride_floats(sum), 0))) return st;
     HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));

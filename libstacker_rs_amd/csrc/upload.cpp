@@ -6,7 +6,7 @@
 namespace stk {
 
 stk_status AsyncUpload::start(stk_ctx* ctx, const stk_frames* frames, void* dst_base, size_t frame_bytes, int batch) {
-    ctx_ = ctx; n_frames_ = frames->n; batch_ = std::max(1, batch); frame_bytes_ = frame_bytes;
+    ctx_ = ctx; n_frames_ = frames->n; batch_ = std::max(1, batch); frame_bytes_ = frame_bytes; copy_bytes_ = std::min(frame_copy_bytes(frames), frame_bytes);
     first_.clear(); count_.clear();
     first_.push_back(0); count_.push_back(1);                          // the reference frame on its own: its planes come first
     for (int i = 1; i < n_frames_; i += batch_) { first_.push_back(i); count_.push_back(std::min(batch_, n_frames_ - i)); }
@@ -30,7 +30,7 @@ stk_status AsyncUpload::start(stk_ctx* ctx, const stk_frames* frames, void* dst_
             for (int k = 0; k < count_[b] && e == hipSuccess; k++) {
                 const int i = first_[b] + k;
                 if (gate && !gate->wait(src[i])) { e = hipErrorInvalidValue; break; }      // the producer (a decoder) failed
-                e = hipMemcpyAsync((uint8_t*)dst_base + frame_bytes_ * (size_t)i, src[i], frame_bytes_, hipMemcpyHostToDevice, cs);
+                e = hipMemcpyAsync((uint8_t*)dst_base + frame_bytes_ * (size_t)i, src[i], copy_bytes_, hipMemcpyHostToDevice, cs);
             }
             if (e == hipSuccess) e = hipEventRecord(events_[b], cs);
             {

@@ -25,7 +25,8 @@ public:
     AsyncUpload(const AsyncUpload&) = delete;
     AsyncUpload& operator=(const AsyncUpload&) = delete;
 
-    // Starts copying frames->data[i] (host) to dst_base + i * frame_bytes. Returns at once.
+    // Starts copying frames->data[i] (host) to dst_base + i * frame_bytes: frame_copy_bytes(frames) of each (context.h — a
+    // padded frame ends at its last pixel, not at the end of its last row's padding). Returns at once.
     stk_status start(stk_ctx* ctx, const stk_frames* frames, void* dst_base, size_t frame_bytes, int batch);
     bool active() const { return n_frames_ > 0; }
     int batches() const { return (int)first_.size(); }
@@ -46,7 +47,7 @@ private:
     void join() { if (thread_.joinable()) thread_.join(); }
     stk_ctx* ctx_ = nullptr;
     int n_frames_ = 0, batch_ = 1;
-    size_t frame_bytes_ = 0;
+    size_t frame_bytes_ = 0, copy_bytes_ = 0;
     std::vector<int> first_, count_;
     std::vector<hipEvent_t> events_;
     hipEvent_t t0_ = nullptr;

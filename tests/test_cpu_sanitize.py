@@ -1,7 +1,7 @@
 """CPU sanitizer builds: the oracle under ASan + UBSan over its own test file, the product's host-side
 parsers (stk_imread: hand-written PNM parser, hand-declared libpng / libjpeg structs) under ASan + UBSan over golden,
-truncated and garbage files, the host half of findHomography under ASan + UBSan, and the keypoint path's thread pool under
-TSan. CPU builds only — GPU AddressSanitizer is not available on the pool."""
+truncated and garbage files, the host half of findHomography under ASan + UBSan, the host -> HBM copies of padded frames under
+ASan, and the keypoint path's thread pool under TSan. CPU builds only — GPU AddressSanitizer is not available on the pool."""
 import os
 import shutil
 import subprocess
@@ -131,6 +131,27 @@ def test_async_upload_under_tsan(tmp_path):
                        preexec_fn=_no_aslr)
     assert r.returncode == 0 and r.stdout.startswith("ok"), r.stdout[-500:] + r.stderr[-3000:]
     assert "WARNING: ThreadSanitizer" not in r.stderr
+
+
+@pytest.mark.timeout(600)
+def test_padded_frame_copies_under_asan(tmp_path):
+    """Host frames that are windows ending on the last byte of their heap blocks, through AsyncUpload and the byte count
+    every other copy site takes (context.h: frame_copy_bytes): no copy may read the last row's padding."""
+    exe = str(tmp_path / "upload_asan")
+    _build("upload_asan.cpp", exe, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=500)
+    assert r.returncode == 0 and r.stdout.startswith("ok"), r.stdout[-500:] + r.stderr[-3000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
+@pytest.mark.timeout(600)
+def test_warp_frame_flags_on_the_host(tmp_path):
+    """WARPFRAME_SRC_ALIGNED4 exactly for dword-aligned bases and strides (common.h: warp_frame_flags): the gate of the warp
+    kernels' dword windows, which a comparison of results cannot see on hardware that loads unaligned dwords."""
+    exe = str(tmp_path / "warp_flags")
+    _build("warp_flags_harness.cpp", exe, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=500)
+    assert r.returncode == 0 and r.stdout.startswith("ok"), r.stdout[-500:] + r.stderr[-3000:]
 
 
 @pytest.mark.timeout(600)
