@@ -52,6 +52,7 @@ enum { STK_METHOD_LEAST_SQUARES = 0, STK_METHOD_LMEDS = 4, /* KeyPointMatchParam
 enum { STK_BORDER_CONSTANT = 0, STK_BORDER_REPLICATE = 1, STK_BORDER_REFLECT = 2,
        STK_BORDER_WRAP = 3, STK_BORDER_REFLECT_101 = 4, STK_BORDER_TRANSPARENT = 5 };
 enum { STK_HOST = 0, STK_DEVICE = 1 };
+enum { STK_INTER_LINEAR = 1, STK_INTER_CUBIC = 2 };   /* option "warp_interpolation"; OpenCV's INTER_LINEAR / INTER_CUBIC numbers */
 enum { STK_DEPTH_U8 = 8, STK_DEPTH_U16 = 16, STK_DEPTH_F32 = 32 };
 
 /* ---- parameter mirrors -------------------------------------------------- */
@@ -109,6 +110,14 @@ typedef struct {
                                          are used — or behind the last one: windows are used on rows 0 .. height - 2 only (the
                                          interior test keeps a row to spare), and the 8-byte load of the last row's last pixel
                                          pair backs off by 2 bytes (warp_body.h, the rim path).
+                                         Under "warp_interpolation" = STK_INTER_CUBIC the generic cubic kernel (warp_accumulate_cubic_kernel,
+                                         warp_cubic_body.h) reads pixels only, element by element: the 4 x 4 taps of a footprint that lies
+                                         wholly inside the frame, and the generic linear kernel's clamped taps elsewhere. The u8 BGR fast kernel
+                                         (warp_accumulate_cubic_u8c3_kernel) reads a footprint row's twelve bytes as one 16-byte window from
+                                         (offset & ~3) when bases and strides are dword-aligned: up to 4 bytes past the last pixel of a row, on
+                                         rows 0 .. height - 2 only (its vote keeps a row to spare below the footprint), never before the row's
+                                         first pixel; everywhere else it reads exactly the twelve bytes, or the linear sample's clamped taps.
+                                         Nothing before the first or behind the last pixel of the span.
                                          The preparation kernels (kernels_prep.hip, kernels_quality.hip) read pixels only. */
 } stk_frames;
 
@@ -229,6 +238,14 @@ void        stk_host_free(void* p);
  *   "kp_workers"         host threads for the per-frame host steps of the keypoint path (Harris cull, RANSAC)
  *   "warp_subpixel_bits" 0 = exact f32 coordinates (OpenCV >= 4.11 kernels); 5 = classic 1/32-px quantised table
  *                        (changes results: it selects the other OpenCV behaviour)
+ *   "warp_interpolation" 1 = STK_INTER_LINEAR (default): bilinear samples, the reference's INTER_LINEAR; 2 = STK_INTER_CUBIC: the
+ *                        bicubic fold defined below ("Bicubic fold"), for every call that folds: stk_warp_accumulate, the
+ *                        whole-stack, shard, mixed-size, files, hybrid and ranked calls, and the clip, quantile, weighted,
+ *                        moments and normalised-rejection combines (changes results: an extension beyond the reference, which
+ *                        knows bilinear samples only). Any other value: STK_INVALID_PARAMS. Cubic is defined on exact
+ *                        coordinates only: with "warp_subpixel_bits" = 5 every call that folds returns STK_INVALID_PARAMS (the
+ *                        pair is checked at the call, so the two options may be set in either order). Alignment (ECC,
+ *                        ORB, homography) does not depend on it: warps, iteration counts and `dropped` are the same
  *   "profile"            0 off, 1 per-stage events (stk_get_timing), 2 + event pairs around ECC launches
  *   "profile_stride"     with profile = 2: bracket every n-th ECC launch only
  *   "prep_stream"        1 (default): ECC templates of a run of frames by the streaming grey + blur kernel, one launch per
@@ -289,6 +306,37 @@ stk_status stk_keypoint_match_shard(stk_ctx* ctx, const stk_frames* frames,
 /* img / (n as f64)  ==  img * (float)(1.0/n)  (lib.rs:339-345, 836-839). In place if out==sum. */
 stk_status stk_finalize_mean(stk_ctx* ctx, const stk_image_f32* sum, int64_t n_frames,
                              stk_image_f32* out);
+
+/* ---- Bicubic fold: an EXTENSION beyond the reference ------------------------------------------------
+ * The reference samples bilinearly (INTER_LINEAR, lib.rs:296, 541, 787, 799, 969, 980), and so does every fold here by
+ * default. Option "warp_interpolation" = STK_INTER_CUBIC replaces the sample — and nothing else — in every call that folds
+ * and every combine built on the fold. For destination pixel (x, y), table entry i and channel c:
+ *   - (X, Y), `finite`, ix = floor X, iy = floor Y, tx = X - ix and ty = Y - iy are exactly what the linear fold computes
+ *     under warp_subpixel_bits = 0: the same fma chains, the same division, the same finite test.
+ *   - Footprint test: finite && ix >= 1 && ix + 2 <= sw - 1 && iy >= 1 && iy + 2 <= sh - 1 (sw x sh: the source frame).
+ *   - Where the test fails the sample is the linear fold's sample, bit for bit, border mode and border value included.
+ *     That covers frames narrower or lower than 4 pixels and the one-pixel ring around every warped frame's image: the
+ *     resampler drops to the lower order at the edge, it does not invent taps.
+ *   - kappa (the coverage weight of the weighted and normalised-rejection combines) is the linear fold's everywhere. It
+ *     is exactly 1.0f wherever the test holds, so participation, `coverage`, the overlap moments and every rim rule keep
+ *     their meaning unchanged.
+ *   - Where the test holds, with A = -0.75f (OpenCV's INTER_CUBIC kernel in factored form); all values f32, each
+ *     operation rounded on its own except where an fma is written. For t in {tx, ty}:
+ *         u = 1 - t;  tt = t * t;  uu = u * u
+ *         w0 = (A * t) * uu
+ *         w1 = fma(fma(1.25f, t, -2.25f), tt, 1.0f)
+ *         w2 = fma(fma(1.25f, u, -2.25f), uu, 1.0f)
+ *         w3 = (A * u) * tt
+ *         p[r][k] = (float)src[iy - 1 + r][ix - 1 + k][c] * alpha          r, k = 0 .. 3
+ *         h_r = fma(wx3, p[r][3], fma(wx2, p[r][2], fma(wx1, p[r][1], wx0 * p[r][0])))
+ *         s   = fma(wy3, h_3,     fma(wy2, h_2,     fma(wy1, h_1,     wy0 * h_0)))
+ * Consequences:
+ *   - t = 0 gives the weights (-0, 1, 0, -0): an integer translation of finite data returns the linear fold's bits.
+ *   - t = 0.5 gives exactly (-3, 19, 19, -3) / 32.
+ *   - The weights have negative lobes (sum |w| <= 1.375 per axis): a sample may leave the range of its taps, and the
+ *     stacked image is not clamped.
+ *   - It is NOT bit-matched to OpenCV's INTER_CUBIC warp, which quantises coordinates to 1/32 px; nothing here pins that.
+ * Cubic is defined on exact coordinates only: with warp_subpixel_bits = 5 every call that folds is STK_INVALID_PARAMS. */
 
 /* ---- sigma-clipped stacking: an EXTENSION beyond the reference ---------------------------------------
  * Kappa-sigma rejection over the same samples the mean adds: per pixel and channel the samples s_i are the warped,

@@ -9,6 +9,7 @@ Importing the package is cheap and never touches the GPU; the shared library is 
 use (api.Stacker / _ffi.load) and there is no CPU fallback.
 """
 from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_WRAP,  # noqa: F401
+                  INTER_CUBIC, INTER_LINEAR,
                   LEAST_SQUARES, LMEDS, RANSAC, RHO, EccMatchParameters, HipError, InvalidParams, IoError,
                   KeyPointMatchParameters, MotionType, NotEnoughFiles, NotImplementedYet, OpenCvError,
                   ProcessingError, QuantileParameters, SelectParameters, SigmaClipParameters, Stacker, StackerError, WeightParameters,

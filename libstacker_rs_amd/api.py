@@ -25,6 +25,7 @@ from . import _ffi
 # OpenCV constants the reference passes through
 RANSAC, LMEDS, RHO, LEAST_SQUARES = 8, 4, 16, 0
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101, BORDER_TRANSPARENT = range(6)
+INTER_LINEAR, INTER_CUBIC = 1, 2          # option "warp_interpolation" (OpenCV's numbers)
 HOST, DEVICE = 0, 1
 
 

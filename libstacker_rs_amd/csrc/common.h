@@ -173,6 +173,7 @@ struct WarpArgs {
     int is_affine;
     int subpixel_bits;           // 0 or 5
     int tune;                    // launch shape of the u8 fast path (option "warp_tune")
+    int interp;                  // STK_INTER_LINEAR / STK_INTER_CUBIC (option "warp_interpolation"; cubic: warp_cubic_body.h)
 };
 
 // One sigma-clipping pass over the fold's frames (kernels_clip.hip; definition: include/stacker.h, stk_clip_params). The

@@ -56,6 +56,7 @@ struct stk_ctx {
     std::string err;
     int opt_ecc_slots = 0;        // 0 = auto
     int opt_subpixel_bits = 0;
+    int opt_interp = STK_INTER_LINEAR;    // option "warp_interpolation": the fold's resampling kernel (cubic needs opt_subpixel_bits == 0: check_frames)
     int opt_profile = 1;
     int opt_ecc_chunk = 0;        // (iterate, solve) pairs between two polls of the completion counter; 0 = by frame size (stacker.cpp: ecc_run)
     int opt_profile_stride = 1;   // profile = 2: bracket every n-th ECC pixel pass with an event pair
@@ -126,7 +127,15 @@ inline size_t frame_copy_bytes(const stk_frames* f) {
     return frame_copy_bytes(f->row_stride_bytes ? f->row_stride_bytes : tight, f->width, f->height, f->channels, f->depth);
 }
 stk_status resolve_frames(stk_ctx* ctx, const stk_frames* f, std::vector<const void*>& dev);
-stk_status check_frames(stk_ctx* ctx, const stk_frames* f, bool need_bgr);
+// folds: the call samples frames through warps (every stacking call): the fold's option pair is checked here, at the call
+stk_status check_frames(stk_ctx* ctx, const stk_frames* f, bool need_bgr, bool folds = true);
+// the bicubic fold is defined on exact coordinates only (include/stacker.h); the two options may be set in either order,
+// so the pair is checked by every call that folds (inline: the files calls check it before they read a file)
+inline stk_status check_fold_options(stk_ctx* ctx) {
+    if (ctx->opt_interp == STK_INTER_CUBIC && ctx->opt_subpixel_bits != 0)
+        return fail(ctx, STK_INVALID_PARAMS, "warp_interpolation = 2 (STK_INTER_CUBIC) needs warp_subpixel_bits = 0: the bicubic fold is defined on exact coordinates only");
+    return STK_OK;
+}
 // (w, h): the SOURCE frames' size; (dw, dh): the accumulator's, 0 = the same (a stack of one geometry)
 stk_status warp_fold(stk_ctx* ctx, std::vector<WarpFrame>& wf, int depth, int w, int h, int cn,
                      size_t src_row_bytes, double alpha, int border_mode, const double* border_value,

@@ -700,6 +700,7 @@ stk_status load_image(stk_ctx* ctx, const char* path, std::vector<unsigned char>
 template <typename Call>
 stk_status match_files(stk_ctx* ctx, const char* const* paths, int32_t n, Call call, const std::function<stk_status()>* on_mixed_sizes = nullptr) {
     if (!ctx) return STK_INVALID_PARAMS;
+    if (const stk_status fo = check_fold_options(ctx)) return fo;                         // every *_files call folds: before any file is read
     if (n <= 0 || !paths) return fail(ctx, STK_NOT_ENOUGH_FILES, "Not enough files");      // lib.rs:155-157, 725-727
     Pnm first;
     std::vector<unsigned char> file0;

@@ -11,7 +11,7 @@
 // The shifted moments keep the variance accurate (the samples sit close to c). Cost over the mean fold's per-sample work:
 // a subtract, a multiply, two adds, two compares and the selects — the c / L / U planes are read once and written once per
 // pass, like the accumulator.
-#include "warp_body.h"
+#include "warp_cubic_body.h"
 
 namespace stk {
 
@@ -110,6 +110,11 @@ struct ClipU8C3 {
 
 hipError_t launch_clip_pass(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
     if (a.n_frames <= 0) return hipErrorInvalidValue;
+    if (a.interp == STK_INTER_CUBIC) {
+        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
+        if (warp_u8c3_applies(a, depth)) return launch_warp_cubic_u8c3<true, ClipU8C3>(a, c, g, s);
+        return launch_warp_cubic<true, ClipGeneric>(a, c, depth, g, s);
+    }
     if (warp_u8c3_applies(a, depth)) {
         // the mean fold's default launch shape (one wave per row of 64 pixels, four frames in flight)
         const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
@@ -268,6 +273,11 @@ struct ClipWU8C3 {
 
 hipError_t launch_clip_pass_weighted(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
     if (a.n_frames <= 0 || !c.coef) return hipErrorInvalidValue;
+    if (a.interp == STK_INTER_CUBIC) {
+        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
+        if (warp_u8c3_applies(a, depth)) return launch_warp_cubic_u8c3<true, ClipWU8C3>(a, c, g, s);
+        return launch_warp_cubic<true, ClipWGeneric>(a, c, depth, g, s);
+    }
     if (warp_u8c3_applies(a, depth)) {
         const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
         if (a.is_affine) warp_accumulate_u8c3_kernel<true, 1, 4, true, ClipWU8C3><<<g, 256, 0, s>>>(a, c);

@@ -12,7 +12,7 @@
 // its G slots (keys[g * 256 + tid], consecutive lanes on consecutive 16-byte slots: conflict-free ds_read_b128).
 // s_(j) by MSB-first bisection: 32 rounds of "how many keys <= prefix | (2^b - 1)". s_(j+1) (only where g != 0) by one
 // more round: s_(j) again if at least j + 2 keys are <= s_(j), else the smallest key above it.
-#include "warp_body.h"
+#include "warp_cubic_body.h"
 
 namespace stk {
 
@@ -148,6 +148,11 @@ hipError_t launch_quantile_select(const float* band, size_t m, int n, int j, flo
 
 hipError_t launch_quantile_store(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
     if (a.n_frames <= 0 || c.band_rows <= 0 || a.dh != c.y0 + c.band_rows) return hipErrorInvalidValue;
+    if (a.interp == STK_INTER_CUBIC) {
+        const dim3 g((a.dw + 63) / 64, (c.band_rows + 3) / 4);
+        if (warp_u8c3_applies(a, depth)) return launch_warp_cubic_u8c3<true, FoldStore<3>>(a, c, g, s);
+        return launch_warp_cubic<true, FoldStore>(a, c, depth, g, s);
+    }
     if (warp_u8c3_applies(a, depth)) {
         // the mean fold's default launch shape (one wave per row of 64 pixels, four frames in flight)
         const dim3 g((a.dw + 63) / 64, (c.band_rows + 3) / 4);
@@ -299,6 +304,11 @@ hipError_t launch_quantile_select_masked(const float* band, size_t m, int n, flo
 
 hipError_t launch_quantile_store_weighted(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
     if (a.n_frames <= 0 || c.band_rows <= 0 || a.dh != c.y0 + c.band_rows || !c.coef) return hipErrorInvalidValue;
+    if (a.interp == STK_INTER_CUBIC) {
+        const dim3 g((a.dw + 63) / 64, (c.band_rows + 3) / 4);
+        if (warp_u8c3_applies(a, depth)) return launch_warp_cubic_u8c3<true, FoldStoreW<3>>(a, c, g, s);
+        return launch_warp_cubic<true, FoldStoreW>(a, c, depth, g, s);
+    }
     if (warp_u8c3_applies(a, depth)) {
         const dim3 g((a.dw + 63) / 64, (c.band_rows + 3) / 4);
         if (a.is_affine) warp_accumulate_u8c3_kernel<true, 1, 4, true, FoldStoreW<3>><<<g, 256, 0, s>>>(a, c);

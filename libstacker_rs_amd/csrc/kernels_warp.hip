@@ -10,7 +10,9 @@
 // NOT HBM-bound: 3 bytes per pixel and frame carry ~65 vector instructions (~108 issue slots at gfx950's rates, twelve
 // byte conversions alone are 24: tools/valu_rates.hip) — the vector pipe is the limit. No LDS needed for
 // the gather (footprints of neighbouring lanes overlap in L1/L2).
-#include "warp_body.h"
+// Option "warp_interpolation" = STK_INTER_CUBIC sends every launch to the bicubic kernels of warp_cubic_body.h instead
+// (WarpArgs::interp; an extension beyond the reference).
+#include "warp_cubic_body.h"
 
 namespace stk {
 
@@ -169,6 +171,10 @@ hipError_t launch_warp_frames_from_ecc(const EccFrameResult* results, const void
 
 hipError_t launch_warp_accumulate(const WarpArgs& a, int depth, hipStream_t s) {
     dim3 grid((a.dw + 63) / 64, (a.dh + 3) / 4);
+    if (a.interp == STK_INTER_CUBIC) {
+        if (warp_u8c3_applies(a, depth)) return launch_warp_cubic_u8c3<false, NoClip>(a, ClipArgs{}, grid, s);
+        return launch_warp_cubic<false, NoClipN>(a, ClipArgs{}, depth, grid, s);
+    }
     if (warp_u8c3_applies(a, depth)) {
         const int v = a.tune & 0xff;                // tuning: bits 0-1 tile shape, bits 4-5 frames in flight
 #define STK_U8C3(WX, WU)                                                                                   \

@@ -9,7 +9,7 @@
 //     bit), grid z = entry - 1. A thread walks `reps` stepped rows of one entry privately in f64 before its wave reduces by
 //     lane shuffles and writes one partial; moments_reduce_kernel then adds an entry's partials in index order. The order
 //     of every addition is fixed by the geometry and the step alone: the same bits on every call. No atomics.
-#include "warp_body.h"
+#include "warp_cubic_body.h"
 
 namespace stk {
 
@@ -34,6 +34,11 @@ __global__ __launch_bounds__(64) void moments_reduce_kernel(const double* __rest
 
 hipError_t launch_weighted_fold(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
     if (a.n_frames <= 0) return hipErrorInvalidValue;
+    if (a.interp == STK_INTER_CUBIC) {
+        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
+        if (warp_u8c3_applies(a, depth)) return launch_warp_cubic_u8c3<true, FoldWeighted<3>>(a, c, g, s);
+        return launch_warp_cubic<true, FoldWeighted>(a, c, depth, g, s);
+    }
     if (warp_u8c3_applies(a, depth)) {
         // the mean fold's default launch shape (one wave per row of 64 pixels, four frames in flight)
         const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
@@ -75,8 +80,14 @@ hipError_t launch_overlap_moments(const WarpArgs& a, ClipArgs c, int depth, int 
     const MomentsPlan p = moments_plan(a.dw, a.dh, step);
     c.step = step; c.reps = p.reps;
     const dim3 grid(p.bx, p.by, a.n_frames - 1);
+    const bool cubic = a.interp == STK_INTER_CUBIC;
+    if (cubic) {
+        const hipError_t ce = launch_warp_cubic<true, FoldMoments>(a, c, depth, grid, s);
+        if (ce != hipSuccess) return ce;
+    }
 #define STK_MOMENTS_CASE(T, CN) warp_accumulate_kernel<T, CN, true, FoldMoments<CN>><<<grid, 256, 0, s>>>(a, c)
-    if (depth == 8 && a.cn == 3) STK_MOMENTS_CASE(uint8_t, 3);
+    if (cubic) {}
+    else if (depth == 8 && a.cn == 3) STK_MOMENTS_CASE(uint8_t, 3);
     else if (depth == 8 && a.cn == 1) STK_MOMENTS_CASE(uint8_t, 1);
     else if (depth == 8 && a.cn == 4) STK_MOMENTS_CASE(uint8_t, 4);
     else if (depth == 16 && a.cn == 3) STK_MOMENTS_CASE(uint16_t, 3);

@@ -785,6 +785,7 @@ stk_status keypoint_align_impl(stk_ctx* ctx, const stk_frames* frames, const stk
             }
             hk->opt_kp_workers = ctx->opt_kp_workers; hk->opt_orb_patch_blur = ctx->opt_orb_patch_blur; hk->opt_orb_resize_tables = ctx->opt_orb_resize_tables; hk->opt_orb_device_cull = ctx->opt_orb_device_cull; hk->opt_kp_tail_priority = ctx->opt_kp_tail_priority; hk->opt_profile = ctx->opt_profile;
             hk->opt_upload_batch = ctx->opt_upload_batch;
+            hk->opt_subpixel_bits = ctx->opt_subpixel_bits; hk->opt_interp = ctx->opt_interp;      // (the lanes do not fold; kept equal all the same)
             timing_begin(hk);
             if (threads > 1) hk->shared_pool = ctx->shared_pool ? ctx->shared_pool : ctx->host_pool;
             HIP_TRY(hipStreamWaitEvent(hk->stream, ctx->gate_ev, 0));

@@ -44,6 +44,7 @@ stk_status stk_keypoint_match_mixed(stk_ctx* ctx, const stk_frames* frames, cons
     }
     // (a multi-device context takes such a stack on its own device alone, frame by frame: the owning context is member 0)
     if (!params) return fail(ctx, STK_INVALID_PARAMS, "null params");
+    if (const stk_status fo = check_fold_options(ctx)) return fo;
     if (frames->channels != 3 && frames->channels != 4) return fail(ctx, STK_BACKEND_ERROR, "cvtColor(BGR2GRAY): frames must have 3 or 4 channels (utils.rs:136)");
     const int cn = frames->channels;
     if (frames->depth != 8) return fail(ctx, STK_BACKEND_ERROR, "ORB: only 8-bit images are supported");

@@ -154,7 +154,7 @@ stk_status ranked_list(stk_ctx* ctx, const stk_frames* frames, const stk_select_
 extern "C" {
 
 stk_status stk_stack_sharpness(stk_ctx* ctx, const stk_frames* frames, int32_t ksize, double* scores) {
-    stk_status st = check_frames(ctx, frames, false);
+    stk_status st = check_frames(ctx, frames, false, false);
     if (st) return st;
     if (!scores) return fail(ctx, STK_INVALID_PARAMS, "null scores");
     if ((st = quality_check(ctx, frames, ksize))) return st;

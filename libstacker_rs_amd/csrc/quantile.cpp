@@ -91,7 +91,7 @@ stk_status quantile_bands(stk_ctx* ctx, int n_frames, int depth, int w, int h, i
     a.border_mode = border_mode;
     for (int k = 0; k < 4; k++) a.bv[k] = border_value ? (float)border_value[k] : 0.f;
     a.acc = nullptr; a.dw = w; a.acc_stride = 0;
-    a.is_affine = is_affine; a.subpixel_bits = ctx->opt_subpixel_bits; a.tune = 0;
+    a.is_affine = is_affine; a.subpixel_bits = ctx->opt_subpixel_bits; a.tune = 0; a.interp = ctx->opt_interp;
     ClipArgs ca{};
     ca.band = band;
     ca.plane_stride = row;

@@ -34,8 +34,9 @@ stk_status resolve_frames(stk_ctx* ctx, const stk_frames* f, std::vector<const v
     return STK_OK;
 }
 
-stk_status check_frames(stk_ctx* ctx, const stk_frames* f, bool need_bgr) {
+stk_status check_frames(stk_ctx* ctx, const stk_frames* f, bool need_bgr, bool folds) {
     if (!ctx) return STK_INVALID_PARAMS;
+    if (folds) { const stk_status fo = check_fold_options(ctx); if (fo) return fo; }
     if (!f || f->n <= 0 || !f->data) return fail(ctx, STK_NOT_ENOUGH_FILES, "Not enough files");
     if (f->width <= 0 || f->height <= 0) return fail(ctx, STK_INVALID_PARAMS, "bad frame geometry");
     if (f->depth != 8 && f->depth != 16 && f->depth != 32) return fail(ctx, STK_INVALID_PARAMS, "depth must be 8, 16 or 32");
@@ -156,6 +157,7 @@ stk_status set_option_one(stk_ctx* ctx, const char* name, int64_t value) {
     const std::string n(name);
     if (n == "ecc_slots") { if (value < 0 || value > 256) return fail(ctx, STK_INVALID_PARAMS, "ecc_slots out of range"); ctx->opt_ecc_slots = (int)value; }
     else if (n == "warp_subpixel_bits") { if (value != 0 && value != 5) return fail(ctx, STK_INVALID_PARAMS, "warp_subpixel_bits must be 0 or 5"); ctx->opt_subpixel_bits = (int)value; }
+    else if (n == "warp_interpolation") { if (value != STK_INTER_LINEAR && value != STK_INTER_CUBIC) return fail(ctx, STK_INVALID_PARAMS, "warp_interpolation must be 1 (STK_INTER_LINEAR) or 2 (STK_INTER_CUBIC)"); ctx->opt_interp = (int)value; }
     else if (n == "profile") ctx->opt_profile = (int)value;
     else if (n == "ecc_chunk") { if (value < 0 || value > 64) return fail(ctx, STK_INVALID_PARAMS, "ecc_chunk out of range"); ctx->opt_ecc_chunk = (int)value; }
     else if (n == "ecc_ring") ctx->opt_ecc_ring = value != 0;
@@ -483,7 +485,7 @@ stk_status warp_fold_enqueue(stk_ctx* ctx, int n_frames, int depth, int w, int h
     a.border_mode = border_mode;
     for (int c = 0; c < 4; c++) a.bv[c] = border_value ? (float)border_value[c] : 0.f;
     a.acc = acc; a.dw = dw > 0 ? dw : w; a.dh = dh > 0 ? dh : h; a.acc_stride = acc_stride_floats;
-    a.accumulate = accumulate; a.is_affine = is_affine; a.subpixel_bits = ctx->opt_subpixel_bits; a.tune = ctx->opt_warp_tune;
+    a.accumulate = accumulate; a.is_affine = is_affine; a.subpixel_bits = ctx->opt_subpixel_bits; a.tune = ctx->opt_warp_tune; a.interp = ctx->opt_interp;
     HIP_TRY(launch_warp_accumulate(a, depth, ctx->stream));
     ctx->timing.warp_launches += 1;
     ctx->timing.warp_frames += (int64_t)n_frames;
@@ -820,7 +822,7 @@ stk_status stk_ecc_match(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_p
 
 // ---- stage-level entry points ------------------------------------------------------------------
 stk_status stk_grey(stk_ctx* ctx, const stk_frames* f, void* out) {
-    stk_status st = check_frames(ctx, f, true);
+    stk_status st = check_frames(ctx, f, true, false);
     if (st) return st;
     if (!out) return fail(ctx, STK_INVALID_PARAMS, "null output");
     (void)hipSetDevice(ctx->device);
@@ -836,7 +838,7 @@ stk_status stk_grey(stk_ctx* ctx, const stk_frames* f, void* out) {
 }
 
 stk_status stk_convert_f32(stk_ctx* ctx, const stk_frames* f, double alpha, float* out) {
-    stk_status st = check_frames(ctx, f, false);
+    stk_status st = check_frames(ctx, f, false, false);
     if (st) return st;
     if (!out) return fail(ctx, STK_INVALID_PARAMS, "null output");
     if (f->row_stride_bytes && f->row_stride_bytes != (size_t)f->width * f->channels * (f->depth / 8))
@@ -875,7 +877,7 @@ stk_status stk_gaussian_blur_f32(stk_ctx* ctx, const void* grey, int32_t depth, 
 }
 
 stk_status stk_grey_blur_f32(stk_ctx* ctx, const stk_frames* f, int32_t ksize, float* out) {
-    stk_status st = check_frames(ctx, f, true);
+    stk_status st = check_frames(ctx, f, true, false);
     if (st) return st;
     if (!out) return fail(ctx, STK_INVALID_PARAMS, "null output");
     // (16-bit frames: only the hybrid extension runs ECC on them, on float(grey16); the stage is exposed for its tests)

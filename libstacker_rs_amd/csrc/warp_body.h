@@ -17,6 +17,10 @@
 // stepped pixels, a thread walking ClipArgs::reps stepped rows before its wave reduces.
 // The normalised, coverage-aware rejection combines add two states that take kappa through the same hooks: the weighted
 // clip (ClipWGeneric<CN> / ClipWU8C3, kernels_clip.hip) and the store mode with participation (FoldStoreW<CN>, below).
+// The bicubic fold (warp_cubic_body.h) is a second kernel that speaks the same hooks. What it shares with the generic kernel
+// here is shared as text, in two fragments that both include inside their frame loops: the coordinates and the bilinear
+// sample (warp_coords.inc.h, warp_linear_sample.inc.h). Text, not helper functions: see the note at
+// warp_accumulate_kernel; the instantiations below compile to the instructions they had before the fragments existed.
 #pragma once
 #include <type_traits>
 
@@ -106,75 +110,10 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
     for (int f = 0; f < (MOMENTS ? 2 : a.n_frames); f++) {
         const WarpFrame* fr = a.frames + (MOMENTS ? f * (1 + (int)blockIdx.z) : f);
         const T* __restrict__ src = (const T*)fr->src;
-        int ix, iy;
-        float ax = 0, ay = 0;
-        float w00 = 0, w01 = 0, w10 = 0, w11 = 0;
-        bool finite = true;
-        if (a.subpixel_bits == 0) {
-            // OpenCV >= 4.11 kernels: f32 matrix, fma chains, true division, floor, lerp by fma
-            float X = __builtin_fmaf(fr->M[0], fx, __builtin_fmaf(fr->M[1], fy, fr->M[2]));
-            float Y = __builtin_fmaf(fr->M[3], fx, __builtin_fmaf(fr->M[4], fy, fr->M[5]));
-            if (!a.is_affine) {
-                const float W = __builtin_fmaf(fr->M[6], fx, __builtin_fmaf(fr->M[7], fy, fr->M[8]));
-                X = X / W; Y = Y / W;
-            }
-            finite = (__builtin_fabsf(X) < 1e9f) & (__builtin_fabsf(Y) < 1e9f);   // false for NaN / inf
-            const float flx = __builtin_floorf(X), fly = __builtin_floorf(Y);
-            ix = finite ? (int)flx : -100000; iy = finite ? (int)fly : -100000;
-            ax = finite ? X - flx : 0.0f; ay = finite ? Y - fly : 0.0f;
-        } else {
-            // classic remap path: 1/32-pixel quantised coordinates, 4-weight table
-            int Xi, Yi;
-            const double* M = fr->Md;
-            if (a.is_affine) {
-                const int adx = sat_int_d(M[0] * px * 1024), bdx = sat_int_d(M[3] * px * 1024);
-                const int X0 = sat_int_d((M[1] * py + M[2]) * 1024) + 16;
-                const int Y0 = sat_int_d((M[4] * py + M[5]) * 1024) + 16;
-                Xi = (X0 + adx) >> 5; Yi = (Y0 + bdx) >> 5;
-            } else {
-                double W = M[6] * px + M[7] * py + M[8];
-                W = W != 0 ? 32.0 / W : 0;
-                const double Xd = fmax(-2147483648.0, fmin(2147483647.0, (M[0] * px + M[1] * py + M[2]) * W));
-                const double Yd = fmax(-2147483648.0, fmin(2147483647.0, (M[3] * px + M[4] * py + M[5]) * W));
-                Xi = sat_int_d(Xd); Yi = sat_int_d(Yd);
-            }
-            ix = Xi >> 5; iy = Yi >> 5;
-            const float qx = (float)(Xi & 31) * (1.f / 32), qy = (float)(Yi & 31) * (1.f / 32);
-            const float ux = 1.f - qx, uy = 1.f - qy;
-            w00 = uy * ux; w01 = uy * qx; w10 = qy * ux; w11 = qy * qx;
-        }
-        int x0 = border_interp(ix, a.sw, mode), x1 = border_interp(ix + 1, a.sw, mode);
-        int y0 = border_interp(iy, a.sh, mode), y1 = border_interp(iy + 1, a.sh, mode);
-        if (!finite) { x0 = x1 = y0 = y1 = (mode == STK_BORDER_CONSTANT) ? -1 : 0; }
-        const bool v00 = (x0 >= 0) & (y0 >= 0), v01 = (x1 >= 0) & (y0 >= 0);
-        const bool v10 = (x0 >= 0) & (y1 >= 0), v11 = (x1 >= 0) & (y1 >= 0);
-        // clamped addresses keep every load in bounds; out-of-image taps are replaced afterwards
-        const int cx0 = max(x0, 0), cx1 = max(x1, 0), cy0 = max(y0, 0), cy1 = max(y1, 0);
-        const T* r0 = src + (size_t)cy0 * a.src_stride;
-        const T* r1 = src + (size_t)cy1 * a.src_stride;
-        if constexpr (WEIGHTED || MOMENTS || ROBUST) {
-            // kappa from the taps that are inside the frame (the BORDER_CONSTANT validity, whatever the fold's border mode)
-            const bool ix0 = (unsigned)ix < (unsigned)a.sw, ix1 = (unsigned)(ix + 1) < (unsigned)a.sw;
-            const bool iy0 = (unsigned)iy < (unsigned)a.sh, iy1 = (unsigned)(iy + 1) < (unsigned)a.sh;
-            cs.entry(fold_kappa(ix0 & iy0, ix1 & iy0, ix0 & iy1, ix1 & iy1, a.subpixel_bits != 0, ax, ay, w00, w01, w10, w11));
-        }
-#pragma unroll
-        for (int c = 0; c < CN; c++) {
-            const float p00 = v00 ? (float)r0[cx0 * CN + c] * a.alpha : a.bv[c];
-            const float p01 = v01 ? (float)r0[cx1 * CN + c] * a.alpha : a.bv[c];
-            const float p10 = v10 ? (float)r1[cx0 * CN + c] * a.alpha : a.bv[c];
-            const float p11 = v11 ? (float)r1[cx1 * CN + c] * a.alpha : a.bv[c];
-            float v;
-            if (a.subpixel_bits == 0) {
-                const float t0 = __builtin_fmaf(ax, p01 - p00, p00);
-                const float t1 = __builtin_fmaf(ax, p11 - p10, p10);
-                v = __builtin_fmaf(ay, t1 - t0, t0);
-            } else {
-                v = p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11;
-            }
-            if constexpr (CLIP) cs.add(c, v);
-            else sum[c] = sum[c] + v;
-        }
+#define STK_SUBPIX a.subpixel_bits
+#include "warp_coords.inc.h"
+#include "warp_linear_sample.inc.h"
+#undef STK_SUBPIX
     }
     } while (MOMENTS && ++rep < ca.reps);
     if constexpr (CLIP) cs.finish(ca, x, y);

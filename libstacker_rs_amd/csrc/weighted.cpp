@@ -92,7 +92,7 @@ WarpArgs weighted_warp_args(stk_ctx* ctx, int n_entries, int depth, int w, int h
     a.border_mode = border_mode;
     for (int k = 0; k < 4; k++) a.bv[k] = border_value ? (float)border_value[k] : 0.f;
     a.acc = nullptr; a.dw = w; a.dh = h; a.acc_stride = 0;
-    a.is_affine = is_affine; a.subpixel_bits = ctx->opt_subpixel_bits; a.tune = 0;
+    a.is_affine = is_affine; a.subpixel_bits = ctx->opt_subpixel_bits; a.tune = 0; a.interp = ctx->opt_interp;
     return a;
 }
 
