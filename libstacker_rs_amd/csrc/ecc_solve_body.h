@@ -251,7 +251,11 @@ __device__ __forceinline__ void ecc_solve_body(const EccIterArgs& a, int slot, i
     STK_TICK(7);
 
     const double last_rho = prev_rho;
-    double rho = correlation / (imgNorm * tmpNorm);
+    // A zero norm: the zero-mean image or template is identically zero over the mask (a constant frame), or the mask is
+    // empty. OpenCV's correlation is then exactly 0 and rho = 0 / 0. Here sum(u v) and mean(v) sum(u) are f32 column sums
+    // that round differently, and the residue they leave in `correlation` must not pass for an infinite rho with a sign.
+    const double norms = imgNorm * tmpNorm;
+    double rho = norms == 0.0 ? (double)__builtin_nanf("") : correlation / norms;
     const int iter = prev_iter + 1;
     int status = 0;
     bool finished = false;

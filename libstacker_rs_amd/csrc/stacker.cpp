@@ -435,8 +435,21 @@ static stk_status ecc_run(stk_ctx* ctx, const EccPlan& pl, EccCriteria crit, con
       fprintf(stderr, "SOLVE_DBG stage1 %lld ticket %lld sums %lld stats %lld lu %lld iph %lld tail %lld (x10ns)\n", hq.dbg[1] - hq.dbg[0], hq.dbg[2] - hq.dbg[1],
               hq.dbg[4] - hq.dbg[2], hq.dbg[5] - hq.dbg[4], hq.dbg[6] - hq.dbg[5], hq.dbg[7] - hq.dbg[6], hq.dbg[8] - hq.dbg[7]); }
 #endif
-    if (crit.n_iter < 1)
-        for (auto& e : res) { for (int k = 0; k < 9; k++) e.warp[k] = (k % 4 == 0) ? 1.f : 0.f; e.iters = 0; e.status = 0; e.rho = -1; }
+    if (crit.n_iter < 1) {
+        // no iteration ran: findTransformECC leaves the warp it was given untouched, so every frame's result is its initial
+        // warp (the caller's start or the hybrid seed; the identity without one), rho = -1 as the loop initialises it
+        std::vector<float> init;
+        if (init_warps_dev) {
+            init.resize((size_t)pl.n_templates * 9);
+            HIP_TRY(hipMemcpyAsync(init.data(), init_warps_dev, sizeof(float) * init.size(), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+        }
+        for (size_t f = 0; f < res.size(); f++) {
+            EccFrameResult& e = res[f];
+            for (int k = 0; k < 9; k++) e.warp[k] = init_warps_dev ? init[f * 9 + k] : ((k % 4 == 0) ? 1.f : 0.f);
+            e.iters = 0; e.status = 0; e.rho = -1;
+        }
+    }
     for (auto& e : res) ctx->timing.ecc_slot_iterations += e.iters;
     return STK_OK;
 }
@@ -976,7 +989,7 @@ stk_status stk_find_transform_ecc(stk_ctx* ctx, const void* templ, const void* i
     std::vector<EccFrameResult> res;
     st = ecc_run(ctx, pl, crit, ctx->init_warps.as<float>(), res);
     if (st) return st;
-    if (crit.n_iter >= 1) for (int k = 0; k < 9; k++) warp[k] = res[0].warp[k];
+    for (int k = 0; k < 9; k++) warp[k] = res[0].warp[k];    // (no iteration: the start itself, row 2 = 0 0 1 for the 2 x 3 motions)
     if (rho) *rho = res[0].rho;
     if (iterations) *iterations = res[0].iters;
     if (res[0].status) return fail(ctx, STK_BACKEND_ERROR, ecc_status_message(res[0].status));

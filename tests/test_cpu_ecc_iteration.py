@@ -117,6 +117,14 @@ def _iteration(templ_blurred_f32, input_blurred_f32, warp3x3, motion, accumulate
     corr = total(q(tz * iz))
     rho = corr / (img_norm * tmp_norm)
 
+    def lambda_d():
+        """The denominator of lambda, whose sign decides the "correlation is going to be minimized" exit. A Hessian with an
+        exactly zero row has no inverse: Mat::inv then returns the zero matrix and the image projection drops out."""
+        if not H.any(axis=0).all():
+            return corr
+        d = 1.0 / np.sqrt(np.diag(H))
+        return corr - float(tp @ (d * np.linalg.solve(H * d[:, None] * d[None, :], d * ip)))
+
     def finish(solve="f64", ulp_rng=None):
         if solve == "f32":
             new, dp = _solve_f32(m, motion, H, ip, tp, corr, img_norm, lambda lam: np.array(
@@ -136,6 +144,7 @@ def _iteration(templ_blurred_f32, input_blurred_f32, warp3x3, motion, accumulate
         ep = np.array([total(q(J[k] * e)) for k in range(P)])
         dp = solve_spd(ep)
         return _updated(m, dp, motion), float(rho), dp, n / (tw * th)
+    finish.hessian, finish.correlation, finish.rho, finish.lambda_d = H, corr, float(rho), lambda_d
     return finish
 
 
@@ -150,6 +159,13 @@ def ecc_iteration_restate(templ_blurred_f32, input_blurred_f32, warp3x3, motion,
     solve = "f64": the normal equations solved in float64 (symmetrically scaled). solve = "f32": the tail as OpenCV runs
     it (_solve_f32), `ulp_rng` moving every f32 entry by one ulp first."""
     return _iteration(templ_blurred_f32, input_blurred_f32, warp3x3, motion, accumulate)(solve, ulp_rng)
+
+
+def ecc_iteration_lambda(templ_blurred_f32, input_blurred_f32, warp3x3, motion):
+    """(lambda_d, correlation, rho, Hessian) of the iteration's float64 sums at `warp3x3`, without the parameter update:
+    defined also where the iteration ends the run (lambda_d <= 0) or moves nothing (a singular Hessian)."""
+    fin = _iteration(templ_blurred_f32, input_blurred_f32, warp3x3, motion, "f64")
+    return fin.lambda_d(), fin.correlation, fin.rho, fin.hessian
 
 
 SOLVE_DRAWS = 16
