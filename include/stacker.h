@@ -200,6 +200,12 @@ const char* stk_last_error(const stk_ctx* ctx);    /* valid until the next call 
  * restores the context's own stream. */
 stk_status  stk_set_stream(stk_ctx* ctx, void* hip_stream);
 stk_status  stk_get_timing(const stk_ctx* ctx, stk_timing* out);
+/* Device-side event counters of the last whole-stack call, by name (stk_timing keeps its layout). Unknown name:
+ * STK_INVALID_PARAMS.
+ *   "ecc_first_iter_slots"  ECC iteration pass, homography: slot-iterations that took the first-iteration route (option
+ *                           "ecc_first_iter"): one per frame that starts at the identity; 0 with the option off, for the
+ *                           other motion types, under "ecc_variant" 0 and for f32 images. */
+stk_status  stk_get_counter(const stk_ctx* ctx, const char* name, int64_t* out);
 /* Pinned (page-locked) host memory for frames: stacks handed over in such buffers cross PCIe by DMA at link rate and
  * overlap with the alignment of the frames that have already arrived (a decoder — the Rust shim's imread — writes into
  * them directly). Pageable frames work too (the HIP runtime locks large sources on the fly: 25 MB frames measured the same
@@ -217,6 +223,9 @@ void        stk_host_free(void* p);
  *   "ecc_variant"        ECC pixel-pass kernel: 3 production (default), 0 the direct cross-check version
  *   "ecc_ring"           homography pass: 1 (default) frame-0 rows go through a per-wave LDS ring where a strip allows it,
  *                        0 every tap is gathered from global memory; the results are bit-identical
+ *   "ecc_first_iter"     homography pass: 1 (default) the first iteration of a frame that starts at the identity reads frame 0 at
+ *                        its own pixels and takes the sums that do not depend on the frame from one evaluation per call
+ *                        (stk_get_counter "ecc_first_iter_slots"); 0 every iteration takes the general route; the results are bit-identical
  *   "ecc_ring_lookahead" debug: frame-0 rows the ring keeps ahead of the row being fetched (5; 1..4 make its run-time check
  *                        fire, the strips then fall back to the gather loop: stk_timing.ecc_ring_fallbacks); same bits
  *   "ecc_groups"         0 (default): by frame size; 2: the slots form two groups with their own (iterate, solve) launch sequences on

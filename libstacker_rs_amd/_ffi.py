@@ -90,6 +90,7 @@ SIGNATURES = {
     "stk_last_error": (C.c_char_p, [C.c_void_p]),
     "stk_set_stream": (c_status, [C.c_void_p, C.c_void_p]),
     "stk_get_timing": (c_status, [C.c_void_p, C.POINTER(Timing)]),
+    "stk_get_counter": (c_status, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
     "stk_set_option": (c_status, [C.c_void_p, C.c_char_p, C.c_int64]),
     "stk_keypoint_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
                                       C.POINTER(ImageF32), C.POINTER(C.c_int32), C.POINTER(FrameStats)]),

@@ -392,7 +392,12 @@ class Stacker:
     def timing(self) -> dict:
         t = _ffi.Timing()
         self._check(self._lib.stk_get_timing(self._h, C.byref(t)))
-        return {k: getattr(t, k) for k, _ in _ffi.Timing._fields_}
+        d = {k: getattr(t, k) for k, _ in _ffi.Timing._fields_}
+        for name in ("ecc_first_iter_slots",):               # counters outside stk_timing (stk_get_counter)
+            v = C.c_int64(0)
+            self._check(self._lib.stk_get_counter(self._h, name.encode(), C.byref(v)))
+            d[name] = v.value
+        return d
 
     def _out_image(self, m: _Marshalled):
         """f32 HxWxC output placed where the inputs live."""

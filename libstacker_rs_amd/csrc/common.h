@@ -62,6 +62,7 @@ struct EccQueue {
     int frames_done;
     int ready;          // templates [0, ready) exist; raised by the prep stream while frames are still arriving over PCIe
     int ring_fallbacks; // strips of the iteration pass that left the LDS ring for the gather loop at run time (stk_timing.ecc_ring_fallbacks)
+    int first_iter_slots; // slot-iterations of the column pass that took the first-iteration route (stk_get_counter "ecc_first_iter_slots")
 #ifdef STK_SOLVE_TIMING
     long long dbg[16];   // wall_clock64 phase deltas of the last solve of slot 0 (10 ns ticks), debug builds only
 #endif
@@ -93,6 +94,11 @@ struct EccIterArgs {
     int ring_lookahead;          // frame-0 rows the ring keeps ahead of the row being fetched: 5; lower only to provoke the fallback (option ecc_ring_lookahead)
     int* ring_fallbacks;         // device counter: strips whose ring bounds failed the run-time check and were redone by the gather loop (EccQueue::ring_fallbacks)
     int units_q, units_r;        // column-walking pass: (column strip, row) units per wave and the remainder (set by launch_ecc_iter)
+    // column-walking homography pass, first iteration of a frame that starts at the identity (option ecc_first_iter): the
+    // block partials [ECC_MAX_SUMS][nb] of that iteration as the pass itself computed them once for this call; the sums
+    // that do not read the template are copied from here. Null: every iteration takes the general route
+    const double* first_sums;
+    int* first_iter_slots;       // device counter: slot-iterations that took that route (EccQueue::first_iter_slots)
 };
 
 struct WarpFrame {
@@ -237,6 +243,8 @@ hipError_t launch_ref_planes(const float* blurred, int in_stride, int w, int h, 
 // variant: 3 = production kernels, 0 = direct cross-check version
 hipError_t launch_ecc_iter_col(const EccIterArgs& a, int motion, hipStream_t s);   // kernels_ecc_col.hip; a.units_q / units_r set
 hipError_t launch_ecc_iter(const EccIterArgs& a, int motion, int variant, hipStream_t s);
+// one slot at the start of a frame's life — frame 0, iteration 0, the identity, no centring (kernels_ecc_col.hip)
+hipError_t launch_ecc_first_slot(EccSlot* slot, hipStream_t s);
 hipError_t launch_ecc_solve(const EccIterArgs& a, int motion, EccCriteria crit, EccQueue* queue,
                             EccFrameResult* results, hipStream_t s, const float* init_warps = nullptr);
 hipError_t launch_sharpness(const void* grey, int depth, int w, int h, int metric, int ksize, void* partials, int n_blocks,

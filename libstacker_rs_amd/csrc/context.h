@@ -70,12 +70,14 @@ struct stk_ctx {
     int opt_ecc_ring = 1;         // column-walking ECC pass: frame-0 rows through the per-wave LDS ring (0: always gather from global memory)
     int opt_ecc_groups = 0;       // ECC slots in this many groups with their own launch sequences on two streams (stacker.cpp: ecc_run); 0 = by frame size
     int opt_ecc_ring_lookahead = 5;   // debug: frame-0 rows the ring keeps ahead (5 = production; less makes the run-time check fire and the strip fall back)
+    int opt_ecc_first_iter = 1;   // column-walking homography pass: a frame's first iteration from the identity takes the short route (stacker.cpp: ecc_run); same bits
     int opt_ecc_variant = 3;      // ECC iteration kernel: 3 = production (column-walking homography pass / pipelined affine family), 0 = direct cross-check
     int opt_quantile_band_rows = 0;   // quantile combines: at most this many rows per band of samples; 0 = as many as fit the band budget
     stk_timing timing{};
+    int64_t ecc_first_iter_slots = 0;   // stk_get_counter: slot-iterations of the last call that took the first-iteration route (reset by timing_begin)
     hipEvent_t ev[8] = {};
     hipEvent_t poll_ev[2] = {};
-    int* host_done = nullptr;     // pinned, 16 ints: [0], [1] completion counters of the two chunks in flight, [2] ring fall-back count
+    int* host_done = nullptr;     // pinned, 16 ints: [0], [1] completion counters of the two chunks in flight, [2] ring fall-back count, [3] first-iteration slots
     const void* ref_zeroed_ptr = nullptr;   // the frame-0 planes' zero border exists for this buffer and geometry (ecc_prepare_reference)
     int ref_zeroed_w = 0, ref_zeroed_h = 0;
     std::vector<hipEvent_t> prof_ev;   // event pairs for per-launch timing (option profile = 2)
@@ -84,7 +86,7 @@ struct stk_ctx {
     // device workspaces: locking 6.4 GB of pages for a 256-frame 4K stack costs more than decoding into them
     unsigned char* files_block = nullptr; size_t files_block_cap = 0; bool files_block_pinned = false;
     // workspace
-    DevBuf frames, ref, blur_tmp, templates, slots, queue, results, partials, warpframes, acc, scratch, init_warps, frameptrs;
+    DevBuf frames, ref, blur_tmp, templates, slots, queue, results, partials, first_sums, warpframes, acc, scratch, init_warps, frameptrs;
     DevBuf clip;                  // sigma clipping (clip.cpp): the c, L and U planes
     DevBuf weighted;              // weighted combine (weighted.cpp): image, den plane, per-entry table, moments and their partials
     DevBuf coef;                  // normalised rejection combines (robust.cpp): the per-entry gain / offset / weight table

@@ -123,6 +123,137 @@ struct ColBlend {              // the bilinear samples of a pixel: I, gx, gy
     float Iw, gxw, gyw;
 };
 
+// ---------------------------------------------------------------------------------------------------
+// The first iteration of a frame that starts at the identity (homography; EccIterArgs::first_sums). With warp = I and
+// cI = cT = 0 the general route below computes, for the pixel (x, y) of lane x: 1/w = 1 (the caller has checked that
+// v_rcp_f32 gives exactly 1), (sx, sy) = (x, y), fractions 0, so the "samples" are the (I, gx, gy) of that pixel itself
+// (a blend fma(0, finite, tap) is the tap), every pixel inside the mask, u = I, v = T. The sums that do not read the
+// template — Hessian, J.u, J.m, the mask count, s_u, s_uu — are then the same for every frame and come from first_sums;
+// the 11 that do — J.v, s_v, s_vv, s_x — are accumulated here by the operations of accumulate() in the same order, flushed
+// per strip by the same fold (a sum's addition tree in lane_transpose_sum does not depend on which register it starts
+// in, and a + b = b + a), added to an f64 total per wave and reduced over the block's waves in the same order. Same unit
+// partition, same lane clamp, same `active` test. Two coalesced loads per row and lane, eight rows in flight twice.
+// STK_FIRST_ITER_OWN_KERNEL: 0 (committed: measured faster) = a branch at the top of the iteration kernel; 1 = a kernel of its
+// own, launched in front of the iteration kernel, whose workgroups of such a slot leave at once.
+#ifndef STK_FIRST_ITER_OWN_KERNEL
+#define STK_FIRST_ITER_OWN_KERNEL 0
+#endif
+typedef float f32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
+constexpr int FIRST_NV = 11;       // J.v (8), s_v, s_vv, s_x
+constexpr int FIRST_ROWS = 8;      // rows per batch of loads
+// the slot is at its first iteration from the identity: all nine floats bitwise, no centring yet, 1/w exactly 1
+__device__ __forceinline__ bool first_iter_route(const EccIterArgs& a, const EccSlot* sl, const SlotConst& c) {
+    if (a.first_sums == nullptr || sl->iter != 0) return false;
+    const float m[9] = {c.m0, c.m1, c.m2, c.m3, c.m4, c.m5, c.m6, c.m7, c.m8};
+    bool eye = c.cI == 0.0f && c.cT == 0.0f;
+#pragma unroll
+    for (int k = 0; k < 9; k++) eye = eye && __builtin_bit_cast(unsigned, m[k]) == (k % 4 == 0 ? 0x3f800000u : 0u);
+    return eye && __builtin_amdgcn_rcpf(c.m8) == 1.0f;
+}
+// T: the slot's template; red: 4 x FIRST_NV doubles of LDS for the block's reduction
+__device__ __forceinline__ void ecc_first_iter_body(const EccIterArgs& a, const float* __restrict__ T, int slot, int region,
+                                                    double (*red)[FIRST_NV]) {
+    constexpr int P = 8, NH = 36, NS = NH + 3 * P + 6, R = FIRST_ROWS;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const float* __restrict__ G = a.ref.igg;
+    const size_t t_row = (size_t)a.templ_row_stride * 4, g_row = (size_t)a.ref.stride * 12;     // bytes per row
+    double dsum = 0.0;             // lane L: f64 total over the wave's strips of the sum number bitreverse6(L) of the 11
+    const int g = region * 4 + wave;
+    int u = g * a.units_q + min(g, a.units_r);
+    const int uend = u + a.units_q + (g < a.units_r ? 1 : 0);
+    while (u < uend) {
+        const int col = u / a.th;
+        const int y0 = u - col * a.th;
+        const int y1 = min(a.th, y0 + (uend - u));
+        u += y1 - y0;
+        const int x = col * 64 + lane;
+        const bool active = x < a.tw;
+        const int xc = min(x, a.tw - 1);
+        const float fx = (float)xc;
+        unsigned t_off = (unsigned)xc * 4u, g_off = (unsigned)xc * 12u;       // (row base) + (lane offset): the saddr + voffset form
+        float m0a = 0.f, m0b = 0.f, m0t = 0.f, m1a = 0.f, m1b = 0.f, m1t = 0.f;     // ms0[3..5], ms1[3..5] of the general route
+        float s_v = 0.f, s_vv = 0.f, s_x = 0.f;
+        auto row = [&](float tval, const f32x3_a4 r, float fy) {
+            const float ja = r.y, jb = r.z;                       // gxw * rw, gyw * rw with rw == 1
+            const float jt = -(fx * ja) - (fy * jb);
+            const float vv = tval, um = r.x;                      // tval - cT, Iw - cI with cI == cT == 0
+            const float ca = ja * vv, cb = jb * vv, ct = jt * vv;
+            m0a += ca; m0b += cb; m0t += ct;
+            m1a = __builtin_fmaf(ca, fy, m1a); m1b = __builtin_fmaf(cb, fy, m1b); m1t = __builtin_fmaf(ct, fy, m1t);
+            s_v += vv;
+            s_vv = __builtin_fmaf(vv, vv, s_vv); s_x = __builtin_fmaf(um, vv, s_x);
+        };
+        struct Rows { float t[R]; f32x3_a4 r[R]; };
+        auto load = [&](Rows& b, int y) {                         // rows y .. y + R - 1, all of them below y1
+            const char* tp = (const char*)T + (size_t)y * t_row;
+            const char* gp = (const char*)G + (ptrdiff_t)y * (ptrdiff_t)g_row;
+            asm volatile("" : "+v"(t_off), "+v"(g_off));
+#pragma unroll
+            for (int k = 0; k < R; k++) {
+                b.t[k] = *(const float*)(tp + k * t_row + t_off);
+                b.r[k] = *(const f32x3_a4*)(gp + k * g_row + g_off);
+            }
+        };
+        auto sum_rows = [&](const Rows& b, int y) {
+            if (!active) return;
+#pragma unroll
+            for (int k = 0; k < R; k++) row(b.t[k], b.r[k], (float)(y + k));
+        };
+        int y = y0;
+        const int n_full = (y1 - y0) / R;
+        if (n_full > 0) {                                         // two batches in flight: the loads of one are issued before the sums of the other
+            Rows A, B;
+            load(A, y);
+            int gi = 0;
+            for (; gi + 2 <= n_full; gi += 2) {
+                load(B, y + R);
+                sum_rows(A, y);
+                if (gi + 2 < n_full) load(A, y + 2 * R);
+                sum_rows(B, y + R);
+                y += 2 * R;
+            }
+            if (gi < n_full) { sum_rows(A, y); y += R; }
+        }
+        for (; y < y1; y++) {
+            const float tval = *(const float*)((const char*)T + (size_t)y * t_row + t_off);
+            const f32x3_a4 r = *(const f32x3_a4*)((const char*)G + (ptrdiff_t)y * (ptrdiff_t)g_row + g_off);
+            if (active) row(tval, r, (float)y);
+        }
+        // flush: the powers of X as in the general route (v[NH + P + i] and the last three sums there), the same fold
+        float v[FIRST_NV] = {m0a * fx, m0b * fx, m0t * fx, m1a, m1b, m1t, m0a, m0b, s_v, s_vv, s_x};
+        lane_transpose_sum<FIRST_NV>(v, lane);
+        dsum = dsum + (double)v[0];
+    }
+    const int k0 = (int)(__builtin_bitreverse32((unsigned)lane) >> 26);
+    if (k0 < FIRST_NV) red[wave][k0] = dsum;
+    __syncthreads();
+    if (threadIdx.x < NS) {
+        const int k = threadIdx.x;
+        const int j = k >= NH + P && k < NH + 2 * P ? k - (NH + P) : k >= NH + 3 * P + 3 ? k - (NH + 3 * P + 3) + P : -1;
+        const double s = j >= 0 ? ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j] : a.first_sums[(size_t)k * a.nb + region];
+        a.partials[((size_t)slot * NS + k) * a.nb + region] = s;   // [slot][sum][block]
+    }
+    if (region == 0 && threadIdx.x == 0) atomicAdd(a.first_iter_slots, 1);
+}
+
+#if STK_FIRST_ITER_OWN_KERNEL
+// same block decode as the iteration kernel; a workgroup whose slot does not take the route leaves at once
+__global__ __launch_bounds__(256) void ecc_first_iter_kernel(EccIterArgs a) {
+    const int bid = (int)blockIdx.x;
+    const int xcd = bid & 7, q = bid >> 3;
+    const int slot = a.slot0 + q % a.n_slots;
+    const int region = (q / a.n_slots) * 8 + xcd;
+    const EccSlot* sl = a.slots + slot;
+    const int frame = sl->frame;
+    if (frame < 0) return;
+    SlotConst c;
+    load_slot_const(sl, a, c);
+    if (!first_iter_route(a, sl, c)) return;
+    __shared__ double red[4][FIRST_NV];
+    ecc_first_iter_body(a, a.templates + (size_t)frame * a.templ_plane_stride, slot, region, red);
+}
+#endif
+
 // MOTION: the homography runs the factorised accumulation described above; translation / euclidean / affine have 15 /
 // 21 / 45 sums, nothing to factorise, and keep one plain accumulator per sum (the Jacobian is formed per pixel from the
 // lane's constant X and the row's Y) — same strips, same ring, same fold. Their warps carry (0, 0, 1) in the last row, so
@@ -148,6 +279,14 @@ __global__ __launch_bounds__(256, STK_COL_WG) void ecc_iter_col_kernel(EccIterAr
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     __shared__ __attribute__((aligned(16))) char ring_all[4 * LWAVE];
     char* const ring = ring_all + wave * LWAVE;          // this wave's ring; nothing in it is shared between waves
+    if constexpr (HOMOGRAPHY) {
+        if (first_iter_route(a, sl, c)) {
+#if !STK_FIRST_ITER_OWN_KERNEL
+            ecc_first_iter_body(a, T, slot, region, reinterpret_cast<double (*)[FIRST_NV]>(ring_all));
+#endif
+            return;                                               // (with a kernel of its own: that one has written this slot's partials)
+        }
+    }
 
     const int rs = a.ref.stride;
     const int corner = REF_PAD * rs + REF_PAD;
@@ -668,8 +807,23 @@ __global__ __launch_bounds__(256, STK_COL_WG) void ecc_iter_col_kernel(EccIterAr
     }
 }
 
+__global__ void ecc_first_slot_kernel(EccSlot* sl) {
+    if (threadIdx.x != 0) return;
+    sl->frame = 0; sl->iter = 0;
+    for (int k = 0; k < 9; k++) sl->warp[k] = (k % 4 == 0) ? 1.f : 0.f;
+    sl->cI = 0; sl->cT = 0;
+    sl->rho = -1; sl->last_rho = 0;
+}
+hipError_t launch_ecc_first_slot(EccSlot* slot, hipStream_t s) {
+    ecc_first_slot_kernel<<<1, 64, 0, s>>>(slot);
+    return hipGetLastError();
+}
+
 hipError_t launch_ecc_iter_col(const EccIterArgs& a, int motion, hipStream_t s) {
     const int grid = a.nb * a.n_slots;
+#if STK_FIRST_ITER_OWN_KERNEL
+    if (motion == STK_MOTION_HOMOGRAPHY && a.first_sums) ecc_first_iter_kernel<<<grid, 256, 0, s>>>(a);
+#endif
     switch (motion) {
         case STK_MOTION_HOMOGRAPHY: ecc_iter_col_kernel<STK_MOTION_HOMOGRAPHY><<<grid, 256, 0, s>>>(a); break;
         case STK_MOTION_AFFINE: ecc_iter_col_kernel<STK_MOTION_AFFINE><<<grid, 256, 0, s>>>(a); break;

@@ -98,7 +98,7 @@ void stk_destroy(stk_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (DevBuf* b : {&ctx->frames, &ctx->ref, &ctx->blur_tmp, &ctx->templates, &ctx->slots, &ctx->queue, &ctx->results,
-                      &ctx->partials, &ctx->warpframes, &ctx->acc, &ctx->scratch, &ctx->init_warps, &ctx->frameptrs, &ctx->clip,
+                      &ctx->partials, &ctx->first_sums, &ctx->warpframes, &ctx->acc, &ctx->scratch, &ctx->init_warps, &ctx->frameptrs, &ctx->clip,
                       &ctx->quantile, &ctx->weighted, &ctx->coef, &ctx->quality})
         b->release();
     keypoint_workspace_destroy(ctx->kp);
@@ -142,6 +142,12 @@ stk_status stk_get_timing(const stk_ctx* ctx, stk_timing* out) {
     return STK_OK;
 }
 
+stk_status stk_get_counter(const stk_ctx* ctx, const char* name, int64_t* out) {
+    if (!ctx || !name || !out) return STK_INVALID_PARAMS;
+    if (std::string(name) == "ecc_first_iter_slots") { *out = ctx->ecc_first_iter_slots; return STK_OK; }
+    return STK_INVALID_PARAMS;
+}
+
 stk_status stk_set_option(stk_ctx* ctx, const char* name, int64_t value) {
     if (!ctx || !name) return STK_INVALID_PARAMS;
     for (int i = 1; i < multi_member_count(ctx); i++) {          // a multi-device context: every device gets the knob
@@ -161,6 +167,7 @@ stk_status set_option_one(stk_ctx* ctx, const char* name, int64_t value) {
     else if (n == "profile") ctx->opt_profile = (int)value;
     else if (n == "ecc_chunk") { if (value < 0 || value > 64) return fail(ctx, STK_INVALID_PARAMS, "ecc_chunk out of range"); ctx->opt_ecc_chunk = (int)value; }
     else if (n == "ecc_ring") ctx->opt_ecc_ring = value != 0;
+    else if (n == "ecc_first_iter") ctx->opt_ecc_first_iter = value != 0;
     else if (n == "ecc_groups") { if (value < 0 || value > 2) return fail(ctx, STK_INVALID_PARAMS, "ecc_groups must be 0 (auto), 1 or 2"); ctx->opt_ecc_groups = (int)value; }
     else if (n == "ecc_ring_lookahead") { if (value < 1 || value > 5) return fail(ctx, STK_INVALID_PARAMS, "ecc_ring_lookahead must be 1..5"); ctx->opt_ecc_ring_lookahead = (int)value; }
     else if (n == "ecc_variant") { if (value != 0 && value != 3) return fail(ctx, STK_INVALID_PARAMS, "ecc_variant must be 3 (production) or 0 (direct cross-check)"); ctx->opt_ecc_variant = (int)value; }
@@ -263,7 +270,7 @@ static stk_status ecc_plan(stk_ctx* ctx, int w, int h, int n_templates, int moti
     HIP_TRY(ctx->blur_tmp.reserve(pl.templ_plane_stride * sizeof(float)));
     // (+ 4 rows: the column pass prefetches template rows up to three past the end of a strip, also behind the last row of the last frame)
     HIP_TRY(ctx->templates.reserve(pl.templ_plane_stride * sizeof(float) * std::max(n_templates, 1) + 4 * (size_t)pl.templ_row_stride * sizeof(float) + 1024));
-    HIP_TRY(ctx->slots.reserve(sizeof(EccSlot) * pl.n_slots));
+    HIP_TRY(ctx->slots.reserve(sizeof(EccSlot) * (pl.n_slots + 1)));          // (+ the scratch slot of ecc_run's first-iteration sums)
     HIP_TRY(ctx->queue.reserve(sizeof(EccQueue)));
     HIP_TRY(ctx->results.reserve(sizeof(EccFrameResult) * std::max(n_templates, 1)));
     HIP_TRY(ctx->partials.reserve(sizeof(double) * pl.n_slots * ((size_t)pl.nb * pl.nsums + ECC_MAX_SUMS) + sizeof(int) * pl.n_slots));
@@ -296,8 +303,10 @@ using EccFeed = std::function<stk_status(bool block, int* enqueued)>;
 // `on_done`, when given, is called once the device-side queue is known to have drained, BEFORE the results travel to the
 // host: the caller enqueues there what may follow the alignment in stream order without the host's help (the fold).
 using EccDone = std::function<stk_status()>;
-static stk_status ecc_run(stk_ctx* ctx, const EccPlan& pl, EccCriteria crit, const float* init_warps_dev,
-                          std::vector<EccFrameResult>& res, const EccFeed* feed = nullptr, const EccDone* on_done = nullptr) {
+// `init_warps_host`: the host's copy of init_warps_dev (n_templates x 9; null with it); `depth`: of the images the planes
+// and templates were prepared from.
+static stk_status ecc_run(stk_ctx* ctx, const EccPlan& pl, EccCriteria crit, const float* init_warps_dev, const float* init_warps_host,
+                          int depth, std::vector<EccFrameResult>& res, const EccFeed* feed = nullptr, const EccDone* on_done = nullptr) {
     res.resize(pl.n_templates);
     if (pl.n_templates == 0) return STK_OK;
     // for (i = 1; i <= nIter && fabs(rho - last_rho) >= eps; i++) with rho = -1, last_rho = -eps: not even the first
@@ -323,8 +332,34 @@ static stk_status ecc_run(stk_ctx* ctx, const EccPlan& pl, EccCriteria crit, con
     EccQueue* q = ctx->queue.as<EccQueue>();
     EccFrameResult* r = ctx->results.as<EccFrameResult>();
     a.ring_fallbacks = &q->ring_fallbacks;
+    a.first_iter_slots = &q->first_iter_slots;
     a.slot0 = 0;
     HIP_TRY(launch_ecc_init(a.slots, pl.n_slots, a.tickets, q, pl.n_templates, r, init_warps_dev, ctx->stream, feed ? 0 : -1));
+    // A frame that starts at the identity samples frame 0 at its own pixels in its first iteration, every pixel inside the
+    // mask: 55 of the homography's 66 sums (the Hessian, J.u, J.m, the mask count, s_u, s_uu) are then the same for every
+    // frame of the call, and the other 11 need neither coordinates nor taps. So the column pass runs that iteration ONCE here, on a
+    // scratch slot with the call's own partition — its block partials are bit for bit what each frame would compute for
+    // itself — and a slot at iteration 0 with the identity takes the short route of the kernel, which computes the 11 sums
+    // that read the template and copies the rest. (The template of this launch is whatever templates[0] holds, possibly
+    // not prepared yet: the sums that read it are the ones not used.) 8- and 16-bit images only: with non-finite f32
+    // pixels 0 x (bottom - top) is not 0 and a blend at fraction 0 is not the tap.
+    bool first_iter = ctx->opt_ecc_first_iter && ctx->opt_ecc_variant == 3 && pl.motion == STK_MOTION_HOMOGRAPHY && depth != 32 && crit.n_iter >= 1;
+    if (first_iter && init_warps_dev) {
+        first_iter = false;
+        static const float eye[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+        for (int f = 0; init_warps_host && f < pl.n_templates && !first_iter; f++)
+            first_iter = std::memcmp(init_warps_host + (size_t)f * 9, eye, sizeof(eye)) == 0;
+    }
+    if (first_iter) {
+        HIP_TRY(ctx->first_sums.reserve(sizeof(double) * ECC_MAX_SUMS * (size_t)pl.nb));
+        EccIterArgs f = a;
+        f.slots = a.slots + pl.n_slots;
+        f.n_slots = 1;
+        f.partials = ctx->first_sums.as<double>();
+        HIP_TRY(launch_ecc_first_slot(f.slots, ctx->stream));
+        HIP_TRY(launch_ecc_iter(f, pl.motion, 3, ctx->stream));
+        a.first_sums = ctx->first_sums.as<double>();
+    }
     int fed = feed ? 0 : pl.n_templates;
     if (feed) {
         // the prep stream may raise `ready` only after the queue exists
@@ -427,9 +462,10 @@ static stk_status ecc_run(stk_ctx* ctx, const EccPlan& pl, EccCriteria crit, con
         }
     }
     HIP_TRY(hipMemcpyAsync(res.data(), r, sizeof(EccFrameResult) * pl.n_templates, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&ctx->host_done[2], &q->ring_fallbacks, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&ctx->host_done[2], &q->ring_fallbacks, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));   // (and first_iter_slots behind it)
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->timing.ecc_ring_fallbacks += ctx->host_done[2];
+    ctx->ecc_first_iter_slots += ctx->host_done[3];
 #ifdef STK_SOLVE_TIMING
     { EccQueue hq; (void)hipMemcpy(&hq, q, sizeof(hq), hipMemcpyDeviceToHost);
       fprintf(stderr, "SOLVE_DBG stage1 %lld ticket %lld sums %lld stats %lld lu %lld iph %lld tail %lld (x10ns)\n", hq.dbg[1] - hq.dbg[0], hq.dbg[2] - hq.dbg[1],
@@ -523,7 +559,7 @@ size_t image_stride_floats(const stk_image_f32* im) {
     return im->row_stride_bytes ? im->row_stride_bytes / 4 : (size_t)im->width * im->channels;
 }
 
-void timing_begin(stk_ctx* ctx) { std::memset(&ctx->timing, 0, sizeof(ctx->timing)); }
+void timing_begin(stk_ctx* ctx) { std::memset(&ctx->timing, 0, sizeof(ctx->timing)); ctx->ecc_first_iter_slots = 0; }
 
 // ecc_match on a shard. `seeds` (n x 9 f32, row-major, h22 == 1; entry 0 unused) replaces the identity as the initial
 // warp of every moving frame; `alpha` is the convertTo scale of the fold; `allow16` admits 16-bit frames (ECC then runs on
@@ -683,7 +719,7 @@ stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_
             *enqueued = enq;
             return STK_OK;
         };
-        st = ecc_run(ctx, pl, crit, seeds_dev, res, &feed, on_done);
+        st = ecc_run(ctx, pl, crit, seeds_dev, seeds_dev ? seeds + 9 : nullptr, frames->depth, res, &feed, on_done);
         double h2d = 0;
         const stk_status fin = up.finish(&h2d);
         if (st) return st;
@@ -708,10 +744,10 @@ stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_
             *enqueued = n - 1;                                  // nothing further depends on the host
             return STK_OK;
         };
-        st = ecc_run(ctx, pl, crit, seeds_dev, res, &feed, on_done);
+        st = ecc_run(ctx, pl, crit, seeds_dev, seeds_dev ? seeds + 9 : nullptr, frames->depth, res, &feed, on_done);
         HIP_TRY(hipStreamSynchronize(ctx->prep_stream));
         if (st) return st;
-    } else if ((st = ecc_run(ctx, pl, crit, seeds_dev, res, nullptr, on_done))) return st;
+    } else if ((st = ecc_run(ctx, pl, crit, seeds_dev, seeds_dev ? seeds + 9 : nullptr, frames->depth, res, nullptr, on_done))) return st;
     if (!folded_on_device) HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
 
     int first_err = -1;
@@ -987,7 +1023,7 @@ stk_status stk_find_transform_ecc(stk_ctx* ctx, const void* templ, const void* i
     HIP_TRY(hipMemcpyAsync(ctx->init_warps.p, w9, sizeof(w9), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     std::vector<EccFrameResult> res;
-    st = ecc_run(ctx, pl, crit, ctx->init_warps.as<float>(), res);
+    st = ecc_run(ctx, pl, crit, ctx->init_warps.as<float>(), w9, depth, res);
     if (st) return st;
     for (int k = 0; k < 9; k++) warp[k] = res[0].warp[k];    // (no iteration: the start itself, row 2 = 0 0 1 for the 2 x 3 motions)
     if (rho) *rho = res[0].rho;
