@@ -204,7 +204,9 @@ stk_status  stk_get_timing(const stk_ctx* ctx, stk_timing* out);
  * STK_INVALID_PARAMS.
  *   "ecc_first_iter_slots"  ECC iteration pass, homography: slot-iterations that took the first-iteration route (option
  *                           "ecc_first_iter"): one per frame that starts at the identity; 0 with the option off, for the
- *                           other motion types, under "ecc_variant" 0 and for f32 images. */
+ *                           other motion types, under "ecc_variant" 0 and for f32 images.
+ *   "robust_select_us"      median / MAD clip (stk_robust_clip_stack and the *_robust_clipped calls): device time of the
+ *                           last such call's selection launches in microseconds, part of its stk_timing.finalize_ms. */
 stk_status  stk_get_counter(const stk_ctx* ctx, const char* name, int64_t* out);
 /* Pinned (page-locked) host memory for frames: stacks handed over in such buffers cross PCIe by DMA at link rate and
  * overlap with the alignment of the frames that have already arrived (a decoder — the Rust shim's imread — writes into
@@ -572,6 +574,91 @@ stk_status stk_keypoint_match_quantile_weighted(stk_ctx* ctx, const stk_frames* 
                                                 const stk_weight_params* weight, const float* weights_or_null, stk_image_f32* out,
                                                 int32_t* dropped, int32_t* counts_or_null, stk_frame_weight* applied_or_null,
                                                 stk_frame_stats* stats_or_null);
+
+/* ---- median / MAD sigma clipping: an EXTENSION beyond the reference -------------------------------------------
+ * Rejection about a robust centre and scale. The clipped combine above judges the samples by their own mean and standard
+ * deviation, and no sample of N lies further than sqrt(N - 1) population standard deviations from their mean (Samuelson's
+ * inequality): with kappa = 3 it rejects nothing at N <= 10, with kappa = 2.5 nothing at N <= 7, whatever the data. Here
+ * the centre is the median and the scale 1.4826 times the median absolute deviation (MAD), which one outlier among a
+ * handful of frames does not move; the result is still the mean of the kept samples, so the noise reduction of stacking
+ * stays (a median has about 1.25 times the noise of a mean at large N).
+ * Samples. The clipped combine's: per pixel and channel s_1 .. s_N are the warped, converted frames in fold order (frame 0
+ * through the identity, then the kept frames in ascending index; in stk_robust_clip_stack the included frames in index
+ * order under the caller's matrices) with the fold's own warp, border mode and value, alpha, warp_subpixel_bits and
+ * warp_interpolation. All arithmetic is f32, each operation rounded on its own, no contraction, `/` correctly rounded; max
+ * and min are C's fmaxf / fminf (a NaN operand gives the other one). med(K) is the quantile combine's formula at
+ * quantile = 0.5 over the multiset K of k samples: vi = (float)(k - 1) * 0.5f; j = floor(vi); g = vi - j; lo = the j-th
+ * smallest (from 0), hi = the (min(j + 1, k - 1))-th; d = hi - lo; med = g == 0 ? lo : hi - d * (1 - g).
+ *   K = all N samples; k = N; L = -inf; U = +inf; c = med(K)
+ *   rounds t = 1 .. iterations:
+ *       if k < 3: stop (c, L, U stay)
+ *       e_i = |s_i - c| for the samples of K
+ *       mad = med({e_i})
+ *       sigma = max(1.4826f * mad, sigma_floor)
+ *       L = max(L, c - kappa_low * sigma);  U = min(U, c + kappa_high * sigma)
+ *       K = {s_i : L <= s_i && s_i <= U};  k = |K|
+ *       if k > 0: c = med(K)
+ *   final pass, the samples in fold order (the clipped combine's last pass, bit for bit):
+ *       k = 0; a = 0;  for each s: d = s - c; if (L <= s && s <= U) { k += 1; a = a + d; }
+ *       out = k > 0 ? c + a / (float)k : c;   counts (optional) = k
+ * sigma_floor. The MAD is 0 whenever more than half of the samples are equal, which is common on 8-bit data (saturated or
+ * flat regions, integer translations); with a scale of 0 every sample one grey level off the median would be rejected.
+ * sigma_floor is the smallest scale the test uses, in the units of the samples (after alpha). Recommended: half a
+ * quantisation step of the input after alpha, i.e. 0.5f / 255 for 8-bit frames under alpha = 1 / 255 (0.5f / 65535 for
+ * 16-bit ones under alpha = 1 / 65535). 0 is allowed: then only samples equal to the centre survive where the MAD is 0.
+ * Non-finite samples. Any NaN sample makes the output of that pixel and channel NaN, as in the quantile (c = NaN, L = -inf,
+ * U = +inf; the final pass produces the NaN). One +-inf sample among finite ones is rejected and the result is finite.
+ * Where the median itself is infinite (or the midpoint of a finite and an infinite sample, or of -inf and +inf, which is
+ * NaN) the deviations inf - inf are NaN; a NaN deviation ranks above every number and a NaN mad gives sigma = sigma_floor:
+ * the output of such a pixel and channel is NaN, and counts is the number of samples the bounds then keep.
+ * N is at most 4096 (STK_NOT_IMPLEMENTED beyond). `out` must be tightly packed; counts_or_null: width * height * channels
+ * int32 in the location of `out`. stk_timing.finalize_ms of these calls is the combine's device time (warp_ms etc. are
+ * the plain call's). The samples go through the quantile combine's band buffer (option "quantile_band_rows"), the centre
+ * and bounds through the clipped combine's planes. A multi-device context runs these calls on its first device.
+ * stk_get_counter "robust_select_us": the device time of the last call's selection launches, in microseconds.
+ * The participation form extends this as the normalised, coverage-aware clip extends the clipped combine: participation
+ * and the normalised sample u = s * g + o are those of stk_clip_stack_weighted; centre and scale are UNWEIGHTED order
+ * statistics of the participating normalised samples (w enters through w > 0 only, as in stk_quantile_stack_weighted); the
+ * final pass is the weighted clip's last pass: a = a + w * d, sw = sw + w, out = k > 0 ? c + a / sw : c, counts = k,
+ * kept_weight = sw. A pixel no entry participates in gives out = 0, counts = 0, kept_weight = 0. With all weights 1,
+ * g = 1, o = 0 and every entry participating this is stk_robust_clip_stack bit for bit on a finite stack. */
+typedef struct {
+    float   kappa_low, kappa_high;  /* rejection below c - kappa_low sigma / above c + kappa_high sigma: > 0, finite */
+    float   sigma_floor;            /* >= 0, finite, in the units of the samples (after alpha); 0.5f / 255 recommended for 8-bit */
+    int32_t iterations;             /* rounds T of median / MAD bounds before the final pass, 1 .. 16 */
+} stk_robust_clip_params;
+
+/* ecc_match / keypoint_match with the median / MAD clip: stats, warps, `dropped` and errors are the plain call's, the
+ * samples those of stk_ecc_match_clipped / stk_keypoint_match_clipped. */
+stk_status stk_ecc_match_robust_clipped(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                        const stk_robust_clip_params* clip, stk_image_f32* out, int32_t* counts_or_null,
+                                        stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_robust_clipped(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                             float scale_down_width, const stk_robust_clip_params* clip, stk_image_f32* out,
+                                             int32_t* dropped, int32_t* counts_or_null, stk_frame_stats* stats_or_null);
+/* The combine alone over caller-held warps, with the arguments of stk_clip_stack. */
+stk_status stk_robust_clip_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                 int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                 const stk_robust_clip_params* clip, stk_image_f32* out, int32_t* counts_or_null);
+/* The participation form, with the arguments of stk_clip_stack_weighted (coverage = 1 puts no condition on the border mode
+ * or value, as there). */
+stk_status stk_robust_clip_stack_weighted(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                          int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                          const stk_robust_clip_params* clip, const stk_frame_weight* per_frame, int32_t coverage,
+                                          stk_image_f32* out, int32_t* counts_or_null, float* kept_weight_or_null);
+/* The whole-stack participation forms, with the arguments of stk_ecc_match_clipped_weighted /
+ * stk_keypoint_match_clipped_weighted; finalize_ms is the device time of the moments pass plus the combine. */
+stk_status stk_ecc_match_robust_clipped_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
+                                                 float scale_down_width, const stk_robust_clip_params* clip,
+                                                 const stk_weight_params* weight, const float* weights_or_null, stk_image_f32* out,
+                                                 int32_t* counts_or_null, float* kept_weight_or_null,
+                                                 stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_robust_clipped_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                                      float scale_down_width, const stk_robust_clip_params* clip,
+                                                      const stk_weight_params* weight, const float* weights_or_null,
+                                                      stk_image_f32* out, int32_t* dropped, int32_t* counts_or_null,
+                                                      float* kept_weight_or_null, stk_frame_weight* applied_or_null,
+                                                      stk_frame_stats* stats_or_null);
 
 /* ---- stage-level entry points (parity tests bind these) ------------------ */
 /* cvt_color(BGR2GRAY) on the integer image, utils.rs:136-142. out: w*h of the input depth

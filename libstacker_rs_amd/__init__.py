@@ -12,9 +12,10 @@ from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_RE
                   INTER_CUBIC, INTER_LINEAR,
                   LEAST_SQUARES, LMEDS, RANSAC, RHO, EccMatchParameters, HipError, InvalidParams, IoError,
                   KeyPointMatchParameters, MotionType, NotEnoughFiles, NotImplementedYet, OpenCvError,
-                  ProcessingError, QuantileParameters, SelectParameters, SigmaClipParameters, Stacker, StackerError, WeightParameters,
+                  ProcessingError, QuantileParameters, RobustClipParameters, SelectParameters, SigmaClipParameters, Stacker,
+                  StackerError, WeightParameters,
                   default_stacker, ecc_match, keypoint_match, rank_frames)
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
-           "StackerError", "Stacker", "SigmaClipParameters", "QuantileParameters", "WeightParameters",
+           "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
            "SelectParameters", "rank_frames"]

@@ -51,6 +51,10 @@ class ClipParams(C.Structure):
     _fields_ = [("kappa_low", C.c_float), ("kappa_high", C.c_float), ("iterations", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RobustClipParams(C.Structure):
+    _fields_ = [("kappa_low", C.c_float), ("kappa_high", C.c_float), ("sigma_floor", C.c_float), ("iterations", C.c_int32)]
+
+
 class QuantileParams(C.Structure):
     _fields_ = [("quantile", C.c_float), ("reserved", C.c_int32)]
 
@@ -147,6 +151,24 @@ SIGNATURES = {
                                                         C.POINTER(QuantileParams), C.POINTER(WeightParams), C.c_void_p,
                                                         C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p, C.POINTER(FrameWeight),
                                                         C.POINTER(FrameStats)]),
+    "stk_ecc_match_robust_clipped": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float,
+                                                C.POINTER(RobustClipParams), C.POINTER(ImageF32), C.c_void_p, C.POINTER(FrameStats)]),
+    "stk_keypoint_match_robust_clipped": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                                     C.POINTER(RobustClipParams), C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p,
+                                                     C.POINTER(FrameStats)]),
+    "stk_robust_clip_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                         C.c_double, C.POINTER(RobustClipParams), C.POINTER(ImageF32), C.c_void_p]),
+    "stk_robust_clip_stack_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.c_void_p, C.c_double, C.POINTER(RobustClipParams), C.POINTER(FrameWeight),
+                                                  C.c_int32, C.POINTER(ImageF32), C.c_void_p, C.c_void_p]),
+    "stk_ecc_match_robust_clipped_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float,
+                                                         C.POINTER(RobustClipParams), C.POINTER(WeightParams), C.c_void_p,
+                                                         C.POINTER(ImageF32), C.c_void_p, C.c_void_p, C.POINTER(FrameWeight),
+                                                         C.POINTER(FrameStats)]),
+    "stk_keypoint_match_robust_clipped_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                                              C.POINTER(RobustClipParams), C.POINTER(WeightParams), C.c_void_p,
+                                                              C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
+                                                              C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
     "stk_grey": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p]),
     "stk_convert_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_double, C.c_void_p]),
     "stk_hybrid_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.POINTER(EccParams),

@@ -117,6 +117,21 @@ class SigmaClipParameters:        # extension beyond the reference: include/stac
 
 
 @dataclass
+class RobustClipParameters:       # extension beyond the reference: include/stacker.h, stk_robust_clip_params
+    """Median / MAD rejection for the *_robust_clipped combines: samples below c - kappa_low sigma or above
+    c + kappa_high sigma are left out, `iterations` times, with c the median and sigma = max(1.4826 MAD, sigma_floor) of
+    the samples still kept, before the final mean of the kept samples. sigma_floor is in the units of the samples (after
+    alpha): half a quantisation step of 8-bit input by default; 0 is allowed."""
+    kappa_low: float = 3.0
+    kappa_high: float = 3.0
+    sigma_floor: float = 0.5 / 255.0
+    iterations: int = 2
+
+    def _c(self) -> _ffi.RobustClipParams:
+        return _ffi.RobustClipParams(float(self.kappa_low), float(self.kappa_high), float(self.sigma_floor), int(self.iterations))
+
+
+@dataclass
 class QuantileParameters:         # extension beyond the reference: include/stacker.h, stk_quantile_params
     """The order statistic for the *_quantile combines: 0 = min, 0.5 = median, 1 = max, linear interpolation between
     the two nearest samples otherwise (numpy.quantile's default method)."""
@@ -393,7 +408,7 @@ class Stacker:
         t = _ffi.Timing()
         self._check(self._lib.stk_get_timing(self._h, C.byref(t)))
         d = {k: getattr(t, k) for k, _ in _ffi.Timing._fields_}
-        for name in ("ecc_first_iter_slots",):               # counters outside stk_timing (stk_get_counter)
+        for name in ("ecc_first_iter_slots", "robust_select_us"):              # counters outside stk_timing (stk_get_counter)
             v = C.c_int64(0)
             self._check(self._lib.stk_get_counter(self._h, name.encode(), C.byref(v)))
             d[name] = v.value
@@ -533,6 +548,10 @@ class Stacker:
                           scale_down_width: Optional[float] = None, return_stats: bool = False, return_counts: bool = False):
         """ecc_match with kappa-sigma rejection over the aligned frames instead of the plain mean (stk_ecc_match_clipped).
         Returns the image, then the per-pixel counts of kept samples (return_counts) and the stats (return_stats)."""
+        return self._ecc_match_clipped(self._lib.stk_ecc_match_clipped, (clip or SigmaClipParameters())._c(), files, params,
+                                       scale_down_width, return_stats, return_counts)
+
+    def _ecc_match_clipped(self, fn, cp, files, params, scale_down_width, return_stats, return_counts):
         if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
             raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
         m = self._marshal(files)
@@ -541,15 +560,18 @@ class Stacker:
         out, img = self._out_image(m)
         cnt, cptr = self._counts_image(m) if return_counts else (None, None)
         stats = (_ffi.FrameStats * m.n)()
-        p, cp = params._c(), (clip or SigmaClipParameters())._c()
-        self._check(self._lib.stk_ecc_match_clipped(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                    C.byref(cp), C.byref(img), cptr, stats))
+        p = params._c()
+        self._check(fn(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(cp), C.byref(img), cptr, stats))
         res = (out,) + ((cnt,) if return_counts else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
         return res if len(res) > 1 else out
 
     def keypoint_match_clipped(self, files, params: KeyPointMatchParameters, clip: Optional["SigmaClipParameters"] = None,
                                scale_down_width: Optional[float] = None, return_stats: bool = False, return_counts: bool = False):
         """keypoint_match with kappa-sigma rejection (stk_keypoint_match_clipped): (dropped, image[, counts][, stats])."""
+        return self._keypoint_match_clipped(self._lib.stk_keypoint_match_clipped, (clip or SigmaClipParameters())._c(), files, params,
+                                            scale_down_width, return_stats, return_counts)
+
+    def _keypoint_match_clipped(self, fn, cp, files, params, scale_down_width, return_stats, return_counts):
         m = self._marshal(files)
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
@@ -557,15 +579,19 @@ class Stacker:
         cnt, cptr = self._counts_image(m) if return_counts else (None, None)
         stats = (_ffi.FrameStats * m.n)()
         dropped = C.c_int32(0)
-        p, cp = params._c(), (clip or SigmaClipParameters())._c()
-        self._check(self._lib.stk_keypoint_match_clipped(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                         C.byref(cp), C.byref(img), C.byref(dropped), cptr, stats))
+        p = params._c()
+        self._check(fn(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(cp), C.byref(img),
+                       C.byref(dropped), cptr, stats))
         return (dropped.value, out) + ((cnt,) if return_counts else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
 
     def clip_stack(self, files, warps, clip: Optional["SigmaClipParameters"] = None, include=None, *, is_affine=False,
                    border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_counts: bool = False):
         """The clipped combine alone over caller-held warps (stk_clip_stack): warps[i] is frame i's forward matrix as
         warp_accumulate takes it (3x3, or 2x3 for affine), frame 0's included; include: per-frame flags or None = all."""
+        return self._clip_stack(self._lib.stk_clip_stack, (clip or SigmaClipParameters())._c(), files, warps, include, is_affine,
+                                border_mode, border_value, alpha, return_counts)
+
+    def _clip_stack(self, fn, cp, files, warps, include, is_affine, border_mode, border_value, alpha, return_counts):
         m = self._marshal(files)
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
@@ -582,12 +608,30 @@ class Stacker:
         bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
         out, img = self._out_image(m)
         cnt, cptr = self._counts_image(m) if return_counts else (None, None)
-        cp = (clip or SigmaClipParameters())._c()
-        self._check(self._lib.stk_clip_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                             None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
-                                             int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(cp),
-                                             C.byref(img), cptr))
+        self._check(fn(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), None if inc is None else C.c_void_p(inc.ctypes.data),
+                       int(is_affine), int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(cp), C.byref(img), cptr))
         return (out, cnt) if return_counts else out
+
+    # -- median / MAD clipped combines (extension beyond the reference) --------------------------------
+    def ecc_match_robust_clipped(self, files, params: EccMatchParameters, clip: Optional["RobustClipParameters"] = None,
+                                 scale_down_width: Optional[float] = None, return_stats: bool = False, return_counts: bool = False):
+        """ecc_match with median / MAD rejection over the aligned frames (stk_ecc_match_robust_clipped): the clip that
+        still rejects on a handful of frames. Returns as ecc_match_clipped."""
+        return self._ecc_match_clipped(self._lib.stk_ecc_match_robust_clipped, (clip or RobustClipParameters())._c(), files, params,
+                                       scale_down_width, return_stats, return_counts)
+
+    def keypoint_match_robust_clipped(self, files, params: KeyPointMatchParameters, clip: Optional["RobustClipParameters"] = None,
+                                      scale_down_width: Optional[float] = None, return_stats: bool = False,
+                                      return_counts: bool = False):
+        """keypoint_match with median / MAD rejection (stk_keypoint_match_robust_clipped): (dropped, image[, counts][, stats])."""
+        return self._keypoint_match_clipped(self._lib.stk_keypoint_match_robust_clipped, (clip or RobustClipParameters())._c(), files,
+                                            params, scale_down_width, return_stats, return_counts)
+
+    def robust_clip_stack(self, files, warps, clip: Optional["RobustClipParameters"] = None, include=None, *, is_affine=False,
+                          border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_counts: bool = False):
+        """The median / MAD clip alone over caller-held warps (stk_robust_clip_stack), with the arguments of clip_stack."""
+        return self._clip_stack(self._lib.stk_robust_clip_stack, (clip or RobustClipParameters())._c(), files, warps, include,
+                                is_affine, border_mode, border_value, alpha, return_counts)
 
     # -- median / quantile combines (extension beyond the reference) -----------------------------------
     def ecc_match_quantile(self, files, params: EccMatchParameters, quantile=None, scale_down_width: Optional[float] = None,
@@ -808,6 +852,22 @@ class Stacker:
         """The normalised, coverage-aware clip alone over caller-held warps (stk_clip_stack_weighted): clip_stack with
         weighted_stack's gain / offset / weights (or `applied`) and coverage. Returns the image, then the counts of kept
         samples (return_counts) and the kept weight (return_kept_weight), both per pixel and channel."""
+        return self._clip_stack_weighted(self._lib.stk_clip_stack_weighted, (clip or SigmaClipParameters())._c(), files, warps, gain,
+                                         offset, weights, include, applied, coverage, is_affine, border_mode, border_value, alpha,
+                                         return_counts, return_kept_weight)
+
+    def robust_clip_stack_weighted(self, files, warps, clip: Optional["RobustClipParameters"] = None, gain=None, offset=None,
+                                   weights=None, include=None, *, applied=None, coverage: bool = True, is_affine=False,
+                                   border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0,
+                                   return_counts: bool = False, return_kept_weight: bool = False):
+        """The median / MAD clip with participation over caller-held warps (stk_robust_clip_stack_weighted), with the
+        arguments and results of clip_stack_weighted."""
+        return self._clip_stack_weighted(self._lib.stk_robust_clip_stack_weighted, (clip or RobustClipParameters())._c(), files, warps,
+                                         gain, offset, weights, include, applied, coverage, is_affine, border_mode, border_value,
+                                         alpha, return_counts, return_kept_weight)
+
+    def _clip_stack_weighted(self, fn, cp, files, warps, gain, offset, weights, include, applied, coverage, is_affine, border_mode,
+                             border_value, alpha, return_counts, return_kept_weight):
         m = self._marshal(files)
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
@@ -817,11 +877,9 @@ class Stacker:
         out, img = self._out_image(m)
         cnt, cptr = self._counts_image(m) if return_counts else (None, None)
         kw, kptr = self._kept_image(m) if return_kept_weight else (None, None)
-        cp = (clip or SigmaClipParameters())._c()
-        self._check(self._lib.stk_clip_stack_weighted(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                      None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
-                                                      int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(cp), rec,
-                                                      int(coverage), C.byref(img), cptr, kptr))
+        self._check(fn(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), None if inc is None else C.c_void_p(inc.ctypes.data),
+                       int(is_affine), int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(cp), rec, int(coverage),
+                       C.byref(img), cptr, kptr))
         res = (out,) + ((cnt,) if return_counts else ()) + ((kw,) if return_kept_weight else ())
         return res if len(res) > 1 else out
 
@@ -853,9 +911,9 @@ class Stacker:
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
         out, img = self._out_image(m)
-        if combine == "clipped":
+        if combine in ("clipped", "robust_clipped"):
             cnt, cptr = self._counts_image(m) if return_counts else (None, None)
-            cp = (cparams or SigmaClipParameters())._c()
+            cp = (cparams or (SigmaClipParameters() if combine == "clipped" else RobustClipParameters()))._c()
         else:
             cnt, cptr = self._pixel_counts_image(m) if return_counts else (None, None)
             cp = _quantile_c(cparams)
@@ -870,7 +928,7 @@ class Stacker:
         if kind == "keypoint":
             args.append(C.byref(dropped))
         args.append(cptr)
-        if combine == "clipped":
+        if combine in ("clipped", "robust_clipped"):
             args.append(kptr)
         self._check(fn(*args, applied, stats))
         res = ((dropped.value,) if kind == "keypoint" else ()) + (out,) + ((cnt,) if return_counts else ()) \
@@ -896,6 +954,26 @@ class Stacker:
         (dropped, image[, counts][, kept weight][, applied][, stats])."""
         return self._robust_match("keypoint", "clipped", files, params, clip, weight, weights, scale_down_width, return_stats,
                                   return_counts, return_kept_weight, return_applied)
+
+    def ecc_match_robust_clipped_weighted(self, files, params: EccMatchParameters, clip: Optional["RobustClipParameters"] = None,
+                                          weight: Optional["WeightParameters"] = None, weights=None,
+                                          scale_down_width: Optional[float] = None, return_stats: bool = False,
+                                          return_counts: bool = False, return_kept_weight: bool = False, return_applied: bool = False):
+        """ecc_match with the median / MAD clip with participation (stk_ecc_match_robust_clipped_weighted); results as
+        ecc_match_clipped_weighted."""
+        return self._robust_match("ecc", "robust_clipped", files, params, clip, weight, weights, scale_down_width, return_stats,
+                                  return_counts, return_kept_weight, return_applied)
+
+    def keypoint_match_robust_clipped_weighted(self, files, params: KeyPointMatchParameters,
+                                               clip: Optional["RobustClipParameters"] = None,
+                                               weight: Optional["WeightParameters"] = None, weights=None,
+                                               scale_down_width: Optional[float] = None, return_stats: bool = False,
+                                               return_counts: bool = False, return_kept_weight: bool = False,
+                                               return_applied: bool = False):
+        """keypoint_match with the median / MAD clip with participation (stk_keypoint_match_robust_clipped_weighted); results
+        as keypoint_match_clipped_weighted."""
+        return self._robust_match("keypoint", "robust_clipped", files, params, clip, weight, weights, scale_down_width,
+                                  return_stats, return_counts, return_kept_weight, return_applied)
 
     def ecc_match_quantile_weighted(self, files, params: EccMatchParameters, quantile=None,
                                     weight: Optional["WeightParameters"] = None, weights=None, scale_down_width: Optional[float] = None,

@@ -284,6 +284,11 @@ hipError_t launch_quantile_select_masked(const float* band, size_t m, int n, flo
 // per column k < m of the n x m samples of a band (frame-major: band[i * m + k]): the quantile with lo = s_(j) and the
 // fraction g (include/stacker.h), into out[k]; n <= QUANTILE_MAX_SAMPLES
 hipError_t launch_quantile_select(const float* band, size_t m, int n, int j, float g, float* out, hipStream_t s);
+// median / MAD clipping (kernels_robust_clip.hip; definition: include/stacker.h, stk_robust_clip_params): per column k < m
+// of such a band the centre and the bounds after p.iterations rounds, into c[k], L[k], U[k]; masked: the band carries
+// QUANTILE_ABSENT_BITS marks (launch_quantile_store_weighted); a column without a sample: c = 0, L = -inf, U = +inf
+hipError_t launch_robust_select(const float* band, size_t m, int n, int masked, const stk_robust_clip_params& p, float* c, float* L,
+                                float* U, hipStream_t s);
 // the fold's frame table straight from the ECC results, on the device: entry 0 = the reference frame under the identity
 // (if add_reference), then template k under results[k].warp — what the host loop of ecc_shard_impl builds, bit for bit
 hipError_t launch_warp_frames_from_ecc(const EccFrameResult* results, const void* const* src_ptrs /* n_templates + 1, device */,

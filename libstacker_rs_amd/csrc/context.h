@@ -82,6 +82,8 @@ struct stk_ctx {
     int ref_zeroed_w = 0, ref_zeroed_h = 0;
     std::vector<hipEvent_t> prof_ev;   // event pairs for per-launch timing (option profile = 2)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> fold_ev;   // event pairs around the keypoint path's fold launches (grow-only pool)
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> select_ev; // event pairs around the median / MAD clip's selection launches, one per band (grow-only pool)
+    int64_t robust_select_us = 0;   // stk_get_counter: device time of the last median / MAD clip's selection launches
     // page-locked host block the path-based entry points decode a stack into (imread.cpp: match_files); grow-only, like the
     // device workspaces: locking 6.4 GB of pages for a 256-frame 4K stack costs more than decoding into them
     unsigned char* files_block = nullptr; size_t files_block_cap = 0; bool files_block_pinned = false;
@@ -172,6 +174,13 @@ stk_status quantile_check_count(stk_ctx* ctx, int n);
 size_t quantile_image_floats(int w, int h, int cn);
 size_t quantile_band_rows(const stk_ctx* ctx, int n, int w, int h, int cn);
 stk_status quantile_reserve(stk_ctx* ctx, int n, int w, int h, int cn);
+stk_status robust_clip_validate(stk_ctx* ctx, const stk_robust_clip_params* p);
+// the median / MAD clip over the n_entries entries of ctx->warpframes (robust_clip.cpp): per band a store launch and the
+// selection into the clip planes, then one last clip pass. coef: the per-entry records of the participation form (then
+// `coverage` and `kept` apply), null = the plain form. Writes out / counts / kept (out's location), adds its device time to *ms
+stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_frame_weight>* coef, int depth, int w, int h, int cn,
+                             size_t src_row_bytes, double alpha, int border_mode, const double* border_value, int is_affine,
+                             int coverage, const stk_robust_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms);
 stk_status weighted_validate(stk_ctx* ctx, const stk_weight_params* p);
 stk_status weighted_check_coefs(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, int cn);
 stk::WarpArgs weighted_warp_args(stk_ctx* ctx, int n_entries, int depth, int w, int h, int cn, size_t src_row_bytes, double alpha,

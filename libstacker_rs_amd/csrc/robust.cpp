@@ -1,7 +1,8 @@
-// robust.cpp — normalised, coverage-aware rejection: stk_clip_stack_weighted, stk_quantile_stack_weighted and the
-// *_clipped_weighted / *_quantile_weighted whole-stack forms (an extension beyond the reference; definition in
-// include/stacker.h, kernels in kernels_clip.hip and kernels_quantile.hip).
-// The two rejection combines with the per-entry gain / offset / weight records and the coverage flag of the weighted
+// robust.cpp — normalised, coverage-aware rejection: stk_clip_stack_weighted, stk_quantile_stack_weighted,
+// stk_robust_clip_stack_weighted and the *_clipped_weighted / *_quantile_weighted / *_robust_clipped_weighted whole-stack
+// forms (an extension beyond the reference; definition in include/stacker.h, kernels in kernels_clip.hip,
+// kernels_quantile.hip and kernels_robust_clip.hip; the median / MAD clip's combine itself is robust_clip.cpp's).
+// The rejection combines with the per-entry gain / offset / weight records and the coverage flag of the weighted
 // mean: an entry is a sample of a pixel only if its weight is > 0 and (coverage = 1) the frame covers the pixel, and the
 // samples are compared after each frame has been mapped onto frame 0's level. The workspaces are the plain combines'
 // (ctx->clip: the c, L and U planes; ctx->quantile: an image, then the band); the record table lives in ctx->coef. The
@@ -192,15 +193,16 @@ stk_status robust_coefs(stk_ctx* ctx, const stk_frames* frames, const std::vecto
 }
 
 struct RobustCombine {
-    const stk_clip_params* clip = nullptr;            // exactly one of the two
+    const stk_clip_params* clip = nullptr;            // exactly one of the three
     const stk_quantile_params* quantile = nullptr;
+    const stk_robust_clip_params* mad = nullptr;      // the median / MAD clip (robust_clip.cpp)
     int32_t* counts = nullptr;
     float* kept = nullptr;
 };
 
 stk_status robust_validate(stk_ctx* ctx, const RobustCombine& rc, const stk_weight_params* weight, const stk_frames* frames,
                            const stk_image_f32* out) {
-    stk_status st = rc.clip ? clip_validate(ctx, rc.clip) : quantile_validate(ctx, rc.quantile);
+    stk_status st = rc.clip ? clip_validate(ctx, rc.clip) : rc.mad ? robust_clip_validate(ctx, rc.mad) : quantile_validate(ctx, rc.quantile);
     if (st) return st;
     if ((st = weighted_validate(ctx, weight))) return st;
     if ((st = check_frames(ctx, frames, true))) return st;
@@ -225,6 +227,9 @@ stk_status robust_finish(stk_ctx* ctx, const stk_frames* frames, const stk_frame
         if (rc.clip)
             st = clip_passes_weighted(ctx, coef, depth, w, h, cn, rb, 1.0 / 255.0, border_mode, border_value, is_affine, weight->coverage,
                                       rc.clip, out, rc.counts, rc.kept, &ms);
+        else if (rc.mad)
+            st = robust_clip_bands(ctx, (int)coef.size(), &coef, depth, w, h, cn, rb, 1.0 / 255.0, border_mode, border_value, is_affine,
+                                   weight->coverage, rc.mad, out, rc.counts, rc.kept, &ms);
         else
             st = quantile_bands_weighted(ctx, coef, depth, w, h, cn, rb, 1.0 / 255.0, border_mode, border_value, is_affine,
                                          weight->coverage, rc.quantile, out, rc.counts, &ms);
@@ -244,9 +249,10 @@ stk_status robust_ecc(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_para
     std::vector<stk_frame_stats> own;
     if (!stats) { own.resize(n); stats = own.data(); }
     // the plain call, on this context's own device, its mean into the combine's workspace image (unused)
-    if (rc.clip) HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
+    const bool planes = rc.clip || rc.mad;
+    if (planes) HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
     else if ((st = quantile_reserve(ctx, 0, w, h, cn))) return st;
-    stk_image_f32 mimg{rc.clip ? ctx->clip.as<float>() : ctx->quantile.as<float>(), w, h, cn, STK_DEVICE, 0};
+    stk_image_f32 mimg{planes ? ctx->clip.as<float>() : ctx->quantile.as<float>(), w, h, cn, STK_DEVICE, 0};
     if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
     const int is_affine = params->motion_type != STK_MOTION_HOMOGRAPHY;
     return robust_finish(ctx, frames, stats, false, frames->depth, STK_BORDER_CONSTANT, nullptr, is_affine, weight, weights, rc, out, applied);
@@ -263,9 +269,10 @@ stk_status robust_keypoint(stk_ctx* ctx, const stk_frames* frames, const stk_key
     const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
     std::vector<stk_frame_stats> own;
     if (!stats) { own.resize(n); stats = own.data(); }
-    if (rc.clip) HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
+    const bool planes = rc.clip || rc.mad;
+    if (planes) HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
     else if ((st = quantile_reserve(ctx, 0, w, h, cn))) return st;
-    stk_image_f32 mimg{rc.clip ? ctx->clip.as<float>() : ctx->quantile.as<float>(), w, h, cn, STK_DEVICE, 0};
+    stk_image_f32 mimg{planes ? ctx->clip.as<float>() : ctx->quantile.as<float>(), w, h, cn, STK_DEVICE, 0};
     if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
     return robust_finish(ctx, frames, stats, true, 8, params->border_mode, params->border_value, 0, weight, weights, rc, out, applied);
 }
@@ -311,6 +318,50 @@ stk_status stk_quantile_stack_weighted(stk_ctx* ctx, const stk_frames* frames, c
                                  border_mode, border_value, is_affine, coverage, quantile, out, counts, &ms);
     ctx->timing.finalize_ms = st ? 0.0 : ms;
     return st;
+}
+
+stk_status stk_robust_clip_stack_weighted(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include,
+                                          int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                          const stk_robust_clip_params* clip, const stk_frame_weight* per_frame, int32_t coverage,
+                                          stk_image_f32* out, int32_t* counts, float* kept_weight) {
+    stk_status st = check_frames(ctx, frames, false);
+    if (st) return st;
+    if ((st = robust_check_border(ctx, border_mode, coverage))) return st;
+    if ((st = robust_clip_validate(ctx, clip))) return st;
+    if ((st = clip_check_out(ctx, out, frames))) return st;
+    int n_in = 0;
+    for (int i = 0; i < frames->n; i++) n_in += (!include || include[i]) ? 1 : 0;
+    if ((st = quantile_check_count(ctx, n_in))) return st;
+    std::vector<stk_frame_weight> coef;
+    if ((st = robust_table(ctx, frames, M, include, is_affine, per_frame, "robust clipping", coef))) return st;
+    double ms = 0.0;
+    st = robust_clip_bands(ctx, (int)coef.size(), &coef, frames->depth, frames->width, frames->height, frames->channels,
+                           frame_row_bytes(frames), alpha, border_mode, border_value, is_affine, coverage, clip, out, counts, kept_weight, &ms);
+    ctx->timing.finalize_ms = st ? 0.0 : ms;
+    return st;
+}
+
+stk_status stk_ecc_match_robust_clipped_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
+                                                 float scale_down_width, const stk_robust_clip_params* clip,
+                                                 const stk_weight_params* weight, const float* weights, stk_image_f32* out,
+                                                 int32_t* counts, float* kept_weight, stk_frame_weight* applied, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    if (!clip) return fail(ctx, STK_INVALID_PARAMS, "null robust clip parameters");
+    RobustCombine rc;
+    rc.mad = clip; rc.counts = counts; rc.kept = kept_weight;
+    return robust_ecc(ctx, frames, params, scale_down_width, weight, weights, rc, out, applied, stats);
+}
+
+stk_status stk_keypoint_match_robust_clipped_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                                      float scale_down_width, const stk_robust_clip_params* clip,
+                                                      const stk_weight_params* weight, const float* weights, stk_image_f32* out,
+                                                      int32_t* dropped, int32_t* counts, float* kept_weight,
+                                                      stk_frame_weight* applied, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    if (!clip) return fail(ctx, STK_INVALID_PARAMS, "null robust clip parameters");
+    RobustCombine rc;
+    rc.mad = clip; rc.counts = counts; rc.kept = kept_weight;
+    return robust_keypoint(ctx, frames, params, scale_down_width, weight, weights, rc, out, dropped, applied, stats);
 }
 
 stk_status stk_ecc_match_clipped_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,

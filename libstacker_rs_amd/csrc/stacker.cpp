@@ -108,6 +108,7 @@ void stk_destroy(stk_ctx* ctx) {
     for (auto& e : ctx->poll_ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->prof_ev) if (e) (void)hipEventDestroy(e);
     for (auto& pr : ctx->fold_ev) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+    for (auto& pr : ctx->select_ev) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     if (ctx->host_done) (void)hipHostFree(ctx->host_done);
     if (ctx->files_block) { if (ctx->files_block_pinned) (void)hipHostFree(ctx->files_block); else std::free(ctx->files_block); }
     for (auto& e : ctx->upload_events) if (e) (void)hipEventDestroy(e);
@@ -145,6 +146,7 @@ stk_status stk_get_timing(const stk_ctx* ctx, stk_timing* out) {
 stk_status stk_get_counter(const stk_ctx* ctx, const char* name, int64_t* out) {
     if (!ctx || !name || !out) return STK_INVALID_PARAMS;
     if (std::string(name) == "ecc_first_iter_slots") { *out = ctx->ecc_first_iter_slots; return STK_OK; }
+    if (std::string(name) == "robust_select_us") { *out = ctx->robust_select_us; return STK_OK; }
     return STK_INVALID_PARAMS;
 }
 

@@ -9,7 +9,7 @@
 //!   decoded by OpenCV's `imread(IMREAD_UNCHANGED)` exactly as `read_grey_and_f32` does (utils.rs:132) and handed over
 //!   as host frames.
 use crate::amd_ffi::*;
-use crate::{utils, EccMatchParameters, KeyPointMatchParameters, StackerError};
+use crate::{utils, EccMatchParameters, KeyPointMatchParameters, RobustClipParameters, StackerError};
 use opencv::core;
 use opencv::imgcodecs;
 use opencv::prelude::*;
@@ -275,6 +275,66 @@ pub(crate) fn keypoint_match(
         unsafe {
             stk_keypoint_match_mixed(ctx, &frames, stack.geometry.as_ptr(), &p, sdw, &mut img, &mut dropped, std::ptr::null_mut())
         }
+    };
+    if st == STK_OK { Ok((dropped, out)) } else { Err(to_err(ctx, st)) }
+}
+
+fn robust_clip_params(p: &RobustClipParameters) -> stk_robust_clip_params {
+    stk_robust_clip_params {
+        kappa_low: p.kappa_low,
+        kappa_high: p.kappa_high,
+        sigma_floor: p.sigma_floor,
+        iterations: p.iterations,
+    }
+}
+
+/// `ecc_match` with the median / MAD clip in place of the mean (include/stacker.h, stk_ecc_match_robust_clipped). The
+/// combine has no `*_files` form: the stack is decoded by OpenCV and handed over as host frames.
+pub(crate) fn ecc_match_robust_clipped(
+    files: &[PathBuf],
+    params: EccMatchParameters,
+    clip: RobustClipParameters,
+    scale_down_width: Option<f32>,
+) -> Result<Mat, StackerError> {
+    if files.is_empty() {
+        return Err(StackerError::NotEnoughFiles);
+    }
+    let guard = shared_ctx()?;
+    let ctx = guard.0;
+    let p = ecc_params(&params);
+    let c = robust_clip_params(&clip);
+    let stack = DecodedStack::read(files)?;
+    let frames = stack.frames()?;
+    let (out, mut img) = new_output(frames.width, frames.height, frames.channels)?;
+    let st = unsafe {
+        stk_ecc_match_robust_clipped(ctx, &frames, &p, scale_down_width.unwrap_or(0.0), &c, &mut img, std::ptr::null_mut(), std::ptr::null_mut())
+    };
+    if st == STK_OK { Ok(out) } else { Err(to_err(ctx, st)) }
+}
+
+/// `keypoint_match` with the median / MAD clip (stk_keypoint_match_robust_clipped): (dropped, image). One geometry for
+/// the whole stack, as the combine asks.
+pub(crate) fn keypoint_match_robust_clipped(
+    files: &[PathBuf],
+    params: KeyPointMatchParameters,
+    clip: RobustClipParameters,
+    scale_down_width: Option<f32>,
+) -> Result<(i32, Mat), StackerError> {
+    if files.is_empty() {
+        return Err(StackerError::NotEnoughFiles);
+    }
+    let guard = shared_ctx()?;
+    let ctx = guard.0;
+    let p = kp_params(&params);
+    let c = robust_clip_params(&clip);
+    let stack = DecodedStack::read(files)?;
+    let frames = stack.frames()?;
+    let (out, mut img) = new_output(frames.width, frames.height, frames.channels)?;
+    let mut dropped: i32 = 0;
+    let st = unsafe {
+        stk_keypoint_match_robust_clipped(
+            ctx, &frames, &p, scale_down_width.unwrap_or(0.0), &c, &mut img, &mut dropped, std::ptr::null_mut(), std::ptr::null_mut(),
+        )
     };
     if st == STK_OK { Ok((dropped, out)) } else { Err(to_err(ctx, st)) }
 }

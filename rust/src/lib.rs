@@ -84,6 +84,25 @@ pub struct EccMatchParameters {
     pub gauss_filt_size: i32,
 }
 
+/// Median / MAD rejection for the `*_robust_clipped` combines, an extension beyond the reference (include/stacker.h,
+/// `stk_robust_clip_params`): samples further than `kappa` sigma from the median are left out, `iterations` times, with
+/// sigma = max(1.4826 MAD, `sigma_floor`); the result is the mean of the kept samples. Unlike a clip about the mean and
+/// the standard deviation it still rejects on a handful of frames.
+#[derive(Debug, Copy, Clone)]
+pub struct RobustClipParameters {
+    pub kappa_low: f32,
+    pub kappa_high: f32,
+    /// In the units of the samples (after the 1/255 scaling); 0 is allowed.
+    pub sigma_floor: f32,
+    pub iterations: i32,
+}
+
+impl Default for RobustClipParameters {
+    fn default() -> Self {
+        Self { kappa_low: 3.0, kappa_high: 3.0, sigma_floor: 0.5 / 255.0, iterations: 2 }
+    }
+}
+
 /// lib.rs:129-137: aligns every frame to the first by ORB + brute-force Hamming + `findHomography`, warps and averages.
 /// Returns (number of frames that could not be matched and were left out, averaged CV_32FC3 image).
 #[cfg(feature = "amd")]
@@ -113,6 +132,38 @@ where
 {
     let files: Vec<PathBuf> = files.into_iter().map(|p| p.as_ref().to_path_buf()).collect();
     amd::ecc_match(&files, params, scale_down_width)
+}
+
+/// `ecc_match` with the aligned frames combined by the median / MAD clip instead of the mean.
+#[cfg(feature = "amd")]
+pub fn ecc_match_robust_clipped<I, P>(
+    files: I,
+    params: EccMatchParameters,
+    clip: RobustClipParameters,
+    scale_down_width: Option<f32>,
+) -> Result<Mat, StackerError>
+where
+    I: IntoIterator<Item = P>,
+    P: AsRef<std::path::Path>,
+{
+    let files: Vec<PathBuf> = files.into_iter().map(|p| p.as_ref().to_path_buf()).collect();
+    amd::ecc_match_robust_clipped(&files, params, clip, scale_down_width)
+}
+
+/// `keypoint_match` with the kept frames combined by the median / MAD clip instead of the mean.
+#[cfg(feature = "amd")]
+pub fn keypoint_match_robust_clipped<I, P>(
+    files: I,
+    params: KeyPointMatchParameters,
+    clip: RobustClipParameters,
+    scale_down_width: Option<f32>,
+) -> Result<(i32, Mat), StackerError>
+where
+    I: IntoIterator<Item = P>,
+    P: AsRef<std::path::Path>,
+{
+    let files: Vec<PathBuf> = files.into_iter().map(|p| p.as_ref().to_path_buf()).collect();
+    amd::keypoint_match_robust_clipped(&files, params, clip, scale_down_width)
 }
 
 /// lib.rs:1032 — 'LAPM' (Nayar89). Single-channel 8-bit or f32 image.
