@@ -255,7 +255,8 @@ void        stk_host_free(void* p);
  *                        moments and normalised-rejection combines (changes results: an extension beyond the reference, which
  *                        knows bilinear samples only). Any other value: STK_INVALID_PARAMS. Cubic is defined on exact
  *                        coordinates only: with "warp_subpixel_bits" = 5 every call that folds returns STK_INVALID_PARAMS (the
- *                        pair is checked at the call, so the two options may be set in either order). Alignment (ECC,
+ *                        pair is checked at the call, so the two options may be set in either order). In the local-weighted
+ *                        fold the sample is cubic and the weight omega stays bilinear. Alignment (ECC,
  *                        ORB, homography) does not depend on it: warps, iteration counts and `dropped` are the same
  *   "profile"            0 off, 1 per-stage events (stk_get_timing), 2 + event pairs around ECC launches
  *   "profile_stride"     with profile = 2: bracket every n-th ECC launch only
@@ -500,6 +501,82 @@ stk_status stk_weighted_stack(stk_ctx* ctx, const stk_frames* frames, const doub
 stk_status stk_overlap_moments(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
                                int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
                                int32_t stat_step, double* moments);
+
+/* ---- per-pixel weight maps and local-sharpness (lucky-region) stacking: an EXTENSION beyond the reference --------
+ * The weighted combine above with a weight that varies per pixel, and a device pass that turns a frame into a local
+ * quality map, so that a stack whose frames are each sharp somewhere else is as sharp as its sharpest frame everywhere.
+ * Local quality map Q_i of frame i. 8-bit input only, in the frame's own pixel grid, integer arithmetic throughout:
+ *   g          the integer grey of the frame: stk_grey's value bit for bit. A one-channel frame is taken as it is; the
+ *              fourth channel of BGRA is ignored.
+ *   r101(p, n) OpenCV's borderInterpolate(p, n, BORDER_REFLECT_101), iterated until the index is inside; n == 1 gives 0.
+ *   ml(x, y)   = |2 g(x,y) - g(r101(x-1,w), y) - g(r101(x+1,w), y)| + |2 g(x,y) - g(x, r101(y-1,h)) - g(x, r101(y+1,h))|:
+ *              the per-pixel term of LAPM, 0 .. 1020.
+ *   mlT        = ml >= threshold ? ml : 0   (Nayar's sum-modified-Laplacian threshold: without it sensor noise, whose ml
+ *              is small but everywhere, dilutes the measure).
+ *   Q(x, y)    = the sum over dy, dx in [-radius, radius] of mlT(r101(x+dx, w), r101(y+dy, h)), stored as f32. It is at
+ *              most 1020 x 31^2 = 980 220 < 2^24: every value is an exactly represented integer, and no tiling,
+ *              summation order or launch shape can change a bit.
+ * Local-weighted fold. The samples s_i,c, the fold order, alpha, warp, warp_subpixel_bits, warp_interpolation and the
+ * coverage weight kappa_i are exactly those of the weighted combine with coverage = 1. The fold must run under
+ * BORDER_CONSTANT with border value 0 in every channel; anything else is STK_INVALID_PARAMS, because a weight taken
+ * outside a frame means nothing. Per destination pixel, entries in fold order; all values f32, each operation rounded on
+ * its own, `/` correctly rounded:
+ *   omega_i = the sample the LINEAR fold gives for plane map_i taken as a one-channel f32 frame of the source size, at
+ *             this entry's coordinates, alpha = 1, BORDER_CONSTANT 0: the same lerp chain, or under warp_subpixel_bits = 5
+ *             the classic four-weight sum. Always bilinear, also under STK_INTER_CUBIC: negative lobes would make
+ *             negative weights.
+ *   b     = omega_i + floor * kappa_i
+ *   u     = b;  repeated (power - 1) times: u = u * b
+ *   W     = w_i * u
+ *   v_c   = s_i,c * g_i,c + o_i,c * kappa_i
+ *   num_c = num_c + W * v_c
+ *   den   = den + W * kappa_i
+ *   out_c = den > 0 ? num_c / den : 0;     den_out (optional, w x h f32, in the location of `out`) = den
+ * g, o, w are the stk_frame_weight records of the weighted combine and follow its validity rules. On the rim s, omega and
+ * kappa are all premultiplied by the same coverage, so a constant scene comes back constant up to round-off. The floor
+ * keeps a pixel that no frame finds sharp (a flat sky: every Q is 0) a plain coverage-weighted mean instead of 0 / 0. Map
+ * values are expected finite and >= 0; they are not checked, and what they produce follows from the arithmetic above.
+ * Entry 0 is frame 0 through the identity, so omega_0 = map_0 exactly. A multi-device context runs these calls on its
+ * first device. */
+typedef struct {
+    int32_t radius;                 /* box window (2 radius + 1)^2 of the local sum: 1 .. 15 */
+    int32_t threshold;              /* modified-Laplacian values below it count 0: 0 .. 1020 */
+    int32_t power;                  /* the weight is the quality to this power: 1 .. 4 */
+    float   floor;                  /* added to the quality before the power: finite, >= 0 */
+    int32_t reserved[2];            /* 0 */
+} stk_local_params;
+
+/* The maps alone: Q of every frame in device passes over the stack. frames: 8-bit, 1, 3 or 4 channels, host or device
+ * memory, any row stride (a frame whose base address or row stride is no multiple of 4 is read byte by byte: same bits,
+ * slower); host frames are copied over in batches that fit the context's frame workspace. maps: n planes, width x
+ * height f32, tightly packed, in frames->location. power and floor are validated but unused. 16-bit and f32 frames:
+ * STK_NOT_IMPLEMENTED. stk_timing.prep_ms is the device time of the pass (for host frames with their copies). */
+stk_status stk_local_sharpness(stk_ctx* ctx, const stk_frames* frames, const stk_local_params* local, float* const* maps);
+/* The fold alone over caller-held warps and caller-held maps, with the arguments of stk_weighted_stack. The maps may be
+ * any non-negative weights: Q, a trail mask, a vignetting weight, an inverse variance. Any depth, 1 / 3 / 4 channels.
+ * maps: n planes (width x height f32, tightly packed) by frame index, in frames->location; planes of excluded frames
+ * are not read. per_frame_or_null: NULL = gain 1, offset 0, weight 1. floor, power: as in stk_local_params. */
+stk_status stk_local_weighted_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                    int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                    const stk_frame_weight* per_frame_or_null, const float* const* maps, float floor,
+                                    int32_t power, stk_image_f32* out, float* den_or_null);
+/* stk_ecc_match_weighted / stk_keypoint_match_weighted with the local-weighted fold: stats, warps, iteration counts,
+ * `dropped` and errors are the plain call's; gains and offsets come from the overlap-moments pass under weight->normalize;
+ * weight->coverage must be 1, else STK_INVALID_PARAMS. The maps of the frames that enter the fold are computed on the
+ * device from the full-size frames, also under scale_down_width (n_entries x width x height x 4 bytes of device memory;
+ * a failed allocation is STK_HIP_ERROR with the byte count in stk_last_error). By definition the result is
+ * stk_local_weighted_stack with the stats' warps, the `applied` records and stk_local_sharpness's maps, bit for bit.
+ * 8-bit BGR(A) frames only (16-bit, f32: STK_NOT_IMPLEMENTED). stk_timing.finalize_ms is the device time of the map
+ * pass plus the moments pass plus the fold. */
+stk_status stk_ecc_match_local_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                        const stk_weight_params* weight, const float* weights_or_null,
+                                        const stk_local_params* local, stk_image_f32* out, float* den_or_null,
+                                        stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_local_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                             float scale_down_width, const stk_weight_params* weight, const float* weights_or_null,
+                                             const stk_local_params* local, stk_image_f32* out, int32_t* dropped,
+                                             float* den_or_null, stk_frame_weight* applied_or_null,
+                                             stk_frame_stats* stats_or_null);
 
 /* ---- normalised, coverage-aware sigma-clip and quantile stacking: an EXTENSION beyond the reference -------------
  * The two rejection combines with the per-frame gain, offset and weight and the coverage of the weighted combine: frames

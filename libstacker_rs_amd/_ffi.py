@@ -67,6 +67,11 @@ class FrameWeight(C.Structure):
     _fields_ = [("gain", C.c_float * 4), ("offset", C.c_float * 4), ("weight", C.c_float), ("flags", C.c_int32)]
 
 
+class LocalParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("threshold", C.c_int32), ("power", C.c_int32), ("floor", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
 class SelectParams(C.Structure):
     _fields_ = [("metric", C.c_int32), ("ksize", C.c_int32), ("drop_worst", C.c_int32), ("keep_fraction", C.c_float),
                 ("weight_mode", C.c_int32), ("reserved", C.c_int32)]
@@ -131,6 +136,17 @@ SIGNATURES = {
                                       C.c_double, C.POINTER(FrameWeight), C.c_int32, C.POINTER(ImageF32), C.c_void_p]),
     "stk_overlap_moments": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_double, C.c_int32, C.c_void_p]),
+    "stk_local_sharpness": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(LocalParams), C.c_void_p]),
+    "stk_local_weighted_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_double, C.POINTER(FrameWeight), C.c_void_p, C.c_float, C.c_int32,
+                                            C.POINTER(ImageF32), C.c_void_p]),
+    "stk_ecc_match_local_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float,
+                                                C.POINTER(WeightParams), C.c_void_p, C.POINTER(LocalParams), C.POINTER(ImageF32),
+                                                C.c_void_p, C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
+    "stk_keypoint_match_local_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                                     C.POINTER(WeightParams), C.c_void_p, C.POINTER(LocalParams),
+                                                     C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p, C.POINTER(FrameWeight),
+                                                     C.POINTER(FrameStats)]),
     "stk_clip_stack_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_double, C.POINTER(ClipParams), C.POINTER(FrameWeight), C.c_int32, C.POINTER(ImageF32),
                                            C.c_void_p, C.c_void_p]),

@@ -157,6 +157,20 @@ class WeightParameters:           # extension beyond the reference: include/stac
         return _ffi.WeightParams(int(self.normalize), int(self.coverage), int(self.stat_step), 0)
 
 
+@dataclass
+class LocalParameters:            # extension beyond the reference: include/stacker.h, stk_local_params
+    """The local-sharpness (lucky-region) combines: the quality map of a frame is the sum of its modified-Laplacian values
+    of at least `threshold` (0 .. 1020) over a (2 radius + 1)^2 window (radius 1 .. 15); a frame's weight at a pixel is
+    (quality there + `floor`) to the `power` (1 .. 4)."""
+    radius: int = 4
+    threshold: int = 16
+    power: int = 2
+    floor: float = 1.0
+
+    def _c(self) -> _ffi.LocalParams:
+        return _ffi.LocalParams(int(self.radius), int(self.threshold), int(self.power), float(self.floor), (C.c_int32 * 2)(0, 0))
+
+
 SHARPNESS_LAPM, SHARPNESS_LAPV, SHARPNESS_TENG, SHARPNESS_GLVN = 0, 1, 2, 3
 QUALITY_WEIGHT_NONE, QUALITY_WEIGHT_SCORE = 0, 1
 
@@ -803,6 +817,115 @@ class Stacker:
                                                   int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), int(stat_step),
                                                   C.c_void_p(mom.ctypes.data)))
         return mom
+
+    # -- per-pixel weight maps and local-sharpness stacking (extension beyond the reference) --------------
+    def local_sharpness(self, files, local: Optional["LocalParameters"] = None):
+        """The local quality map of every frame of an 8-bit stack (stk_local_sharpness): n x H x W float32, exact integers,
+        placed where the frames live (a numpy array for host frames, a tensor for device frames)."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        if m.location == DEVICE:
+            import torch
+            maps = torch.empty((m.n, m.h, m.w), dtype=torch.float32, device=m.torch_device)
+            base = maps.data_ptr()
+        else:
+            maps = np.empty((m.n, m.h, m.w), np.float32)
+            base = maps.ctypes.data
+        ptrs = (C.c_void_p * m.n)(*[base + i * m.h * m.w * 4 for i in range(m.n)])
+        lp = (local or LocalParameters())._c()
+        self._check(self._lib.stk_local_sharpness(self._h, C.byref(m.c_frames), C.byref(lp), C.cast(ptrs, C.c_void_p)))
+        return maps
+
+    def _maps_arg(self, m: _Marshalled, maps):
+        """n tightly packed H x W float32 planes where the frames live: (owners, pointer array)."""
+        planes = list(maps)
+        if len(planes) != m.n:
+            raise InvalidParams("one weight map per frame expected")
+        keep, ptrs = [], []
+        for p in planes:
+            if m.location == DEVICE:
+                import torch
+                t = p if _is_torch(p) else torch.from_numpy(np.ascontiguousarray(np.asarray(p, np.float32)))
+                t = t.to(device=m.torch_device, dtype=torch.float32).contiguous()
+                if tuple(t.shape) != (m.h, m.w):
+                    raise InvalidParams("weight maps: H x W planes expected")
+                keep.append(t)
+                ptrs.append(t.data_ptr())
+            else:
+                a = np.ascontiguousarray(np.asarray(p.cpu().numpy() if _is_torch(p) else p, np.float32))
+                if a.shape != (m.h, m.w):
+                    raise InvalidParams("weight maps: H x W planes expected")
+                keep.append(a)
+                ptrs.append(a.ctypes.data)
+        return keep, (C.c_void_p * m.n)(*ptrs)
+
+    def local_weighted_stack(self, files, warps, maps, gain=None, offset=None, weights=None, include=None, *, applied=None,
+                             floor: float = 1.0, power: int = 2, is_affine=False, border_mode=BORDER_CONSTANT,
+                             border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_coverage: bool = False):
+        """The local-weighted fold alone over caller-held warps and caller-held per-pixel weight maps
+        (stk_local_weighted_stack): weighted_stack with the weight of frame i at a pixel multiplied by (the bilinear sample
+        of maps[i] there + floor) ** power. maps: n H x W float32 planes of non-negative weights (a quality map from
+        local_sharpness, a mask, an inverse variance). return_coverage adds the summed weight den."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Md, inc = self._warps_arg(warps, include, m.n)
+        rec = None if (gain is None and offset is None and weights is None and applied is None) \
+            else self._records_arg(m, gain, offset, weights, applied)
+        mkeep, mptrs = self._maps_arg(m, maps)
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        out, img = self._out_image(m)
+        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
+        self._check(self._lib.stk_local_weighted_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                       None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
+                                                       int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), rec,
+                                                       C.cast(mptrs, C.c_void_p), float(floor), int(power), C.byref(img), cptr))
+        return (out, cov) if return_coverage else out
+
+    def ecc_match_local_weighted(self, files, params: EccMatchParameters, local: Optional["LocalParameters"] = None,
+                                 weight: Optional["WeightParameters"] = None, weights=None, scale_down_width: Optional[float] = None,
+                                 return_stats: bool = False, return_coverage: bool = False, return_applied: bool = False):
+        """ecc_match with the local-weighted fold (stk_ecc_match_local_weighted): every frame weighs in at a pixel by its
+        local sharpness there. Arguments and results as ecc_match_weighted; weight.coverage must be True."""
+        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
+        wkeep, wptr = self._weights_arg(weights, m.n)
+        applied = (_ffi.FrameWeight * m.n)()
+        stats = (_ffi.FrameStats * m.n)()
+        p, wp, lp = params._c(), (weight or WeightParameters())._c(), (local or LocalParameters())._c()
+        self._check(self._lib.stk_ecc_match_local_weighted(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                           C.byref(wp), wptr, C.byref(lp), C.byref(img), cptr, applied, stats))
+        res = (out,) + ((cov,) if return_coverage else ()) + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) \
+            + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return res if len(res) > 1 else out
+
+    def keypoint_match_local_weighted(self, files, params: KeyPointMatchParameters, local: Optional["LocalParameters"] = None,
+                                      weight: Optional["WeightParameters"] = None, weights=None,
+                                      scale_down_width: Optional[float] = None, return_stats: bool = False,
+                                      return_coverage: bool = False, return_applied: bool = False):
+        """keypoint_match with the local-weighted fold (stk_keypoint_match_local_weighted): (dropped, image[, coverage]
+        [, applied][, stats]). A dropped frame is no sample: weight 0 in `applied`."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
+        wkeep, wptr = self._weights_arg(weights, m.n)
+        applied = (_ffi.FrameWeight * m.n)()
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p, wp, lp = params._c(), (weight or WeightParameters())._c(), (local or LocalParameters())._c()
+        self._check(self._lib.stk_keypoint_match_local_weighted(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                                C.byref(wp), wptr, C.byref(lp), C.byref(img), C.byref(dropped), cptr,
+                                                                applied, stats))
+        return (dropped.value, out) + ((cov,) if return_coverage else ()) \
+            + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
 
     # -- normalised, coverage-aware rejection combines (extension beyond the reference) -----------------
     def _pixel_counts_image(self, m: _Marshalled):

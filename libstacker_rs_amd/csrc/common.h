@@ -214,6 +214,13 @@ struct ClipArgs {
     // participating samples, written to the c plane; nothing is read); last pass: the kept weight sw to `kept` (optional)
     int centre;
     float* kept;
+    // the fold's local mode (FoldLocal, warp_body.h; kernels_local.hip; definition: include/stacker.h, stk_local_params):
+    // coef / out / den as in the weighted mode; maps[i] = the weight plane of table entry i (sw x sh f32, row stride
+    // map_stride floats), sampled bilinearly at the entry's coordinates; floor and power shape the weight
+    const float* const* maps;
+    size_t map_stride;
+    float floor;
+    int power;
 };
 
 // quantile combines: samples per pixel the selection kernel takes (64 lanes of a wave x 64 keys in registers)
@@ -266,6 +273,14 @@ hipError_t launch_clip_pass(const WarpArgs& a, const ClipArgs& c, int depth, hip
 // the weighted fold over the frames of `a` (c.coef, c.coverage, c.out / c.out_stride, c.den / c.den_stride; a.acc unused);
 // same kernel choice as launch_clip_pass
 hipError_t launch_weighted_fold(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
+// the local-weighted fold over the frames of `a` (c.coef, c.maps / c.map_stride, c.floor, c.power, c.out / c.out_stride,
+// c.den / c.den_stride; a.acc unused): the generic kernels, linear or cubic (kernels_local.hip)
+hipError_t launch_local_fold(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
+// the local quality maps of n 8-bit frames (cn 1, 3 or 4; frames_dev / maps_dev: device arrays of n frame pointers and n
+// w x h f32 plane pointers) in one launch (kernels_local.hip; definition: include/stacker.h, stk_local_params); n <= 65535
+int local_map_tiles(int w, int h);
+hipError_t launch_local_maps(const void* const* frames_dev, float* const* maps_dev, int n, int cn, int w, int h, size_t stride_bytes,
+                             int radius, int threshold, hipStream_t s);
 // stepped grid of the moments pass for a dw x dh destination: columns, rows per thread, workgroups in x and y
 struct MomentsPlan { int gw, gh, reps, bx, by; size_t parts() const { return (size_t)bx * by * 4; } };
 MomentsPlan moments_plan(int dw, int dh, int step);

@@ -93,6 +93,7 @@ struct stk_ctx {
     DevBuf weighted;              // weighted combine (weighted.cpp): image, den plane, per-entry table, moments and their partials
     DevBuf coef;                  // normalised rejection combines (robust.cpp): the per-entry gain / offset / weight table
     DevBuf quantile;              // quantile combines (quantile.cpp): a w x h x cn f32 image, then the band of samples
+    DevBuf local;                 // per-pixel weights (local.cpp): pointer tables, per-entry table, image, den plane, the entries' map planes
     DevBuf quality;               // whole-stack sharpness (quality.cpp): frame pointers, per-frame records, tile partials
     stk::KeypointWorkspace* kp = nullptr;
     stk::geom::HgWorkspace* hg = nullptr;   // findHomography batch workspace (homography.cpp)
@@ -182,6 +183,12 @@ stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_
                              size_t src_row_bytes, double alpha, int border_mode, const double* border_value, int is_affine,
                              int coverage, const stk_robust_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms);
 stk_status weighted_validate(stk_ctx* ctx, const stk_weight_params* p);
+stk_status weighted_check_out(stk_ctx* ctx, const stk_image_f32* out, const stk_frames* f);
+stk_status weighted_check_border(stk_ctx* ctx, int border_mode, const double* border_value, int coverage);
+// the caller-held-warps forms' frame table: uploads host frames, fills ctx->warpframes with the included frames under M
+// (entry_frame[k] = the frame index of entry k), begins the call's timing and synchronises
+stk_status weighted_table(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int is_affine,
+                          std::vector<int>& entry_frame);
 stk_status weighted_check_coefs(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, int cn);
 stk::WarpArgs weighted_warp_args(stk_ctx* ctx, int n_entries, int depth, int w, int h, int cn, size_t src_row_bytes, double alpha,
                                  int border_mode, const double* border_value, int is_affine);

@@ -15,6 +15,9 @@
 // an all-ones frame), which the rim paths compute and the u8 fast kernel's interior path knows to be 1. The generic kernel
 // has a fifth mode, moments (FoldMoments<CN>): the overlap moments of entry 1 + blockIdx.z against entry 0 over the
 // stepped pixels, a thread walking ClipArgs::reps stepped rows before its wave reduces.
+// The local mode (FoldLocal<CN>, below; launched from kernels_local.hip) is the weighted mode with a weight that varies per
+// pixel: besides kappa its hooks get the entry's coordinates (cs.coords), at which the state samples the entry's weight
+// plane itself. Generic kernels only.
 // The normalised, coverage-aware rejection combines add two states that take kappa through the same hooks: the weighted
 // clip (ClipWGeneric<CN> / ClipWU8C3, kernels_clip.hip) and the store mode with participation (FoldStoreW<CN>, below).
 // The bicubic fold (warp_cubic_body.h) is a second kernel that speaks the same hooks. What it shares with the generic kernel
@@ -32,6 +35,7 @@ template <int CN> struct FoldStore;
 template <int CN> struct FoldWeighted;
 template <int CN> struct FoldMoments;
 template <int CN> struct FoldStoreW;
+template <int CN> struct FoldLocal;
 template <int CN> struct ClipWGeneric;
 struct ClipWU8C3;
 
@@ -84,6 +88,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
     constexpr bool MOMENTS = std::is_same_v<ClipState, FoldMoments<CN>>;
     // the normalised, coverage-aware rejection states (kernels_clip.hip, FoldStoreW below) take kappa like the weighted mode
     constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>;
+    constexpr bool LOCAL = std::is_same_v<ClipState, FoldLocal<CN>>;      // kappa like the weighted mode, and the coordinates
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if constexpr (std::is_same_v<ClipState, FoldStore<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
@@ -276,6 +281,66 @@ struct FoldWeighted {
     __device__ __forceinline__ void add3k(float s0, float s1, float s2, float k) {
         entry(k);
         add(0, s0); add(1, s1); add(2, s2);
+    }
+    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
+        float* o = ca.out + (size_t)y * ca.out_stride + (size_t)x * CN;
+#pragma unroll
+        for (int c = 0; c < CN; c++) o[c] = den > 0.f ? num[c] / den : 0.f;
+        if (ca.den) ca.den[(size_t)y * ca.den_stride + x] = den;
+    }
+};
+
+// The local mode's state (definition: include/stacker.h, stk_local_params): FoldWeighted with coverage = 1 and a weight per
+// pixel. Per entry i of the frame table, in hook order entry(kappa), coords(..), add(0 .. CN - 1):
+//     omega = the bilinear sample of plane maps[i] at the entry's coordinates (four clamped loads, 0 where a tap is
+//             outside or the coordinate is not finite; the fold's lerp chain, or the classic four-weight sum; always
+//             bilinear, also under the cubic fold, whose kernel hands over the same coordinates)
+//     b = omega + floor * kappa;  u = b, (power - 1) times u = u * b;  W = w_i * u
+//     v = s * g_i,c + o_i,c * kappa;  num_c = num_c + W * v;  den = den + W * kappa
+// The table pointers (records, planes) move on after channel CN - 1.
+template <int CN>
+struct FoldLocal {
+    float num[CN], den, kap, W;
+    const stk_frame_weight* e;
+    const float* const* mp;
+    size_t ms;
+    float floor;
+    int power;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int, int) {
+#pragma unroll
+        for (int c = 0; c < CN; c++) num[c] = 0.f;
+        den = 0.f; kap = 1.0f; W = 0.f;
+        e = ca.coef; mp = ca.maps; ms = ca.map_stride; floor = ca.floor; power = ca.power;
+    }
+    __device__ __forceinline__ void entry(float k) { kap = k; }
+    __device__ __forceinline__ void coords(int ix, int iy, float ax, float ay, bool finite, bool classic, float w00, float w01,
+                                           float w10, float w11, int sw, int sh) {
+        const float* __restrict__ m = *mp;
+        const bool ix0 = finite & ((unsigned)ix < (unsigned)sw), ix1 = finite & ((unsigned)(ix + 1) < (unsigned)sw);
+        const bool iy0 = (unsigned)iy < (unsigned)sh, iy1 = (unsigned)(iy + 1) < (unsigned)sh;
+        // clamped addresses keep every load in bounds; out-of-plane taps are replaced afterwards
+        const int cx0 = min(max(ix, 0), sw - 1), cx1 = min(max(ix + 1, 0), sw - 1);
+        const int cy0 = min(max(iy, 0), sh - 1), cy1 = min(max(iy + 1, 0), sh - 1);
+        const float* r0 = m + (size_t)cy0 * ms;
+        const float* r1 = m + (size_t)cy1 * ms;
+        const float p00 = (ix0 & iy0) ? r0[cx0] : 0.0f, p01 = (ix1 & iy0) ? r0[cx1] : 0.0f;
+        const float p10 = (ix0 & iy1) ? r1[cx0] : 0.0f, p11 = (ix1 & iy1) ? r1[cx1] : 0.0f;
+        float om;
+        if (classic) om = p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11;
+        else {
+            const float t0 = __builtin_fmaf(ax, p01 - p00, p00);
+            const float t1 = __builtin_fmaf(ax, p11 - p10, p10);
+            om = __builtin_fmaf(ay, t1 - t0, t0);
+        }
+        const float b = om + floor * kap;
+        float u = b;
+        for (int k = 1; k < power; k++) u = u * b;
+        W = e->weight * u;
+    }
+    __device__ __forceinline__ void add(int c, float s) {
+        const float v = s * e->gain[c] + e->offset[c] * kap;
+        num[c] = num[c] + W * v;
+        if (c == CN - 1) { den = den + W * kap; e++; mp++; }
     }
     __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
         float* o = ca.out + (size_t)y * ca.out_stride + (size_t)x * CN;

@@ -32,6 +32,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_cubic_kernel(WarpArgs a, 
     constexpr bool WEIGHTED = std::is_same_v<ClipState, FoldWeighted<CN>>;
     constexpr bool MOMENTS = std::is_same_v<ClipState, FoldMoments<CN>>;
     constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>;
+    constexpr bool LOCAL = std::is_same_v<ClipState, FoldLocal<CN>>;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if constexpr (std::is_same_v<ClipState, FoldStore<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
@@ -65,7 +66,9 @@ __global__ __launch_bounds__(256) void warp_accumulate_cubic_kernel(WarpArgs a, 
             cubic_weights(ay, wy);
             // every tap is inside the frame: no clamps, no border selects, and kappa is exactly 1
             const T* q = src + (size_t)(iy - 1) * a.src_stride + (size_t)(ix - 1) * CN;
-            if constexpr (WEIGHTED || MOMENTS || ROBUST) cs.entry(1.0f);
+            if constexpr (WEIGHTED || MOMENTS || ROBUST || LOCAL) cs.entry(1.0f);
+            // the local mode's weight stays bilinear: the four inner taps of the footprint, all inside
+            if constexpr (LOCAL) cs.coords(ix, iy, ax, ay, true, false, 0.f, 0.f, 0.f, 0.f, a.sw, a.sh);
 #pragma unroll
             for (int c = 0; c < CN; c++) {
                 float hr[4];
@@ -137,6 +140,8 @@ struct LinearCollect {
     float v[3], k;
     __device__ __forceinline__ void entry(float kk) { k = kk; }
     __device__ __forceinline__ void add(int c, float s) { v[c] = s; }
+    // (never called: the fragment names the local mode's hook, and this state's type does not depend on a template argument)
+    __device__ __forceinline__ void coords(int, int, float, float, bool, bool, float, float, float, float, int, int) {}
 };
 
 // WU: frames in flight per lane. MODE = false: the mean fold (running sums into a.acc); true: the hooks of FastState.
@@ -252,7 +257,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_cubic_u8c3_kernel(WarpArg
                     // the linear sample: the generic kernels' text, collected instead of folded
                     typedef uint8_t T;
                     constexpr int CN = 3;
-                    constexpr bool CLIP = true, WEIGHTED = KAPPA, MOMENTS = false, ROBUST = false;
+                    constexpr bool CLIP = true, WEIGHTED = KAPPA, MOMENTS = false, ROBUST = false, LOCAL = false;
                     constexpr int mode = STK_BORDER_CONSTANT;
                     const T* __restrict__ src = (const T*)fr->src;
                     const float w00 = 0, w01 = 0, w10 = 0, w11 = 0;

@@ -142,6 +142,24 @@ void weighted_estimate(const double* m /* cn x 6 */, int cn, int mode, stk_frame
     }
 }
 
+// common argument checks of the caller-held-warps forms (shared with local.cpp: context.h); fills the table's frame indices
+stk_status weighted_table(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int is_affine,
+                          std::vector<int>& entry_frame) {
+    const int n = frames->n, w = frames->width, h = frames->height;
+    for (int i = 0; i < n; i++) if (!include || include[i]) entry_frame.push_back(i);
+    if (entry_frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "weighted: no frame included");
+    (void)hipSetDevice(ctx->device);
+    timing_begin(ctx);
+    std::vector<const void*> dev;
+    stk_status st = resolve_frames(ctx, frames, dev);
+    if (st) return st;
+    std::vector<WarpFrame> wf(entry_frame.size());
+    for (size_t k = 0; k < entry_frame.size(); k++) make_warp_frame(wf[k], dev[entry_frame[k]], M + 9 * (size_t)entry_frame[k], is_affine);
+    if ((st = warp_table_upload(ctx, wf, frame_row_bytes(frames), w, h, is_affine))) return st;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));       // `wf` leaves scope
+    return STK_OK;
+}
+
 namespace {
 
 // The weighted fold over the n_entries entries of ctx->warpframes with the per-entry records `coef`. Writes `out` and
@@ -204,24 +222,6 @@ stk_status weighted_finish(stk_ctx* ctx, const stk_frames* frames, const std::ve
         for (int i = 0; i < n; i++) { weighted_estimate(nullptr, cn, 0, &applied[i]); applied[i].weight = 0.0f; }
         for (int k = 0; k < ne; k++) applied[entry_frame[k]] = coef[k];
     }
-    return STK_OK;
-}
-
-// common argument checks of the two caller-held-warps forms; fills the table's frame indices
-stk_status weighted_table(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int is_affine,
-                          std::vector<int>& entry_frame) {
-    const int n = frames->n, w = frames->width, h = frames->height;
-    for (int i = 0; i < n; i++) if (!include || include[i]) entry_frame.push_back(i);
-    if (entry_frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "weighted: no frame included");
-    (void)hipSetDevice(ctx->device);
-    timing_begin(ctx);
-    std::vector<const void*> dev;
-    stk_status st = resolve_frames(ctx, frames, dev);
-    if (st) return st;
-    std::vector<WarpFrame> wf(entry_frame.size());
-    for (size_t k = 0; k < entry_frame.size(); k++) make_warp_frame(wf[k], dev[entry_frame[k]], M + 9 * (size_t)entry_frame[k], is_affine);
-    if ((st = warp_table_upload(ctx, wf, frame_row_bytes(frames), w, h, is_affine))) return st;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));       // `wf` leaves scope
     return STK_OK;
 }
 

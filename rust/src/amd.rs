@@ -9,7 +9,7 @@
 //!   decoded by OpenCV's `imread(IMREAD_UNCHANGED)` exactly as `read_grey_and_f32` does (utils.rs:132) and handed over
 //!   as host frames.
 use crate::amd_ffi::*;
-use crate::{utils, EccMatchParameters, KeyPointMatchParameters, RobustClipParameters, StackerError};
+use crate::{utils, EccMatchParameters, KeyPointMatchParameters, LocalParameters, RobustClipParameters, StackerError};
 use opencv::core;
 use opencv::imgcodecs;
 use opencv::prelude::*;
@@ -334,6 +334,75 @@ pub(crate) fn keypoint_match_robust_clipped(
     let st = unsafe {
         stk_keypoint_match_robust_clipped(
             ctx, &frames, &p, scale_down_width.unwrap_or(0.0), &c, &mut img, &mut dropped, std::ptr::null_mut(), std::ptr::null_mut(),
+        )
+    };
+    if st == STK_OK { Ok((dropped, out)) } else { Err(to_err(ctx, st)) }
+}
+
+fn local_params(p: &LocalParameters) -> stk_local_params {
+    stk_local_params { radius: p.radius, threshold: p.threshold, power: p.power, floor: p.floor, reserved: [0, 0] }
+}
+
+/// the `*_local_weighted` combines' normalisation: LINEAR onto frame 0, coverage on (the fold requires it), default step
+fn local_weight_params(normalize: i32) -> stk_weight_params {
+    stk_weight_params { normalize, coverage: 1, stat_step: 0, reserved: 0 }
+}
+
+/// `ecc_match` with the local-weighted fold in place of the mean (include/stacker.h, stk_ecc_match_local_weighted): every
+/// frame weighs in at a pixel by its local sharpness there. The combine has no `*_files` form: the stack is decoded by
+/// OpenCV and handed over as host frames.
+pub(crate) fn ecc_match_local_weighted(
+    files: &[PathBuf],
+    params: EccMatchParameters,
+    local: LocalParameters,
+    normalize: i32,
+    scale_down_width: Option<f32>,
+) -> Result<Mat, StackerError> {
+    if files.is_empty() {
+        return Err(StackerError::NotEnoughFiles);
+    }
+    let guard = shared_ctx()?;
+    let ctx = guard.0;
+    let p = ecc_params(&params);
+    let l = local_params(&local);
+    let w = local_weight_params(normalize);
+    let stack = DecodedStack::read(files)?;
+    let frames = stack.frames()?;
+    let (out, mut img) = new_output(frames.width, frames.height, frames.channels)?;
+    let st = unsafe {
+        stk_ecc_match_local_weighted(
+            ctx, &frames, &p, scale_down_width.unwrap_or(0.0), &w, std::ptr::null(), &l, &mut img, std::ptr::null_mut(),
+            std::ptr::null_mut(), std::ptr::null_mut(),
+        )
+    };
+    if st == STK_OK { Ok(out) } else { Err(to_err(ctx, st)) }
+}
+
+/// `keypoint_match` with the local-weighted fold (stk_keypoint_match_local_weighted): (dropped, image). One geometry for
+/// the whole stack, as the combine asks.
+pub(crate) fn keypoint_match_local_weighted(
+    files: &[PathBuf],
+    params: KeyPointMatchParameters,
+    local: LocalParameters,
+    normalize: i32,
+    scale_down_width: Option<f32>,
+) -> Result<(i32, Mat), StackerError> {
+    if files.is_empty() {
+        return Err(StackerError::NotEnoughFiles);
+    }
+    let guard = shared_ctx()?;
+    let ctx = guard.0;
+    let p = kp_params(&params);
+    let l = local_params(&local);
+    let w = local_weight_params(normalize);
+    let stack = DecodedStack::read(files)?;
+    let frames = stack.frames()?;
+    let (out, mut img) = new_output(frames.width, frames.height, frames.channels)?;
+    let mut dropped: i32 = 0;
+    let st = unsafe {
+        stk_keypoint_match_local_weighted(
+            ctx, &frames, &p, scale_down_width.unwrap_or(0.0), &w, std::ptr::null(), &l, &mut img, &mut dropped, std::ptr::null_mut(),
+            std::ptr::null_mut(), std::ptr::null_mut(),
         )
     };
     if st == STK_OK { Ok((dropped, out)) } else { Err(to_err(ctx, st)) }

@@ -103,6 +103,27 @@ impl Default for RobustClipParameters {
     }
 }
 
+/// Local-sharpness (lucky-region) weighting for the `*_local_weighted` combines, an extension beyond the reference
+/// (include/stacker.h, `stk_local_params`): a frame's quality at a pixel is the sum of its modified-Laplacian values of at
+/// least `threshold` over a (2 `radius` + 1)^2 window, and its weight there is (quality + `floor`) to the `power`.
+#[derive(Debug, Copy, Clone)]
+pub struct LocalParameters {
+    /// 1 ..= 15
+    pub radius: i32,
+    /// 0 ..= 1020
+    pub threshold: i32,
+    /// 1 ..= 4
+    pub power: i32,
+    /// finite, >= 0
+    pub floor: f32,
+}
+
+impl Default for LocalParameters {
+    fn default() -> Self {
+        Self { radius: 4, threshold: 16, power: 2, floor: 1.0 }
+    }
+}
+
 /// lib.rs:129-137: aligns every frame to the first by ORB + brute-force Hamming + `findHomography`, warps and averages.
 /// Returns (number of frames that could not be matched and were left out, averaged CV_32FC3 image).
 #[cfg(feature = "amd")]
@@ -164,6 +185,41 @@ where
 {
     let files: Vec<PathBuf> = files.into_iter().map(|p| p.as_ref().to_path_buf()).collect();
     amd::keypoint_match_robust_clipped(&files, params, clip, scale_down_width)
+}
+
+/// `ecc_match` with every frame weighing in at a pixel by its local sharpness there instead of the plain mean.
+/// `normalize`: 0 none, 1 offset, 2 gain, 3 linear (the weighted combine's per-frame normalisation onto frame 0).
+#[cfg(feature = "amd")]
+pub fn ecc_match_local_weighted<I, P>(
+    files: I,
+    params: EccMatchParameters,
+    local: LocalParameters,
+    normalize: i32,
+    scale_down_width: Option<f32>,
+) -> Result<Mat, StackerError>
+where
+    I: IntoIterator<Item = P>,
+    P: AsRef<std::path::Path>,
+{
+    let files: Vec<PathBuf> = files.into_iter().map(|p| p.as_ref().to_path_buf()).collect();
+    amd::ecc_match_local_weighted(&files, params, local, normalize, scale_down_width)
+}
+
+/// `keypoint_match` with the kept frames combined by their local sharpness instead of the plain mean.
+#[cfg(feature = "amd")]
+pub fn keypoint_match_local_weighted<I, P>(
+    files: I,
+    params: KeyPointMatchParameters,
+    local: LocalParameters,
+    normalize: i32,
+    scale_down_width: Option<f32>,
+) -> Result<(i32, Mat), StackerError>
+where
+    I: IntoIterator<Item = P>,
+    P: AsRef<std::path::Path>,
+{
+    let files: Vec<PathBuf> = files.into_iter().map(|p| p.as_ref().to_path_buf()).collect();
+    amd::keypoint_match_local_weighted(&files, params, local, normalize, scale_down_width)
 }
 
 /// lib.rs:1032 — 'LAPM' (Nayar89). Single-channel 8-bit or f32 image.
