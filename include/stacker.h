@@ -578,6 +578,98 @@ stk_status stk_keypoint_match_local_weighted(stk_ctx* ctx, const stk_frames* fra
                                              float* den_or_null, stk_frame_weight* applied_or_null,
                                              stk_frame_stats* stats_or_null);
 
+/* ---- local alignment: per-frame displacement fields on a node grid: an EXTENSION beyond the reference -------------
+ * Every other alignment here is one global map per frame. The atmosphere moves each part of a frame by its own one to
+ * three pixels, which no homography removes; this section measures, per frame, a residual displacement on a grid of nodes
+ * on top of the frame's global warp ("alignment points"), and folds through it. w x h is the destination size, which is
+ * frame 0's; sw x sh the source frames' (all frames of a stk_frames share one geometry, so sw = w and sh = h).
+ * Grid. gw = (w - 1 + step - 1) / step + 1, gh likewise from h (stk_mesh_grid). Node (j, k) sits at destination pixel
+ *   (cx, cy) = (k step, j step); the last column and row may lie on or beyond the image edge. A field is gh x gw x 2 f32
+ *   (dx, dy interleaved), tightly packed; a status plane is gh x gw int32.
+ * Estimation ("local align"). 8-bit frames of 1, 3 or 4 channels. g_i is stk_grey's integer grey of frame i (a one-channel
+ *   frame as it is; the fourth channel of BGRA ignored). For an included frame i >= 1, M_i is the fold's own f32
+ *   destination -> source matrix: the forward warp inverted in double (cv::invert's adjugate, or invertAffineTransform),
+ *   then cast to f32. Template gradients, exact integers: Tx(x,y) = g_0(x+1,y) - g_0(x-1,y), Ty(x,y) = g_0(x,y+1) - g_0(x,y-1).
+ *   Per node the patch P is the set of integer pixels with |x - cx| <= radius, |y - cy| <= radius, 1 <= x <= w - 2 and
+ *   1 <= y <= h - 2. P empty: status -1. Otherwise d = (0, 0) in f32, and for it = 1 .. max_iters:
+ *   1. per pixel of P, in f32, each operation rounded on its own: fx = (float)x + dx, fy = (float)y + dy; (X, Y), finite,
+ *      ix, iy, ax, ay exactly the fold's at (fx, fy) under warp_subpixel_bits = 0 with M_i and is_affine (fma chains, true
+ *      division, floor; finite = |X| < 1e9 and |Y| < 1e9). The pixel is live iff finite && ix >= 0 && ix + 1 <= sw - 1 &&
+ *      iy >= 0 && iy + 1 <= sh - 1. I = the fold's lerp chain over (float)g_i at the four taps: t0 = fma(ax, p01 - p00, p00),
+ *      t1 = fma(ax, p11 - p10, p10), I = fma(ay, t1 - t0, t0). e = I - (float)g_0(x,y).
+ *   2. over the live pixels, in f64: n, Sxx = sum Tx^2, Sxy = sum Tx Ty, Syy = sum Ty^2 (integers, exact), bx = sum Tx e,
+ *      by = sum Ty e (every product exact; the order of the additions is the kernel's, and it is fixed: a lane's pixels in
+ *      patch order, then a xor-shuffle tree over the wave).
+ *   3. 2 n < |P|: status -2.
+ *   4. lam = 0.5 ((Sxx + Syy) - sqrt((Sxx - Syy)^2 + 4 Sxy^2)), det = Sxx Syy - Sxy^2, in f64, each operation rounded on
+ *      its own. det <= 0 or lam < (4 min_eig) n: status -3 (the factor 4: the gradients are the unscaled differences).
+ *   5. Dx = 2 (Syy bx - Sxy by) / det, Dy = 2 (Sxx by - Sxy bx) / det; dx = (float)((double)dx - Dx), dy likewise.
+ *   6. dx^2 + dy^2 (in f64) > max_shift^2, or not finite: status -4.
+ *   7. Dx^2 + Dy^2 (in f64) < epsilon^2: stop.
+ *   The status is the number of iterations run, 1 .. max_iters; a node that exhausts max_iters is valid and keeps its last
+ *   d. An invalid node has d = (0, 0). Frame 0 and excluded frames get no field: their planes are not written.
+ *   This is inverse-compositional Lucas-Kanade for a translation in DESTINATION space: the warped frame W(p) = I_i(M_i p)
+ *   is matched to frame 0 at p + d, so the fold only has to move the destination coordinate before it applies its matrix.
+ * Fill. `fill` Jacobi passes over each frame's grid. m = 1 for valid nodes; k = [1 2 1]^T [1 2 1]. For every node with
+ *   m = 0, over its in-grid 3 x 3 neighbours with m = 1 in row-major order, in f32: den = den + k, num_c = num_c + k d_c;
+ *   den > 0: d = num / den and the node counts as valid from the next pass on. Valid nodes never change. The status plane
+ *   keeps the estimation's codes. (No smoothing of valid nodes: a 3 x 3 binomial smoothing made the prototype worse.)
+ * Mesh fold. Destination pixel (x, y), table entry i with field D: k = x / step, j = y / step, k1 = min(k + 1, gw - 1),
+ *   j1 = min(j + 1, gh - 1); u = (float)(x - k step) * (1.0f / step), v likewise (both exact); per component c:
+ *   t0 = fma(u, D[j][k1][c] - D[j][k][c], D[j][k][c]), t1 the same on row j1, d_c = fma(v, t1 - t0, t0);
+ *   fx = (float)x + d_0, fy = (float)y + d_1. Everything after that is the existing fold, unchanged: coordinates, sample,
+ *   border, alpha, kappa, and the local-weighted fold's omega at the displaced coordinates. Frame 0 has no field (its plane
+ *   is not read). A zero field returns the plain fold's bits. Field values are expected finite and are not checked.
+ *   warp_subpixel_bits = 5: STK_INVALID_PARAMS. warp_interpolation = STK_INTER_CUBIC: STK_NOT_IMPLEMENTED for the mesh
+ *   folds (the bicubic mesh fold is a follow-up). A multi-device context runs these calls on its first device. */
+typedef struct {
+    int32_t step;       /* node spacing in destination pixels: 8, 16, 32, 64, 128 or 256 (a power of two) */
+    int32_t radius;     /* patch half size, patch = (2 radius + 1)^2: 2 .. 32 */
+    int32_t max_iters;  /* 1 .. 32 */
+    float   epsilon;    /* stop when |delta|^2 < epsilon^2; finite, >= 0 (0: always max_iters iterations) */
+    float   max_shift;  /* a node whose |d| exceeds it is invalid: finite, > 0, <= 64 */
+    float   min_eig;    /* texture threshold, grey levels^2 per live pixel: finite, >= 0 */
+    int32_t fill;       /* hole-filling passes: 0 .. 16 */
+    int32_t reserved;   /* 0 */
+} stk_mesh_params;
+
+/* The grid of a width x height destination. Bad arguments (a step that is no power of two in 8 .. 256, a NULL pointer):
+ * STK_INVALID_PARAMS. */
+stk_status stk_mesh_grid(int32_t width, int32_t height, int32_t step, int32_t* gw, int32_t* gh);
+/* The fields alone. M: forward warps by frame index (9 doubles each), include_or_null, is_affine: as in stk_weighted_stack.
+ * fields / status_or_null: n planes by frame index, in frames->location; entries for frame 0 and for excluded frames may
+ * be NULL and are not written; status_or_null or single entries of it may be NULL. Host frames are copied over in batches
+ * that fit the context's frame workspace. 16-bit and f32 frames: STK_NOT_IMPLEMENTED. stk_timing.align_ms is the device
+ * time of the pass (estimation and fill). */
+stk_status stk_local_align(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null, int32_t is_affine,
+                           const stk_mesh_params* mesh, float* const* fields, int32_t* const* status_or_null);
+/* The plain mean through the fields: the sums in fold order x (float)(1.0 / N), N = the included frames. Arguments as
+ * stk_clip_stack's; any depth, 1 / 3 / 4 channels, border modes 0 .. 4. fields: n planes by frame index in
+ * frames->location for the grid of `step`; those of frame 0 and of excluded frames are not read. `out` tightly packed. */
+stk_status stk_mesh_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null, int32_t is_affine,
+                          int32_t border_mode, const double* border_value, double alpha, const float* const* fields, int32_t step,
+                          stk_image_f32* out);
+/* stk_local_weighted_stack through the fields: its arguments, its checks, its arithmetic at the displaced coordinates. */
+stk_status stk_mesh_local_weighted_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                         int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                         const stk_frame_weight* per_frame_or_null, const float* const* maps, float floor,
+                                         int32_t power, const float* const* fields, int32_t step, stk_image_f32* out,
+                                         float* den_or_null);
+/* stk_ecc_match / stk_keypoint_match with local alignment: stats, warps, iteration counts, `dropped` and errors are the
+ * plain call's. The fields of the frames that enter the fold are computed on the device from the full-size resident frames
+ * with the stats' warps, also under scale_down_width. local_or_null == NULL: the result is stk_mesh_stack's (alpha 1 / 255;
+ * BORDER_CONSTANT 0, or the keypoint parameters' border); otherwise stk_mesh_local_weighted_stack's with NULL records,
+ * stk_local_sharpness's maps and local's floor and power (the keypoint parameters' border must then be BORDER_CONSTANT 0).
+ * By definition the result equals those parts bit for bit. 8-bit BGR(A) frames only (16-bit, f32: STK_NOT_IMPLEMENTED).
+ * stk_timing.finalize_ms is the device time of the field pass plus the map pass plus the fold. A failed device
+ * allocation is STK_HIP_ERROR with the byte count in stk_last_error. */
+stk_status stk_ecc_match_local_aligned(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                       const stk_mesh_params* mesh, const stk_local_params* local_or_null, stk_image_f32* out,
+                                       stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_local_aligned(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                            float scale_down_width, const stk_mesh_params* mesh, const stk_local_params* local_or_null,
+                                            stk_image_f32* out, int32_t* dropped, stk_frame_stats* stats_or_null);
+
 /* ---- normalised, coverage-aware sigma-clip and quantile stacking: an EXTENSION beyond the reference -------------
  * The two rejection combines with the per-frame gain, offset and weight and the coverage of the weighted combine: frames
  * are compared after each has been mapped onto frame 0's level, and a frame that does not cover a pixel is no sample of

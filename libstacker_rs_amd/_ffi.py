@@ -72,6 +72,11 @@ class LocalParams(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class MeshParams(C.Structure):
+    _fields_ = [("step", C.c_int32), ("radius", C.c_int32), ("max_iters", C.c_int32), ("epsilon", C.c_float),
+                ("max_shift", C.c_float), ("min_eig", C.c_float), ("fill", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SelectParams(C.Structure):
     _fields_ = [("metric", C.c_int32), ("ksize", C.c_int32), ("drop_worst", C.c_int32), ("keep_fraction", C.c_float),
                 ("weight_mode", C.c_int32), ("reserved", C.c_int32)]
@@ -147,6 +152,19 @@ SIGNATURES = {
                                                      C.POINTER(WeightParams), C.c_void_p, C.POINTER(LocalParams),
                                                      C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p, C.POINTER(FrameWeight),
                                                      C.POINTER(FrameStats)]),
+    "stk_mesh_grid": (c_status, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "stk_local_align": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MeshParams), C.c_void_p,
+                                   C.c_void_p]),
+    "stk_mesh_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_double, C.c_void_p, C.c_int32, C.POINTER(ImageF32)]),
+    "stk_mesh_local_weighted_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                 C.c_void_p, C.c_double, C.POINTER(FrameWeight), C.c_void_p, C.c_float, C.c_int32,
+                                                 C.c_void_p, C.c_int32, C.POINTER(ImageF32), C.c_void_p]),
+    "stk_ecc_match_local_aligned": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float, C.POINTER(MeshParams),
+                                               C.POINTER(LocalParams), C.POINTER(ImageF32), C.POINTER(FrameStats)]),
+    "stk_keypoint_match_local_aligned": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                                    C.POINTER(MeshParams), C.POINTER(LocalParams), C.POINTER(ImageF32),
+                                                    C.POINTER(C.c_int32), C.POINTER(FrameStats)]),
     "stk_clip_stack_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_double, C.POINTER(ClipParams), C.POINTER(FrameWeight), C.c_int32, C.POINTER(ImageF32),
                                            C.c_void_p, C.c_void_p]),

@@ -171,6 +171,33 @@ class LocalParameters:            # extension beyond the reference: include/stac
         return _ffi.LocalParams(int(self.radius), int(self.threshold), int(self.power), float(self.floor), (C.c_int32 * 2)(0, 0))
 
 
+@dataclass
+class MeshParameters:             # extension beyond the reference: include/stacker.h, stk_mesh_params
+    """Local alignment: per frame a residual displacement on a grid of nodes `step` destination pixels apart (a power of
+    two, 8 .. 256), each from a (2 radius + 1)^2 patch (radius 2 .. 32) by at most `max_iters` Lucas-Kanade iterations that
+    stop below `epsilon` px. A node that moves beyond `max_shift` px, sees less than half its patch or has less texture
+    than `min_eig` (grey levels^2 per pixel) is invalid; `fill` passes fill such holes from their neighbours."""
+    step: int = 16
+    radius: int = 8
+    max_iters: int = 10
+    epsilon: float = 0.01
+    max_shift: float = 8.0
+    min_eig: float = 1.0
+    fill: int = 2
+
+    def _c(self) -> _ffi.MeshParams:
+        return _ffi.MeshParams(int(self.step), int(self.radius), int(self.max_iters), float(self.epsilon), float(self.max_shift),
+                               float(self.min_eig), int(self.fill), 0)
+
+
+def mesh_grid(width: int, height: int, step: int):
+    """(gw, gh): the node grid of a width x height destination at spacing `step` (stk_mesh_grid)."""
+    gw, gh = C.c_int32(0), C.c_int32(0)
+    if _ffi.load().stk_mesh_grid(int(width), int(height), int(step), C.byref(gw), C.byref(gh)) != 0:
+        raise InvalidParams("mesh_grid: width and height must be positive, step a power of two in 8 .. 256")
+    return gw.value, gh.value
+
+
 SHARPNESS_LAPM, SHARPNESS_LAPV, SHARPNESS_TENG, SHARPNESS_GLVN = 0, 1, 2, 3
 QUALITY_WEIGHT_NONE, QUALITY_WEIGHT_SCORE = 0, 1
 
@@ -926,6 +953,133 @@ class Stacker:
                                                                 applied, stats))
         return (dropped.value, out) + ((cov,) if return_coverage else ()) \
             + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+
+    # -- local alignment: displacement fields on a node grid (extension beyond the reference) -----------
+    def local_align(self, files, warps, mesh: Optional["MeshParameters"] = None, include=None, *, is_affine=False,
+                    return_status: bool = False):
+        """The displacement fields of an 8-bit stack over caller-held warps (stk_local_align): n x gh x gw x 2 float32
+        (dx, dy), placed where the frames live; frame 0's and excluded frames' are zero. return_status adds the
+        n x gh x gw int32 status planes (iterations run, or -1 .. -4; 0 for frames without a field)."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        mp = (mesh or MeshParameters())._c()
+        Md, inc = self._warps_arg(warps, include, m.n)
+        gw, gh = mesh_grid(m.w, m.h, mp.step) if mp.step in (8, 16, 32, 64, 128, 256) else (1, 1)
+        if m.location == DEVICE:
+            import torch
+            fields = torch.zeros((m.n, gh, gw, 2), dtype=torch.float32, device=m.torch_device)
+            status = torch.zeros((m.n, gh, gw), dtype=torch.int32, device=m.torch_device)
+            fbase, sbase = fields.data_ptr(), status.data_ptr()
+        else:
+            fields = np.zeros((m.n, gh, gw, 2), np.float32)
+            status = np.zeros((m.n, gh, gw), np.int32)
+            fbase, sbase = fields.ctypes.data, status.ctypes.data
+        fp = (C.c_void_p * m.n)(*[fbase + i * gh * gw * 8 for i in range(m.n)])
+        sp = (C.c_void_p * m.n)(*[sbase + i * gh * gw * 4 for i in range(m.n)])
+        self._check(self._lib.stk_local_align(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                              None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine), C.byref(mp),
+                                              C.cast(fp, C.c_void_p), C.cast(sp, C.c_void_p) if return_status else None))
+        return (fields, status) if return_status else fields
+
+    def _fields_arg(self, m: _Marshalled, fields, step):
+        """n tightly packed gh x gw x 2 float32 planes where the frames live: (owners, pointer array)."""
+        gw, gh = mesh_grid(m.w, m.h, step) if step in (8, 16, 32, 64, 128, 256) else (None, None)
+        planes = list(fields)
+        if len(planes) != m.n:
+            raise InvalidParams("one field per frame expected")
+        keep, ptrs = [], []
+        for p in planes:
+            if m.location == DEVICE:
+                import torch
+                t = p if _is_torch(p) else torch.from_numpy(np.ascontiguousarray(np.asarray(p, np.float32)))
+                t = t.to(device=m.torch_device, dtype=torch.float32).contiguous()
+                shape = tuple(t.shape)
+                keep.append(t)
+                ptrs.append(t.data_ptr())
+            else:
+                a = np.ascontiguousarray(np.asarray(p.cpu().numpy() if _is_torch(p) else p, np.float32))
+                shape = a.shape
+                keep.append(a)
+                ptrs.append(a.ctypes.data)
+            if gw is not None and shape != (gh, gw, 2):
+                raise InvalidParams("fields: gh x gw x 2 planes expected (mesh_grid)")
+        return keep, (C.c_void_p * m.n)(*ptrs)
+
+    def mesh_stack(self, files, warps, fields, step: int, include=None, *, is_affine=False, border_mode=BORDER_CONSTANT,
+                   border_value=(0, 0, 0, 0), alpha=1.0 / 255.0):
+        """The plain mean of the included frames, each folded through its warp and its displacement field
+        (stk_mesh_stack). fields: n gh x gw x 2 float32 planes for the grid of `step` (local_align's result)."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Md, inc = self._warps_arg(warps, include, m.n)
+        fkeep, fptrs = self._fields_arg(m, fields, step)
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        out, img = self._out_image(m)
+        self._check(self._lib.stk_mesh_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                             None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine), int(border_mode),
+                                             C.c_void_p(bv.ctypes.data), float(alpha), C.cast(fptrs, C.c_void_p), int(step),
+                                             C.byref(img)))
+        return out
+
+    def mesh_local_weighted_stack(self, files, warps, maps, fields, step: int, gain=None, offset=None, weights=None, include=None, *,
+                                  applied=None, floor: float = 1.0, power: int = 2, is_affine=False, border_mode=BORDER_CONSTANT,
+                                  border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_coverage: bool = False):
+        """local_weighted_stack through displacement fields (stk_mesh_local_weighted_stack): samples, coverage and the
+        weight maps are all taken at the displaced coordinates."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Md, inc = self._warps_arg(warps, include, m.n)
+        rec = None if (gain is None and offset is None and weights is None and applied is None) \
+            else self._records_arg(m, gain, offset, weights, applied)
+        mkeep, mptrs = self._maps_arg(m, maps)
+        fkeep, fptrs = self._fields_arg(m, fields, step)
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        out, img = self._out_image(m)
+        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
+        self._check(self._lib.stk_mesh_local_weighted_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                            None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
+                                                            int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), rec,
+                                                            C.cast(mptrs, C.c_void_p), float(floor), int(power),
+                                                            C.cast(fptrs, C.c_void_p), int(step), C.byref(img), cptr))
+        return (out, cov) if return_coverage else out
+
+    def ecc_match_local_aligned(self, files, params: EccMatchParameters, mesh: Optional["MeshParameters"] = None,
+                                local: Optional["LocalParameters"] = None, scale_down_width: Optional[float] = None,
+                                return_stats: bool = False):
+        """ecc_match with local alignment (stk_ecc_match_local_aligned): every frame is folded through its ECC warp and the
+        displacement field measured on top of it. local = None: the plain mean; else the local-sharpness weighted fold."""
+        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        stats = (_ffi.FrameStats * m.n)()
+        p, mp = params._c(), (mesh or MeshParameters())._c()
+        lp = None if local is None else local._c()
+        self._check(self._lib.stk_ecc_match_local_aligned(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                          C.byref(mp), None if lp is None else C.byref(lp), C.byref(img), stats))
+        return (out, self._stats_list(stats, m.n)) if return_stats else out
+
+    def keypoint_match_local_aligned(self, files, params: KeyPointMatchParameters, mesh: Optional["MeshParameters"] = None,
+                                     local: Optional["LocalParameters"] = None, scale_down_width: Optional[float] = None,
+                                     return_stats: bool = False):
+        """keypoint_match with local alignment (stk_keypoint_match_local_aligned): (dropped, image[, stats])."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p, mp = params._c(), (mesh or MeshParameters())._c()
+        lp = None if local is None else local._c()
+        self._check(self._lib.stk_keypoint_match_local_aligned(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                               C.byref(mp), None if lp is None else C.byref(lp), C.byref(img),
+                                                               C.byref(dropped), stats))
+        return (dropped.value, out) + ((self._stats_list(stats, m.n),) if return_stats else ())
 
     # -- normalised, coverage-aware rejection combines (extension beyond the reference) -----------------
     def _pixel_counts_image(self, m: _Marshalled):

@@ -221,6 +221,12 @@ struct ClipArgs {
     size_t map_stride;
     float floor;
     int power;
+    // the generic kernel's mesh variant (Mesh<State>, warp_body.h; kernels_mesh.hip; definition: include/stacker.h, "Mesh
+    // fold"): fields[i] = the node field of table entry i (mesh_gh x mesh_gw x 2 f32, dx and dy interleaved; null = the
+    // entry is not displaced), node spacing 1 << mesh_shift destination pixels, mesh_inv = 1.0f / spacing
+    const float* const* fields;
+    int mesh_shift, mesh_gw, mesh_gh;
+    float mesh_inv;
 };
 
 // quantile combines: samples per pixel the selection kernel takes (64 lanes of a wave x 64 keys in registers)
@@ -281,6 +287,29 @@ hipError_t launch_local_fold(const WarpArgs& a, const ClipArgs& c, int depth, hi
 int local_map_tiles(int w, int h);
 hipError_t launch_local_maps(const void* const* frames_dev, float* const* maps_dev, int n, int cn, int w, int h, size_t stride_bytes,
                              int radius, int threshold, hipStream_t s);
+// local alignment (kernels_mesh.hip; definition: include/stacker.h, stk_mesh_params). Entry 0 of `frames` is frame 0 (its
+// matrix is not read); entries 1 .. n_entries - 1 are the frames that get a field: fields[k] (gh x gw x 2 f32) and status[k]
+// (gh x gw int32; the array or an entry may be null) are indexed like the table
+struct MeshLkArgs {
+    const WarpFrame* frames;
+    float* const* fields;
+    int* const* status;
+    int n_entries;
+    int w, h;                    // the frames' size = the destination's
+    size_t stride;               // bytes per frame row
+    int is_affine;
+    int step, gw, gh, radius, max_iters;
+    double eps2, max_shift2, min_eig4;   // epsilon^2, max_shift^2, 4 min_eig
+};
+hipError_t launch_mesh_lk(const MeshLkArgs& a, int cn, hipStream_t s);
+// `passes` hole-filling passes over the fields of entries 1 .. n_entries - 1; scratch: (n_entries - 1) x
+// mesh_fill_scratch_bytes(gw, gh) bytes of device memory
+size_t mesh_fill_scratch_bytes(int gw, int gh);
+hipError_t launch_mesh_fill(float* const* fields, const int* const* status, int n_entries, int gw, int gh, int passes, void* scratch,
+                            hipStream_t s);
+// the mesh folds over the frames of `a` (c.fields, c.mesh_*): the generic kernel's mesh variant, linear only; local: the
+// local-weighted state (launch_local_fold's fields of c), else the running sums into a.acc
+hipError_t launch_mesh_fold(const WarpArgs& a, const ClipArgs& c, int depth, bool local, hipStream_t s);
 // stepped grid of the moments pass for a dw x dh destination: columns, rows per thread, workgroups in x and y
 struct MomentsPlan { int gw, gh, reps, bx, by; size_t parts() const { return (size_t)bx * by * 4; } };
 MomentsPlan moments_plan(int dw, int dh, int step);

@@ -94,6 +94,7 @@ struct stk_ctx {
     DevBuf coef;                  // normalised rejection combines (robust.cpp): the per-entry gain / offset / weight table
     DevBuf quantile;              // quantile combines (quantile.cpp): a w x h x cn f32 image, then the band of samples
     DevBuf local;                 // per-pixel weights (local.cpp): pointer tables, per-entry table, image, den plane, the entries' map planes
+    DevBuf mesh;                  // local alignment (mesh.cpp): pointer tables, field and status planes, fill scratch, a w x h x cn f32 image
     DevBuf quality;               // whole-stack sharpness (quality.cpp): frame pointers, per-frame records, tile partials
     stk::KeypointWorkspace* kp = nullptr;
     stk::geom::HgWorkspace* hg = nullptr;   // findHomography batch workspace (homography.cpp)
@@ -195,6 +196,34 @@ stk::WarpArgs weighted_warp_args(stk_ctx* ctx, int n_entries, int depth, int w, 
 stk_status weighted_moments(stk_ctx* ctx, int n_entries, int depth, int w, int h, int cn, size_t src_row_bytes, double alpha,
                             int border_mode, const double* border_value, int is_affine, int step, double* host, double* ms);
 void weighted_estimate(const double* m /* cn x 6 */, int cn, int mode, stk_frame_weight* e);
+// the pieces of the local-weighted combine (local.cpp) that the mesh folds (mesh.cpp) are built from
+struct LocalLayout {
+    size_t fptrs, mptrs, coef, image, den, planes, plane, total;     // byte offsets into ctx->local; plane: bytes of one map plane
+};
+LocalLayout local_layout(size_t n_ptrs, int n_entries, int w, int h, int cn, size_t n_planes);
+stk_status local_reserve(stk_ctx* ctx, const LocalLayout& L, size_t n_planes);
+stk_status local_validate(stk_ctx* ctx, const stk_local_params* p);
+stk_status local_check_border(stk_ctx* ctx, int border_mode, const double* border_value);
+stk_status local_maps_enqueue(stk_ctx* ctx, const LocalLayout& L, const std::vector<const void*>& frames, const std::vector<float*>& planes);
+stk_status local_maps_launch(stk_ctx* ctx, const LocalLayout& L, size_t first, size_t n, int cn, int w, int h, size_t rb,
+                             const stk_local_params* p);
+// the field table of a mesh fold, in device memory and indexed like the frame table (null entry: not displaced)
+struct MeshFoldArgs { const float* const* fields; int step, gw, gh; };
+void mesh_fold_clip_args(const MeshFoldArgs& m, stk::ClipArgs& ca);
+stk_status local_fold(stk_ctx* ctx, const LocalLayout& L, const std::vector<stk_frame_weight>& coef, int depth, int w, int h, int cn,
+                      size_t src_row_bytes, double alpha, int is_affine, float floor, int power, stk_image_f32* out, float* den_out,
+                      double* ms, const MeshFoldArgs* mesh = nullptr);
+// stk_local_weighted_stack, and with `fields` (n planes by frame index, in frames->location) stk_mesh_local_weighted_stack
+stk_status local_weighted_stack_impl(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                                     int32_t border_mode, const double* border_value, double alpha, const stk_frame_weight* per_frame,
+                                     const float* const* maps, float floor, int32_t power, const float* const* fields, int32_t step,
+                                     stk_image_f32* out, float* den_out);
+// the checks of a mesh fold's step and of the fold options it runs under (mesh.cpp)
+stk_status mesh_check_fold(stk_ctx* ctx, int step);
+// uploads the fields of the table's entries (host planes into ctx->mesh) and their pointer table; frame 0 gets no field.
+// Synchronises.
+stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const std::vector<int>& entry_frame, const float* const* fields,
+                           int step, MeshFoldArgs* out);
 stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
                           int32_t add_reference, stk_image_f32* sum, int32_t* n_added, stk_frame_stats* stats,
                           const float* seeds, double alpha, bool allow16);

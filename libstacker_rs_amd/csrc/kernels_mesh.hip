@@ -1,0 +1,210 @@
+// kernels_mesh.hip — local alignment (include/stacker.h, stk_mesh_params): the residual displacement of every
+// frame on a grid of nodes, the hole filling of those fields, and the launch of the folds that apply them (the generic
+// kernel's mesh variant, Mesh<State> in warp_body.h).
+//
+// mesh_lk_kernel: one workgroup per node (blockIdx.x) and four table entries (blockIdx.y), one wave per (node, entry).
+//   1. the whole workgroup loads frame 0's patch plus a one-pixel halo into LDS as grey bytes (0 outside the frame: a patch
+//      pixel has 1 <= x <= w - 2, so its four neighbours are inside). T, Tx and Ty come from there, as integers.
+//   2. each wave iterates on its own: its lanes stride over the patch; a live pixel costs the fold's coordinates
+//      (warp_coords.inc.h, the fold's own text), four taps of the entry's frame turned into the integer grey, the fold's
+//      lerp chain and two f64 products. n, Sxx, Sxy, Syy are integers below 2^31 and are summed as such (the f64 sums of
+//      the definition, exactly); bx and by are f64 sums in a fixed order: the lane's pixels in patch order, then the
+//      xor-shuffle tree, after which every lane holds the same bits and solves the 2 x 2 system itself.
+//   3. lane 0 writes d and the status. No atomics, no traffic between waves after the load: a wave leaves when it stops.
+// Every global address is formed from a coordinate that was tested first: the halo load tests (x, y) against the frame,
+// a tap is read only where the pixel is live (0 <= ix, ix + 1 <= w - 1, 0 <= iy, iy + 1 <= h - 1).
+#include "grey.h"
+#include "warp_body.h"
+
+namespace stk {
+
+constexpr int MESH_RMAX = 32;                    // largest radius
+constexpr int MESH_SIDE = 2 * MESH_RMAX + 3;     // patch + halo at the largest radius: 67
+constexpr int MESH_LS = 68;                      // bytes per LDS row
+
+template <int CN>
+__device__ __forceinline__ int mesh_grey_px(const uint8_t* p) {
+    if constexpr (CN == 1) return p[0];
+    else return grey_u8(p[0], p[1], p[2]);
+}
+
+template <int CN>
+__global__ __launch_bounds__(256) void mesh_lk_kernel(MeshLkArgs a) {
+    __shared__ uint8_t g0[MESH_SIDE * MESH_LS];
+    const int node = blockIdx.x;
+    const int nj = node / a.gw, nk = node - nj * a.gw;
+    const int cx = nk * a.step, cy = nj * a.step, R = a.radius;
+    const int ox = cx - R - 1, oy = cy - R - 1, side = 2 * R + 3;
+    {
+        const uint8_t* __restrict__ f0 = static_cast<const uint8_t*>(a.frames[0].src);
+        for (int i = threadIdx.x; i < side * side; i += 256) {
+            const int r = i / side, c = i - r * side;
+            const int x = ox + c, y = oy + r;
+            int v = 0;
+            if ((unsigned)x < (unsigned)a.w && (unsigned)y < (unsigned)a.h) v = mesh_grey_px<CN>(f0 + (size_t)y * a.stride + (size_t)x * CN);
+            g0[r * MESH_LS + c] = (uint8_t)v;
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int e = __builtin_amdgcn_readfirstlane(1 + (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6));     // wave-uniform
+    if (e >= a.n_entries) return;
+    const WarpFrame* fr = a.frames + e;
+    const uint8_t* __restrict__ src = static_cast<const uint8_t*>(fr->src);
+    const int xa = max(cx - R, 1), xb = min(cx + R, a.w - 2), ya = max(cy - R, 1), yb = min(cy + R, a.h - 2);
+    const int pw = xb - xa + 1, ph = yb - ya + 1;
+    float dx = 0.0f, dy = 0.0f;
+    int status = -1;                                 // an empty patch
+    if (pw > 0 && ph > 0) {
+        const int np = pw * ph;
+        for (int it = 1;; it++) {
+            int n = 0, sxx = 0, sxy = 0, syy = 0;
+            double bx = 0.0, by = 0.0;
+            for (int q = lane; q < np; q += 64) {
+                const int yy = q / pw, xx = q - yy * pw;
+                const int px = xa + xx, py = ya + yy;
+                const float fx = (float)px + dx, fy = (float)py + dy;
+#define STK_SUBPIX 0
+#include "warp_coords.inc.h"
+#undef STK_SUBPIX
+                (void)w00; (void)w01; (void)w10; (void)w11;
+                const bool live = finite && ix >= 0 && ix + 1 <= a.w - 1 && iy >= 0 && iy + 1 <= a.h - 1;
+                if (live) {
+                    const uint8_t* r0 = src + (size_t)iy * a.stride + (size_t)ix * CN;
+                    const uint8_t* r1 = r0 + a.stride;
+                    const float p00 = (float)mesh_grey_px<CN>(r0), p01 = (float)mesh_grey_px<CN>(r0 + CN);
+                    const float p10 = (float)mesh_grey_px<CN>(r1), p11 = (float)mesh_grey_px<CN>(r1 + CN);
+                    const float t0 = __builtin_fmaf(ax, p01 - p00, p00);
+                    const float t1 = __builtin_fmaf(ax, p11 - p10, p10);
+                    const float I = __builtin_fmaf(ay, t1 - t0, t0);
+                    const uint8_t* t = &g0[(py - oy) * MESH_LS + (px - ox)];
+                    const int tx = (int)t[1] - (int)t[-1], ty = (int)t[MESH_LS] - (int)t[-MESH_LS];
+                    const float err = I - (float)(int)t[0];
+                    n += 1; sxx += tx * tx; sxy += tx * ty; syy += ty * ty;
+                    bx = bx + (double)tx * (double)err;
+                    by = by + (double)ty * (double)err;
+                }
+            }
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {
+                n += __shfl_xor(n, m, 64); sxx += __shfl_xor(sxx, m, 64); sxy += __shfl_xor(sxy, m, 64); syy += __shfl_xor(syy, m, 64);
+                bx = bx + __shfl_xor(bx, m, 64);
+                by = by + __shfl_xor(by, m, 64);
+            }
+            if (2 * n < np) { status = -2; break; }
+            const double N = (double)n, Sxx = (double)sxx, Sxy = (double)sxy, Syy = (double)syy;
+            const double dif = Sxx - Syy;
+            const double lam = 0.5 * ((Sxx + Syy) - __builtin_sqrt(dif * dif + 4.0 * (Sxy * Sxy)));
+            const double det = Sxx * Syy - Sxy * Sxy;
+            if (det <= 0.0 || lam < a.min_eig4 * N) { status = -3; break; }
+            const double ddx = 2.0 * (Syy * bx - Sxy * by) / det;
+            const double ddy = 2.0 * (Sxx * by - Sxy * bx) / det;
+            dx = (float)((double)dx - ddx);
+            dy = (float)((double)dy - ddy);
+            if (!((double)dx * (double)dx + (double)dy * (double)dy <= a.max_shift2)) { status = -4; break; }
+            status = it;
+            if (ddx * ddx + ddy * ddy < a.eps2 || it >= a.max_iters) break;
+        }
+    }
+    if (status < 0) { dx = 0.0f; dy = 0.0f; }
+    if (lane == 0) {
+        float* __restrict__ D = a.fields[e];
+        D[(size_t)node * 2] = dx; D[(size_t)node * 2 + 1] = dy;
+        if (a.status && a.status[e]) a.status[e][node] = status;
+    }
+}
+
+hipError_t launch_mesh_lk(const MeshLkArgs& a, int cn, hipStream_t s) {
+    if (a.n_entries < 2 || a.radius < 2 || a.radius > MESH_RMAX || a.gw <= 0 || a.gh <= 0 || (size_t)a.gw * a.gh > 0x7fffffffu ||
+        (a.n_entries + 2) / 4 > 65535)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(a.gw * a.gh), (unsigned)((a.n_entries - 1 + 3) / 4));
+    if (cn == 1) mesh_lk_kernel<1><<<grid, 256, 0, s>>>(a);
+    else if (cn == 3) mesh_lk_kernel<3><<<grid, 256, 0, s>>>(a);
+    else if (cn == 4) mesh_lk_kernel<4><<<grid, 256, 0, s>>>(a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// Hole filling: one workgroup per field (blockIdx.x + 1 = the table entry). Jacobi passes between the field itself and a
+// scratch copy, the validity alongside as bytes; the workgroup's barrier orders a pass's writes before the next pass's
+// reads. A node that is valid is copied; a hole takes the [1 2 1]^T [1 2 1] mean of its valid in-grid neighbours, row-major.
+size_t mesh_fill_scratch_bytes(int gw, int gh) { return ((size_t)gw * gh * (2 * sizeof(float) + 2) + 255) & ~(size_t)255; }
+
+__global__ __launch_bounds__(256) void mesh_fill_kernel(float* const* fields, const int* const* status, int gw, int gh, int passes,
+                                                        char* scratch, size_t scratch_stride) {
+    const int e = 1 + blockIdx.x, nn = gw * gh;
+    float* A = fields[e];
+    const int* __restrict__ st = status[e];
+    float* B = reinterpret_cast<float*>(scratch + (size_t)blockIdx.x * scratch_stride);
+    uint8_t* ms = reinterpret_cast<uint8_t*>(B + (size_t)nn * 2);
+    uint8_t* md = ms + nn;
+    for (int i = threadIdx.x; i < nn; i += 256) ms[i] = st[i] > 0 ? 1 : 0;
+    __syncthreads();
+    float* src = A;
+    float* dst = B;
+    for (int p = 0; p < passes; p++) {
+        for (int i = threadIdx.x; i < nn; i += 256) {
+            float d0 = src[2 * i], d1 = src[2 * i + 1];
+            uint8_t m = ms[i];
+            if (!m) {
+                const int j = i / gw, k = i - j * gw;
+                float den = 0.0f, n0 = 0.0f, n1 = 0.0f;
+                for (int dj = -1; dj <= 1; dj++)
+                    for (int dk = -1; dk <= 1; dk++) {
+                        const int jj = j + dj, kk = k + dk;
+                        if ((unsigned)jj >= (unsigned)gh || (unsigned)kk >= (unsigned)gw) continue;
+                        const int q = jj * gw + kk;
+                        if (!ms[q]) continue;
+                        const float wgt = (float)((2 - (dj < 0 ? -dj : dj)) * (2 - (dk < 0 ? -dk : dk)));
+                        den = den + wgt;
+                        n0 = n0 + wgt * src[2 * q];
+                        n1 = n1 + wgt * src[2 * q + 1];
+                    }
+                if (den > 0.0f) { d0 = n0 / den; d1 = n1 / den; m = 1; }
+            }
+            dst[2 * i] = d0; dst[2 * i + 1] = d1; md[i] = m;
+        }
+        __syncthreads();
+        float* t = src; src = dst; dst = t;
+        uint8_t* u = ms; ms = md; md = u;
+    }
+    if (src != A)
+        for (int i = threadIdx.x; i < 2 * nn; i += 256) A[i] = src[i];
+}
+
+hipError_t launch_mesh_fill(float* const* fields, const int* const* status, int n_entries, int gw, int gh, int passes, void* scratch,
+                            hipStream_t s) {
+    if (n_entries < 2 || passes <= 0) return hipSuccess;
+    if (!fields || !status || !scratch || gw <= 0 || gh <= 0) return hipErrorInvalidValue;
+    mesh_fill_kernel<<<(unsigned)(n_entries - 1), 256, 0, s>>>(fields, status, gw, gh, passes, static_cast<char*>(scratch),
+                                                                mesh_fill_scratch_bytes(gw, gh));
+    return hipGetLastError();
+}
+
+// The mesh folds: the generic kernel only (the u8 BGR fast kernels and the bicubic kernels do not serve them).
+hipError_t launch_mesh_fold(const WarpArgs& a, const ClipArgs& c, int depth, bool local, hipStream_t s) {
+    if (a.n_frames <= 0 || !c.fields || c.mesh_gw <= 0 || c.mesh_gh <= 0 || a.interp != STK_INTER_LINEAR || a.subpixel_bits != 0)
+        return hipErrorInvalidValue;
+    if (local ? (!c.maps || c.power < 1 || c.power > 4) : !a.acc) return hipErrorInvalidValue;
+    const dim3 grid((a.dw + 63) / 64, (a.dh + 3) / 4);
+#define STK_MESH_CASE(T, CN)                                                                             \
+    do {                                                                                                 \
+        if (local) warp_accumulate_kernel<T, CN, true, Mesh<FoldLocal<CN>>><<<grid, 256, 0, s>>>(a, c);  \
+        else warp_accumulate_kernel<T, CN, false, Mesh<NoClip>><<<grid, 256, 0, s>>>(a, c);              \
+    } while (0)
+    if (depth == 8 && a.cn == 3) STK_MESH_CASE(uint8_t, 3);
+    else if (depth == 8 && a.cn == 1) STK_MESH_CASE(uint8_t, 1);
+    else if (depth == 8 && a.cn == 4) STK_MESH_CASE(uint8_t, 4);
+    else if (depth == 16 && a.cn == 3) STK_MESH_CASE(uint16_t, 3);
+    else if (depth == 16 && a.cn == 1) STK_MESH_CASE(uint16_t, 1);
+    else if (depth == 16 && a.cn == 4) STK_MESH_CASE(uint16_t, 4);
+    else if (depth == 32 && a.cn == 3) STK_MESH_CASE(float, 3);
+    else if (depth == 32 && a.cn == 1) STK_MESH_CASE(float, 1);
+    else if (depth == 32 && a.cn == 4) STK_MESH_CASE(float, 4);
+    else return hipErrorInvalidValue;
+#undef STK_MESH_CASE
+    return hipGetLastError();
+}
+
+}  // namespace stk

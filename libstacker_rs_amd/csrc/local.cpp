@@ -15,12 +15,7 @@
 
 using namespace stk;
 
-namespace {
-
-struct LocalLayout {
-    size_t fptrs, mptrs, coef, image, den, planes, plane, total;     // byte offsets; plane: bytes of one map plane
-};
-
+// (the layout, the checks, the map pass and the fold are shared with mesh.cpp: context.h)
 // cn == 0: the map pass alone (no per-entry table, image or den plane)
 LocalLayout local_layout(size_t n_ptrs, int n_entries, int w, int h, int cn, size_t n_planes) {
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -55,6 +50,8 @@ stk_status local_validate(stk_ctx* ctx, const stk_local_params* p) {
     return STK_OK;
 }
 
+namespace {
+
 stk_status local_check_depth(stk_ctx* ctx, const stk_frames* f) {
     if (f->depth != 8)
         return fail(ctx, STK_NOT_IMPLEMENTED,
@@ -62,6 +59,8 @@ stk_status local_check_depth(stk_ctx* ctx, const stk_frames* f) {
                     "integers below 2^24");
     return STK_OK;
 }
+
+}  // namespace
 
 // a weight taken outside a frame means nothing: the fold runs under BORDER_CONSTANT with border value 0
 stk_status local_check_border(stk_ctx* ctx, int border_mode, const double* border_value) {
@@ -97,9 +96,10 @@ stk_status local_maps_launch(stk_ctx* ctx, const LocalLayout& L, size_t first, s
 
 // The local-weighted fold over the n_entries entries of ctx->warpframes with the per-entry records `coef` and the plane
 // table at L.mptrs (uploaded by the caller). Writes `out` and `den_out` (out's location); adds its device time to *ms.
+// mesh: the generic kernel's mesh variant with that field table (mesh.cpp).
 stk_status local_fold(stk_ctx* ctx, const LocalLayout& L, const std::vector<stk_frame_weight>& coef, int depth, int w, int h, int cn,
                       size_t src_row_bytes, double alpha, int is_affine, float floor, int power, stk_image_f32* out, float* den_out,
-                      double* ms) {
+                      double* ms, const MeshFoldArgs* mesh) {
     char* base = ctx->local.as<char>();
     const bool host = out->location != STK_DEVICE;
     const WarpArgs a = weighted_warp_args(ctx, (int)coef.size(), depth, w, h, cn, src_row_bytes, alpha, STK_BORDER_CONSTANT, nullptr, is_affine);
@@ -116,7 +116,10 @@ stk_status local_fold(stk_ctx* ctx, const LocalLayout& L, const std::vector<stk_
     ca.power = power;
     HIP_TRY(hipMemcpyAsync(base + L.coef, coef.data(), coef.size() * sizeof(stk_frame_weight), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
-    HIP_TRY(launch_local_fold(a, ca, depth, ctx->stream));
+    if (mesh) {
+        mesh_fold_clip_args(*mesh, ca);
+        HIP_TRY(launch_mesh_fold(a, ca, depth, true, ctx->stream));
+    } else HIP_TRY(launch_local_fold(a, ca, depth, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
     if (host) {
         HIP_TRY(hipMemcpyAsync(out->data, ca.out, (size_t)w * h * cn * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -126,6 +129,8 @@ stk_status local_fold(stk_ctx* ctx, const LocalLayout& L, const std::vector<stk_
     if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
     return STK_OK;
 }
+
+namespace {
 
 // the checks the two whole-stack forms share, in the order the errors are reported
 stk_status local_match_check(stk_ctx* ctx, const stk_frames* frames, const stk_weight_params* weight, const stk_local_params* local,
@@ -235,10 +240,21 @@ stk_status stk_local_sharpness(stk_ctx* ctx, const stk_frames* frames, const stk
 stk_status stk_local_weighted_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
                                     int32_t border_mode, const double* border_value, double alpha, const stk_frame_weight* per_frame,
                                     const float* const* maps, float floor, int32_t power, stk_image_f32* out, float* den_out) {
+    return local_weighted_stack_impl(ctx, frames, M, include, is_affine, border_mode, border_value, alpha, per_frame, maps, floor, power,
+                                     nullptr, 0, out, den_out);
+}
+
+}  // extern "C"
+
+stk_status local_weighted_stack_impl(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                                     int32_t border_mode, const double* border_value, double alpha, const stk_frame_weight* per_frame,
+                                     const float* const* maps, float floor, int32_t power, const float* const* fields, int32_t step,
+                                     stk_image_f32* out, float* den_out) {
     stk_status st = check_frames(ctx, frames, false);
     if (st) return st;
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
     if (!maps) return fail(ctx, STK_INVALID_PARAMS, "null maps");
+    if (fields && (st = mesh_check_fold(ctx, step))) return st;
     if ((st = local_check_border(ctx, border_mode, border_value))) return st;
     if (power < 1 || power > 4) return fail(ctx, STK_INVALID_PARAMS, "local: power must be 1 .. 4");
     if (!std::isfinite(floor) || floor < 0.0f) return fail(ctx, STK_INVALID_PARAMS, "local: floor must be finite and >= 0");
@@ -248,6 +264,7 @@ stk_status stk_local_weighted_stack(stk_ctx* ctx, const stk_frames* frames, cons
     for (int i = 0; i < n; i++) {
         if (include && !include[i]) continue;
         if (!maps[i]) return fail(ctx, STK_INVALID_PARAMS, "null map plane of an included frame");
+        if (fields && i > 0 && !fields[i]) return fail(ctx, STK_INVALID_PARAMS, "null field plane of an included frame");
         stk_frame_weight e;
         if (per_frame) e = per_frame[i];
         else { weighted_estimate(nullptr, cn, 0, &e); e.weight = 1.0f; }
@@ -272,12 +289,17 @@ stk_status stk_local_weighted_stack(stk_ctx* ctx, const stk_frames* frames, cons
     }
     HIP_TRY(hipMemcpyAsync(base + L.mptrs, mptr.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
     double ms = 0.0;
+    MeshFoldArgs mf{};
+    if (fields && (st = mesh_fold_table(ctx, frames, entry_frame, fields, step, &mf))) return st;
     // (local_fold synchronises: `mptr` outlives the copy)
-    if ((st = local_fold(ctx, L, coef, frames->depth, w, h, cn, frame_row_bytes(frames), alpha, is_affine, floor, power, out, den_out, &ms)))
+    if ((st = local_fold(ctx, L, coef, frames->depth, w, h, cn, frame_row_bytes(frames), alpha, is_affine, floor, power, out, den_out, &ms,
+                         fields ? &mf : nullptr)))
         return st;
     ctx->timing.finalize_ms = ms;
     return STK_OK;
 }
+
+extern "C" {
 
 stk_status stk_ecc_match_local_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
                                         const stk_weight_params* weight, const float* weights, const stk_local_params* local,

@@ -1,0 +1,443 @@
+// mesh.cpp — local alignment: stk_mesh_grid, stk_local_align, stk_mesh_stack, stk_mesh_local_weighted_stack,
+// stk_ecc_match_local_aligned, stk_keypoint_match_local_aligned (an extension beyond the reference; definition in
+// include/stacker.h, stk_mesh_params; kernels in kernels_mesh.hip and warp_body.h).
+// ctx->mesh (grow-only like the other workspaces) holds three pointer tables indexed like the frame table (the fold's
+// fields, the field pass's fields and status planes), the field and status planes the caller does not hold on the device,
+// the fill pass's scratch and a w x h x cn f32 image (the plain call's mean in the whole-stack forms, then a host output's
+// staging copy). The frame table, the checks of the caller-held-warps forms and the local-weighted fold are the weighted
+// and the local combine's (weighted.cpp, local.cpp, through context.h). Like those, the whole-stack forms run the plain
+// call first and take the warps and the kept set from its stats; the frames are still resident in HBM, full size.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "context.h"
+
+using namespace stk;
+
+namespace {
+
+struct MeshLayout {
+    size_t tptrs, fptrs, sptrs, fields, status, scratch, image, fplane, splane, cplane, total;   // byte offsets; *plane: bytes of one plane
+};
+
+MeshLayout mesh_layout(size_t n_ptrs, size_t n_fields, size_t n_status, size_t n_scratch, int gw, int gh, size_t image_floats) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t nn = (size_t)gw * gh, pt = up(std::max<size_t>(n_ptrs, 1) * sizeof(void*));
+    MeshLayout L{};
+    L.fplane = up(nn * 2 * sizeof(float));
+    L.splane = up(nn * sizeof(int32_t));
+    L.cplane = mesh_fill_scratch_bytes(gw, gh);
+    L.tptrs = 0;
+    L.fptrs = pt;
+    L.sptrs = 2 * pt;
+    L.fields = 3 * pt;
+    L.status = L.fields + n_fields * L.fplane;
+    L.scratch = L.status + n_status * L.splane;
+    L.image = L.scratch + n_scratch * L.cplane;
+    L.total = L.image + up(image_floats * sizeof(float));
+    return L;
+}
+
+stk_status mesh_reserve(stk_ctx* ctx, const MeshLayout& L) {
+    if (ctx->mesh.reserve(L.total) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, STK_HIP_ERROR, "mesh: device allocation of " + std::to_string(L.total) + " bytes failed (field planes of " +
+                                            std::to_string(L.fplane) + " bytes)");
+    }
+    return STK_OK;
+}
+
+bool mesh_step_ok(int step) { return step >= 8 && step <= 256 && (step & (step - 1)) == 0; }
+void mesh_grid_of(int w, int h, int step, int* gw, int* gh) {
+    *gw = (w - 1 + step - 1) / step + 1;
+    *gh = (h - 1 + step - 1) / step + 1;
+}
+
+stk_status mesh_validate(stk_ctx* ctx, const stk_mesh_params* p) {
+    if (!p) return fail(ctx, STK_INVALID_PARAMS, "null mesh parameters");
+    if (!mesh_step_ok(p->step)) return fail(ctx, STK_INVALID_PARAMS, "mesh: step must be 8, 16, 32, 64, 128 or 256");
+    if (p->radius < 2 || p->radius > 32) return fail(ctx, STK_INVALID_PARAMS, "mesh: radius must be 2 .. 32");
+    if (p->max_iters < 1 || p->max_iters > 32) return fail(ctx, STK_INVALID_PARAMS, "mesh: max_iters must be 1 .. 32");
+    if (!std::isfinite(p->epsilon) || p->epsilon < 0.0f) return fail(ctx, STK_INVALID_PARAMS, "mesh: epsilon must be finite and >= 0");
+    if (!std::isfinite(p->max_shift) || !(p->max_shift > 0.0f) || p->max_shift > 64.0f)
+        return fail(ctx, STK_INVALID_PARAMS, "mesh: max_shift must be finite, > 0 and <= 64");
+    if (!std::isfinite(p->min_eig) || p->min_eig < 0.0f) return fail(ctx, STK_INVALID_PARAMS, "mesh: min_eig must be finite and >= 0");
+    if (p->fill < 0 || p->fill > 16) return fail(ctx, STK_INVALID_PARAMS, "mesh: fill must be 0 .. 16");
+    if (p->reserved != 0) return fail(ctx, STK_INVALID_PARAMS, "mesh parameters: reserved must be 0");
+    return STK_OK;
+}
+
+stk_status mesh_check_depth(stk_ctx* ctx, const stk_frames* f) {
+    if (f->depth != 8)
+        return fail(ctx, STK_NOT_IMPLEMENTED,
+                    "local alignment takes 8-bit frames: the displacement is estimated on the 8-bit integer grey, its gradients are exact integers");
+    return STK_OK;
+}
+
+// The field pass over entries 1 .. ne - 1 of ctx->warpframes (entry 0 = frame 0; the table is uploaded): fdev[k] / sdev[k]
+// are the device planes of entry k (sdev[k] never null; index 0 unused). Tables at L.fptrs / L.sptrs, fill scratch at
+// L.scratch (ne - 1 planes). Synchronises; adds the device time of the two kernels to *ms.
+stk_status mesh_align_entries(stk_ctx* ctx, const MeshLayout& L, int ne, int w, int h, int cn, size_t rb, int is_affine,
+                              const stk_mesh_params* p, int gw, int gh, const std::vector<float*>& fdev, const std::vector<int32_t*>& sdev,
+                              double* ms) {
+    if (ne < 2) return STK_OK;
+    char* base = ctx->mesh.as<char>();
+    HIP_TRY(hipMemcpyAsync(base + L.fptrs, fdev.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base + L.sptrs, sdev.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    MeshLkArgs a{};
+    a.frames = ctx->warpframes.as<WarpFrame>();
+    a.fields = (float* const*)(base + L.fptrs);
+    a.status = (int* const*)(base + L.sptrs);
+    a.n_entries = ne;
+    a.w = w; a.h = h; a.stride = rb; a.is_affine = is_affine;
+    a.step = p->step; a.gw = gw; a.gh = gh; a.radius = p->radius; a.max_iters = p->max_iters;
+    a.eps2 = (double)p->epsilon * (double)p->epsilon;
+    a.max_shift2 = (double)p->max_shift * (double)p->max_shift;
+    a.min_eig4 = 4.0 * (double)p->min_eig;
+    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    HIP_TRY(launch_mesh_lk(a, cn, ctx->stream));
+    if (p->fill > 0)
+        HIP_TRY(launch_mesh_fill(a.fields, (const int* const*)a.status, ne, gw, gh, p->fill, base + L.scratch, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // the pointer vectors leave scope
+    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
+    return STK_OK;
+}
+
+// The mesh mean fold over the ne entries of ctx->warpframes with the field table `mf`: sums in fold order, then x
+// (float)(1.0 / ne). `image`: a w x h x cn f32 device buffer for a host output. Synchronises; adds its device time to *ms.
+stk_status mesh_mean_fold(stk_ctx* ctx, int ne, int depth, int w, int h, int cn, size_t rb, double alpha, int border_mode,
+                          const double* border_value, int is_affine, const MeshFoldArgs& mf, float* image, stk_image_f32* out, double* ms) {
+    const bool host = out->location != STK_DEVICE;
+    const size_t nel = (size_t)w * h * cn;
+    WarpArgs a = weighted_warp_args(ctx, ne, depth, w, h, cn, rb, alpha, border_mode, border_value, is_affine);
+    a.acc = host ? image : out->data;
+    a.acc_stride = (size_t)w * cn;
+    a.accumulate = 0;
+    ClipArgs ca{};
+    mesh_fold_clip_args(mf, ca);
+    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    HIP_TRY(launch_mesh_fold(a, ca, depth, false, ctx->stream));
+    HIP_TRY(launch_scale(a.acc, a.acc, nel, (float)(1.0 / (double)ne), ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+    if (host) HIP_TRY(hipMemcpyAsync(out->data, a.acc, nel * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
+    return STK_OK;
+}
+
+// the checks the two whole-stack forms share, in the order the errors are reported
+stk_status mesh_match_check(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mesh, const stk_local_params* local,
+                            const stk_image_f32* out) {
+    stk_status st = mesh_validate(ctx, mesh);
+    if (st) return st;
+    if (local && (st = local_validate(ctx, local))) return st;
+    if ((st = check_frames(ctx, frames, true))) return st;
+    if ((st = mesh_check_fold(ctx, mesh->step))) return st;
+    if ((st = mesh_check_depth(ctx, frames))) return st;
+    return weighted_check_out(ctx, out, frames);
+}
+
+// the tail of the whole-stack forms: `entry_frame[k]` is the frame index of table entry k (entry 0 = frame 0), `dev` the
+// resident full-size frames by frame index; the frame table is uploaded. Field pass, then the mesh mean fold, or the map
+// pass and the mesh local-weighted fold with unit records.
+stk_status mesh_finish(stk_ctx* ctx, const MeshLayout& L, const stk_frames* frames, const std::vector<int>& entry_frame,
+                       const std::vector<const void*>& dev, size_t rb, int is_affine, int border_mode, const double* border_value,
+                       const stk_mesh_params* mp, const stk_local_params* lp, stk_image_f32* out) {
+    const int w = frames->width, h = frames->height, cn = frames->channels;
+    const int ne = (int)entry_frame.size();
+    const double alpha = 1.0 / 255.0;
+    int gw, gh;
+    mesh_grid_of(w, h, mp->step, &gw, &gh);
+    char* base = ctx->mesh.as<char>();
+    double ms = 0.0;
+    std::vector<float*> fdev(ne, nullptr);
+    std::vector<int32_t*> sdev(ne, nullptr);
+    for (int k = 1; k < ne; k++) {
+        fdev[k] = (float*)(base + L.fields + (size_t)(k - 1) * L.fplane);
+        sdev[k] = (int32_t*)(base + L.status + (size_t)(k - 1) * L.splane);
+    }
+    stk_status st = mesh_align_entries(ctx, L, ne, w, h, cn, rb, is_affine, mp, gw, gh, fdev, sdev, &ms);
+    if (st) return st;
+    HIP_TRY(hipMemcpyAsync(base + L.tptrs, fdev.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    const MeshFoldArgs mf{(const float* const*)(base + L.tptrs), mp->step, gw, gh};
+    if (!lp) {
+        // (mesh_mean_fold synchronises: `fdev` outlives the copy)
+        st = mesh_mean_fold(ctx, ne, 8, w, h, cn, rb, alpha, border_mode, border_value, is_affine, mf, (float*)(base + L.image), out, &ms);
+    } else {
+        const LocalLayout LL = local_layout((size_t)ne, ne, w, h, cn, (size_t)ne);
+        char* lbase = ctx->local.as<char>();
+        std::vector<const void*> fptr(ne);
+        std::vector<float*> mptr(ne);
+        for (int k = 0; k < ne; k++) { fptr[k] = dev[entry_frame[k]]; mptr[k] = (float*)(lbase + LL.planes + (size_t)k * LL.plane); }
+        if ((st = local_maps_enqueue(ctx, LL, fptr, mptr))) return st;
+        HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+        if ((st = local_maps_launch(ctx, LL, 0, (size_t)ne, cn, w, h, rb, lp))) return st;
+        HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        ms += ev_ms(ctx->ev[4], ctx->ev[5]);
+        std::vector<stk_frame_weight> coef(ne);
+        for (stk_frame_weight& e : coef) { weighted_estimate(nullptr, cn, 0, &e); e.weight = 1.0f; }
+        st = local_fold(ctx, LL, coef, 8, w, h, cn, rb, alpha, is_affine, lp->floor, lp->power, out, nullptr, &ms, &mf);
+    }
+    if (st) return st;
+    ctx->timing.finalize_ms = ms;
+    return STK_OK;
+}
+
+// the workspaces of a whole-stack form over n frames, reserved before the plain call writes its mean into ctx->mesh
+stk_status mesh_match_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mp, const stk_local_params* lp, MeshLayout* L) {
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    int gw, gh;
+    mesh_grid_of(w, h, mp->step, &gw, &gh);
+    *L = mesh_layout((size_t)n, (size_t)n, (size_t)n, (size_t)n, gw, gh, (size_t)w * h * cn);
+    stk_status st = mesh_reserve(ctx, *L);
+    if (st) return st;
+    if (lp) {
+        const LocalLayout LL = local_layout((size_t)n, n, w, h, cn, (size_t)n);
+        if ((st = local_reserve(ctx, LL, (size_t)n))) return st;
+    }
+    return STK_OK;
+}
+
+}  // namespace
+
+void mesh_fold_clip_args(const MeshFoldArgs& m, ClipArgs& ca) {
+    ca.fields = m.fields;
+    ca.mesh_shift = 0;
+    while ((1 << ca.mesh_shift) < m.step) ca.mesh_shift++;
+    ca.mesh_gw = m.gw; ca.mesh_gh = m.gh;
+    ca.mesh_inv = 1.0f / (float)m.step;
+}
+
+stk_status mesh_check_fold(stk_ctx* ctx, int step) {
+    if (!mesh_step_ok(step)) return fail(ctx, STK_INVALID_PARAMS, "mesh: step must be 8, 16, 32, 64, 128 or 256");
+    if (ctx->opt_subpixel_bits != 0)
+        return fail(ctx, STK_INVALID_PARAMS, "mesh: the displaced coordinates are exact ones: warp_subpixel_bits must be 0");
+    if (ctx->opt_interp == STK_INTER_CUBIC)
+        return fail(ctx, STK_NOT_IMPLEMENTED, "mesh: the mesh folds are bilinear; warp_interpolation = 2 (STK_INTER_CUBIC) is not implemented for them");
+    return STK_OK;
+}
+
+stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const std::vector<int>& entry_frame, const float* const* fields,
+                           int step, MeshFoldArgs* out) {
+    const int ne = (int)entry_frame.size();
+    const bool host = frames->location != STK_DEVICE;
+    int gw, gh;
+    mesh_grid_of(frames->width, frames->height, step, &gw, &gh);
+    const MeshLayout L = mesh_layout((size_t)ne, host ? (size_t)ne : 0, 0, 0, gw, gh, (size_t)frames->width * frames->height * frames->channels);
+    stk_status st = mesh_reserve(ctx, L);
+    if (st) return st;
+    char* base = ctx->mesh.as<char>();
+    std::vector<const float*> ptr(ne, nullptr);
+    for (int k = 0; k < ne; k++) {
+        const int i = entry_frame[k];
+        if (i == 0) continue;                              // frame 0 is the grid's own frame
+        if (host) {
+            float* d = (float*)(base + L.fields + (size_t)k * L.fplane);
+            HIP_TRY(hipMemcpyAsync(d, fields[i], (size_t)gw * gh * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            ptr[k] = d;
+        } else ptr[k] = fields[i];
+    }
+    HIP_TRY(hipMemcpyAsync(base + L.tptrs, ptr.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // `ptr` leaves scope
+    *out = MeshFoldArgs{(const float* const*)(base + L.tptrs), step, gw, gh};
+    return STK_OK;
+}
+
+extern "C" {
+
+stk_status stk_mesh_grid(int32_t width, int32_t height, int32_t step, int32_t* gw, int32_t* gh) {
+    if (width <= 0 || height <= 0 || !mesh_step_ok(step) || !gw || !gh) return STK_INVALID_PARAMS;
+    mesh_grid_of(width, height, step, gw, gh);
+    return STK_OK;
+}
+
+stk_status stk_local_align(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                           const stk_mesh_params* p, float* const* fields, int32_t* const* status) {
+    stk_status st = check_frames(ctx, frames, false, false);
+    if (st) return st;
+    if ((st = mesh_validate(ctx, p))) return st;
+    if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
+    if (!fields) return fail(ctx, STK_INVALID_PARAMS, "null fields");
+    if ((st = mesh_check_depth(ctx, frames))) return st;
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    std::vector<int> moving;
+    for (int i = 1; i < n; i++) {
+        if (include && !include[i]) continue;
+        if (!fields[i]) return fail(ctx, STK_INVALID_PARAMS, "null field plane of an included frame");
+        moving.push_back(i);
+    }
+    (void)hipSetDevice(ctx->device);
+    timing_begin(ctx);
+    if (moving.empty()) return STK_OK;
+    int gw, gh;
+    mesh_grid_of(w, h, p->step, &gw, &gh);
+    const size_t nn = (size_t)gw * gh, rb = frame_row_bytes(frames), fb = rb * h;
+    const bool host = frames->location == STK_HOST;
+    // host frames go through the frame workspace in batches that fit it (at least "upload_batch" frames, and frame 0 with
+    // one more), as in stk_local_sharpness: frame 0 stays in the first place, a batch's frames follow it
+    int batch = (int)moving.size();
+    if (host) {
+        const size_t budget = std::max<size_t>(ctx->frames.cap, (size_t)ctx->opt_upload_batch * fb);
+        batch = (int)std::min<size_t>(moving.size(), std::max<size_t>(2, budget / fb) - 1);
+        HIP_TRY(ctx->frames.reserve(fb * (size_t)(batch + 1)));
+        HIP_TRY(hipMemcpyAsync(ctx->frames.p, frames->data[0], frame_copy_bytes(frames), hipMemcpyHostToDevice, ctx->stream));
+    }
+    const MeshLayout L = mesh_layout((size_t)batch + 1, host ? (size_t)batch : 0, (size_t)batch, (size_t)batch, gw, gh, 0);
+    if ((st = mesh_reserve(ctx, L))) return st;
+    char* base = ctx->mesh.as<char>();
+    double ms = 0.0;
+    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (size_t b0 = 0; b0 < moving.size(); b0 += (size_t)batch) {
+        const int nb = (int)std::min<size_t>((size_t)batch, moving.size() - b0);
+        std::vector<WarpFrame> wf(nb + 1);
+        std::vector<float*> fdev(nb + 1, nullptr);
+        std::vector<int32_t*> sdev(nb + 1, nullptr);
+        make_warp_frame(wf[0], host ? (const void*)ctx->frames.p : frames->data[0], I3, is_affine);
+        for (int k = 1; k <= nb; k++) {
+            const int i = moving[b0 + k - 1];
+            const void* src = frames->data[i];
+            if (host) {
+                void* d = ctx->frames.as<uint8_t>() + fb * (size_t)k;
+                HIP_TRY(hipMemcpyAsync(d, frames->data[i], frame_copy_bytes(frames), hipMemcpyHostToDevice, ctx->stream));
+                src = d;
+            }
+            make_warp_frame(wf[k], src, M + 9 * (size_t)i, is_affine);
+            fdev[k] = host ? (float*)(base + L.fields + (size_t)(k - 1) * L.fplane) : fields[i];
+            sdev[k] = (!host && status && status[i]) ? status[i] : (int32_t*)(base + L.status + (size_t)(k - 1) * L.splane);
+        }
+        if ((st = warp_table_upload(ctx, wf, rb, w, h, is_affine))) return st;
+        // (mesh_align_entries synchronises: `wf` and the pointer vectors outlive the copies)
+        if ((st = mesh_align_entries(ctx, L, nb + 1, w, h, cn, rb, is_affine, p, gw, gh, fdev, sdev, &ms))) return st;
+        if (host) {
+            for (int k = 1; k <= nb; k++) {
+                const int i = moving[b0 + k - 1];
+                HIP_TRY(hipMemcpyAsync(fields[i], fdev[k], nn * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+                if (status && status[i]) HIP_TRY(hipMemcpyAsync(status[i], sdev[k], nn * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+            }
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    ctx->timing.align_ms = ms;
+    return STK_OK;
+}
+
+stk_status stk_mesh_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                          int32_t border_mode, const double* border_value, double alpha, const float* const* fields, int32_t step,
+                          stk_image_f32* out) {
+    stk_status st = check_frames(ctx, frames, false);
+    if (st) return st;
+    if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
+    if (!fields) return fail(ctx, STK_INVALID_PARAMS, "null fields");
+    if (border_mode < 0 || border_mode > 4)
+        return fail(ctx, border_mode == STK_BORDER_TRANSPARENT ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS,
+                    "border mode not supported (BORDER_TRANSPARENT leaves the reference's output uninitialised)");
+    if ((st = mesh_check_fold(ctx, step))) return st;
+    if ((st = weighted_check_out(ctx, out, frames))) return st;
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    for (int i = 1; i < n; i++)
+        if ((!include || include[i]) && !fields[i]) return fail(ctx, STK_INVALID_PARAMS, "null field plane of an included frame");
+    std::vector<int> entry_frame;
+    if ((st = weighted_table(ctx, frames, M, include, is_affine, entry_frame))) return st;
+    MeshFoldArgs mf{};
+    if ((st = mesh_fold_table(ctx, frames, entry_frame, fields, step, &mf))) return st;
+    // (mesh_fold_table's layout: the image follows the planes it uploaded)
+    const bool host = frames->location != STK_DEVICE;
+    const MeshLayout L = mesh_layout(entry_frame.size(), host ? entry_frame.size() : 0, 0, 0, mf.gw, mf.gh, (size_t)w * h * cn);
+    double ms = 0.0;
+    if ((st = mesh_mean_fold(ctx, (int)entry_frame.size(), frames->depth, w, h, cn, frame_row_bytes(frames), alpha, border_mode, border_value,
+                             is_affine, mf, (float*)(ctx->mesh.as<char>() + L.image), out, &ms)))
+        return st;
+    ctx->timing.finalize_ms = ms;
+    return STK_OK;
+}
+
+stk_status stk_mesh_local_weighted_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                                         int32_t border_mode, const double* border_value, double alpha, const stk_frame_weight* per_frame,
+                                         const float* const* maps, float floor, int32_t power, const float* const* fields, int32_t step,
+                                         stk_image_f32* out, float* den_out) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    if (!fields) return fail(ctx, STK_INVALID_PARAMS, "null fields");
+    return local_weighted_stack_impl(ctx, frames, M, include, is_affine, border_mode, border_value, alpha, per_frame, maps, floor, power,
+                                     fields, step, out, den_out);
+}
+
+stk_status stk_ecc_match_local_aligned(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                       const stk_mesh_params* mesh, const stk_local_params* local, stk_image_f32* out,
+                                       stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    stk_status st = mesh_match_check(ctx, frames, mesh, local, out);
+    if (st) return st;
+    (void)hipSetDevice(ctx->device);
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    MeshLayout L;
+    if ((st = mesh_match_reserve(ctx, frames, mesh, local, &L))) return st;
+    std::vector<stk_frame_stats> own;
+    if (!stats) { own.resize(n); stats = own.data(); }
+    // the plain call, on this context's own device, its mean into the workspace image (unused)
+    stk_image_f32 mimg{(float*)(ctx->mesh.as<char>() + L.image), w, h, cn, STK_DEVICE, 0};
+    if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
+    const stk_timing keep = ctx->timing;
+    // every frame is a sample: frame 0 through the identity, frame i through its warp (as in stk_ecc_match_weighted)
+    const int is_affine = params->motion_type != STK_MOTION_HOMOGRAPHY;
+    std::vector<const void*> dev;
+    resident_frames(ctx, frames, dev);
+    std::vector<WarpFrame> wf(n);
+    std::vector<int> entry_frame(n);
+    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    make_warp_frame(wf[0], dev[0], I3, is_affine);
+    for (int i = 1; i < n; i++) make_warp_frame(wf[i], dev[i], stats[i].warp, is_affine);
+    for (int i = 0; i < n; i++) entry_frame[i] = i;
+    const size_t rb = frame_row_bytes(frames);
+    if ((st = warp_table_upload(ctx, wf, rb, w, h, is_affine))) return st;
+    st = mesh_finish(ctx, L, frames, entry_frame, dev, rb, is_affine, STK_BORDER_CONSTANT, nullptr, mesh, local, out);
+    const double fin = ctx->timing.finalize_ms;
+    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : fin;
+    return st;
+}
+
+stk_status stk_keypoint_match_local_aligned(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                            float scale_down_width, const stk_mesh_params* mesh, const stk_local_params* local,
+                                            stk_image_f32* out, int32_t* dropped, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    stk_status st = mesh_match_check(ctx, frames, mesh, local, out);
+    if (st) return st;
+    if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
+    if (local && (st = local_check_border(ctx, params->border_mode, params->border_value))) return st;
+    (void)hipSetDevice(ctx->device);
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    MeshLayout L;
+    if ((st = mesh_match_reserve(ctx, frames, mesh, local, &L))) return st;
+    std::vector<stk_frame_stats> own;
+    if (!stats) { own.resize(n); stats = own.data(); }
+    stk_image_f32 mimg{(float*)(ctx->mesh.as<char>() + L.image), w, h, cn, STK_DEVICE, 0};
+    if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
+    const stk_timing keep = ctx->timing;
+    // the samples: frame 0 through the identity and the frames with a homography (status 0), in stack order, with the
+    // params' border (as in stk_keypoint_match_weighted)
+    std::vector<const void*> dev;
+    resident_frames(ctx, frames, dev);
+    std::vector<WarpFrame> wf;
+    std::vector<int> entry_frame;
+    wf.reserve(n);
+    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    wf.emplace_back();
+    make_warp_frame(wf.back(), dev[0], I3, 0);
+    entry_frame.push_back(0);
+    for (int i = 1; i < n; i++) {
+        if (stats[i].status != 0) continue;
+        wf.emplace_back();
+        make_warp_frame(wf.back(), dev[i], stats[i].warp, 0);
+        entry_frame.push_back(i);
+    }
+    const size_t rb = frame_row_bytes(frames);
+    if ((st = warp_table_upload(ctx, wf, rb, w, h, 0))) return st;
+    st = mesh_finish(ctx, L, frames, entry_frame, dev, rb, 0, params->border_mode, params->border_value, mesh, local, out);
+    const double fin = ctx->timing.finalize_ms;
+    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : fin;
+    return st;
+}
+
+}  // extern "C"

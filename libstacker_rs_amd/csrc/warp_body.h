@@ -38,6 +38,11 @@ template <int CN> struct FoldStoreW;
 template <int CN> struct FoldLocal;
 template <int CN> struct ClipWGeneric;
 struct ClipWU8C3;
+struct NoClip;
+// The mesh variant of the generic kernel (kernels_mesh.hip; definition: include/stacker.h, "Mesh fold"): a state wrapped in
+// Mesh<> runs the same hooks at coordinates displaced by the entry's field. A wrapper around the state, not a further
+// template parameter: the instantiations without it keep their names and their instructions.
+template <class State> struct Mesh : State {};
 
 // The coverage weight of one sample: what the fold's interpolation (lerp chain, or the classic four-weight sum) gives for a
 // frame whose every value is 1.0f under alpha = 1 and BORDER_CONSTANT 0; i00 .. i11 say which taps are inside the frame.
@@ -76,6 +81,31 @@ __device__ __forceinline__ int sat_int_d(double v) {
     return (int)__builtin_rint(v);
 }
 
+// The mesh fold's coordinates of destination pixel (x, y) under table entry f (include/stacker.h, "Mesh fold"): the
+// bilinear sample of the entry's node field (ClipArgs::fields[f]: mesh_gh x mesh_gw x 2 f32, node spacing 1 << mesh_shift;
+// a null plane = no displacement), lerp chain by fma, added to the pixel's own coordinates.
+struct MeshXY { float x, y; };
+__device__ __forceinline__ MeshXY mesh_displace(const ClipArgs& ca, int f, int x, int y) {
+    MeshXY r{(float)x, (float)y};
+    const float* __restrict__ D = ca.fields[f];
+    if (D) {
+        const int k = x >> ca.mesh_shift, j = y >> ca.mesh_shift;
+        const int k1 = min(k + 1, ca.mesh_gw - 1), j1 = min(j + 1, ca.mesh_gh - 1);
+        const float u = (float)(x - (k << ca.mesh_shift)) * ca.mesh_inv, v = (float)(y - (j << ca.mesh_shift)) * ca.mesh_inv;
+        const float* r0 = D + (size_t)j * ca.mesh_gw * 2;
+        const float* r1 = D + (size_t)j1 * ca.mesh_gw * 2;
+        float d[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            const float t0 = __builtin_fmaf(u, r0[k1 * 2 + c] - r0[k * 2 + c], r0[k * 2 + c]);
+            const float t1 = __builtin_fmaf(u, r1[k1 * 2 + c] - r1[k * 2 + c], r1[k * 2 + c]);
+            d[c] = __builtin_fmaf(v, t1 - t0, t0);
+        }
+        r.x = r.x + d[0]; r.y = r.y + d[1];
+    }
+    return r;
+}
+
 // The generic fold: any depth, 1 / 3 / 4 channels, every border mode, both subpixel modes. One thread owns one destination
 // pixel and loops over the frame table. CLIP = false: the mean fold (running sums, acc (+)= sum of the samples);
 // true: one sigma-clipping pass (ClipState, kernels_clip.hip) over the same samples.
@@ -84,11 +114,12 @@ __device__ __forceinline__ int sat_int_d(double v) {
 // reads compiled to flat loads — a different, slower mean kernel.)
 template <typename T, int CN, bool CLIP, class ClipState>
 __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipArgs ca) {
+    constexpr bool MESH = std::is_same_v<ClipState, Mesh<NoClip>> || std::is_same_v<ClipState, Mesh<FoldLocal<CN>>>;
     constexpr bool WEIGHTED = std::is_same_v<ClipState, FoldWeighted<CN>>;
     constexpr bool MOMENTS = std::is_same_v<ClipState, FoldMoments<CN>>;
     // the normalised, coverage-aware rejection states (kernels_clip.hip, FoldStoreW below) take kappa like the weighted mode
     constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>;
-    constexpr bool LOCAL = std::is_same_v<ClipState, FoldLocal<CN>>;      // kappa like the weighted mode, and the coordinates
+    constexpr bool LOCAL = std::is_same_v<ClipState, FoldLocal<CN>> || std::is_same_v<ClipState, Mesh<FoldLocal<CN>>>;   // kappa like the weighted mode, and the coordinates
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if constexpr (std::is_same_v<ClipState, FoldStore<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
@@ -116,8 +147,16 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
         const WarpFrame* fr = a.frames + (MOMENTS ? f * (1 + (int)blockIdx.z) : f);
         const T* __restrict__ src = (const T*)fr->src;
 #define STK_SUBPIX a.subpixel_bits
+        if constexpr (MESH) {
+            // the entry's field moves the destination coordinate; these two shadow the pixel's own for the fragments below
+            const MeshXY mxy = mesh_displace(ca, f, x, y);
+            const float fx = mxy.x, fy = mxy.y;
 #include "warp_coords.inc.h"
 #include "warp_linear_sample.inc.h"
+        } else {
+#include "warp_coords.inc.h"
+#include "warp_linear_sample.inc.h"
+        }
 #undef STK_SUBPIX
     }
     } while (MOMENTS && ++rep < ca.reps);
