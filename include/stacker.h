@@ -670,6 +670,96 @@ stk_status stk_keypoint_match_local_aligned(stk_ctx* ctx, const stk_frames* fram
                                             float scale_down_width, const stk_mesh_params* mesh, const stk_local_params* local_or_null,
                                             stk_image_f32* out, int32_t* dropped, stk_frame_stats* stats_or_null);
 
+/* ---- drizzle integration onto a finer or larger output grid: an EXTENSION beyond the reference --------------------
+ * Variable-pixel linear reconstruction (Fruchter & Hook 2002). Every other combine writes onto frame 0's own grid and
+ * samples by interpolation; this one has an output grid with its own scale, origin and size, shrinks every source pixel to
+ * a "drop" of side pixfrac before it spreads it over the output pixels it overlaps, and records in a weight image how much
+ * landed where. Formulated as a GATHER: one output pixel collects from the source pixels that reach it, entries in fold
+ * order, no scatter, no atomics, the same bits on every call whatever the options. sw x sh is the source frames' size,
+ * ow x oh the output's (taken from `out`), s = scale, p = pixfrac.
+ * Output grid. The centre of output pixel (X, Y) lies at the frame-0 coordinate
+ *   x0 = (X + 0.5) / s - 0.5 + origin_x,   y0 = (Y + 0.5) / s - 0.5 + origin_y.
+ *   s = 1 with origin 0 is frame 0's own grid; a negative origin with a larger `out` is a canvas that extends past frame 0.
+ * Coordinates. For table entry i (the included frames in index order; in the whole-stack forms frame 0 through the
+ *   identity, then the kept frames) the host composes in double, each operation rounded on its own:
+ *     inv = the fold's inverse of the forward matrix M_i (cv::invert's adjugate, or invertAffineTransform)
+ *     g = 1.0 / (double)s;  tx = (0.5 * g - 0.5) + (double)origin_x;  ty = (0.5 * g - 0.5) + (double)origin_y
+ *     per row r:  A[r][0] = inv[r][0] * g;  A[r][1] = inv[r][1] * g;  A[r][2] = (inv[r][0] * tx + inv[r][1] * ty) + inv[r][2]
+ *   and rounds A to f32. (u, v) of output pixel (X, Y), `finite`, ix = floor u, iy = floor v and the fractions ax = u - ix,
+ *   ay = v - iy are exactly the fold's under warp_subpixel_bits = 0 with matrix A at ((float)X, (float)Y): the same fma
+ *   chains, the same true division for a homography, the same test finite = |u| < 1e9 and |v| < 1e9.
+ *   warp_subpixel_bits = 5: every drizzle call is STK_INVALID_PARAMS, as for cubic. warp_interpolation is ignored: drizzle
+ *   does not interpolate.
+ * Everything below is f32 multiplies, adds, subtractions, one reciprocal, min and max, each rounded on its own (no fma);
+ * min and max are C's fminf / fmaxf (a NaN operand gives the other one); `/` is correctly rounded.
+ * Local coordinates. The nearest source pixel and the offset from it, so that no large magnitudes cancel:
+ *   jn = ax >= 0.5f ? ix + 1 : ix;   d = ax >= 0.5f ? ax - 1.0f : ax      (exact; d in [-0.5, 0.5]; jn = floor(u + 0.5), d = u - jn)
+ *   kn and e likewise from iy and ay.
+ * Footprint. The output pixel's half-extent in source pixels is half the bounding box of its image under the local
+ *   Jacobian: hx = (|du/dX| + |du/dY|) / 2, hy = (|dv/dX| + |dv/dY|) / 2, both clamped to [0, hmax], hmax = 1.5f - 0.5f * p.
+ *   With |d| <= 0.5 the clamp keeps the footprint [d - hx, d + hx] inside (-2 + p/2, 2 - p/2): it never reaches the drop of
+ *   source pixel jn - 2 or jn + 2, so THREE TAPS PER AXIS ARE ALWAYS SUFFICIENT.
+ *   Affine entry (constants of the entry, on the host in double from the f32 values of A, rounded to f32, then the clamp):
+ *     hx = fminf((float)(0.5 * (|A00| + |A01|)), hmax);   hy = fminf((float)(0.5 * (|A10| + |A11|)), hmax)
+ *   Perspective entry (per pixel):
+ *     uu = (float)jn + d;  vv = (float)kn + e;  W = (A20 * (float)X + A21 * (float)Y) + A22;  rw = 1.0f / |W|
+ *     hx = fminf(((|A00 - uu * A20| + |A01 - uu * A21|) * rw) * 0.5f, hmax)
+ *     hy = fminf(((|A10 - vv * A20| + |A11 - vv * A21|) * rw) * 0.5f, hmax)
+ * Taps and weights. hp = 0.5f * p. For a in {-1, 0, 1}:
+ *     ox_a = fmaxf(0, fminf(d + hx, (float)a + hp) - fmaxf(d - hx, (float)a - hp))
+ *   and ox_a = 0 if column jn + a is outside [0, sw) or the coordinate is not finite; oy_b likewise from e, hy, kn and sh.
+ *   Tap (jn + a, kn + b) is LIVE iff ox_a > 0 and oy_b > 0 and, with maps, the entry's map value there is > 0. Its weight
+ *   is wgt = ox_a * oy_b, with maps (ox_a * oy_b) * map value. Only live taps are read. There is no border mode: what is
+ *   outside a frame contributes nothing. maps: sw x sh f32 planes by frame index exactly as stk_local_weighted_stack takes
+ *   them, read at the integer tap, no interpolation; a NULL plane (or maps == NULL) means all ones. This is how bad-pixel
+ *   masks and inverse-variance maps enter: a pixel whose map value is 0 is never read, whatever it holds.
+ * Combine. Entries in fold order, live taps row-major (b outer, a inner):
+ *     num_c = 0;  den = 0
+ *     for each entry i with w_i > 0:
+ *         s_c = 0;  k = 0
+ *         for each live tap:  t = (float)src[tap][c] * alpha;  s_c = s_c + wgt * t;  k = k + wgt
+ *         if k > 0:  num_c = num_c + w_i * (s_c * g_i,c + o_i,c * k);  den = den + w_i * k
+ *     out_c = den > 0 ? num_c / den : fill;     den_out (optional, ow x oh f32, in the location of `out`) = den
+ *   g, o, w are the stk_frame_weight records of the weighted combine (NULL = gain 1, offset 0, weight 1). den is the
+ *   drizzle weight image.
+ * Consequences.
+ *   - s = 1, p = 1, origin 0, no maps, a pure translation: hx = hy = 0.5 and ox_a = max(0, 1 - |d - a|), the bilinear
+ *     weights. The result is the mathematics of the weighted combine with coverage = 1, not its bits (the order differs).
+ *   - Small p with few frames leaves holes: den = 0 and out = fill.
+ *   - The bounding-box footprint over-covers under rotation: this is the "turbo" approximation of the drizzle literature,
+ *     not polygon clipping. The clamp cuts the footprint of a map that shrinks the output by more than 3 - p per axis.
+ * Validation, on the host before any launch; anything else is STK_INVALID_PARAMS: s finite in [1, 4]; p finite in (0, 1];
+ * origins and fill finite; reserved = 0; 1 <= ow, oh <= 32768; out->channels = the frames'; `out` tightly packed; weights
+ * finite and >= 0 and at least one included weight > 0; gains and offsets finite. stk_timing.finalize_ms is the device
+ * time of the drizzle launch (in the whole-stack forms warp_ms etc. are the plain call's). A multi-device context runs
+ * these calls on its first device. */
+typedef struct {
+    float   scale, pixfrac;         /* output pixels per frame-0 pixel: 1 .. 4;  drop side in source pixels: (0, 1] */
+    float   origin_x, origin_y;     /* frame-0 coordinate of the output grid's corner pixel at scale 1 (see above) */
+    float   fill;                   /* value of output pixels nothing landed on: finite */
+    int32_t reserved;               /* 0 */
+} stk_drizzle_params;
+
+/* Drizzle over caller-held warps. M, include_or_null, is_affine, alpha: as in stk_clip_stack. Any depth, 1 / 3 / 4 channels.
+ * Frames and maps are in frames->location (host frames and their maps are copied over), `out` and den_or_null in
+ * out->location. per_frame_or_null: n records by frame index (flags ignored; excluded frames' records are not read).
+ * maps_or_null: n plane pointers by frame index, single entries may be NULL. out: ow x oh x channels, tightly packed. */
+stk_status stk_drizzle_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                             int32_t is_affine, double alpha, const stk_drizzle_params* drizzle,
+                             const stk_frame_weight* per_frame_or_null, const float* const* maps_or_null, stk_image_f32* out,
+                             float* den_or_null);
+/* stk_ecc_match / stk_keypoint_match with the drizzle combine: the stack is aligned exactly as the plain call aligns it
+ * (stats, warps, iteration counts, `dropped` and errors are the plain call's), then frame 0 (identity) and the kept frames
+ * (keypoint: status 0) are drizzled from the full-size resident frames with alpha = 1 / 255, all weights 1 and no maps. The
+ * keypoint parameters' border mode is not used. By definition the result equals stk_drizzle_stack on the stats' warps bit
+ * for bit. 8-bit BGR(A) frames, as the plain calls take them. */
+stk_status stk_ecc_match_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                 const stk_drizzle_params* drizzle, stk_image_f32* out, float* den_or_null,
+                                 stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                      float scale_down_width, const stk_drizzle_params* drizzle, stk_image_f32* out,
+                                      int32_t* dropped, float* den_or_null, stk_frame_stats* stats_or_null);
+
 /* ---- normalised, coverage-aware sigma-clip and quantile stacking: an EXTENSION beyond the reference -------------
  * The two rejection combines with the per-frame gain, offset and weight and the coverage of the weighted combine: frames
  * are compared after each has been mapped onto frame 0's level, and a frame that does not cover a pixel is no sample of

@@ -10,7 +10,7 @@ use (api.Stacker / _ffi.load) and there is no CPU fallback.
 """
 from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_WRAP,  # noqa: F401
                   INTER_CUBIC, INTER_LINEAR,
-                  LEAST_SQUARES, LMEDS, RANSAC, RHO, EccMatchParameters, HipError, InvalidParams, IoError,
+                  LEAST_SQUARES, LMEDS, RANSAC, RHO, DrizzleParameters, EccMatchParameters, HipError, InvalidParams, IoError,
                   KeyPointMatchParameters, LocalParameters, MeshParameters, MotionType, NotEnoughFiles, NotImplementedYet, OpenCvError,
                   ProcessingError, QuantileParameters, RobustClipParameters, SelectParameters, SigmaClipParameters, Stacker,
                   StackerError, WeightParameters,
@@ -18,4 +18,4 @@ from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_RE
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
-           "SelectParameters", "rank_frames", "LocalParameters", "MeshParameters", "mesh_grid"]
+           "SelectParameters", "rank_frames", "LocalParameters", "MeshParameters", "mesh_grid", "DrizzleParameters"]

@@ -77,6 +77,11 @@ class MeshParams(C.Structure):
                 ("max_shift", C.c_float), ("min_eig", C.c_float), ("fill", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DrizzleParams(C.Structure):
+    _fields_ = [("scale", C.c_float), ("pixfrac", C.c_float), ("origin_x", C.c_float), ("origin_y", C.c_float),
+                ("fill", C.c_float), ("reserved", C.c_int32)]
+
+
 class SelectParams(C.Structure):
     _fields_ = [("metric", C.c_int32), ("ksize", C.c_int32), ("drop_worst", C.c_int32), ("keep_fraction", C.c_float),
                 ("weight_mode", C.c_int32), ("reserved", C.c_int32)]
@@ -165,6 +170,13 @@ SIGNATURES = {
     "stk_keypoint_match_local_aligned": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
                                                     C.POINTER(MeshParams), C.POINTER(LocalParams), C.POINTER(ImageF32),
                                                     C.POINTER(C.c_int32), C.POINTER(FrameStats)]),
+    "stk_drizzle_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
+                                     C.POINTER(DrizzleParams), C.POINTER(FrameWeight), C.c_void_p, C.POINTER(ImageF32), C.c_void_p]),
+    "stk_ecc_match_drizzle": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float, C.POINTER(DrizzleParams),
+                                         C.POINTER(ImageF32), C.c_void_p, C.POINTER(FrameStats)]),
+    "stk_keypoint_match_drizzle": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                              C.POINTER(DrizzleParams), C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p,
+                                              C.POINTER(FrameStats)]),
     "stk_clip_stack_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_double, C.POINTER(ClipParams), C.POINTER(FrameWeight), C.c_int32, C.POINTER(ImageF32),
                                            C.c_void_p, C.c_void_p]),

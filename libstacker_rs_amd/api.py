@@ -12,6 +12,7 @@ marshals pointers; it has no CPU fallback and raises if the library is missing.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import os
 import enum
@@ -188,6 +189,26 @@ class MeshParameters:             # extension beyond the reference: include/stac
     def _c(self) -> _ffi.MeshParams:
         return _ffi.MeshParams(int(self.step), int(self.radius), int(self.max_iters), float(self.epsilon), float(self.max_shift),
                                float(self.min_eig), int(self.fill), 0)
+
+
+@dataclass
+class DrizzleParameters:          # extension beyond the reference: include/stacker.h, stk_drizzle_params
+    """Drizzle integration: the output grid has `scale` (1 .. 4) pixels per frame-0 pixel and starts at frame-0 coordinate
+    (`origin_x`, `origin_y`); every source pixel is shrunk to a drop of side `pixfrac` (0 < pixfrac <= 1) before it is
+    spread over the output pixels it overlaps. An output pixel nothing landed on gets `fill`."""
+    scale: float = 2.0
+    pixfrac: float = 0.5
+    origin_x: float = 0.0
+    origin_y: float = 0.0
+    fill: float = 0.0
+
+    def _c(self) -> _ffi.DrizzleParams:
+        return _ffi.DrizzleParams(float(self.scale), float(self.pixfrac), float(self.origin_x), float(self.origin_y),
+                                  float(self.fill), 0)
+
+    def out_shape(self, height: int, width: int):
+        """(oh, ow) of the output that covers a height x width frame 0 from the origin on: ceil(scale * size)."""
+        return int(np.ceil(float(self.scale) * height)), int(np.ceil(float(self.scale) * width))
 
 
 def mesh_grid(width: int, height: int, step: int):
@@ -1080,6 +1101,93 @@ class Stacker:
                                                                C.byref(mp), None if lp is None else C.byref(lp), C.byref(img),
                                                                C.byref(dropped), stats))
         return (dropped.value, out) + ((self._stats_list(stats, m.n),) if return_stats else ())
+
+    # -- drizzle integration onto a finer or larger output grid (extension beyond the reference) ----------
+    def _drizzle_images(self, m: _Marshalled, drizzle: "DrizzleParameters", out_shape, return_den: bool):
+        """The oh x ow x C output (out_shape, or what covers frame 0 at the scale) and the weight image, where the frames live."""
+        oh, ow = (int(v) for v in out_shape) if out_shape is not None else drizzle.out_shape(m.h, m.w)
+        if oh < 1 or ow < 1:
+            raise InvalidParams("drizzle: the output must be at least one pixel wide and high")
+        if m.location == DEVICE:
+            import torch
+            out = torch.empty((oh, ow, m.c), dtype=torch.float32, device=m.torch_device)
+            den = torch.empty((oh, ow), dtype=torch.float32, device=m.torch_device) if return_den else None
+            ptr = (lambda t: t.data_ptr())
+        else:
+            out = np.empty((oh, ow, m.c), np.float32)
+            den = np.empty((oh, ow), np.float32) if return_den else None
+            ptr = (lambda a: a.ctypes.data)
+        img = _ffi.ImageF32(ptr(out), ow, oh, m.c, m.location, 0)
+        return out, img, den, (C.c_void_p(ptr(den)) if return_den else None)
+
+    def drizzle_stack(self, files, warps, drizzle: Optional["DrizzleParameters"] = None, gain=None, offset=None, weights=None,
+                      include=None, *, applied=None, maps=None, out_shape=None, is_affine=False, alpha=1.0 / 255.0,
+                      return_den: bool = False):
+        """Drizzle over caller-held warps (stk_drizzle_stack) onto an out_shape = (oh, ow) grid (default: what covers frame 0
+        at the scale). gain, offset, weights, applied: as in weighted_stack (None = 1 / 0 / 1). maps: None, or one H x W
+        float32 plane of non-negative weights per frame (a bad-pixel mask, an inverse variance), single entries may be None
+        = all ones. Returns the image, with return_den also the weight image."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        dz = drizzle or DrizzleParameters()
+        Md, inc = self._warps_arg(warps, include, m.n)
+        rec = None if (gain is None and offset is None and weights is None and applied is None) \
+            else self._records_arg(m, gain, offset, weights, applied)
+        mkeep, mptrs = None, None
+        if maps is not None:
+            planes = list(maps)
+            if len(planes) != m.n:
+                raise InvalidParams("one weight map (or None) per frame expected")
+            some = [p for p in planes if p is not None]
+            sub = copy.copy(m)                      # the planes that exist, marshalled like local_weighted_stack's
+            sub.n = len(some)
+            mkeep, some_ptrs = self._maps_arg(sub, some) if some else ([], [])
+            it = iter(some_ptrs)
+            mptrs = (C.c_void_p * m.n)(*[None if p is None else next(it) for p in planes])
+        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
+        p = dz._c()
+        self._check(self._lib.stk_drizzle_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine), float(alpha),
+                                                C.byref(p), rec, None if mptrs is None else C.cast(mptrs, C.c_void_p), C.byref(img),
+                                                dptr))
+        return (out, den) if return_den else out
+
+    def ecc_match_drizzle(self, files, params: EccMatchParameters, drizzle: Optional["DrizzleParameters"] = None,
+                          scale_down_width: Optional[float] = None, *, out_shape=None, return_den: bool = False,
+                          return_stats: bool = False):
+        """ecc_match with the drizzle combine (stk_ecc_match_drizzle): aligned as ecc_match aligns, then frame 0 and every
+        frame under its warp drizzled onto the output grid. Returns the image[, the weight image][, the stats]."""
+        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        dz = drizzle or DrizzleParameters()
+        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
+        stats = (_ffi.FrameStats * m.n)()
+        p, dp = params._c(), dz._c()
+        self._check(self._lib.stk_ecc_match_drizzle(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                    C.byref(dp), C.byref(img), dptr, stats))
+        res = (out,) + ((den,) if return_den else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return res if len(res) > 1 else out
+
+    def keypoint_match_drizzle(self, files, params: KeyPointMatchParameters, drizzle: Optional["DrizzleParameters"] = None,
+                               scale_down_width: Optional[float] = None, *, out_shape=None, return_den: bool = False,
+                               return_stats: bool = False):
+        """keypoint_match with the drizzle combine (stk_keypoint_match_drizzle): (dropped, image[, weight image][, stats]).
+        A dropped frame is no sample: it is absent from the weight image."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        dz = drizzle or DrizzleParameters()
+        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p, dp = params._c(), dz._c()
+        self._check(self._lib.stk_keypoint_match_drizzle(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                         C.byref(dp), C.byref(img), C.byref(dropped), dptr, stats))
+        return (dropped.value, out) + ((den,) if return_den else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
 
     # -- normalised, coverage-aware rejection combines (extension beyond the reference) -----------------
     def _pixel_counts_image(self, m: _Marshalled):

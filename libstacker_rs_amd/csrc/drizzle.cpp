@@ -1,0 +1,254 @@
+// drizzle.cpp — drizzle integration onto a finer or larger output grid: stk_drizzle_stack, stk_ecc_match_drizzle,
+// stk_keypoint_match_drizzle (an extension beyond the reference; definition in include/stacker.h, stk_drizzle_params;
+// kernel in kernels_drizzle.hip). The frame table is the fold's (ctx->warpframes), its matrices composed here with the
+// output grid's map. ctx->local (grow-only, shared with local.cpp; one call at a time) holds, in this order: in the
+// whole-stack forms the plain call's mean (unused), then the footprint table, the per-entry records, the map pointer
+// table, a host output's staging image and den plane, and host maps' planes. Like weighted.cpp, the whole-stack forms run
+// the plain call first and take the warps and the kept set from its stats; the frames are still resident in HBM.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "context.h"
+#include "drizzle.h"
+
+using namespace stk;
+
+namespace {
+
+struct DrizzleLayout {
+    size_t foot, coef, mptrs, image, den, planes, plane, total;     // byte offsets into ctx->local; plane: bytes of one map plane
+};
+
+// pre: bytes in front (the plain call's mean); the image, den and planes only where they are staged for the host
+DrizzleLayout drizzle_layout(size_t pre, int n_entries, int sw, int sh, int ow, int oh, int cn, bool host_out, size_t n_planes) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t ne = (size_t)std::max(n_entries, 1);
+    DrizzleLayout L{};
+    L.foot = up(pre);
+    L.coef = L.foot + up(ne * 2 * sizeof(float));
+    L.mptrs = L.coef + up(ne * sizeof(stk_frame_weight));
+    L.image = L.mptrs + up(ne * sizeof(void*));
+    L.den = L.image + (host_out ? up((size_t)ow * oh * cn * sizeof(float)) : 0);
+    L.planes = L.den + (host_out ? up((size_t)ow * oh * sizeof(float)) : 0);
+    L.plane = up((size_t)sw * sh * sizeof(float));
+    L.total = L.planes + n_planes * L.plane;
+    return L;
+}
+
+stk_status drizzle_reserve(stk_ctx* ctx, const DrizzleLayout& L) {
+    if (ctx->local.reserve(L.total) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, STK_HIP_ERROR, "drizzle: device allocation of " + std::to_string(L.total) + " bytes failed");
+    }
+    return STK_OK;
+}
+
+// every check that needs neither the matrices nor the records, in the order the errors are reported
+stk_status drizzle_validate(stk_ctx* ctx, const stk_frames* frames, bool need_bgr, const stk_drizzle_params* p, const stk_image_f32* out) {
+    stk_status st = check_frames(ctx, frames, need_bgr, false);     // warp_interpolation is ignored: the option pair is not asked
+    if (st) return st;
+    if (ctx->opt_subpixel_bits != 0)
+        return fail(ctx, STK_INVALID_PARAMS, "drizzle needs warp_subpixel_bits = 0: it is defined on exact coordinates only");
+    if (!p) return fail(ctx, STK_INVALID_PARAMS, "null drizzle parameters");
+    if (!std::isfinite(p->scale) || p->scale < 1.0f || p->scale > 4.0f) return fail(ctx, STK_INVALID_PARAMS, "drizzle: scale must be 1 .. 4");
+    if (!std::isfinite(p->pixfrac) || !(p->pixfrac > 0.0f) || p->pixfrac > 1.0f)
+        return fail(ctx, STK_INVALID_PARAMS, "drizzle: pixfrac must be in (0, 1]");
+    if (!std::isfinite(p->origin_x) || !std::isfinite(p->origin_y)) return fail(ctx, STK_INVALID_PARAMS, "drizzle: the origin must be finite");
+    if (!std::isfinite(p->fill)) return fail(ctx, STK_INVALID_PARAMS, "drizzle: fill must be finite");
+    if (p->reserved != 0) return fail(ctx, STK_INVALID_PARAMS, "drizzle parameters: reserved must be 0");
+    if (!out || !out->data) return fail(ctx, STK_INVALID_PARAMS, "null output image");
+    if (out->width < 1 || out->height < 1 || out->width > 32768 || out->height > 32768)
+        return fail(ctx, STK_INVALID_PARAMS, "drizzle: the output must be 1 .. 32768 pixels wide and high");
+    if (out->channels != frames->channels) return fail(ctx, STK_INVALID_PARAMS, "drizzle: the output must have the frames' channels");
+    if (out->row_stride_bytes && out->row_stride_bytes != (size_t)out->width * out->channels * sizeof(float))
+        return fail(ctx, STK_INVALID_PARAMS, "output must be tightly packed");
+    return STK_OK;
+}
+
+// Table entry under forward matrix M (include/stacker.h, "Coordinates"): A = inv(M) . G in double, each operation rounded on
+// its own, cast to f32; for an affine entry the footprint half-extents from the f32 values of A.
+void drizzle_entry(WarpFrame& wf, float* foot, const void* src, const double* M, int is_affine, const stk_drizzle_params* p) {
+    double inv[9], A[9];
+    if (is_affine) warp_invert_affine(M, inv); else warp_invert3x3(M, inv);
+    const double g = 1.0 / (double)p->scale;
+    const double tx = (0.5 * g - 0.5) + (double)p->origin_x, ty = (0.5 * g - 0.5) + (double)p->origin_y;
+    for (int r = 0; r < 3; r++) {
+        A[3 * r] = inv[3 * r] * g;
+        A[3 * r + 1] = inv[3 * r + 1] * g;
+        A[3 * r + 2] = (inv[3 * r] * tx + inv[3 * r + 1] * ty) + inv[3 * r + 2];
+    }
+    wf.src = src;
+    wf.flags = 0;
+    for (int k = 0; k < 9; k++) { wf.Md[k] = A[k]; wf.M[k] = (float)A[k]; }
+    const float hmax = 1.5f - 0.5f * p->pixfrac;
+    foot[0] = std::fmin((float)(0.5 * (std::fabs((double)wf.M[0]) + std::fabs((double)wf.M[1]))), hmax);
+    foot[1] = std::fmin((float)(0.5 * (std::fabs((double)wf.M[3]) + std::fabs((double)wf.M[4]))), hmax);
+}
+
+// The drizzle launch over `dev[entry_frame[k]]` under Ms[k] (9 doubles each) with the records `coef` (per entry) and the
+// maps (by frame index, in frames->location, or null). ctx->local is reserved for L. Writes `out` and `den_out` (out's
+// location), synchronises, returns the launch's device time in *ms.
+stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* frames, const std::vector<const void*>& dev,
+                       const std::vector<int>& entry_frame, const std::vector<const double*>& Ms, int is_affine, double alpha,
+                       const stk_drizzle_params* p, const std::vector<stk_frame_weight>& coef, const float* const* maps,
+                       stk_image_f32* out, float* den_out, double* ms) {
+    const int ne = (int)entry_frame.size(), sw = frames->width, sh = frames->height, cn = frames->channels;
+    const int ow = out->width, oh = out->height;
+    const size_t rb = frame_row_bytes(frames);
+    char* base = ctx->local.as<char>();
+    const bool host_out = out->location != STK_DEVICE, host_maps = frames->location != STK_DEVICE;
+    std::vector<WarpFrame> wf(ne);
+    std::vector<float> foot((size_t)ne * 2);
+    std::vector<const float*> mptr(ne, nullptr);
+    for (int k = 0; k < ne; k++) drizzle_entry(wf[k], &foot[2 * (size_t)k], dev[entry_frame[k]], Ms[k], is_affine, p);
+    stk_status st = warp_table_upload(ctx, wf, rb, ow, oh, is_affine);
+    if (st) return st;
+    HIP_TRY(hipMemcpyAsync(base + L.foot, foot.data(), foot.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base + L.coef, coef.data(), coef.size() * sizeof(stk_frame_weight), hipMemcpyHostToDevice, ctx->stream));
+    if (maps) {
+        size_t slot = 0;
+        for (int k = 0; k < ne; k++) {
+            const float* m = maps[entry_frame[k]];
+            if (m && host_maps) {
+                float* d = (float*)(base + L.planes + slot++ * L.plane);
+                HIP_TRY(hipMemcpyAsync(d, m, (size_t)sw * sh * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+                m = d;
+            }
+            mptr[k] = m;
+        }
+        HIP_TRY(hipMemcpyAsync(base + L.mptrs, mptr.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    }
+    DrizzleArgs a{};
+    a.frames = ctx->warpframes.as<WarpFrame>();
+    a.n_frames = ne;
+    a.sw = sw; a.sh = sh; a.cn = cn;
+    a.src_stride = rb / (frames->depth / 8);
+    a.alpha = (float)alpha;
+    a.is_affine = is_affine;
+    a.foot = (const float*)(base + L.foot);
+    a.coef = (const stk_frame_weight*)(base + L.coef);
+    a.maps = maps ? (const float* const*)(base + L.mptrs) : nullptr;
+    a.hp = 0.5f * p->pixfrac; a.hmax = 1.5f - 0.5f * p->pixfrac; a.fill = p->fill;
+    a.out = host_out ? (float*)(base + L.image) : out->data;
+    a.den = den_out ? (host_out ? (float*)(base + L.den) : den_out) : nullptr;
+    a.ow = ow; a.oh = oh;
+    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    HIP_TRY(launch_drizzle(a, frames->depth, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+    if (host_out) {
+        HIP_TRY(hipMemcpyAsync(out->data, a.out, (size_t)ow * oh * cn * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (den_out) HIP_TRY(hipMemcpyAsync(den_out, a.den, (size_t)ow * oh * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // the host tables leave scope
+    *ms = ev_ms(ctx->ev[4], ctx->ev[5]);
+    return STK_OK;
+}
+
+void drizzle_unit_record(stk_frame_weight* e) {
+    for (int c = 0; c < 4; c++) { e->gain[c] = 1.0f; e->offset[c] = 0.0f; }
+    e->weight = 1.0f; e->flags = 0;
+}
+
+// the tail of the whole-stack forms: the frames of `entry_frame` (frame 0 through the identity, the others under the
+// stats' warps), all weights 1, no maps, alpha = 1 / 255; the timing stays the plain call's but for finalize_ms
+stk_status drizzle_finish(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* frames, const std::vector<int>& entry_frame,
+                          const stk_frame_stats* stats, int is_affine, const stk_drizzle_params* p, stk_image_f32* out, float* den_out) {
+    static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    std::vector<const void*> dev;
+    resident_frames(ctx, frames, dev);
+    std::vector<const double*> Ms(entry_frame.size());
+    for (size_t k = 0; k < entry_frame.size(); k++) Ms[k] = entry_frame[k] == 0 ? I3 : stats[entry_frame[k]].warp;
+    std::vector<stk_frame_weight> coef(entry_frame.size());
+    for (stk_frame_weight& e : coef) drizzle_unit_record(&e);
+    const stk_timing keep = ctx->timing;
+    double ms = 0.0;
+    const stk_status st = drizzle_run(ctx, L, frames, dev, entry_frame, Ms, is_affine, 1.0 / 255.0, p, coef, nullptr, out, den_out, &ms);
+    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : ms;
+    return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+stk_status stk_drizzle_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                             double alpha, const stk_drizzle_params* p, const stk_frame_weight* per_frame, const float* const* maps,
+                             stk_image_f32* out, float* den_out) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    stk_status st = drizzle_validate(ctx, frames, false, p, out);
+    if (st) return st;
+    if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
+    const int n = frames->n, cn = frames->channels;
+    std::vector<int> entry_frame;
+    std::vector<stk_frame_weight> coef;
+    std::vector<const double*> Ms;
+    size_t n_planes = 0;
+    for (int i = 0; i < n; i++) {
+        if (include && !include[i]) continue;
+        stk_frame_weight e;
+        if (per_frame) e = per_frame[i]; else drizzle_unit_record(&e);
+        entry_frame.push_back(i);
+        coef.push_back(e);
+        Ms.push_back(M + 9 * (size_t)i);
+        if (maps && maps[i] && frames->location != STK_DEVICE) n_planes++;
+    }
+    if (coef.empty()) return fail(ctx, STK_INVALID_PARAMS, "drizzle: no frame included");
+    if ((st = weighted_check_coefs(ctx, coef, cn))) return st;
+    (void)hipSetDevice(ctx->device);
+    timing_begin(ctx);
+    const DrizzleLayout L = drizzle_layout(0, (int)coef.size(), frames->width, frames->height, out->width, out->height, cn,
+                                           out->location != STK_DEVICE, n_planes);
+    if ((st = drizzle_reserve(ctx, L))) return st;
+    std::vector<const void*> dev;
+    if ((st = resolve_frames(ctx, frames, dev))) return st;
+    double ms = 0.0;
+    if ((st = drizzle_run(ctx, L, frames, dev, entry_frame, Ms, is_affine != 0, alpha, p, coef, maps, out, den_out, &ms))) return st;
+    ctx->timing.finalize_ms = ms;
+    return STK_OK;
+}
+
+stk_status stk_ecc_match_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                 const stk_drizzle_params* p, stk_image_f32* out, float* den_out, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    stk_status st = drizzle_validate(ctx, frames, true, p, out);
+    if (st) return st;
+    (void)hipSetDevice(ctx->device);
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    const size_t pre = (size_t)w * h * cn * sizeof(float);
+    const DrizzleLayout L = drizzle_layout(pre, n, w, h, out->width, out->height, cn, out->location != STK_DEVICE, 0);
+    if ((st = drizzle_reserve(ctx, L))) return st;
+    std::vector<stk_frame_stats> own;
+    if (!stats) { own.resize(n); stats = own.data(); }
+    // the plain call, on this context's own device, its mean into the head of the workspace (unused)
+    stk_image_f32 mimg{ctx->local.as<float>(), w, h, cn, STK_DEVICE, 0};
+    if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
+    // every frame is a sample: frame 0 through the identity, frame i through its warp (as in stk_ecc_match_weighted)
+    std::vector<int> entry_frame(n);
+    for (int i = 0; i < n; i++) entry_frame[i] = i;
+    return drizzle_finish(ctx, L, frames, entry_frame, stats, params->motion_type != STK_MOTION_HOMOGRAPHY, p, out, den_out);
+}
+
+stk_status stk_keypoint_match_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,
+                                      const stk_drizzle_params* p, stk_image_f32* out, int32_t* dropped, float* den_out,
+                                      stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    stk_status st = drizzle_validate(ctx, frames, true, p, out);
+    if (st) return st;
+    if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
+    (void)hipSetDevice(ctx->device);
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    const size_t pre = (size_t)w * h * cn * sizeof(float);
+    const DrizzleLayout L = drizzle_layout(pre, n, w, h, out->width, out->height, cn, out->location != STK_DEVICE, 0);
+    if ((st = drizzle_reserve(ctx, L))) return st;
+    std::vector<stk_frame_stats> own;
+    if (!stats) { own.resize(n); stats = own.data(); }
+    stk_image_f32 mimg{ctx->local.as<float>(), w, h, cn, STK_DEVICE, 0};
+    if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
+    // the samples: frame 0 through the identity and the frames with a homography (status 0), in stack order
+    std::vector<int> entry_frame{0};
+    for (int i = 1; i < n; i++) if (stats[i].status == 0) entry_frame.push_back(i);
+    return drizzle_finish(ctx, L, frames, entry_frame, stats, 0, p, out, den_out);
+}
+
+}  // extern "C"

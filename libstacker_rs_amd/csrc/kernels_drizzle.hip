@@ -1,0 +1,147 @@
+// kernels_drizzle.hip — drizzle integration onto a finer or larger output grid (include/stacker.h, stk_drizzle_params;
+// DESIGN §4.14). A gather: one thread owns one OUTPUT pixel and loops over the frame table in fold order, as every other
+// fold here does; no scatter, no atomics, the same bits whatever the launch shape. Launch shape of the fold: 64 x 4
+// threads, a wave is 64 consecutive pixels of one output row.
+// Per entry:
+//   * the coordinates come from the fold's own fragment (warp_coords.inc.h at STK_SUBPIX == 0) with the entry's matrix,
+//     which the host composed with the output grid's map;
+//   * the three ox and the three oy overlaps are computed once (the weight is separable), with the in-frame test folded
+//     into them: a column or row outside the frame has overlap 0;
+//   * a wave none of whose pixels has a live column and a live row skips the entry by a vote (an output canvas larger than
+//     a frame's image, a frame that does not reach this part of the mosaic);
+//   * a tap row or column whose 1-D overlap is 0 is not loaded: at scale 2, pixfrac 0.5 at most two of three per axis are
+//     live, under a translation usually one;
+//   * affine entries read (hx, hy) from the table; perspective entries compute them from the matrix, (u, v) and W.
+// Every live address is inside its frame by construction: ox_a > 0 implies 0 <= jn + a < sw, oy_b > 0 implies
+// 0 <= kn + b < sh, and a non-finite coordinate has every overlap 0. The directory compiles with -ffp-contract=off: the
+// only fused operations are the fragment's.
+#include "drizzle.h"
+#include "warp_body.h"
+
+namespace stk {
+
+template <typename T, int CN, bool PERSPECTIVE, bool MAPS>
+__global__ __launch_bounds__(256) void drizzle_kernel(DrizzleArgs da) {
+    const int px = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int py = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (px >= da.ow || py >= da.oh) return;
+    const float fx = (float)px, fy = (float)py;
+    const float hp = da.hp, hmax = da.hmax, alpha = da.alpha;
+    const int sw = da.sw, sh = da.sh;
+    float num[CN], den = 0.0f;
+#pragma unroll
+    for (int c = 0; c < CN; c++) num[c] = 0.0f;
+
+    for (int f = 0; f < da.n_frames; f++) {
+        const stk_frame_weight* __restrict__ rec = da.coef + f;
+        const float wi = rec->weight;
+        if (!(wi > 0.0f)) continue;                                  // (uniform)
+        const WarpFrame* fr = da.frames + f;
+        // the fragment reads a.is_affine: a constant here, so that the division exists in the perspective kernels only
+        constexpr struct { int is_affine; } a{PERSPECTIVE ? 0 : 1};
+#define STK_SUBPIX 0
+#include "warp_coords.inc.h"
+#undef STK_SUBPIX
+        (void)w00; (void)w01; (void)w10; (void)w11;
+        // local coordinates: the nearest source pixel and the offset from it (exact)
+        const bool upx = ax >= 0.5f, upy = ay >= 0.5f;
+        const int jn = upx ? ix + 1 : ix, kn = upy ? iy + 1 : iy;
+        const float d = upx ? ax - 1.0f : ax, e = upy ? ay - 1.0f : ay;
+        float hx, hy;
+        if constexpr (PERSPECTIVE) {
+            const float uu = (float)jn + d, vv = (float)kn + e;
+            const float W = (fr->M[6] * fx + fr->M[7] * fy) + fr->M[8];
+            const float rw = 1.0f / __builtin_fabsf(W);
+            hx = fminf(((__builtin_fabsf(fr->M[0] - uu * fr->M[6]) + __builtin_fabsf(fr->M[1] - uu * fr->M[7])) * rw) * 0.5f, hmax);
+            hy = fminf(((__builtin_fabsf(fr->M[3] - vv * fr->M[6]) + __builtin_fabsf(fr->M[4] - vv * fr->M[7])) * rw) * 0.5f, hmax);
+        } else {
+            hx = da.foot[2 * f]; hy = da.foot[2 * f + 1];
+        }
+        const float lox = d - hx, hix = d + hx, loy = e - hy, hiy = e + hy;
+        float ox[3], oy[3];
+#pragma unroll
+        for (int t = 0; t < 3; t++) {
+            const float c = (float)(t - 1);
+            const float vx = fmaxf(0.0f, fminf(hix, c + hp) - fmaxf(lox, c - hp));
+            const float vy = fmaxf(0.0f, fminf(hiy, c + hp) - fmaxf(loy, c - hp));
+            ox[t] = (finite & ((unsigned)(jn + t - 1) < (unsigned)sw)) ? vx : 0.0f;
+            oy[t] = (finite & ((unsigned)(kn + t - 1) < (unsigned)sh)) ? vy : 0.0f;
+        }
+        const bool live = ((ox[0] > 0.0f) | (ox[1] > 0.0f) | (ox[2] > 0.0f)) & ((oy[0] > 0.0f) | (oy[1] > 0.0f) | (oy[2] > 0.0f));
+        if (__ballot(live) == 0) continue;                           // no pixel of this wave has a tap in this frame
+
+        const T* __restrict__ src = (const T*)fr->src;
+        const float* __restrict__ mp = nullptr;
+        if constexpr (MAPS) mp = da.maps[f];
+        float s[CN], k = 0.0f;
+#pragma unroll
+        for (int c = 0; c < CN; c++) s[c] = 0.0f;
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            if (!(oy[b] > 0.0f)) continue;
+            const int yy = kn + b - 1;
+            const T* __restrict__ row = src + (size_t)yy * da.src_stride;
+#pragma unroll
+            for (int t = 0; t < 3; t++) {
+                if (!(ox[t] > 0.0f)) continue;
+                const int xx = jn + t - 1;
+                float wgt = ox[t] * oy[b];
+                if constexpr (MAPS) {
+                    if (mp) {
+                        const float mv = mp[(size_t)yy * sw + xx];
+                        if (!(mv > 0.0f)) continue;
+                        wgt = wgt * mv;
+                    }
+                }
+                const T* __restrict__ p = row + (size_t)xx * CN;
+#pragma unroll
+                for (int c = 0; c < CN; c++) {
+                    const float v = (float)p[c] * alpha;
+                    s[c] = s[c] + wgt * v;
+                }
+                k = k + wgt;
+            }
+        }
+        if (k > 0.0f) {
+#pragma unroll
+            for (int c = 0; c < CN; c++) num[c] = num[c] + wi * (s[c] * rec->gain[c] + rec->offset[c] * k);
+            den = den + wi * k;
+        }
+    }
+    float* __restrict__ o = da.out + ((size_t)py * da.ow + px) * CN;
+#pragma unroll
+    for (int c = 0; c < CN; c++) o[c] = den > 0.0f ? num[c] / den : da.fill;
+    if (da.den) da.den[(size_t)py * da.ow + px] = den;
+}
+
+template <typename T, int CN>
+static void drizzle_launch(const DrizzleArgs& a, dim3 grid, hipStream_t s) {
+    const bool persp = !a.is_affine, maps = a.maps != nullptr;
+    if (persp && maps) drizzle_kernel<T, CN, true, true><<<grid, 256, 0, s>>>(a);
+    else if (persp) drizzle_kernel<T, CN, true, false><<<grid, 256, 0, s>>>(a);
+    else if (maps) drizzle_kernel<T, CN, false, true><<<grid, 256, 0, s>>>(a);
+    else drizzle_kernel<T, CN, false, false><<<grid, 256, 0, s>>>(a);
+}
+
+// A missing kernel is an error: every depth and channel count the entry points admit has its instantiation here.
+hipError_t launch_drizzle(const DrizzleArgs& a, int depth, hipStream_t s) {
+    if (a.n_frames <= 0 || a.ow <= 0 || a.oh <= 0 || a.ow > 32768 || a.oh > 32768 || !a.frames || !a.coef || !a.out ||
+        (a.is_affine && !a.foot))
+        return hipErrorInvalidValue;
+    const dim3 grid((a.ow + 63) / 64, (a.oh + 3) / 4);
+#define STK_DRIZZLE_CASE(D, T, CN) if (depth == D && a.cn == CN) drizzle_launch<T, CN>(a, grid, s)
+    STK_DRIZZLE_CASE(8, uint8_t, 3);
+    else STK_DRIZZLE_CASE(8, uint8_t, 1);
+    else STK_DRIZZLE_CASE(8, uint8_t, 4);
+    else STK_DRIZZLE_CASE(16, uint16_t, 3);
+    else STK_DRIZZLE_CASE(16, uint16_t, 1);
+    else STK_DRIZZLE_CASE(16, uint16_t, 4);
+    else STK_DRIZZLE_CASE(32, float, 3);
+    else STK_DRIZZLE_CASE(32, float, 1);
+    else STK_DRIZZLE_CASE(32, float, 4);
+    else return hipErrorInvalidValue;
+#undef STK_DRIZZLE_CASE
+    return hipGetLastError();
+}
+
+}  // namespace stk
