@@ -760,6 +760,66 @@ stk_status stk_keypoint_match_drizzle(stk_ctx* ctx, const stk_frames* frames, co
                                       float scale_down_width, const stk_drizzle_params* drizzle, stk_image_f32* out,
                                       int32_t* dropped, float* den_or_null, stk_frame_stats* stats_or_null);
 
+/* ---- mesh-displaced drizzle: drizzle through local-alignment fields: an EXTENSION beyond the reference -------------
+ * The two sections above in one combine: the drizzle of a stack whose frames carry, on top of their global warp, the
+ * residual displacement fields of stk_local_align. The grid map of drizzle is a scaling and a shift, so moving the frame-0
+ * coordinate of an output pixel by d is moving the output coordinate by s d: the host's composed matrix A_i stays as it
+ * is, and the fold's fragment runs at the displaced output coordinate. s, g, tx, ty and A_i are the drizzle definition's
+ * own; D_i is entry i's field, gh x gw x 2 f32 on the grid of stk_mesh_grid(sw, sh, step), exactly the planes
+ * stk_local_align writes; shift = log2 step. Everything is f32 with each operation rounded on its own, except where fma is
+ * written.
+ * Frame-0 coordinate of output pixel (X, Y):  x0 = (float)X * (float)g + (float)tx;  y0 = (float)Y * (float)g + (float)ty
+ *   (at s = 1, origin 0: (float)X and (float)Y exactly).
+ * Field sample. xc = fminf(fmaxf(x0, 0), (float)(sw - 1));  k = (int)xc >> shift;  k1 = min(k + 1, gw - 1);
+ *   u = (xc - (float)(k << shift)) * (1.0f / step);  yc, j, j1 and v likewise from y0, sh and gh. Per component c:
+ *     t0 = fma(u, D[j][k1][c] - D[j][k][c], D[j][k][c]);  t1 the same on row j1;  d_c = fma(v, t1 - t0, t0)
+ *   the mesh fold's own chain. Outside frame 0's image (a canvas) the field is that of the nearest edge. Every field address
+ *   comes from the clamped coordinate, never from a field value.
+ * Field slopes, from the differences the lerp already has. With a_c = D[j][k1][c] - D[j][k][c], b_c the same on row j1,
+ *   p_c = D[j1][k][c] - D[j][k][c] and q_c the same on column k1:
+ *     dxd_c = fma(v, b_c - a_c, a_c) * (1.0f / step);   dyd_c = fma(u, q_c - p_c, p_c) * (1.0f / step)
+ *   and dxd_c = 0 where x0 != xc (the coordinate was clamped along x), dyd_c = 0 where y0 != yc. (On a last node column
+ *   that lies on the image's last column k1 = k: a_c = b_c = 0 and the slope along x is 0 there; rows likewise.)
+ * Displaced coordinate.  Xd = (float)X + (float)s * d_0;  Yd = (float)Y + (float)s * d_1.  (u, v), finite, ix, iy, ax, ay are
+ *   the fold's under warp_subpixel_bits = 0 with A_i at (Xd, Yd) instead of ((float)X, (float)Y); the perspective W of the
+ *   footprint uses (Xd, Yd) too.
+ * Footprint. The un-halved rows of drizzle's local Jacobian times the displacement's own Jacobian E = I + grad d:
+ *     e00 = 1.0f + dxd_0;  e01 = dyd_0;  e10 = dxd_1;  e11 = 1.0f + dyd_1
+ *   Affine entry:       hx = fminf((|A00 * e00 + A01 * e10| + |A00 * e01 + A01 * e11|) * 0.5f, hmax);  hy the same from A10, A11
+ *   Perspective entry:  j0 = A00 - uu * A20;  j1 = A01 - uu * A21 (uu, vv, W, rw as in drizzle, at the displaced coordinates);
+ *                       hx = fminf(((|j0 * e00 + j1 * e10| + |j0 * e01 + j1 * e11|) * rw) * 0.5f, hmax);  hy the same from vv and
+ *                       A10, A11. (rw multiplies the sum, as in drizzle, not each row: a zero field then gives drizzle's bits.)
+ *   Without the slope term den is no area measure where a field stretches or compresses.
+ * Everything after that is the drizzle definition, unchanged: local coordinates, overlaps, taps, maps, records, combine, fill.
+ * An entry whose field pointer is NULL (frame 0, or any the caller leaves out) is plain drizzle arithmetic, including the
+ * host's affine footprint table. Field values are expected finite and are not checked; a non-finite value makes the
+ * coordinate non-finite, so every overlap is 0 and the entry contributes nothing at that pixel.
+ * Consequences: NULL fields, or all-zero fields, return stk_drizzle_stack's bits; at s = 1, origin 0 the displaced
+ * coordinates inside frame 0 are the mesh fold's bits; two calls return the same bits. */
+
+/* stk_drizzle_stack through the fields: its arguments and checks, plus `fields` / `step` as stk_mesh_stack takes them: n
+ * plane pointers by frame index, the planes in frames->location; those of frame 0 and of excluded frames are not read, a
+ * NULL entry means no displacement. fields == NULL, or a step that is no power of two in 8 .. 256: STK_INVALID_PARAMS, as
+ * is warp_subpixel_bits = 5. */
+stk_status stk_mesh_drizzle_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                  int32_t is_affine, double alpha, const stk_drizzle_params* drizzle,
+                                  const stk_frame_weight* per_frame_or_null, const float* const* maps_or_null,
+                                  const float* const* fields, int32_t step, stk_image_f32* out, float* den_or_null);
+/* stk_ecc_match_drizzle / stk_keypoint_match_drizzle with local alignment: the plain call, then stk_local_align's field
+ * pass on the full-size resident frames with the stats' warps, then the mesh drizzle of frame 0 (no field) and the kept
+ * frames. By definition the result equals stk_local_align + stk_mesh_drizzle_stack on the stats' warps bit for bit. 8-bit
+ * BGR(A) frames only (16-bit, f32: STK_NOT_IMPLEMENTED). Device memory is reserved before the plain call runs; a failed
+ * allocation is STK_HIP_ERROR with the byte count in stk_last_error. stk_timing.finalize_ms is the device time of the
+ * field pass plus the drizzle launch. A multi-device context runs these calls on its first device. */
+stk_status stk_ecc_match_local_aligned_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
+                                               float scale_down_width, const stk_mesh_params* mesh,
+                                               const stk_drizzle_params* drizzle, stk_image_f32* out, float* den_or_null,
+                                               stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_local_aligned_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                                    float scale_down_width, const stk_mesh_params* mesh,
+                                                    const stk_drizzle_params* drizzle, stk_image_f32* out, int32_t* dropped,
+                                                    float* den_or_null, stk_frame_stats* stats_or_null);
+
 /* ---- normalised, coverage-aware sigma-clip and quantile stacking: an EXTENSION beyond the reference -------------
  * The two rejection combines with the per-frame gain, offset and weight and the coverage of the weighted combine: frames
  * are compared after each has been mapped onto frame 0's level, and a frame that does not cover a pixel is no sample of

@@ -177,6 +177,15 @@ SIGNATURES = {
     "stk_keypoint_match_drizzle": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
                                               C.POINTER(DrizzleParams), C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p,
                                               C.POINTER(FrameStats)]),
+    "stk_mesh_drizzle_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
+                                          C.POINTER(DrizzleParams), C.POINTER(FrameWeight), C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.POINTER(ImageF32), C.c_void_p]),
+    "stk_ecc_match_local_aligned_drizzle": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float,
+                                                       C.POINTER(MeshParams), C.POINTER(DrizzleParams), C.POINTER(ImageF32), C.c_void_p,
+                                                       C.POINTER(FrameStats)]),
+    "stk_keypoint_match_local_aligned_drizzle": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                                            C.POINTER(MeshParams), C.POINTER(DrizzleParams), C.POINTER(ImageF32),
+                                                            C.POINTER(C.c_int32), C.c_void_p, C.POINTER(FrameStats)]),
     "stk_clip_stack_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_double, C.POINTER(ClipParams), C.POINTER(FrameWeight), C.c_int32, C.POINTER(ImageF32),
                                            C.c_void_p, C.c_void_p]),

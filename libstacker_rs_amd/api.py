@@ -1003,14 +1003,18 @@ class Stacker:
                                               C.cast(fp, C.c_void_p), C.cast(sp, C.c_void_p) if return_status else None))
         return (fields, status) if return_status else fields
 
-    def _fields_arg(self, m: _Marshalled, fields, step):
-        """n tightly packed gh x gw x 2 float32 planes where the frames live: (owners, pointer array)."""
+    def _fields_arg(self, m: _Marshalled, fields, step, allow_none: bool = False):
+        """n tightly packed gh x gw x 2 float32 planes where the frames live: (owners, pointer array). allow_none: an entry
+        may be None (a NULL plane: no displacement)."""
         gw, gh = mesh_grid(m.w, m.h, step) if step in (8, 16, 32, 64, 128, 256) else (None, None)
         planes = list(fields)
         if len(planes) != m.n:
             raise InvalidParams("one field per frame expected")
         keep, ptrs = [], []
         for p in planes:
+            if p is None and allow_none:
+                ptrs.append(None)
+                continue
             if m.location == DEVICE:
                 import torch
                 t = p if _is_torch(p) else torch.from_numpy(np.ascontiguousarray(np.asarray(p, np.float32)))
@@ -1187,6 +1191,76 @@ class Stacker:
         p, dp = params._c(), dz._c()
         self._check(self._lib.stk_keypoint_match_drizzle(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
                                                          C.byref(dp), C.byref(img), C.byref(dropped), dptr, stats))
+        return (dropped.value, out) + ((den,) if return_den else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+
+    # -- mesh-displaced drizzle: drizzle through local-alignment fields (extension beyond the reference) --
+    def mesh_drizzle_stack(self, files, warps, fields, step: int, drizzle: Optional["DrizzleParameters"] = None, gain=None, offset=None,
+                           weights=None, include=None, *, applied=None, maps=None, out_shape=None, is_affine=False, alpha=1.0 / 255.0,
+                           return_den: bool = False):
+        """drizzle_stack through displacement fields (stk_mesh_drizzle_stack). fields: n gh x gw x 2 float32 planes for the
+        grid of `step` (local_align's result), single entries may be None = not displaced; frame 0's is not read."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        dz = drizzle or DrizzleParameters()
+        Md, inc = self._warps_arg(warps, include, m.n)
+        rec = None if (gain is None and offset is None and weights is None and applied is None) \
+            else self._records_arg(m, gain, offset, weights, applied)
+        mkeep, mptrs = None, None
+        if maps is not None:
+            planes = list(maps)
+            if len(planes) != m.n:
+                raise InvalidParams("one weight map (or None) per frame expected")
+            some = [p for p in planes if p is not None]
+            sub = copy.copy(m)
+            sub.n = len(some)
+            mkeep, some_ptrs = self._maps_arg(sub, some) if some else ([], [])
+            it = iter(some_ptrs)
+            mptrs = (C.c_void_p * m.n)(*[None if p is None else next(it) for p in planes])
+        fkeep, fptrs = self._fields_arg(m, fields, step, allow_none=True)
+        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
+        p = dz._c()
+        self._check(self._lib.stk_mesh_drizzle_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                     None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine), float(alpha),
+                                                     C.byref(p), rec, None if mptrs is None else C.cast(mptrs, C.c_void_p),
+                                                     C.cast(fptrs, C.c_void_p), int(step), C.byref(img), dptr))
+        return (out, den) if return_den else out
+
+    def ecc_match_local_aligned_drizzle(self, files, params: EccMatchParameters, mesh: Optional["MeshParameters"] = None,
+                                        drizzle: Optional["DrizzleParameters"] = None, scale_down_width: Optional[float] = None, *,
+                                        out_shape=None, return_den: bool = False, return_stats: bool = False):
+        """ecc_match_drizzle with local alignment (stk_ecc_match_local_aligned_drizzle): every frame is drizzled through its
+        ECC warp and the displacement field measured on top of it. Returns the image[, the weight image][, the stats]."""
+        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        dz = drizzle or DrizzleParameters()
+        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
+        stats = (_ffi.FrameStats * m.n)()
+        p, mp, dp = params._c(), (mesh or MeshParameters())._c(), dz._c()
+        self._check(self._lib.stk_ecc_match_local_aligned_drizzle(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                                  C.byref(mp), C.byref(dp), C.byref(img), dptr, stats))
+        res = (out,) + ((den,) if return_den else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return res if len(res) > 1 else out
+
+    def keypoint_match_local_aligned_drizzle(self, files, params: KeyPointMatchParameters, mesh: Optional["MeshParameters"] = None,
+                                             drizzle: Optional["DrizzleParameters"] = None, scale_down_width: Optional[float] = None, *,
+                                             out_shape=None, return_den: bool = False, return_stats: bool = False):
+        """keypoint_match_drizzle with local alignment (stk_keypoint_match_local_aligned_drizzle):
+        (dropped, image[, weight image][, stats])."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        dz = drizzle or DrizzleParameters()
+        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p, mp, dp = params._c(), (mesh or MeshParameters())._c(), dz._c()
+        self._check(self._lib.stk_keypoint_match_local_aligned_drizzle(self._h, C.byref(m.c_frames), C.byref(p),
+                                                                       float(scale_down_width or 0.0), C.byref(mp), C.byref(dp),
+                                                                       C.byref(img), C.byref(dropped), dptr, stats))
         return (dropped.value, out) + ((den,) if return_den else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
 
     # -- normalised, coverage-aware rejection combines (extension beyond the reference) -----------------

@@ -220,10 +220,18 @@ stk_status local_weighted_stack_impl(stk_ctx* ctx, const stk_frames* frames, con
                                      stk_image_f32* out, float* den_out);
 // the checks of a mesh fold's step and of the fold options it runs under (mesh.cpp)
 stk_status mesh_check_fold(stk_ctx* ctx, int step);
-// uploads the fields of the table's entries (host planes into ctx->mesh) and their pointer table; frame 0 gets no field.
-// Synchronises.
+// uploads the fields of the table's entries (host planes into ctx->mesh) and their pointer table; frame 0 and an entry
+// whose plane is null get no field. Synchronises.
 stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const std::vector<int>& entry_frame, const float* const* fields,
                            int step, MeshFoldArgs* out);
+// the field pass of the whole-stack forms for a combine outside mesh.cpp (drizzle.cpp): the checks of the mesh parameters
+// and of the frames' depth; ctx->mesh reserved for frames->n entries; the pass over the n_entries entries of ctx->warpframes
+// (entry 0 = frame 0; the table is uploaded), which leaves the fold's field table in *out, synchronises and adds its device
+// time to *ms
+stk_status mesh_match_fields_check(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mp);
+stk_status mesh_match_fields_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mp);
+stk_status mesh_match_fields(stk_ctx* ctx, const stk_frames* frames, int n_entries, int is_affine, const stk_mesh_params* mp,
+                             MeshFoldArgs* out, double* ms);
 stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
                           int32_t add_reference, stk_image_f32* sum, int32_t* n_added, stk_frame_stats* stats,
                           const float* seeds, double alpha, bool allow16);

@@ -1,6 +1,8 @@
 // drizzle.cpp — drizzle integration onto a finer or larger output grid: stk_drizzle_stack, stk_ecc_match_drizzle,
-// stk_keypoint_match_drizzle (an extension beyond the reference; definition in include/stacker.h, stk_drizzle_params;
-// kernel in kernels_drizzle.hip). The frame table is the fold's (ctx->warpframes), its matrices composed here with the
+// stk_keypoint_match_drizzle, and their forms through local-alignment fields: stk_mesh_drizzle_stack,
+// stk_ecc_match_local_aligned_drizzle, stk_keypoint_match_local_aligned_drizzle (an extension beyond the reference;
+// definition in include/stacker.h, stk_drizzle_params and the block after it; kernel in kernels_drizzle.hip). The fields
+// and their pointer table live in ctx->mesh and are mesh.cpp's to place (through context.h). The frame table is the fold's (ctx->warpframes), its matrices composed here with the
 // output grid's map. ctx->local (grow-only, shared with local.cpp; one call at a time) holds, in this order: in the
 // whole-stack forms the plain call's mean (unused), then the footprint table, the per-entry records, the map pointer
 // table, a host output's staging image and den plane, and host maps' planes. Like weighted.cpp, the whole-stack forms run
@@ -92,7 +94,7 @@ void drizzle_entry(WarpFrame& wf, float* foot, const void* src, const double* M,
 stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* frames, const std::vector<const void*>& dev,
                        const std::vector<int>& entry_frame, const std::vector<const double*>& Ms, int is_affine, double alpha,
                        const stk_drizzle_params* p, const std::vector<stk_frame_weight>& coef, const float* const* maps,
-                       stk_image_f32* out, float* den_out, double* ms) {
+                       stk_image_f32* out, float* den_out, double* ms, const MeshFoldArgs* mesh = nullptr) {
     const int ne = (int)entry_frame.size(), sw = frames->width, sh = frames->height, cn = frames->channels;
     const int ow = out->width, oh = out->height;
     const size_t rb = frame_row_bytes(frames);
@@ -133,6 +135,19 @@ stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* f
     a.out = host_out ? (float*)(base + L.image) : out->data;
     a.den = den_out ? (host_out ? (float*)(base + L.den) : den_out) : nullptr;
     a.ow = ow; a.oh = oh;
+    if (mesh) {
+        // the grid's map onto frame 0, as drizzle_entry composes it
+        const double g = 1.0 / (double)p->scale;
+        a.fields = mesh->fields;
+        a.mesh_shift = 0;
+        while ((1 << a.mesh_shift) < mesh->step) a.mesh_shift++;
+        a.mesh_gw = mesh->gw; a.mesh_gh = mesh->gh;
+        a.mesh_inv = 1.0f / (float)mesh->step;
+        a.mesh_g = (float)g;
+        a.mesh_tx = (float)((0.5 * g - 0.5) + (double)p->origin_x);
+        a.mesh_ty = (float)((0.5 * g - 0.5) + (double)p->origin_y);
+        a.mesh_s = p->scale;
+    }
     HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
     HIP_TRY(launch_drizzle(a, frames->depth, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
@@ -151,9 +166,12 @@ void drizzle_unit_record(stk_frame_weight* e) {
 }
 
 // the tail of the whole-stack forms: the frames of `entry_frame` (frame 0 through the identity, the others under the
-// stats' warps), all weights 1, no maps, alpha = 1 / 255; the timing stays the plain call's but for finalize_ms
+// stats' warps), all weights 1, no maps, alpha = 1 / 255; the timing stays the plain call's but for finalize_ms. With mesh
+// parameters: the field pass over the same entries under the fold's matrices first (ctx->mesh is reserved), the drizzle
+// through its fields, and finalize_ms the sum of the two.
 stk_status drizzle_finish(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* frames, const std::vector<int>& entry_frame,
-                          const stk_frame_stats* stats, int is_affine, const stk_drizzle_params* p, stk_image_f32* out, float* den_out) {
+                          const stk_frame_stats* stats, int is_affine, const stk_drizzle_params* p, stk_image_f32* out, float* den_out,
+                          const stk_mesh_params* mp = nullptr) {
     static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     std::vector<const void*> dev;
     resident_frames(ctx, frames, dev);
@@ -162,23 +180,34 @@ stk_status drizzle_finish(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames
     std::vector<stk_frame_weight> coef(entry_frame.size());
     for (stk_frame_weight& e : coef) drizzle_unit_record(&e);
     const stk_timing keep = ctx->timing;
-    double ms = 0.0;
-    const stk_status st = drizzle_run(ctx, L, frames, dev, entry_frame, Ms, is_affine, 1.0 / 255.0, p, coef, nullptr, out, den_out, &ms);
-    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : ms;
+    double ms = 0.0, fms = 0.0;
+    stk_status st = STK_OK;
+    MeshFoldArgs mf{};
+    if (mp) {
+        std::vector<WarpFrame> wf(entry_frame.size());
+        for (size_t k = 0; k < entry_frame.size(); k++) make_warp_frame(wf[k], dev[entry_frame[k]], Ms[k], is_affine);
+        // (mesh_match_fields synchronises: `wf` outlives the copy)
+        if (!(st = warp_table_upload(ctx, wf, frame_row_bytes(frames), frames->width, frames->height, is_affine)))
+            st = mesh_match_fields(ctx, frames, (int)entry_frame.size(), is_affine, mp, &mf, &fms);
+    }
+    if (!st) st = drizzle_run(ctx, L, frames, dev, entry_frame, Ms, is_affine, 1.0 / 255.0, p, coef, nullptr, out, den_out, &ms, mp ? &mf : nullptr);
+    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : fms + ms;
     return st;
 }
 
-}  // namespace
-
-extern "C" {
-
-stk_status stk_drizzle_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
-                             double alpha, const stk_drizzle_params* p, const stk_frame_weight* per_frame, const float* const* maps,
-                             stk_image_f32* out, float* den_out) {
+// stk_drizzle_stack, and with `fields` (n planes by frame index, in frames->location) stk_mesh_drizzle_stack
+stk_status drizzle_stack_impl(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                              double alpha, const stk_drizzle_params* p, const stk_frame_weight* per_frame, const float* const* maps,
+                              bool mesh, const float* const* fields, int32_t step, stk_image_f32* out, float* den_out) {
     if (!ctx) return STK_INVALID_PARAMS;
     stk_status st = drizzle_validate(ctx, frames, false, p, out);
     if (st) return st;
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
+    if (mesh) {
+        if (!fields) return fail(ctx, STK_INVALID_PARAMS, "null fields");
+        if (step < 8 || step > 256 || (step & (step - 1)) != 0)
+            return fail(ctx, STK_INVALID_PARAMS, "mesh: step must be 8, 16, 32, 64, 128 or 256");
+    }
     const int n = frames->n, cn = frames->channels;
     std::vector<int> entry_frame;
     std::vector<stk_frame_weight> coef;
@@ -202,22 +231,29 @@ stk_status stk_drizzle_stack(stk_ctx* ctx, const stk_frames* frames, const doubl
     if ((st = drizzle_reserve(ctx, L))) return st;
     std::vector<const void*> dev;
     if ((st = resolve_frames(ctx, frames, dev))) return st;
+    MeshFoldArgs mf{};
+    if (mesh && (st = mesh_fold_table(ctx, frames, entry_frame, fields, step, &mf))) return st;
     double ms = 0.0;
-    if ((st = drizzle_run(ctx, L, frames, dev, entry_frame, Ms, is_affine != 0, alpha, p, coef, maps, out, den_out, &ms))) return st;
+    if ((st = drizzle_run(ctx, L, frames, dev, entry_frame, Ms, is_affine != 0, alpha, p, coef, maps, out, den_out, &ms, mesh ? &mf : nullptr)))
+        return st;
     ctx->timing.finalize_ms = ms;
     return STK_OK;
 }
 
-stk_status stk_ecc_match_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
-                                 const stk_drizzle_params* p, stk_image_f32* out, float* den_out, stk_frame_stats* stats) {
+// stk_ecc_match_drizzle, and with mesh parameters stk_ecc_match_local_aligned_drizzle
+stk_status ecc_match_drizzle_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                  const stk_mesh_params* mesh, const stk_drizzle_params* p, stk_image_f32* out, float* den_out,
+                                  stk_frame_stats* stats) {
     if (!ctx) return STK_INVALID_PARAMS;
     stk_status st = drizzle_validate(ctx, frames, true, p, out);
     if (st) return st;
+    if (mesh && (st = mesh_match_fields_check(ctx, frames, mesh))) return st;
     (void)hipSetDevice(ctx->device);
     const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
     const size_t pre = (size_t)w * h * cn * sizeof(float);
     const DrizzleLayout L = drizzle_layout(pre, n, w, h, out->width, out->height, cn, out->location != STK_DEVICE, 0);
     if ((st = drizzle_reserve(ctx, L))) return st;
+    if (mesh && (st = mesh_match_fields_reserve(ctx, frames, mesh))) return st;
     std::vector<stk_frame_stats> own;
     if (!stats) { own.resize(n); stats = own.data(); }
     // the plain call, on this context's own device, its mean into the head of the workspace (unused)
@@ -226,21 +262,24 @@ stk_status stk_ecc_match_drizzle(stk_ctx* ctx, const stk_frames* frames, const s
     // every frame is a sample: frame 0 through the identity, frame i through its warp (as in stk_ecc_match_weighted)
     std::vector<int> entry_frame(n);
     for (int i = 0; i < n; i++) entry_frame[i] = i;
-    return drizzle_finish(ctx, L, frames, entry_frame, stats, params->motion_type != STK_MOTION_HOMOGRAPHY, p, out, den_out);
+    return drizzle_finish(ctx, L, frames, entry_frame, stats, params->motion_type != STK_MOTION_HOMOGRAPHY, p, out, den_out, mesh);
 }
 
-stk_status stk_keypoint_match_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,
-                                      const stk_drizzle_params* p, stk_image_f32* out, int32_t* dropped, float* den_out,
-                                      stk_frame_stats* stats) {
+// stk_keypoint_match_drizzle, and with mesh parameters stk_keypoint_match_local_aligned_drizzle
+stk_status keypoint_match_drizzle_impl(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,
+                                       const stk_mesh_params* mesh, const stk_drizzle_params* p, stk_image_f32* out, int32_t* dropped,
+                                       float* den_out, stk_frame_stats* stats) {
     if (!ctx) return STK_INVALID_PARAMS;
     stk_status st = drizzle_validate(ctx, frames, true, p, out);
     if (st) return st;
     if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
+    if (mesh && (st = mesh_match_fields_check(ctx, frames, mesh))) return st;
     (void)hipSetDevice(ctx->device);
     const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
     const size_t pre = (size_t)w * h * cn * sizeof(float);
     const DrizzleLayout L = drizzle_layout(pre, n, w, h, out->width, out->height, cn, out->location != STK_DEVICE, 0);
     if ((st = drizzle_reserve(ctx, L))) return st;
+    if (mesh && (st = mesh_match_fields_reserve(ctx, frames, mesh))) return st;
     std::vector<stk_frame_stats> own;
     if (!stats) { own.resize(n); stats = own.data(); }
     stk_image_f32 mimg{ctx->local.as<float>(), w, h, cn, STK_DEVICE, 0};
@@ -248,7 +287,50 @@ stk_status stk_keypoint_match_drizzle(stk_ctx* ctx, const stk_frames* frames, co
     // the samples: frame 0 through the identity and the frames with a homography (status 0), in stack order
     std::vector<int> entry_frame{0};
     for (int i = 1; i < n; i++) if (stats[i].status == 0) entry_frame.push_back(i);
-    return drizzle_finish(ctx, L, frames, entry_frame, stats, 0, p, out, den_out);
+    return drizzle_finish(ctx, L, frames, entry_frame, stats, 0, p, out, den_out, mesh);
+}
+
+}  // namespace
+
+extern "C" {
+
+stk_status stk_drizzle_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                             double alpha, const stk_drizzle_params* p, const stk_frame_weight* per_frame, const float* const* maps,
+                             stk_image_f32* out, float* den_out) {
+    return drizzle_stack_impl(ctx, frames, M, include, is_affine, alpha, p, per_frame, maps, false, nullptr, 0, out, den_out);
+}
+
+stk_status stk_mesh_drizzle_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                                  double alpha, const stk_drizzle_params* p, const stk_frame_weight* per_frame, const float* const* maps,
+                                  const float* const* fields, int32_t step, stk_image_f32* out, float* den_out) {
+    return drizzle_stack_impl(ctx, frames, M, include, is_affine, alpha, p, per_frame, maps, true, fields, step, out, den_out);
+}
+
+stk_status stk_ecc_match_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                 const stk_drizzle_params* p, stk_image_f32* out, float* den_out, stk_frame_stats* stats) {
+    return ecc_match_drizzle_impl(ctx, frames, params, scale_down_width, nullptr, p, out, den_out, stats);
+}
+
+stk_status stk_keypoint_match_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,
+                                      const stk_drizzle_params* p, stk_image_f32* out, int32_t* dropped, float* den_out,
+                                      stk_frame_stats* stats) {
+    return keypoint_match_drizzle_impl(ctx, frames, params, scale_down_width, nullptr, p, out, dropped, den_out, stats);
+}
+
+stk_status stk_ecc_match_local_aligned_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
+                                               float scale_down_width, const stk_mesh_params* mesh, const stk_drizzle_params* p,
+                                               stk_image_f32* out, float* den_out, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    if (!mesh) return fail(ctx, STK_INVALID_PARAMS, "null mesh parameters");
+    return ecc_match_drizzle_impl(ctx, frames, params, scale_down_width, mesh, p, out, den_out, stats);
+}
+
+stk_status stk_keypoint_match_local_aligned_drizzle(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                                    float scale_down_width, const stk_mesh_params* mesh, const stk_drizzle_params* p,
+                                                    stk_image_f32* out, int32_t* dropped, float* den_out, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    if (!mesh) return fail(ctx, STK_INVALID_PARAMS, "null mesh parameters");
+    return keypoint_match_drizzle_impl(ctx, frames, params, scale_down_width, mesh, p, out, dropped, den_out, stats);
 }
 
 }  // extern "C"

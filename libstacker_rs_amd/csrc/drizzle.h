@@ -20,6 +20,12 @@ struct DrizzleArgs {
     float* out;                      // ow x oh x cn, tightly packed
     float* den;                      // ow x oh, or null
     int ow, oh;
+    // the mesh form (stk_mesh_drizzle_stack); fields == null: the plain kernels
+    const float* const* fields;      // per entry a gh x gw x 2 f32 field on the grid of 1 << mesh_shift over sw x sh, or null = not displaced
+    int mesh_shift, mesh_gw, mesh_gh;
+    float mesh_inv;                  // 1.0f / step
+    float mesh_g, mesh_tx, mesh_ty;  // the output grid's map onto frame 0, (float) of the host's g, tx, ty
+    float mesh_s;                    // the scale
 };
 
 hipError_t launch_drizzle(const DrizzleArgs& a, int depth, hipStream_t s);

@@ -139,6 +139,28 @@ stk_status mesh_match_check(stk_ctx* ctx, const stk_frames* frames, const stk_me
     return weighted_check_out(ctx, out, frames);
 }
 
+// The field pass of a whole-stack form over the ne entries of ctx->warpframes (entry 0 = frame 0; the table is uploaded):
+// the planes of entries 1 .. ne - 1 into L.fields, then the fold's pointer table (entry 0: null) at L.tptrs. Synchronises;
+// adds the pass's device time to *ms.
+stk_status mesh_entry_fields(stk_ctx* ctx, const MeshLayout& L, int ne, int w, int h, int cn, size_t rb, int is_affine,
+                             const stk_mesh_params* mp, MeshFoldArgs* out, double* ms) {
+    int gw, gh;
+    mesh_grid_of(w, h, mp->step, &gw, &gh);
+    char* base = ctx->mesh.as<char>();
+    std::vector<float*> fdev(ne, nullptr);
+    std::vector<int32_t*> sdev(ne, nullptr);
+    for (int k = 1; k < ne; k++) {
+        fdev[k] = (float*)(base + L.fields + (size_t)(k - 1) * L.fplane);
+        sdev[k] = (int32_t*)(base + L.status + (size_t)(k - 1) * L.splane);
+    }
+    stk_status st = mesh_align_entries(ctx, L, ne, w, h, cn, rb, is_affine, mp, gw, gh, fdev, sdev, ms);
+    if (st) return st;
+    HIP_TRY(hipMemcpyAsync(base + L.tptrs, fdev.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // `fdev` leaves scope
+    *out = MeshFoldArgs{(const float* const*)(base + L.tptrs), mp->step, gw, gh};
+    return STK_OK;
+}
+
 // the tail of the whole-stack forms: `entry_frame[k]` is the frame index of table entry k (entry 0 = frame 0), `dev` the
 // resident full-size frames by frame index; the frame table is uploaded. Field pass, then the mesh mean fold, or the map
 // pass and the mesh local-weighted fold with unit records.
@@ -148,22 +170,12 @@ stk_status mesh_finish(stk_ctx* ctx, const MeshLayout& L, const stk_frames* fram
     const int w = frames->width, h = frames->height, cn = frames->channels;
     const int ne = (int)entry_frame.size();
     const double alpha = 1.0 / 255.0;
-    int gw, gh;
-    mesh_grid_of(w, h, mp->step, &gw, &gh);
     char* base = ctx->mesh.as<char>();
     double ms = 0.0;
-    std::vector<float*> fdev(ne, nullptr);
-    std::vector<int32_t*> sdev(ne, nullptr);
-    for (int k = 1; k < ne; k++) {
-        fdev[k] = (float*)(base + L.fields + (size_t)(k - 1) * L.fplane);
-        sdev[k] = (int32_t*)(base + L.status + (size_t)(k - 1) * L.splane);
-    }
-    stk_status st = mesh_align_entries(ctx, L, ne, w, h, cn, rb, is_affine, mp, gw, gh, fdev, sdev, &ms);
+    MeshFoldArgs mf{};
+    stk_status st = mesh_entry_fields(ctx, L, ne, w, h, cn, rb, is_affine, mp, &mf, &ms);
     if (st) return st;
-    HIP_TRY(hipMemcpyAsync(base + L.tptrs, fdev.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
-    const MeshFoldArgs mf{(const float* const*)(base + L.tptrs), mp->step, gw, gh};
     if (!lp) {
-        // (mesh_mean_fold synchronises: `fdev` outlives the copy)
         st = mesh_mean_fold(ctx, ne, 8, w, h, cn, rb, alpha, border_mode, border_value, is_affine, mf, (float*)(base + L.image), out, &ms);
     } else {
         const LocalLayout LL = local_layout((size_t)ne, ne, w, h, cn, (size_t)ne);
@@ -220,6 +232,28 @@ stk_status mesh_check_fold(stk_ctx* ctx, int step) {
     return STK_OK;
 }
 
+stk_status mesh_match_fields_check(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mp) {
+    stk_status st = mesh_validate(ctx, mp);
+    if (st) return st;
+    return mesh_check_depth(ctx, frames);
+}
+
+stk_status mesh_match_fields_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mp) {
+    const size_t n = (size_t)frames->n;
+    int gw, gh;
+    mesh_grid_of(frames->width, frames->height, mp->step, &gw, &gh);
+    return mesh_reserve(ctx, mesh_layout(n, n, n, n, gw, gh, 0));
+}
+
+stk_status mesh_match_fields(stk_ctx* ctx, const stk_frames* frames, int n_entries, int is_affine, const stk_mesh_params* mp,
+                             MeshFoldArgs* out, double* ms) {
+    const size_t n = (size_t)frames->n;
+    int gw, gh;
+    mesh_grid_of(frames->width, frames->height, mp->step, &gw, &gh);
+    return mesh_entry_fields(ctx, mesh_layout(n, n, n, n, gw, gh, 0), n_entries, frames->width, frames->height, frames->channels,
+                             frame_row_bytes(frames), is_affine, mp, out, ms);
+}
+
 stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const std::vector<int>& entry_frame, const float* const* fields,
                            int step, MeshFoldArgs* out) {
     const int ne = (int)entry_frame.size();
@@ -233,7 +267,7 @@ stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const std::ve
     std::vector<const float*> ptr(ne, nullptr);
     for (int k = 0; k < ne; k++) {
         const int i = entry_frame[k];
-        if (i == 0) continue;                              // frame 0 is the grid's own frame
+        if (i == 0 || !fields[i]) continue;                // frame 0 is the grid's own frame; a null plane: not displaced
         if (host) {
             float* d = (float*)(base + L.fields + (size_t)k * L.fplane);
             HIP_TRY(hipMemcpyAsync(d, fields[i], (size_t)gw * gh * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
