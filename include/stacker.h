@@ -820,6 +820,101 @@ stk_status stk_keypoint_match_local_aligned_drizzle(stk_ctx* ctx, const stk_fram
                                                     const stk_drizzle_params* drizzle, stk_image_f32* out, int32_t* dropped,
                                                     float* den_or_null, stk_frame_stats* stats_or_null);
 
+/* ---- blot-and-compare rejection maps for drizzle: an EXTENSION beyond the reference ------------------------------
+ * Drizzle has no rejection of its own: a trail, a cosmic-ray hit or a hot pixel of one frame goes straight into num / den.
+ * This pass makes the per-frame masks that keep them out (Fruchter & Hook's `blot` and `driz_cr`): a clean image on frame
+ * 0's grid (a robust combine, e.g. stk_quantile_stack_weighted at 0.5) is resampled ("blotted") into each frame's own pixel
+ * grid, the frame is compared with that model under a tolerance that grows with the model's local gradient (an undersampled
+ * frame legitimately differs from an interpolated model at edges), and the failures, grown by one pixel under a tighter
+ * tolerance, become a sw x sh f32 plane per frame that stk_drizzle_stack, stk_mesh_drizzle_stack and
+ * stk_local_weighted_stack take as `maps`.
+ * All arithmetic is f32, each operation rounded on its own, no contraction except where fma is written; sqrt is correctly
+ * rounded; fmaxf is C's. sw x sh is the frames' geometry and the clean image's (frame 0's grid is the destination grid), cn
+ * the channel count (all cn channels are judged). C is the clean image, sh x sw x cn f32, tightly packed, at the level of
+ * normalised samples; cnt an optional sh x sw int32 plane, exactly what stk_quantile_stack_weighted writes to `counts`.
+ * For an included frame i with forward matrix M_i and record (g, o) (per_frame_or_null; NULL = 1, 0), for EVERY lattice
+ * point (x, y), integer, also outside the frame:
+ * Blot coordinate. (X, Y), finite, ix, iy, ax, ay are exactly the fold's under warp_subpixel_bits = 0 at ((float)x, (float)y)
+ *   with the matrix F_i: the nine doubles of the FORWARD matrix cast to f32, NOT inverted (the forward map takes frame-i
+ *   pixels to frame-0 coordinates). is_affine selects the division as in the fold. warp_subpixel_bits = 5:
+ *   STK_INVALID_PARAMS, as for drizzle. warp_interpolation is ignored: the model is always bilinear.
+ * Valid. valid(x, y) iff finite && ix >= 0 && ix + 1 <= sw - 1 && iy >= 0 && iy + 1 <= sh - 1 and, with cnt, cnt >= min_count
+ *   at all four taps. Only valid points read C or cnt: every address is inside by construction.
+ * Model. t0 = fma(ax, C01 - C00, C00);  t1 = fma(ax, C11 - C10, C10);  B_c = fma(ay, t1 - t0, t0)    (the fold's lerp chain;
+ *   C00 = C[iy][ix][c], C01 = C[iy][ix + 1][c], C10 = C[iy + 1][ix][c], C11 = C[iy + 1][ix + 1][c]).
+ * Gradient. D_c(x, y) = the maximum of |B_c(n) - B_c(x, y)| over those of the four neighbours n = (x-1, y), (x+1, y),
+ *   (x, y-1), (x, y+1), in that order, that are valid; D_c starts from 0 (no valid neighbour: 0), D_c = fmaxf(D_c, |..|). A
+ *   neighbour may lie outside the frame's pixel grid: B is a function of the lattice point, not of the frame.
+ * Sample. u_c = ((float)src[y][x][c] * alpha) * g_c + o_c.
+ * Noise. sigma_c = sqrt(rn * rn + pg * fmaxf(B_c, 0)), rn = read_noise, pg = poisson_gain, both in the units of the samples
+ *   after alpha.
+ * Judged. judged(x, y) iff valid && 0 <= x < sw && 0 <= y < sh and, with maps_in and a non-NULL entry, maps_in[i][y][x] > 0.
+ * First flag. e_c = |u_c - B_c|;  f1 = judged && any c with e_c > scale1 * D_c + snr1 * sigma_c (the products and the sum
+ *   each rounded). A NaN makes the comparison false: the pixel is kept.
+ * Grow. f2 = judged && (any f1 in the 3 x 3 around (x, y), itself included) && any c with e_c > scale2 * D_c + snr2 * sigma_c.
+ * Result. rej = f1 || f2;  maps_out[i][y][x] = rej ? 0 : (maps_in entry ? its value : 1.0f). An unjudged pixel keeps its
+ *   input value (or 1): what cannot be compared is not rejected. rejected[i] = the number of pixels with rej,
+ *   judged_count[i] = the number judged: int64, host memory, optional, 0 for excluded frames; exact integers, so any
+ *   reduction order gives the same values. Frame 0 is processed like every other frame: a trail in the reference is
+ *   rejected too. Planes of excluded frames are not written. maps_out[i] may BE maps_in[i] (in place; the definition reads a
+ *   pixel's own input value only, the engine works from a copy of such a plane); planes that overlap in any other way are
+ *   not supported.
+ * Consequences. An identity matrix with C equal to the frame rejects nothing. An integer translation blots exactly
+ *   (ax = ay = 0): B is C shifted. On a constant C the gradient is 0 and the test is |u - C| > snr * rn (pg = 0). The
+ *   one-pixel ring of frame-0 coverage (ix + 1 > sw - 1) is never judged; on a 1 x 1 stack nothing is. Two calls return the
+ *   same bits.
+ * Validation, on the host before any launch; anything else is STK_INVALID_PARAMS with a message: snr1, snr2 finite and > 0;
+ * scale1, scale2, read_noise, poisson_gain finite and >= 0 (read_noise = poisson_gain = 0 is allowed: then only the
+ * gradient term tolerates anything); min_count >= 0; reserved = 0; gains and offsets finite (the records are checked as
+ * stk_weighted_stack checks them; the weights themselves are not used). */
+typedef struct {
+    float   snr1, snr2;          /* > 0, finite; astrodrizzle's defaults are 4, 3 */
+    float   scale1, scale2;      /* >= 0, finite; defaults 1.2, 0.7 */
+    float   read_noise;          /* >= 0, finite */
+    float   poisson_gain;        /* >= 0, finite */
+    int32_t min_count;           /* >= 0; with a counts plane, a clean pixel with fewer samples judges nothing; 3 recommended */
+    int32_t reserved;            /* 0 */
+} stk_reject_params;
+
+/* The pass over caller-held warps. M, include_or_null, is_affine, alpha: as in stk_drizzle_stack. Any depth, 1 / 3 / 4
+ * channels, any row stride. `clean`, clean_counts_or_null, the planes of maps_in_or_null (n pointers by frame index, single
+ * entries may be NULL = all ones) and of maps_out (n pointers by frame index; those of included frames must not be NULL)
+ * are in frames->location. rejected_or_null, judged_or_null: n int64 each, host memory. stk_timing.finalize_ms is the device
+ * time of the pass. A multi-device context runs it on its first device. */
+stk_status stk_reject_maps(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                           int32_t is_affine, double alpha, const stk_frame_weight* per_frame_or_null,
+                           const float* clean, const int32_t* clean_counts_or_null, const stk_reject_params* reject,
+                           const float* const* maps_in_or_null, float* const* maps_out,
+                           int64_t* rejected_or_null, int64_t* judged_or_null);
+/* stk_ecc_match_drizzle / stk_keypoint_match_drizzle with rejection. In this order: (1) the plain call: its stats, warps,
+ * `dropped` and errors are the result's; (2) the records exactly as stk_ecc_match_weighted / stk_keypoint_match_weighted
+ * make them (the moments pass and the estimator under weight->normalize, the caller's weights_or_null by frame index);
+ * (3) the clean image: stk_quantile_stack_weighted at quantile = 0.5, coverage = 1, BORDER_CONSTANT 0, alpha = 1 / 255 with
+ * those records over frame 0 (identity) and the kept frames, with its `counts`; (4) stk_reject_maps with those counts and
+ * reject->min_count, the records, alpha = 1 / 255 and no input maps; (5) stk_drizzle_stack with the records and the maps. By
+ * definition the result equals those parts called one after another on the stats' warps, bit for bit: the image, den, the
+ * maps and the counts. weight->coverage must be 1 (and, for the keypoint form, the parameters' border BORDER_CONSTANT 0, as
+ * stk_keypoint_match_weighted asks under coverage); anything else is STK_INVALID_PARAMS. maps_or_null: n planes by frame
+ * index in frames->location, entries may be NULL, receiving the maps the drizzle used (a dropped frame's plane is not
+ * written). rejected_or_null: n int64, host. applied_or_null: the records, as stk_ecc_match_weighted returns them. 8-bit
+ * BGR(A) frames only, as for the other whole-stack drizzle forms. Device memory is reserved before the plain call runs
+ * (n x sw x sh x 4 bytes of maps, the clean image and its counts, plus what the median and the drizzle need); a failed
+ * allocation is STK_HIP_ERROR with the byte count in stk_last_error. stk_timing.finalize_ms is the sum of the device times
+ * of moments + median + reject + drizzle; warp_ms etc. stay the plain call's. A multi-device context runs these calls on
+ * its first device. */
+stk_status stk_ecc_match_drizzle_rejected(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
+                                          float scale_down_width, const stk_drizzle_params* drizzle,
+                                          const stk_weight_params* weight, const float* weights_or_null,
+                                          const stk_reject_params* reject, stk_image_f32* out, float* den_or_null,
+                                          float* const* maps_or_null, int64_t* rejected_or_null,
+                                          stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_drizzle_rejected(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                               float scale_down_width, const stk_drizzle_params* drizzle,
+                                               const stk_weight_params* weight, const float* weights_or_null,
+                                               const stk_reject_params* reject, stk_image_f32* out, int32_t* dropped,
+                                               float* den_or_null, float* const* maps_or_null, int64_t* rejected_or_null,
+                                               stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
+
 /* ---- normalised, coverage-aware sigma-clip and quantile stacking: an EXTENSION beyond the reference -------------
  * The two rejection combines with the per-frame gain, offset and weight and the coverage of the weighted combine: frames
  * are compared after each has been mapped onto frame 0's level, and a frame that does not cover a pixel is no sample of

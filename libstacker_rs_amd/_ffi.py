@@ -82,6 +82,11 @@ class DrizzleParams(C.Structure):
                 ("fill", C.c_float), ("reserved", C.c_int32)]
 
 
+class RejectParams(C.Structure):
+    _fields_ = [("snr1", C.c_float), ("snr2", C.c_float), ("scale1", C.c_float), ("scale2", C.c_float),
+                ("read_noise", C.c_float), ("poisson_gain", C.c_float), ("min_count", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SelectParams(C.Structure):
     _fields_ = [("metric", C.c_int32), ("ksize", C.c_int32), ("drop_worst", C.c_int32), ("keep_fraction", C.c_float),
                 ("weight_mode", C.c_int32), ("reserved", C.c_int32)]
@@ -186,6 +191,16 @@ SIGNATURES = {
     "stk_keypoint_match_local_aligned_drizzle": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
                                                             C.POINTER(MeshParams), C.POINTER(DrizzleParams), C.POINTER(ImageF32),
                                                             C.POINTER(C.c_int32), C.c_void_p, C.POINTER(FrameStats)]),
+    "stk_reject_maps": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.POINTER(FrameWeight),
+                                   C.c_void_p, C.c_void_p, C.POINTER(RejectParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stk_ecc_match_drizzle_rejected": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float,
+                                                  C.POINTER(DrizzleParams), C.POINTER(WeightParams), C.c_void_p,
+                                                  C.POINTER(RejectParams), C.POINTER(ImageF32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
+    "stk_keypoint_match_drizzle_rejected": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                                       C.POINTER(DrizzleParams), C.POINTER(WeightParams), C.c_void_p,
+                                                       C.POINTER(RejectParams), C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
     "stk_clip_stack_weighted": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_double, C.POINTER(ClipParams), C.POINTER(FrameWeight), C.c_int32, C.POINTER(ImageF32),
                                            C.c_void_p, C.c_void_p]),

@@ -211,6 +211,25 @@ class DrizzleParameters:          # extension beyond the reference: include/stac
         return int(np.ceil(float(self.scale) * height)), int(np.ceil(float(self.scale) * width))
 
 
+@dataclass
+class RejectParameters:           # extension beyond the reference: include/stacker.h, stk_reject_params
+    """Blot-and-compare rejection maps: a frame pixel is rejected where it differs from the blotted clean image by more than
+    `scale1` x the model's local gradient + `snr1` x sigma, or, next to such a pixel, by more than `scale2` x gradient +
+    `snr2` x sigma; sigma = sqrt(read_noise^2 + poisson_gain x model), in the units of the samples after alpha. With a
+    counts plane a clean pixel made from fewer than `min_count` samples judges nothing."""
+    snr1: float = 4.0
+    snr2: float = 3.0
+    scale1: float = 1.2
+    scale2: float = 0.7
+    read_noise: float = 2.0 / 255.0
+    poisson_gain: float = 0.0
+    min_count: int = 3
+
+    def _c(self) -> _ffi.RejectParams:
+        return _ffi.RejectParams(float(self.snr1), float(self.snr2), float(self.scale1), float(self.scale2), float(self.read_noise),
+                                 float(self.poisson_gain), int(self.min_count), 0)
+
+
 def mesh_grid(width: int, height: int, step: int):
     """(gw, gh): the node grid of a width x height destination at spacing `step` (stk_mesh_grid)."""
     gw, gh = C.c_int32(0), C.c_int32(0)
@@ -1262,6 +1281,135 @@ class Stacker:
                                                                        float(scale_down_width or 0.0), C.byref(mp), C.byref(dp),
                                                                        C.byref(img), C.byref(dropped), dptr, stats))
         return (dropped.value, out) + ((den,) if return_den else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+
+    # -- blot-and-compare rejection maps for drizzle (extension beyond the reference) ---------------------
+    def _array_arg(self, m: _Marshalled, x, dtype, shape, what: str):
+        """`x` as a contiguous array of `dtype` and `shape` where the frames live: (owner, address). An array that is
+        already that is used as it is, so that a caller's buffer can be written in place."""
+        if m.location == DEVICE:
+            import torch
+            tdt = torch.float32 if dtype == np.float32 else torch.int32
+            t = x if _is_torch(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype)))
+            t = t.to(device=m.torch_device, dtype=tdt).contiguous()
+            if tuple(t.shape) != tuple(shape):
+                raise InvalidParams(f"{what}: shape {tuple(shape)} expected")
+            return t, t.data_ptr()
+        a = np.ascontiguousarray(np.asarray(x.cpu().numpy() if _is_torch(x) else x, dtype))
+        if a.shape != tuple(shape):
+            raise InvalidParams(f"{what}: shape {tuple(shape)} expected")
+        return a, a.ctypes.data
+
+    def _map_planes(self, m: _Marshalled):
+        """n x H x W float32 ones where the frames live."""
+        if m.location == DEVICE:
+            import torch
+            return torch.ones((m.n, m.h, m.w), dtype=torch.float32, device=m.torch_device)
+        return np.ones((m.n, m.h, m.w), np.float32)
+
+    def reject_maps(self, files, warps, clean, reject: Optional["RejectParameters"] = None, counts=None, gain=None, offset=None,
+                    include=None, *, applied=None, maps=None, out=None, is_affine=False, alpha=1.0 / 255.0,
+                    return_counts: bool = False):
+        """Blot-and-compare rejection maps over caller-held warps (stk_reject_maps). clean: the H x W x C float32 clean image
+        on frame 0's grid (quantile_stack_weighted at 0.5); counts: its H x W int32 participation counts, or None; gain,
+        offset, applied: as in weighted_stack (None = 1 / 0); maps: None, or one H x W float32 input plane per frame (an
+        n x H x W array, or a list whose entries may be None = all ones). out: None, or an n x H x W float32 array where the
+        frames live to write into; it may be `maps` itself (in place). Returns the n x H x W maps (0 = rejected, else the
+        input value or 1; an excluded frame's plane is left as it is, all ones in a fresh array), with return_counts also
+        the per-frame numbers of rejected and of judged pixels (int64)."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        rp = (reject or RejectParameters())._c()
+        Md, inc = self._warps_arg(warps, include, m.n)
+        rec = None if (gain is None and offset is None and applied is None) else self._records_arg(m, gain, offset, None, applied)
+        ckeep, cptr = self._array_arg(m, clean, np.float32, (m.h, m.w, m.c), "clean image")
+        nkeep, nptr = (None, None) if counts is None else self._array_arg(m, counts, np.int32, (m.h, m.w), "counts")
+        plane = m.h * m.w * 4
+        res = self._map_planes(m) if out is None else out
+        okeep, optr = self._array_arg(m, res, np.float32, (m.n, m.h, m.w), "out")
+        if out is not None and okeep is not out:
+            raise InvalidParams("out: a contiguous n x H x W float32 array where the frames live expected")
+        optrs = (C.c_void_p * m.n)(*[optr + i * plane for i in range(m.n)])
+        ikeep, iptrs = [], None
+        if maps is not None:
+            if maps is out or not isinstance(maps, (list, tuple)):
+                k, base = self._array_arg(m, maps, np.float32, (m.n, m.h, m.w), "maps")
+                ikeep.append(k)
+                addr = [base + i * plane for i in range(m.n)]
+            else:
+                if len(maps) != m.n:
+                    raise InvalidParams("one input map (or None) per frame expected")
+                addr = []
+                for p in maps:
+                    if p is None:
+                        addr.append(None)
+                        continue
+                    k, a = self._array_arg(m, p, np.float32, (m.h, m.w), "maps")
+                    ikeep.append(k)
+                    addr.append(a)
+            iptrs = (C.c_void_p * m.n)(*addr)
+        rej = np.zeros(m.n, np.int64)
+        jud = np.zeros(m.n, np.int64)
+        self._check(self._lib.stk_reject_maps(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                              None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine), float(alpha), rec,
+                                              C.c_void_p(cptr), None if nptr is None else C.c_void_p(nptr), C.byref(rp),
+                                              None if iptrs is None else C.cast(iptrs, C.c_void_p), C.cast(optrs, C.c_void_p),
+                                              C.c_void_p(rej.ctypes.data), C.c_void_p(jud.ctypes.data)))
+        return (res, rej, jud) if return_counts else res
+
+    def _drizzle_rejected(self, kind, files, params, drizzle, reject, weight, weights, scale_down_width, out_shape, return_den,
+                          return_maps, return_rejected, return_applied, return_stats):
+        if kind == "ecc" and isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        dz = drizzle or DrizzleParameters()
+        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
+        maps, mptrs = None, None
+        if return_maps:
+            maps = self._map_planes(m)
+            base = maps.data_ptr() if m.location == DEVICE else maps.ctypes.data
+            mptrs = C.cast((C.c_void_p * m.n)(*[base + i * m.h * m.w * 4 for i in range(m.n)]), C.c_void_p)
+        rej = np.zeros(m.n, np.int64)
+        wkeep, wptr = self._weights_arg(weights, m.n)
+        applied = (_ffi.FrameWeight * m.n)()
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p, dp, wp, rp = params._c(), dz._c(), (weight or WeightParameters())._c(), (reject or RejectParameters())._c()
+        fn = getattr(self._lib, f"stk_{kind}_match_drizzle_rejected")
+        args = [self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(dp), C.byref(wp), wptr, C.byref(rp),
+                C.byref(img)]
+        if kind == "keypoint":
+            args.append(C.byref(dropped))
+        self._check(fn(*args, dptr, mptrs, C.c_void_p(rej.ctypes.data), applied, stats))
+        res = ((dropped.value,) if kind == "keypoint" else ()) + (out,) + ((den,) if return_den else ()) \
+            + ((maps,) if return_maps else ()) + ((rej,) if return_rejected else ()) \
+            + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return res if len(res) > 1 else out
+
+    def ecc_match_drizzle_rejected(self, files, params: EccMatchParameters, drizzle: Optional["DrizzleParameters"] = None,
+                                   reject: Optional["RejectParameters"] = None, weight: Optional["WeightParameters"] = None,
+                                   weights=None, scale_down_width: Optional[float] = None, *, out_shape=None, return_den: bool = False,
+                                   return_maps: bool = False, return_rejected: bool = False, return_applied: bool = False,
+                                   return_stats: bool = False):
+        """ecc_match_drizzle with blot-and-compare rejection (stk_ecc_match_drizzle_rejected): aligned as ecc_match aligns,
+        the records of ecc_match_weighted, the coverage-aware median as the clean image, the rejection maps against it, then
+        the drizzle with the records and the maps. weight.coverage must be True. Returns the image[, the weight image]
+        [, the n x H x W maps the drizzle used][, the per-frame numbers of rejected pixels][, the records][, the stats]."""
+        return self._drizzle_rejected("ecc", files, params, drizzle, reject, weight, weights, scale_down_width, out_shape, return_den,
+                                      return_maps, return_rejected, return_applied, return_stats)
+
+    def keypoint_match_drizzle_rejected(self, files, params: KeyPointMatchParameters, drizzle: Optional["DrizzleParameters"] = None,
+                                        reject: Optional["RejectParameters"] = None, weight: Optional["WeightParameters"] = None,
+                                        weights=None, scale_down_width: Optional[float] = None, *, out_shape=None,
+                                        return_den: bool = False, return_maps: bool = False, return_rejected: bool = False,
+                                        return_applied: bool = False, return_stats: bool = False):
+        """keypoint_match_drizzle with blot-and-compare rejection (stk_keypoint_match_drizzle_rejected): (dropped, image
+        [, weight image][, maps][, rejected][, applied][, stats]). A dropped frame is no sample: its map stays all ones and
+        its count 0."""
+        return self._drizzle_rejected("keypoint", files, params, drizzle, reject, weight, weights, scale_down_width, out_shape,
+                                      return_den, return_maps, return_rejected, return_applied, return_stats)
 
     # -- normalised, coverage-aware rejection combines (extension beyond the reference) -----------------
     def _pixel_counts_image(self, m: _Marshalled):

@@ -95,6 +95,7 @@ struct stk_ctx {
     DevBuf quantile;              // quantile combines (quantile.cpp): a w x h x cn f32 image, then the band of samples
     DevBuf local;                 // per-pixel weights (local.cpp): pointer tables, per-entry table, image, den plane, the entries' map planes
     DevBuf mesh;                  // local alignment (mesh.cpp): pointer tables, field and status planes, fill scratch, a w x h x cn f32 image
+    DevBuf reject;                // rejection maps (reject.cpp): entry table, counters, clean image, counts, map planes
     DevBuf quality;               // whole-stack sharpness (quality.cpp): frame pointers, per-frame records, tile partials
     stk::KeypointWorkspace* kp = nullptr;
     stk::geom::HgWorkspace* hg = nullptr;   // findHomography batch workspace (homography.cpp)
@@ -232,6 +233,26 @@ stk_status mesh_match_fields_check(stk_ctx* ctx, const stk_frames* frames, const
 stk_status mesh_match_fields_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mp);
 stk_status mesh_match_fields(stk_ctx* ctx, const stk_frames* frames, int n_entries, int is_affine, const stk_mesh_params* mp,
                              MeshFoldArgs* out, double* ms);
+// rejection maps (reject.cpp) and the pieces of the combines that the rejected drizzle (drizzle.cpp) is built from
+struct RejectLayout {
+    size_t entries, tallies, clean, counts, planes, plane, total;    // byte offsets into ctx->reject; plane: bytes of one map plane
+};
+RejectLayout reject_layout(int n_entries, int sw, int sh, int cn, bool clean, bool counts, size_t n_planes);
+stk_status reject_reserve(stk_ctx* ctx, const RejectLayout& L);
+stk_status reject_validate(stk_ctx* ctx, const stk_reject_params* p);
+stk_status reject_run(stk_ctx* ctx, const RejectLayout& L, const stk_frames* frames, const std::vector<const void*>& dev,
+                      const std::vector<int>& entry_frame, const std::vector<const double*>& Ms, int is_affine, double alpha,
+                      const std::vector<stk_frame_weight>& coef, const float* clean, const int32_t* counts,
+                      const stk_reject_params* p, const std::vector<const float*>& in, const std::vector<float*>& out,
+                      int64_t* rejected, int64_t* judged, double* ms);
+// after a plain whole-stack call (robust.cpp): the frame table of frame 0 and the kept frames into ctx->warpframes and the
+// records as stk_*_match_weighted makes them; then the coverage-aware median (quantile 0.5, coverage 1, BORDER_CONSTANT 0,
+// alpha 1 / 255) of that table with its counts, both device memory. Each adds its device time to *ms.
+stk_status robust_match_records(stk_ctx* ctx, const stk_frames* frames, const stk_frame_stats* stats, bool keypoint, int border_mode,
+                                const double* border_value, int is_affine, const stk_weight_params* weight, const float* weights,
+                                std::vector<int>& entry_frame, std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms);
+stk_status robust_match_median(stk_ctx* ctx, const stk_frames* frames, const std::vector<stk_frame_weight>& coef, int is_affine,
+                               float* clean, int32_t* counts, double* ms);
 stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
                           int32_t add_reference, stk_image_f32* sum, int32_t* n_added, stk_frame_stats* stats,
                           const float* seeds, double alpha, bool allow16);

@@ -1,6 +1,7 @@
 // drizzle.cpp — drizzle integration onto a finer or larger output grid: stk_drizzle_stack, stk_ecc_match_drizzle,
-// stk_keypoint_match_drizzle, and their forms through local-alignment fields: stk_mesh_drizzle_stack,
-// stk_ecc_match_local_aligned_drizzle, stk_keypoint_match_local_aligned_drizzle (an extension beyond the reference;
+// stk_keypoint_match_drizzle, their forms through local-alignment fields: stk_mesh_drizzle_stack,
+// stk_ecc_match_local_aligned_drizzle, stk_keypoint_match_local_aligned_drizzle, and their forms with rejection maps
+// (reject.cpp): stk_ecc_match_drizzle_rejected, stk_keypoint_match_drizzle_rejected (an extension beyond the reference;
 // definition in include/stacker.h, stk_drizzle_params and the block after it; kernel in kernels_drizzle.hip). The fields
 // and their pointer table live in ctx->mesh and are mesh.cpp's to place (through context.h). The frame table is the fold's (ctx->warpframes), its matrices composed here with the
 // output grid's map. ctx->local (grow-only, shared with local.cpp; one call at a time) holds, in this order: in the
@@ -89,17 +90,18 @@ void drizzle_entry(WarpFrame& wf, float* foot, const void* src, const double* M,
 }
 
 // The drizzle launch over `dev[entry_frame[k]]` under Ms[k] (9 doubles each) with the records `coef` (per entry) and the
-// maps (by frame index, in frames->location, or null). ctx->local is reserved for L. Writes `out` and `den_out` (out's
-// location), synchronises, returns the launch's device time in *ms.
+// maps (by frame index, in frames->location or with maps_device in device memory whatever the frames' location, or null).
+// ctx->local is reserved for L. Writes `out` and `den_out` (out's location), synchronises, returns the launch's device time
+// in *ms.
 stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* frames, const std::vector<const void*>& dev,
                        const std::vector<int>& entry_frame, const std::vector<const double*>& Ms, int is_affine, double alpha,
                        const stk_drizzle_params* p, const std::vector<stk_frame_weight>& coef, const float* const* maps,
-                       stk_image_f32* out, float* den_out, double* ms, const MeshFoldArgs* mesh = nullptr) {
+                       stk_image_f32* out, float* den_out, double* ms, const MeshFoldArgs* mesh = nullptr, bool maps_device = false) {
     const int ne = (int)entry_frame.size(), sw = frames->width, sh = frames->height, cn = frames->channels;
     const int ow = out->width, oh = out->height;
     const size_t rb = frame_row_bytes(frames);
     char* base = ctx->local.as<char>();
-    const bool host_out = out->location != STK_DEVICE, host_maps = frames->location != STK_DEVICE;
+    const bool host_out = out->location != STK_DEVICE, host_maps = frames->location != STK_DEVICE && !maps_device;
     std::vector<WarpFrame> wf(ne);
     std::vector<float> foot((size_t)ne * 2);
     std::vector<const float*> mptr(ne, nullptr);
@@ -290,9 +292,128 @@ stk_status keypoint_match_drizzle_impl(stk_ctx* ctx, const stk_frames* frames, c
     return drizzle_finish(ctx, L, frames, entry_frame, stats, 0, p, out, den_out, mesh);
 }
 
+// the checks of the rejected forms beyond drizzle's own, in the order the errors are reported
+stk_status drizzle_rejected_validate(stk_ctx* ctx, const stk_frames* frames, const stk_weight_params* weight, const stk_reject_params* reject) {
+    stk_status st = weighted_validate(ctx, weight);
+    if (st) return st;
+    if (weight->coverage != 1) return fail(ctx, STK_INVALID_PARAMS, "rejected drizzle: weight coverage must be 1 (the clean image is the coverage-aware median)");
+    if ((st = reject_validate(ctx, reject))) return st;
+    return quantile_check_count(ctx, frames->n);
+}
+
+struct RejectedLayouts { DrizzleLayout D; RejectLayout R; };
+
+// device memory of the rejected forms, before the plain call runs: the maps, the clean image and its counts (ctx->reject),
+// the median's image and band (ctx->quantile), the drizzle's tables and staging behind the plain call's mean (ctx->local)
+stk_status drizzle_rejected_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_image_f32* out, RejectedLayouts* Ls) {
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    Ls->D = drizzle_layout((size_t)w * h * cn * sizeof(float), n, w, h, out->width, out->height, cn, out->location != STK_DEVICE, 0);
+    Ls->R = reject_layout(n, w, h, cn, true, true, (size_t)n);
+    stk_status st = reject_reserve(ctx, Ls->R);
+    if (st) return st;
+    if ((st = drizzle_reserve(ctx, Ls->D))) return st;
+    return quantile_reserve(ctx, n, w, h, cn);
+}
+
+// the tail of the rejected forms, after the plain call: records, median, reject maps, drizzle (include/stacker.h, the steps
+// of stk_ecc_match_drizzle_rejected); finalize_ms = the sum of their device times, the rest of the timing the plain call's
+stk_status drizzle_rejected_finish(stk_ctx* ctx, const RejectedLayouts& Ls, const stk_frames* frames, const stk_frame_stats* stats,
+                                   bool keypoint, int border_mode, const double* border_value, int is_affine,
+                                   const stk_drizzle_params* p, const stk_weight_params* weight, const float* weights,
+                                   const stk_reject_params* reject, stk_image_f32* out, float* den_out, float* const* maps,
+                                   int64_t* rejected, stk_frame_weight* applied) {
+    static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    const int n = frames->n, w = frames->width, h = frames->height;
+    const stk_timing keep = ctx->timing;
+    std::vector<int> entry_frame;
+    std::vector<stk_frame_weight> coef;
+    double ms = 0.0, dms = 0.0;
+    char* base = ctx->reject.as<char>();
+    float* clean = (float*)(base + Ls.R.clean);
+    int32_t* counts = (int32_t*)(base + Ls.R.counts);
+    stk_status st = robust_match_records(ctx, frames, stats, keypoint, border_mode, border_value, is_affine, weight, weights, entry_frame,
+                                         coef, applied, &ms);
+    if (!st) st = robust_match_median(ctx, frames, coef, is_affine, clean, counts, &ms);
+    std::vector<const void*> dev;
+    resident_frames(ctx, frames, dev);
+    const size_t ne = entry_frame.size();
+    std::vector<const double*> Ms(ne);
+    std::vector<const float*> in(ne, nullptr), by_frame(n, nullptr);
+    std::vector<float*> planes(ne);
+    std::vector<int64_t> rej(ne);
+    for (size_t k = 0; k < ne; k++) {
+        Ms[k] = entry_frame[k] == 0 ? I3 : stats[entry_frame[k]].warp;
+        planes[k] = (float*)(base + Ls.R.planes + k * Ls.R.plane);
+        by_frame[entry_frame[k]] = planes[k];
+    }
+    if (!st) st = reject_run(ctx, Ls.R, frames, dev, entry_frame, Ms, is_affine, 1.0 / 255.0, coef, clean, counts, reject, in, planes,
+                             rej.data(), nullptr, &ms);
+    if (!st) st = drizzle_run(ctx, Ls.D, frames, dev, entry_frame, Ms, is_affine, 1.0 / 255.0, p, coef, by_frame.data(), out, den_out, &dms,
+                              nullptr, true);
+    if (!st && maps) {
+        const hipMemcpyKind kind = frames->location != STK_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+        for (size_t k = 0; k < ne && !st; k++) {
+            float* dst = maps[entry_frame[k]];
+            if (dst && hipMemcpyAsync(dst, planes[k], (size_t)w * h * sizeof(float), kind, ctx->stream) != hipSuccess)
+                st = fail(ctx, STK_HIP_ERROR, "rejected drizzle: copying a map out failed");
+        }
+        if (!st && hipStreamSynchronize(ctx->stream) != hipSuccess) st = fail(ctx, STK_HIP_ERROR, "rejected drizzle: copying the maps out failed");
+    }
+    if (!st && rejected) {
+        for (int i = 0; i < n; i++) rejected[i] = 0;
+        for (size_t k = 0; k < ne; k++) rejected[entry_frame[k]] = rej[k];
+    }
+    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : ms + dms;
+    return st;
+}
+
 }  // namespace
 
 extern "C" {
+
+stk_status stk_ecc_match_drizzle_rejected(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                          const stk_drizzle_params* p, const stk_weight_params* weight, const float* weights,
+                                          const stk_reject_params* reject, stk_image_f32* out, float* den_out, float* const* maps,
+                                          int64_t* rejected, stk_frame_weight* applied, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    stk_status st = drizzle_validate(ctx, frames, true, p, out);
+    if (st) return st;
+    if ((st = drizzle_rejected_validate(ctx, frames, weight, reject))) return st;
+    (void)hipSetDevice(ctx->device);
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    RejectedLayouts Ls;
+    if ((st = drizzle_rejected_reserve(ctx, frames, out, &Ls))) return st;
+    std::vector<stk_frame_stats> own;
+    if (!stats) { own.resize(n); stats = own.data(); }
+    // the plain call, on this context's own device, its mean into the head of the workspace (unused)
+    stk_image_f32 mimg{ctx->local.as<float>(), w, h, cn, STK_DEVICE, 0};
+    if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
+    return drizzle_rejected_finish(ctx, Ls, frames, stats, false, STK_BORDER_CONSTANT, nullptr, params->motion_type != STK_MOTION_HOMOGRAPHY,
+                                   p, weight, weights, reject, out, den_out, maps, rejected, applied);
+}
+
+stk_status stk_keypoint_match_drizzle_rejected(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                               float scale_down_width, const stk_drizzle_params* p, const stk_weight_params* weight,
+                                               const float* weights, const stk_reject_params* reject, stk_image_f32* out,
+                                               int32_t* dropped, float* den_out, float* const* maps, int64_t* rejected,
+                                               stk_frame_weight* applied, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    stk_status st = drizzle_validate(ctx, frames, true, p, out);
+    if (st) return st;
+    if ((st = drizzle_rejected_validate(ctx, frames, weight, reject))) return st;
+    if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
+    if ((st = weighted_check_border(ctx, params->border_mode, params->border_value, 1))) return st;
+    (void)hipSetDevice(ctx->device);
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    RejectedLayouts Ls;
+    if ((st = drizzle_rejected_reserve(ctx, frames, out, &Ls))) return st;
+    std::vector<stk_frame_stats> own;
+    if (!stats) { own.resize(n); stats = own.data(); }
+    stk_image_f32 mimg{ctx->local.as<float>(), w, h, cn, STK_DEVICE, 0};
+    if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
+    return drizzle_rejected_finish(ctx, Ls, frames, stats, true, params->border_mode, params->border_value, 0, p, weight, weights, reject,
+                                   out, den_out, maps, rejected, applied);
+}
 
 stk_status stk_drizzle_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
                              double alpha, const stk_drizzle_params* p, const stk_frame_weight* per_frame, const float* const* maps,

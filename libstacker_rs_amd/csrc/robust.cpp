@@ -279,6 +279,23 @@ stk_status robust_keypoint(stk_ctx* ctx, const stk_frames* frames, const stk_key
 
 }  // namespace
 
+// (shared with drizzle.cpp: context.h)
+stk_status robust_match_records(stk_ctx* ctx, const stk_frames* frames, const stk_frame_stats* stats, bool keypoint, int border_mode,
+                                const double* border_value, int is_affine, const stk_weight_params* weight, const float* weights,
+                                std::vector<int>& entry_frame, std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms) {
+    stk_status st = robust_stack_table(ctx, frames, stats, keypoint, is_affine, entry_frame);
+    if (st) return st;
+    return robust_coefs(ctx, frames, entry_frame, frames->depth, border_mode, border_value, is_affine, weight, weights, coef, applied, ms);
+}
+
+stk_status robust_match_median(stk_ctx* ctx, const stk_frames* frames, const std::vector<stk_frame_weight>& coef, int is_affine,
+                               float* clean, int32_t* counts, double* ms) {
+    const stk_quantile_params qp{0.5f, 0};
+    stk_image_f32 img{clean, frames->width, frames->height, frames->channels, STK_DEVICE, 0};
+    return quantile_bands_weighted(ctx, coef, frames->depth, frames->width, frames->height, frames->channels, frame_row_bytes(frames),
+                                   1.0 / 255.0, STK_BORDER_CONSTANT, nullptr, is_affine, 1, &qp, &img, counts, ms);
+}
+
 extern "C" {
 
 stk_status stk_clip_stack_weighted(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,

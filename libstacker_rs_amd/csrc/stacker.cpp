@@ -99,7 +99,7 @@ void stk_destroy(stk_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (DevBuf* b : {&ctx->frames, &ctx->ref, &ctx->blur_tmp, &ctx->templates, &ctx->slots, &ctx->queue, &ctx->results,
                       &ctx->partials, &ctx->first_sums, &ctx->warpframes, &ctx->acc, &ctx->scratch, &ctx->init_warps, &ctx->frameptrs, &ctx->clip,
-                      &ctx->quantile, &ctx->weighted, &ctx->coef, &ctx->quality, &ctx->local, &ctx->mesh})
+                      &ctx->quantile, &ctx->weighted, &ctx->coef, &ctx->quality, &ctx->local, &ctx->mesh, &ctx->reject})
         b->release();
     keypoint_workspace_destroy(ctx->kp);
     geom::hg_workspace_destroy(ctx->hg);
