@@ -1,10 +1,12 @@
-// context.h — the engine's per-GPU context (stk_ctx) and host helpers shared by stacker.cpp and keypoint.cpp.
+// context.h — the engine's per-GPU context (stk_ctx) and host helpers shared by stacker.cpp, keypoint.cpp and the combines
+// (whose common front end is combine.h).
 #pragma once
 #include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "combine.h"
 #include "common.h"
 #include "homography.h"
 #include "keypoint.h"
@@ -169,9 +171,9 @@ stk_status keypoint_match_single(stk_ctx* ctx, const stk_frames* frames, const s
                                  stk_image_f32* out, int32_t* dropped, stk_frame_stats* stats);
 // the frame table of a fold into ctx->warpframes (flags for a w x h destination; asynchronous: `wf` must outlive the copy)
 stk_status warp_table_upload(stk_ctx* ctx, std::vector<WarpFrame>& wf, size_t src_row_bytes, int w, int h, int is_affine);
-// shared by the combines (clip.cpp, quantile.cpp, weighted.cpp; used again by robust.cpp)
+// shared by the combines (clip.cpp, quantile.cpp, weighted.cpp; used again by robust.cpp); the frame table, the fold's
+// geometry and the whole-stack scaffold they all start from: combine.h
 stk_status clip_validate(stk_ctx* ctx, const stk_clip_params* p);
-stk_status clip_check_out(stk_ctx* ctx, const stk_image_f32* out, const stk_frames* f);
 stk_status quantile_validate(stk_ctx* ctx, const stk_quantile_params* p);
 stk_status quantile_check_count(stk_ctx* ctx, int n);
 size_t quantile_image_floats(int w, int h, int cn);
@@ -181,22 +183,18 @@ stk_status robust_clip_validate(stk_ctx* ctx, const stk_robust_clip_params* p);
 // the median / MAD clip over the n_entries entries of ctx->warpframes (robust_clip.cpp): per band a store launch and the
 // selection into the clip planes, then one last clip pass. coef: the per-entry records of the participation form (then
 // `coverage` and `kept` apply), null = the plain form. Writes out / counts / kept (out's location), adds its device time to *ms
-stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_frame_weight>* coef, int depth, int w, int h, int cn,
-                             size_t src_row_bytes, double alpha, int border_mode, const double* border_value, int is_affine,
-                             int coverage, const stk_robust_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms);
+stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_frame_weight>* coef, const FoldSpec& spec, int coverage,
+                             const stk_robust_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms);
 stk_status weighted_validate(stk_ctx* ctx, const stk_weight_params* p);
-stk_status weighted_check_out(stk_ctx* ctx, const stk_image_f32* out, const stk_frames* f);
 stk_status weighted_check_border(stk_ctx* ctx, int border_mode, const double* border_value, int coverage);
-// the caller-held-warps forms' frame table: uploads host frames, fills ctx->warpframes with the included frames under M
-// (entry_frame[k] = the frame index of entry k), begins the call's timing and synchronises
-stk_status weighted_table(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int is_affine,
-                          std::vector<int>& entry_frame);
 stk_status weighted_check_coefs(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, int cn);
-stk::WarpArgs weighted_warp_args(stk_ctx* ctx, int n_entries, int depth, int w, int h, int cn, size_t src_row_bytes, double alpha,
-                                 int border_mode, const double* border_value, int is_affine);
-stk_status weighted_moments(stk_ctx* ctx, int n_entries, int depth, int w, int h, int cn, size_t src_row_bytes, double alpha,
-                            int border_mode, const double* border_value, int is_affine, int step, double* host, double* ms);
+stk_status weighted_moments(stk_ctx* ctx, int n_entries, const FoldSpec& spec, int step, double* host, double* ms);
 void weighted_estimate(const double* m /* cn x 6 */, int cn, int mode, stk_frame_weight* e);
+// the records of a whole-stack table's entries (entry 0 = frame 0; the table is uploaded), as stk_*_match_weighted makes
+// them: the moments pass and the estimator when normalize != 0, the caller's weights by frame index; `applied` (or null) by
+// frame index over the n frames (a dropped frame: weight 0, gains 1). Adds the pass's device time to *ms.
+stk_status weighted_match_records(stk_ctx* ctx, int n, const EntryTable& table, const FoldSpec& spec, const stk_weight_params* p,
+                                  const float* weights, std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms);
 // the pieces of the local-weighted combine (local.cpp) that the mesh folds (mesh.cpp) are built from
 struct LocalLayout {
     size_t fptrs, mptrs, coef, image, den, planes, plane, total;     // byte offsets into ctx->local; plane: bytes of one map plane
@@ -211,9 +209,9 @@ stk_status local_maps_launch(stk_ctx* ctx, const LocalLayout& L, size_t first, s
 // the field table of a mesh fold, in device memory and indexed like the frame table (null entry: not displaced)
 struct MeshFoldArgs { const float* const* fields; int step, gw, gh; };
 void mesh_fold_clip_args(const MeshFoldArgs& m, stk::ClipArgs& ca);
-stk_status local_fold(stk_ctx* ctx, const LocalLayout& L, const std::vector<stk_frame_weight>& coef, int depth, int w, int h, int cn,
-                      size_t src_row_bytes, double alpha, int is_affine, float floor, int power, stk_image_f32* out, float* den_out,
-                      double* ms, const MeshFoldArgs* mesh = nullptr);
+// (the fold runs under BORDER_CONSTANT 0 whatever the spec's border: local_check_border)
+stk_status local_fold(stk_ctx* ctx, const LocalLayout& L, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, float floor,
+                      int power, stk_image_f32* out, float* den_out, double* ms, const MeshFoldArgs* mesh = nullptr);
 // stk_local_weighted_stack, and with `fields` (n planes by frame index, in frames->location) stk_mesh_local_weighted_stack
 stk_status local_weighted_stack_impl(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
                                      int32_t border_mode, const double* border_value, double alpha, const stk_frame_weight* per_frame,
@@ -223,8 +221,8 @@ stk_status local_weighted_stack_impl(stk_ctx* ctx, const stk_frames* frames, con
 stk_status mesh_check_fold(stk_ctx* ctx, int step);
 // uploads the fields of the table's entries (host planes into ctx->mesh) and their pointer table; frame 0 and an entry
 // whose plane is null get no field. Synchronises.
-stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const std::vector<int>& entry_frame, const float* const* fields,
-                           int step, MeshFoldArgs* out);
+stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const EntryTable& table, const float* const* fields, int step,
+                           MeshFoldArgs* out);
 // the field pass of the whole-stack forms for a combine outside mesh.cpp (drizzle.cpp): the checks of the mesh parameters
 // and of the frames' depth; ctx->mesh reserved for frames->n entries; the pass over the n_entries entries of ctx->warpframes
 // (entry 0 = frame 0; the table is uploaded), which leaves the fold's field table in *out, synchronises and adds its device
@@ -241,16 +239,16 @@ RejectLayout reject_layout(int n_entries, int sw, int sh, int cn, bool clean, bo
 stk_status reject_reserve(stk_ctx* ctx, const RejectLayout& L);
 stk_status reject_validate(stk_ctx* ctx, const stk_reject_params* p);
 stk_status reject_run(stk_ctx* ctx, const RejectLayout& L, const stk_frames* frames, const std::vector<const void*>& dev,
-                      const std::vector<int>& entry_frame, const std::vector<const double*>& Ms, int is_affine, double alpha,
-                      const std::vector<stk_frame_weight>& coef, const float* clean, const int32_t* counts,
-                      const stk_reject_params* p, const std::vector<const float*>& in, const std::vector<float*>& out,
-                      int64_t* rejected, int64_t* judged, double* ms);
-// after a plain whole-stack call (robust.cpp): the frame table of frame 0 and the kept frames into ctx->warpframes and the
-// records as stk_*_match_weighted makes them; then the coverage-aware median (quantile 0.5, coverage 1, BORDER_CONSTANT 0,
-// alpha 1 / 255) of that table with its counts, both device memory. Each adds its device time to *ms.
-stk_status robust_match_records(stk_ctx* ctx, const stk_frames* frames, const stk_frame_stats* stats, bool keypoint, int border_mode,
-                                const double* border_value, int is_affine, const stk_weight_params* weight, const float* weights,
-                                std::vector<int>& entry_frame, std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms);
+                      const EntryTable& table, int is_affine, double alpha, const std::vector<stk_frame_weight>& coef, const float* clean,
+                      const int32_t* counts, const stk_reject_params* p, const std::vector<const float*>& in,
+                      const std::vector<float*>& out, int64_t* rejected, int64_t* judged, double* ms);
+// after a plain whole-stack call (robust.cpp): the frame table of frame 0 and the kept frames (`table`) into
+// ctx->warpframes and the records as stk_*_match_weighted makes them under `spec`; then the coverage-aware median
+// (quantile 0.5, coverage 1, BORDER_CONSTANT 0, alpha 1 / 255) of that table with its counts, both device memory. Each adds
+// its device time to *ms.
+stk_status robust_match_records(stk_ctx* ctx, const stk_frames* frames, const stk_frame_stats* stats, bool keypoint, const FoldSpec& spec,
+                                const stk_weight_params* weight, const float* weights, EntryTable& table,
+                                std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms);
 stk_status robust_match_median(stk_ctx* ctx, const stk_frames* frames, const std::vector<stk_frame_weight>& coef, int is_affine,
                                float* clean, int32_t* counts, double* ms);
 stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,

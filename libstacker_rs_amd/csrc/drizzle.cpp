@@ -89,15 +89,15 @@ void drizzle_entry(WarpFrame& wf, float* foot, const void* src, const double* M,
     foot[1] = std::fmin((float)(0.5 * (std::fabs((double)wf.M[3]) + std::fabs((double)wf.M[4]))), hmax);
 }
 
-// The drizzle launch over `dev[entry_frame[k]]` under Ms[k] (9 doubles each) with the records `coef` (per entry) and the
+// The drizzle launch over the table's entries, `dev[table.frame[k]]` under table.M[k], with the records `coef` (per entry) and the
 // maps (by frame index, in frames->location or with maps_device in device memory whatever the frames' location, or null).
 // ctx->local is reserved for L. Writes `out` and `den_out` (out's location), synchronises, returns the launch's device time
 // in *ms.
 stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* frames, const std::vector<const void*>& dev,
-                       const std::vector<int>& entry_frame, const std::vector<const double*>& Ms, int is_affine, double alpha,
+                       const EntryTable& table, int is_affine, double alpha,
                        const stk_drizzle_params* p, const std::vector<stk_frame_weight>& coef, const float* const* maps,
                        stk_image_f32* out, float* den_out, double* ms, const MeshFoldArgs* mesh = nullptr, bool maps_device = false) {
-    const int ne = (int)entry_frame.size(), sw = frames->width, sh = frames->height, cn = frames->channels;
+    const int ne = table.size(), sw = frames->width, sh = frames->height, cn = frames->channels;
     const int ow = out->width, oh = out->height;
     const size_t rb = frame_row_bytes(frames);
     char* base = ctx->local.as<char>();
@@ -105,7 +105,7 @@ stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* f
     std::vector<WarpFrame> wf(ne);
     std::vector<float> foot((size_t)ne * 2);
     std::vector<const float*> mptr(ne, nullptr);
-    for (int k = 0; k < ne; k++) drizzle_entry(wf[k], &foot[2 * (size_t)k], dev[entry_frame[k]], Ms[k], is_affine, p);
+    for (int k = 0; k < ne; k++) drizzle_entry(wf[k], &foot[2 * (size_t)k], dev[table.frame[k]], table.M[k], is_affine, p);
     stk_status st = warp_table_upload(ctx, wf, rb, ow, oh, is_affine);
     if (st) return st;
     HIP_TRY(hipMemcpyAsync(base + L.foot, foot.data(), foot.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -113,7 +113,7 @@ stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* f
     if (maps) {
         size_t slot = 0;
         for (int k = 0; k < ne; k++) {
-            const float* m = maps[entry_frame[k]];
+            const float* m = maps[table.frame[k]];
             if (m && host_maps) {
                 float* d = (float*)(base + L.planes + slot++ * L.plane);
                 HIP_TRY(hipMemcpyAsync(d, m, (size_t)sw * sh * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -162,37 +162,25 @@ stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* f
     return STK_OK;
 }
 
-void drizzle_unit_record(stk_frame_weight* e) {
-    for (int c = 0; c < 4; c++) { e->gain[c] = 1.0f; e->offset[c] = 0.0f; }
-    e->weight = 1.0f; e->flags = 0;
-}
-
-// the tail of the whole-stack forms: the frames of `entry_frame` (frame 0 through the identity, the others under the
-// stats' warps), all weights 1, no maps, alpha = 1 / 255; the timing stays the plain call's but for finalize_ms. With mesh
-// parameters: the field pass over the same entries under the fold's matrices first (ctx->mesh is reserved), the drizzle
-// through its fields, and finalize_ms the sum of the two.
-stk_status drizzle_finish(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* frames, const std::vector<int>& entry_frame,
-                          const stk_frame_stats* stats, int is_affine, const stk_drizzle_params* p, stk_image_f32* out, float* den_out,
-                          const stk_mesh_params* mp = nullptr) {
-    static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+// the tail of the whole-stack forms: the frames the plain call kept (combine.h: entries_from_stats), all weights 1, no
+// maps, alpha = 1 / 255; the timing stays the plain call's but for finalize_ms. With mesh parameters: the field pass over
+// the same entries under the fold's matrices first (ctx->mesh is reserved), the drizzle through its fields, and
+// finalize_ms the sum of the two. (Not combine.h's scaffold: the drizzle's own table has the output's geometry, and
+// without mesh parameters the fold's table is never uploaded.)
+stk_status drizzle_finish(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* frames, const stk_frame_stats* stats, bool keypoint,
+                          int is_affine, const stk_drizzle_params* p, stk_image_f32* out, float* den_out, const stk_mesh_params* mp = nullptr) {
     std::vector<const void*> dev;
     resident_frames(ctx, frames, dev);
-    std::vector<const double*> Ms(entry_frame.size());
-    for (size_t k = 0; k < entry_frame.size(); k++) Ms[k] = entry_frame[k] == 0 ? I3 : stats[entry_frame[k]].warp;
-    std::vector<stk_frame_weight> coef(entry_frame.size());
-    for (stk_frame_weight& e : coef) drizzle_unit_record(&e);
+    EntryTable table;
+    entries_from_stats(frames->n, stats, keypoint, table);
+    const std::vector<stk_frame_weight> coef(table.frame.size(), unit_record());
     const stk_timing keep = ctx->timing;
     double ms = 0.0, fms = 0.0;
     stk_status st = STK_OK;
     MeshFoldArgs mf{};
-    if (mp) {
-        std::vector<WarpFrame> wf(entry_frame.size());
-        for (size_t k = 0; k < entry_frame.size(); k++) make_warp_frame(wf[k], dev[entry_frame[k]], Ms[k], is_affine);
-        // (mesh_match_fields synchronises: `wf` outlives the copy)
-        if (!(st = warp_table_upload(ctx, wf, frame_row_bytes(frames), frames->width, frames->height, is_affine)))
-            st = mesh_match_fields(ctx, frames, (int)entry_frame.size(), is_affine, mp, &mf, &fms);
-    }
-    if (!st) st = drizzle_run(ctx, L, frames, dev, entry_frame, Ms, is_affine, 1.0 / 255.0, p, coef, nullptr, out, den_out, &ms, mp ? &mf : nullptr);
+    if (mp && !(st = entry_table_upload(ctx, frames, dev, table, is_affine)))
+        st = mesh_match_fields(ctx, frames, table.size(), is_affine, mp, &mf, &fms);
+    if (!st) st = drizzle_run(ctx, L, frames, dev, table, is_affine, 1.0 / 255.0, p, coef, nullptr, out, den_out, &ms, mp ? &mf : nullptr);
     ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : fms + ms;
     return st;
 }
@@ -211,20 +199,14 @@ stk_status drizzle_stack_impl(stk_ctx* ctx, const stk_frames* frames, const doub
             return fail(ctx, STK_INVALID_PARAMS, "mesh: step must be 8, 16, 32, 64, 128 or 256");
     }
     const int n = frames->n, cn = frames->channels;
-    std::vector<int> entry_frame;
+    EntryTable table;
+    entries_from_include(n, M, include, table);
+    if (table.frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "drizzle: no frame included");
     std::vector<stk_frame_weight> coef;
-    std::vector<const double*> Ms;
+    gather_records(table, per_frame, coef);
     size_t n_planes = 0;
-    for (int i = 0; i < n; i++) {
-        if (include && !include[i]) continue;
-        stk_frame_weight e;
-        if (per_frame) e = per_frame[i]; else drizzle_unit_record(&e);
-        entry_frame.push_back(i);
-        coef.push_back(e);
-        Ms.push_back(M + 9 * (size_t)i);
+    for (int i : table.frame)
         if (maps && maps[i] && frames->location != STK_DEVICE) n_planes++;
-    }
-    if (coef.empty()) return fail(ctx, STK_INVALID_PARAMS, "drizzle: no frame included");
     if ((st = weighted_check_coefs(ctx, coef, cn))) return st;
     (void)hipSetDevice(ctx->device);
     timing_begin(ctx);
@@ -234,9 +216,9 @@ stk_status drizzle_stack_impl(stk_ctx* ctx, const stk_frames* frames, const doub
     std::vector<const void*> dev;
     if ((st = resolve_frames(ctx, frames, dev))) return st;
     MeshFoldArgs mf{};
-    if (mesh && (st = mesh_fold_table(ctx, frames, entry_frame, fields, step, &mf))) return st;
+    if (mesh && (st = mesh_fold_table(ctx, frames, table, fields, step, &mf))) return st;
     double ms = 0.0;
-    if ((st = drizzle_run(ctx, L, frames, dev, entry_frame, Ms, is_affine != 0, alpha, p, coef, maps, out, den_out, &ms, mesh ? &mf : nullptr)))
+    if ((st = drizzle_run(ctx, L, frames, dev, table, is_affine != 0, alpha, p, coef, maps, out, den_out, &ms, mesh ? &mf : nullptr)))
         return st;
     ctx->timing.finalize_ms = ms;
     return STK_OK;
@@ -261,10 +243,7 @@ stk_status ecc_match_drizzle_impl(stk_ctx* ctx, const stk_frames* frames, const 
     // the plain call, on this context's own device, its mean into the head of the workspace (unused)
     stk_image_f32 mimg{ctx->local.as<float>(), w, h, cn, STK_DEVICE, 0};
     if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
-    // every frame is a sample: frame 0 through the identity, frame i through its warp (as in stk_ecc_match_weighted)
-    std::vector<int> entry_frame(n);
-    for (int i = 0; i < n; i++) entry_frame[i] = i;
-    return drizzle_finish(ctx, L, frames, entry_frame, stats, params->motion_type != STK_MOTION_HOMOGRAPHY, p, out, den_out, mesh);
+    return drizzle_finish(ctx, L, frames, stats, false, params->motion_type != STK_MOTION_HOMOGRAPHY, p, out, den_out, mesh);
 }
 
 // stk_keypoint_match_drizzle, and with mesh parameters stk_keypoint_match_local_aligned_drizzle
@@ -286,10 +265,7 @@ stk_status keypoint_match_drizzle_impl(stk_ctx* ctx, const stk_frames* frames, c
     if (!stats) { own.resize(n); stats = own.data(); }
     stk_image_f32 mimg{ctx->local.as<float>(), w, h, cn, STK_DEVICE, 0};
     if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
-    // the samples: frame 0 through the identity and the frames with a homography (status 0), in stack order
-    std::vector<int> entry_frame{0};
-    for (int i = 1; i < n; i++) if (stats[i].status == 0) entry_frame.push_back(i);
-    return drizzle_finish(ctx, L, frames, entry_frame, stats, 0, p, out, den_out, mesh);
+    return drizzle_finish(ctx, L, frames, stats, true, 0, p, out, den_out, mesh);
 }
 
 // the checks of the rejected forms beyond drizzle's own, in the order the errors are reported
@@ -318,38 +294,34 @@ stk_status drizzle_rejected_reserve(stk_ctx* ctx, const stk_frames* frames, cons
 // the tail of the rejected forms, after the plain call: records, median, reject maps, drizzle (include/stacker.h, the steps
 // of stk_ecc_match_drizzle_rejected); finalize_ms = the sum of their device times, the rest of the timing the plain call's
 stk_status drizzle_rejected_finish(stk_ctx* ctx, const RejectedLayouts& Ls, const stk_frames* frames, const stk_frame_stats* stats,
-                                   bool keypoint, int border_mode, const double* border_value, int is_affine,
-                                   const stk_drizzle_params* p, const stk_weight_params* weight, const float* weights,
-                                   const stk_reject_params* reject, stk_image_f32* out, float* den_out, float* const* maps,
-                                   int64_t* rejected, stk_frame_weight* applied) {
-    static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    const int n = frames->n, w = frames->width, h = frames->height;
+                                   bool keypoint, const FoldSpec& spec, const stk_drizzle_params* p, const stk_weight_params* weight,
+                                   const float* weights, const stk_reject_params* reject, stk_image_f32* out, float* den_out,
+                                   float* const* maps, int64_t* rejected, stk_frame_weight* applied) {
+    const int n = frames->n, w = frames->width, h = frames->height, is_affine = spec.is_affine;
     const stk_timing keep = ctx->timing;
-    std::vector<int> entry_frame;
+    EntryTable table;
+    const std::vector<int>& entry_frame = table.frame;
     std::vector<stk_frame_weight> coef;
     double ms = 0.0, dms = 0.0;
     char* base = ctx->reject.as<char>();
     float* clean = (float*)(base + Ls.R.clean);
     int32_t* counts = (int32_t*)(base + Ls.R.counts);
-    stk_status st = robust_match_records(ctx, frames, stats, keypoint, border_mode, border_value, is_affine, weight, weights, entry_frame,
-                                         coef, applied, &ms);
+    stk_status st = robust_match_records(ctx, frames, stats, keypoint, spec, weight, weights, table, coef, applied, &ms);
     if (!st) st = robust_match_median(ctx, frames, coef, is_affine, clean, counts, &ms);
     std::vector<const void*> dev;
     resident_frames(ctx, frames, dev);
     const size_t ne = entry_frame.size();
-    std::vector<const double*> Ms(ne);
     std::vector<const float*> in(ne, nullptr), by_frame(n, nullptr);
     std::vector<float*> planes(ne);
     std::vector<int64_t> rej(ne);
     for (size_t k = 0; k < ne; k++) {
-        Ms[k] = entry_frame[k] == 0 ? I3 : stats[entry_frame[k]].warp;
         planes[k] = (float*)(base + Ls.R.planes + k * Ls.R.plane);
         by_frame[entry_frame[k]] = planes[k];
     }
-    if (!st) st = reject_run(ctx, Ls.R, frames, dev, entry_frame, Ms, is_affine, 1.0 / 255.0, coef, clean, counts, reject, in, planes,
-                             rej.data(), nullptr, &ms);
-    if (!st) st = drizzle_run(ctx, Ls.D, frames, dev, entry_frame, Ms, is_affine, 1.0 / 255.0, p, coef, by_frame.data(), out, den_out, &dms,
-                              nullptr, true);
+    if (!st) st = reject_run(ctx, Ls.R, frames, dev, table, is_affine, 1.0 / 255.0, coef, clean, counts, reject, in, planes, rej.data(), nullptr,
+                             &ms);
+    if (!st) st = drizzle_run(ctx, Ls.D, frames, dev, table, is_affine, 1.0 / 255.0, p, coef, by_frame.data(), out, den_out, &dms, nullptr,
+                              true);
     if (!st && maps) {
         const hipMemcpyKind kind = frames->location != STK_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
         for (size_t k = 0; k < ne && !st; k++) {
@@ -388,8 +360,8 @@ stk_status stk_ecc_match_drizzle_rejected(stk_ctx* ctx, const stk_frames* frames
     // the plain call, on this context's own device, its mean into the head of the workspace (unused)
     stk_image_f32 mimg{ctx->local.as<float>(), w, h, cn, STK_DEVICE, 0};
     if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
-    return drizzle_rejected_finish(ctx, Ls, frames, stats, false, STK_BORDER_CONSTANT, nullptr, params->motion_type != STK_MOTION_HOMOGRAPHY,
-                                   p, weight, weights, reject, out, den_out, maps, rejected, applied);
+    return drizzle_rejected_finish(ctx, Ls, frames, stats, false, fold_spec_ecc(frames, params), p, weight, weights, reject, out, den_out,
+                                   maps, rejected, applied);
 }
 
 stk_status stk_keypoint_match_drizzle_rejected(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
@@ -411,8 +383,8 @@ stk_status stk_keypoint_match_drizzle_rejected(stk_ctx* ctx, const stk_frames* f
     if (!stats) { own.resize(n); stats = own.data(); }
     stk_image_f32 mimg{ctx->local.as<float>(), w, h, cn, STK_DEVICE, 0};
     if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
-    return drizzle_rejected_finish(ctx, Ls, frames, stats, true, params->border_mode, params->border_value, 0, p, weight, weights, reject,
-                                   out, den_out, maps, rejected, applied);
+    return drizzle_rejected_finish(ctx, Ls, frames, stats, true, fold_spec_keypoint(frames, params), p, weight, weights, reject, out,
+                                   den_out, maps, rejected, applied);
 }
 
 stk_status stk_drizzle_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,

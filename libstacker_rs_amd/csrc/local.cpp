@@ -3,8 +3,8 @@
 // reference; definition in include/stacker.h, stk_local_params; kernels in kernels_local.hip and warp_body.h).
 // ctx->local (grow-only like the other workspaces) holds the pointer tables of the map pass and of the fold, the per-entry
 // gain / offset / weight table, a w x h x cn f32 image (the plain call's mean in the whole-stack forms, then a host
-// output's staging copy), the w x h den plane and the map planes of the fold's entries. The checks, the frame table, the
-// moments pass and the estimator are the weighted combine's (weighted.cpp, through context.h). Like weighted.cpp, the
+// output's staging copy), the w x h den plane and the map planes of the fold's entries. The frame table is combine.h's; the
+// checks, the moments pass and the estimator are the weighted combine's (weighted.cpp, through context.h). Like weighted.cpp, the
 // whole-stack forms run the plain call first and take the warps and the kept set from its stats; the frames are still
 // resident in HBM, full size, and the maps of the entries are computed from them.
 #include <algorithm>
@@ -60,13 +60,18 @@ stk_status local_check_depth(stk_ctx* ctx, const stk_frames* f) {
     return STK_OK;
 }
 
+// what local_check_border has checked, written the one way the kernels have always been given it
+FoldSpec local_border(FoldSpec spec) {
+    spec.border_mode = STK_BORDER_CONSTANT; spec.border_value = nullptr;
+    return spec;
+}
+
 }  // namespace
 
 // a weight taken outside a frame means nothing: the fold runs under BORDER_CONSTANT with border value 0
 stk_status local_check_border(stk_ctx* ctx, int border_mode, const double* border_value) {
-    if (border_mode < 0 || border_mode > 4)
-        return fail(ctx, border_mode == STK_BORDER_TRANSPARENT ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS,
-                    "border mode not supported (BORDER_TRANSPARENT leaves the reference's output uninitialised)");
+    stk_status st = check_border_mode(ctx, border_mode);
+    if (st) return st;
     bool zero = border_mode == STK_BORDER_CONSTANT;
     for (int k = 0; k < 4 && border_value; k++) zero = zero && border_value[k] == 0.0;
     if (!zero) return fail(ctx, STK_INVALID_PARAMS, "local: the fold needs border_mode BORDER_CONSTANT with border_value 0");
@@ -97,12 +102,12 @@ stk_status local_maps_launch(stk_ctx* ctx, const LocalLayout& L, size_t first, s
 // The local-weighted fold over the n_entries entries of ctx->warpframes with the per-entry records `coef` and the plane
 // table at L.mptrs (uploaded by the caller). Writes `out` and `den_out` (out's location); adds its device time to *ms.
 // mesh: the generic kernel's mesh variant with that field table (mesh.cpp).
-stk_status local_fold(stk_ctx* ctx, const LocalLayout& L, const std::vector<stk_frame_weight>& coef, int depth, int w, int h, int cn,
-                      size_t src_row_bytes, double alpha, int is_affine, float floor, int power, stk_image_f32* out, float* den_out,
-                      double* ms, const MeshFoldArgs* mesh) {
+stk_status local_fold(stk_ctx* ctx, const LocalLayout& L, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, float floor,
+                      int power, stk_image_f32* out, float* den_out, double* ms, const MeshFoldArgs* mesh) {
+    const int w = spec.w, h = spec.h, cn = spec.cn, depth = spec.depth;
     char* base = ctx->local.as<char>();
     const bool host = out->location != STK_DEVICE;
-    const WarpArgs a = weighted_warp_args(ctx, (int)coef.size(), depth, w, h, cn, src_row_bytes, alpha, STK_BORDER_CONSTANT, nullptr, is_affine);
+    const WarpArgs a = fold_warp_args(ctx, (int)coef.size(), local_border(spec));
     ClipArgs ca{};
     ca.coef = (const stk_frame_weight*)(base + L.coef);
     ca.coverage = 1;
@@ -141,48 +146,38 @@ stk_status local_match_check(stk_ctx* ctx, const stk_frames* frames, const stk_w
     if ((st = local_validate(ctx, local))) return st;
     if ((st = check_frames(ctx, frames, true))) return st;
     if ((st = local_check_depth(ctx, frames))) return st;
-    return weighted_check_out(ctx, out, frames);
+    return combine_check_out(ctx, out, frames);
 }
 
-// the tail of the whole-stack forms: `entry_frame[k]` is the frame index of table entry k (entry 0 = frame 0), `dev` the
-// resident full-size frames by frame index; the frame table is uploaded. Map pass, moments pass, estimator, fold.
-stk_status local_finish(stk_ctx* ctx, const LocalLayout& L, const stk_frames* frames, const std::vector<int>& entry_frame,
-                        const std::vector<const void*>& dev, size_t rb, int is_affine, const stk_weight_params* p, const float* weights,
-                        const stk_local_params* lp, stk_image_f32* out, float* den_out, stk_frame_weight* applied) {
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    const int ne = (int)entry_frame.size();
-    const double alpha = 1.0 / 255.0;
-    char* base = ctx->local.as<char>();
-    double ms = 0.0;
-    std::vector<const void*> fptr(ne);
-    std::vector<float*> mptr(ne);
-    for (int k = 0; k < ne; k++) { fptr[k] = dev[entry_frame[k]]; mptr[k] = (float*)(base + L.planes + (size_t)k * L.plane); }
-    stk_status st = local_maps_enqueue(ctx, L, fptr, mptr);
-    if (st) return st;
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
-    if ((st = local_maps_launch(ctx, L, 0, (size_t)ne, cn, w, h, rb, lp))) return st;
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    std::vector<stk_frame_weight> coef(ne);
-    std::vector<double> mom((size_t)std::max(ne - 1, 0) * cn * 6);
-    if (p->normalize != 0 && ne > 1) {
-        const int step = p->stat_step ? p->stat_step : 4;
-        if ((st = weighted_moments(ctx, ne, 8, w, h, cn, rb, alpha, STK_BORDER_CONSTANT, nullptr, is_affine, step, mom.data(), &ms))) return st;
-    }
-    for (int k = 0; k < ne; k++) {
-        if (k == 0) weighted_estimate(nullptr, cn, 0, &coef[k]);
-        else weighted_estimate(mom.data() + (size_t)(k - 1) * cn * 6, cn, p->normalize, &coef[k]);
-        coef[k].weight = weights ? weights[entry_frame[k]] : 1.0f;
-    }
-    if ((st = weighted_check_coefs(ctx, coef, cn))) return st;
-    if ((st = local_fold(ctx, L, coef, 8, w, h, cn, rb, alpha, is_affine, lp->floor, lp->power, out, den_out, &ms))) return st;
-    ctx->timing.finalize_ms = ms;
-    if (applied) {
-        for (int i = 0; i < n; i++) { weighted_estimate(nullptr, cn, 0, &applied[i]); applied[i].weight = 0.0f; }
-        for (int k = 0; k < ne; k++) applied[entry_frame[k]] = coef[k];
-    }
-    return STK_OK;
+// their workspace (the plain call's mean lands in its image, unused)
+stk_status local_match_reserve(stk_ctx* ctx, const stk_frames* frames, LocalLayout* L) {
+    (void)hipSetDevice(ctx->device);
+    const int n = frames->n;
+    *L = local_layout((size_t)n, n, frames->width, frames->height, frames->channels, (size_t)n);
+    return local_reserve(ctx, *L, (size_t)n);
+}
+
+// and their combine over the kept frames (`dev`: the resident full-size frames by frame index): map pass, records, fold
+CombineFinish local_match_finish(stk_ctx* ctx, const LocalLayout& L, int n, const stk_weight_params* p, const float* weights,
+                                 const stk_local_params* lp, stk_image_f32* out, float* den_out, stk_frame_weight* applied) {
+    return [=](const EntryTable& table, const std::vector<const void*>& dev, const FoldSpec& plain, const stk_frame_stats*, double* ms) {
+        const FoldSpec spec = local_border(plain);
+        const int ne = table.size();
+        char* base = ctx->local.as<char>();
+        std::vector<const void*> fptr(ne);
+        std::vector<float*> mptr(ne);
+        for (int k = 0; k < ne; k++) { fptr[k] = dev[table.frame[k]]; mptr[k] = (float*)(base + L.planes + (size_t)k * L.plane); }
+        stk_status st = local_maps_enqueue(ctx, L, fptr, mptr);
+        if (st) return st;
+        HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+        if ((st = local_maps_launch(ctx, L, 0, (size_t)ne, spec.cn, spec.w, spec.h, spec.src_row_bytes, lp))) return st;
+        HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
+        std::vector<stk_frame_weight> coef;
+        if ((st = weighted_match_records(ctx, n, table, spec, p, weights, coef, applied, ms))) return st;
+        return local_fold(ctx, L, coef, spec, lp->floor, lp->power, out, den_out, ms);
+    };
 }
 
 }  // namespace
@@ -258,23 +253,20 @@ stk_status local_weighted_stack_impl(stk_ctx* ctx, const stk_frames* frames, con
     if ((st = local_check_border(ctx, border_mode, border_value))) return st;
     if (power < 1 || power > 4) return fail(ctx, STK_INVALID_PARAMS, "local: power must be 1 .. 4");
     if (!std::isfinite(floor) || floor < 0.0f) return fail(ctx, STK_INVALID_PARAMS, "local: floor must be finite and >= 0");
-    if ((st = weighted_check_out(ctx, out, frames))) return st;
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    std::vector<stk_frame_weight> coef;
-    for (int i = 0; i < n; i++) {
-        if (include && !include[i]) continue;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    const int w = frames->width, h = frames->height, cn = frames->channels;
+    EntryTable table;
+    entries_from_include(frames->n, M, include, table);
+    for (int i : table.frame) {
         if (!maps[i]) return fail(ctx, STK_INVALID_PARAMS, "null map plane of an included frame");
         if (fields && i > 0 && !fields[i]) return fail(ctx, STK_INVALID_PARAMS, "null field plane of an included frame");
-        stk_frame_weight e;
-        if (per_frame) e = per_frame[i];
-        else { weighted_estimate(nullptr, cn, 0, &e); e.weight = 1.0f; }
-        coef.push_back(e);
     }
-    if (coef.empty()) return fail(ctx, STK_INVALID_PARAMS, "weighted: no frame included");
+    if (table.frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "weighted: no frame included");
+    std::vector<stk_frame_weight> coef;
+    gather_records(table, per_frame, coef);
     if ((st = weighted_check_coefs(ctx, coef, cn))) return st;
-    std::vector<int> entry_frame;
-    if ((st = weighted_table(ctx, frames, M, include, is_affine, entry_frame))) return st;
-    const int ne = (int)entry_frame.size();
+    if ((st = entry_table_begin(ctx, frames, table, is_affine))) return st;
+    const int ne = table.size();
     const bool host = frames->location != STK_DEVICE;       // the planes are where the frames are
     const LocalLayout L = local_layout((size_t)ne, ne, w, h, cn, host ? (size_t)ne : 0);
     if ((st = local_reserve(ctx, L, host ? (size_t)ne : 0))) return st;
@@ -283,16 +275,16 @@ stk_status local_weighted_stack_impl(stk_ctx* ctx, const stk_frames* frames, con
     for (int k = 0; k < ne; k++) {
         if (host) {
             float* d = (float*)(base + L.planes + (size_t)k * L.plane);
-            HIP_TRY(hipMemcpyAsync(d, maps[entry_frame[k]], (size_t)w * h * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(d, maps[table.frame[k]], (size_t)w * h * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
             mptr[k] = d;
-        } else mptr[k] = maps[entry_frame[k]];
+        } else mptr[k] = maps[table.frame[k]];
     }
     HIP_TRY(hipMemcpyAsync(base + L.mptrs, mptr.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
     double ms = 0.0;
     MeshFoldArgs mf{};
-    if (fields && (st = mesh_fold_table(ctx, frames, entry_frame, fields, step, &mf))) return st;
+    if (fields && (st = mesh_fold_table(ctx, frames, table, fields, step, &mf))) return st;
     // (local_fold synchronises: `mptr` outlives the copy)
-    if ((st = local_fold(ctx, L, coef, frames->depth, w, h, cn, frame_row_bytes(frames), alpha, is_affine, floor, power, out, den_out, &ms,
+    if ((st = local_fold(ctx, L, coef, fold_spec(frames, alpha, border_mode, border_value, is_affine), floor, power, out, den_out, &ms,
                          fields ? &mf : nullptr)))
         return st;
     ctx->timing.finalize_ms = ms;
@@ -307,32 +299,10 @@ stk_status stk_ecc_match_local_weighted(stk_ctx* ctx, const stk_frames* frames, 
     if (!ctx) return STK_INVALID_PARAMS;
     stk_status st = local_match_check(ctx, frames, weight, local, out);
     if (st) return st;
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    const LocalLayout L = local_layout((size_t)n, n, w, h, cn, (size_t)n);
-    if ((st = local_reserve(ctx, L, (size_t)n))) return st;
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    // the plain call, on this context's own device, its mean into the workspace image (unused)
-    stk_image_f32 mimg{(float*)(ctx->local.as<char>() + L.image), w, h, cn, STK_DEVICE, 0};
-    if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
-    const stk_timing keep = ctx->timing;
-    // every frame is a sample: frame 0 through the identity, frame i through its warp (as in stk_ecc_match_weighted)
-    const int is_affine = params->motion_type != STK_MOTION_HOMOGRAPHY;
-    std::vector<const void*> dev;
-    resident_frames(ctx, frames, dev);
-    std::vector<WarpFrame> wf(n);
-    std::vector<int> entry_frame(n);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    make_warp_frame(wf[0], dev[0], I3, is_affine);
-    for (int i = 1; i < n; i++) make_warp_frame(wf[i], dev[i], stats[i].warp, is_affine);
-    for (int i = 0; i < n; i++) entry_frame[i] = i;
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, is_affine))) return st;
-    st = local_finish(ctx, L, frames, entry_frame, dev, rb, is_affine, weight, weights, local, out, den_out, applied);
-    const double fin = ctx->timing.finalize_ms;
-    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : fin;
-    return st;
+    LocalLayout L;
+    if ((st = local_match_reserve(ctx, frames, &L))) return st;
+    return ecc_match_then(ctx, frames, params, scale_down_width, (float*)(ctx->local.as<char>() + L.image), stats,
+                          local_match_finish(ctx, L, frames->n, weight, weights, local, out, den_out, applied));
 }
 
 stk_status stk_keypoint_match_local_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
@@ -344,38 +314,10 @@ stk_status stk_keypoint_match_local_weighted(stk_ctx* ctx, const stk_frames* fra
     if (st) return st;
     if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
     if ((st = local_check_border(ctx, params->border_mode, params->border_value))) return st;
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    const LocalLayout L = local_layout((size_t)n, n, w, h, cn, (size_t)n);
-    if ((st = local_reserve(ctx, L, (size_t)n))) return st;
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    stk_image_f32 mimg{(float*)(ctx->local.as<char>() + L.image), w, h, cn, STK_DEVICE, 0};
-    if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
-    const stk_timing keep = ctx->timing;
-    // the samples: frame 0 through the identity and the frames with a homography (status 0), in stack order (as in
-    // stk_keypoint_match_weighted)
-    std::vector<const void*> dev;
-    resident_frames(ctx, frames, dev);
-    std::vector<WarpFrame> wf;
-    std::vector<int> entry_frame;
-    wf.reserve(n);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    wf.emplace_back();
-    make_warp_frame(wf.back(), dev[0], I3, 0);
-    entry_frame.push_back(0);
-    for (int i = 1; i < n; i++) {
-        if (stats[i].status != 0) continue;
-        wf.emplace_back();
-        make_warp_frame(wf.back(), dev[i], stats[i].warp, 0);
-        entry_frame.push_back(i);
-    }
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, 0))) return st;
-    st = local_finish(ctx, L, frames, entry_frame, dev, rb, 0, weight, weights, local, out, den_out, applied);
-    const double fin = ctx->timing.finalize_ms;
-    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : fin;
-    return st;
+    LocalLayout L;
+    if ((st = local_match_reserve(ctx, frames, &L))) return st;
+    return keypoint_match_then(ctx, frames, params, scale_down_width, (float*)(ctx->local.as<char>() + L.image), dropped, stats,
+                               local_match_finish(ctx, L, frames->n, weight, weights, local, out, den_out, applied));
 }
 
 }  // extern "C"

@@ -4,8 +4,8 @@
 // ctx->mesh (grow-only like the other workspaces) holds three pointer tables indexed like the frame table (the fold's
 // fields, the field pass's fields and status planes), the field and status planes the caller does not hold on the device,
 // the fill pass's scratch and a w x h x cn f32 image (the plain call's mean in the whole-stack forms, then a host output's
-// staging copy). The frame table, the checks of the caller-held-warps forms and the local-weighted fold are the weighted
-// and the local combine's (weighted.cpp, local.cpp, through context.h). Like those, the whole-stack forms run the plain
+// staging copy). The frame table is combine.h's; the local-weighted fold and its map pass are the local combine's
+// (local.cpp, through context.h). Like the other combines, the whole-stack forms run the plain
 // call first and take the warps and the kept set from its stats; the frames are still resident in HBM, full size.
 #include <algorithm>
 #include <cmath>
@@ -107,18 +107,17 @@ stk_status mesh_align_entries(stk_ctx* ctx, const MeshLayout& L, int ne, int w, 
 
 // The mesh mean fold over the ne entries of ctx->warpframes with the field table `mf`: sums in fold order, then x
 // (float)(1.0 / ne). `image`: a w x h x cn f32 device buffer for a host output. Synchronises; adds its device time to *ms.
-stk_status mesh_mean_fold(stk_ctx* ctx, int ne, int depth, int w, int h, int cn, size_t rb, double alpha, int border_mode,
-                          const double* border_value, int is_affine, const MeshFoldArgs& mf, float* image, stk_image_f32* out, double* ms) {
+stk_status mesh_mean_fold(stk_ctx* ctx, int ne, const FoldSpec& spec, const MeshFoldArgs& mf, float* image, stk_image_f32* out, double* ms) {
     const bool host = out->location != STK_DEVICE;
-    const size_t nel = (size_t)w * h * cn;
-    WarpArgs a = weighted_warp_args(ctx, ne, depth, w, h, cn, rb, alpha, border_mode, border_value, is_affine);
+    const size_t nel = (size_t)spec.w * spec.h * spec.cn;
+    WarpArgs a = fold_warp_args(ctx, ne, spec);
     a.acc = host ? image : out->data;
-    a.acc_stride = (size_t)w * cn;
+    a.acc_stride = (size_t)spec.w * spec.cn;
     a.accumulate = 0;
     ClipArgs ca{};
     mesh_fold_clip_args(mf, ca);
     HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
-    HIP_TRY(launch_mesh_fold(a, ca, depth, false, ctx->stream));
+    HIP_TRY(launch_mesh_fold(a, ca, spec.depth, false, ctx->stream));
     HIP_TRY(launch_scale(a.acc, a.acc, nel, (float)(1.0 / (double)ne), ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
     if (host) HIP_TRY(hipMemcpyAsync(out->data, a.acc, nel * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -136,7 +135,7 @@ stk_status mesh_match_check(stk_ctx* ctx, const stk_frames* frames, const stk_me
     if ((st = check_frames(ctx, frames, true))) return st;
     if ((st = mesh_check_fold(ctx, mesh->step))) return st;
     if ((st = mesh_check_depth(ctx, frames))) return st;
-    return weighted_check_out(ctx, out, frames);
+    return combine_check_out(ctx, out, frames);
 }
 
 // The field pass of a whole-stack form over the ne entries of ctx->warpframes (entry 0 = frame 0; the table is uploaded):
@@ -161,45 +160,9 @@ stk_status mesh_entry_fields(stk_ctx* ctx, const MeshLayout& L, int ne, int w, i
     return STK_OK;
 }
 
-// the tail of the whole-stack forms: `entry_frame[k]` is the frame index of table entry k (entry 0 = frame 0), `dev` the
-// resident full-size frames by frame index; the frame table is uploaded. Field pass, then the mesh mean fold, or the map
-// pass and the mesh local-weighted fold with unit records.
-stk_status mesh_finish(stk_ctx* ctx, const MeshLayout& L, const stk_frames* frames, const std::vector<int>& entry_frame,
-                       const std::vector<const void*>& dev, size_t rb, int is_affine, int border_mode, const double* border_value,
-                       const stk_mesh_params* mp, const stk_local_params* lp, stk_image_f32* out) {
-    const int w = frames->width, h = frames->height, cn = frames->channels;
-    const int ne = (int)entry_frame.size();
-    const double alpha = 1.0 / 255.0;
-    char* base = ctx->mesh.as<char>();
-    double ms = 0.0;
-    MeshFoldArgs mf{};
-    stk_status st = mesh_entry_fields(ctx, L, ne, w, h, cn, rb, is_affine, mp, &mf, &ms);
-    if (st) return st;
-    if (!lp) {
-        st = mesh_mean_fold(ctx, ne, 8, w, h, cn, rb, alpha, border_mode, border_value, is_affine, mf, (float*)(base + L.image), out, &ms);
-    } else {
-        const LocalLayout LL = local_layout((size_t)ne, ne, w, h, cn, (size_t)ne);
-        char* lbase = ctx->local.as<char>();
-        std::vector<const void*> fptr(ne);
-        std::vector<float*> mptr(ne);
-        for (int k = 0; k < ne; k++) { fptr[k] = dev[entry_frame[k]]; mptr[k] = (float*)(lbase + LL.planes + (size_t)k * LL.plane); }
-        if ((st = local_maps_enqueue(ctx, LL, fptr, mptr))) return st;
-        HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
-        if ((st = local_maps_launch(ctx, LL, 0, (size_t)ne, cn, w, h, rb, lp))) return st;
-        HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-        std::vector<stk_frame_weight> coef(ne);
-        for (stk_frame_weight& e : coef) { weighted_estimate(nullptr, cn, 0, &e); e.weight = 1.0f; }
-        st = local_fold(ctx, LL, coef, 8, w, h, cn, rb, alpha, is_affine, lp->floor, lp->power, out, nullptr, &ms, &mf);
-    }
-    if (st) return st;
-    ctx->timing.finalize_ms = ms;
-    return STK_OK;
-}
-
 // the workspaces of a whole-stack form over n frames, reserved before the plain call writes its mean into ctx->mesh
 stk_status mesh_match_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mp, const stk_local_params* lp, MeshLayout* L) {
+    (void)hipSetDevice(ctx->device);
     const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
     int gw, gh;
     mesh_grid_of(w, h, mp->step, &gw, &gh);
@@ -212,6 +175,32 @@ stk_status mesh_match_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_
     }
     return STK_OK;
 }
+
+// the combine of the whole-stack forms over the kept frames (`dev`: the resident full-size frames by frame index): field
+// pass, then the mesh mean fold, or the map pass and the mesh local-weighted fold with unit records
+CombineFinish mesh_match_finish(stk_ctx* ctx, const MeshLayout& L, const stk_mesh_params* mp, const stk_local_params* lp, stk_image_f32* out) {
+    return [=](const EntryTable& table, const std::vector<const void*>& dev, const FoldSpec& spec, const stk_frame_stats*, double* ms) {
+        const int ne = table.size(), w = spec.w, h = spec.h, cn = spec.cn;
+        const size_t rb = spec.src_row_bytes;
+        MeshFoldArgs mf{};
+        stk_status st = mesh_entry_fields(ctx, L, ne, w, h, cn, rb, spec.is_affine, mp, &mf, ms);
+        if (st) return st;
+        if (!lp) return mesh_mean_fold(ctx, ne, spec, mf, (float*)(ctx->mesh.as<char>() + L.image), out, ms);
+        const LocalLayout LL = local_layout((size_t)ne, ne, w, h, cn, (size_t)ne);
+        char* lbase = ctx->local.as<char>();
+        std::vector<const void*> fptr(ne);
+        std::vector<float*> mptr(ne);
+        for (int k = 0; k < ne; k++) { fptr[k] = dev[table.frame[k]]; mptr[k] = (float*)(lbase + LL.planes + (size_t)k * LL.plane); }
+        if ((st = local_maps_enqueue(ctx, LL, fptr, mptr))) return st;
+        HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+        if ((st = local_maps_launch(ctx, LL, 0, (size_t)ne, cn, w, h, rb, lp))) return st;
+        HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
+        return local_fold(ctx, LL, std::vector<stk_frame_weight>(ne, unit_record()), spec, lp->floor, lp->power, out, nullptr, ms, &mf);
+    };
+}
+
 
 }  // namespace
 
@@ -254,9 +243,9 @@ stk_status mesh_match_fields(stk_ctx* ctx, const stk_frames* frames, int n_entri
                              frame_row_bytes(frames), is_affine, mp, out, ms);
 }
 
-stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const std::vector<int>& entry_frame, const float* const* fields,
-                           int step, MeshFoldArgs* out) {
-    const int ne = (int)entry_frame.size();
+stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const EntryTable& table, const float* const* fields, int step,
+                           MeshFoldArgs* out) {
+    const int ne = table.size();
     const bool host = frames->location != STK_DEVICE;
     int gw, gh;
     mesh_grid_of(frames->width, frames->height, step, &gw, &gh);
@@ -266,7 +255,7 @@ stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const std::ve
     char* base = ctx->mesh.as<char>();
     std::vector<const float*> ptr(ne, nullptr);
     for (int k = 0; k < ne; k++) {
-        const int i = entry_frame[k];
+        const int i = table.frame[k];
         if (i == 0 || !fields[i]) continue;                // frame 0 is the grid's own frame; a null plane: not displaced
         if (host) {
             float* d = (float*)(base + L.fields + (size_t)k * L.fplane);
@@ -323,13 +312,12 @@ stk_status stk_local_align(stk_ctx* ctx, const stk_frames* frames, const double*
     if ((st = mesh_reserve(ctx, L))) return st;
     char* base = ctx->mesh.as<char>();
     double ms = 0.0;
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     for (size_t b0 = 0; b0 < moving.size(); b0 += (size_t)batch) {
         const int nb = (int)std::min<size_t>((size_t)batch, moving.size() - b0);
         std::vector<WarpFrame> wf(nb + 1);
         std::vector<float*> fdev(nb + 1, nullptr);
         std::vector<int32_t*> sdev(nb + 1, nullptr);
-        make_warp_frame(wf[0], host ? (const void*)ctx->frames.p : frames->data[0], I3, is_affine);
+        make_warp_frame(wf[0], host ? (const void*)ctx->frames.p : frames->data[0], IDENTITY3, is_affine);
         for (int k = 1; k <= nb; k++) {
             const int i = moving[b0 + k - 1];
             const void* src = frames->data[i];
@@ -365,24 +353,24 @@ stk_status stk_mesh_stack(stk_ctx* ctx, const stk_frames* frames, const double* 
     if (st) return st;
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
     if (!fields) return fail(ctx, STK_INVALID_PARAMS, "null fields");
-    if (border_mode < 0 || border_mode > 4)
-        return fail(ctx, border_mode == STK_BORDER_TRANSPARENT ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS,
-                    "border mode not supported (BORDER_TRANSPARENT leaves the reference's output uninitialised)");
+    if ((st = check_border_mode(ctx, border_mode))) return st;
     if ((st = mesh_check_fold(ctx, step))) return st;
-    if ((st = weighted_check_out(ctx, out, frames))) return st;
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    for (int i = 1; i < n; i++)
-        if ((!include || include[i]) && !fields[i]) return fail(ctx, STK_INVALID_PARAMS, "null field plane of an included frame");
-    std::vector<int> entry_frame;
-    if ((st = weighted_table(ctx, frames, M, include, is_affine, entry_frame))) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    EntryTable table;
+    entries_from_include(frames->n, M, include, table);
+    for (int i : table.frame)
+        if (i > 0 && !fields[i]) return fail(ctx, STK_INVALID_PARAMS, "null field plane of an included frame");
+    if (table.frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "weighted: no frame included");
+    if ((st = entry_table_begin(ctx, frames, table, is_affine))) return st;
     MeshFoldArgs mf{};
-    if ((st = mesh_fold_table(ctx, frames, entry_frame, fields, step, &mf))) return st;
+    if ((st = mesh_fold_table(ctx, frames, table, fields, step, &mf))) return st;
     // (mesh_fold_table's layout: the image follows the planes it uploaded)
     const bool host = frames->location != STK_DEVICE;
-    const MeshLayout L = mesh_layout(entry_frame.size(), host ? entry_frame.size() : 0, 0, 0, mf.gw, mf.gh, (size_t)w * h * cn);
+    const size_t ne = table.frame.size();
+    const MeshLayout L = mesh_layout(ne, host ? ne : 0, 0, 0, mf.gw, mf.gh, (size_t)frames->width * frames->height * frames->channels);
     double ms = 0.0;
-    if ((st = mesh_mean_fold(ctx, (int)entry_frame.size(), frames->depth, w, h, cn, frame_row_bytes(frames), alpha, border_mode, border_value,
-                             is_affine, mf, (float*)(ctx->mesh.as<char>() + L.image), out, &ms)))
+    if ((st = mesh_mean_fold(ctx, (int)ne, fold_spec(frames, alpha, border_mode, border_value, is_affine), mf,
+                             (float*)(ctx->mesh.as<char>() + L.image), out, &ms)))
         return st;
     ctx->timing.finalize_ms = ms;
     return STK_OK;
@@ -404,32 +392,10 @@ stk_status stk_ecc_match_local_aligned(stk_ctx* ctx, const stk_frames* frames, c
     if (!ctx) return STK_INVALID_PARAMS;
     stk_status st = mesh_match_check(ctx, frames, mesh, local, out);
     if (st) return st;
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
     MeshLayout L;
     if ((st = mesh_match_reserve(ctx, frames, mesh, local, &L))) return st;
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    // the plain call, on this context's own device, its mean into the workspace image (unused)
-    stk_image_f32 mimg{(float*)(ctx->mesh.as<char>() + L.image), w, h, cn, STK_DEVICE, 0};
-    if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
-    const stk_timing keep = ctx->timing;
-    // every frame is a sample: frame 0 through the identity, frame i through its warp (as in stk_ecc_match_weighted)
-    const int is_affine = params->motion_type != STK_MOTION_HOMOGRAPHY;
-    std::vector<const void*> dev;
-    resident_frames(ctx, frames, dev);
-    std::vector<WarpFrame> wf(n);
-    std::vector<int> entry_frame(n);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    make_warp_frame(wf[0], dev[0], I3, is_affine);
-    for (int i = 1; i < n; i++) make_warp_frame(wf[i], dev[i], stats[i].warp, is_affine);
-    for (int i = 0; i < n; i++) entry_frame[i] = i;
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, is_affine))) return st;
-    st = mesh_finish(ctx, L, frames, entry_frame, dev, rb, is_affine, STK_BORDER_CONSTANT, nullptr, mesh, local, out);
-    const double fin = ctx->timing.finalize_ms;
-    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : fin;
-    return st;
+    return ecc_match_then(ctx, frames, params, scale_down_width, (float*)(ctx->mesh.as<char>() + L.image), stats,
+                          mesh_match_finish(ctx, L, mesh, local, out));
 }
 
 stk_status stk_keypoint_match_local_aligned(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
@@ -440,38 +406,10 @@ stk_status stk_keypoint_match_local_aligned(stk_ctx* ctx, const stk_frames* fram
     if (st) return st;
     if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
     if (local && (st = local_check_border(ctx, params->border_mode, params->border_value))) return st;
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
     MeshLayout L;
     if ((st = mesh_match_reserve(ctx, frames, mesh, local, &L))) return st;
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    stk_image_f32 mimg{(float*)(ctx->mesh.as<char>() + L.image), w, h, cn, STK_DEVICE, 0};
-    if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
-    const stk_timing keep = ctx->timing;
-    // the samples: frame 0 through the identity and the frames with a homography (status 0), in stack order, with the
-    // params' border (as in stk_keypoint_match_weighted)
-    std::vector<const void*> dev;
-    resident_frames(ctx, frames, dev);
-    std::vector<WarpFrame> wf;
-    std::vector<int> entry_frame;
-    wf.reserve(n);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    wf.emplace_back();
-    make_warp_frame(wf.back(), dev[0], I3, 0);
-    entry_frame.push_back(0);
-    for (int i = 1; i < n; i++) {
-        if (stats[i].status != 0) continue;
-        wf.emplace_back();
-        make_warp_frame(wf.back(), dev[i], stats[i].warp, 0);
-        entry_frame.push_back(i);
-    }
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, 0))) return st;
-    st = mesh_finish(ctx, L, frames, entry_frame, dev, rb, 0, params->border_mode, params->border_value, mesh, local, out);
-    const double fin = ctx->timing.finalize_ms;
-    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : fin;
-    return st;
+    return keypoint_match_then(ctx, frames, params, scale_down_width, (float*)(ctx->mesh.as<char>() + L.image), dropped, stats,
+                               mesh_match_finish(ctx, L, mesh, local, out));
 }
 
 }  // extern "C"

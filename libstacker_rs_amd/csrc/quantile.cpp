@@ -5,7 +5,7 @@
 // kernel reduces them to R output rows. ctx->quantile holds a w x h x cn f32 image (the plain call's mean in the
 // whole-stack forms, then a host output's staging copy) followed by the band. It is grow-only like the other workspaces;
 // R is sized to a 4 GiB band (option quantile_band_rows caps it). Like clip.cpp, the whole-stack forms run the plain call
-// first and take the warps and the kept set from its stats; the frames are still resident in HBM.
+// first and take the warps and the kept set from its stats (combine.h); the frames are still resident in HBM.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -26,14 +26,6 @@ stk_status quantile_validate(stk_ctx* ctx, const stk_quantile_params* p) {
     if (!(p->quantile >= 0.0f && p->quantile <= 1.0f))
         return fail(ctx, STK_INVALID_PARAMS, "quantile must be in [0, 1], got " + std::to_string(p->quantile));
     if (p->reserved != 0) return fail(ctx, STK_INVALID_PARAMS, "quantile parameters: reserved must be 0");
-    return STK_OK;
-}
-
-stk_status quantile_check_out(stk_ctx* ctx, const stk_image_f32* out, const stk_frames* f) {
-    stk_status st = image_check(ctx, out, f->width, f->height, f->channels);
-    if (st) return st;
-    if (out->row_stride_bytes && out->row_stride_bytes != (size_t)f->width * f->channels * sizeof(float))
-        return fail(ctx, STK_INVALID_PARAMS, "output must be tightly packed");
     return STK_OK;
 }
 
@@ -64,11 +56,10 @@ stk_status quantile_reserve(stk_ctx* ctx, int n, int w, int h, int cn) {
 namespace {
 
 // The combine over the n_frames entries of ctx->warpframes (uploaded for the w x h destination): per band a store launch,
-// then a selection launch into `out` (device) or the staging image (host, one copy back at the end). Sets
-// stk_timing.finalize_ms to the device time of all bands.
-stk_status quantile_bands(stk_ctx* ctx, int n_frames, int depth, int w, int h, int cn, size_t src_row_bytes, double alpha,
-                          int border_mode, const double* border_value, int is_affine, const stk_quantile_params* p,
-                          stk_image_f32* out) {
+// then a selection launch into `out` (device) or the staging image (host, one copy back at the end). Adds the device time
+// of all bands to *ms.
+stk_status quantile_bands(stk_ctx* ctx, int n_frames, const FoldSpec& spec, const stk_quantile_params* p, stk_image_f32* out, double* ms) {
+    const int w = spec.w, h = spec.h, cn = spec.cn, depth = spec.depth;
     stk_status st = quantile_check_count(ctx, n_frames);
     if (st) return st;
     if ((st = quantile_reserve(ctx, n_frames, w, h, cn))) return st;
@@ -82,16 +73,7 @@ stk_status quantile_bands(stk_ctx* ctx, int n_frames, int depth, int w, int h, i
     const float jf = std::floor(vi);
     const float g = vi - jf;
     const int j = (int)jf;
-    WarpArgs a{};
-    a.frames = ctx->warpframes.as<WarpFrame>();
-    a.n_frames = n_frames;
-    a.sw = w; a.sh = h; a.cn = cn;
-    a.src_stride = src_row_bytes / (depth / 8);
-    a.alpha = (float)alpha;
-    a.border_mode = border_mode;
-    for (int k = 0; k < 4; k++) a.bv[k] = border_value ? (float)border_value[k] : 0.f;
-    a.acc = nullptr; a.dw = w; a.acc_stride = 0;
-    a.is_affine = is_affine; a.subpixel_bits = ctx->opt_subpixel_bits; a.tune = 0; a.interp = ctx->opt_interp;
+    WarpArgs a = fold_warp_args(ctx, n_frames, spec);      // (dh: per band)
     ClipArgs ca{};
     ca.band = band;
     ca.plane_stride = row;
@@ -106,8 +88,27 @@ stk_status quantile_bands(stk_ctx* ctx, int n_frames, int depth, int w, int h, i
     HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
     if (host) HIP_TRY(hipMemcpyAsync(out->data, img, (size_t)h * row * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->timing.finalize_ms = ev_ms(ctx->ev[4], ctx->ev[5]);
+    *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
     return STK_OK;
+}
+
+// the checks and the workspace of the two whole-stack forms: the image only (the plain call's mean lands in front of the
+// band, unused); the band comes after the plain call
+stk_status quantile_match_begin(stk_ctx* ctx, const stk_frames* frames, const stk_quantile_params* quantile, const stk_image_f32* out) {
+    stk_status st = quantile_validate(ctx, quantile);
+    if (st) return st;
+    if ((st = check_frames(ctx, frames, true))) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    if ((st = quantile_check_count(ctx, frames->n))) return st;
+    (void)hipSetDevice(ctx->device);
+    return quantile_reserve(ctx, 0, frames->width, frames->height, frames->channels);
+}
+
+// and their combine over the kept frames
+CombineFinish quantile_match_finish(stk_ctx* ctx, const stk_quantile_params* quantile, stk_image_f32* out) {
+    return [=](const EntryTable& table, const std::vector<const void*>&, const FoldSpec& spec, const stk_frame_stats*, double* ms) {
+        return quantile_bands(ctx, table.size(), spec, quantile, out, ms);
+    };
 }
 
 }  // namespace
@@ -120,102 +121,36 @@ stk_status stk_quantile_stack(stk_ctx* ctx, const stk_frames* frames, const doub
     stk_status st = check_frames(ctx, frames, false);
     if (st) return st;
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
-    if (border_mode < 0 || border_mode > 4)
-        return fail(ctx, border_mode == STK_BORDER_TRANSPARENT ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS,
-                    "border mode not supported (BORDER_TRANSPARENT leaves the reference's output uninitialised)");
+    if ((st = check_border_mode(ctx, border_mode))) return st;
     if ((st = quantile_validate(ctx, quantile))) return st;
-    if ((st = quantile_check_out(ctx, out, frames))) return st;
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    int n_in = 0;
-    for (int i = 0; i < n; i++) n_in += (!include || include[i]) ? 1 : 0;
-    if (n_in == 0) return fail(ctx, STK_INVALID_PARAMS, "quantile: no frame included");
-    if ((st = quantile_check_count(ctx, n_in))) return st;
-    (void)hipSetDevice(ctx->device);
-    timing_begin(ctx);
-    std::vector<const void*> dev;
-    if ((st = resolve_frames(ctx, frames, dev))) return st;
-    std::vector<WarpFrame> wf;
-    wf.reserve(n_in);
-    for (int i = 0; i < n; i++) {
-        if (include && !include[i]) continue;
-        wf.emplace_back();
-        make_warp_frame(wf.back(), dev[i], M + 9 * (size_t)i, is_affine);
-    }
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, is_affine))) return st;
-    return quantile_bands(ctx, n_in, frames->depth, w, h, cn, rb, alpha, border_mode, border_value, is_affine, quantile, out);
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    EntryTable table;
+    entries_from_include(frames->n, M, include, table);
+    if (table.frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "quantile: no frame included");
+    if ((st = quantile_check_count(ctx, table.size()))) return st;
+    if ((st = entry_table_begin(ctx, frames, table, is_affine))) return st;
+    double ms = 0.0;
+    if ((st = quantile_bands(ctx, table.size(), fold_spec(frames, alpha, border_mode, border_value, is_affine), quantile, out, &ms))) return st;
+    ctx->timing.finalize_ms = ms;
+    return STK_OK;
 }
 
 stk_status stk_ecc_match_quantile(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
                                   const stk_quantile_params* quantile, stk_image_f32* out, stk_frame_stats* stats) {
     if (!ctx) return STK_INVALID_PARAMS;
-    stk_status st = quantile_validate(ctx, quantile);
+    stk_status st = quantile_match_begin(ctx, frames, quantile, out);
     if (st) return st;
-    if ((st = check_frames(ctx, frames, true))) return st;
-    if ((st = quantile_check_out(ctx, out, frames))) return st;
-    if ((st = quantile_check_count(ctx, frames->n))) return st;
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    if ((st = quantile_reserve(ctx, 0, w, h, cn))) return st;        // the image only: the band comes after the plain call
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    // the plain call, on this context's own device, its mean into the image in front of the band (unused)
-    stk_image_f32 mimg{ctx->quantile.as<float>(), w, h, cn, STK_DEVICE, 0};
-    if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
-    const stk_timing keep = ctx->timing;
-    // every frame is a sample: frame 0 through the identity, frame i through its warp (as in stk_ecc_match_clipped)
-    const int is_affine = params->motion_type != STK_MOTION_HOMOGRAPHY;
-    std::vector<const void*> dev;
-    resident_frames(ctx, frames, dev);
-    std::vector<WarpFrame> wf(n);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    make_warp_frame(wf[0], dev[0], I3, is_affine);
-    for (int i = 1; i < n; i++) make_warp_frame(wf[i], dev[i], stats[i].warp, is_affine);
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, is_affine))) return st;
-    st = quantile_bands(ctx, n, frames->depth, w, h, cn, rb, 1.0 / 255.0, STK_BORDER_CONSTANT, nullptr, is_affine, quantile, out);
-    const double fin = ctx->timing.finalize_ms;
-    ctx->timing = keep; ctx->timing.finalize_ms = fin;
-    return st;
+    return ecc_match_then(ctx, frames, params, scale_down_width, ctx->quantile.as<float>(), stats, quantile_match_finish(ctx, quantile, out));
 }
 
 stk_status stk_keypoint_match_quantile(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,
                                        const stk_quantile_params* quantile, stk_image_f32* out, int32_t* dropped,
                                        stk_frame_stats* stats) {
     if (!ctx) return STK_INVALID_PARAMS;
-    stk_status st = quantile_validate(ctx, quantile);
+    stk_status st = quantile_match_begin(ctx, frames, quantile, out);
     if (st) return st;
-    if ((st = check_frames(ctx, frames, true))) return st;
-    if ((st = quantile_check_out(ctx, out, frames))) return st;
-    if ((st = quantile_check_count(ctx, frames->n))) return st;
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    if ((st = quantile_reserve(ctx, 0, w, h, cn))) return st;        // the image only: the band comes after the plain call
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    stk_image_f32 mimg{ctx->quantile.as<float>(), w, h, cn, STK_DEVICE, 0};
-    if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
-    const stk_timing keep = ctx->timing;
-    // the samples: frame 0 through the identity and the frames with a homography (status 0), in stack order, with the
-    // params' border (as in stk_keypoint_match_clipped)
-    std::vector<const void*> dev;
-    resident_frames(ctx, frames, dev);
-    std::vector<WarpFrame> wf;
-    wf.reserve(n);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    wf.emplace_back();
-    make_warp_frame(wf.back(), dev[0], I3, 0);
-    for (int i = 1; i < n; i++) {
-        if (stats[i].status != 0) continue;
-        wf.emplace_back();
-        make_warp_frame(wf.back(), dev[i], stats[i].warp, 0);
-    }
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, 0))) return st;
-    st = quantile_bands(ctx, (int)wf.size(), 8, w, h, cn, rb, 1.0 / 255.0, params->border_mode, params->border_value, 0, quantile, out);
-    const double fin = ctx->timing.finalize_ms;
-    ctx->timing = keep; ctx->timing.finalize_ms = fin;
-    return st;
+    return keypoint_match_then(ctx, frames, params, scale_down_width, ctx->quantile.as<float>(), dropped, stats,
+                               quantile_match_finish(ctx, quantile, out));
 }
 
 }  // extern "C"

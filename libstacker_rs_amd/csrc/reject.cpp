@@ -50,23 +50,22 @@ stk_status reject_validate(stk_ctx* ctx, const stk_reject_params* p) {
     return STK_OK;
 }
 
-// The pass over `dev[entry_frame[k]]` under the FORWARD matrices Ms[k] (9 doubles each) with the records `coef` (per
-// entry). clean, counts (or null), in[k] (or null; never out[k]) and out[k] are device memory; ctx->reject is reserved for
-// L. Writes the planes, synchronises, leaves the counters per entry in rejected / judged (or null) and adds the launch's
+// The pass over the table's entries, `dev[table.frame[k]]` under the FORWARD matrices table.M[k], with the records `coef`
+// (per entry). clean, counts (or null), in[k] (or null; never out[k]) and out[k] are device memory; ctx->reject is reserved
+// for L. Writes the planes, synchronises, leaves the counters per entry in rejected / judged (or null) and adds the launch's
 // device time to *ms.
 stk_status reject_run(stk_ctx* ctx, const RejectLayout& L, const stk_frames* frames, const std::vector<const void*>& dev,
-                      const std::vector<int>& entry_frame, const std::vector<const double*>& Ms, int is_affine, double alpha,
-                      const std::vector<stk_frame_weight>& coef, const float* clean, const int32_t* counts,
-                      const stk_reject_params* p, const std::vector<const float*>& in, const std::vector<float*>& out,
-                      int64_t* rejected, int64_t* judged, double* ms) {
-    const int ne = (int)entry_frame.size();
+                      const EntryTable& table, int is_affine, double alpha, const std::vector<stk_frame_weight>& coef, const float* clean,
+                      const int32_t* counts, const stk_reject_params* p, const std::vector<const float*>& in,
+                      const std::vector<float*>& out, int64_t* rejected, int64_t* judged, double* ms) {
+    const int ne = table.size();
     char* base = ctx->reject.as<char>();
     std::vector<RejectEntry> tab(ne);
     for (int k = 0; k < ne; k++) {
         RejectEntry& e = tab[k];
         std::memset(&e, 0, sizeof(e));
-        e.f.src = dev[entry_frame[k]];
-        for (int j = 0; j < 9; j++) { e.f.Md[j] = Ms[k][j]; e.f.M[j] = (float)Ms[k][j]; }
+        e.f.src = dev[table.frame[k]];
+        for (int j = 0; j < 9; j++) { e.f.Md[j] = table.M[k][j]; e.f.M[j] = (float)table.M[k][j]; }
         for (int c = 0; c < 4; c++) { e.gain[c] = coef[k].gain[c]; e.offset[c] = coef[k].offset[c]; }
         e.map_in = in[k];
         e.map_out = out[k];
@@ -116,24 +115,19 @@ stk_status stk_reject_maps(stk_ctx* ctx, const stk_frames* frames, const double*
     if (!maps_out) return fail(ctx, STK_INVALID_PARAMS, "null output maps");
     const int n = frames->n, sw = frames->width, sh = frames->height, cn = frames->channels;
     const bool host = frames->location != STK_DEVICE;
-    std::vector<int> entry_frame;
-    std::vector<stk_frame_weight> coef;
-    std::vector<const double*> Ms;
+    EntryTable table;
+    entries_from_include(n, M, include, table);
+    const std::vector<int>& entry_frame = table.frame;
     size_t n_in = 0, n_alias = 0;
-    for (int i = 0; i < n; i++) {
-        if (include && !include[i]) continue;
+    for (int i : entry_frame) {
         if (!maps_out[i]) return fail(ctx, STK_INVALID_PARAMS, "reject maps: an included frame has no output plane");
-        stk_frame_weight e;
-        if (per_frame) e = per_frame[i];
-        else { for (int c = 0; c < 4; c++) { e.gain[c] = 1.0f; e.offset[c] = 0.0f; } e.weight = 1.0f; e.flags = 0; }
-        entry_frame.push_back(i);
-        coef.push_back(e);
-        Ms.push_back(M + 9 * (size_t)i);
         if (maps_in && maps_in[i]) { n_in++; if (maps_in[i] == maps_out[i]) n_alias++; }
     }
-    if (coef.empty()) return fail(ctx, STK_INVALID_PARAMS, "reject maps: no frame included");
+    if (entry_frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "reject maps: no frame included");
+    std::vector<stk_frame_weight> coef;
+    gather_records(table, per_frame, coef);
     if ((st = weighted_check_coefs(ctx, coef, cn))) return st;
-    const int ne = (int)coef.size();
+    const int ne = table.size();
     (void)hipSetDevice(ctx->device);
     timing_begin(ctx);
     // host: the clean image, the counts, the input planes and the output planes are staged; device: the in-place planes
@@ -169,7 +163,7 @@ stk_status stk_reject_maps(stk_ctx* ctx, const stk_frames* frames, const double*
     }
     std::vector<int64_t> rej(ne), jud(ne);
     double ms = 0.0;
-    if ((st = reject_run(ctx, L, frames, dev, entry_frame, Ms, is_affine != 0, alpha, coef, dclean, dcounts, reject, in, out, rej.data(),
+    if ((st = reject_run(ctx, L, frames, dev, table, is_affine != 0, alpha, coef, dclean, dcounts, reject, in, out, rej.data(),
                          jud.data(), &ms)))
         return st;
     if (host) {

@@ -6,8 +6,8 @@
 // mean: an entry is a sample of a pixel only if its weight is > 0 and (coverage = 1) the frame covers the pixel, and the
 // samples are compared after each frame has been mapped onto frame 0's level. The workspaces are the plain combines'
 // (ctx->clip: the c, L and U planes; ctx->quantile: an image, then the band); the record table lives in ctx->coef. The
-// whole-stack forms run the plain call first, like clip.cpp, then the moments pass and the estimator of weighted.cpp
-// (both unchanged) when normalize != 0, then the combine.
+// whole-stack forms run the plain call first, like clip.cpp (combine.h's scaffold), then the moments pass and the estimator
+// of weighted.cpp (weighted_match_records) when normalize != 0, then the combine.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -19,9 +19,8 @@ using namespace stk;
 namespace {
 
 stk_status robust_check_border(stk_ctx* ctx, int border_mode, int coverage) {
-    if (border_mode < 0 || border_mode > 4)
-        return fail(ctx, border_mode == STK_BORDER_TRANSPARENT ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS,
-                    "border mode not supported (BORDER_TRANSPARENT leaves the reference's output uninitialised)");
+    stk_status st = check_border_mode(ctx, border_mode);
+    if (st) return st;
     if (coverage < 0 || coverage > 1) return fail(ctx, STK_INVALID_PARAMS, "weighted: coverage must be 0 or 1");
     return STK_OK;
 }
@@ -35,13 +34,13 @@ stk_status coef_upload(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef) 
 
 // The weighted clip over the entries of ctx->warpframes with the records `coef`: the centre pass, then iterations + 1
 // passes. Writes `out`, `counts` and `kept` (out's location); adds its device time to *ms.
-stk_status clip_passes_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, int depth, int w, int h, int cn,
-                                size_t src_row_bytes, double alpha, int border_mode, const double* border_value, int is_affine,
-                                int coverage, const stk_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms) {
-    const size_t nel = (size_t)w * h * cn;
+stk_status clip_passes_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage,
+                                const stk_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms) {
+    const int w = spec.w, cn = spec.cn, depth = spec.depth;
+    const size_t nel = (size_t)w * spec.h * cn;
     HIP_TRY(ctx->clip.reserve(3 * nel * sizeof(float)));
     float* c = ctx->clip.as<float>();
-    const WarpArgs a = weighted_warp_args(ctx, (int)coef.size(), depth, w, h, cn, src_row_bytes, alpha, border_mode, border_value, is_affine);
+    const WarpArgs a = fold_warp_args(ctx, (int)coef.size(), spec);
     stk_status st = coef_upload(ctx, coef);
     if (st) return st;
     const bool host = out->location != STK_DEVICE;
@@ -78,10 +77,9 @@ stk_status clip_passes_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight
 
 // The quantile with participation over the entries of ctx->warpframes: per band a store launch (normalised samples and
 // absent marks), then the selection with a per-pixel rank. `counts` (w x h, out's location) is optional.
-stk_status quantile_bands_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, int depth, int w, int h, int cn,
-                                   size_t src_row_bytes, double alpha, int border_mode, const double* border_value, int is_affine,
-                                   int coverage, const stk_quantile_params* p, stk_image_f32* out, int32_t* counts, double* ms) {
-    const int n_entries = (int)coef.size();
+stk_status quantile_bands_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage,
+                                   const stk_quantile_params* p, stk_image_f32* out, int32_t* counts, double* ms) {
+    const int n_entries = (int)coef.size(), w = spec.w, h = spec.h, cn = spec.cn, depth = spec.depth;
     stk_status st = quantile_check_count(ctx, n_entries);
     if (st) return st;
     const bool host = out->location != STK_DEVICE;
@@ -93,7 +91,7 @@ stk_status quantile_bands_weighted(stk_ctx* ctx, const std::vector<stk_frame_wei
     float* band = img + img_floats;
     float* dst = host ? img : out->data;
     int* cdst = counts ? (host ? (int*)(band + band_floats) : counts) : nullptr;
-    WarpArgs a = weighted_warp_args(ctx, n_entries, depth, w, h, cn, src_row_bytes, alpha, border_mode, border_value, is_affine);
+    WarpArgs a = fold_warp_args(ctx, n_entries, spec);
     if ((st = coef_upload(ctx, coef))) return st;
     ClipArgs ca{};
     ca.band = band;
@@ -119,77 +117,24 @@ stk_status quantile_bands_weighted(stk_ctx* ctx, const std::vector<stk_frame_wei
     return STK_OK;
 }
 
-// the caller-held-warps forms: argument checks, the records of the included frames, the frame table
-stk_status robust_table(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int is_affine,
-                        const stk_frame_weight* per_frame, const char* what, std::vector<stk_frame_weight>& coef) {
+int count_included(const stk_frames* frames, const int32_t* include) {
+    int n_in = 0;
+    for (int i = 0; i < frames->n; i++) n_in += (!include || include[i]) ? 1 : 0;
+    return n_in;
+}
+
+// the caller-held-warps forms: the last argument checks, the records of the included frames, the frame table
+stk_status robust_stack_begin(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int is_affine,
+                              const stk_frame_weight* per_frame, const char* what, std::vector<stk_frame_weight>& coef) {
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
     if (!per_frame) return fail(ctx, STK_INVALID_PARAMS, "null per-frame records");
-    const int n = frames->n, w = frames->width, h = frames->height;
-    std::vector<int> entry_frame;
-    for (int i = 0; i < n; i++) if (!include || include[i]) { entry_frame.push_back(i); coef.push_back(per_frame[i]); }
-    if (coef.empty()) return fail(ctx, STK_INVALID_PARAMS, std::string(what) + ": no frame included");
+    EntryTable table;
+    entries_from_include(frames->n, M, include, table);
+    if (table.frame.empty()) return fail(ctx, STK_INVALID_PARAMS, std::string(what) + ": no frame included");
+    gather_records(table, per_frame, coef);
     stk_status st = weighted_check_coefs(ctx, coef, frames->channels);
     if (st) return st;
-    (void)hipSetDevice(ctx->device);
-    timing_begin(ctx);
-    std::vector<const void*> dev;
-    if ((st = resolve_frames(ctx, frames, dev))) return st;
-    std::vector<WarpFrame> wf(entry_frame.size());
-    for (size_t k = 0; k < entry_frame.size(); k++) make_warp_frame(wf[k], dev[entry_frame[k]], M + 9 * (size_t)entry_frame[k], is_affine);
-    if ((st = warp_table_upload(ctx, wf, frame_row_bytes(frames), w, h, is_affine))) return st;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));       // `wf` leaves scope
-    return STK_OK;
-}
-
-// the whole-stack forms: the frame table of the kept frames (entry 0 = frame 0 under the identity) from the plain call's
-// stats, as clip.cpp builds it; `keypoint`: frames with a non-zero status are no entries
-stk_status robust_stack_table(stk_ctx* ctx, const stk_frames* frames, const stk_frame_stats* stats, bool keypoint, int is_affine,
-                              std::vector<int>& entry_frame) {
-    const int n = frames->n;
-    std::vector<const void*> dev;
-    resident_frames(ctx, frames, dev);
-    std::vector<WarpFrame> wf;
-    wf.reserve(n);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    for (int i = 0; i < n; i++) {
-        if (i > 0 && keypoint && stats[i].status != 0) continue;
-        wf.emplace_back();
-        make_warp_frame(wf.back(), dev[i], i == 0 ? I3 : stats[i].warp, is_affine);
-        entry_frame.push_back(i);
-    }
-    stk_status st = warp_table_upload(ctx, wf, frame_row_bytes(frames), frames->width, frames->height, is_affine);
-    if (st) return st;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));       // `wf` leaves scope
-    return STK_OK;
-}
-
-// the records of the table's entries, as stk_*_match_weighted makes them: the moments pass and the estimator when
-// normalize != 0, the caller's weights by frame index; `applied` by frame index (a dropped frame: weight 0, gains 1)
-stk_status robust_coefs(stk_ctx* ctx, const stk_frames* frames, const std::vector<int>& entry_frame, int depth, int border_mode,
-                        const double* border_value, int is_affine, const stk_weight_params* p, const float* weights,
-                        std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms) {
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    const int ne = (int)entry_frame.size();
-    coef.resize(ne);
-    std::vector<double> mom((size_t)std::max(ne - 1, 0) * cn * 6);
-    if (p->normalize != 0 && ne > 1) {
-        const int step = p->stat_step ? p->stat_step : 4;
-        stk_status st = weighted_moments(ctx, ne, depth, w, h, cn, frame_row_bytes(frames), 1.0 / 255.0, border_mode, border_value,
-                                         is_affine, step, mom.data(), ms);
-        if (st) return st;
-    }
-    for (int k = 0; k < ne; k++) {
-        if (k == 0) weighted_estimate(nullptr, cn, 0, &coef[k]);
-        else weighted_estimate(mom.data() + (size_t)(k - 1) * cn * 6, cn, p->normalize, &coef[k]);
-        coef[k].weight = weights ? weights[entry_frame[k]] : 1.0f;
-    }
-    stk_status st = weighted_check_coefs(ctx, coef, cn);
-    if (st) return st;
-    if (applied) {
-        for (int i = 0; i < n; i++) { weighted_estimate(nullptr, cn, 0, &applied[i]); applied[i].weight = 0.0f; }
-        for (int k = 0; k < ne; k++) applied[entry_frame[k]] = coef[k];
-    }
-    return STK_OK;
+    return entry_table_begin(ctx, frames, table, is_affine);
 }
 
 struct RobustCombine {
@@ -206,94 +151,76 @@ stk_status robust_validate(stk_ctx* ctx, const RobustCombine& rc, const stk_weig
     if (st) return st;
     if ((st = weighted_validate(ctx, weight))) return st;
     if ((st = check_frames(ctx, frames, true))) return st;
-    if ((st = clip_check_out(ctx, out, frames))) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
     if (!rc.clip && (st = quantile_check_count(ctx, frames->n))) return st;
     return STK_OK;
 }
 
-// the tail of the whole-stack forms, after the plain call: table, records, combine; finalize_ms = moments + combine
-stk_status robust_finish(stk_ctx* ctx, const stk_frames* frames, const stk_frame_stats* stats, bool keypoint, int depth, int border_mode,
-                         const double* border_value, int is_affine, const stk_weight_params* weight, const float* weights,
-                         const RobustCombine& rc, stk_image_f32* out, stk_frame_weight* applied) {
+// the combine's workspace image, which takes the plain call's mean (unused)
+stk_status robust_reserve(stk_ctx* ctx, const RobustCombine& rc, const stk_frames* frames, float** mean) {
+    (void)hipSetDevice(ctx->device);
     const int w = frames->width, h = frames->height, cn = frames->channels;
-    const stk_timing keep = ctx->timing;
-    std::vector<int> entry_frame;
-    std::vector<stk_frame_weight> coef;
-    double ms = 0.0;
-    stk_status st = robust_stack_table(ctx, frames, stats, keypoint, is_affine, entry_frame);
-    if (!st) st = robust_coefs(ctx, frames, entry_frame, depth, border_mode, border_value, is_affine, weight, weights, coef, applied, &ms);
-    const size_t rb = frame_row_bytes(frames);
-    if (!st) {
-        if (rc.clip)
-            st = clip_passes_weighted(ctx, coef, depth, w, h, cn, rb, 1.0 / 255.0, border_mode, border_value, is_affine, weight->coverage,
-                                      rc.clip, out, rc.counts, rc.kept, &ms);
-        else if (rc.mad)
-            st = robust_clip_bands(ctx, (int)coef.size(), &coef, depth, w, h, cn, rb, 1.0 / 255.0, border_mode, border_value, is_affine,
-                                   weight->coverage, rc.mad, out, rc.counts, rc.kept, &ms);
-        else
-            st = quantile_bands_weighted(ctx, coef, depth, w, h, cn, rb, 1.0 / 255.0, border_mode, border_value, is_affine,
-                                         weight->coverage, rc.quantile, out, rc.counts, &ms);
-    }
-    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : ms;
-    return st;
+    const bool planes = rc.clip || rc.mad;
+    if (planes) HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
+    else if (stk_status st = quantile_reserve(ctx, 0, w, h, cn)) return st;
+    *mean = planes ? ctx->clip.as<float>() : ctx->quantile.as<float>();
+    return STK_OK;
+}
+
+// the combine of the whole-stack forms over the kept frames: records, then the combine; finalize_ms = moments + combine
+CombineFinish robust_finish(stk_ctx* ctx, int n, const stk_weight_params* weight, const float* weights, const RobustCombine& rc,
+                            stk_image_f32* out, stk_frame_weight* applied) {
+    return [=](const EntryTable& table, const std::vector<const void*>&, const FoldSpec& spec, const stk_frame_stats*, double* ms) {
+        std::vector<stk_frame_weight> coef;
+        stk_status st = weighted_match_records(ctx, n, table, spec, weight, weights, coef, applied, ms);
+        if (st) return st;
+        if (rc.clip) return clip_passes_weighted(ctx, coef, spec, weight->coverage, rc.clip, out, rc.counts, rc.kept, ms);
+        if (rc.mad) return robust_clip_bands(ctx, (int)coef.size(), &coef, spec, weight->coverage, rc.mad, out, rc.counts, rc.kept, ms);
+        return quantile_bands_weighted(ctx, coef, spec, weight->coverage, rc.quantile, out, rc.counts, ms);
+    };
 }
 
 stk_status robust_ecc(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
                       const stk_weight_params* weight, const float* weights, const RobustCombine& rc, stk_image_f32* out,
                       stk_frame_weight* applied, stk_frame_stats* stats) {
-    if (!ctx) return STK_INVALID_PARAMS;
     stk_status st = robust_validate(ctx, rc, weight, frames, out);
     if (st) return st;
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    // the plain call, on this context's own device, its mean into the combine's workspace image (unused)
-    const bool planes = rc.clip || rc.mad;
-    if (planes) HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
-    else if ((st = quantile_reserve(ctx, 0, w, h, cn))) return st;
-    stk_image_f32 mimg{planes ? ctx->clip.as<float>() : ctx->quantile.as<float>(), w, h, cn, STK_DEVICE, 0};
-    if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
-    const int is_affine = params->motion_type != STK_MOTION_HOMOGRAPHY;
-    return robust_finish(ctx, frames, stats, false, frames->depth, STK_BORDER_CONSTANT, nullptr, is_affine, weight, weights, rc, out, applied);
+    float* mean = nullptr;
+    if ((st = robust_reserve(ctx, rc, frames, &mean))) return st;
+    return ecc_match_then(ctx, frames, params, scale_down_width, mean, stats, robust_finish(ctx, frames->n, weight, weights, rc, out, applied));
 }
 
 stk_status robust_keypoint(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,
                            const stk_weight_params* weight, const float* weights, const RobustCombine& rc, stk_image_f32* out,
                            int32_t* dropped, stk_frame_weight* applied, stk_frame_stats* stats) {
-    if (!ctx) return STK_INVALID_PARAMS;
     stk_status st = robust_validate(ctx, rc, weight, frames, out);
     if (st) return st;
     if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    const bool planes = rc.clip || rc.mad;
-    if (planes) HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
-    else if ((st = quantile_reserve(ctx, 0, w, h, cn))) return st;
-    stk_image_f32 mimg{planes ? ctx->clip.as<float>() : ctx->quantile.as<float>(), w, h, cn, STK_DEVICE, 0};
-    if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
-    return robust_finish(ctx, frames, stats, true, 8, params->border_mode, params->border_value, 0, weight, weights, rc, out, applied);
+    float* mean = nullptr;
+    if ((st = robust_reserve(ctx, rc, frames, &mean))) return st;
+    return keypoint_match_then(ctx, frames, params, scale_down_width, mean, dropped, stats,
+                               robust_finish(ctx, frames->n, weight, weights, rc, out, applied));
 }
 
 }  // namespace
 
 // (shared with drizzle.cpp: context.h)
-stk_status robust_match_records(stk_ctx* ctx, const stk_frames* frames, const stk_frame_stats* stats, bool keypoint, int border_mode,
-                                const double* border_value, int is_affine, const stk_weight_params* weight, const float* weights,
-                                std::vector<int>& entry_frame, std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms) {
-    stk_status st = robust_stack_table(ctx, frames, stats, keypoint, is_affine, entry_frame);
+stk_status robust_match_records(stk_ctx* ctx, const stk_frames* frames, const stk_frame_stats* stats, bool keypoint, const FoldSpec& spec,
+                                const stk_weight_params* weight, const float* weights, EntryTable& table,
+                                std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms) {
+    std::vector<const void*> dev;
+    resident_frames(ctx, frames, dev);
+    entries_from_stats(frames->n, stats, keypoint, table);
+    stk_status st = entry_table_upload(ctx, frames, dev, table, spec.is_affine);
     if (st) return st;
-    return robust_coefs(ctx, frames, entry_frame, frames->depth, border_mode, border_value, is_affine, weight, weights, coef, applied, ms);
+    return weighted_match_records(ctx, frames->n, table, spec, weight, weights, coef, applied, ms);
 }
 
 stk_status robust_match_median(stk_ctx* ctx, const stk_frames* frames, const std::vector<stk_frame_weight>& coef, int is_affine,
                                float* clean, int32_t* counts, double* ms) {
     const stk_quantile_params qp{0.5f, 0};
     stk_image_f32 img{clean, frames->width, frames->height, frames->channels, STK_DEVICE, 0};
-    return quantile_bands_weighted(ctx, coef, frames->depth, frames->width, frames->height, frames->channels, frame_row_bytes(frames),
-                                   1.0 / 255.0, STK_BORDER_CONSTANT, nullptr, is_affine, 1, &qp, &img, counts, ms);
+    return quantile_bands_weighted(ctx, coef, fold_spec(frames, 1.0 / 255.0, STK_BORDER_CONSTANT, nullptr, is_affine), 1, &qp, &img, counts, ms);
 }
 
 extern "C" {
@@ -306,12 +233,12 @@ stk_status stk_clip_stack_weighted(stk_ctx* ctx, const stk_frames* frames, const
     if (st) return st;
     if ((st = robust_check_border(ctx, border_mode, coverage))) return st;
     if ((st = clip_validate(ctx, clip))) return st;
-    if ((st = clip_check_out(ctx, out, frames))) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
     std::vector<stk_frame_weight> coef;
-    if ((st = robust_table(ctx, frames, M, include, is_affine, per_frame, "sigma clipping", coef))) return st;
+    if ((st = robust_stack_begin(ctx, frames, M, include, is_affine, per_frame, "sigma clipping", coef))) return st;
     double ms = 0.0;
-    st = clip_passes_weighted(ctx, coef, frames->depth, frames->width, frames->height, frames->channels, frame_row_bytes(frames), alpha,
-                              border_mode, border_value, is_affine, coverage, clip, out, counts, kept_weight, &ms);
+    st = clip_passes_weighted(ctx, coef, fold_spec(frames, alpha, border_mode, border_value, is_affine), coverage, clip, out, counts,
+                              kept_weight, &ms);
     ctx->timing.finalize_ms = st ? 0.0 : ms;
     return st;
 }
@@ -324,15 +251,12 @@ stk_status stk_quantile_stack_weighted(stk_ctx* ctx, const stk_frames* frames, c
     if (st) return st;
     if ((st = robust_check_border(ctx, border_mode, coverage))) return st;
     if ((st = quantile_validate(ctx, quantile))) return st;
-    if ((st = clip_check_out(ctx, out, frames))) return st;
-    int n_in = 0;
-    for (int i = 0; i < frames->n; i++) n_in += (!include || include[i]) ? 1 : 0;
-    if ((st = quantile_check_count(ctx, n_in))) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    if ((st = quantile_check_count(ctx, count_included(frames, include)))) return st;
     std::vector<stk_frame_weight> coef;
-    if ((st = robust_table(ctx, frames, M, include, is_affine, per_frame, "quantile", coef))) return st;
+    if ((st = robust_stack_begin(ctx, frames, M, include, is_affine, per_frame, "quantile", coef))) return st;
     double ms = 0.0;
-    st = quantile_bands_weighted(ctx, coef, frames->depth, frames->width, frames->height, frames->channels, frame_row_bytes(frames), alpha,
-                                 border_mode, border_value, is_affine, coverage, quantile, out, counts, &ms);
+    st = quantile_bands_weighted(ctx, coef, fold_spec(frames, alpha, border_mode, border_value, is_affine), coverage, quantile, out, counts, &ms);
     ctx->timing.finalize_ms = st ? 0.0 : ms;
     return st;
 }
@@ -345,15 +269,13 @@ stk_status stk_robust_clip_stack_weighted(stk_ctx* ctx, const stk_frames* frames
     if (st) return st;
     if ((st = robust_check_border(ctx, border_mode, coverage))) return st;
     if ((st = robust_clip_validate(ctx, clip))) return st;
-    if ((st = clip_check_out(ctx, out, frames))) return st;
-    int n_in = 0;
-    for (int i = 0; i < frames->n; i++) n_in += (!include || include[i]) ? 1 : 0;
-    if ((st = quantile_check_count(ctx, n_in))) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    if ((st = quantile_check_count(ctx, count_included(frames, include)))) return st;
     std::vector<stk_frame_weight> coef;
-    if ((st = robust_table(ctx, frames, M, include, is_affine, per_frame, "robust clipping", coef))) return st;
+    if ((st = robust_stack_begin(ctx, frames, M, include, is_affine, per_frame, "robust clipping", coef))) return st;
     double ms = 0.0;
-    st = robust_clip_bands(ctx, (int)coef.size(), &coef, frames->depth, frames->width, frames->height, frames->channels,
-                           frame_row_bytes(frames), alpha, border_mode, border_value, is_affine, coverage, clip, out, counts, kept_weight, &ms);
+    st = robust_clip_bands(ctx, (int)coef.size(), &coef, fold_spec(frames, alpha, border_mode, border_value, is_affine), coverage, clip, out,
+                           counts, kept_weight, &ms);
     ctx->timing.finalize_ms = st ? 0.0 : ms;
     return st;
 }

@@ -8,7 +8,7 @@
 // planes (ctx->clip). When every band has filled its rows, one last clip pass over the whole frame sums the kept samples in
 // fold order: the output is the clipped combine's sequential sum, with no summation order of its own. Like clip.cpp, the
 // whole-stack forms run the plain call first (its mean lands in the c plane and is overwritten) and take the warps and
-// the kept set from its stats.
+// the kept set from its stats (combine.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -28,9 +28,9 @@ stk_status robust_clip_validate(stk_ctx* ctx, const stk_robust_clip_params* p) {
     return STK_OK;
 }
 
-stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_frame_weight>* coef, int depth, int w, int h, int cn,
-                             size_t src_row_bytes, double alpha, int border_mode, const double* border_value, int is_affine,
-                             int coverage, const stk_robust_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms) {
+stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_frame_weight>* coef, const FoldSpec& spec, int coverage,
+                             const stk_robust_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms) {
+    const int w = spec.w, h = spec.h, cn = spec.cn, depth = spec.depth;
     stk_status st = quantile_check_count(ctx, n_entries);
     if (st) return st;
     const size_t row = (size_t)w * cn, nel = row * h;
@@ -39,7 +39,7 @@ stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_
     HIP_TRY(ctx->quantile.reserve(R * n_entries * row * sizeof(float)));
     float* c = ctx->clip.as<float>();
     float* band = ctx->quantile.as<float>();
-    WarpArgs a = weighted_warp_args(ctx, n_entries, depth, w, h, cn, src_row_bytes, alpha, border_mode, border_value, is_affine);
+    WarpArgs a = fold_warp_args(ctx, n_entries, spec);
     const bool host = out->location != STK_DEVICE;
     ClipArgs ca{};
     ca.c = c; ca.L = c + nel; ca.U = c + 2 * nel;
@@ -93,6 +93,30 @@ stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_
     return STK_OK;
 }
 
+namespace {
+
+// the checks and the workspace of the two whole-stack forms: the plain call's mean lands in the c plane (unused: the
+// selection overwrites it)
+stk_status robust_clip_match_begin(stk_ctx* ctx, const stk_frames* frames, const stk_robust_clip_params* clip, const stk_image_f32* out) {
+    stk_status st = robust_clip_validate(ctx, clip);
+    if (st) return st;
+    if ((st = check_frames(ctx, frames, true))) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    if ((st = quantile_check_count(ctx, frames->n))) return st;
+    (void)hipSetDevice(ctx->device);
+    HIP_TRY(ctx->clip.reserve(3 * (size_t)frames->width * frames->height * frames->channels * sizeof(float)));
+    return STK_OK;
+}
+
+// and their combine over the kept frames
+CombineFinish robust_clip_match_finish(stk_ctx* ctx, const stk_robust_clip_params* clip, stk_image_f32* out, int32_t* counts) {
+    return [=](const EntryTable& table, const std::vector<const void*>&, const FoldSpec& spec, const stk_frame_stats*, double* ms) {
+        return robust_clip_bands(ctx, table.size(), nullptr, spec, 0, clip, out, counts, nullptr, ms);
+    };
+}
+
+}  // namespace
+
 extern "C" {
 
 stk_status stk_robust_clip_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
@@ -101,32 +125,17 @@ stk_status stk_robust_clip_stack(stk_ctx* ctx, const stk_frames* frames, const d
     stk_status st = check_frames(ctx, frames, false);
     if (st) return st;
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
-    if (border_mode < 0 || border_mode > 4)
-        return fail(ctx, border_mode == STK_BORDER_TRANSPARENT ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS,
-                    "border mode not supported (BORDER_TRANSPARENT leaves the reference's output uninitialised)");
+    if ((st = check_border_mode(ctx, border_mode))) return st;
     if ((st = robust_clip_validate(ctx, clip))) return st;
-    if ((st = clip_check_out(ctx, out, frames))) return st;
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    int n_in = 0;
-    for (int i = 0; i < n; i++) n_in += (!include || include[i]) ? 1 : 0;
-    if (n_in == 0) return fail(ctx, STK_INVALID_PARAMS, "robust clipping: no frame included");
-    if ((st = quantile_check_count(ctx, n_in))) return st;
-    (void)hipSetDevice(ctx->device);
-    timing_begin(ctx);
-    std::vector<const void*> dev;
-    if ((st = resolve_frames(ctx, frames, dev))) return st;
-    std::vector<WarpFrame> wf;
-    wf.reserve(n_in);
-    for (int i = 0; i < n; i++) {
-        if (include && !include[i]) continue;
-        wf.emplace_back();
-        make_warp_frame(wf.back(), dev[i], M + 9 * (size_t)i, is_affine);
-    }
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, is_affine))) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    EntryTable table;
+    entries_from_include(frames->n, M, include, table);
+    if (table.frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "robust clipping: no frame included");
+    if ((st = quantile_check_count(ctx, table.size()))) return st;
+    if ((st = entry_table_begin(ctx, frames, table, is_affine))) return st;
     double ms = 0.0;
-    st = robust_clip_bands(ctx, n_in, nullptr, frames->depth, w, h, cn, rb, alpha, border_mode, border_value, is_affine, 0, clip, out,
-                           counts, nullptr, &ms);
+    st = robust_clip_bands(ctx, table.size(), nullptr, fold_spec(frames, alpha, border_mode, border_value, is_affine), 0, clip, out, counts,
+                           nullptr, &ms);
     ctx->timing.finalize_ms = st ? 0.0 : ms;
     return st;
 }
@@ -135,75 +144,20 @@ stk_status stk_ecc_match_robust_clipped(stk_ctx* ctx, const stk_frames* frames, 
                                         const stk_robust_clip_params* clip, stk_image_f32* out, int32_t* counts,
                                         stk_frame_stats* stats) {
     if (!ctx) return STK_INVALID_PARAMS;
-    stk_status st = robust_clip_validate(ctx, clip);
+    stk_status st = robust_clip_match_begin(ctx, frames, clip, out);
     if (st) return st;
-    if ((st = check_frames(ctx, frames, true))) return st;
-    if ((st = clip_check_out(ctx, out, frames))) return st;
-    if ((st = quantile_check_count(ctx, frames->n))) return st;
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    // the plain call, on this context's own device, its mean into the c plane (unused: the selection overwrites it)
-    stk_image_f32 cimg{ctx->clip.as<float>(), w, h, cn, STK_DEVICE, 0};
-    if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &cimg, stats))) return st;
-    const stk_timing keep = ctx->timing;
-    // every frame is a sample: frame 0 through the identity, frame i through its warp (as in stk_ecc_match_clipped)
-    const int is_affine = params->motion_type != STK_MOTION_HOMOGRAPHY;
-    std::vector<const void*> dev;
-    resident_frames(ctx, frames, dev);
-    std::vector<WarpFrame> wf(n);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    make_warp_frame(wf[0], dev[0], I3, is_affine);
-    for (int i = 1; i < n; i++) make_warp_frame(wf[i], dev[i], stats[i].warp, is_affine);
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, is_affine))) return st;
-    double ms = 0.0;
-    st = robust_clip_bands(ctx, n, nullptr, frames->depth, w, h, cn, rb, 1.0 / 255.0, STK_BORDER_CONSTANT, nullptr, is_affine, 0, clip, out,
-                           counts, nullptr, &ms);
-    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : ms;
-    return st;
+    return ecc_match_then(ctx, frames, params, scale_down_width, ctx->clip.as<float>(), stats,
+                          robust_clip_match_finish(ctx, clip, out, counts));
 }
 
 stk_status stk_keypoint_match_robust_clipped(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
                                              float scale_down_width, const stk_robust_clip_params* clip, stk_image_f32* out,
                                              int32_t* dropped, int32_t* counts, stk_frame_stats* stats) {
     if (!ctx) return STK_INVALID_PARAMS;
-    stk_status st = robust_clip_validate(ctx, clip);
+    stk_status st = robust_clip_match_begin(ctx, frames, clip, out);
     if (st) return st;
-    if ((st = check_frames(ctx, frames, true))) return st;
-    if ((st = clip_check_out(ctx, out, frames))) return st;
-    if ((st = quantile_check_count(ctx, frames->n))) return st;
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    stk_image_f32 cimg{ctx->clip.as<float>(), w, h, cn, STK_DEVICE, 0};
-    if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &cimg, dropped, stats))) return st;
-    const stk_timing keep = ctx->timing;
-    // the samples: frame 0 through the identity and the frames with a homography (status 0), in stack order, with the
-    // params' border (as in stk_keypoint_match_clipped)
-    std::vector<const void*> dev;
-    resident_frames(ctx, frames, dev);
-    std::vector<WarpFrame> wf;
-    wf.reserve(n);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    wf.emplace_back();
-    make_warp_frame(wf.back(), dev[0], I3, 0);
-    for (int i = 1; i < n; i++) {
-        if (stats[i].status != 0) continue;
-        wf.emplace_back();
-        make_warp_frame(wf.back(), dev[i], stats[i].warp, 0);
-    }
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, 0))) return st;
-    double ms = 0.0;
-    st = robust_clip_bands(ctx, (int)wf.size(), nullptr, 8, w, h, cn, rb, 1.0 / 255.0, params->border_mode, params->border_value, 0, 0,
-                           clip, out, counts, nullptr, &ms);
-    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : ms;
-    return st;
+    return keypoint_match_then(ctx, frames, params, scale_down_width, ctx->clip.as<float>(), dropped, stats,
+                               robust_clip_match_finish(ctx, clip, out, counts));
 }
 
 }  // extern "C"

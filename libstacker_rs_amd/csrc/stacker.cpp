@@ -1039,9 +1039,7 @@ stk_status stk_warp_accumulate(stk_ctx* ctx, const stk_frames* f, const double* 
     stk_status st = check_frames(ctx, f, false);
     if (st) return st;
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
-    if (border_mode < 0 || border_mode > 4)
-        return fail(ctx, border_mode == STK_BORDER_TRANSPARENT ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS,
-                    "border mode not supported (BORDER_TRANSPARENT leaves the reference's output uninitialised)");
+    if ((st = check_border_mode(ctx, border_mode))) return st;
     if ((st = image_check(ctx, acc, f->width, f->height, f->channels))) return st;
     (void)hipSetDevice(ctx->device);
     std::vector<const void*> dev;

@@ -4,8 +4,9 @@
 // ctx->weighted (grow-only like the other workspaces) holds a w x h x cn f32 image (the plain call's mean in the
 // whole-stack forms, then a host output's staging copy), the w x h den plane, the per-entry gain / offset / weight table,
 // the moments and the per-wave partials they are reduced from. Like clip.cpp, the whole-stack forms run the plain call
-// first and take the warps and the kept set from its stats; the frames are still resident in HBM. With normalize != 0 the
-// moments pass and the host estimator follow, then one weighted fold.
+// first and take the warps and the kept set from its stats (combine.h); the frames are still resident in HBM. With
+// normalize != 0 the moments pass and the host estimator follow (weighted_match_records, which every whole-stack form with
+// stk_weight_params shares), then one weighted fold.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -37,14 +38,6 @@ WeightedLayout weighted_layout(int n_entries, int w, int h, int cn, int step) {
 }  // namespace
 
 // (the checks, the moments pass and the estimator are shared with robust.cpp: context.h)
-stk_status weighted_check_out(stk_ctx* ctx, const stk_image_f32* out, const stk_frames* f) {
-    stk_status st = image_check(ctx, out, f->width, f->height, f->channels);
-    if (st) return st;
-    if (out->row_stride_bytes && out->row_stride_bytes != (size_t)f->width * f->channels * sizeof(float))
-        return fail(ctx, STK_INVALID_PARAMS, "output must be tightly packed");
-    return STK_OK;
-}
-
 stk_status weighted_validate(stk_ctx* ctx, const stk_weight_params* p) {
     if (!p) return fail(ctx, STK_INVALID_PARAMS, "null weight parameters");
     if (p->normalize < 0 || p->normalize > 3) return fail(ctx, STK_INVALID_PARAMS, "weighted: normalize must be 0 .. 3");
@@ -55,9 +48,8 @@ stk_status weighted_validate(stk_ctx* ctx, const stk_weight_params* p) {
 }
 
 stk_status weighted_check_border(stk_ctx* ctx, int border_mode, const double* border_value, int coverage) {
-    if (border_mode < 0 || border_mode > 4)
-        return fail(ctx, border_mode == STK_BORDER_TRANSPARENT ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS,
-                    "border mode not supported (BORDER_TRANSPARENT leaves the reference's output uninitialised)");
+    stk_status st = check_border_mode(ctx, border_mode);
+    if (st) return st;
     if (coverage < 0 || coverage > 1) return fail(ctx, STK_INVALID_PARAMS, "weighted: coverage must be 0 or 1");
     if (coverage) {
         bool zero = border_mode == STK_BORDER_CONSTANT;
@@ -81,37 +73,21 @@ stk_status weighted_check_coefs(stk_ctx* ctx, const std::vector<stk_frame_weight
     return STK_OK;
 }
 
-WarpArgs weighted_warp_args(stk_ctx* ctx, int n_entries, int depth, int w, int h, int cn, size_t src_row_bytes, double alpha,
-                            int border_mode, const double* border_value, int is_affine) {
-    WarpArgs a{};
-    a.frames = ctx->warpframes.as<WarpFrame>();
-    a.n_frames = n_entries;
-    a.sw = w; a.sh = h; a.cn = cn;
-    a.src_stride = src_row_bytes / (depth / 8);
-    a.alpha = (float)alpha;
-    a.border_mode = border_mode;
-    for (int k = 0; k < 4; k++) a.bv[k] = border_value ? (float)border_value[k] : 0.f;
-    a.acc = nullptr; a.dw = w; a.dh = h; a.acc_stride = 0;
-    a.is_affine = is_affine; a.subpixel_bits = ctx->opt_subpixel_bits; a.tune = 0; a.interp = ctx->opt_interp;
-    return a;
-}
-
 // The moments pass over the n_entries entries of ctx->warpframes (uploaded for the w x h destination): (n_entries - 1) x
 // cn x 6 doubles into `host`, entry 1 first. Synchronises; adds its device time to *ms.
-stk_status weighted_moments(stk_ctx* ctx, int n_entries, int depth, int w, int h, int cn, size_t src_row_bytes, double alpha,
-                            int border_mode, const double* border_value, int is_affine, int step, double* host, double* ms) {
+stk_status weighted_moments(stk_ctx* ctx, int n_entries, const FoldSpec& spec, int step, double* host, double* ms) {
     if (n_entries < 2) return STK_OK;
-    const WeightedLayout L = weighted_layout(n_entries, w, h, cn, step);
+    const WeightedLayout L = weighted_layout(n_entries, spec.w, spec.h, spec.cn, step);
     HIP_TRY(ctx->weighted.reserve(L.total));
     char* base = ctx->weighted.as<char>();
-    const WarpArgs a = weighted_warp_args(ctx, n_entries, depth, w, h, cn, src_row_bytes, alpha, border_mode, border_value, is_affine);
+    const WarpArgs a = fold_warp_args(ctx, n_entries, spec);
     ClipArgs ca{};
     ca.partials = (double*)(base + L.partials);
     double* mom = (double*)(base + L.moments);
     HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
-    HIP_TRY(launch_overlap_moments(a, ca, depth, step, mom, ctx->stream));
+    HIP_TRY(launch_overlap_moments(a, ca, spec.depth, step, mom, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    HIP_TRY(hipMemcpyAsync(host, mom, (size_t)(n_entries - 1) * cn * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(host, mom, (size_t)(n_entries - 1) * spec.cn * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
     return STK_OK;
@@ -142,37 +118,41 @@ void weighted_estimate(const double* m /* cn x 6 */, int cn, int mode, stk_frame
     }
 }
 
-// common argument checks of the caller-held-warps forms (shared with local.cpp: context.h); fills the table's frame indices
-stk_status weighted_table(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int is_affine,
-                          std::vector<int>& entry_frame) {
-    const int n = frames->n, w = frames->width, h = frames->height;
-    for (int i = 0; i < n; i++) if (!include || include[i]) entry_frame.push_back(i);
-    if (entry_frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "weighted: no frame included");
-    (void)hipSetDevice(ctx->device);
-    timing_begin(ctx);
-    std::vector<const void*> dev;
-    stk_status st = resolve_frames(ctx, frames, dev);
+// (shared by every whole-stack form that takes stk_weight_params: robust.cpp, local.cpp, drizzle.cpp through context.h)
+stk_status weighted_match_records(stk_ctx* ctx, int n, const EntryTable& table, const FoldSpec& spec, const stk_weight_params* p,
+                                  const float* weights, std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms) {
+    const int ne = table.size(), cn = spec.cn;
+    std::vector<double> mom((size_t)std::max(ne - 1, 0) * cn * 6);
+    if (p->normalize != 0 && ne > 1) {
+        stk_status st = weighted_moments(ctx, ne, spec, p->stat_step ? p->stat_step : 4, mom.data(), ms);
+        if (st) return st;
+    }
+    coef.assign(ne, unit_record());
+    for (int k = 0; k < ne; k++) {
+        if (k > 0) weighted_estimate(mom.data() + (size_t)(k - 1) * cn * 6, cn, p->normalize, &coef[k]);
+        coef[k].weight = weights ? weights[table.frame[k]] : 1.0f;
+    }
+    stk_status st = weighted_check_coefs(ctx, coef, cn);
     if (st) return st;
-    std::vector<WarpFrame> wf(entry_frame.size());
-    for (size_t k = 0; k < entry_frame.size(); k++) make_warp_frame(wf[k], dev[entry_frame[k]], M + 9 * (size_t)entry_frame[k], is_affine);
-    if ((st = warp_table_upload(ctx, wf, frame_row_bytes(frames), w, h, is_affine))) return st;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));       // `wf` leaves scope
+    if (applied) {
+        for (int i = 0; i < n; i++) { applied[i] = unit_record(); applied[i].weight = 0.0f; }
+        for (int k = 0; k < ne; k++) applied[table.frame[k]] = coef[k];
+    }
     return STK_OK;
 }
 
 namespace {
 
-// The weighted fold over the n_entries entries of ctx->warpframes with the per-entry records `coef`. Writes `out` and
-// `coverage_out` (out's location); adds its device time to *ms.
-stk_status weighted_fold(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, int depth, int w, int h, int cn, size_t src_row_bytes,
-                         double alpha, int border_mode, const double* border_value, int is_affine, int coverage,
-                         stk_image_f32* out, float* coverage_out, double* ms) {
-    const int n_entries = (int)coef.size();
+// The weighted fold over the entries of ctx->warpframes with the per-entry records `coef`. Writes `out` and `coverage_out`
+// (out's location); adds its device time to *ms.
+stk_status weighted_fold(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage, stk_image_f32* out,
+                         float* coverage_out, double* ms) {
+    const int n_entries = (int)coef.size(), w = spec.w, h = spec.h, cn = spec.cn;
     const WeightedLayout L = weighted_layout(n_entries, w, h, cn, 0);
     HIP_TRY(ctx->weighted.reserve(L.total));
     char* base = ctx->weighted.as<char>();
     const bool host = out->location != STK_DEVICE;
-    const WarpArgs a = weighted_warp_args(ctx, n_entries, depth, w, h, cn, src_row_bytes, alpha, border_mode, border_value, is_affine);
+    const WarpArgs a = fold_warp_args(ctx, n_entries, spec);
     ClipArgs ca{};
     ca.coef = (const stk_frame_weight*)(base + L.coef);
     ca.coverage = coverage;
@@ -182,7 +162,7 @@ stk_status weighted_fold(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef
     ca.den_stride = (size_t)w;
     HIP_TRY(hipMemcpyAsync(base + L.coef, coef.data(), coef.size() * sizeof(stk_frame_weight), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
-    HIP_TRY(launch_weighted_fold(a, ca, depth, ctx->stream));
+    HIP_TRY(launch_weighted_fold(a, ca, spec.depth, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
     if (host) {
         HIP_TRY(hipMemcpyAsync(out->data, ca.out, (size_t)w * h * cn * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -193,36 +173,30 @@ stk_status weighted_fold(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef
     return STK_OK;
 }
 
-// the tail of the whole-stack forms: `entry_frame[k]` is the frame index of table entry k (entry 0 = frame 0)
-stk_status weighted_finish(stk_ctx* ctx, const stk_frames* frames, const std::vector<int>& entry_frame, int depth, size_t rb,
-                           int border_mode, const double* border_value, int is_affine, const stk_weight_params* p,
-                           const float* weights, stk_image_f32* out, float* coverage_out, stk_frame_weight* applied) {
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    const int ne = (int)entry_frame.size();
-    const double alpha = 1.0 / 255.0;
-    std::vector<stk_frame_weight> coef(ne);
-    double ms = 0.0;
-    std::vector<double> mom((size_t)std::max(ne - 1, 0) * cn * 6);
-    if (p->normalize != 0 && ne > 1) {
-        const int step = p->stat_step ? p->stat_step : 4;
-        stk_status st = weighted_moments(ctx, ne, depth, w, h, cn, rb, alpha, border_mode, border_value, is_affine, step, mom.data(), &ms);
-        if (st) return st;
-    }
-    for (int k = 0; k < ne; k++) {
-        if (k == 0) weighted_estimate(nullptr, cn, 0, &coef[k]);
-        else weighted_estimate(mom.data() + (size_t)(k - 1) * cn * 6, cn, p->normalize, &coef[k]);
-        coef[k].weight = weights ? weights[entry_frame[k]] : 1.0f;
-    }
-    stk_status st = weighted_check_coefs(ctx, coef, cn);
+// the checks the two whole-stack forms share, in the order the errors are reported; then their workspace (the plain call's
+// mean lands in its image, unused)
+stk_status weighted_match_check(stk_ctx* ctx, const stk_frames* frames, const stk_weight_params* weight, const stk_image_f32* out) {
+    stk_status st = weighted_validate(ctx, weight);
     if (st) return st;
-    if ((st = weighted_fold(ctx, coef, depth, w, h, cn, rb, alpha, border_mode, border_value, is_affine, p->coverage, out, coverage_out, &ms)))
-        return st;
-    ctx->timing.finalize_ms = ms;
-    if (applied) {
-        for (int i = 0; i < n; i++) { weighted_estimate(nullptr, cn, 0, &applied[i]); applied[i].weight = 0.0f; }
-        for (int k = 0; k < ne; k++) applied[entry_frame[k]] = coef[k];
-    }
+    if ((st = check_frames(ctx, frames, true))) return st;
+    return combine_check_out(ctx, out, frames);
+}
+stk_status weighted_match_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_weight_params* weight) {
+    (void)hipSetDevice(ctx->device);
+    const int step = weight->normalize ? (weight->stat_step ? weight->stat_step : 4) : 0;
+    HIP_TRY(ctx->weighted.reserve(weighted_layout(frames->n, frames->width, frames->height, frames->channels, step).total));
     return STK_OK;
+}
+
+// and their combine over the kept frames: the records, then one weighted fold
+CombineFinish weighted_match_finish(stk_ctx* ctx, int n, const stk_weight_params* weight, const float* weights, stk_image_f32* out,
+                                    float* coverage_out, stk_frame_weight* applied) {
+    return [=](const EntryTable& table, const std::vector<const void*>&, const FoldSpec& spec, const stk_frame_stats*, double* ms) {
+        std::vector<stk_frame_weight> coef;
+        stk_status st = weighted_match_records(ctx, n, table, spec, weight, weights, coef, applied, ms);
+        if (st) return st;
+        return weighted_fold(ctx, coef, spec, weight->coverage, out, coverage_out, ms);
+    };
 }
 
 }  // namespace
@@ -237,17 +211,16 @@ stk_status stk_weighted_stack(stk_ctx* ctx, const stk_frames* frames, const doub
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
     if (!per_frame) return fail(ctx, STK_INVALID_PARAMS, "null per-frame records");
     if ((st = weighted_check_border(ctx, border_mode, border_value, coverage))) return st;
-    if ((st = weighted_check_out(ctx, out, frames))) return st;
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    EntryTable table;
+    entries_from_include(frames->n, M, include, table);
+    if (table.frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "weighted: no frame included");
     std::vector<stk_frame_weight> coef;
-    for (int i = 0; i < n; i++) if (!include || include[i]) coef.push_back(per_frame[i]);
-    if (coef.empty()) return fail(ctx, STK_INVALID_PARAMS, "weighted: no frame included");
-    if ((st = weighted_check_coefs(ctx, coef, cn))) return st;
-    std::vector<int> entry_frame;
-    if ((st = weighted_table(ctx, frames, M, include, is_affine, entry_frame))) return st;
+    gather_records(table, per_frame, coef);
+    if ((st = weighted_check_coefs(ctx, coef, frames->channels))) return st;
+    if ((st = entry_table_begin(ctx, frames, table, is_affine))) return st;
     double ms = 0.0;
-    if ((st = weighted_fold(ctx, coef, frames->depth, w, h, cn, frame_row_bytes(frames), alpha, border_mode, border_value, is_affine,
-                            coverage, out, coverage_out, &ms)))
+    if ((st = weighted_fold(ctx, coef, fold_spec(frames, alpha, border_mode, border_value, is_affine), coverage, out, coverage_out, &ms)))
         return st;
     ctx->timing.finalize_ms = ms;
     return STK_OK;
@@ -262,19 +235,19 @@ stk_status stk_overlap_moments(stk_ctx* ctx, const stk_frames* frames, const dou
     if ((st = weighted_check_border(ctx, border_mode, border_value, 0))) return st;
     if (stat_step < 1 || stat_step > 64) return fail(ctx, STK_INVALID_PARAMS, "overlap moments: stat_step must be 1 .. 64");
     if (include && !include[0]) return fail(ctx, STK_INVALID_PARAMS, "overlap moments: frame 0 must be included");
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    std::vector<int> entry_frame;
-    if ((st = weighted_table(ctx, frames, M, include, is_affine, entry_frame))) return st;
-    const int ne = (int)entry_frame.size();
+    const int n = frames->n, cn = frames->channels;
+    EntryTable table;
+    entries_from_include(n, M, include, table);
+    if (table.frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "weighted: no frame included");
+    if ((st = entry_table_begin(ctx, frames, table, is_affine))) return st;
+    const int ne = table.size();
     std::vector<double> mom((size_t)std::max(ne - 1, 0) * cn * 6);
     double ms = 0.0;
-    if ((st = weighted_moments(ctx, ne, frames->depth, w, h, cn, frame_row_bytes(frames), alpha, border_mode, border_value, is_affine,
-                               stat_step, mom.data(), &ms)))
-        return st;
+    if ((st = weighted_moments(ctx, ne, fold_spec(frames, alpha, border_mode, border_value, is_affine), stat_step, mom.data(), &ms))) return st;
     ctx->timing.finalize_ms = ms;
     std::memset(moments, 0, (size_t)n * cn * 6 * sizeof(double));
     for (int k = 1; k < ne; k++)
-        std::memcpy(moments + (size_t)entry_frame[k] * cn * 6, mom.data() + (size_t)(k - 1) * cn * 6, (size_t)cn * 6 * sizeof(double));
+        std::memcpy(moments + (size_t)table.frame[k] * cn * 6, mom.data() + (size_t)(k - 1) * cn * 6, (size_t)cn * 6 * sizeof(double));
     return STK_OK;
 }
 
@@ -282,82 +255,24 @@ stk_status stk_ecc_match_weighted(stk_ctx* ctx, const stk_frames* frames, const 
                                   const stk_weight_params* weight, const float* weights, stk_image_f32* out, float* coverage_out,
                                   stk_frame_weight* applied, stk_frame_stats* stats) {
     if (!ctx) return STK_INVALID_PARAMS;
-    stk_status st = weighted_validate(ctx, weight);
+    stk_status st = weighted_match_check(ctx, frames, weight, out);
     if (st) return st;
-    if ((st = check_frames(ctx, frames, true))) return st;
-    if ((st = weighted_check_out(ctx, out, frames))) return st;
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    const int step = weight->normalize ? (weight->stat_step ? weight->stat_step : 4) : 0;
-    HIP_TRY(ctx->weighted.reserve(weighted_layout(n, w, h, cn, step).total));
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    // the plain call, on this context's own device, its mean into the workspace image (unused)
-    stk_image_f32 mimg{ctx->weighted.as<float>(), w, h, cn, STK_DEVICE, 0};
-    if ((st = ecc_match_single(ctx, frames, params, scale_down_width, &mimg, stats))) return st;
-    const stk_timing keep = ctx->timing;
-    // every frame is a sample: frame 0 through the identity, frame i through its warp (as in stk_ecc_match_clipped)
-    const int is_affine = params->motion_type != STK_MOTION_HOMOGRAPHY;
-    std::vector<const void*> dev;
-    resident_frames(ctx, frames, dev);
-    std::vector<WarpFrame> wf(n);
-    std::vector<int> entry_frame(n);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    make_warp_frame(wf[0], dev[0], I3, is_affine);
-    for (int i = 1; i < n; i++) make_warp_frame(wf[i], dev[i], stats[i].warp, is_affine);
-    for (int i = 0; i < n; i++) entry_frame[i] = i;
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, is_affine))) return st;
-    st = weighted_finish(ctx, frames, entry_frame, frames->depth, rb, STK_BORDER_CONSTANT, nullptr, is_affine, weight, weights, out,
-                         coverage_out, applied);
-    const double fin = ctx->timing.finalize_ms;
-    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : fin;
-    return st;
+    if ((st = weighted_match_reserve(ctx, frames, weight))) return st;
+    return ecc_match_then(ctx, frames, params, scale_down_width, ctx->weighted.as<float>(), stats,
+                          weighted_match_finish(ctx, frames->n, weight, weights, out, coverage_out, applied));
 }
 
 stk_status stk_keypoint_match_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,
                                        const stk_weight_params* weight, const float* weights, stk_image_f32* out, int32_t* dropped,
                                        float* coverage_out, stk_frame_weight* applied, stk_frame_stats* stats) {
     if (!ctx) return STK_INVALID_PARAMS;
-    stk_status st = weighted_validate(ctx, weight);
+    stk_status st = weighted_match_check(ctx, frames, weight, out);
     if (st) return st;
-    if ((st = check_frames(ctx, frames, true))) return st;
-    if ((st = weighted_check_out(ctx, out, frames))) return st;
     if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
     if (weight->coverage && (st = weighted_check_border(ctx, params->border_mode, params->border_value, 1))) return st;
-    (void)hipSetDevice(ctx->device);
-    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
-    const int step = weight->normalize ? (weight->stat_step ? weight->stat_step : 4) : 0;
-    HIP_TRY(ctx->weighted.reserve(weighted_layout(n, w, h, cn, step).total));
-    std::vector<stk_frame_stats> own;
-    if (!stats) { own.resize(n); stats = own.data(); }
-    stk_image_f32 mimg{ctx->weighted.as<float>(), w, h, cn, STK_DEVICE, 0};
-    if ((st = keypoint_match_single(ctx, frames, params, scale_down_width, &mimg, dropped, stats))) return st;
-    const stk_timing keep = ctx->timing;
-    // the samples: frame 0 through the identity and the frames with a homography (status 0), in stack order, with the
-    // params' border (as in stk_keypoint_match_clipped)
-    std::vector<const void*> dev;
-    resident_frames(ctx, frames, dev);
-    std::vector<WarpFrame> wf;
-    std::vector<int> entry_frame;
-    wf.reserve(n);
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    wf.emplace_back();
-    make_warp_frame(wf.back(), dev[0], I3, 0);
-    entry_frame.push_back(0);
-    for (int i = 1; i < n; i++) {
-        if (stats[i].status != 0) continue;
-        wf.emplace_back();
-        make_warp_frame(wf.back(), dev[i], stats[i].warp, 0);
-        entry_frame.push_back(i);
-    }
-    const size_t rb = frame_row_bytes(frames);
-    if ((st = warp_table_upload(ctx, wf, rb, w, h, 0))) return st;
-    st = weighted_finish(ctx, frames, entry_frame, 8, rb, params->border_mode, params->border_value, 0, weight, weights, out, coverage_out,
-                         applied);
-    const double fin = ctx->timing.finalize_ms;
-    ctx->timing = keep; ctx->timing.finalize_ms = st ? 0.0 : fin;
-    return st;
+    if ((st = weighted_match_reserve(ctx, frames, weight))) return st;
+    return keypoint_match_then(ctx, frames, params, scale_down_width, ctx->weighted.as<float>(), dropped, stats,
+                               weighted_match_finish(ctx, frames->n, weight, weights, out, coverage_out, applied));
 }
 
 }  // extern "C"

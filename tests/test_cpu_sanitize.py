@@ -155,6 +155,17 @@ def test_warp_frame_flags_on_the_host(tmp_path):
 
 
 @pytest.mark.timeout(600)
+def test_combine_entry_tables_on_the_host(tmp_path):
+    """Which frames are samples of a combine and under which matrix (combine.h: entries_from_include, entries_from_stats):
+    the one rule every combine's result rests on, against tables written out by hand, under ASan + UBSan."""
+    exe = str(tmp_path / "entries")
+    _build("entries_harness.cpp", exe, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=500)
+    assert r.returncode == 0 and r.stdout.startswith("ok"), r.stdout[-1500:] + r.stderr[-3000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
+@pytest.mark.timeout(600)
 def test_ransac_host_half_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "ransac_host")
     _build("ransac_host_harness.cpp", exe, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
