@@ -633,6 +633,36 @@ typedef struct {
     int32_t reserved;   /* 0 */
 } stk_mesh_params;
 
+/* ---- coarse-to-fine local alignment (the *_pyramid calls below): shifts beyond a patch's capture range ---------------
+ * The estimation above starts every node at d = (0, 0) and follows the gradient of one patch: beyond a fraction of the
+ * finest scene period it settles in a wrong minimum with a positive status. The pyramid form runs the same estimation on
+ * `levels` = 1 .. 4 levels, coarsest first, and seeds each level with the one above. Level l has scale s = 2^l.
+ * Level images. g_i^0 is stk_grey's integer grey, as above. g_i^l(x, y) = (g^{l-1}(2x, 2y) + g^{l-1}(2x+1, 2y) +
+ *   g^{l-1}(2x, 2y+1) + g^{l-1}(2x+1, 2y+1) + 2) >> 2, stored as u8; w_l = w_{l-1} >> 1, h_l likewise (an odd last column
+ *   or row is dropped). The planes are exact integers.
+ * Level matrices. Pixel x of level l sits at full-resolution coordinate s x + (s - 1) / 2: C_l = [[s, 0, c], [0, s, c],
+ *   [0, 0, 1]] with c = (s - 1) / 2. The destination -> source matrix of level l is C_l^-1 Minv_i C_l in double, Minv_i the
+ *   double inverse of the single-level definition, then cast to f32. In operations, each rounded on its own, row r of
+ *   A = Minv_i C_l is (m_r0 s, m_r1 s, (m_r0 c + m_r1 c) + m_r2), and rows 0 and 1 of the product are
+ *   A_r (1 / s) - (c / s) A_2, row 2 is A_2 (an affine last row stays (0, 0, 1)). Level 0 is Minv_i itself.
+ * Nodes. Every level uses the same gw x gh grid. Node (j, k) of level l is centred at the integer level pixel
+ *   ((k step) >> l, (j step) >> l); its patch has the same `radius` in level pixels, limited to 1 <= x <= w_l - 2 and
+ *   1 <= y <= h_l - 2.
+ * Estimation at level l. Steps 1 - 7 above on g_0^l and g_i^l with w_l, h_l and the level matrix, but d starts at the
+ *   node's seed instead of (0, 0), and max_shift is replaced by max_shift 2^-l (exact in f32), tested on the total d.
+ *   epsilon, min_eig and max_iters are unchanged, in level pixels and level grey.
+ * Carrying. Each node carries a validity bit m. The top level l = levels - 1 starts with seed (0, 0) and m_seed = 0. After
+ *   the estimation at level l a node with status > 0 has its d and m = 1; any other node has d = seed and m = m_seed. The
+ *   `fill` Jacobi passes then run on (d, m): the arithmetic of "Fill" above with m in place of status > 0. For the next
+ *   level down, seed = 2 d (f32, exact) and m_seed = m after the fill.
+ * Result. The field is level 0's d after its fill; the status plane is level 0's estimation codes. A node that fails at
+ *   level 0 therefore keeps a negative code but carries the coarser level's measurement. levels = 1 is stk_local_align
+ *   (estimation and fill) bit for bit.
+ * Refusals, STK_INVALID_PARAMS: levels outside 1 .. 4; step >> (levels - 1) < 4; min(w, h) >> (levels - 1) < 16;
+ *   everything stk_local_align refuses. 16-bit and f32 frames: STK_NOT_IMPLEMENTED.
+ * The drizzle forms get no pyramid entry point: the fields of stk_local_align_pyramid go into stk_mesh_drizzle_stack as
+ *   they are. */
+
 /* The grid of a width x height destination. Bad arguments (a step that is no power of two in 8 .. 256, a NULL pointer):
  * STK_INVALID_PARAMS. */
 stk_status stk_mesh_grid(int32_t width, int32_t height, int32_t step, int32_t* gw, int32_t* gh);
@@ -669,6 +699,29 @@ stk_status stk_ecc_match_local_aligned(stk_ctx* ctx, const stk_frames* frames, c
 stk_status stk_keypoint_match_local_aligned(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
                                             float scale_down_width, const stk_mesh_params* mesh, const stk_local_params* local_or_null,
                                             stk_image_f32* out, int32_t* dropped, stk_frame_stats* stats_or_null);
+/* Levels 1 .. levels - 1 of the box pyramid of ONE 8-bit frame (frames->n == 1; 1, 3 or 4 channels, any row stride):
+ * planes[l] receives (w >> l) x (h >> l) bytes, tightly packed, in frames->location; planes[0] is not used. levels is
+ * 2 .. 4 with min(w, h) >> (levels - 1) >= 1, else STK_INVALID_PARAMS. The pyramid kernel on its own, so that it can be
+ * held to exact integers. */
+stk_status stk_grey_pyramid(stk_ctx* ctx, const stk_frames* frame, int32_t levels, uint8_t* const* planes);
+/* stk_local_align, coarse to fine (definition above): its arguments and conventions, plus `levels`. Host frames go through
+ * the frame workspace in batches behind frame 0, whose pyramid is built once. stk_timing.prep_ms is the device time of the
+ * pyramid pass, align_ms that of the levels' estimations and fills. A failed device allocation is STK_HIP_ERROR with the
+ * byte count in stk_last_error. */
+stk_status stk_local_align_pyramid(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                   int32_t is_affine, const stk_mesh_params* mesh, int32_t levels, float* const* fields,
+                                   int32_t* const* status_or_null);
+/* stk_ecc_match_local_aligned / stk_keypoint_match_local_aligned with the coarse-to-fine field pass: by definition the
+ * plain call + stk_local_align_pyramid on the stats' warps + the mesh fold (with local_or_null: the map pass and the mesh
+ * local-weighted fold), bit for bit. */
+stk_status stk_ecc_match_local_aligned_pyramid(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
+                                               float scale_down_width, const stk_mesh_params* mesh, int32_t levels,
+                                               const stk_local_params* local_or_null, stk_image_f32* out,
+                                               stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_local_aligned_pyramid(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                                    float scale_down_width, const stk_mesh_params* mesh, int32_t levels,
+                                                    const stk_local_params* local_or_null, stk_image_f32* out, int32_t* dropped,
+                                                    stk_frame_stats* stats_or_null);
 
 /* ---- drizzle integration onto a finer or larger output grid: an EXTENSION beyond the reference --------------------
  * Variable-pixel linear reconstruction (Fruchter & Hook 2002). Every other combine writes onto frame 0's own grid and

@@ -14,9 +14,9 @@ from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_RE
                   KeyPointMatchParameters, LocalParameters, MeshParameters, MotionType, NotEnoughFiles, NotImplementedYet, OpenCvError,
                   ProcessingError, QuantileParameters, RejectParameters, RobustClipParameters, SelectParameters, SigmaClipParameters, Stacker,
                   StackerError, WeightParameters,
-                  default_stacker, ecc_match, keypoint_match, mesh_grid, rank_frames)
+                  default_stacker, ecc_match, keypoint_match, mesh_grid, mesh_pyramid_shapes, rank_frames)
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
-           "SelectParameters", "rank_frames", "LocalParameters", "MeshParameters", "mesh_grid", "DrizzleParameters",
+           "SelectParameters", "rank_frames", "LocalParameters", "MeshParameters", "mesh_grid", "mesh_pyramid_shapes", "DrizzleParameters",
            "RejectParameters"]

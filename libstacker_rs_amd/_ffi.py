@@ -175,6 +175,15 @@ SIGNATURES = {
     "stk_keypoint_match_local_aligned": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
                                                     C.POINTER(MeshParams), C.POINTER(LocalParams), C.POINTER(ImageF32),
                                                     C.POINTER(C.c_int32), C.POINTER(FrameStats)]),
+    "stk_grey_pyramid": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_int32, C.c_void_p]),
+    "stk_local_align_pyramid": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MeshParams),
+                                           C.c_int32, C.c_void_p, C.c_void_p]),
+    "stk_ecc_match_local_aligned_pyramid": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float,
+                                                       C.POINTER(MeshParams), C.c_int32, C.POINTER(LocalParams), C.POINTER(ImageF32),
+                                                       C.POINTER(FrameStats)]),
+    "stk_keypoint_match_local_aligned_pyramid": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                                            C.POINTER(MeshParams), C.c_int32, C.POINTER(LocalParams),
+                                                            C.POINTER(ImageF32), C.POINTER(C.c_int32), C.POINTER(FrameStats)]),
     "stk_drizzle_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
                                      C.POINTER(DrizzleParams), C.POINTER(FrameWeight), C.c_void_p, C.POINTER(ImageF32), C.c_void_p]),
     "stk_ecc_match_drizzle": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float, C.POINTER(DrizzleParams),

@@ -238,6 +238,14 @@ def mesh_grid(width: int, height: int, step: int):
     return gw.value, gh.value
 
 
+def mesh_pyramid_shapes(width: int, height: int, levels: int):
+    """[(h >> l, w >> l) for l = 0 .. levels - 1]: the level images of the coarse-to-fine local alignment
+    (local_align_pyramid, grey_pyramid); an odd last column or row is dropped at every halving."""
+    if not 1 <= int(levels) <= 4 or width <= 0 or height <= 0:
+        raise InvalidParams("mesh_pyramid_shapes: width and height must be positive, levels 1 .. 4")
+    return [(int(height) >> l, int(width) >> l) for l in range(int(levels))]
+
+
 SHARPNESS_LAPM, SHARPNESS_LAPV, SHARPNESS_TENG, SHARPNESS_GLVN = 0, 1, 2, 3
 QUALITY_WEIGHT_NONE, QUALITY_WEIGHT_SCORE = 0, 1
 
@@ -1000,6 +1008,37 @@ class Stacker:
         """The displacement fields of an 8-bit stack over caller-held warps (stk_local_align): n x gh x gw x 2 float32
         (dx, dy), placed where the frames live; frame 0's and excluded frames' are zero. return_status adds the
         n x gh x gw int32 status planes (iterations run, or -1 .. -4; 0 for frames without a field)."""
+        return self._local_align(files, warps, mesh, include, is_affine, return_status, None)
+
+    def local_align_pyramid(self, files, warps, mesh: Optional["MeshParameters"] = None, levels: int = 3, include=None, *,
+                            is_affine=False, return_status: bool = False):
+        """local_align, coarse to fine over `levels` = 1 .. 4 pyramid levels (stk_local_align_pyramid): for shifts beyond a
+        patch's capture range. The status planes are level 0's; levels = 1 gives local_align's bits. The fields go into
+        mesh_stack, mesh_local_weighted_stack and mesh_drizzle_stack as they are."""
+        return self._local_align(files, warps, mesh, include, is_affine, return_status, int(levels))
+
+    def grey_pyramid(self, frame, levels: int):
+        """Levels 1 .. levels - 1 of the box pyramid of one 8-bit frame's integer grey (stk_grey_pyramid): a list of
+        (h >> l) x (w >> l) uint8 planes, placed where the frame lives."""
+        m = self._marshal([frame] if getattr(frame, "ndim", 0) == 3 else frame)
+        if m.n != 1:
+            raise InvalidParams("grey_pyramid: one frame expected")
+        levels = int(levels)
+        planes, ptrs = [], [None]
+        for l in range(1, max(levels, 1)):
+            shape = (max(m.h >> l, 1), max(m.w >> l, 1))
+            if m.location == DEVICE:
+                import torch
+                planes.append(torch.zeros(shape, dtype=torch.uint8, device=m.torch_device))
+                ptrs.append(planes[-1].data_ptr())
+            else:
+                planes.append(np.zeros(shape, np.uint8))
+                ptrs.append(planes[-1].ctypes.data)
+        pp = (C.c_void_p * len(ptrs))(*ptrs)
+        self._check(self._lib.stk_grey_pyramid(self._h, C.byref(m.c_frames), levels, C.cast(pp, C.c_void_p)))
+        return planes
+
+    def _local_align(self, files, warps, mesh, include, is_affine, return_status, levels):
         m = self._marshal(files)
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
@@ -1017,9 +1056,14 @@ class Stacker:
             fbase, sbase = fields.ctypes.data, status.ctypes.data
         fp = (C.c_void_p * m.n)(*[fbase + i * gh * gw * 8 for i in range(m.n)])
         sp = (C.c_void_p * m.n)(*[sbase + i * gh * gw * 4 for i in range(m.n)])
-        self._check(self._lib.stk_local_align(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                              None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine), C.byref(mp),
-                                              C.cast(fp, C.c_void_p), C.cast(sp, C.c_void_p) if return_status else None))
+        iptr = None if inc is None else C.c_void_p(inc.ctypes.data)
+        sptr = C.cast(sp, C.c_void_p) if return_status else None
+        if levels is None:
+            self._check(self._lib.stk_local_align(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), iptr, int(is_affine),
+                                                  C.byref(mp), C.cast(fp, C.c_void_p), sptr))
+        else:
+            self._check(self._lib.stk_local_align_pyramid(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), iptr, int(is_affine),
+                                                          C.byref(mp), levels, C.cast(fp, C.c_void_p), sptr))
         return (fields, status) if return_status else fields
 
     def _fields_arg(self, m: _Marshalled, fields, step, allow_none: bool = False):
@@ -1092,7 +1136,7 @@ class Stacker:
 
     def ecc_match_local_aligned(self, files, params: EccMatchParameters, mesh: Optional["MeshParameters"] = None,
                                 local: Optional["LocalParameters"] = None, scale_down_width: Optional[float] = None,
-                                return_stats: bool = False):
+                                return_stats: bool = False, *, _levels: Optional[int] = None):
         """ecc_match with local alignment (stk_ecc_match_local_aligned): every frame is folded through its ECC warp and the
         displacement field measured on top of it. local = None: the plain mean; else the local-sharpness weighted fold."""
         if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
@@ -1104,13 +1148,30 @@ class Stacker:
         stats = (_ffi.FrameStats * m.n)()
         p, mp = params._c(), (mesh or MeshParameters())._c()
         lp = None if local is None else local._c()
-        self._check(self._lib.stk_ecc_match_local_aligned(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                          C.byref(mp), None if lp is None else C.byref(lp), C.byref(img), stats))
+        if _levels is None:
+            self._check(self._lib.stk_ecc_match_local_aligned(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                              C.byref(mp), None if lp is None else C.byref(lp), C.byref(img), stats))
+        else:
+            self._check(self._lib.stk_ecc_match_local_aligned_pyramid(self._h, C.byref(m.c_frames), C.byref(p),
+                                                                      float(scale_down_width or 0.0), C.byref(mp), int(_levels),
+                                                                      None if lp is None else C.byref(lp), C.byref(img), stats))
         return (out, self._stats_list(stats, m.n)) if return_stats else out
+
+    def ecc_match_local_aligned_pyramid(self, files, params: EccMatchParameters, mesh: Optional["MeshParameters"] = None,
+                                        levels: int = 3, local: Optional["LocalParameters"] = None,
+                                        scale_down_width: Optional[float] = None, return_stats: bool = False):
+        """ecc_match_local_aligned with the coarse-to-fine field pass (stk_ecc_match_local_aligned_pyramid)."""
+        return self.ecc_match_local_aligned(files, params, mesh, local, scale_down_width, return_stats, _levels=int(levels))
+
+    def keypoint_match_local_aligned_pyramid(self, files, params: KeyPointMatchParameters, mesh: Optional["MeshParameters"] = None,
+                                             levels: int = 3, local: Optional["LocalParameters"] = None,
+                                             scale_down_width: Optional[float] = None, return_stats: bool = False):
+        """keypoint_match_local_aligned with the coarse-to-fine field pass (stk_keypoint_match_local_aligned_pyramid)."""
+        return self.keypoint_match_local_aligned(files, params, mesh, local, scale_down_width, return_stats, _levels=int(levels))
 
     def keypoint_match_local_aligned(self, files, params: KeyPointMatchParameters, mesh: Optional["MeshParameters"] = None,
                                      local: Optional["LocalParameters"] = None, scale_down_width: Optional[float] = None,
-                                     return_stats: bool = False):
+                                     return_stats: bool = False, *, _levels: Optional[int] = None):
         """keypoint_match with local alignment (stk_keypoint_match_local_aligned): (dropped, image[, stats])."""
         m = self._marshal(files)
         if m.n == 0:
@@ -1120,9 +1181,15 @@ class Stacker:
         dropped = C.c_int32(0)
         p, mp = params._c(), (mesh or MeshParameters())._c()
         lp = None if local is None else local._c()
-        self._check(self._lib.stk_keypoint_match_local_aligned(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                               C.byref(mp), None if lp is None else C.byref(lp), C.byref(img),
-                                                               C.byref(dropped), stats))
+        if _levels is None:
+            self._check(self._lib.stk_keypoint_match_local_aligned(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
+                                                                   C.byref(mp), None if lp is None else C.byref(lp), C.byref(img),
+                                                                   C.byref(dropped), stats))
+        else:
+            self._check(self._lib.stk_keypoint_match_local_aligned_pyramid(self._h, C.byref(m.c_frames), C.byref(p),
+                                                                           float(scale_down_width or 0.0), C.byref(mp), int(_levels),
+                                                                           None if lp is None else C.byref(lp), C.byref(img),
+                                                                           C.byref(dropped), stats))
         return (dropped.value, out) + ((self._stats_list(stats, m.n),) if return_stats else ())
 
     # -- drizzle integration onto a finer or larger output grid (extension beyond the reference) ----------

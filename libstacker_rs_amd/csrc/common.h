@@ -300,8 +300,33 @@ struct MeshLkArgs {
     int is_affine;
     int step, gw, gh, radius, max_iters;
     double eps2, max_shift2, min_eig4;   // epsilon^2, max_shift^2, 4 min_eig
+    // the seeded form only (launch_mesh_lk_seeded; one level of stk_local_align_pyramid): w, h, stride and the table are the
+    // level's, a node's centre is (k step >> level, j step >> level). valid[k]: the validity bytes of entry k (gh x gw).
+    // top != 0: the seed is (0, 0) and valid = status > 0; else the seed is 2 x fields[k][node] and a node that fails keeps
+    // its byte. A node that fails keeps its seed as d.
+    uint8_t* const* valid;
+    int level, top;
 };
 hipError_t launch_mesh_lk(const MeshLkArgs& a, int cn, hipStream_t s);
+hipError_t launch_mesh_lk_seeded(const MeshLkArgs& a, int cn, hipStream_t s);
+// the hole filling with the validity carried in valid[k] (read first, written back after the last pass) instead of status > 0
+hipError_t launch_mesh_fill_valid(float* const* fields, uint8_t* const* valid, int n_entries, int gw, int gh, int passes, void* scratch,
+                                  hipStream_t s);
+// Box pyramid of the integer grey (include/stacker.h, "Level images"): levels 1 .. levels - 1 of table entries first ..
+// first + n - 1 (frames[k].src: w x h x cn u8, `stride` bytes per row) in one pass. Level l of entry k is (w >> l) x
+// (h >> l) bytes, tightly packed, at planes + k entry_stride + mesh_pyr_offset(w, h, l).
+struct MeshPyrArgs {
+    const WarpFrame* frames;
+    uint8_t* planes;
+    size_t entry_stride, stride;
+    int first, n, w, h, levels;
+};
+__host__ __device__ inline size_t mesh_pyr_offset(int w, int h, int level) {
+    size_t o = 0;
+    for (int l = 1; l < level; l++) o += (size_t)(w >> l) * (size_t)(h >> l);
+    return o;
+}
+hipError_t launch_mesh_pyr(const MeshPyrArgs& a, int cn, hipStream_t s);
 // `passes` hole-filling passes over the fields of entries 1 .. n_entries - 1; scratch: (n_entries - 1) x
 // mesh_fill_scratch_bytes(gw, gh) bytes of device memory
 size_t mesh_fill_scratch_bytes(int gw, int gh);

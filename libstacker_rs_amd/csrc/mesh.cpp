@@ -1,10 +1,11 @@
 // mesh.cpp — local alignment: stk_mesh_grid, stk_local_align, stk_mesh_stack, stk_mesh_local_weighted_stack,
-// stk_ecc_match_local_aligned, stk_keypoint_match_local_aligned (an extension beyond the reference; definition in
+// stk_ecc_match_local_aligned, stk_keypoint_match_local_aligned, and the coarse-to-fine forms stk_grey_pyramid,
+// stk_local_align_pyramid, stk_*_match_local_aligned_pyramid (an extension beyond the reference; definition in
 // include/stacker.h, stk_mesh_params; kernels in kernels_mesh.hip and warp_body.h).
 // ctx->mesh (grow-only like the other workspaces) holds three pointer tables indexed like the frame table (the fold's
 // fields, the field pass's fields and status planes), the field and status planes the caller does not hold on the device,
 // the fill pass's scratch and a w x h x cn f32 image (the plain call's mean in the whole-stack forms, then a host output's
-// staging copy). The frame table is combine.h's; the local-weighted fold and its map pass are the local combine's
+// staging copy); behind that, for the coarse-to-fine forms, what PyrLayout lists. The frame table is combine.h's; the local-weighted fold and its map pass are the local combine's
 // (local.cpp, through context.h). Like the other combines, the whole-stack forms run the plain
 // call first and take the warps and the kept set from its stats; the frames are still resident in HBM, full size.
 #include <algorithm>
@@ -39,14 +40,19 @@ MeshLayout mesh_layout(size_t n_ptrs, size_t n_fields, size_t n_status, size_t n
     return L;
 }
 
-stk_status mesh_reserve(stk_ctx* ctx, const MeshLayout& L) {
-    if (ctx->mesh.reserve(L.total) != hipSuccess) {
+// total: the bytes of the layout with what follows it (the pyramid form's PyrLayout), 0 = the layout alone
+stk_status mesh_reserve(stk_ctx* ctx, const MeshLayout& L, size_t total = 0) {
+    total = std::max(total, L.total);
+    if (ctx->mesh.reserve(total) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(ctx, STK_HIP_ERROR, "mesh: device allocation of " + std::to_string(L.total) + " bytes failed (field planes of " +
+        return fail(ctx, STK_HIP_ERROR, "mesh: device allocation of " + std::to_string(total) + " bytes failed (field planes of " +
                                             std::to_string(L.fplane) + " bytes)");
     }
     return STK_OK;
 }
+
+stk_status local_align_impl(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                            const stk_mesh_params* p, int levels, float* const* fields, int32_t* const* status);
 
 bool mesh_step_ok(int step) { return step >= 8 && step <= 256 && (step & (step - 1)) == 0; }
 void mesh_grid_of(int w, int h, int step, int* gw, int* gh) {
@@ -126,6 +132,113 @@ stk_status mesh_mean_fold(stk_ctx* ctx, int ne, const FoldSpec& spec, const Mesh
     return STK_OK;
 }
 
+// ---- the coarse-to-fine form (include/stacker.h, "coarse-to-fine local alignment") -------------------------------------
+// What it keeps in ctx->mesh behind a MeshLayout, per table entry (entry 0 = frame 0): the validity bytes' pointer table and
+// planes, the pyramid planes (levels 1 .. levels - 1, mesh_pyr_offset) and one frame table per level above 0.
+struct PyrLayout {
+    size_t vptrs, valid, vplane, planes, pstride, tables, tbytes, total;     // byte offsets; vplane, pstride, tbytes: bytes of one
+};
+
+PyrLayout pyr_layout(size_t base, size_t n_entries, int gw, int gh, int w, int h, int levels) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    PyrLayout P{};
+    P.vptrs = up(base);
+    P.vplane = up((size_t)gw * gh);
+    P.valid = P.vptrs + up(n_entries * sizeof(void*));
+    P.pstride = up(mesh_pyr_offset(w, h, levels));
+    P.planes = P.valid + n_entries * P.vplane;
+    P.tbytes = up(n_entries * sizeof(WarpFrame));
+    P.tables = P.planes + n_entries * P.pstride;
+    P.total = P.tables + (size_t)(levels - 1) * P.tbytes;
+    return P;
+}
+
+stk_status pyr_validate(stk_ctx* ctx, const stk_frames* f, const stk_mesh_params* p, int levels) {
+    if (levels < 1 || levels > 4) return fail(ctx, STK_INVALID_PARAMS, "mesh: levels must be 1 .. 4");
+    if ((p->step >> (levels - 1)) < 4) return fail(ctx, STK_INVALID_PARAMS, "mesh: step >> (levels - 1) must be at least 4");
+    if ((std::min(f->width, f->height) >> (levels - 1)) < 16)
+        return fail(ctx, STK_INVALID_PARAMS, "mesh: min(width, height) >> (levels - 1) must be at least 16");
+    return STK_OK;
+}
+
+// C_l^-1 inv C_l in double, in the header's order of operations
+void pyr_level_matrix(const double* inv, int level, double* o) {
+    const double s = (double)(1 << level), c = 0.5 * (s - 1.0), is = 1.0 / s, cs = c * is;
+    double A[9];
+    for (int r = 0; r < 3; r++) {
+        A[3 * r] = inv[3 * r] * s;
+        A[3 * r + 1] = inv[3 * r + 1] * s;
+        A[3 * r + 2] = (inv[3 * r] * c + inv[3 * r + 1] * c) + inv[3 * r + 2];
+    }
+    for (int j = 0; j < 3; j++) {
+        o[j] = A[j] * is - cs * A[6 + j];
+        o[3 + j] = A[3 + j] * is - cs * A[6 + j];
+        o[6 + j] = A[6 + j];
+    }
+}
+
+// mesh_align_entries, coarse to fine: the pyramid of entries (build_ref ? 0 : 1) .. ne - 1, then per level from the top the
+// seeded estimation and the fill on the carried validity, all in stream order. fwd[k]: the forward matrix of entry k (k >= 1),
+// the one its uploaded table entry was made from. Synchronises; adds the device time of the levels to *ms and of the
+// pyramid pass to *pyr_ms.
+stk_status mesh_align_entries_pyr(stk_ctx* ctx, const MeshLayout& L, const PyrLayout& P, int ne, int w, int h, int cn, size_t rb,
+                                  int is_affine, const stk_mesh_params* p, int levels, int gw, int gh, const std::vector<float*>& fdev,
+                                  const std::vector<int32_t*>& sdev, const std::vector<const double*>& fwd, bool build_ref, double* ms,
+                                  double* pyr_ms) {
+    if (ne < 2) return STK_OK;
+    char* base = ctx->mesh.as<char>();
+    std::vector<uint8_t*> vdev(ne, nullptr);
+    for (int k = 1; k < ne; k++) vdev[k] = (uint8_t*)(base + P.valid + (size_t)k * P.vplane);
+    HIP_TRY(hipMemcpyAsync(base + L.fptrs, fdev.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base + L.sptrs, sdev.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base + P.vptrs, vdev.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<WarpFrame> lt((size_t)(levels - 1) * ne);
+    for (int l = 1; l < levels; l++) {
+        for (int k = 0; k < ne; k++) {
+            WarpFrame& f = lt[(size_t)(l - 1) * ne + k];
+            WarpFrame full;
+            warp_frame_make(full, nullptr, k ? fwd[k] : IDENTITY3, is_affine);
+            pyr_level_matrix(full.Md, l, f.Md);
+            for (int q = 0; q < 9; q++) f.M[q] = (float)f.Md[q];
+            f.src = base + P.planes + (size_t)k * P.pstride + mesh_pyr_offset(w, h, l);
+            f.flags = 0;
+        }
+        HIP_TRY(hipMemcpyAsync(base + P.tables + (size_t)(l - 1) * P.tbytes, &lt[(size_t)(l - 1) * ne], (size_t)ne * sizeof(WarpFrame),
+                               hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    MeshPyrArgs pa{};
+    pa.frames = ctx->warpframes.as<WarpFrame>();
+    pa.planes = (uint8_t*)(base + P.planes);
+    pa.entry_stride = P.pstride; pa.stride = rb;
+    pa.first = build_ref ? 0 : 1; pa.n = ne - pa.first;
+    pa.w = w; pa.h = h; pa.levels = levels;
+    HIP_TRY(launch_mesh_pyr(pa, cn, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev[6], ctx->stream));
+    for (int l = levels - 1; l >= 0; l--) {
+        MeshLkArgs a{};
+        a.frames = l ? (const WarpFrame*)(base + P.tables + (size_t)(l - 1) * P.tbytes) : ctx->warpframes.as<WarpFrame>();
+        a.fields = (float* const*)(base + L.fptrs);
+        a.status = l ? nullptr : (int* const*)(base + L.sptrs);
+        a.valid = (uint8_t* const*)(base + P.vptrs);
+        a.n_entries = ne;
+        a.w = w >> l; a.h = h >> l; a.stride = l ? (size_t)(w >> l) : rb; a.is_affine = is_affine;
+        a.step = p->step; a.gw = gw; a.gh = gh; a.radius = p->radius; a.max_iters = p->max_iters;
+        a.level = l; a.top = l == levels - 1;
+        const float max_shift = p->max_shift * (1.0f / (float)(1 << l));
+        a.eps2 = (double)p->epsilon * (double)p->epsilon;
+        a.max_shift2 = (double)max_shift * (double)max_shift;
+        a.min_eig4 = 4.0 * (double)p->min_eig;
+        HIP_TRY(launch_mesh_lk_seeded(a, l ? 1 : cn, ctx->stream));
+        HIP_TRY(launch_mesh_fill_valid(a.fields, a.valid, ne, gw, gh, p->fill, base + L.scratch, ctx->stream));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // the host tables leave scope
+    if (ms) *ms += ev_ms(ctx->ev[6], ctx->ev[5]);
+    if (pyr_ms) *pyr_ms += ev_ms(ctx->ev[4], ctx->ev[6]);
+    return STK_OK;
+}
+
 // the checks the two whole-stack forms share, in the order the errors are reported
 stk_status mesh_match_check(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mesh, const stk_local_params* local,
                             const stk_image_f32* out) {
@@ -141,8 +254,10 @@ stk_status mesh_match_check(stk_ctx* ctx, const stk_frames* frames, const stk_me
 // The field pass of a whole-stack form over the ne entries of ctx->warpframes (entry 0 = frame 0; the table is uploaded):
 // the planes of entries 1 .. ne - 1 into L.fields, then the fold's pointer table (entry 0: null) at L.tptrs. Synchronises;
 // adds the pass's device time to *ms.
+// levels > 0: the coarse-to-fine pass (P: its layout behind L; fwd: the entries' forward matrices).
 stk_status mesh_entry_fields(stk_ctx* ctx, const MeshLayout& L, int ne, int w, int h, int cn, size_t rb, int is_affine,
-                             const stk_mesh_params* mp, MeshFoldArgs* out, double* ms) {
+                             const stk_mesh_params* mp, MeshFoldArgs* out, double* ms, int levels = 0, const PyrLayout* P = nullptr,
+                             const std::vector<const double*>* fwd = nullptr) {
     int gw, gh;
     mesh_grid_of(w, h, mp->step, &gw, &gh);
     char* base = ctx->mesh.as<char>();
@@ -152,7 +267,8 @@ stk_status mesh_entry_fields(stk_ctx* ctx, const MeshLayout& L, int ne, int w, i
         fdev[k] = (float*)(base + L.fields + (size_t)(k - 1) * L.fplane);
         sdev[k] = (int32_t*)(base + L.status + (size_t)(k - 1) * L.splane);
     }
-    stk_status st = mesh_align_entries(ctx, L, ne, w, h, cn, rb, is_affine, mp, gw, gh, fdev, sdev, ms);
+    stk_status st = levels > 0 ? mesh_align_entries_pyr(ctx, L, *P, ne, w, h, cn, rb, is_affine, mp, levels, gw, gh, fdev, sdev, *fwd, true, ms, ms)
+                               : mesh_align_entries(ctx, L, ne, w, h, cn, rb, is_affine, mp, gw, gh, fdev, sdev, ms);
     if (st) return st;
     HIP_TRY(hipMemcpyAsync(base + L.tptrs, fdev.data(), (size_t)ne * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));          // `fdev` leaves scope
@@ -161,13 +277,15 @@ stk_status mesh_entry_fields(stk_ctx* ctx, const MeshLayout& L, int ne, int w, i
 }
 
 // the workspaces of a whole-stack form over n frames, reserved before the plain call writes its mean into ctx->mesh
-stk_status mesh_match_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mp, const stk_local_params* lp, MeshLayout* L) {
+stk_status mesh_match_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mp, const stk_local_params* lp, MeshLayout* L,
+                              int levels = 0, PyrLayout* P = nullptr) {
     (void)hipSetDevice(ctx->device);
     const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
     int gw, gh;
     mesh_grid_of(w, h, mp->step, &gw, &gh);
     *L = mesh_layout((size_t)n, (size_t)n, (size_t)n, (size_t)n, gw, gh, (size_t)w * h * cn);
-    stk_status st = mesh_reserve(ctx, *L);
+    if (levels > 0) *P = pyr_layout(L->total, (size_t)n, gw, gh, w, h, levels);
+    stk_status st = mesh_reserve(ctx, *L, levels > 0 ? P->total : 0);
     if (st) return st;
     if (lp) {
         const LocalLayout LL = local_layout((size_t)n, n, w, h, cn, (size_t)n);
@@ -178,12 +296,13 @@ stk_status mesh_match_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_
 
 // the combine of the whole-stack forms over the kept frames (`dev`: the resident full-size frames by frame index): field
 // pass, then the mesh mean fold, or the map pass and the mesh local-weighted fold with unit records
-CombineFinish mesh_match_finish(stk_ctx* ctx, const MeshLayout& L, const stk_mesh_params* mp, const stk_local_params* lp, stk_image_f32* out) {
+CombineFinish mesh_match_finish(stk_ctx* ctx, const MeshLayout& L, const stk_mesh_params* mp, const stk_local_params* lp, stk_image_f32* out,
+                                int levels = 0, const PyrLayout& P = PyrLayout{}) {
     return [=](const EntryTable& table, const std::vector<const void*>& dev, const FoldSpec& spec, const stk_frame_stats*, double* ms) {
         const int ne = table.size(), w = spec.w, h = spec.h, cn = spec.cn;
         const size_t rb = spec.src_row_bytes;
         MeshFoldArgs mf{};
-        stk_status st = mesh_entry_fields(ctx, L, ne, w, h, cn, rb, spec.is_affine, mp, &mf, ms);
+        stk_status st = mesh_entry_fields(ctx, L, ne, w, h, cn, rb, spec.is_affine, mp, &mf, ms, levels, &P, &table.M);
         if (st) return st;
         if (!lp) return mesh_mean_fold(ctx, ne, spec, mf, (float*)(ctx->mesh.as<char>() + L.image), out, ms);
         const LocalLayout LL = local_layout((size_t)ne, ne, w, h, cn, (size_t)ne);
@@ -279,6 +398,100 @@ stk_status stk_mesh_grid(int32_t width, int32_t height, int32_t step, int32_t* g
 
 stk_status stk_local_align(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
                            const stk_mesh_params* p, float* const* fields, int32_t* const* status) {
+    return local_align_impl(ctx, frames, M, include, is_affine, p, 0, fields, status);
+}
+
+stk_status stk_local_align_pyramid(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                                   const stk_mesh_params* p, int32_t levels, float* const* fields, int32_t* const* status) {
+    stk_status st = check_frames(ctx, frames, false, false);
+    if (st) return st;
+    if ((st = mesh_validate(ctx, p))) return st;
+    if ((st = pyr_validate(ctx, frames, p, levels))) return st;
+    return local_align_impl(ctx, frames, M, include, is_affine, p, levels, fields, status);
+}
+
+stk_status stk_grey_pyramid(stk_ctx* ctx, const stk_frames* frame, int32_t levels, uint8_t* const* planes) {
+    stk_status st = check_frames(ctx, frame, false, false);
+    if (st) return st;
+    if (frame->n != 1) return fail(ctx, STK_INVALID_PARAMS, "grey pyramid: one frame expected");
+    if ((st = mesh_check_depth(ctx, frame))) return st;
+    const int w = frame->width, h = frame->height, cn = frame->channels;
+    if (levels < 2 || levels > 4) return fail(ctx, STK_INVALID_PARAMS, "grey pyramid: levels must be 2 .. 4");
+    if ((std::min(w, h) >> (levels - 1)) < 1) return fail(ctx, STK_INVALID_PARAMS, "grey pyramid: min(width, height) >> (levels - 1) must be at least 1");
+    if (!planes) return fail(ctx, STK_INVALID_PARAMS, "null planes");
+    for (int l = 1; l < levels; l++)
+        if (!planes[l]) return fail(ctx, STK_INVALID_PARAMS, "null pyramid plane");
+    (void)hipSetDevice(ctx->device);
+    timing_begin(ctx);
+    const size_t rb = frame_row_bytes(frame), fb = rb * h;
+    const bool host = frame->location == STK_HOST;
+    const void* src = frame->data[0];
+    if (host) {
+        HIP_TRY(ctx->frames.reserve(fb));
+        HIP_TRY(hipMemcpyAsync(ctx->frames.p, frame->data[0], frame_copy_bytes(frame), hipMemcpyHostToDevice, ctx->stream));
+        src = ctx->frames.p;
+    }
+    const size_t bytes = mesh_pyr_offset(w, h, levels);
+    if (ctx->mesh.reserve(bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, STK_HIP_ERROR, "mesh: device allocation of " + std::to_string(bytes) + " bytes failed (pyramid planes)");
+    }
+    std::vector<WarpFrame> wf(1);
+    make_warp_frame(wf[0], src, IDENTITY3, 1);
+    if ((st = warp_table_upload(ctx, wf, rb, w, h, 1))) return st;
+    MeshPyrArgs pa{};
+    pa.frames = ctx->warpframes.as<WarpFrame>();
+    pa.planes = ctx->mesh.as<uint8_t>();
+    pa.entry_stride = bytes; pa.stride = rb; pa.first = 0; pa.n = 1; pa.w = w; pa.h = h; pa.levels = levels;
+    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    HIP_TRY(launch_mesh_pyr(pa, cn, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+    for (int l = 1; l < levels; l++)
+        HIP_TRY(hipMemcpyAsync(planes[l], pa.planes + mesh_pyr_offset(w, h, l), (size_t)(w >> l) * (size_t)(h >> l),
+                               host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // `wf` leaves scope
+    ctx->timing.prep_ms = ev_ms(ctx->ev[4], ctx->ev[5]);
+    return STK_OK;
+}
+
+stk_status stk_ecc_match_local_aligned_pyramid(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                               const stk_mesh_params* mesh, int32_t levels, const stk_local_params* local,
+                                               stk_image_f32* out, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    stk_status st = mesh_match_check(ctx, frames, mesh, local, out);
+    if (st) return st;
+    if ((st = pyr_validate(ctx, frames, mesh, levels))) return st;
+    MeshLayout L;
+    PyrLayout P;
+    if ((st = mesh_match_reserve(ctx, frames, mesh, local, &L, levels, &P))) return st;
+    return ecc_match_then(ctx, frames, params, scale_down_width, (float*)(ctx->mesh.as<char>() + L.image), stats,
+                          mesh_match_finish(ctx, L, mesh, local, out, levels, P));
+}
+
+stk_status stk_keypoint_match_local_aligned_pyramid(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                                    float scale_down_width, const stk_mesh_params* mesh, int32_t levels,
+                                                    const stk_local_params* local, stk_image_f32* out, int32_t* dropped,
+                                                    stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    stk_status st = mesh_match_check(ctx, frames, mesh, local, out);
+    if (st) return st;
+    if ((st = pyr_validate(ctx, frames, mesh, levels))) return st;
+    if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
+    if (local && (st = local_check_border(ctx, params->border_mode, params->border_value))) return st;
+    MeshLayout L;
+    PyrLayout P;
+    if ((st = mesh_match_reserve(ctx, frames, mesh, local, &L, levels, &P))) return st;
+    return keypoint_match_then(ctx, frames, params, scale_down_width, (float*)(ctx->mesh.as<char>() + L.image), dropped, stats,
+                               mesh_match_finish(ctx, L, mesh, local, out, levels, P));
+}
+
+}  // extern "C"
+
+namespace {
+
+// stk_local_align (levels = 0: the single-level kernel) and stk_local_align_pyramid (levels >= 1, checked)
+stk_status local_align_impl(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                            const stk_mesh_params* p, int levels, float* const* fields, int32_t* const* status) {
     stk_status st = check_frames(ctx, frames, false, false);
     if (st) return st;
     if ((st = mesh_validate(ctx, p))) return st;
@@ -309,14 +522,17 @@ stk_status stk_local_align(stk_ctx* ctx, const stk_frames* frames, const double*
         HIP_TRY(hipMemcpyAsync(ctx->frames.p, frames->data[0], frame_copy_bytes(frames), hipMemcpyHostToDevice, ctx->stream));
     }
     const MeshLayout L = mesh_layout((size_t)batch + 1, host ? (size_t)batch : 0, (size_t)batch, (size_t)batch, gw, gh, 0);
-    if ((st = mesh_reserve(ctx, L))) return st;
+    PyrLayout P{};
+    if (levels > 0) P = pyr_layout(L.total, (size_t)batch + 1, gw, gh, w, h, levels);
+    if ((st = mesh_reserve(ctx, L, P.total))) return st;
     char* base = ctx->mesh.as<char>();
-    double ms = 0.0;
+    double ms = 0.0, pyr_ms = 0.0;
     for (size_t b0 = 0; b0 < moving.size(); b0 += (size_t)batch) {
         const int nb = (int)std::min<size_t>((size_t)batch, moving.size() - b0);
         std::vector<WarpFrame> wf(nb + 1);
         std::vector<float*> fdev(nb + 1, nullptr);
         std::vector<int32_t*> sdev(nb + 1, nullptr);
+        std::vector<const double*> fwd(nb + 1, nullptr);
         make_warp_frame(wf[0], host ? (const void*)ctx->frames.p : frames->data[0], IDENTITY3, is_affine);
         for (int k = 1; k <= nb; k++) {
             const int i = moving[b0 + k - 1];
@@ -327,12 +543,16 @@ stk_status stk_local_align(stk_ctx* ctx, const stk_frames* frames, const double*
                 src = d;
             }
             make_warp_frame(wf[k], src, M + 9 * (size_t)i, is_affine);
+            fwd[k] = M + 9 * (size_t)i;
             fdev[k] = host ? (float*)(base + L.fields + (size_t)(k - 1) * L.fplane) : fields[i];
             sdev[k] = (!host && status && status[i]) ? status[i] : (int32_t*)(base + L.status + (size_t)(k - 1) * L.splane);
         }
         if ((st = warp_table_upload(ctx, wf, rb, w, h, is_affine))) return st;
         // (mesh_align_entries synchronises: `wf` and the pointer vectors outlive the copies)
-        if ((st = mesh_align_entries(ctx, L, nb + 1, w, h, cn, rb, is_affine, p, gw, gh, fdev, sdev, &ms))) return st;
+        if (levels > 0)
+            st = mesh_align_entries_pyr(ctx, L, P, nb + 1, w, h, cn, rb, is_affine, p, levels, gw, gh, fdev, sdev, fwd, b0 == 0, &ms, &pyr_ms);
+        else st = mesh_align_entries(ctx, L, nb + 1, w, h, cn, rb, is_affine, p, gw, gh, fdev, sdev, &ms);
+        if (st) return st;
         if (host) {
             for (int k = 1; k <= nb; k++) {
                 const int i = moving[b0 + k - 1];
@@ -343,8 +563,13 @@ stk_status stk_local_align(stk_ctx* ctx, const stk_frames* frames, const double*
         }
     }
     ctx->timing.align_ms = ms;
+    ctx->timing.prep_ms = pyr_ms;
     return STK_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 stk_status stk_mesh_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
                           int32_t border_mode, const double* border_value, double alpha, const float* const* fields, int32_t step,
