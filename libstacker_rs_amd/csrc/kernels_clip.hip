@@ -11,7 +11,7 @@
 // The shifted moments keep the variance accurate (the samples sit close to c). Cost over the mean fold's per-sample work:
 // a subtract, a multiply, two adds, two compares and the selects — the c / L / U planes are read once and written once per
 // pass, like the accumulator.
-#include "warp_cubic_body.h"
+#include "fold_launch.h"
 
 namespace stk {
 
@@ -110,32 +110,7 @@ struct ClipU8C3 {
 
 hipError_t launch_clip_pass(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
     if (a.n_frames <= 0) return hipErrorInvalidValue;
-    if (a.interp == STK_INTER_CUBIC) {
-        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
-        if (warp_u8c3_applies(a, depth)) return launch_warp_cubic_u8c3<true, ClipU8C3>(a, c, g, s);
-        return launch_warp_cubic<true, ClipGeneric>(a, c, depth, g, s);
-    }
-    if (warp_u8c3_applies(a, depth)) {
-        // the mean fold's default launch shape (one wave per row of 64 pixels, four frames in flight)
-        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
-        if (a.is_affine) warp_accumulate_u8c3_kernel<true, 1, 4, true, ClipU8C3><<<g, 256, 0, s>>>(a, c);
-        else warp_accumulate_u8c3_kernel<false, 1, 4, true, ClipU8C3><<<g, 256, 0, s>>>(a, c);
-        return hipGetLastError();
-    }
-    const dim3 grid((a.dw + 63) / 64, (a.dh + 3) / 4);
-#define STK_CLIP_CASE(T, CN) warp_accumulate_kernel<T, CN, true, ClipGeneric<CN>><<<grid, 256, 0, s>>>(a, c)
-    if (depth == 8 && a.cn == 3) STK_CLIP_CASE(uint8_t, 3);
-    else if (depth == 8 && a.cn == 1) STK_CLIP_CASE(uint8_t, 1);
-    else if (depth == 8 && a.cn == 4) STK_CLIP_CASE(uint8_t, 4);
-    else if (depth == 16 && a.cn == 3) STK_CLIP_CASE(uint16_t, 3);
-    else if (depth == 16 && a.cn == 1) STK_CLIP_CASE(uint16_t, 1);
-    else if (depth == 16 && a.cn == 4) STK_CLIP_CASE(uint16_t, 4);
-    else if (depth == 32 && a.cn == 3) STK_CLIP_CASE(float, 3);
-    else if (depth == 32 && a.cn == 1) STK_CLIP_CASE(float, 1);
-    else if (depth == 32 && a.cn == 4) STK_CLIP_CASE(float, 4);
-    else return hipErrorInvalidValue;
-#undef STK_CLIP_CASE
-    return hipGetLastError();
+    return launch_fold<ClipU8C3, ClipGeneric>(a, c, depth, a.dh, s);
 }
 
 // ---- the weighted clip: normalised, coverage-aware rejection (stk_clip_stack_weighted and the *_clipped_weighted entry
@@ -273,31 +248,7 @@ struct ClipWU8C3 {
 
 hipError_t launch_clip_pass_weighted(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
     if (a.n_frames <= 0 || !c.coef) return hipErrorInvalidValue;
-    if (a.interp == STK_INTER_CUBIC) {
-        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
-        if (warp_u8c3_applies(a, depth)) return launch_warp_cubic_u8c3<true, ClipWU8C3>(a, c, g, s);
-        return launch_warp_cubic<true, ClipWGeneric>(a, c, depth, g, s);
-    }
-    if (warp_u8c3_applies(a, depth)) {
-        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
-        if (a.is_affine) warp_accumulate_u8c3_kernel<true, 1, 4, true, ClipWU8C3><<<g, 256, 0, s>>>(a, c);
-        else warp_accumulate_u8c3_kernel<false, 1, 4, true, ClipWU8C3><<<g, 256, 0, s>>>(a, c);
-        return hipGetLastError();
-    }
-    const dim3 grid((a.dw + 63) / 64, (a.dh + 3) / 4);
-#define STK_CLIPW_CASE(T, CN) warp_accumulate_kernel<T, CN, true, ClipWGeneric<CN>><<<grid, 256, 0, s>>>(a, c)
-    if (depth == 8 && a.cn == 3) STK_CLIPW_CASE(uint8_t, 3);
-    else if (depth == 8 && a.cn == 1) STK_CLIPW_CASE(uint8_t, 1);
-    else if (depth == 8 && a.cn == 4) STK_CLIPW_CASE(uint8_t, 4);
-    else if (depth == 16 && a.cn == 3) STK_CLIPW_CASE(uint16_t, 3);
-    else if (depth == 16 && a.cn == 1) STK_CLIPW_CASE(uint16_t, 1);
-    else if (depth == 16 && a.cn == 4) STK_CLIPW_CASE(uint16_t, 4);
-    else if (depth == 32 && a.cn == 3) STK_CLIPW_CASE(float, 3);
-    else if (depth == 32 && a.cn == 1) STK_CLIPW_CASE(float, 1);
-    else if (depth == 32 && a.cn == 4) STK_CLIPW_CASE(float, 4);
-    else return hipErrorInvalidValue;
-#undef STK_CLIPW_CASE
-    return hipGetLastError();
+    return launch_fold<ClipWU8C3, ClipWGeneric>(a, c, depth, a.dh, s);
 }
 
 }  // namespace stk

@@ -194,19 +194,7 @@ hipError_t launch_drizzle(const DrizzleArgs& a, int depth, hipStream_t s) {
                      a.mesh_gh != ((a.sh - 1 + (1 << a.mesh_shift) - 1) >> a.mesh_shift) + 1))
         return hipErrorInvalidValue;                                 // the field planes are read on this grid and no other
     const dim3 grid((a.ow + 63) / 64, (a.oh + 3) / 4);
-#define STK_DRIZZLE_CASE(D, T, CN) if (depth == D && a.cn == CN) drizzle_launch<T, CN>(a, grid, s)
-    STK_DRIZZLE_CASE(8, uint8_t, 3);
-    else STK_DRIZZLE_CASE(8, uint8_t, 1);
-    else STK_DRIZZLE_CASE(8, uint8_t, 4);
-    else STK_DRIZZLE_CASE(16, uint16_t, 3);
-    else STK_DRIZZLE_CASE(16, uint16_t, 1);
-    else STK_DRIZZLE_CASE(16, uint16_t, 4);
-    else STK_DRIZZLE_CASE(32, float, 3);
-    else STK_DRIZZLE_CASE(32, float, 1);
-    else STK_DRIZZLE_CASE(32, float, 4);
-    else return hipErrorInvalidValue;
-#undef STK_DRIZZLE_CASE
-    return hipGetLastError();
+    return dispatch_depth_cn(depth, a.cn, [&](auto t, auto ch) { drizzle_launch<decltype(t), decltype(ch)::value>(a, grid, s); });
 }
 
 }  // namespace stk

@@ -184,19 +184,10 @@ hipError_t launch_local_fold(const WarpArgs& a, const ClipArgs& c, int depth, hi
     if (a.n_frames <= 0 || !c.maps || c.power < 1 || c.power > 4) return hipErrorInvalidValue;
     const dim3 grid((a.dw + 63) / 64, (a.dh + 3) / 4);
     if (a.interp == STK_INTER_CUBIC) return launch_warp_cubic<true, FoldLocal>(a, c, depth, grid, s);
-#define STK_LOCAL_CASE(T, CN) warp_accumulate_kernel<T, CN, true, FoldLocal<CN>><<<grid, 256, 0, s>>>(a, c)
-    if (depth == 8 && a.cn == 3) STK_LOCAL_CASE(uint8_t, 3);
-    else if (depth == 8 && a.cn == 1) STK_LOCAL_CASE(uint8_t, 1);
-    else if (depth == 8 && a.cn == 4) STK_LOCAL_CASE(uint8_t, 4);
-    else if (depth == 16 && a.cn == 3) STK_LOCAL_CASE(uint16_t, 3);
-    else if (depth == 16 && a.cn == 1) STK_LOCAL_CASE(uint16_t, 1);
-    else if (depth == 16 && a.cn == 4) STK_LOCAL_CASE(uint16_t, 4);
-    else if (depth == 32 && a.cn == 3) STK_LOCAL_CASE(float, 3);
-    else if (depth == 32 && a.cn == 1) STK_LOCAL_CASE(float, 1);
-    else if (depth == 32 && a.cn == 4) STK_LOCAL_CASE(float, 4);
-    else return hipErrorInvalidValue;
-#undef STK_LOCAL_CASE
-    return hipGetLastError();
+    return dispatch_depth_cn(depth, a.cn, [&](auto t, auto ch) {
+        constexpr int CN = decltype(ch)::value;
+        warp_accumulate_kernel<decltype(t), CN, true, FoldLocal<CN>><<<grid, 256, 0, s>>>(a, c);
+    });
 }
 
 }  // namespace stk

@@ -330,23 +330,11 @@ hipError_t launch_mesh_fold(const WarpArgs& a, const ClipArgs& c, int depth, boo
         return hipErrorInvalidValue;
     if (local ? (!c.maps || c.power < 1 || c.power > 4) : !a.acc) return hipErrorInvalidValue;
     const dim3 grid((a.dw + 63) / 64, (a.dh + 3) / 4);
-#define STK_MESH_CASE(T, CN)                                                                             \
-    do {                                                                                                 \
-        if (local) warp_accumulate_kernel<T, CN, true, Mesh<FoldLocal<CN>>><<<grid, 256, 0, s>>>(a, c);  \
-        else warp_accumulate_kernel<T, CN, false, Mesh<NoClip>><<<grid, 256, 0, s>>>(a, c);              \
-    } while (0)
-    if (depth == 8 && a.cn == 3) STK_MESH_CASE(uint8_t, 3);
-    else if (depth == 8 && a.cn == 1) STK_MESH_CASE(uint8_t, 1);
-    else if (depth == 8 && a.cn == 4) STK_MESH_CASE(uint8_t, 4);
-    else if (depth == 16 && a.cn == 3) STK_MESH_CASE(uint16_t, 3);
-    else if (depth == 16 && a.cn == 1) STK_MESH_CASE(uint16_t, 1);
-    else if (depth == 16 && a.cn == 4) STK_MESH_CASE(uint16_t, 4);
-    else if (depth == 32 && a.cn == 3) STK_MESH_CASE(float, 3);
-    else if (depth == 32 && a.cn == 1) STK_MESH_CASE(float, 1);
-    else if (depth == 32 && a.cn == 4) STK_MESH_CASE(float, 4);
-    else return hipErrorInvalidValue;
-#undef STK_MESH_CASE
-    return hipGetLastError();
+    return dispatch_depth_cn(depth, a.cn, [&](auto t, auto ch) {
+        constexpr int CN = decltype(ch)::value;
+        if (local) warp_accumulate_kernel<decltype(t), CN, true, Mesh<FoldLocal<CN>>><<<grid, 256, 0, s>>>(a, c);
+        else warp_accumulate_kernel<decltype(t), CN, false, Mesh<NoClip>><<<grid, 256, 0, s>>>(a, c);
+    });
 }
 
 }  // namespace stk

@@ -145,19 +145,7 @@ hipError_t launch_reject(const RejectArgs& a, int depth, hipStream_t s) {
         return hipErrorInvalidValue;
     const dim3 grid((a.sw + REJECT_TW - 1) / REJECT_TW, (a.sh + REJECT_TH - 1) / REJECT_TH, a.n_entries);
     if (grid.y > 65535) return hipErrorInvalidValue;
-#define STK_REJECT_CASE(D, T, CN) if (depth == D && a.cn == CN) reject_launch<T, CN>(a, grid, s)
-    STK_REJECT_CASE(8, uint8_t, 3);
-    else STK_REJECT_CASE(8, uint8_t, 1);
-    else STK_REJECT_CASE(8, uint8_t, 4);
-    else STK_REJECT_CASE(16, uint16_t, 3);
-    else STK_REJECT_CASE(16, uint16_t, 1);
-    else STK_REJECT_CASE(16, uint16_t, 4);
-    else STK_REJECT_CASE(32, float, 3);
-    else STK_REJECT_CASE(32, float, 1);
-    else STK_REJECT_CASE(32, float, 4);
-    else return hipErrorInvalidValue;
-#undef STK_REJECT_CASE
-    return hipGetLastError();
+    return dispatch_depth_cn(depth, a.cn, [&](auto t, auto ch) { reject_launch<decltype(t), decltype(ch)::value>(a, grid, s); });
 }
 
 }  // namespace stk

@@ -202,19 +202,9 @@ hipError_t launch_warp_accumulate(const WarpArgs& a, int depth, hipStream_t s) {
         else warp_accumulate_u16c3_kernel<false><<<grid, 256, 0, s>>>(a);
         return hipGetLastError();
     }
-#define STK_WARP_CASE(T, CN) warp_accumulate_kernel<T, CN, false, NoClip><<<grid, 256, 0, s>>>(a, ClipArgs{})
-    if (depth == 8 && a.cn == 3) STK_WARP_CASE(uint8_t, 3);
-    else if (depth == 8 && a.cn == 1) STK_WARP_CASE(uint8_t, 1);
-    else if (depth == 16 && a.cn == 3) STK_WARP_CASE(uint16_t, 3);
-    else if (depth == 16 && a.cn == 1) STK_WARP_CASE(uint16_t, 1);
-    else if (depth == 32 && a.cn == 3) STK_WARP_CASE(float, 3);
-    else if (depth == 32 && a.cn == 1) STK_WARP_CASE(float, 1);
-    else if (depth == 8 && a.cn == 4) STK_WARP_CASE(uint8_t, 4);        // BGRA: the alpha plane is warped and summed like a colour (the
-    else if (depth == 16 && a.cn == 4) STK_WARP_CASE(uint16_t, 4);      // reference converts, warps and adds whatever imread returned)
-    else if (depth == 32 && a.cn == 4) STK_WARP_CASE(float, 4);
-    else return hipErrorInvalidValue;
-#undef STK_WARP_CASE
-    return hipGetLastError();
+    return dispatch_depth_cn(depth, a.cn, [&](auto t, auto ch) {
+        warp_accumulate_kernel<decltype(t), decltype(ch)::value, false, NoClip><<<grid, 256, 0, s>>>(a, ClipArgs{});
+    });
 }
 
 }  // namespace stk

@@ -9,7 +9,7 @@
 //     bit), grid z = entry - 1. A thread walks `reps` stepped rows of one entry privately in f64 before its wave reduces by
 //     lane shuffles and writes one partial; moments_reduce_kernel then adds an entry's partials in index order. The order
 //     of every addition is fixed by the geometry and the step alone: the same bits on every call. No atomics.
-#include "warp_cubic_body.h"
+#include "fold_launch.h"
 
 namespace stk {
 
@@ -34,32 +34,7 @@ __global__ __launch_bounds__(64) void moments_reduce_kernel(const double* __rest
 
 hipError_t launch_weighted_fold(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
     if (a.n_frames <= 0) return hipErrorInvalidValue;
-    if (a.interp == STK_INTER_CUBIC) {
-        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
-        if (warp_u8c3_applies(a, depth)) return launch_warp_cubic_u8c3<true, FoldWeighted<3>>(a, c, g, s);
-        return launch_warp_cubic<true, FoldWeighted>(a, c, depth, g, s);
-    }
-    if (warp_u8c3_applies(a, depth)) {
-        // the mean fold's default launch shape (one wave per row of 64 pixels, four frames in flight)
-        const dim3 g((a.dw + 63) / 64, (a.dh + 3) / 4);
-        if (a.is_affine) warp_accumulate_u8c3_kernel<true, 1, 4, true, FoldWeighted<3>><<<g, 256, 0, s>>>(a, c);
-        else warp_accumulate_u8c3_kernel<false, 1, 4, true, FoldWeighted<3>><<<g, 256, 0, s>>>(a, c);
-        return hipGetLastError();
-    }
-    const dim3 grid((a.dw + 63) / 64, (a.dh + 3) / 4);
-#define STK_WEIGHTED_CASE(T, CN) warp_accumulate_kernel<T, CN, true, FoldWeighted<CN>><<<grid, 256, 0, s>>>(a, c)
-    if (depth == 8 && a.cn == 3) STK_WEIGHTED_CASE(uint8_t, 3);
-    else if (depth == 8 && a.cn == 1) STK_WEIGHTED_CASE(uint8_t, 1);
-    else if (depth == 8 && a.cn == 4) STK_WEIGHTED_CASE(uint8_t, 4);
-    else if (depth == 16 && a.cn == 3) STK_WEIGHTED_CASE(uint16_t, 3);
-    else if (depth == 16 && a.cn == 1) STK_WEIGHTED_CASE(uint16_t, 1);
-    else if (depth == 16 && a.cn == 4) STK_WEIGHTED_CASE(uint16_t, 4);
-    else if (depth == 32 && a.cn == 3) STK_WEIGHTED_CASE(float, 3);
-    else if (depth == 32 && a.cn == 1) STK_WEIGHTED_CASE(float, 1);
-    else if (depth == 32 && a.cn == 4) STK_WEIGHTED_CASE(float, 4);
-    else return hipErrorInvalidValue;
-#undef STK_WEIGHTED_CASE
-    return hipGetLastError();
+    return launch_fold<FoldWeighted<3>, FoldWeighted>(a, c, depth, a.dh, s);
 }
 
 // rows per thread: at least 8, and enough that an entry has about 1024 partials at most (the second launch adds them one
@@ -80,25 +55,12 @@ hipError_t launch_overlap_moments(const WarpArgs& a, ClipArgs c, int depth, int 
     const MomentsPlan p = moments_plan(a.dw, a.dh, step);
     c.step = step; c.reps = p.reps;
     const dim3 grid(p.bx, p.by, a.n_frames - 1);
-    const bool cubic = a.interp == STK_INTER_CUBIC;
-    if (cubic) {
-        const hipError_t ce = launch_warp_cubic<true, FoldMoments>(a, c, depth, grid, s);
-        if (ce != hipSuccess) return ce;
-    }
-#define STK_MOMENTS_CASE(T, CN) warp_accumulate_kernel<T, CN, true, FoldMoments<CN>><<<grid, 256, 0, s>>>(a, c)
-    if (cubic) {}
-    else if (depth == 8 && a.cn == 3) STK_MOMENTS_CASE(uint8_t, 3);
-    else if (depth == 8 && a.cn == 1) STK_MOMENTS_CASE(uint8_t, 1);
-    else if (depth == 8 && a.cn == 4) STK_MOMENTS_CASE(uint8_t, 4);
-    else if (depth == 16 && a.cn == 3) STK_MOMENTS_CASE(uint16_t, 3);
-    else if (depth == 16 && a.cn == 1) STK_MOMENTS_CASE(uint16_t, 1);
-    else if (depth == 16 && a.cn == 4) STK_MOMENTS_CASE(uint16_t, 4);
-    else if (depth == 32 && a.cn == 3) STK_MOMENTS_CASE(float, 3);
-    else if (depth == 32 && a.cn == 1) STK_MOMENTS_CASE(float, 1);
-    else if (depth == 32 && a.cn == 4) STK_MOMENTS_CASE(float, 4);
-    else return hipErrorInvalidValue;
-#undef STK_MOMENTS_CASE
-    hipError_t e = hipGetLastError();
+    hipError_t e;
+    if (a.interp == STK_INTER_CUBIC) e = launch_warp_cubic<true, FoldMoments>(a, c, depth, grid, s);
+    else e = dispatch_depth_cn(depth, a.cn, [&](auto t, auto ch) {
+        constexpr int CN = decltype(ch)::value;
+        warp_accumulate_kernel<decltype(t), CN, true, FoldMoments<CN>><<<grid, 256, 0, s>>>(a, c);
+    });
     if (e != hipSuccess) return e;
     moments_reduce_kernel<<<a.n_frames - 1, 64, 0, s>>>(c.partials, p.parts(), 1 + 5 * a.cn, a.cn, moments);
     return hipGetLastError();

@@ -620,4 +620,25 @@ inline bool warp_u8c3_applies(const WarpArgs& a, int depth) {
            (size_t)a.sw * a.sh * 3 >= 16 && a.src_stride * (size_t)a.sh < ((size_t)1 << 31) && a.src_stride < (1u << 23) && a.sh < (1 << 23);
 }
 
+// The one (depth, cn) ladder of every launcher (host side): launch(T{}, Channels<CN>{}) for the sample type T of `depth`
+// (8, 16 or 32 bits) and cn = 1, 3 or 4 (BGRA: the alpha plane is warped and summed like a colour — the reference converts,
+// warps and adds whatever imread returned). Returns the launch's error; a missing kernel is an error: any other
+// (depth, cn) is hipErrorInvalidValue. `launch` is a generic lambda:
+//     [&](auto t, auto ch) { kernel<decltype(t), decltype(ch)::value, ...><<<grid, 256, 0, s>>>(...); }
+template <int CN> using Channels = std::integral_constant<int, CN>;
+template <class Launch>
+hipError_t dispatch_depth_cn(int depth, int cn, Launch&& launch) {
+    if (depth == 8 && cn == 3) launch(uint8_t{}, Channels<3>{});
+    else if (depth == 8 && cn == 1) launch(uint8_t{}, Channels<1>{});
+    else if (depth == 8 && cn == 4) launch(uint8_t{}, Channels<4>{});
+    else if (depth == 16 && cn == 3) launch(uint16_t{}, Channels<3>{});
+    else if (depth == 16 && cn == 1) launch(uint16_t{}, Channels<1>{});
+    else if (depth == 16 && cn == 4) launch(uint16_t{}, Channels<4>{});
+    else if (depth == 32 && cn == 3) launch(float{}, Channels<3>{});
+    else if (depth == 32 && cn == 1) launch(float{}, Channels<1>{});
+    else if (depth == 32 && cn == 4) launch(float{}, Channels<4>{});
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 }  // namespace stk

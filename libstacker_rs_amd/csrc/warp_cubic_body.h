@@ -295,19 +295,10 @@ template <int CN> using NoClipN = NoClip;   // the mean fold's state under the l
 template <bool CLIP, template <int> class State>
 hipError_t launch_warp_cubic(const WarpArgs& a, const ClipArgs& c, int depth, dim3 grid, hipStream_t s) {
     if (a.subpixel_bits != 0) return hipErrorInvalidValue;      // cubic is defined on exact coordinates only
-#define STK_CUBIC_CASE(T, CN) warp_accumulate_cubic_kernel<T, CN, CLIP, State<CN>><<<grid, 256, 0, s>>>(a, c)
-    if (depth == 8 && a.cn == 3) STK_CUBIC_CASE(uint8_t, 3);
-    else if (depth == 8 && a.cn == 1) STK_CUBIC_CASE(uint8_t, 1);
-    else if (depth == 8 && a.cn == 4) STK_CUBIC_CASE(uint8_t, 4);
-    else if (depth == 16 && a.cn == 3) STK_CUBIC_CASE(uint16_t, 3);
-    else if (depth == 16 && a.cn == 1) STK_CUBIC_CASE(uint16_t, 1);
-    else if (depth == 16 && a.cn == 4) STK_CUBIC_CASE(uint16_t, 4);
-    else if (depth == 32 && a.cn == 3) STK_CUBIC_CASE(float, 3);
-    else if (depth == 32 && a.cn == 1) STK_CUBIC_CASE(float, 1);
-    else if (depth == 32 && a.cn == 4) STK_CUBIC_CASE(float, 4);
-    else return hipErrorInvalidValue;
-#undef STK_CUBIC_CASE
-    return hipGetLastError();
+    return dispatch_depth_cn(depth, a.cn, [&](auto t, auto ch) {
+        constexpr int CN = decltype(ch)::value;
+        warp_accumulate_cubic_kernel<decltype(t), CN, CLIP, State<CN>><<<grid, 256, 0, s>>>(a, c);
+    });
 }
 
 }  // namespace stk

@@ -13,8 +13,9 @@ MAX_SAMPLES = 4096
 
 
 def launch_class(n):
-    """(ls, G) of launch_quantile_select / launch_quantile_select_masked / launch_robust_select for n samples: a
-    pixel-channel's keys lie on S = 2^ls lanes of one wave, 4G keys per lane; frame i on split i // (4G)."""
+    """(ls, G) of select_plan (select_body.h), through which launch_quantile_select, launch_quantile_select_masked and
+    launch_robust_select all go, for n samples: a pixel-channel's keys lie on S = 2^ls lanes of one wave, 4G keys per lane;
+    frame i on split i // (4G)."""
     groups = (n + 3) // 4
     ls = 0
     while ls < 6 and (groups + (1 << ls) - 1) >> ls > 8:
@@ -26,8 +27,8 @@ def launch_class(n):
 
 CLASSES = [(0, 1), (0, 2), (0, 4), (0, 8), (1, 8), (2, 8), (3, 8), (4, 8), (5, 8), (6, 8), (6, 16)]
 
-# Both ends of every class's range and one n in it that is no multiple of 4. If the dispatch in kernels_quantile.hip or
-# kernels_robust_clip.hip changes, launch_class above has to follow it (test_cpu_selection_classes.py compares the text)
+# Both ends of every class's range and one n in it that is no multiple of 4. If the dispatch in select_plan (select_body.h)
+# changes, launch_class above has to follow it (test_cpu_selection_classes.py compares the text)
 # and check_class_coverage then fails on this list: revisit it, the classes' edges have moved.
 N_LIST = [1, 4, 5, 8, 9, 16, 17, 30, 32, 33, 61, 64, 65, 126, 128, 129, 250, 256,
           257, 507, 512, 513, 1021, 1024, 1025, 2047, 2048, 2049, 4095, 4096]

@@ -16,17 +16,24 @@ CSRC = Path(__file__).resolve().parent.parent / "libstacker_rs_amd" / "csrc"
 
 # ---- 1. the dispatch and the class coverage ---------------------------------------------------------------------------
 def test_launch_class_is_the_launchers_dispatch():
-    """The three launchers hold the same four lines; launch_class restates them. A change of the dispatch fails here first:
-    follow it in launch_class, then check_class_coverage says what N_LIST no longer hits."""
+    """select_plan (select_body.h) holds the four lines, once, and no other file under csrc/ holds them or computes a G or a
+    group count of its own: the three launchers all go through it. launch_class restates them. A change of the dispatch
+    fails here first: follow it in launch_class, then check_class_coverage says what N_LIST no longer hits."""
     lines = ["const int groups = (n + 3) / 4;",
              "while (ls < 6 && (groups + (1 << ls) - 1) >> ls > 8) ls++;",
              "const int per = (groups + (1 << ls) - 1) >> ls;",
              "const int G = per <= 1 ? 1 : per <= 2 ? 2 : per <= 4 ? 4 : per <= 8 ? 8 : 16;"]
-    for name, launchers in (("kernels_quantile.hip", 2), ("kernels_robust_clip.hip", 1)):
-        text = (CSRC / name).read_text()
+    files = sorted(p for p in CSRC.iterdir() if p.is_file())
+    assert CSRC / "select_body.h" in files and CSRC / "kernels_quantile.hip" in files and CSRC / "kernels_robust_clip.hip" in files
+    for path in files:
+        text = path.read_text(errors="replace")
+        once = 1 if path.name == "select_body.h" else 0
         for line in lines:
-            assert text.count(line) == launchers, (name, line)
-        assert len(re.findall(r"const int groups\b", text)) == launchers and len(re.findall(r"const int G\b", text)) == launchers
+            assert text.count(line) == once, (path.name, line)
+        if path.suffix in (".hip", ".h"):                # (stacker.cpp has an ECC variable named groups)
+            assert len(re.findall(r"const int groups\b", text)) == once and len(re.findall(r"const int G\b", text)) == once, path.name
+    for name in ("kernels_quantile.hip", "kernels_robust_clip.hip"):
+        assert "select_plan(m, n)" in (CSRC / name).read_text()
     assert "constexpr int QUANTILE_MAX_SAMPLES = 4096;" in (CSRC / "common.h").read_text()
     assert sc.MAX_SAMPLES == 4096
 

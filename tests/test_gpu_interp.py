@@ -272,27 +272,27 @@ def test_seven_frame_folds_u8_equal_float_and_padded_equals_tight(st, shape):
 
 
 # ---- 6. every combine sees the cubic sample ------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind", KINDS[:2], ids=KIND_IDS[:2])
-def test_every_combine_sees_the_cubic_sample(st, kind):
+def _every_combine(st, kind, shape, n, affine, interp, reach, steps, seed):
+    """Every combine built on the fold with a u8 BGR fast state (the clip, the weighted mean, the moments, the two quantile
+    stores; with and without normalisation) under `interp`, each against its restatement on the engine's own samples."""
     dtype, cn, border, bv = kind
-    h, w = SHAPES[0]
-    rng = np.random.default_rng(zlib.crc32(str(kind).encode()))
-    n = 7
+    h, w = shape
+    rng = np.random.default_rng(zlib.crc32(seed.encode()))
     frames = random_frames(rng, n, h, w, cn, dtype)
-    warps = shifted_warps(rng, n, False, reach=6.0)
+    warps = shifted_warps(rng, n, affine, reach=reach)
     idx = list(range(n))
     g = rng.uniform(0.5, 2.0, (n, cn)).astype(F)
     o = rng.uniform(-0.1, 0.1, (n, cn)).astype(F)
     wt = rng.uniform(0.1, 2.0, n).astype(F)
     wt[2] = 0.0
-    kw = dict(border_mode=border, border_value=bv, alpha=ALPHA[dtype])
+    kw = dict(is_affine=affine, border_mode=border, border_value=bv, alpha=ALPHA[dtype])
     clip = SigmaClipParameters(2.0, 2.5, 2)
     # kappa is the linear fold's by definition (a cubic sample of an all-ones frame need not round to 1.0f)
-    kappa = engine_kappa(st, (h, w), warps, idx, False)
+    kappa = engine_kappa(st, (h, w), warps, idx, affine)
     linear_samples = engine_samples(st, frames, warps, idx, **kw)
     covs = (False, True) if border == BORDER_CONSTANT else (False,)
     got = {}
-    with cubic(st):
+    with (cubic(st) if interp == INTER_CUBIC else contextlib.nullcontext()):
         samples = engine_samples(st, frames, warps, idx, **kw)
         got["clip"] = st.clip_stack(frames, warps, clip, return_counts=True, **kw)
         for q in (0.5, 0.9):
@@ -302,11 +302,11 @@ def test_every_combine_sees_the_cubic_sample(st, kind):
             got["cw", cov] = st.clip_stack_weighted(frames, warps, clip, g, o, wt, coverage=cov, return_counts=True,
                                                     return_kept_weight=True, **kw)
             got["qw", cov] = st.quantile_stack_weighted(frames, warps, 0.5, g, o, wt, coverage=cov, return_counts=True, **kw)
-        for step in (1, 3):
+        for step in steps:
             got["m", step] = st.overlap_moments(frames, warps, stat_step=step, **kw)
     full = kappa == F(1.0)
     assert (~full).mean() >= 0.03, (~full).mean()            # the rim is a real share of the (pixel, entry) pairs
-    assert not np.array_equal(samples, linear_samples)
+    assert np.array_equal(samples, linear_samples) == (interp == INTER_LINEAR)
     ref, ref_k = clip_restate(samples, clip.kappa_low, clip.kappa_high, clip.iterations)
     assert np.array_equal(got["clip"][0], ref, equal_nan=True) and np.array_equal(got["clip"][1], ref_k)
     for q in (0.5, 0.9):
@@ -321,7 +321,7 @@ def test_every_combine_sees_the_cubic_sample(st, kind):
         qref, qn = robust_quantile_restate(samples, part, g, o, wt, 0.5)
         assert np.array_equal(got["qw", cov][1], qn) and np.array_equal(got["qw", cov][0], qref, equal_nan=True), cov
     u = 2.0 ** -53
-    for step in (1, 3):
+    for step in steps:
         exact, mag = _exact_moments(samples, kappa, step)
         mom = got["m", step]
         for i in range(1, n):
@@ -330,6 +330,23 @@ def test_every_combine_sees_the_cubic_sample(st, kind):
             gamma = (cnt - 1) * u / (1 - (cnt - 1) * u) if cnt > 1 else 0.0
             assert (np.abs(mom[i] - exact[i]) <= gamma * mag[i]).all(), (step, i)
         assert any(exact[i, 0, 0] > 50 for i in range(1, n))
+
+
+@pytest.mark.parametrize("kind", KINDS[:2], ids=KIND_IDS[:2])
+def test_every_combine_sees_the_cubic_sample(st, kind):
+    _every_combine(st, kind, SHAPES[0], 7, False, INTER_CUBIC, 6.0, (1, 3), str(kind))
+
+
+# Which kernel a combine runs is decided by one launcher (fold_launch.h) and one (depth, cn) ladder: every cell of
+# depth x channels x interpolation x motion model, for all six combines at once. 70 x 6: the 64-wide and the 4-row tile both
+# have a ragged second tile; 5 frames: a clip still has k >= 3 after one rejection. (DESIGN.md 4.19 has the table.)
+@pytest.mark.parametrize("interp", [INTER_LINEAR, INTER_CUBIC], ids=["linear", "cubic"])
+@pytest.mark.parametrize("affine", [True, False], ids=["affine", "persp"])
+@pytest.mark.parametrize("cn", [1, 3, 4])
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.float32], ids=["u8", "u16", "f32"])
+def test_every_combine_at_every_launcher_cell(st, dtype, cn, affine, interp):
+    kind = (dtype, cn, BORDER_CONSTANT, (0, 0, 0, 0))
+    _every_combine(st, kind, (6, 70), 5, affine, interp, 2.0, (1, 2), f"cell {np.dtype(dtype).name} {cn} {affine} {interp}")
 
 
 # ---- 7. whole-stack calls equal their parts ----------------------------------------------------------------------------

@@ -112,13 +112,12 @@ def engine_omega(st, maps, warps, idx, is_affine):
                                                    border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0))[..., 0] for i in idx])
 
 
-def _fold_case(st, case, interp):
+def _fold_case(st, case, interp, n=9, reach=6.0):
     import torch
     dtype, cn, affine, border, _, sub, _, _, (h, w) = case
     rng = np.random.default_rng(zlib.crc32(("local" + str(case)).encode()))
-    n = 9
     frames = random_frames(rng, n, h, w, cn, dtype)
-    warps = shifted_warps(rng, n, affine)
+    warps = shifted_warps(rng, n, affine, reach=reach)
     include = [1] * n
     include[4] = 0
     idx = [i for i in range(n) if include[i]]
@@ -173,6 +172,17 @@ def test_local_weighted_stack_cubic_samples_linear_weights(st):
     case = CASES[0]
     assert case[5] == 0                     # cubic is defined on exact coordinates only
     _fold_case(st, case, 2)
+
+
+# launch_local_fold at every cell of depth x channels x interpolation x motion model (the one (depth, cn) ladder decides the
+# kernel). 70 x 6: the 64-wide and the 4-row tile both have a ragged second tile; 5 frames, 4 of them included, shifts of up to 2 px so
+# that every frame keeps rows inside.
+@pytest.mark.parametrize("interp", [1, 2], ids=["linear", "cubic"])
+@pytest.mark.parametrize("affine", [True, False], ids=["affine", "persp"])
+@pytest.mark.parametrize("cn", [1, 3, 4])
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.float32], ids=["u8", "u16", "f32"])
+def test_local_weighted_stack_at_every_launcher_cell(st, dtype, cn, affine, interp):
+    _fold_case(st, (dtype, cn, affine, BORDER_CONSTANT, None, 0, None, None, (6, 70)), interp, n=5, reach=2.0)
 
 
 def test_null_records_mean_unit_records(st):

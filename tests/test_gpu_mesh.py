@@ -204,6 +204,9 @@ def _fold_inputs(seed, n, h, w, cn, dtype, affine, step):
 FOLD_CASES = [(np.uint8, 3, False, 16, (45, 70)), (np.uint8, 1, True, 8, (33, 65)), (np.uint8, 4, False, 32, (37, 70)),
               (np.uint16, 3, True, 16, (45, 70)), (np.uint16, 1, False, 32, (33, 65)), (np.uint16, 4, True, 8, (20, 70)),
               (np.float32, 3, False, 8, (45, 70)), (np.float32, 1, True, 16, (17, 33)), (np.float32, 4, False, 16, (33, 65))]
+# the other motion model of each (depth, channels): with the nine above, every cell launch_mesh_fold's ladder has. 70 x 6: the
+# 64-wide and the 4-row tile both have a ragged second tile
+FOLD_CASES += [(c[0], c[1], not c[2], 8, (6, 70)) for c in FOLD_CASES]
 _FOLD_IDS = [f"{np.dtype(c[0]).name}c{c[1]}-{'aff' if c[2] else 'persp'}-s{c[3]}-{c[4][0]}x{c[4][1]}" for c in FOLD_CASES]
 
 
