@@ -214,16 +214,18 @@ def test_lds_ring_run_time_check_falls_back_to_the_gather_loop(stacker):
 
 
 def test_lds_ring_against_gather_on_random_start_warps(stacker):
-    """The ring route decides per column strip whether its source footprint fits (window of 76 columns, lanes at most 2.5
+    """The ring route decides per column strip whether its source footprint fits (window of 85 columns, end lanes at most 0.9
     rows apart, source row rising by 0.6 .. 1.4 per template row, corners with w >= 1/4) and falls back to the gather loop
     otherwise. Random start homographies — rotations up to 8 degrees, scale 0.8 .. 1.25, perspective, shifts — put strips on
-    every side of those limits; two fixed iterations from each start must give the same bits by both routes."""
+    every side of those limits; two fixed iterations from each start must give the same bits by both routes. At least one
+    start must put strips into the ring at all: under ecc_ring_lookahead = 1 every ring strip fails the run-time check at its
+    first step, so the fall-back counter is then the number of strips that took the ring."""
     rng = np.random.default_rng(7)
     frames, _ = synth.make_stack(2, 1280, 960)
     g0, g1 = oracle.grey(frames.numpy()[0]), oracle.grey(frames.numpy()[1])
     p2 = EccMatchParameters(MotionType.Homography, 2, None, 5)
     w, h = 1280, 960
-    n_checked = 0
+    n_checked = n_ring_strips = 0
     for k in range(24):
         th = np.radians(rng.uniform(-8, 8)) * (k % 3 != 0)
         sc = rng.uniform(0.8, 1.25) if k % 2 else rng.uniform(0.97, 1.03)
@@ -247,7 +249,16 @@ def test_lds_ring_against_gather_on_random_start_warps(stacker):
             continue
         n_checked += 1
         assert np.array_equal(outs[0][0], outs[1][0]) and outs[0][1] == outs[1][1] and outs[0][2] == outs[1][2], k
+        if n_ring_strips == 0:
+            stacker.set_option("ecc_ring_lookahead", 1)
+            try:
+                again = stacker.find_transform_ecc(g0, g1, W0.copy(), p2)
+                n_ring_strips += stacker.timing()["ecc_ring_fallbacks"]
+            finally:
+                stacker.set_option("ecc_ring_lookahead", 5)
+            assert np.array_equal(again[0], outs[1][0]) and again[1] == outs[1][1] and again[2] == outs[1][2], k
     assert n_checked >= 12
+    assert n_ring_strips > 0, "no start put a strip into the ring: the comparison above compared the gather route with itself"
 
 
 def test_frames_entering_idle_slots_do_not_change_results(stacker):
