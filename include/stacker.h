@@ -206,7 +206,9 @@ stk_status  stk_get_timing(const stk_ctx* ctx, stk_timing* out);
  *                           "ecc_first_iter"): one per frame that starts at the identity; 0 with the option off, for the
  *                           other motion types, under "ecc_variant" 0 and for f32 images.
  *   "robust_select_us"      median / MAD clip (stk_robust_clip_stack and the *_robust_clipped calls): device time of the
- *                           last such call's selection launches in microseconds, part of its stk_timing.finalize_ms. */
+ *                           last such call's selection launches in microseconds, part of its stk_timing.finalize_ms.
+ *   "prep_stream_frames"    test hook: ECC templates of the last call that the streaming grey + blur kernel wrote (one launch
+ *                           per run of frames, option "prep_stream"); the others took the per-frame kernels. */
 stk_status  stk_get_counter(const stk_ctx* ctx, const char* name, int64_t* out);
 /* Pinned (page-locked) host memory for frames: stacks handed over in such buffers cross PCIe by DMA at link rate and
  * overlap with the alignment of the frames that have already arrived (a decoder — the Rust shim's imread — writes into
@@ -1245,6 +1247,21 @@ stk_status stk_find_transform_ecc(stk_ctx* ctx, const void* templ, const void* i
                                   int32_t depth, int32_t width, int32_t height, int32_t location,
                                   const stk_ecc_params* params, float* warp, double* rho,
                                   int32_t* iterations);
+/* Test hooks: what the last ECC preparation on this context left for the iteration kernels. Neither changes what a call
+ * launches. Usable after any stk_ecc_match* / stk_hybrid_match* / stk_find_transform_ecc call that got as far as its
+ * iterations, whether or not a frame's ECC then failed (the iteration kernels only read these buffers); on a context that
+ * has prepared nothing both return STK_INVALID_PARAMS. A multi-device context answers for its first device's shard.
+ * stk_ecc_prepared_geometry: size of the planes ECC ran on (the scaled-down size under scale_down_width), the number of
+ * moving-frame templates and the width of the zero border around the frame-0 planes.
+ * stk_ecc_prepared: drains the context's streams and copies one plane to host memory, tightly packed:
+ *   what = STK_PREP_TEMPLATE   template `index` (moving frame index + 1): height x width floats
+ *   what = STK_PREP_I / STK_PREP_GX / STK_PREP_GY   blurred frame 0 and its central-difference gradients, WITH the zero
+ *          border: (height + 2 pad) x (width + 2 pad) floats
+ *   what = STK_PREP_GXY / STK_PREP_IGG   the interleaved (gx, gy) and (I, gx, gy) copies, with the border: 2 and 3 floats per pixel
+ * (`index` is ignored for the frame-0 planes.) capacity_floats below the plane's size: STK_INVALID_PARAMS. */
+enum { STK_PREP_TEMPLATE = 0, STK_PREP_I = 1, STK_PREP_GX = 2, STK_PREP_GY = 3, STK_PREP_GXY = 4, STK_PREP_IGG = 5 };
+stk_status stk_ecc_prepared_geometry(const stk_ctx* ctx, int32_t* width, int32_t* height, int32_t* n_templates, int32_t* pad);
+stk_status stk_ecc_prepared(stk_ctx* ctx, int32_t what, int32_t index, float* out_host, size_t capacity_floats);
 /* imgproc::warp_perspective / warp_affine (INTER_LINEAR, no WARP_INVERSE_MAP: M is inverted)
  * of convert(frame, 1/255)  fused with  acc += warped   (lib.rs:290-316, 780-814).
  * M: 9 doubles row-major (affine: last row 0 0 1). acc: device or host f32 w*h*c.

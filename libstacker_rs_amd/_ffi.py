@@ -279,6 +279,9 @@ SIGNATURES = {
     "stk_find_transform_ecc": (c_status, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.POINTER(EccParams), C.c_void_p, C.POINTER(C.c_double),
                                           C.POINTER(C.c_int32)]),
+    "stk_ecc_prepared_geometry": (c_status, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32)]),
+    "stk_ecc_prepared": (c_status, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),
     "stk_warp_accumulate": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_double, C.c_int32, C.POINTER(ImageF32)]),
     "stk_scale_image_grey": (c_status, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,

@@ -497,7 +497,7 @@ class Stacker:
         t = _ffi.Timing()
         self._check(self._lib.stk_get_timing(self._h, C.byref(t)))
         d = {k: getattr(t, k) for k, _ in _ffi.Timing._fields_}
-        for name in ("ecc_first_iter_slots", "robust_select_us"):              # counters outside stk_timing (stk_get_counter)
+        for name in ("ecc_first_iter_slots", "robust_select_us", "prep_stream_frames"):   # counters outside stk_timing (stk_get_counter)
             v = C.c_int64(0)
             self._check(self._lib.stk_get_counter(self._h, name.encode(), C.byref(v)))
             d[name] = v.value
@@ -1882,6 +1882,26 @@ class Stacker:
                                               C.c_void_p(wm.ctypes.data), C.byref(rho), C.byref(its))
         self._check(st)
         return wm, rho.value, its.value
+
+    def ecc_prepared(self) -> dict:
+        """Test hook (stk_ecc_prepared): the planes the last ECC preparation on this context left for the iteration kernels,
+        as host arrays: "templates" [n, h, w]; "I", "gx", "gy" [h + 2 pad, w + 2 pad] and the interleaved "gxy" [.., 2] and
+        "igg" [.., 3], all with their zero border; "pad" its width."""
+        w, h, n, pad = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        st = self._lib.stk_ecc_prepared_geometry(self._h, C.byref(w), C.byref(h), C.byref(n), C.byref(pad))
+        if st != 0:
+            raise InvalidParams("no ECC preparation has run on this context")
+        w, h, n, pad = w.value, h.value, n.value, pad.value
+
+        def fetch(what, index, shape):
+            a = np.empty(shape, np.float32)
+            self._check(self._lib.stk_ecc_prepared(self._h, what, index, C.c_void_p(a.ctypes.data), a.size))
+            return a
+        out = {"templates": np.stack([fetch(0, i, (h, w)) for i in range(n)]) if n else np.empty((0, h, w), np.float32), "pad": pad}
+        hp, wp = h + 2 * pad, w + 2 * pad
+        for what, (name, k) in enumerate((("I", 1), ("gx", 1), ("gy", 1), ("gxy", 2), ("igg", 3)), start=1):
+            out[name] = fetch(what, 0, (hp, wp) if k == 1 else (hp, wp, k))
+        return out
 
     def warp_accumulate(self, frame, M, *, is_affine=False, border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0),
                         alpha=1.0 / 255.0, acc=None):

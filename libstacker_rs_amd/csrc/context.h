@@ -82,6 +82,14 @@ struct stk_ctx {
     int* host_done = nullptr;     // pinned, 16 ints: [0], [1] completion counters of the two chunks in flight, [2] ring fall-back count, [3] first-iteration slots
     const void* ref_zeroed_ptr = nullptr;   // the frame-0 planes' zero border exists for this buffer and geometry (ecc_prepare_reference)
     int ref_zeroed_w = 0, ref_zeroed_h = 0;
+    // test hooks (stk_ecc_prepared, stk_get_counter "prep_stream_frames"): the geometry of the last ECC preparation, as
+    // ecc_plan laid it out in ctx->templates / ctx->ref, and how many of its templates the streaming kernel wrote
+    struct EccPrepared {
+        bool valid = false;
+        int w = 0, h = 0, n_templates = 0, templ_row_stride = 0, ref_stride = 0;
+        size_t templ_plane_stride = 0, ref_plane_floats = 0;
+    } ecc_prepared;
+    int64_t prep_stream_frames = 0;     // (reset by timing_begin)
     std::vector<hipEvent_t> prof_ev;   // event pairs for per-launch timing (option profile = 2)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> fold_ev;   // event pairs around the keypoint path's fold launches (grow-only pool)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> select_ev; // event pairs around the median / MAD clip's selection launches, one per band (grow-only pool)

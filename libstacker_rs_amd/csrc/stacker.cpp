@@ -147,6 +147,7 @@ stk_status stk_get_counter(const stk_ctx* ctx, const char* name, int64_t* out) {
     if (!ctx || !name || !out) return STK_INVALID_PARAMS;
     if (std::string(name) == "ecc_first_iter_slots") { *out = ctx->ecc_first_iter_slots; return STK_OK; }
     if (std::string(name) == "robust_select_us") { *out = ctx->robust_select_us; return STK_OK; }
+    if (std::string(name) == "prep_stream_frames") { *out = ctx->prep_stream_frames; return STK_OK; }
     return STK_INVALID_PARAMS;
 }
 
@@ -561,7 +562,15 @@ size_t image_stride_floats(const stk_image_f32* im) {
     return im->row_stride_bytes ? im->row_stride_bytes / 4 : (size_t)im->width * im->channels;
 }
 
-void timing_begin(stk_ctx* ctx) { std::memset(&ctx->timing, 0, sizeof(ctx->timing)); ctx->ecc_first_iter_slots = 0; }
+void timing_begin(stk_ctx* ctx) { std::memset(&ctx->timing, 0, sizeof(ctx->timing)); ctx->ecc_first_iter_slots = 0; ctx->prep_stream_frames = 0; }
+
+// test hook (stk_ecc_prepared): where the preparation of this call puts its planes
+static void ecc_remember_plan(stk_ctx* ctx, const EccPlan& pl) {
+    ctx->ecc_prepared.valid = true;
+    ctx->ecc_prepared.w = pl.w; ctx->ecc_prepared.h = pl.h; ctx->ecc_prepared.n_templates = pl.n_templates;
+    ctx->ecc_prepared.templ_row_stride = pl.templ_row_stride; ctx->ecc_prepared.templ_plane_stride = pl.templ_plane_stride;
+    ctx->ecc_prepared.ref_stride = pl.ref_stride; ctx->ecc_prepared.ref_plane_floats = pl.ref_plane_floats;
+}
 
 // ecc_match on a shard. `seeds` (n x 9 f32, row-major, h22 == 1; entry 0 unused) replaces the identity as the initial
 // warp of every moving frame; `alpha` is the convertTo scale of the fold; `allow16` admits 16-bit frames (ECC then runs on
@@ -615,6 +624,7 @@ stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_
     auto bail = [&](stk_status e) { (void)up.finish(nullptr); return e; };      // never leave the helper thread behind
     EccPlan pl{};
     if ((st = ecc_plan(ctx, ew, eh, n - 1, params->motion_type, pl))) return bail(st);
+    ecc_remember_plan(ctx, pl);
     // (scaled: the grey image and its INTER_AREA reduction keep the frames' depth, 8-bit or f32, as cvtColor and resize do)
     const int gdepth = frames->depth;
     const size_t gel = (size_t)gdepth / 8;
@@ -641,7 +651,7 @@ stk_status ecc_shard_impl(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_
             const hipError_t e = launch_grey_blur_batch(nullptr, dev[first], (size_t)step, count, frames->depth, w, h, rb, params->gauss_filt_size,
                                                         ctx->templates.as<float>() + pl.templ_plane_stride * (size_t)(first - 1), pl.templ_row_stride,
                                                         pl.templ_plane_stride, s);
-            if (e == hipSuccess) return STK_OK;
+            if (e == hipSuccess) { ctx->prep_stream_frames += count; return STK_OK; }
             if (e != hipErrorNotSupported) return fail(ctx, STK_HIP_ERROR, std::string("grey_blur batch: ") + hipGetErrorString(e));
         }
         for (int k = 0; k < count; k++) { const stk_status ps = prepare_template(first + k, s); if (ps) return ps; }
@@ -1015,6 +1025,7 @@ stk_status stk_find_transform_ecc(stk_ctx* ctx, const void* templ, const void* i
     if (guard.saved != 0 && params->motion_type == STK_MOTION_HOMOGRAPHY && warp[8] != 1.0f) ctx->opt_ecc_variant = 0;
     st = ecc_plan(ctx, width, height, 1, params->motion_type, pl);
     if (st) return st;
+    ecc_remember_plan(ctx, pl);
     const size_t rb = (size_t)width * (depth / 8);
     if ((st = ecc_prepare_reference(ctx, pl, in, depth, 1, rb, params->gauss_filt_size))) return st;
     HIP_TRY(launch_grey_blur(t, depth, 1, width, height, rb, params->gauss_filt_size, ctx->templates.as<float>(), pl.templ_row_stride, ctx->stream));
@@ -1031,6 +1042,50 @@ stk_status stk_find_transform_ecc(stk_ctx* ctx, const void* templ, const void* i
     if (rho) *rho = res[0].rho;
     if (iterations) *iterations = res[0].iters;
     if (res[0].status) return fail(ctx, STK_BACKEND_ERROR, ecc_status_message(res[0].status));
+    return STK_OK;
+}
+
+// ---- test hooks: the planes the last ECC preparation left for the iteration kernels ------------------------------------
+stk_status stk_ecc_prepared_geometry(const stk_ctx* ctx, int32_t* width, int32_t* height, int32_t* n_templates, int32_t* pad) {
+    if (!ctx || !ctx->ecc_prepared.valid) return STK_INVALID_PARAMS;
+    if (width) *width = ctx->ecc_prepared.w;
+    if (height) *height = ctx->ecc_prepared.h;
+    if (n_templates) *n_templates = ctx->ecc_prepared.n_templates;
+    if (pad) *pad = REF_PAD;
+    return STK_OK;
+}
+
+stk_status stk_ecc_prepared(stk_ctx* ctx, int32_t what, int32_t index, float* out_host, size_t capacity_floats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    const auto& g = ctx->ecc_prepared;
+    if (!g.valid) return fail(ctx, STK_INVALID_PARAMS, "no ECC preparation has run on this context");
+    if (!out_host) return fail(ctx, STK_INVALID_PARAMS, "null output");
+    (void)hipSetDevice(ctx->device);
+    for (hipStream_t s : {ctx->copy_stream, ctx->prep_stream, ctx->ecc_stream2, ctx->stream}) HIP_TRY(hipStreamSynchronize(s));
+    const float* src; size_t pitch_floats, row_floats; int rows;
+    if (what == STK_PREP_TEMPLATE) {
+        if (index < 0 || index >= g.n_templates) return fail(ctx, STK_INVALID_PARAMS, "template index out of range");
+        src = ctx->templates.as<float>() + g.templ_plane_stride * (size_t)index;
+        pitch_floats = (size_t)g.templ_row_stride; row_floats = (size_t)g.w; rows = g.h;
+    } else {
+        // plane offsets as ecc_prepare_reference / ecc_run lay them out: I, gx, gy one float per pixel at planes 0, 1, 2;
+        // (gx, gy) two floats per pixel from plane 3; (I, gx, gy) three floats per pixel from plane 5
+        size_t first_plane, per_px;
+        switch (what) {
+            case STK_PREP_I: first_plane = 0; per_px = 1; break;
+            case STK_PREP_GX: first_plane = 1; per_px = 1; break;
+            case STK_PREP_GY: first_plane = 2; per_px = 1; break;
+            case STK_PREP_GXY: first_plane = 3; per_px = 2; break;
+            case STK_PREP_IGG: first_plane = 5; per_px = 3; break;
+            default: return fail(ctx, STK_INVALID_PARAMS, "unknown plane");
+        }
+        src = ctx->ref.as<float>() + first_plane * g.ref_plane_floats;
+        pitch_floats = (size_t)g.ref_stride * per_px; row_floats = (size_t)(g.w + 2 * REF_PAD) * per_px; rows = g.h + 2 * REF_PAD;
+    }
+    if (capacity_floats < row_floats * (size_t)rows) return fail(ctx, STK_INVALID_PARAMS, "output too small for the plane");
+    HIP_TRY(hipMemcpy2DAsync(out_host, row_floats * sizeof(float), src, pitch_floats * sizeof(float), row_floats * sizeof(float), (size_t)rows,
+                             hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return STK_OK;
 }
 

@@ -397,6 +397,7 @@ def test_streaming_grey_blur_is_bit_identical_to_the_tiled_kernel(stacker, depth
             a, sa = run()
         except Exception as e:                      # a sliver this small may not correlate: both paths must then fail alike
             a, sa = None, repr(type(e))
+        assert stacker.timing()["prep_stream_frames"] == len(fr) - 1      # the streaming kernel did write every template ...
         stacker.set_option("prep_stream", 0)
         try:
             try:
@@ -405,6 +406,7 @@ def test_streaming_grey_blur_is_bit_identical_to_the_tiled_kernel(stacker, depth
                 b, sb = None, repr(type(e))
         finally:
             stacker.set_option("prep_stream", 1)
+        assert stacker.timing()["prep_stream_frames"] == 0                # ... and none of them with the option off
         if a is None or b is None:
             assert a is None and b is None and sa == sb
             continue
