@@ -1129,6 +1129,106 @@ stk_status stk_keypoint_match_robust_clipped_weighted(stk_ctx* ctx, const stk_fr
                                                       float* kept_weight_or_null, stk_frame_weight* applied_or_null,
                                                       stk_frame_stats* stats_or_null);
 
+/* ---- local normalisation: per-frame gain and offset fields on a node grid: an EXTENSION beyond the reference --------
+ * The weighted combine and the participation quantile map each frame onto frame 0's level with ONE gain and offset per
+ * frame and channel. A sky gradient that turns over a session, thin cloud over one corner or vignetting under a dither
+ * differ from frame 0 by a smooth field, not by a constant. This section estimates, per frame, a gain and an offset on
+ * the node grid of the mesh section and folds through their bilinear interpolation, as the mesh fold does for geometry.
+ * w x h is the destination size (frame 0's), cn the channel count. Samples s_i,c, fold order, alpha, warp, border
+ * handling, warp_subpixel_bits and the coverage weight kappa_i are the weighted combine's.
+ * Grids. Nodes are those of stk_mesh_grid(w, h, step): gw x gh, node (j, k) at destination pixel (k step, j step), step a
+ *   power of two in 8 .. 256. Cells: cw = (w + step - 1) / step by ch likewise; cell (J, K) covers x in [K step,
+ *   min((K + 1) step, w)) and y likewise.
+ * Cell moments. For entry i >= 1, cell (J, K) and channel c: the destination pixels of the cell with x % stat_step == 0,
+ *   y % stat_step == 0 and kappa_i == 1.0f, kappa_i being the BORDER_CONSTANT one whatever the fold's border mode, exactly
+ *   as in stk_overlap_moments. X = (double)s_i,c, Y = (double)s_0,c; the samples are always the LINEAR fold's, also under
+ *   STK_INTER_CUBIC (these are statistics, not an image). The six f64 values per channel are n, sum X, sum Y, sum X^2,
+ *   sum Y^2, sum XY; products are formed in f64, so every term is exact. The order of the additions is fixed by the
+ *   geometry, step and stat_step alone (one wave per cell and entry: a lane's pixels in row-major order, then a
+ *   xor-shuffle tree; no atomics): the same bits on every call and under every option. A cell without a stepped pixel has
+ *   n = 0.
+ * Node moments of node (j, k): the sum of the existing cells among (j-1, k-1), (j-1, k), (j, k-1), (j, k), in that order,
+ *   in f64: the 2 step square around the node; windows overlap by half.
+ * Global moments of a frame: the sum of all its cells in row-major order, in f64. Not promised to be bit-equal to
+ *   stk_overlap_moments (the order differs); n is equal.
+ * Estimator, on the host in f64, results rounded to f32: per node and channel the weighted combine's formulas for
+ *   normalize 0 .. 3 on the node moments. A (node, channel) is invalid if n < min_count, if the formula falls back (a
+ *   denominator <= 0 or a non-finite result), or if the gain lies outside [0.25, 4].
+ * Fill. `fill` Jacobi passes per channel on the pair (g_c, o_c): the arithmetic of the mesh section's "Fill" (k = [1 2 1]^T
+ *   [1 2 1], in-grid neighbours in row-major order, f32, den = den + k, num = num + k value, value = num / den) with the
+ *   channel's validity as m. A (node, channel) still invalid afterwards takes the frame's global (g_c, o_c), the same
+ *   formulas on the global moments (no count or range test); where that falls back it is (1, 0). The global record
+ *   (stk_frame_weight: gains, offsets, weight 1; bit c of flags set iff the global formula of channel c fell back) is
+ *   returned beside the plane.
+ * Plane: gh x gw x 2 cn f32, tightly packed, per node g_0 .. g_{cn-1}, o_0 .. o_{cn-1}. Planes are small and always HOST
+ *   memory, whatever the frames' location. Frame 0 and excluded frames have no plane.
+ * Locally normalised fold. Destination pixel (x, y): k = x / step, j = y / step, k1 = min(k + 1, gw - 1), j1 = min(j + 1,
+ *   gh - 1); u = (float)(x - k step) * (1.0f / step), v likewise (both exact). For entry i with plane P and each of the 2 cn
+ *   components q, the mesh fold's chain: t0 = fma(u, P[j][k1][q] - P[j][k][q], P[j][k][q]), t1 the same on row j1, value =
+ *   fma(v, t1 - t0, t0): G_c = value of q = c, O_c = value of q = cn + c. An entry with a NULL plane uses its record's gain
+ *   and offset as constants. Then, as in the weighted combine, v_c = s_i,c * G_c + O_c * kappa_i; num_c = num_c + w_i * v_c;
+ *   den = den + w_i * kappa_i; out_c = den > 0 ? num_c / den : 0. For an entry with a plane w_i comes from the record and
+ *   the record's gain and offset are ignored. NULL records mean unit records. coverage as in stk_weighted_stack.
+ * Locally normalised quantile: the participation quantile of the section above with u = s * G_c + O_c.
+ * Consequences. With every plane NULL, or every plane constant and equal to its record, the results are
+ *   stk_weighted_stack's and stk_quantile_stack_weighted's bit for bit (fma(u, 0, g) = g). warp_subpixel_bits = 5 and
+ *   STK_INTER_CUBIC are served (generic kernels, as the local-weighted fold). A multi-device context runs these calls on
+ *   its first device. Plane values are expected finite and are not checked. */
+typedef struct {
+    int32_t step;        /* node spacing: 8 .. 256, a power of two */
+    int32_t stat_step;   /* 1 .. 64; 0 = 4 */
+    int32_t normalize;   /* 0 NONE .. 3 LINEAR, as stk_weight_params */
+    int32_t coverage;    /* as stk_weight_params */
+    int32_t min_count;   /* pixels a node's window needs: >= 1; 0 = 16 */
+    int32_t fill;        /* 0 .. 16 */
+    int32_t reserved[2]; /* 0 */
+} stk_local_norm_params;
+
+/* The cell moments alone of every included frame i >= 1 against frame 0, which must be included. Arguments as
+ * stk_overlap_moments; step: the node spacing; stat_step: 1 .. 64. moments: n x (ch cw) x channels x 6 doubles on the host,
+ * frame index order, cells in row-major order; frame 0 and excluded frames: zeros. stk_timing.finalize_ms is the pass. */
+stk_status stk_local_moments(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                             int32_t is_affine, int32_t border_mode, const double* border_value, double alpha, int32_t step,
+                             int32_t stat_step, double* moments);
+/* Estimator and fill for one frame: pure host code, no context (a bad argument is STK_INVALID_PARAMS without a message).
+ * cell_moments_of_one_frame: (ch cw) x channels x 6 doubles; plane: gh x gw x 2 channels f32; global_or_null: the global
+ * record; valid_or_null: gh x gw int32, bit c = (node, channel c) was valid BEFORE the fill. params->coverage is not read. */
+stk_status stk_local_norm_estimate(int32_t width, int32_t height, int32_t channels, const stk_local_norm_params* params,
+                                   const double* cell_moments_of_one_frame, float* plane, stk_frame_weight* global_or_null,
+                                   int32_t* valid_or_null);
+/* The locally normalised mean alone over caller-held warps: stk_weighted_stack's arguments with per_frame_or_null, then
+ * norm_or_null: n host planes by frame index for the grid of `step` (an entry, or the array, may be NULL: no plane). */
+stk_status stk_local_norm_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                const stk_frame_weight* per_frame_or_null, const float* const* norm_or_null, int32_t step,
+                                int32_t coverage, stk_image_f32* out, float* den_or_null);
+/* The locally normalised quantile alone: stk_quantile_stack_weighted's arguments with per_frame_or_null, then the planes. */
+stk_status stk_quantile_stack_local_norm(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                         int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                         const stk_quantile_params* quantile, const stk_frame_weight* per_frame_or_null,
+                                         const float* const* norm_or_null, int32_t step, int32_t coverage, stk_image_f32* out,
+                                         int32_t* counts_or_null);
+/* The whole-stack forms: the plain call (its stats, warps, `dropped` and errors), the cell moments on the stats' warps over
+ * the resident frames, the estimator, then the mean (quantile_or_null == NULL) or the quantile through the planes; by
+ * definition the result of those parts, bit for bit. The records are units with weights_or_null's weights (NULL = all 1).
+ * den_or_null (w x h f32, the mean only) and counts_or_null (w x h int32, the quantile only) are in the location of `out`;
+ * the one that does not belong to the chosen combine must be NULL (STK_INVALID_PARAMS). norm_out_or_null: n host planes by
+ * frame index, NULL entries skipped; frame 0's and a dropped frame's are not written. applied_or_null: n records by frame
+ * index: the frame's global record with its weight; frame 0: a unit record; a dropped frame: weight 0. The fold runs under
+ * the plain call's border (coverage = 1 needs BORDER_CONSTANT 0). finalize_ms is the moments pass plus the combine. */
+stk_status stk_ecc_match_local_normalized(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
+                                          float scale_down_width, const stk_local_norm_params* norm,
+                                          const stk_quantile_params* quantile_or_null, const float* weights_or_null,
+                                          stk_image_f32* out, float* den_or_null, int32_t* counts_or_null,
+                                          float* const* norm_out_or_null, stk_frame_weight* applied_or_null,
+                                          stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_local_normalized(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                               float scale_down_width, const stk_local_norm_params* norm,
+                                               const stk_quantile_params* quantile_or_null, const float* weights_or_null,
+                                               stk_image_f32* out, int32_t* dropped, float* den_or_null,
+                                               int32_t* counts_or_null, float* const* norm_out_or_null,
+                                               stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
+
 /* ---- stage-level entry points (parity tests bind these) ------------------ */
 /* cvt_color(BGR2GRAY) on the integer image, utils.rs:136-142. out: w*h of the input depth
  * (u8 / u16 / f32), tightly packed, same location as the frame. */

@@ -11,12 +11,12 @@ use (api.Stacker / _ffi.load) and there is no CPU fallback.
 from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_WRAP,  # noqa: F401
                   INTER_CUBIC, INTER_LINEAR,
                   LEAST_SQUARES, LMEDS, RANSAC, RHO, DrizzleParameters, EccMatchParameters, HipError, InvalidParams, IoError,
-                  KeyPointMatchParameters, LocalParameters, MeshParameters, MotionType, NotEnoughFiles, NotImplementedYet, OpenCvError,
+                  KeyPointMatchParameters, LocalNormParameters, LocalParameters, MeshParameters, MotionType, NotEnoughFiles, NotImplementedYet, OpenCvError,
                   ProcessingError, QuantileParameters, RejectParameters, RobustClipParameters, SelectParameters, SigmaClipParameters, Stacker,
                   StackerError, WeightParameters,
-                  default_stacker, ecc_match, keypoint_match, mesh_grid, mesh_pyramid_shapes, rank_frames)
+                  default_stacker, ecc_match, keypoint_match, local_norm_estimate, local_norm_grid, mesh_grid, mesh_pyramid_shapes, rank_frames)
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
            "SelectParameters", "rank_frames", "LocalParameters", "MeshParameters", "mesh_grid", "mesh_pyramid_shapes", "DrizzleParameters",
-           "RejectParameters"]
+           "RejectParameters", "LocalNormParameters", "local_norm_estimate", "local_norm_grid"]

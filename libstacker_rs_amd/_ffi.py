@@ -72,6 +72,11 @@ class LocalParams(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class LocalNormParams(C.Structure):
+    _fields_ = [("step", C.c_int32), ("stat_step", C.c_int32), ("normalize", C.c_int32), ("coverage", C.c_int32),
+                ("min_count", C.c_int32), ("fill", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class MeshParams(C.Structure):
     _fields_ = [("step", C.c_int32), ("radius", C.c_int32), ("max_iters", C.c_int32), ("epsilon", C.c_float),
                 ("max_shift", C.c_float), ("min_eig", C.c_float), ("fill", C.c_int32), ("reserved", C.c_int32)]
@@ -248,6 +253,24 @@ SIGNATURES = {
                                                               C.POINTER(RobustClipParams), C.POINTER(WeightParams), C.c_void_p,
                                                               C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
                                                               C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
+    "stk_local_moments": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_double, C.c_int32, C.c_int32, C.c_void_p]),
+    "stk_local_norm_estimate": (c_status, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(LocalNormParams), C.c_void_p, C.c_void_p,
+                                           C.POINTER(FrameWeight), C.c_void_p]),
+    "stk_local_norm_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_double, C.POINTER(FrameWeight), C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ImageF32),
+                                        C.c_void_p]),
+    "stk_quantile_stack_local_norm": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                 C.c_void_p, C.c_double, C.POINTER(QuantileParams), C.POINTER(FrameWeight),
+                                                 C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ImageF32), C.c_void_p]),
+    "stk_ecc_match_local_normalized": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float,
+                                                  C.POINTER(LocalNormParams), C.POINTER(QuantileParams), C.c_void_p,
+                                                  C.POINTER(ImageF32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameWeight),
+                                                  C.POINTER(FrameStats)]),
+    "stk_keypoint_match_local_normalized": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                                       C.POINTER(LocalNormParams), C.POINTER(QuantileParams), C.c_void_p,
+                                                       C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
     "stk_grey": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p]),
     "stk_convert_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_double, C.c_void_p]),
     "stk_hybrid_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.POINTER(EccParams),

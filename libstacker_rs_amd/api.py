@@ -173,6 +173,52 @@ class LocalParameters:            # extension beyond the reference: include/stac
 
 
 @dataclass
+class LocalNormParameters:        # extension beyond the reference: include/stacker.h, stk_local_norm_params
+    """Local normalisation: per frame a gain and an offset field on a grid of nodes `step` destination pixels apart (a power
+    of two, 8 .. 256), each node estimated (`normalize` as in WeightParameters) from the moments of the 2 step window around
+    it on every `stat_step`-th row and column (0 = 4). A node with fewer than `min_count` pixels (0 = 16), a degenerate
+    formula or a gain outside [0.25, 4] is invalid; `fill` passes fill such holes from their neighbours, the rest takes the
+    frame's global gain and offset."""
+    step: int = 64
+    stat_step: int = 0
+    normalize: int = NORMALIZE_LINEAR
+    coverage: bool = True
+    min_count: int = 0
+    fill: int = 4
+
+    def _c(self) -> _ffi.LocalNormParams:
+        return _ffi.LocalNormParams(int(self.step), int(self.stat_step), int(self.normalize), int(self.coverage), int(self.min_count),
+                                    int(self.fill), (C.c_int32 * 2)(0, 0))
+
+
+def local_norm_grid(width: int, height: int, step: int):
+    """(gh, gw, ch, cw): the node grid (mesh_grid's) and the cell grid of local normalisation for a width x height image."""
+    gw, gh = mesh_grid(width, height, step)
+    return gh, gw, (height + step - 1) // step, (width + step - 1) // step
+
+
+def local_norm_estimate(width: int, height: int, channels: int, cell_moments, norm: Optional["LocalNormParameters"] = None,
+                        return_global: bool = False, return_valid: bool = False):
+    """Estimator and fill of local normalisation for one frame (stk_local_norm_estimate; host code, no GPU): the
+    gh x gw x 2 channels f32 plane from the frame's (ch cw) x channels x 6 cell moments, then the global record
+    (return_global) and the per-node validity masks before the fill (return_valid, gh x gw int32)."""
+    p = (norm or LocalNormParameters())._c()
+    gh, gw, ch, cw = local_norm_grid(width, height, int(p.step))
+    mom = np.ascontiguousarray(np.asarray(cell_moments, np.float64).reshape(-1))
+    if mom.size != ch * cw * channels * 6:
+        raise InvalidParams("cell moments: (ch cw) x channels x 6 expected")
+    plane = np.zeros((gh, gw, 2 * channels), np.float32)
+    glob = _ffi.FrameWeight()
+    valid = np.zeros((gh, gw), np.int32)
+    st = _ffi.load().stk_local_norm_estimate(int(width), int(height), int(channels), C.byref(p), C.c_void_p(mom.ctypes.data),
+                                             C.c_void_p(plane.ctypes.data), C.byref(glob), C.c_void_p(valid.ctypes.data))
+    if st:
+        raise InvalidParams("stk_local_norm_estimate refused its arguments")
+    res = (plane,) + ((Stacker._applied_list([glob], 1, channels)[0],) if return_global else ()) + ((valid,) if return_valid else ())
+    return res if len(res) > 1 else plane
+
+
+@dataclass
 class MeshParameters:             # extension beyond the reference: include/stacker.h, stk_mesh_params
     """Local alignment: per frame a residual displacement on a grid of nodes `step` destination pixels apart (a power of
     two, 8 .. 256), each from a (2 radius + 1)^2 patch (radius 2 .. 32) by at most `max_iters` Lucas-Kanade iterations that
@@ -892,6 +938,150 @@ class Stacker:
                                                   int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), int(stat_step),
                                                   C.c_void_p(mom.ctypes.data)))
         return mom
+
+    # -- local normalisation: gain and offset fields on a node grid (extension beyond the reference) ------
+    def local_moments(self, files, warps, step: int, include=None, *, stat_step: int = 4, is_affine=False,
+                      border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0):
+        """The cell moments of every included frame against frame 0 (stk_local_moments): an n x ch x cw x channels x 6
+        float64 array, zeros for frame 0 and excluded frames."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Md, inc = self._warps_arg(warps, include, m.n)
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        step = int(step)
+        ch, cw = ((m.h + step - 1) // step, (m.w + step - 1) // step) if step > 0 else (1, 1)
+        mom = np.zeros((m.n, ch, cw, m.c, 6), np.float64)
+        self._check(self._lib.stk_local_moments(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
+                                                int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), step, int(stat_step),
+                                                C.c_void_p(mom.ctypes.data)))
+        return mom
+
+    @staticmethod
+    def _norm_arg(m: _Marshalled, norm):
+        """n host planes by frame index (None entries allowed) -> (keep-alive list, pointer array or None)."""
+        if norm is None:
+            return None, None
+        if len(norm) != m.n:
+            raise InvalidParams("one normalisation plane (or None) per frame expected")
+        keep = [None if p is None else np.ascontiguousarray(np.asarray(p, np.float32)) for p in norm]
+        if any(p is not None and (p.ndim != 3 or p.shape[2] != 2 * m.c) for p in keep):
+            raise InvalidParams("normalisation planes: gh x gw x 2 channels f32 expected")
+        ptrs = (C.c_void_p * m.n)(*[None if p is None else p.ctypes.data for p in keep])
+        return keep, ptrs
+
+    def local_norm_stack(self, files, warps, norm, step: int, gain=None, offset=None, weights=None, include=None, *, applied=None,
+                         coverage: bool = True, is_affine=False, border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0),
+                         alpha=1.0 / 255.0, return_den: bool = False):
+        """The locally normalised mean alone over caller-held warps (stk_local_norm_stack): weighted_stack whose gain and
+        offset come from `norm`, n planes (gh x gw x 2 channels, numpy) by frame index for the grid of `step`; a frame whose
+        plane is None uses its record (gain / offset / `applied`)."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Md, inc = self._warps_arg(warps, include, m.n)
+        rec = self._records_arg(m, gain, offset, weights, applied)
+        keep, nptr = self._norm_arg(m, norm)
+        if keep is not None:
+            self._norm_shapes(m, keep, step)
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        out, img = self._out_image(m)
+        den, dptr = self._coverage_image(m) if return_den else (None, None)
+        self._check(self._lib.stk_local_norm_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                   None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
+                                                   int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), rec, nptr, int(step),
+                                                   int(coverage), C.byref(img), dptr))
+        return (out, den) if return_den else out
+
+    @staticmethod
+    def _norm_shapes(m: _Marshalled, keep, step):
+        try:
+            gw, gh = mesh_grid(m.w, m.h, int(step))
+        except InvalidParams:
+            return                                # the engine reports the bad step
+        if any(p is not None and p.shape[:2] != (gh, gw) for p in keep):
+            raise InvalidParams("normalisation planes: gh x gw x 2 channels f32 expected")
+
+    def quantile_stack_local_norm(self, files, warps, norm, step: int, quantile=None, gain=None, offset=None, weights=None,
+                                  include=None, *, applied=None, coverage: bool = True, is_affine=False,
+                                  border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0,
+                                  return_counts: bool = False):
+        """The locally normalised quantile alone over caller-held warps (stk_quantile_stack_local_norm):
+        quantile_stack_weighted through the planes of local_norm_stack."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Md, inc = self._warps_arg(warps, include, m.n)
+        rec = self._records_arg(m, gain, offset, weights, applied)
+        keep, nptr = self._norm_arg(m, norm)
+        if keep is not None:
+            self._norm_shapes(m, keep, step)
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        out, img = self._out_image(m)
+        cnt, cptr = self._pixel_counts_image(m) if return_counts else (None, None)
+        qp = _quantile_c(quantile)
+        self._check(self._lib.stk_quantile_stack_local_norm(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
+                                                            None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
+                                                            int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(qp),
+                                                            rec, nptr, int(step), int(coverage), C.byref(img), cptr))
+        return (out, cnt) if return_counts else out
+
+    def _match_local_normalized(self, kind, files, params, norm, quantile, weights, scale_down_width, return_stats, return_den,
+                                return_counts, return_norm, return_applied):
+        if kind == "ecc" and isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        np_ = (norm or LocalNormParameters())._c()
+        den, dptr = self._coverage_image(m) if return_den else (None, None)
+        cnt, cptr = self._pixel_counts_image(m) if return_counts else (None, None)
+        qp = None if quantile is None else _quantile_c(quantile)
+        wkeep, wptr = self._weights_arg(weights, m.n)
+        planes, pptr = None, None
+        if return_norm:
+            gw, gh = mesh_grid(m.w, m.h, int(np_.step))
+            planes = [np.zeros((gh, gw, 2 * m.c), np.float32) for _ in range(m.n)]
+            pptr = (C.c_void_p * m.n)(*[p.ctypes.data for p in planes])
+        applied = (_ffi.FrameWeight * m.n)()
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p = params._c()
+        fn = getattr(self._lib, f"stk_{kind}_match_local_normalized")
+        args = [self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(np_),
+                None if qp is None else C.byref(qp), wptr, C.byref(img)]
+        if kind == "keypoint":
+            args.append(C.byref(dropped))
+        self._check(fn(*args, dptr, cptr, pptr, applied, stats))
+        stl = self._stats_list(stats, m.n)
+        if planes is not None:                      # frame 0 and dropped frames have no plane
+            planes = [None if i == 0 or (kind == "keypoint" and stl[i]["status"] != 0) else planes[i] for i in range(m.n)]
+        res = ((dropped.value,) if kind == "keypoint" else ()) + (out,) + ((den,) if return_den else ()) \
+            + ((cnt,) if return_counts else ()) + ((planes,) if return_norm else ()) \
+            + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) + ((stl,) if return_stats else ())
+        return res if len(res) > 1 else out
+
+    def ecc_match_local_normalized(self, files, params: EccMatchParameters, norm: Optional["LocalNormParameters"] = None,
+                                   quantile=None, weights=None, scale_down_width: Optional[float] = None, return_stats: bool = False,
+                                   return_den: bool = False, return_counts: bool = False, return_norm: bool = False,
+                                   return_applied: bool = False):
+        """ecc_match with local normalisation (stk_ecc_match_local_normalized): the locally normalised mean, or with
+        `quantile` the locally normalised quantile. Returns the image, then den (return_den, mean only), the counts
+        (return_counts, quantile only), the planes by frame index (return_norm; None for frame 0), the global records
+        (return_applied) and the stats."""
+        return self._match_local_normalized("ecc", files, params, norm, quantile, weights, scale_down_width, return_stats, return_den,
+                                            return_counts, return_norm, return_applied)
+
+    def keypoint_match_local_normalized(self, files, params: KeyPointMatchParameters, norm: Optional["LocalNormParameters"] = None,
+                                        quantile=None, weights=None, scale_down_width: Optional[float] = None,
+                                        return_stats: bool = False, return_den: bool = False, return_counts: bool = False,
+                                        return_norm: bool = False, return_applied: bool = False):
+        """keypoint_match with local normalisation (stk_keypoint_match_local_normalized): (dropped, image, ...) as
+        ecc_match_local_normalized; a dropped frame has no plane and weight 0 in `applied`."""
+        return self._match_local_normalized("keypoint", files, params, norm, quantile, weights, scale_down_width, return_stats,
+                                            return_den, return_counts, return_norm, return_applied)
 
     # -- per-pixel weight maps and local-sharpness stacking (extension beyond the reference) --------------
     def local_sharpness(self, files, local: Optional["LocalParameters"] = None):

@@ -227,6 +227,17 @@ struct ClipArgs {
     const float* const* fields;
     int mesh_shift, mesh_gw, mesh_gh;
     float mesh_inv;
+    // local normalisation (FoldNorm / FoldStoreNorm, warp_body.h; kernels_local_norm.hip; definition: include/stacker.h,
+    // "Local normalisation"): norm[i] = the gain / offset plane of table entry i (norm_gh x norm_gw x 2 cn f32, per node
+    // the cn gains, then the cn offsets; null = the entry's record in coef as constants), node spacing 1 << norm_shift
+    // destination pixels, norm_inv = 1.0f / spacing. coef / coverage / out / den / band as in the weighted modes
+    const float* const* norm;
+    int norm_shift, norm_gw, norm_gh;
+    float norm_inv;
+    // the cell moments pass (local_moments_kernel): cells = (n_frames - 1) x cell_h x cell_w records of cn x 6 doubles,
+    // entry 1 first; a cell is 1 << cell_shift destination pixels wide and high; `step` above is the stat step
+    double* cells;
+    int cell_shift, cell_w, cell_h;
 };
 
 // quantile combines: samples per pixel the selection kernel takes (64 lanes of a wave x 64 keys in registers)
@@ -341,6 +352,13 @@ MomentsPlan moments_plan(int dw, int dh, int step);
 // overlap moments of entries 1 .. a.n_frames - 1 against entry 0 (include/stacker.h): per-wave partials into c.partials
 // ((n_frames - 1) x plan.parts() x (1 + 5 cn) doubles), then reduced in index order into moments ((n_frames - 1) x cn x 6)
 hipError_t launch_overlap_moments(const WarpArgs& a, ClipArgs c, int depth, int step, double* moments, hipStream_t s);
+// local normalisation (kernels_local_norm.hip). The cell moments of entries 1 .. a.n_frames - 1 against entry 0 into
+// c.cells (c.step, c.cell_shift, c.cell_w, c.cell_h): one wave per (cell, entry), no partials. The two folds through the
+// planes of c.norm (c.norm_*; c.coef, c.coverage): the mean into c.out / c.den, and the store mode with participation for
+// one band (launch_quantile_store_weighted's fields of c). Generic kernels only, linear or cubic.
+hipError_t launch_local_moments(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
+hipError_t launch_norm_fold(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
+hipError_t launch_norm_store(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
 hipError_t launch_quantile_store(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
 // one pass of the weighted clip (c.coef, c.coverage, c.centre, c.kept besides launch_clip_pass's fields)
 hipError_t launch_clip_pass_weighted(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);

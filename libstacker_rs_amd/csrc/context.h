@@ -103,7 +103,7 @@ struct stk_ctx {
     DevBuf weighted;              // weighted combine (weighted.cpp): image, den plane, per-entry table, moments and their partials
     DevBuf coef;                  // normalised rejection combines (robust.cpp): the per-entry gain / offset / weight table
     DevBuf quantile;              // quantile combines (quantile.cpp): a w x h x cn f32 image, then the band of samples
-    DevBuf local;                 // per-pixel weights (local.cpp): pointer tables, per-entry table, image, den plane, the entries' map planes
+    DevBuf local;                 // per-pixel weights (local.cpp): pointer tables, per-entry table, image, den plane, the entries' map planes; local normalisation (local_norm.cpp) lays its own tables, cell moments and planes into it
     DevBuf mesh;                  // local alignment (mesh.cpp): pointer tables, field and status planes, fill scratch, a w x h x cn f32 image
     DevBuf reject;                // rejection maps (reject.cpp): entry table, counters, clean image, counts, map planes
     DevBuf quality;               // whole-stack sharpness (quality.cpp): frame pointers, per-frame records, tile partials
@@ -239,6 +239,13 @@ stk_status mesh_match_fields_check(stk_ctx* ctx, const stk_frames* frames, const
 stk_status mesh_match_fields_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_mesh_params* mp);
 stk_status mesh_match_fields(stk_ctx* ctx, const stk_frames* frames, int n_entries, int is_affine, const stk_mesh_params* mp,
                              MeshFoldArgs* out, double* ms);
+// local normalisation (local_norm.cpp): the plane table of a locally normalised fold, in device memory and indexed like
+// the frame table (null entry: the entry's record as constants)
+struct NormFoldArgs { const float* const* planes; int step, gw, gh; };
+void norm_fold_clip_args(const NormFoldArgs& n, stk::ClipArgs& ca);
+// quantile_bands_weighted (robust.cpp) with the locally normalised store launch: same bands, workspaces and selection
+stk_status quantile_bands_norm(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage,
+                               const stk_quantile_params* p, const NormFoldArgs& norm, stk_image_f32* out, int32_t* counts, double* ms);
 // rejection maps (reject.cpp) and the pieces of the combines that the rejected drizzle (drizzle.cpp) is built from
 struct RejectLayout {
     size_t entries, tallies, clean, counts, planes, plane, total;    // byte offsets into ctx->reject; plane: bytes of one map plane

@@ -78,7 +78,8 @@ stk_status clip_passes_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight
 // The quantile with participation over the entries of ctx->warpframes: per band a store launch (normalised samples and
 // absent marks), then the selection with a per-pixel rank. `counts` (w x h, out's location) is optional.
 stk_status quantile_bands_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage,
-                                   const stk_quantile_params* p, stk_image_f32* out, int32_t* counts, double* ms) {
+                                   const stk_quantile_params* p, stk_image_f32* out, int32_t* counts, double* ms,
+                                   const NormFoldArgs* norm = nullptr) {
     const int n_entries = (int)coef.size(), w = spec.w, h = spec.h, cn = spec.cn, depth = spec.depth;
     stk_status st = quantile_check_count(ctx, n_entries);
     if (st) return st;
@@ -98,12 +99,14 @@ stk_status quantile_bands_weighted(stk_ctx* ctx, const std::vector<stk_frame_wei
     ca.plane_stride = row;
     ca.coef = ctx->coef.as<stk_frame_weight>();
     ca.coverage = coverage;
+    if (norm) norm_fold_clip_args(*norm, ca);        // the locally normalised quantile (local_norm.cpp): the same bands, its own store launch
     HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
     for (size_t y0 = 0; y0 < (size_t)h; y0 += R) {
         const size_t rows = std::min(R, (size_t)h - y0);
         ca.y0 = (int)y0; ca.band_rows = (int)rows;
         a.dh = (int)(y0 + rows);
-        HIP_TRY(launch_quantile_store_weighted(a, ca, depth, ctx->stream));
+        if (norm) HIP_TRY(launch_norm_store(a, ca, depth, ctx->stream));
+        else HIP_TRY(launch_quantile_store_weighted(a, ca, depth, ctx->stream));
         HIP_TRY(launch_quantile_select_masked(band, rows * row, n_entries, p->quantile, cn, dst + y0 * row,
                                               cdst ? cdst + y0 * (size_t)w : nullptr, ctx->stream));
     }
@@ -214,6 +217,11 @@ stk_status robust_match_records(stk_ctx* ctx, const stk_frames* frames, const st
     stk_status st = entry_table_upload(ctx, frames, dev, table, spec.is_affine);
     if (st) return st;
     return weighted_match_records(ctx, frames->n, table, spec, weight, weights, coef, applied, ms);
+}
+
+stk_status quantile_bands_norm(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage,
+                               const stk_quantile_params* p, const NormFoldArgs& norm, stk_image_f32* out, int32_t* counts, double* ms) {
+    return quantile_bands_weighted(ctx, coef, spec, coverage, p, out, counts, ms, &norm);
 }
 
 stk_status robust_match_median(stk_ctx* ctx, const stk_frames* frames, const std::vector<stk_frame_weight>& coef, int is_affine,

@@ -20,6 +20,9 @@
 // plane itself. Generic kernels only.
 // The normalised, coverage-aware rejection combines add two states that take kappa through the same hooks: the weighted
 // clip (ClipWGeneric<CN> / ClipWU8C3, kernels_clip.hip) and the store mode with participation (FoldStoreW<CN>, below).
+// Local normalisation adds two more of that kind (FoldNorm<CN>, FoldStoreNorm<CN>, below; launched from
+// kernels_local_norm.hip): the weighted mode and the store mode with participation with the entry's gain and offset
+// interpolated from a node grid. Generic kernels only.
 // The bicubic fold (warp_cubic_body.h) is a second kernel that speaks the same hooks. What it shares with the generic kernel
 // here is shared as text, in two fragments that both include inside their frame loops: the coordinates and the bilinear
 // sample (warp_coords.inc.h, warp_linear_sample.inc.h). Text, not helper functions: see the note at
@@ -36,6 +39,8 @@ template <int CN> struct FoldWeighted;
 template <int CN> struct FoldMoments;
 template <int CN> struct FoldStoreW;
 template <int CN> struct FoldLocal;
+template <int CN> struct FoldNorm;
+template <int CN> struct FoldStoreNorm;
 template <int CN> struct ClipWGeneric;
 struct ClipWU8C3;
 struct NoClip;
@@ -118,11 +123,13 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
     constexpr bool WEIGHTED = std::is_same_v<ClipState, FoldWeighted<CN>>;
     constexpr bool MOMENTS = std::is_same_v<ClipState, FoldMoments<CN>>;
     // the normalised, coverage-aware rejection states (kernels_clip.hip, FoldStoreW below) take kappa like the weighted mode
-    constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>;
+    constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>> ||
+                            std::is_same_v<ClipState, FoldNorm<CN>> || std::is_same_v<ClipState, FoldStoreNorm<CN>>;   // (and the two local-normalisation states)
     constexpr bool LOCAL = std::is_same_v<ClipState, FoldLocal<CN>> || std::is_same_v<ClipState, Mesh<FoldLocal<CN>>>;   // kappa like the weighted mode, and the coordinates
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if constexpr (std::is_same_v<ClipState, FoldStore<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
+    if constexpr (std::is_same_v<ClipState, FoldStore<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>> ||
+                  std::is_same_v<ClipState, FoldStoreNorm<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
     // (moments mode: (x, y) index the stepped grid and every lane stays for the wave reduction; see the loop below)
     if constexpr (!MOMENTS) { if (x >= a.dw || y >= a.dh) return; }
     float* accp = a.acc + (size_t)y * a.acc_stride + (size_t)x * CN;
@@ -387,6 +394,97 @@ struct FoldLocal {
         for (int c = 0; c < CN; c++) o[c] = den > 0.f ? num[c] / den : 0.f;
         if (ca.den) ca.den[(size_t)y * ca.den_stride + x] = den;
     }
+};
+
+// Local normalisation (definition: include/stacker.h, "Local normalisation"; launched from kernels_local_norm.hip, generic
+// kernels only): the weighted mode and the store mode with participation, with the entry's gain and offset read from a
+// node grid instead of its record. NormAt is a destination pixel's place on that grid, computed once per pixel in begin():
+// the float offsets of its four nodes within a plane and the two fractions. The pixel's OWN y addresses the grid, also in
+// the store mode, whose band pointer is the only thing that counts rows from ClipArgs::y0. at(P, q) is component q of
+// plane P at the pixel: the mesh fold's chain (mesh_displace above), operation by operation.
+struct NormAt {
+    int o00, o01, o10, o11;
+    float u, v;
+    __device__ __forceinline__ void set(const ClipArgs& ca, int x, int y, int comps) {
+        const int k = x >> ca.norm_shift, j = y >> ca.norm_shift;
+        const int k1 = min(k + 1, ca.norm_gw - 1), j1 = min(j + 1, ca.norm_gh - 1);
+        u = (float)(x - (k << ca.norm_shift)) * ca.norm_inv; v = (float)(y - (j << ca.norm_shift)) * ca.norm_inv;
+        o00 = (j * ca.norm_gw + k) * comps; o01 = (j * ca.norm_gw + k1) * comps;
+        o10 = (j1 * ca.norm_gw + k) * comps; o11 = (j1 * ca.norm_gw + k1) * comps;
+    }
+    __device__ __forceinline__ float at(const float* __restrict__ P, int q) const {
+        const float t0 = __builtin_fmaf(u, P[o01 + q] - P[o00 + q], P[o00 + q]);
+        const float t1 = __builtin_fmaf(u, P[o11 + q] - P[o10 + q], P[o10 + q]);
+        return __builtin_fmaf(v, t1 - t0, t0);
+    }
+};
+
+// The locally normalised mean: FoldWeighted with (G, O) = the entry's plane at the pixel, or its record's gain and offset
+// where the entry has no plane (fma(u, 0, g) = g: a constant plane and a record give the same bits). The table pointers
+// (records, planes) move on after channel CN - 1.
+template <int CN>
+struct FoldNorm {
+    float num[CN], den, kap;
+    const stk_frame_weight* e;
+    const float* const* np;
+    NormAt at;
+    int cov;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+#pragma unroll
+        for (int c = 0; c < CN; c++) num[c] = 0.f;
+        den = 0.f; kap = 1.0f;
+        e = ca.coef; np = ca.norm; cov = ca.coverage;
+        at.set(ca, x, y, 2 * CN);
+    }
+    __device__ __forceinline__ void entry(float k) { kap = cov ? k : 1.0f; }
+    __device__ __forceinline__ void add(int c, float s) {
+        const float* __restrict__ P = *np;
+        const float G = P ? at.at(P, c) : e->gain[c], O = P ? at.at(P, CN + c) : e->offset[c];
+        const float v = s * G + O * kap;
+        num[c] = num[c] + e->weight * v;
+        if (c == CN - 1) { den = den + e->weight * kap; e++; np++; }
+    }
+    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
+        float* o = ca.out + (size_t)y * ca.out_stride + (size_t)x * CN;
+#pragma unroll
+        for (int c = 0; c < CN; c++) o[c] = den > 0.f ? num[c] / den : 0.f;
+        if (ca.den) ca.den[(size_t)y * ca.den_stride + x] = den;
+    }
+};
+
+// The locally normalised store mode: FoldStoreW with u = s * G + O. The record and plane tables are read through
+// constant-address-space pointers for FoldStoreW's reason (the band's stores could alias them as far as the compiler knows).
+template <int CN>
+struct FoldStoreNorm {
+    typedef const stk_frame_weight __attribute__((address_space(4))) * CoefPtr;
+    typedef const float* const __attribute__((address_space(4))) * PlanePtr;
+    float* p;
+    size_t slab;
+    CoefPtr e;
+    PlanePtr np;
+    NormAt at;
+    float v[CN];
+    int cov;
+    bool part;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+        p = ca.band + (size_t)(y - ca.y0) * ca.plane_stride + (size_t)x * CN;
+        slab = (size_t)ca.band_rows * ca.plane_stride;
+        e = (CoefPtr)(uintptr_t)ca.coef; np = (PlanePtr)(uintptr_t)ca.norm; cov = ca.coverage; part = true;
+        at.set(ca, x, y, 2 * CN);         // y, not y - y0: the grid is the destination's
+    }
+    __device__ __forceinline__ void entry(float k) { part = (e->weight > 0.0f) & (cov ? k == 1.0f : true); }
+    __device__ __forceinline__ void add(int c, float s) {
+        const float* __restrict__ P = *np;
+        const float G = P ? at.at(P, c) : e->gain[c], O = P ? at.at(P, CN + c) : e->offset[c];
+        const float u = s * G + O;
+        v[c] = part ? u : __uint_as_float(QUANTILE_ABSENT_BITS);
+        if (c == CN - 1) {
+#pragma unroll
+            for (int i = 0; i < CN; i++) p[i] = v[i];
+            p += slab; e++; np++;
+        }
+    }
+    __device__ __forceinline__ void finish(const ClipArgs&, int, int) {}
 };
 
 // The moments mode's state (generic kernel only): the thread's private f64 sums n, and per channel sum X, sum Y, sum X^2,

@@ -31,11 +31,13 @@ template <typename T, int CN, bool CLIP, class ClipState>
 __global__ __launch_bounds__(256) void warp_accumulate_cubic_kernel(WarpArgs a, ClipArgs ca) {
     constexpr bool WEIGHTED = std::is_same_v<ClipState, FoldWeighted<CN>>;
     constexpr bool MOMENTS = std::is_same_v<ClipState, FoldMoments<CN>>;
-    constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>;
+    constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>> ||
+                            std::is_same_v<ClipState, FoldNorm<CN>> || std::is_same_v<ClipState, FoldStoreNorm<CN>>;
     constexpr bool LOCAL = std::is_same_v<ClipState, FoldLocal<CN>>;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if constexpr (std::is_same_v<ClipState, FoldStore<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
+    if constexpr (std::is_same_v<ClipState, FoldStore<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>> ||
+                  std::is_same_v<ClipState, FoldStoreNorm<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
     if constexpr (!MOMENTS) { if (x >= a.dw || y >= a.dh) return; }
     float* accp = a.acc + (size_t)y * a.acc_stride + (size_t)x * CN;
     float sum[CN];
