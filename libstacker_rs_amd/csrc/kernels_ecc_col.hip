@@ -25,6 +25,10 @@ namespace stk {
 //     base plus a constant lane offset (no per-pixel address arithmetic), the loop counters live in SGPRs.
 //   * J.u, J.v, J.m are factorised the same way: J = (a, b, t) (x) (X, Y, 1), so a lane keeps sum c*w and sum c*w*Y for
 //     c in {a, b, t}, w in {u, v, m}: 18 accumulators instead of 24, no J vector at all.
+//   * Y is multiplied into the three Jacobian terms, not into their products: with j = (a, b, t) and jy = j * Y (three
+//     multiplies per pixel) every one of the 18 Hessian moments is ONE fma of two of those six values (j.j, jy.j, jy.jy)
+//     and every projection moment one fma (j.w, jy.w) — 21 + 12 operations where rounding each product first and
+//     scaling it by Y and Y^2 afterwards took 25 + 18.
 //   * (Round 2 wrote everything that comes in pairs as v_pk_* on float2; round 4 measured that a packed instruction
 //     occupies the SIMD exactly as long as the two plain ones it replaces, see below.)
 //   * A strip whose four corners map well inside the frame-0 image (the image of a convex set under a homography with
@@ -177,9 +181,10 @@ __device__ __forceinline__ void ecc_first_iter_body(const EccIterArgs& a, const 
             const float ja = r.y, jb = r.z;                       // gxw * rw, gyw * rw with rw == 1
             const float jt = -(fx * ja) - (fy * jb);
             const float vv = tval, um = r.x;                      // tval - cT, Iw - cI with cI == cT == 0
-            const float ca = ja * vv, cb = jb * vv, ct = jt * vv;
-            m0a += ca; m0b += cb; m0t += ct;
-            m1a = __builtin_fmaf(ca, fy, m1a); m1b = __builtin_fmaf(cb, fy, m1b); m1t = __builtin_fmaf(ct, fy, m1t);
+            const float jya = ja * fy, jyb = jb * fy, jyt = jt * fy;   // Y into the Jacobian terms first, as accumulate() does
+            m0a = __builtin_fmaf(ja, vv, m0a); m1a = __builtin_fmaf(jya, vv, m1a);
+            m0b = __builtin_fmaf(jb, vv, m0b); m1b = __builtin_fmaf(jyb, vv, m1b);
+            m0t = __builtin_fmaf(jt, vv, m0t); m1t = __builtin_fmaf(jyt, vv, m1t);
             s_v += vv;
             s_vv = __builtin_fmaf(vv, vv, s_vv); s_x = __builtin_fmaf(um, vv, s_x);
         };
@@ -436,14 +441,19 @@ __global__ __launch_bounds__(256, STK_COL_WG) void ecc_iter_col_kernel(EccIterAr
                 accp[NH + 3 * P + 5] = __builtin_fmaf(um, v, accp[NH + 3 * P + 5]);
                 return;
             } else {
-                const float fyy = fy * fy;
                 const float sx = co.sx, sy = co.sy, rw = co.rw, Iw = bl.Iw;
                 const float ja = bl.gxw * rw, jb = bl.gyw * rw;
                 const float jt = -(sx * ja) - (sy * jb);            // hatX*ja + hatY*jb
-                const float pr[6] = {ja * ja, jb * jb, ja * jt, jb * jt, ja * jb, jt * jt};
+                // Y goes into the Jacobian terms FIRST (three multiplies), so that every moment sum below is one fma of two
+                // of these six values: no product is formed, rounded and then scaled by Y or Y^2
+                const float j[3] = {ja, jb, jt};
+                const float jy[3] = {ja * fy, jb * fy, jt * fy};
+                constexpr int pa[6] = {0, 1, 0, 1, 0, 2}, pb[6] = {0, 1, 2, 2, 1, 2};     // aa bb at bt ab tt
 #pragma unroll
                 for (int k = 0; k < 6; k++) {
-                    hs[k][0] += pr[k]; hs[k][1] = __builtin_fmaf(pr[k], fy, hs[k][1]); hs[k][2] = __builtin_fmaf(pr[k], fyy, hs[k][2]);
+                    hs[k][0] = __builtin_fmaf(j[pa[k]], j[pb[k]], hs[k][0]);
+                    hs[k][1] = __builtin_fmaf(jy[pa[k]], j[pb[k]], hs[k][1]);
+                    hs[k][2] = __builtin_fmaf(jy[pa[k]], jy[pb[k]], hs[k][2]);
                 }
                 const float cu = Iw - c.cI, cv = tval - c.cT;     // centred samples
                 float uu, vv, um, mf = 1.0f;
@@ -465,11 +475,18 @@ __global__ __launch_bounds__(256, STK_COL_WG) void ecc_iter_col_kernel(EccIterAr
                 const float w[3] = {uu, vv, mf};
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
-                    // (FAST: mf is the constant 1 and the products with it fold away)
-                    const float ca = ja * w[k], cb = jb * w[k], ct = jt * w[k];
-                    ms0[3 * k + 0] += ca; ms0[3 * k + 1] += cb; ms0[3 * k + 2] += ct;
-                    ms1[3 * k + 0] = __builtin_fmaf(ca, fy, ms1[3 * k + 0]); ms1[3 * k + 1] = __builtin_fmaf(cb, fy, ms1[3 * k + 1]);
-                    ms1[3 * k + 2] = __builtin_fmaf(ct, fy, ms1[3 * k + 2]);
+#pragma unroll
+                    for (int cc = 0; cc < 3; cc++) {
+                        if constexpr (FAST) {
+                            if (k == 2) {                         // mf is the constant 1: fma(j, 1, s) is s + j, bit for bit
+                                ms0[6 + cc] += j[cc];
+                                ms1[6 + cc] += jy[cc];
+                                continue;
+                            }
+                        }
+                        ms0[3 * k + cc] = __builtin_fmaf(j[cc], w[k], ms0[3 * k + cc]);
+                        ms1[3 * k + cc] = __builtin_fmaf(jy[cc], w[k], ms1[3 * k + cc]);
+                    }
                 }
                 s_u += um; s_v += vv;
                 s_uu = __builtin_fmaf(um, uu, s_uu); s_vv = __builtin_fmaf(vv, vv, s_vv); s_x = __builtin_fmaf(um, vv, s_x);
