@@ -32,31 +32,25 @@ stk_status clip_passes(stk_ctx* ctx, int n_frames, const FoldSpec& spec, const s
                        double* ms) {
     const int w = spec.w, cn = spec.cn, depth = spec.depth;
     const size_t nel = (size_t)w * spec.h * cn;
-    float* c = ctx->clip.as<float>();
+    const ClipLayout L = clip_layout(nel);
+    char* base = ctx->clip.as<char>();
     const WarpArgs a = fold_warp_args(ctx, n_frames, spec);
-    const bool host = out->location != STK_DEVICE;
     ClipArgs ca{};
-    ca.c = c; ca.L = c + nel; ca.U = c + 2 * nel;
+    ca.c = (float*)(base + L.c); ca.L = (float*)(base + L.L); ca.U = (float*)(base + L.U);
     ca.plane_stride = (size_t)w * cn;
     // a host output goes through the planes themselves: each thread reads its c, L, U before it writes out / counts there
-    ca.out = host ? c : out->data;
+    const CombineOutputs o(out, ca.c, nel, {counts, ca.L, nel});
+    ca.out = o.image();
     ca.out_stride = (size_t)w * cn;
-    ca.counts = counts ? (host ? (int*)ca.L : counts) : nullptr;
+    ca.counts = o.side<int>(0);
     ca.kappa_low = p->kappa_low; ca.kappa_high = p->kappa_high;
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if (stk_status st = combine_begin(ctx)) return st;
     for (int t = 1; t <= p->iterations + 1; t++) {
         ca.first = t == 1;
         ca.last = t == p->iterations + 1;
         HIP_TRY(launch_clip_pass(a, ca, depth, ctx->stream));
     }
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    if (host) {
-        HIP_TRY(hipMemcpyAsync(out->data, c, nel * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (counts) HIP_TRY(hipMemcpyAsync(counts, ca.L, nel * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms, &o);
 }
 
 // the checks and the workspace of the two whole-stack forms: the plain call writes its mean straight into the c plane
@@ -66,8 +60,7 @@ stk_status clip_match_begin(stk_ctx* ctx, const stk_frames* frames, const stk_cl
     if ((st = check_frames(ctx, frames, true))) return st;
     if ((st = combine_check_out(ctx, out, frames))) return st;
     (void)hipSetDevice(ctx->device);
-    HIP_TRY(ctx->clip.reserve(3 * (size_t)frames->width * frames->height * frames->channels * sizeof(float)));
-    return STK_OK;
+    return workspace_reserve(ctx, ctx->clip, clip_layout((size_t)frames->width * frames->height * frames->channels).total, "sigma clipping");
 }
 
 // and their combine over the kept frames
@@ -96,7 +89,7 @@ stk_status stk_clip_stack(stk_ctx* ctx, const stk_frames* frames, const double* 
     if ((st = entry_table_begin(ctx, frames, table, is_affine))) return st;
     const FoldSpec spec = fold_spec(frames, alpha, border_mode, border_value, is_affine);
     const size_t nel = (size_t)spec.w * spec.h * spec.cn;
-    HIP_TRY(ctx->clip.reserve(3 * nel * sizeof(float)));
+    if ((st = workspace_reserve(ctx, ctx->clip, clip_layout(nel).total, "sigma clipping"))) return st;
     // c = the plain mean: the fold, then stk_finalize_mean's scale
     float* c = ctx->clip.as<float>();
     HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));

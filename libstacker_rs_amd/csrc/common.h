@@ -340,15 +340,25 @@ __host__ __device__ inline size_t mesh_pyr_offset(int w, int h, int level) {
 hipError_t launch_mesh_pyr(const MeshPyrArgs& a, int cn, hipStream_t s);
 // `passes` hole-filling passes over the fields of entries 1 .. n_entries - 1; scratch: (n_entries - 1) x
 // mesh_fill_scratch_bytes(gw, gh) bytes of device memory
-size_t mesh_fill_scratch_bytes(int gw, int gh);
+inline size_t mesh_fill_scratch_bytes(int gw, int gh) { return ((size_t)gw * gh * (2 * sizeof(float) + 2) + 255) & ~(size_t)255; }
 hipError_t launch_mesh_fill(float* const* fields, const int* const* status, int n_entries, int gw, int gh, int passes, void* scratch,
                             hipStream_t s);
 // the mesh folds over the frames of `a` (c.fields, c.mesh_*): the generic kernel's mesh variant, linear only; local: the
 // local-weighted state (launch_local_fold's fields of c), else the running sums into a.acc
 hipError_t launch_mesh_fold(const WarpArgs& a, const ClipArgs& c, int depth, bool local, hipStream_t s);
-// stepped grid of the moments pass for a dw x dh destination: columns, rows per thread, workgroups in x and y
+// stepped grid of the moments pass for a dw x dh destination: columns, rows per thread, workgroups in x and y. Rows per
+// thread: at least 8, and enough that an entry has about 1024 partials at most (the second launch adds them one after the other)
 struct MomentsPlan { int gw, gh, reps, bx, by; size_t parts() const { return (size_t)bx * by * 4; } };
-MomentsPlan moments_plan(int dw, int dh, int step);
+inline MomentsPlan moments_plan(int dw, int dh, int step) {
+    MomentsPlan p;
+    p.gw = (dw + step - 1) / step;
+    p.gh = (dh + step - 1) / step;
+    p.bx = (p.gw + 63) / 64;
+    const long long want = ((long long)p.bx * p.gh + 1023) / 1024;
+    p.reps = (int)(want < 8 ? 8 : want);
+    p.by = (p.gh + 4 * p.reps - 1) / (4 * p.reps);
+    return p;
+}
 // overlap moments of entries 1 .. a.n_frames - 1 against entry 0 (include/stacker.h): per-wave partials into c.partials
 // ((n_frames - 1) x plan.parts() x (1 + 5 cn) doubles), then reduced in index order into moments ((n_frames - 1) x cn x 6)
 hipError_t launch_overlap_moments(const WarpArgs& a, ClipArgs c, int depth, int step, double* moments, hipStream_t s);

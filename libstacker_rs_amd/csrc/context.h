@@ -1,5 +1,5 @@
 // context.h — the engine's per-GPU context (stk_ctx) and host helpers shared by stacker.cpp, keypoint.cpp and the combines
-// (whose common front end is combine.h).
+// (whose common front end is combine.h and whose common back end is workspace.h).
 #pragma once
 #include <functional>
 #include <mutex>
@@ -99,13 +99,14 @@ struct stk_ctx {
     unsigned char* files_block = nullptr; size_t files_block_cap = 0; bool files_block_pinned = false;
     // workspace
     DevBuf frames, ref, blur_tmp, templates, slots, queue, results, partials, first_sums, warpframes, acc, scratch, init_warps, frameptrs;
-    DevBuf clip;                  // sigma clipping (clip.cpp): the c, L and U planes
-    DevBuf weighted;              // weighted combine (weighted.cpp): image, den plane, per-entry table, moments and their partials
-    DevBuf coef;                  // normalised rejection combines (robust.cpp): the per-entry gain / offset / weight table
-    DevBuf quantile;              // quantile combines (quantile.cpp): a w x h x cn f32 image, then the band of samples
-    DevBuf local;                 // per-pixel weights (local.cpp): pointer tables, per-entry table, image, den plane, the entries' map planes; local normalisation (local_norm.cpp) lays its own tables, cell moments and planes into it
-    DevBuf mesh;                  // local alignment (mesh.cpp): pointer tables, field and status planes, fill scratch, a w x h x cn f32 image
-    DevBuf reject;                // rejection maps (reject.cpp): entry table, counters, clean image, counts, map planes
+    // the combines' workspaces, each laid out by the struct named (workspace.h)
+    DevBuf clip;                  // ClipLayout (clip.cpp, robust.cpp, robust_clip.cpp)
+    DevBuf weighted;              // WeightedLayout
+    DevBuf coef;                  // the rejection combines' per-entry record table (robust.cpp, robust_clip.cpp)
+    DevBuf quantile;              // QuantileLayout; the band alone in robust_clip.cpp
+    DevBuf local;                 // LocalLayout, NormLayout or DrizzleLayout, one call at a time
+    DevBuf mesh;                  // MeshLayout, then PyrLayout; the pyramid planes alone in stk_grey_pyramid
+    DevBuf reject;                // RejectLayout
     DevBuf quality;               // whole-stack sharpness (quality.cpp): frame pointers, per-frame records, tile partials
     stk::KeypointWorkspace* kp = nullptr;
     stk::geom::HgWorkspace* hg = nullptr;   // findHomography batch workspace (homography.cpp)
@@ -168,6 +169,8 @@ void timing_begin(stk_ctx* ctx);
 double sharpness_finish(int metric, double s, double sq, int width, int height);
 float ev_ms(hipEvent_t a, hipEvent_t b);
 
+#include "workspace.h"
+
 // shared internals of the entry points (stacker.cpp / keypoint.cpp / hybrid.cpp / clip.cpp / quantile.cpp)
 // where the frames of a stack are after a whole-stack call on this context (upload.cpp / keypoint.cpp put host-fed stacks
 // at ctx->frames + i * frame bytes)
@@ -184,9 +187,9 @@ stk_status warp_table_upload(stk_ctx* ctx, std::vector<WarpFrame>& wf, size_t sr
 stk_status clip_validate(stk_ctx* ctx, const stk_clip_params* p);
 stk_status quantile_validate(stk_ctx* ctx, const stk_quantile_params* p);
 stk_status quantile_check_count(stk_ctx* ctx, int n);
-size_t quantile_image_floats(int w, int h, int cn);
 size_t quantile_band_rows(const stk_ctx* ctx, int n, int w, int h, int cn);
-stk_status quantile_reserve(stk_ctx* ctx, int n, int w, int h, int cn);
+// the layout of an n-frame w x h x cn stack's quantile combine (n = 0: the image alone), ctx->quantile reserved for it
+stk_status quantile_reserve(stk_ctx* ctx, int n, int w, int h, int cn, bool counts, QuantileLayout* L);
 stk_status robust_clip_validate(stk_ctx* ctx, const stk_robust_clip_params* p);
 // the median / MAD clip over the n_entries entries of ctx->warpframes (robust_clip.cpp): per band a store launch and the
 // selection into the clip planes, then one last clip pass. coef: the per-entry records of the participation form (then
@@ -204,11 +207,6 @@ void weighted_estimate(const double* m /* cn x 6 */, int cn, int mode, stk_frame
 stk_status weighted_match_records(stk_ctx* ctx, int n, const EntryTable& table, const FoldSpec& spec, const stk_weight_params* p,
                                   const float* weights, std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms);
 // the pieces of the local-weighted combine (local.cpp) that the mesh folds (mesh.cpp) are built from
-struct LocalLayout {
-    size_t fptrs, mptrs, coef, image, den, planes, plane, total;     // byte offsets into ctx->local; plane: bytes of one map plane
-};
-LocalLayout local_layout(size_t n_ptrs, int n_entries, int w, int h, int cn, size_t n_planes);
-stk_status local_reserve(stk_ctx* ctx, const LocalLayout& L, size_t n_planes);
 stk_status local_validate(stk_ctx* ctx, const stk_local_params* p);
 stk_status local_check_border(stk_ctx* ctx, int border_mode, const double* border_value);
 stk_status local_maps_enqueue(stk_ctx* ctx, const LocalLayout& L, const std::vector<const void*>& frames, const std::vector<float*>& planes);
@@ -247,11 +245,6 @@ void norm_fold_clip_args(const NormFoldArgs& n, stk::ClipArgs& ca);
 stk_status quantile_bands_norm(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage,
                                const stk_quantile_params* p, const NormFoldArgs& norm, stk_image_f32* out, int32_t* counts, double* ms);
 // rejection maps (reject.cpp) and the pieces of the combines that the rejected drizzle (drizzle.cpp) is built from
-struct RejectLayout {
-    size_t entries, tallies, clean, counts, planes, plane, total;    // byte offsets into ctx->reject; plane: bytes of one map plane
-};
-RejectLayout reject_layout(int n_entries, int sw, int sh, int cn, bool clean, bool counts, size_t n_planes);
-stk_status reject_reserve(stk_ctx* ctx, const RejectLayout& L);
 stk_status reject_validate(stk_ctx* ctx, const stk_reject_params* p);
 stk_status reject_run(stk_ctx* ctx, const RejectLayout& L, const stk_frames* frames, const std::vector<const void*>& dev,
                       const EntryTable& table, int is_affine, double alpha, const std::vector<stk_frame_weight>& coef, const float* clean,

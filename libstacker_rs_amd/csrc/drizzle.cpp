@@ -19,34 +19,6 @@ using namespace stk;
 
 namespace {
 
-struct DrizzleLayout {
-    size_t foot, coef, mptrs, image, den, planes, plane, total;     // byte offsets into ctx->local; plane: bytes of one map plane
-};
-
-// pre: bytes in front (the plain call's mean); the image, den and planes only where they are staged for the host
-DrizzleLayout drizzle_layout(size_t pre, int n_entries, int sw, int sh, int ow, int oh, int cn, bool host_out, size_t n_planes) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t ne = (size_t)std::max(n_entries, 1);
-    DrizzleLayout L{};
-    L.foot = up(pre);
-    L.coef = L.foot + up(ne * 2 * sizeof(float));
-    L.mptrs = L.coef + up(ne * sizeof(stk_frame_weight));
-    L.image = L.mptrs + up(ne * sizeof(void*));
-    L.den = L.image + (host_out ? up((size_t)ow * oh * cn * sizeof(float)) : 0);
-    L.planes = L.den + (host_out ? up((size_t)ow * oh * sizeof(float)) : 0);
-    L.plane = up((size_t)sw * sh * sizeof(float));
-    L.total = L.planes + n_planes * L.plane;
-    return L;
-}
-
-stk_status drizzle_reserve(stk_ctx* ctx, const DrizzleLayout& L) {
-    if (ctx->local.reserve(L.total) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, STK_HIP_ERROR, "drizzle: device allocation of " + std::to_string(L.total) + " bytes failed");
-    }
-    return STK_OK;
-}
-
 // every check that needs neither the matrices nor the records, in the order the errors are reported
 stk_status drizzle_validate(stk_ctx* ctx, const stk_frames* frames, bool need_bgr, const stk_drizzle_params* p, const stk_image_f32* out) {
     stk_status st = check_frames(ctx, frames, need_bgr, false);     // warp_interpolation is ignored: the option pair is not asked
@@ -91,8 +63,8 @@ void drizzle_entry(WarpFrame& wf, float* foot, const void* src, const double* M,
 
 // The drizzle launch over the table's entries, `dev[table.frame[k]]` under table.M[k], with the records `coef` (per entry) and the
 // maps (by frame index, in frames->location or with maps_device in device memory whatever the frames' location, or null).
-// ctx->local is reserved for L. Writes `out` and `den_out` (out's location), synchronises, returns the launch's device time
-// in *ms.
+// ctx->local is reserved for L. Writes `out` and `den_out` (out's location), synchronises, adds the launch's device time
+// to *ms.
 stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* frames, const std::vector<const void*>& dev,
                        const EntryTable& table, int is_affine, double alpha,
                        const stk_drizzle_params* p, const std::vector<stk_frame_weight>& coef, const float* const* maps,
@@ -101,7 +73,8 @@ stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* f
     const int ow = out->width, oh = out->height;
     const size_t rb = frame_row_bytes(frames);
     char* base = ctx->local.as<char>();
-    const bool host_out = out->location != STK_DEVICE, host_maps = frames->location != STK_DEVICE && !maps_device;
+    const bool host_maps = frames->location != STK_DEVICE && !maps_device;
+    const CombineOutputs o(out, (float*)(base + L.image), (size_t)ow * oh * cn, {den_out, base + L.den, (size_t)ow * oh});
     std::vector<WarpFrame> wf(ne);
     std::vector<float> foot((size_t)ne * 2);
     std::vector<const float*> mptr(ne, nullptr);
@@ -109,7 +82,7 @@ stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* f
     stk_status st = warp_table_upload(ctx, wf, rb, ow, oh, is_affine);
     if (st) return st;
     HIP_TRY(hipMemcpyAsync(base + L.foot, foot.data(), foot.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(base + L.coef, coef.data(), coef.size() * sizeof(stk_frame_weight), hipMemcpyHostToDevice, ctx->stream));
+    if ((st = records_upload(ctx, base + L.coef, coef))) return st;
     if (maps) {
         size_t slot = 0;
         for (int k = 0; k < ne; k++) {
@@ -134,8 +107,8 @@ stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* f
     a.coef = (const stk_frame_weight*)(base + L.coef);
     a.maps = maps ? (const float* const*)(base + L.mptrs) : nullptr;
     a.hp = 0.5f * p->pixfrac; a.hmax = 1.5f - 0.5f * p->pixfrac; a.fill = p->fill;
-    a.out = host_out ? (float*)(base + L.image) : out->data;
-    a.den = den_out ? (host_out ? (float*)(base + L.den) : den_out) : nullptr;
+    a.out = o.image();
+    a.den = o.side<float>(0);
     a.ow = ow; a.oh = oh;
     if (mesh) {
         // the grid's map onto frame 0, as drizzle_entry composes it
@@ -150,16 +123,9 @@ stk_status drizzle_run(stk_ctx* ctx, const DrizzleLayout& L, const stk_frames* f
         a.mesh_ty = (float)((0.5 * g - 0.5) + (double)p->origin_y);
         a.mesh_s = p->scale;
     }
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if ((st = combine_begin(ctx))) return st;
     HIP_TRY(launch_drizzle(a, frames->depth, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    if (host_out) {
-        HIP_TRY(hipMemcpyAsync(out->data, a.out, (size_t)ow * oh * cn * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (den_out) HIP_TRY(hipMemcpyAsync(den_out, a.den, (size_t)ow * oh * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));          // the host tables leave scope
-    *ms = ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms, &o);                     // (synchronises: the host tables leave scope)
 }
 
 // the tail of the whole-stack forms: the frames the plain call kept (combine.h: entries_from_stats), all weights 1, no
@@ -195,8 +161,7 @@ stk_status drizzle_stack_impl(stk_ctx* ctx, const stk_frames* frames, const doub
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
     if (mesh) {
         if (!fields) return fail(ctx, STK_INVALID_PARAMS, "null fields");
-        if (step < 8 || step > 256 || (step & (step - 1)) != 0)
-            return fail(ctx, STK_INVALID_PARAMS, "mesh: step must be 8, 16, 32, 64, 128 or 256");
+        if (!grid_step_ok(step)) return fail(ctx, STK_INVALID_PARAMS, "mesh: step must be 8, 16, 32, 64, 128 or 256");
     }
     const int n = frames->n, cn = frames->channels;
     EntryTable table;
@@ -212,7 +177,7 @@ stk_status drizzle_stack_impl(stk_ctx* ctx, const stk_frames* frames, const doub
     timing_begin(ctx);
     const DrizzleLayout L = drizzle_layout(0, (int)coef.size(), frames->width, frames->height, out->width, out->height, cn,
                                            out->location != STK_DEVICE, n_planes);
-    if ((st = drizzle_reserve(ctx, L))) return st;
+    if ((st = workspace_reserve(ctx, ctx->local, L.total, "drizzle"))) return st;
     std::vector<const void*> dev;
     if ((st = resolve_frames(ctx, frames, dev))) return st;
     MeshFoldArgs mf{};
@@ -236,7 +201,7 @@ stk_status ecc_match_drizzle_impl(stk_ctx* ctx, const stk_frames* frames, const 
     const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
     const size_t pre = (size_t)w * h * cn * sizeof(float);
     const DrizzleLayout L = drizzle_layout(pre, n, w, h, out->width, out->height, cn, out->location != STK_DEVICE, 0);
-    if ((st = drizzle_reserve(ctx, L))) return st;
+    if ((st = workspace_reserve(ctx, ctx->local, L.total, "drizzle"))) return st;
     if (mesh && (st = mesh_match_fields_reserve(ctx, frames, mesh))) return st;
     std::vector<stk_frame_stats> own;
     if (!stats) { own.resize(n); stats = own.data(); }
@@ -259,7 +224,7 @@ stk_status keypoint_match_drizzle_impl(stk_ctx* ctx, const stk_frames* frames, c
     const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
     const size_t pre = (size_t)w * h * cn * sizeof(float);
     const DrizzleLayout L = drizzle_layout(pre, n, w, h, out->width, out->height, cn, out->location != STK_DEVICE, 0);
-    if ((st = drizzle_reserve(ctx, L))) return st;
+    if ((st = workspace_reserve(ctx, ctx->local, L.total, "drizzle"))) return st;
     if (mesh && (st = mesh_match_fields_reserve(ctx, frames, mesh))) return st;
     std::vector<stk_frame_stats> own;
     if (!stats) { own.resize(n); stats = own.data(); }
@@ -285,10 +250,10 @@ stk_status drizzle_rejected_reserve(stk_ctx* ctx, const stk_frames* frames, cons
     const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
     Ls->D = drizzle_layout((size_t)w * h * cn * sizeof(float), n, w, h, out->width, out->height, cn, out->location != STK_DEVICE, 0);
     Ls->R = reject_layout(n, w, h, cn, true, true, (size_t)n);
-    stk_status st = reject_reserve(ctx, Ls->R);
+    stk_status st = workspace_reserve(ctx, ctx->reject, Ls->R.total, "reject maps");
     if (st) return st;
-    if ((st = drizzle_reserve(ctx, Ls->D))) return st;
-    return quantile_reserve(ctx, n, w, h, cn);
+    if ((st = workspace_reserve(ctx, ctx->local, Ls->D.total, "drizzle"))) return st;
+    return quantile_reserve(ctx, n, w, h, cn, false, nullptr);
 }
 
 // the tail of the rejected forms, after the plain call: records, median, reject maps, drizzle (include/stacker.h, the steps

@@ -259,8 +259,6 @@ hipError_t launch_mesh_pyr(const MeshPyrArgs& a, int cn, hipStream_t s) {
 // Hole filling: one workgroup per field (blockIdx.x + 1 = the table entry). Jacobi passes between the field itself and a
 // scratch copy, the validity alongside as bytes; the workgroup's barrier orders a pass's writes before the next pass's
 // reads. A node that is valid is copied; a hole takes the [1 2 1]^T [1 2 1] mean of its valid in-grid neighbours, row-major.
-size_t mesh_fill_scratch_bytes(int gw, int gh) { return ((size_t)gw * gh * (2 * sizeof(float) + 2) + 255) & ~(size_t)255; }
-
 // valid != null: the validity comes from valid[e] instead of status > 0 and goes back there after the last pass.
 __global__ __launch_bounds__(256) void mesh_fill_kernel(float* const* fields, const int* const* status, uint8_t* const* valid, int gw, int gh,
                                                         int passes, char* scratch, size_t scratch_stride) {

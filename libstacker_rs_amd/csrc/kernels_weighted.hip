@@ -37,19 +37,6 @@ hipError_t launch_weighted_fold(const WarpArgs& a, const ClipArgs& c, int depth,
     return launch_fold<FoldWeighted<3>, FoldWeighted>(a, c, depth, a.dh, s);
 }
 
-// rows per thread: at least 8, and enough that an entry has about 1024 partials at most (the second launch adds them one
-// after the other)
-MomentsPlan moments_plan(int dw, int dh, int step) {
-    MomentsPlan p;
-    p.gw = (dw + step - 1) / step;
-    p.gh = (dh + step - 1) / step;
-    p.bx = (p.gw + 63) / 64;
-    const long long want = ((long long)p.bx * p.gh + 1023) / 1024;
-    p.reps = (int)(want < 8 ? 8 : want);
-    p.by = (p.gh + 4 * p.reps - 1) / (4 * p.reps);
-    return p;
-}
-
 hipError_t launch_overlap_moments(const WarpArgs& a, ClipArgs c, int depth, int step, double* moments, hipStream_t s) {
     if (a.n_frames < 2 || step < 1) return hipErrorInvalidValue;
     const MomentsPlan p = moments_plan(a.dw, a.dh, step);

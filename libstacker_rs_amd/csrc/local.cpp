@@ -15,31 +15,7 @@
 
 using namespace stk;
 
-// (the layout, the checks, the map pass and the fold are shared with mesh.cpp: context.h)
-// cn == 0: the map pass alone (no per-entry table, image or den plane)
-LocalLayout local_layout(size_t n_ptrs, int n_entries, int w, int h, int cn, size_t n_planes) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    LocalLayout L{};
-    L.fptrs = 0;
-    L.mptrs = up(std::max<size_t>(n_ptrs, 1) * sizeof(void*));
-    L.coef = L.mptrs + up(std::max<size_t>(n_ptrs, 1) * sizeof(void*));
-    L.image = L.coef + (cn ? up((size_t)std::max(n_entries, 1) * sizeof(stk_frame_weight)) : 0);
-    L.den = L.image + up((size_t)w * h * cn * sizeof(float));
-    L.planes = L.den + (cn ? up((size_t)w * h * sizeof(float)) : 0);
-    L.plane = up((size_t)w * h * sizeof(float));
-    L.total = L.planes + n_planes * L.plane;
-    return L;
-}
-
-stk_status local_reserve(stk_ctx* ctx, const LocalLayout& L, size_t n_planes) {
-    if (ctx->local.reserve(L.total) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, STK_HIP_ERROR, "local: device allocation of " + std::to_string(L.total) + " bytes failed (" +
-                                            std::to_string(n_planes) + " map planes of " + std::to_string(L.plane) + " bytes)");
-    }
-    return STK_OK;
-}
-
+// (the checks, the map pass and the fold are shared with mesh.cpp: context.h; the layout: workspace.h)
 stk_status local_validate(stk_ctx* ctx, const stk_local_params* p) {
     if (!p) return fail(ctx, STK_INVALID_PARAMS, "null local parameters");
     if (p->radius < 1 || p->radius > 15) return fail(ctx, STK_INVALID_PARAMS, "local: radius must be 1 .. 15");
@@ -106,33 +82,26 @@ stk_status local_fold(stk_ctx* ctx, const LocalLayout& L, const std::vector<stk_
                       int power, stk_image_f32* out, float* den_out, double* ms, const MeshFoldArgs* mesh) {
     const int w = spec.w, h = spec.h, cn = spec.cn, depth = spec.depth;
     char* base = ctx->local.as<char>();
-    const bool host = out->location != STK_DEVICE;
+    const CombineOutputs o(out, (float*)(base + L.image), (size_t)w * h * cn, {den_out, base + L.den, (size_t)w * h});
     const WarpArgs a = fold_warp_args(ctx, (int)coef.size(), local_border(spec));
     ClipArgs ca{};
     ca.coef = (const stk_frame_weight*)(base + L.coef);
     ca.coverage = 1;
-    ca.out = host ? (float*)(base + L.image) : out->data;
+    ca.out = o.image();
     ca.out_stride = (size_t)w * cn;
-    ca.den = den_out ? (host ? (float*)(base + L.den) : den_out) : nullptr;
+    ca.den = o.side<float>(0);
     ca.den_stride = (size_t)w;
     ca.maps = (const float* const*)(base + L.mptrs);
     ca.map_stride = (size_t)w;
     ca.floor = floor;
     ca.power = power;
-    HIP_TRY(hipMemcpyAsync(base + L.coef, coef.data(), coef.size() * sizeof(stk_frame_weight), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    stk_status st = records_upload(ctx, base + L.coef, coef);
+    if (st || (st = combine_begin(ctx))) return st;
     if (mesh) {
         mesh_fold_clip_args(*mesh, ca);
         HIP_TRY(launch_mesh_fold(a, ca, depth, true, ctx->stream));
     } else HIP_TRY(launch_local_fold(a, ca, depth, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    if (host) {
-        HIP_TRY(hipMemcpyAsync(out->data, ca.out, (size_t)w * h * cn * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (den_out) HIP_TRY(hipMemcpyAsync(den_out, ca.den, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms, &o);
 }
 
 namespace {
@@ -154,7 +123,7 @@ stk_status local_match_reserve(stk_ctx* ctx, const stk_frames* frames, LocalLayo
     (void)hipSetDevice(ctx->device);
     const int n = frames->n;
     *L = local_layout((size_t)n, n, frames->width, frames->height, frames->channels, (size_t)n);
-    return local_reserve(ctx, *L, (size_t)n);
+    return workspace_reserve(ctx, ctx->local, L->total, "local");
 }
 
 // and their combine over the kept frames (`dev`: the resident full-size frames by frame index): map pass, records, fold
@@ -169,11 +138,9 @@ CombineFinish local_match_finish(stk_ctx* ctx, const LocalLayout& L, int n, cons
         for (int k = 0; k < ne; k++) { fptr[k] = dev[table.frame[k]]; mptr[k] = (float*)(base + L.planes + (size_t)k * L.plane); }
         stk_status st = local_maps_enqueue(ctx, L, fptr, mptr);
         if (st) return st;
-        HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+        if ((st = combine_begin(ctx))) return st;
         if ((st = local_maps_launch(ctx, L, 0, (size_t)ne, spec.cn, spec.w, spec.h, spec.src_row_bytes, lp))) return st;
-        HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
+        if ((st = combine_end(ctx, ms))) return st;
         std::vector<stk_frame_weight> coef;
         if ((st = weighted_match_records(ctx, n, table, spec, p, weights, coef, applied, ms))) return st;
         return local_fold(ctx, L, coef, spec, lp->floor, lp->power, out, den_out, ms);
@@ -202,11 +169,11 @@ stk_status stk_local_sharpness(stk_ctx* ctx, const stk_frames* frames, const stk
     if (host) {
         const size_t budget = std::max<size_t>(ctx->frames.cap, (size_t)ctx->opt_upload_batch * fb);
         batch = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / fb));
-        HIP_TRY(ctx->frames.reserve(fb * (size_t)batch));
+        if ((st = workspace_reserve(ctx, ctx->frames, fb * (size_t)batch, "local sharpness frames"))) return st;
     }
     const size_t n_ptrs = host ? (size_t)batch : (size_t)n;
     const LocalLayout Lp = local_layout(n_ptrs, 0, w, h, 0, host ? (size_t)batch : 0);
-    if ((st = local_reserve(ctx, Lp, host ? (size_t)batch : 0))) return st;
+    if ((st = workspace_reserve(ctx, ctx->local, Lp.total, "local"))) return st;
     char* base = ctx->local.as<char>();
     std::vector<const void*> fptr(n_ptrs);                         // (outlive the copies: the call synchronises below)
     std::vector<float*> mptr(n_ptrs);
@@ -269,7 +236,7 @@ stk_status local_weighted_stack_impl(stk_ctx* ctx, const stk_frames* frames, con
     const int ne = table.size();
     const bool host = frames->location != STK_DEVICE;       // the planes are where the frames are
     const LocalLayout L = local_layout((size_t)ne, ne, w, h, cn, host ? (size_t)ne : 0);
-    if ((st = local_reserve(ctx, L, host ? (size_t)ne : 0))) return st;
+    if ((st = workspace_reserve(ctx, ctx->local, L.total, "local"))) return st;
     char* base = ctx->local.as<char>();
     std::vector<const float*> mptr(ne);
     for (int k = 0; k < ne; k++) {

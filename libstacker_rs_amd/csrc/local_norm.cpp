@@ -25,21 +25,9 @@ void norm_fold_clip_args(const NormFoldArgs& n, ClipArgs& ca) {
 
 namespace {
 
-bool norm_step_ok(int step) { return step >= 8 && step <= 256 && (step & (step - 1)) == 0; }
-
-struct NormGrid { int step, shift, gw, gh, cw, ch; size_t cells() const { return (size_t)cw * ch; } size_t nodes() const { return (size_t)gw * gh; } };
-NormGrid norm_grid(int w, int h, int step) {
-    NormGrid g{};
-    g.step = step;
-    while ((1 << g.shift) < step) g.shift++;
-    g.gw = (w - 1 + step - 1) / step + 1; g.gh = (h - 1 + step - 1) / step + 1;      // stk_mesh_grid
-    g.cw = (w + step - 1) / step; g.ch = (h + step - 1) / step;
-    return g;
-}
-
 const char* norm_params_error(const stk_local_norm_params* p) {
     if (!p) return "null local normalisation parameters";
-    if (!norm_step_ok(p->step)) return "local normalisation: step must be 8, 16, 32, 64, 128 or 256";
+    if (!grid_step_ok(p->step)) return "local normalisation: step must be 8, 16, 32, 64, 128 or 256";
     if (p->stat_step < 0 || p->stat_step > 64) return "local normalisation: stat_step must be 0 .. 64";
     if (p->normalize < 0 || p->normalize > 3) return "local normalisation: normalize must be 0 .. 3";
     if (p->coverage < 0 || p->coverage > 1) return "local normalisation: coverage must be 0 or 1";
@@ -54,35 +42,9 @@ stk_status norm_validate(stk_ctx* ctx, const stk_local_norm_params* p) {
 }
 int norm_stat_step(const stk_local_norm_params* p) { return p->stat_step ? p->stat_step : 4; }
 
-struct NormLayout {
-    size_t ptrs, coef, image, den, cells, planes, plane, total;      // byte offsets into ctx->local; plane: bytes of one plane
-};
-// cells: the moments pass's records of n_entries - 1 entries; planes: one per entry
-NormLayout norm_layout(int n_entries, int w, int h, int cn, const NormGrid& g, bool cells, bool planes) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t ne = (size_t)std::max(n_entries, 1);
-    NormLayout L{};
-    L.ptrs = 0;
-    L.coef = up(ne * sizeof(void*));
-    L.image = L.coef + up(ne * sizeof(stk_frame_weight));
-    L.den = L.image + up((size_t)w * h * cn * sizeof(float));
-    L.cells = L.den + up((size_t)w * h * sizeof(float));
-    L.planes = L.cells + (cells ? up((ne - 1) * g.cells() * cn * 6 * sizeof(double)) : 0);
-    L.plane = up(g.nodes() * 2 * cn * sizeof(float));
-    L.total = L.planes + (planes ? ne * L.plane : 0);
-    return L;
-}
-stk_status norm_reserve(stk_ctx* ctx, const NormLayout& L) {
-    if (ctx->local.reserve(L.total) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, STK_HIP_ERROR, "local normalisation: device allocation of " + std::to_string(L.total) + " bytes failed");
-    }
-    return STK_OK;
-}
-
 // The cell moments pass over the n_entries entries of ctx->warpframes (uploaded for the w x h destination): (n_entries - 1)
 // x cells x cn x 6 doubles into `host`, entry 1 first. Synchronises; adds its device time to *ms.
-stk_status norm_moments(stk_ctx* ctx, const NormLayout& L, int n_entries, const FoldSpec& spec, const NormGrid& g, int stat_step,
+stk_status norm_moments(stk_ctx* ctx, const NormLayout& L, int n_entries, const FoldSpec& spec, const NodeGrid& g, int stat_step,
                         double* host, double* ms) {
     if (n_entries < 2) return STK_OK;
     if (n_entries - 1 > 65535) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: at most 65536 frames");
@@ -92,19 +54,15 @@ stk_status norm_moments(stk_ctx* ctx, const NormLayout& L, int n_entries, const 
     ca.cells = (double*)(base + L.cells);
     ca.step = stat_step;
     ca.cell_shift = g.shift; ca.cell_w = g.cw; ca.cell_h = g.ch;
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    const CombineOutputs o(host, ca.cells, (size_t)(n_entries - 1) * g.cells() * spec.cn * 6, sizeof(double));
+    if (stk_status st = combine_begin(ctx)) return st;
     HIP_TRY(launch_local_moments(a, ca, spec.depth, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    HIP_TRY(hipMemcpyAsync(host, ca.cells, (size_t)(n_entries - 1) * g.cells() * spec.cn * 6 * sizeof(double), hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms, &o);
 }
 
 // The planes of the table's entries (host memory, indexed like the table; null = none) into ctx->local with their pointer
 // table. Synchronises.
-stk_status norm_planes_upload(stk_ctx* ctx, const NormLayout& L, const std::vector<const float*>& planes, const NormGrid& g, int cn,
+stk_status norm_planes_upload(stk_ctx* ctx, const NormLayout& L, const std::vector<const float*>& planes, const NodeGrid& g, int cn,
                               NormFoldArgs* out) {
     char* base = ctx->local.as<char>();
     const size_t ne = planes.size();
@@ -127,27 +85,20 @@ stk_status norm_fold(stk_ctx* ctx, const NormLayout& L, const std::vector<stk_fr
                      const FoldSpec& spec, int coverage, stk_image_f32* out, float* den_out, double* ms) {
     const int w = spec.w, h = spec.h, cn = spec.cn;
     char* base = ctx->local.as<char>();
-    const bool host = out->location != STK_DEVICE;
+    const CombineOutputs o(out, (float*)(base + L.image), (size_t)w * h * cn, {den_out, base + L.den, (size_t)w * h});
     const WarpArgs a = fold_warp_args(ctx, (int)coef.size(), spec);
     ClipArgs ca{};
     ca.coef = (const stk_frame_weight*)(base + L.coef);
     ca.coverage = coverage;
-    ca.out = host ? (float*)(base + L.image) : out->data;
+    ca.out = o.image();
     ca.out_stride = (size_t)w * cn;
-    ca.den = den_out ? (host ? (float*)(base + L.den) : den_out) : nullptr;
+    ca.den = o.side<float>(0);
     ca.den_stride = (size_t)w;
     norm_fold_clip_args(nf, ca);
-    HIP_TRY(hipMemcpyAsync(base + L.coef, coef.data(), coef.size() * sizeof(stk_frame_weight), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    stk_status st = records_upload(ctx, base + L.coef, coef);
+    if (st || (st = combine_begin(ctx))) return st;
     HIP_TRY(launch_norm_fold(a, ca, spec.depth, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    if (host) {
-        HIP_TRY(hipMemcpyAsync(out->data, ca.out, (size_t)w * h * cn * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (den_out) HIP_TRY(hipMemcpyAsync(den_out, ca.den, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms, &o);
 }
 
 // the caller-held-warps forms of the two combines, after the combine's own checks: quantile == null is the mean
@@ -155,7 +106,7 @@ stk_status norm_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, c
                       const double* border_value, double alpha, const stk_quantile_params* quantile, const stk_frame_weight* per_frame,
                       const float* const* norm, int step, int coverage, stk_image_f32* out, float* den_out, int32_t* counts) {
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
-    if (!norm_step_ok(step)) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: step must be 8, 16, 32, 64, 128 or 256");
+    if (!grid_step_ok(step)) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: step must be 8, 16, 32, 64, 128 or 256");
     stk_status st = combine_check_out(ctx, out, frames);
     if (st) return st;
     const int w = frames->width, h = frames->height, cn = frames->channels;
@@ -168,9 +119,9 @@ stk_status norm_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, c
     if ((st = weighted_check_coefs(ctx, coef, cn))) return st;
     if ((st = entry_table_begin(ctx, frames, table, is_affine))) return st;
     const int ne = table.size();
-    const NormGrid g = norm_grid(w, h, step);
+    const NodeGrid g = node_grid(w, h, step);
     const NormLayout L = norm_layout(ne, w, h, cn, g, false, true);
-    if ((st = norm_reserve(ctx, L))) return st;
+    if ((st = workspace_reserve(ctx, ctx->local, L.total, "local normalisation"))) return st;
     std::vector<const float*> planes(ne, nullptr);
     for (int k = 0; k < ne; k++) planes[k] = norm ? norm[table.frame[k]] : nullptr;
     NormFoldArgs nf{};
@@ -201,9 +152,9 @@ stk_status norm_match_check(stk_ctx* ctx, const stk_frames* frames, const stk_lo
 // their workspace (the plain call's mean lands in its image, unused), sized for all n frames
 stk_status norm_match_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_local_norm_params* p, NormLayout* L) {
     (void)hipSetDevice(ctx->device);
-    const NormGrid g = norm_grid(frames->width, frames->height, p->step);
+    const NodeGrid g = node_grid(frames->width, frames->height, p->step);
     *L = norm_layout(frames->n, frames->width, frames->height, frames->channels, g, true, true);
-    return norm_reserve(ctx, *L);
+    return workspace_reserve(ctx, ctx->local, L->total, "local normalisation");
 }
 
 // and their combine over the kept frames: cell moments, estimator, planes, then the mean or the quantile
@@ -212,7 +163,7 @@ CombineFinish norm_match_finish(stk_ctx* ctx, const NormLayout& L, int n, const 
                                 stk_frame_weight* applied) {
     return [=](const EntryTable& table, const std::vector<const void*>&, const FoldSpec& spec, const stk_frame_stats*, double* ms) {
         const int ne = table.size(), cn = spec.cn;
-        const NormGrid g = norm_grid(spec.w, spec.h, p->step);
+        const NodeGrid g = node_grid(spec.w, spec.h, p->step);
         const size_t rec = g.cells() * cn * 6, pl = g.nodes() * 2 * cn;
         std::vector<double> mom((size_t)std::max(ne - 1, 0) * rec);
         stk_status st = norm_moments(ctx, L, ne, spec, g, norm_stat_step(p), mom.data(), ms);
@@ -250,7 +201,7 @@ stk_status stk_local_norm_estimate(int32_t width, int32_t height, int32_t channe
     if (norm_params_error(p) || width <= 0 || height <= 0 || (channels != 1 && channels != 3 && channels != 4) || !cells || !plane)
         return STK_INVALID_PARAMS;
     const int cn = channels;
-    const NormGrid g = norm_grid(width, height, p->step);
+    const NodeGrid g = node_grid(width, height, p->step);
     const int gw = g.gw, gh = g.gh, nn = gw * gh;
     const double min_count = (double)(p->min_count ? p->min_count : 16);
     // the global moments: all cells in row-major order
@@ -333,7 +284,7 @@ stk_status stk_local_moments(stk_ctx* ctx, const stk_frames* frames, const doubl
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
     if (!moments) return fail(ctx, STK_INVALID_PARAMS, "null moments");
     if ((st = weighted_check_border(ctx, border_mode, border_value, 0))) return st;
-    if (!norm_step_ok(step)) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: step must be 8, 16, 32, 64, 128 or 256");
+    if (!grid_step_ok(step)) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: step must be 8, 16, 32, 64, 128 or 256");
     if (stat_step < 1 || stat_step > 64) return fail(ctx, STK_INVALID_PARAMS, "local moments: stat_step must be 1 .. 64");
     if (include && !include[0]) return fail(ctx, STK_INVALID_PARAMS, "local moments: frame 0 must be included");
     const int n = frames->n, cn = frames->channels;
@@ -343,9 +294,9 @@ stk_status stk_local_moments(stk_ctx* ctx, const stk_frames* frames, const doubl
     if (table.size() - 1 > 65535) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: at most 65536 frames");
     if ((st = entry_table_begin(ctx, frames, table, is_affine))) return st;
     const int ne = table.size();
-    const NormGrid g = norm_grid(frames->width, frames->height, step);
+    const NodeGrid g = node_grid(frames->width, frames->height, step);
     const NormLayout L = norm_layout(ne, frames->width, frames->height, cn, g, true, false);
-    if ((st = norm_reserve(ctx, L))) return st;
+    if ((st = workspace_reserve(ctx, ctx->local, L.total, "local normalisation"))) return st;
     const size_t rec = g.cells() * cn * 6;
     std::vector<double> mom((size_t)std::max(ne - 1, 0) * rec);
     double ms = 0.0;

@@ -18,51 +18,17 @@ using namespace stk;
 
 namespace {
 
-struct MeshLayout {
-    size_t tptrs, fptrs, sptrs, fields, status, scratch, image, fplane, splane, cplane, total;   // byte offsets; *plane: bytes of one plane
-};
-
-MeshLayout mesh_layout(size_t n_ptrs, size_t n_fields, size_t n_status, size_t n_scratch, int gw, int gh, size_t image_floats) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t nn = (size_t)gw * gh, pt = up(std::max<size_t>(n_ptrs, 1) * sizeof(void*));
-    MeshLayout L{};
-    L.fplane = up(nn * 2 * sizeof(float));
-    L.splane = up(nn * sizeof(int32_t));
-    L.cplane = mesh_fill_scratch_bytes(gw, gh);
-    L.tptrs = 0;
-    L.fptrs = pt;
-    L.sptrs = 2 * pt;
-    L.fields = 3 * pt;
-    L.status = L.fields + n_fields * L.fplane;
-    L.scratch = L.status + n_status * L.splane;
-    L.image = L.scratch + n_scratch * L.cplane;
-    L.total = L.image + up(image_floats * sizeof(float));
-    return L;
-}
-
-// total: the bytes of the layout with what follows it (the pyramid form's PyrLayout), 0 = the layout alone
-stk_status mesh_reserve(stk_ctx* ctx, const MeshLayout& L, size_t total = 0) {
-    total = std::max(total, L.total);
-    if (ctx->mesh.reserve(total) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, STK_HIP_ERROR, "mesh: device allocation of " + std::to_string(total) + " bytes failed (field planes of " +
-                                            std::to_string(L.fplane) + " bytes)");
-    }
-    return STK_OK;
-}
-
 stk_status local_align_impl(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
                             const stk_mesh_params* p, int levels, float* const* fields, int32_t* const* status);
 
-bool mesh_step_ok(int step) { return step >= 8 && step <= 256 && (step & (step - 1)) == 0; }
 void mesh_grid_of(int w, int h, int step, int* gw, int* gh) {
-    *gw = (w - 1 + step - 1) / step + 1;
-    *gh = (h - 1 + step - 1) / step + 1;
+    const NodeGrid g = node_grid(w, h, step);
+    *gw = g.gw; *gh = g.gh;
 }
 
 stk_status mesh_validate(stk_ctx* ctx, const stk_mesh_params* p) {
     if (!p) return fail(ctx, STK_INVALID_PARAMS, "null mesh parameters");
-    if (!mesh_step_ok(p->step)) return fail(ctx, STK_INVALID_PARAMS, "mesh: step must be 8, 16, 32, 64, 128 or 256");
+    if (!grid_step_ok(p->step)) return fail(ctx, STK_INVALID_PARAMS, "mesh: step must be 8, 16, 32, 64, 128 or 256");
     if (p->radius < 2 || p->radius > 32) return fail(ctx, STK_INVALID_PARAMS, "mesh: radius must be 2 .. 32");
     if (p->max_iters < 1 || p->max_iters > 32) return fail(ctx, STK_INVALID_PARAMS, "mesh: max_iters must be 1 .. 32");
     if (!std::isfinite(p->epsilon) || p->epsilon < 0.0f) return fail(ctx, STK_INVALID_PARAMS, "mesh: epsilon must be finite and >= 0");
@@ -101,58 +67,32 @@ stk_status mesh_align_entries(stk_ctx* ctx, const MeshLayout& L, int ne, int w, 
     a.eps2 = (double)p->epsilon * (double)p->epsilon;
     a.max_shift2 = (double)p->max_shift * (double)p->max_shift;
     a.min_eig4 = 4.0 * (double)p->min_eig;
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if (stk_status st = combine_begin(ctx)) return st;
     HIP_TRY(launch_mesh_lk(a, cn, ctx->stream));
     if (p->fill > 0)
         HIP_TRY(launch_mesh_fill(a.fields, (const int* const*)a.status, ne, gw, gh, p->fill, base + L.scratch, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));          // the pointer vectors leave scope
-    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms);                         // (synchronises: the pointer vectors leave scope)
 }
 
 // The mesh mean fold over the ne entries of ctx->warpframes with the field table `mf`: sums in fold order, then x
 // (float)(1.0 / ne). `image`: a w x h x cn f32 device buffer for a host output. Synchronises; adds its device time to *ms.
 stk_status mesh_mean_fold(stk_ctx* ctx, int ne, const FoldSpec& spec, const MeshFoldArgs& mf, float* image, stk_image_f32* out, double* ms) {
-    const bool host = out->location != STK_DEVICE;
     const size_t nel = (size_t)spec.w * spec.h * spec.cn;
+    const CombineOutputs o(out, image, nel);
     WarpArgs a = fold_warp_args(ctx, ne, spec);
-    a.acc = host ? image : out->data;
+    a.acc = o.image();
     a.acc_stride = (size_t)spec.w * spec.cn;
     a.accumulate = 0;
     ClipArgs ca{};
     mesh_fold_clip_args(mf, ca);
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if (stk_status st = combine_begin(ctx)) return st;
     HIP_TRY(launch_mesh_fold(a, ca, spec.depth, false, ctx->stream));
     HIP_TRY(launch_scale(a.acc, a.acc, nel, (float)(1.0 / (double)ne), ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    if (host) HIP_TRY(hipMemcpyAsync(out->data, a.acc, nel * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms, &o);
 }
 
 // ---- the coarse-to-fine form (include/stacker.h, "coarse-to-fine local alignment") -------------------------------------
-// What it keeps in ctx->mesh behind a MeshLayout, per table entry (entry 0 = frame 0): the validity bytes' pointer table and
-// planes, the pyramid planes (levels 1 .. levels - 1, mesh_pyr_offset) and one frame table per level above 0.
-struct PyrLayout {
-    size_t vptrs, valid, vplane, planes, pstride, tables, tbytes, total;     // byte offsets; vplane, pstride, tbytes: bytes of one
-};
-
-PyrLayout pyr_layout(size_t base, size_t n_entries, int gw, int gh, int w, int h, int levels) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    PyrLayout P{};
-    P.vptrs = up(base);
-    P.vplane = up((size_t)gw * gh);
-    P.valid = P.vptrs + up(n_entries * sizeof(void*));
-    P.pstride = up(mesh_pyr_offset(w, h, levels));
-    P.planes = P.valid + n_entries * P.vplane;
-    P.tbytes = up(n_entries * sizeof(WarpFrame));
-    P.tables = P.planes + n_entries * P.pstride;
-    P.total = P.tables + (size_t)(levels - 1) * P.tbytes;
-    return P;
-}
-
+// What it keeps in ctx->mesh behind a MeshLayout: PyrLayout (workspace.h).
 stk_status pyr_validate(stk_ctx* ctx, const stk_frames* f, const stk_mesh_params* p, int levels) {
     if (levels < 1 || levels > 4) return fail(ctx, STK_INVALID_PARAMS, "mesh: levels must be 1 .. 4");
     if ((p->step >> (levels - 1)) < 4) return fail(ctx, STK_INVALID_PARAMS, "mesh: step >> (levels - 1) must be at least 4");
@@ -206,7 +146,7 @@ stk_status mesh_align_entries_pyr(stk_ctx* ctx, const MeshLayout& L, const PyrLa
         HIP_TRY(hipMemcpyAsync(base + P.tables + (size_t)(l - 1) * P.tbytes, &lt[(size_t)(l - 1) * ne], (size_t)ne * sizeof(WarpFrame),
                                hipMemcpyHostToDevice, ctx->stream));
     }
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if (stk_status st = combine_begin(ctx)) return st;
     MeshPyrArgs pa{};
     pa.frames = ctx->warpframes.as<WarpFrame>();
     pa.planes = (uint8_t*)(base + P.planes);
@@ -285,11 +225,11 @@ stk_status mesh_match_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_
     mesh_grid_of(w, h, mp->step, &gw, &gh);
     *L = mesh_layout((size_t)n, (size_t)n, (size_t)n, (size_t)n, gw, gh, (size_t)w * h * cn);
     if (levels > 0) *P = pyr_layout(L->total, (size_t)n, gw, gh, w, h, levels);
-    stk_status st = mesh_reserve(ctx, *L, levels > 0 ? P->total : 0);
+    stk_status st = workspace_reserve(ctx, ctx->mesh, levels > 0 ? P->total : L->total, "mesh");
     if (st) return st;
     if (lp) {
         const LocalLayout LL = local_layout((size_t)n, n, w, h, cn, (size_t)n);
-        if ((st = local_reserve(ctx, LL, (size_t)n))) return st;
+        if ((st = workspace_reserve(ctx, ctx->local, LL.total, "local"))) return st;
     }
     return STK_OK;
 }
@@ -311,11 +251,9 @@ CombineFinish mesh_match_finish(stk_ctx* ctx, const MeshLayout& L, const stk_mes
         std::vector<float*> mptr(ne);
         for (int k = 0; k < ne; k++) { fptr[k] = dev[table.frame[k]]; mptr[k] = (float*)(lbase + LL.planes + (size_t)k * LL.plane); }
         if ((st = local_maps_enqueue(ctx, LL, fptr, mptr))) return st;
-        HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+        if ((st = combine_begin(ctx))) return st;
         if ((st = local_maps_launch(ctx, LL, 0, (size_t)ne, cn, w, h, rb, lp))) return st;
-        HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
+        if ((st = combine_end(ctx, ms))) return st;
         return local_fold(ctx, LL, std::vector<stk_frame_weight>(ne, unit_record()), spec, lp->floor, lp->power, out, nullptr, ms, &mf);
     };
 }
@@ -332,7 +270,7 @@ void mesh_fold_clip_args(const MeshFoldArgs& m, ClipArgs& ca) {
 }
 
 stk_status mesh_check_fold(stk_ctx* ctx, int step) {
-    if (!mesh_step_ok(step)) return fail(ctx, STK_INVALID_PARAMS, "mesh: step must be 8, 16, 32, 64, 128 or 256");
+    if (!grid_step_ok(step)) return fail(ctx, STK_INVALID_PARAMS, "mesh: step must be 8, 16, 32, 64, 128 or 256");
     if (ctx->opt_subpixel_bits != 0)
         return fail(ctx, STK_INVALID_PARAMS, "mesh: the displaced coordinates are exact ones: warp_subpixel_bits must be 0");
     if (ctx->opt_interp == STK_INTER_CUBIC)
@@ -350,7 +288,7 @@ stk_status mesh_match_fields_reserve(stk_ctx* ctx, const stk_frames* frames, con
     const size_t n = (size_t)frames->n;
     int gw, gh;
     mesh_grid_of(frames->width, frames->height, mp->step, &gw, &gh);
-    return mesh_reserve(ctx, mesh_layout(n, n, n, n, gw, gh, 0));
+    return workspace_reserve(ctx, ctx->mesh, mesh_layout(n, n, n, n, gw, gh, 0).total, "mesh");
 }
 
 stk_status mesh_match_fields(stk_ctx* ctx, const stk_frames* frames, int n_entries, int is_affine, const stk_mesh_params* mp,
@@ -369,7 +307,7 @@ stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const EntryTa
     int gw, gh;
     mesh_grid_of(frames->width, frames->height, step, &gw, &gh);
     const MeshLayout L = mesh_layout((size_t)ne, host ? (size_t)ne : 0, 0, 0, gw, gh, (size_t)frames->width * frames->height * frames->channels);
-    stk_status st = mesh_reserve(ctx, L);
+    stk_status st = workspace_reserve(ctx, ctx->mesh, L.total, "mesh");
     if (st) return st;
     char* base = ctx->mesh.as<char>();
     std::vector<const float*> ptr(ne, nullptr);
@@ -391,7 +329,7 @@ stk_status mesh_fold_table(stk_ctx* ctx, const stk_frames* frames, const EntryTa
 extern "C" {
 
 stk_status stk_mesh_grid(int32_t width, int32_t height, int32_t step, int32_t* gw, int32_t* gh) {
-    if (width <= 0 || height <= 0 || !mesh_step_ok(step) || !gw || !gh) return STK_INVALID_PARAMS;
+    if (width <= 0 || height <= 0 || !grid_step_ok(step) || !gw || !gh) return STK_INVALID_PARAMS;
     mesh_grid_of(width, height, step, gw, gh);
     return STK_OK;
 }
@@ -427,15 +365,12 @@ stk_status stk_grey_pyramid(stk_ctx* ctx, const stk_frames* frame, int32_t level
     const bool host = frame->location == STK_HOST;
     const void* src = frame->data[0];
     if (host) {
-        HIP_TRY(ctx->frames.reserve(fb));
+        if ((st = workspace_reserve(ctx, ctx->frames, fb, "grey pyramid frame"))) return st;
         HIP_TRY(hipMemcpyAsync(ctx->frames.p, frame->data[0], frame_copy_bytes(frame), hipMemcpyHostToDevice, ctx->stream));
         src = ctx->frames.p;
     }
     const size_t bytes = mesh_pyr_offset(w, h, levels);
-    if (ctx->mesh.reserve(bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, STK_HIP_ERROR, "mesh: device allocation of " + std::to_string(bytes) + " bytes failed (pyramid planes)");
-    }
+    if ((st = workspace_reserve(ctx, ctx->mesh, bytes, "mesh pyramid planes"))) return st;
     std::vector<WarpFrame> wf(1);
     make_warp_frame(wf[0], src, IDENTITY3, 1);
     if ((st = warp_table_upload(ctx, wf, rb, w, h, 1))) return st;
@@ -443,7 +378,7 @@ stk_status stk_grey_pyramid(stk_ctx* ctx, const stk_frames* frame, int32_t level
     pa.frames = ctx->warpframes.as<WarpFrame>();
     pa.planes = ctx->mesh.as<uint8_t>();
     pa.entry_stride = bytes; pa.stride = rb; pa.first = 0; pa.n = 1; pa.w = w; pa.h = h; pa.levels = levels;
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if ((st = combine_begin(ctx))) return st;
     HIP_TRY(launch_mesh_pyr(pa, cn, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
     for (int l = 1; l < levels; l++)
@@ -518,13 +453,13 @@ stk_status local_align_impl(stk_ctx* ctx, const stk_frames* frames, const double
     if (host) {
         const size_t budget = std::max<size_t>(ctx->frames.cap, (size_t)ctx->opt_upload_batch * fb);
         batch = (int)std::min<size_t>(moving.size(), std::max<size_t>(2, budget / fb) - 1);
-        HIP_TRY(ctx->frames.reserve(fb * (size_t)(batch + 1)));
+        if ((st = workspace_reserve(ctx, ctx->frames, fb * (size_t)(batch + 1), "local alignment frames"))) return st;
         HIP_TRY(hipMemcpyAsync(ctx->frames.p, frames->data[0], frame_copy_bytes(frames), hipMemcpyHostToDevice, ctx->stream));
     }
     const MeshLayout L = mesh_layout((size_t)batch + 1, host ? (size_t)batch : 0, (size_t)batch, (size_t)batch, gw, gh, 0);
     PyrLayout P{};
     if (levels > 0) P = pyr_layout(L.total, (size_t)batch + 1, gw, gh, w, h, levels);
-    if ((st = mesh_reserve(ctx, L, P.total))) return st;
+    if ((st = workspace_reserve(ctx, ctx->mesh, std::max(L.total, P.total), "mesh"))) return st;
     char* base = ctx->mesh.as<char>();
     double ms = 0.0, pyr_ms = 0.0;
     for (size_t b0 = 0; b0 < moving.size(); b0 += (size_t)batch) {

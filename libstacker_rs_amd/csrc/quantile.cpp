@@ -36,9 +36,6 @@ stk_status quantile_check_count(stk_ctx* ctx, int n) {
     return STK_OK;
 }
 
-// floats of the image in front of the band (rounded up to 256 bytes: the band's rows start aligned)
-size_t quantile_image_floats(int w, int h, int cn) { return ((size_t)w * h * cn + 63) & ~(size_t)63; }
-
 size_t quantile_band_rows(const stk_ctx* ctx, int n, int w, int h, int cn) {
     const size_t row = (size_t)n * w * cn * sizeof(float);
     size_t R = std::max<size_t>(1, QUANTILE_BAND_BYTES / row);
@@ -46,11 +43,10 @@ size_t quantile_band_rows(const stk_ctx* ctx, int n, int w, int h, int cn) {
     return std::min<size_t>(R, (size_t)h);
 }
 
-// room for the image and, n > 0, the band of an n-frame w x h x cn stack
-stk_status quantile_reserve(stk_ctx* ctx, int n, int w, int h, int cn) {
-    const size_t R = n > 0 ? quantile_band_rows(ctx, n, w, h, cn) : 0;
-    HIP_TRY(ctx->quantile.reserve((quantile_image_floats(w, h, cn) + R * n * w * cn) * sizeof(float)));
-    return STK_OK;
+stk_status quantile_reserve(stk_ctx* ctx, int n, int w, int h, int cn, bool counts, QuantileLayout* L) {
+    const QuantileLayout Q = quantile_layout(n, n > 0 ? quantile_band_rows(ctx, n, w, h, cn) : 0, w, h, cn, counts);
+    if (L) *L = Q;
+    return workspace_reserve(ctx, ctx->quantile, Q.total, "quantile");
 }
 
 namespace {
@@ -62,12 +58,12 @@ stk_status quantile_bands(stk_ctx* ctx, int n_frames, const FoldSpec& spec, cons
     const int w = spec.w, h = spec.h, cn = spec.cn, depth = spec.depth;
     stk_status st = quantile_check_count(ctx, n_frames);
     if (st) return st;
-    if ((st = quantile_reserve(ctx, n_frames, w, h, cn))) return st;
+    QuantileLayout L;
+    if ((st = quantile_reserve(ctx, n_frames, w, h, cn, false, &L))) return st;
     const size_t R = quantile_band_rows(ctx, n_frames, w, h, cn), row = (size_t)w * cn;
-    float* img = ctx->quantile.as<float>();
-    float* band = img + quantile_image_floats(w, h, cn);
-    const bool host = out->location != STK_DEVICE;
-    float* dst = host ? img : out->data;
+    float* band = (float*)(ctx->quantile.as<char>() + L.band);
+    const CombineOutputs o(out, (float*)(ctx->quantile.as<char>() + L.image), (size_t)h * row);
+    float* dst = o.image();
     // j and g in f32, each operation rounded on its own, as the definition states them
     const float vi = (float)(n_frames - 1) * p->quantile;
     const float jf = std::floor(vi);
@@ -77,7 +73,7 @@ stk_status quantile_bands(stk_ctx* ctx, int n_frames, const FoldSpec& spec, cons
     ClipArgs ca{};
     ca.band = band;
     ca.plane_stride = row;
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if ((st = combine_begin(ctx))) return st;
     for (size_t y0 = 0; y0 < (size_t)h; y0 += R) {
         const size_t rows = std::min(R, (size_t)h - y0);
         ca.y0 = (int)y0; ca.band_rows = (int)rows;
@@ -85,11 +81,7 @@ stk_status quantile_bands(stk_ctx* ctx, int n_frames, const FoldSpec& spec, cons
         HIP_TRY(launch_quantile_store(a, ca, depth, ctx->stream));
         HIP_TRY(launch_quantile_select(band, rows * row, n_frames, j, g, dst + y0 * row, ctx->stream));
     }
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    if (host) HIP_TRY(hipMemcpyAsync(out->data, img, (size_t)h * row * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms, &o);
 }
 
 // the checks and the workspace of the two whole-stack forms: the image only (the plain call's mean lands in front of the
@@ -101,7 +93,7 @@ stk_status quantile_match_begin(stk_ctx* ctx, const stk_frames* frames, const st
     if ((st = combine_check_out(ctx, out, frames))) return st;
     if ((st = quantile_check_count(ctx, frames->n))) return st;
     (void)hipSetDevice(ctx->device);
-    return quantile_reserve(ctx, 0, frames->width, frames->height, frames->channels);
+    return quantile_reserve(ctx, 0, frames->width, frames->height, frames->channels, false, nullptr);
 }
 
 // and their combine over the kept frames

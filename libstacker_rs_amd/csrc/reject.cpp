@@ -12,28 +12,6 @@
 
 using namespace stk;
 
-RejectLayout reject_layout(int n_entries, int sw, int sh, int cn, bool clean, bool counts, size_t n_planes) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t ne = (size_t)(n_entries > 0 ? n_entries : 1);
-    RejectLayout L{};
-    L.entries = 0;
-    L.tallies = up(ne * sizeof(RejectEntry));
-    L.clean = L.tallies + up(ne * 2 * sizeof(unsigned long long));
-    L.counts = L.clean + (clean ? up((size_t)sw * sh * cn * sizeof(float)) : 0);
-    L.planes = L.counts + (counts ? up((size_t)sw * sh * sizeof(int32_t)) : 0);
-    L.plane = up((size_t)sw * sh * sizeof(float));
-    L.total = L.planes + n_planes * L.plane;
-    return L;
-}
-
-stk_status reject_reserve(stk_ctx* ctx, const RejectLayout& L) {
-    if (ctx->reject.reserve(L.total) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, STK_HIP_ERROR, "reject maps: device allocation of " + std::to_string(L.total) + " bytes failed");
-    }
-    return STK_OK;
-}
-
 stk_status reject_validate(stk_ctx* ctx, const stk_reject_params* p) {
     if (!p) return fail(ctx, STK_INVALID_PARAMS, "null reject parameters");
     if (ctx->opt_subpixel_bits != 0)
@@ -86,17 +64,16 @@ stk_status reject_run(stk_ctx* ctx, const RejectLayout& L, const stk_frames* fra
     a.snr1 = p->snr1; a.snr2 = p->snr2; a.scale1 = p->scale1; a.scale2 = p->scale2;
     a.rn2 = p->read_noise * p->read_noise; a.pg = p->poisson_gain;
     a.tallies = tallies;
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
-    HIP_TRY(launch_reject(a, frames->depth, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
     std::vector<unsigned long long> host((size_t)ne * 2);
-    HIP_TRY(hipMemcpyAsync(host.data(), tallies, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));          // the host tables leave scope
+    const CombineOutputs o(host.data(), tallies, host.size(), sizeof(unsigned long long));
+    stk_status st = combine_begin(ctx);
+    if (st) return st;
+    HIP_TRY(launch_reject(a, frames->depth, ctx->stream));
+    if ((st = combine_end(ctx, ms, &o))) return st;     // (synchronises: the host tables leave scope)
     for (int k = 0; k < ne; k++) {
         if (rejected) rejected[k] = (int64_t)host[2 * (size_t)k];
         if (judged) judged[k] = (int64_t)host[2 * (size_t)k + 1];
     }
-    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
     return STK_OK;
 }
 
@@ -132,7 +109,7 @@ stk_status stk_reject_maps(stk_ctx* ctx, const stk_frames* frames, const double*
     timing_begin(ctx);
     // host: the clean image, the counts, the input planes and the output planes are staged; device: the in-place planes
     const RejectLayout L = reject_layout(ne, sw, sh, cn, host, host && clean_counts, host ? n_in + (size_t)ne : n_alias);
-    if ((st = reject_reserve(ctx, L))) return st;
+    if ((st = workspace_reserve(ctx, ctx->reject, L.total, "reject maps"))) return st;
     std::vector<const void*> dev;
     if ((st = resolve_frames(ctx, frames, dev))) return st;
     char* base = ctx->reject.as<char>();

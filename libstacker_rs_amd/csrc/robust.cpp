@@ -27,9 +27,8 @@ stk_status robust_check_border(stk_ctx* ctx, int border_mode, int coverage) {
 
 // the record table into ctx->coef (asynchronous: `coef` must outlive the copy)
 stk_status coef_upload(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef) {
-    HIP_TRY(ctx->coef.reserve(coef.size() * sizeof(stk_frame_weight)));
-    HIP_TRY(hipMemcpyAsync(ctx->coef.p, coef.data(), coef.size() * sizeof(stk_frame_weight), hipMemcpyHostToDevice, ctx->stream));
-    return STK_OK;
+    stk_status st = workspace_reserve(ctx, ctx->coef, coef.size() * sizeof(stk_frame_weight), "record table");
+    return st ? st : records_upload(ctx, ctx->coef.p, coef);
 }
 
 // The weighted clip over the entries of ctx->warpframes with the records `coef`: the centre pass, then iterations + 1
@@ -38,24 +37,25 @@ stk_status clip_passes_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight
                                 const stk_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms) {
     const int w = spec.w, cn = spec.cn, depth = spec.depth;
     const size_t nel = (size_t)w * spec.h * cn;
-    HIP_TRY(ctx->clip.reserve(3 * nel * sizeof(float)));
-    float* c = ctx->clip.as<float>();
-    const WarpArgs a = fold_warp_args(ctx, (int)coef.size(), spec);
-    stk_status st = coef_upload(ctx, coef);
+    const ClipLayout L = clip_layout(nel);
+    stk_status st = workspace_reserve(ctx, ctx->clip, L.total, "sigma clipping");
     if (st) return st;
-    const bool host = out->location != STK_DEVICE;
+    char* base = ctx->clip.as<char>();
+    const WarpArgs a = fold_warp_args(ctx, (int)coef.size(), spec);
+    if ((st = coef_upload(ctx, coef))) return st;
     ClipArgs ca{};
-    ca.c = c; ca.L = c + nel; ca.U = c + 2 * nel;
+    ca.c = (float*)(base + L.c); ca.L = (float*)(base + L.L); ca.U = (float*)(base + L.U);
     ca.plane_stride = (size_t)w * cn;
     // a host output goes through the planes themselves: each thread reads its c, L, U before it writes out / counts / kept
-    ca.out = host ? c : out->data;
+    const CombineOutputs o(out, ca.c, nel, {counts, ca.L, nel}, {kept, ca.U, nel});
+    ca.out = o.image();
     ca.out_stride = (size_t)w * cn;
-    ca.counts = counts ? (host ? (int*)ca.L : counts) : nullptr;
-    ca.kept = kept ? (host ? ca.U : kept) : nullptr;
+    ca.counts = o.side<int>(0);
+    ca.kept = o.side<float>(1);
     ca.kappa_low = p->kappa_low; ca.kappa_high = p->kappa_high;
     ca.coef = ctx->coef.as<stk_frame_weight>();
     ca.coverage = coverage;
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if ((st = combine_begin(ctx))) return st;
     ca.centre = 1; ca.first = 1; ca.last = 0;
     HIP_TRY(launch_clip_pass_weighted(a, ca, depth, ctx->stream));
     ca.centre = 0;
@@ -64,15 +64,7 @@ stk_status clip_passes_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight
         ca.last = t == p->iterations + 1;
         HIP_TRY(launch_clip_pass_weighted(a, ca, depth, ctx->stream));
     }
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    if (host) {
-        HIP_TRY(hipMemcpyAsync(out->data, c, nel * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (counts) HIP_TRY(hipMemcpyAsync(counts, ca.L, nel * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        if (kept) HIP_TRY(hipMemcpyAsync(kept, ca.U, nel * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms, &o);
 }
 
 // The quantile with participation over the entries of ctx->warpframes: per band a store launch (normalised samples and
@@ -83,15 +75,14 @@ stk_status quantile_bands_weighted(stk_ctx* ctx, const std::vector<stk_frame_wei
     const int n_entries = (int)coef.size(), w = spec.w, h = spec.h, cn = spec.cn, depth = spec.depth;
     stk_status st = quantile_check_count(ctx, n_entries);
     if (st) return st;
-    const bool host = out->location != STK_DEVICE;
     const size_t R = quantile_band_rows(ctx, n_entries, w, h, cn), row = (size_t)w * cn;
-    // the workspace: the image, the band, and behind it the staging copy of a host caller's counts
-    const size_t img_floats = quantile_image_floats(w, h, cn), band_floats = (R * n_entries * row + 63) & ~(size_t)63;
-    HIP_TRY(ctx->quantile.reserve((img_floats + band_floats + (host && counts ? (size_t)w * h : 0)) * sizeof(float)));
-    float* img = ctx->quantile.as<float>();
-    float* band = img + img_floats;
-    float* dst = host ? img : out->data;
-    int* cdst = counts ? (host ? (int*)(band + band_floats) : counts) : nullptr;
+    QuantileLayout L;
+    if ((st = quantile_reserve(ctx, n_entries, w, h, cn, out->location != STK_DEVICE && counts, &L))) return st;
+    char* base = ctx->quantile.as<char>();
+    float* band = (float*)(base + L.band);
+    const CombineOutputs o(out, (float*)(base + L.image), (size_t)h * row, {counts, base + L.counts, (size_t)w * h});
+    float* dst = o.image();
+    int* cdst = o.side<int>(0);
     WarpArgs a = fold_warp_args(ctx, n_entries, spec);
     if ((st = coef_upload(ctx, coef))) return st;
     ClipArgs ca{};
@@ -100,7 +91,7 @@ stk_status quantile_bands_weighted(stk_ctx* ctx, const std::vector<stk_frame_wei
     ca.coef = ctx->coef.as<stk_frame_weight>();
     ca.coverage = coverage;
     if (norm) norm_fold_clip_args(*norm, ca);        // the locally normalised quantile (local_norm.cpp): the same bands, its own store launch
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if ((st = combine_begin(ctx))) return st;
     for (size_t y0 = 0; y0 < (size_t)h; y0 += R) {
         const size_t rows = std::min(R, (size_t)h - y0);
         ca.y0 = (int)y0; ca.band_rows = (int)rows;
@@ -110,14 +101,7 @@ stk_status quantile_bands_weighted(stk_ctx* ctx, const std::vector<stk_frame_wei
         HIP_TRY(launch_quantile_select_masked(band, rows * row, n_entries, p->quantile, cn, dst + y0 * row,
                                               cdst ? cdst + y0 * (size_t)w : nullptr, ctx->stream));
     }
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    if (host) {
-        HIP_TRY(hipMemcpyAsync(out->data, img, (size_t)h * row * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (counts) HIP_TRY(hipMemcpyAsync(counts, cdst, (size_t)w * h * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms, &o);
 }
 
 int count_included(const stk_frames* frames, const int32_t* include) {
@@ -164,8 +148,9 @@ stk_status robust_reserve(stk_ctx* ctx, const RobustCombine& rc, const stk_frame
     (void)hipSetDevice(ctx->device);
     const int w = frames->width, h = frames->height, cn = frames->channels;
     const bool planes = rc.clip || rc.mad;
-    if (planes) HIP_TRY(ctx->clip.reserve(3 * (size_t)w * h * cn * sizeof(float)));
-    else if (stk_status st = quantile_reserve(ctx, 0, w, h, cn)) return st;
+    if (stk_status st = planes ? workspace_reserve(ctx, ctx->clip, clip_layout((size_t)w * h * cn).total, "sigma clipping")
+                               : quantile_reserve(ctx, 0, w, h, cn, false, nullptr))
+        return st;
     *mean = planes ? ctx->clip.as<float>() : ctx->quantile.as<float>();
     return STK_OK;
 }

@@ -35,25 +35,26 @@ stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_
     if (st) return st;
     const size_t row = (size_t)w * cn, nel = row * h;
     const size_t R = quantile_band_rows(ctx, n_entries, w, h, cn);
-    HIP_TRY(ctx->clip.reserve(3 * nel * sizeof(float)));
-    HIP_TRY(ctx->quantile.reserve(R * n_entries * row * sizeof(float)));
-    float* c = ctx->clip.as<float>();
+    const ClipLayout L = clip_layout(nel);
+    if ((st = workspace_reserve(ctx, ctx->clip, L.total, "robust clipping"))) return st;
+    if ((st = workspace_reserve(ctx, ctx->quantile, R * n_entries * row * sizeof(float), "robust clipping band"))) return st;
+    char* base = ctx->clip.as<char>();
     float* band = ctx->quantile.as<float>();
     WarpArgs a = fold_warp_args(ctx, n_entries, spec);
-    const bool host = out->location != STK_DEVICE;
     ClipArgs ca{};
-    ca.c = c; ca.L = c + nel; ca.U = c + 2 * nel;
+    ca.c = (float*)(base + L.c); ca.L = (float*)(base + L.L); ca.U = (float*)(base + L.U);
     ca.plane_stride = row;
     // a host output goes through the planes themselves, as in clip.cpp: the last pass reads c, L, U before it writes there
-    ca.out = host ? c : out->data;
+    const CombineOutputs o(out, ca.c, nel, {counts, ca.L, nel}, {coef ? kept : nullptr, ca.U, nel});
+    ca.out = o.image();
     ca.out_stride = row;
-    ca.counts = counts ? (host ? (int*)ca.L : counts) : nullptr;
-    ca.kept = coef && kept ? (host ? ca.U : kept) : nullptr;
+    ca.counts = o.side<int>(0);
+    ca.kept = o.side<float>(1);
     ca.kappa_low = p->kappa_low; ca.kappa_high = p->kappa_high;
     ca.band = band;
     if (coef) {
-        HIP_TRY(ctx->coef.reserve(coef->size() * sizeof(stk_frame_weight)));
-        HIP_TRY(hipMemcpyAsync(ctx->coef.p, coef->data(), coef->size() * sizeof(stk_frame_weight), hipMemcpyHostToDevice, ctx->stream));
+        if ((st = workspace_reserve(ctx, ctx->coef, coef->size() * sizeof(stk_frame_weight), "record table"))) return st;
+        if ((st = records_upload(ctx, ctx->coef.p, *coef))) return st;
         ca.coef = ctx->coef.as<stk_frame_weight>();
         ca.coverage = coverage;
     }
@@ -63,7 +64,7 @@ stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_
         HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
         ctx->select_ev.emplace_back(e0, e1);
     }
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if ((st = combine_begin(ctx))) return st;
     size_t b = 0;
     for (size_t y0 = 0; y0 < (size_t)h; y0 += R, b++) {
         const size_t rows = std::min(R, (size_t)h - y0);
@@ -79,14 +80,7 @@ stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_
     a.dh = h;
     ca.first = 0; ca.last = 1; ca.centre = 0;
     HIP_TRY(coef ? launch_clip_pass_weighted(a, ca, depth, ctx->stream) : launch_clip_pass(a, ca, depth, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    if (host) {
-        HIP_TRY(hipMemcpyAsync(out->data, c, nel * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (counts) HIP_TRY(hipMemcpyAsync(counts, ca.L, nel * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        if (ca.kept) HIP_TRY(hipMemcpyAsync(kept, ca.U, nel * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
+    if ((st = combine_end(ctx, ms, &o))) return st;
     double sel = 0.0;
     for (size_t k = 0; k < n_bands; k++) sel += ev_ms(ctx->select_ev[k].first, ctx->select_ev[k].second);
     ctx->robust_select_us = (int64_t)std::llround(sel * 1000.0);
@@ -104,8 +98,7 @@ stk_status robust_clip_match_begin(stk_ctx* ctx, const stk_frames* frames, const
     if ((st = combine_check_out(ctx, out, frames))) return st;
     if ((st = quantile_check_count(ctx, frames->n))) return st;
     (void)hipSetDevice(ctx->device);
-    HIP_TRY(ctx->clip.reserve(3 * (size_t)frames->width * frames->height * frames->channels * sizeof(float)));
-    return STK_OK;
+    return workspace_reserve(ctx, ctx->clip, clip_layout((size_t)frames->width * frames->height * frames->channels).total, "robust clipping");
 }
 
 // and their combine over the kept frames

@@ -15,28 +15,6 @@
 
 using namespace stk;
 
-namespace {
-
-struct WeightedLayout {
-    size_t image, den, coef, moments, partials, total;     // byte offsets
-};
-
-WeightedLayout weighted_layout(int n_entries, int w, int h, int cn, int step) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    WeightedLayout L{};
-    L.image = 0;
-    L.den = up((size_t)w * h * cn * sizeof(float));
-    L.coef = L.den + up((size_t)w * h * sizeof(float));
-    L.moments = L.coef + up((size_t)std::max(n_entries, 1) * sizeof(stk_frame_weight));
-    L.partials = L.moments + up((size_t)std::max(n_entries, 1) * cn * 6 * sizeof(double));
-    size_t parts = 0;
-    if (step > 0 && n_entries > 1) parts = moments_plan(w, h, step).parts() * (size_t)(n_entries - 1) * (1 + 5 * cn) * sizeof(double);
-    L.total = L.partials + up(parts);
-    return L;
-}
-
-}  // namespace
-
 // (the checks, the moments pass and the estimator are shared with robust.cpp: context.h)
 stk_status weighted_validate(stk_ctx* ctx, const stk_weight_params* p) {
     if (!p) return fail(ctx, STK_INVALID_PARAMS, "null weight parameters");
@@ -78,19 +56,17 @@ stk_status weighted_check_coefs(stk_ctx* ctx, const std::vector<stk_frame_weight
 stk_status weighted_moments(stk_ctx* ctx, int n_entries, const FoldSpec& spec, int step, double* host, double* ms) {
     if (n_entries < 2) return STK_OK;
     const WeightedLayout L = weighted_layout(n_entries, spec.w, spec.h, spec.cn, step);
-    HIP_TRY(ctx->weighted.reserve(L.total));
+    stk_status st = workspace_reserve(ctx, ctx->weighted, L.total, "weighted");
+    if (st) return st;
     char* base = ctx->weighted.as<char>();
     const WarpArgs a = fold_warp_args(ctx, n_entries, spec);
     ClipArgs ca{};
     ca.partials = (double*)(base + L.partials);
     double* mom = (double*)(base + L.moments);
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    const CombineOutputs o(host, mom, (size_t)(n_entries - 1) * spec.cn * 6, sizeof(double));
+    if ((st = combine_begin(ctx))) return st;
     HIP_TRY(launch_overlap_moments(a, ca, spec.depth, step, mom, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    HIP_TRY(hipMemcpyAsync(host, mom, (size_t)(n_entries - 1) * spec.cn * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms, &o);
 }
 
 // The estimator (include/stacker.h): f64 on the host, each operation rounded on its own, results rounded to f32.
@@ -149,28 +125,22 @@ stk_status weighted_fold(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef
                          float* coverage_out, double* ms) {
     const int n_entries = (int)coef.size(), w = spec.w, h = spec.h, cn = spec.cn;
     const WeightedLayout L = weighted_layout(n_entries, w, h, cn, 0);
-    HIP_TRY(ctx->weighted.reserve(L.total));
+    stk_status st = workspace_reserve(ctx, ctx->weighted, L.total, "weighted");
+    if (st) return st;
     char* base = ctx->weighted.as<char>();
-    const bool host = out->location != STK_DEVICE;
+    const CombineOutputs o(out, (float*)(base + L.image), (size_t)w * h * cn, {coverage_out, base + L.den, (size_t)w * h});
     const WarpArgs a = fold_warp_args(ctx, n_entries, spec);
     ClipArgs ca{};
     ca.coef = (const stk_frame_weight*)(base + L.coef);
     ca.coverage = coverage;
-    ca.out = host ? (float*)(base + L.image) : out->data;
+    ca.out = o.image();
     ca.out_stride = (size_t)w * cn;
-    ca.den = coverage_out ? (host ? (float*)(base + L.den) : coverage_out) : nullptr;
+    ca.den = o.side<float>(0);
     ca.den_stride = (size_t)w;
-    HIP_TRY(hipMemcpyAsync(base + L.coef, coef.data(), coef.size() * sizeof(stk_frame_weight), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if ((st = records_upload(ctx, base + L.coef, coef))) return st;
+    if ((st = combine_begin(ctx))) return st;
     HIP_TRY(launch_weighted_fold(a, ca, spec.depth, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
-    if (host) {
-        HIP_TRY(hipMemcpyAsync(out->data, ca.out, (size_t)w * h * cn * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (coverage_out) HIP_TRY(hipMemcpyAsync(coverage_out, ca.den, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ms) *ms += ev_ms(ctx->ev[4], ctx->ev[5]);
-    return STK_OK;
+    return combine_end(ctx, ms, &o);
 }
 
 // the checks the two whole-stack forms share, in the order the errors are reported; then their workspace (the plain call's
@@ -184,8 +154,7 @@ stk_status weighted_match_check(stk_ctx* ctx, const stk_frames* frames, const st
 stk_status weighted_match_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_weight_params* weight) {
     (void)hipSetDevice(ctx->device);
     const int step = weight->normalize ? (weight->stat_step ? weight->stat_step : 4) : 0;
-    HIP_TRY(ctx->weighted.reserve(weighted_layout(frames->n, frames->width, frames->height, frames->channels, step).total));
-    return STK_OK;
+    return workspace_reserve(ctx, ctx->weighted, weighted_layout(frames->n, frames->width, frames->height, frames->channels, step).total, "weighted");
 }
 
 // and their combine over the kept frames: the records, then one weighted fold

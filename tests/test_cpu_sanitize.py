@@ -166,6 +166,19 @@ def test_combine_entry_tables_on_the_host(tmp_path):
 
 
 @pytest.mark.timeout(600)
+def test_combine_workspaces_and_outputs_on_the_host(tmp_path):
+    """Where every combine puts its regions in a workspace and what it copies back to a host caller (workspace.h: the
+    carver, the layouts, CombineOutputs, combine_begin / combine_end): regions aligned, disjoint and large enough over a
+    grid of shapes, offsets against numbers written out by hand, and copy-backs into heap blocks of exactly the documented
+    size, under ASan + UBSan."""
+    exe = str(tmp_path / "workspace")
+    _build("workspace_harness.cpp", exe, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=500)
+    assert r.returncode == 0 and r.stdout.startswith("ok"), r.stdout[-1500:] + r.stderr[-3000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
+@pytest.mark.timeout(600)
 def test_ransac_host_half_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "ransac_host")
     _build("ransac_host_harness.cpp", exe, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
