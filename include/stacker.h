@@ -1229,6 +1229,56 @@ stk_status stk_keypoint_match_local_normalized(stk_ctx* ctx, const stk_frames* f
                                                int32_t* counts_or_null, float* const* norm_out_or_null,
                                                stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
 
+/* Local normalisation, continued: the two clip combines through the planes.
+ * Locally normalised clip: stk_clip_stack_weighted's definition, word for word, with one change: the normalised sample is
+ *   u = s * G_c + O_c, (G_c, O_c) the entry's plane at the destination pixel by the chain "Locally normalised fold" states
+ *   (k, j, k1, j1, u, v, then t0, t1, value by fma). An entry with a NULL plane uses its record's gain and offset as
+ *   constants. For an entry with a plane w comes from the record and the record's gain and offset are ignored. NULL
+ *   records mean unit records. Unchanged from stk_clip_stack_weighted: participation (w > 0 and, with coverage = 1,
+ *   kappa == 1.0f), the centre pass, passes 1 .. T + 1, the k >= 3 rule, out, counts, kept_weight, and the pixel that no
+ *   entry participates in.
+ * Locally normalised median / MAD clip: the participation form of stk_robust_clip_stack_weighted with the same u: centre
+ *   and scale are unweighted order statistics of the participating u; the final pass is the locally normalised clip's
+ *   last pass.
+ * Consequences. With every plane NULL, or every plane constant and equal to its record, the results are
+ *   stk_clip_stack_weighted's and stk_robust_clip_stack_weighted's bit for bit, also where those run the u8 BGR fast
+ *   kernels (the new calls run them too: BGR u8 under BORDER_CONSTANT with exact coordinates). warp_subpixel_bits = 5 and
+ *   STK_INTER_CUBIC are served. A multi-device context runs these calls on its first device. Plane values are expected
+ *   finite and are not checked.
+ * Checks: those of stk_clip_stack_weighted / stk_robust_clip_stack_weighted (coverage = 1 puts no condition on the border;
+ *   the median / MAD form keeps N <= 4096: STK_NOT_IMPLEMENTED beyond), then stk_local_norm_stack's step check.
+ * The caller-held forms: stk_clip_stack_weighted's / stk_robust_clip_stack_weighted's arguments with per_frame_or_null, then
+ * norm_or_null and step as in stk_local_norm_stack. counts_or_null (w x h x cn int32) and kept_weight_or_null (w x h x cn
+ * f32) are in the location of `out`. */
+stk_status stk_clip_stack_local_norm(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                     int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                     const stk_clip_params* clip, const stk_frame_weight* per_frame_or_null,
+                                     const float* const* norm_or_null, int32_t step, int32_t coverage, stk_image_f32* out,
+                                     int32_t* counts_or_null, float* kept_weight_or_null);
+stk_status stk_robust_clip_stack_local_norm(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include_or_null,
+                                            int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                            const stk_robust_clip_params* clip, const stk_frame_weight* per_frame_or_null,
+                                            const float* const* norm_or_null, int32_t step, int32_t coverage, stk_image_f32* out,
+                                            int32_t* counts_or_null, float* kept_weight_or_null);
+/* The whole-stack forms: by definition the result of their parts, bit for bit: the plain call, stk_local_moments on its
+ * warps, stk_local_norm_estimate per frame, then stk_clip_stack_local_norm (clip_or_null given) or
+ * stk_robust_clip_stack_local_norm (robust_or_null given) with unit records carrying weights_or_null. Exactly one of
+ * clip_or_null / robust_or_null must be non-NULL (STK_INVALID_PARAMS otherwise). norm_out_or_null, applied_or_null and
+ * finalize_ms (moments plus combine) as in stk_ecc_match_local_normalized. */
+stk_status stk_ecc_match_local_normalized_clipped(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
+                                                  float scale_down_width, const stk_local_norm_params* norm,
+                                                  const stk_clip_params* clip_or_null, const stk_robust_clip_params* robust_or_null,
+                                                  const float* weights_or_null, stk_image_f32* out, int32_t* counts_or_null,
+                                                  float* kept_weight_or_null, float* const* norm_out_or_null,
+                                                  stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
+stk_status stk_keypoint_match_local_normalized_clipped(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                                       float scale_down_width, const stk_local_norm_params* norm,
+                                                       const stk_clip_params* clip_or_null,
+                                                       const stk_robust_clip_params* robust_or_null, const float* weights_or_null,
+                                                       stk_image_f32* out, int32_t* dropped, int32_t* counts_or_null,
+                                                       float* kept_weight_or_null, float* const* norm_out_or_null,
+                                                       stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
+
 /* ---- stage-level entry points (parity tests bind these) ------------------ */
 /* cvt_color(BGR2GRAY) on the integer image, utils.rs:136-142. out: w*h of the input depth
  * (u8 / u16 / f32), tightly packed, same location as the frame. */

@@ -271,7 +271,22 @@ SIGNATURES = {
                                                        C.POINTER(LocalNormParams), C.POINTER(QuantileParams), C.c_void_p,
                                                        C.POINTER(ImageF32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
-    "stk_grey": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p]),
+    "stk_clip_stack_local_norm": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_double, C.POINTER(ClipParams), C.POINTER(FrameWeight), C.c_void_p, C.c_int32,
+                                             C.c_int32, C.POINTER(ImageF32), C.c_void_p, C.c_void_p]),
+    "stk_robust_clip_stack_local_norm": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                    C.c_void_p, C.c_double, C.POINTER(RobustClipParams), C.POINTER(FrameWeight),
+                                                    C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ImageF32), C.c_void_p, C.c_void_p]),
+    "stk_ecc_match_local_normalized_clipped": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(EccParams), C.c_float,
+                                                          C.POINTER(LocalNormParams), C.POINTER(ClipParams),
+                                                          C.POINTER(RobustClipParams), C.c_void_p, C.POINTER(ImageF32), C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
+    "stk_keypoint_match_local_normalized_clipped": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
+                                                               C.POINTER(LocalNormParams), C.POINTER(ClipParams),
+                                                               C.POINTER(RobustClipParams), C.c_void_p, C.POINTER(ImageF32),
+                                                               C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                               C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
+    "stk_grey":(c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p]),
     "stk_convert_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_double, C.c_void_p]),
     "stk_hybrid_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.POINTER(EccParams),
                                     C.POINTER(ImageF32), C.POINTER(FrameStats)]),

@@ -1083,6 +1083,114 @@ class Stacker:
         return self._match_local_normalized("keypoint", files, params, norm, quantile, weights, scale_down_width, return_stats,
                                             return_den, return_counts, return_norm, return_applied)
 
+    # -- the two clip combines through the planes --
+    def _clip_stack_local_norm(self, fn, cp, files, warps, norm, step, gain, offset, weights, include, applied, coverage, is_affine,
+                               border_mode, border_value, alpha, return_counts, return_kept_weight):
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        Md, inc = self._warps_arg(warps, include, m.n)
+        rec = self._records_arg(m, gain, offset, weights, applied)
+        keep, nptr = self._norm_arg(m, norm)
+        if keep is not None:
+            self._norm_shapes(m, keep, step)
+        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        out, img = self._out_image(m)
+        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
+        kw, kptr = self._kept_image(m) if return_kept_weight else (None, None)
+        self._check(fn(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), None if inc is None else C.c_void_p(inc.ctypes.data),
+                       int(is_affine), int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(cp), rec, nptr, int(step),
+                       int(coverage), C.byref(img), cptr, kptr))
+        res = (out,) + ((cnt,) if return_counts else ()) + ((kw,) if return_kept_weight else ())
+        return res if len(res) > 1 else out
+
+    def clip_stack_local_norm(self, files, warps, norm, step: int, clip: Optional["SigmaClipParameters"] = None, gain=None,
+                              offset=None, weights=None, include=None, *, applied=None, coverage: bool = True, is_affine=False,
+                              border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0,
+                              return_counts: bool = False, return_kept_weight: bool = False):
+        """The locally normalised sigma clip alone over caller-held warps (stk_clip_stack_local_norm): clip_stack_weighted
+        through the planes of local_norm_stack. Returns the image, then the counts and the kept weight per pixel and channel."""
+        return self._clip_stack_local_norm(self._lib.stk_clip_stack_local_norm, (clip or SigmaClipParameters())._c(), files, warps,
+                                           norm, step, gain, offset, weights, include, applied, coverage, is_affine, border_mode,
+                                           border_value, alpha, return_counts, return_kept_weight)
+
+    def robust_clip_stack_local_norm(self, files, warps, norm, step: int, clip: Optional["RobustClipParameters"] = None, gain=None,
+                                     offset=None, weights=None, include=None, *, applied=None, coverage: bool = True,
+                                     is_affine=False, border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0,
+                                     return_counts: bool = False, return_kept_weight: bool = False):
+        """The locally normalised median / MAD clip alone over caller-held warps (stk_robust_clip_stack_local_norm), with the
+        arguments and results of clip_stack_local_norm."""
+        return self._clip_stack_local_norm(self._lib.stk_robust_clip_stack_local_norm, (clip or RobustClipParameters())._c(), files,
+                                           warps, norm, step, gain, offset, weights, include, applied, coverage, is_affine,
+                                           border_mode, border_value, alpha, return_counts, return_kept_weight)
+
+    @staticmethod
+    def _clip_choice(clip):
+        """clip= of the *_local_normalized_clipped calls -> (stk_clip_params or None, stk_robust_clip_params or None)."""
+        if isinstance(clip, SigmaClipParameters):
+            return clip._c(), None
+        if isinstance(clip, RobustClipParameters):
+            return None, clip._c()
+        if isinstance(clip, (tuple, list)) and len(clip) == 2 and all(c is not None for c in clip):
+            raise InvalidParams("clip: one of SigmaClipParameters and RobustClipParameters expected, not both")
+        raise InvalidParams("clip: a SigmaClipParameters or a RobustClipParameters expected")
+
+    def _match_local_normalized_clipped(self, kind, files, params, norm, clip, weights, scale_down_width, return_stats, return_counts,
+                                        return_kept_weight, return_norm, return_applied):
+        cp, rp = self._clip_choice(clip)
+        if kind == "ecc" and isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        out, img = self._out_image(m)
+        np_ = (norm or LocalNormParameters())._c()
+        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
+        kw, kptr = self._kept_image(m) if return_kept_weight else (None, None)
+        wkeep, wptr = self._weights_arg(weights, m.n)
+        planes, pptr = None, None
+        if return_norm:
+            gw, gh = mesh_grid(m.w, m.h, int(np_.step))
+            planes = [np.zeros((gh, gw, 2 * m.c), np.float32) for _ in range(m.n)]
+            pptr = (C.c_void_p * m.n)(*[p.ctypes.data for p in planes])
+        applied = (_ffi.FrameWeight * m.n)()
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p = params._c()
+        fn = getattr(self._lib, f"stk_{kind}_match_local_normalized_clipped")
+        args = [self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(np_),
+                None if cp is None else C.byref(cp), None if rp is None else C.byref(rp), wptr, C.byref(img)]
+        if kind == "keypoint":
+            args.append(C.byref(dropped))
+        self._check(fn(*args, cptr, kptr, pptr, applied, stats))
+        stl = self._stats_list(stats, m.n)
+        if planes is not None:                      # frame 0 and dropped frames have no plane
+            planes = [None if i == 0 or (kind == "keypoint" and stl[i]["status"] != 0) else planes[i] for i in range(m.n)]
+        res = ((dropped.value,) if kind == "keypoint" else ()) + (out,) + ((cnt,) if return_counts else ()) \
+            + ((kw,) if return_kept_weight else ()) + ((planes,) if return_norm else ()) \
+            + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) + ((stl,) if return_stats else ())
+        return res if len(res) > 1 else out
+
+    def ecc_match_local_normalized_clipped(self, files, params: EccMatchParameters, norm: Optional["LocalNormParameters"] = None,
+                                           clip=None, weights=None, scale_down_width: Optional[float] = None,
+                                           return_stats: bool = False, return_counts: bool = False, return_kept_weight: bool = False,
+                                           return_norm: bool = False, return_applied: bool = False):
+        """ecc_match with local normalisation and rejection (stk_ecc_match_local_normalized_clipped). clip: a
+        SigmaClipParameters (the locally normalised sigma clip) or a RobustClipParameters (the median / MAD clip); exactly
+        one. Returns the image, then the counts, the kept weight, the planes by frame index, the global records and the stats."""
+        return self._match_local_normalized_clipped("ecc", files, params, norm, clip, weights, scale_down_width, return_stats,
+                                                    return_counts, return_kept_weight, return_norm, return_applied)
+
+    def keypoint_match_local_normalized_clipped(self, files, params: KeyPointMatchParameters,
+                                                norm: Optional["LocalNormParameters"] = None, clip=None, weights=None,
+                                                scale_down_width: Optional[float] = None, return_stats: bool = False,
+                                                return_counts: bool = False, return_kept_weight: bool = False,
+                                                return_norm: bool = False, return_applied: bool = False):
+        """keypoint_match with local normalisation and rejection (stk_keypoint_match_local_normalized_clipped): (dropped,
+        image, ...) as ecc_match_local_normalized_clipped."""
+        return self._match_local_normalized_clipped("keypoint", files, params, norm, clip, weights, scale_down_width, return_stats,
+                                                    return_counts, return_kept_weight, return_norm, return_applied)
+
     # -- per-pixel weight maps and local-sharpness stacking (extension beyond the reference) --------------
     def local_sharpness(self, files, local: Optional["LocalParameters"] = None):
         """The local quality map of every frame of an 8-bit stack (stk_local_sharpness): n x H x W float32, exact integers,

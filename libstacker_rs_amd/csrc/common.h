@@ -372,6 +372,9 @@ hipError_t launch_norm_store(const WarpArgs& a, const ClipArgs& c, int depth, hi
 hipError_t launch_quantile_store(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
 // one pass of the weighted clip (c.coef, c.coverage, c.centre, c.kept besides launch_clip_pass's fields)
 hipError_t launch_clip_pass_weighted(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
+// one pass of the weighted clip through the planes of c.norm (c.norm_* besides launch_clip_pass_weighted's fields;
+// ClipNorm / ClipNormU8C3, kernels_clip.hip): every kernel launch_clip_pass_weighted may choose, the u8 BGR fast ones included
+hipError_t launch_clip_pass_norm(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);
 // the store mode with participation (c.coef, c.coverage besides launch_quantile_store's fields): the normalised sample
 // u = s * g + o, QUANTILE_ABSENT_BITS for an entry that is no sample of the pixel
 hipError_t launch_quantile_store_weighted(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s);

@@ -193,9 +193,12 @@ stk_status quantile_reserve(stk_ctx* ctx, int n, int w, int h, int cn, bool coun
 stk_status robust_clip_validate(stk_ctx* ctx, const stk_robust_clip_params* p);
 // the median / MAD clip over the n_entries entries of ctx->warpframes (robust_clip.cpp): per band a store launch and the
 // selection into the clip planes, then one last clip pass. coef: the per-entry records of the participation form (then
-// `coverage` and `kept` apply), null = the plain form. Writes out / counts / kept (out's location), adds its device time to *ms
+// `coverage` and `kept` apply), null = the plain form. Writes out / counts / kept (out's location), adds its device time to *ms.
+// norm (with coef): the locally normalised form, the store launch and the last pass through its plane table
+struct NormFoldArgs;
 stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_frame_weight>* coef, const FoldSpec& spec, int coverage,
-                             const stk_robust_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms);
+                             const stk_robust_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms,
+                             const NormFoldArgs* norm = nullptr);
 stk_status weighted_validate(stk_ctx* ctx, const stk_weight_params* p);
 stk_status weighted_check_border(stk_ctx* ctx, int border_mode, const double* border_value, int coverage);
 stk_status weighted_check_coefs(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, int cn);
@@ -244,6 +247,9 @@ void norm_fold_clip_args(const NormFoldArgs& n, stk::ClipArgs& ca);
 // quantile_bands_weighted (robust.cpp) with the locally normalised store launch: same bands, workspaces and selection
 stk_status quantile_bands_norm(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage,
                                const stk_quantile_params* p, const NormFoldArgs& norm, stk_image_f32* out, int32_t* counts, double* ms);
+// clip_passes_weighted (robust.cpp) with the locally normalised clip pass: same planes, workspaces and passes
+stk_status clip_passes_norm(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage,
+                            const stk_clip_params* p, const NormFoldArgs& norm, stk_image_f32* out, int32_t* counts, float* kept, double* ms);
 // rejection maps (reject.cpp) and the pieces of the combines that the rejected drizzle (drizzle.cpp) is built from
 stk_status reject_validate(stk_ctx* ctx, const stk_reject_params* p);
 stk_status reject_run(stk_ctx* ctx, const RejectLayout& L, const stk_frames* frames, const std::vector<const void*>& dev,

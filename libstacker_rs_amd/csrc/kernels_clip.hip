@@ -251,4 +251,153 @@ hipError_t launch_clip_pass_weighted(const WarpArgs& a, const ClipArgs& c, int d
     return launch_fold<ClipWU8C3, ClipWGeneric>(a, c, depth, a.dh, s);
 }
 
+// ---- the weighted clip through local-normalisation planes (stk_clip_stack_local_norm, stk_robust_clip_stack_local_norm
+// and the *_local_normalized_clipped entry points; definition in include/stacker.h, "Locally normalised clip") ------------
+// The weighted clip's states with u = s * G + O, (G, O) the entry's plane at the destination pixel (NormAt, warp_body.h,
+// as FoldNorm reads it), or the record's gain and offset where the entry has no plane. The plane pointer table moves with
+// the record pointer; the epilogue is clip_end_w.
+template <int CN>
+struct ClipNorm {
+    float c[CN], L[CN], U[CN], a[CN], b[CN], sw[CN];
+    int k[CN];
+    size_t p;
+    const stk_frame_weight* e;
+    const float* const* np;
+    NormAt at;
+    int cov;
+    bool part, centre;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+        p = (size_t)y * ca.plane_stride + (size_t)x * CN;
+        const bool open = ca.first | ca.centre;
+#pragma unroll
+        for (int i = 0; i < CN; i++) {
+            c[i] = ca.centre ? 0.0f : ca.c[p + i];
+            L[i] = open ? -__builtin_inff() : ca.L[p + i];
+            U[i] = open ? __builtin_inff() : ca.U[p + i];
+            a[i] = 0.f; b[i] = 0.f; sw[i] = 0.f; k[i] = 0;
+        }
+        e = ca.coef; np = ca.norm; cov = ca.coverage; centre = ca.centre != 0; part = true;
+        at.set(ca, x, y, 2 * CN);
+    }
+    __device__ __forceinline__ void entry(float kap) { part = (e->weight > 0.0f) & (cov ? kap == 1.0f : true); }
+    __device__ __forceinline__ void add(int i, float s) {
+        const float w = e->weight;
+        const float* __restrict__ P = *np;
+        const float G = P ? at.at(P, i) : e->gain[i], O = P ? at.at(P, CN + i) : e->offset[i];
+        const float u = s * G + O;
+        const float d = u - c[i];
+        const bool in = part & (centre | clip_in(u, L[i], U[i]));
+        const float wi = in ? w : 0.0f, di = in ? d : 0.0f;       // (as ClipWGeneric: a sample that is out adds +0)
+        k[i] += in ? 1 : 0;
+        sw[i] = sw[i] + wi;
+        a[i] = a[i] + wi * di;
+        b[i] = b[i] + wi * (di * di);
+        if (i == CN - 1) { e++; np++; }
+    }
+    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
+        const size_t o = (size_t)y * ca.out_stride + (size_t)x * CN;
+#pragma unroll
+        for (int i = 0; i < CN; i++) clip_end_w(ca, p + i, o + i, c[i], L[i], U[i], k[i], sw[i], a[i], b[i]);
+    }
+};
+
+// u8 BGR fast kernels' state: ClipWU8C3 with the six chains (three gains, three offsets) per entry. The first fast-kernel
+// state that reads the node grid. A wave of the fast kernels is a run of consecutive x in one row, so from a node spacing
+// of 64 on its lanes usually share their four nodes: begin() takes a wave vote on the four node offsets (all lanes' equal
+// the first lane's; nothing is assumed about the launch shape), and where it holds the plane values are read through the
+// first lane's offsets and a constant-address-space pointer, which makes them scalar loads into scalar registers (the
+// planes are written before the launch only). Where it does not hold (spacing 8 .. 32, or a wave across a node column)
+// every lane loads its own. The arithmetic is NormAt::at's, operation for operation (sub, fma, sub, fma, sub, fma), so the
+// two paths and ClipNorm<3> give the same bits.
+struct ClipNormU8C3 {
+    typedef const float __attribute__((address_space(4))) * UniformPlane;
+    f32x2 c01, L01, U01, a01, b01, sw01;
+    float c2, L2, U2, a2, b2, sw2;
+    int k0, k1, k2;
+    size_t p;
+    const stk_frame_weight* e;
+    const float* const* np;
+    NormAt at;
+    int s00, s01, s10, s11;          // the first lane's node offsets (wave-uniform)
+    int cov;
+    bool centre, uniform;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+        p = (size_t)y * ca.plane_stride + (size_t)x * 3;
+        if (ca.centre) { c01 = f32x2{0.f, 0.f}; c2 = 0.f; }
+        else { c01 = f32x2{ca.c[p], ca.c[p + 1]}; c2 = ca.c[p + 2]; }
+        if (ca.first | ca.centre) {
+            L01 = f32x2{-__builtin_inff(), -__builtin_inff()}; L2 = -__builtin_inff();
+            U01 = f32x2{__builtin_inff(), __builtin_inff()}; U2 = __builtin_inff();
+        } else {
+            L01 = f32x2{ca.L[p], ca.L[p + 1]}; L2 = ca.L[p + 2];
+            U01 = f32x2{ca.U[p], ca.U[p + 1]}; U2 = ca.U[p + 2];
+        }
+        a01 = f32x2{0.f, 0.f}; b01 = f32x2{0.f, 0.f}; sw01 = f32x2{0.f, 0.f}; a2 = 0.f; b2 = 0.f; sw2 = 0.f;
+        k0 = k1 = k2 = 0;
+        e = ca.coef; np = ca.norm; cov = ca.coverage; centre = ca.centre != 0;
+        at.set(ca, x, y, 6);
+        s00 = __builtin_amdgcn_readfirstlane(at.o00); s01 = __builtin_amdgcn_readfirstlane(at.o01);
+        s10 = __builtin_amdgcn_readfirstlane(at.o10); s11 = __builtin_amdgcn_readfirstlane(at.o11);
+        uniform = __all((at.o00 == s00) & (at.o01 == s01) & (at.o10 == s10) & (at.o11 == s11)) != 0;
+#ifdef STK_NORM_CLIP_NO_VOTE                                  // measurement only (tools/local_norm_clip_time.py): always per-lane loads
+        uniform = false;
+#endif
+    }
+    // NormAt::at on four node values
+    __device__ __forceinline__ float chain(float p00, float p01, float p10, float p11) const {
+        const float t0 = __builtin_fmaf(at.u, p01 - p00, p00);
+        const float t1 = __builtin_fmaf(at.u, p11 - p10, p10);
+        return __builtin_fmaf(at.v, t1 - t0, t0);
+    }
+    __device__ __forceinline__ void fold(f32x2 s01v, float s2, bool part) {
+        const float w = e->weight;
+        const float* __restrict__ P = *np;
+        float q[6];                      // G of B, G, R, then O of B, G, R
+        if (!P) {
+#pragma unroll
+            for (int i = 0; i < 3; i++) { q[i] = e->gain[i]; q[3 + i] = e->offset[i]; }
+        } else if (uniform) {
+            const UniformPlane S = (UniformPlane)(uintptr_t)P;
+#pragma unroll
+            for (int i = 0; i < 6; i++) q[i] = chain(S[s00 + i], S[s01 + i], S[s10 + i], S[s11 + i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 6; i++) q[i] = at.at(P, i);
+        }
+        const f32x2 u01 = s01v * f32x2{q[0], q[1]} + f32x2{q[3], q[4]};
+        const f32x2 d = u01 - c01;
+        const bool i0 = part & (centre | clip_in(u01.x, L01.x, U01.x)), i1 = part & (centre | clip_in(u01.y, L01.y, U01.y));
+        // (as ClipWU8C3: a sample that is out adds w = 0 times d = 0, and the sums stay packed)
+        const f32x2 wi = {i0 ? w : 0.0f, i1 ? w : 0.0f}, di = {i0 ? d.x : 0.0f, i1 ? d.y : 0.0f};
+        k0 += i0 ? 1 : 0; k1 += i1 ? 1 : 0;
+        sw01 = sw01 + wi;
+        a01 = a01 + wi * di;
+        b01 = b01 + wi * (di * di);
+        const float u2 = s2 * q[2] + q[5];
+        const float d2 = u2 - c2;
+        const bool i2 = part & (centre | clip_in(u2, L2, U2));
+        const float w2 = i2 ? w : 0.0f, dd2 = i2 ? d2 : 0.0f;
+        k2 += i2 ? 1 : 0;
+        sw2 = sw2 + w2;
+        a2 = a2 + w2 * dd2;
+        b2 = b2 + w2 * (dd2 * dd2);
+        e++; np++;
+    }
+    __device__ __forceinline__ void add2(f32x2 s01v, float s2) { fold(s01v, s2, e->weight > 0.0f); }
+    __device__ __forceinline__ void add3k(float s0, float s1, float s2, float kap) {
+        fold(f32x2{s0, s1}, s2, (e->weight > 0.0f) & (cov ? kap == 1.0f : true));
+    }
+    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
+        const size_t o = (size_t)y * ca.out_stride + (size_t)x * 3;
+        clip_end_w(ca, p, o, c01.x, L01.x, U01.x, k0, sw01.x, a01.x, b01.x);
+        clip_end_w(ca, p + 1, o + 1, c01.y, L01.y, U01.y, k1, sw01.y, a01.y, b01.y);
+        clip_end_w(ca, p + 2, o + 2, c2, L2, U2, k2, sw2, a2, b2);
+    }
+};
+
+hipError_t launch_clip_pass_norm(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
+    if (!norm_args_ok(a, c)) return hipErrorInvalidValue;
+    return launch_fold<ClipNormU8C3, ClipNorm>(a, c, depth, a.dh, s);
+}
+
 }  // namespace stk

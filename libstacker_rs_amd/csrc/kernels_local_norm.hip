@@ -105,12 +105,6 @@ hipError_t launch_local_moments(const WarpArgs& a, const ClipArgs& c, int depth,
     });
 }
 
-static bool norm_args_ok(const WarpArgs& a, const ClipArgs& c) {
-    if (a.n_frames <= 0 || !c.norm || !c.coef || c.norm_shift < 3 || c.norm_shift > 8) return false;
-    const int step = 1 << c.norm_shift;
-    return c.norm_gw == (a.dw - 1 + step - 1) / step + 1 && c.norm_gh >= (a.dh - 1 + step - 1) / step + 1;
-}
-
 // The locally normalised mean over the frames of `a`: the generic kernels, linear or cubic. The u8 BGR fast kernels do not
 // serve these states.
 hipError_t launch_norm_fold(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {

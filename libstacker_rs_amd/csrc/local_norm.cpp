@@ -1,12 +1,15 @@
 // local_norm.cpp — local normalisation: stk_local_moments, stk_local_norm_estimate, stk_local_norm_stack,
-// stk_quantile_stack_local_norm, stk_ecc_match_local_normalized, stk_keypoint_match_local_normalized (an extension beyond
-// the reference; definition in include/stacker.h, "local normalisation"; kernels in kernels_local_norm.hip and warp_body.h).
+// stk_quantile_stack_local_norm, stk_clip_stack_local_norm, stk_robust_clip_stack_local_norm, stk_ecc_match_local_normalized,
+// stk_keypoint_match_local_normalized and their *_clipped forms (an extension beyond the reference; definition in
+// include/stacker.h, "local normalisation"; kernels in kernels_local_norm.hip, warp_body.h and kernels_clip.hip).
 // ctx->local (grow-only like the other workspaces; the local-weighted combine's buffer, laid out here by NormLayout) holds
 // the plane pointer table of the fold, the per-entry record table, a w x h x cn f32 image (the plain call's mean in the
 // whole-stack forms, then a host output's staging copy), the w x h den plane, the cell moments of the entries and their
 // planes. The frame table is combine.h's; the checks and the per-channel formulas are the weighted combine's (weighted.cpp,
-// through context.h); the quantile's bands and selection are robust.cpp's (quantile_bands_norm). The estimator and the fill
-// are plain host code without a context: stk_local_norm_estimate is what the whole-stack forms call per frame.
+// through context.h); the quantile's bands and selection are robust.cpp's (quantile_bands_norm), the two clips are
+// robust.cpp's and robust_clip.cpp's (clip_passes_norm, robust_clip_bands with a plane table), with their own workspaces.
+// The estimator and the fill are plain host code without a context: stk_local_norm_estimate is what the whole-stack forms
+// call per frame.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -101,10 +104,31 @@ stk_status norm_fold(stk_ctx* ctx, const NormLayout& L, const std::vector<stk_fr
     return combine_end(ctx, ms, &o);
 }
 
-// the caller-held-warps forms of the two combines, after the combine's own checks: quantile == null is the mean
+// Which combine runs through the planes, and its side outputs: at most one of quantile / clip / mad is set (none: the
+// mean). den belongs to the mean, counts to the quantile (w x h) or to a clip (w x h x cn), kept to a clip.
+struct NormCombine {
+    const stk_quantile_params* quantile = nullptr;
+    const stk_clip_params* clip = nullptr;
+    const stk_robust_clip_params* mad = nullptr;      // the median / MAD clip
+    float* den = nullptr;
+    int32_t* counts = nullptr;
+    float* kept = nullptr;
+    bool selects() const { return quantile || mad; }  // goes through the selection kernels: N <= 4096
+};
+
+// the combine over the entries of ctx->warpframes with the records `coef` and the plane table `nf`
+stk_status norm_combine(stk_ctx* ctx, const NormLayout& L, const NormCombine& nc, const std::vector<stk_frame_weight>& coef,
+                        const NormFoldArgs& nf, const FoldSpec& spec, int coverage, stk_image_f32* out, double* ms) {
+    if (nc.quantile) return quantile_bands_norm(ctx, coef, spec, coverage, nc.quantile, nf, out, nc.counts, ms);
+    if (nc.clip) return clip_passes_norm(ctx, coef, spec, coverage, nc.clip, nf, out, nc.counts, nc.kept, ms);
+    if (nc.mad) return robust_clip_bands(ctx, (int)coef.size(), &coef, spec, coverage, nc.mad, out, nc.counts, nc.kept, ms, &nf);
+    return norm_fold(ctx, L, coef, nf, spec, coverage, out, nc.den, ms);
+}
+
+// the caller-held-warps forms of the combines, after the combine's own checks
 stk_status norm_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int is_affine, int border_mode,
-                      const double* border_value, double alpha, const stk_quantile_params* quantile, const stk_frame_weight* per_frame,
-                      const float* const* norm, int step, int coverage, stk_image_f32* out, float* den_out, int32_t* counts) {
+                      const double* border_value, double alpha, const NormCombine& nc, const stk_frame_weight* per_frame,
+                      const float* const* norm, int step, int coverage, stk_image_f32* out) {
     if (!M) return fail(ctx, STK_INVALID_PARAMS, "null matrix");
     if (!grid_step_ok(step)) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: step must be 8, 16, 32, 64, 128 or 256");
     stk_status st = combine_check_out(ctx, out, frames);
@@ -113,7 +137,7 @@ stk_status norm_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, c
     EntryTable table;
     entries_from_include(frames->n, M, include, table);
     if (table.frame.empty()) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: no frame included");
-    if (quantile && (st = quantile_check_count(ctx, table.size()))) return st;
+    if (nc.selects() && (st = quantile_check_count(ctx, table.size()))) return st;
     std::vector<stk_frame_weight> coef;
     gather_records(table, per_frame, coef);
     if ((st = weighted_check_coefs(ctx, coef, cn))) return st;
@@ -128,23 +152,25 @@ stk_status norm_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, c
     if ((st = norm_planes_upload(ctx, L, planes, g, cn, &nf))) return st;
     const FoldSpec spec = fold_spec(frames, alpha, border_mode, border_value, is_affine);
     double ms = 0.0;
-    st = quantile ? quantile_bands_norm(ctx, coef, spec, coverage, quantile, nf, out, counts, &ms)
-                  : norm_fold(ctx, L, coef, nf, spec, coverage, out, den_out, &ms);
+    st = norm_combine(ctx, L, nc, coef, nf, spec, coverage, out, &ms);
     ctx->timing.finalize_ms = st ? 0.0 : ms;
     return st;
 }
 
 // the checks the two whole-stack forms share, in the order the errors are reported
-stk_status norm_match_check(stk_ctx* ctx, const stk_frames* frames, const stk_local_norm_params* p, const stk_quantile_params* quantile,
-                            const stk_image_f32* out, const float* den_out, const int32_t* counts) {
+stk_status norm_match_check(stk_ctx* ctx, const stk_frames* frames, const stk_local_norm_params* p, const NormCombine& nc,
+                            const stk_image_f32* out) {
     stk_status st = norm_validate(ctx, p);
     if (st) return st;
-    if (quantile && (st = quantile_validate(ctx, quantile))) return st;
-    if (quantile && den_out) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: den belongs to the mean, not to the quantile");
-    if (!quantile && counts) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: counts belong to the quantile, not to the mean");
+    if (nc.quantile && (st = quantile_validate(ctx, nc.quantile))) return st;
+    if (nc.clip && (st = clip_validate(ctx, nc.clip))) return st;
+    if (nc.mad && (st = robust_clip_validate(ctx, nc.mad))) return st;
+    if (nc.quantile && nc.den) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: den belongs to the mean, not to the quantile");
+    if (!nc.quantile && !nc.clip && !nc.mad && nc.counts)
+        return fail(ctx, STK_INVALID_PARAMS, "local normalisation: counts belong to the quantile, not to the mean");
     if ((st = check_frames(ctx, frames, true))) return st;
     if ((st = combine_check_out(ctx, out, frames))) return st;
-    if (quantile && (st = quantile_check_count(ctx, frames->n))) return st;
+    if (nc.selects() && (st = quantile_check_count(ctx, frames->n))) return st;
     if (frames->n - 1 > 65535) return fail(ctx, STK_INVALID_PARAMS, "local normalisation: at most 65536 frames");
     return STK_OK;
 }
@@ -157,10 +183,9 @@ stk_status norm_match_reserve(stk_ctx* ctx, const stk_frames* frames, const stk_
     return workspace_reserve(ctx, ctx->local, L->total, "local normalisation");
 }
 
-// and their combine over the kept frames: cell moments, estimator, planes, then the mean or the quantile
-CombineFinish norm_match_finish(stk_ctx* ctx, const NormLayout& L, int n, const stk_local_norm_params* p, const stk_quantile_params* quantile,
-                                const float* weights, stk_image_f32* out, float* den_out, int32_t* counts, float* const* norm_out,
-                                stk_frame_weight* applied) {
+// and their combine over the kept frames: cell moments, estimator, planes, then the combine
+CombineFinish norm_match_finish(stk_ctx* ctx, const NormLayout& L, int n, const stk_local_norm_params* p, const NormCombine& nc,
+                                const float* weights, stk_image_f32* out, float* const* norm_out, stk_frame_weight* applied) {
     return [=](const EntryTable& table, const std::vector<const void*>&, const FoldSpec& spec, const stk_frame_stats*, double* ms) {
         const int ne = table.size(), cn = spec.cn;
         const NodeGrid g = node_grid(spec.w, spec.h, p->step);
@@ -187,9 +212,54 @@ CombineFinish norm_match_finish(stk_ctx* ctx, const NormLayout& L, int n, const 
         }
         NormFoldArgs nf{};
         if ((st = norm_planes_upload(ctx, L, planes, g, cn, &nf))) return st;
-        if (quantile) return quantile_bands_norm(ctx, coef, spec, p->coverage, quantile, nf, out, counts, ms);
-        return norm_fold(ctx, L, coef, nf, spec, p->coverage, out, den_out, ms);
+        return norm_combine(ctx, L, nc, coef, nf, spec, p->coverage, out, ms);
     };
+}
+
+// the two whole-stack forms of every combine: the plain call, then norm_match_finish over its kept frames
+stk_status norm_match_ecc(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                          const stk_local_norm_params* norm, const NormCombine& nc, const float* weights, stk_image_f32* out,
+                          float* const* norm_out, stk_frame_weight* applied, stk_frame_stats* stats) {
+    stk_status st = norm_match_check(ctx, frames, norm, nc, out);
+    if (st) return st;
+    NormLayout L;
+    if ((st = norm_match_reserve(ctx, frames, norm, &L))) return st;
+    return ecc_match_then(ctx, frames, params, scale_down_width, (float*)(ctx->local.as<char>() + L.image), stats,
+                          norm_match_finish(ctx, L, frames->n, norm, nc, weights, out, norm_out, applied));
+}
+
+stk_status norm_match_keypoint(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,
+                               const stk_local_norm_params* norm, const NormCombine& nc, const float* weights, stk_image_f32* out,
+                               int32_t* dropped, float* const* norm_out, stk_frame_weight* applied, stk_frame_stats* stats) {
+    stk_status st = norm_match_check(ctx, frames, norm, nc, out);
+    if (st) return st;
+    if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
+    // the mean alone needs the weighted combine's border under coverage = 1; participation puts no condition on it
+    const bool mean = !nc.quantile && !nc.clip && !nc.mad;
+    if (mean && norm->coverage && (st = weighted_check_border(ctx, params->border_mode, params->border_value, 1))) return st;
+    NormLayout L;
+    if ((st = norm_match_reserve(ctx, frames, norm, &L))) return st;
+    return keypoint_match_then(ctx, frames, params, scale_down_width, (float*)(ctx->local.as<char>() + L.image), dropped, stats,
+                               norm_match_finish(ctx, L, frames->n, norm, nc, weights, out, norm_out, applied));
+}
+
+// exactly one of the two clips of a *_local_normalized_clipped call
+stk_status norm_clip_choice(stk_ctx* ctx, const stk_clip_params* clip, const stk_robust_clip_params* robust, int32_t* counts, float* kept,
+                            NormCombine* nc) {
+    if ((clip != nullptr) == (robust != nullptr))
+        return fail(ctx, STK_INVALID_PARAMS, "local normalisation: exactly one of the sigma clip and the median / MAD clip parameters must be given");
+    nc->clip = clip; nc->mad = robust; nc->counts = counts; nc->kept = kept;
+    return STK_OK;
+}
+
+// the checks the two caller-held clip forms share: stk_clip_stack_weighted's, with the clip's own between
+stk_status norm_clip_stack_check(stk_ctx* ctx, const stk_frames* frames, int border_mode, int coverage) {
+    stk_status st = check_frames(ctx, frames, false);
+    if (st) return st;
+    // (as stk_clip_stack_weighted: coverage = 1 puts no condition on the border mode or value)
+    if ((st = check_border_mode(ctx, border_mode))) return st;
+    if (coverage < 0 || coverage > 1) return fail(ctx, STK_INVALID_PARAMS, "weighted: coverage must be 0 or 1");
+    return STK_OK;
 }
 
 }  // namespace
@@ -314,8 +384,9 @@ stk_status stk_local_norm_stack(stk_ctx* ctx, const stk_frames* frames, const do
     stk_status st = check_frames(ctx, frames, false);
     if (st) return st;
     if ((st = weighted_check_border(ctx, border_mode, border_value, coverage))) return st;
-    return norm_stack(ctx, frames, M, include, is_affine, border_mode, border_value, alpha, nullptr, per_frame, norm, step, coverage, out,
-                      den_out, nullptr);
+    NormCombine nc;
+    nc.den = den_out;
+    return norm_stack(ctx, frames, M, include, is_affine, border_mode, border_value, alpha, nc, per_frame, norm, step, coverage, out);
 }
 
 stk_status stk_quantile_stack_local_norm(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include,
@@ -328,8 +399,9 @@ stk_status stk_quantile_stack_local_norm(stk_ctx* ctx, const stk_frames* frames,
     if ((st = check_border_mode(ctx, border_mode))) return st;
     if (coverage < 0 || coverage > 1) return fail(ctx, STK_INVALID_PARAMS, "weighted: coverage must be 0 or 1");
     if ((st = quantile_validate(ctx, quantile))) return st;
-    return norm_stack(ctx, frames, M, include, is_affine, border_mode, border_value, alpha, quantile, per_frame, norm, step, coverage, out,
-                      nullptr, counts);
+    NormCombine nc;
+    nc.quantile = quantile; nc.counts = counts;
+    return norm_stack(ctx, frames, M, include, is_affine, border_mode, border_value, alpha, nc, per_frame, norm, step, coverage, out);
 }
 
 stk_status stk_ecc_match_local_normalized(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
@@ -337,12 +409,9 @@ stk_status stk_ecc_match_local_normalized(stk_ctx* ctx, const stk_frames* frames
                                           stk_image_f32* out, float* den_out, int32_t* counts, float* const* norm_out,
                                           stk_frame_weight* applied, stk_frame_stats* stats) {
     if (!ctx) return STK_INVALID_PARAMS;
-    stk_status st = norm_match_check(ctx, frames, norm, quantile, out, den_out, counts);
-    if (st) return st;
-    NormLayout L;
-    if ((st = norm_match_reserve(ctx, frames, norm, &L))) return st;
-    return ecc_match_then(ctx, frames, params, scale_down_width, (float*)(ctx->local.as<char>() + L.image), stats,
-                          norm_match_finish(ctx, L, frames->n, norm, quantile, weights, out, den_out, counts, norm_out, applied));
+    NormCombine nc;
+    nc.quantile = quantile; nc.den = den_out; nc.counts = counts;
+    return norm_match_ecc(ctx, frames, params, scale_down_width, norm, nc, weights, out, norm_out, applied, stats);
 }
 
 stk_status stk_keypoint_match_local_normalized(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
@@ -351,14 +420,59 @@ stk_status stk_keypoint_match_local_normalized(stk_ctx* ctx, const stk_frames* f
                                                int32_t* dropped, float* den_out, int32_t* counts, float* const* norm_out,
                                                stk_frame_weight* applied, stk_frame_stats* stats) {
     if (!ctx) return STK_INVALID_PARAMS;
-    stk_status st = norm_match_check(ctx, frames, norm, quantile, out, den_out, counts);
+    NormCombine nc;
+    nc.quantile = quantile; nc.den = den_out; nc.counts = counts;
+    return norm_match_keypoint(ctx, frames, params, scale_down_width, norm, nc, weights, out, dropped, norm_out, applied, stats);
+}
+
+stk_status stk_clip_stack_local_norm(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
+                                     int32_t border_mode, const double* border_value, double alpha, const stk_clip_params* clip,
+                                     const stk_frame_weight* per_frame, const float* const* norm, int32_t step, int32_t coverage,
+                                     stk_image_f32* out, int32_t* counts, float* kept_weight) {
+    stk_status st = norm_clip_stack_check(ctx, frames, border_mode, coverage);
     if (st) return st;
-    if (!params) return fail(ctx, STK_INVALID_PARAMS, "null parameters");
-    if (!quantile && norm->coverage && (st = weighted_check_border(ctx, params->border_mode, params->border_value, 1))) return st;
-    NormLayout L;
-    if ((st = norm_match_reserve(ctx, frames, norm, &L))) return st;
-    return keypoint_match_then(ctx, frames, params, scale_down_width, (float*)(ctx->local.as<char>() + L.image), dropped, stats,
-                               norm_match_finish(ctx, L, frames->n, norm, quantile, weights, out, den_out, counts, norm_out, applied));
+    if ((st = clip_validate(ctx, clip))) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    NormCombine nc;
+    nc.clip = clip; nc.counts = counts; nc.kept = kept_weight;
+    return norm_stack(ctx, frames, M, include, is_affine, border_mode, border_value, alpha, nc, per_frame, norm, step, coverage, out);
+}
+
+stk_status stk_robust_clip_stack_local_norm(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include,
+                                            int32_t is_affine, int32_t border_mode, const double* border_value, double alpha,
+                                            const stk_robust_clip_params* clip, const stk_frame_weight* per_frame,
+                                            const float* const* norm, int32_t step, int32_t coverage, stk_image_f32* out,
+                                            int32_t* counts, float* kept_weight) {
+    stk_status st = norm_clip_stack_check(ctx, frames, border_mode, coverage);
+    if (st) return st;
+    if ((st = robust_clip_validate(ctx, clip))) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    NormCombine nc;
+    nc.mad = clip; nc.counts = counts; nc.kept = kept_weight;
+    return norm_stack(ctx, frames, M, include, is_affine, border_mode, border_value, alpha, nc, per_frame, norm, step, coverage, out);
+}
+
+stk_status stk_ecc_match_local_normalized_clipped(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params,
+                                                  float scale_down_width, const stk_local_norm_params* norm, const stk_clip_params* clip,
+                                                  const stk_robust_clip_params* robust, const float* weights, stk_image_f32* out,
+                                                  int32_t* counts, float* kept_weight, float* const* norm_out,
+                                                  stk_frame_weight* applied, stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    NormCombine nc;
+    if (stk_status st = norm_clip_choice(ctx, clip, robust, counts, kept_weight, &nc)) return st;
+    return norm_match_ecc(ctx, frames, params, scale_down_width, norm, nc, weights, out, norm_out, applied, stats);
+}
+
+stk_status stk_keypoint_match_local_normalized_clipped(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                                       float scale_down_width, const stk_local_norm_params* norm,
+                                                       const stk_clip_params* clip, const stk_robust_clip_params* robust,
+                                                       const float* weights, stk_image_f32* out, int32_t* dropped, int32_t* counts,
+                                                       float* kept_weight, float* const* norm_out, stk_frame_weight* applied,
+                                                       stk_frame_stats* stats) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    NormCombine nc;
+    if (stk_status st = norm_clip_choice(ctx, clip, robust, counts, kept_weight, &nc)) return st;
+    return norm_match_keypoint(ctx, frames, params, scale_down_width, norm, nc, weights, out, dropped, norm_out, applied, stats);
 }
 
 }  // extern "C"

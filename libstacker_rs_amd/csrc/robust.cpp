@@ -32,9 +32,11 @@ stk_status coef_upload(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef) 
 }
 
 // The weighted clip over the entries of ctx->warpframes with the records `coef`: the centre pass, then iterations + 1
-// passes. Writes `out`, `counts` and `kept` (out's location); adds its device time to *ms.
+// passes. Writes `out`, `counts` and `kept` (out's location); adds its device time to *ms. norm: the locally normalised clip
+// (local_norm.cpp): the same planes and passes through its plane table.
 stk_status clip_passes_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage,
-                                const stk_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms) {
+                                const stk_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms,
+                                const NormFoldArgs* norm = nullptr) {
     const int w = spec.w, cn = spec.cn, depth = spec.depth;
     const size_t nel = (size_t)w * spec.h * cn;
     const ClipLayout L = clip_layout(nel);
@@ -55,14 +57,16 @@ stk_status clip_passes_weighted(stk_ctx* ctx, const std::vector<stk_frame_weight
     ca.kappa_low = p->kappa_low; ca.kappa_high = p->kappa_high;
     ca.coef = ctx->coef.as<stk_frame_weight>();
     ca.coverage = coverage;
+    if (norm) norm_fold_clip_args(*norm, ca);
+    const auto launch_pass = norm ? launch_clip_pass_norm : launch_clip_pass_weighted;
     if ((st = combine_begin(ctx))) return st;
     ca.centre = 1; ca.first = 1; ca.last = 0;
-    HIP_TRY(launch_clip_pass_weighted(a, ca, depth, ctx->stream));
+    HIP_TRY(launch_pass(a, ca, depth, ctx->stream));
     ca.centre = 0;
     for (int t = 1; t <= p->iterations + 1; t++) {
         ca.first = t == 1;
         ca.last = t == p->iterations + 1;
-        HIP_TRY(launch_clip_pass_weighted(a, ca, depth, ctx->stream));
+        HIP_TRY(launch_pass(a, ca, depth, ctx->stream));
     }
     return combine_end(ctx, ms, &o);
 }
@@ -207,6 +211,11 @@ stk_status robust_match_records(stk_ctx* ctx, const stk_frames* frames, const st
 stk_status quantile_bands_norm(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage,
                                const stk_quantile_params* p, const NormFoldArgs& norm, stk_image_f32* out, int32_t* counts, double* ms) {
     return quantile_bands_weighted(ctx, coef, spec, coverage, p, out, counts, ms, &norm);
+}
+
+stk_status clip_passes_norm(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage,
+                            const stk_clip_params* p, const NormFoldArgs& norm, stk_image_f32* out, int32_t* counts, float* kept, double* ms) {
+    return clip_passes_weighted(ctx, coef, spec, coverage, p, out, counts, kept, ms, &norm);
 }
 
 stk_status robust_match_median(stk_ctx* ctx, const stk_frames* frames, const std::vector<stk_frame_weight>& coef, int is_affine,

@@ -29,7 +29,9 @@ stk_status robust_clip_validate(stk_ctx* ctx, const stk_robust_clip_params* p) {
 }
 
 stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_frame_weight>* coef, const FoldSpec& spec, int coverage,
-                             const stk_robust_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms) {
+                             const stk_robust_clip_params* p, stk_image_f32* out, int32_t* counts, float* kept, double* ms,
+                             const NormFoldArgs* norm) {
+    if (norm && !coef) return fail(ctx, STK_INVALID_PARAMS, "robust clipping: a plane table needs the record table");
     const int w = spec.w, h = spec.h, cn = spec.cn, depth = spec.depth;
     stk_status st = quantile_check_count(ctx, n_entries);
     if (st) return st;
@@ -58,6 +60,7 @@ stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_
         ca.coef = ctx->coef.as<stk_frame_weight>();
         ca.coverage = coverage;
     }
+    if (norm) norm_fold_clip_args(*norm, ca);        // the locally normalised form (local_norm.cpp): its own store launch and last pass
     const size_t n_bands = ((size_t)h + R - 1) / R;
     while (ctx->select_ev.size() < n_bands) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -70,7 +73,9 @@ stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_
         const size_t rows = std::min(R, (size_t)h - y0);
         ca.y0 = (int)y0; ca.band_rows = (int)rows;
         a.dh = (int)(y0 + rows);
-        HIP_TRY(coef ? launch_quantile_store_weighted(a, ca, depth, ctx->stream) : launch_quantile_store(a, ca, depth, ctx->stream));
+        HIP_TRY(norm   ? launch_norm_store(a, ca, depth, ctx->stream)
+                : coef ? launch_quantile_store_weighted(a, ca, depth, ctx->stream)
+                       : launch_quantile_store(a, ca, depth, ctx->stream));
         HIP_TRY(hipEventRecord(ctx->select_ev[b].first, ctx->stream));
         HIP_TRY(launch_robust_select(band, rows * row, n_entries, coef ? 1 : 0, *p, ca.c + y0 * row, ca.L + y0 * row, ca.U + y0 * row,
                                      ctx->stream));
@@ -79,7 +84,9 @@ stk_status robust_clip_bands(stk_ctx* ctx, int n_entries, const std::vector<stk_
     // the planes are complete: the last pass of the (weighted) clip over the whole frame
     a.dh = h;
     ca.first = 0; ca.last = 1; ca.centre = 0;
-    HIP_TRY(coef ? launch_clip_pass_weighted(a, ca, depth, ctx->stream) : launch_clip_pass(a, ca, depth, ctx->stream));
+    HIP_TRY(norm   ? launch_clip_pass_norm(a, ca, depth, ctx->stream)
+            : coef ? launch_clip_pass_weighted(a, ca, depth, ctx->stream)
+                   : launch_clip_pass(a, ca, depth, ctx->stream));
     if ((st = combine_end(ctx, ms, &o))) return st;
     double sel = 0.0;
     for (size_t k = 0; k < n_bands; k++) sel += ev_ms(ctx->select_ev[k].first, ctx->select_ev[k].second);

@@ -22,7 +22,8 @@
 // clip (ClipWGeneric<CN> / ClipWU8C3, kernels_clip.hip) and the store mode with participation (FoldStoreW<CN>, below).
 // Local normalisation adds two more of that kind (FoldNorm<CN>, FoldStoreNorm<CN>, below; launched from
 // kernels_local_norm.hip): the weighted mode and the store mode with participation with the entry's gain and offset
-// interpolated from a node grid. Generic kernels only.
+// interpolated from a node grid. Generic kernels only. The weighted clip through the same planes (ClipNorm<CN> /
+// ClipNormU8C3, kernels_clip.hip) runs on every kernel the weighted clip runs on, the u8 BGR fast ones included.
 // The bicubic fold (warp_cubic_body.h) is a second kernel that speaks the same hooks. What it shares with the generic kernel
 // here is shared as text, in two fragments that both include inside their frame loops: the coordinates and the bilinear
 // sample (warp_coords.inc.h, warp_linear_sample.inc.h). Text, not helper functions: see the note at
@@ -43,6 +44,8 @@ template <int CN> struct FoldNorm;
 template <int CN> struct FoldStoreNorm;
 template <int CN> struct ClipWGeneric;
 struct ClipWU8C3;
+template <int CN> struct ClipNorm;
+struct ClipNormU8C3;
 struct NoClip;
 // The mesh variant of the generic kernel (kernels_mesh.hip; definition: include/stacker.h, "Mesh fold"): a state wrapped in
 // Mesh<> runs the same hooks at coordinates displaced by the entry's field. A wrapper around the state, not a further
@@ -124,7 +127,8 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
     constexpr bool MOMENTS = std::is_same_v<ClipState, FoldMoments<CN>>;
     // the normalised, coverage-aware rejection states (kernels_clip.hip, FoldStoreW below) take kappa like the weighted mode
     constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>> ||
-                            std::is_same_v<ClipState, FoldNorm<CN>> || std::is_same_v<ClipState, FoldStoreNorm<CN>>;   // (and the two local-normalisation states)
+                            std::is_same_v<ClipState, FoldNorm<CN>> || std::is_same_v<ClipState, FoldStoreNorm<CN>> ||   // (and the two local-normalisation states)
+                            std::is_same_v<ClipState, ClipNorm<CN>>;                                                  // (and the clip through them)
     constexpr bool LOCAL = std::is_same_v<ClipState, FoldLocal<CN>> || std::is_same_v<ClipState, Mesh<FoldLocal<CN>>>;   // kappa like the weighted mode, and the coordinates
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -697,7 +701,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_u8c3_kernel(WarpArgs a, C
                     if constexpr (CLIP) vr = v; else s2 = s2 + v;
                 }
                 if constexpr (std::is_same_v<ClipState, FoldWeighted<3>> || std::is_same_v<ClipState, ClipWU8C3> ||
-                              std::is_same_v<ClipState, FoldStoreW<3>>)
+                              std::is_same_v<ClipState, FoldStoreW<3>> || std::is_same_v<ClipState, ClipNormU8C3>)
                     cs.add3k(vb, vg, vr, STK_LERP(v00 ? 1.0f : 0.0f, v01 ? 1.0f : 0.0f, v10 ? 1.0f : 0.0f, v11 ? 1.0f : 0.0f));
                 else if constexpr (CLIP) cs.add3(vb, vg, vr);
             }
@@ -716,6 +720,14 @@ __global__ __launch_bounds__(256) void warp_accumulate_u8c3_kernel(WarpArgs a, C
 inline bool warp_u8c3_applies(const WarpArgs& a, int depth) {
     return depth == 8 && a.cn == 3 && a.subpixel_bits == 0 && a.border_mode == STK_BORDER_CONSTANT && a.sw >= 2 && a.sh >= 2 &&
            (size_t)a.sw * a.sh * 3 >= 16 && a.src_stride * (size_t)a.sh < ((size_t)1 << 31) && a.src_stride < (1u << 23) && a.sh < (1 << 23);
+}
+
+// the launch conditions of a fold through local-normalisation planes (host side): the tables are there and the grid is the
+// destination's (a store launch's a.dh is its band's end; c.norm_gh is the whole destination's, hence the >=)
+inline bool norm_args_ok(const WarpArgs& a, const ClipArgs& c) {
+    if (a.n_frames <= 0 || !c.norm || !c.coef || c.norm_shift < 3 || c.norm_shift > 8) return false;
+    const int step = 1 << c.norm_shift;
+    return c.norm_gw == (a.dw - 1 + step - 1) / step + 1 && c.norm_gh >= (a.dh - 1 + step - 1) / step + 1;
 }
 
 // The one (depth, cn) ladder of every launcher (host side): launch(T{}, Channels<CN>{}) for the sample type T of `depth`

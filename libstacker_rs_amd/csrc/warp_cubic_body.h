@@ -32,7 +32,8 @@ __global__ __launch_bounds__(256) void warp_accumulate_cubic_kernel(WarpArgs a, 
     constexpr bool WEIGHTED = std::is_same_v<ClipState, FoldWeighted<CN>>;
     constexpr bool MOMENTS = std::is_same_v<ClipState, FoldMoments<CN>>;
     constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>> ||
-                            std::is_same_v<ClipState, FoldNorm<CN>> || std::is_same_v<ClipState, FoldStoreNorm<CN>>;
+                            std::is_same_v<ClipState, FoldNorm<CN>> || std::is_same_v<ClipState, FoldStoreNorm<CN>> ||
+                            std::is_same_v<ClipState, ClipNorm<CN>>;
     constexpr bool LOCAL = std::is_same_v<ClipState, FoldLocal<CN>>;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -150,7 +151,7 @@ struct LinearCollect {
 template <bool AFFINE, int WU, bool MODE, class FastState>
 __global__ __launch_bounds__(256) void warp_accumulate_cubic_u8c3_kernel(WarpArgs a, ClipArgs ca) {
     constexpr bool KAPPA = std::is_same_v<FastState, FoldWeighted<3>> || std::is_same_v<FastState, ClipWU8C3> ||
-                           std::is_same_v<FastState, FoldStoreW<3>>;
+                           std::is_same_v<FastState, FoldStoreW<3>> || std::is_same_v<FastState, ClipNormU8C3>;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if constexpr (std::is_same_v<FastState, FoldStore<3>> || std::is_same_v<FastState, FoldStoreW<3>>) y += ca.y0;      // store mode: a band of rows (a.dh = its end)

@@ -9,7 +9,9 @@
 //!   decoded by OpenCV's `imread(IMREAD_UNCHANGED)` exactly as `read_grey_and_f32` does (utils.rs:132) and handed over
 //!   as host frames.
 use crate::amd_ffi::*;
-use crate::{utils, EccMatchParameters, KeyPointMatchParameters, LocalParameters, RobustClipParameters, StackerError};
+use crate::{
+    utils, EccMatchParameters, KeyPointMatchParameters, LocalNormParameters, LocalParameters, NormClip, RobustClipParameters, StackerError,
+};
 use opencv::core;
 use opencv::imgcodecs;
 use opencv::prelude::*;
@@ -402,6 +404,94 @@ pub(crate) fn keypoint_match_local_weighted(
     let st = unsafe {
         stk_keypoint_match_local_weighted(
             ctx, &frames, &p, scale_down_width.unwrap_or(0.0), &w, std::ptr::null(), &l, &mut img, &mut dropped, std::ptr::null_mut(),
+            std::ptr::null_mut(), std::ptr::null_mut(),
+        )
+    };
+    if st == STK_OK { Ok((dropped, out)) } else { Err(to_err(ctx, st)) }
+}
+
+fn local_norm_params(p: &LocalNormParameters) -> stk_local_norm_params {
+    stk_local_norm_params {
+        step: p.step,
+        stat_step: p.stat_step,
+        normalize: p.normalize,
+        coverage: 1,
+        min_count: p.min_count,
+        fill: p.fill,
+        reserved: [0, 0],
+    }
+}
+
+/// the clip of a `*_local_normalized_clipped` call as the pair the engine takes: exactly one of the two is set
+fn norm_clip_params(clip: &NormClip) -> (Option<stk_clip_params>, Option<stk_robust_clip_params>) {
+    match clip {
+        NormClip::Sigma(s) => {
+            (Some(stk_clip_params { kappa_low: s.kappa_low, kappa_high: s.kappa_high, iterations: s.iterations, reserved: 0 }), None)
+        }
+        NormClip::Robust(r) => (None, Some(robust_clip_params(r))),
+    }
+}
+
+/// `ecc_match` with local normalisation and rejection (include/stacker.h, stk_ecc_match_local_normalized_clipped): every
+/// moving frame is mapped onto frame 0 by a gain and an offset field on a node grid, and the samples are compared through
+/// those fields. The combine has no `*_files` form: the stack is decoded by OpenCV and handed over as host frames.
+pub(crate) fn ecc_match_local_normalized_clipped(
+    files: &[PathBuf],
+    params: EccMatchParameters,
+    norm: LocalNormParameters,
+    clip: NormClip,
+    scale_down_width: Option<f32>,
+) -> Result<Mat, StackerError> {
+    if files.is_empty() {
+        return Err(StackerError::NotEnoughFiles);
+    }
+    let guard = shared_ctx()?;
+    let ctx = guard.0;
+    let p = ecc_params(&params);
+    let n = local_norm_params(&norm);
+    let (c, r) = norm_clip_params(&clip);
+    let stack = DecodedStack::read(files)?;
+    let frames = stack.frames()?;
+    let (out, mut img) = new_output(frames.width, frames.height, frames.channels)?;
+    let st = unsafe {
+        stk_ecc_match_local_normalized_clipped(
+            ctx, &frames, &p, scale_down_width.unwrap_or(0.0), &n,
+            c.as_ref().map_or(std::ptr::null(), |v| v as *const stk_clip_params),
+            r.as_ref().map_or(std::ptr::null(), |v| v as *const stk_robust_clip_params),
+            std::ptr::null(), &mut img, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null(), std::ptr::null_mut(),
+            std::ptr::null_mut(),
+        )
+    };
+    if st == STK_OK { Ok(out) } else { Err(to_err(ctx, st)) }
+}
+
+/// `keypoint_match` with local normalisation and rejection (stk_keypoint_match_local_normalized_clipped): (dropped, image).
+/// One geometry for the whole stack, as the combine asks.
+pub(crate) fn keypoint_match_local_normalized_clipped(
+    files: &[PathBuf],
+    params: KeyPointMatchParameters,
+    norm: LocalNormParameters,
+    clip: NormClip,
+    scale_down_width: Option<f32>,
+) -> Result<(i32, Mat), StackerError> {
+    if files.is_empty() {
+        return Err(StackerError::NotEnoughFiles);
+    }
+    let guard = shared_ctx()?;
+    let ctx = guard.0;
+    let p = kp_params(&params);
+    let n = local_norm_params(&norm);
+    let (c, r) = norm_clip_params(&clip);
+    let stack = DecodedStack::read(files)?;
+    let frames = stack.frames()?;
+    let (out, mut img) = new_output(frames.width, frames.height, frames.channels)?;
+    let mut dropped: i32 = 0;
+    let st = unsafe {
+        stk_keypoint_match_local_normalized_clipped(
+            ctx, &frames, &p, scale_down_width.unwrap_or(0.0), &n,
+            c.as_ref().map_or(std::ptr::null(), |v| v as *const stk_clip_params),
+            r.as_ref().map_or(std::ptr::null(), |v| v as *const stk_robust_clip_params),
+            std::ptr::null(), &mut img, &mut dropped, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null(),
             std::ptr::null_mut(), std::ptr::null_mut(),
         )
     };

@@ -124,6 +124,51 @@ impl Default for LocalParameters {
     }
 }
 
+/// Local normalisation for the `*_local_normalized_clipped` combines, an extension beyond the reference
+/// (include/stacker.h, `stk_local_norm_params`): per moving frame a gain and an offset on a node grid of spacing `step`,
+/// estimated against frame 0 from the overlap's moments and interpolated bilinearly at every pixel.
+#[derive(Debug, Copy, Clone)]
+pub struct LocalNormParameters {
+    /// node spacing in pixels: 8, 16, 32, 64, 128 or 256
+    pub step: i32,
+    /// every `stat_step`-th pixel in x and y enters the moments: 1 ..= 64; 0 = 4
+    pub stat_step: i32,
+    /// 0 none, 1 offset, 2 gain, 3 linear
+    pub normalize: i32,
+    /// pixels a node's window needs to be valid; 0 = 16
+    pub min_count: i32,
+    /// hole-filling passes over the invalid nodes: 0 ..= 16
+    pub fill: i32,
+}
+
+impl Default for LocalNormParameters {
+    fn default() -> Self {
+        Self { step: 64, stat_step: 0, normalize: 3, min_count: 0, fill: 4 }
+    }
+}
+
+/// Kappa-sigma rejection (include/stacker.h, `stk_clip_params`): samples below c - `kappa_low` sigma or above
+/// c + `kappa_high` sigma are left out, `iterations` times, before the final mean of the kept samples.
+#[derive(Debug, Copy, Clone)]
+pub struct SigmaClipParameters {
+    pub kappa_low: f32,
+    pub kappa_high: f32,
+    pub iterations: i32,
+}
+
+impl Default for SigmaClipParameters {
+    fn default() -> Self {
+        Self { kappa_low: 3.0, kappa_high: 3.0, iterations: 2 }
+    }
+}
+
+/// Which rejection a `*_local_normalized_clipped` combine runs through the normalisation fields.
+#[derive(Debug, Copy, Clone)]
+pub enum NormClip {
+    Sigma(SigmaClipParameters),
+    Robust(RobustClipParameters),
+}
+
 /// lib.rs:129-137: aligns every frame to the first by ORB + brute-force Hamming + `findHomography`, warps and averages.
 /// Returns (number of frames that could not be matched and were left out, averaged CV_32FC3 image).
 #[cfg(feature = "amd")]
@@ -220,6 +265,41 @@ where
 {
     let files: Vec<PathBuf> = files.into_iter().map(|p| p.as_ref().to_path_buf()).collect();
     amd::keypoint_match_local_weighted(&files, params, local, normalize, scale_down_width)
+}
+
+/// `ecc_match` with every moving frame mapped onto frame 0 by local gain and offset fields and the aligned frames combined
+/// by a sigma clip or a median / MAD clip that compares the samples through those fields.
+#[cfg(feature = "amd")]
+pub fn ecc_match_local_normalized_clipped<I, P>(
+    files: I,
+    params: EccMatchParameters,
+    norm: LocalNormParameters,
+    clip: NormClip,
+    scale_down_width: Option<f32>,
+) -> Result<Mat, StackerError>
+where
+    I: IntoIterator<Item = P>,
+    P: AsRef<std::path::Path>,
+{
+    let files: Vec<PathBuf> = files.into_iter().map(|p| p.as_ref().to_path_buf()).collect();
+    amd::ecc_match_local_normalized_clipped(&files, params, norm, clip, scale_down_width)
+}
+
+/// `keypoint_match` with the kept frames combined by a clip through local normalisation fields.
+#[cfg(feature = "amd")]
+pub fn keypoint_match_local_normalized_clipped<I, P>(
+    files: I,
+    params: KeyPointMatchParameters,
+    norm: LocalNormParameters,
+    clip: NormClip,
+    scale_down_width: Option<f32>,
+) -> Result<(i32, Mat), StackerError>
+where
+    I: IntoIterator<Item = P>,
+    P: AsRef<std::path::Path>,
+{
+    let files: Vec<PathBuf> = files.into_iter().map(|p| p.as_ref().to_path_buf()).collect();
+    amd::keypoint_match_local_normalized_clipped(&files, params, norm, clip, scale_down_width)
 }
 
 /// lib.rs:1032 — 'LAPM' (Nayar89). Single-channel 8-bit or f32 image.
