@@ -1279,6 +1279,98 @@ stk_status stk_keypoint_match_local_normalized_clipped(stk_ctx* ctx, const stk_f
                                                        float* kept_weight_or_null, float* const* norm_out_or_null,
                                                        stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null);
 
+/* ---- star registration: detect stars, match triangles, align the stack: an EXTENSION beyond the reference ----------
+ * A third aligner beside stk_ecc_match and stk_keypoint_match, for 8-bit star fields (1, 3 or 4 channels; the whole-stack
+ * forms 3 or 4): BRIEF descriptors of point sources on a black sky are not distinctive, and ECC starts at the identity
+ * with a capture range of a few pixels. Stars are found as background-subtracted centroids, matched by triangle
+ * similarity (rotation-, scale- and flip-free up to the tolerance), fitted with findHomography. Depth 16 / 32:
+ * STK_NOT_IMPLEMENTED.
+ * Detection, all in integers (kernels_star.hip). g: the 8-bit grey (stk_grey's; one-channel frames as they are),
+ * r = radius, T: the 64 x 64 tile (origin at multiples of 64) that holds the pixel in question.
+ *   1. Tile statistics. n = the tile's pixels inside the frame, k = (n + 1) / 2; med_T = the k-th smallest g of the tile,
+ *      mad_T = the k-th smallest |g - med_T|; d_T = max((int)ceilf(ks * (float)mad_T), min_contrast) with
+ *      ks = (float)(kappa * 1.4826) (the product in double); thr_T = med_T + d_T.
+ *   2. Pixel p = (px, py) of tile T is a peak when r <= px < w - r and r <= py < h - r (the whole window inside the frame,
+ *      no reflection); g(p) >= thr_T; for every q != p of the (2r + 1)^2 window g(q) < g(p) if q precedes p in raster
+ *      order and g(q) <= g(p) otherwise (a plateau yields its raster-first pixel); and
+ *      npix = #{q in the window: g(q) >= thr_T} >= min_pixels (a hot pixel has npix 1).
+ *   3. Moments over the window with v(q) = max(g(q) - med_T, 0): S = sum v, Sx = sum v (qx - px), Sy = sum v (qy - py), int32.
+ *   4. Per tile the peaks are ranked by the key (S descending, py ascending, px ascending); the first STK_STAR_TILE_CAP are
+ *      kept. Per frame the tiles' peaks are merged, sorted by the same key and cut to max_stars. n_peaks counts every peak
+ *      of the frame, those beyond a tile's cap and beyond max_stars included.
+ *   5. x = (float)((double)px + (double)Sx / (double)S), y likewise, flux = (float)S; peak = g(p).
+ *   The same bits on every call: no float arithmetic but the one multiply and ceil, no ordering races.
+ * Matching (star_match.cpp: host only, f64 on the f32 coordinates; a distance is sqrt(dx*dx + dy*dy)).
+ *   1. Triangles of a list: P = its first min(match_stars, count) stars. For each star i its `neighbours` nearest others in
+ *      P (ties: lower index; fewer when P is smaller); one triangle for every pair of them with i; deduplicated by the sorted
+ *      index triple and kept in that (lexicographic) order. Sides a >= b >= c, a side named by its opposite vertex, ties
+ *      to the lower opposite vertex index; skipped when a <= 0 or c / a < 0.1. Descriptor (b / a, c / a); vertices listed
+ *      as (opposite a, opposite b, opposite c).
+ *   2. Votes: each triangle of the moving list takes the reference triangle of smallest squared descriptor distance (ties:
+ *      lower index), accepted when that is <= tri_tolerance^2; an accepted pair adds one vote to each of its three vertex
+ *      correspondences.
+ *   3. Pairs: moving star i pairs with j = argmax of row i (lowest j on ties) when votes >= min_votes and i is the argmax
+ *      of column j (lowest i on ties); in ascending i.
+ *   4. Fit: with >= 4 pairs, findHomography(moving -> frame 0, method, ransac_reproj_threshold) as stk_find_homography.
+ *   5. Refine (refine = 1): every star of the frame is projected by H; it pairs with the nearest reference star (all of
+ *      frame 0's stars) at distance <= ransac_reproj_threshold (ties: lower index) when it is in turn the nearest projected
+ *      star of that reference star (ties: lower index); with >= 4 such pairs a second fit, kept when found with at least
+ *      the first fit's inliers.
+ *   6. A frame is DROPPED (status 1, never an error) with fewer than min_stars stars (frame 0 below min_stars drops every
+ *      frame), fewer than 4 pairs, no model, or fewer than min_inliers inliers. Every moving frame dropped: the call fails
+ *      as stk_keypoint_match does (STK_INVALID_PARAMS), the stats filled all the same.
+ *   Stats: n_keypoints = the stars kept, n_matches = the pairs of the last fit run, n_inliers and warp = the kept fit's
+ *   (frame 0: its stars, the identity).
+ * Checks: radius 2 .. 7, kappa finite and >= 0, min_contrast 1 .. 255, min_pixels 1 .. (2r+1)^2, max_stars 4 .. 1024,
+ *   match_stars 4 .. 200, neighbours 2 .. 8, tri_tolerance finite and > 0, min_votes >= 1, refine 0 / 1, min_stars >= 4,
+ *   min_inliers >= 4, method 0 / STK_METHOD_LMEDS / STK_METHOD_RANSAC (RHO, USAC: STK_NOT_IMPLEMENTED), threshold finite and
+ *   > 0, border_mode as stk_keypoint_match: STK_INVALID_PARAMS otherwise. The stack forms need n >= 2 (STK_NOT_ENOUGH_FILES).
+ * A multi-device context runs these calls on its first device. Follow-ups, not here: 16-bit and f32 detection, a similarity
+ * or affine model for fields of fewer than about 12 stars, whole-stack star_match_* forms of each combine, a shard form, a
+ * files form, an interpolated (non-piecewise) background, a device-side matcher. */
+enum { STK_STAR_TILE_CAP = 32 };
+typedef struct {
+    float   x, y, flux;
+    int32_t px, py, peak, npix, reserved;
+} stk_star;
+typedef struct {
+    int32_t radius;                 /* 2 .. 7, default 4 */
+    float   kappa;                  /* default 4 */
+    int32_t min_contrast;           /* >= 1, default 8 */
+    int32_t min_pixels;             /* 1 .. (2r+1)^2, default 3 */
+    int32_t max_stars;              /* 4 .. 1024, default 200 */
+    int32_t match_stars;            /* brightest m used for triangles, 4 .. 200, default 50 */
+    int32_t neighbours;             /* 2 .. 8, default 5 */
+    double  tri_tolerance;          /* default 0.01 */
+    int32_t min_votes;              /* default 2 */
+    int32_t refine;                 /* 1 (default): guided re-match of all stars under the first H */
+    int32_t min_stars;              /* a frame with fewer detected stars is dropped, >= 4, default 6 */
+    int32_t min_inliers;            /* >= 4, default 7: a homography fits ANY four pairs exactly, so 4 rejects nothing; a frame
+                                       of another star field reached 4 - 6 inliers in 80 seeded trials, a true 12-star field 13 */
+    int32_t method;                 /* STK_METHOD_*, as stk_keypoint_params */
+    double  ransac_reproj_threshold;   /* default 2.0 */
+    int32_t border_mode;            /* STK_BORDER_* (stk_star_match's fold) */
+    double  border_value[4];
+} stk_star_params;
+
+/* The stars of every frame, brightest first: stars holds n x max_stars entries (frame i from i * max_stars; entries from
+ * n_stars[i] on are zeroed), n_stars n counts, n_peaks_or_null n counts before truncation. Host or device frames, padded
+ * rows, 1 / 3 / 4 channels. All outputs are host memory. */
+stk_status stk_star_detect(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, stk_star* stars,
+                           int32_t* n_stars, int32_t* n_peaks_or_null);
+/* Steps 1 - 3 on two lists; no context, no GPU. pairs: up to match_stars x 2 int32 (moving index, reference index). */
+stk_status stk_star_match_lists(const stk_star* moving, int32_t n_moving, const stk_star* ref, int32_t n_ref,
+                                const stk_star_params* params, int32_t* pairs, int32_t* n_pairs);
+/* Detection and steps 1 - 6, no fold: stats (n entries) feed any *_stack combine as M with include[i] = (status == 0) and
+ * is_affine = 0. dropped: the number of moving frames dropped. */
+stk_status stk_star_align(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, int32_t* dropped,
+                          stk_frame_stats* stats);
+/* stk_star_align, then the plain mean over frame 0 and the kept frames: by definition stk_warp_accumulate of those frames
+ * under the stats' warps in frame order (alpha 1 / 255, the params' border, never affine), then
+ * stk_finalize_mean(n - dropped), bit for bit. */
+stk_status stk_star_match(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, stk_image_f32* out,
+                          int32_t* dropped, stk_frame_stats* stats_or_null);
+
 /* ---- stage-level entry points (parity tests bind these) ------------------ */
 /* cvt_color(BGR2GRAY) on the integer image, utils.rs:136-142. out: w*h of the input depth
  * (u8 / u16 / f32), tightly packed, same location as the frame. */

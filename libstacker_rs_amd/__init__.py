@@ -13,10 +13,12 @@ from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_RE
                   LEAST_SQUARES, LMEDS, RANSAC, RHO, DrizzleParameters, EccMatchParameters, HipError, InvalidParams, IoError,
                   KeyPointMatchParameters, LocalNormParameters, LocalParameters, MeshParameters, MotionType, NotEnoughFiles, NotImplementedYet, OpenCvError,
                   ProcessingError, QuantileParameters, RejectParameters, RobustClipParameters, SelectParameters, SigmaClipParameters, Stacker,
-                  StackerError, WeightParameters,
-                  default_stacker, ecc_match, keypoint_match, local_norm_estimate, local_norm_grid, mesh_grid, mesh_pyramid_shapes, rank_frames)
+                  StackerError, StarParameters, STAR_DTYPE, WeightParameters,
+                  default_stacker, ecc_match, keypoint_match, local_norm_estimate, local_norm_grid, mesh_grid, mesh_pyramid_shapes, rank_frames,
+                  star_match_lists)
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
            "SelectParameters", "rank_frames", "LocalParameters", "MeshParameters", "mesh_grid", "mesh_pyramid_shapes", "DrizzleParameters",
-           "RejectParameters", "LocalNormParameters", "local_norm_estimate", "local_norm_grid"]
+           "RejectParameters", "LocalNormParameters", "local_norm_estimate", "local_norm_grid",
+           "StarParameters", "STAR_DTYPE", "star_match_lists"]

@@ -97,6 +97,19 @@ class SelectParams(C.Structure):
                 ("weight_mode", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Star(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("flux", C.c_float), ("px", C.c_int32), ("py", C.c_int32),
+                ("peak", C.c_int32), ("npix", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StarParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("kappa", C.c_float), ("min_contrast", C.c_int32), ("min_pixels", C.c_int32),
+                ("max_stars", C.c_int32), ("match_stars", C.c_int32), ("neighbours", C.c_int32), ("tri_tolerance", C.c_double),
+                ("min_votes", C.c_int32), ("refine", C.c_int32), ("min_stars", C.c_int32), ("min_inliers", C.c_int32),
+                ("method", C.c_int32), ("ransac_reproj_threshold", C.c_double), ("border_mode", C.c_int32),
+                ("border_value", C.c_double * 4)]
+
+
 class Timing(C.Structure):
     _fields_ = [("prep_ms", C.c_double), ("align_ms", C.c_double), ("warp_ms", C.c_double),
                 ("finalize_ms", C.c_double), ("ecc_iter_launches", C.c_int64),
@@ -286,6 +299,13 @@ SIGNATURES = {
                                                                C.POINTER(RobustClipParams), C.c_void_p, C.POINTER(ImageF32),
                                                                C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
                                                                C.POINTER(FrameWeight), C.POINTER(FrameStats)]),
+    "stk_star_detect": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(StarParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stk_star_match_lists": (c_status, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(StarParams), C.c_void_p,
+                                        C.POINTER(C.c_int32)]),
+    "stk_star_align": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(StarParams), C.POINTER(C.c_int32),
+                                  C.POINTER(FrameStats)]),
+    "stk_star_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(StarParams), C.POINTER(ImageF32), C.POINTER(C.c_int32),
+                                  C.POINTER(FrameStats)]),
     "stk_grey":(c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p]),
     "stk_convert_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_double, C.c_void_p]),
     "stk_hybrid_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.POINTER(EccParams),

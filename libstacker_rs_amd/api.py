@@ -172,6 +172,66 @@ class LocalParameters:            # extension beyond the reference: include/stac
         return _ffi.LocalParams(int(self.radius), int(self.threshold), int(self.power), float(self.floor), (C.c_int32 * 2)(0, 0))
 
 
+STAR_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("flux", "<f4"), ("px", "<i4"), ("py", "<i4"), ("peak", "<i4"),
+                       ("npix", "<i4"), ("reserved", "<i4")])          # stk_star
+
+
+@dataclass
+class StarParameters:             # extension beyond the reference: include/stacker.h, stk_star_params
+    """Star registration. Detection: a peak is the maximum of its (2 radius + 1)^2 window, at least
+    max(ceil(kappa 1.4826 MAD), min_contrast) above its 64 x 64 tile's median, with at least min_pixels window pixels that
+    high; the max_stars brightest are kept. Matching: triangles over each of the match_stars brightest stars and its
+    `neighbours` nearest, matched within tri_tolerance, at least min_votes per pair; `refine` re-matches all stars under
+    the first homography. A frame with fewer than min_stars stars or min_inliers inliers is dropped. method, threshold
+    and border as KeyPointMatchParameters."""
+    radius: int = 4
+    kappa: float = 4.0
+    min_contrast: int = 8
+    min_pixels: int = 3
+    max_stars: int = 200
+    match_stars: int = 50
+    neighbours: int = 5
+    tri_tolerance: float = 0.01
+    min_votes: int = 2
+    refine: bool = True
+    min_stars: int = 6
+    min_inliers: int = 7              # not 4: four pairs always fit a homography exactly, so 4 rejects nothing (DESIGN §4.23)
+    method: int = 8                   # RANSAC
+    ransac_reproj_threshold: float = 2.0
+    border_mode: int = 0              # BORDER_CONSTANT
+    border_value: Sequence[float] = (0.0, 0.0, 0.0, 0.0)
+
+    def _c(self) -> _ffi.StarParams:
+        bv = (C.c_double * 4)(*([float(v) for v in self.border_value] + [0.0] * 4)[:4])
+        return _ffi.StarParams(int(self.radius), float(self.kappa), int(self.min_contrast), int(self.min_pixels), int(self.max_stars),
+                               int(self.match_stars), int(self.neighbours), float(self.tri_tolerance), int(self.min_votes),
+                               int(self.refine), int(self.min_stars), int(self.min_inliers), int(self.method),
+                               float(self.ransac_reproj_threshold), int(self.border_mode), bv)
+
+
+def star_match_lists(moving, ref, params: Optional["StarParameters"] = None):
+    """Triangle matching of two star lists (stk_star_match_lists; host code, no GPU): a k x 2 int32 array of (moving index,
+    reference index) pairs in ascending moving index. The lists are STAR_DTYPE arrays, or n x 2 arrays of (x, y)."""
+    def as_stars(a):
+        a = np.asarray(a)
+        if a.dtype == STAR_DTYPE:
+            return np.ascontiguousarray(a)
+        s = np.zeros(len(a), STAR_DTYPE)
+        if len(a):
+            xy = np.asarray(a, np.float32).reshape(len(a), -1)
+            s["x"], s["y"] = xy[:, 0], xy[:, 1]
+        return s
+    mv, rf = as_stars(moving), as_stars(ref)
+    p = (params or StarParameters())._c()
+    pairs = np.zeros((max(int(p.match_stars), 1), 2), np.int32)
+    n = C.c_int32(0)
+    st = _ffi.load().stk_star_match_lists(C.c_void_p(mv.ctypes.data if len(mv) else 0), len(mv), C.c_void_p(rf.ctypes.data if len(rf) else 0),
+                                          len(rf), C.byref(p), C.c_void_p(pairs.ctypes.data), C.byref(n))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("star_match_lists: bad parameters or star lists")
+    return pairs[:n.value].copy()
+
+
 @dataclass
 class LocalNormParameters:        # extension beyond the reference: include/stacker.h, stk_local_norm_params
     """Local normalisation: per frame a gain and an offset field on a grid of nodes `step` destination pixels apart (a power
@@ -1209,6 +1269,49 @@ class Stacker:
         lp = (local or LocalParameters())._c()
         self._check(self._lib.stk_local_sharpness(self._h, C.byref(m.c_frames), C.byref(lp), C.cast(ptrs, C.c_void_p)))
         return maps
+
+    # -- star registration (extension beyond the reference) ------------------------------------------------
+    def star_detect(self, files, params: Optional["StarParameters"] = None, return_peaks: bool = False):
+        """The stars of every frame of an 8-bit stack (stk_star_detect), brightest first: a list of n STAR_DTYPE arrays;
+        return_peaks adds the n peak counts before truncation."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        p = (params or StarParameters())._c()
+        cap = max(int(p.max_stars), 1)
+        stars = np.zeros((m.n, cap), STAR_DTYPE)
+        n_stars = np.zeros(m.n, np.int32)
+        n_peaks = np.zeros(m.n, np.int32)
+        self._check(self._lib.stk_star_detect(self._h, C.byref(m.c_frames), C.byref(p), C.c_void_p(stars.ctypes.data),
+                                              C.c_void_p(n_stars.ctypes.data), C.c_void_p(n_peaks.ctypes.data)))
+        lists = [stars[i, :n_stars[i]].copy() for i in range(m.n)]
+        return (lists, n_peaks) if return_peaks else lists
+
+    star_match_lists = staticmethod(star_match_lists)
+
+    def star_align(self, files, params: Optional["StarParameters"] = None):
+        """Star registration without the fold (stk_star_align): (dropped, stats). The stats' warps feed any *_stack combine
+        with include = [s["status"] == 0 for s in stats] and is_affine = False."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        p = (params or StarParameters())._c()
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        self._check(self._lib.stk_star_align(self._h, C.byref(m.c_frames), C.byref(p), C.byref(dropped), stats))
+        return dropped.value, self._stats_list(stats, m.n)
+
+    def star_match(self, files, params: Optional["StarParameters"] = None, return_stats: bool = False):
+        """Star registration and the plain mean over frame 0 and the kept frames (stk_star_match): (dropped, image[, stats])."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        p = (params or StarParameters())._c()
+        out, img = self._out_image(m)
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        self._check(self._lib.stk_star_match(self._h, C.byref(m.c_frames), C.byref(p), C.byref(img), C.byref(dropped), stats))
+        return (dropped.value, out, self._stats_list(stats, m.n)) if return_stats else (dropped.value, out)
 
     def _maps_arg(self, m: _Marshalled, maps):
         """n tightly packed H x W float32 planes where the frames live: (owners, pointer array)."""

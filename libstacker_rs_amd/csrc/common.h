@@ -298,6 +298,26 @@ hipError_t launch_local_fold(const WarpArgs& a, const ClipArgs& c, int depth, hi
 int local_map_tiles(int w, int h);
 hipError_t launch_local_maps(const void* const* frames_dev, float* const* maps_dev, int n, int cn, int w, int h, size_t stride_bytes,
                              int radius, int threshold, hipStream_t s);
+// star detection over n 8-bit frames (cn 1, 3 or 4; frames_dev: a device array of n frame pointers) in one launch
+// (kernels_star.hip; definition: include/stacker.h, stk_star_params); n <= 65535. Per (frame, tile of 64 x 64): counts[frame *
+// tiles + tile] = the tile's peaks, records[(frame * tiles + tile) * STAR_TILE_CAP + rank] = the peak of that rank under the
+// key (S descending, py ascending, px ascending), rank < STAR_TILE_CAP; slots from min(count, STAR_TILE_CAP) on are not written
+constexpr int STAR_TILE_CAP = 32;            // include/stacker.h: STK_STAR_TILE_CAP
+struct StarRecord { int32_t px, py, S, Sx, Sy, peak, npix, pad; };
+struct StarDetectArgs {
+    const void* const* frames;
+    int32_t* counts;
+    StarRecord* records;
+    int w, h;
+    size_t stride;               // bytes per frame row
+    int tiles_x, tiles;
+    int radius;
+    float ks;                    // (float)(kappa * 1.4826), from the host
+    int min_contrast, min_pixels;
+};
+int star_tiles(int w, int h);
+hipError_t launch_star_detect(const void* const* frames_dev, int n, int cn, int w, int h, size_t stride_bytes, int radius, float ks,
+                              int min_contrast, int min_pixels, int32_t* counts, StarRecord* records, hipStream_t s);
 // local alignment (kernels_mesh.hip; definition: include/stacker.h, stk_mesh_params). Entry 0 of `frames` is frame 0 (its
 // matrix is not read); entries 1 .. n_entries - 1 are the frames that get a field: fields[k] (gh x gw x 2 f32) and status[k]
 // (gh x gw int32; the array or an entry may be null) are indexed like the table

@@ -1,0 +1,274 @@
+// star.cpp — star registration: stk_star_detect, stk_star_align, stk_star_match (an extension beyond the reference;
+// definition in include/stacker.h, stk_star_params; kernel in kernels_star.hip, the host matching in star_match.cpp).
+// ctx->local (StarLayout, workspace.h) holds the frame pointer table and, per (frame, tile), the peak count and the
+// record slots; one copy of the counts and one of the records bring a stack's detection back. The triangle and vote steps
+// of the frames run on the context's host pool (frame 0's triangles are built once); the fits are findHomography's
+// batched device path (homography.h), unchanged, one batch per stack as in keypoint.cpp; the fold is the plain one over the
+// table of frame 0 and the kept frames.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <functional>
+
+#include "context.h"
+#include "host_pool.h"
+#include "star_match.h"
+
+using namespace stk;
+
+namespace {
+
+// run fn(i) for i in [0, n) on the context's host pool (pure host work), as keypoint.cpp does
+void star_parallel_for(stk_ctx* ctx, int n, const std::function<void(int)>& fn) {
+    const int threads = ctx->opt_kp_workers;
+    if (threads <= 1 || n <= 1) { for (int i = 0; i < n; i++) fn(i); return; }
+    if (ctx->shared_pool) { ctx->shared_pool->run(n, fn); return; }
+    if (!ctx->host_pool || ctx->host_pool->size() != threads - 1) {
+        host_pool_destroy(ctx->host_pool);
+        ctx->host_pool = new HostPool(threads - 1);          // the caller is the remaining thread
+    }
+    ctx->host_pool->run(n, fn);
+}
+
+stk_status star_check(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, bool stack_form, bool folds) {
+    stk_status st = check_frames(ctx, frames, stack_form, folds);
+    if (st) return st;
+    bool ni = false;
+    if (const char* msg = star::validate(params, &ni)) return fail(ctx, ni ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS, msg);
+    if (folds && (params->border_mode < 0 || params->border_mode > 4))
+        return fail(ctx, params->border_mode == STK_BORDER_TRANSPARENT ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS, "unsupported border mode");
+    if (frames->depth != 8)
+        return fail(ctx, STK_NOT_IMPLEMENTED, "star detection takes 8-bit frames: the statistics and moments are defined on the 8-bit integer grey");
+    if (stack_form && frames->n < 2) return fail(ctx, STK_NOT_ENOUGH_FILES, "star registration needs a reference frame and at least one moving frame");
+    return STK_OK;
+}
+
+bool star_before(const StarRecord& a, const StarRecord& b) {
+    if (a.S != b.S) return a.S > b.S;
+    if (a.py != b.py) return a.py < b.py;
+    return a.px < b.px;
+}
+
+// Detection of the whole stack: dev = the frames in HBM by frame index, lists[i] = frame i's stars (at most max_stars,
+// brightest first), n_peaks[i] = its peaks before any truncation. prep_ms of the timing: the launches' device time.
+stk_status star_detect_impl(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* p, std::vector<const void*>& dev,
+                            std::vector<std::vector<stk_star>>& lists, std::vector<int32_t>& n_peaks) {
+    (void)hipSetDevice(ctx->device);
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    const size_t rb = frame_row_bytes(frames), tiles = (size_t)star_tiles(w, h);
+    stk_status st = resolve_frames(ctx, frames, dev);
+    if (st) return st;
+    const StarLayout L = star_layout((size_t)n, tiles);
+    if ((st = workspace_reserve(ctx, ctx->local, L.total, "star"))) return st;
+    char* base = ctx->local.as<char>();
+    const float ks = (float)((double)p->kappa * 1.4826);
+    HIP_TRY(hipMemcpyAsync(base + L.fptrs, dev.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+    for (int f0 = 0; f0 < n; f0 += 65535) {
+        const int nl = std::min(65535, n - f0);
+        HIP_TRY(launch_star_detect((const void* const*)(base + L.fptrs) + f0, nl, cn, w, h, rb, p->radius, ks, p->min_contrast, p->min_pixels,
+                                   (int32_t*)(base + L.counts) + (size_t)f0 * tiles,
+                                   (StarRecord*)(base + L.records) + (size_t)f0 * tiles * STAR_TILE_CAP, ctx->stream));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+    std::vector<int32_t> counts((size_t)n * tiles);
+    std::vector<StarRecord> records((size_t)n * tiles * STAR_TILE_CAP);
+    HIP_TRY(hipMemcpyAsync(counts.data(), base + L.counts, counts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(records.data(), base + L.records, records.size() * sizeof(StarRecord), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->timing.prep_ms += ev_ms(ctx->ev[0], ctx->ev[1]);
+    lists.assign(n, {});
+    n_peaks.assign(n, 0);
+    star_parallel_for(ctx, n, [&](int i) {
+        std::vector<StarRecord> all;
+        int64_t total = 0;
+        for (size_t t = 0; t < tiles; t++) {
+            const int c = counts[(size_t)i * tiles + t];
+            total += c;
+            const StarRecord* r = &records[((size_t)i * tiles + t) * STAR_TILE_CAP];
+            all.insert(all.end(), r, r + std::min(c, STAR_TILE_CAP));
+        }
+        n_peaks[i] = (int32_t)std::min<int64_t>(total, INT32_MAX);
+        std::sort(all.begin(), all.end(), star_before);
+        if ((int)all.size() > p->max_stars) all.resize(p->max_stars);
+        std::vector<stk_star>& o = lists[i];
+        o.resize(all.size());
+        for (size_t k = 0; k < all.size(); k++) {
+            const StarRecord& r = all[k];
+            o[k].x = (float)((double)r.px + (double)r.Sx / (double)r.S);
+            o[k].y = (float)((double)r.py + (double)r.Sy / (double)r.S);
+            o[k].flux = (float)r.S;
+            o[k].px = r.px; o[k].py = r.py; o[k].peak = r.peak; o[k].npix = r.npix; o[k].reserved = 0;
+        }
+    });
+    return STK_OK;
+}
+
+// one batched fit over the frames that have at least 4 pairs (pairs[i]: moving index, reference index); outc by frame
+stk_status star_fit(stk_ctx* ctx, const stk_star_params* p, const std::vector<std::vector<stk_star>>& lists,
+                    const std::vector<std::vector<int32_t>>& pairs, std::vector<geom::HgOutcome>& outc, std::vector<char>& ran) {
+    const int n = (int)lists.size();
+    outc.assign(n, geom::HgOutcome{});
+    ran.assign(n, 0);
+    std::vector<std::vector<float>> from(n), to(n);
+    std::vector<geom::HgProblem> probs;
+    std::vector<int> owner;
+    for (int i = 1; i < n; i++) {
+        const size_t np = pairs[i].size() / 2;
+        if (np < 4) continue;
+        from[i].resize(np * 2); to[i].resize(np * 2);
+        for (size_t k = 0; k < np; k++) {
+            const stk_star& m = lists[i][pairs[i][2 * k]];
+            const stk_star& r = lists[0][pairs[i][2 * k + 1]];
+            from[i][2 * k] = m.x; from[i][2 * k + 1] = m.y;
+            to[i][2 * k] = r.x; to[i][2 * k + 1] = r.y;
+        }
+        probs.push_back({from[i].data(), to[i].data(), (int)np, nullptr});
+        owner.push_back(i);
+    }
+    if (probs.empty()) return STK_OK;
+    std::vector<geom::HgOutcome> got(probs.size());
+    const int hst = geom::find_homography_batch(ctx, ctx->stream, ctx->hg, probs.data(), (int)probs.size(), p->method,
+                                                p->ransac_reproj_threshold, got.data());
+    if (hst) return (stk_status)hst;
+    for (size_t k = 0; k < probs.size(); k++) { outc[owner[k]] = got[k]; ran[owner[k]] = 1; }
+    return STK_OK;
+}
+
+// detection and steps 1 - 6: the stats of all n frames, the frames in HBM, the number of moving frames dropped. Every
+// moving frame dropped: STK_INVALID_PARAMS behind the filled stats.
+stk_status star_align_impl(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* p, stk_frame_stats* stats,
+                           std::vector<const void*>& dev, int32_t* dropped) {
+    const int n = frames->n;
+    std::vector<std::vector<stk_star>> lists;
+    std::vector<int32_t> n_peaks;
+    stk_status st = star_detect_impl(ctx, frames, p, dev, lists, n_peaks);
+    if (st) return st;
+    HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+    std::memset(stats, 0, sizeof(stk_frame_stats) * (size_t)n);
+    for (int i = 0; i < n; i++) {
+        stats[i].n_keypoints = (int32_t)lists[i].size();
+        stats[i].status = i == 0 ? 0 : 1;
+        stats[i].warp[0] = stats[i].warp[4] = stats[i].warp[8] = 1;
+    }
+    const int m = p->match_stars, n0 = (int)lists[0].size();
+    std::vector<std::vector<int32_t>> pairs(n);
+    if (n0 >= p->min_stars) {
+        std::vector<star::Triangle> tri0;
+        star::triangles(lists[0].data(), n0, m, p->neighbours, tri0);
+        star_parallel_for(ctx, n - 1, [&](int k) {
+            const int i = k + 1, ni = (int)lists[i].size();
+            if (ni < p->min_stars) return;
+            std::vector<star::Triangle> tri;
+            star::triangles(lists[i].data(), ni, m, p->neighbours, tri);
+            star::vote_pairs(tri, std::min(m, ni), tri0, std::min(m, n0), p->tri_tolerance, p->min_votes, pairs[i]);
+        });
+    }
+    std::vector<geom::HgOutcome> fit, fit2;
+    std::vector<char> ran, ran2;
+    if ((st = star_fit(ctx, p, lists, pairs, fit, ran))) return st;
+    std::vector<int32_t> n_matches(n, 0);
+    for (int i = 1; i < n; i++) n_matches[i] = (int32_t)(pairs[i].size() / 2);
+    if (p->refine) {
+        std::vector<std::vector<int32_t>> guided(n);
+        star_parallel_for(ctx, n - 1, [&](int k) {
+            const int i = k + 1;
+            if (!ran[i] || fit[i].rc != 0 || !fit[i].found) return;
+            star::guided_pairs(lists[i].data(), (int)lists[i].size(), lists[0].data(), n0, fit[i].H, p->ransac_reproj_threshold, guided[i]);
+        });
+        if ((st = star_fit(ctx, p, lists, guided, fit2, ran2))) return st;
+        for (int i = 1; i < n; i++) {
+            if (!ran2[i]) continue;
+            n_matches[i] = (int32_t)(guided[i].size() / 2);
+            if (fit2[i].rc == 0 && fit2[i].found && fit2[i].n_inliers >= fit[i].n_inliers) fit[i] = fit2[i];
+        }
+    }
+    int nd = 0;
+    for (int i = 1; i < n; i++) {
+        stats[i].n_matches = n_matches[i];
+        const bool ok = ran[i] && fit[i].rc == 0 && fit[i].found && fit[i].n_inliers >= p->min_inliers;
+        if (!ok) { nd++; continue; }
+        stats[i].status = 0;
+        stats[i].n_inliers = fit[i].n_inliers;
+        for (int k = 0; k < 9; k++) stats[i].warp[k] = fit[i].H[k];
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->timing.align_ms += ev_ms(ctx->ev[2], ctx->ev[3]);
+    if (dropped) *dropped = nd;
+    if (nd == n - 1)
+        return fail(ctx, STK_INVALID_PARAMS, "All images discarded: no moving frame could be registered against the reference's stars");
+    return STK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+stk_status stk_star_detect(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, stk_star* stars, int32_t* n_stars,
+                           int32_t* n_peaks) {
+    stk_status st = star_check(ctx, frames, params, false, false);
+    if (st) return st;
+    if (!stars || !n_stars) return fail(ctx, STK_INVALID_PARAMS, "null star outputs");
+    timing_begin(ctx);
+    std::vector<const void*> dev;
+    std::vector<std::vector<stk_star>> lists;
+    std::vector<int32_t> peaks;
+    if ((st = star_detect_impl(ctx, frames, params, dev, lists, peaks))) return st;
+    std::memset(stars, 0, sizeof(stk_star) * (size_t)frames->n * (size_t)params->max_stars);
+    for (int i = 0; i < frames->n; i++) {
+        n_stars[i] = (int32_t)lists[i].size();
+        if (n_peaks) n_peaks[i] = peaks[i];
+        if (!lists[i].empty()) std::memcpy(stars + (size_t)i * params->max_stars, lists[i].data(), sizeof(stk_star) * lists[i].size());
+    }
+    return STK_OK;
+}
+
+stk_status stk_star_align(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, int32_t* dropped,
+                          stk_frame_stats* stats) {
+    stk_status st = star_check(ctx, frames, params, true, false);
+    if (st) return st;
+    if (!stats) return fail(ctx, STK_INVALID_PARAMS, "null stats");
+    timing_begin(ctx);
+    std::vector<const void*> dev;
+    return star_align_impl(ctx, frames, params, stats, dev, dropped);
+}
+
+stk_status stk_star_match(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, stk_image_f32* out, int32_t* dropped,
+                          stk_frame_stats* stats) {
+    stk_status st = star_check(ctx, frames, params, true, true);
+    if (st) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    timing_begin(ctx);
+    const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
+    std::vector<stk_frame_stats> own;
+    if (!stats) { own.resize(n); stats = own.data(); }
+    std::vector<const void*> dev;
+    int32_t nd = 0;
+    if ((st = star_align_impl(ctx, frames, params, stats, dev, &nd))) { if (dropped) *dropped = nd; return st; }
+    if (dropped) *dropped = nd;
+    // the plain mean, with the fold of fold_spec_keypoint's shape: depth 8, alpha 1 / 255, the params' border, never affine
+    const size_t nel = (size_t)w * h * cn;
+    stk_image_f32 sum = *out;
+    if (out->location != STK_DEVICE) {
+        if ((st = workspace_reserve(ctx, ctx->acc, nel * sizeof(float), "star sum"))) return st;
+        sum.data = ctx->acc.as<float>(); sum.location = STK_DEVICE;
+    }
+    EntryTable table;
+    entries_from_stats(n, stats, true, table);
+    if ((st = entry_table_upload(ctx, frames, dev, table, 0))) return st;
+    HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    if ((st = warp_fold_enqueue(ctx, table.size(), 8, w, h, cn, frame_row_bytes(frames), 1.0 / 255.0, params->border_mode,
+                                params->border_value, 0, sum.data, image_stride_floats(&sum), 0)))
+        return st;
+    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const float warp_ms = ev_ms(ctx->ev[4], ctx->ev[5]);
+    const stk_timing keep = ctx->timing;
+    st = stk_finalize_mean(ctx, &sum, n - nd, out);
+    const double fin = ctx->timing.finalize_ms;
+    ctx->timing = keep; ctx->timing.warp_ms = warp_ms; ctx->timing.finalize_ms = fin;
+    return st;
+}
+
+}  // extern "C"

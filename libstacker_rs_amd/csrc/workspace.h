@@ -183,6 +183,19 @@ inline RejectLayout reject_layout(int n_entries, int sw, int sh, int cn, bool cl
     return L;
 }
 
+// ctx->local, star detection (star.cpp): the frame pointers of the stack, then per (frame, tile) the peak count and the
+// STAR_TILE_CAP record slots
+struct StarLayout { size_t fptrs, counts, records, total; };
+inline StarLayout star_layout(size_t n_frames, size_t tiles) {
+    Carver c;
+    StarLayout L{};
+    L.fptrs = c.take(std::max<size_t>(n_frames, 1) * sizeof(void*));
+    L.counts = c.take(n_frames * tiles * sizeof(int32_t));
+    L.records = c.take(n_frames * tiles * stk::STAR_TILE_CAP * sizeof(stk::StarRecord));
+    L.total = c.total;
+    return L;
+}
+
 // ---------------------------------------------------------------------------------------------
 // room for `bytes` in a workspace, or STK_HIP_ERROR (the allocator's sticky error is cleared: the context stays usable)
 inline stk_status workspace_reserve(stk_ctx* ctx, DevBuf& buf, size_t bytes, const char* what) {

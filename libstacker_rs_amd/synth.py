@@ -133,6 +133,79 @@ def make_stack(n: int, width: int, height: int, *, seed: int = SEED, depth: int 
     return torch.stack(frames), Gs
 
 
+def star_motion(width: int, height: int, angle_deg: float = 0.0, tx: float = 0.0, ty: float = 0.0, scale: float = 1.0,
+                p1: float = 0.0, p2: float = 0.0) -> np.ndarray:
+    """G = C . T(tx,ty) . R(angle) . Sc(scale) . P(p1,p2) . C^-1 about the image centre (3x3 f64), random_homography's
+    composition with the parameters given: frame-i pixel -> frame-0 pixel."""
+    th = math.radians(angle_deg)
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    C = np.array([[1, 0, cx], [0, 1, cy], [0, 0, 1]], np.float64)
+    Ci = np.array([[1, 0, -cx], [0, 1, -cy], [0, 0, 1]], np.float64)
+    T = np.array([[1, 0, tx], [0, 1, ty], [0, 0, 1]], np.float64)
+    R = np.array([[math.cos(th), -math.sin(th), 0], [math.sin(th), math.cos(th), 0], [0, 0, 1]], np.float64)
+    S = np.diag([scale, scale, 1.0])
+    P = np.array([[1, 0, 0], [0, 1, 0], [p1, p2, 1]], np.float64)
+    G = C @ T @ R @ S @ P @ Ci
+    return G / G[2, 2]
+
+
+def make_star_stack(motions, width: int, height: int, n_stars: int, *, seed: int = SEED, psf_sigma: float = 1.5,
+                    sky=(18.0, 28.0), noise_sigma: float = 2.0, min_peak: float = 24.0, pareto_shape: float = 1.2,
+                    channels: int = 3, fields=None, empty=()):
+    """A seeded star field seen through known motions: returns (frames, G), frames a numpy uint8 array [n, H, W, channels]
+    (channels 1: [n, H, W]), G = [n, 3, 3] float64 with frame_i(x) ~= frame_0(G_i x). motions: one 3 x 3 matrix per frame
+    (frame-i pixel -> frame-0 pixel; None = identity; motions[0] should be the identity).
+
+    The field: about n_stars stars per frame area, uniform over a square that covers the frame under any rotation about
+    its centre; peak amplitudes min_peak * (1 + Pareto(pareto_shape)), capped so that sky + peak stays below 250; a
+    Gaussian PSF of psf_sigma px sampled at the pixel centres (not warped: the motions are near-isometries). The sky is a
+    linear gradient from sky[0] to sky[1] across the frame's diagonal, in frame coordinates (it does not move with the
+    stars); noise is Gaussian, seeded per frame. All channels carry the same value, so the integer grey equals it.
+    fields[i]: which star field frame i shows (default 0 for all; another number is another sky); frames listed in
+    `empty` show no star at all (sky and noise only)."""
+    n = len(motions)
+    G = np.stack([np.eye(3) if m is None else np.asarray(m, np.float64).reshape(3, 3) for m in motions])
+    fields = [0] * n if fields is None else list(fields)
+    side = math.hypot(width, height) + 80.0
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    n_field = int(math.ceil(n_stars * side * side / float(width * height)))
+    yy, xx = np.mgrid[0:height, 0:width].astype(np.float64)
+    grad = sky[0] + (sky[1] - sky[0]) * (xx / max(width - 1, 1) + yy / max(height - 1, 1)) * 0.5
+    cache = {}
+    frames = np.zeros((n, height, width), np.uint8)
+    rad = int(math.ceil(5.0 * psf_sigma))
+    for i in range(n):
+        img = grad.copy()
+        if i not in empty:
+            if fields[i] not in cache:
+                rng = np.random.Generator(np.random.PCG64(seed + 7919 * (1 + fields[i])))
+                pos = np.stack([rng.uniform(cx - side / 2, cx + side / 2, n_field), rng.uniform(cy - side / 2, cy + side / 2, n_field)], 1)
+                amp = np.minimum(min_peak * (1.0 + rng.pareto(pareto_shape, n_field)), 250.0 - max(sky))
+                cache[fields[i]] = (pos, amp)
+            pos, amp = cache[fields[i]]
+            Gi = np.linalg.inv(G[i])                                   # frame-0 (sky) position -> frame-i pixel
+            q = Gi @ np.concatenate([pos.T, np.ones((1, len(pos)))], 0)
+            px, py = q[0] / q[2], q[1] / q[2]
+            for x, y, a in zip(px, py, amp):
+                if x < -rad or y < -rad or x > width - 1 + rad or y > height - 1 + rad:
+                    continue
+                x0, x1 = max(int(math.floor(x)) - rad, 0), min(int(math.floor(x)) + rad + 2, width)
+                y0, y1 = max(int(math.floor(y)) - rad, 0), min(int(math.floor(y)) + rad + 2, height)
+                if x0 >= x1 or y0 >= y1:
+                    continue
+                dx, dy = xx[y0:y1, x0:x1] - x, yy[y0:y1, x0:x1] - y
+                img[y0:y1, x0:x1] += a * np.exp(-(dx * dx + dy * dy) / (2.0 * psf_sigma * psf_sigma))
+        if noise_sigma > 0:
+            img += np.random.Generator(np.random.PCG64(seed + 1000 + i)).standard_normal(img.shape) * noise_sigma
+        frames[i] = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+    if channels == 1:
+        return frames, G
+    out = np.repeat(frames[..., None], channels, axis=3)
+    if channels == 4:
+        out[..., 3] = 255
+    return np.ascontiguousarray(out), G
+
+
 def corner_error(A: np.ndarray, B: np.ndarray, width: int, height: int) -> float:
     """Max displacement (pixels) between the images of the four frame corners under A and B."""
     pts = np.array([[0, 0, 1], [width - 1, 0, 1], [0, height - 1, 1], [width - 1, height - 1, 1]], np.float64).T
