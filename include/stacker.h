@@ -118,7 +118,10 @@ typedef struct {
                                          rows 0 .. height - 2 only (its vote keeps a row to spare below the footprint), never before the row's
                                          first pixel; everywhere else it reads exactly the twelve bytes, or the linear sample's clamped taps.
                                          Nothing before the first or behind the last pixel of the span.
-                                         The preparation kernels (kernels_prep.hip, kernels_quality.hip) read pixels only. */
+                                         The preparation kernels (kernels_prep.hip, kernels_quality.hip) read pixels only, and
+                                         so does the calibration kernel (calibrate_kernel, kernels_calibrate.hip): element by
+                                         element, a pixel's own channels and, for a defective pixel, those of its in-frame
+                                         neighbours at +-defect_step. */
 } stk_frames;
 
 /* Geometry of ONE frame of a stack whose frames differ in size (stk_keypoint_match_mixed). */
@@ -270,7 +273,10 @@ void        stk_host_free(void* p);
  *   "upload_batch"       host-fed stacks: frames per host -> HBM batch (default 8); a batch is the unit the ECC queue
  *                        and the batched ORB wait for
  *   "quantile_band_rows" quantile combines: rows per band of samples. 0 (default): as many as fit a 4 GiB sample buffer;
- *                        n > 0: at most n. Same bits either way */
+ *                        n > 0: at most n. Same bits either way
+ *   "calibrate_chunk"    stk_calibrate: frames a workgroup runs through with its tile of the masters in registers. 0
+ *                        (default): 16; 1 .. 4096 as given (1: the masters are read once per frame, for measuring what
+ *                        holding them buys). Same bits either way */
 stk_status  stk_set_option(stk_ctx* ctx, const char* name, int64_t value);
 const char* stk_version(void);
 
@@ -1370,6 +1376,97 @@ stk_status stk_star_align(stk_ctx* ctx, const stk_frames* frames, const stk_star
  * stk_finalize_mean(n - dropped), bit for bit. */
 stk_status stk_star_match(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, stk_image_f32* out,
                           int32_t* dropped, stk_frame_stats* stats_or_null);
+
+/* ---- frame calibration: an EXTENSION beyond the reference ---------------------------------------------------------------
+ * The front half of a stacking pipeline: bias, dark and flat masters applied to every frame of a stack, defective pixels
+ * repaired from their neighbours, the defect map found from the masters, and the masters themselves built from stacks of
+ * calibration frames. The frames stay where they are (host or device); a calibrated stack feeds every aligner and combine.
+ * stk_calibrate. Per frame i, pixel p and channel c < min(channels, 3), f32 throughout, each operation rounded on its own,
+ * no contraction, `/` correctly rounded; B, D, F are the masters' values at (p, c), s_i = dark_scale[i] (1 without):
+ *   v = (float)raw
+ *   bias:  v = v - B
+ *   dark:  v = v - s_i * D                           (s_i * D rounded first)
+ *   flat:  t = v * flat_mean[c];  v = t / fmaxf(F, flat_min)      (C's fmaxf: a NaN F gives flat_min)
+ *   v = v + pedestal                                  (always, also without any master)
+ * Channel 3 (alpha) is (float)raw, untouched by masters, pedestal and repair. The masters are in the frames' RAW sample units
+ * (what stk_master_stack returns for raw calibration frames): no alpha scaling anywhere.
+ * Defect repair, where bit c of defects[p] is set. N = the positions among the eight at offsets (+-step, 0), (0, +-step),
+ * (+-step, +-step) (step = defect_step) that lie inside the frame and whose bit c is clear; a_0 <= .. <= a_(m-1) the values
+ * v (as computed above: unrepaired, nothing cascades) of those m positions. The order is the total order of the bit
+ * patterns: -0 below +0, every NaN above every number (a NaN enters as the canonical quiet NaN). The repaired value is
+ * a_((m-1)/2) for odd m, (a_(m/2-1) + a_(m/2)) * 0.5f for even m, and v itself when m = 0.
+ * Output. out_depth = STK_DEPTH_F32: v. Otherwise (out_depth = frames->depth, integer frames only): r = rintf(v) (half to
+ * even, cvRound), then fminf(fmaxf(r, 0), 255 or 65535) converted; a NaN gives 0. out: n pointers in the frames' location,
+ * rows out_row_stride_bytes apart (0 = tightly packed; else at least a row's bytes and a multiple of the element size).
+ * Only the pixel bytes of `out` are written: row padding keeps its contents. `out` must not overlap any frame, master or
+ * the map (STK_INVALID_PARAMS); in-place calibration is a follow-up, because repair reads the neighbours' raw values.
+ * Every depth, 1 / 3 / 4 channels, padded and misaligned rows, any subset of the masters and the map (none: a plain
+ * conversion plus pedestal). Masters and map may each be host or device memory whatever the frames' location; a master may
+ * have padded rows (row_stride_bytes a multiple of 4). STK_INVALID_PARAMS: a master whose width, height or channels differ
+ * from the frames'; out_depth neither frames->depth nor STK_DEPTH_F32; defect_step outside {1, 2}; with a flat, a flat_mean[c]
+ * (c < min(channels, 3)) or flat_min that is not finite or not > 0; a non-finite pedestal or dark_scale; null outputs.
+ * Kernel (kernels_calibrate.hip): a workgroup owns a 64 x 4 tile and a chunk of 16 frames (option "calibrate_chunk"); a
+ * thread keeps its pixel's master values and map byte in registers across the chunk, so the masters are read once per chunk,
+ * not once per frame. A wave in which some lane is defective takes the neighbour path (a ballot); the others never see it.
+ * stk_defect_map. Per pixel p and channel c < min(channels, 3) of a master: X = its value, med = the median rule above over
+ * the master's own values at ALL in-frame positions among the eight at +-step (no exclusion; m = 0: no test applies).
+ *   bit c = !isfinite(X)  ||  (tests & 1 && X - med > high_abs)  ||  (tests & 2 && X < low_ratio * med)
+ * (a NaN med fails both comparisons). accumulate = 1: the byte is ORed into the one already in `map`, else it replaces it.
+ * map: width * height bytes, tightly packed, in map_location; the same bytes on every call. counts_or_null: 4 int64 on the
+ * host, the set bits per channel of the map after the call (counts[3] = 0; integer sums, any order). The map is what
+ * stk_calibrate takes as `defects`, and, as weight = (byte == 0), what stk_drizzle_stack takes through `maps`.
+ * STK_INVALID_PARAMS: tests outside 1 .. 3, high_abs not finite or < 0, low_ratio outside [0, 1], step outside {1, 2},
+ * accumulate outside {0, 1}.
+ * stk_image_mean. Per-channel means of an f32 image (host or device): f64 sums, one partial per image row (a wave per row,
+ * lanes striding the row, a fixed shuffle tree), the rows' partials added in row order; mean = sum / (width * height). The
+ * order depends on the geometry alone: the same bits on every call. mean[c] = 0 for c >= channels. The source of flat_mean.
+ * stk_master_stack. By definition, and bit for bit, a composition of existing calls: stk_robust_clip_stack_weighted over
+ * all n frames under identity matrices (is_affine 0, STK_BORDER_CONSTANT 0, alpha = 1, coverage 0, weights 1) with
+ * normalize = 0 (bias, darks): gains 1, offsets 0;
+ * normalize = 2 (flats):       the GAIN records of the estimator above from stk_overlap_moments (same matrices, border and
+ *                              alpha, stat_step; 0 = 4) against frame 0: every flat is brought to frame 0's level first.
+ * Any other normalize: STK_INVALID_PARAMS; otherwise it refuses what those calls refuse (more than 4096 frames:
+ * STK_NOT_IMPLEMENTED; "warp_interpolation" = 2 with "warp_subpixel_bits" = 5). The identity fold returns each pixel's value
+ * exactly for every depth, the last row and column included, under the default options ("warp_interpolation" 1,
+ * "warp_subpixel_bits" 0) and finite samples: the lerp chain is fma(0, b - a, a) = a. The one exception is f32 frames that
+ * hold +-inf or NaN: b - a is then not finite and 0 * inf is NaN, so such a sample comes back NaN (an infinity included)
+ * and so do its left, upper and upper-left neighbours. That case is not refused (finding it would cost a pass over the
+ * stack): it is a property of the fold to know. Under the other options the masters are those options' folds.
+ * A multi-device context runs these calls on its first device. Follow-ups, not here: in-place calibration; dark-scale
+ * optimisation (choosing s_i by minimising the residual noise); per-frame cosmetic detection without masters; demosaicing
+ * and CFA-aware drizzle; whole-stack *_match_calibrated forms (calibrate, then call any existing entry point); shard and
+ * files forms; a u8 BGR dword-window fast path of the calibration kernel. */
+typedef struct {
+    const stk_image_f32* bias_or_null;  /* masters: width x height x frames->channels f32, in the frames' RAW sample units */
+    const stk_image_f32* dark_or_null;  /* (what stk_master_stack returns); host or device; channel 3 is never read */
+    const stk_image_f32* flat_or_null;
+    const float*   dark_scale_or_null;  /* n per-frame factors (exposure ratio), host; NULL = all 1 */
+    float          flat_mean[4];        /* the level the flat is divided by, per channel; finite and > 0 with a flat */
+    float          flat_min;            /* > 0: the flat is clamped from below to this before the division */
+    float          pedestal;            /* added last; finite */
+    int32_t        reserved;            /* 0 */
+    const uint8_t* defects_or_null;     /* width x height bytes, bit c = channel c of that pixel is defective; tightly packed */
+    int32_t        defects_location;    /* STK_HOST | STK_DEVICE */
+    int32_t        defect_step;         /* 1, or 2 for a colour-filter mosaic held in one channel */
+    int32_t        out_depth;           /* frames->depth (rounded, saturated) or STK_DEPTH_F32 */
+    int32_t        reserved2;           /* 0 */
+} stk_calibration;
+typedef struct {
+    int32_t tests;                      /* bit 0: high test, bit 1: low test */
+    float   high_abs;                   /* flagged when X - med > high_abs (dark: hot pixels); finite, >= 0 */
+    float   low_ratio;                  /* flagged when X < low_ratio * med (flat: dead pixels, dust); 0 .. 1 */
+    int32_t step;                       /* 1 or 2, as defect_step */
+    int32_t accumulate;                 /* 1: OR into the map already there (dark first, then flat) */
+    int32_t reserved;                   /* 0 */
+} stk_defect_params;
+
+stk_status stk_calibrate(stk_ctx* ctx, const stk_frames* frames, const stk_calibration* cal, void* const* out,
+                         size_t out_row_stride_bytes);
+stk_status stk_defect_map(stk_ctx* ctx, const stk_image_f32* master, const stk_defect_params* params, uint8_t* map,
+                          int32_t map_location, int64_t* counts_or_null);
+stk_status stk_image_mean(stk_ctx* ctx, const stk_image_f32* image, double* mean);
+stk_status stk_master_stack(stk_ctx* ctx, const stk_frames* frames, int32_t normalize, int32_t stat_step,
+                            const stk_robust_clip_params* clip, stk_image_f32* out, int32_t* counts_or_null);
 
 /* ---- stage-level entry points (parity tests bind these) ------------------ */
 /* cvt_color(BGR2GRAY) on the integer image, utils.rs:136-142. out: w*h of the input depth

@@ -10,7 +10,7 @@ use (api.Stacker / _ffi.load) and there is no CPU fallback.
 """
 from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_WRAP,  # noqa: F401
                   INTER_CUBIC, INTER_LINEAR,
-                  LEAST_SQUARES, LMEDS, RANSAC, RHO, DrizzleParameters, EccMatchParameters, HipError, InvalidParams, IoError,
+                  LEAST_SQUARES, LMEDS, RANSAC, RHO, CalibrationParameters, DefectParameters, DrizzleParameters, EccMatchParameters, HipError, InvalidParams, IoError,
                   KeyPointMatchParameters, LocalNormParameters, LocalParameters, MeshParameters, MotionType, NotEnoughFiles, NotImplementedYet, OpenCvError,
                   ProcessingError, QuantileParameters, RejectParameters, RobustClipParameters, SelectParameters, SigmaClipParameters, Stacker,
                   StackerError, StarParameters, STAR_DTYPE, WeightParameters,
@@ -21,4 +21,4 @@ __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchPa
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
            "SelectParameters", "rank_frames", "LocalParameters", "MeshParameters", "mesh_grid", "mesh_pyramid_shapes", "DrizzleParameters",
            "RejectParameters", "LocalNormParameters", "local_norm_estimate", "local_norm_grid",
-           "StarParameters", "STAR_DTYPE", "star_match_lists"]
+           "StarParameters", "STAR_DTYPE", "star_match_lists", "CalibrationParameters", "DefectParameters"]

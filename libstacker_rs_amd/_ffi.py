@@ -110,6 +110,18 @@ class StarParams(C.Structure):
                 ("border_value", C.c_double * 4)]
 
 
+class Calibration(C.Structure):
+    _fields_ = [("bias_or_null", C.POINTER(ImageF32)), ("dark_or_null", C.POINTER(ImageF32)), ("flat_or_null", C.POINTER(ImageF32)),
+                ("dark_scale_or_null", C.c_void_p), ("flat_mean", C.c_float * 4), ("flat_min", C.c_float), ("pedestal", C.c_float),
+                ("reserved", C.c_int32), ("defects_or_null", C.c_void_p), ("defects_location", C.c_int32),
+                ("defect_step", C.c_int32), ("out_depth", C.c_int32), ("reserved2", C.c_int32)]
+
+
+class DefectParams(C.Structure):
+    _fields_ = [("tests", C.c_int32), ("high_abs", C.c_float), ("low_ratio", C.c_float), ("step", C.c_int32),
+                ("accumulate", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Timing(C.Structure):
     _fields_ = [("prep_ms", C.c_double), ("align_ms", C.c_double), ("warp_ms", C.c_double),
                 ("finalize_ms", C.c_double), ("ecc_iter_launches", C.c_int64),
@@ -306,6 +318,11 @@ SIGNATURES = {
                                   C.POINTER(FrameStats)]),
     "stk_star_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(StarParams), C.POINTER(ImageF32), C.POINTER(C.c_int32),
                                   C.POINTER(FrameStats)]),
+    "stk_calibrate": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(Calibration), C.c_void_p, C.c_size_t]),
+    "stk_defect_map": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.POINTER(DefectParams), C.c_void_p, C.c_int32, C.c_void_p]),
+    "stk_image_mean": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_void_p]),
+    "stk_master_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_int32, C.c_int32, C.POINTER(RobustClipParams),
+                                    C.POINTER(ImageF32), C.c_void_p]),
     "stk_grey":(c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p]),
     "stk_convert_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_double, C.c_void_p]),
     "stk_hybrid_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.POINTER(EccParams),

@@ -133,6 +133,42 @@ class RobustClipParameters:       # extension beyond the reference: include/stac
 
 
 @dataclass
+class CalibrationParameters:      # extension beyond the reference: include/stacker.h, stk_calibration
+    """What Stacker.calibrate applies to every frame: v = ((raw - bias) - dark_scale[i] * dark) * flat_mean / max(flat,
+    flat_min) + pedestal per colour channel, then the repair of the pixels flagged in `defects` by the median of their good
+    neighbours at +-defect_step. bias, dark, flat: H x W x C float32 in the frames' raw sample units (numpy arrays or
+    tensors, host or device, whatever the frames' location), any subset. flat_mean None: Stacker.image_mean(flat);
+    flat_min None: a thousandth of the smallest flat_mean. out_depth None: the frames' own depth (rounded half to even,
+    saturated); 32: float32."""
+    bias: object = None
+    dark: object = None
+    flat: object = None
+    dark_scale: Optional[Sequence[float]] = None
+    flat_mean: Optional[Sequence[float]] = None
+    flat_min: Optional[float] = None
+    pedestal: float = 0.0
+    defects: object = None
+    defect_step: int = 1
+    out_depth: Optional[int] = None
+
+
+@dataclass
+class DefectParameters:           # extension beyond the reference: include/stacker.h, stk_defect_params
+    """Stacker.defect_map's tests of a master against the median of its neighbours at +-step: high (hot pixels of a dark):
+    X - med > high_abs; low (dead pixels and dust of a flat): X < low_ratio * med. accumulate: OR into the map handed in."""
+    high: bool = True
+    low: bool = False
+    high_abs: float = 0.0
+    low_ratio: float = 0.5
+    step: int = 1
+    accumulate: bool = False
+
+    def _c(self) -> _ffi.DefectParams:
+        return _ffi.DefectParams((1 if self.high else 0) | (2 if self.low else 0), float(self.high_abs), float(self.low_ratio),
+                                 int(self.step), int(bool(self.accumulate)), 0)
+
+
+@dataclass
 class QuantileParameters:         # extension beyond the reference: include/stacker.h, stk_quantile_params
     """The order statistic for the *_quantile combines: 0 = min, 0.5 = median, 1 = max, linear interpolation between
     the two nearest samples otherwise (numpy.quantile's default method)."""
@@ -1312,6 +1348,193 @@ class Stacker:
         dropped = C.c_int32(0)
         self._check(self._lib.stk_star_match(self._h, C.byref(m.c_frames), C.byref(p), C.byref(img), C.byref(dropped), stats))
         return (dropped.value, out, self._stats_list(stats, m.n)) if return_stats else (dropped.value, out)
+
+    # -- frame calibration (extension beyond the reference) -------------------------------------------------
+    def _image_arg(self, x, keep, what: str = "image"):
+        """An H x W x C (or H x W) float32 image the caller holds, host or device, contiguous or a row-strided view, as an
+        stk_image_f32; the owner is appended to `keep`."""
+        if _is_torch(x):
+            if str(x.dtype) != "torch.float32" or x.dim() not in (2, 3):
+                raise InvalidParams(f"{what}: an H x W x C float32 image expected")
+            if x.is_cuda:
+                self._tensor_ready(x)
+            else:
+                x = x.numpy()
+        if not _is_torch(x):
+            x = np.asarray(x)
+            if x.dtype != np.float32 or x.ndim not in (2, 3):
+                raise InvalidParams(f"{what}: an H x W x C float32 image expected")
+        try:
+            rs = _image_stride_bytes(x)
+        except InvalidParams:
+            x = x.contiguous() if _is_torch(x) else np.ascontiguousarray(x)
+            rs = 0
+        keep.append(x)
+        h, w = int(x.shape[0]), int(x.shape[1])
+        c = int(x.shape[2]) if len(x.shape) == 3 else 1
+        if _is_torch(x):
+            return _ffi.ImageF32(x.data_ptr(), w, h, c, DEVICE, rs)
+        return _ffi.ImageF32(x.ctypes.data, w, h, c, HOST, rs)
+
+    def _bytes_arg(self, x, keep, h, w, what: str):
+        """An H x W uint8 plane, host or device, tightly packed: (pointer, location)."""
+        if _is_torch(x) and x.is_cuda:
+            if str(x.dtype) != "torch.uint8" or tuple(x.shape) != (h, w):
+                raise InvalidParams(f"{what}: an H x W uint8 plane expected")
+            x = x.contiguous()
+            self._tensor_ready(x)
+            keep.append(x)
+            return x.data_ptr(), DEVICE
+        a = np.ascontiguousarray(x.numpy() if _is_torch(x) else x)
+        if a.dtype != np.uint8 or a.shape != (h, w):
+            raise InvalidParams(f"{what}: an H x W uint8 plane expected")
+        keep.append(a)
+        return a.ctypes.data, HOST
+
+    def calibrate(self, files, cal: "CalibrationParameters", out=None):
+        """Apply masters and defect repair to every frame of a stack (stk_calibrate). Returns the calibrated stack where
+        the frames live: an n x H x W x C array or tensor of the frames' dtype (or float32, cal.out_depth = 32). `out`: n
+        images the caller holds instead (same location as the frames; row-strided views allowed, all with one row step);
+        only their pixel bytes are written, and they must not overlap the frames or the masters."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        keep = []
+        c = _ffi.Calibration()
+        for name in ("bias", "dark", "flat"):
+            x = getattr(cal, name)
+            if x is not None:
+                setattr(c, name + "_or_null", C.pointer(self._image_arg(x, keep, name + " master")))
+        if cal.dark_scale is not None:
+            ds = np.ascontiguousarray(np.asarray(cal.dark_scale, np.float32).reshape(-1))
+            if ds.size != m.n:
+                raise InvalidParams("one dark_scale per frame expected")
+            keep.append(ds)
+            c.dark_scale_or_null = ds.ctypes.data
+        fm = cal.flat_mean
+        if cal.flat is not None and fm is None:
+            fm = self.image_mean(cal.flat)
+        fm = [1.0] * 4 if fm is None else (list(np.asarray(fm, np.float64).reshape(-1)) + [1.0] * 4)[:4]
+        for k in range(4):
+            c.flat_mean[k] = float(fm[k])
+        c.flat_min = float(cal.flat_min) if cal.flat_min is not None else 1e-3 * float(min(fm[:min(m.c, 3)]))
+        c.pedestal = float(cal.pedestal)
+        if cal.defects is not None:
+            c.defects_or_null, c.defects_location = self._bytes_arg(cal.defects, keep, m.h, m.w, "defects")
+        c.defect_step = int(cal.defect_step)
+        c.out_depth = int(m.depth if cal.out_depth is None else cal.out_depth)
+        dt = {8: "uint8", 16: "uint16", 32: "float32"}.get(c.out_depth)
+        stride = 0
+        if out is None:
+            if dt is None:
+                raise InvalidParams("out_depth must be 8, 16 or 32")
+            if m.location == DEVICE:
+                import torch
+                res = torch.empty((m.n, m.h, m.w, m.c), dtype=getattr(torch, dt), device=m.torch_device)
+                base = res.data_ptr()
+            else:
+                res = np.empty((m.n, m.h, m.w, m.c), dt)
+                base = res.ctypes.data
+            ptrs = [base + i * m.h * m.w * m.c * (c.out_depth // 8) for i in range(m.n)]
+        else:
+            res = out
+            outs = list(out)
+            if len(outs) != m.n:
+                raise InvalidParams("one output per frame expected")
+            ptrs, strides = [], set()
+            el = c.out_depth // 8
+            for o in outs:
+                dev = _is_torch(o) and o.is_cuda
+                if dev != (m.location == DEVICE):
+                    raise InvalidParams("the outputs must live where the frames live")
+                name = str(o.dtype).replace("torch.", "")
+                shape = tuple(int(v) for v in o.shape)
+                if name != dt or shape not in ((m.h, m.w, m.c),) + (((m.h, m.w),) if m.c == 1 else ()):
+                    raise InvalidParams("every output must be H x W x C of the output depth")
+                if not dev and _is_torch(o):
+                    o = o.numpy()
+                if dev:
+                    self._tensor_ready(o)
+                    rs = m.w * m.c * el if o.is_contiguous() else _row_stride_bytes(shape, [s * el for s in o.stride()], el)
+                    ptrs.append(o.data_ptr())
+                else:
+                    rs = m.w * m.c * el if o.flags.c_contiguous else _row_stride_bytes(shape, o.strides, el)
+                    ptrs.append(o.ctypes.data)
+                if not rs:
+                    raise InvalidParams("an output must be contiguous or a view whose only non-contiguity is its row step")
+                strides.add(rs)
+                keep.append(o)
+            if len(strides) != 1:
+                raise InvalidParams("all outputs must share one row step")
+            stride = strides.pop()
+        arr = (C.c_void_p * m.n)(*ptrs)
+        self._check(self._lib.stk_calibrate(self._h, C.byref(m.c_frames), C.byref(c), C.cast(arr, C.c_void_p), stride))
+        return res
+
+    def defect_map(self, master, params: Optional["DefectParameters"] = None, map=None, return_counts: bool = False):
+        """The defect map of a master (stk_defect_map): H x W uint8, bit c = channel c is hot / dead / not finite, placed
+        where the master lives. `map`: the map to write (params.accumulate: to OR into). return_counts adds the set bits
+        per channel after the call."""
+        keep = []
+        img = self._image_arg(master, keep, "master")
+        p = (params or DefectParameters())._c()
+        if map is None:
+            if p.accumulate:
+                raise InvalidParams("accumulate needs the map to accumulate into")
+            if img.location == DEVICE:
+                import torch
+                map = torch.empty((img.height, img.width), dtype=torch.uint8, device=keep[0].device)
+            else:
+                map = np.empty((img.height, img.width), np.uint8)
+        if _is_torch(map) and not map.is_cuda:
+            map = map.numpy()
+        if (_is_torch(map) and not map.is_contiguous()) or (not _is_torch(map) and not (isinstance(map, np.ndarray) and map.flags.c_contiguous)):
+            raise InvalidParams("the map must be a contiguous H x W uint8 plane")
+        ptr, loc = self._bytes_arg(map, keep, img.height, img.width, "map")
+        counts = np.zeros(4, np.int64)
+        self._check(self._lib.stk_defect_map(self._h, C.byref(img), C.byref(p), C.c_void_p(ptr), loc, C.c_void_p(counts.ctypes.data)))
+        return (map, counts) if return_counts else map
+
+    @staticmethod
+    def defect_weights(map):
+        """A defect map as the weight plane stk_drizzle_stack takes through `maps`: float32, 1 where the byte is 0."""
+        if _is_torch(map):
+            import torch
+            return (map == 0).to(torch.float32)
+        return (np.asarray(map) == 0).astype(np.float32)
+
+    def image_mean(self, image):
+        """Per-channel means of a float32 image (stk_image_mean): `channels` float64 values, the same bits on every call."""
+        keep = []
+        img = self._image_arg(image, keep)
+        mean = np.zeros(4, np.float64)
+        self._check(self._lib.stk_image_mean(self._h, C.byref(img), C.c_void_p(mean.ctypes.data)))
+        return mean[:img.channels].copy()
+
+    def master_stack(self, files, normalize: int = 0, clip: Optional["RobustClipParameters"] = None, *, stat_step: int = 4,
+                     return_counts: bool = False):
+        """A master from a stack of calibration frames (stk_master_stack): the median / MAD clip over all frames under
+        identity warps in raw sample units; normalize = 2 (flats) brings every frame to frame 0's level first. clip None:
+        kappa 3 / 3, sigma_floor 0.5 (half a step of integer frames), 2 iterations."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        cp = (clip or RobustClipParameters(3.0, 3.0, 0.5, 2))._c()
+        out, img = self._out_image(m)
+        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
+        self._check(self._lib.stk_master_stack(self._h, C.byref(m.c_frames), int(normalize), int(stat_step), C.byref(cp), C.byref(img), cptr))
+        return (out, cnt) if return_counts else out
+
+    def master_dark(self, darks, bias=None, clip: Optional["RobustClipParameters"] = None):
+        """The master dark (or, without `bias`, the master bias of a stack of bias frames): the frames minus the master
+        bias as float32, then master_stack(normalize = 0)."""
+        return self.master_stack(self.calibrate(darks, CalibrationParameters(bias=bias, out_depth=32)), 0, clip)
+
+    def master_flat(self, flats, bias=None, dark=None, dark_scale=None, clip: Optional["RobustClipParameters"] = None, *,
+                    stat_step: int = 4):
+        """The master flat: the frames minus bias and scaled dark as float32, then master_stack(normalize = 2)."""
+        cal = self.calibrate(flats, CalibrationParameters(bias=bias, dark=dark, dark_scale=dark_scale, out_depth=32))
+        return self.master_stack(cal, 2, clip, stat_step=stat_step)
 
     def _maps_arg(self, m: _Marshalled, maps):
         """n tightly packed H x W float32 planes where the frames live: (owners, pointer array)."""

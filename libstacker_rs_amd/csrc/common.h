@@ -318,6 +318,33 @@ struct StarDetectArgs {
 int star_tiles(int w, int h);
 hipError_t launch_star_detect(const void* const* frames_dev, int n, int cn, int w, int h, size_t stride_bytes, int radius, float ks,
                               int min_contrast, int min_pixels, int32_t* counts, StarRecord* records, hipStream_t s);
+// frame calibration (kernels_calibrate.hip; definition: include/stacker.h, stk_calibration). One record per frame of the
+// launch; a master that is absent is a null pointer. Strides of the frames in bytes, of the masters in floats.
+constexpr int CAL_TW = 64, CAL_TH = 4;       // pixels per workgroup tile of calibrate_kernel
+constexpr int CAL_CHUNK = 16;                // frames per workgroup (option "calibrate_chunk")
+constexpr int DEF_TW = 64, DEF_TH = 16;      // pixels per workgroup tile of defect_map_kernel
+struct CalFrame { const void* src; void* dst; float dark_scale; int pad; };
+struct CalArgs {
+    const CalFrame* frames;
+    int n, chunk;
+    int w, h;
+    size_t in_stride, out_stride;
+    const float* bias; const float* dark; const float* flat;
+    size_t bias_stride, dark_stride, flat_stride;
+    const uint8_t* defects;      // w x h, tightly packed; null = none
+    int step;
+    float flat_mean[4];
+    float flat_min, pedestal;
+};
+// depth: the frames' (8 / 16 / 32); out_depth: depth or 32; cn 1, 3 or 4; a.n <= a.chunk * 65535
+hipError_t launch_calibrate(const CalArgs& a, int depth, int out_depth, int cn, hipStream_t s);
+// the defect map of one master (w x h x cn f32, `stride` floats per row) into map (w x h bytes); counts: 4 device counters
+// (unsigned long long), zeroed by the caller, that receive the set bits per channel of the bytes written
+hipError_t launch_defect_map(const float* master, size_t stride, int w, int h, int cn, int tests, float high_abs, float low_ratio,
+                             int step, int accumulate, uint8_t* map, unsigned long long* counts, hipStream_t s);
+// per-channel f64 sums of an f32 image: one partial per row and channel into partials (h x 4 doubles), then added in row
+// order into sums (4 doubles)
+hipError_t launch_image_sums(const float* image, size_t stride, int w, int h, int cn, double* partials, double* sums, hipStream_t s);
 // local alignment (kernels_mesh.hip; definition: include/stacker.h, stk_mesh_params). Entry 0 of `frames` is frame 0 (its
 // matrix is not read); entries 1 .. n_entries - 1 are the frames that get a field: fields[k] (gh x gw x 2 f32) and status[k]
 // (gh x gw int32; the array or an entry may be null) are indexed like the table

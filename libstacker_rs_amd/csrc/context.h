@@ -75,6 +75,7 @@ struct stk_ctx {
     int opt_ecc_first_iter = 1;   // column-walking homography pass: a frame's first iteration from the identity takes the short route (stacker.cpp: ecc_run); same bits
     int opt_ecc_variant = 3;      // ECC iteration kernel: 3 = production (column-walking homography pass / pipelined affine family), 0 = direct cross-check
     int opt_quantile_band_rows = 0;   // quantile combines: at most this many rows per band of samples; 0 = as many as fit the band budget
+    int opt_calibrate_chunk = 0;      // stk_calibrate: frames per workgroup with the masters in registers; 0 = CAL_CHUNK
     stk_timing timing{};
     int64_t ecc_first_iter_slots = 0;   // stk_get_counter: slot-iterations of the last call that took the first-iteration route (reset by timing_begin)
     hipEvent_t ev[8] = {};

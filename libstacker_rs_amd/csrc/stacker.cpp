@@ -186,6 +186,7 @@ stk_status set_option_one(stk_ctx* ctx, const char* name, int64_t value) {
     else if (n == "prep_overlap") ctx->opt_prep_overlap = value != 0;
     else if (n == "upload_batch") { if (value < 1 || value > 1024) return fail(ctx, STK_INVALID_PARAMS, "upload_batch out of range"); ctx->opt_upload_batch = (int)value; }
     else if (n == "quantile_band_rows") { if (value < 0 || value > (1 << 24)) return fail(ctx, STK_INVALID_PARAMS, "quantile_band_rows out of range"); ctx->opt_quantile_band_rows = (int)value; }
+    else if (n == "calibrate_chunk") { if (value < 0 || value > 4096) return fail(ctx, STK_INVALID_PARAMS, "calibrate_chunk out of range"); ctx->opt_calibrate_chunk = (int)value; }
     else if (n == "ecc_blocks") { if (value != 0 && (value < 8 || value > 65536)) return fail(ctx, STK_INVALID_PARAMS, "ecc_blocks out of range"); ctx->opt_ecc_blocks = (int)value; }
     else return fail(ctx, STK_INVALID_PARAMS, "unknown option " + n);
     return STK_OK;

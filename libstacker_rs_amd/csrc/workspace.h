@@ -196,6 +196,33 @@ inline StarLayout star_layout(size_t n_frames, size_t tiles) {
     return L;
 }
 
+// ctx->local, frame calibration (calibrate.cpp): the per-frame records, the copies of host masters (bias, dark, flat; 0
+// bytes for a device or absent one) and of a host map, the tightly packed outputs of host frames
+struct CalLayout { size_t records, master[3], map, out, total; };
+inline CalLayout cal_layout(size_t n_frames, const size_t master_bytes[3], size_t map_bytes, size_t out_bytes) {
+    Carver c;
+    CalLayout L{};
+    L.records = c.take(std::max<size_t>(n_frames, 1) * sizeof(stk::CalFrame));
+    for (int k = 0; k < 3; k++) L.master[k] = c.take(master_bytes[k]);
+    L.map = c.take(map_bytes);
+    L.out = c.take(out_bytes);
+    L.total = c.total;
+    return L;
+}
+// ctx->local, stk_defect_map and stk_image_mean: the four counters or sums, the row partials of the sums, the copy of a host
+// image, the copy of a host map
+struct ImageLayout { size_t counters, partials, image, map, total; };
+inline ImageLayout image_layout(size_t partial_rows, size_t image_bytes, size_t map_bytes) {
+    Carver c;
+    ImageLayout L{};
+    L.counters = c.take(4 * sizeof(double));
+    L.partials = c.take(partial_rows * 4 * sizeof(double));
+    L.image = c.take(image_bytes);
+    L.map = c.take(map_bytes);
+    L.total = c.total;
+    return L;
+}
+
 // ---------------------------------------------------------------------------------------------
 // room for `bytes` in a workspace, or STK_HIP_ERROR (the allocator's sticky error is cleared: the context stays usable)
 inline stk_status workspace_reserve(stk_ctx* ctx, DevBuf& buf, size_t bytes, const char* what) {
