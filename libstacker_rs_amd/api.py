@@ -584,7 +584,7 @@ class Stacker:
         """Pointers of a frame stack; device tensors must be complete before the engine's stream reads them. If this
         context runs ON torch's current stream of that device (use_torch_stream) stream order already guarantees it;
         otherwise — an unbound context, a `with torch.cuda.stream(...)` block, another device — the producer streams
-        are drained first."""
+        are drained first (behind the .contiguous() copies _Marshalled itself makes of frames in other layouts)."""
         m = _Marshalled(frames)
         if m.location == DEVICE:
             import torch
@@ -595,6 +595,9 @@ class Stacker:
         return m
 
     def _tensor_ready(self, t):
+        """A device tensor the engine is about to touch is complete: the LAST thing the wrapper does with it, behind
+        every torch op (a fill, a cast, a .contiguous() copy) the wrapper itself enqueued on it after _marshal's drain.
+        Nothing on a context bound to torch's current stream (stream order holds there); a drain of that stream otherwise."""
         import torch
         cur = torch.cuda.current_stream(t.device)
         if not (self._bound_stream is not None and t.device.index == self.device and cur.cuda_stream == self._bound_stream):
@@ -1356,9 +1359,7 @@ class Stacker:
         if _is_torch(x):
             if str(x.dtype) != "torch.float32" or x.dim() not in (2, 3):
                 raise InvalidParams(f"{what}: an H x W x C float32 image expected")
-            if x.is_cuda:
-                self._tensor_ready(x)
-            else:
+            if not x.is_cuda:
                 x = x.numpy()
         if not _is_torch(x):
             x = np.asarray(x)
@@ -1369,6 +1370,8 @@ class Stacker:
         except InvalidParams:
             x = x.contiguous() if _is_torch(x) else np.ascontiguousarray(x)
             rs = 0
+        if _is_torch(x):
+            self._tensor_ready(x)                 # behind the copy above, if there was one
         keep.append(x)
         h, w = int(x.shape[0]), int(x.shape[1])
         c = int(x.shape[2]) if len(x.shape) == 3 else 1
@@ -1557,6 +1560,8 @@ class Stacker:
                     raise InvalidParams("weight maps: H x W planes expected")
                 keep.append(a)
                 ptrs.append(a.ctypes.data)
+        if m.location == DEVICE and keep:
+            self._tensor_ready(keep[-1])          # the casts and copies above all went onto one stream
         return keep, (C.c_void_p * m.n)(*ptrs)
 
     def local_weighted_stack(self, files, warps, maps, gain=None, offset=None, weights=None, include=None, *, applied=None,
@@ -1658,6 +1663,8 @@ class Stacker:
             else:
                 planes.append(np.zeros(shape, np.uint8))
                 ptrs.append(planes[-1].ctypes.data)
+        if m.location == DEVICE and planes:
+            self._tensor_ready(planes[-1])        # the fills above
         pp = (C.c_void_p * len(ptrs))(*ptrs)
         self._check(self._lib.stk_grey_pyramid(self._h, C.byref(m.c_frames), levels, C.cast(pp, C.c_void_p)))
         return planes
@@ -1673,6 +1680,7 @@ class Stacker:
             import torch
             fields = torch.zeros((m.n, gh, gw, 2), dtype=torch.float32, device=m.torch_device)
             status = torch.zeros((m.n, gh, gw), dtype=torch.int32, device=m.torch_device)
+            self._tensor_ready(status)            # both fills: the engine writes over them
             fbase, sbase = fields.data_ptr(), status.data_ptr()
         else:
             fields = np.zeros((m.n, gh, gw, 2), np.float32)
@@ -1716,6 +1724,8 @@ class Stacker:
                 ptrs.append(a.ctypes.data)
             if gw is not None and shape != (gh, gw, 2):
                 raise InvalidParams("fields: gh x gw x 2 planes expected (mesh_grid)")
+        if m.location == DEVICE and keep:
+            self._tensor_ready(keep[-1])          # the casts and copies above all went onto one stream
         return keep, (C.c_void_p * m.n)(*ptrs)
 
     def mesh_stack(self, files, warps, fields, step: int, include=None, *, is_affine=False, border_mode=BORDER_CONSTANT,
@@ -1984,6 +1994,7 @@ class Stacker:
             t = t.to(device=m.torch_device, dtype=tdt).contiguous()
             if tuple(t.shape) != tuple(shape):
                 raise InvalidParams(f"{what}: shape {tuple(shape)} expected")
+            self._tensor_ready(t)
             return t, t.data_ptr()
         a = np.ascontiguousarray(np.asarray(x.cpu().numpy() if _is_torch(x) else x, dtype))
         if a.shape != tuple(shape):
@@ -1994,7 +2005,9 @@ class Stacker:
         """n x H x W float32 ones where the frames live."""
         if m.location == DEVICE:
             import torch
-            return torch.ones((m.n, m.h, m.w), dtype=torch.float32, device=m.torch_device)
+            planes = torch.ones((m.n, m.h, m.w), dtype=torch.float32, device=m.torch_device)
+            self._tensor_ready(planes)            # the engine reads and writes these planes: the fill must have landed
+            return planes
         return np.ones((m.n, m.h, m.w), np.float32)
 
     def reject_maps(self, files, warps, clean, reject: Optional["RejectParameters"] = None, counts=None, gain=None, offset=None,
@@ -2297,6 +2310,7 @@ class Stacker:
         m = self._marshal(files)
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
+        self._tensor_ready(sum_out)
         img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, _image_stride_bytes(sum_out))
         added = C.c_int32(0)
         stats = (_ffi.FrameStats * m.n)()
@@ -2311,6 +2325,7 @@ class Stacker:
         m = self._marshal(files)
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
+        self._tensor_ready(sum_out)
         img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, _image_stride_bytes(sum_out))
         added, dropped = C.c_int32(0), C.c_int32(0)
         stats = (_ffi.FrameStats * m.n)()
@@ -2326,6 +2341,8 @@ class Stacker:
         self._tensor_ready(sum_img)
         h, w, c = sum_img.shape
         out = sum_img if out is None else out
+        if out is not sum_img:
+            self._tensor_ready(out)
         a = _ffi.ImageF32(sum_img.data_ptr(), w, h, c, DEVICE, 0)
         b = _ffi.ImageF32(out.data_ptr(), w, h, c, DEVICE, 0)
         self._check(self._lib.stk_finalize_mean(self._h, C.byref(a), int(n_frames), C.byref(b)))
@@ -2373,6 +2390,7 @@ class Stacker:
         m = self._marshal(files)
         if m.n == 0:
             raise NotEnoughFiles("Not enough files")
+        self._tensor_ready(sum_out)
         img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, _image_stride_bytes(sum_out))
         added = C.c_int32(0)
         stats = (_ffi.FrameStats * m.n)()
@@ -2539,6 +2557,8 @@ class Stacker:
         if accumulate:
             out = acc
             if _is_torch(out):
+                if out.is_cuda:
+                    self._tensor_ready(out)
                 img = _ffi.ImageF32(out.data_ptr(), m.w, m.h, m.c, DEVICE if out.is_cuda else HOST, _image_stride_bytes(out))
             else:
                 img = _ffi.ImageF32(out.ctypes.data, m.w, m.h, m.c, HOST, _image_stride_bytes(out))
