@@ -12,7 +12,6 @@ marshals pointers; it has no CPU fallback and raises if the library is missing.
 """
 from __future__ import annotations
 
-import copy
 import ctypes as C
 import os
 import enum
@@ -648,16 +647,213 @@ class Stacker:
             d[name] = v.value
         return d
 
-    def _out_image(self, m: _Marshalled):
-        """f32 HxWxC output placed where the inputs live."""
+    # -- what every call is built from ------------------------------------------------------
+    # Stream ordering: _marshal and _tensor_ready are always called through self; _tensor_ready is the last torch-visible
+    # thing done to a device argument and to a freshly filled result. Ownership: every array whose address goes into a
+    # call stays referenced until that call has returned — a helper that returns an address returns or holds its owner.
+    # Refusals come in one order within a call: sizes (ECC), the empty stack, warps and include flags, records, maps,
+    # fields, norm planes, then the output's shape; records are NULL only where _records_arg(optional=True) says so.
+    def _stack(self, files) -> "_Marshalled":
+        """self._marshal and the empty-stack refusal."""
+        m = self._marshal(files)
+        if m.n == 0:
+            raise NotEnoughFiles("Not enough files")
+        return m
+
+    def _alloc(self, where, shape, dtype, fill=None):
+        """An array of `shape` and `dtype` (numpy's) where the frames live (`where`: the marshalled stack; or a torch device,
+        or None = the host), and its address: (array, address). fill None: uninitialised, the engine writes all of it; else
+        filled, and a filled tensor is made ready for the engine here (_tensor_ready behind the fill)."""
+        device = getattr(where, "torch_device", where)
+        if device is not None:
+            import torch
+            a = torch.empty(tuple(shape), dtype=getattr(torch, np.dtype(dtype).name), device=device)
+            if fill is not None:
+                a.fill_(fill)
+                self._tensor_ready(a)
+            return a, a.data_ptr()
+        a = np.empty(tuple(shape), dtype)
+        if fill is not None:
+            a.fill(fill)
+        return a, a.ctypes.data
+
+    def _image(self, m: _Marshalled, shape=None):
+        """The f32 h x w x C output (default: the frames' size) where the frames live: (array, stk_image_f32)."""
+        h, w = shape or (m.h, m.w)
+        out, addr = self._alloc(m, (h, w, m.c), np.float32)
+        return out, _ffi.ImageF32(addr, w, h, m.c, m.location, 0)
+
+    def _optional(self, m: _Marshalled, wanted, dtype, per_channel=False, shape=None):
+        """An optional output plane (H x W, or H x W x C, or `shape`) where the frames live: (array, c_void_p), or
+        (None, None) = NULL when it is not wanted."""
+        if not wanted:
+            return None, None
+        a, addr = self._alloc(m, shape or ((m.h, m.w, m.c) if per_channel else (m.h, m.w)), dtype)
+        return a, C.c_void_p(addr)
+
+    def _plane_table(self, m: _Marshalled, shape, dtype, fill=None):
+        """n planes in one n x shape array where the frames live, and the table of their addresses: (array, c_void_p of the
+        table). The table is its own owner (ctypes keeps the array a cast pointer came from)."""
+        a, base = self._alloc(m, (m.n,) + tuple(shape), dtype, fill)
+        step = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        return a, C.cast((C.c_void_p * m.n)(*[base + i * step for i in range(m.n)]), C.c_void_p)
+
+    def _as_array(self, m: _Marshalled, x, dtype, shape, error: str):
+        """`x` as a contiguous array of `dtype` (and `shape`, unless None; InvalidParams(error) otherwise) where the frames
+        live: (owner, address). An array that is already that is used as it is, so that a caller's buffer can be written
+        in place. A device conversion is enqueued on torch's stream: the caller ends with _tensor_ready on the owner."""
         if m.location == DEVICE:
             import torch
-            out = torch.empty((m.h, m.w, m.c), dtype=torch.float32, device=m.torch_device)
-            img = _ffi.ImageF32(out.data_ptr(), m.w, m.h, m.c, DEVICE, 0)
-        else:
-            out = np.empty((m.h, m.w, m.c), np.float32)
-            img = _ffi.ImageF32(out.ctypes.data, m.w, m.h, m.c, HOST, 0)
-        return out, img
+            t = x if _is_torch(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype)))
+            t = t.to(device=m.torch_device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
+            if shape is not None and tuple(t.shape) != tuple(shape):
+                raise InvalidParams(error)
+            return t, t.data_ptr()
+        a = np.ascontiguousarray(np.asarray(x.cpu().numpy() if _is_torch(x) else x, dtype))
+        if shape is not None and a.shape != tuple(shape):
+            raise InvalidParams(error)
+        return a, a.ctypes.data
+
+    def _array_arg(self, m: _Marshalled, x, dtype, shape, what: str):
+        """One argument through _as_array, ready for the engine: (owner, address)."""
+        k, addr = self._as_array(m, x, dtype, shape, f"{what}: shape {tuple(shape)} expected")
+        if m.location == DEVICE:
+            self._tensor_ready(k)
+        return k, addr
+
+    def _planes_arg(self, m: _Marshalled, planes, shape, count_error: str, shape_error: str, allow_none: bool = False):
+        """n float32 planes through _as_array: (owners, pointer array). allow_none: an entry may be None (a NULL plane).
+        One _tensor_ready behind the last conversion: the casts and copies all went onto one stream."""
+        planes = list(planes)
+        if len(planes) != m.n:
+            raise InvalidParams(count_error)
+        keep, ptrs = [], []
+        for p in planes:
+            if p is None and allow_none:
+                ptrs.append(None)
+                continue
+            k, addr = self._as_array(m, p, np.float32, shape, shape_error)
+            keep.append(k)
+            ptrs.append(addr)
+        if m.location == DEVICE and keep:
+            self._tensor_ready(keep[-1])
+        return keep, (C.c_void_p * m.n)(*ptrs)
+
+    def _maps_arg(self, m: _Marshalled, maps, optional: bool = False):
+        """n tightly packed H x W float32 planes where the frames live: (owners, pointer array). optional: `maps` may be
+        None (no table: (None, None)) and single entries may be None (NULL planes: all ones)."""
+        if optional and maps is None:
+            return None, None
+        return self._planes_arg(m, maps, (m.h, m.w), "one weight map (or None) per frame expected" if optional
+                                else "one weight map per frame expected", "weight maps: H x W planes expected", optional)
+
+    def _fields_arg(self, m: _Marshalled, fields, step, allow_none: bool = False):
+        """n tightly packed gh x gw x 2 float32 planes where the frames live: (owners, pointer array). allow_none: an entry
+        may be None (a NULL plane: no displacement). A bad step is left to the engine."""
+        shape = mesh_grid(m.w, m.h, step)[::-1] + (2,) if step in (8, 16, 32, 64, 128, 256) else None
+        return self._planes_arg(m, fields, shape, "one field per frame expected", "fields: gh x gw x 2 planes expected (mesh_grid)",
+                                allow_none)
+
+    def _warps_arg(self, warps, include, n):
+        Ms = []
+        for w in warps:
+            Md = np.asarray(w, np.float64).reshape(-1)
+            Ms.append(np.concatenate([Md, [0.0, 0.0, 1.0]]) if Md.size == 6 else Md)
+        if len(Ms) != n or any(x.size != 9 for x in Ms):
+            raise InvalidParams("one 3x3 (or 2x3) warp per frame expected")
+        inc = None if include is None else np.ascontiguousarray(np.asarray(include, np.int32).reshape(-1))
+        if inc is not None and inc.size != n:
+            raise InvalidParams("one include flag per frame expected")
+        return np.ascontiguousarray(np.stack(Ms)), inc
+
+    @staticmethod
+    def _border_arg(border_value):
+        """border_value padded to the four doubles the ABI reads."""
+        return np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+
+    def _warped(self, files, warps, include, is_affine, border=None, alpha=None):
+        """The head of every caller-held-warps call: self._stack, the warps and include flags (_warps_arg: the first
+        refusals of such a call), and the run every such ABI function starts with — [ctx, frames, warps, include,
+        is_affine, (border_mode, border_value), (alpha)], border = (border_mode, border_value) and alpha present or absent
+        as the function has them (drizzle and reject: no border; local_align: neither). Returns (m, head); the arrays behind
+        the head's addresses go into m.keep, so hold m until the C call has returned."""
+        m = self._stack(files)
+        Md, inc = self._warps_arg(warps, include, m.n)
+        m.keep += [Md, inc]
+        head = [self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), None if inc is None else C.c_void_p(inc.ctypes.data),
+                int(is_affine)]
+        if border is not None:
+            bv = self._border_arg(border[1])
+            m.keep.append(bv)
+            head += [int(border[0]), C.c_void_p(bv.ctypes.data)]
+        if alpha is not None:
+            head.append(float(alpha))
+        return m, head
+
+    def _whole_stack(self, kind, suffix, files, params, scale_down_width, return_stats, combine=(), outputs=(), after_stats=(),
+                     image_shape=None, n_stats=None):
+        """Every ecc_match* / keypoint_match* form (kind "ecc" or "keypoint", stk_<kind>_match<suffix>): the ECC-only size
+        refusal, self._stack, the output image, stats and dropped, the call, the result. The ABI's fixed order —
+        [ctx, frames, params, scale_down_width, *combine, image, (dropped if keypoint), *outputs, stats, *after_stats].
+        combine: the combine-specific arguments: a ctypes structure goes by reference, a numpy array by address, None as
+        NULL, a scalar as it is; a function is called with m first (what needs n: per-frame weights). They stay referenced
+        here until the call has returned. outputs, after_stats: [(wanted, make)], make(m, wanted) -> (argument or list of
+        arguments, value(stats list)) — built after the image, in the ABI's order, which is the order of the result.
+        image_shape(m): another output size than the frames'; n_stats(): how many stats the result carries (default n).
+        The result: a keypoint form always returns a tuple that starts with dropped; an ECC form the bare image when
+        nothing else is wanted, else the tuple; then the wanted values in order; the stats last."""
+        if kind == "ecc" and isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
+            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
+        m = self._stack(files)
+        out, img = self._image(m, image_shape(m) if image_shape else None)
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        p = params._c()
+        keep = [x(m) if callable(x) else x for x in combine]
+        args = [self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0)]
+        args += [C.byref(x) if isinstance(x, C.Structure) else C.c_void_p(x.ctypes.data) if isinstance(x, np.ndarray) else x for x in keep]
+        args += [C.byref(img)] + ([C.byref(dropped)] if kind == "keypoint" else [])
+        values = []
+        for group, end in ((outputs, [stats]), (after_stats, [])):
+            for wanted, make in group:
+                arg, value = make(m, wanted)
+                args += arg if isinstance(arg, list) else [arg]
+                if wanted:
+                    values.append(value)
+            args += end
+        self._check(getattr(self._lib, f"stk_{kind}_match{suffix}")(*args))
+        stl = self._stats_list(stats, m.n if n_stats is None else n_stats())
+        res = ((dropped.value,) if kind == "keypoint" else ()) + (out,) + tuple(v(stl) for v in values) + ((stl,) if return_stats else ())
+        return res if kind == "keypoint" or len(res) > 1 else out
+
+    # the makers of _whole_stack's optional outputs
+    def _out_plane(self, dtype, per_channel=False, shape=None):
+        """An optional output plane (_optional), NULL when not wanted; shape(m): another size than H x W."""
+        def make(m, wanted):
+            a, ptr = self._optional(m, wanted, dtype, per_channel, shape(m) if shape else None)
+            return ptr, lambda stl: a
+        return make
+
+    @staticmethod
+    def _out_applied(m, wanted):
+        """The per-frame records the fold used: always passed."""
+        applied = (_ffi.FrameWeight * m.n)()
+        return applied, lambda stl: Stacker._applied_list(applied, m.n, m.c)
+
+    def _out_norm_planes(self, kind, step):
+        """The local-normalisation planes by frame index, zeroed; frame 0 and dropped frames have none (None in the result)."""
+        def make(m, wanted):
+            if not wanted:
+                return None, None
+            gw, gh = mesh_grid(m.w, m.h, int(step))
+            planes = [np.zeros((gh, gw, 2 * m.c), np.float32) for _ in range(m.n)]
+            return (C.c_void_p * m.n)(*[p.ctypes.data for p in planes]), \
+                lambda stl: [None if i == 0 or (kind == "keypoint" and stl[i]["status"] != 0) else planes[i] for i in range(m.n)]
+        return make
+
+    def _weights_combine(self, weights):
+        """The per-frame weights of a whole-stack call as a combine argument: n f32, or NULL = all 1."""
+        return lambda m: self._weights_arg(weights, m.n)
 
     @staticmethod
     def _stats_list(stats, n):
@@ -668,18 +864,7 @@ class Stacker:
     # -- whole-stack API (the reference's two entry points) ---------------------------------------
     def ecc_match(self, files, params: EccMatchParameters, scale_down_width: Optional[float] = None,
                   return_stats: bool = False):
-        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        stats = (_ffi.FrameStats * m.n)()
-        p = params._c()
-        st = self._lib.stk_ecc_match(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                     C.byref(img), stats)
-        self._check(st)
-        return (out, self._stats_list(stats, m.n)) if return_stats else out
+        return self._whole_stack("ecc", "", files, params, scale_down_width, return_stats)
 
     def _keypoint_match_mixed(self, frames, params: KeyPointMatchParameters, return_stats: bool, scale_down_width=None):
         """Frames of differing size (host arrays, HxWx3 u8): ORB at each frame's own size, every frame warped into the FIRST
@@ -706,25 +891,13 @@ class Stacker:
                        return_stats: bool = False):
         if isinstance(files, (list, tuple)) and len({tuple(f.shape) for f in files}) > 1:
             return self._keypoint_match_mixed(files, params, return_stats, scale_down_width)
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p = params._c()
-        st = self._lib.stk_keypoint_match(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                          C.byref(img), C.byref(dropped), stats)
-        self._check(st)
-        return (dropped.value, out, self._stats_list(stats, m.n)) if return_stats else (dropped.value, out)
+        return self._whole_stack("keypoint", "", files, params, scale_down_width, return_stats)
 
     # -- score and rank a whole stack (the first half of examples/main.rs) ---------------------------------
     def stack_sharpness(self, files, ksize: int = 3):
         """LAPM, LAPV, TENG(ksize) and GLVN of every frame of an 8-bit stack in one device pass (stk_stack_sharpness): an
         n x 4 float64 array, the doubles sharpness_*(grey(frame)) return."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        m = self._stack(files)
         scores = np.zeros((m.n, 4), np.float64)
         self._check(self._lib.stk_stack_sharpness(self._h, C.byref(m.c_frames), int(ksize), C.c_void_p(scores.ctypes.data)))
         return scores
@@ -737,25 +910,19 @@ class Stacker:
         return order, n_kept, scores, weights
 
     def _ranked_match(self, kind, files, params, select, scale_down_width, return_stats, return_scores):
-        if kind == "ecc" and isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        stats = (_ffi.FrameStats * m.n)()
-        order = (C.c_int32 * m.n)()
-        kept, dropped = C.c_int32(0), C.c_int32(0)
-        scores = np.zeros((m.n, 4), np.float64)
-        p, sp = params._c(), (select or SelectParameters())._c()
-        args = [self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(img)]
-        if kind == "keypoint":
-            args.append(C.byref(dropped))
-        fn = self._lib.stk_keypoint_match_ranked if kind == "keypoint" else self._lib.stk_ecc_match_ranked
-        self._check(fn(*args, stats, C.byref(sp), order, C.byref(kept), C.c_void_p(scores.ctypes.data)))
-        res = ((dropped.value,) if kind == "keypoint" else ()) + (out, np.array(order[:kept.value], np.int32)) \
-            + ((scores,) if return_scores else ()) + ((self._stats_list(stats, kept.value),) if return_stats else ())
-        return res
+        """The ranked forms pass their ranking behind the stats — [.., stats, select, order, kept, scores] — and return
+        order[:kept] and the stats of the kept list."""
+        sp, kept = (select or SelectParameters())._c(), C.c_int32(0)
+
+        def ranking(m, wanted):
+            order = (C.c_int32 * m.n)()
+            return [C.byref(sp), order, C.byref(kept)], lambda stl: np.array(order[:kept.value], np.int32)
+
+        def scores(m, wanted):
+            sc = np.zeros((m.n, 4), np.float64)
+            return C.c_void_p(sc.ctypes.data), lambda stl: sc
+        return self._whole_stack(kind, "_ranked", files, params, scale_down_width, return_stats,
+                                 after_stats=[(True, ranking), (return_scores, scores)], n_stats=lambda: kept.value)
 
     def ecc_match_ranked(self, files, params: EccMatchParameters, select: Optional["SelectParameters"] = None,
                          scale_down_width: Optional[float] = None, return_scores: bool = False, return_stats: bool = False):
@@ -769,54 +936,22 @@ class Stacker:
         return self._ranked_match("keypoint", files, params, select, scale_down_width, return_stats, return_scores)
 
     # -- sigma-clipped combines (extension beyond the reference) -----------------------------------------
-    def _counts_image(self, m: _Marshalled):
-        """int32 HxWxC counts placed where the output lives."""
-        if m.location == DEVICE:
-            import torch
-            cnt = torch.empty((m.h, m.w, m.c), dtype=torch.int32, device=m.torch_device)
-            return cnt, C.c_void_p(cnt.data_ptr())
-        cnt = np.empty((m.h, m.w, m.c), np.int32)
-        return cnt, C.c_void_p(cnt.ctypes.data)
+    def _match_clipped(self, kind, suffix, cp, files, params, scale_down_width, return_stats, return_counts):
+        return self._whole_stack(kind, suffix, files, params, scale_down_width, return_stats, [cp],
+                                 [(return_counts, self._out_plane(np.int32, True))])
 
     def ecc_match_clipped(self, files, params: EccMatchParameters, clip: Optional["SigmaClipParameters"] = None,
                           scale_down_width: Optional[float] = None, return_stats: bool = False, return_counts: bool = False):
         """ecc_match with kappa-sigma rejection over the aligned frames instead of the plain mean (stk_ecc_match_clipped).
         Returns the image, then the per-pixel counts of kept samples (return_counts) and the stats (return_stats)."""
-        return self._ecc_match_clipped(self._lib.stk_ecc_match_clipped, (clip or SigmaClipParameters())._c(), files, params,
-                                       scale_down_width, return_stats, return_counts)
-
-    def _ecc_match_clipped(self, fn, cp, files, params, scale_down_width, return_stats, return_counts):
-        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
-        stats = (_ffi.FrameStats * m.n)()
-        p = params._c()
-        self._check(fn(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(cp), C.byref(img), cptr, stats))
-        res = (out,) + ((cnt,) if return_counts else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
-        return res if len(res) > 1 else out
+        return self._match_clipped("ecc", "_clipped", (clip or SigmaClipParameters())._c(), files, params, scale_down_width,
+                                   return_stats, return_counts)
 
     def keypoint_match_clipped(self, files, params: KeyPointMatchParameters, clip: Optional["SigmaClipParameters"] = None,
                                scale_down_width: Optional[float] = None, return_stats: bool = False, return_counts: bool = False):
         """keypoint_match with kappa-sigma rejection (stk_keypoint_match_clipped): (dropped, image[, counts][, stats])."""
-        return self._keypoint_match_clipped(self._lib.stk_keypoint_match_clipped, (clip or SigmaClipParameters())._c(), files, params,
-                                            scale_down_width, return_stats, return_counts)
-
-    def _keypoint_match_clipped(self, fn, cp, files, params, scale_down_width, return_stats, return_counts):
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p = params._c()
-        self._check(fn(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(cp), C.byref(img),
-                       C.byref(dropped), cptr, stats))
-        return (dropped.value, out) + ((cnt,) if return_counts else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return self._match_clipped("keypoint", "_clipped", (clip or SigmaClipParameters())._c(), files, params, scale_down_width,
+                                   return_stats, return_counts)
 
     def clip_stack(self, files, warps, clip: Optional["SigmaClipParameters"] = None, include=None, *, is_affine=False,
                    border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_counts: bool = False):
@@ -826,24 +961,10 @@ class Stacker:
                                 border_mode, border_value, alpha, return_counts)
 
     def _clip_stack(self, fn, cp, files, warps, include, is_affine, border_mode, border_value, alpha, return_counts):
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Ms = []
-        for w in warps:
-            Md = np.asarray(w, np.float64).reshape(-1)
-            Ms.append(np.concatenate([Md, [0.0, 0.0, 1.0]]) if Md.size == 6 else Md)
-        if len(Ms) != m.n or any(x.size != 9 for x in Ms):
-            raise InvalidParams("one 3x3 (or 2x3) warp per frame expected")
-        Md = np.ascontiguousarray(np.stack(Ms))
-        inc = None if include is None else np.ascontiguousarray(np.asarray(include, np.int32).reshape(-1))
-        if inc is not None and inc.size != m.n:
-            raise InvalidParams("one include flag per frame expected")
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
-        out, img = self._out_image(m)
-        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
-        self._check(fn(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), None if inc is None else C.c_void_p(inc.ctypes.data),
-                       int(is_affine), int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(cp), C.byref(img), cptr))
+        m, head = self._warped(files, warps, include, is_affine, (border_mode, border_value), alpha)
+        out, img = self._image(m)
+        cnt, cptr = self._optional(m, return_counts, np.int32, True)
+        self._check(fn(*head, C.byref(cp), C.byref(img), cptr))
         return (out, cnt) if return_counts else out
 
     # -- median / MAD clipped combines (extension beyond the reference) --------------------------------
@@ -851,15 +972,15 @@ class Stacker:
                                  scale_down_width: Optional[float] = None, return_stats: bool = False, return_counts: bool = False):
         """ecc_match with median / MAD rejection over the aligned frames (stk_ecc_match_robust_clipped): the clip that
         still rejects on a handful of frames. Returns as ecc_match_clipped."""
-        return self._ecc_match_clipped(self._lib.stk_ecc_match_robust_clipped, (clip or RobustClipParameters())._c(), files, params,
-                                       scale_down_width, return_stats, return_counts)
+        return self._match_clipped("ecc", "_robust_clipped", (clip or RobustClipParameters())._c(), files, params, scale_down_width,
+                                   return_stats, return_counts)
 
     def keypoint_match_robust_clipped(self, files, params: KeyPointMatchParameters, clip: Optional["RobustClipParameters"] = None,
                                       scale_down_width: Optional[float] = None, return_stats: bool = False,
                                       return_counts: bool = False):
         """keypoint_match with median / MAD rejection (stk_keypoint_match_robust_clipped): (dropped, image[, counts][, stats])."""
-        return self._keypoint_match_clipped(self._lib.stk_keypoint_match_robust_clipped, (clip or RobustClipParameters())._c(), files,
-                                            params, scale_down_width, return_stats, return_counts)
+        return self._match_clipped("keypoint", "_robust_clipped", (clip or RobustClipParameters())._c(), files, params,
+                                   scale_down_width, return_stats, return_counts)
 
     def robust_clip_stack(self, files, warps, clip: Optional["RobustClipParameters"] = None, include=None, *, is_affine=False,
                           border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_counts: bool = False):
@@ -872,67 +993,23 @@ class Stacker:
                            return_stats: bool = False):
         """ecc_match with a per-pixel quantile of the aligned frames instead of the plain mean (stk_ecc_match_quantile).
         quantile: QuantileParameters or a float in [0, 1]; None = the median."""
-        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        stats = (_ffi.FrameStats * m.n)()
-        p, qp = params._c(), _quantile_c(quantile)
-        self._check(self._lib.stk_ecc_match_quantile(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                     C.byref(qp), C.byref(img), stats))
-        return (out, self._stats_list(stats, m.n)) if return_stats else out
+        return self._whole_stack("ecc", "_quantile", files, params, scale_down_width, return_stats, [_quantile_c(quantile)])
 
     def keypoint_match_quantile(self, files, params: KeyPointMatchParameters, quantile=None,
                                 scale_down_width: Optional[float] = None, return_stats: bool = False):
         """keypoint_match with the quantile combine (stk_keypoint_match_quantile): (dropped, image[, stats])."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p, qp = params._c(), _quantile_c(quantile)
-        self._check(self._lib.stk_keypoint_match_quantile(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                          C.byref(qp), C.byref(img), C.byref(dropped), stats))
-        return (dropped.value, out, self._stats_list(stats, m.n)) if return_stats else (dropped.value, out)
+        return self._whole_stack("keypoint", "_quantile", files, params, scale_down_width, return_stats, [_quantile_c(quantile)])
 
     def quantile_stack(self, files, warps, quantile=None, include=None, *, is_affine=False, border_mode=BORDER_CONSTANT,
                        border_value=(0, 0, 0, 0), alpha=1.0 / 255.0):
         """The quantile combine alone over caller-held warps (stk_quantile_stack), with the arguments of clip_stack."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Ms = []
-        for w in warps:
-            Md = np.asarray(w, np.float64).reshape(-1)
-            Ms.append(np.concatenate([Md, [0.0, 0.0, 1.0]]) if Md.size == 6 else Md)
-        if len(Ms) != m.n or any(x.size != 9 for x in Ms):
-            raise InvalidParams("one 3x3 (or 2x3) warp per frame expected")
-        Md = np.ascontiguousarray(np.stack(Ms))
-        inc = None if include is None else np.ascontiguousarray(np.asarray(include, np.int32).reshape(-1))
-        if inc is not None and inc.size != m.n:
-            raise InvalidParams("one include flag per frame expected")
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
-        out, img = self._out_image(m)
+        m, head = self._warped(files, warps, include, is_affine, (border_mode, border_value), alpha)
+        out, img = self._image(m)
         qp = _quantile_c(quantile)
-        self._check(self._lib.stk_quantile_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                 None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
-                                                 int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(qp),
-                                                 C.byref(img)))
+        self._check(self._lib.stk_quantile_stack(*head, C.byref(qp), C.byref(img)))
         return out
 
     # -- weighted, coverage-aware combines (extension beyond the reference) ----------------------------
-    def _coverage_image(self, m: _Marshalled):
-        """f32 HxW summed-weight plane placed where the output lives."""
-        if m.location == DEVICE:
-            import torch
-            cov = torch.empty((m.h, m.w), dtype=torch.float32, device=m.torch_device)
-            return cov, C.c_void_p(cov.data_ptr())
-        cov = np.empty((m.h, m.w), np.float32)
-        return cov, C.c_void_p(cov.ctypes.data)
-
     @staticmethod
     def _applied_list(applied, n, cn):
         return [dict(gain=np.array(list(a.gain)[:cn], np.float32), offset=np.array(list(a.offset)[:cn], np.float32),
@@ -940,12 +1017,19 @@ class Stacker:
 
     @staticmethod
     def _weights_arg(weights, n):
+        """n per-frame weights as an f32 array, or None = all 1."""
         if weights is None:
-            return None, None
+            return None
         w = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
         if w.size != n:
             raise InvalidParams("one weight per frame expected")
-        return w, C.c_void_p(w.ctypes.data)
+        return w
+
+    def _match_weighted(self, kind, suffix, files, params, weight, weights, local, scale_down_width, return_stats, return_coverage,
+                        return_applied):
+        combine = [(weight or WeightParameters())._c(), self._weights_combine(weights)] + ([local._c()] if local else [])
+        return self._whole_stack(kind, suffix, files, params, scale_down_width, return_stats, combine,
+                                 [(return_coverage, self._out_plane(np.float32)), (return_applied, self._out_applied)])
 
     def ecc_match_weighted(self, files, params: EccMatchParameters, weight: Optional["WeightParameters"] = None, weights=None,
                            scale_down_width: Optional[float] = None, return_stats: bool = False, return_coverage: bool = False,
@@ -953,54 +1037,16 @@ class Stacker:
         """ecc_match with the weighted, coverage-aware mean and per-frame normalisation instead of the plain mean
         (stk_ecc_match_weighted). weights: one per frame or None = all 1. Returns the image, then the summed-weight plane
         (return_coverage), the per-frame records the fold used (return_applied) and the stats (return_stats)."""
-        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
-        wkeep, wptr = self._weights_arg(weights, m.n)
-        applied = (_ffi.FrameWeight * m.n)()
-        stats = (_ffi.FrameStats * m.n)()
-        p, wp = params._c(), (weight or WeightParameters())._c()
-        self._check(self._lib.stk_ecc_match_weighted(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                     C.byref(wp), wptr, C.byref(img), cptr, applied, stats))
-        res = (out,) + ((cov,) if return_coverage else ()) + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) \
-            + ((self._stats_list(stats, m.n),) if return_stats else ())
-        return res if len(res) > 1 else out
+        return self._match_weighted("ecc", "_weighted", files, params, weight, weights, None, scale_down_width, return_stats,
+                                    return_coverage, return_applied)
 
     def keypoint_match_weighted(self, files, params: KeyPointMatchParameters, weight: Optional["WeightParameters"] = None,
                                 weights=None, scale_down_width: Optional[float] = None, return_stats: bool = False,
                                 return_coverage: bool = False, return_applied: bool = False):
         """keypoint_match with the weighted combine (stk_keypoint_match_weighted): (dropped, image[, coverage][, applied]
         [, stats]). A dropped frame is no sample: weight 0 in `applied`."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
-        wkeep, wptr = self._weights_arg(weights, m.n)
-        applied = (_ffi.FrameWeight * m.n)()
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p, wp = params._c(), (weight or WeightParameters())._c()
-        self._check(self._lib.stk_keypoint_match_weighted(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                          C.byref(wp), wptr, C.byref(img), C.byref(dropped), cptr, applied, stats))
-        return (dropped.value, out) + ((cov,) if return_coverage else ()) \
-            + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
-
-    def _warps_arg(self, warps, include, n):
-        Ms = []
-        for w in warps:
-            Md = np.asarray(w, np.float64).reshape(-1)
-            Ms.append(np.concatenate([Md, [0.0, 0.0, 1.0]]) if Md.size == 6 else Md)
-        if len(Ms) != n or any(x.size != 9 for x in Ms):
-            raise InvalidParams("one 3x3 (or 2x3) warp per frame expected")
-        inc = None if include is None else np.ascontiguousarray(np.asarray(include, np.int32).reshape(-1))
-        if inc is not None and inc.size != n:
-            raise InvalidParams("one include flag per frame expected")
-        return np.ascontiguousarray(np.stack(Ms)), inc
+        return self._match_weighted("keypoint", "_weighted", files, params, weight, weights, None, scale_down_width, return_stats,
+                                    return_coverage, return_applied)
 
     def weighted_stack(self, files, warps, gain=None, offset=None, weights=None, include=None, *, applied=None, coverage: bool = True,
                        is_affine=False, border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0,
@@ -1008,34 +1054,20 @@ class Stacker:
         """The weighted combine alone over caller-held warps (stk_weighted_stack), with the arguments of clip_stack.
         gain, offset: n x channels (None = 1 / 0); weights: n (None = 1); or `applied`: the per-frame records another
         weighted call returned, used as given."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Md, inc = self._warps_arg(warps, include, m.n)
+        m, head = self._warped(files, warps, include, is_affine, (border_mode, border_value), alpha)
         rec = self._records_arg(m, gain, offset, weights, applied)
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
-        out, img = self._out_image(m)
-        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
-        self._check(self._lib.stk_weighted_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                 None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
-                                                 int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), rec, int(coverage),
-                                                 C.byref(img), cptr))
+        out, img = self._image(m)
+        cov, cptr = self._optional(m, return_coverage, np.float32)
+        self._check(self._lib.stk_weighted_stack(*head, rec, int(coverage), C.byref(img), cptr))
         return (out, cov) if return_coverage else out
 
     def overlap_moments(self, files, warps, include=None, *, stat_step: int = 4, is_affine=False, border_mode=BORDER_CONSTANT,
                         border_value=(0, 0, 0, 0), alpha=1.0 / 255.0):
         """The overlap moments of every included frame against frame 0 (stk_overlap_moments): an n x channels x 6 float64
         array (n, sum X, sum Y, sum X^2, sum Y^2, sum XY), zeros for frame 0 and excluded frames."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Md, inc = self._warps_arg(warps, include, m.n)
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        m, head = self._warped(files, warps, include, is_affine, (border_mode, border_value), alpha)
         mom = np.zeros((m.n, m.c, 6), np.float64)
-        self._check(self._lib.stk_overlap_moments(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                  None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
-                                                  int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), int(stat_step),
-                                                  C.c_void_p(mom.ctypes.data)))
+        self._check(self._lib.stk_overlap_moments(*head, int(stat_step), C.c_void_p(mom.ctypes.data)))
         return mom
 
     # -- local normalisation: gain and offset fields on a node grid (extension beyond the reference) ------
@@ -1043,23 +1075,16 @@ class Stacker:
                       border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0):
         """The cell moments of every included frame against frame 0 (stk_local_moments): an n x ch x cw x channels x 6
         float64 array, zeros for frame 0 and excluded frames."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Md, inc = self._warps_arg(warps, include, m.n)
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        m, head = self._warped(files, warps, include, is_affine, (border_mode, border_value), alpha)
         step = int(step)
         ch, cw = ((m.h + step - 1) // step, (m.w + step - 1) // step) if step > 0 else (1, 1)
         mom = np.zeros((m.n, ch, cw, m.c, 6), np.float64)
-        self._check(self._lib.stk_local_moments(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
-                                                int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), step, int(stat_step),
-                                                C.c_void_p(mom.ctypes.data)))
+        self._check(self._lib.stk_local_moments(*head, step, int(stat_step), C.c_void_p(mom.ctypes.data)))
         return mom
 
-    @staticmethod
-    def _norm_arg(m: _Marshalled, norm):
-        """n host planes by frame index (None entries allowed) -> (keep-alive list, pointer array or None)."""
+    def _norm_arg(self, m: _Marshalled, norm, step):
+        """n host planes by frame index (None entries allowed) for the grid of `step` -> (keep-alive list, pointer array or
+        None)."""
         if norm is None:
             return None, None
         if len(norm) != m.n:
@@ -1067,31 +1092,8 @@ class Stacker:
         keep = [None if p is None else np.ascontiguousarray(np.asarray(p, np.float32)) for p in norm]
         if any(p is not None and (p.ndim != 3 or p.shape[2] != 2 * m.c) for p in keep):
             raise InvalidParams("normalisation planes: gh x gw x 2 channels f32 expected")
-        ptrs = (C.c_void_p * m.n)(*[None if p is None else p.ctypes.data for p in keep])
-        return keep, ptrs
-
-    def local_norm_stack(self, files, warps, norm, step: int, gain=None, offset=None, weights=None, include=None, *, applied=None,
-                         coverage: bool = True, is_affine=False, border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0),
-                         alpha=1.0 / 255.0, return_den: bool = False):
-        """The locally normalised mean alone over caller-held warps (stk_local_norm_stack): weighted_stack whose gain and
-        offset come from `norm`, n planes (gh x gw x 2 channels, numpy) by frame index for the grid of `step`; a frame whose
-        plane is None uses its record (gain / offset / `applied`)."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Md, inc = self._warps_arg(warps, include, m.n)
-        rec = self._records_arg(m, gain, offset, weights, applied)
-        keep, nptr = self._norm_arg(m, norm)
-        if keep is not None:
-            self._norm_shapes(m, keep, step)
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
-        out, img = self._out_image(m)
-        den, dptr = self._coverage_image(m) if return_den else (None, None)
-        self._check(self._lib.stk_local_norm_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                   None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
-                                                   int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), rec, nptr, int(step),
-                                                   int(coverage), C.byref(img), dptr))
-        return (out, den) if return_den else out
+        self._norm_shapes(m, keep, step)
+        return keep, (C.c_void_p * m.n)(*[None if p is None else p.ctypes.data for p in keep])
 
     @staticmethod
     def _norm_shapes(m: _Marshalled, keep, step):
@@ -1102,65 +1104,47 @@ class Stacker:
         if any(p is not None and p.shape[:2] != (gh, gw) for p in keep):
             raise InvalidParams("normalisation planes: gh x gw x 2 channels f32 expected")
 
+    def _local_norm_stack(self, fn, cp, files, warps, norm, step, gain, offset, weights, include, applied, coverage, is_affine,
+                          border_mode, border_value, alpha, outputs):
+        """The *_local_norm stacks: [head, (combine parameters), records, planes, step, coverage, image, *outputs];
+        outputs: [(wanted, dtype, per_channel)]. The records are always built."""
+        m, head = self._warped(files, warps, include, is_affine, (border_mode, border_value), alpha)
+        rec = self._records_arg(m, gain, offset, weights, applied)
+        keep, nptr = self._norm_arg(m, norm, step)
+        out, img = self._image(m)
+        outs = [self._optional(m, *o) for o in outputs]
+        self._check(fn(*head, *([] if cp is None else [C.byref(cp)]), rec, nptr, int(step), int(coverage), C.byref(img),
+                       *[ptr for _, ptr in outs]))
+        res = (out,) + tuple(a for a, _ in outs if a is not None)
+        return res if len(res) > 1 else out
+
+    def local_norm_stack(self, files, warps, norm, step: int, gain=None, offset=None, weights=None, include=None, *, applied=None,
+                         coverage: bool = True, is_affine=False, border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0),
+                         alpha=1.0 / 255.0, return_den: bool = False):
+        """The locally normalised mean alone over caller-held warps (stk_local_norm_stack): weighted_stack whose gain and
+        offset come from `norm`, n planes (gh x gw x 2 channels, numpy) by frame index for the grid of `step`; a frame whose
+        plane is None uses its record (gain / offset / `applied`)."""
+        return self._local_norm_stack(self._lib.stk_local_norm_stack, None, files, warps, norm, step, gain, offset, weights, include,
+                                      applied, coverage, is_affine, border_mode, border_value, alpha, [(return_den, np.float32)])
+
     def quantile_stack_local_norm(self, files, warps, norm, step: int, quantile=None, gain=None, offset=None, weights=None,
                                   include=None, *, applied=None, coverage: bool = True, is_affine=False,
                                   border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0,
                                   return_counts: bool = False):
         """The locally normalised quantile alone over caller-held warps (stk_quantile_stack_local_norm):
         quantile_stack_weighted through the planes of local_norm_stack."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Md, inc = self._warps_arg(warps, include, m.n)
-        rec = self._records_arg(m, gain, offset, weights, applied)
-        keep, nptr = self._norm_arg(m, norm)
-        if keep is not None:
-            self._norm_shapes(m, keep, step)
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
-        out, img = self._out_image(m)
-        cnt, cptr = self._pixel_counts_image(m) if return_counts else (None, None)
-        qp = _quantile_c(quantile)
-        self._check(self._lib.stk_quantile_stack_local_norm(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                            None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
-                                                            int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(qp),
-                                                            rec, nptr, int(step), int(coverage), C.byref(img), cptr))
-        return (out, cnt) if return_counts else out
+        return self._local_norm_stack(self._lib.stk_quantile_stack_local_norm, _quantile_c(quantile), files, warps, norm, step, gain,
+                                      offset, weights, include, applied, coverage, is_affine, border_mode, border_value, alpha,
+                                      [(return_counts, np.int32)])
 
-    def _match_local_normalized(self, kind, files, params, norm, quantile, weights, scale_down_width, return_stats, return_den,
-                                return_counts, return_norm, return_applied):
-        if kind == "ecc" and isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
+    def _match_local_normalized(self, kind, suffix, files, params, norm, combine, weights, scale_down_width, return_stats, outputs,
+                                return_norm, return_applied):
+        """Both local-normalised families: [.., norm parameters, *combine, weights, image, .., *outputs, planes, applied,
+        stats]; frame 0 and dropped frames have no plane (_out_norm_planes)."""
         np_ = (norm or LocalNormParameters())._c()
-        den, dptr = self._coverage_image(m) if return_den else (None, None)
-        cnt, cptr = self._pixel_counts_image(m) if return_counts else (None, None)
-        qp = None if quantile is None else _quantile_c(quantile)
-        wkeep, wptr = self._weights_arg(weights, m.n)
-        planes, pptr = None, None
-        if return_norm:
-            gw, gh = mesh_grid(m.w, m.h, int(np_.step))
-            planes = [np.zeros((gh, gw, 2 * m.c), np.float32) for _ in range(m.n)]
-            pptr = (C.c_void_p * m.n)(*[p.ctypes.data for p in planes])
-        applied = (_ffi.FrameWeight * m.n)()
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p = params._c()
-        fn = getattr(self._lib, f"stk_{kind}_match_local_normalized")
-        args = [self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(np_),
-                None if qp is None else C.byref(qp), wptr, C.byref(img)]
-        if kind == "keypoint":
-            args.append(C.byref(dropped))
-        self._check(fn(*args, dptr, cptr, pptr, applied, stats))
-        stl = self._stats_list(stats, m.n)
-        if planes is not None:                      # frame 0 and dropped frames have no plane
-            planes = [None if i == 0 or (kind == "keypoint" and stl[i]["status"] != 0) else planes[i] for i in range(m.n)]
-        res = ((dropped.value,) if kind == "keypoint" else ()) + (out,) + ((den,) if return_den else ()) \
-            + ((cnt,) if return_counts else ()) + ((planes,) if return_norm else ()) \
-            + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) + ((stl,) if return_stats else ())
-        return res if len(res) > 1 else out
+        return self._whole_stack(kind, suffix, files, params, scale_down_width, return_stats,
+                                 [np_] + combine + [self._weights_combine(weights)],
+                                 outputs + [(return_norm, self._out_norm_planes(kind, np_.step)), (return_applied, self._out_applied)])
 
     def ecc_match_local_normalized(self, files, params: EccMatchParameters, norm: Optional["LocalNormParameters"] = None,
                                    quantile=None, weights=None, scale_down_width: Optional[float] = None, return_stats: bool = False,
@@ -1170,8 +1154,10 @@ class Stacker:
         `quantile` the locally normalised quantile. Returns the image, then den (return_den, mean only), the counts
         (return_counts, quantile only), the planes by frame index (return_norm; None for frame 0), the global records
         (return_applied) and the stats."""
-        return self._match_local_normalized("ecc", files, params, norm, quantile, weights, scale_down_width, return_stats, return_den,
-                                            return_counts, return_norm, return_applied)
+        return self._match_local_normalized("ecc", "_local_normalized", files, params, norm,
+                                            [None if quantile is None else _quantile_c(quantile)], weights, scale_down_width, return_stats,
+                                            [(return_den, self._out_plane(np.float32)), (return_counts, self._out_plane(np.int32))],
+                                            return_norm, return_applied)
 
     def keypoint_match_local_normalized(self, files, params: KeyPointMatchParameters, norm: Optional["LocalNormParameters"] = None,
                                         quantile=None, weights=None, scale_down_width: Optional[float] = None,
@@ -1179,39 +1165,21 @@ class Stacker:
                                         return_norm: bool = False, return_applied: bool = False):
         """keypoint_match with local normalisation (stk_keypoint_match_local_normalized): (dropped, image, ...) as
         ecc_match_local_normalized; a dropped frame has no plane and weight 0 in `applied`."""
-        return self._match_local_normalized("keypoint", files, params, norm, quantile, weights, scale_down_width, return_stats,
-                                            return_den, return_counts, return_norm, return_applied)
+        return self._match_local_normalized("keypoint", "_local_normalized", files, params, norm,
+                                            [None if quantile is None else _quantile_c(quantile)], weights, scale_down_width, return_stats,
+                                            [(return_den, self._out_plane(np.float32)), (return_counts, self._out_plane(np.int32))],
+                                            return_norm, return_applied)
 
     # -- the two clip combines through the planes --
-    def _clip_stack_local_norm(self, fn, cp, files, warps, norm, step, gain, offset, weights, include, applied, coverage, is_affine,
-                               border_mode, border_value, alpha, return_counts, return_kept_weight):
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Md, inc = self._warps_arg(warps, include, m.n)
-        rec = self._records_arg(m, gain, offset, weights, applied)
-        keep, nptr = self._norm_arg(m, norm)
-        if keep is not None:
-            self._norm_shapes(m, keep, step)
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
-        out, img = self._out_image(m)
-        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
-        kw, kptr = self._kept_image(m) if return_kept_weight else (None, None)
-        self._check(fn(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), None if inc is None else C.c_void_p(inc.ctypes.data),
-                       int(is_affine), int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(cp), rec, nptr, int(step),
-                       int(coverage), C.byref(img), cptr, kptr))
-        res = (out,) + ((cnt,) if return_counts else ()) + ((kw,) if return_kept_weight else ())
-        return res if len(res) > 1 else out
-
     def clip_stack_local_norm(self, files, warps, norm, step: int, clip: Optional["SigmaClipParameters"] = None, gain=None,
                               offset=None, weights=None, include=None, *, applied=None, coverage: bool = True, is_affine=False,
                               border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0,
                               return_counts: bool = False, return_kept_weight: bool = False):
         """The locally normalised sigma clip alone over caller-held warps (stk_clip_stack_local_norm): clip_stack_weighted
         through the planes of local_norm_stack. Returns the image, then the counts and the kept weight per pixel and channel."""
-        return self._clip_stack_local_norm(self._lib.stk_clip_stack_local_norm, (clip or SigmaClipParameters())._c(), files, warps,
-                                           norm, step, gain, offset, weights, include, applied, coverage, is_affine, border_mode,
-                                           border_value, alpha, return_counts, return_kept_weight)
+        return self._local_norm_stack(self._lib.stk_clip_stack_local_norm, (clip or SigmaClipParameters())._c(), files, warps, norm,
+                                      step, gain, offset, weights, include, applied, coverage, is_affine, border_mode, border_value,
+                                      alpha, [(return_counts, np.int32, True), (return_kept_weight, np.float32, True)])
 
     def robust_clip_stack_local_norm(self, files, warps, norm, step: int, clip: Optional["RobustClipParameters"] = None, gain=None,
                                      offset=None, weights=None, include=None, *, applied=None, coverage: bool = True,
@@ -1219,9 +1187,9 @@ class Stacker:
                                      return_counts: bool = False, return_kept_weight: bool = False):
         """The locally normalised median / MAD clip alone over caller-held warps (stk_robust_clip_stack_local_norm), with the
         arguments and results of clip_stack_local_norm."""
-        return self._clip_stack_local_norm(self._lib.stk_robust_clip_stack_local_norm, (clip or RobustClipParameters())._c(), files,
-                                           warps, norm, step, gain, offset, weights, include, applied, coverage, is_affine,
-                                           border_mode, border_value, alpha, return_counts, return_kept_weight)
+        return self._local_norm_stack(self._lib.stk_robust_clip_stack_local_norm, (clip or RobustClipParameters())._c(), files, warps,
+                                      norm, step, gain, offset, weights, include, applied, coverage, is_affine, border_mode,
+                                      border_value, alpha, [(return_counts, np.int32, True), (return_kept_weight, np.float32, True)])
 
     @staticmethod
     def _clip_choice(clip):
@@ -1234,42 +1202,6 @@ class Stacker:
             raise InvalidParams("clip: one of SigmaClipParameters and RobustClipParameters expected, not both")
         raise InvalidParams("clip: a SigmaClipParameters or a RobustClipParameters expected")
 
-    def _match_local_normalized_clipped(self, kind, files, params, norm, clip, weights, scale_down_width, return_stats, return_counts,
-                                        return_kept_weight, return_norm, return_applied):
-        cp, rp = self._clip_choice(clip)
-        if kind == "ecc" and isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        np_ = (norm or LocalNormParameters())._c()
-        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
-        kw, kptr = self._kept_image(m) if return_kept_weight else (None, None)
-        wkeep, wptr = self._weights_arg(weights, m.n)
-        planes, pptr = None, None
-        if return_norm:
-            gw, gh = mesh_grid(m.w, m.h, int(np_.step))
-            planes = [np.zeros((gh, gw, 2 * m.c), np.float32) for _ in range(m.n)]
-            pptr = (C.c_void_p * m.n)(*[p.ctypes.data for p in planes])
-        applied = (_ffi.FrameWeight * m.n)()
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p = params._c()
-        fn = getattr(self._lib, f"stk_{kind}_match_local_normalized_clipped")
-        args = [self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(np_),
-                None if cp is None else C.byref(cp), None if rp is None else C.byref(rp), wptr, C.byref(img)]
-        if kind == "keypoint":
-            args.append(C.byref(dropped))
-        self._check(fn(*args, cptr, kptr, pptr, applied, stats))
-        stl = self._stats_list(stats, m.n)
-        if planes is not None:                      # frame 0 and dropped frames have no plane
-            planes = [None if i == 0 or (kind == "keypoint" and stl[i]["status"] != 0) else planes[i] for i in range(m.n)]
-        res = ((dropped.value,) if kind == "keypoint" else ()) + (out,) + ((cnt,) if return_counts else ()) \
-            + ((kw,) if return_kept_weight else ()) + ((planes,) if return_norm else ()) \
-            + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) + ((stl,) if return_stats else ())
-        return res if len(res) > 1 else out
-
     def ecc_match_local_normalized_clipped(self, files, params: EccMatchParameters, norm: Optional["LocalNormParameters"] = None,
                                            clip=None, weights=None, scale_down_width: Optional[float] = None,
                                            return_stats: bool = False, return_counts: bool = False, return_kept_weight: bool = False,
@@ -1277,8 +1209,10 @@ class Stacker:
         """ecc_match with local normalisation and rejection (stk_ecc_match_local_normalized_clipped). clip: a
         SigmaClipParameters (the locally normalised sigma clip) or a RobustClipParameters (the median / MAD clip); exactly
         one. Returns the image, then the counts, the kept weight, the planes by frame index, the global records and the stats."""
-        return self._match_local_normalized_clipped("ecc", files, params, norm, clip, weights, scale_down_width, return_stats,
-                                                    return_counts, return_kept_weight, return_norm, return_applied)
+        return self._match_local_normalized("ecc", "_local_normalized_clipped", files, params, norm, list(self._clip_choice(clip)),
+                                            weights, scale_down_width, return_stats,
+                                            [(return_counts, self._out_plane(np.int32, True)),
+                                             (return_kept_weight, self._out_plane(np.float32, True))], return_norm, return_applied)
 
     def keypoint_match_local_normalized_clipped(self, files, params: KeyPointMatchParameters,
                                                 norm: Optional["LocalNormParameters"] = None, clip=None, weights=None,
@@ -1287,35 +1221,26 @@ class Stacker:
                                                 return_norm: bool = False, return_applied: bool = False):
         """keypoint_match with local normalisation and rejection (stk_keypoint_match_local_normalized_clipped): (dropped,
         image, ...) as ecc_match_local_normalized_clipped."""
-        return self._match_local_normalized_clipped("keypoint", files, params, norm, clip, weights, scale_down_width, return_stats,
-                                                    return_counts, return_kept_weight, return_norm, return_applied)
+        return self._match_local_normalized("keypoint", "_local_normalized_clipped", files, params, norm, list(self._clip_choice(clip)),
+                                            weights, scale_down_width, return_stats,
+                                            [(return_counts, self._out_plane(np.int32, True)),
+                                             (return_kept_weight, self._out_plane(np.float32, True))], return_norm, return_applied)
 
     # -- per-pixel weight maps and local-sharpness stacking (extension beyond the reference) --------------
     def local_sharpness(self, files, local: Optional["LocalParameters"] = None):
         """The local quality map of every frame of an 8-bit stack (stk_local_sharpness): n x H x W float32, exact integers,
         placed where the frames live (a numpy array for host frames, a tensor for device frames)."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        if m.location == DEVICE:
-            import torch
-            maps = torch.empty((m.n, m.h, m.w), dtype=torch.float32, device=m.torch_device)
-            base = maps.data_ptr()
-        else:
-            maps = np.empty((m.n, m.h, m.w), np.float32)
-            base = maps.ctypes.data
-        ptrs = (C.c_void_p * m.n)(*[base + i * m.h * m.w * 4 for i in range(m.n)])
+        m = self._stack(files)
+        maps, ptrs = self._plane_table(m, (m.h, m.w), np.float32)
         lp = (local or LocalParameters())._c()
-        self._check(self._lib.stk_local_sharpness(self._h, C.byref(m.c_frames), C.byref(lp), C.cast(ptrs, C.c_void_p)))
+        self._check(self._lib.stk_local_sharpness(self._h, C.byref(m.c_frames), C.byref(lp), ptrs))
         return maps
 
     # -- star registration (extension beyond the reference) ------------------------------------------------
     def star_detect(self, files, params: Optional["StarParameters"] = None, return_peaks: bool = False):
         """The stars of every frame of an 8-bit stack (stk_star_detect), brightest first: a list of n STAR_DTYPE arrays;
         return_peaks adds the n peak counts before truncation."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        m = self._stack(files)
         p = (params or StarParameters())._c()
         cap = max(int(p.max_stars), 1)
         stars = np.zeros((m.n, cap), STAR_DTYPE)
@@ -1331,9 +1256,7 @@ class Stacker:
     def star_align(self, files, params: Optional["StarParameters"] = None):
         """Star registration without the fold (stk_star_align): (dropped, stats). The stats' warps feed any *_stack combine
         with include = [s["status"] == 0 for s in stats] and is_affine = False."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        m = self._stack(files)
         p = (params or StarParameters())._c()
         stats = (_ffi.FrameStats * m.n)()
         dropped = C.c_int32(0)
@@ -1342,11 +1265,9 @@ class Stacker:
 
     def star_match(self, files, params: Optional["StarParameters"] = None, return_stats: bool = False):
         """Star registration and the plain mean over frame 0 and the kept frames (stk_star_match): (dropped, image[, stats])."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        m = self._stack(files)
         p = (params or StarParameters())._c()
-        out, img = self._out_image(m)
+        out, img = self._image(m)
         stats = (_ffi.FrameStats * m.n)()
         dropped = C.c_int32(0)
         self._check(self._lib.stk_star_match(self._h, C.byref(m.c_frames), C.byref(p), C.byref(img), C.byref(dropped), stats))
@@ -1399,9 +1320,7 @@ class Stacker:
         the frames live: an n x H x W x C array or tensor of the frames' dtype (or float32, cal.out_depth = 32). `out`: n
         images the caller holds instead (same location as the frames; row-strided views allowed, all with one row step);
         only their pixel bytes are written, and they must not overlap the frames or the masters."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        m = self._stack(files)
         keep = []
         c = _ffi.Calibration()
         for name in ("bias", "dark", "flat"):
@@ -1431,13 +1350,7 @@ class Stacker:
         if out is None:
             if dt is None:
                 raise InvalidParams("out_depth must be 8, 16 or 32")
-            if m.location == DEVICE:
-                import torch
-                res = torch.empty((m.n, m.h, m.w, m.c), dtype=getattr(torch, dt), device=m.torch_device)
-                base = res.data_ptr()
-            else:
-                res = np.empty((m.n, m.h, m.w, m.c), dt)
-                base = res.ctypes.data
+            res, base = self._alloc(m, (m.n, m.h, m.w, m.c), dt)
             ptrs = [base + i * m.h * m.w * m.c * (c.out_depth // 8) for i in range(m.n)]
         else:
             res = out
@@ -1484,11 +1397,7 @@ class Stacker:
         if map is None:
             if p.accumulate:
                 raise InvalidParams("accumulate needs the map to accumulate into")
-            if img.location == DEVICE:
-                import torch
-                map = torch.empty((img.height, img.width), dtype=torch.uint8, device=keep[0].device)
-            else:
-                map = np.empty((img.height, img.width), np.uint8)
+            map = self._alloc(keep[0].device if img.location == DEVICE else None, (img.height, img.width), np.uint8)[0]
         if _is_torch(map) and not map.is_cuda:
             map = map.numpy()
         if (_is_torch(map) and not map.is_contiguous()) or (not _is_torch(map) and not (isinstance(map, np.ndarray) and map.flags.c_contiguous)):
@@ -1519,12 +1428,10 @@ class Stacker:
         """A master from a stack of calibration frames (stk_master_stack): the median / MAD clip over all frames under
         identity warps in raw sample units; normalize = 2 (flats) brings every frame to frame 0's level first. clip None:
         kappa 3 / 3, sigma_floor 0.5 (half a step of integer frames), 2 iterations."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        m = self._stack(files)
         cp = (clip or RobustClipParameters(3.0, 3.0, 0.5, 2))._c()
-        out, img = self._out_image(m)
-        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
+        out, img = self._image(m)
+        cnt, cptr = self._optional(m, return_counts, np.int32, True)
         self._check(self._lib.stk_master_stack(self._h, C.byref(m.c_frames), int(normalize), int(stat_step), C.byref(cp), C.byref(img), cptr))
         return (out, cnt) if return_counts else out
 
@@ -1539,31 +1446,6 @@ class Stacker:
         cal = self.calibrate(flats, CalibrationParameters(bias=bias, dark=dark, dark_scale=dark_scale, out_depth=32))
         return self.master_stack(cal, 2, clip, stat_step=stat_step)
 
-    def _maps_arg(self, m: _Marshalled, maps):
-        """n tightly packed H x W float32 planes where the frames live: (owners, pointer array)."""
-        planes = list(maps)
-        if len(planes) != m.n:
-            raise InvalidParams("one weight map per frame expected")
-        keep, ptrs = [], []
-        for p in planes:
-            if m.location == DEVICE:
-                import torch
-                t = p if _is_torch(p) else torch.from_numpy(np.ascontiguousarray(np.asarray(p, np.float32)))
-                t = t.to(device=m.torch_device, dtype=torch.float32).contiguous()
-                if tuple(t.shape) != (m.h, m.w):
-                    raise InvalidParams("weight maps: H x W planes expected")
-                keep.append(t)
-                ptrs.append(t.data_ptr())
-            else:
-                a = np.ascontiguousarray(np.asarray(p.cpu().numpy() if _is_torch(p) else p, np.float32))
-                if a.shape != (m.h, m.w):
-                    raise InvalidParams("weight maps: H x W planes expected")
-                keep.append(a)
-                ptrs.append(a.ctypes.data)
-        if m.location == DEVICE and keep:
-            self._tensor_ready(keep[-1])          # the casts and copies above all went onto one stream
-        return keep, (C.c_void_p * m.n)(*ptrs)
-
     def local_weighted_stack(self, files, warps, maps, gain=None, offset=None, weights=None, include=None, *, applied=None,
                              floor: float = 1.0, power: int = 2, is_affine=False, border_mode=BORDER_CONSTANT,
                              border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_coverage: bool = False):
@@ -1571,20 +1453,13 @@ class Stacker:
         (stk_local_weighted_stack): weighted_stack with the weight of frame i at a pixel multiplied by (the bilinear sample
         of maps[i] there + floor) ** power. maps: n H x W float32 planes of non-negative weights (a quality map from
         local_sharpness, a mask, an inverse variance). return_coverage adds the summed weight den."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Md, inc = self._warps_arg(warps, include, m.n)
-        rec = None if (gain is None and offset is None and weights is None and applied is None) \
-            else self._records_arg(m, gain, offset, weights, applied)
+        m, head = self._warped(files, warps, include, is_affine, (border_mode, border_value), alpha)
+        rec = self._records_arg(m, gain, offset, weights, applied, optional=True)
         mkeep, mptrs = self._maps_arg(m, maps)
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
-        out, img = self._out_image(m)
-        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
-        self._check(self._lib.stk_local_weighted_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                       None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
-                                                       int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), rec,
-                                                       C.cast(mptrs, C.c_void_p), float(floor), int(power), C.byref(img), cptr))
+        out, img = self._image(m)
+        cov, cptr = self._optional(m, return_coverage, np.float32)
+        self._check(self._lib.stk_local_weighted_stack(*head, rec, C.cast(mptrs, C.c_void_p), float(floor), int(power), C.byref(img),
+                                                       cptr))
         return (out, cov) if return_coverage else out
 
     def ecc_match_local_weighted(self, files, params: EccMatchParameters, local: Optional["LocalParameters"] = None,
@@ -1592,22 +1467,8 @@ class Stacker:
                                  return_stats: bool = False, return_coverage: bool = False, return_applied: bool = False):
         """ecc_match with the local-weighted fold (stk_ecc_match_local_weighted): every frame weighs in at a pixel by its
         local sharpness there. Arguments and results as ecc_match_weighted; weight.coverage must be True."""
-        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
-        wkeep, wptr = self._weights_arg(weights, m.n)
-        applied = (_ffi.FrameWeight * m.n)()
-        stats = (_ffi.FrameStats * m.n)()
-        p, wp, lp = params._c(), (weight or WeightParameters())._c(), (local or LocalParameters())._c()
-        self._check(self._lib.stk_ecc_match_local_weighted(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                           C.byref(wp), wptr, C.byref(lp), C.byref(img), cptr, applied, stats))
-        res = (out,) + ((cov,) if return_coverage else ()) + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) \
-            + ((self._stats_list(stats, m.n),) if return_stats else ())
-        return res if len(res) > 1 else out
+        return self._match_weighted("ecc", "_local_weighted", files, params, weight, weights, local or LocalParameters(),
+                                    scale_down_width, return_stats, return_coverage, return_applied)
 
     def keypoint_match_local_weighted(self, files, params: KeyPointMatchParameters, local: Optional["LocalParameters"] = None,
                                       weight: Optional["WeightParameters"] = None, weights=None,
@@ -1615,21 +1476,8 @@ class Stacker:
                                       return_coverage: bool = False, return_applied: bool = False):
         """keypoint_match with the local-weighted fold (stk_keypoint_match_local_weighted): (dropped, image[, coverage]
         [, applied][, stats]). A dropped frame is no sample: weight 0 in `applied`."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
-        wkeep, wptr = self._weights_arg(weights, m.n)
-        applied = (_ffi.FrameWeight * m.n)()
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p, wp, lp = params._c(), (weight or WeightParameters())._c(), (local or LocalParameters())._c()
-        self._check(self._lib.stk_keypoint_match_local_weighted(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                                C.byref(wp), wptr, C.byref(lp), C.byref(img), C.byref(dropped), cptr,
-                                                                applied, stats))
-        return (dropped.value, out) + ((cov,) if return_coverage else ()) \
-            + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return self._match_weighted("keypoint", "_local_weighted", files, params, weight, weights, local or LocalParameters(),
+                                    scale_down_width, return_stats, return_coverage, return_applied)
 
     # -- local alignment: displacement fields on a node grid (extension beyond the reference) -----------
     def local_align(self, files, warps, mesh: Optional["MeshParameters"] = None, include=None, *, is_affine=False,
@@ -1653,96 +1501,31 @@ class Stacker:
         if m.n != 1:
             raise InvalidParams("grey_pyramid: one frame expected")
         levels = int(levels)
-        planes, ptrs = [], [None]
-        for l in range(1, max(levels, 1)):
-            shape = (max(m.h >> l, 1), max(m.w >> l, 1))
-            if m.location == DEVICE:
-                import torch
-                planes.append(torch.zeros(shape, dtype=torch.uint8, device=m.torch_device))
-                ptrs.append(planes[-1].data_ptr())
-            else:
-                planes.append(np.zeros(shape, np.uint8))
-                ptrs.append(planes[-1].ctypes.data)
-        if m.location == DEVICE and planes:
-            self._tensor_ready(planes[-1])        # the fills above
-        pp = (C.c_void_p * len(ptrs))(*ptrs)
+        made = [self._alloc(m, (max(m.h >> l, 1), max(m.w >> l, 1)), np.uint8, 0) for l in range(1, max(levels, 1))]
+        pp = (C.c_void_p * (len(made) + 1))(None, *[addr for _, addr in made])
         self._check(self._lib.stk_grey_pyramid(self._h, C.byref(m.c_frames), levels, C.cast(pp, C.c_void_p)))
-        return planes
+        return [a for a, _ in made]
 
     def _local_align(self, files, warps, mesh, include, is_affine, return_status, levels):
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        m, head = self._warped(files, warps, include, is_affine)
         mp = (mesh or MeshParameters())._c()
-        Md, inc = self._warps_arg(warps, include, m.n)
         gw, gh = mesh_grid(m.w, m.h, mp.step) if mp.step in (8, 16, 32, 64, 128, 256) else (1, 1)
-        if m.location == DEVICE:
-            import torch
-            fields = torch.zeros((m.n, gh, gw, 2), dtype=torch.float32, device=m.torch_device)
-            status = torch.zeros((m.n, gh, gw), dtype=torch.int32, device=m.torch_device)
-            self._tensor_ready(status)            # both fills: the engine writes over them
-            fbase, sbase = fields.data_ptr(), status.data_ptr()
-        else:
-            fields = np.zeros((m.n, gh, gw, 2), np.float32)
-            status = np.zeros((m.n, gh, gw), np.int32)
-            fbase, sbase = fields.ctypes.data, status.ctypes.data
-        fp = (C.c_void_p * m.n)(*[fbase + i * gh * gw * 8 for i in range(m.n)])
-        sp = (C.c_void_p * m.n)(*[sbase + i * gh * gw * 4 for i in range(m.n)])
-        iptr = None if inc is None else C.c_void_p(inc.ctypes.data)
-        sptr = C.cast(sp, C.c_void_p) if return_status else None
+        fields, fptr = self._plane_table(m, (gh, gw, 2), np.float32, 0)      # zeroed: the engine writes over them
+        status, sptr = self._plane_table(m, (gh, gw), np.int32, 0)
         if levels is None:
-            self._check(self._lib.stk_local_align(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), iptr, int(is_affine),
-                                                  C.byref(mp), C.cast(fp, C.c_void_p), sptr))
+            self._check(self._lib.stk_local_align(*head, C.byref(mp), fptr, sptr if return_status else None))
         else:
-            self._check(self._lib.stk_local_align_pyramid(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), iptr, int(is_affine),
-                                                          C.byref(mp), levels, C.cast(fp, C.c_void_p), sptr))
+            self._check(self._lib.stk_local_align_pyramid(*head, C.byref(mp), levels, fptr, sptr if return_status else None))
         return (fields, status) if return_status else fields
-
-    def _fields_arg(self, m: _Marshalled, fields, step, allow_none: bool = False):
-        """n tightly packed gh x gw x 2 float32 planes where the frames live: (owners, pointer array). allow_none: an entry
-        may be None (a NULL plane: no displacement)."""
-        gw, gh = mesh_grid(m.w, m.h, step) if step in (8, 16, 32, 64, 128, 256) else (None, None)
-        planes = list(fields)
-        if len(planes) != m.n:
-            raise InvalidParams("one field per frame expected")
-        keep, ptrs = [], []
-        for p in planes:
-            if p is None and allow_none:
-                ptrs.append(None)
-                continue
-            if m.location == DEVICE:
-                import torch
-                t = p if _is_torch(p) else torch.from_numpy(np.ascontiguousarray(np.asarray(p, np.float32)))
-                t = t.to(device=m.torch_device, dtype=torch.float32).contiguous()
-                shape = tuple(t.shape)
-                keep.append(t)
-                ptrs.append(t.data_ptr())
-            else:
-                a = np.ascontiguousarray(np.asarray(p.cpu().numpy() if _is_torch(p) else p, np.float32))
-                shape = a.shape
-                keep.append(a)
-                ptrs.append(a.ctypes.data)
-            if gw is not None and shape != (gh, gw, 2):
-                raise InvalidParams("fields: gh x gw x 2 planes expected (mesh_grid)")
-        if m.location == DEVICE and keep:
-            self._tensor_ready(keep[-1])          # the casts and copies above all went onto one stream
-        return keep, (C.c_void_p * m.n)(*ptrs)
 
     def mesh_stack(self, files, warps, fields, step: int, include=None, *, is_affine=False, border_mode=BORDER_CONSTANT,
                    border_value=(0, 0, 0, 0), alpha=1.0 / 255.0):
         """The plain mean of the included frames, each folded through its warp and its displacement field
         (stk_mesh_stack). fields: n gh x gw x 2 float32 planes for the grid of `step` (local_align's result)."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Md, inc = self._warps_arg(warps, include, m.n)
+        m, head = self._warped(files, warps, include, is_affine, (border_mode, border_value), alpha)
         fkeep, fptrs = self._fields_arg(m, fields, step)
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
-        out, img = self._out_image(m)
-        self._check(self._lib.stk_mesh_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                             None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine), int(border_mode),
-                                             C.c_void_p(bv.ctypes.data), float(alpha), C.cast(fptrs, C.c_void_p), int(step),
-                                             C.byref(img)))
+        out, img = self._image(m)
+        self._check(self._lib.stk_mesh_stack(*head, C.cast(fptrs, C.c_void_p), int(step), C.byref(img)))
         return out
 
     def mesh_local_weighted_stack(self, files, warps, maps, fields, step: int, gain=None, offset=None, weights=None, include=None, *,
@@ -1750,46 +1533,29 @@ class Stacker:
                                   border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_coverage: bool = False):
         """local_weighted_stack through displacement fields (stk_mesh_local_weighted_stack): samples, coverage and the
         weight maps are all taken at the displaced coordinates."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Md, inc = self._warps_arg(warps, include, m.n)
-        rec = None if (gain is None and offset is None and weights is None and applied is None) \
-            else self._records_arg(m, gain, offset, weights, applied)
+        m, head = self._warped(files, warps, include, is_affine, (border_mode, border_value), alpha)
+        rec = self._records_arg(m, gain, offset, weights, applied, optional=True)
         mkeep, mptrs = self._maps_arg(m, maps)
         fkeep, fptrs = self._fields_arg(m, fields, step)
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
-        out, img = self._out_image(m)
-        cov, cptr = self._coverage_image(m) if return_coverage else (None, None)
-        self._check(self._lib.stk_mesh_local_weighted_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                            None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
-                                                            int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), rec,
-                                                            C.cast(mptrs, C.c_void_p), float(floor), int(power),
+        out, img = self._image(m)
+        cov, cptr = self._optional(m, return_coverage, np.float32)
+        self._check(self._lib.stk_mesh_local_weighted_stack(*head, rec, C.cast(mptrs, C.c_void_p), float(floor), int(power),
                                                             C.cast(fptrs, C.c_void_p), int(step), C.byref(img), cptr))
         return (out, cov) if return_coverage else out
+
+    def _match_local_aligned(self, kind, files, params, mesh, local, scale_down_width, return_stats, levels):
+        """The plain function, or with `levels` the pyramid one: [.., mesh, (levels), local or NULL, image, ..]."""
+        mp, lp = (mesh or MeshParameters())._c(), None if local is None else local._c()
+        if levels is None:
+            return self._whole_stack(kind, "_local_aligned", files, params, scale_down_width, return_stats, [mp, lp])
+        return self._whole_stack(kind, "_local_aligned_pyramid", files, params, scale_down_width, return_stats, [mp, int(levels), lp])
 
     def ecc_match_local_aligned(self, files, params: EccMatchParameters, mesh: Optional["MeshParameters"] = None,
                                 local: Optional["LocalParameters"] = None, scale_down_width: Optional[float] = None,
                                 return_stats: bool = False, *, _levels: Optional[int] = None):
         """ecc_match with local alignment (stk_ecc_match_local_aligned): every frame is folded through its ECC warp and the
         displacement field measured on top of it. local = None: the plain mean; else the local-sharpness weighted fold."""
-        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        stats = (_ffi.FrameStats * m.n)()
-        p, mp = params._c(), (mesh or MeshParameters())._c()
-        lp = None if local is None else local._c()
-        if _levels is None:
-            self._check(self._lib.stk_ecc_match_local_aligned(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                              C.byref(mp), None if lp is None else C.byref(lp), C.byref(img), stats))
-        else:
-            self._check(self._lib.stk_ecc_match_local_aligned_pyramid(self._h, C.byref(m.c_frames), C.byref(p),
-                                                                      float(scale_down_width or 0.0), C.byref(mp), int(_levels),
-                                                                      None if lp is None else C.byref(lp), C.byref(img), stats))
-        return (out, self._stats_list(stats, m.n)) if return_stats else out
+        return self._match_local_aligned("ecc", files, params, mesh, local, scale_down_width, return_stats, _levels)
 
     def ecc_match_local_aligned_pyramid(self, files, params: EccMatchParameters, mesh: Optional["MeshParameters"] = None,
                                         levels: int = 3, local: Optional["LocalParameters"] = None,
@@ -1807,42 +1573,35 @@ class Stacker:
                                      local: Optional["LocalParameters"] = None, scale_down_width: Optional[float] = None,
                                      return_stats: bool = False, *, _levels: Optional[int] = None):
         """keypoint_match with local alignment (stk_keypoint_match_local_aligned): (dropped, image[, stats])."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p, mp = params._c(), (mesh or MeshParameters())._c()
-        lp = None if local is None else local._c()
-        if _levels is None:
-            self._check(self._lib.stk_keypoint_match_local_aligned(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                                   C.byref(mp), None if lp is None else C.byref(lp), C.byref(img),
-                                                                   C.byref(dropped), stats))
-        else:
-            self._check(self._lib.stk_keypoint_match_local_aligned_pyramid(self._h, C.byref(m.c_frames), C.byref(p),
-                                                                           float(scale_down_width or 0.0), C.byref(mp), int(_levels),
-                                                                           None if lp is None else C.byref(lp), C.byref(img),
-                                                                           C.byref(dropped), stats))
-        return (dropped.value, out) + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return self._match_local_aligned("keypoint", files, params, mesh, local, scale_down_width, return_stats, _levels)
 
     # -- drizzle integration onto a finer or larger output grid (extension beyond the reference) ----------
-    def _drizzle_images(self, m: _Marshalled, drizzle: "DrizzleParameters", out_shape, return_den: bool):
-        """The oh x ow x C output (out_shape, or what covers frame 0 at the scale) and the weight image, where the frames live."""
-        oh, ow = (int(v) for v in out_shape) if out_shape is not None else drizzle.out_shape(m.h, m.w)
-        if oh < 1 or ow < 1:
-            raise InvalidParams("drizzle: the output must be at least one pixel wide and high")
-        if m.location == DEVICE:
-            import torch
-            out = torch.empty((oh, ow, m.c), dtype=torch.float32, device=m.torch_device)
-            den = torch.empty((oh, ow), dtype=torch.float32, device=m.torch_device) if return_den else None
-            ptr = (lambda t: t.data_ptr())
-        else:
-            out = np.empty((oh, ow, m.c), np.float32)
-            den = np.empty((oh, ow), np.float32) if return_den else None
-            ptr = (lambda a: a.ctypes.data)
-        img = _ffi.ImageF32(ptr(out), ow, oh, m.c, m.location, 0)
-        return out, img, den, (C.c_void_p(ptr(den)) if return_den else None)
+    @staticmethod
+    def _drizzle_shape(drizzle: "DrizzleParameters", out_shape):
+        """m -> the (oh, ow) of a drizzle output: out_shape, or what covers frame 0 at the scale."""
+        def shape(m):
+            oh, ow = (int(v) for v in out_shape) if out_shape is not None else drizzle.out_shape(m.h, m.w)
+            if oh < 1 or ow < 1:
+                raise InvalidParams("drizzle: the output must be at least one pixel wide and high")
+            return oh, ow
+        return shape
+
+    def _drizzle_stack(self, fn, files, warps, mesh, drizzle, gain, offset, weights, include, applied, maps, out_shape,
+                       is_affine, alpha, return_den):
+        """Both drizzle stacks: [head, drizzle, records or NULL, maps or NULL, (fields, step), image, den]."""
+        m, head = self._warped(files, warps, include, is_affine, None, alpha)
+        dz = drizzle or DrizzleParameters()
+        rec = self._records_arg(m, gain, offset, weights, applied, optional=True)
+        mkeep, mptrs = self._maps_arg(m, maps, optional=True)
+        if mesh is not None:                          # (fields, step)
+            fkeep, fptrs = self._fields_arg(m, mesh[0], mesh[1], allow_none=True)
+            mesh = [C.cast(fptrs, C.c_void_p), int(mesh[1])]
+        shape = self._drizzle_shape(dz, out_shape)(m)
+        out, img = self._image(m, shape)
+        den, dptr = self._optional(m, return_den, np.float32, shape=shape)
+        p = dz._c()
+        self._check(fn(*head, C.byref(p), rec, None if mptrs is None else C.cast(mptrs, C.c_void_p), *(mesh or []), C.byref(img), dptr))
+        return (out, den) if return_den else out
 
     def drizzle_stack(self, files, warps, drizzle: Optional["DrizzleParameters"] = None, gain=None, offset=None, weights=None,
                       include=None, *, applied=None, maps=None, out_shape=None, is_affine=False, alpha=1.0 / 255.0,
@@ -1851,67 +1610,29 @@ class Stacker:
         at the scale). gain, offset, weights, applied: as in weighted_stack (None = 1 / 0 / 1). maps: None, or one H x W
         float32 plane of non-negative weights per frame (a bad-pixel mask, an inverse variance), single entries may be None
         = all ones. Returns the image, with return_den also the weight image."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        return self._drizzle_stack(self._lib.stk_drizzle_stack, files, warps, None, drizzle, gain, offset, weights, include,
+                                   applied, maps, out_shape, is_affine, alpha, return_den)
+
+    def _match_drizzle(self, kind, suffix, files, params, combine, drizzle, scale_down_width, out_shape, return_den, return_stats):
         dz = drizzle or DrizzleParameters()
-        Md, inc = self._warps_arg(warps, include, m.n)
-        rec = None if (gain is None and offset is None and weights is None and applied is None) \
-            else self._records_arg(m, gain, offset, weights, applied)
-        mkeep, mptrs = None, None
-        if maps is not None:
-            planes = list(maps)
-            if len(planes) != m.n:
-                raise InvalidParams("one weight map (or None) per frame expected")
-            some = [p for p in planes if p is not None]
-            sub = copy.copy(m)                      # the planes that exist, marshalled like local_weighted_stack's
-            sub.n = len(some)
-            mkeep, some_ptrs = self._maps_arg(sub, some) if some else ([], [])
-            it = iter(some_ptrs)
-            mptrs = (C.c_void_p * m.n)(*[None if p is None else next(it) for p in planes])
-        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
-        p = dz._c()
-        self._check(self._lib.stk_drizzle_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine), float(alpha),
-                                                C.byref(p), rec, None if mptrs is None else C.cast(mptrs, C.c_void_p), C.byref(img),
-                                                dptr))
-        return (out, den) if return_den else out
+        shape = self._drizzle_shape(dz, out_shape)
+        return self._whole_stack(kind, suffix, files, params, scale_down_width, return_stats, combine + [dz._c()],
+                                 [(return_den, self._out_plane(np.float32, shape=shape))], image_shape=shape)
 
     def ecc_match_drizzle(self, files, params: EccMatchParameters, drizzle: Optional["DrizzleParameters"] = None,
                           scale_down_width: Optional[float] = None, *, out_shape=None, return_den: bool = False,
                           return_stats: bool = False):
         """ecc_match with the drizzle combine (stk_ecc_match_drizzle): aligned as ecc_match aligns, then frame 0 and every
         frame under its warp drizzled onto the output grid. Returns the image[, the weight image][, the stats]."""
-        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        dz = drizzle or DrizzleParameters()
-        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
-        stats = (_ffi.FrameStats * m.n)()
-        p, dp = params._c(), dz._c()
-        self._check(self._lib.stk_ecc_match_drizzle(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                    C.byref(dp), C.byref(img), dptr, stats))
-        res = (out,) + ((den,) if return_den else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
-        return res if len(res) > 1 else out
+        return self._match_drizzle("ecc", "_drizzle", files, params, [], drizzle, scale_down_width, out_shape, return_den, return_stats)
 
     def keypoint_match_drizzle(self, files, params: KeyPointMatchParameters, drizzle: Optional["DrizzleParameters"] = None,
                                scale_down_width: Optional[float] = None, *, out_shape=None, return_den: bool = False,
                                return_stats: bool = False):
         """keypoint_match with the drizzle combine (stk_keypoint_match_drizzle): (dropped, image[, weight image][, stats]).
         A dropped frame is no sample: it is absent from the weight image."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        dz = drizzle or DrizzleParameters()
-        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p, dp = params._c(), dz._c()
-        self._check(self._lib.stk_keypoint_match_drizzle(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                         C.byref(dp), C.byref(img), C.byref(dropped), dptr, stats))
-        return (dropped.value, out) + ((den,) if return_den else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return self._match_drizzle("keypoint", "_drizzle", files, params, [], drizzle, scale_down_width, out_shape, return_den,
+                                   return_stats)
 
     # -- mesh-displaced drizzle: drizzle through local-alignment fields (extension beyond the reference) --
     def mesh_drizzle_stack(self, files, warps, fields, step: int, drizzle: Optional["DrizzleParameters"] = None, gain=None, offset=None,
@@ -1919,97 +1640,26 @@ class Stacker:
                            return_den: bool = False):
         """drizzle_stack through displacement fields (stk_mesh_drizzle_stack). fields: n gh x gw x 2 float32 planes for the
         grid of `step` (local_align's result), single entries may be None = not displaced; frame 0's is not read."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        dz = drizzle or DrizzleParameters()
-        Md, inc = self._warps_arg(warps, include, m.n)
-        rec = None if (gain is None and offset is None and weights is None and applied is None) \
-            else self._records_arg(m, gain, offset, weights, applied)
-        mkeep, mptrs = None, None
-        if maps is not None:
-            planes = list(maps)
-            if len(planes) != m.n:
-                raise InvalidParams("one weight map (or None) per frame expected")
-            some = [p for p in planes if p is not None]
-            sub = copy.copy(m)
-            sub.n = len(some)
-            mkeep, some_ptrs = self._maps_arg(sub, some) if some else ([], [])
-            it = iter(some_ptrs)
-            mptrs = (C.c_void_p * m.n)(*[None if p is None else next(it) for p in planes])
-        fkeep, fptrs = self._fields_arg(m, fields, step, allow_none=True)
-        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
-        p = dz._c()
-        self._check(self._lib.stk_mesh_drizzle_stack(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                     None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine), float(alpha),
-                                                     C.byref(p), rec, None if mptrs is None else C.cast(mptrs, C.c_void_p),
-                                                     C.cast(fptrs, C.c_void_p), int(step), C.byref(img), dptr))
-        return (out, den) if return_den else out
+        return self._drizzle_stack(self._lib.stk_mesh_drizzle_stack, files, warps, (fields, step), drizzle, gain, offset, weights,
+                                   include, applied, maps, out_shape, is_affine, alpha, return_den)
 
     def ecc_match_local_aligned_drizzle(self, files, params: EccMatchParameters, mesh: Optional["MeshParameters"] = None,
                                         drizzle: Optional["DrizzleParameters"] = None, scale_down_width: Optional[float] = None, *,
                                         out_shape=None, return_den: bool = False, return_stats: bool = False):
         """ecc_match_drizzle with local alignment (stk_ecc_match_local_aligned_drizzle): every frame is drizzled through its
         ECC warp and the displacement field measured on top of it. Returns the image[, the weight image][, the stats]."""
-        if isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        dz = drizzle or DrizzleParameters()
-        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
-        stats = (_ffi.FrameStats * m.n)()
-        p, mp, dp = params._c(), (mesh or MeshParameters())._c(), dz._c()
-        self._check(self._lib.stk_ecc_match_local_aligned_drizzle(self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0),
-                                                                  C.byref(mp), C.byref(dp), C.byref(img), dptr, stats))
-        res = (out,) + ((den,) if return_den else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
-        return res if len(res) > 1 else out
+        return self._match_drizzle("ecc", "_local_aligned_drizzle", files, params, [(mesh or MeshParameters())._c()], drizzle,
+                                   scale_down_width, out_shape, return_den, return_stats)
 
     def keypoint_match_local_aligned_drizzle(self, files, params: KeyPointMatchParameters, mesh: Optional["MeshParameters"] = None,
                                              drizzle: Optional["DrizzleParameters"] = None, scale_down_width: Optional[float] = None, *,
                                              out_shape=None, return_den: bool = False, return_stats: bool = False):
         """keypoint_match_drizzle with local alignment (stk_keypoint_match_local_aligned_drizzle):
         (dropped, image[, weight image][, stats])."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        dz = drizzle or DrizzleParameters()
-        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p, mp, dp = params._c(), (mesh or MeshParameters())._c(), dz._c()
-        self._check(self._lib.stk_keypoint_match_local_aligned_drizzle(self._h, C.byref(m.c_frames), C.byref(p),
-                                                                       float(scale_down_width or 0.0), C.byref(mp), C.byref(dp),
-                                                                       C.byref(img), C.byref(dropped), dptr, stats))
-        return (dropped.value, out) + ((den,) if return_den else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
+        return self._match_drizzle("keypoint", "_local_aligned_drizzle", files, params, [(mesh or MeshParameters())._c()], drizzle,
+                                   scale_down_width, out_shape, return_den, return_stats)
 
     # -- blot-and-compare rejection maps for drizzle (extension beyond the reference) ---------------------
-    def _array_arg(self, m: _Marshalled, x, dtype, shape, what: str):
-        """`x` as a contiguous array of `dtype` and `shape` where the frames live: (owner, address). An array that is
-        already that is used as it is, so that a caller's buffer can be written in place."""
-        if m.location == DEVICE:
-            import torch
-            tdt = torch.float32 if dtype == np.float32 else torch.int32
-            t = x if _is_torch(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype)))
-            t = t.to(device=m.torch_device, dtype=tdt).contiguous()
-            if tuple(t.shape) != tuple(shape):
-                raise InvalidParams(f"{what}: shape {tuple(shape)} expected")
-            self._tensor_ready(t)
-            return t, t.data_ptr()
-        a = np.ascontiguousarray(np.asarray(x.cpu().numpy() if _is_torch(x) else x, dtype))
-        if a.shape != tuple(shape):
-            raise InvalidParams(f"{what}: shape {tuple(shape)} expected")
-        return a, a.ctypes.data
-
-    def _map_planes(self, m: _Marshalled):
-        """n x H x W float32 ones where the frames live."""
-        if m.location == DEVICE:
-            import torch
-            planes = torch.ones((m.n, m.h, m.w), dtype=torch.float32, device=m.torch_device)
-            self._tensor_ready(planes)            # the engine reads and writes these planes: the fill must have landed
-            return planes
-        return np.ones((m.n, m.h, m.w), np.float32)
-
     def reject_maps(self, files, warps, clean, reject: Optional["RejectParameters"] = None, counts=None, gain=None, offset=None,
                     include=None, *, applied=None, maps=None, out=None, is_affine=False, alpha=1.0 / 255.0,
                     return_counts: bool = False):
@@ -2020,77 +1670,47 @@ class Stacker:
         frames live to write into; it may be `maps` itself (in place). Returns the n x H x W maps (0 = rejected, else the
         input value or 1; an excluded frame's plane is left as it is, all ones in a fresh array), with return_counts also
         the per-frame numbers of rejected and of judged pixels (int64)."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        m, head = self._warped(files, warps, include, is_affine, None, alpha)
         rp = (reject or RejectParameters())._c()
-        Md, inc = self._warps_arg(warps, include, m.n)
-        rec = None if (gain is None and offset is None and applied is None) else self._records_arg(m, gain, offset, None, applied)
+        rec = self._records_arg(m, gain, offset, None, applied, optional=True)
         ckeep, cptr = self._array_arg(m, clean, np.float32, (m.h, m.w, m.c), "clean image")
         nkeep, nptr = (None, None) if counts is None else self._array_arg(m, counts, np.int32, (m.h, m.w), "counts")
         plane = m.h * m.w * 4
-        res = self._map_planes(m) if out is None else out
+        res = self._alloc(m, (m.n, m.h, m.w), np.float32, 1)[0] if out is None else out     # fresh planes: all ones
         okeep, optr = self._array_arg(m, res, np.float32, (m.n, m.h, m.w), "out")
         if out is not None and okeep is not out:
             raise InvalidParams("out: a contiguous n x H x W float32 array where the frames live expected")
         optrs = (C.c_void_p * m.n)(*[optr + i * plane for i in range(m.n)])
-        ikeep, iptrs = [], None
-        if maps is not None:
-            if maps is out or not isinstance(maps, (list, tuple)):
-                k, base = self._array_arg(m, maps, np.float32, (m.n, m.h, m.w), "maps")
-                ikeep.append(k)
-                addr = [base + i * plane for i in range(m.n)]
-            else:
-                if len(maps) != m.n:
-                    raise InvalidParams("one input map (or None) per frame expected")
-                addr = []
-                for p in maps:
-                    if p is None:
-                        addr.append(None)
-                        continue
-                    k, a = self._array_arg(m, p, np.float32, (m.h, m.w), "maps")
-                    ikeep.append(k)
-                    addr.append(a)
-            iptrs = (C.c_void_p * m.n)(*addr)
+        ikeep, iptrs = None, None
+        if maps is not None and (maps is out or not isinstance(maps, (list, tuple))):
+            ikeep, base = self._array_arg(m, maps, np.float32, (m.n, m.h, m.w), "maps")
+            iptrs = (C.c_void_p * m.n)(*[base + i * plane for i in range(m.n)])
+        elif maps is not None:
+            ikeep, iptrs = self._planes_arg(m, maps, (m.h, m.w), "one input map (or None) per frame expected",
+                                            f"maps: shape {(m.h, m.w)} expected", allow_none=True)
         rej = np.zeros(m.n, np.int64)
         jud = np.zeros(m.n, np.int64)
-        self._check(self._lib.stk_reject_maps(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                              None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine), float(alpha), rec,
-                                              C.c_void_p(cptr), None if nptr is None else C.c_void_p(nptr), C.byref(rp),
+        self._check(self._lib.stk_reject_maps(*head, rec, C.c_void_p(cptr), None if nptr is None else C.c_void_p(nptr), C.byref(rp),
                                               None if iptrs is None else C.cast(iptrs, C.c_void_p), C.cast(optrs, C.c_void_p),
                                               C.c_void_p(rej.ctypes.data), C.c_void_p(jud.ctypes.data)))
         return (res, rej, jud) if return_counts else res
 
     def _drizzle_rejected(self, kind, files, params, drizzle, reject, weight, weights, scale_down_width, out_shape, return_den,
                           return_maps, return_rejected, return_applied, return_stats):
-        if kind == "ecc" and isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
         dz = drizzle or DrizzleParameters()
-        out, img, den, dptr = self._drizzle_images(m, dz, out_shape, return_den)
-        maps, mptrs = None, None
-        if return_maps:
-            maps = self._map_planes(m)
-            base = maps.data_ptr() if m.location == DEVICE else maps.ctypes.data
-            mptrs = C.cast((C.c_void_p * m.n)(*[base + i * m.h * m.w * 4 for i in range(m.n)]), C.c_void_p)
-        rej = np.zeros(m.n, np.int64)
-        wkeep, wptr = self._weights_arg(weights, m.n)
-        applied = (_ffi.FrameWeight * m.n)()
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p, dp, wp, rp = params._c(), dz._c(), (weight or WeightParameters())._c(), (reject or RejectParameters())._c()
-        fn = getattr(self._lib, f"stk_{kind}_match_drizzle_rejected")
-        args = [self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(dp), C.byref(wp), wptr, C.byref(rp),
-                C.byref(img)]
-        if kind == "keypoint":
-            args.append(C.byref(dropped))
-        self._check(fn(*args, dptr, mptrs, C.c_void_p(rej.ctypes.data), applied, stats))
-        res = ((dropped.value,) if kind == "keypoint" else ()) + (out,) + ((den,) if return_den else ()) \
-            + ((maps,) if return_maps else ()) + ((rej,) if return_rejected else ()) \
-            + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
-        return res if len(res) > 1 else out
+        shape = self._drizzle_shape(dz, out_shape)
+
+        def maps(m, wanted):                          # the planes the drizzle used: all ones where nothing was rejected
+            a, ptrs = self._plane_table(m, (m.h, m.w), np.float32, 1) if wanted else (None, None)
+            return ptrs, lambda stl: a
+
+        def rejected(m, wanted):                      # always passed
+            rej = np.zeros(m.n, np.int64)
+            return C.c_void_p(rej.ctypes.data), lambda stl: rej
+        combine = [dz._c(), (weight or WeightParameters())._c(), self._weights_combine(weights), (reject or RejectParameters())._c()]
+        return self._whole_stack(kind, "_drizzle_rejected", files, params, scale_down_width, return_stats, combine,
+                                 [(return_den, self._out_plane(np.float32, shape=shape)), (return_maps, maps),
+                                  (return_rejected, rejected), (return_applied, self._out_applied)], image_shape=shape)
 
     def ecc_match_drizzle_rejected(self, files, params: EccMatchParameters, drizzle: Optional["DrizzleParameters"] = None,
                                    reject: Optional["RejectParameters"] = None, weight: Optional["WeightParameters"] = None,
@@ -2116,27 +1736,12 @@ class Stacker:
                                       return_den, return_maps, return_rejected, return_applied, return_stats)
 
     # -- normalised, coverage-aware rejection combines (extension beyond the reference) -----------------
-    def _pixel_counts_image(self, m: _Marshalled):
-        """int32 HxW per-pixel counts placed where the output lives."""
-        if m.location == DEVICE:
-            import torch
-            cnt = torch.empty((m.h, m.w), dtype=torch.int32, device=m.torch_device)
-            return cnt, C.c_void_p(cnt.data_ptr())
-        cnt = np.empty((m.h, m.w), np.int32)
-        return cnt, C.c_void_p(cnt.ctypes.data)
-
-    def _kept_image(self, m: _Marshalled):
-        """f32 HxWxC kept-weight planes placed where the output lives."""
-        if m.location == DEVICE:
-            import torch
-            kw = torch.empty((m.h, m.w, m.c), dtype=torch.float32, device=m.torch_device)
-            return kw, C.c_void_p(kw.data_ptr())
-        kw = np.empty((m.h, m.w, m.c), np.float32)
-        return kw, C.c_void_p(kw.ctypes.data)
-
     @staticmethod
-    def _records_arg(m: _Marshalled, gain, offset, weights, applied):
-        """n stk_frame_weight records from gain / offset (n x channels), weights (n) or another call's `applied`."""
+    def _records_arg(m: _Marshalled, gain, offset, weights, applied, optional: bool = False):
+        """n stk_frame_weight records from gain / offset (n x channels), weights (n) or another call's `applied`.
+        optional: None = NULL when nothing was given (the engine's defaults); else the records are always built."""
+        if optional and gain is None and offset is None and weights is None and applied is None:
+            return None
         rec = (_ffi.FrameWeight * m.n)()
         if applied is not None:
             if len(applied) != m.n:
@@ -2163,9 +1768,9 @@ class Stacker:
         """The normalised, coverage-aware clip alone over caller-held warps (stk_clip_stack_weighted): clip_stack with
         weighted_stack's gain / offset / weights (or `applied`) and coverage. Returns the image, then the counts of kept
         samples (return_counts) and the kept weight (return_kept_weight), both per pixel and channel."""
-        return self._clip_stack_weighted(self._lib.stk_clip_stack_weighted, (clip or SigmaClipParameters())._c(), files, warps, gain,
-                                         offset, weights, include, applied, coverage, is_affine, border_mode, border_value, alpha,
-                                         return_counts, return_kept_weight)
+        return self._stack_weighted(self._lib.stk_clip_stack_weighted, (clip or SigmaClipParameters())._c(), files, warps, gain,
+                                    offset, weights, include, applied, coverage, is_affine, border_mode, border_value, alpha,
+                                    [(return_counts, np.int32, True), (return_kept_weight, np.float32, True)])
 
     def robust_clip_stack_weighted(self, files, warps, clip: Optional["RobustClipParameters"] = None, gain=None, offset=None,
                                    weights=None, include=None, *, applied=None, coverage: bool = True, is_affine=False,
@@ -2173,25 +1778,20 @@ class Stacker:
                                    return_counts: bool = False, return_kept_weight: bool = False):
         """The median / MAD clip with participation over caller-held warps (stk_robust_clip_stack_weighted), with the
         arguments and results of clip_stack_weighted."""
-        return self._clip_stack_weighted(self._lib.stk_robust_clip_stack_weighted, (clip or RobustClipParameters())._c(), files, warps,
-                                         gain, offset, weights, include, applied, coverage, is_affine, border_mode, border_value,
-                                         alpha, return_counts, return_kept_weight)
+        return self._stack_weighted(self._lib.stk_robust_clip_stack_weighted, (clip or RobustClipParameters())._c(), files, warps,
+                                    gain, offset, weights, include, applied, coverage, is_affine, border_mode, border_value, alpha,
+                                    [(return_counts, np.int32, True), (return_kept_weight, np.float32, True)])
 
-    def _clip_stack_weighted(self, fn, cp, files, warps, gain, offset, weights, include, applied, coverage, is_affine, border_mode,
-                             border_value, alpha, return_counts, return_kept_weight):
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Md, inc = self._warps_arg(warps, include, m.n)
+    def _stack_weighted(self, fn, cp, files, warps, gain, offset, weights, include, applied, coverage, is_affine, border_mode,
+                        border_value, alpha, outputs):
+        """The clip and quantile stacks with records: [head, combine parameters, records, coverage, image, *outputs];
+        outputs: [(wanted, dtype, per_channel)]. The records are always built."""
+        m, head = self._warped(files, warps, include, is_affine, (border_mode, border_value), alpha)
         rec = self._records_arg(m, gain, offset, weights, applied)
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
-        out, img = self._out_image(m)
-        cnt, cptr = self._counts_image(m) if return_counts else (None, None)
-        kw, kptr = self._kept_image(m) if return_kept_weight else (None, None)
-        self._check(fn(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), None if inc is None else C.c_void_p(inc.ctypes.data),
-                       int(is_affine), int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(cp), rec, int(coverage),
-                       C.byref(img), cptr, kptr))
-        res = (out,) + ((cnt,) if return_counts else ()) + ((kw,) if return_kept_weight else ())
+        out, img = self._image(m)
+        outs = [self._optional(m, *o) for o in outputs]
+        self._check(fn(*head, C.byref(cp), rec, int(coverage), C.byref(img), *[ptr for _, ptr in outs]))
+        res = (out,) + tuple(a for a, _ in outs if a is not None)
         return res if len(res) > 1 else out
 
     def quantile_stack_weighted(self, files, warps, quantile=None, gain=None, offset=None, weights=None, include=None, *,
@@ -2199,53 +1799,17 @@ class Stacker:
                                 border_value=(0, 0, 0, 0), alpha=1.0 / 255.0, return_counts: bool = False):
         """The normalised, coverage-aware quantile alone over caller-held warps (stk_quantile_stack_weighted). Returns the
         image, then the per-pixel number of participating frames (return_counts, HxW)."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        Md, inc = self._warps_arg(warps, include, m.n)
-        rec = self._records_arg(m, gain, offset, weights, applied)
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
-        out, img = self._out_image(m)
-        cnt, cptr = self._pixel_counts_image(m) if return_counts else (None, None)
-        qp = _quantile_c(quantile)
-        self._check(self._lib.stk_quantile_stack_weighted(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data),
-                                                          None if inc is None else C.c_void_p(inc.ctypes.data), int(is_affine),
-                                                          int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha), C.byref(qp), rec,
-                                                          int(coverage), C.byref(img), cptr))
-        return (out, cnt) if return_counts else out
+        return self._stack_weighted(self._lib.stk_quantile_stack_weighted, _quantile_c(quantile), files, warps, gain, offset, weights,
+                                    include, applied, coverage, is_affine, border_mode, border_value, alpha, [(return_counts, np.int32)])
 
-    def _robust_match(self, kind, combine, files, params, cparams, weight, weights, scale_down_width, return_stats, return_counts,
-                      return_kept_weight, return_applied):
-        if kind == "ecc" and isinstance(files, (list, tuple)) and len({tuple(f.shape[:2]) for f in files}) > 1:
-            raise OpenCvError("the frames differ in size: the reference fails on such a stack in cv::add (lib.rs:809)")
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
-        if combine in ("clipped", "robust_clipped"):
-            cnt, cptr = self._counts_image(m) if return_counts else (None, None)
-            cp = (cparams or (SigmaClipParameters() if combine == "clipped" else RobustClipParameters()))._c()
-        else:
-            cnt, cptr = self._pixel_counts_image(m) if return_counts else (None, None)
-            cp = _quantile_c(cparams)
-        kw, kptr = self._kept_image(m) if return_kept_weight else (None, None)
-        wkeep, wptr = self._weights_arg(weights, m.n)
-        applied = (_ffi.FrameWeight * m.n)()
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        p, wp = params._c(), (weight or WeightParameters())._c()
-        fn = getattr(self._lib, f"stk_{kind}_match_{combine}_weighted")
-        args = [self._h, C.byref(m.c_frames), C.byref(p), float(scale_down_width or 0.0), C.byref(cp), C.byref(wp), wptr, C.byref(img)]
-        if kind == "keypoint":
-            args.append(C.byref(dropped))
-        args.append(cptr)
-        if combine in ("clipped", "robust_clipped"):
-            args.append(kptr)
-        self._check(fn(*args, applied, stats))
-        res = ((dropped.value,) if kind == "keypoint" else ()) + (out,) + ((cnt,) if return_counts else ()) \
-            + ((kw,) if return_kept_weight else ()) + ((self._applied_list(applied, m.n, m.c),) if return_applied else ()) \
-            + ((self._stats_list(stats, m.n),) if return_stats else ())
-        return res if len(res) > 1 else out
+    def _robust_match(self, kind, suffix, cp, per_channel, files, params, weight, weights, scale_down_width, return_stats,
+                      return_counts, return_kept_weight, return_applied):
+        """The clip and quantile forms with records: [.., combine parameters, weight, weights, image, .., counts,
+        (kept weight: the clips only), applied, stats]; the clips count per pixel and channel, the quantile per pixel."""
+        kept = [(return_kept_weight, self._out_plane(np.float32, True))] if per_channel else []
+        return self._whole_stack(kind, suffix, files, params, scale_down_width, return_stats,
+                                 [cp, (weight or WeightParameters())._c(), self._weights_combine(weights)],
+                                 [(return_counts, self._out_plane(np.int32, per_channel))] + kept + [(return_applied, self._out_applied)])
 
     def ecc_match_clipped_weighted(self, files, params: EccMatchParameters, clip: Optional["SigmaClipParameters"] = None,
                                    weight: Optional["WeightParameters"] = None, weights=None, scale_down_width: Optional[float] = None,
@@ -2254,8 +1818,8 @@ class Stacker:
         """ecc_match with the normalised, coverage-aware sigma clip (stk_ecc_match_clipped_weighted): the image, then the
         counts (return_counts), the kept weight (return_kept_weight), the per-frame records used (return_applied) and the
         stats (return_stats)."""
-        return self._robust_match("ecc", "clipped", files, params, clip, weight, weights, scale_down_width, return_stats,
-                                  return_counts, return_kept_weight, return_applied)
+        return self._robust_match("ecc", "_clipped_weighted", (clip or SigmaClipParameters())._c(), True, files, params, weight, weights,
+                                  scale_down_width, return_stats, return_counts, return_kept_weight, return_applied)
 
     def keypoint_match_clipped_weighted(self, files, params: KeyPointMatchParameters, clip: Optional["SigmaClipParameters"] = None,
                                         weight: Optional["WeightParameters"] = None, weights=None,
@@ -2263,8 +1827,8 @@ class Stacker:
                                         return_counts: bool = False, return_kept_weight: bool = False, return_applied: bool = False):
         """keypoint_match with the normalised, coverage-aware sigma clip (stk_keypoint_match_clipped_weighted):
         (dropped, image[, counts][, kept weight][, applied][, stats])."""
-        return self._robust_match("keypoint", "clipped", files, params, clip, weight, weights, scale_down_width, return_stats,
-                                  return_counts, return_kept_weight, return_applied)
+        return self._robust_match("keypoint", "_clipped_weighted", (clip or SigmaClipParameters())._c(), True, files, params, weight,
+                                  weights, scale_down_width, return_stats, return_counts, return_kept_weight, return_applied)
 
     def ecc_match_robust_clipped_weighted(self, files, params: EccMatchParameters, clip: Optional["RobustClipParameters"] = None,
                                           weight: Optional["WeightParameters"] = None, weights=None,
@@ -2272,8 +1836,8 @@ class Stacker:
                                           return_counts: bool = False, return_kept_weight: bool = False, return_applied: bool = False):
         """ecc_match with the median / MAD clip with participation (stk_ecc_match_robust_clipped_weighted); results as
         ecc_match_clipped_weighted."""
-        return self._robust_match("ecc", "robust_clipped", files, params, clip, weight, weights, scale_down_width, return_stats,
-                                  return_counts, return_kept_weight, return_applied)
+        return self._robust_match("ecc", "_robust_clipped_weighted", (clip or RobustClipParameters())._c(), True, files, params, weight,
+                                  weights, scale_down_width, return_stats, return_counts, return_kept_weight, return_applied)
 
     def keypoint_match_robust_clipped_weighted(self, files, params: KeyPointMatchParameters,
                                                clip: Optional["RobustClipParameters"] = None,
@@ -2283,16 +1847,16 @@ class Stacker:
                                                return_applied: bool = False):
         """keypoint_match with the median / MAD clip with participation (stk_keypoint_match_robust_clipped_weighted); results
         as keypoint_match_clipped_weighted."""
-        return self._robust_match("keypoint", "robust_clipped", files, params, clip, weight, weights, scale_down_width,
-                                  return_stats, return_counts, return_kept_weight, return_applied)
+        return self._robust_match("keypoint", "_robust_clipped_weighted", (clip or RobustClipParameters())._c(), True, files, params,
+                                  weight, weights, scale_down_width, return_stats, return_counts, return_kept_weight, return_applied)
 
     def ecc_match_quantile_weighted(self, files, params: EccMatchParameters, quantile=None,
                                     weight: Optional["WeightParameters"] = None, weights=None, scale_down_width: Optional[float] = None,
                                     return_stats: bool = False, return_counts: bool = False, return_applied: bool = False):
         """ecc_match with the normalised, coverage-aware quantile (stk_ecc_match_quantile_weighted): the image, then the
         per-pixel number of participating frames (return_counts), the records (return_applied) and the stats."""
-        return self._robust_match("ecc", "quantile", files, params, quantile, weight, weights, scale_down_width, return_stats,
-                                  return_counts, False, return_applied)
+        return self._robust_match("ecc", "_quantile_weighted", _quantile_c(quantile), False, files, params, weight, weights,
+                                  scale_down_width, return_stats, return_counts, False, return_applied)
 
     def keypoint_match_quantile_weighted(self, files, params: KeyPointMatchParameters, quantile=None,
                                          weight: Optional["WeightParameters"] = None, weights=None,
@@ -2300,16 +1864,14 @@ class Stacker:
                                          return_counts: bool = False, return_applied: bool = False):
         """keypoint_match with the normalised, coverage-aware quantile (stk_keypoint_match_quantile_weighted):
         (dropped, image[, counts][, applied][, stats])."""
-        return self._robust_match("keypoint", "quantile", files, params, quantile, weight, weights, scale_down_width, return_stats,
-                                  return_counts, False, return_applied)
+        return self._robust_match("keypoint", "_quantile_weighted", _quantile_c(quantile), False, files, params, weight, weights,
+                                  scale_down_width, return_stats, return_counts, False, return_applied)
 
     # -- shard-level (one process per GPU; frames[0] = reference frame) ------------------------------
     def ecc_match_shard(self, files, params: EccMatchParameters, add_reference: bool, sum_out,
                         scale_down_width: Optional[float] = None, return_stats: bool = True):
         """Un-normalised f32 sum of this rank's aligned frames into `sum_out` (cuda tensor HxWx3)."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        m = self._stack(files)
         self._tensor_ready(sum_out)
         img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, _image_stride_bytes(sum_out))
         added = C.c_int32(0)
@@ -2322,9 +1884,7 @@ class Stacker:
 
     def keypoint_match_shard(self, files, params: KeyPointMatchParameters, add_reference: bool, sum_out,
                              scale_down_width: Optional[float] = None, return_stats: bool = True):
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        m = self._stack(files)
         self._tensor_ready(sum_out)
         img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, _image_stride_bytes(sum_out))
         added, dropped = C.c_int32(0), C.c_int32(0)
@@ -2351,35 +1911,21 @@ class Stacker:
     # -- stage-level (parity tests) ------------------------------------------------------------------
     def grey(self, frame):
         m = self._marshal([frame])
-        if m.location == DEVICE:
-            import torch
-            out = torch.empty((m.h, m.w), dtype=m.keep[0].dtype, device=m.torch_device)
-            ptr = out.data_ptr()
-        else:
-            out = np.empty((m.h, m.w), m.keep[0].dtype)
-            ptr = out.ctypes.data
+        out, ptr = self._alloc(m, (m.h, m.w), {8: np.uint8, 16: np.uint16, 32: np.float32}[m.depth])
         self._check(self._lib.stk_grey(self._h, C.byref(m.c_frames), C.c_void_p(ptr)))
         return out
 
     def convert_f32(self, frame, alpha: float = 1.0 / 255.0):
         m = self._marshal([frame])
-        if m.location == DEVICE:
-            import torch
-            out = torch.empty(tuple(m.keep[0].shape), dtype=torch.float32, device=m.torch_device)
-            ptr = out.data_ptr()
-        else:
-            out = np.empty(m.keep[0].shape, np.float32)
-            ptr = out.ctypes.data
+        out, ptr = self._alloc(m, tuple(m.keep[0].shape), np.float32)
         self._check(self._lib.stk_convert_f32(self._h, C.byref(m.c_frames), float(alpha), C.c_void_p(ptr)))
         return out
 
     # -- BASELINE configs[4] (extension): ORB-seeded ECC on 8- or 16-bit stacks --------------------------------
     def hybrid_match(self, files, kp_params: KeyPointMatchParameters, ecc_params: EccMatchParameters, return_stats=False):
         """ORB + RANSAC homography as the initial warp of findTransformECC; 16-bit frames folded with alpha 1/65535."""
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
-        out, img = self._out_image(m)
+        m = self._stack(files)
+        out, img = self._image(m)
         stats = (_ffi.FrameStats * m.n)()
         kp, ep = kp_params._c(), ecc_params._c()
         self._check(self._lib.stk_hybrid_match(self._h, C.byref(m.c_frames), C.byref(kp), C.byref(ep), C.byref(img), stats))
@@ -2387,9 +1933,7 @@ class Stacker:
 
     def hybrid_match_shard(self, files, kp_params: KeyPointMatchParameters, ecc_params: EccMatchParameters,
                            add_reference: bool, sum_out, return_stats: bool = True):
-        m = self._marshal(files)
-        if m.n == 0:
-            raise NotEnoughFiles("Not enough files")
+        m = self._stack(files)
         self._tensor_ready(sum_out)
         img = _ffi.ImageF32(sum_out.data_ptr(), m.w, m.h, 3, DEVICE, _image_stride_bytes(sum_out))
         added = C.c_int32(0)
@@ -2490,13 +2034,7 @@ class Stacker:
     def grey_blur_f32(self, frame, ksize: int):
         """cvt_color(BGR2GRAY) + findTransformECC's GaussianBlur of one frame, fused (the per-frame ECC preparation)."""
         m = self._marshal([frame])
-        if m.location == DEVICE:
-            import torch
-            out = torch.empty((m.h, m.w), dtype=torch.float32, device=m.torch_device)
-            ptr = out.data_ptr()
-        else:
-            out = np.empty((m.h, m.w), np.float32)
-            ptr = out.ctypes.data
+        out, ptr = self._alloc(m, (m.h, m.w), np.float32)
         self._check(self._lib.stk_grey_blur_f32(self._h, C.byref(m.c_frames), int(ksize), C.c_void_p(ptr)))
         return out
 
@@ -2552,7 +2090,7 @@ class Stacker:
         Md = np.ascontiguousarray(np.asarray(M, np.float64).reshape(-1))
         if Md.size == 6:
             Md = np.concatenate([Md, [0.0, 0.0, 1.0]])
-        bv = np.asarray((list(border_value) + [0.0] * 4)[:4], np.float64)
+        bv = self._border_arg(border_value)
         accumulate = acc is not None
         if accumulate:
             out = acc
@@ -2563,7 +2101,7 @@ class Stacker:
             else:
                 img = _ffi.ImageF32(out.ctypes.data, m.w, m.h, m.c, HOST, _image_stride_bytes(out))
         else:
-            out, img = self._out_image(m)
+            out, img = self._image(m)
         st = self._lib.stk_warp_accumulate(self._h, C.byref(m.c_frames), C.c_void_p(Md.ctypes.data), int(is_affine),
                                            int(border_mode), C.c_void_p(bv.ctypes.data), float(alpha),
                                            int(accumulate), C.byref(img))
