@@ -211,7 +211,10 @@ stk_status  stk_get_timing(const stk_ctx* ctx, stk_timing* out);
  *   "robust_select_us"      median / MAD clip (stk_robust_clip_stack and the *_robust_clipped calls): device time of the
  *                           last such call's selection launches in microseconds, part of its stk_timing.finalize_ms.
  *   "prep_stream_frames"    test hook: ECC templates of the last call that the streaming grey + blur kernel wrote (one launch
- *                           per run of frames, option "prep_stream"); the others took the per-frame kernels. */
+ *                           per run of frames, option "prep_stream"); the others took the per-frame kernels.
+ *   "workspaces_empty"      test hook: how many of the grow-only device workspaces of this context, of its hidden keypoint
+ *                           lane contexts and of its multi-device state have never been reserved (capacity 0).
+ *   "debug_poison_bytes"    test hook: the bytes the last "debug_poison" (stk_set_option) filled; 0 before the first. */
 stk_status  stk_get_counter(const stk_ctx* ctx, const char* name, int64_t* out);
 /* Pinned (page-locked) host memory for frames: stacks handed over in such buffers cross PCIe by DMA at link rate and
  * overlap with the alignment of the frames that have already arrived (a decoder — the Rust shim's imread — writes into
@@ -276,7 +279,16 @@ void        stk_host_free(void* p);
  *                        n > 0: at most n. Same bits either way
  *   "calibrate_chunk"    stk_calibrate: frames a workgroup runs through with its tile of the masters in registers. 0
  *                        (default): 16; 1 .. 4096 as given (1: the masters are read once per frame, for measuring what
- *                        holding them buys). Same bits either way */
+ *                        holding them buys). Same bits either way
+ *   "debug_poison"       debug, acts at once and is not remembered: value b, 0 .. 255 (anything else: STK_INVALID_PARAMS,
+ *                        nothing touched). Every stream of the context is drained; every grow-only device workspace (over
+ *                        its whole capacity) and every page-locked host block the context owns is filled with the byte b;
+ *                        the streams are drained again; the same happens to every hidden keypoint lane context, to every
+ *                        member of a multi-device context and to its accumulators. What the context remembers about the
+ *                        CONTENT of a workspace (the ECC reference planes' zero border, the ORB resize tables) is forgotten;
+ *                        memory of the caller's is never written. The contract it tests: the outputs and per-frame
+ *                        statistics of a call are a function of the call's arguments and the context's options only, never
+ *                        of what the context did before. Changes no result (stk_get_counter "debug_poison_bytes") */
 stk_status  stk_set_option(stk_ctx* ctx, const char* name, int64_t value);
 const char* stk_version(void);
 

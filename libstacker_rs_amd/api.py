@@ -641,7 +641,8 @@ class Stacker:
         t = _ffi.Timing()
         self._check(self._lib.stk_get_timing(self._h, C.byref(t)))
         d = {k: getattr(t, k) for k, _ in _ffi.Timing._fields_}
-        for name in ("ecc_first_iter_slots", "robust_select_us", "prep_stream_frames"):   # counters outside stk_timing (stk_get_counter)
+        for name in ("ecc_first_iter_slots", "robust_select_us", "prep_stream_frames",
+                     "workspaces_empty", "debug_poison_bytes"):   # counters outside stk_timing (stk_get_counter)
             v = C.c_int64(0)
             self._check(self._lib.stk_get_counter(self._h, name.encode(), C.byref(v)))
             d[name] = v.value

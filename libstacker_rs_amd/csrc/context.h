@@ -1,6 +1,7 @@
 // context.h — the engine's per-GPU context (stk_ctx) and host helpers shared by stacker.cpp, keypoint.cpp and the combines
 // (whose common front end is combine.h and whose common back end is workspace.h).
 #pragma once
+#include <cstdlib>
 #include <functional>
 #include <mutex>
 #include <string>
@@ -117,7 +118,39 @@ struct stk_ctx {
 
     stk::MultiState* multi = nullptr;      // non-null: this context spans several devices (multi.cpp); it is member 0 itself   // persistent host threads of the keypoint path (keypoint.cpp)
     std::mutex err_mutex;
+    int64_t debug_poison_bytes = 0;        // stk_get_counter: the bytes the last debug_poison filled (this context, its lanes, its multi state)
 };
+
+// ---------------------------------------------------------------------------------------------
+// The persistent memory of a context, enumerated in ONE place per struct: what stk_destroy (and its siblings) release and
+// what the debug_poison option fills is the same list by construction (tests/test_cpu_history.py checks the members
+// against it). `dev` sees every DevBuf; `host` every page-locked host block as (pointer, bytes, pinned), a null pointer
+// included — files_block alone may be pageable (imread.cpp falls back to malloc), which is what `pinned` says.
+using DevBufVisitor = std::function<void(DevBuf&)>;
+using HostBlockVisitor = std::function<void(void* p, size_t bytes, bool pinned)>;
+inline void for_each_workspace(stk_ctx* ctx, const DevBufVisitor& dev, const HostBlockVisitor& host = nullptr) {
+    for (DevBuf* b : {&ctx->frames, &ctx->ref, &ctx->blur_tmp, &ctx->templates, &ctx->slots, &ctx->queue, &ctx->results, &ctx->partials,
+                      &ctx->first_sums, &ctx->warpframes, &ctx->acc, &ctx->scratch, &ctx->init_warps, &ctx->frameptrs, &ctx->clip,
+                      &ctx->weighted, &ctx->coef, &ctx->quantile, &ctx->local, &ctx->mesh, &ctx->reject, &ctx->quality})
+        if (dev) dev(*b);
+    if (!host) return;
+    host(ctx->host_done, 16 * sizeof(int), true);
+    host(ctx->files_block, ctx->files_block_cap, ctx->files_block_pinned);
+}
+namespace stk {
+void for_each_workspace(KeypointWorkspace* k, const DevBufVisitor& dev, const HostBlockVisitor& host = nullptr);    // keypoint.cpp
+// the caches of workspace CONTENT (the ORB resize tables' geometry key) forgotten: the next call computes them again
+void keypoint_workspace_forget(KeypointWorkspace* k);
+namespace geom { void for_each_workspace(HgWorkspace* w, const DevBufVisitor& dev, const HostBlockVisitor& host = nullptr); }   // homography.cpp
+// (no host blocks; on_device: each member's device is made current for its buffers, the caller restores its own)
+void for_each_workspace(MultiState* ms, const DevBufVisitor& dev, bool on_device = true);                         // multi.cpp
+}  // namespace stk
+// what every destroy does with the two kinds
+inline void workspace_release_dev(DevBuf& b) { b.release(); }
+inline void workspace_release_host(void* p, size_t, bool pinned) { if (!p) return; if (pinned) (void)hipHostFree(p); else std::free(p); }
+// option debug_poison on a multi-device context's owner: its multi state's buffers, every one on its member's device
+stk_status multi_poison(stk_ctx* ctx, int byte, int64_t* bytes);
+int multi_workspaces_empty(const stk_ctx* ctx);
 
 inline stk_status fail(stk_ctx* ctx, stk_status st, const std::string& msg) {
     if (!ctx) return st;

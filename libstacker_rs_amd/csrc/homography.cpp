@@ -28,10 +28,15 @@ struct HgWorkspace {
 };
 
 HgWorkspace* hg_workspace_create() { return new HgWorkspace(); }
+void for_each_workspace(HgWorkspace* w, const DevBufVisitor& dev, const HostBlockVisitor& host) {
+    if (!w) return;
+    for (DevBuf* b : {&w->pts, &w->frames, &w->samples, &w->scores, &w->err, &w->jobs, &w->results, &w->masks})
+        if (dev) dev(*b);
+    if (host) host(w->pinned, w->pinned_cap, true);
+}
 void hg_workspace_destroy(HgWorkspace* w) {
     if (!w) return;
-    for (DevBuf* b : {&w->pts, &w->frames, &w->samples, &w->scores, &w->err, &w->jobs, &w->results, &w->masks}) b->release();
-    if (w->pinned) (void)hipHostFree(w->pinned);
+    for_each_workspace(w, workspace_release_dev, workspace_release_host);
     delete w;
 }
 

@@ -36,6 +36,11 @@ using namespace stk;
             return fail((c), STK_HIP_ERROR, std::string(#expr) + ": " + hipGetErrorString(e_));    \
     } while (0)
 
+namespace {
+constexpr size_t MAX_KP = 4096;   // descriptor rows per frame (500 + ties)
+constexpr int ORB_PACK = 512;     // short-list entries per level fetched in the one strided copy (2 n_l + ties fit; else a 2nd copy)
+}  // namespace
+
 namespace stk {
 
 struct KeypointWorkspace {
@@ -54,16 +59,24 @@ struct KeypointWorkspace {
 };
 
 KeypointWorkspace* keypoint_workspace_create() { return new KeypointWorkspace(); }
-void keypoint_workspace_destroy(KeypointWorkspace* k) {
+// every DevBuf and every pinned host block of the workspace (context.h: the one list behind destroy and debug_poison)
+void for_each_workspace(KeypointWorkspace* k, const DevBufVisitor& dev, const HostBlockVisitor& host) {
     if (!k) return;
     for (DevBuf* b : {&k->pyr, &k->score, &k->blur, &k->tmpf, &k->cand, &k->sel, &k->states, &k->final_kps, &k->desc0, &k->desc, &k->knn, &k->gfull, &k->counts, &k->rtab, &k->kept, &k->kept_cnt})
-        b->release();
-    if (k->host_sel) (void)hipHostFree(k->host_sel);
-    if (k->host_states) (void)hipHostFree(k->host_states);
-    if (k->host_kept) (void)hipHostFree(k->host_kept);
-    if (k->host_kept_cnt) (void)hipHostFree(k->host_kept_cnt);
-    if (k->host_knn) (void)hipHostFree(k->host_knn);
-    if (k->host_final) (void)hipHostFree(k->host_final);
+        if (dev) dev(*b);
+    if (!host) return;
+    const size_t F = k->host_frames_cap;
+    host(k->host_sel, sizeof(OrbSelected) * ORB_PACK * ORB_LEVELS * F, true);
+    host(k->host_states, sizeof(OrbLevelState) * ORB_LEVELS * F, true);
+    host(k->host_kept, sizeof(OrbKept) * ORB_KEEP_PACK * ORB_LEVELS * F, true);
+    host(k->host_kept_cnt, sizeof(int) * ORB_LEVELS * F, true);
+    host(k->host_knn, sizeof(int) * k->host_knn_cap, true);
+    host(k->host_final, sizeof(OrbFinalKeypoint) * k->host_final_cap, true);
+}
+void keypoint_workspace_forget(KeypointWorkspace* k) { if (k) k->rtab_w = k->rtab_h = 0; }
+void keypoint_workspace_destroy(KeypointWorkspace* k) {
+    if (!k) return;
+    for_each_workspace(k, workspace_release_dev, workspace_release_host);
     delete k;
 }
 
@@ -130,9 +143,6 @@ void orb_geometry(int w, int h, OrbGeometry& g) {
     for (int i = 0; i < 7; i++) { const double x = i - 3; kd[i] = std::exp(-0.5 * x * x / 4.0); ks += kd[i]; }
     for (int i = 0; i < 7; i++) g.g7.k[i] = (float)(kd[i] * (1.0 / ks));
 }
-
-constexpr size_t MAX_KP = 4096;   // descriptor rows per frame (500 + ties)
-constexpr int ORB_PACK = 512;     // short-list entries per level fetched in the one strided copy (2 n_l + ties fit; else a 2nd copy)
 
 }  // namespace
 

@@ -80,17 +80,43 @@ static stk_status load_rccl(stk_ctx* ctx, RcclApi& a) {
         if (r_ != ncclSuccess) return fail(ctx, STK_HIP_ERROR, std::string(#expr) + ": " + ms->api.GetErrorString(r_)); \
     } while (0)
 
+// every DevBuf of the multi state, each with its member's device current unless on_device = false (context.h: the one list
+// behind destroy and debug_poison)
+void stk::for_each_workspace(MultiState* ms, const DevBufVisitor& dev, bool on_device) {
+    if (!ms || !dev) return;
+    for (size_t i = 0; i < ms->sums.size(); i++) {
+        if (on_device && i < ms->devices.size()) (void)hipSetDevice(ms->devices[i]);
+        for (std::vector<DevBuf>* v : {&ms->sums, &ms->counts, &ms->stage}) dev((*v)[i]);
+    }
+}
+
+stk_status multi_poison(stk_ctx* ctx, int byte, int64_t* bytes) {
+    MultiState* ms = ctx->multi;
+    if (!ms) return STK_OK;
+    hipError_t e = hipSuccess;
+    for_each_workspace(ms, [&](DevBuf& b) {
+        if (!b.p || e != hipSuccess) return;
+        if ((e = hipMemset(b.p, byte, b.cap)) == hipSuccess) e = hipDeviceSynchronize();
+        *bytes += (int64_t)b.cap;
+    });
+    (void)hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, STK_HIP_ERROR, std::string("debug_poison: ") + hipGetErrorString(e));
+    return STK_OK;
+}
+int multi_workspaces_empty(const stk_ctx* ctx) {
+    int empty = 0;
+    if (ctx->multi) for_each_workspace(ctx->multi, [&](DevBuf& b) { empty += b.cap == 0; }, false);   // a count: no device is touched
+    return empty;
+}
+
 void multi_destroy(stk_ctx* ctx) {
     MultiState* ms = ctx->multi;
     if (!ms) return;
     for (size_t i = 0; i < ms->comms.size(); i++) if (ms->comms[i]) (void)ms->api.CommDestroy(ms->comms[i]);
-    for (size_t i = 0; i < ms->members.size(); i++) {
-        (void)hipSetDevice(ms->devices[i]);
-        // (the buffers are sized for all devices before the first member is created: a failed stk_create_multi arrives
-        // here with fewer members than buffers, never the other way round)
-        if (i < ms->sums.size()) { ms->sums[i].release(); ms->counts[i].release(); ms->stage[i].release(); }
-        if (i > 0) stk_destroy(ms->members[i]);
-    }
+    // (the buffers are sized for all devices before the first member is created: a failed stk_create_multi arrives here
+    // with fewer members than buffers, never the other way round; the buffers of a member that never existed are empty)
+    for_each_workspace(ms, workspace_release_dev);
+    for (size_t i = 1; i < ms->members.size(); i++) stk_destroy(ms->members[i]);
     (void)hipSetDevice(ctx->device);
     delete ms;
     ctx->multi = nullptr;

@@ -97,10 +97,7 @@ void stk_destroy(stk_ctx* ctx) {
     for (stk_ctx*& h : ctx->lanes) if (h) { stk_destroy(h); h = nullptr; }
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (DevBuf* b : {&ctx->frames, &ctx->ref, &ctx->blur_tmp, &ctx->templates, &ctx->slots, &ctx->queue, &ctx->results,
-                      &ctx->partials, &ctx->first_sums, &ctx->warpframes, &ctx->acc, &ctx->scratch, &ctx->init_warps, &ctx->frameptrs, &ctx->clip,
-                      &ctx->quantile, &ctx->weighted, &ctx->coef, &ctx->quality, &ctx->local, &ctx->mesh, &ctx->reject})
-        b->release();
+    for_each_workspace(ctx, workspace_release_dev, workspace_release_host);
     keypoint_workspace_destroy(ctx->kp);
     geom::hg_workspace_destroy(ctx->hg);
     host_pool_destroy(ctx->host_pool);
@@ -109,8 +106,6 @@ void stk_destroy(stk_ctx* ctx) {
     for (auto& e : ctx->prof_ev) if (e) (void)hipEventDestroy(e);
     for (auto& pr : ctx->fold_ev) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (auto& pr : ctx->select_ev) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    if (ctx->host_done) (void)hipHostFree(ctx->host_done);
-    if (ctx->files_block) { if (ctx->files_block_pinned) (void)hipHostFree(ctx->files_block); else std::free(ctx->files_block); }
     for (auto& e : ctx->upload_events) if (e) (void)hipEventDestroy(e);
     if (ctx->gate_ev) (void)hipEventDestroy(ctx->gate_ev);
     if (ctx->gate_ev2) (void)hipEventDestroy(ctx->gate_ev2);
@@ -143,11 +138,25 @@ stk_status stk_get_timing(const stk_ctx* ctx, stk_timing* out) {
     return STK_OK;
 }
 
+// stk_get_counter "workspaces_empty": the enumerated DevBufs of this context and of its keypoint lanes that were never reserved
+static int workspaces_empty(const stk_ctx* ctx) {
+    int empty = 0;
+    const DevBufVisitor count = [&](DevBuf& b) { empty += b.cap == 0; };
+    stk_ctx* c = const_cast<stk_ctx*>(ctx);
+    for_each_workspace(c, count);
+    for_each_workspace(c->kp, count);
+    for_each_workspace(c->hg, count);
+    for (const stk_ctx* h : ctx->lanes) if (h) empty += workspaces_empty(h);
+    return empty;
+}
+
 stk_status stk_get_counter(const stk_ctx* ctx, const char* name, int64_t* out) {
     if (!ctx || !name || !out) return STK_INVALID_PARAMS;
     if (std::string(name) == "ecc_first_iter_slots") { *out = ctx->ecc_first_iter_slots; return STK_OK; }
     if (std::string(name) == "robust_select_us") { *out = ctx->robust_select_us; return STK_OK; }
     if (std::string(name) == "prep_stream_frames") { *out = ctx->prep_stream_frames; return STK_OK; }
+    if (std::string(name) == "debug_poison_bytes") { *out = ctx->debug_poison_bytes; return STK_OK; }
+    if (std::string(name) == "workspaces_empty") { *out = workspaces_empty(ctx) + multi_workspaces_empty(ctx); return STK_OK; }
     return STK_INVALID_PARAMS;
 }
 
@@ -162,8 +171,54 @@ stk_status stk_set_option(stk_ctx* ctx, const char* name, int64_t value) {
 
 }  // extern "C"
 
+// Option debug_poison: every byte of the context's persistent memory becomes `byte` (include/stacker.h). All streams are
+// idle before and after; only the context's own allocations are written, each over its own capacity; what the context
+// remembers about the CONTENT of a workspace is forgotten (the hook has destroyed it), what it remembers about geometry stays.
+static stk_status poison_context(stk_ctx* ctx, int byte, int64_t* bytes) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    const auto idle = [&]() -> hipError_t {
+        for (hipStream_t s : {ctx->stream, ctx->own_stream, ctx->copy_stream, ctx->prep_stream, ctx->tail_stream, ctx->ecc_stream2})
+            if (s) { const hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) return e; }
+        return hipSuccess;
+    };
+    HIP_TRY(idle());
+    hipError_t err = hipSuccess;
+    const DevBufVisitor dev = [&](DevBuf& b) {
+        if (!b.p || err != hipSuccess) return;
+        err = hipMemsetAsync(b.p, byte, b.cap, ctx->stream);
+        *bytes += (int64_t)b.cap;
+    };
+    const HostBlockVisitor host = [&](void* p, size_t n, bool) {
+        if (!p || !n) return;
+        std::memset(p, byte, n);
+        *bytes += (int64_t)n;
+    };
+    for_each_workspace(ctx, dev, host);
+    for_each_workspace(ctx->kp, dev, host);
+    for_each_workspace(ctx->hg, dev, host);
+    HIP_TRY(err);
+    HIP_TRY(idle());
+    ctx->ref_zeroed_ptr = nullptr; ctx->ref_zeroed_w = ctx->ref_zeroed_h = 0;
+    keypoint_workspace_forget(ctx->kp);
+    for (stk_ctx* h : ctx->lanes)
+        if (h) {
+            const stk_status st = poison_context(h, byte, bytes);
+            if (st) return fail(ctx, st, stk_last_error(h));
+        }
+    HIP_TRY(hipSetDevice(ctx->device));
+    return STK_OK;
+}
+
 stk_status set_option_one(stk_ctx* ctx, const char* name, int64_t value) {
     const std::string n(name);
+    if (n == "debug_poison") {
+        if (value < 0 || value > 255) return fail(ctx, STK_INVALID_PARAMS, "debug_poison must be a byte, 0..255");
+        int64_t bytes = 0;
+        stk_status st = poison_context(ctx, (int)value, &bytes);
+        if (!st) st = multi_poison(ctx, (int)value, &bytes);          // (the owner of a multi-device context only)
+        ctx->debug_poison_bytes = bytes;
+        return st;
+    }
     if (n == "ecc_slots") { if (value < 0 || value > 256) return fail(ctx, STK_INVALID_PARAMS, "ecc_slots out of range"); ctx->opt_ecc_slots = (int)value; }
     else if (n == "warp_subpixel_bits") { if (value != 0 && value != 5) return fail(ctx, STK_INVALID_PARAMS, "warp_subpixel_bits must be 0 or 5"); ctx->opt_subpixel_bits = (int)value; }
     else if (n == "warp_interpolation") { if (value != STK_INTER_LINEAR && value != STK_INTER_CUBIC) return fail(ctx, STK_INVALID_PARAMS, "warp_interpolation must be 1 (STK_INTER_LINEAR) or 2 (STK_INTER_CUBIC)"); ctx->opt_interp = (int)value; }
