@@ -1445,8 +1445,8 @@ stk_status stk_star_match(stk_ctx* ctx, const stk_frames* frames, const stk_star
  * and so do its left, upper and upper-left neighbours. That case is not refused (finding it would cost a pass over the
  * stack): it is a property of the fold to know. Under the other options the masters are those options' folds.
  * A multi-device context runs these calls on its first device. Follow-ups, not here: in-place calibration; dark-scale
- * optimisation (choosing s_i by minimising the residual noise); per-frame cosmetic detection without masters; demosaicing
- * and CFA-aware drizzle; whole-stack *_match_calibrated forms (calibrate, then call any existing entry point); shard and
+ * optimisation (choosing s_i by minimising the residual noise); per-frame cosmetic detection without masters; (demosaicing
+ * and Bayer drizzle: the next section;) whole-stack *_match_calibrated forms (calibrate, then call any existing entry point); shard and
  * files forms; a u8 BGR dword-window fast path of the calibration kernel. */
 typedef struct {
     const stk_image_f32* bias_or_null;  /* masters: width x height x frames->channels f32, in the frames' RAW sample units */
@@ -1479,6 +1479,87 @@ stk_status stk_defect_map(stk_ctx* ctx, const stk_image_f32* master, const stk_d
 stk_status stk_image_mean(stk_ctx* ctx, const stk_image_f32* image, double* mean);
 stk_status stk_master_stack(stk_ctx* ctx, const stk_frames* frames, int32_t normalize, int32_t stat_step,
                             const stk_robust_clip_params* clip, stk_image_f32* out, int32_t* counts_or_null);
+
+/* ---- colour-filter mosaics: an EXTENSION beyond the reference ------------------------------------------------------------
+ * The step between calibration and alignment for a one-shot-colour camera: a stack of single-channel Bayer mosaics in, a
+ * stack of B G R frames out (stk_demosaic), and the colour mask of a pattern (stk_cfa_mask), with which the existing drizzle
+ * integrates a mosaic without interpolating it. The order of a pipeline: stk_calibrate on the mosaic as ONE channel
+ * (defect_step 2, preferably to f32), stk_demosaic, then any aligner or combine.
+ * Site colours. A pattern is named by its 2 x 2 cell in reading order; the colour of pixel (x, y) is
+ * cell[(y & 1) * 2 + (x & 1)], the cell's top-left sample being pixel (0, 0). The red sites of STK_CFA_RGGB / GRBG / GBRG /
+ * BGGR have (x & 1, y & 1) = (0, 0) / (1, 0) / (0, 1) / (1, 1) = (pattern & 1, pattern >> 1); blue is diagonal to red.
+ * Cropping: a window of a mosaic that starts on an odd column is the mosaic of pattern ^ 1, on an odd row of pattern ^ 2.
+ * Borders. BORDER_REFLECT_101 on the MOSAIC: index -k is k, index w - 1 + k is w - 1 - k, applied again where the result
+ * is still outside (a 3-wide mosaic under HA). The reflection keeps an index's parity, so a reflected sample has the colour
+ * its position asks for. Width and height are at least 3 (SUPERPIXEL: 2), anything smaller is STK_INVALID_PARAMS.
+ * Integer mosaics (u8, u16). Every sum below is exact in int32 and every value is a numerator S over a power of two D
+ * (|S| < 2^24 for u16). Integer output: floor((S + D / 2) / D) saturated to [0, 255 or 65535]; f32 output: (float)S *
+ * (1.0f / D), exact. A site's own colour is the sample itself. With c the site, N S W E at distance 1, N2 S2 W2 E2 at distance
+ * 2, NW NE SW SE the diagonals:  h1 = W + E, v1 = N + S, h2 = W2 + E2, v2 = N2 + S2, x1 = v1 + h1, x2 = v2 + h2,
+ * d = (NW + NE) + (SW + SE).
+ *   STK_DEMOSAIC_BILINEAR   the mean of the same-colour sites of the 3 x 3 window (2 or 4 under the reflection):
+ *       G at R / B: x1 / 4.  R or B at a G site: h1 / 2 or v1 / 2, the pair of that colour.  R at B, B at R: d / 4.
+ *   STK_DEMOSAIC_MHC        Malvar, He, Cutler 2004, "High-quality linear interpolation for demosaicing of Bayer-patterned
+ *       color images", the coefficients doubled to integers, D = 16:
+ *       G at R / B:                                    8c + 4 x1 - 2 x2
+ *       R or B at a G site whose ROW holds it:         10c + 8 h1 - 2 d - 2 h2 + v2
+ *       R or B at a G site whose COLUMN holds it:      10c + 8 v1 - 2 d - 2 v2 + h2
+ *       R at B, B at R:                                12c + 4 d - 3 x2
+ *   STK_DEMOSAIC_HA         Hamilton-Adams green, colour differences for red and blue. At every R / B site
+ *       tH = 2c - W2 - E2, dH = |W - E| + |tH|, gH = 2 h1 + tH, and tV, dV, gV the same vertically;
+ *       G8 = 2 gH if dH < dV, 2 gV if dV < dH, else gH + gV: the green in eighths, unrounded, unclamped; D8 = 8c - G8.
+ *       At a G site G8 = 8c. Green out: G8 / 8. R or B at a G site with that colour in its row: (2 G8 + D8(W) + D8(E)) / 16,
+ *       in its column: (2 G8 + D8(N) + D8(S)) / 16. R at B, B at R: (4 G8 + (D8(NW) + D8(NE)) + (D8(SW) + D8(SE))) / 32.
+ *       The reach on the mosaic is 3. G8 at a position outside the frame is the formula on the reflected mosaic; for
+ *       integer mosaics that is G8 at the reflected position (the formulas are symmetric in W / E and N / S); for f32 the two
+ *       may differ by the order of the two subtractions of tH.
+ *   STK_DEMOSAIC_SUPERPIXEL the output is (width / 2) x (height / 2), one pixel per cell of the pattern: B and R are the
+ *       cell's samples, G = (G1 + G2) / 2; nothing is interpolated (a last odd row or column is not read). The choice for
+ *       oversampled data.
+ * f32 mosaics: the same formulas in f32, one rounding per operation, no contraction; terms are added left to right as
+ * written, parenthesised groups and the named sums (h1, x2, d, tH ..) first; tH = (2c - W2) - E2; products by powers of two
+ * are exact, 10 * c, 12 * c and 3 * x2 round once each; the last step is a multiplication by 1 / D (none for a site's own
+ * colour). The HA comparisons are plain `<`: a NaN takes the gH + gV branch. Non-finite samples spread through the stencil
+ * and are not refused.
+ * Which method: MHC and HA use the correlation between the colour planes and roughly halve BILINEAR's error on natural and
+ * astronomical scenes (DESIGN §4.25 has the figures); where the planes are NOT correlated (synthetic scenes with independent
+ * colours, narrow-band filters in front of a colour sensor) they are worse, and BILINEAR is the right choice.
+ * Outputs. out: n pointers in the mosaic's location, each 3 channels (B G R interleaved, as everywhere) of out_depth =
+ * the mosaic's depth or STK_DEPTH_F32 (f32 mosaics: f32 only), rows out_row_stride_bytes apart (0 = tightly packed; else at
+ * least a row's bytes and a multiple of the element size). Only pixel bytes are written: row padding keeps its contents. Of
+ * plane i the bytes [data[i], data[i] + row_stride_bytes * (height - 1) + width * depth / 8) are read, pixel bytes only. An
+ * output that overlaps a plane is STK_INVALID_PARAMS.
+ * STK_INVALID_PARAMS: a null context, mosaic, table, plane or output; n < 1; a pattern, method, depth or location outside
+ * the enums; out_depth neither the depth nor STK_DEPTH_F32; a size below the minimum or above 2^30 pixels; a row stride
+ * below a row or no multiple of the element size. STK_NOT_IMPLEMENTED: n > 65535, or more than 65535 tile rows (16 mosaic
+ * rows each; SUPERPIXEL: 8).
+ * Kernel (kernels_demosaic.hip): a workgroup of 256 threads owns a 64 x 16 tile of one frame, a thread one 2 x 2 cell on a
+ * cell grid shifted by the pattern, so that every lane runs the same code on one R, two G and one B site; the tile and its
+ * halo are staged in LDS with the reflection applied on the way in; HA keeps a second LDS plane of G8.
+ * stk_cfa_mask. plane: width x height f32, tightly packed, host or device: 1.0f where the colour of (x, y) is `channel` (0 =
+ * B, 1 = G, 2 = R), else 0.0f. It is the plane stk_drizzle_stack, stk_local_weighted_stack and stk_reject_maps take through
+ * `maps`; a pixel whose map value is 0 is never read, so drizzling the mosaic as single-channel frames once per colour with
+ * that colour's mask (the same plane n times) is Bayer drizzle: no interpolated sample enters the result, and den shows the
+ * 1 : 2 : 1 coverage. STK_INVALID_PARAMS: a null context or plane, width or height < 1, pattern, channel or location out of
+ * range.
+ * A multi-device context runs these calls on its first device. Follow-ups, not here: a fused three-colour CFA drizzle kernel
+ * and CFA-aware rejection maps; X-Trans and other patterns that are not 2 x 2; VNG / AHD; demosaicing inside stk_calibrate's
+ * launch; whole-stack *_match_cfa forms (stk_demosaic, then any entry point); a shard form; file front-ends for raw formats;
+ * wider loads and stores for 8-bit rows (a dword store path through LDS was measured and was slower: DESIGN §4.25). */
+enum { STK_CFA_RGGB = 0, STK_CFA_GRBG = 1, STK_CFA_GBRG = 2, STK_CFA_BGGR = 3 };
+enum { STK_DEMOSAIC_BILINEAR = 0, STK_DEMOSAIC_MHC = 1, STK_DEMOSAIC_HA = 2, STK_DEMOSAIC_SUPERPIXEL = 3 };
+typedef struct {
+    const void* const* data;        /* n single-channel planes */
+    int32_t n, width, height;
+    int32_t depth;                  /* STK_DEPTH_U8 / U16 / F32 */
+    int32_t location;               /* STK_HOST | STK_DEVICE */
+    int32_t pattern;                /* STK_CFA_*: the 2 x 2 cell whose top-left sample is pixel (0, 0) */
+    size_t  row_stride_bytes;       /* 0 = tightly packed; else >= a row and a multiple of the element size */
+} stk_mosaic;
+stk_status stk_demosaic(stk_ctx* ctx, const stk_mosaic* mosaic, int32_t method, int32_t out_depth, void* const* out,
+                        size_t out_row_stride_bytes);
+stk_status stk_cfa_mask(stk_ctx* ctx, int32_t width, int32_t height, int32_t pattern, int32_t channel, float* plane,
+                        int32_t location);
 
 /* ---- stage-level entry points (parity tests bind these) ------------------ */
 /* cvt_color(BGR2GRAY) on the integer image, utils.rs:136-142. out: w*h of the input depth

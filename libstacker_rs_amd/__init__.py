@@ -9,6 +9,7 @@ Importing the package is cheap and never touches the GPU; the shared library is 
 use (api.Stacker / _ffi.load) and there is no CPU fallback.
 """
 from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, BORDER_WRAP,  # noqa: F401
+                  CFA_BGGR, CFA_GBRG, CFA_GRBG, CFA_RGGB, DEMOSAIC_BILINEAR, DEMOSAIC_HA, DEMOSAIC_MHC, DEMOSAIC_SUPERPIXEL,
                   INTER_CUBIC, INTER_LINEAR,
                   LEAST_SQUARES, LMEDS, RANSAC, RHO, CalibrationParameters, DefectParameters, DrizzleParameters, EccMatchParameters, HipError, InvalidParams, IoError,
                   KeyPointMatchParameters, LocalNormParameters, LocalParameters, MeshParameters, MotionType, NotEnoughFiles, NotImplementedYet, OpenCvError,
@@ -21,4 +22,5 @@ __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchPa
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
            "SelectParameters", "rank_frames", "LocalParameters", "MeshParameters", "mesh_grid", "mesh_pyramid_shapes", "DrizzleParameters",
            "RejectParameters", "LocalNormParameters", "local_norm_estimate", "local_norm_grid",
-           "StarParameters", "STAR_DTYPE", "star_match_lists", "CalibrationParameters", "DefectParameters"]
+           "StarParameters", "STAR_DTYPE", "star_match_lists", "CalibrationParameters", "DefectParameters",
+           "CFA_RGGB", "CFA_GRBG", "CFA_GBRG", "CFA_BGGR", "DEMOSAIC_BILINEAR", "DEMOSAIC_MHC", "DEMOSAIC_HA", "DEMOSAIC_SUPERPIXEL"]

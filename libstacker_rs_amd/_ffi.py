@@ -122,6 +122,11 @@ class DefectParams(C.Structure):
                 ("accumulate", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Mosaic(C.Structure):
+    _fields_ = [("data", C.POINTER(C.c_void_p)), ("n", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("depth", C.c_int32), ("location", C.c_int32), ("pattern", C.c_int32), ("row_stride_bytes", C.c_size_t)]
+
+
 class Timing(C.Structure):
     _fields_ = [("prep_ms", C.c_double), ("align_ms", C.c_double), ("warp_ms", C.c_double),
                 ("finalize_ms", C.c_double), ("ecc_iter_launches", C.c_int64),
@@ -323,6 +328,8 @@ SIGNATURES = {
     "stk_image_mean": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_void_p]),
     "stk_master_stack": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_int32, C.c_int32, C.POINTER(RobustClipParams),
                                     C.POINTER(ImageF32), C.c_void_p]),
+    "stk_demosaic": (c_status, [C.c_void_p, C.POINTER(Mosaic), C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),
+    "stk_cfa_mask": (c_status, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
     "stk_grey":(c_status, [C.c_void_p, C.POINTER(Frames), C.c_void_p]),
     "stk_convert_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_double, C.c_void_p]),
     "stk_hybrid_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.POINTER(EccParams),

@@ -27,6 +27,8 @@ RANSAC, LMEDS, RHO, LEAST_SQUARES = 8, 4, 16, 0
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101, BORDER_TRANSPARENT = range(6)
 INTER_LINEAR, INTER_CUBIC = 1, 2          # option "warp_interpolation" (OpenCV's numbers)
 HOST, DEVICE = 0, 1
+CFA_RGGB, CFA_GRBG, CFA_GBRG, CFA_BGGR = range(4)          # STK_CFA_*: the 2 x 2 cell in reading order
+DEMOSAIC_BILINEAR, DEMOSAIC_MHC, DEMOSAIC_HA, DEMOSAIC_SUPERPIXEL = range(4)
 
 
 class StackerError(Exception):
@@ -1446,6 +1448,98 @@ class Stacker:
         """The master flat: the frames minus bias and scaled dark as float32, then master_stack(normalize = 2)."""
         cal = self.calibrate(flats, CalibrationParameters(bias=bias, dark=dark, dark_scale=dark_scale, out_depth=32))
         return self.master_stack(cal, 2, clip, stat_step=stat_step)
+
+    # -- colour-filter mosaics (extension beyond the reference) ------------------------------------------------
+    def demosaic(self, files, pattern: int, method: int = DEMOSAIC_MHC, out_depth: Optional[int] = None, out=None):
+        """A stack of single-channel Bayer mosaics (H x W or H x W x 1; host arrays or device tensors; padded row views as
+        calibrate takes them) as B G R frames (stk_demosaic). pattern: CFA_*; method: DEMOSAIC_*. Returns n x H x W x 3
+        (DEMOSAIC_SUPERPIXEL: n x H/2 x W/2 x 3) of the mosaics' dtype (or float32, out_depth = 32) where the mosaics live.
+        `out`: n images the caller holds instead, by calibrate's rules (same location, row-strided views allowed, all with one
+        row step); only their pixel bytes are written, and they must not overlap the mosaics."""
+        m = self._stack(files)
+        if m.c != 1:
+            raise InvalidParams("demosaic takes single-channel mosaics (H x W or H x W x 1)")
+        od = int(m.depth if out_depth is None else out_depth)
+        dt = {8: "uint8", 16: "uint16", 32: "float32"}.get(od)
+        if dt is None:
+            raise InvalidParams("out_depth must be 8, 16 or 32")
+        half = int(method) == DEMOSAIC_SUPERPIXEL
+        oh, ow = (m.h // 2, m.w // 2) if half else (m.h, m.w)
+        el = od // 8
+        keep = []
+        stride = 0
+        if out is None:
+            res, base = self._alloc(m, (m.n, oh, ow, 3), dt)
+            ptrs = [base + i * oh * ow * 3 * el for i in range(m.n)]
+        else:
+            res = out
+            outs = list(out)
+            if len(outs) != m.n:
+                raise InvalidParams("one output per mosaic expected")
+            ptrs, strides = [], set()
+            for o in outs:
+                dev = _is_torch(o) and o.is_cuda
+                if dev != (m.location == DEVICE):
+                    raise InvalidParams("the outputs must live where the mosaics live")
+                shape = tuple(int(v) for v in o.shape)
+                if str(o.dtype).replace("torch.", "") != dt or shape != (oh, ow, 3):
+                    raise InvalidParams("every output must be H x W x 3 of the output depth")
+                if not dev and _is_torch(o):
+                    o = o.numpy()
+                if dev:
+                    self._tensor_ready(o)
+                    rs = ow * 3 * el if o.is_contiguous() else _row_stride_bytes(shape, [s * el for s in o.stride()], el)
+                    ptrs.append(o.data_ptr())
+                else:
+                    rs = ow * 3 * el if o.flags.c_contiguous else _row_stride_bytes(shape, o.strides, el)
+                    ptrs.append(o.ctypes.data)
+                if not rs:
+                    raise InvalidParams("an output must be contiguous or a view whose only non-contiguity is its row step")
+                strides.add(rs)
+                keep.append(o)
+            if len(strides) != 1:
+                raise InvalidParams("all outputs must share one row step")
+            stride = strides.pop()
+        f = m.c_frames
+        mosaic = _ffi.Mosaic(f.data, m.n, m.w, m.h, m.depth, m.location, int(pattern), f.row_stride_bytes)
+        arr = (C.c_void_p * m.n)(*ptrs)
+        self._check(self._lib.stk_demosaic(self._h, C.byref(mosaic), int(method), od, C.cast(arr, C.c_void_p), stride))
+        return res
+
+    def cfa_mask(self, width: int, height: int, pattern: int, channel: int, device=False):
+        """The H x W float32 plane that is 1 where the colour of a pattern's site is `channel` (0 = B, 1 = G, 2 = R) and 0
+        elsewhere (stk_cfa_mask): what drizzle_stack, local_weighted_stack and reject_maps take through `maps`. device:
+        False = a numpy array, True = a tensor on this context's device, or a torch device."""
+        where = None
+        if device is not False and device is not None:
+            import torch
+            where = torch.device("cuda", self.device) if device is True else torch.device(device)
+        plane, addr = self._alloc(where, (int(height), int(width)), np.float32)
+        self._check(self._lib.stk_cfa_mask(self._h, int(width), int(height), int(pattern), int(channel), C.c_void_p(addr),
+                                           HOST if where is None else DEVICE))
+        return plane
+
+    def cfa_drizzle_stack(self, files, warps, pattern: int, drizzle: Optional["DrizzleParameters"] = None, **drizzle_kw):
+        """Bayer drizzle: the single-channel mosaics drizzled once per colour with that colour's cfa_mask as every frame's
+        map, so that no interpolated sample enters the result. By definition three drizzle_stack calls (drizzle_kw goes to
+        each; `maps` and `return_den` are this call's own), stacked: returns (image, den), both oh x ow x 3 in B G R order;
+        den shows the 1 : 2 : 1 coverage of the colours."""
+        if "maps" in drizzle_kw or "return_den" in drizzle_kw:
+            raise InvalidParams("cfa_drizzle_stack sets maps and return_den itself")
+        files = files if hasattr(files, "shape") else list(files)
+        m = self._stack(files)
+        if m.c != 1:
+            raise InvalidParams("cfa_drizzle_stack takes single-channel mosaics (H x W or H x W x 1)")
+        images, dens = [], []
+        for channel in range(3):
+            mask = self.cfa_mask(m.w, m.h, pattern, channel, device=m.torch_device if m.location == DEVICE else False)
+            img, den = self.drizzle_stack(files, warps, drizzle, maps=[mask] * m.n, return_den=True, **drizzle_kw)
+            images.append(img.reshape(den.shape))
+            dens.append(den)
+        if _is_torch(dens[0]):
+            import torch
+            return torch.stack(images, -1), torch.stack(dens, -1)
+        return np.stack(images, -1), np.stack(dens, -1)
 
     def local_weighted_stack(self, files, warps, maps, gain=None, offset=None, weights=None, include=None, *, applied=None,
                              floor: float = 1.0, power: int = 2, is_affine=False, border_mode=BORDER_CONSTANT,

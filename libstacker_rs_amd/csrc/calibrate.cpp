@@ -10,12 +10,11 @@
 #include <cstring>
 
 #include "context.h"
+#include "spans.h"
 
 using namespace stk;
 
 namespace {
-
-struct Span { uintptr_t lo, hi; };
 
 stk_status master_check(stk_ctx* ctx, const stk_image_f32* m, const stk_frames* f, const char* what) {
     if (!m) return STK_OK;
@@ -95,22 +94,15 @@ stk_status stk_calibrate(stk_ctx* ctx, const stk_frames* frames, const stk_calib
     // no output may overlap anything the call reads in the same memory space
     const bool host = frames->location == STK_HOST;
     {
-        std::vector<Span> in;
-        const size_t ispan = frame_copy_bytes(frames);
-        for (int i = 0; i < n; i++) in.push_back({(uintptr_t)frames->data[i], (uintptr_t)frames->data[i] + ispan});
+        SpanSet in;
+        for (int i = 0; i < n; i++) in.add(frames->data[i], frame_copy_bytes(frames));
         for (const stk_image_f32* m : masters)
-            if (m && m->location == frames->location) in.push_back({(uintptr_t)m->data, (uintptr_t)m->data + image_span_bytes(m)});
-        if (cal->defects_or_null && cal->defects_location == frames->location)
-            in.push_back({(uintptr_t)cal->defects_or_null, (uintptr_t)cal->defects_or_null + (size_t)w * h});
-        std::sort(in.begin(), in.end(), [](const Span& a, const Span& b) { return a.lo < b.lo; });
-        std::vector<uintptr_t> reach(in.size());               // the furthest end among the spans up to this one
-        for (size_t k = 0; k < in.size(); k++) reach[k] = std::max(in[k].hi, k ? reach[k - 1] : 0);
+            if (m && m->location == frames->location) in.add(m->data, image_span_bytes(m));
+        if (cal->defects_or_null && cal->defects_location == frames->location) in.add(cal->defects_or_null, (size_t)w * h);
+        in.seal();
         const size_t ospan = ostride * (size_t)(h - 1) + orow;
-        for (int i = 0; i < n; i++) {
-            const uintptr_t lo = (uintptr_t)out[i], hi = lo + ospan;
-            const size_t k = std::lower_bound(in.begin(), in.end(), hi, [](const Span& s, uintptr_t v) { return s.lo < v; }) - in.begin();
-            if (k > 0 && reach[k - 1] > lo) return fail(ctx, STK_INVALID_PARAMS, "calibrate: an output overlaps a frame, a master or the map (in-place calibration is not supported)");
-        }
+        for (int i = 0; i < n; i++)
+            if (in.overlaps(out[i], ospan)) return fail(ctx, STK_INVALID_PARAMS, "calibrate: an output overlaps a frame, a master or the map (in-place calibration is not supported)");
     }
 
     timing_begin(ctx);

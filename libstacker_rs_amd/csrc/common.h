@@ -345,6 +345,22 @@ hipError_t launch_defect_map(const float* master, size_t stride, int w, int h, i
 // per-channel f64 sums of an f32 image: one partial per row and channel into partials (h x 4 doubles), then added in row
 // order into sums (4 doubles)
 hipError_t launch_image_sums(const float* image, size_t stride, int w, int h, int cn, double* partials, double* sums, hipStream_t s);
+// colour-filter mosaics (kernels_demosaic.hip; definition: include/stacker.h, stk_mosaic). One record per frame of the
+// launch; strides in bytes; (w, h): the mosaic's size, at least 3 x 3 (superpixel: 2 x 2).
+constexpr int DEM_TW = 64, DEM_TH = 16;      // output pixels per workgroup tile of demosaic_kernel (32 x 8 cells of 2 x 2)
+constexpr int DEM_SP_TH = 4;                 // output rows per workgroup of the superpixel kernel
+struct DemFrame { const void* src; void* dst; };
+struct DemArgs {
+    const DemFrame* frames;
+    int n;
+    int w, h;
+    int pattern;                 // STK_CFA_*: bit 0 / bit 1 = the column / row parity of the red sites
+    size_t in_stride, out_stride;
+};
+// depth: the mosaic's (8 / 16 / 32); out_depth: depth or 32; method: STK_DEMOSAIC_*; a.n <= 65535
+hipError_t launch_demosaic(const DemArgs& a, int depth, int out_depth, int method, hipStream_t s);
+// plane (w x h f32, tightly packed): 1 where the site's colour is `channel` (0 = B, 1 = G, 2 = R), else 0
+hipError_t launch_cfa_mask(float* plane, int w, int h, int pattern, int channel, hipStream_t s);
 // local alignment (kernels_mesh.hip; definition: include/stacker.h, stk_mesh_params). Entry 0 of `frames` is frame 0 (its
 // matrix is not read); entries 1 .. n_entries - 1 are the frames that get a field: fields[k] (gh x gw x 2 f32) and status[k]
 // (gh x gw int32; the array or an entry may be null) are indexed like the table

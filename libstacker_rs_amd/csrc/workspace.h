@@ -223,6 +223,23 @@ inline ImageLayout image_layout(size_t partial_rows, size_t image_bytes, size_t 
     return L;
 }
 
+// ctx->local, colour-filter mosaics (demosaic.cpp): the per-frame records, then the tightly packed outputs of host mosaics
+// (stk_cfa_mask: no records, the plane of a host caller)
+struct DemosaicLayout { size_t records, out, total; };
+inline DemosaicLayout demosaic_layout(size_t n_frames, size_t out_bytes) {
+    Carver c;
+    DemosaicLayout L{};
+    L.records = c.take(n_frames * sizeof(stk::DemFrame));
+    L.out = c.take(out_bytes);
+    L.total = c.total;
+    return L;
+}
+// the workgroup rows of a demosaic launch over h mosaic rows: the cell grid starts one row early where red lies on odd rows
+// (bit 1 of the pattern); the superpixel kernel (method 3) has DEM_SP_TH output rows per workgroup
+inline int demosaic_grid_rows(int h, int pattern, int method) {
+    return method == 3 ? (h / 2 + stk::DEM_SP_TH - 1) / stk::DEM_SP_TH : (h + (pattern >> 1) + stk::DEM_TH - 1) / stk::DEM_TH;
+}
+
 // ---------------------------------------------------------------------------------------------
 // room for `bytes` in a workspace, or STK_HIP_ERROR (the allocator's sticky error is cleared: the context stays usable)
 inline stk_status workspace_reserve(stk_ctx* ctx, DevBuf& buf, size_t bytes, const char* what) {
