@@ -1665,6 +1665,86 @@ stk_status stk_keypoint_match_ranked(stk_ctx* ctx, const stk_frames* frames, con
                                      stk_frame_stats* stats_or_null, const stk_select_params* select, int32_t* order,
                                      int32_t* n_kept, double* scores_or_null);
 
+/* ---- per-frame noise estimation and inverse-variance frame weights (an extension beyond the reference) -----------
+ * Every combine takes a per-frame weight; for a deep-sky stack the weight that minimises the result's noise is the
+ * inverse of the frame's noise variance. stk_stack_noise measures that noise, per frame and channel, on the frame's OWN
+ * grid (before any warp: interpolation changes the noise), from two exact histograms that one device pass produces:
+ *   HV: the counts of v(x, y) over all w x h pixels; BV = 256 bins at depth 8, 65 536 at depth 16.
+ *   HR: the counts of min(|r(x, y)|, BR - 1) over the (w - 2)(h - 2) interior pixels 1 <= x <= w - 2, 1 <= y <= h - 2 (no
+ *       border extension: a pixel outside the frame forms no address), r = Immerkaer's noise mask in integers,
+ *           r = v(x-1,y-1) - 2 v(x,y-1) + v(x+1,y-1) - 2 v(x-1,y) + 4 v(x,y) - 2 v(x+1,y) + v(x-1,y+1) - 2 v(x,y+1) + v(x+1,y+1).
+ *       Depth 8: BR = 2041 (|r| <= 8 x 255: the cap never acts). Depth 16: BR = 65 536, and the last bin collects every
+ *       |r| >= 65 535 (the overflow bin).
+ * Counts are uint32 and exact: tiling, launch shape and summation order cannot change a bit.
+ *
+ * stk_noise_from_hist reduces one (frame, channel)'s pair of histograms. Host code: no context, no GPU; f64 and integers,
+ * in this order:
+ *   1. n = sum HV, k = (n + 1) / 2; median = the k-th smallest value; mad = the k-th smallest |v - median| (the smallest d
+ *      with #{|v - median| <= d} >= k, from the cumulative counts). An empty histogram gives 0 and 0.
+ *   2. m = sum HR, k' = (m + 1) / 2; res_median = the k'-th smallest capped |r|.
+ *   3. s = max(1.4826 * (double)res_median, 0.5); top = overflow_bin ? br - 2 : br - 1; prev = -1.
+ *   4. at most 16 rounds: cut = min((int)floor(3.0 * s), top); stop when cut == prev, else prev = cut;
+ *      N = sum_{b <= cut} HR[b], Q = sum_{b <= cut} b^2 HR[b] (int64, exact); if N == 0 or Q == 0: sigma = 0, flag bit 0,
+ *      stop; s = sqrt((double)Q / (double)N) * 1.0136 (the 3-sigma truncation correction 1 / sqrt(1 - 6 phi(3) / (2 Phi(3) - 1))).
+ *   5. sigma = s / 6.0 (the mask's coefficients have squared sum 36); kept = N of the last round.
+ *   6. flag bit 1: overflow_bin is set and the last cut == top — the noise is beyond what the capped histogram resolves.
+ * bv in [1, 65 536], br in [2, 65 536], overflow_bin 0 or 1, no null pointer: else STK_INVALID_PARAMS. Below sigma = 1.5
+ * grey levels the quantisation's 1/12 biases the estimate upward. */
+typedef struct {
+    int32_t median;                 /* of the values */
+    int32_t mad;                    /* median absolute deviation of the values from `median` */
+    int32_t res_median;             /* median of the capped |r| */
+    int32_t flags;                  /* bit 0: no residual energy under the cut (sigma = 0); bit 1: the cut reached the cap */
+    double  sigma;                  /* the noise's standard deviation in grey levels of the frame's depth */
+    int64_t kept;                   /* residuals under the last cut */
+} stk_noise_stat;
+stk_status stk_noise_from_hist(const uint32_t* hv, int32_t bv, const uint32_t* hr, int32_t br, int32_t overflow_bin,
+                               stk_noise_stat* out);
+
+/* The histograms and statistics of every frame and channel of a u8 or u16 stack in one device pass: each frame is read
+ * once. frames: 1, 3 or 4 channels (a fourth channel is treated like the others), host or device memory, any row stride (a
+ * frame whose base address or row stride is no multiple of 4 is read element by element: same result, slower); host
+ * frames and large stacks go through the context's workspaces in batches. stats: n x 4, frame-major, the unused channel
+ * slots zeroed; each is stk_noise_from_hist of that frame and channel (overflow_bin = 1 at depth 16). hist_or_null: host
+ * memory, n x channels x (BV + BR) uint32, HV then HR per frame and channel. The device histograms are zeroed on the
+ * call's stream inside the call: no result depends on what the context held before. width or height below 3:
+ * STK_INVALID_PARAMS; f32 frames, and frames above 2^27 pixels (the int64 sums stay exact within it): STK_NOT_IMPLEMENTED.
+ * stk_timing.prep_ms is the device time of the pass (for host frames with their copies), every other field 0; the host
+ * reduction is not in it. A multi-device context uses its first device. */
+stk_status stk_stack_noise(stk_ctx* ctx, const stk_frames* frames, stk_noise_stat* stats /* n x 4 */, uint32_t* hist_or_null);
+
+/* Inverse-variance weights from the statistics. Host code: no context, no GPU. With C = min(channels, 3),
+ *   V_i = sum_{c < C} (g_ic * max(sigma_ic, sigma_floor))^2     (f64, c ascending; g_ic = records[i].gain[c], or 1 without records),
+ *   w_i = (float)((u_i * V_ref) / V_i),                          u_i = weights_or_null[i], or 1; ref = the first included frame;
+ * an excluded frame (include_or_null[i] == 0) gets weight 0. This is the inverse variance of the frame AFTER the combine's
+ * own gain has mapped it onto the reference, so normalisation and weighting compose: pass the gains the fold will apply.
+ * The change of the noise under the fold's interpolation (a bilinear or bicubic sample averages neighbours, by an amount
+ * that depends on the sub-pixel phase) is NOT modelled. stats: n x 4 as stk_stack_noise returns them. sigma_floor must be
+ * finite and > 0, every u_i finite and >= 0, every sigma read finite and >= 0, every gain read finite, V_i > 0, channels 1,
+ * 3 or 4, n >= 1, one frame included: else STK_INVALID_PARAMS. */
+stk_status stk_noise_weights(const stk_noise_stat* stats /* n x 4 */, int32_t n, int32_t channels,
+                             const stk_frame_weight* records_or_null, const int32_t* include_or_null,
+                             const float* weights_or_null, double sigma_floor, float* weights_out /* n */);
+
+/* stk_ecc_match_weighted / stk_keypoint_match_weighted with the weights from the frames' noise. By definition each equals
+ * its parts, bit for bit: (1) the plain call's stats; (2) the weighted form's gain / offset estimate from the overlap moments
+ * (weight->normalize); (3) stk_stack_noise on the same frames; (4) stk_noise_weights with those records, the caller's
+ * weights_or_null as u and sigma_floor, the frames the plain call dropped excluded; (5) stk_weighted_stack with the
+ * resulting records. applied_or_null returns what the fold used; noise_or_null (n x 4) the statistics. The frames are
+ * still resident in HBM for the noise pass: nothing is uploaded again. stk_timing is the plain call's but for
+ * finalize_ms, which holds the moments pass, the noise pass and the fold. Frames of depth 8 or 16 where the plain call
+ * takes them; the refusals of stk_stack_noise and stk_noise_weights apply. The clip, quantile, drizzle and star combines
+ * have no such form: compose stk_stack_noise + stk_noise_weights + the *_stack call. */
+stk_status stk_ecc_match_noise_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_ecc_params* params, float scale_down_width,
+                                        const stk_weight_params* weight, const float* weights_or_null, double sigma_floor,
+                                        stk_image_f32* out, float* coverage_or_null, stk_frame_weight* applied_or_null,
+                                        stk_frame_stats* stats_or_null, stk_noise_stat* noise_or_null);
+stk_status stk_keypoint_match_noise_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params,
+                                             float scale_down_width, const stk_weight_params* weight, const float* weights_or_null,
+                                             double sigma_floor, stk_image_f32* out, int32_t* dropped, float* coverage_or_null,
+                                             stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null,
+                                             stk_noise_stat* noise_or_null);
+
 /* One frame's whole ECC preparation as ecc_match runs it per frame: cvt_color(BGR2GRAY) (utils.rs:136-142) followed
  * by findTransformECC's own GaussianBlur of the float image (lib.rs:769-777) in one fused pass. `out` is a tightly
  * packed width x height f32 plane in the frame's location. BGR frames, 8-bit or f32. */

@@ -12,10 +12,11 @@ from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_RE
                   CFA_BGGR, CFA_GBRG, CFA_GRBG, CFA_RGGB, DEMOSAIC_BILINEAR, DEMOSAIC_HA, DEMOSAIC_MHC, DEMOSAIC_SUPERPIXEL,
                   INTER_CUBIC, INTER_LINEAR,
                   LEAST_SQUARES, LMEDS, RANSAC, RHO, CalibrationParameters, DefectParameters, DrizzleParameters, EccMatchParameters, HipError, InvalidParams, IoError,
-                  KeyPointMatchParameters, LocalNormParameters, LocalParameters, MeshParameters, MotionType, NotEnoughFiles, NotImplementedYet, OpenCvError,
+                  KeyPointMatchParameters, LocalNormParameters, LocalParameters, MeshParameters, MotionType, NOISE_DTYPE, NoiseParameters, NotEnoughFiles, NotImplementedYet, OpenCvError,
                   ProcessingError, QuantileParameters, RejectParameters, RobustClipParameters, SelectParameters, SigmaClipParameters, Stacker,
                   StackerError, StarParameters, STAR_DTYPE, WeightParameters,
-                  default_stacker, ecc_match, keypoint_match, local_norm_estimate, local_norm_grid, mesh_grid, mesh_pyramid_shapes, rank_frames,
+                  default_stacker, ecc_match, keypoint_match, local_norm_estimate, local_norm_grid, mesh_grid, mesh_pyramid_shapes, noise_from_hist, noise_weights,
+                  rank_frames,
                   star_match_lists)
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
@@ -23,4 +24,5 @@ __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchPa
            "SelectParameters", "rank_frames", "LocalParameters", "MeshParameters", "mesh_grid", "mesh_pyramid_shapes", "DrizzleParameters",
            "RejectParameters", "LocalNormParameters", "local_norm_estimate", "local_norm_grid",
            "StarParameters", "STAR_DTYPE", "star_match_lists", "CalibrationParameters", "DefectParameters",
+           "NoiseParameters", "NOISE_DTYPE", "noise_from_hist", "noise_weights",
            "CFA_RGGB", "CFA_GRBG", "CFA_GBRG", "CFA_BGGR", "DEMOSAIC_BILINEAR", "DEMOSAIC_MHC", "DEMOSAIC_HA", "DEMOSAIC_SUPERPIXEL"]

@@ -110,6 +110,11 @@ class StarParams(C.Structure):
                 ("border_value", C.c_double * 4)]
 
 
+class NoiseStat(C.Structure):
+    _fields_ = [("median", C.c_int32), ("mad", C.c_int32), ("res_median", C.c_int32), ("flags", C.c_int32),
+                ("sigma", C.c_double), ("kept", C.c_int64)]
+
+
 class Calibration(C.Structure):
     _fields_ = [("bias_or_null", C.POINTER(ImageF32)), ("dark_or_null", C.POINTER(ImageF32)), ("flat_or_null", C.POINTER(ImageF32)),
                 ("dark_scale_or_null", C.c_void_p), ("flat_mean", C.c_float * 4), ("flat_min", C.c_float), ("pedestal", C.c_float),
@@ -355,6 +360,19 @@ SIGNATURES = {
     "stk_keypoint_match_ranked": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(KeypointParams), C.c_float,
                                              C.POINTER(ImageF32), C.POINTER(C.c_int32), C.POINTER(FrameStats),
                                              C.POINTER(SelectParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
+    "stk_noise_from_hist": (c_status, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(NoiseStat)]),
+    # (the noise calls take their stk_frames by address, as a void pointer: api.py passes byref(m.c_frames) all the same, and
+    # tests/test_cpu_noise.py reads the structure back through that address)
+    "stk_stack_noise": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(NoiseStat), C.c_void_p]),
+    "stk_noise_weights": (c_status, [C.POINTER(NoiseStat), C.c_int32, C.c_int32, C.POINTER(FrameWeight), C.c_void_p, C.c_void_p,
+                                     C.c_double, C.c_void_p]),
+    "stk_ecc_match_noise_weighted": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(EccParams), C.c_float, C.POINTER(WeightParams),
+                                                C.c_void_p, C.c_double, C.POINTER(ImageF32), C.c_void_p, C.POINTER(FrameWeight),
+                                                C.POINTER(FrameStats), C.POINTER(NoiseStat)]),
+    "stk_keypoint_match_noise_weighted": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(KeypointParams), C.c_float,
+                                                     C.POINTER(WeightParams), C.c_void_p, C.c_double, C.POINTER(ImageF32),
+                                                     C.POINTER(C.c_int32), C.c_void_p, C.POINTER(FrameWeight), C.POINTER(FrameStats),
+                                                     C.POINTER(NoiseStat)]),
     "stk_grey_blur_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_int32, C.c_void_p]),
     "stk_gaussian_blur_f32": (c_status, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p]),

@@ -427,6 +427,68 @@ def rank_frames(scores, select: Optional["SelectParameters"] = None):
     return order[:n], kept.value, weights[:n]
 
 
+# one stk_noise_stat (include/stacker.h)
+NOISE_DTYPE = np.dtype([("median", "<i4"), ("mad", "<i4"), ("res_median", "<i4"), ("flags", "<i4"), ("sigma", "<f8"), ("kept", "<i8")])
+
+
+@dataclass
+class NoiseParameters:            # extension beyond the reference: include/stacker.h, stk_noise_weights
+    """How noise statistics become frame weights: `sigma_floor`, in grey levels of the frames' depth, is the least noise a
+    frame is credited with (a frame cannot earn unbounded weight from a clipped or quantised background). None: 0.25 for
+    8-bit and 64 for 16-bit frames."""
+    sigma_floor: Optional[float] = None
+
+    def floor(self, depth: int = 8) -> float:
+        return float(self.sigma_floor) if self.sigma_floor is not None else (0.25 if depth == 8 else 64.0)
+
+
+def noise_from_hist(hv, hr, overflow_bin: bool = False):
+    """stk_noise_from_hist on one (frame, channel)'s value and residual histograms (Stacker.stack_noise(return_hist=True)):
+    one NOISE_DTYPE record. overflow_bin: the last residual bin collects everything above it (16-bit frames). Host code:
+    needs the library, not a GPU."""
+    hv = np.ascontiguousarray(np.asarray(hv, np.uint32).reshape(-1))
+    hr = np.ascontiguousarray(np.asarray(hr, np.uint32).reshape(-1))
+    out = np.zeros(1, NOISE_DTYPE)
+    st = _ffi.load().stk_noise_from_hist(C.c_void_p(hv.ctypes.data), hv.size, C.c_void_p(hr.ctypes.data), hr.size, int(overflow_bin),
+                                         out.ctypes.data_as(C.POINTER(_ffi.NoiseStat)))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("noise_from_hist: 1 .. 65536 value bins and 2 .. 65536 residual bins expected")
+    return out[0]
+
+
+def noise_weights(stats, channels: int, gain=None, include=None, weights=None, sigma_floor: float = 0.25, *, applied=None):
+    """stk_noise_weights: n float32 inverse-variance weights from an n x 4 NOISE_DTYPE array (Stacker.stack_noise). gain:
+    n x channels, the gains the combine will apply (None = 1), or `applied`: the records a weighted call returned; include:
+    per-frame flags (None = all; an excluded frame gets 0); weights: the caller's own per-frame factors (None = 1). Host code:
+    needs the library, not a GPU."""
+    ns = np.ascontiguousarray(np.asarray(stats, NOISE_DTYPE))
+    if ns.ndim != 2 or ns.shape[1] != 4:
+        raise InvalidParams("stats: an n x 4 array of NOISE_DTYPE expected")
+    n = ns.shape[0]
+    rec = None
+    if applied is not None:
+        gain = [list(a["gain"]) + [1.0] * (4 - len(a["gain"])) for a in applied]
+    if gain is not None:
+        g = np.asarray(gain, np.float32).reshape(n, -1)
+        rec = (_ffi.FrameWeight * max(n, 1))()
+        for i in range(n):
+            for c in range(4):
+                rec[i].gain[c] = float(g[i, c]) if c < g.shape[1] else 1.0
+            rec[i].weight = 1.0
+    inc = None if include is None else np.ascontiguousarray(np.asarray(include, np.int32).reshape(-1))
+    u = None if weights is None else np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+    if (inc is not None and inc.size != n) or (u is not None and u.size != n):
+        raise InvalidParams("one include flag and one weight per frame expected")
+    out = np.zeros(max(n, 1), np.float32)
+    st = _ffi.load().stk_noise_weights(ns.ctypes.data_as(C.POINTER(_ffi.NoiseStat)), n, int(channels), rec,
+                                       None if inc is None else C.c_void_p(inc.ctypes.data),
+                                       None if u is None else C.c_void_p(u.ctypes.data), float(sigma_floor), C.c_void_p(out.ctypes.data))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("noise_weights: sigma_floor must be finite and > 0, weights finite and >= 0, "
+                                                "sigmas and gains finite, one frame included")
+    return out[:n]
+
+
 def _quantile_c(q) -> _ffi.QuantileParams:
     """QuantileParameters, a bare float, or None (the median)."""
     if q is None:
@@ -1050,6 +1112,52 @@ class Stacker:
         [, stats]). A dropped frame is no sample: weight 0 in `applied`."""
         return self._match_weighted("keypoint", "_weighted", files, params, weight, weights, None, scale_down_width, return_stats,
                                     return_coverage, return_applied)
+
+    # -- noise estimation and inverse-variance weights (extension beyond the reference) ---------------
+    def stack_noise(self, files, return_hist: bool = False):
+        """The noise statistics of every frame and channel of a u8 or u16 stack in one device pass (stk_stack_noise): an
+        n x 4 NOISE_DTYPE array (the unused channel slots zeroed); with return_hist also the exact histograms, an
+        n x channels x (BV + BR) uint32 array: the values' (256 / 65 536 bins), then the capped residuals' (2041 / 65 536)."""
+        m = self._stack(files)
+        stats = np.zeros((m.n, 4), NOISE_DTYPE)
+        hist = np.zeros((m.n, m.c, (256 + 2041) if m.depth == 8 else 131072), np.uint32) if return_hist else None
+        self._check(self._lib.stk_stack_noise(self._h, C.byref(m.c_frames), stats.ctypes.data_as(C.POINTER(_ffi.NoiseStat)),
+                                              None if hist is None else C.c_void_p(hist.ctypes.data)))
+        return (stats, hist) if return_hist else stats
+
+    def _match_noise_weighted(self, kind, files, params, weight, weights, noise, scale_down_width, return_stats, return_coverage,
+                              return_applied, return_noise):
+        """The noise-weighted forms pass sigma_floor behind the weights and the statistics behind the stats."""
+        def noise_out(m, wanted):
+            if not wanted:
+                return None, None
+            ns = np.zeros((m.n, 4), NOISE_DTYPE)
+            return ns.ctypes.data_as(C.POINTER(_ffi.NoiseStat)), lambda stl: ns
+        combine = [(weight or WeightParameters())._c(), self._weights_combine(weights),
+                   lambda m: C.c_double((noise or NoiseParameters()).floor(m.depth))]
+        return self._whole_stack(kind, "_noise_weighted", files, params, scale_down_width, return_stats, combine,
+                                 [(return_coverage, self._out_plane(np.float32)), (return_applied, self._out_applied)],
+                                 after_stats=[(return_noise, noise_out)])
+
+    def ecc_match_noise_weighted(self, files, params: EccMatchParameters, weight: Optional["WeightParameters"] = None, weights=None,
+                                 noise: Optional["NoiseParameters"] = None, scale_down_width: Optional[float] = None,
+                                 return_stats: bool = False, return_coverage: bool = False, return_applied: bool = False,
+                                 return_noise: bool = False):
+        """ecc_match_weighted with every frame weighted by the inverse of its measured noise variance
+        (stk_ecc_match_noise_weighted): stack_noise, noise_weights under the gains of `weight`'s normalisation, one weighted
+        fold. weights: the caller's own per-frame factors. Returns the image, then as asked the coverage, the applied
+        records, the noise statistics (return_noise) and, last, the stats."""
+        return self._match_noise_weighted("ecc", files, params, weight, weights, noise, scale_down_width, return_stats, return_coverage,
+                                          return_applied, return_noise)
+
+    def keypoint_match_noise_weighted(self, files, params: KeyPointMatchParameters, weight: Optional["WeightParameters"] = None,
+                                      weights=None, noise: Optional["NoiseParameters"] = None, scale_down_width: Optional[float] = None,
+                                      return_stats: bool = False, return_coverage: bool = False, return_applied: bool = False,
+                                      return_noise: bool = False):
+        """keypoint_match_weighted with noise weights (stk_keypoint_match_noise_weighted): (dropped, image[, coverage]
+        [, applied][, noise][, stats]). A dropped frame is no sample: weight 0 in `applied`."""
+        return self._match_noise_weighted("keypoint", files, params, weight, weights, noise, scale_down_width, return_stats,
+                                          return_coverage, return_applied, return_noise)
 
     def weighted_stack(self, files, warps, gain=None, offset=None, weights=None, include=None, *, applied=None, coverage: bool = True,
                        is_affine=False, border_mode=BORDER_CONSTANT, border_value=(0, 0, 0, 0), alpha=1.0 / 255.0,

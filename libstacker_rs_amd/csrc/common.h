@@ -318,6 +318,13 @@ struct StarDetectArgs {
 int star_tiles(int w, int h);
 hipError_t launch_star_detect(const void* const* frames_dev, int n, int cn, int w, int h, size_t stride_bytes, int radius, float ks,
                               int min_contrast, int min_pixels, int32_t* counts, StarRecord* records, hipStream_t s);
+// the noise histograms of n 8- or 16-bit frames (cn 1, 3 or 4; frames_dev: a device array of n frame pointers) in one launch
+// (kernels_noise.hip; definition: include/stacker.h, stk_noise_stat); n <= 65535, w, h >= 3. hist: n x cn x
+// noise_hist_bins(depth) uint32, ZEROED by the caller on the same stream: per frame and channel the value histogram (256 /
+// 65 536 bins), then the residual histogram (2041 / 65 536 bins). origin: n x cn int32 of scratch (depth 16 only)
+size_t noise_hist_bins(int depth);
+hipError_t launch_noise_hist(const void* const* frames_dev, int n, int cn, int depth, int w, int h, size_t stride_bytes, uint32_t* hist,
+                             int32_t* origin, hipStream_t s);
 // frame calibration (kernels_calibrate.hip; definition: include/stacker.h, stk_calibration). One record per frame of the
 // launch; a master that is absent is a null pointer. Strides of the frames in bytes, of the masters in floats.
 constexpr int CAL_TW = 64, CAL_TH = 4;       // pixels per workgroup tile of calibrate_kernel

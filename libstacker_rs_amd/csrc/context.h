@@ -109,7 +109,8 @@ struct stk_ctx {
     DevBuf local;                 // LocalLayout, NormLayout or DrizzleLayout, one call at a time
     DevBuf mesh;                  // MeshLayout, then PyrLayout; the pyramid planes alone in stk_grey_pyramid
     DevBuf reject;                // RejectLayout
-    DevBuf quality;               // whole-stack sharpness (quality.cpp): frame pointers, per-frame records, tile partials
+    DevBuf quality;               // the whole-stack passes, one call at a time: sharpness (quality.cpp: frame pointers, per-frame records, tile
+                                  // partials) or noise (noise.cpp: frame pointers, window origins, one batch's histograms)
     stk::KeypointWorkspace* kp = nullptr;
     stk::geom::HgWorkspace* hg = nullptr;   // findHomography batch workspace (homography.cpp)
     stk::HostPool* host_pool = nullptr;
@@ -243,6 +244,10 @@ void weighted_estimate(const double* m /* cn x 6 */, int cn, int mode, stk_frame
 // frame index over the n frames (a dropped frame: weight 0, gains 1). Adds the pass's device time to *ms.
 stk_status weighted_match_records(stk_ctx* ctx, int n, const EntryTable& table, const FoldSpec& spec, const stk_weight_params* p,
                                   const float* weights, std::vector<stk_frame_weight>& coef, stk_frame_weight* applied, double* ms);
+// the weighted fold over the entries of ctx->warpframes under the per-entry records `coef` (weighted.cpp): writes out and
+// coverage_out (out's location), adds its device time to *ms
+stk_status weighted_fold_records(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage, stk_image_f32* out,
+                                 float* coverage_out, double* ms);
 // the pieces of the local-weighted combine (local.cpp) that the mesh folds (mesh.cpp) are built from
 stk_status local_validate(stk_ctx* ctx, const stk_local_params* p);
 stk_status local_check_border(stk_ctx* ctx, int border_mode, const double* border_value);

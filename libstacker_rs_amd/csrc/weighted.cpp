@@ -170,6 +170,12 @@ CombineFinish weighted_match_finish(stk_ctx* ctx, int n, const stk_weight_params
 
 }  // namespace
 
+// (the fold alone, for a whole-stack form outside this file that makes its own records: noise.cpp)
+stk_status weighted_fold_records(stk_ctx* ctx, const std::vector<stk_frame_weight>& coef, const FoldSpec& spec, int coverage, stk_image_f32* out,
+                                 float* coverage_out, double* ms) {
+    return weighted_fold(ctx, coef, spec, coverage, out, coverage_out, ms);
+}
+
 extern "C" {
 
 stk_status stk_weighted_stack(stk_ctx* ctx, const stk_frames* frames, const double* M, const int32_t* include, int32_t is_affine,
