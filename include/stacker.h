@@ -1808,6 +1808,30 @@ stk_status stk_find_homography(stk_ctx* ctx, const float* src_pts, const float* 
                                int32_t method, double ransac_reproj_threshold, double* H,
                                uint8_t* inlier_mask_or_null, int32_t* found);
 
+/* stk_find_homography for `count` independent problems in one call: the batch the keypoint path and star registration
+ * hand to the engine (every round's models of every problem in one launch, every problem's refinement in one launch).
+ * Problem i of a batch returns the bits that problem returns alone. Host pointers; points are n x 2 float pairs. */
+typedef struct {
+    const float* src_pts;
+    const float* dst_pts;
+    int32_t n;
+    uint8_t* inlier_mask_or_null;   /* n bytes: 1 inlier, 0 outlier; all 0 when nothing is found or rc != 0 */
+} stk_hg_problem;
+typedef struct {
+    int32_t rc;                     /* 0: see found; 3: arguments findHomography rejects (n < 4, unknown method); 7: RHO */
+    int32_t found;                  /* 0 when OpenCV would return an empty Mat */
+    double  H[9];                   /* row-major, H[8] == 1 when found, else zeros */
+    int32_t n_inliers;              /* points the final fit ran over (0 when nothing is found) */
+    int32_t models_evaluated;       /* 4-point models scored for this problem: 0 for method 0, n == 4 and a problem
+                                     * without an admissible sample. RANSAC: up to the end of the round (32, 288, 2000
+                                     * models) in which its adaptive iteration count was reached; LMEDS: its fixed count */
+} stk_hg_outcome;
+/* Per-problem errors are reported in outcomes[i].rc and do not fail the call. count <= 0: STK_OK, nothing written. A null
+ * problems or outcomes, or a problem with n > 0 and a null point list: STK_INVALID_PARAMS. A problem of more than 4096
+ * points: STK_NOT_IMPLEMENTED for the whole call. ransac_reproj_threshold <= 0 means 3, as in findHomography. */
+stk_status stk_find_homography_batch(stk_ctx* ctx, const stk_hg_problem* problems, int32_t count, int32_t method,
+                                     double ransac_reproj_threshold, stk_hg_outcome* outcomes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,15 @@ class NoiseStat(C.Structure):
                 ("sigma", C.c_double), ("kept", C.c_int64)]
 
 
+class HgProblem(C.Structure):
+    _fields_ = [("src_pts", C.c_void_p), ("dst_pts", C.c_void_p), ("n", C.c_int32), ("inlier_mask_or_null", C.c_void_p)]
+
+
+class HgOutcome(C.Structure):
+    _fields_ = [("rc", C.c_int32), ("found", C.c_int32), ("H", C.c_double * 9), ("n_inliers", C.c_int32),
+                ("models_evaluated", C.c_int32)]
+
+
 class Calibration(C.Structure):
     _fields_ = [("bias_or_null", C.POINTER(ImageF32)), ("dark_or_null", C.POINTER(ImageF32)), ("flat_or_null", C.POINTER(ImageF32)),
                 ("dark_scale_or_null", C.c_void_p), ("flat_mean", C.c_float * 4), ("flat_min", C.c_float), ("pedestal", C.c_float),
@@ -393,6 +402,8 @@ SIGNATURES = {
     "stk_bf_knn2_hamming": (c_status, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "stk_find_homography": (c_status, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double,
                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "stk_find_homography_batch": (c_status, [C.c_void_p, C.POINTER(HgProblem), C.c_int32, C.c_int32, C.c_double,
+                                             C.POINTER(HgOutcome)]),
 }
 
 _lib = None

@@ -2356,6 +2356,27 @@ class Stacker:
         self._check(st)
         return (H.reshape(3, 3) if found.value else None), mask
 
+    def find_homography_batch(self, problems, method: int = RANSAC, ransac_reproj_threshold: float = 3.0):
+        """find_homography for a list of (src, dst) point pairs in one call. One dict per problem: H (3x3 f64, or None when
+        nothing is found or rc != 0), mask (n x uint8), rc (0, or 3 / 7 as findHomography would throw: the call itself does
+        not raise for them), n_inliers, models_evaluated. Problem i returns the bits it returns alone."""
+        pairs = [(np.ascontiguousarray(s, np.float32).reshape(-1, 2), np.ascontiguousarray(d, np.float32).reshape(-1, 2))
+                 for s, d in problems]
+        if not pairs:
+            return []
+        for s, d in pairs:
+            if s.shape != d.shape:
+                raise InvalidParams("find_homography_batch: src and dst of a problem differ in length")
+        masks = [np.zeros(s.shape[0], np.uint8) for s, _ in pairs]
+        probs = (_ffi.HgProblem * len(pairs))()
+        for p, (s, d), m in zip(probs, pairs, masks):
+            p.src_pts, p.dst_pts, p.n, p.inlier_mask_or_null = s.ctypes.data, d.ctypes.data, s.shape[0], m.ctypes.data
+        outc = (_ffi.HgOutcome * len(pairs))()
+        st = self._lib.stk_find_homography_batch(self._h, probs, len(pairs), int(method), float(ransac_reproj_threshold), outc)
+        self._check(st)
+        return [dict(H=np.array(o.H, np.float64).reshape(3, 3) if o.rc == 0 and o.found else None, mask=m, rc=int(o.rc),
+                     n_inliers=int(o.n_inliers), models_evaluated=int(o.models_evaluated)) for o, m in zip(outc, masks)]
+
 
 _default: dict[int, Stacker] = {}
 

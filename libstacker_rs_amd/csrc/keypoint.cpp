@@ -508,6 +508,30 @@ stk_status stk_find_homography(stk_ctx* ctx, const float* src_pts, const float* 
     return STK_OK;
 }
 
+stk_status stk_find_homography_batch(stk_ctx* ctx, const stk_hg_problem* problems, int32_t count, int32_t method, double thr,
+                                     stk_hg_outcome* outcomes) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    if (count <= 0) return STK_OK;
+    if (!problems || !outcomes) return fail(ctx, STK_INVALID_PARAMS, "bad arguments");
+    std::vector<geom::HgProblem> probs((size_t)count);
+    for (int i = 0; i < count; i++) {
+        const stk_hg_problem& p = problems[i];
+        if (p.n > 0 && (!p.src_pts || !p.dst_pts)) return fail(ctx, STK_INVALID_PARAMS, "bad arguments");
+        probs[i] = geom::HgProblem{p.src_pts, p.dst_pts, p.n, p.inlier_mask_or_null};
+    }
+    (void)hipSetDevice(ctx->device);
+    std::vector<geom::HgOutcome> outc((size_t)count);
+    const int st = geom::find_homography_batch(ctx, ctx->stream, ctx->hg, probs.data(), count, method, thr, outc.data());
+    if (st) return (stk_status)st;
+    for (int i = 0; i < count; i++) {
+        const geom::HgOutcome& o = outc[i];
+        stk_hg_outcome& r = outcomes[i];
+        r.rc = o.rc; r.found = o.found; r.n_inliers = o.n_inliers; r.models_evaluated = o.models_evaluated;
+        for (int k = 0; k < 9; k++) r.H[k] = o.H[k];
+    }
+    return STK_OK;
+}
+
 }  // extern "C"
 
 stk_status keypoint_align_impl(stk_ctx* ctx, const stk_frames* frames, const stk_keypoint_params* params, float scale_down_width,

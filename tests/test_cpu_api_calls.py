@@ -47,6 +47,7 @@ EXEMPT = {
 P_FRAMES, P_IMAGE, P_I32 = C.POINTER(_ffi.Frames), C.POINTER(_ffi.ImageF32), C.POINTER(C.c_int32)
 P_STATS, P_WEIGHT, P_GEO, P_CAL = (C.POINTER(_ffi.FrameStats), C.POINTER(_ffi.FrameWeight), C.POINTER(_ffi.FrameGeometry),
                                    C.POINTER(_ffi.Calibration))
+P_HG, P_HGOUT = C.POINTER(_ffi.HgProblem), C.POINTER(_ffi.HgOutcome)
 SEEN = set()
 
 
@@ -57,10 +58,10 @@ def _bytes_of(s):
 class Recorder:
     """The stand-in for libstacker_amd.so. reads: {argument index: nbytes | ("tbl", count, nbytes per entry)} to snapshot
     behind void pointers; pokes: {argument index: int or list} written through int32 pointers; status: {frame: status}
-    written into the stats."""
+    written into the stats; outcomes: [(rc, found, H, n_inliers, models_evaluated)] written into stk_hg_outcome records."""
 
     def __init__(self):
-        self.calls, self.reads, self.pokes, self.status = [], {}, {}, {}
+        self.calls, self.reads, self.pokes, self.status, self.outcomes = [], {}, {}, {}, []
         real = _ffi.load()
         for name, (res, argtypes) in _ffi.SIGNATURES.items():
             if name in HOST_FUNCS:
@@ -118,6 +119,14 @@ class Recorder:
                 out.append(dict(imgs, dark_scale=None if not scale else bytes(C.string_at(scale, 4 * n)), flat_mean=list(c.flat_mean), flat_min=c.flat_min,
                                 pedestal=c.pedestal, defects=c.defects_or_null, defects_location=c.defects_location,
                                 defect_step=c.defect_step, out_depth=c.out_depth))
+            elif t is P_HG:                                      # `count` problems: the count is the next argument
+                out.append([dict(n=a[k].n, src=bytes(C.string_at(a[k].src_pts, 8 * a[k].n)), dst=bytes(C.string_at(a[k].dst_pts, 8 * a[k].n)),
+                                 mask=a[k].inlier_mask_or_null) for k in range(args[i + 1])])
+            elif t is P_HGOUT:
+                for k, (rc, found, Hm, n_in, n_ev) in enumerate(self.outcomes):
+                    a[k].rc, a[k].found, a[k].n_inliers, a[k].models_evaluated = rc, found, n_in, n_ev
+                    a[k].H[:] = list(Hm)
+                out.append(C.addressof(a.contents) if a else None)
             elif isinstance(t, type) and issubclass(t, C._Pointer):
                 out.append(_bytes_of(a.contents) if a else None)
             elif t is C.c_void_p and i in self.reads and a:
@@ -1030,6 +1039,37 @@ def test_hybrid_mixed_and_warp_accumulate():
               [("frames", GREY[1:2]), ("buf", WARPS9[2]), ("val", 0), ("val", 0), ("buf", np.zeros(4)), ("val", 1.0 / 255.0), ("val", 1),
                ("img", first, (H, W, 1))], GREY[1], WARPS[2], acc=acc)
     assert res is acc
+
+
+def test_find_homography_batch():
+    """[ctx, problems, count, method, threshold, outcomes]: every problem's points as contiguous f32 pairs whatever the caller
+    gave, one mask of n bytes per problem whose address is the returned array's, and the result built from the records."""
+    src = [_rng.random((5, 2)), _rng.random((3, 2)).astype(np.float32), _rng.random((2 * 7, 2))[::2].tolist()]
+    dst = [_rng.random((5, 2)), _rng.random(6).astype(np.float32), _rng.random((7, 2)).astype(np.float32)]
+    Hm = np.arange(9.0) + 0.5
+    st = new_stacker()
+    st._lib.outcomes = [(0, 1, Hm, 4, 32), (3, 0, np.zeros(9), 0, 0), (0, 0, np.zeros(9), 0, 288)]
+    res = st.find_homography_batch(list(zip(src, dst)), 4, 2)
+    name, snap = st._lib.last()
+    assert name == "stk_find_homography_batch" and len(st._lib.calls) == 1
+    assert snap[0] == CTX and snap[2:5] == [3, 4, 2.0] and type(snap[4]) is float and snap[5] is not None
+    for got, s, d, r in zip(snap[1], src, dst, res):
+        want_s, want_d = np.asarray(s, np.float32).reshape(-1, 2), np.asarray(d, np.float32).reshape(-1, 2)
+        assert got["n"] == len(want_s) and got["src"] == want_s.tobytes() and got["dst"] == want_d.tobytes()
+        assert r["mask"].dtype == np.uint8 and r["mask"].shape == (len(want_s),) and got["mask"] == addr(r["mask"])
+        assert set(r) == {"H", "mask", "rc", "n_inliers", "models_evaluated"}
+    assert res[0]["H"].dtype == np.float64 and res[0]["H"].shape == (3, 3) and res[0]["H"].ravel().tolist() == Hm.tolist()
+    assert (res[0]["rc"], res[0]["n_inliers"], res[0]["models_evaluated"]) == (0, 4, 32)
+    assert res[1]["H"] is None and res[1]["rc"] == 3                        # an argument error of one problem: no exception
+    assert res[2]["H"] is None and (res[2]["rc"], res[2]["models_evaluated"]) == (0, 288)
+    st = new_stacker()                                                     # the defaults: RANSAC, 3.0
+    st.find_homography_batch([(src[0], dst[0])])
+    assert st._lib.last()[1][2:5] == [1, RANSAC, 3.0]
+    st = new_stacker()                                                     # before any C call
+    assert st.find_homography_batch([]) == []
+    with pytest.raises(InvalidParams, match="^find_homography_batch: src and dst of a problem differ in length$"):
+        st.find_homography_batch([(src[0], dst[0]), (src[1], dst[2])])
+    assert not st._lib.calls
 
 
 def test_every_name_that_takes_frames_is_driven_or_exempt():

@@ -46,6 +46,27 @@ def test_struct_layouts_match_the_header():
     assert C.sizeof(_ffi.Timing) == 16 * 8
 
 
+def test_homography_batch_records_match_the_header(tmp_path):
+    """stk_hg_problem / stk_hg_outcome: size and every offset as a C compiler lays the header's structs out, and the new
+    call's argument count against its declaration."""
+    layouts = {"stk_hg_problem": _ffi.HgProblem, "stk_hg_outcome": _ffi.HgOutcome}
+    body = "".join('  printf("%%zu ", sizeof(%s));\n' % n + "".join('  printf("%%zu ", offsetof(%s, %s));\n' % (n, f) for f, _ in t._fields_)
+                   for n, t in layouts.items())
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "stacker.h"\nint main(void) {\n' + body + "  return 0;\n}\n")
+    exe = str(tmp_path / "sizes")
+    subprocess.run(["cc", "-std=c99", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
+    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    want = [v for t in layouts.values() for v in [C.sizeof(t)] + [getattr(t, f).offset for f, _ in t._fields_]]
+    assert got == want
+    assert C.sizeof(_ffi.HgProblem) == 32 and C.sizeof(_ffi.HgOutcome) == 88      # the driver's HgOutcome: 2 + 2 int32 around 9 doubles
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "stacker.h")).read(), flags=re.S)
+    args = re.search(r"\bstk_find_homography_batch\s*\(([^;]*)\)\s*;", hdr).group(1)
+    res, sig = _ffi.SIGNATURES["stk_find_homography_batch"]
+    assert res is _ffi.c_status and len(args.split(",")) == len(sig) and sig[2] is C.c_int32 and sig[4] is C.c_double
+    assert hasattr(_ffi.load(), "stk_find_homography_batch")
+
+
 def test_no_gpu_fails_loudly_not_silently():
     import torch
     if torch.cuda.is_available():

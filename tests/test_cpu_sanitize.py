@@ -193,6 +193,19 @@ def test_ransac_host_half_under_asan_ubsan(tmp_path):
     assert [int(x) for x in r.stdout.split()[2:4]] == exp
 
 
+@pytest.mark.timeout(600)
+def test_homography_batch_driver_under_asan_ubsan(tmp_path):
+    """find_homography_batch end to end (homography.cpp: admission, the pinned staging layout, the rounds, the replay, the
+    refinement jobs) over random mixed batches, with scalar stand-ins for the two launches that read and write through the
+    offsets the driver hands them: the driver's decisions equal the textbook sequential loop's, problem i of a batch equals
+    that problem alone, and nothing leaves a buffer."""
+    exe = str(tmp_path / "hg_batch")
+    _build("hg_batch_harness.cpp", exe, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=500)
+    assert r.returncode == 0 and r.stdout.startswith("ok"), r.stdout[-1500:] + r.stderr[-3000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
 @pytest.mark.timeout(900)
 def test_oracle_under_asan_ubsan(tmp_path):
     """`make -C oracle asan` and the oracle's own CPU test file run against that build (LD_PRELOAD of libasan, the

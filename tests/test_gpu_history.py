@@ -193,16 +193,25 @@ def _grey(k, w, h):
     return _memo(("grey", k, w, h), lambda: np.ascontiguousarray(_stack(2, w, h, bright=bool(k))[1].float().mean(-1).round().byte().cpu().numpy()))
 
 
-def _points(n, seed):
-    """Point pairs under a homography: a tenth of them outliers, the rest with a little noise."""
+def _points(n, seed, outliers=None):
+    """Point pairs under a homography: a tenth of them (or the fraction `outliers`) outliers, the rest with a little noise."""
     rng = np.random.default_rng(seed)
     src = rng.uniform(0, 600, (n, 2))
     H = np.array([[1.01, 0.02, 3.0], [-0.015, 0.99, -2.0], [1e-5, -2e-5, 1.0]])
     p = np.concatenate([src, np.ones((n, 1))], 1) @ H.T
     dst = p[:, :2] / p[:, 2:] + rng.normal(0, 0.3, (n, 2))
-    bad = rng.choice(n, n // 10, replace=False)
+    bad = rng.choice(n, n // 10 if outliers is None else int(outliers * n), replace=False)
     dst[bad] = rng.uniform(0, 600, (len(bad), 2))
     return src.astype(np.float32), dst.astype(np.float32)
+
+
+def _point_batch(k, seed):
+    """A batch for find_homography_batch whose members end in different rounds (10 %, 50 % and 70 % of outliers), with a
+    member that never reaches the device (3 points) and one that needs no round (4 points) between them; the neighbour's
+    batch is larger in every buffer."""
+    plan = ([(3, 0.0), (129, 0.7), (40, 0.1), (4, 0.0), (65, 0.5), (300, 0.1), (64, 0.7)],
+            [(500, 0.7), (5, 0.0), (200, 0.5), (700, 0.1), (3, 0.0), (100, 0.7), (90, 0.5), (33, 0.1), (260, 0.7)])[k]
+    return [_points(n, seed + 10 * i, f) for i, (n, f) in enumerate(plan)]
 
 
 # ---- the catalogue ------------------------------------------------------------------------------------------------------
@@ -386,6 +395,18 @@ def _(k):
 def _(k):
     s, d = _points((200, 350)[k], 62 + k)
     return lambda st: st.find_homography(s, d, LMEDS, 3.0)
+
+
+@case("find_homography_batch RANSAC")
+def _(k):
+    batch = _point_batch(k, 600 + k)
+    return lambda st: st.find_homography_batch(batch, RANSAC, 3.0)
+
+
+@case("find_homography_batch LMEDS")
+def _(k):
+    batch = _point_batch(k, 640 + k)
+    return lambda st: st.find_homography_batch(batch, LMEDS, 3.0)
 
 
 # star registration -------------------------------------------------------------------------------------------------------
