@@ -7,7 +7,10 @@
 //                      (one wave per row of 64 pixels, four frames in flight)
 //   linear, generic -> warp_accumulate_kernel<T, CN, true, State<CN>>
 // with (T, CN) from the one ladder (dispatch_depth_cn, warp_body.h). `rows`: the destination rows of the launch — a.dh for
-// a whole-image pass, c.band_rows for a store launch (whose kernels start at c.y0).
+// a whole-image pass, c.band_rows for a store launch (whose states declare in_band: their kernels start at c.y0).
+// What a kernel does for a state follows from the state's traits (FoldTraits, warp_body.h), not from this launcher. That
+// the fast kernels never run FoldNorm / FoldStoreNorm is a property of the launchers (kernels_local_norm.hip launches the
+// generic kernels itself; those states have no add2 / add3k, so naming them here would not compile), not of the traits.
 #pragma once
 #include "warp_cubic_body.h"
 

@@ -1,6 +1,7 @@
 // kernels_clip.hip — kappa-sigma clipping over the aligned frames (stk_clip_stack and the *_clipped entry points).
-// One pass is one more fold of the same frames: the fold kernels of warp_body.h in their clip mode, the sample of every
-// frame computed by the very instructions the mean fold adds. Per pixel and channel a pass keeps the moments of the
+// One pass is one more fold of the same frames: the fold kernels with a clip state (the table of states is at the top of
+// warp_body.h; this file ends with that table as static_asserts), the sample of every frame computed by the very
+// instructions the mean fold adds. Per pixel and channel a pass keeps the moments of the
 // samples inside [L, U] about the previous centre c (k, a = sum d, b = sum d^2 with d = s - c), and its epilogue turns them
 // into the next (c, L, U) — or, on the last pass, into the clipped mean and the count of kept samples. Definition (bit for
 // bit, f32, no contraction: the Makefile's -ffp-contract=off; `/` and sqrt are the correctly rounded forms):
@@ -37,21 +38,48 @@ __device__ __forceinline__ void clip_end(const ClipArgs& ca, size_t p, size_t o,
     ca.c[p] = c; ca.L[p] = L; ca.U[p] = U;
 }
 
-// generic kernel's state: CN channels, indexed by the (unrolled) channel loop
+// The prologue of every pass, for the generic kernels' states (CN channels, indexed by the unrolled channel loop): c / L / U
+// of the pixel from their planes. A first pass opens the interval; so does the weighted clip's centre pass, which also
+// starts from c = 0 (`centre` = ClipArgs::centre there, 0 in the plain clip, which has no such pass). Returns the plane index.
 template <int CN>
-struct ClipGeneric {
+__device__ __forceinline__ size_t clip_load(const ClipArgs& ca, int x, int y, int centre, float* c, float* L, float* U) {
+    const size_t p = (size_t)y * ca.plane_stride + (size_t)x * CN;
+    const bool open = ca.first | centre;
+#pragma unroll
+    for (int i = 0; i < CN; i++) {
+        c[i] = centre ? 0.0f : ca.c[p + i];
+        L[i] = open ? -__builtin_inff() : ca.L[p + i];
+        U[i] = open ? __builtin_inff() : ca.U[p + i];
+    }
+    return p;
+}
+
+// the same for the u8 BGR fast kernels' states: (B, G) as register pairs, R apart
+__device__ __forceinline__ size_t clip_load_u8c3(const ClipArgs& ca, int x, int y, int centre, f32x2& c01, f32x2& L01, f32x2& U01,
+                                                 float& c2, float& L2, float& U2) {
+    const size_t p = (size_t)y * ca.plane_stride + (size_t)x * 3;
+    if (centre) { c01 = f32x2{0.f, 0.f}; c2 = 0.f; }
+    else { c01 = f32x2{ca.c[p], ca.c[p + 1]}; c2 = ca.c[p + 2]; }
+    if (ca.first | centre) {
+        L01 = f32x2{-__builtin_inff(), -__builtin_inff()}; L2 = -__builtin_inff();
+        U01 = f32x2{__builtin_inff(), __builtin_inff()}; U2 = __builtin_inff();
+    } else {
+        L01 = f32x2{ca.L[p], ca.L[p + 1]}; L2 = ca.L[p + 2];
+        U01 = f32x2{ca.U[p], ca.U[p + 1]}; U2 = ca.U[p + 2];
+    }
+    return p;
+}
+
+// generic kernel's state
+template <int CN>
+struct ClipGeneric : FoldTraits {
     float c[CN], L[CN], U[CN], a[CN], b[CN];
     int k[CN];
     size_t p;
     __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
-        p = (size_t)y * ca.plane_stride + (size_t)x * CN;
+        p = clip_load<CN>(ca, x, y, 0, c, L, U);
 #pragma unroll
-        for (int i = 0; i < CN; i++) {
-            c[i] = ca.c[p + i];
-            L[i] = ca.first ? -__builtin_inff() : ca.L[p + i];
-            U[i] = ca.first ? __builtin_inff() : ca.U[p + i];
-            a[i] = 0.f; b[i] = 0.f; k[i] = 0;
-        }
+        for (int i = 0; i < CN; i++) { a[i] = 0.f; b[i] = 0.f; k[i] = 0; }
     }
     __device__ __forceinline__ void add(int i, float s) {
         const float d = s - c[i];
@@ -67,22 +95,14 @@ struct ClipGeneric {
     }
 };
 
-// u8 BGR fast kernel's state: (B, G) as register pairs (v_pk_add / v_pk_mul for the moments), R apart
-struct ClipU8C3 {
+// u8 BGR fast kernel's state: v_pk_add / v_pk_mul for the moments of (B, G)
+struct ClipU8C3 : FoldTraits {
     f32x2 c01, L01, U01, a01, b01;
     float c2, L2, U2, a2, b2;
     int k0, k1, k2;
     size_t p;
     __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
-        p = (size_t)y * ca.plane_stride + (size_t)x * 3;
-        c01 = f32x2{ca.c[p], ca.c[p + 1]}; c2 = ca.c[p + 2];
-        if (ca.first) {
-            L01 = f32x2{-__builtin_inff(), -__builtin_inff()}; L2 = -__builtin_inff();
-            U01 = f32x2{__builtin_inff(), __builtin_inff()}; U2 = __builtin_inff();
-        } else {
-            L01 = f32x2{ca.L[p], ca.L[p + 1]}; L2 = ca.L[p + 2];
-            U01 = f32x2{ca.U[p], ca.U[p + 1]}; U2 = ca.U[p + 2];
-        }
+        p = clip_load_u8c3(ca, x, y, 0, c01, L01, U01, c2, L2, U2);
         a01 = f32x2{0.f, 0.f}; b01 = f32x2{0.f, 0.f}; a2 = 0.f; b2 = 0.f;
         k0 = k1 = k2 = 0;
     }
@@ -146,30 +166,27 @@ __device__ __forceinline__ void clip_end_w(const ClipArgs& ca, size_t p, size_t 
     ca.c[p] = c; ca.L[p] = L; ca.U[p] = U;
 }
 
-template <int CN>
-struct ClipWGeneric {
+// Written once over the coefficient source Src (warp_body.h): the records, or the local-normalisation planes below.
+template <int CN, class Src>
+struct ClipW : FoldTraits {
+    static constexpr bool wants_kappa = true;
     float c[CN], L[CN], U[CN], a[CN], b[CN], sw[CN];
     int k[CN];
     size_t p;
-    const stk_frame_weight* e;
+    Src src;
     int cov;
     bool part, centre;
     __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
-        p = (size_t)y * ca.plane_stride + (size_t)x * CN;
-        const bool open = ca.first | ca.centre;
+        p = clip_load<CN>(ca, x, y, ca.centre, c, L, U);
 #pragma unroll
-        for (int i = 0; i < CN; i++) {
-            c[i] = ca.centre ? 0.0f : ca.c[p + i];
-            L[i] = open ? -__builtin_inff() : ca.L[p + i];
-            U[i] = open ? __builtin_inff() : ca.U[p + i];
-            a[i] = 0.f; b[i] = 0.f; sw[i] = 0.f; k[i] = 0;
-        }
-        e = ca.coef; cov = ca.coverage; centre = ca.centre != 0; part = true;
+        for (int i = 0; i < CN; i++) { a[i] = 0.f; b[i] = 0.f; sw[i] = 0.f; k[i] = 0; }
+        cov = ca.coverage; centre = ca.centre != 0; part = true; src.begin(ca, x, y);
     }
-    __device__ __forceinline__ void entry(float kap) { part = (e->weight > 0.0f) & (cov ? kap == 1.0f : true); }
+    __device__ __forceinline__ void entry(float kap) { part = (src.weight() > 0.0f) & (cov ? kap == 1.0f : true); }
     __device__ __forceinline__ void add(int i, float s) {
-        const float w = e->weight;
-        const float u = s * e->gain[i] + e->offset[i];
+        const float w = src.weight();
+        const auto g = src.coef(i);
+        const float u = s * g.g + g.o;
         const float d = u - c[i];
         const bool in = part & (centre | clip_in(u, L[i], U[i]));
         // a sample that is out adds w = 0 times d = 0: +0 to each sum, whatever u is (two selects instead of three)
@@ -178,7 +195,7 @@ struct ClipWGeneric {
         sw[i] = sw[i] + wi;
         a[i] = a[i] + wi * di;
         b[i] = b[i] + wi * (di * di);
-        if (i == CN - 1) e++;
+        if (i == CN - 1) src.next();
     }
     __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
         const size_t o = (size_t)y * ca.out_stride + (size_t)x * CN;
@@ -187,34 +204,28 @@ struct ClipWGeneric {
     }
 };
 
-// u8 BGR fast kernel's state: (B, G) as register pairs, R apart. add2 is the interior path (kappa = 1: the entry
-// participates iff w > 0), add3k the rim path with its kappa.
-struct ClipWU8C3 {
+// u8 BGR fast kernels' state: (B, G) as register pairs, R apart. add2 is the interior path (kappa = 1: the entry
+// participates iff w > 0), add3k the rim path with its kappa. Src hands over the entry's six coefficients at once (coef3).
+template <class Src>
+struct ClipWFast : FoldTraits {
+    static constexpr bool wants_kappa = true;
     f32x2 c01, L01, U01, a01, b01, sw01;
     float c2, L2, U2, a2, b2, sw2;
     int k0, k1, k2;
     size_t p;
-    const stk_frame_weight* e;
+    Src src;
     int cov;
     bool centre;
     __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
-        p = (size_t)y * ca.plane_stride + (size_t)x * 3;
-        if (ca.centre) { c01 = f32x2{0.f, 0.f}; c2 = 0.f; }
-        else { c01 = f32x2{ca.c[p], ca.c[p + 1]}; c2 = ca.c[p + 2]; }
-        if (ca.first | ca.centre) {
-            L01 = f32x2{-__builtin_inff(), -__builtin_inff()}; L2 = -__builtin_inff();
-            U01 = f32x2{__builtin_inff(), __builtin_inff()}; U2 = __builtin_inff();
-        } else {
-            L01 = f32x2{ca.L[p], ca.L[p + 1]}; L2 = ca.L[p + 2];
-            U01 = f32x2{ca.U[p], ca.U[p + 1]}; U2 = ca.U[p + 2];
-        }
+        p = clip_load_u8c3(ca, x, y, ca.centre, c01, L01, U01, c2, L2, U2);
         a01 = f32x2{0.f, 0.f}; b01 = f32x2{0.f, 0.f}; sw01 = f32x2{0.f, 0.f}; a2 = 0.f; b2 = 0.f; sw2 = 0.f;
         k0 = k1 = k2 = 0;
-        e = ca.coef; cov = ca.coverage; centre = ca.centre != 0;
+        cov = ca.coverage; centre = ca.centre != 0; src.begin(ca, x, y);
     }
     __device__ __forceinline__ void fold(f32x2 s01, float s2, bool part) {
-        const float w = e->weight;
-        const f32x2 u01 = s01 * f32x2{e->gain[0], e->gain[1]} + f32x2{e->offset[0], e->offset[1]};
+        const float w = src.weight();
+        const auto q = src.coef3();
+        const f32x2 u01 = s01 * f32x2{q.g0, q.g1} + f32x2{q.o0, q.o1};
         const f32x2 d = u01 - c01;
         const bool i0 = part & (centre | clip_in(u01.x, L01.x, U01.x)), i1 = part & (centre | clip_in(u01.y, L01.y, U01.y));
         // a sample that is out adds w = 0 times d = 0: +0 to each sum, whatever u is (two selects per channel instead of
@@ -224,7 +235,7 @@ struct ClipWU8C3 {
         sw01 = sw01 + wi;
         a01 = a01 + wi * di;
         b01 = b01 + wi * (di * di);
-        const float u2 = s2 * e->gain[2] + e->offset[2];
+        const float u2 = s2 * q.g2 + q.o2;
         const float d2 = u2 - c2;
         const bool i2 = part & (centre | clip_in(u2, L2, U2));
         const float w2 = i2 ? w : 0.0f, dd2 = i2 ? d2 : 0.0f;
@@ -232,11 +243,11 @@ struct ClipWU8C3 {
         sw2 = sw2 + w2;
         a2 = a2 + w2 * dd2;
         b2 = b2 + w2 * (dd2 * dd2);
-        e++;
+        src.next();
     }
-    __device__ __forceinline__ void add2(f32x2 s01, float s2) { fold(s01, s2, e->weight > 0.0f); }
+    __device__ __forceinline__ void add2(f32x2 s01, float s2) { fold(s01, s2, src.weight() > 0.0f); }
     __device__ __forceinline__ void add3k(float s0, float s1, float s2, float kap) {
-        fold(f32x2{s0, s1}, s2, (e->weight > 0.0f) & (cov ? kap == 1.0f : true));
+        fold(f32x2{s0, s1}, s2, (src.weight() > 0.0f) & (cov ? kap == 1.0f : true));
     }
     __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
         const size_t o = (size_t)y * ca.out_stride + (size_t)x * 3;
@@ -246,6 +257,9 @@ struct ClipWU8C3 {
     }
 };
 
+template <int CN> struct ClipWGeneric : ClipW<CN, FromRecord<PlainTables>> {};
+struct ClipWU8C3 : ClipWFast<FromRecord<PlainTables>> {};
+
 hipError_t launch_clip_pass_weighted(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
     if (a.n_frames <= 0 || !c.coef) return hipErrorInvalidValue;
     return launch_fold<ClipWU8C3, ClipWGeneric>(a, c, depth, a.dh, s);
@@ -253,55 +267,11 @@ hipError_t launch_clip_pass_weighted(const WarpArgs& a, const ClipArgs& c, int d
 
 // ---- the weighted clip through local-normalisation planes (stk_clip_stack_local_norm, stk_robust_clip_stack_local_norm
 // and the *_local_normalized_clipped entry points; definition in include/stacker.h, "Locally normalised clip") ------------
-// The weighted clip's states with u = s * G + O, (G, O) the entry's plane at the destination pixel (NormAt, warp_body.h,
-// as FoldNorm reads it), or the record's gain and offset where the entry has no plane. The plane pointer table moves with
-// the record pointer; the epilogue is clip_end_w.
-template <int CN>
-struct ClipNorm {
-    float c[CN], L[CN], U[CN], a[CN], b[CN], sw[CN];
-    int k[CN];
-    size_t p;
-    const stk_frame_weight* e;
-    const float* const* np;
-    NormAt at;
-    int cov;
-    bool part, centre;
-    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
-        p = (size_t)y * ca.plane_stride + (size_t)x * CN;
-        const bool open = ca.first | ca.centre;
-#pragma unroll
-        for (int i = 0; i < CN; i++) {
-            c[i] = ca.centre ? 0.0f : ca.c[p + i];
-            L[i] = open ? -__builtin_inff() : ca.L[p + i];
-            U[i] = open ? __builtin_inff() : ca.U[p + i];
-            a[i] = 0.f; b[i] = 0.f; sw[i] = 0.f; k[i] = 0;
-        }
-        e = ca.coef; np = ca.norm; cov = ca.coverage; centre = ca.centre != 0; part = true;
-        at.set(ca, x, y, 2 * CN);
-    }
-    __device__ __forceinline__ void entry(float kap) { part = (e->weight > 0.0f) & (cov ? kap == 1.0f : true); }
-    __device__ __forceinline__ void add(int i, float s) {
-        const float w = e->weight;
-        const float* __restrict__ P = *np;
-        const float G = P ? at.at(P, i) : e->gain[i], O = P ? at.at(P, CN + i) : e->offset[i];
-        const float u = s * G + O;
-        const float d = u - c[i];
-        const bool in = part & (centre | clip_in(u, L[i], U[i]));
-        const float wi = in ? w : 0.0f, di = in ? d : 0.0f;       // (as ClipWGeneric: a sample that is out adds +0)
-        k[i] += in ? 1 : 0;
-        sw[i] = sw[i] + wi;
-        a[i] = a[i] + wi * di;
-        b[i] = b[i] + wi * (di * di);
-        if (i == CN - 1) { e++; np++; }
-    }
-    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
-        const size_t o = (size_t)y * ca.out_stride + (size_t)x * CN;
-#pragma unroll
-        for (int i = 0; i < CN; i++) clip_end_w(ca, p + i, o + i, c[i], L[i], U[i], k[i], sw[i], a[i], b[i]);
-    }
-};
+// The weighted clip's states over the plane source: u = s * G + O, (G, O) the entry's plane at the destination pixel, or
+// the record's gain and offset where the entry has no plane (FromPlane, warp_body.h, as FoldNorm reads it).
+template <int CN> struct ClipNorm : ClipW<CN, FromPlane<PlainTables, CN>> {};
 
-// u8 BGR fast kernels' state: ClipWU8C3 with the six chains (three gains, three offsets) per entry. The first fast-kernel
+// The plane source of the u8 BGR fast kernels: six chains (three gains, three offsets) per entry. The first fast-kernel
 // state that reads the node grid. A wave of the fast kernels is a run of consecutive x in one row, so from a node spacing
 // of 64 on its lanes usually share their four nodes: begin() takes a wave vote on the four node offsets (all lanes' equal
 // the first lane's; nothing is assumed about the launch shape), and where it holds the plane values are read through the
@@ -309,33 +279,12 @@ struct ClipNorm {
 // planes are written before the launch only). Where it does not hold (spacing 8 .. 32, or a wave across a node column)
 // every lane loads its own. The arithmetic is NormAt::at's, operation for operation (sub, fma, sub, fma, sub, fma), so the
 // two paths and ClipNorm<3> give the same bits.
-struct ClipNormU8C3 {
+struct VotedPlane : FromPlane<PlainTables, 3> {
     typedef const float __attribute__((address_space(4))) * UniformPlane;
-    f32x2 c01, L01, U01, a01, b01, sw01;
-    float c2, L2, U2, a2, b2, sw2;
-    int k0, k1, k2;
-    size_t p;
-    const stk_frame_weight* e;
-    const float* const* np;
-    NormAt at;
     int s00, s01, s10, s11;          // the first lane's node offsets (wave-uniform)
-    int cov;
-    bool centre, uniform;
+    bool uniform;
     __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
-        p = (size_t)y * ca.plane_stride + (size_t)x * 3;
-        if (ca.centre) { c01 = f32x2{0.f, 0.f}; c2 = 0.f; }
-        else { c01 = f32x2{ca.c[p], ca.c[p + 1]}; c2 = ca.c[p + 2]; }
-        if (ca.first | ca.centre) {
-            L01 = f32x2{-__builtin_inff(), -__builtin_inff()}; L2 = -__builtin_inff();
-            U01 = f32x2{__builtin_inff(), __builtin_inff()}; U2 = __builtin_inff();
-        } else {
-            L01 = f32x2{ca.L[p], ca.L[p + 1]}; L2 = ca.L[p + 2];
-            U01 = f32x2{ca.U[p], ca.U[p + 1]}; U2 = ca.U[p + 2];
-        }
-        a01 = f32x2{0.f, 0.f}; b01 = f32x2{0.f, 0.f}; sw01 = f32x2{0.f, 0.f}; a2 = 0.f; b2 = 0.f; sw2 = 0.f;
-        k0 = k1 = k2 = 0;
-        e = ca.coef; np = ca.norm; cov = ca.coverage; centre = ca.centre != 0;
-        at.set(ca, x, y, 6);
+        FromPlane<PlainTables, 3>::begin(ca, x, y);
         s00 = __builtin_amdgcn_readfirstlane(at.o00); s01 = __builtin_amdgcn_readfirstlane(at.o01);
         s10 = __builtin_amdgcn_readfirstlane(at.o10); s11 = __builtin_amdgcn_readfirstlane(at.o11);
         uniform = __all((at.o00 == s00) & (at.o01 == s01) & (at.o10 == s10) & (at.o11 == s11)) != 0;
@@ -349,8 +298,7 @@ struct ClipNormU8C3 {
         const float t1 = __builtin_fmaf(at.u, p11 - p10, p10);
         return __builtin_fmaf(at.v, t1 - t0, t0);
     }
-    __device__ __forceinline__ void fold(f32x2 s01v, float s2, bool part) {
-        const float w = e->weight;
+    __device__ __forceinline__ Coef3<float> coef3() const {
         const float* __restrict__ P = *np;
         float q[6];                      // G of B, G, R, then O of B, G, R
         if (!P) {
@@ -364,40 +312,33 @@ struct ClipNormU8C3 {
 #pragma unroll
             for (int i = 0; i < 6; i++) q[i] = at.at(P, i);
         }
-        const f32x2 u01 = s01v * f32x2{q[0], q[1]} + f32x2{q[3], q[4]};
-        const f32x2 d = u01 - c01;
-        const bool i0 = part & (centre | clip_in(u01.x, L01.x, U01.x)), i1 = part & (centre | clip_in(u01.y, L01.y, U01.y));
-        // (as ClipWU8C3: a sample that is out adds w = 0 times d = 0, and the sums stay packed)
-        const f32x2 wi = {i0 ? w : 0.0f, i1 ? w : 0.0f}, di = {i0 ? d.x : 0.0f, i1 ? d.y : 0.0f};
-        k0 += i0 ? 1 : 0; k1 += i1 ? 1 : 0;
-        sw01 = sw01 + wi;
-        a01 = a01 + wi * di;
-        b01 = b01 + wi * (di * di);
-        const float u2 = s2 * q[2] + q[5];
-        const float d2 = u2 - c2;
-        const bool i2 = part & (centre | clip_in(u2, L2, U2));
-        const float w2 = i2 ? w : 0.0f, dd2 = i2 ? d2 : 0.0f;
-        k2 += i2 ? 1 : 0;
-        sw2 = sw2 + w2;
-        a2 = a2 + w2 * dd2;
-        b2 = b2 + w2 * (dd2 * dd2);
-        e++; np++;
-    }
-    __device__ __forceinline__ void add2(f32x2 s01v, float s2) { fold(s01v, s2, e->weight > 0.0f); }
-    __device__ __forceinline__ void add3k(float s0, float s1, float s2, float kap) {
-        fold(f32x2{s0, s1}, s2, (e->weight > 0.0f) & (cov ? kap == 1.0f : true));
-    }
-    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
-        const size_t o = (size_t)y * ca.out_stride + (size_t)x * 3;
-        clip_end_w(ca, p, o, c01.x, L01.x, U01.x, k0, sw01.x, a01.x, b01.x);
-        clip_end_w(ca, p + 1, o + 1, c01.y, L01.y, U01.y, k1, sw01.y, a01.y, b01.y);
-        clip_end_w(ca, p + 2, o + 2, c2, L2, U2, k2, sw2, a2, b2);
+        return {q[0], q[1], q[2], q[3], q[4], q[5]};
     }
 };
+
+struct ClipNormU8C3 : ClipWFast<VotedPlane> {};
 
 hipError_t launch_clip_pass_norm(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
     if (!norm_args_ok(a, c)) return hipErrorInvalidValue;
     return launch_fold<ClipNormU8C3, ClipNorm>(a, c, depth, a.dh, s);
 }
+
+// ---- what every state asks of its kernel, pinned: one line per (state, trait) that holds, so that a change to a state's
+// traits is a change here too. (This unit sees every state: fold_launch.h includes both fold headers.) ------------------
+#define STK_ASKS(State, trait) static_assert(State::trait, #State " asks for " #trait)
+#define STK_ASKS_NOT(State, trait) static_assert(!State::trait, #State " does not ask for " #trait)
+STK_ASKS(FoldWeighted<3>, wants_kappa);   STK_ASKS(FoldNorm<3>, wants_kappa);       STK_ASKS(FoldMoments<3>, wants_kappa);
+STK_ASKS(FoldStoreW<3>, wants_kappa);     STK_ASKS(FoldStoreNorm<3>, wants_kappa);  STK_ASKS(FoldLocal<3>, wants_kappa);
+STK_ASKS(ClipWGeneric<3>, wants_kappa);   STK_ASKS(ClipNorm<3>, wants_kappa);       STK_ASKS(Mesh<FoldLocal<3>>, wants_kappa);
+STK_ASKS(ClipWU8C3, wants_kappa);         STK_ASKS(ClipNormU8C3, wants_kappa);
+STK_ASKS(FoldLocal<3>, wants_coords);     STK_ASKS(Mesh<FoldLocal<3>>, wants_coords);
+STK_ASKS(FoldStore<3>, in_band);          STK_ASKS(FoldStoreW<3>, in_band);         STK_ASKS(FoldStoreNorm<3>, in_band);
+STK_ASKS(FoldMoments<3>, stepped);
+STK_ASKS(Mesh<NoClip>, displaced);        STK_ASKS(Mesh<FoldLocal<3>>, displaced);
+STK_ASKS_NOT(NoClip, wants_kappa);        STK_ASKS_NOT(ClipGeneric<3>, wants_kappa); STK_ASKS_NOT(ClipU8C3, wants_kappa);
+STK_ASKS_NOT(FoldStore<3>, wants_kappa);  STK_ASKS_NOT(FoldLocal<3>, displaced);     STK_ASKS_NOT(FoldWeighted<3>, in_band);
+STK_ASKS_NOT(FoldNorm<3>, in_band);       STK_ASKS_NOT(FoldWeighted<3>, stepped);
+#undef STK_ASKS
+#undef STK_ASKS_NOT
 
 }  // namespace stk

@@ -1,6 +1,6 @@
 // kernels_local_norm.hip — local normalisation (include/stacker.h, "Local normalisation"): the cell moments
-// pass, and the launches of the two folds whose gain and offset come from a node grid (FoldNorm<CN> / FoldStoreNorm<CN>,
-// warp_body.h).
+// pass, and the launches of the two folds whose gain and offset come from a node grid (FoldNorm<CN> / FoldStoreNorm<CN>:
+// the weighted mean and the store with participation over the plane source, warp_body.h).
 //
 // The moments pass. One wave owns one (cell, entry): blockIdx.x * 4 + wave = the cell in row-major order, blockIdx.y + 1 =
 // the table entry. Its lanes walk the cell's stepped pixels (x % step == 0, y % step == 0) lane-strided in row-major order;
@@ -15,39 +15,12 @@
 
 namespace stk {
 
-// FoldMoments' sums without its stepped-grid bookkeeping: every pixel the wave visits is a stepped pixel of the cell.
-template <int CN>
-struct CellMoments {
-    static constexpr int NM = 1 + 5 * CN;
-    double S[NM];
-    float Y[CN], kap;
-    int which;
-    __device__ __forceinline__ void begin() {
-#pragma unroll
-        for (int k = 0; k < NM; k++) S[k] = 0.0;
-        which = 0; kap = 0.f;
-    }
-    __device__ __forceinline__ void entry(float k) { kap = k; }
-    __device__ __forceinline__ void add(int c, float v) {
-        if (which == 0) Y[c] = v;
-        else {
-            const bool in = kap == 1.0f;
-            const double X = in ? (double)v : 0.0, Yd = in ? (double)Y[c] : 0.0;    // masked terms add +0
-            if (c == 0) S[0] = S[0] + (in ? 1.0 : 0.0);
-            S[1 + 5 * c] = S[1 + 5 * c] + X;
-            S[2 + 5 * c] = S[2 + 5 * c] + Yd;
-            S[3 + 5 * c] = S[3 + 5 * c] + X * X;
-            S[4 + 5 * c] = S[4 + 5 * c] + Yd * Yd;
-            S[5 + 5 * c] = S[5 + 5 * c] + X * Yd;
-        }
-        if (c == CN - 1) which ^= 1;
-    }
-};
+// FoldMoments' sums (MomentSums, warp_body.h: wants_kappa is all it asks of the sample fragment) without the stepped-grid
+// bookkeeping and its mask: every pixel the wave visits is a stepped pixel of the cell.
+template <int CN> struct CellMoments : MomentSums<CN, false> {};
 
 template <typename T, int CN>
 __global__ __launch_bounds__(256) void local_moments_kernel(WarpArgs a, ClipArgs ca) {
-    // the modes the sample fragment asks about: kappa is wanted, nothing else
-    constexpr bool CLIP = CN > 0, WEIGHTED = false, MOMENTS = CN > 0, ROBUST = false, LOCAL = CN < 0;
     const int lane = threadIdx.x & 63;
     const int cell = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (cell >= ca.cell_w * ca.cell_h) return;                       // (the whole wave)
@@ -59,9 +32,8 @@ __global__ __launch_bounds__(256) void local_moments_kernel(WarpArgs a, ClipArgs
     const int sx0 = (xa + st - 1) / st, sx1 = (xb + st - 1) / st;
     const int sy0 = (ya + st - 1) / st, sy1 = (yb + st - 1) / st;
     const int nx = sx1 - sx0, npix = nx * (sy1 - sy0);
-    [[maybe_unused]] float sum[CN];
     CellMoments<CN> cs;
-    cs.begin();
+    cs.zero();
     const int mode = a.border_mode;
     for (int i = lane; i < npix; i += 64) {
         const int ry = i / nx, rx = i - ry * nx;
@@ -71,8 +43,10 @@ __global__ __launch_bounds__(256) void local_moments_kernel(WarpArgs a, ClipArgs
             const WarpFrame* fr = a.frames + f * (1 + (int)blockIdx.y);
             const T* __restrict__ src = (const T*)fr->src;
 #define STK_SUBPIX a.subpixel_bits
+#define STK_SAMPLE(c, v) cs.add(c, v)
 #include "warp_coords.inc.h"
 #include "warp_linear_sample.inc.h"
+#undef STK_SAMPLE
 #undef STK_SUBPIX
         }
     }
@@ -106,7 +80,7 @@ hipError_t launch_local_moments(const WarpArgs& a, const ClipArgs& c, int depth,
 }
 
 // The locally normalised mean over the frames of `a`: the generic kernels, linear or cubic. The u8 BGR fast kernels do not
-// serve these states.
+// serve these states (they have no add2 / add3k): a matter of these two launchers, not of the states' traits.
 hipError_t launch_norm_fold(const WarpArgs& a, const ClipArgs& c, int depth, hipStream_t s) {
     if (!norm_args_ok(a, c) || !c.out) return hipErrorInvalidValue;
     const dim3 grid((a.dw + 63) / 64, (a.dh + 3) / 4);

@@ -1,56 +1,59 @@
-// warp_body.h — the warp fold kernels, shared by the mean fold (kernels_warp.hip) and the sigma-clipping passes
-// (kernels_clip.hip): "the sample the clip sees" is the mean's sample by construction, one source for both. Each kernel has
-// a template mode CLIP that selects the per-sample body only:
-//   * warp_accumulate_kernel<T, CN, CLIP, ClipState>: the generic kernel; clip mode calls ClipState::add(c, v) per channel;
-//   * warp_accumulate_u8c3_kernel<AFFINE, WX, WU, CLIP, ClipState>: the u8 BGR BORDER_CONSTANT fast kernel (interior vote,
-//     shared reciprocal chain, 8-byte tap loads, packed lerps); clip mode calls add2 ((B, G) pair + R, interior path) / add3
-//     (rim path).
-// In clip mode ClipState::begin() / finish() are the prologue / epilogue. The mean instantiations (CLIP = false, NoClip)
-// compile to the instructions these kernels had before the clip mode existed.
-// The third mode, store (CLIP = true with ClipState = FoldStore<CN>, below; kernels_quantile.hip), writes every sample to
-// a band buffer instead: the quantile combines' samples, again the mean's by construction. It is the only mode whose rows
-// start at ClipArgs::y0 (a band of the destination); the frame table is the full frame's, unchanged.
-// The fourth mode, weighted (ClipState = FoldWeighted<CN>, below; kernels_weighted.hip), is the weighted, coverage-aware
-// mean: its hooks also get the entry's coverage weight kappa (fold_kappa below: the sample the same lerp chain gives for
-// an all-ones frame), which the rim paths compute and the u8 fast kernel's interior path knows to be 1. The generic kernel
-// has a fifth mode, moments (FoldMoments<CN>): the overlap moments of entry 1 + blockIdx.z against entry 0 over the
-// stepped pixels, a thread walking ClipArgs::reps stepped rows before its wave reduces.
-// The local mode (FoldLocal<CN>, below; launched from kernels_local.hip) is the weighted mode with a weight that varies per
-// pixel: besides kappa its hooks get the entry's coordinates (cs.coords), at which the state samples the entry's weight
-// plane itself. Generic kernels only.
-// The normalised, coverage-aware rejection combines add two states that take kappa through the same hooks: the weighted
-// clip (ClipWGeneric<CN> / ClipWU8C3, kernels_clip.hip) and the store mode with participation (FoldStoreW<CN>, below).
-// Local normalisation adds two more of that kind (FoldNorm<CN>, FoldStoreNorm<CN>, below; launched from
-// kernels_local_norm.hip): the weighted mode and the store mode with participation with the entry's gain and offset
-// interpolated from a node grid. Generic kernels only. The weighted clip through the same planes (ClipNorm<CN> /
-// ClipNormU8C3, kernels_clip.hip) runs on every kernel the weighted clip runs on, the u8 BGR fast ones included.
-// The bicubic fold (warp_cubic_body.h) is a second kernel that speaks the same hooks. What it shares with the generic kernel
-// here is shared as text, in two fragments that both include inside their frame loops: the coordinates and the bilinear
-// sample (warp_coords.inc.h, warp_linear_sample.inc.h). Text, not helper functions: see the note at
-// warp_accumulate_kernel; the instantiations below compile to the instructions they had before the fragments existed.
+// warp_body.h — the linear warp fold kernels and the states every combine plugs into them. One source for "the sample":
+// whatever a combine does with the aligned frames, it does with the mean fold's samples, computed by the same instructions.
+//   G   warp_accumulate_kernel<T, CN, CLIP, State>: the generic kernel (any depth, 1 / 3 / 4 channels, every border mode);
+//   F   warp_accumulate_u8c3_kernel<AFFINE, WX, WU, CLIP, State>: the u8 BGR BORDER_CONSTANT fast kernel;
+//   C / CF   the bicubic fold's two kernels (warp_cubic_body.h), which speak the same hooks.
+// CLIP = false is the mean fold (NoClip: running sums into WarpArgs::acc; these instantiations compile to what they were
+// before there were states). CLIP = true hands every sample to the state:
+//   begin(ca, x, y) ... per table entry, in frame order: [entry(kappa)] [coords(..)] add(c, v) per channel ... finish(ca, x, y)
+// and on F / CF add2((B, G), R) where the kernel knows kappa = 1 (interior), add3(B, G, R) or add3k(B, G, R, kappa) on the
+// rim. kappa is the entry's coverage weight (fold_kappa below). What else a state needs from its kernel it declares as
+// traits (FoldTraits below); the kernels and the sample fragment ask the traits, never which state they run.
+//
+//   state                traits                       kernels      launched from
+//   NoClip               -                            G F C CF     kernels_warp.hip (the mean)
+//   FoldStore<CN>        in_band                      G F C CF     kernels_quantile.hip (launch_fold)
+//   FoldStoreW<CN>       in_band wants_kappa          G F C CF     kernels_quantile.hip (launch_fold)
+//   FoldStoreNorm<CN>    in_band wants_kappa          G C          kernels_local_norm.hip
+//   FoldWeighted<CN>     wants_kappa                  G F C CF     kernels_weighted.hip (launch_fold)
+//   FoldNorm<CN>         wants_kappa                  G C          kernels_local_norm.hip
+//   FoldLocal<CN>        wants_kappa wants_coords     G C          kernels_local.hip
+//   FoldMoments<CN>      wants_kappa stepped          G C          kernels_weighted.hip
+//   Mesh<NoClip>         displaced                    G            kernels_mesh.hip
+//   Mesh<FoldLocal<CN>>  displaced + FoldLocal's      G            kernels_mesh.hip
+//   ClipGeneric<CN> / ClipU8C3        -               G C / F CF   kernels_clip.hip (launch_fold)
+//   ClipWGeneric<CN> / ClipWU8C3      wants_kappa     G C / F CF   kernels_clip.hip (launch_fold)
+//   ClipNorm<CN> / ClipNormU8C3       wants_kappa     G C / F CF   kernels_clip.hip (launch_fold)
+//   (CellMoments<CN>     wants_kappa                  local_moments_kernel, kernels_local_norm.hip: the sample fragment only)
+// The pairs FoldWeighted / FoldNorm, FoldStoreW / FoldStoreNorm, ClipWGeneric / ClipNorm and ClipWU8C3 / ClipNormU8C3 are
+// one state each over two coefficient sources (FromRecord, FromPlane below). A state without add2 / add3 / add3k is for the
+// generic kernels only: a fast launch with it does not compile. kernels_clip.hip pins the table as static_asserts.
+//
+// To add a state: derive from FoldTraits, set the traits, write the hooks; launch it through launch_fold (fold_launch.h) if
+// it has a fast form, else as kernels_local.hip does; add its lines to the table and to the asserts.
+//
+// What the generic kernels share with each other (and with local_moments_kernel) is shared as text, in two fragments that
+// they include inside their frame loops: the coordinates and the bilinear sample (warp_coords.inc.h,
+// warp_linear_sample.inc.h). Text, not helper functions: see the note at warp_accumulate_kernel.
 #pragma once
-#include <type_traits>
-
 #include "common.h"
 
 namespace stk {
 
-template <int CN> struct FoldStore;
-template <int CN> struct FoldWeighted;
-template <int CN> struct FoldMoments;
-template <int CN> struct FoldStoreW;
-template <int CN> struct FoldLocal;
-template <int CN> struct FoldNorm;
-template <int CN> struct FoldStoreNorm;
-template <int CN> struct ClipWGeneric;
-struct ClipWU8C3;
-template <int CN> struct ClipNorm;
-struct ClipNormU8C3;
-struct NoClip;
+// What a state asks of the kernel that runs it, as compile-time members; a state overrides the ones it wants. The kernels
+// and the sample fragment ask these and nothing else about a state.
+struct FoldTraits {
+    static constexpr bool wants_kappa = false;    // entry(kappa) before the entry's samples; add3k, not add3, on the fast kernels' rims
+    static constexpr bool wants_coords = false;   // coords(..) after entry: the entry's coordinates
+    static constexpr bool in_band = false;        // rows start at ClipArgs::y0: a store launch covers a band of the destination
+    static constexpr bool stepped = false;        // the moments walk: (x, y) index the stepped grid, entry 0 against entry 1 + blockIdx.z
+    static constexpr bool displaced = false;      // coordinates displaced by the entry's field (Mesh<> below)
+};
+
 // The mesh variant of the generic kernel (kernels_mesh.hip; definition: include/stacker.h, "Mesh fold"): a state wrapped in
 // Mesh<> runs the same hooks at coordinates displaced by the entry's field. A wrapper around the state, not a further
 // template parameter: the instantiations without it keep their names and their instructions.
-template <class State> struct Mesh : State {};
+template <class State> struct Mesh : State { static constexpr bool displaced = true; };
 
 // The coverage weight of one sample: what the fold's interpolation (lerp chain, or the classic four-weight sum) gives for a
 // frame whose every value is 1.0f under alpha = 1 and BORDER_CONSTANT 0; i00 .. i11 say which taps are inside the frame.
@@ -122,18 +125,10 @@ __device__ __forceinline__ MeshXY mesh_displace(const ClipArgs& ca, int f, int x
 // reads compiled to flat loads — a different, slower mean kernel.)
 template <typename T, int CN, bool CLIP, class ClipState>
 __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipArgs ca) {
-    constexpr bool MESH = std::is_same_v<ClipState, Mesh<NoClip>> || std::is_same_v<ClipState, Mesh<FoldLocal<CN>>>;
-    constexpr bool WEIGHTED = std::is_same_v<ClipState, FoldWeighted<CN>>;
-    constexpr bool MOMENTS = std::is_same_v<ClipState, FoldMoments<CN>>;
-    // the normalised, coverage-aware rejection states (kernels_clip.hip, FoldStoreW below) take kappa like the weighted mode
-    constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>> ||
-                            std::is_same_v<ClipState, FoldNorm<CN>> || std::is_same_v<ClipState, FoldStoreNorm<CN>> ||   // (and the two local-normalisation states)
-                            std::is_same_v<ClipState, ClipNorm<CN>>;                                                  // (and the clip through them)
-    constexpr bool LOCAL = std::is_same_v<ClipState, FoldLocal<CN>> || std::is_same_v<ClipState, Mesh<FoldLocal<CN>>>;   // kappa like the weighted mode, and the coordinates
+    constexpr bool MESH = ClipState::displaced, MOMENTS = ClipState::stepped;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if constexpr (std::is_same_v<ClipState, FoldStore<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>> ||
-                  std::is_same_v<ClipState, FoldStoreNorm<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
+    if constexpr (ClipState::in_band) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
     // (moments mode: (x, y) index the stepped grid and every lane stays for the wave reduction; see the loop below)
     if constexpr (!MOMENTS) { if (x >= a.dw || y >= a.dh) return; }
     float* accp = a.acc + (size_t)y * a.acc_stride + (size_t)x * CN;
@@ -158,6 +153,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
         const WarpFrame* fr = a.frames + (MOMENTS ? f * (1 + (int)blockIdx.z) : f);
         const T* __restrict__ src = (const T*)fr->src;
 #define STK_SUBPIX a.subpixel_bits
+#define STK_SAMPLE(c, v) if constexpr (CLIP) cs.add(c, v); else sum[c] = sum[c] + v
         if constexpr (MESH) {
             // the entry's field moves the destination coordinate; these two shadow the pixel's own for the fragments below
             const MeshXY mxy = mesh_displace(ca, f, x, y);
@@ -168,6 +164,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
 #include "warp_coords.inc.h"
 #include "warp_linear_sample.inc.h"
         }
+#undef STK_SAMPLE
 #undef STK_SUBPIX
     }
     } while (MOMENTS && ++rep < ca.reps);
@@ -178,7 +175,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_kernel(WarpArgs a, ClipAr
     }
 }
 
-struct NoClip {};   // the mean fold's (unused) clip state
+struct NoClip : FoldTraits {};   // the mean fold's (unused) clip state
 
 // -----------------------------------------------------------------------------------------------
 // Fast path for the production configuration: BGR u8 source, BORDER_CONSTANT, exact f32 coordinates.
@@ -234,7 +231,8 @@ __device__ __forceinline__ f32x2 div2_shared(f32x2 n, float d) {
 // (ClipArgs), so a wave's stores for one frame are contiguous. The hooks run in frame order, so the entry index is a
 // pointer that moves one frame slab per frame: after channel CN - 1 (add) or once per call (add2 / add3).
 template <int CN>
-struct FoldStore {
+struct FoldStore : FoldTraits {
+    static constexpr bool in_band = true;
     float* p;
     size_t slab;
     __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
@@ -250,87 +248,149 @@ struct FoldStore {
     __device__ __forceinline__ void finish(const ClipArgs&, int, int) {}
 };
 
+// ---- where an entry's coefficients come from --------------------------------------------------------------------------
+// Four combines exist twice: with the entry's gain and offset read from its record (ClipArgs::coef[i], indexed like the
+// frame table), and with them interpolated from a node grid (local normalisation; definition: include/stacker.h, "Local
+// normalisation"). Each is written once over a source (begin / weight / coef / next). The hooks run in frame
+// order, so a source is a pointer, or two, that its state moves on after the entry's last sample.
+//
+// NormAt is a destination pixel's place on the node grid, computed once per pixel in begin(): the float offsets of its four
+// nodes within a plane and the two fractions. The pixel's OWN y addresses the grid, also in the store mode, whose band
+// pointer is the only thing that counts rows from ClipArgs::y0. at(P, q) is component q of plane P at the pixel: the mesh
+// fold's chain (mesh_displace above), operation by operation.
+struct NormAt {
+    int o00, o01, o10, o11;
+    float u, v;
+    __device__ __forceinline__ void set(const ClipArgs& ca, int x, int y, int comps) {
+        const int k = x >> ca.norm_shift, j = y >> ca.norm_shift;
+        const int k1 = min(k + 1, ca.norm_gw - 1), j1 = min(j + 1, ca.norm_gh - 1);
+        u = (float)(x - (k << ca.norm_shift)) * ca.norm_inv; v = (float)(y - (j << ca.norm_shift)) * ca.norm_inv;
+        o00 = (j * ca.norm_gw + k) * comps; o01 = (j * ca.norm_gw + k1) * comps;
+        o10 = (j1 * ca.norm_gw + k) * comps; o11 = (j1 * ca.norm_gw + k1) * comps;
+    }
+    __device__ __forceinline__ float at(const float* __restrict__ P, int q) const {
+        const float t0 = __builtin_fmaf(u, P[o01 + q] - P[o00 + q], P[o00 + q]);
+        const float t1 = __builtin_fmaf(u, P[o11 + q] - P[o10 + q], P[o10 + q]);
+        return __builtin_fmaf(v, t1 - t0, t0);
+    }
+};
+
+// How a source points into the record and plane tables: plainly, or (the store states, see StoreW) through the constant
+// address space.
+struct PlainTables {
+    typedef const stk_frame_weight* Records;
+    typedef const float* const* Planes;
+};
+struct ConstantTables {
+    typedef const stk_frame_weight __attribute__((address_space(4))) * Records;
+    typedef const float* const __attribute__((address_space(4))) * Planes;
+};
+
+// An entry's gain and offset for one channel, and for B, G, R at once (the u8 BGR fast kernels' states), as a source hands
+// them over: F = float, or a reference into the entry's record.
+template <class F> struct Coef { F g, o; };
+template <class F> struct Coef3 { F g0, g1, g2, o0, o1, o2; };
+
+// The record source: w, g, o of the entry from its record. coef hands out references, not values: the reads then happen
+// where the state uses them, as when each state read its record itself. (A value is loaded in here, ahead of the state's
+// own conditions; the store states' and the fast weighted clip's kernels then compile differently. DESIGN §4.27.)
+// (The cast through an integer is what the constant address space needs; on plain pointers it folds away.)
+template <class Tables>
+struct FromRecord {
+    typename Tables::Records e;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int, int) { e = (typename Tables::Records)(uintptr_t)ca.coef; }
+    __device__ __forceinline__ float weight() const { return e->weight; }
+    __device__ __forceinline__ auto coef(int c) const { return Coef<decltype((e->gain[c]))>{e->gain[c], e->offset[c]}; }
+    __device__ __forceinline__ auto coef3() const {
+        return Coef3<decltype((e->gain[0]))>{e->gain[0], e->gain[1], e->gain[2], e->offset[0], e->offset[1], e->offset[2]};
+    }
+    __device__ __forceinline__ void next() { e++; }
+};
+
+// The plane source: w from the record; (G, O) = the entry's plane (ClipArgs::norm[i]: per node CN gains, then CN offsets) at
+// the pixel, or the record's gain and offset where the entry has no plane (fma(u, 0, g) = g: a constant plane and a
+// record give the same bits). The plane pointer moves with the record pointer.
+template <class Tables, int CN>
+struct FromPlane : FromRecord<Tables> {
+    typename Tables::Planes np;
+    NormAt at;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+        FromRecord<Tables>::begin(ca, x, y);
+        np = (typename Tables::Planes)(uintptr_t)ca.norm;
+        at.set(ca, x, y, 2 * CN);         // y, also in a store launch (not y - y0): the grid is the destination's
+    }
+    __device__ __forceinline__ Coef<float> coef(int c) const {
+        const float* __restrict__ P = *np;
+        const float G = P ? at.at(P, c) : this->e->gain[c], O = P ? at.at(P, CN + c) : this->e->offset[c];
+        return {G, O};
+    }
+    __device__ __forceinline__ void next() { this->e++; np++; }
+};
+
 // The store mode with participation (the normalised, coverage-aware quantile; definition: include/stacker.h): FoldStore's
 // layout, but the value written for entry i is the normalised sample u = s * g_i,c + o_i,c if the entry participates in
 // the pixel (w_i > 0 and, with ClipArgs::coverage, kappa_i == 1.0f) and the bit pattern QUANTILE_ABSENT_BITS if not: a
 // signalling NaN, which u, the result of an add, never is (common.h), so the selection kernel cannot take a genuine NaN
-// for an absent entry. g, o, w from ClipArgs::coef by a pointer that moves once per frame, as in FoldWeighted.
-template <int CN>
-struct FoldStoreW {
-    // The records are read through a constant-address-space pointer: the band's stores (through p) could alias a plain
-    // global pointer as far as the compiler knows, which turned every record read into a vector load behind the previous
-    // frame's stores and kept a pixel's three stores apart. The table is written before the launch only.
-    typedef const stk_frame_weight __attribute__((address_space(4))) * CoefPtr;
+// for an absent entry. The values of a pixel are stored together, after the last channel's.
+// Src reads the tables through constant-address-space pointers: the band's stores (through p) could alias a plain global
+// pointer as far as the compiler knows, which turned every record read into a vector load behind the previous frame's
+// stores and kept a pixel's three stores apart. The tables are written before the launch only.
+template <int CN, class Src>
+struct StoreW : FoldTraits {
+    static constexpr bool wants_kappa = true, in_band = true;
     float* p;
     size_t slab;
-    CoefPtr e;
+    Src src;
     float v[CN];
     int cov;
     bool part;
     __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
         p = ca.band + (size_t)(y - ca.y0) * ca.plane_stride + (size_t)x * CN;
         slab = (size_t)ca.band_rows * ca.plane_stride;
-        e = (CoefPtr)(uintptr_t)ca.coef; cov = ca.coverage; part = true;
+        src.begin(ca, x, y); cov = ca.coverage; part = true;
     }
+    __device__ __forceinline__ void entry(float k) { part = (src.weight() > 0.0f) & (cov ? k == 1.0f : true); }
     __device__ __forceinline__ float value(int c, float s) const {
-        const float u = s * e->gain[c] + e->offset[c];
+        const auto k = src.coef(c);
+        const float u = s * k.g + k.o;
         return part ? u : __uint_as_float(QUANTILE_ABSENT_BITS);
     }
-    __device__ __forceinline__ void entry(float k) { part = (e->weight > 0.0f) & (cov ? k == 1.0f : true); }
-    // the values of a pixel are stored together, after the last channel's
     __device__ __forceinline__ void add(int c, float s) {
         v[c] = value(c, s);
         if (c == CN - 1) {
 #pragma unroll
             for (int i = 0; i < CN; i++) p[i] = v[i];
-            p += slab; e++;
+            p += slab; src.next();
         }
-    }
-    __device__ __forceinline__ void add2(f32x2 s01, float s2) { add3k(s01.x, s01.y, s2, 1.0f); }
-    __device__ __forceinline__ void add3k(float s0, float s1, float s2, float k) {
-        entry(k);
-        const float v0 = value(0, s0), v1 = value(1, s1), v2 = value(2, s2);
-        p[0] = v0; p[1] = v1; p[2] = v2;
-        p += slab; e++;
     }
     __device__ __forceinline__ void finish(const ClipArgs&, int, int) {}
 };
 
-// The weighted mode's state (definition: include/stacker.h, stk_weight_params): per entry i of the frame table
-//     v = s * g_i,c + o_i,c * kappa_i;  num_c = num_c + w_i * v;  den = den + w_i * kappa_i
-// with g, o, w from ClipArgs::coef[i] (indexed like the frame table; the hooks run in frame order, so the entry is a
-// pointer that moves on after channel CN - 1 or once per add2 / add3k call). ClipArgs::coverage == 0: kappa = 1 by
-// definition. kappa = 1 makes o * kappa and w * kappa o and w bit for bit: add2 (the u8 fast kernel's interior path)
-// multiplies neither.
+// from the records: every kernel
 template <int CN>
-struct FoldWeighted {
-    float num[CN], den, kap;
-    const stk_frame_weight* e;
-    int cov;
-    __device__ __forceinline__ void begin(const ClipArgs& ca, int, int) {
+struct FoldStoreW : StoreW<CN, FromRecord<ConstantTables>> {
+    using StoreW<CN, FromRecord<ConstantTables>>::p;
+    __device__ __forceinline__ void add2(f32x2 s01, float s2) { add3k(s01.x, s01.y, s2, 1.0f); }
+    __device__ __forceinline__ void add3k(float s0, float s1, float s2, float k) {
+        this->entry(k);
+        const float v0 = this->value(0, s0), v1 = this->value(1, s1), v2 = this->value(2, s2);
+        p[0] = v0; p[1] = v1; p[2] = v2;
+        p += this->slab; this->src.next();
+    }
+};
+
+// through the planes: generic kernels only (no add2 / add3k: a fast launch does not compile)
+template <int CN> struct FoldStoreNorm : StoreW<CN, FromPlane<ConstantTables, CN>> {};
+
+// The sums and the epilogue of the weighted means (WeightedMean, FoldLocal): num / den, 0 where nothing weighed in, and den
+// to its plane.
+template <int CN>
+struct WeightedSums : FoldTraits {
+    float num[CN], den;
+    __device__ __forceinline__ void zero() {
 #pragma unroll
         for (int c = 0; c < CN; c++) num[c] = 0.f;
-        den = 0.f; kap = 1.0f;
-        e = ca.coef; cov = ca.coverage;
-    }
-    __device__ __forceinline__ void entry(float k) { kap = cov ? k : 1.0f; }
-    __device__ __forceinline__ void add(int c, float s) {
-        const float v = s * e->gain[c] + e->offset[c] * kap;
-        num[c] = num[c] + e->weight * v;
-        if (c == CN - 1) { den = den + e->weight * kap; e++; }
-    }
-    __device__ __forceinline__ void add2(f32x2 s01, float s2) {
-        const float w = e->weight;
-        const f32x2 v01 = s01 * f32x2{e->gain[0], e->gain[1]} + f32x2{e->offset[0], e->offset[1]};
-        const f32x2 n01 = f32x2{num[0], num[1]} + f32x2{w, w} * v01;
-        num[0] = n01.x; num[1] = n01.y;
-        num[2] = num[2] + w * (s2 * e->gain[2] + e->offset[2]);
-        den = den + w;
-        e++;
-    }
-    __device__ __forceinline__ void add3k(float s0, float s1, float s2, float k) {
-        entry(k);
-        add(0, s0); add(1, s1); add(2, s2);
+        den = 0.f;
     }
     __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
         float* o = ca.out + (size_t)y * ca.out_stride + (size_t)x * CN;
@@ -340,6 +400,55 @@ struct FoldWeighted {
     }
 };
 
+// The weighted mode's state (definition: include/stacker.h, stk_weight_params): per entry i of the frame table
+//     v = s * g_i,c + o_i,c * kappa_i;  num_c = num_c + w_i * v;  den = den + w_i * kappa_i
+// with g, o, w from Src. ClipArgs::coverage == 0: kappa = 1 by definition.
+template <int CN, class Src>
+struct WeightedMean : WeightedSums<CN> {
+    static constexpr bool wants_kappa = true;
+    using WeightedSums<CN>::num;
+    using WeightedSums<CN>::den;
+    float kap;
+    Src src;
+    int cov;
+    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
+        this->zero(); kap = 1.0f;
+        src.begin(ca, x, y); cov = ca.coverage;
+    }
+    __device__ __forceinline__ void entry(float k) { kap = cov ? k : 1.0f; }
+    __device__ __forceinline__ void add(int c, float s) {
+        const auto k = src.coef(c);
+        const float v = s * k.g + k.o * kap;
+        num[c] = num[c] + src.weight() * v;
+        if (c == CN - 1) { den = den + src.weight() * kap; src.next(); }
+    }
+};
+
+// from the records: every kernel. kappa = 1 makes o * kappa and w * kappa o and w bit for bit: add2 (the u8 fast kernels'
+// interior path) multiplies neither, and packs (B, G).
+template <int CN>
+struct FoldWeighted : WeightedMean<CN, FromRecord<PlainTables>> {
+    using WeightedSums<CN>::num;
+    using WeightedSums<CN>::den;
+    __device__ __forceinline__ void add2(f32x2 s01, float s2) {
+        auto& e = this->src.e;
+        const float w = e->weight;
+        const f32x2 v01 = s01 * f32x2{e->gain[0], e->gain[1]} + f32x2{e->offset[0], e->offset[1]};
+        const f32x2 n01 = f32x2{num[0], num[1]} + f32x2{w, w} * v01;
+        num[0] = n01.x; num[1] = n01.y;
+        num[2] = num[2] + w * (s2 * e->gain[2] + e->offset[2]);
+        den = den + w;
+        e++;
+    }
+    __device__ __forceinline__ void add3k(float s0, float s1, float s2, float k) {
+        this->entry(k);
+        this->add(0, s0); this->add(1, s1); this->add(2, s2);
+    }
+};
+
+// through the planes (the locally normalised mean): generic kernels only (no add2 / add3k: a fast launch does not compile)
+template <int CN> struct FoldNorm : WeightedMean<CN, FromPlane<PlainTables, CN>> {};
+
 // The local mode's state (definition: include/stacker.h, stk_local_params): FoldWeighted with coverage = 1 and a weight per
 // pixel. Per entry i of the frame table, in hook order entry(kappa), coords(..), add(0 .. CN - 1):
 //     omega = the bilinear sample of plane maps[i] at the entry's coordinates (four clamped loads, 0 where a tap is
@@ -347,19 +456,20 @@ struct FoldWeighted {
 //             bilinear, also under the cubic fold, whose kernel hands over the same coordinates)
 //     b = omega + floor * kappa;  u = b, (power - 1) times u = u * b;  W = w_i * u
 //     v = s * g_i,c + o_i,c * kappa;  num_c = num_c + W * v;  den = den + W * kappa
-// The table pointers (records, planes) move on after channel CN - 1.
+// The table pointers (records, planes) move on after channel CN - 1. Generic kernels only.
 template <int CN>
-struct FoldLocal {
-    float num[CN], den, kap, W;
+struct FoldLocal : WeightedSums<CN> {
+    static constexpr bool wants_kappa = true, wants_coords = true;
+    using WeightedSums<CN>::num;
+    using WeightedSums<CN>::den;
+    float kap, W;
     const stk_frame_weight* e;
     const float* const* mp;
     size_t ms;
     float floor;
     int power;
     __device__ __forceinline__ void begin(const ClipArgs& ca, int, int) {
-#pragma unroll
-        for (int c = 0; c < CN; c++) num[c] = 0.f;
-        den = 0.f; kap = 1.0f; W = 0.f;
+        this->zero(); kap = 1.0f; W = 0.f;
         e = ca.coef; mp = ca.maps; ms = ca.map_stride; floor = ca.floor; power = ca.power;
     }
     __device__ __forceinline__ void entry(float k) { kap = k; }
@@ -392,118 +502,22 @@ struct FoldLocal {
         num[c] = num[c] + W * v;
         if (c == CN - 1) { den = den + W * kap; e++; mp++; }
     }
-    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
-        float* o = ca.out + (size_t)y * ca.out_stride + (size_t)x * CN;
-#pragma unroll
-        for (int c = 0; c < CN; c++) o[c] = den > 0.f ? num[c] / den : 0.f;
-        if (ca.den) ca.den[(size_t)y * ca.den_stride + x] = den;
-    }
 };
 
-// Local normalisation (definition: include/stacker.h, "Local normalisation"; launched from kernels_local_norm.hip, generic
-// kernels only): the weighted mode and the store mode with participation, with the entry's gain and offset read from a
-// node grid instead of its record. NormAt is a destination pixel's place on that grid, computed once per pixel in begin():
-// the float offsets of its four nodes within a plane and the two fractions. The pixel's OWN y addresses the grid, also in
-// the store mode, whose band pointer is the only thing that counts rows from ClipArgs::y0. at(P, q) is component q of
-// plane P at the pixel: the mesh fold's chain (mesh_displace above), operation by operation.
-struct NormAt {
-    int o00, o01, o10, o11;
-    float u, v;
-    __device__ __forceinline__ void set(const ClipArgs& ca, int x, int y, int comps) {
-        const int k = x >> ca.norm_shift, j = y >> ca.norm_shift;
-        const int k1 = min(k + 1, ca.norm_gw - 1), j1 = min(j + 1, ca.norm_gh - 1);
-        u = (float)(x - (k << ca.norm_shift)) * ca.norm_inv; v = (float)(y - (j << ca.norm_shift)) * ca.norm_inv;
-        o00 = (j * ca.norm_gw + k) * comps; o01 = (j * ca.norm_gw + k1) * comps;
-        o10 = (j1 * ca.norm_gw + k) * comps; o11 = (j1 * ca.norm_gw + k1) * comps;
-    }
-    __device__ __forceinline__ float at(const float* __restrict__ P, int q) const {
-        const float t0 = __builtin_fmaf(u, P[o01 + q] - P[o00 + q], P[o00 + q]);
-        const float t1 = __builtin_fmaf(u, P[o11 + q] - P[o10 + q], P[o10 + q]);
-        return __builtin_fmaf(v, t1 - t0, t0);
-    }
-};
-
-// The locally normalised mean: FoldWeighted with (G, O) = the entry's plane at the pixel, or its record's gain and offset
-// where the entry has no plane (fma(u, 0, g) = g: a constant plane and a record give the same bits). The table pointers
-// (records, planes) move on after channel CN - 1.
-template <int CN>
-struct FoldNorm {
-    float num[CN], den, kap;
-    const stk_frame_weight* e;
-    const float* const* np;
-    NormAt at;
-    int cov;
-    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
-#pragma unroll
-        for (int c = 0; c < CN; c++) num[c] = 0.f;
-        den = 0.f; kap = 1.0f;
-        e = ca.coef; np = ca.norm; cov = ca.coverage;
-        at.set(ca, x, y, 2 * CN);
-    }
-    __device__ __forceinline__ void entry(float k) { kap = cov ? k : 1.0f; }
-    __device__ __forceinline__ void add(int c, float s) {
-        const float* __restrict__ P = *np;
-        const float G = P ? at.at(P, c) : e->gain[c], O = P ? at.at(P, CN + c) : e->offset[c];
-        const float v = s * G + O * kap;
-        num[c] = num[c] + e->weight * v;
-        if (c == CN - 1) { den = den + e->weight * kap; e++; np++; }
-    }
-    __device__ __forceinline__ void finish(const ClipArgs& ca, int x, int y) {
-        float* o = ca.out + (size_t)y * ca.out_stride + (size_t)x * CN;
-#pragma unroll
-        for (int c = 0; c < CN; c++) o[c] = den > 0.f ? num[c] / den : 0.f;
-        if (ca.den) ca.den[(size_t)y * ca.den_stride + x] = den;
-    }
-};
-
-// The locally normalised store mode: FoldStoreW with u = s * G + O. The record and plane tables are read through
-// constant-address-space pointers for FoldStoreW's reason (the band's stores could alias them as far as the compiler knows).
-template <int CN>
-struct FoldStoreNorm {
-    typedef const stk_frame_weight __attribute__((address_space(4))) * CoefPtr;
-    typedef const float* const __attribute__((address_space(4))) * PlanePtr;
-    float* p;
-    size_t slab;
-    CoefPtr e;
-    PlanePtr np;
-    NormAt at;
-    float v[CN];
-    int cov;
-    bool part;
-    __device__ __forceinline__ void begin(const ClipArgs& ca, int x, int y) {
-        p = ca.band + (size_t)(y - ca.y0) * ca.plane_stride + (size_t)x * CN;
-        slab = (size_t)ca.band_rows * ca.plane_stride;
-        e = (CoefPtr)(uintptr_t)ca.coef; np = (PlanePtr)(uintptr_t)ca.norm; cov = ca.coverage; part = true;
-        at.set(ca, x, y, 2 * CN);         // y, not y - y0: the grid is the destination's
-    }
-    __device__ __forceinline__ void entry(float k) { part = (e->weight > 0.0f) & (cov ? k == 1.0f : true); }
-    __device__ __forceinline__ void add(int c, float s) {
-        const float* __restrict__ P = *np;
-        const float G = P ? at.at(P, c) : e->gain[c], O = P ? at.at(P, CN + c) : e->offset[c];
-        const float u = s * G + O;
-        v[c] = part ? u : __uint_as_float(QUANTILE_ABSENT_BITS);
-        if (c == CN - 1) {
-#pragma unroll
-            for (int i = 0; i < CN; i++) p[i] = v[i];
-            p += slab; e++; np++;
-        }
-    }
-    __device__ __forceinline__ void finish(const ClipArgs&, int, int) {}
-};
-
-// The moments mode's state (generic kernel only): the thread's private f64 sums n, and per channel sum X, sum Y, sum X^2,
-// sum Y^2, sum XY with Y = entry 0's sample and X = entry i's over the stepped pixels where kappa_i == 1.0f. X and Y are
-// f32 values, so each product is exact in f64 and only the order of the additions matters: it is fixed — the thread's rows
-// in order, the xor-shuffle tree over the wave, then one partial per wave to ClipArgs::partials, which
-// moments_reduce_kernel (kernels_weighted.hip) adds in index order. No atomics.
-template <int CN>
-struct FoldMoments {
+// The overlap moments of entry i against entry 0: private f64 sums n, and per channel sum X, sum Y, sum X^2, sum Y^2,
+// sum XY with Y = entry 0's sample and X = entry i's over the pixels where `live` and kappa_i == 1.0f. X and Y are f32
+// values, so each product is exact in f64 and only the order of the additions matters. The hooks see entry 0, then entry i.
+// MASKED: whether there is a `live` to ask: FoldMoments' kernels set it per stepped row; every pixel CellMoments
+// (kernels_local_norm.hip) sees counts.
+template <int CN, bool MASKED>
+struct MomentSums : FoldTraits {
+    static constexpr bool wants_kappa = true;
     static constexpr int NM = 1 + 5 * CN;
     double S[NM];
     float Y[CN], kap;
     int which;
     bool live;
-    __device__ __forceinline__ void begin(const ClipArgs&, int, int) {
+    __device__ __forceinline__ void zero() {
 #pragma unroll
         for (int k = 0; k < NM; k++) S[k] = 0.0;
         which = 0; kap = 0.f; live = false;
@@ -512,7 +526,7 @@ struct FoldMoments {
     __device__ __forceinline__ void add(int c, float v) {
         if (which == 0) Y[c] = v;
         else {
-            const bool in = live & (kap == 1.0f);
+            const bool in = MASKED ? live & (kap == 1.0f) : kap == 1.0f;
             const double X = in ? (double)v : 0.0, Yd = in ? (double)Y[c] : 0.0;    // masked terms add +0
             if (c == 0) S[0] = S[0] + (in ? 1.0 : 0.0);
             S[1 + 5 * c] = S[1 + 5 * c] + X;
@@ -523,6 +537,18 @@ struct FoldMoments {
         }
         if (c == CN - 1) which ^= 1;
     }
+};
+
+// The moments mode's state (generic kernels only): MomentSums over the stepped pixels, of which the kernel says per stepped
+// row whether they are inside the destination (`live`). The order of the additions is fixed — the thread's rows in order,
+// the xor-shuffle tree over the wave, then one partial per wave to ClipArgs::partials, which moments_reduce_kernel
+// (kernels_weighted.hip) adds in index order. No atomics.
+template <int CN>
+struct FoldMoments : MomentSums<CN, true> {
+    static constexpr bool stepped = true;
+    using MomentSums<CN, true>::NM;
+    using MomentSums<CN, true>::S;
+    __device__ __forceinline__ void begin(const ClipArgs&, int, int) { this->zero(); }
     __device__ __forceinline__ void finish(const ClipArgs& ca, int, int) {
 #pragma unroll
         for (int k = 0; k < NM; k++) {
@@ -548,7 +574,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_u8c3_kernel(WarpArgs a, C
     const int wave = threadIdx.x >> 6;
     const int x = (blockIdx.x * WX + (wave % WX)) * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * (4 / WX) + wave / WX;
-    if constexpr (std::is_same_v<ClipState, FoldStore<3>> || std::is_same_v<ClipState, FoldStoreW<3>>) y += ca.y0;      // store mode: a band of rows (a.dh = its end)
+    if constexpr (ClipState::in_band) y += ca.y0;      // store mode: a band of rows (a.dh = its end)
     if (x >= a.dw || y >= a.dh) return;
     float* accp = a.acc + (size_t)y * a.acc_stride + (size_t)x * 3;
     f32x2 s01 = {0.f, 0.f};                   // (B, G) running sums as a register pair, R apart
@@ -700,8 +726,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_u8c3_kernel(WarpArgs a, C
                     const float v = STK_LERP(p00, p01, p10, p11);
                     if constexpr (CLIP) vr = v; else s2 = s2 + v;
                 }
-                if constexpr (std::is_same_v<ClipState, FoldWeighted<3>> || std::is_same_v<ClipState, ClipWU8C3> ||
-                              std::is_same_v<ClipState, FoldStoreW<3>> || std::is_same_v<ClipState, ClipNormU8C3>)
+                if constexpr (ClipState::wants_kappa)
                     cs.add3k(vb, vg, vr, STK_LERP(v00 ? 1.0f : 0.0f, v01 ? 1.0f : 0.0f, v10 ? 1.0f : 0.0f, v11 ? 1.0f : 0.0f));
                 else if constexpr (CLIP) cs.add3(vb, vg, vr);
             }

@@ -1,8 +1,9 @@
 // warp_coords.inc.h — a FRAGMENT of a kernel body, included inside the frame loop of the generic fold kernels (warp_body.h,
-// warp_cubic_body.h): the source coordinates of destination pixel (px, py) = (fx, fy) under table entry `fr`. Leaves
-// ix, iy (floor), ax, ay (fractions), `finite`, and under the classic path the four weights. STK_SUBPIX is the including
-// kernel's subpixel mode (a.subpixel_bits, or the constant 0). One text for every kernel that samples: the cubic fold's
-// coordinates are the linear fold's by construction.
+// warp_cubic_body.h) and of the kernels that only need the coordinates: the source coordinates of destination pixel
+// (px, py) = (fx, fy) under table entry `fr`. Leaves ix, iy (floor), ax, ay (fractions), `finite`, and under the classic
+// path the four weights w00 .. w11. The including scope provides a, fr, fx, fy, px, py (the last two are read only where
+// STK_SUBPIX != 0) and STK_SUBPIX, its subpixel mode (a.subpixel_bits, or the constant 0). One text for every kernel that
+// samples: the cubic fold's coordinates are the linear fold's by construction.
         int ix, iy;
         float ax = 0, ay = 0;
         float w00 = 0, w01 = 0, w10 = 0, w11 = 0;

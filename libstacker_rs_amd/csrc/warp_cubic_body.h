@@ -1,7 +1,8 @@
 // warp_cubic_body.h — the bicubic fold (option "warp_interpolation" = STK_INTER_CUBIC; definition: include/stacker.h,
-// "Bicubic fold"). A kernel template of its own next to warp_body.h's, speaking the same hooks (begin / entry / add /
-// finish), so every combine built on the fold gets the cubic sample from one source; the linear kernels are not touched
-// (no run-time branch in them: their instantiations keep their instructions).
+// "Bicubic fold"). A kernel template of its own next to warp_body.h's, speaking the same hooks (begin / entry / coords /
+// add / finish) and asking the same traits of its state (FoldTraits; the table of states is at the top of warp_body.h),
+// so every combine built on the fold gets the cubic sample from one source; the linear kernels are not touched (no
+// run-time branch in them: their instantiations keep their instructions).
 //   * warp_accumulate_cubic_kernel<T, CN, CLIP, ClipState>: every depth, 1 / 3 / 4 channels, every border mode and every
 //     state of the generic linear kernel, the moments mode's stepped walk included. One thread per destination pixel.
 // The coordinates are the linear fold's (warp_coords.inc.h, exact mode only: the host refuses cubic with
@@ -29,16 +30,10 @@ __device__ __forceinline__ void cubic_weights(float t, float* w) {
 // (one __global__ template, not a helper shared with the linear kernel: see the note at warp_accumulate_kernel)
 template <typename T, int CN, bool CLIP, class ClipState>
 __global__ __launch_bounds__(256) void warp_accumulate_cubic_kernel(WarpArgs a, ClipArgs ca) {
-    constexpr bool WEIGHTED = std::is_same_v<ClipState, FoldWeighted<CN>>;
-    constexpr bool MOMENTS = std::is_same_v<ClipState, FoldMoments<CN>>;
-    constexpr bool ROBUST = std::is_same_v<ClipState, ClipWGeneric<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>> ||
-                            std::is_same_v<ClipState, FoldNorm<CN>> || std::is_same_v<ClipState, FoldStoreNorm<CN>> ||
-                            std::is_same_v<ClipState, ClipNorm<CN>>;
-    constexpr bool LOCAL = std::is_same_v<ClipState, FoldLocal<CN>>;
+    constexpr bool MOMENTS = ClipState::stepped;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if constexpr (std::is_same_v<ClipState, FoldStore<CN>> || std::is_same_v<ClipState, FoldStoreW<CN>> ||
-                  std::is_same_v<ClipState, FoldStoreNorm<CN>>) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
+    if constexpr (ClipState::in_band) y += ca.y0;     // store mode: a band of rows (a.dh = its end)
     if constexpr (!MOMENTS) { if (x >= a.dw || y >= a.dh) return; }
     float* accp = a.acc + (size_t)y * a.acc_stride + (size_t)x * CN;
     float sum[CN];
@@ -60,6 +55,7 @@ __global__ __launch_bounds__(256) void warp_accumulate_cubic_kernel(WarpArgs a, 
         const WarpFrame* fr = a.frames + (MOMENTS ? f * (1 + (int)blockIdx.z) : f);
         const T* __restrict__ src = (const T*)fr->src;
 #define STK_SUBPIX 0
+#define STK_SAMPLE(c, v) if constexpr (CLIP) cs.add(c, v); else sum[c] = sum[c] + v
 #include "warp_coords.inc.h"
         // the 4 x 4 footprint (columns ix - 1 .. ix + 2, rows iy - 1 .. iy + 2) wholly inside the frame; a non-finite
         // coordinate has ix = iy = -100000 and fails by itself
@@ -69,9 +65,9 @@ __global__ __launch_bounds__(256) void warp_accumulate_cubic_kernel(WarpArgs a, 
             cubic_weights(ay, wy);
             // every tap is inside the frame: no clamps, no border selects, and kappa is exactly 1
             const T* q = src + (size_t)(iy - 1) * a.src_stride + (size_t)(ix - 1) * CN;
-            if constexpr (WEIGHTED || MOMENTS || ROBUST || LOCAL) cs.entry(1.0f);
+            if constexpr (ClipState::wants_kappa) cs.entry(1.0f);
             // the local mode's weight stays bilinear: the four inner taps of the footprint, all inside
-            if constexpr (LOCAL) cs.coords(ix, iy, ax, ay, true, false, 0.f, 0.f, 0.f, 0.f, a.sw, a.sh);
+            if constexpr (ClipState::wants_coords) cs.coords(ix, iy, ax, ay, true, false, 0.f, 0.f, 0.f, 0.f, a.sw, a.sh);
 #pragma unroll
             for (int c = 0; c < CN; c++) {
                 float hr[4];
@@ -83,12 +79,12 @@ __global__ __launch_bounds__(256) void warp_accumulate_cubic_kernel(WarpArgs a, 
                     hr[r] = __builtin_fmaf(wx[3], p3, __builtin_fmaf(wx[2], p2, __builtin_fmaf(wx[1], p1, wx[0] * p0)));
                 }
                 const float v = __builtin_fmaf(wy[3], hr[3], __builtin_fmaf(wy[2], hr[2], __builtin_fmaf(wy[1], hr[1], wy[0] * hr[0])));
-                if constexpr (CLIP) cs.add(c, v);
-                else sum[c] = sum[c] + v;
+                STK_SAMPLE(c, v);
             }
         } else {
 #include "warp_linear_sample.inc.h"
         }
+#undef STK_SAMPLE
 #undef STK_SUBPIX
     }
     } while (MOMENTS && ++rep < ca.reps);
@@ -138,23 +134,23 @@ __device__ __forceinline__ void cubic_u8c3_sample(const CubicRows& w, const floa
     vr = __builtin_fmaf(wy[3], hr[3], __builtin_fmaf(wy[2], hr[2], __builtin_fmaf(wy[1], hr[1], wy[0] * hr[0])));
 }
 
-// what warp_linear_sample.inc.h hands over, kept for the fast kernel's add3 / add3k hooks
-struct LinearCollect {
+// what warp_linear_sample.inc.h hands over, kept for the fast kernel's add3 / add3k hooks; kappa is asked for if the fast
+// state asks for it
+template <bool KAPPA>
+struct LinearCollect : FoldTraits {
+    static constexpr bool wants_kappa = KAPPA;
     float v[3], k;
     __device__ __forceinline__ void entry(float kk) { k = kk; }
     __device__ __forceinline__ void add(int c, float s) { v[c] = s; }
-    // (never called: the fragment names the local mode's hook, and this state's type does not depend on a template argument)
-    __device__ __forceinline__ void coords(int, int, float, float, bool, bool, float, float, float, float, int, int) {}
 };
 
 // WU: frames in flight per lane. MODE = false: the mean fold (running sums into a.acc); true: the hooks of FastState.
 template <bool AFFINE, int WU, bool MODE, class FastState>
 __global__ __launch_bounds__(256) void warp_accumulate_cubic_u8c3_kernel(WarpArgs a, ClipArgs ca) {
-    constexpr bool KAPPA = std::is_same_v<FastState, FoldWeighted<3>> || std::is_same_v<FastState, ClipWU8C3> ||
-                           std::is_same_v<FastState, FoldStoreW<3>> || std::is_same_v<FastState, ClipNormU8C3>;
+    constexpr bool KAPPA = FastState::wants_kappa;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if constexpr (std::is_same_v<FastState, FoldStore<3>> || std::is_same_v<FastState, FoldStoreW<3>>) y += ca.y0;      // store mode: a band of rows (a.dh = its end)
+    if constexpr (FastState::in_band) y += ca.y0;      // store mode: a band of rows (a.dh = its end)
     if (x >= a.dw || y >= a.dh) return;
     float* accp = a.acc + (size_t)y * a.acc_stride + (size_t)x * 3;
     f32x2 s01 = {0.f, 0.f};
@@ -163,7 +159,6 @@ __global__ __launch_bounds__(256) void warp_accumulate_cubic_u8c3_kernel(WarpArg
     if constexpr (MODE) st.begin(ca, x, y);
     else if (a.accumulate) { s01.x = accp[0]; s01.y = accp[1]; s2 = accp[2]; }
     const float fx = (float)x, fy = (float)y;
-    const int px = x, py = y;
     const int sw = a.sw, sh = a.sh;
     const int stride32 = (int)a.src_stride;
     const float alpha = a.alpha;
@@ -257,18 +252,17 @@ __global__ __launch_bounds__(256) void warp_accumulate_cubic_u8c3_kernel(WarpArg
                     if constexpr (MODE) st.add2(vbg, vr);
                     else { s01 = s01 + vbg; s2 = s2 + vr; }
                 } else {
-                    // the linear sample: the generic kernels' text, collected instead of folded
+                    // the linear sample: the generic kernels' text, collected instead of folded. The names the fragment asks for:
                     typedef uint8_t T;
                     constexpr int CN = 3;
-                    constexpr bool CLIP = true, WEIGHTED = KAPPA, MOMENTS = false, ROBUST = false, LOCAL = false;
                     constexpr int mode = STK_BORDER_CONSTANT;
                     const T* __restrict__ src = (const T*)fr->src;
-                    const float w00 = 0, w01 = 0, w10 = 0, w11 = 0;
-                    float sum[CN];
-                    LinearCollect cs;
-                    (void)sum; (void)px; (void)py;
+                    const float w00 = 0, w01 = 0, w10 = 0, w11 = 0;     // (the classic path's weights: exact coordinates here)
+                    LinearCollect<KAPPA> cs;
 #define STK_SUBPIX 0
+#define STK_SAMPLE(c, v) cs.add(c, v)
 #include "warp_linear_sample.inc.h"
+#undef STK_SAMPLE
 #undef STK_SUBPIX
                     if constexpr (KAPPA) st.add3k(cs.v[0], cs.v[1], cs.v[2], cs.k);
                     else if constexpr (MODE) st.add3(cs.v[0], cs.v[1], cs.v[2]);
@@ -294,7 +288,9 @@ hipError_t launch_warp_cubic_u8c3(const WarpArgs& a, const ClipArgs& c, dim3 gri
 template <int CN> using NoClipN = NoClip;   // the mean fold's state under the launcher below
 
 // The cubic launch of one fold: State<CN> as the linear launcher of the same combine would choose it for the generic
-// kernel, `grid` that launcher's generic grid (the moments pass has a z extent).
+// kernel, `grid` that launcher's generic grid (the moments pass has a z extent). No launcher hands it a Mesh<> state, and the
+// cubic kernel does not ask `displaced`: that there is no cubic mesh fold is a property of the launchers (kernels_mesh.hip
+// launches the linear generic kernel only), not of the states.
 template <bool CLIP, template <int> class State>
 hipError_t launch_warp_cubic(const WarpArgs& a, const ClipArgs& c, int depth, dim3 grid, hipStream_t s) {
     if (a.subpixel_bits != 0) return hipErrorInvalidValue;      // cubic is defined on exact coordinates only
