@@ -1343,9 +1343,9 @@ stk_status stk_keypoint_match_local_normalized_clipped(stk_ctx* ctx, const stk_f
  *   match_stars 4 .. 200, neighbours 2 .. 8, tri_tolerance finite and > 0, min_votes >= 1, refine 0 / 1, min_stars >= 4,
  *   min_inliers >= 4, method 0 / STK_METHOD_LMEDS / STK_METHOD_RANSAC (RHO, USAC: STK_NOT_IMPLEMENTED), threshold finite and
  *   > 0, border_mode as stk_keypoint_match: STK_INVALID_PARAMS otherwise. The stack forms need n >= 2 (STK_NOT_ENOUGH_FILES).
- * A multi-device context runs these calls on its first device. Follow-ups, not here: 16-bit and f32 detection, a similarity
- * or affine model for fields of fewer than about 12 stars, whole-stack star_match_* forms of each combine, a shard form, a
- * files form, an interpolated (non-piecewise) background, a device-side matcher. */
+ * A multi-device context runs these calls on its first device. 16-bit and f32 frames: the *_deep calls of the next section.
+ * Follow-ups, not here: a similarity or affine model for fields of fewer than about 12 stars, whole-stack star_match_* forms
+ * of each combine, a shard form, a files form, an interpolated (non-piecewise) background, a device-side matcher. */
 enum { STK_STAR_TILE_CAP = 32 };
 typedef struct {
     float   x, y, flux;
@@ -1388,6 +1388,45 @@ stk_status stk_star_align(stk_ctx* ctx, const stk_frames* frames, const stk_star
  * stk_finalize_mean(n - dropped), bit for bit. */
 stk_status stk_star_match(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, stk_image_f32* out,
                           int32_t* dropped, stk_frame_stats* stats_or_null);
+
+/* ---- star registration on 8-bit, 16-bit and f32 frames: an EXTENSION beyond the reference ---------------------------------
+ * The three calls above on the data the front half of a pipeline produces (stk_calibrate and stk_demosaic return u16 or f32):
+ * a star 200 - 300 counts over a 16-bit sky of sigma 40 is less than one grey level of the (g + 128) / 257 reduction. Detection
+ * runs on a 16-bit integer KEY K(p) in 0 .. 65535 (kernels_star_deep.hip); stk_star_params, stk_star, stk_star_match_lists and
+ * the matching, fits, refine and drop rules are those of the section above, to the letter.
+ * The key. Depth 8: K = the 8-bit grey above. Depth 16: K = stk_grey's 16-bit grey,
+ *   (b * 1868 + g * 9617 + r * 4899 + 2^13) >> 14. Depth 32: gf = b * 0.114f + g * 0.587f + r * 0.299f (every product and
+ *   sum rounded to f32, no contraction: stk_grey's), K = (int)fminf(fmaxf(rintf(gf * f32_scale), 0.0f), 65535.0f); a NaN
+ *   gives 0, +inf 65535, -inf 0. One-channel frames: the value itself in place of the grey. The fourth channel is not read.
+ * Detection: steps 1 - 5 of stk_star_params with K in place of g, and these changes only:
+ *   - med_T and mad_T are the exact k-th smallest K and the exact k-th smallest |K - med_T| of the tile's pixels inside the
+ *     frame (a two-level radix selection on integer histograms: no estimate, no dependence on scheduling);
+ *   - d_T = max((int)fminf(ceilf(ks * (float)mad_T), 65536.0f), min_contrast);
+ *   - min_contrast is in key units and is checked as 1 .. 65535 by these entry points; every other check is the 8-bit calls';
+ *   - S, Sx, Sy stay int32: S <= 225 * 65535 = 14 745 375, |Sx|, |Sy| <= 840 * 65535 = 55 049 400 (840 = the sum of |dx|
+ *     over the 15 x 15 window).
+ * Consequences. On 8-bit frames every output equals the 8-bit call's, bit for bit (stk_star_match_deep with alpha 1 / 255
+ *   equals stk_star_match). A one-channel u16 frame holding values <= 255 gives the stars of the u8 frame with the same
+ *   values. An f32 frame holding a u16 frame's values gives, under f32_scale = 1, the u16 frame's stars.
+ * Refusals: a null `deep`, reserved != 0, f32_scale not finite or <= 0 at depth 32, a non-finite alpha: STK_INVALID_PARAMS;
+ *   everything else as the 8-bit calls refuse. A multi-device context runs these calls on its first device. */
+typedef struct {
+    float   f32_scale;   /* depth 32 only: key = rint(grey * f32_scale), clamped; finite, > 0. Ignored at depth 8 / 16 */
+    int32_t reserved;    /* 0 */
+} stk_star_deep_params;
+
+/* stk_star_detect on the key: the same outputs. */
+stk_status stk_star_detect_deep(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params,
+                                const stk_star_deep_params* deep, stk_star* stars, int32_t* n_stars, int32_t* n_peaks_or_null);
+/* stk_star_align on the key: the stats feed any *_stack combine of the frames' own depth. */
+stk_status stk_star_align_deep(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params,
+                               const stk_star_deep_params* deep, int32_t* dropped, stk_frame_stats* stats);
+/* stk_star_align_deep, then the plain mean over frame 0 and the kept frames: by definition, and bit for bit,
+ * stk_warp_accumulate of those frames under the stats' warps in frame order (at the frames' depth, the given alpha, the
+ * params' border, never affine), then stk_finalize_mean(n - dropped). */
+stk_status stk_star_match_deep(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params,
+                               const stk_star_deep_params* deep, double alpha, stk_image_f32* out, int32_t* dropped,
+                               stk_frame_stats* stats_or_null);
 
 /* ---- frame calibration: an EXTENSION beyond the reference ---------------------------------------------------------------
  * The front half of a stacking pipeline: bias, dark and flat masters applied to every frame of a stack, defective pixels

@@ -14,7 +14,7 @@ from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_RE
                   LEAST_SQUARES, LMEDS, RANSAC, RHO, CalibrationParameters, DefectParameters, DrizzleParameters, EccMatchParameters, HipError, InvalidParams, IoError,
                   KeyPointMatchParameters, LocalNormParameters, LocalParameters, MeshParameters, MotionType, NOISE_DTYPE, NoiseParameters, NotEnoughFiles, NotImplementedYet, OpenCvError,
                   ProcessingError, QuantileParameters, RejectParameters, RobustClipParameters, SelectParameters, SigmaClipParameters, Stacker,
-                  StackerError, StarParameters, STAR_DTYPE, WeightParameters,
+                  StackerError, StarDeepParameters, StarParameters, STAR_DTYPE, WeightParameters,
                   default_stacker, ecc_match, keypoint_match, local_norm_estimate, local_norm_grid, mesh_grid, mesh_pyramid_shapes, noise_from_hist, noise_weights,
                   rank_frames,
                   star_match_lists)
@@ -23,6 +23,6 @@ __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchPa
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
            "SelectParameters", "rank_frames", "LocalParameters", "MeshParameters", "mesh_grid", "mesh_pyramid_shapes", "DrizzleParameters",
            "RejectParameters", "LocalNormParameters", "local_norm_estimate", "local_norm_grid",
-           "StarParameters", "STAR_DTYPE", "star_match_lists", "CalibrationParameters", "DefectParameters",
+           "StarParameters", "StarDeepParameters", "STAR_DTYPE", "star_match_lists", "CalibrationParameters", "DefectParameters",
            "NoiseParameters", "NOISE_DTYPE", "noise_from_hist", "noise_weights",
            "CFA_RGGB", "CFA_GRBG", "CFA_GBRG", "CFA_BGGR", "DEMOSAIC_BILINEAR", "DEMOSAIC_MHC", "DEMOSAIC_HA", "DEMOSAIC_SUPERPIXEL"]

@@ -110,6 +110,10 @@ class StarParams(C.Structure):
                 ("border_value", C.c_double * 4)]
 
 
+class StarDeepParams(C.Structure):
+    _fields_ = [("f32_scale", C.c_float), ("reserved", C.c_int32)]
+
+
 class NoiseStat(C.Structure):
     _fields_ = [("median", C.c_int32), ("mad", C.c_int32), ("res_median", C.c_int32), ("flags", C.c_int32),
                 ("sigma", C.c_double), ("kept", C.c_int64)]
@@ -337,6 +341,14 @@ SIGNATURES = {
                                   C.POINTER(FrameStats)]),
     "stk_star_match": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(StarParams), C.POINTER(ImageF32), C.POINTER(C.c_int32),
                                   C.POINTER(FrameStats)]),
+    # (the deep star calls take their stk_frames by address, as a void pointer, like the noise calls below: api.py passes
+    # byref(m.c_frames) all the same, and tests/test_cpu_star_deep.py reads the structure back through that address)
+    "stk_star_detect_deep": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(StarParams), C.POINTER(StarDeepParams), C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "stk_star_align_deep": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(StarParams), C.POINTER(StarDeepParams), C.POINTER(C.c_int32),
+                                       C.POINTER(FrameStats)]),
+    "stk_star_match_deep": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(StarParams), C.POINTER(StarDeepParams), C.c_double,
+                                       C.POINTER(ImageF32), C.POINTER(C.c_int32), C.POINTER(FrameStats)]),
     "stk_calibrate": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(Calibration), C.c_void_p, C.c_size_t]),
     "stk_defect_map": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.POINTER(DefectParams), C.c_void_p, C.c_int32, C.c_void_p]),
     "stk_image_mean": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_void_p]),

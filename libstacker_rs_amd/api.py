@@ -246,6 +246,16 @@ class StarParameters:             # extension beyond the reference: include/stac
                                float(self.ransac_reproj_threshold), int(self.border_mode), bv)
 
 
+@dataclass
+class StarDeepParameters:         # extension beyond the reference: include/stacker.h, stk_star_deep_params
+    """The key of star detection on deep frames. f32_scale: an f32 frame's key is rint(grey * f32_scale) clamped to
+    0 .. 65535 (1.0 for frames in 16-bit counts, 65535.0 for frames in 0 .. 1); not read for u8 and u16 frames."""
+    f32_scale: float = 1.0
+
+    def _c(self) -> _ffi.StarDeepParams:
+        return _ffi.StarDeepParams(float(self.f32_scale), 0)
+
+
 def star_match_lists(moving, ref, params: Optional["StarParameters"] = None):
     """Triangle matching of two star lists (stk_star_match_lists; host code, no GPU): a k x 2 int32 array of (moving index,
     reference index) pairs in ascending moving index. The lists are STAR_DTYPE arrays, or n x 2 arrays of (x, y)."""
@@ -1348,41 +1358,72 @@ class Stacker:
         return maps
 
     # -- star registration (extension beyond the reference) ------------------------------------------------
-    def star_detect(self, files, params: Optional["StarParameters"] = None, return_peaks: bool = False):
-        """The stars of every frame of an 8-bit stack (stk_star_detect), brightest first: a list of n STAR_DTYPE arrays;
-        return_peaks adds the n peak counts before truncation."""
-        m = self._stack(files)
+    def _star_detect(self, fn, m, params, extra, return_peaks):
+        """stk_star_detect / stk_star_detect_deep: `extra` = the arguments between the params and the outputs"""
         p = (params or StarParameters())._c()
         cap = max(int(p.max_stars), 1)
         stars = np.zeros((m.n, cap), STAR_DTYPE)
         n_stars = np.zeros(m.n, np.int32)
         n_peaks = np.zeros(m.n, np.int32)
-        self._check(self._lib.stk_star_detect(self._h, C.byref(m.c_frames), C.byref(p), C.c_void_p(stars.ctypes.data),
-                                              C.c_void_p(n_stars.ctypes.data), C.c_void_p(n_peaks.ctypes.data)))
+        self._check(fn(self._h, C.byref(m.c_frames), C.byref(p), *extra, C.c_void_p(stars.ctypes.data),
+                       C.c_void_p(n_stars.ctypes.data), C.c_void_p(n_peaks.ctypes.data)))
         lists = [stars[i, :n_stars[i]].copy() for i in range(m.n)]
         return (lists, n_peaks) if return_peaks else lists
+
+    def _star_align(self, fn, m, params, extra):
+        p = (params or StarParameters())._c()
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        self._check(fn(self._h, C.byref(m.c_frames), C.byref(p), *extra, C.byref(dropped), stats))
+        return dropped.value, self._stats_list(stats, m.n)
+
+    def _star_match(self, fn, m, params, extra, return_stats):
+        p = (params or StarParameters())._c()
+        out, img = self._image(m)
+        stats = (_ffi.FrameStats * m.n)()
+        dropped = C.c_int32(0)
+        self._check(fn(self._h, C.byref(m.c_frames), C.byref(p), *extra, C.byref(img), C.byref(dropped), stats))
+        return (dropped.value, out, self._stats_list(stats, m.n)) if return_stats else (dropped.value, out)
+
+    def star_detect(self, files, params: Optional["StarParameters"] = None, return_peaks: bool = False):
+        """The stars of every frame of an 8-bit stack (stk_star_detect), brightest first: a list of n STAR_DTYPE arrays;
+        return_peaks adds the n peak counts before truncation."""
+        return self._star_detect(self._lib.stk_star_detect, self._stack(files), params, (), return_peaks)
 
     star_match_lists = staticmethod(star_match_lists)
 
     def star_align(self, files, params: Optional["StarParameters"] = None):
         """Star registration without the fold (stk_star_align): (dropped, stats). The stats' warps feed any *_stack combine
         with include = [s["status"] == 0 for s in stats] and is_affine = False."""
-        m = self._stack(files)
-        p = (params or StarParameters())._c()
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        self._check(self._lib.stk_star_align(self._h, C.byref(m.c_frames), C.byref(p), C.byref(dropped), stats))
-        return dropped.value, self._stats_list(stats, m.n)
+        return self._star_align(self._lib.stk_star_align, self._stack(files), params, ())
 
     def star_match(self, files, params: Optional["StarParameters"] = None, return_stats: bool = False):
         """Star registration and the plain mean over frame 0 and the kept frames (stk_star_match): (dropped, image[, stats])."""
+        return self._star_match(self._lib.stk_star_match, self._stack(files), params, (), return_stats)
+
+    # -- star registration on 8-bit, 16-bit and f32 frames (stk_star_deep_params) ---------------------------
+    def star_detect_deep(self, files, params: Optional["StarParameters"] = None, deep: Optional["StarDeepParameters"] = None,
+                         return_peaks: bool = False):
+        """star_detect on the 16-bit key of a u8, u16 or f32 stack (stk_star_detect_deep); params.min_contrast is in key
+        units, 1 .. 65535."""
+        dp = (deep or StarDeepParameters())._c()
+        return self._star_detect(self._lib.stk_star_detect_deep, self._stack(files), params, (C.byref(dp),), return_peaks)
+
+    def star_align_deep(self, files, params: Optional["StarParameters"] = None, deep: Optional["StarDeepParameters"] = None):
+        """star_align on the key (stk_star_align_deep): (dropped, stats); the stats feed any *_stack combine of the frames."""
+        dp = (deep or StarDeepParameters())._c()
+        return self._star_align(self._lib.stk_star_align_deep, self._stack(files), params, (C.byref(dp),))
+
+    def star_match_deep(self, files, params: Optional["StarParameters"] = None, deep: Optional["StarDeepParameters"] = None,
+                        alpha: Optional[float] = None, return_stats: bool = False):
+        """star_align_deep and the plain mean of frame 0 and the kept frames at their own depth (stk_star_match_deep):
+        (dropped, image[, stats]). alpha: the fold's scale, by default 1 / 255, 1 / 65535 or 1 / f32_scale by depth."""
         m = self._stack(files)
-        p = (params or StarParameters())._c()
-        out, img = self._image(m)
-        stats = (_ffi.FrameStats * m.n)()
-        dropped = C.c_int32(0)
-        self._check(self._lib.stk_star_match(self._h, C.byref(m.c_frames), C.byref(p), C.byref(img), C.byref(dropped), stats))
-        return (dropped.value, out, self._stats_list(stats, m.n)) if return_stats else (dropped.value, out)
+        deep = deep or StarDeepParameters()
+        if alpha is None:
+            alpha = {8: 1.0 / 255.0, 16: 1.0 / 65535.0}.get(m.depth, 1.0 / float(deep.f32_scale) if deep.f32_scale else float("nan"))
+        dp = deep._c()
+        return self._star_match(self._lib.stk_star_match_deep, m, params, (C.byref(dp), C.c_double(float(alpha))), return_stats)
 
     # -- frame calibration (extension beyond the reference) -------------------------------------------------
     def _image_arg(self, x, keep, what: str = "image"):

@@ -318,6 +318,12 @@ struct StarDetectArgs {
 int star_tiles(int w, int h);
 hipError_t launch_star_detect(const void* const* frames_dev, int n, int cn, int w, int h, size_t stride_bytes, int radius, float ks,
                               int min_contrast, int min_pixels, int32_t* counts, StarRecord* records, hipStream_t s);
+// the same over frames of depth 8, 16 or 32 on the 16-bit key (kernels_star_deep.hip; definition: include/stacker.h,
+// stk_star_deep_params): exact median and MAD of 16-bit keys, min_contrast in key units, f32_scale read at depth 32 only. The
+// same counts and record slots
+hipError_t launch_star_detect_deep(const void* const* frames_dev, int n, int depth, int cn, int w, int h, size_t stride_bytes, int radius,
+                                   float ks, int min_contrast, int min_pixels, float f32_scale, int32_t* counts, StarRecord* records,
+                                   hipStream_t s);
 // the noise histograms of n 8- or 16-bit frames (cn 1, 3 or 4; frames_dev: a device array of n frame pointers) in one launch
 // (kernels_noise.hip; definition: include/stacker.h, stk_noise_stat); n <= 65535, w, h >= 3. hist: n x cn x
 // noise_hist_bins(depth) uint32, ZEROED by the caller on the same stream: per frame and channel the value histogram (256 /

@@ -17,13 +17,7 @@ __device__ __forceinline__ int reflect101(int p, int len) {
     return p;
 }
 
-// ---- grey -------------------------------------------------------------------------------------
-__device__ __forceinline__ uint16_t grey_u16(unsigned b, unsigned g, unsigned r) {
-    return (uint16_t)((b * 1868u + g * 9617u + r * 4899u + (1u << 13)) >> 14);
-}
-__device__ __forceinline__ float grey_f32(float b, float g, float r) {
-    return b * 0.114f + g * 0.587f + r * 0.299f;   // -ffp-contract=off: three roundings, as the oracle
-}
+// ---- grey (grey_u8, grey_u16, grey_f32: grey.h) -----------------------------------------------
 
 // blockIdx.z = frame of a batch: source frames `src_frame_stride` elements apart, outputs `out_frame_stride` apart
 // CN = 3 (BGR) or 4 (BGRA: cvtColor(BGR2GRAY) takes four channels and ignores the fourth, utils.rs:136-142)

@@ -5,6 +5,8 @@
 // of the frames run on the context's host pool (frame 0's triangles are built once); the fits are findHomography's
 // batched device path (homography.h), unchanged, one batch per stack as in keypoint.cpp; the fold is the plain one over the
 // table of frame 0 and the kept frames.
+// The *_deep calls (include/stacker.h, stk_star_deep_params; kernel in kernels_star_deep.hip) are the same code with another
+// launch (StarMode) and the fold at the frames' own depth under the caller's alpha.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -30,16 +32,38 @@ void star_parallel_for(stk_ctx* ctx, int n, const std::function<void(int)>& fn) 
     ctx->host_pool->run(n, fn);
 }
 
-stk_status star_check(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, bool stack_form, bool folds) {
+// which detection launch a call uses: the 8-bit kernel (stk_star_*), or the key kernel (stk_star_*_deep) with its scale
+struct StarMode { bool deep; float f32_scale; };
+
+stk_status star_check(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, bool stack_form, bool folds,
+                      const StarMode& mode = StarMode{false, 1.0f}) {
     stk_status st = check_frames(ctx, frames, stack_form, folds);
     if (st) return st;
     bool ni = false;
-    if (const char* msg = star::validate(params, &ni)) return fail(ctx, ni ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS, msg);
+    stk_star_params q;
+    const stk_star_params* checked = params;
+    if (mode.deep && params && params->min_contrast > 255 && params->min_contrast <= 65535) {   // key units: 1 .. 65535
+        q = *params; q.min_contrast = 255; checked = &q;
+    }
+    if (const char* msg = star::validate(checked, &ni)) return fail(ctx, ni ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS, msg);
     if (folds && (params->border_mode < 0 || params->border_mode > 4))
         return fail(ctx, params->border_mode == STK_BORDER_TRANSPARENT ? STK_NOT_IMPLEMENTED : STK_INVALID_PARAMS, "unsupported border mode");
-    if (frames->depth != 8)
+    if (!mode.deep && frames->depth != 8)
         return fail(ctx, STK_NOT_IMPLEMENTED, "star detection takes 8-bit frames: the statistics and moments are defined on the 8-bit integer grey");
     if (stack_form && frames->n < 2) return fail(ctx, STK_NOT_ENOUGH_FILES, "star registration needs a reference frame and at least one moving frame");
+    return STK_OK;
+}
+
+// the deep calls' own argument: checked before anything else of the call
+stk_status star_deep_mode(stk_ctx* ctx, const stk_frames* frames, const stk_star_deep_params* deep, StarMode& mode) {
+    if (!ctx) return STK_INVALID_PARAMS;
+    if (!deep) return fail(ctx, STK_INVALID_PARAMS, "null star deep parameters");
+    if (deep->reserved != 0) return fail(ctx, STK_INVALID_PARAMS, "star deep: reserved must be 0");
+    mode = StarMode{true, 1.0f};
+    if (frames && frames->depth == 32) {
+        if (!std::isfinite(deep->f32_scale) || !(deep->f32_scale > 0.0f)) return fail(ctx, STK_INVALID_PARAMS, "star deep: f32_scale must be finite and > 0");
+        mode.f32_scale = deep->f32_scale;
+    }
     return STK_OK;
 }
 
@@ -51,8 +75,8 @@ bool star_before(const StarRecord& a, const StarRecord& b) {
 
 // Detection of the whole stack: dev = the frames in HBM by frame index, lists[i] = frame i's stars (at most max_stars,
 // brightest first), n_peaks[i] = its peaks before any truncation. prep_ms of the timing: the launches' device time.
-stk_status star_detect_impl(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* p, std::vector<const void*>& dev,
-                            std::vector<std::vector<stk_star>>& lists, std::vector<int32_t>& n_peaks) {
+stk_status star_detect_impl(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* p, const StarMode& mode,
+                            std::vector<const void*>& dev, std::vector<std::vector<stk_star>>& lists, std::vector<int32_t>& n_peaks) {
     (void)hipSetDevice(ctx->device);
     const int n = frames->n, w = frames->width, h = frames->height, cn = frames->channels;
     const size_t rb = frame_row_bytes(frames), tiles = (size_t)star_tiles(w, h);
@@ -66,9 +90,14 @@ stk_status star_detect_impl(stk_ctx* ctx, const stk_frames* frames, const stk_st
     HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
     for (int f0 = 0; f0 < n; f0 += 65535) {
         const int nl = std::min(65535, n - f0);
-        HIP_TRY(launch_star_detect((const void* const*)(base + L.fptrs) + f0, nl, cn, w, h, rb, p->radius, ks, p->min_contrast, p->min_pixels,
-                                   (int32_t*)(base + L.counts) + (size_t)f0 * tiles,
-                                   (StarRecord*)(base + L.records) + (size_t)f0 * tiles * STAR_TILE_CAP, ctx->stream));
+        const void* const* fp = (const void* const*)(base + L.fptrs) + f0;
+        int32_t* cnt = (int32_t*)(base + L.counts) + (size_t)f0 * tiles;
+        StarRecord* rec = (StarRecord*)(base + L.records) + (size_t)f0 * tiles * STAR_TILE_CAP;
+        if (mode.deep)
+            HIP_TRY(launch_star_detect_deep(fp, nl, frames->depth, cn, w, h, rb, p->radius, ks, p->min_contrast, p->min_pixels, mode.f32_scale,
+                                            cnt, rec, ctx->stream));
+        else
+            HIP_TRY(launch_star_detect(fp, nl, cn, w, h, rb, p->radius, ks, p->min_contrast, p->min_pixels, cnt, rec, ctx->stream));
     }
     HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
     std::vector<int32_t> counts((size_t)n * tiles);
@@ -137,12 +166,12 @@ stk_status star_fit(stk_ctx* ctx, const stk_star_params* p, const std::vector<st
 
 // detection and steps 1 - 6: the stats of all n frames, the frames in HBM, the number of moving frames dropped. Every
 // moving frame dropped: STK_INVALID_PARAMS behind the filled stats.
-stk_status star_align_impl(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* p, stk_frame_stats* stats,
+stk_status star_align_impl(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* p, const StarMode& mode, stk_frame_stats* stats,
                            std::vector<const void*>& dev, int32_t* dropped) {
     const int n = frames->n;
     std::vector<std::vector<stk_star>> lists;
     std::vector<int32_t> n_peaks;
-    stk_status st = star_detect_impl(ctx, frames, p, dev, lists, n_peaks);
+    stk_status st = star_detect_impl(ctx, frames, p, mode, dev, lists, n_peaks);
     if (st) return st;
     HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
     std::memset(stats, 0, sizeof(stk_frame_stats) * (size_t)n);
@@ -201,20 +230,17 @@ stk_status star_align_impl(stk_ctx* ctx, const stk_frames* frames, const stk_sta
     return STK_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-stk_status stk_star_detect(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, stk_star* stars, int32_t* n_stars,
-                           int32_t* n_peaks) {
-    stk_status st = star_check(ctx, frames, params, false, false);
+// stk_star_detect / stk_star_detect_deep behind their checks
+stk_status star_detect_call(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, const StarMode& mode, stk_star* stars,
+                            int32_t* n_stars, int32_t* n_peaks) {
+    stk_status st = star_check(ctx, frames, params, false, false, mode);
     if (st) return st;
     if (!stars || !n_stars) return fail(ctx, STK_INVALID_PARAMS, "null star outputs");
     timing_begin(ctx);
     std::vector<const void*> dev;
     std::vector<std::vector<stk_star>> lists;
     std::vector<int32_t> peaks;
-    if ((st = star_detect_impl(ctx, frames, params, dev, lists, peaks))) return st;
+    if ((st = star_detect_impl(ctx, frames, params, mode, dev, lists, peaks))) return st;
     std::memset(stars, 0, sizeof(stk_star) * (size_t)frames->n * (size_t)params->max_stars);
     for (int i = 0; i < frames->n; i++) {
         n_stars[i] = (int32_t)lists[i].size();
@@ -224,19 +250,21 @@ stk_status stk_star_detect(stk_ctx* ctx, const stk_frames* frames, const stk_sta
     return STK_OK;
 }
 
-stk_status stk_star_align(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, int32_t* dropped,
-                          stk_frame_stats* stats) {
-    stk_status st = star_check(ctx, frames, params, true, false);
+stk_status star_align_call(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, const StarMode& mode, int32_t* dropped,
+                           stk_frame_stats* stats) {
+    stk_status st = star_check(ctx, frames, params, true, false, mode);
     if (st) return st;
     if (!stats) return fail(ctx, STK_INVALID_PARAMS, "null stats");
     timing_begin(ctx);
     std::vector<const void*> dev;
-    return star_align_impl(ctx, frames, params, stats, dev, dropped);
+    return star_align_impl(ctx, frames, params, mode, stats, dev, dropped);
 }
 
-stk_status stk_star_match(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, stk_image_f32* out, int32_t* dropped,
-                          stk_frame_stats* stats) {
-    stk_status st = star_check(ctx, frames, params, true, true);
+// the alignment, then the plain mean with the fold of fold_spec_keypoint's shape: the given depth and alpha, the params'
+// border, never affine
+stk_status star_match_call(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, const StarMode& mode, int depth, double alpha,
+                           stk_image_f32* out, int32_t* dropped, stk_frame_stats* stats) {
+    stk_status st = star_check(ctx, frames, params, true, true, mode);
     if (st) return st;
     if ((st = combine_check_out(ctx, out, frames))) return st;
     timing_begin(ctx);
@@ -245,9 +273,8 @@ stk_status stk_star_match(stk_ctx* ctx, const stk_frames* frames, const stk_star
     if (!stats) { own.resize(n); stats = own.data(); }
     std::vector<const void*> dev;
     int32_t nd = 0;
-    if ((st = star_align_impl(ctx, frames, params, stats, dev, &nd))) { if (dropped) *dropped = nd; return st; }
+    if ((st = star_align_impl(ctx, frames, params, mode, stats, dev, &nd))) { if (dropped) *dropped = nd; return st; }
     if (dropped) *dropped = nd;
-    // the plain mean, with the fold of fold_spec_keypoint's shape: depth 8, alpha 1 / 255, the params' border, never affine
     const size_t nel = (size_t)w * h * cn;
     stk_image_f32 sum = *out;
     if (out->location != STK_DEVICE) {
@@ -258,7 +285,7 @@ stk_status stk_star_match(stk_ctx* ctx, const stk_frames* frames, const stk_star
     entries_from_stats(n, stats, true, table);
     if ((st = entry_table_upload(ctx, frames, dev, table, 0))) return st;
     HIP_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
-    if ((st = warp_fold_enqueue(ctx, table.size(), 8, w, h, cn, frame_row_bytes(frames), 1.0 / 255.0, params->border_mode,
+    if ((st = warp_fold_enqueue(ctx, table.size(), depth, w, h, cn, frame_row_bytes(frames), alpha, params->border_mode,
                                 params->border_value, 0, sum.data, image_stride_floats(&sum), 0)))
         return st;
     HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
@@ -269,6 +296,49 @@ stk_status stk_star_match(stk_ctx* ctx, const stk_frames* frames, const stk_star
     const double fin = ctx->timing.finalize_ms;
     ctx->timing = keep; ctx->timing.warp_ms = warp_ms; ctx->timing.finalize_ms = fin;
     return st;
+}
+
+const StarMode kStarU8{false, 1.0f};
+
+}  // namespace
+
+extern "C" {
+
+stk_status stk_star_detect(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, stk_star* stars, int32_t* n_stars,
+                           int32_t* n_peaks) {
+    return star_detect_call(ctx, frames, params, kStarU8, stars, n_stars, n_peaks);
+}
+
+stk_status stk_star_align(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, int32_t* dropped,
+                          stk_frame_stats* stats) {
+    return star_align_call(ctx, frames, params, kStarU8, dropped, stats);
+}
+
+stk_status stk_star_match(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, stk_image_f32* out, int32_t* dropped,
+                          stk_frame_stats* stats) {
+    return star_match_call(ctx, frames, params, kStarU8, 8, 1.0 / 255.0, out, dropped, stats);
+}
+
+stk_status stk_star_detect_deep(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, const stk_star_deep_params* deep,
+                                stk_star* stars, int32_t* n_stars, int32_t* n_peaks) {
+    StarMode mode{};
+    if (const stk_status st = star_deep_mode(ctx, frames, deep, mode)) return st;
+    return star_detect_call(ctx, frames, params, mode, stars, n_stars, n_peaks);
+}
+
+stk_status stk_star_align_deep(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, const stk_star_deep_params* deep,
+                               int32_t* dropped, stk_frame_stats* stats) {
+    StarMode mode{};
+    if (const stk_status st = star_deep_mode(ctx, frames, deep, mode)) return st;
+    return star_align_call(ctx, frames, params, mode, dropped, stats);
+}
+
+stk_status stk_star_match_deep(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params, const stk_star_deep_params* deep,
+                               double alpha, stk_image_f32* out, int32_t* dropped, stk_frame_stats* stats) {
+    StarMode mode{};
+    if (const stk_status st = star_deep_mode(ctx, frames, deep, mode)) return st;
+    if (!std::isfinite(alpha)) return fail(ctx, STK_INVALID_PARAMS, "star match: alpha must be finite");
+    return star_match_call(ctx, frames, params, mode, frames ? frames->depth : 8, alpha, out, dropped, stats);
 }
 
 }  // extern "C"

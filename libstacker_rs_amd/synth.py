@@ -151,7 +151,7 @@ def star_motion(width: int, height: int, angle_deg: float = 0.0, tx: float = 0.0
 
 def make_star_stack(motions, width: int, height: int, n_stars: int, *, seed: int = SEED, psf_sigma: float = 1.5,
                     sky=(18.0, 28.0), noise_sigma: float = 2.0, min_peak: float = 24.0, pareto_shape: float = 1.2,
-                    channels: int = 3, fields=None, empty=()):
+                    channels: int = 3, fields=None, empty=(), depth: int = 8):
     """A seeded star field seen through known motions: returns (frames, G), frames a numpy uint8 array [n, H, W, channels]
     (channels 1: [n, H, W]), G = [n, 3, 3] float64 with frame_i(x) ~= frame_0(G_i x). motions: one 3 x 3 matrix per frame
     (frame-i pixel -> frame-0 pixel; None = identity; motions[0] should be the identity).
@@ -162,7 +162,11 @@ def make_star_stack(motions, width: int, height: int, n_stars: int, *, seed: int
     linear gradient from sky[0] to sky[1] across the frame's diagonal, in frame coordinates (it does not move with the
     stars); noise is Gaussian, seeded per frame. All channels carry the same value, so the integer grey equals it.
     fields[i]: which star field frame i shows (default 0 for all; another number is another sky); frames listed in
-    `empty` show no star at all (sky and noise only)."""
+    `empty` show no star at all (sky and noise only).
+    depth 16: uint16 frames; sky, noise_sigma and min_peak are then in 16-bit counts and the cap is 64 250 (= 250 * 257)."""
+    if depth not in (8, 16):
+        raise ValueError("depth must be 8 or 16")
+    top, cap, dtype = (255, 250.0, np.uint8) if depth == 8 else (65535, 64250.0, np.uint16)
     n = len(motions)
     G = np.stack([np.eye(3) if m is None else np.asarray(m, np.float64).reshape(3, 3) for m in motions])
     fields = [0] * n if fields is None else list(fields)
@@ -172,7 +176,7 @@ def make_star_stack(motions, width: int, height: int, n_stars: int, *, seed: int
     yy, xx = np.mgrid[0:height, 0:width].astype(np.float64)
     grad = sky[0] + (sky[1] - sky[0]) * (xx / max(width - 1, 1) + yy / max(height - 1, 1)) * 0.5
     cache = {}
-    frames = np.zeros((n, height, width), np.uint8)
+    frames = np.zeros((n, height, width), dtype)
     rad = int(math.ceil(5.0 * psf_sigma))
     for i in range(n):
         img = grad.copy()
@@ -180,7 +184,7 @@ def make_star_stack(motions, width: int, height: int, n_stars: int, *, seed: int
             if fields[i] not in cache:
                 rng = np.random.Generator(np.random.PCG64(seed + 7919 * (1 + fields[i])))
                 pos = np.stack([rng.uniform(cx - side / 2, cx + side / 2, n_field), rng.uniform(cy - side / 2, cy + side / 2, n_field)], 1)
-                amp = np.minimum(min_peak * (1.0 + rng.pareto(pareto_shape, n_field)), 250.0 - max(sky))
+                amp = np.minimum(min_peak * (1.0 + rng.pareto(pareto_shape, n_field)), cap - max(sky))
                 cache[fields[i]] = (pos, amp)
             pos, amp = cache[fields[i]]
             Gi = np.linalg.inv(G[i])                                   # frame-0 (sky) position -> frame-i pixel
@@ -197,12 +201,12 @@ def make_star_stack(motions, width: int, height: int, n_stars: int, *, seed: int
                 img[y0:y1, x0:x1] += a * np.exp(-(dx * dx + dy * dy) / (2.0 * psf_sigma * psf_sigma))
         if noise_sigma > 0:
             img += np.random.Generator(np.random.PCG64(seed + 1000 + i)).standard_normal(img.shape) * noise_sigma
-        frames[i] = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+        frames[i] = np.clip(np.rint(img), 0, top).astype(dtype)
     if channels == 1:
         return frames, G
     out = np.repeat(frames[..., None], channels, axis=3)
     if channels == 4:
-        out[..., 3] = 255
+        out[..., 3] = top
     return np.ascontiguousarray(out), G
 
 

@@ -1,0 +1,392 @@
+"""Star registration on 8-bit, 16-bit and f32 frames on the GPU (include/stacker.h, stk_star_deep_params):
+stk_star_detect_deep against the numpy restatement (tests/star_deep_restate.py) star for star and bit for bit on every
+stk_star field and on n_peaks; the header's three consequences, engine against engine; stk_star_align_deep against the
+restated pipeline on the 16-bit motions and on the faint field; stk_star_match_deep against its parts bit for bit; the
+composition with robust_clip_stack; every refusal."""
+import itertools
+
+import numpy as np
+import pytest
+
+import star_deep_restate as sd
+from libstacker_rs_amd import (BORDER_CONSTANT, BORDER_REPLICATE, InvalidParams, NotEnoughFiles, NotImplementedYet, RobustClipParameters,
+                               Stacker, StarDeepParameters, StarParameters, synth)
+from test_cpu_star import H, MOTIONS, W, motion_stack, rejects_stack
+from test_cpu_star_deep import DEEP16, FAINT_P, FAINT_STACK_P, P16, faint_stack, motion_stack16
+from test_gpu_star import _stats_equal
+
+pytestmark = pytest.mark.gpu
+DTYPES = {8: np.uint8, 16: np.uint16, 32: np.float32}
+F32 = StarDeepParameters(f32_scale=16.0)                                   # the f32 cases: keys = rint(16 v)
+
+
+@pytest.fixture(scope="module")
+def st():
+    s = Stacker(0)
+    yield s
+    s.close()
+
+
+def _np(x):
+    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+
+def _place(frame, padded, device):
+    """The frame where the call shall find it: host or device; tightly packed from an aligned base (the vector route where the
+    row stride allows it), or (padded) rows 5 elements longer from a base one element past an aligned address (the
+    element-wise route)."""
+    f3 = frame if frame.ndim == 3 else frame[..., None]
+    h, w, cn = f3.shape
+    if not padded:
+        if device:
+            import torch
+            return torch.from_numpy(np.ascontiguousarray(frame)).cuda()
+        return np.ascontiguousarray(frame)
+    row = w * cn + 5
+    if device:
+        import torch
+        big = torch.zeros(h * row + 4, dtype=torch.from_numpy(f3[:1, :1]).dtype, device="cuda")
+        assert big.data_ptr() % 16 == 0
+        rows = big[1:1 + h * row].view(h, row)
+        rows[:, :w * cn] = torch.from_numpy(np.ascontiguousarray(f3).reshape(h, w * cn)).cuda()
+        view = rows[:, :w * cn].unflatten(1, (w, cn))
+        assert view.data_ptr() == big.data_ptr() + big.element_size() and (h == 1 or view.stride(0) == row)
+        return view
+    big = np.zeros(h * row + 16, frame.dtype)
+    off = (-big.ctypes.data % 16) // big.itemsize + 1                      # one element past a 16-byte boundary
+    rows = big[off:off + h * row].reshape(h, row)
+    rows[:, :w * cn] = f3.reshape(h, w * cn)
+    view = rows[:, :w * cn].reshape(h, w, cn)
+    assert np.shares_memory(view, big) and view.strides[0] == row * big.itemsize and view.ctypes.data % 16 == big.itemsize
+    return view
+
+
+def _frame(key, depth, cn, rng):
+    """A frame of the given depth and channel count whose key is `key` (u8: 0 .. 255, u16: 0 .. 65535) or, at depth 32, a frame
+    of f32 values v with fractions, 16 v around `key`; B, G and R differ where cn >= 3, the fourth channel is noise."""
+    top = 255 if depth == 8 else 65535
+    k = np.minimum(key, top).astype(np.int64)
+    if cn == 1:
+        planes = [k]
+    else:
+        d = rng.integers(0, 3 if depth == 8 else 200, k.shape)
+        planes = [np.minimum(k + d, top), k, np.maximum(k - d, 0)] + ([rng.integers(0, top + 1, k.shape)] if cn == 4 else [])
+    f = np.stack(planes, -1) if cn > 1 else k
+    if depth == 32:
+        return (f.astype(np.float32) / np.float32(16.0) + rng.random(f.shape, dtype=np.float32) * np.float32(0.05)).astype(np.float32)
+    return f.astype(DTYPES[depth])
+
+
+def _speckle(rng, h, w, depth):
+    """noise over a few hundred keys with one pixel in 40 raised far above it, some of them in 2 x 2 groups: many peaks, ties
+    and plateaus; at depth 16 / 32 the keys span several high bytes"""
+    lo, hi = (24, 256) if depth == 8 else (3000, 65536)
+    g = rng.integers(0, lo, (h, w))
+    m = rng.random((h, w)) < 0.025
+    g[m] = rng.integers(lo + 16, hi, int(m.sum()))
+    ys, xs = np.nonzero(m & (rng.random((h, w)) < 0.3))
+    for y, x in zip(ys, xs):
+        g[y:y + 2, x:x + 2] = g[y, x]
+    return g
+
+
+def _check_detect(st, frames, p, deep, device, padded):
+    lists, peaks = st.star_detect_deep([_place(f, padded, device) for f in frames], p, deep, return_peaks=True)
+    total = 0
+    for k, f in enumerate(frames):
+        want, n_peaks = sd.detect(f, p, deep)
+        assert int(peaks[k]) == n_peaks, (k, int(peaks[k]), n_peaks)
+        assert len(lists[k]) == len(want), (k, len(lists[k]), len(want))
+        assert lists[k].tobytes() == want.tobytes(), k
+        total += len(want)
+    return total
+
+
+# depth x channels, each at the three sizes; radius, placement, row layout and frames per launch rotate so that every depth
+# meets every radius, both placements and both layouts, and every size meets both layouts at every depth
+SIZES = [(130, 70), (64, 64), (200, 129)]
+DETECT_CASES = []
+for i, (depth, cn) in enumerate(itertools.product((8, 16, 32), (1, 3, 4))):
+    for j, (w, h) in enumerate(SIZES):
+        DETECT_CASES.append((depth, cn, w, h, (2, 4, 7)[(i + j) % 3], (i + j) % 2, (i // 3 + i + j + 1) % 2, 3 if (i + j) % 3 == 0 else 1))
+
+
+@pytest.mark.parametrize("case", DETECT_CASES, ids=["d%d-c%d-%dx%d-r%d-%s-%s-n%d" % (c[0], c[1], c[2], c[3], c[4], "dev" if c[5] else "host", "padded" if c[6] else "tight", c[7])
+                                                    for c in DETECT_CASES])
+def test_detect_equals_the_restatement(st, case):
+    depth, cn, w, h, r, device, padded, n = case
+    rng = np.random.default_rng(100000 * depth + 1000 * w + 10 * cn + r)
+    frames = [_frame(_speckle(rng, h, w, depth), depth, cn, rng) for _ in range(n)]
+    mc = 1 if depth == 8 else 257
+    found = _check_detect(st, frames, StarParameters(radius=r, min_pixels=1, max_stars=1024, min_contrast=8 * mc), F32, device, padded)
+    found += _check_detect(st, frames, StarParameters(radius=r, min_pixels=2, kappa=1.0, min_contrast=3 * mc, max_stars=50), F32, device, padded)
+    assert found >= 5                                                       # the case does exercise the records
+
+
+@pytest.mark.parametrize("depth", [8, 16, 32])
+def test_both_routes_and_both_placements_give_the_same_stars(st, depth):
+    rng = np.random.default_rng(depth)
+    p = StarParameters(radius=4, min_pixels=1, max_stars=1024, min_contrast=8 if depth == 8 else 2056)
+    for cn in (1, 3, 4):
+        frames = [_frame(_speckle(rng, 129, 200, depth), depth, cn, rng) for _ in range(2)]
+        got = [st.star_detect_deep([_place(f, padded, device) for f in frames], p, F32) for padded in (0, 1) for device in (0, 1)]
+        assert len(got[0][0]) > 20
+        for other in got[1:]:
+            assert [a.tobytes() for a in other] == [a.tobytes() for a in got[0]]
+
+
+# ---- the inputs the issue names -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("depth,cn", [(16, 1), (16, 3), (32, 1), (32, 4)])
+def test_keys_over_the_full_range_in_one_tile(st, depth, cn):
+    """Tile 0: keys uniform over 0 .. 65535, so the median (about 32768, high byte 128) and the MAD (about 16384, high byte 64)
+    sit in different bins of the first radix level and the second level decides both. Tile 1: 60 % of the keys are 30000 (MAD 0,
+    d = min_contrast) among keys of the whole range. Tile 2: two values only, 300 and 40000, the median among the upper ones."""
+    rng = np.random.default_rng(7 + depth + cn)
+    k = rng.integers(0, 65536, (64, 192))
+    k[:, 64:128][rng.random((64, 64)) < 0.6] = 30000
+    k[:, 128:] = np.where(rng.random((64, 64)) < 0.49, 300, 40000)
+    med, mad, _ = sd.tile_stats(k, StarParameters())
+    assert med[0, 0] >> 8 != mad[0, 0] >> 8 and mad[0, 0] > 255 and (med[0, 1], mad[0, 1]) == (30000, 0) and (med[0, 2], mad[0, 2]) == (40000, 0)
+    frames = [_frame(k, depth, cn, rng)]
+    for p in (StarParameters(radius=2, kappa=0.1, min_pixels=1, max_stars=1024, min_contrast=1),
+              StarParameters(radius=4, kappa=1.0, min_pixels=2, max_stars=1024, min_contrast=65535),
+              StarParameters(radius=7, kappa=0.5, min_pixels=1, max_stars=1024, min_contrast=500)):
+        for device, padded in ((1, 0), (0, 1)):
+            found = _check_detect(st, frames, p, F32, device, padded)
+        assert found >= (0 if p.min_contrast == 65535 else 5)
+
+
+@pytest.mark.parametrize("depth", [16, 32])
+def test_saturated_plateau_across_a_tile_corner(st, depth):
+    k = np.full((130, 130), 2000, np.int64)
+    k[62:66, 62:66] = 65535                                                 # a saturated plateau on the corner of four tiles
+    k[20, 63] = k[20, 64] = 65535                                           # across a vertical tile border
+    k[63, 100] = k[64, 100] = 60000                                         # across a horizontal one
+    k[100, 64] = k[100, 65] = k[101, 63] = 50000                            # raster-first (64, 100): the pixel below-left comes later
+    f = k.astype(np.uint16) if depth == 16 else k.astype(np.float32) / np.float32(16.0)    # exact keys: the plateaus are ties
+    if depth == 32:
+        f[62:66, 62:66] = np.float32(1e7)                                   # far above 65535 / f32_scale: clamped to the same key
+        f[20, 63] = np.inf
+    for r in (2, 4, 7):
+        p = StarParameters(radius=r, min_pixels=2, min_contrast=1000)
+        for device in (0, 1):
+            _check_detect(st, [f], p, F32, device, 0)
+        lists = st.star_detect_deep([f], p, F32)
+        assert [(int(s["px"]), int(s["py"]), int(s["peak"])) for s in lists[0]] == [(62, 62, 65535), (64, 100, 50000), (63, 20, 65535), (100, 63, 60000)]
+
+
+def test_more_than_32_peaks_in_a_tile(st):
+    p = StarParameters(radius=2, min_pixels=1, max_stars=200, min_contrast=300)
+    g = np.full((64, 128), 1000, np.uint16)
+    vals = 4000 + 400 * np.random.default_rng(3).permutation(144)           # 144 distinct keys on a lattice of spacing r + 1
+    for k, v in enumerate(vals):
+        g[2 + 3 * (k // 12), 66 + 3 * (k % 12)] = v
+    g[30, 30] = 65000
+    lists, peaks = st.star_detect_deep([g], p, return_peaks=True)
+    assert peaks[0] == 145 and len(lists[0]) == 33
+    assert lists[0]["peak"].tolist() == [65000] + [4000 + 400 * v for v in range(143, 111, -1)]     # the 32 largest of the tile
+    g2 = np.full((64, 64), 1000, np.uint16)
+    for i in range(20):
+        for j in range(20):
+            g2[2 + 3 * i, 2 + 3 * j] = 4000 + 300 * ((7 * i + 13 * j) % 200)   # the densest lattice, repeated fluxes
+    for device, padded in ((1, 0), (0, 1)):
+        _check_detect(st, [g, g], p, None, device, padded)
+        _check_detect(st, [g2], p, None, device, padded)
+        _check_detect(st, [g2.astype(np.float32)], p, StarDeepParameters(1.0), device, padded)
+
+
+def test_constant_frames_give_no_peak(st):
+    p = StarParameters(min_pixels=1, min_contrast=1)
+    for f in [np.full((70, 130, 3), v, np.uint16) for v in (0, 30000, 65535)] + [np.full((70, 130), v, np.float32) for v in (0.0, 7.25, 1e9, -4.0, np.nan)] + \
+             [np.full((70, 130, 4), 17, np.uint8)]:
+        lists, peaks = st.star_detect_deep([f], p, F32, return_peaks=True)
+        assert len(lists[0]) == 0 and peaks[0] == 0
+
+
+@pytest.mark.parametrize("cn", [1, 3])
+def test_f32_frames_with_nan_inf_negatives_and_values_above_the_range(st, cn):
+    rng = np.random.default_rng(40 + cn)
+    f = _frame(_speckle(rng, 129, 200, 32), 32, cn, rng)
+    for value, share in ((np.nan, 0.01), (np.inf, 0.003), (-np.inf, 0.01), (-50.0, 0.05), (65535.0 / 16.0 + 1.0, 0.003), (3e38, 0.002)):
+        m = rng.random(f.shape) < share
+        f[m] = value
+    assert np.isnan(f).any() and np.isinf(f).any()
+    for r in (2, 7):
+        p = StarParameters(radius=r, min_pixels=1, max_stars=1024, min_contrast=2056)
+        for device, padded in ((1, 0), (0, 1), (1, 1)):
+            assert _check_detect(st, [f, f[::-1].copy()], p, F32, device, padded) > 20
+
+
+# ---- the header's consequences, engine against engine ---------------------------------------------------------------
+def test_on_8_bit_frames_every_output_equals_the_8_bit_calls(st):
+    import torch
+    frames, _ = rejects_stack()
+    for files in (list(frames), torch.from_numpy(frames).cuda()):
+        for p in (StarParameters(), StarParameters(radius=2, min_pixels=1, max_stars=1024, border_mode=BORDER_REPLICATE)):
+            a, pa = st.star_detect(files, p, return_peaks=True)
+            b, pb = st.star_detect_deep(files, p, return_peaks=True)
+            assert pa.tolist() == pb.tolist() and [x.tobytes() for x in a] == [x.tobytes() for x in b] and len(a[0]) > 20
+            da, sa = st.star_align(files, p)
+            db, sb = st.star_align_deep(files, p)
+            assert da == db == 2
+            for x, y in zip(sa, sb):
+                assert {k: x[k] for k in ("status", "n_keypoints", "n_matches", "n_inliers")} == {k: y[k] for k in ("status", "n_keypoints", "n_matches", "n_inliers")}
+                assert np.array_equal(x["warp"], y["warp"])
+            da, oa = st.star_match(files, p)
+            db, ob = st.star_match_deep(files, p, alpha=1.0 / 255.0)
+            dc, oc = st.star_match_deep(files, p)                           # the default alpha at depth 8
+            assert da == db == dc and np.array_equal(_np(oa), _np(ob)) and np.array_equal(_np(oa), _np(oc))
+    g1, _ = synth.make_star_stack([None], 200, 150, 40, seed=5, channels=1)
+    a = st.star_detect(list(g1))
+    assert [x.tobytes() for x in st.star_detect_deep(list(g1))] == [x.tobytes() for x in a]
+    # a one-channel u16 frame holding values <= 255 gives the stars of the u8 frame with the same values
+    assert [x.tobytes() for x in st.star_detect_deep([g1[0].astype(np.uint16)])] == [x.tobytes() for x in a] and len(a[0]) >= 20
+
+
+def test_an_f32_frame_holding_a_u16_frames_values_gives_its_stars(st):
+    g16, _ = synth.make_star_stack([None], 200, 150, 40, seed=5, channels=1, **DEEP16)
+    p = StarParameters(**P16)
+    a, pa = st.star_detect_deep(list(g16), p, return_peaks=True)
+    b, pb = st.star_detect_deep([g16[0].astype(np.float32)], p, StarDeepParameters(1.0), return_peaks=True)
+    assert len(a[0]) >= 20 and pa.tolist() == pb.tolist() and a[0].tobytes() == b[0].tobytes()
+    # and f32 values of v / 65535 under f32_scale = 65535, where every product rounds back to v
+    unit = (g16[0].astype(np.float32) / np.float32(65535.0)).astype(np.float32)
+    assert np.array_equal(sd.key(unit, StarDeepParameters(65535.0)), g16[0])
+    c = st.star_detect_deep([unit], p, StarDeepParameters(65535.0))
+    assert c[0].tobytes() == a[0].tobytes()
+
+
+# ---- stk_star_align_deep against the restated pipeline --------------------------------------------------------------
+@pytest.mark.parametrize("k", range(len(MOTIONS)))
+def test_align_equals_the_restated_pipeline_at_16_bits(st, k):
+    import torch
+    frames, G = motion_stack16(k)
+    p = StarParameters(**P16)
+    want, lists = sd.align(list(frames), p)
+    dropped, got = st.star_align_deep(torch.from_numpy(frames).cuda() if k % 2 else list(frames), p)
+    assert [a.tobytes() for a in st.star_detect_deep(list(frames), p)] == [a.tobytes() for a in lists]
+    _stats_equal(got, want, W, H)
+    assert dropped == sum(s["status"] != 0 for s in got[1:])
+    err = synth.corner_error(got[1]["warp"], G[1], W, H)
+    print(MOTIONS[k], "stars", got[0]["n_keypoints"], got[1]["n_keypoints"], "inliers", got[1]["n_inliers"], "corner error %.3f px" % err)
+    if min(len(lists[0]), len(lists[1])) >= 12:
+        assert got[1]["status"] == 0 and err <= 0.5
+
+
+def test_faint_star_stack_is_registered_within_half_a_pixel(st):
+    frames, G = faint_stack(4)
+    p = StarParameters(**FAINT_STACK_P)
+    dropped, stats = st.star_align_deep(list(frames), p)
+    errs = [synth.corner_error(s["warp"], g, W, H) for s, g in zip(stats[1:], G[1:])]
+    print("faint stack: stars", [s["n_keypoints"] for s in stats], "corner errors", np.round(errs, 3))
+    assert dropped == 0 and [s["status"] for s in stats] == [0, 0, 0, 0]
+    assert max(errs) <= 0.5
+    # the (K + 128) / 257 reduction of the same frames has no star for the 8-bit aligner
+    red = [((f.astype(np.int64) + 128) // 257).astype(np.uint8) for f in frames]
+    with pytest.raises(InvalidParams, match="All images discarded"):
+        st.star_align(red)
+
+
+# ---- stk_star_match_deep against its parts --------------------------------------------------------------------------
+@pytest.mark.parametrize("depth,cn,device,border", [(16, 3, 1, BORDER_CONSTANT), (16, 4, 0, BORDER_REPLICATE), (32, 3, 0, BORDER_CONSTANT),
+                                                    (32, 4, 1, BORDER_REPLICATE)])
+def test_match_equals_its_parts(st, depth, cn, device, border):
+    import torch
+    mots = [None, synth.star_motion(W, H, 5.0, 4.0, -3.0), None, None]
+    frames, G = synth.make_star_stack(mots, W, H, 60, seed=102, fields=[0, 0, 1, 0], empty=(3,), channels=cn, **DEEP16)
+    deep = StarDeepParameters(f32_scale=65535.0)
+    if depth == 32:
+        frames = (frames.astype(np.float32) / np.float32(65535.0)).astype(np.float32)
+    files = [torch.from_numpy(f).cuda() for f in frames] if device else list(frames)
+    p = StarParameters(border_mode=border, border_value=(0.1, 0.2, 0.3, 0.4), **P16)
+    for alpha in (None, 0.37):
+        dropped, out, stats = st.star_match_deep(files, p, deep, alpha=alpha, return_stats=True)
+        d2, stats2 = st.star_align_deep(files, p, deep)
+        assert dropped == d2 == 2 and [s["status"] for s in stats] == [0, 0, 1, 1]
+        for a, b in zip(stats, stats2):
+            assert np.array_equal(a["warp"], b["warp"]) and a["n_inliers"] == b["n_inliers"]
+        used = alpha if alpha is not None else (1.0 / 65535.0 if depth == 16 else 1.0 / 65535.0)
+        acc = None
+        for f, s in zip(frames, stats):
+            if s["status"] == 0:
+                acc = st.warp_accumulate(torch.from_numpy(f).cuda(), s["warp"], border_mode=border, border_value=p.border_value, alpha=used, acc=acc)
+        want = st.finalize_mean(acc, len(frames) - dropped)
+        assert np.array_equal(_np(out), _np(want))
+        assert float(_np(out).max()) > 0.1 * used * 65535 * (1.0 if depth == 16 else 1.0 / 65535.0)
+
+
+def test_stats_feed_robust_clip_on_the_u16_frames(st):
+    n, w, h = 6, 240, 180
+    mots = [None] + [synth.star_motion(w, h, 3.0 * i, 1.5 * i, -1.0 * i) for i in range(1, n)]
+    frames, G = synth.make_star_stack(mots, w, h, 60, seed=9, **DEEP16)
+    dropped, stats = st.star_align_deep(list(frames), StarParameters(**P16))
+    assert dropped == 0 and max(synth.corner_error(s["warp"], g, w, h) for s, g in zip(stats, G)) <= 0.5
+    warps = [s["warp"] for s in stats]
+    include = [s["status"] == 0 for s in stats]
+    out, cnt = st.robust_clip_stack(list(frames), warps, RobustClipParameters(3.0, 3.0, 0.5 / 255.0, 2), include, alpha=1.0 / 65535.0, return_counts=True)
+    assert out.shape == (h, w, 3) and cnt.shape == (h, w, 3) and np.isfinite(out).all() and cnt.max() == n
+    mean = None
+    for f, M in zip(frames, warps):
+        mean = st.warp_accumulate(f, M, alpha=1.0 / 65535.0, acc=mean)
+    mean = _np(mean) / np.float32(n)
+    inner = (slice(40, h - 40), slice(50, w - 50))                          # where every frame covers
+    assert np.abs(_np(out)[inner] - mean[inner]).mean() <= 2.0 * 257 / 65535   # the clipped combine of clean frames stays at the mean, within the noise
+
+
+# ---- refusals -------------------------------------------------------------------------------------------------------
+def test_refusals(st):
+    frames, _ = motion_stack16(4)
+    ok = list(frames)
+    okf = [f.astype(np.float32) for f in ok]
+    good = StarParameters(**P16)
+    calls = (st.star_detect_deep, st.star_align_deep, st.star_match_deep)
+    for call in calls:
+        for scale in (0.0, -1.0, float("nan"), float("inf")):
+            with pytest.raises(InvalidParams):
+                call(okf, good, StarDeepParameters(f32_scale=scale))
+        call(ok, good, StarDeepParameters(f32_scale=0.0), **({"alpha": 1.0} if call is st.star_match_deep else {}))   # not read at depth 16
+
+    class Reserved(StarDeepParameters):
+        def _c(self):
+            c = super()._c()
+            c.reserved = 1
+            return c
+
+    for call in calls:
+        with pytest.raises(InvalidParams):
+            call(ok, good, Reserved())
+    import ctypes as C
+    from libstacker_rs_amd.api import _Marshalled
+    m = _Marshalled(ok)
+    sp = good._c()
+    stars, cnt = np.zeros((2, 200), sd.sr.STAR_DTYPE), np.zeros(2, np.int32)
+    assert st._lib.stk_star_detect_deep(st._h, C.byref(m.c_frames), C.byref(sp), None, C.c_void_p(stars.ctypes.data), C.c_void_p(cnt.ctypes.data), None) == 2
+    for alpha in (float("nan"), float("inf")):
+        with pytest.raises(InvalidParams):
+            st.star_match_deep(ok, good, alpha=alpha)
+    for kw in (dict(radius=1), dict(radius=8), dict(kappa=-1.0), dict(kappa=float("nan")), dict(min_contrast=0), dict(min_contrast=65536),
+               dict(min_pixels=0), dict(min_pixels=82), dict(radius=2, min_pixels=26), dict(max_stars=3), dict(max_stars=1025),
+               dict(match_stars=3), dict(match_stars=201), dict(neighbours=1), dict(neighbours=9), dict(tri_tolerance=0.0),
+               dict(tri_tolerance=float("inf")), dict(min_votes=0), dict(refine=2), dict(min_stars=3), dict(min_inliers=3),
+               dict(method=3), dict(ransac_reproj_threshold=0.0), dict(ransac_reproj_threshold=float("nan"))):
+        for call in calls:
+            with pytest.raises(InvalidParams):
+                call(ok, StarParameters(**kw))
+    for mc in (256, 65535):                                                 # key units
+        assert len(st.star_detect_deep(ok, StarParameters(min_contrast=mc))) == 2
+    with pytest.raises(InvalidParams):
+        st.star_match_deep(ok, StarParameters(border_mode=7))
+    for method in (16, 32, 38):                                             # RHO and the USAC family
+        with pytest.raises(NotImplementedYet):
+            st.star_align_deep(ok, StarParameters(method=method))
+    for call in (st.star_align_deep, st.star_match_deep):                   # n < 2 for the stack forms
+        with pytest.raises(NotEnoughFiles):
+            call(ok[:1])
+    assert len(st.star_detect_deep(ok[:1], good)) == 1                      # detection takes one frame
+    # the 8-bit calls still refuse deep frames
+    for call in (st.star_detect, st.star_align, st.star_match):
+        with pytest.raises(NotImplementedYet):
+            call(ok)
+    # the context is still usable
+    dropped, stats = st.star_align_deep(ok, good)
+    assert dropped == 0 and stats[1]["status"] == 0
