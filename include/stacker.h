@@ -252,6 +252,9 @@ void        stk_host_free(void* p);
  *   "kp_tail_priority"   1 (default): on device-resident stacks that run in several lanes, a lane's descriptor / 2-NN / homography launches
  *                        go to a highest-priority stream (they queue behind the other lanes' large launches otherwise); 0: one stream
  *   "orb_device_cull"    1 (default): ORB's Harris cull (retainBest) and ordering run on the device; 0: on the host pool. Same keypoints
+ *   "orb_fast_all"       1 (default): ORB's FAST, non-maximum suppression and short lists run for all pyramid levels in four launches
+ *                        where the pyramid allows it (below 2^32 bytes per frame); 0: level by level, the route of larger
+ *                        pyramids. Same keypoints either way
  *   "orb_patch_blur"     1 (default): ORB's 7x7 blur is computed by the descriptor kernel, for the 45 x 40 window around each kept
  *                        keypoint only; 0: every pyramid level is blurred whole first. Same bits either way
  *   "kp_workers"         host threads for the per-frame host steps of the keypoint path (Harris cull, RANSAC)

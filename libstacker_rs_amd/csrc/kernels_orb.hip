@@ -266,8 +266,7 @@ hipError_t launch_resize_area_u8(const uint8_t* src, int sw, int sh, uint8_t* ds
 //   pass 2  list A: brighter / darker ring masks, 9-contiguous-bits test                           -> list B (corners)
 //   pass 3  list B: corner strength (min / max over the sixteen 9-arcs) into an LDS score tile
 //   pass 4  the 128 x 32 interior: strict 3x3 maximum, runByImageBorder(edge), score histogram, candidate list
-// The score map never goes to memory. Same candidates and histogram as fast_score_kernel + fast_nms_kernel (kept for
-// tiny levels); the candidate ORDER differs (atomics), which the later stages do not depend on.
+// The score map never goes to memory. The candidate ORDER depends on the atomics, which the later stages do not depend on.
 constexpr int FT_X = 128, FT_Y = 32, FT_H = 4;
 constexpr int FT_TW = FT_X + 2 * FT_H;               // 136 bytes per image-tile row
 constexpr int FT_TH = FT_Y + 2 * FT_H;               // 40 rows
@@ -767,14 +766,12 @@ hipError_t launch_fast_level(const uint8_t* img, int w, int h, int thr, int edge
                              const OrbUmax& um, hipStream_t s, int n_frames, size_t pyr_stride, size_t states_stride,
                              size_t cand_stride, size_t sel_stride) {
     const OrbBatch bs{pyr_stride, states_stride, cand_stride, sel_stride};
-    if (w >= 16 && h >= 8 && (reinterpret_cast<uintptr_t>(img) & 3) == 0 && (pyr_stride & 3) == 0) {
-        if (w > 2 * edge && h > 2 * edge) {               // otherwise runByImageBorder leaves nothing: no candidates at all
-            dim3 tgrid((w + FT_X - 1) / FT_X, (h + FT_Y - 1) / FT_Y, n_frames);
-            fast_nms_tiled_kernel<<<tgrid, 256, 0, s>>>(img, w, h, thr, edge, st, cand, cap, bs);
-        }
-    } else {
-        const hipError_t e = launch_fast_score_nms_plain(img, w, h, thr, edge, score, st, cand, cap, s, n_frames, bs);
-        if (e != hipSuccess) return e;
+    // the tiled kernel reads aligned dwords; levels are 256-byte aligned (orb_geometry), so this refuses a caller's mistake only
+    if ((reinterpret_cast<uintptr_t>(img) & 3) != 0 || (pyr_stride & 3) != 0) return hipErrorInvalidValue;
+    (void)score;
+    if (w > 2 * edge && h > 2 * edge) {                   // otherwise runByImageBorder leaves nothing: no candidates at all
+        dim3 tgrid((w + FT_X - 1) / FT_X, (h + FT_Y - 1) / FT_Y, n_frames);      // (2 * edge = 62: such a level is >= 16 x 8, what the kernel needs)
+        fast_nms_tiled_kernel<<<tgrid, 256, 0, s>>>(img, w, h, thr, edge, st, cand, cap, bs);
     }
     fast_threshold_kernel<<<n_frames, 64, 0, s>>>(st, keep, bs);
     fast_pick_kernel<<<dim3(std::min((cap + 63) / 64, 64), n_frames), 64, 0, s>>>(st, cand, cap, sel, sel_cap, bs);
@@ -888,12 +885,14 @@ __global__ __launch_bounds__(256) void gauss7_fused_kernel(const uint8_t* __rest
 // (10 byte conversions and 28 multiply-adds per 4 pixels and row), not by barriers, so the tiled kernel stays.)
 hipError_t launch_gauss7(const uint8_t* src, int w, int h, const Gauss7& k, float* tmp, uint8_t* dst, hipStream_t s,
                          int n_frames, size_t pyr_stride, size_t tmp_stride) {
-    if (w >= 8 && h >= 4 && (reinterpret_cast<uintptr_t>(src) & 3) == 0 && (pyr_stride & 3) == 0) {
-        dim3 fgrid((w + G7_X - 1) / G7_X, (h + G7_Y - 1) / G7_Y, n_frames);
-        gauss7_fused_kernel<<<fgrid, 256, 0, s>>>(src, w, h, k, dst, pyr_stride);
-        return hipGetLastError();
-    }
-    return launch_gauss7_plain(src, w, h, k, tmp, dst, s, n_frames, pyr_stride, tmp_stride);
+    // the fused kernel reads aligned dwords; levels are 256-byte aligned (orb_geometry), so this refuses a caller's mistake only
+    if ((reinterpret_cast<uintptr_t>(src) & 3) != 0 || (pyr_stride & 3) != 0) return hipErrorInvalidValue;
+    (void)tmp; (void)tmp_stride;
+    // a level narrower than 8 or lower than 4 pixels lies inside the 31-pixel border: it has no keypoint, nothing reads its blur
+    if (w < 8 || h < 4) return hipSuccess;
+    dim3 fgrid((w + G7_X - 1) / G7_X, (h + G7_Y - 1) / G7_Y, n_frames);
+    gauss7_fused_kernel<<<fgrid, 256, 0, s>>>(src, w, h, k, dst, pyr_stride);
+    return hipGetLastError();
 }
 
 // ---- rotated BRIEF ------------------------------------------------------------------------------------

@@ -1,10 +1,11 @@
-// kernels_orb_small.hip — the plain, one-thread-per-pixel forms of three ORB stages: the INTER_LINEAR_EXACT pyramid step
-// (per pixel, and tiled with per-tile coefficient tables), FAST score + 3x3 non-maximum suppression through a score plane,
-// and the separable 7x7 blur through an f32 plane. They are what the first round ran everywhere; since rounds 2-3 the
-// production path (kernels_orb.hip) uses the table-driven pyramid step, the tiled FAST + NMS of all levels in one launch and
-// the blur of the sampled patch, and comes here only for levels the tiled kernels do not take (narrower than 16 / 8 pixels,
-// not dword-aligned) or when an option asks for them as a cross-check: every production kernel is tested bit for bit against
-// the plain form it replaced (tests/test_gpu_keypoint.py, test_gpu_stages.py).
+// kernels_orb_small.hip — the plain forms of the INTER_LINEAR_EXACT pyramid step (per pixel, and tiled with per-tile
+// coefficient tables). They are what the first round ran everywhere; since rounds 2-3 the production path (kernels_orb.hip)
+// uses the table-driven pyramid step and comes here only for steps the tiled kernels do not take or when
+// "orb_resize_tables" = 0 asks for them as a cross-check (tests/test_gpu_keypoint.py).
+// (The plain FAST score + 3x3 non-maximum suppression and the separable 7x7 blur lived here too. A level that the tiled
+// kernels of kernels_orb.hip do not take is narrower than 16 or lower than 8 pixels — level rows are 256-byte aligned by
+// orb_geometry — and such a level lies inside the 31-pixel border: it has no candidate and no keypoint, nothing reads its
+// blur. What they wrote was read by nobody, so they are gone: DESIGN §4.29.)
 #include "orb_device.h"
 
 namespace stk {
@@ -132,78 +133,6 @@ hipError_t launch_resize_exact_plain(const uint8_t* src, int sw, int sh, uint8_t
     }
     dim3 grid((dw + 63) / 64, (dh + 3) / 4, n_frames);
     resize_exact_kernel<<<grid, 256, 0, s>>>(src, sw, sh, dst, dw, dh, sx, sy, frame_stride);
-    return hipGetLastError();
-}
-
-// ---- FAST score plane + 3x3 non-maximum suppression ------------------------------------------------------
-__global__ __launch_bounds__(256) void fast_score_kernel(const uint8_t* __restrict__ img, int w, int h, int thr,
-                                                         uint8_t* __restrict__ score, OrbBatch bs) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= w || y >= h) return;
-    img += blockIdx.z * bs.pyr; score += blockIdx.z * bs.pyr;
-    int s = 0;
-    if (x >= 3 && x < w - 3 && y >= 3 && y < h - 3) s = fast_score_at(img + (size_t)y * w + x, w, thr);
-    score[(size_t)y * w + x] = (uint8_t)s;
-}
-
-__global__ __launch_bounds__(256) void fast_nms_kernel(const uint8_t* __restrict__ score, int w, int h, int edge,
-                                                       OrbLevelState* st, OrbCandidate* cand, int cap, OrbBatch bs) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63) + edge, y = blockIdx.y * 4 + (threadIdx.x >> 6) + edge;
-    if (x >= w - edge || y >= h - edge) return;
-    score += blockIdx.z * bs.pyr; st += blockIdx.z * bs.states; cand += blockIdx.z * bs.cand;
-    const uint8_t* c = score + (size_t)y * w + x;
-    const int s = c[0];
-    if (!s) return;
-    if (s > c[-1] && s > c[1] && s > c[-w - 1] && s > c[-w] && s > c[-w + 1] && s > c[w - 1] && s > c[w] && s > c[w + 1]) {
-        atomicAdd(&st->hist[s], 1);
-        const int i = atomicAdd(&st->n_cand, 1);
-        if (i < cap) { cand[i].xy = x | (y << 16); cand[i].score = s; }
-    }
-}
-
-hipError_t launch_fast_score_nms_plain(const uint8_t* img, int w, int h, int thr, int edge, uint8_t* score, OrbLevelState* st, OrbCandidate* cand,
-                                       int cap, hipStream_t s, int n_frames, const OrbBatch& bs) {
-    dim3 grid((w + 63) / 64, (h + 3) / 4, n_frames);
-    fast_score_kernel<<<grid, 256, 0, s>>>(img, w, h, thr, score, bs);
-    if (w > 2 * edge && h > 2 * edge) {               // otherwise runByImageBorder leaves nothing: no candidates at all
-        dim3 g2((w - 2 * edge + 63) / 64, (h - 2 * edge + 3) / 4, n_frames);
-        fast_nms_kernel<<<g2, 256, 0, s>>>(score, w, h, edge, st, cand, cap, bs);
-    }
-    return hipGetLastError();
-}
-
-// ---- 7x7 Gaussian, separable through an f32 plane ------------------------------------------------------------
-// ---- 7x7 Gaussian on 8-bit levels -----------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gauss7_rows_kernel(const uint8_t* __restrict__ src, int w, int h, Gauss7 k,
-                                                          float* __restrict__ tmp, size_t pyr_stride, size_t tmp_stride) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= w || y >= h) return;
-    src += blockIdx.z * pyr_stride; tmp += blockIdx.z * tmp_stride;
-    const uint8_t* s = src + (size_t)y * w;
-    float acc = k.k[0] * (float)s[refl101(x - 3, w)];
-#pragma unroll
-    for (int i = 1; i < 7; i++) acc += k.k[i] * (float)s[refl101(x - 3 + i, w)];
-    tmp[(size_t)y * w + x] = acc;
-}
-
-__global__ __launch_bounds__(256) void gauss7_cols_kernel(const float* __restrict__ tmp, int w, int h, Gauss7 k,
-                                                          uint8_t* __restrict__ dst, size_t pyr_stride, size_t tmp_stride) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= w || y >= h) return;
-    tmp += blockIdx.z * tmp_stride; dst += blockIdx.z * pyr_stride;
-    float acc = k.k[3] * tmp[(size_t)y * w + x];
-#pragma unroll
-    for (int i = 1; i <= 3; i++)
-        acc += k.k[3 + i] * (tmp[(size_t)refl101(y - i, h) * w + x] + tmp[(size_t)refl101(y + i, h) * w + x]);
-    const int r = (int)__builtin_rintf(acc);
-    dst[(size_t)y * w + x] = (uint8_t)min(max(r, 0), 255);
-}
-
-hipError_t launch_gauss7_plain(const uint8_t* src, int w, int h, const Gauss7& k, float* tmp, uint8_t* dst, hipStream_t s, int n_frames,
-                               size_t pyr_stride, size_t tmp_stride) {
-    dim3 grid((w + 63) / 64, (h + 3) / 4, n_frames);
-    gauss7_rows_kernel<<<grid, 256, 0, s>>>(src, w, h, k, tmp, pyr_stride, tmp_stride);
-    gauss7_cols_kernel<<<grid, 256, 0, s>>>(tmp, w, h, k, dst, pyr_stride, tmp_stride);
     return hipGetLastError();
 }
 

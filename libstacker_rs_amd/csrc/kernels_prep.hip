@@ -68,14 +68,8 @@ hipError_t launch_grey(const void* bgr, int depth, int w, int h, size_t stride_b
     return hipGetLastError();
 }
 
-// 16-bit grey -> 8-bit grey for ORB on 16-bit stacks (BASELINE configs[4], an extension: SURVEY 8d): (g + 128) / 257
-__global__ __launch_bounds__(256) void grey16_to_8_kernel(const uint16_t* __restrict__ src, size_t n, uint8_t* __restrict__ dst) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t step = (size_t)gridDim.x * 256;
-    for (; i < n; i += step) dst[i] = (uint8_t)(((unsigned)src[i] + 128u) / 257u);
-}
-
-// BGR 16-bit frame -> 8-bit grey in one pass: grey16 by the 16U formula, then (g + 128) / 257. Batched over frames.
+// BGR 16-bit frame -> 8-bit grey for ORB on 16-bit stacks (BASELINE configs[4], an extension: SURVEY 8d) in one pass: grey16
+// by the 16U formula, then (g + 128) / 257. Batched over frames.
 __global__ __launch_bounds__(256) void bgr16_to_grey8_kernel(const uint16_t* __restrict__ src, size_t stride, int w, int h,
                                                              uint8_t* __restrict__ out, size_t src_frame_stride, size_t out_frame_stride) {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
@@ -151,12 +145,6 @@ hipError_t launch_bgr16_to_grey8(const void* bgr16, int w, int h, size_t stride_
     }
     dim3 grid((w + 255) / 256, h, n_frames);
     bgr16_to_grey8_kernel<<<grid, 256, 0, s>>>((const uint16_t*)bgr16, stride_bytes / 2, w, h, out, src_frame_bytes / 2, out_frame_elems);
-    return hipGetLastError();
-}
-
-hipError_t launch_grey16_to_8(const uint16_t* src, size_t n, uint8_t* dst, hipStream_t s) {
-    const int blocks = (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 8192));
-    grey16_to_8_kernel<<<blocks, 256, 0, s>>>(src, n, dst);
     return hipGetLastError();
 }
 
@@ -511,7 +499,7 @@ hipError_t launch_grey_blur(const void* src, int depth, int cn, int w, int h, si
     if (depth == 8 && cn == 3) grey_blur_kernel<uint8_t, 3><<<grid, 256, lds_bytes, s>>>((const uint8_t*)src, stride_bytes, w, h, taps, out, out_stride);
     else if (depth == 8 && cn == 1) grey_blur_kernel<uint8_t, 1><<<grid, 256, lds_bytes, s>>>((const uint8_t*)src, stride_bytes, w, h, taps, out, out_stride);
     else if (depth == 16 && cn == 3) grey_blur_kernel<uint16_t, 3><<<grid, 256, lds_bytes, s>>>((const uint16_t*)src, stride_bytes / 2, w, h, taps, out, out_stride);
-    else if (depth == 16 && cn == 1) grey_blur_kernel<uint16_t, 1><<<grid, 256, lds_bytes, s>>>((const uint16_t*)src, stride_bytes / 2, w, h, taps, out, out_stride);
+    // (no 16-bit grey: the only 16-bit caller is the hybrid extension, which is never scaled down and hands over BGR or BGRA frames)
     else if (depth == 32 && cn == 3) grey_blur_kernel<float, 3><<<grid, 256, lds_bytes, s>>>((const float*)src, stride_bytes / 4, w, h, taps, out, out_stride);
     else if (depth == 32 && cn == 1) grey_blur_kernel<float, 1><<<grid, 256, lds_bytes, s>>>((const float*)src, stride_bytes / 4, w, h, taps, out, out_stride);
     else if (depth == 8 && cn == 4) grey_blur_kernel<uint8_t, 4><<<grid, 256, lds_bytes, s>>>((const uint8_t*)src, stride_bytes, w, h, taps, out, out_stride);

@@ -208,7 +208,7 @@ stk_status orb_run(stk_ctx* ctx, KeypointWorkspace* ws, hipStream_t s, const Orb
         if (lw <= 6 || lh <= 6) all_ok = false;
     }
     hipError_t fe = hipErrorNotSupported;
-    if (all_ok) {
+    if (all_ok && ctx->opt_orb_fast_all) {
         fe = launch_fast_all(pyr, L, ORB_FAST_THRESHOLD, ORB_EDGE, st, ws->cand.as<OrbCandidate>(), ws->sel.as<OrbSelected>(), ORB_SEL_CAP,
                              g.umax, s, n_frames, PT, ORB_LEVELS, g.cand_total, SELF,
                              ctx->opt_orb_device_cull ? ws->kept.as<OrbKept>() : nullptr, ctx->opt_orb_device_cull ? ws->kept_cnt.as<int>() : nullptr);
@@ -817,7 +817,7 @@ stk_status keypoint_align_impl(stk_ctx* ctx, const stk_frames* frames, const stk
                 if ((st = stk_create(ctx->device, &hk))) return fail(ctx, st, "keypoint lane: helper context creation failed");
                 (void)hipSetDevice(ctx->device);
             }
-            hk->opt_kp_workers = ctx->opt_kp_workers; hk->opt_orb_patch_blur = ctx->opt_orb_patch_blur; hk->opt_orb_resize_tables = ctx->opt_orb_resize_tables; hk->opt_orb_device_cull = ctx->opt_orb_device_cull; hk->opt_kp_tail_priority = ctx->opt_kp_tail_priority; hk->opt_profile = ctx->opt_profile;
+            hk->opt_kp_workers = ctx->opt_kp_workers; hk->opt_orb_patch_blur = ctx->opt_orb_patch_blur; hk->opt_orb_resize_tables = ctx->opt_orb_resize_tables; hk->opt_orb_device_cull = ctx->opt_orb_device_cull; hk->opt_orb_fast_all = ctx->opt_orb_fast_all; hk->opt_kp_tail_priority = ctx->opt_kp_tail_priority; hk->opt_profile = ctx->opt_profile;
             hk->opt_upload_batch = ctx->opt_upload_batch;
             hk->opt_subpixel_bits = ctx->opt_subpixel_bits; hk->opt_interp = ctx->opt_interp;      // (the lanes do not fold; kept equal all the same)
             timing_begin(hk);

@@ -70,9 +70,5 @@ __device__ __forceinline__ int fast_score_at(const uint8_t* __restrict__ p, int 
 
 // the plain forms (kernels_orb_small.hip)
 hipError_t launch_resize_exact_plain(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, hipStream_t s, int n_frames, size_t frame_stride);
-hipError_t launch_fast_score_nms_plain(const uint8_t* img, int w, int h, int thr, int edge, uint8_t* score, OrbLevelState* st, OrbCandidate* cand,
-                                       int cap, hipStream_t s, int n_frames, const OrbBatch& bs);
-hipError_t launch_gauss7_plain(const uint8_t* src, int w, int h, const Gauss7& k, float* tmp, uint8_t* dst, hipStream_t s, int n_frames,
-                               size_t pyr_stride, size_t tmp_stride);
 
 }  // namespace stk

@@ -235,6 +235,7 @@ stk_status set_option_one(stk_ctx* ctx, const char* name, int64_t value) {
     else if (n == "kp_tail_priority") ctx->opt_kp_tail_priority = value != 0;
     else if (n == "orb_device_cull") ctx->opt_orb_device_cull = value != 0;
     else if (n == "orb_patch_blur") ctx->opt_orb_patch_blur = value != 0;
+    else if (n == "orb_fast_all") ctx->opt_orb_fast_all = value != 0;
     else if (n == "kp_workers") { if (value < 1 || value > 16) return fail(ctx, STK_INVALID_PARAMS, "kp_workers out of range"); ctx->opt_kp_workers = (int)value; }
     else if (n == "warp_tune") ctx->opt_warp_tune = (int)value;
     else if (n == "prep_stream") ctx->opt_prep_stream = value != 0;

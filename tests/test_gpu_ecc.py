@@ -440,3 +440,40 @@ def test_slot_groups_do_not_change_results(stacker):
     assert np.array_equal(res["dev"][0], res["host"][0]) and np.array_equal(res["dev"][0], res["dev-12-slots"][0])
     with pytest.raises(Exception):
         stacker.set_option("ecc_groups", 3)
+
+
+# "warp_tune" picks the launch shape of the u8 BGR mean fold: bits 0-1 the tile (1, 2 or 4 waves wide: 64 x 4, 128 x 2, 256 x 1
+# destinations), bits 4-5 the frames in flight (4, 8, 2). 262 x 134: a ragged last tile for every shape, in x and in y;
+# 9 frames: whole groups of 2, 4 and 8 frames in flight and an odd tail of one frame behind each.
+WARP_TUNES = [0x00, 0x01, 0x02, 0x10, 0x11, 0x12, 0x20, 0x22]
+
+
+@pytest.mark.parametrize("motion", [MotionType.Homography, MotionType.Affine], ids=["persp", "affine"])
+def test_every_warp_tune_launch_shape_folds_the_oracles_sum(stacker, motion):
+    """The stack of ecc_match under every launch shape against the oracle's fold of the same frames through the warps the call
+    reports: given the warps the fold is exact to f32 round-off, the bound of test_ecc_match_stack_matches_oracle (1e-6 per
+    folded frame before the division by N: 4e-6 covers N = 9 as it covers N = 4; and the north-star tolerance)."""
+    frames, _ = synth.make_stack(9, 262, 134)
+    host, dev = frames.numpy(), frames.cuda()
+    params = EccMatchParameters(motion, 5000, 1e-5, 5)
+    affine = motion == MotionType.Affine
+    ref = None
+    try:
+        for tune in WARP_TUNES:
+            stacker.set_option("warp_tune", tune)
+            out, stats = stacker.ecc_match(dev, params, return_stats=True)
+            assert all(s["status"] == 0 for s in stats)
+            if ref is None:
+                acc = oracle.warp_frame(host[0], np.eye(3))
+                for i in range(1, len(host)):
+                    W = np.asarray(stats[i]["warp"], np.float64)
+                    acc = oracle.warp_frame(host[i], W[:2] if affine else W, is_affine=affine, acc=acc)
+                ref = oracle.scale(acc, len(host))
+                warps = np.stack([s["warp"] for s in stats])
+                assert np.abs(warps[1:] - np.eye(3)[:warps.shape[1]]).max() > 0.5      # the frames do move
+            assert np.array_equal(np.stack([s["warp"] for s in stats]), warps), tune
+            d = np.abs(out.cpu().numpy() - ref)
+            assert d.max() <= 1e-4 * np.abs(ref).max(), (tune, d.max())
+            assert d.max() <= 4e-6, (tune, d.max())
+    finally:
+        stacker.set_option("warp_tune", 0)

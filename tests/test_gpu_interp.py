@@ -349,6 +349,15 @@ def test_every_combine_at_every_launcher_cell(st, dtype, cn, affine, interp):
     _every_combine(st, kind, (6, 70), 5, affine, interp, 2.0, (1, 2), f"cell {np.dtype(dtype).name} {cn} {affine} {interp}")
 
 
+# u8 BGR where the fast state does not apply (any border mode but BORDER_CONSTANT): the launcher then takes the generic cubic
+# kernel at <uint8_t, 3> with the combine's generic state, which the cells above (BORDER_CONSTANT: the cubic u8 BGR kernel)
+# never reach. The same 70 x 6 destinations and 5 frames.
+@pytest.mark.parametrize("affine", [True, False], ids=["affine", "persp"])
+def test_every_combine_under_cubic_where_u8_bgr_takes_the_generic_kernel(st, affine):
+    kind = (np.uint8, 3, BORDER_REPLICATE, (0, 0, 0, 0))
+    _every_combine(st, kind, (6, 70), 5, affine, INTER_CUBIC, 2.0, (1, 2), f"generic u8 bgr cubic {affine}")
+
+
 # ---- 7. whole-stack calls equal their parts ----------------------------------------------------------------------------
 def _mean_of_parts(st, frames, stats, n_total, **kw):
     """The mean fold in fold order (frame 0, then the kept frames in ascending index) by single-frame accumulates."""

@@ -438,3 +438,26 @@ def test_orb_device_cull_equals_the_host_cull(stacker):
     for i in (1, 3, 4):                                                           # and against the oracle
         ko, do = oracle.orb_detect_and_compute(imgs[i])
         assert np.array_equal(got[1][0][i][0], ko) and np.array_equal(got[1][0][i][1], do), i
+
+
+@pytest.mark.parametrize("shape", [(129, 257), (127, 383), (161, 130), (70, 70), (40, 50)])
+def test_orb_level_by_level_fast_is_bit_exact(stacker, shape):
+    """FAST, non-maximum suppression and the short lists level by level (orb_fast_all = 0: the per-level tiled kernel, the route
+    of pyramids of 2^32 bytes and more, which no test image reaches) against the oracle, exactly, on the images of
+    test_orb_tile_boundaries_bit_exact: sizes just above the 128 x 32 tile multiples in x and in y, an image barely larger than
+    the 2 x 31 px border, and one inside it (no level has an interior: nothing is launched, nothing is found)."""
+    rng = np.random.default_rng(shape[0] * 1000 + shape[1])
+    base = rng.integers(0, 256, (shape[0] // 4 + 2, shape[1] // 4 + 2), dtype=np.uint8)
+    g = np.kron(base, np.ones((4, 4), np.uint8))[: shape[0], : shape[1]]        # blocky texture: many real corners
+    g = np.clip(g.astype(np.int16) + rng.integers(-6, 7, g.shape), 0, 255).astype(np.uint8)
+    stacker.set_option("orb_fast_all", 0)
+    try:
+        kp, de = stacker.orb_detect_and_compute(g, 4096)
+    finally:
+        stacker.set_option("orb_fast_all", 1)
+    kpo, deo = oracle.orb_detect_and_compute(g)
+    assert kp.shape == kpo.shape and np.array_equal(kp, kpo) and np.array_equal(de, deo)
+    if min(shape) > 100:
+        assert len(kp) > 50
+    if min(shape) <= 62:
+        assert len(kp) == 0

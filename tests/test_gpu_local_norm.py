@@ -270,6 +270,48 @@ def test_cubic_and_classic_folds_match_the_restatement(st, option, value, back):
     assert np.array_equal(qc, qn) and np.array_equal(qo, qref)
 
 
+# The cubic folds at every depth and channel count (kernels_local_norm.hip launches the generic cubic kernel for FoldNorm and
+# FoldStoreNorm itself, through the one (depth, cn) ladder): 70 x 6 destinations, a ragged second 64-wide and 4-row tile;
+# 5 frames; step 8, a 10 x 2 grid. Affine and perspective tables alternate down the list.
+CUBIC_FORMATS = [(dt, cn) for dt in (np.uint8, np.uint16, np.float32) for cn in (1, 3, 4)]
+
+
+@pytest.mark.parametrize("dtype,cn", CUBIC_FORMATS, ids=[f"{np.dtype(dt).name}c{cn}" for dt, cn in CUBIC_FORMATS])
+def test_cubic_folds_match_the_restatement_at_every_depth_and_channel_count(st, dtype, cn):
+    idx = CUBIC_FORMATS.index((dtype, cn))
+    rng = np.random.default_rng(900 + idx)
+    n, h, w, step = 5, 6, 70, 8
+    affine = bool(idx % 2)
+    frames = random_frames(rng, n, h, w, cn, dtype)
+    warps = shifted_warps(rng, n, affine, reach=1.5)
+    planes = _random_planes(rng, n, h, w, cn, step, (2,))
+    g = rng.uniform(0.5, 2.0, (n, cn)).astype(F)
+    o = rng.uniform(-0.1, 0.1, (n, cn)).astype(F)
+    wt = rng.uniform(0.1, 2.0, n).astype(F)
+    wt[3] = 0.0
+    kw = dict(is_affine=affine, alpha=_ALPHA[dtype])
+    # kappa is the linear fold's under the cubic fold too (the exact-coordinate one)
+    kappa = engine_kappa(st, (h, w), warps, range(n), affine)
+    plain = engine_samples(st, frames, warps, range(n), **kw)
+    st.set_option("warp_interpolation", INTER_CUBIC)
+    try:
+        samples = engine_samples(st, frames, warps, range(n), **kw)
+        out, den = st.local_norm_stack(frames, warps, planes, step, g, o, wt, return_den=True, **kw)
+        qo, qc = st.quantile_stack_local_norm(frames, warps, planes, step, 0.5, g, o, wt, return_counts=True, **kw)
+    finally:
+        st.set_option("warp_interpolation", INTER_LINEAR)
+    assert not np.array_equal(plain, samples)                       # the option is in force
+    assert (kappa < 1).mean() >= 0.03 and (kappa == F(1)).mean() >= 0.3
+    ref, ref_den = norm_mean_restate(samples, kappa, planes, step, g, o, wt)
+    assert np.array_equal(den, ref_den)
+    assert np.array_equal(out, ref, equal_nan=True)
+    qref, qn = norm_quantile_restate(samples, kappa == F(1), planes, step, 0.5, g, o, wt)
+    assert np.array_equal(qc, qn)
+    assert np.array_equal(qo, qref, equal_nan=True)
+    # the planes matter: the restatement with the records instead is something else
+    assert not np.array_equal(norm_mean_restate(samples, kappa, [None] * n, step, g, o, wt)[0], ref)
+
+
 # ---- 3. whole-stack forms --------------------------------------------------------------------------------------------
 def _graded_stack():
     """A 320 x 240, N = 6 synth stack whose moving frames carry their own gain and a linear gradient."""

@@ -197,6 +197,46 @@ def test_cubic_and_classic_clips_match_the_restatement(st, option, value, back, 
     _same(mgot, norm_robust_clip_restate(samples, part, planes, step, 2.0, 2.5, FLOOR, 1, g, o))
 
 
+# The cubic clip pass at every depth and channel count (ClipNorm through the generic cubic kernel, and for u8 BGR under an
+# affine table the cubic u8 BGR kernel with ClipNormU8C3; the perspective one runs above): 70 x 6 destinations, a ragged
+# second 64-wide and 4-row tile; 5 frames, so that a clip still has k >= 3 after one rejection; step 8, a 10 x 2 grid.
+CUBIC_FORMATS = [(dt, cn) for dt in (np.uint8, np.uint16, np.float32) for cn in (1, 3, 4)]
+
+
+@pytest.mark.parametrize("dtype,cn", CUBIC_FORMATS, ids=[f"{np.dtype(dt).name}c{cn}" for dt, cn in CUBIC_FORMATS])
+def test_cubic_clips_match_the_restatement_at_every_depth_and_channel_count(st, dtype, cn):
+    idx = CUBIC_FORMATS.index((dtype, cn))
+    rng = np.random.default_rng(950 + idx)
+    n, h, w, step = 5, 6, 70, 8
+    affine = (dtype, cn) == (np.uint8, 3) or bool(idx % 2)
+    frames = random_frames(rng, n, h, w, cn, dtype)
+    warps = shifted_warps(rng, n, affine, reach=1.5)
+    planes = _planes(rng, n, h, w, cn, step, (2,))
+    g = rng.uniform(0.8, 1.25, (n, cn)).astype(F)
+    o = rng.uniform(-0.05, 0.05, (n, cn)).astype(F)
+    wt = rng.uniform(0.1, 2.0, n).astype(F)
+    kw = dict(is_affine=affine, alpha=_ALPHA[dtype])
+    # kappa is the linear fold's under the cubic fold too (the exact-coordinate one)
+    kappa = engine_kappa(st, (h, w), warps, range(n), affine)
+    plain = engine_samples(st, frames, warps, range(n), **kw)
+    st.set_option("warp_interpolation", INTER_CUBIC)
+    try:
+        samples = engine_samples(st, frames, warps, range(n), **kw)
+        got = st.clip_stack_local_norm(frames, warps, planes, step, SigmaClipParameters(1.5, 2.0, 2), g, o, wt, **RET, **kw)
+        mgot = st.robust_clip_stack_local_norm(frames, warps, planes, step, RobustClipParameters(2.0, 2.5, FLOOR, 1), g, o, wt, **RET, **kw)
+    finally:
+        st.set_option("warp_interpolation", INTER_LINEAR)
+    assert not np.array_equal(plain, samples)                       # the option is in force
+    part = kappa == F(1)
+    assert (~part).mean() >= 0.03 and part.mean() >= 0.3
+    ref = norm_clip_restate(samples, part, planes, step, 1.5, 2.0, 2, g, o, wt)
+    _same(got, ref)
+    _same(mgot, norm_robust_clip_restate(samples, part, planes, step, 2.0, 2.5, FLOOR, 1, g, o, wt))
+    assert (ref[1] < ref[1].max()).any()                            # something is rejected or uncovered
+    # the planes matter: the restatement with the records instead is something else
+    assert not np.array_equal(norm_clip_restate(samples, part, None, step, 1.5, 2.0, 2, g, o, wt)[0], ref[0])
+
+
 # ---- 5. bands ------------------------------------------------------------------------------------------------------------------
 def test_banded_median_mad_clip_addresses_the_grid_by_the_pixels_own_row(st):
     """quantile_band_rows = 7 on h = 45: bands start at rows that are no multiple of the step; the store launch must address

@@ -80,6 +80,21 @@ def test_fused_grey_blur_f32_input_and_large_kernel(stacker):
     np.testing.assert_allclose(stacker.grey_blur_f32(img8, 9), oracle.gaussian_blur_f32(oracle.grey(img8), 9), rtol=2e-6, atol=1e-4)
 
 
+@pytest.mark.parametrize("ksize", [3, 5, 7])
+def test_fused_grey_blur_bgra_deep_frames(stacker, ksize):
+    """16-bit and f32 BGRA frames (the tiled kernel at <uint16_t, 4> and <float, 4>): the grey of B, G, R — the alpha plane is
+    not read, 65535 / NaN there must not show — then the blur, under the assertions of the 16-bit and f32 BGR tests above.
+    19 x 67: one whole 64 x 16 tile and a ragged second one in x and in y."""
+    img = _rng_img(19, 67, 4, np.uint16, 13)
+    img[..., 3] = 65535
+    ref = oracle.gaussian_blur_f32(oracle.grey(np.ascontiguousarray(img[..., :3])).astype(np.float32), ksize)
+    assert np.array_equal(stacker.grey_blur_f32(img, ksize), ref)
+    imgf = _rng_img(19, 67, 4, np.float32, 14)
+    imgf[..., 3] = np.nan
+    got = stacker.grey_blur_f32(imgf, ksize)
+    np.testing.assert_allclose(got, oracle.gaussian_blur_f32(oracle.grey(np.ascontiguousarray(imgf[..., :3])), ksize), rtol=2e-6, atol=1e-6)
+
+
 H_CASES = {
     "identity": np.eye(3),
     "shift_int": np.array([[1, 0, 5], [0, 1, -3], [0, 0, 1.0]]),

@@ -1,0 +1,173 @@
+"""Which GPU test file launches which device kernel: builds and checks tests/kernel_map.tsv.
+
+    tools/kernel_coverage.py kernels                    the kernels of the tree, one `unit<TAB>mangled name` per line
+    tools/kernel_coverage.py map TRACES [--keep]        write tests/kernel_map.tsv from the traces under TRACES
+    tools/kernel_coverage.py [uncovered]                the rows of the map that no qualifying test file launched
+
+Kernels of the build: every translation unit csrc/*.hip is compiled to device-only assembly with the command the Makefile
+would run for it (`make -n -B`, so per-unit flags are included; `-c -o x.o` becomes `--cuda-device-only -S -o x.s`, as
+tools/isa_diff.py takes its input), and the `.amdhsa_kernel` lines are the kernels. At most 16 compiles run at a time.
+
+Kernels launched: TRACES holds one directory per test file, named after it (TRACES/test_gpu_drizzle/...), written by
+    rocprofv3 --kernel-trace --mangled-kernels -f csv -d TRACES/test_gpu_drizzle -- python -m pytest tests/test_gpu_drizzle.py
+Every *kernel_trace.csv below that directory counts (a test may start children, each process writes its own file). Only
+the engine's symbols (_ZN3stk...) are read, a `.kd` suffix dropped; torch's kernels are ignored. `--keep` keeps, for test
+files that TRACES does not hold, what the existing map says of them, so that only changed files need tracing again.
+
+Covered: launched by a tests/test_gpu_*.py other than test_gpu_fullsize.py and the test_gpu_00_* bench and multi-rank
+files. Exit status of `uncovered` is 1 if any row has no qualifying file. Only symbol names are read, never instructions."""
+import argparse
+import concurrent.futures
+import glob
+import os
+import re
+import shlex
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "libstacker_rs_amd", "csrc")
+MAP = os.path.join(ROOT, "tests", "kernel_map.tsv")
+HEADER = "unit\tmangled\tdemangled\ttest files"
+MAX_COMPILES = 16
+SYMBOL = re.compile(r"_ZN3stk\w+")
+
+
+def qualifies(test_file):
+    """True for the small GPU test files whose launches count as coverage."""
+    return (test_file.startswith("test_gpu_") and test_file.endswith(".py")
+            and test_file != "test_gpu_fullsize.py" and not test_file.startswith("test_gpu_00_"))
+
+
+def unit_commands(csrc=CSRC):
+    """{unit: argv} — the Makefile's own compile line of every .hip unit, turned into a device-only assembly run."""
+    dry = subprocess.run(["make", "-C", csrc, "-n", "-B", "--no-print-directory", "OBJDIR=@OBJ@"],
+                         check=True, capture_output=True, text=True).stdout
+    cmds = {}
+    for ln in dry.split("\n"):
+        argv = shlex.split(ln) if " -c -o @OBJ@/" in ln else []
+        if not argv or not argv[-1].endswith(".hip"):
+            continue
+        i = argv.index("-c")
+        assert argv[i + 1] == "-o" and argv[i + 2].startswith("@OBJ@/"), ln
+        cmds[os.path.splitext(argv[-1])[0]] = argv[:i] + ["--cuda-device-only", "-S", "-o", None] + argv[i + 3:]
+    on_disk = {os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(csrc, "*.hip"))}
+    assert set(cmds) == on_disk, ("the Makefile's dry run and csrc/*.hip disagree", sorted(set(cmds) ^ on_disk))
+    return cmds
+
+
+def build_kernels(csrc=CSRC, workdir=None):
+    """{unit: sorted mangled kernel names} of the tree under `csrc`, compiled as its Makefile compiles it."""
+    cmds = unit_commands(csrc)
+    with tempfile.TemporaryDirectory(dir=workdir) as tmp:
+        def one(unit):
+            out = os.path.join(tmp, unit + ".s")
+            argv = [out if a is None else a for a in cmds[unit]]
+            r = subprocess.run(argv, cwd=csrc, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(f"{' '.join(argv)}\n{r.stderr[-4000:]}")
+            names = set()
+            with open(out) as f:
+                for ln in f:
+                    if ln.lstrip().startswith(".amdhsa_kernel"):
+                        names.add(ln.split()[1])
+            return unit, sorted(names)
+        workers = min(MAX_COMPILES, len(os.sched_getaffinity(0)), len(cmds)) or 1
+        with concurrent.futures.ThreadPoolExecutor(workers) as pool:
+            return dict(pool.map(one, sorted(cmds)))
+
+
+def demangle(names):
+    names = list(names)
+    out = subprocess.run(["c++filt"], input="\n".join(names) + "\n", check=True, capture_output=True, text=True).stdout
+    lines = out.split("\n")[:len(names)]
+    assert len(lines) == len(names)
+    return dict(zip(names, lines))
+
+
+def launched(traces):
+    """{mangled name: set of test files} from TRACES/<test file stem>/**/*kernel_trace.csv."""
+    seen, files = {}, []
+    for d in sorted(os.listdir(traces)):
+        if not os.path.isdir(os.path.join(traces, d)):
+            continue
+        test_file = d + ".py"
+        files.append(test_file)
+        for path in glob.glob(os.path.join(traces, d, "**", "*kernel_trace.csv"), recursive=True):
+            with open(path, errors="replace") as f:
+                for name in set(SYMBOL.findall(f.read())):
+                    seen.setdefault(name, set()).add(test_file)
+    return seen, files
+
+
+def read_map(path=MAP):
+    """[(unit, mangled, demangled, [test files])] of the committed map."""
+    rows = []
+    with open(path) as f:
+        lines = f.read().split("\n")
+    assert lines[0] == HEADER, lines[0]
+    for ln in lines[1:]:
+        if not ln:
+            continue
+        unit, mangled, demangled, files = ln.split("\t")
+        rows.append((unit, mangled, demangled, [t for t in files.split(",") if t]))
+    return rows
+
+
+def write_map(kernels, seen, path=MAP):
+    pretty = demangle(n for names in kernels.values() for n in names)
+    with open(path, "w") as f:
+        f.write(HEADER + "\n")
+        for unit in sorted(kernels):
+            for n in kernels[unit]:
+                f.write(f"{unit}\t{n}\t{pretty[n]}\t{','.join(sorted(seen.get(n, ())))}\n")
+
+
+def uncovered(rows):
+    return [r for r in rows if not any(qualifies(t) for t in r[3])]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    sub = ap.add_subparsers(dest="cmd")
+    sub.add_parser("kernels")
+    m = sub.add_parser("map")
+    m.add_argument("traces")
+    m.add_argument("--keep", action="store_true")
+    m.add_argument("--out", default=MAP)
+    u = sub.add_parser("uncovered")
+    u.add_argument("--map", default=MAP)
+    args = ap.parse_args()
+    if args.cmd == "kernels":
+        for unit, names in build_kernels().items():
+            for n in names:
+                print(f"{unit}\t{n}")
+        return 0
+    if args.cmd == "map":
+        seen, traced = launched(args.traces)
+        if args.keep:
+            for _, mangled, _, files in read_map(args.out):
+                for t in files:
+                    if t not in traced:
+                        seen.setdefault(mangled, set()).add(t)
+        kernels = build_kernels()
+        known = {n for names in kernels.values() for n in names}
+        strangers = sorted(set(seen) - known)
+        if strangers:
+            print(f"{len(strangers)} traced stk kernels are not in the build (stale library?):", *strangers[:5], sep="\n  ", file=sys.stderr)
+            return 2
+        write_map(kernels, seen, args.out)
+        print(f"{args.out}: {len(known)} kernels, {len(traced)} test files traced")
+    rows = read_map(getattr(args, "map", None) or getattr(args, "out", MAP))
+    bare = uncovered(rows)
+    per_unit = {}
+    for unit, mangled, demangled, files in bare:
+        per_unit[unit] = per_unit.get(unit, 0) + 1
+        print(f"{unit}\t{mangled}\t{demangled}\t{','.join(files)}")
+    print(f"{len(bare)} of {len(rows)} kernels uncovered", *(f"{u}: {c}" for u, c in sorted(per_unit.items())), sep="\n  " if bare else "")
+    return 1 if bare else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
