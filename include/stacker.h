@@ -1431,6 +1431,125 @@ stk_status stk_star_match_deep(stk_ctx* ctx, const stk_frames* frames, const stk
                                const stk_star_deep_params* deep, double alpha, stk_image_f32* out, int32_t* dropped,
                                stk_frame_stats* stats_or_null);
 
+/* ---- star shapes per frame: FWHM, eccentricity, SNR, quality weights: an EXTENSION beyond the reference -------------------
+ * A deep-sky stacker grades a star-field frame by the size and roundness of its stars: seeing, focus drift, wind and tracking
+ * errors show there and nowhere else (stk_stack_sharpness sums gradients of 8-bit greys, which a star field's noise and star
+ * count dominate). stk_star_measure measures every detected star's shape in exact integers on the device
+ * (kernels_star_measure.hip); host code (f64, no context, no GPU) turns the measurements into per-frame quality, into scores
+ * that stk_rank_frames takes unchanged and into weights that every *_stack combine takes unchanged.
+ *
+ * 1. The measurement. Input: the frames and the star lists stk_star_detect / stk_star_detect_deep return; only px and py are
+ *    read. K is the 16-bit key of stk_star_deep_params (f32_scale at depth 32), to the letter. Per star p = (px, py), with
+ *    dx = qx - px, dy = qy - py, R = radius, Ri = ring_inner, Ro = ring_outer; everything is integer except the one multiply
+ *    and ceilf, which are detection's:
+ *    0. px - R < 0, py - R < 0, px + R > w - 1 or py + R > h - 1 (coordinates outside the frame included): flags bit 0 and
+ *       every other field 0. Decided on the host: such a star never reaches the device; the kernel guards it as well.
+ *    1. Ring: the pixels q inside the frame with Ri^2 <= dx^2 + dy^2 <= Ro^2 (a ring pixel outside the frame forms no address
+ *       and does not count). n_ring = their number, k = (n_ring + 1) / 2, bg = the exact k-th smallest K of the ring, mad =
+ *       the exact k-th smallest |K - bg| (n_ring = 0, possible only on frames narrower than the ring: bg = mad = 0).
+ *    2. thr = max((int)fminf(ceilf(ks * (float)mad), 65536.0f), min_contrast), ks = (float)((double)kappa * 1.4826).
+ *    3. Aperture: dx^2 + dy^2 <= R^2; v(q) = K(q) - bg if that is >= thr, else 0. npix = #{v > 0}, peak = max K over the
+ *       aperture, S = sum v, Sx = sum v dx, Sy = sum v dy, Sxx = sum v dx^2, Syy = sum v dy^2, Sxy = sum v dx dy, all int64
+ *       (Sxx reaches 65535 x 144 x 441 > 2^31).
+ *    4. flags bit 1: saturation > 0 and peak >= saturation. flags bit 2: npix < min_pixels or S == 0.
+ *    No result depends on scheduling: the selection is a two-level radix selection on integer histograms, the sums are
+ *    integer trees. Checks: radius 2 .. 12, ring_inner radius + 1 .. 15, ring_outer ring_inner .. 16, kappa finite and >= 0,
+ *    min_contrast 1 .. 65535, min_pixels >= 1, saturation 0 (off) or 1 .. 65535, reserved 0: STK_INVALID_PARAMS otherwise.
+ *
+ * 2. Derived values, stk_star_shape_derive (host, f64): for a shape with flags == 0, each operation rounded on its own, only
+ *    + - x / and sqrt:
+ *      mx = Sx/S;  my = Sy/S;  x = px + mx;  y = py + my
+ *      cxx = Sxx/S - mx mx;  cyy = Syy/S - my my;  cxy = Sxy/S - mx my
+ *      tr = cxx + cyy;  df = sqrt((cxx - cyy)(cxx - cyy) + 4 (cxy cxy));  l1 = (tr + df)/2;  l2 = (tr - df)/2
+ *      not (l2 > 0): flags bit 3, fwhm = ecc = snr = 0 (x, y and the moments stay)
+ *      fwhm = 2.3548200450309493 sqrt(tr/2);  ecc = sqrt(max(1 - l2/l1, 0))
+ *      snr  = S / (max(1.4826 mad, 0.5) sqrt((double)npix))
+ *    A shape with flags != 0 gets zeros in every double. These are ISOPHOTAL moments, as SExtractor's are: sums over the
+ *    pixels above thr. The FWHM of a Gaussian comes out a few per cent low, because the threshold cuts the wings; noise gives
+ *    round stars an ecc floor of 0.2 - 0.35. The values compare frames with each other; they do not fit PSFs.
+ *
+ * 3. Frame quality, scores, weights (host, no context).
+ *    stk_star_frame_quality: over frame i's shapes with flags == 0 (m of them; shapes holds n x max_stars entries, frame i
+ *      from i * max_stars, n_stars[i] of them filled), each of fwhm, ecc, snr, bg and noise (= 1.4826 mad) is the lower
+ *      median, the ((m + 1) / 2)-th smallest, each taken on its own. n_stars and n_measured = m are filled; m = 0: all 0.
+ *    stk_star_quality_scores: scores[i] = {m ? 1 / fwhm : 0, m ? 1 - ecc : 0, snr, (double)m}, higher is better; the columns
+ *      are STK_STAR_SCORE_*. stk_rank_frames orders, keeps and weights on them as on sharpness scores, select->metric naming
+ *      the column: a star stack is ranked at any depth.
+ *    stk_star_quality_weights: frame i PASSES when it is included (include_or_null), n_measured >= min_measured and
+ *      (fwhm_max == 0 or fwhm <= fwhm_max) and (ecc_max == 0 or ecc <= ecc_max). Frame `reference` (-1 = none) passes whatever
+ *      the limits say when it is included; reference >= n, < -1, not included or with n_measured == 0: STK_INVALID_PARAMS.
+ *      Over the passing frames F = min fwhm, E = max (1 - ecc), Z = max snr. w = u_i (weights_or_null[i], or 1), then
+ *      w = w (F / fwhm_i) fwhm_power times, w = w ((1 - ecc_i) / E) ecc_power times, w = w (snr_i / Z) snr_power times; a
+ *      factor whose denominator is 0 is 1. All in f64, in that order; weights_out[i] = (float)w. A failing frame gets weight
+ *      0 and include_out 0; rejected counts the included frames that failed. No passing frame, a non-finite or negative
+ *      input (fwhm, ecc, snr, u_i), limits not finite or < 0, min_measured < 1, a power outside 0 .. 4, reserved != 0, n < 1
+ *      or a null quality, params or weights_out: STK_INVALID_PARAMS. include_out and rejected may be null.
+ *
+ * 4. stk_star_match_quality_weighted. By definition, and bit for bit, it equals its parts: (1) stk_star_align_deep;
+ *    (2) stk_star_detect_deep + stk_star_measure on every frame; (3) stk_star_frame_quality; (4) stk_star_quality_weights with
+ *    include = (status == 0), reference 0 and the caller's weights_or_null as u; (5) stk_weighted_stack of the frames that
+ *    passed (include_out) under the stats' warps with records (gain 1, offset 0, weight w), the params' border, is_affine 0
+ *    and the given alpha and coverage. The refusals are the parts'; stk_star_align_deep's "every frame dropped" fails the
+ *    call behind the filled stats. The frames are not uploaded twice and detection runs once. dropped: the alignment's;
+ *    rejected: step 4's. A multi-device context uses its first device, like the other star calls. */
+typedef struct {
+    int32_t radius;                 /* aperture R, 2 .. 12, default 7 */
+    int32_t ring_inner;             /* Ri, R + 1 .. 15, default 10 */
+    int32_t ring_outer;             /* Ro, Ri .. 16, default 14 */
+    float   kappa;                  /* finite, >= 0, default 3 */
+    int32_t min_contrast;           /* 1 .. 65535, key units, default 1 */
+    int32_t min_pixels;             /* >= 1, default 5 */
+    int32_t saturation;             /* 0 = off, else 1 .. 65535, default 0 */
+    int32_t reserved;               /* 0 */
+} stk_star_measure_params;
+typedef struct {
+    int64_t S, Sx, Sy, Sxx, Syy, Sxy;
+    int32_t px, py, bg, mad, thr, npix, peak, n_ring;
+    int32_t flags;                  /* bit 0: aperture not inside the frame; bit 1: saturated; bit 2: npix < min_pixels or
+                                       S == 0; bit 3 (stk_star_shape_derive): no positive minor axis */
+    int32_t reserved;
+    double  x, y, cxx, cyy, cxy, fwhm, ecc, snr;
+} stk_star_shape;
+typedef struct {
+    double  fwhm, ecc, snr, bg, noise;   /* lower medians over the frame's shapes with flags == 0 */
+    int32_t n_stars, n_measured;
+} stk_star_quality;
+typedef struct {
+    double  fwhm_max;               /* 0 = off */
+    double  ecc_max;                /* 0 = off */
+    int32_t min_measured;           /* >= 1, default 5 */
+    int32_t fwhm_power;             /* 0 .. 4, default 2 */
+    int32_t ecc_power;              /* 0 .. 4, default 0 */
+    int32_t snr_power;              /* 0 .. 4, default 0 */
+    int32_t reserved;               /* 0 */
+} stk_star_quality_params;
+enum { STK_STAR_SCORE_FWHM = 0, STK_STAR_SCORE_ROUND = 1, STK_STAR_SCORE_SNR = 2, STK_STAR_SCORE_COUNT = 3 };
+
+/* The shapes of the stars of every frame: stars and n_stars as stk_star_detect(_deep) returned them for the same frames
+ * (n x max_stars entries, max_stars 1 .. 4096; n_stars[i] 0 .. max_stars); shapes: n x max_stars, entries from n_stars[i] on
+ * zeroed; the derived values are filled (stk_star_shape_derive). Frames of depth 8, 16 or 32, 1 / 3 / 4 channels, host or
+ * device memory, padded and misaligned rows; host frames and large stacks go through the context's workspaces as in
+ * stk_star_detect_deep. All other arguments are host memory. deep: as in stk_star_detect_deep. stk_timing.prep_ms is the
+ * device time of the measure launches. A multi-device context uses its first device. */
+stk_status stk_star_measure(stk_ctx* ctx, const stk_frames* frames, const stk_star_deep_params* deep,
+                            const stk_star_measure_params* params, const stk_star* stars, const int32_t* n_stars,
+                            int32_t max_stars, stk_star_shape* shapes);
+/* Section 2 on `count` shapes in place: reads the integers, writes the doubles and flags bit 3. count < 0 or a null list
+ * with count > 0: STK_INVALID_PARAMS. */
+stk_status stk_star_shape_derive(stk_star_shape* shapes, int32_t count);
+stk_status stk_star_frame_quality(const stk_star_shape* shapes, const int32_t* n_stars, int32_t n, int32_t max_stars,
+                                  stk_star_quality* out /* n */);
+stk_status stk_star_quality_scores(const stk_star_quality* quality, int32_t n, double* scores /* n x 4 */);
+stk_status stk_star_quality_weights(const stk_star_quality* quality, int32_t n, const stk_star_quality_params* params,
+                                    int32_t reference, const int32_t* include_or_null, const float* weights_or_null,
+                                    float* weights_out /* n */, int32_t* include_out_or_null /* n */, int32_t* rejected_or_null);
+stk_status stk_star_match_quality_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params,
+                                           const stk_star_deep_params* deep, const stk_star_measure_params* measure,
+                                           const stk_star_quality_params* quality, double alpha, int32_t coverage,
+                                           const float* weights_or_null, stk_image_f32* out, float* coverage_or_null,
+                                           int32_t* dropped, int32_t* rejected, stk_frame_weight* applied_or_null,
+                                           stk_frame_stats* stats_or_null, stk_star_quality* quality_or_null);
+
 /* ---- frame calibration: an EXTENSION beyond the reference ---------------------------------------------------------------
  * The front half of a stacking pipeline: bias, dark and flat masters applied to every frame of a stack, defective pixels
  * repaired from their neighbours, the defect map found from the masters, and the masters themselves built from stacks of

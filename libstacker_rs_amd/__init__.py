@@ -17,7 +17,9 @@ from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_RE
                   StackerError, StarDeepParameters, StarParameters, STAR_DTYPE, WeightParameters,
                   default_stacker, ecc_match, keypoint_match, local_norm_estimate, local_norm_grid, mesh_grid, mesh_pyramid_shapes, noise_from_hist, noise_weights,
                   rank_frames,
-                  star_match_lists)
+                  star_match_lists,
+                  QUALITY_DTYPE, SHAPE_DTYPE, STAR_SCORE_COUNT, STAR_SCORE_FWHM, STAR_SCORE_ROUND, STAR_SCORE_SNR, StarMeasureParameters,
+                  StarQualityParameters, star_frame_quality, star_quality_scores, star_quality_weights, star_shape_derive)
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
@@ -25,4 +27,6 @@ __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchPa
            "RejectParameters", "LocalNormParameters", "local_norm_estimate", "local_norm_grid",
            "StarParameters", "StarDeepParameters", "STAR_DTYPE", "star_match_lists", "CalibrationParameters", "DefectParameters",
            "NoiseParameters", "NOISE_DTYPE", "noise_from_hist", "noise_weights",
+           "StarMeasureParameters", "StarQualityParameters", "SHAPE_DTYPE", "QUALITY_DTYPE", "star_shape_derive", "star_frame_quality",
+           "star_quality_scores", "star_quality_weights", "STAR_SCORE_FWHM", "STAR_SCORE_ROUND", "STAR_SCORE_SNR", "STAR_SCORE_COUNT",
            "CFA_RGGB", "CFA_GRBG", "CFA_GBRG", "CFA_BGGR", "DEMOSAIC_BILINEAR", "DEMOSAIC_MHC", "DEMOSAIC_HA", "DEMOSAIC_SUPERPIXEL"]

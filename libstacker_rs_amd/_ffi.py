@@ -114,6 +114,29 @@ class StarDeepParams(C.Structure):
     _fields_ = [("f32_scale", C.c_float), ("reserved", C.c_int32)]
 
 
+class StarMeasureParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("ring_inner", C.c_int32), ("ring_outer", C.c_int32), ("kappa", C.c_float),
+                ("min_contrast", C.c_int32), ("min_pixels", C.c_int32), ("saturation", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StarShape(C.Structure):
+    _fields_ = [("S", C.c_int64), ("Sx", C.c_int64), ("Sy", C.c_int64), ("Sxx", C.c_int64), ("Syy", C.c_int64), ("Sxy", C.c_int64),
+                ("px", C.c_int32), ("py", C.c_int32), ("bg", C.c_int32), ("mad", C.c_int32), ("thr", C.c_int32), ("npix", C.c_int32),
+                ("peak", C.c_int32), ("n_ring", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+                ("x", C.c_double), ("y", C.c_double), ("cxx", C.c_double), ("cyy", C.c_double), ("cxy", C.c_double),
+                ("fwhm", C.c_double), ("ecc", C.c_double), ("snr", C.c_double)]
+
+
+class StarQuality(C.Structure):
+    _fields_ = [("fwhm", C.c_double), ("ecc", C.c_double), ("snr", C.c_double), ("bg", C.c_double), ("noise", C.c_double),
+                ("n_stars", C.c_int32), ("n_measured", C.c_int32)]
+
+
+class StarQualityParams(C.Structure):
+    _fields_ = [("fwhm_max", C.c_double), ("ecc_max", C.c_double), ("min_measured", C.c_int32), ("fwhm_power", C.c_int32),
+                ("ecc_power", C.c_int32), ("snr_power", C.c_int32), ("reserved", C.c_int32)]
+
+
 class NoiseStat(C.Structure):
     _fields_ = [("median", C.c_int32), ("mad", C.c_int32), ("res_median", C.c_int32), ("flags", C.c_int32),
                 ("sigma", C.c_double), ("kept", C.c_int64)]
@@ -349,6 +372,19 @@ SIGNATURES = {
                                        C.POINTER(FrameStats)]),
     "stk_star_match_deep": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(StarParams), C.POINTER(StarDeepParams), C.c_double,
                                        C.POINTER(ImageF32), C.POINTER(C.c_int32), C.POINTER(FrameStats)]),
+    # (star measurement: the stk_frames by address as a void pointer, like the deep star calls above)
+    "stk_star_measure": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(StarDeepParams), C.POINTER(StarMeasureParams), C.c_void_p,
+                                    C.c_void_p, C.c_int32, C.POINTER(StarShape)]),
+    "stk_star_shape_derive": (c_status, [C.POINTER(StarShape), C.c_int32]),
+    "stk_star_frame_quality": (c_status, [C.POINTER(StarShape), C.c_void_p, C.c_int32, C.c_int32, C.POINTER(StarQuality)]),
+    "stk_star_quality_scores": (c_status, [C.POINTER(StarQuality), C.c_int32, C.c_void_p]),
+    "stk_star_quality_weights": (c_status, [C.POINTER(StarQuality), C.c_int32, C.POINTER(StarQualityParams), C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "stk_star_match_quality_weighted": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(StarParams), C.POINTER(StarDeepParams),
+                                                   C.POINTER(StarMeasureParams), C.POINTER(StarQualityParams), C.c_double, C.c_int32,
+                                                   C.c_void_p, C.POINTER(ImageF32), C.c_void_p, C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32), C.POINTER(FrameWeight), C.POINTER(FrameStats),
+                                                   C.POINTER(StarQuality)]),
     "stk_calibrate": (c_status, [C.c_void_p, C.POINTER(Frames), C.POINTER(Calibration), C.c_void_p, C.c_size_t]),
     "stk_defect_map": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.POINTER(DefectParams), C.c_void_p, C.c_int32, C.c_void_p]),
     "stk_image_mean": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_void_p]),

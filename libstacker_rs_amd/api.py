@@ -279,6 +279,122 @@ def star_match_lists(moving, ref, params: Optional["StarParameters"] = None):
     return pairs[:n.value].copy()
 
 
+# one stk_star_shape and one stk_star_quality (include/stacker.h)
+SHAPE_DTYPE = np.dtype([("S", "<i8"), ("Sx", "<i8"), ("Sy", "<i8"), ("Sxx", "<i8"), ("Syy", "<i8"), ("Sxy", "<i8"),
+                        ("px", "<i4"), ("py", "<i4"), ("bg", "<i4"), ("mad", "<i4"), ("thr", "<i4"), ("npix", "<i4"), ("peak", "<i4"),
+                        ("n_ring", "<i4"), ("flags", "<i4"), ("reserved", "<i4"),
+                        ("x", "<f8"), ("y", "<f8"), ("cxx", "<f8"), ("cyy", "<f8"), ("cxy", "<f8"), ("fwhm", "<f8"), ("ecc", "<f8"),
+                        ("snr", "<f8")])
+QUALITY_DTYPE = np.dtype([("fwhm", "<f8"), ("ecc", "<f8"), ("snr", "<f8"), ("bg", "<f8"), ("noise", "<f8"), ("n_stars", "<i4"),
+                          ("n_measured", "<i4")])
+STAR_SCORE_FWHM, STAR_SCORE_ROUND, STAR_SCORE_SNR, STAR_SCORE_COUNT = 0, 1, 2, 3
+
+
+@dataclass
+class StarMeasureParameters:      # extension beyond the reference: include/stacker.h, stk_star_measure_params
+    """Star measurement on the 16-bit key. The background and its MAD are the exact medians of the ring ring_inner ..
+    ring_outer around the star; the moments are summed over the aperture of `radius` on the pixels at least
+    max(ceil(kappa 1.4826 MAD), min_contrast) above the background. A star with fewer than min_pixels such pixels, or with a
+    peak at or above `saturation` (0 = off), is flagged and takes no part in a frame's quality."""
+    radius: int = 7
+    ring_inner: int = 10
+    ring_outer: int = 14
+    kappa: float = 3.0
+    min_contrast: int = 1
+    min_pixels: int = 5
+    saturation: int = 0
+
+    def _c(self) -> _ffi.StarMeasureParams:
+        return _ffi.StarMeasureParams(int(self.radius), int(self.ring_inner), int(self.ring_outer), float(self.kappa),
+                                      int(self.min_contrast), int(self.min_pixels), int(self.saturation), 0)
+
+
+@dataclass
+class StarQualityParameters:      # extension beyond the reference: include/stacker.h, stk_star_quality_params
+    """How a frame's star quality becomes its weight: a frame with fewer than min_measured measured stars, a median FWHM
+    above fwhm_max or a median eccentricity above ecc_max (0 = no limit) is rejected; a kept frame's weight is
+    (best FWHM / FWHM)^fwhm_power x (roundness / best roundness)^ecc_power x (SNR / best SNR)^snr_power, powers 0 .. 4."""
+    fwhm_max: float = 0.0
+    ecc_max: float = 0.0
+    min_measured: int = 5
+    fwhm_power: int = 2
+    ecc_power: int = 0
+    snr_power: int = 0
+
+    def _c(self) -> _ffi.StarQualityParams:
+        return _ffi.StarQualityParams(float(self.fwhm_max), float(self.ecc_max), int(self.min_measured), int(self.fwhm_power),
+                                      int(self.ecc_power), int(self.snr_power), 0)
+
+
+def _shape_table(shapes):
+    """A list of per-frame SHAPE_DTYPE arrays (or one n x max_stars array) as (n x max_stars array, n counts)."""
+    if isinstance(shapes, np.ndarray) and shapes.ndim == 2:
+        tab = np.ascontiguousarray(shapes.astype(SHAPE_DTYPE, copy=False))
+        return tab, np.full(tab.shape[0], tab.shape[1], np.int32)
+    lists = [np.asarray(s, SHAPE_DTYPE).reshape(-1) for s in shapes]
+    tab = np.zeros((len(lists), max([len(s) for s in lists] + [1])), SHAPE_DTYPE)
+    for i, s in enumerate(lists):
+        tab[i, :len(s)] = s
+    return tab, np.array([len(s) for s in lists], np.int32)
+
+
+def star_shape_derive(shapes):
+    """stk_star_shape_derive on a SHAPE_DTYPE array of any shape: a copy with x, y, the central moments, fwhm, ecc and snr
+    filled from the integer sums (and flags bit 3 where there is no positive minor axis). Host code: needs the library, not a
+    GPU."""
+    s = np.array(shapes, SHAPE_DTYPE, copy=True, order="C")
+    st = _ffi.load().stk_star_shape_derive(s.ctypes.data_as(C.POINTER(_ffi.StarShape)), s.size)
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("star_shape_derive: a list of shapes expected")
+    return s
+
+
+def star_frame_quality(shapes):
+    """stk_star_frame_quality: one QUALITY_DTYPE record per frame from the frames' shapes (Stacker.star_measure): the lower
+    medians of fwhm, ecc, snr, bg and 1.4826 mad over the shapes with flags == 0. Host code."""
+    tab, counts = _shape_table(shapes)
+    n = tab.shape[0]
+    out = np.zeros(max(n, 1), QUALITY_DTYPE)
+    st = _ffi.load().stk_star_frame_quality(tab.ctypes.data_as(C.POINTER(_ffi.StarShape)), C.c_void_p(counts.ctypes.data), n, tab.shape[1],
+                                            out.ctypes.data_as(C.POINTER(_ffi.StarQuality)))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("star_frame_quality: at least one frame's shapes expected")
+    return out[:n]
+
+
+def star_quality_scores(quality):
+    """stk_star_quality_scores: an n x 4 float64 array (1 / fwhm, 1 - ecc, snr, measured stars; higher is better) that
+    rank_frames takes with SelectParameters(metric=STAR_SCORE_*). Host code."""
+    q = np.ascontiguousarray(np.asarray(quality, QUALITY_DTYPE).reshape(-1))
+    scores = np.zeros((max(q.size, 1), 4), np.float64)
+    st = _ffi.load().stk_star_quality_scores(q.ctypes.data_as(C.POINTER(_ffi.StarQuality)), q.size, C.c_void_p(scores.ctypes.data))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("star_quality_scores: at least one frame's quality expected")
+    return scores[:q.size]
+
+
+def star_quality_weights(quality, params: Optional["StarQualityParameters"] = None, reference: int = -1, include=None, weights=None):
+    """stk_star_quality_weights: (weights, include, rejected): n float32 frame weights and n int32 flags for any *_stack
+    combine, and the number of included frames the limits rejected. reference: a frame that passes whatever the limits say
+    (-1 = none); include: per-frame flags (None = all); weights: the caller's own per-frame factors (None = 1). Host code."""
+    q = np.ascontiguousarray(np.asarray(quality, QUALITY_DTYPE).reshape(-1))
+    n = q.size
+    inc = None if include is None else np.ascontiguousarray(np.asarray(include, np.int32).reshape(-1))
+    u = None if weights is None else np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+    if (inc is not None and inc.size != n) or (u is not None and u.size != n):
+        raise InvalidParams("one include flag and one weight per frame expected")
+    p = (params or StarQualityParameters())._c()
+    out, inc_out, rejected = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32), C.c_int32(0)
+    st = _ffi.load().stk_star_quality_weights(q.ctypes.data_as(C.POINTER(_ffi.StarQuality)), n, C.byref(p), int(reference),
+                                              None if inc is None else C.c_void_p(inc.ctypes.data),
+                                              None if u is None else C.c_void_p(u.ctypes.data), C.c_void_p(out.ctypes.data),
+                                              C.c_void_p(inc_out.ctypes.data), C.byref(rejected))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("star_quality_weights: limits finite and >= 0, min_measured >= 1, powers 0 .. 4, "
+                                                "weights finite and >= 0, a measured and included reference, one frame passing")
+    return out[:n], inc_out[:n], rejected.value
+
+
 @dataclass
 class LocalNormParameters:        # extension beyond the reference: include/stacker.h, stk_local_norm_params
     """Local normalisation: per frame a gain and an offset field on a grid of nodes `step` destination pixels apart (a power
@@ -1424,6 +1540,55 @@ class Stacker:
             alpha = {8: 1.0 / 255.0, 16: 1.0 / 65535.0}.get(m.depth, 1.0 / float(deep.f32_scale) if deep.f32_scale else float("nan"))
         dp = deep._c()
         return self._star_match(self._lib.stk_star_match_deep, m, params, (C.byref(dp), C.c_double(float(alpha))), return_stats)
+
+    # -- star shapes, frame quality and quality weights (stk_star_measure_params) -----------------------------
+    def star_measure(self, files, stars, measure: Optional["StarMeasureParameters"] = None, deep: Optional["StarDeepParameters"] = None):
+        """The shape of every star of every frame (stk_star_measure): a list of n SHAPE_DTYPE arrays, one entry per entry of
+        `stars`, the lists star_detect / star_detect_deep returned for the same frames (only px and py are read).
+        star_frame_quality, star_quality_scores and star_quality_weights turn them into frame quality, scores for rank_frames
+        and weights for any *_stack combine."""
+        m = self._stack(files)
+        lists = [np.asarray(s, STAR_DTYPE).reshape(-1) for s in stars]
+        if len(lists) != m.n:
+            raise InvalidParams("one star list per frame expected")
+        cap = max([len(s) for s in lists] + [1])
+        tab = np.zeros((m.n, cap), STAR_DTYPE)
+        for i, s in enumerate(lists):
+            tab[i, :len(s)] = s
+        counts = np.array([len(s) for s in lists], np.int32)
+        shapes = np.zeros((m.n, cap), SHAPE_DTYPE)
+        dp, mp = (deep or StarDeepParameters())._c(), (measure or StarMeasureParameters())._c()
+        self._check(self._lib.stk_star_measure(self._h, C.byref(m.c_frames), C.byref(dp), C.byref(mp), C.c_void_p(tab.ctypes.data),
+                                               C.c_void_p(counts.ctypes.data), cap, shapes.ctypes.data_as(C.POINTER(_ffi.StarShape))))
+        return [shapes[i, :counts[i]].copy() for i in range(m.n)]
+
+    def star_match_quality_weighted(self, files, params: Optional["StarParameters"] = None, deep: Optional["StarDeepParameters"] = None,
+                                    measure: Optional["StarMeasureParameters"] = None, quality: Optional["StarQualityParameters"] = None,
+                                    alpha: Optional[float] = None, coverage: bool = True, weights=None, return_coverage: bool = False,
+                                    return_applied: bool = False, return_quality: bool = False, return_stats: bool = False):
+        """star_align_deep, the shapes of every frame's stars, their quality weights and one weighted fold
+        (stk_star_match_quality_weighted): (dropped, rejected, image[, coverage][, applied][, quality][, stats]). dropped:
+        the frames the alignment dropped; rejected: the aligned frames the quality limits rejected; both have weight 0 in
+        `applied`. alpha as in star_match_deep."""
+        m = self._stack(files)
+        deep = deep or StarDeepParameters()
+        if alpha is None:
+            alpha = {8: 1.0 / 255.0, 16: 1.0 / 65535.0}.get(m.depth, 1.0 / float(deep.f32_scale) if deep.f32_scale else float("nan"))
+        p, dp = (params or StarParameters())._c(), deep._c()
+        mp, qp = (measure or StarMeasureParameters())._c(), (quality or StarQualityParameters())._c()
+        u = self._weights_arg(weights, m.n)
+        out, img = self._image(m)
+        cov, cptr = self._optional(m, return_coverage, np.float32)
+        dropped, rejected = C.c_int32(0), C.c_int32(0)
+        applied, stats = (_ffi.FrameWeight * m.n)(), (_ffi.FrameStats * m.n)()
+        q = np.zeros(m.n, QUALITY_DTYPE)
+        self._check(self._lib.stk_star_match_quality_weighted(
+            self._h, C.byref(m.c_frames), C.byref(p), C.byref(dp), C.byref(mp), C.byref(qp), C.c_double(float(alpha)), int(coverage),
+            None if u is None else C.c_void_p(u.ctypes.data), C.byref(img), cptr, C.byref(dropped), C.byref(rejected), applied, stats,
+            q.ctypes.data_as(C.POINTER(_ffi.StarQuality))))
+        res = (dropped.value, rejected.value, out)
+        res += ((cov,) if return_coverage else ()) + ((self._applied_list(applied, m.n, m.c),) if return_applied else ())
+        return res + ((q,) if return_quality else ()) + ((self._stats_list(stats, m.n),) if return_stats else ())
 
     # -- frame calibration (extension beyond the reference) -------------------------------------------------
     def _image_arg(self, x, keep, what: str = "image"):

@@ -323,6 +323,23 @@ hipError_t launch_star_detect(const void* const* frames_dev, int n, int cn, int 
 hipError_t launch_star_detect_deep(const void* const* frames_dev, int n, int depth, int cn, int w, int h, size_t stride_bytes, int radius,
                                    float ks, int min_contrast, int min_pixels, float f32_scale, int32_t* counts, StarRecord* records,
                                    hipStream_t s);
+// star shapes on the same key (kernels_star_measure.hip; definition: include/stacker.h, stk_star_measure_params): one wave per
+// star, n <= 65535 frames in one launch. stars: n x max_stars (px, py) pairs, counts[frame] of them in use; records: n x
+// max_stars, record k of a frame = the measurement of its k-th pair; slots from counts[frame] on are not written
+struct StarMeasureRecord { int64_t S, Sx, Sy, Sxx, Syy, Sxy; int32_t bg, mad, thr, npix, peak, n_ring, flags, pad; };
+struct StarMeasureArgs {
+    const void* const* frames;
+    const int32_t* stars;        // px, py per star
+    const int32_t* counts;
+    StarMeasureRecord* records;
+    int w, h;
+    size_t stride;               // bytes per frame row
+    int max_stars;
+    int radius, ring_inner, ring_outer;
+    float ks;                    // (float)(kappa * 1.4826), from the host
+    int min_contrast, min_pixels, saturation;
+};
+hipError_t launch_star_measure(const StarMeasureArgs& a, int n, int depth, int cn, float f32_scale, hipStream_t s);
 // the noise histograms of n 8- or 16-bit frames (cn 1, 3 or 4; frames_dev: a device array of n frame pointers) in one launch
 // (kernels_noise.hip; definition: include/stacker.h, stk_noise_stat); n <= 65535, w, h >= 3. hist: n x cn x
 // noise_hist_bins(depth) uint32, ZEROED by the caller on the same stream: per frame and channel the value histogram (256 /

@@ -20,6 +20,7 @@
 // No global atomics, no floating-point atomics, no scratch.
 #include "common.h"
 #include "grey.h"
+#include "star_key.h"
 
 namespace stk {
 
@@ -32,17 +33,7 @@ constexpr int SD_GS = SD + 2 * SD_LEFT;      // keys per LDS row = 80 (160 bytes
 constexpr int SD_ROWS = SD + 2 * SD_RMAX;    // rows at the largest radius = 78
 constexpr int SD_LIST = 484;                 // ceil(64 / 3)^2 peaks at the smallest radius (kernels_star.hip's bound)
 
-__device__ __forceinline__ uint32_t key_f32(float gf, float scale) {
-    return (uint32_t)(int)fminf(fmaxf(rintf(gf * scale), 0.0f), 65535.0f);     // fmaxf(NaN, 0) = 0
-}
-
-// the key of the pixel whose first element is p[0]
-template <typename T, int CN>
-__device__ __forceinline__ uint32_t deep_key(const T* p, float scale) {
-    if constexpr (sizeof(T) == 1) { if constexpr (CN == 1) return p[0]; else return grey_u8(p[0], p[1], p[2]); }
-    else if constexpr (sizeof(T) == 2) { if constexpr (CN == 1) return p[0]; else return grey_u16(p[0], p[1], p[2]); }
-    else { if constexpr (CN == 1) return key_f32(p[0], scale); else return key_f32(grey_f32(p[0], p[1], p[2]), scale); }
-}
+// key_f32 and deep_key, the key of one pixel: star_key.h
 
 // four consecutive pixels from an aligned address (4 bytes for u8 / u16, 16 for f32) -> four keys, k[0] the first pixel
 template <typename T, int CN>

@@ -7,6 +7,11 @@
 // table of frame 0 and the kept frames.
 // The *_deep calls (include/stacker.h, stk_star_deep_params; kernel in kernels_star_deep.hip) are the same code with another
 // launch (StarMode) and the fold at the frames' own depth under the caller's alpha.
+// Star measurement (include/stacker.h, stk_star_measure_params; kernel in kernels_star_measure.hip, the host half in
+// star_shape_host.h): ctx->local (StarMeasureLayout) holds the frame pointer table, the (px, py) pairs of the stars whose
+// aperture lies inside the frame, their count per frame and the record slots; one copy brings a stack's records back.
+// stk_star_match_quality_weighted runs the alignment, measures the stars that detection found on the frames still resident
+// in HBM, and folds once with the quality weights.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -15,6 +20,7 @@
 #include "context.h"
 #include "host_pool.h"
 #include "star_match.h"
+#include "star_shape_host.h"
 
 using namespace stk;
 
@@ -167,9 +173,10 @@ stk_status star_fit(stk_ctx* ctx, const stk_star_params* p, const std::vector<st
 // detection and steps 1 - 6: the stats of all n frames, the frames in HBM, the number of moving frames dropped. Every
 // moving frame dropped: STK_INVALID_PARAMS behind the filled stats.
 stk_status star_align_impl(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* p, const StarMode& mode, stk_frame_stats* stats,
-                           std::vector<const void*>& dev, int32_t* dropped) {
+                           std::vector<const void*>& dev, int32_t* dropped, std::vector<std::vector<stk_star>>* lists_out = nullptr) {
     const int n = frames->n;
-    std::vector<std::vector<stk_star>> lists;
+    std::vector<std::vector<stk_star>> own_lists;
+    std::vector<std::vector<stk_star>>& lists = lists_out ? *lists_out : own_lists;
     std::vector<int32_t> n_peaks;
     stk_status st = star_detect_impl(ctx, frames, p, mode, dev, lists, n_peaks);
     if (st) return st;
@@ -300,6 +307,68 @@ stk_status star_match_call(stk_ctx* ctx, const stk_frames* frames, const stk_sta
 
 const StarMode kStarU8{false, 1.0f};
 
+// The shapes of the stars `stars` (n x max_stars, n_stars[i] in use) on the frames `dev` (in HBM, by frame index): n x
+// max_stars shapes, zeroed behind n_stars[i], the derived values filled. A star whose aperture is not inside the frame is
+// flagged here and never reaches the device list. Synchronises; adds the launches' device time to prep_ms.
+stk_status star_measure_impl(stk_ctx* ctx, const stk_frames* frames, const std::vector<const void*>& dev, float f32_scale,
+                             const stk_star_measure_params* mp, const stk_star* stars, const int32_t* n_stars, int max_stars,
+                             stk_star_shape* shapes) {
+    (void)hipSetDevice(ctx->device);
+    const int n = frames->n, w = frames->width, h = frames->height, R = mp->radius;
+    const StarMeasureLayout L = star_measure_layout((size_t)n, (size_t)max_stars);
+    stk_status st = workspace_reserve(ctx, ctx->local, L.total, "star measure");
+    if (st) return st;
+    char* base = ctx->local.as<char>();
+    std::vector<int32_t> pairs((size_t)n * max_stars * 2, 0), counts((size_t)n, 0), slot_of((size_t)n * max_stars, 0);
+    std::memset(shapes, 0, sizeof(stk_star_shape) * (size_t)n * max_stars);
+    for (int i = 0; i < n; i++) {
+        int c = 0;
+        for (int k = 0; k < n_stars[i]; k++) {
+            const size_t at = (size_t)i * max_stars + k;
+            stk_star_shape& o = shapes[at];
+            const int px = stars[at].px, py = stars[at].py;
+            o.px = px; o.py = py;
+            if (px < R || py < R || px > w - 1 - R || py > h - 1 - R) { o.flags = 1; continue; }
+            const size_t d = (size_t)i * max_stars + c;
+            pairs[2 * d] = px; pairs[2 * d + 1] = py; slot_of[d] = k;
+            c++;
+        }
+        counts[i] = c;
+    }
+    const float ks = (float)((double)mp->kappa * 1.4826);
+    HIP_TRY(hipMemcpyAsync(base + L.fptrs, dev.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base + L.stars, pairs.data(), pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base + L.counts, counts.data(), counts.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+    for (int f0 = 0; f0 < n; f0 += 65535) {
+        const int nl = std::min(65535, n - f0);
+        StarMeasureArgs a{};
+        a.frames = (const void* const*)(base + L.fptrs) + f0;
+        a.stars = (const int32_t*)(base + L.stars) + (size_t)f0 * max_stars * 2;
+        a.counts = (const int32_t*)(base + L.counts) + f0;
+        a.records = (StarMeasureRecord*)(base + L.records) + (size_t)f0 * max_stars;
+        a.w = w; a.h = h; a.stride = frame_row_bytes(frames); a.max_stars = max_stars;
+        a.radius = R; a.ring_inner = mp->ring_inner; a.ring_outer = mp->ring_outer;
+        a.ks = ks; a.min_contrast = mp->min_contrast; a.min_pixels = mp->min_pixels; a.saturation = mp->saturation;
+        HIP_TRY(launch_star_measure(a, nl, frames->depth, frames->channels, f32_scale, ctx->stream));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+    std::vector<StarMeasureRecord> rec((size_t)n * max_stars);
+    HIP_TRY(hipMemcpyAsync(rec.data(), base + L.records, rec.size() * sizeof(StarMeasureRecord), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->timing.prep_ms += ev_ms(ctx->ev[0], ctx->ev[1]);
+    for (int i = 0; i < n; i++)
+        for (int c = 0; c < counts[i]; c++) {                             // (slots from counts[i] on were not written: not read)
+            const size_t d = (size_t)i * max_stars + c;
+            const StarMeasureRecord& r = rec[d];
+            stk_star_shape& o = shapes[(size_t)i * max_stars + slot_of[d]];
+            o.S = r.S; o.Sx = r.Sx; o.Sy = r.Sy; o.Sxx = r.Sxx; o.Syy = r.Syy; o.Sxy = r.Sxy;
+            o.bg = r.bg; o.mad = r.mad; o.thr = r.thr; o.npix = r.npix; o.peak = r.peak; o.n_ring = r.n_ring; o.flags = r.flags;
+        }
+    shape::derive(shapes, n * max_stars);
+    return STK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -339,6 +408,104 @@ stk_status stk_star_match_deep(stk_ctx* ctx, const stk_frames* frames, const stk
     if (const stk_status st = star_deep_mode(ctx, frames, deep, mode)) return st;
     if (!std::isfinite(alpha)) return fail(ctx, STK_INVALID_PARAMS, "star match: alpha must be finite");
     return star_match_call(ctx, frames, params, mode, frames ? frames->depth : 8, alpha, out, dropped, stats);
+}
+
+stk_status stk_star_shape_derive(stk_star_shape* shapes, int32_t count) { return shape::derive(shapes, count); }
+
+stk_status stk_star_frame_quality(const stk_star_shape* shapes, const int32_t* n_stars, int32_t n, int32_t max_stars, stk_star_quality* out) {
+    return shape::frame_quality(shapes, n_stars, n, max_stars, out);
+}
+
+stk_status stk_star_quality_scores(const stk_star_quality* quality, int32_t n, double* scores) {
+    return shape::quality_scores(quality, n, scores);
+}
+
+stk_status stk_star_quality_weights(const stk_star_quality* quality, int32_t n, const stk_star_quality_params* params, int32_t reference,
+                                    const int32_t* include_or_null, const float* weights_or_null, float* weights_out,
+                                    int32_t* include_out_or_null, int32_t* rejected_or_null) {
+    return shape::quality_weights(quality, n, params, reference, include_or_null, weights_or_null, weights_out, include_out_or_null,
+                                  rejected_or_null);
+}
+
+stk_status stk_star_measure(stk_ctx* ctx, const stk_frames* frames, const stk_star_deep_params* deep, const stk_star_measure_params* params,
+                            const stk_star* stars, const int32_t* n_stars, int32_t max_stars, stk_star_shape* shapes) {
+    StarMode mode{};
+    if (const stk_status st = star_deep_mode(ctx, frames, deep, mode)) return st;
+    stk_status st = check_frames(ctx, frames, false, false);
+    if (st) return st;
+    if (const char* msg = shape::validate(params)) return fail(ctx, STK_INVALID_PARAMS, msg);
+    if (!stars || !n_stars || !shapes) return fail(ctx, STK_INVALID_PARAMS, "null star lists or shapes");
+    if (max_stars < 1 || max_stars > 4096) return fail(ctx, STK_INVALID_PARAMS, "star measure: max_stars must be 1 .. 4096");
+    for (int i = 0; i < frames->n; i++)
+        if (n_stars[i] < 0 || n_stars[i] > max_stars) return fail(ctx, STK_INVALID_PARAMS, "star measure: n_stars must be 0 .. max_stars");
+    timing_begin(ctx);
+    (void)hipSetDevice(ctx->device);
+    std::vector<const void*> dev;
+    if ((st = resolve_frames(ctx, frames, dev))) return st;
+    return star_measure_impl(ctx, frames, dev, mode.f32_scale, params, stars, n_stars, max_stars, shapes);
+}
+
+stk_status stk_star_match_quality_weighted(stk_ctx* ctx, const stk_frames* frames, const stk_star_params* params,
+                                           const stk_star_deep_params* deep, const stk_star_measure_params* measure,
+                                           const stk_star_quality_params* quality, double alpha, int32_t coverage, const float* weights,
+                                           stk_image_f32* out, float* coverage_out, int32_t* dropped, int32_t* rejected,
+                                           stk_frame_weight* applied, stk_frame_stats* stats, stk_star_quality* quality_out) {
+    StarMode mode{};
+    if (const stk_status st = star_deep_mode(ctx, frames, deep, mode)) return st;
+    if (!std::isfinite(alpha)) return fail(ctx, STK_INVALID_PARAMS, "star match: alpha must be finite");
+    stk_status st = star_check(ctx, frames, params, true, true, mode);
+    if (st) return st;
+    if (const char* msg = shape::validate(measure)) return fail(ctx, STK_INVALID_PARAMS, msg);
+    if (const char* msg = shape::validate(quality)) return fail(ctx, STK_INVALID_PARAMS, msg);
+    if ((st = weighted_check_border(ctx, params->border_mode, params->border_value, coverage))) return st;
+    if ((st = combine_check_out(ctx, out, frames))) return st;
+    timing_begin(ctx);
+    const int n = frames->n, ms_cap = params->max_stars;
+    std::vector<stk_frame_stats> own;
+    if (!stats) { own.resize(n); stats = own.data(); }
+    std::vector<const void*> dev;
+    std::vector<std::vector<stk_star>> lists;
+    int32_t nd = 0;
+    st = star_align_impl(ctx, frames, params, mode, stats, dev, &nd, &lists);
+    if (dropped) *dropped = nd;
+    if (st) return st;
+    // the stars detection found, as stk_star_detect_deep lays them out; the frames are still resident
+    std::vector<stk_star> stars((size_t)n * ms_cap);
+    std::vector<int32_t> n_stars((size_t)n);
+    std::memset(stars.data(), 0, sizeof(stk_star) * stars.size());
+    for (int i = 0; i < n; i++) {
+        n_stars[i] = (int32_t)lists[i].size();
+        if (!lists[i].empty()) std::memcpy(&stars[(size_t)i * ms_cap], lists[i].data(), sizeof(stk_star) * lists[i].size());
+    }
+    std::vector<stk_star_shape> shapes((size_t)n * ms_cap);
+    if ((st = star_measure_impl(ctx, frames, dev, mode.f32_scale, measure, stars.data(), n_stars.data(), ms_cap, shapes.data()))) return st;
+    std::vector<stk_star_quality> own_q;
+    if (!quality_out) { own_q.resize(n); quality_out = own_q.data(); }
+    shape::frame_quality(shapes.data(), n_stars.data(), n, ms_cap, quality_out);
+    std::vector<int32_t> include((size_t)n), pass((size_t)n);
+    for (int i = 0; i < n; i++) include[i] = stats[i].status == 0;
+    std::vector<float> wq((size_t)n);
+    int32_t nr = 0;
+    if ((st = shape::quality_weights(quality_out, n, quality, 0, include.data(), weights, wq.data(), pass.data(), &nr)))
+        return fail(ctx, st, "star quality weights: the reference frame has no measured star, no frame passes, or a weight is not finite and >= 0");
+    if (rejected) *rejected = nr;
+    std::vector<stk_frame_weight> rec((size_t)n, unit_record());
+    for (int i = 0; i < n; i++) rec[i].weight = wq[i];
+    if (applied) std::memcpy(applied, rec.data(), sizeof(stk_frame_weight) * (size_t)n);
+    std::vector<double> M((size_t)n * 9);
+    for (int i = 0; i < n; i++) std::memcpy(&M[(size_t)i * 9], stats[i].warp, sizeof(double) * 9);
+    EntryTable table;
+    entries_from_include(n, M.data(), pass.data(), table);
+    std::vector<stk_frame_weight> coef;
+    gather_records(table, rec.data(), coef);
+    if ((st = weighted_check_coefs(ctx, coef, frames->channels))) return st;
+    if ((st = entry_table_upload(ctx, frames, dev, table, 0))) return st;
+    double ms = 0.0;
+    if ((st = weighted_fold_records(ctx, coef, fold_spec(frames, alpha, params->border_mode, params->border_value, 0), coverage, out,
+                                    coverage_out, &ms)))
+        return st;
+    ctx->timing.finalize_ms = ms;
+    return STK_OK;
 }
 
 }  // extern "C"

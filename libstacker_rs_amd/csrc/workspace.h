@@ -196,6 +196,20 @@ inline StarLayout star_layout(size_t n_frames, size_t tiles) {
     return L;
 }
 
+// ctx->local, star measurement (star.cpp): the frame pointers of the stack, then per frame max_stars (px, py) pairs, the number
+// of them in use and max_stars record slots
+struct StarMeasureLayout { size_t fptrs, stars, counts, records, total; };
+inline StarMeasureLayout star_measure_layout(size_t n_frames, size_t max_stars) {
+    Carver c;
+    StarMeasureLayout L{};
+    L.fptrs = c.take(std::max<size_t>(n_frames, 1) * sizeof(void*));
+    L.stars = c.take(n_frames * max_stars * 2 * sizeof(int32_t));
+    L.counts = c.take(n_frames * sizeof(int32_t));
+    L.records = c.take(n_frames * max_stars * sizeof(stk::StarMeasureRecord));
+    L.total = c.total;
+    return L;
+}
+
 // ctx->local, frame calibration (calibrate.cpp): the per-frame records, the copies of host masters (bias, dark, flat; 0
 // bytes for a device or absent one) and of a host map, the tightly packed outputs of host frames
 struct CalLayout { size_t records, master[3], map, out, total; };

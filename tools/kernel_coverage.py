@@ -14,6 +14,10 @@ Every *kernel_trace.csv below that directory counts (a test may start children, 
 the engine's symbols (_ZN3stk...) are read, a `.kd` suffix dropped; torch's kernels are ignored. `--keep` keeps, for test
 files that TRACES does not hold, what the existing map says of them, so that only changed files need tracing again.
 
+The map is tests/kernel_map.tsv together with its supplements tests/kernel_map_<feature>.tsv (same header, same columns): a
+change that adds kernels commits their rows as a new supplement and leaves the committed rows as they are; `map` writes a
+kernel's row back into the file that lists it, and a kernel no file lists into tests/kernel_map.tsv.
+
 Covered: launched by a tests/test_gpu_*.py other than test_gpu_fullsize.py and the test_gpu_00_* bench and multi-rank
 files. Exit status of `uncovered` is 1 if any row has no qualifying file. Only symbol names are read, never instructions."""
 import argparse
@@ -101,12 +105,18 @@ def launched(traces):
     return seen, files
 
 
-def read_map(path=MAP):
-    """[(unit, mangled, demangled, [test files])] of the committed map."""
+def supplements(path=MAP):
+    """The supplement files of a map: tests/kernel_map_<feature>.tsv beside tests/kernel_map.tsv, sorted. A change that adds
+    kernels adds its rows in a file of its own, so that the rows already committed stay as they are."""
+    stem, ext = os.path.splitext(path)
+    return sorted(glob.glob(glob.escape(stem) + "_*" + ext))
+
+
+def read_file(path):
     rows = []
     with open(path) as f:
         lines = f.read().split("\n")
-    assert lines[0] == HEADER, lines[0]
+    assert lines[0] == HEADER, (path, lines[0])
     for ln in lines[1:]:
         if not ln:
             continue
@@ -115,13 +125,27 @@ def read_map(path=MAP):
     return rows
 
 
+def read_map(path=MAP):
+    """[(unit, mangled, demangled, [test files])] of the committed map: the file and its supplements, in that order. Nothing
+    is merged: a kernel with a row in two files is there twice, which tests/test_cpu_kernel_map.py refuses."""
+    rows = read_file(path)
+    for extra in supplements(path):
+        rows += read_file(extra)
+    return rows
+
+
 def write_map(kernels, seen, path=MAP):
+    """The rows of every kernel of the build: a kernel that a supplement of `path` lists stays in that supplement, every other
+    one goes to `path`; a supplement none of whose kernels is left in the build is written with its header alone."""
     pretty = demangle(n for names in kernels.values() for n in names)
-    with open(path, "w") as f:
-        f.write(HEADER + "\n")
-        for unit in sorted(kernels):
-            for n in kernels[unit]:
-                f.write(f"{unit}\t{n}\t{pretty[n]}\t{','.join(sorted(seen.get(n, ())))}\n")
+    home = {r[1]: extra for extra in supplements(path) for r in read_file(extra)}
+    lines = {p: [] for p in [path] + supplements(path)}
+    for unit in sorted(kernels):
+        for n in kernels[unit]:
+            lines[home.get(n, path)].append(f"{unit}\t{n}\t{pretty[n]}\t{','.join(sorted(seen.get(n, ())))}\n")
+    for p, body in lines.items():
+        with open(p, "w") as f:
+            f.write(HEADER + "\n" + "".join(body))
 
 
 def uncovered(rows):
