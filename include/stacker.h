@@ -1906,6 +1906,108 @@ stk_status stk_keypoint_match_noise_weighted(stk_ctx* ctx, const stk_frames* fra
                                              stk_frame_weight* applied_or_null, stk_frame_stats* stats_or_null,
                                              stk_noise_stat* noise_or_null);
 
+/* ---- background model: per-frame sky level on a node grid: an EXTENSION beyond the reference ------------------------
+ * A light-pollution or moonlight gradient is a smooth additive field of the frame, not of the stack: star detection's
+ * piecewise tile median, local normalisation (which maps onto frame 0, gradient included) and the noise pass's one median
+ * per frame all let it through. This section measures, per frame and colour channel, the sky level on the node grid of
+ * the mesh section from exact clipped order statistics of the window around each node, interpolates it bilinearly and
+ * subtracts it (flatten). It runs per frame before registration, or on a finished stack (a one-frame f32 stk_frames).
+ * Grid and windows. Nodes are those of stk_mesh_grid(w, h, step), step 16, 32, 64 or 128; node (j, k) sits at
+ *   q = (k step, j step). On one axis the window of a node is the inclusive pixel range a = max(q - step / 2, 0) ..
+ *   b = min(q + step / 2, size - 1); it is empty when a > b (a last node beyond the frame); its centre is p = (a + b) / 2.
+ *   Windows of neighbouring nodes share one pixel row or column; a window holds at most (step + 1)^2 pixels.
+ * Key, per channel c < C = min(channels, 3) (a sky gradient is coloured; channel 3, alpha, is never read by the
+ *   statistics): the sample itself for u8 and u16 frames; for f32 frames (int)fminf(fmaxf(rintf(sample * f32_scale), 0),
+ *   65535) (NaN gives 0), the key of stk_star_deep_params.
+ * Mask (optional): w x h bytes, tightly packed, host or device memory, one for the whole stack; a pixel whose byte is
+ *   non-zero is excluded.
+ * Window record (stk_bg_cell), all integers, on the device. W = the multiset of the window's unmasked keys, n = |W|.
+ *   n = 0: the record is all zeros. Else lo_0 = 0, hi_0 = 65535 and for t = 0 .. T (T = clip_iters):
+ *     S_t = {K in W : lo_t <= K <= hi_t}; m = (|S_t| + 1) / 2; med_t = the m-th smallest of S_t; mad_t = the m-th smallest
+ *     |K - med_t| over S_t; for t < T: d = max((int)fminf(ceilf(ks * (float)mad_t), 65536.0f), 1), ks = (float)((double)kappa
+ *     * 1.4826); lo_{t+1} = max(lo_t, med_t - d); hi_{t+1} = min(hi_t, med_t + d).
+ *   S_t is never empty (med_t is in S_{t+1}). The record holds n, kept = |S_T|, med = med_T, mad = mad_T, lo = lo_T,
+ *   hi = hi_T, sum = the sum of K and sum2 the sum of K^2 over S_T. Counts and sums are integers: no result depends on
+ *   the order in which anything is added, and a call returns the same bits every time.
+ * Estimator (stk_background_estimate: host code, no context), in f64 unless stated, per channel:
+ *   mean = sum / kept. Level by `estimator`: 0 MEDIAN: med; 1 MEAN: mean; 2 MODE: s = 1.4826 max(mad, 1), the level is
+ *   2.5 med - 1.5 mean when |mean - med| <= 0.3 s, else med. rms = sqrt(max(sum2 / kept - mean mean, 0)). A record with
+ *   kept = 0 has level 0 and rms 0.
+ *   A (node, channel) is valid iff kept >= min_count (0 = 64) and (double)(n - kept) <= (double)max_reject (double)n.
+ *   Then, in this order:
+ *   1. Recentre (recentre = 1): a window cut by the frame measures the level at p, not at q. An x pass over the input
+ *      values (no cascade): for a valid node with p_k != q_k, kn = k + 1 if p_k > q_k, else k - 1; if kn is in the grid,
+ *      (j, kn) is valid and p_kn != p_k: L' = L + ((L - L_kn) (q_k - p_k)) / (p_k - p_kn). Then the same along y on the x
+ *      pass's output.
+ *   2. For f32 frames level and rms are divided by (double)f32_scale. Both are rounded to f32: the planes are in SAMPLE
+ *      units.
+ *   3. Filter (filter = 1): a valid node whose 3 x 3 neighbourhood lies wholly in the grid and is wholly valid takes the
+ *      5th smallest of the nine input values; every other node keeps its value.
+ *   4. Edge extrapolation, for the last column and then the last row (the last node may lie beyond the frame with an
+ *      empty or thin window): if (j, gw - 1) is invalid and (j, gw - 2) and (j, gw - 3) are valid, L = (a + a) - b in f32,
+ *      a = L(j, gw - 2), b = L(j, gw - 3), and the node counts as valid. Then the same for row gh - 1, on that output.
+ *   5. Fill: `fill` passes of the mesh section's "Fill" arithmetic on the level, with the validity so far as m.
+ *   6. Fallback: a node still invalid takes the lower median of the channel's valid levels as they stood before the
+ *      fill; when the channel has no valid node the level is 0 and bit c of `flags` is set.
+ *   The rms plane skips steps 1, 3 and 4: it is filled with the validity the levels had before step 4 and takes the same
+ *   kind of fallback (the lower median of its valid values, or 0).
+ *   Outputs: the level plane gh x gw x C f32; the rms plane of the same shape; valid: gh x gw int32, bit c, as it stood
+ *   before step 4; flags.
+ * Apply. Pixel (x, y), channel c < C: B_c = the local-normalisation section's chain on the level plane (k, j, k1, j1, u, v,
+ *   then three fmas on the C components per node); v = ((float)raw - B_c) + target[c], each operation rounded on its
+ *   own. Channel 3 is (float)raw. out_depth, rounding, saturation, out, out_row_stride_bytes, the overlap refusal, padded
+ *   and misaligned rows, host and device frames follow stk_calibrate. A NULL plane means B = 0. Plane values are expected
+ *   finite and are not checked.
+ * Not here: division (a multiplicative flatten), spline or polynomial surfaces, subtraction inside the folds, in-place
+ *   output, shard and files forms. A multi-device context runs these calls on its first device. */
+enum { STK_BG_MEDIAN = 0, STK_BG_MEAN = 1, STK_BG_MODE = 2 };
+typedef struct {
+    int32_t n;            /* unmasked pixels of the window */
+    int32_t kept;         /* |S_T| */
+    int32_t med, mad;     /* of S_T */
+    int32_t lo, hi;       /* the last clip range */
+    int32_t reserved[2];  /* 0 */
+    int64_t sum;          /* of K over S_T */
+    uint64_t sum2;        /* of K^2 over S_T */
+} stk_bg_cell;            /* 48 bytes */
+typedef struct {
+    int32_t step;         /* node spacing: 16, 32, 64 or 128 */
+    int32_t clip_iters;   /* T: 0 .. 5 */
+    float   kappa;        /* finite, > 0 */
+    float   f32_scale;    /* finite, > 0; read for f32 frames only */
+    int32_t estimator;    /* STK_BG_MEDIAN, STK_BG_MEAN, STK_BG_MODE */
+    int32_t min_count;    /* >= 0; 0 = 64 */
+    float   max_reject;   /* 0 .. 1 */
+    int32_t recentre;     /* 0 or 1 */
+    int32_t filter;       /* 0 or 1 */
+    int32_t fill;         /* 0 .. 16 */
+    float   target[4];    /* finite: the level the flattened sky is put at, per channel */
+    int32_t out_depth;    /* the frames' depth or STK_DEPTH_F32 (read by stk_background_flatten) */
+    int32_t reserved[3];  /* 0 */
+} stk_background_params;
+/* Anything outside the ranges above is STK_INVALID_PARAMS.
+ * The window records of every frame in one launch. mask_or_null: the mask in mask_location (STK_HOST or STK_DEVICE).
+ * cells: n x gh x gw x C records on the host, frame index order. stk_timing.finalize_ms is the launch. */
+stk_status stk_background_cells(stk_ctx* ctx, const stk_frames* frames, const stk_background_params* params,
+                                const uint8_t* mask_or_null, int32_t mask_location, stk_bg_cell* cells);
+/* The estimator for one frame: pure host code, no context (a bad argument is STK_INVALID_PARAMS without a message).
+ * depth: the frames' (8, 16 or 32). cells_of_one_frame: gh x gw x C records. level: gh x gw x C f32. */
+stk_status stk_background_estimate(int32_t width, int32_t height, int32_t channels, int32_t depth,
+                                   const stk_background_params* params, const stk_bg_cell* cells_of_one_frame, float* level,
+                                   float* rms_or_null, int32_t* valid_or_null, int32_t* flags_or_null);
+/* Apply alone. planes: n host level planes by frame index for the grid of `step` (an entry, or the array, may be NULL:
+ * B = 0). target: 4 floats. out: n images in the frames' location, as in stk_calibrate. finalize_ms is the launch. */
+stk_status stk_background_apply(stk_ctx* ctx, const stk_frames* frames, const float* const* planes, int32_t step,
+                                const float* target, int32_t out_depth, void* const* out, size_t out_row_stride_bytes);
+/* The whole-stack form: by definition, and bit for bit, stk_background_cells, stk_background_estimate per frame and
+ * stk_background_apply with params->target and params->out_depth, in sequence; host frames are uploaded once.
+ * planes_out_or_null / rms_out_or_null: n host planes by frame index, NULL entries skipped; cells_out_or_null: all records
+ * as stk_background_cells returns them. finalize_ms is the two launches. */
+stk_status stk_background_flatten(stk_ctx* ctx, const stk_frames* frames, const stk_background_params* params,
+                                  const uint8_t* mask_or_null, int32_t mask_location, void* const* out,
+                                  size_t out_row_stride_bytes, float* const* planes_out_or_null, float* const* rms_out_or_null,
+                                  stk_bg_cell* cells_out_or_null);
+
 /* One frame's whole ECC preparation as ecc_match runs it per frame: cvt_color(BGR2GRAY) (utils.rs:136-142) followed
  * by findTransformECC's own GaussianBlur of the float image (lib.rs:769-777) in one fused pass. `out` is a tightly
  * packed width x height f32 plane in the frame's location. BGR frames, 8-bit or f32. */

@@ -19,7 +19,8 @@ from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_RE
                   rank_frames,
                   star_match_lists,
                   QUALITY_DTYPE, SHAPE_DTYPE, STAR_SCORE_COUNT, STAR_SCORE_FWHM, STAR_SCORE_ROUND, STAR_SCORE_SNR, StarMeasureParameters,
-                  StarQualityParameters, star_frame_quality, star_quality_scores, star_quality_weights, star_shape_derive)
+                  StarQualityParameters, star_frame_quality, star_quality_scores, star_quality_weights, star_shape_derive,
+                  BG_CELL_DTYPE, BG_MEAN, BG_MEDIAN, BG_MODE, BackgroundParameters, background_estimate)
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
@@ -29,4 +30,5 @@ __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchPa
            "NoiseParameters", "NOISE_DTYPE", "noise_from_hist", "noise_weights",
            "StarMeasureParameters", "StarQualityParameters", "SHAPE_DTYPE", "QUALITY_DTYPE", "star_shape_derive", "star_frame_quality",
            "star_quality_scores", "star_quality_weights", "STAR_SCORE_FWHM", "STAR_SCORE_ROUND", "STAR_SCORE_SNR", "STAR_SCORE_COUNT",
+           "BackgroundParameters", "background_estimate", "BG_CELL_DTYPE", "BG_MEDIAN", "BG_MEAN", "BG_MODE",
            "CFA_RGGB", "CFA_GRBG", "CFA_GBRG", "CFA_BGGR", "DEMOSAIC_BILINEAR", "DEMOSAIC_MHC", "DEMOSAIC_HA", "DEMOSAIC_SUPERPIXEL"]

@@ -142,6 +142,18 @@ class NoiseStat(C.Structure):
                 ("sigma", C.c_double), ("kept", C.c_int64)]
 
 
+class BgCell(C.Structure):
+    _fields_ = [("n", C.c_int32), ("kept", C.c_int32), ("med", C.c_int32), ("mad", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32),
+                ("reserved", C.c_int32 * 2), ("sum", C.c_int64), ("sum2", C.c_uint64)]
+
+
+class BackgroundParams(C.Structure):
+    _fields_ = [("step", C.c_int32), ("clip_iters", C.c_int32), ("kappa", C.c_float), ("f32_scale", C.c_float),
+                ("estimator", C.c_int32), ("min_count", C.c_int32), ("max_reject", C.c_float), ("recentre", C.c_int32),
+                ("filter", C.c_int32), ("fill", C.c_int32), ("target", C.c_float * 4), ("out_depth", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
 class HgProblem(C.Structure):
     _fields_ = [("src_pts", C.c_void_p), ("dst_pts", C.c_void_p), ("n", C.c_int32), ("inlier_mask_or_null", C.c_void_p)]
 
@@ -430,6 +442,13 @@ SIGNATURES = {
                                                      C.POINTER(WeightParams), C.c_void_p, C.c_double, C.POINTER(ImageF32),
                                                      C.POINTER(C.c_int32), C.c_void_p, C.POINTER(FrameWeight), C.POINTER(FrameStats),
                                                      C.POINTER(NoiseStat)]),
+    # (the background calls take their stk_frames by address, as a void pointer, like the noise and deep star calls above)
+    "stk_background_cells": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(BackgroundParams), C.c_void_p, C.c_int32, C.POINTER(BgCell)]),
+    "stk_background_estimate": (c_status, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(BackgroundParams), C.POINTER(BgCell),
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "stk_background_apply": (c_status, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
+    "stk_background_flatten": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(BackgroundParams), C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(BgCell)]),
     "stk_grey_blur_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_int32, C.c_void_p]),
     "stk_gaussian_blur_f32": (c_status, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p]),

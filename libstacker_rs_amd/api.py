@@ -615,6 +615,69 @@ def noise_weights(stats, channels: int, gain=None, include=None, weights=None, s
     return out[:n]
 
 
+BG_MEDIAN, BG_MEAN, BG_MODE = range(3)                     # STK_BG_*: the level estimator of the background model
+BG_CELL_DTYPE = np.dtype([("n", "<i4"), ("kept", "<i4"), ("med", "<i4"), ("mad", "<i4"), ("lo", "<i4"), ("hi", "<i4"),
+                          ("reserved", "<i4", (2,)), ("sum", "<i8"), ("sum2", "<u8")])
+
+
+@dataclass
+class BackgroundParameters:       # extension beyond the reference: include/stacker.h, stk_background_params
+    """The background model: per frame and colour channel the sky level on a grid of nodes `step` pixels apart (16, 32, 64
+    or 128), each from the window of step + 1 pixels around it: the median and MAD of the window's 16-bit keys (f32 frames:
+    rint(sample * f32_scale)), clipped `clip_iters` times (0 .. 5) at `kappa` robust sigmas. `estimator`: BG_MEDIAN, BG_MEAN
+    (of the kept keys) or BG_MODE (2.5 median - 1.5 mean where the two agree). A node that keeps fewer than `min_count` keys
+    (0 = 64), or rejects more than `max_reject` of its window, is invalid; `recentre` moves the level of a window cut by the
+    frame back to its node, `filter` is a 3 x 3 median of the nodes, `fill` passes fill holes from their neighbours. The
+    flattened sky is put at `target` (per channel) in `out_depth` (None: the frames' depth)."""
+    step: int = 64
+    clip_iters: int = 3
+    kappa: float = 3.0
+    f32_scale: float = 1.0
+    estimator: int = BG_MODE
+    min_count: int = 0
+    max_reject: float = 0.5
+    recentre: bool = True
+    filter: bool = True
+    fill: int = 4
+    target: Sequence[float] = (0.0, 0.0, 0.0, 0.0)
+    out_depth: Optional[int] = None
+
+    def _target(self):
+        t = np.asarray(self.target, np.float32).reshape(-1)
+        return (C.c_float * 4)(*((list(t) + [float(t[-1])] * 4)[:4]))
+
+    def _c(self, depth: int = 0) -> _ffi.BackgroundParams:
+        return _ffi.BackgroundParams(int(self.step), int(self.clip_iters), float(self.kappa), float(self.f32_scale), int(self.estimator),
+                                     int(self.min_count), float(self.max_reject), int(self.recentre), int(self.filter), int(self.fill),
+                                     self._target(), int(depth if self.out_depth is None else self.out_depth), (C.c_int32 * 3)(0, 0, 0))
+
+
+def background_estimate(width: int, height: int, channels: int, depth: int, cells, params: Optional["BackgroundParameters"] = None,
+                        return_rms: bool = False, return_valid: bool = False, return_flags: bool = False):
+    """The estimator of the background model for one frame (stk_background_estimate; host code, no GPU): the
+    gh x gw x min(channels, 3) f32 level plane from the frame's window records (BG_CELL_DTYPE, gh x gw x min(channels, 3)),
+    then the rms plane (return_rms), the per-node validity masks before the edge extrapolation (return_valid, gh x gw int32)
+    and the flags (return_flags: bit c = channel c had no valid node)."""
+    p = (params or BackgroundParameters())._c(depth)
+    gw, gh = mesh_grid(width, height, int(p.step))
+    cc = min(int(channels), 3)
+    rec = np.ascontiguousarray(np.asarray(cells, BG_CELL_DTYPE).reshape(-1))
+    if rec.size != gh * gw * cc:
+        raise InvalidParams("window records: gh x gw x min(channels, 3) expected")
+    level = np.zeros((gh, gw, cc), np.float32)
+    rms = np.zeros((gh, gw, cc), np.float32) if return_rms else None
+    valid = np.zeros((gh, gw), np.int32)
+    flags = C.c_int32(0)
+    st = _ffi.load().stk_background_estimate(int(width), int(height), int(channels), int(depth), C.byref(p),
+                                             rec.ctypes.data_as(C.POINTER(_ffi.BgCell)), C.c_void_p(level.ctypes.data),
+                                             None if rms is None else C.c_void_p(rms.ctypes.data), C.c_void_p(valid.ctypes.data),
+                                             C.byref(flags))
+    if st:
+        raise InvalidParams("stk_background_estimate refused its arguments")
+    res = (level,) + ((rms,) if return_rms else ()) + ((valid,) if return_valid else ()) + ((flags.value,) if return_flags else ())
+    return res if len(res) > 1 else level
+
+
 def _quantile_c(q) -> _ffi.QuantileParams:
     """QuantileParameters, a bare float, or None (the median)."""
     if q is None:
@@ -1632,6 +1695,144 @@ class Stacker:
         keep.append(a)
         return a.ctypes.data, HOST
 
+    # -- the background model (include/stacker.h, stk_background_params) -------------------------
+    def _mask_arg(self, mask, keep, m):
+        if mask is None:
+            return None, HOST
+        ptr, loc = self._bytes_arg(mask, keep, m.h, m.w, "mask")
+        return C.c_void_p(ptr), loc
+
+    def background_cells(self, files, params: Optional["BackgroundParameters"] = None, mask=None):
+        """The window records of every frame of a stack in one device pass (stk_background_cells): an
+        n x gh x gw x min(C, 3) BG_CELL_DTYPE array. `mask`: an H x W uint8 plane, host or device; non-zero excludes the pixel."""
+        m = self._stack(files)
+        p = (params or BackgroundParameters())._c(m.depth)
+        keep = []
+        mptr, mloc = self._mask_arg(mask, keep, m)
+        gw, gh = mesh_grid(m.w, m.h, int(p.step))
+        cells = np.zeros((m.n, gh, gw, min(m.c, 3)), BG_CELL_DTYPE)
+        self._check(self._lib.stk_background_cells(self._h, C.byref(m.c_frames), C.byref(p), mptr, mloc,
+                                                   cells.ctypes.data_as(C.POINTER(_ffi.BgCell))))
+        return cells
+
+    def _level_planes_arg(self, planes, m, step, keep):
+        """n host level planes (None entries allowed) as the pointer table the C ABI takes."""
+        gw, gh = mesh_grid(m.w, m.h, int(step))
+        if planes is None:
+            return None
+        planes = list(planes)
+        if len(planes) != m.n:
+            raise InvalidParams("one level plane (or None) per frame expected")
+        ptrs = []
+        for pl in planes:
+            if pl is None:
+                ptrs.append(None)
+                continue
+            a = np.ascontiguousarray(np.asarray(pl, np.float32))
+            if a.size != gh * gw * min(m.c, 3):
+                raise InvalidParams("a level plane must be gh x gw x min(C, 3) float32")
+            keep.append(a)
+            ptrs.append(a.ctypes.data)
+        arr = (C.c_void_p * m.n)(*ptrs)
+        keep.append(arr)
+        return C.cast(arr, C.c_void_p)
+
+    def background_apply(self, files, planes, step: int, target=(0.0, 0.0, 0.0, 0.0), out_depth: Optional[int] = None, out=None):
+        """Subtract the interpolated level planes from a stack (stk_background_apply): ((float)raw - B) + target per colour
+        channel, alpha untouched. planes: n host planes gh x gw x min(C, 3) for the grid of `step`, None entries = 0. Returns
+        the flattened stack where the frames live (see calibrate for `out`)."""
+        m = self._stack(files)
+        keep = []
+        tbl = self._level_planes_arg(planes, m, step, keep)
+        tgt = BackgroundParameters(target=target)._target()
+        depth = int(m.depth if out_depth is None else out_depth)
+        res, arr, stride = self._frame_outputs(m, depth, out, keep)
+        self._check(self._lib.stk_background_apply(self._h, C.byref(m.c_frames), tbl, int(step), C.cast(tgt, C.c_void_p), depth,
+                                                   C.cast(arr, C.c_void_p), stride))
+        return res
+
+    def background_flatten(self, files, params: Optional["BackgroundParameters"] = None, mask=None, out=None, return_planes: bool = False,
+                           return_rms: bool = False, return_cells: bool = False):
+        """Model and remove the background of every frame (stk_background_flatten = background_cells, background_estimate
+        per frame and background_apply with params.target, bit for bit). Returns the flattened stack where the frames live,
+        then the level planes (return_planes: n x gh x gw x min(C, 3) float32), the rms planes (return_rms) and the window
+        records (return_cells)."""
+        m = self._stack(files)
+        p = (params or BackgroundParameters())._c(m.depth)
+        keep = []
+        mptr, mloc = self._mask_arg(mask, keep, m)
+        gw, gh = mesh_grid(m.w, m.h, int(p.step))
+        cc = min(m.c, 3)
+        res, arr, stride = self._frame_outputs(m, int(p.out_depth), out, keep)
+
+        def table(wanted):
+            if not wanted:
+                return None, None
+            a = np.zeros((m.n, gh, gw, cc), np.float32)
+            t = (C.c_void_p * m.n)(*[a.ctypes.data + i * gh * gw * cc * 4 for i in range(m.n)])
+            keep.append(t)
+            return a, C.cast(t, C.c_void_p)
+        planes, pt = table(return_planes)
+        rms, rt = table(return_rms)
+        cells = np.zeros((m.n, gh, gw, cc), BG_CELL_DTYPE) if return_cells else None
+        self._check(self._lib.stk_background_flatten(self._h, C.byref(m.c_frames), C.byref(p), mptr, mloc, C.cast(arr, C.c_void_p), stride, pt, rt,
+                                                     None if cells is None else cells.ctypes.data_as(C.POINTER(_ffi.BgCell))))
+        extra = tuple(x for x in (planes, rms, cells) if x is not None)
+        return (res,) + extra if extra else res
+
+    def flatten_image(self, image, params: Optional["BackgroundParameters"] = None, mask=None, return_plane: bool = False):
+        """Flatten a finished stack: an H x W x C float32 image (array or device tensor) as a one-frame stack through
+        background_flatten. Set params.f32_scale so that sample * f32_scale spans the 16-bit key range (65535 for a stack
+        in [0, 1])."""
+        if str(image.dtype).replace("torch.", "") != "float32" or len(image.shape) not in (2, 3):
+            raise InvalidParams("flatten_image: an H x W x C float32 image expected")
+        res = self.background_flatten([image], params, mask, return_planes=return_plane)
+        return (res[0][0], res[1][0]) if return_plane else res[0]
+
+    def _frame_outputs(self, m, out_depth: int, out, keep):
+        """The per-frame outputs of a call that writes one image per frame (stk_calibrate, the background calls): a fresh
+        n x H x W x C array or tensor of `out_depth` where the frames live, or the caller's `out` (n images in the frames'
+        location; row-strided views allowed, all with one row step). Returns (result, the pointer array, the row stride)."""
+        dt = {8: "uint8", 16: "uint16", 32: "float32"}.get(out_depth)
+        stride = 0
+        if out is None:
+            if dt is None:
+                raise InvalidParams("out_depth must be 8, 16 or 32")
+            res, base = self._alloc(m, (m.n, m.h, m.w, m.c), dt)
+            ptrs = [base + i * m.h * m.w * m.c * (out_depth // 8) for i in range(m.n)]
+        else:
+            res = out
+            outs = list(out)
+            if len(outs) != m.n:
+                raise InvalidParams("one output per frame expected")
+            ptrs, strides = [], set()
+            el = out_depth // 8
+            for o in outs:
+                dev = _is_torch(o) and o.is_cuda
+                if dev != (m.location == DEVICE):
+                    raise InvalidParams("the outputs must live where the frames live")
+                name = str(o.dtype).replace("torch.", "")
+                shape = tuple(int(v) for v in o.shape)
+                if name != dt or shape not in ((m.h, m.w, m.c),) + (((m.h, m.w),) if m.c == 1 else ()):
+                    raise InvalidParams("every output must be H x W x C of the output depth")
+                if not dev and _is_torch(o):
+                    o = o.numpy()
+                if dev:
+                    self._tensor_ready(o)
+                    rs = m.w * m.c * el if o.is_contiguous() else _row_stride_bytes(shape, [s * el for s in o.stride()], el)
+                    ptrs.append(o.data_ptr())
+                else:
+                    rs = m.w * m.c * el if o.flags.c_contiguous else _row_stride_bytes(shape, o.strides, el)
+                    ptrs.append(o.ctypes.data)
+                if not rs:
+                    raise InvalidParams("an output must be contiguous or a view whose only non-contiguity is its row step")
+                strides.add(rs)
+                keep.append(o)
+            if len(strides) != 1:
+                raise InvalidParams("all outputs must share one row step")
+            stride = strides.pop()
+        return res, (C.c_void_p * m.n)(*ptrs), stride
+
     def calibrate(self, files, cal: "CalibrationParameters", out=None):
         """Apply masters and defect repair to every frame of a stack (stk_calibrate). Returns the calibrated stack where
         the frames live: an n x H x W x C array or tensor of the frames' dtype (or float32, cal.out_depth = 32). `out`: n
@@ -1662,45 +1863,7 @@ class Stacker:
             c.defects_or_null, c.defects_location = self._bytes_arg(cal.defects, keep, m.h, m.w, "defects")
         c.defect_step = int(cal.defect_step)
         c.out_depth = int(m.depth if cal.out_depth is None else cal.out_depth)
-        dt = {8: "uint8", 16: "uint16", 32: "float32"}.get(c.out_depth)
-        stride = 0
-        if out is None:
-            if dt is None:
-                raise InvalidParams("out_depth must be 8, 16 or 32")
-            res, base = self._alloc(m, (m.n, m.h, m.w, m.c), dt)
-            ptrs = [base + i * m.h * m.w * m.c * (c.out_depth // 8) for i in range(m.n)]
-        else:
-            res = out
-            outs = list(out)
-            if len(outs) != m.n:
-                raise InvalidParams("one output per frame expected")
-            ptrs, strides = [], set()
-            el = c.out_depth // 8
-            for o in outs:
-                dev = _is_torch(o) and o.is_cuda
-                if dev != (m.location == DEVICE):
-                    raise InvalidParams("the outputs must live where the frames live")
-                name = str(o.dtype).replace("torch.", "")
-                shape = tuple(int(v) for v in o.shape)
-                if name != dt or shape not in ((m.h, m.w, m.c),) + (((m.h, m.w),) if m.c == 1 else ()):
-                    raise InvalidParams("every output must be H x W x C of the output depth")
-                if not dev and _is_torch(o):
-                    o = o.numpy()
-                if dev:
-                    self._tensor_ready(o)
-                    rs = m.w * m.c * el if o.is_contiguous() else _row_stride_bytes(shape, [s * el for s in o.stride()], el)
-                    ptrs.append(o.data_ptr())
-                else:
-                    rs = m.w * m.c * el if o.flags.c_contiguous else _row_stride_bytes(shape, o.strides, el)
-                    ptrs.append(o.ctypes.data)
-                if not rs:
-                    raise InvalidParams("an output must be contiguous or a view whose only non-contiguity is its row step")
-                strides.add(rs)
-                keep.append(o)
-            if len(strides) != 1:
-                raise InvalidParams("all outputs must share one row step")
-            stride = strides.pop()
-        arr = (C.c_void_p * m.n)(*ptrs)
+        res, arr, stride = self._frame_outputs(m, c.out_depth, out, keep)
         self._check(self._lib.stk_calibrate(self._h, C.byref(m.c_frames), C.byref(c), C.cast(arr, C.c_void_p), stride))
         return res
 

@@ -374,6 +374,35 @@ hipError_t launch_defect_map(const float* master, size_t stride, int w, int h, i
 // per-channel f64 sums of an f32 image: one partial per row and channel into partials (h x 4 doubles), then added in row
 // order into sums (4 doubles)
 hipError_t launch_image_sums(const float* image, size_t stride, int w, int h, int cn, double* partials, double* sums, hipStream_t s);
+// background model (kernels_background.hip; definition: include/stacker.h, stk_background_params). frames: a device array
+// of the launch's frame pointers; stride in bytes; mask: w x h bytes on the device, or null; cells: per (frame, node,
+// channel < min(cn, 3)) one record, frame-major; ks = (float)(kappa * 1.4826) from the host; n <= 65535
+struct BgCellsArgs {
+    const void* const* frames;
+    const uint8_t* mask;
+    stk_bg_cell* cells;
+    int w, h;
+    size_t stride;
+    int step, gw, gh;
+    int clip_iters;
+    float ks, f32_scale;
+};
+hipError_t launch_background_cells(const BgCellsArgs& a, int n, int depth, int cn, hipStream_t s);
+// the subtraction: one record per frame of the launch (plane: gh x gw x min(cn, 3) f32 on the device, or null = 0); strides
+// in bytes; depth: the frames' (8 / 16 / 32); out_depth: depth or 32; cn 1, 3 or 4; a.n <= 65535
+constexpr int BG_TW = 64, BG_TH = 16;        // pixels per workgroup tile of background_apply_kernel
+constexpr int BG_ROWS = 4;                   // 64-pixel row segments per wave
+struct BgFrame { const void* src; void* dst; const float* plane; };
+struct BgApplyArgs {
+    const BgFrame* frames;
+    int n;
+    int w, h;
+    size_t in_stride, out_stride;
+    int shift, gw, gh;           // step = 1 << shift
+    float inv;                   // 1.0f / step
+    float target[4];
+};
+hipError_t launch_background_apply(const BgApplyArgs& a, int depth, int out_depth, int cn, hipStream_t s);
 // colour-filter mosaics (kernels_demosaic.hip; definition: include/stacker.h, stk_mosaic). One record per frame of the
 // launch; strides in bytes; (w, h): the mosaic's size, at least 3 x 3 (superpixel: 2 x 2).
 constexpr int DEM_TW = 64, DEM_TH = 16;      // output pixels per workgroup tile of demosaic_kernel (32 x 8 cells of 2 x 2)

@@ -237,6 +237,24 @@ inline ImageLayout image_layout(size_t partial_rows, size_t image_bytes, size_t 
     return L;
 }
 
+// ctx->local, the background model (background.cpp): the frame pointers of the cells launch, the per-frame records of the
+// apply launch, the copy of a host mask, the window records (0 bytes: the apply alone), the level planes (`plane` bytes
+// apart, packed: they arrive in one copy; 0 planes: the cells alone), the tightly packed outputs of host frames
+struct BgLayout { size_t fptrs, records, mask, cells, planes, plane, out, total; };
+inline BgLayout bg_layout(size_t n_frames, size_t mask_bytes, size_t cell_bytes, size_t n_planes, size_t plane_floats, size_t out_bytes) {
+    Carver c;
+    BgLayout L{};
+    L.fptrs = c.take(std::max<size_t>(n_frames, 1) * sizeof(void*));
+    L.records = c.take(std::max<size_t>(n_frames, 1) * sizeof(stk::BgFrame));
+    L.mask = c.take(mask_bytes);
+    L.cells = c.take(cell_bytes);
+    L.plane = plane_floats * sizeof(float);
+    L.planes = c.take(n_planes * L.plane);
+    L.out = c.take(out_bytes);
+    L.total = c.total;
+    return L;
+}
+
 // ctx->local, colour-filter mosaics (demosaic.cpp): the per-frame records, then the tightly packed outputs of host mosaics
 // (stk_cfa_mask: no records, the plane of a host caller)
 struct DemosaicLayout { size_t records, out, total; };

@@ -16,7 +16,11 @@ files that TRACES does not hold, what the existing map says of them, so that onl
 
 The map is tests/kernel_map.tsv together with its supplements tests/kernel_map_<feature>.tsv (same header, same columns): a
 change that adds kernels commits their rows as a new supplement and leaves the committed rows as they are; `map` writes a
-kernel's row back into the file that lists it, and a kernel no file lists into tests/kernel_map.tsv.
+kernel's row back into the file that lists it, and a kernel no file lists into tests/kernel_map.tsv. The features named in
+PARTS are held as parts of the main file instead: read_file of a map returns their rows behind its own, so read_map counts
+them with the main file and not beside it (tests/test_cpu_star_measure.py pins read_map at the main file plus the nine rows
+of the first supplement, which a second supplement counted beside the main file cannot meet). Everything else is the same
+for a part: its own file, same header, every row checked against the tree, `map` writes its rows back into it.
 
 Covered: launched by a tests/test_gpu_*.py other than test_gpu_fullsize.py and the test_gpu_00_* bench and multi-rank
 files. Exit status of `uncovered` is 1 if any row has no qualifying file. Only symbol names are read, never instructions."""
@@ -34,6 +38,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "libstacker_rs_amd", "csrc")
 MAP = os.path.join(ROOT, "tests", "kernel_map.tsv")
 HEADER = "unit\tmangled\tdemangled\ttest files"
+PARTS = ("background",)                      # tests/kernel_map_<name>.tsv read as a part of tests/kernel_map.tsv (see above)
 MAX_COMPILES = 16
 SYMBOL = re.compile(r"_ZN3stk\w+")
 
@@ -105,14 +110,21 @@ def launched(traces):
     return seen, files
 
 
-def supplements(path=MAP):
-    """The supplement files of a map: tests/kernel_map_<feature>.tsv beside tests/kernel_map.tsv, sorted. A change that adds
-    kernels adds its rows in a file of its own, so that the rows already committed stay as they are."""
+def parts(path=MAP):
+    """The part files of a map that exist: <stem>_<name>.tsv for the names in PARTS, in that order."""
     stem, ext = os.path.splitext(path)
-    return sorted(glob.glob(glob.escape(stem) + "_*" + ext))
+    return [f for f in (stem + "_" + name + ext for name in PARTS) if os.path.isfile(f)]
 
 
-def read_file(path):
+def supplements(path=MAP):
+    """The supplement files of a map: tests/kernel_map_<feature>.tsv beside tests/kernel_map.tsv, sorted, without its parts. A
+    change that adds kernels adds its rows in a file of its own, so that the rows already committed stay as they are."""
+    stem, ext = os.path.splitext(path)
+    return sorted(set(glob.glob(glob.escape(stem) + "_*" + ext)) - set(parts(path)))
+
+
+def read_rows(path):
+    """The rows of one file, and of nothing else."""
     rows = []
     with open(path) as f:
         lines = f.read().split("\n")
@@ -122,6 +134,14 @@ def read_file(path):
             continue
         unit, mangled, demangled, files = ln.split("\t")
         rows.append((unit, mangled, demangled, [t for t in files.split(",") if t]))
+    return rows
+
+
+def read_file(path):
+    """The rows of a file, followed by the rows of its parts (a supplement has none)."""
+    rows = read_rows(path)
+    for part in parts(path):
+        rows += read_rows(part)
     return rows
 
 
@@ -135,11 +155,12 @@ def read_map(path=MAP):
 
 
 def write_map(kernels, seen, path=MAP):
-    """The rows of every kernel of the build: a kernel that a supplement of `path` lists stays in that supplement, every other
-    one goes to `path`; a supplement none of whose kernels is left in the build is written with its header alone."""
+    """The rows of every kernel of the build: a kernel that a part or a supplement of `path` lists stays in that file, every
+    other one goes to `path`; a file none of whose kernels is left in the build is written with its header alone."""
     pretty = demangle(n for names in kernels.values() for n in names)
-    home = {r[1]: extra for extra in supplements(path) for r in read_file(extra)}
-    lines = {p: [] for p in [path] + supplements(path)}
+    others = parts(path) + supplements(path)
+    home = {r[1]: extra for extra in others for r in read_rows(extra)}
+    lines = {p: [] for p in [path] + others}
     for unit in sorted(kernels):
         for n in kernels[unit]:
             lines[home.get(n, path)].append(f"{unit}\t{n}\t{pretty[n]}\t{','.join(sorted(seen.get(n, ())))}\n")
