@@ -2008,6 +2008,67 @@ stk_status stk_background_flatten(stk_ctx* ctx, const stk_frames* frames, const 
                                   size_t out_row_stride_bytes, float* const* planes_out_or_null, float* const* rms_out_or_null,
                                   stk_bg_cell* cells_out_or_null);
 
+/* ---- deconvolution: Richardson-Lucy on a finished stack, with a PSF from its stars: an EXTENSION beyond the reference --
+ * The consumer of the measured star shapes (stk_star_measure): a PSF model from their second moments, and the
+ * Richardson-Lucy iteration of a linear f32 image with it, optionally with the total-variation regulariser of Dey et al.
+ * It runs on the finished stack, after the combine and stk_background_flatten, before any stretch.
+ * Everything is f32 and each operation is rounded on its own (no contraction); every fmaf below is one; `/` and sqrtf are
+ * the correctly rounded ones.
+ * Inputs: an stk_image_f32 d with 1, 3 or 4 channels; a PSF P[(2R+1)^2], row-major, R = radius; optionally a one-channel
+ *   f32 mask plane M (width x height, its own row stride in bytes, 0 = tightly packed; host or device memory). Channels
+ *   are processed independently with the same PSF; with 4 channels the fourth (alpha) is copied through unchanged.
+ * 1. D(q) = d(q) + pedestal; a D that is not finite or is below 0 becomes 0. u_0 = D.
+ * 2. For k = 0 .. iterations - 1, coordinates outside the image mapped by BORDER_REFLECT_101:
+ *      A(q) = sum_j sum_i P[j+R][i+R] u_k(x - i, y - j): acc = 0.0f; acc = fmaf(P, u, acc), j = -R .. R outermost, i = -R .. R
+ *        inside it (a true convolution).
+ *      r(q) = D(q) / fmaxf(A(q), floor).
+ *      C(q) = sum_j sum_i P[j+R][i+R] r(x + i, y + j), same order, same border (a correlation: the flipped PSF).
+ *      v(q) = u_k(q) C(q).
+ *      lambda == 0: u_{k+1} = v. lambda > 0, forward differences:
+ *        gx(q) = u_k(x+1, y) - u_k(q), 0 in the last column; gy(q) = u_k(x, y+1) - u_k(q), 0 in the last row;
+ *        n = sqrtf(fmaf(gx, gx, fmaf(gy, gy, e2))), e2 = tv_eps * tv_eps computed once on the host in f32;
+ *        px = gx / n; py = gy / n; div(q) = (px(q) - px(x-1, y)) + (py(q) - py(x, y-1)), px at x = -1 and py at y = -1 are 0;
+ *        u_{k+1}(q) = v(q) / fmaxf(fmaf(-lambda, div, 1.0f), 0.5f).
+ * 3. m(q) = amount without a mask, else amount * M(q). m == 1.0f: o = u_K - pedestal; else o = fmaf(m, u_K - D, D) - pedestal.
+ * Checks (anything else is STK_INVALID_PARAMS): iterations 1 .. 1000; radius 1 .. 16; width and height >= radius + 1;
+ *   floor finite and > 0; pedestal finite; lambda finite and >= 0; tv_eps finite and > 0; amount 0 .. 1; reserved 0; every
+ *   PSF tap finite and >= 0; the PSF's f64 sum (row-major order) within 1e-3 of 1.
+ * In place: `out` may be exactly the input (same pointer, same row stride): the work runs on workspace copies. Any other
+ *   overlap of out with the input or the mask in the same memory space is refused. out has the input's geometry and location.
+ * No result depends on scheduling, on the tiling or on what the context held before; a padded or misaligned image gives
+ *   the bits of its tight copy; host and device images give the same bits. Only pixel bytes are written.
+ * Not here: an empirical PSF from star cut-outs, a separable path for rank-1 PSFs, per-channel or spatially varying PSFs,
+ *   early stopping, automatic star-protection masks, shard and files forms. A multi-device context uses its first device. */
+enum { STK_PSF_GAUSSIAN = 0, STK_PSF_MOFFAT = 1 };
+typedef struct {
+    int32_t iterations;   /* 1 .. 1000, default 30 */
+    int32_t radius;       /* R, 1 .. 16, default 8 */
+    float   floor;        /* finite, > 0, default 1e-6 */
+    float   pedestal;     /* finite, default 0 */
+    float   lambda;       /* finite, >= 0; 0 = no regulariser; default 0 */
+    float   tv_eps;       /* finite, > 0, default 1e-3 */
+    float   amount;       /* 0 .. 1, default 1 */
+    int32_t reserved;     /* 0 */
+} stk_deconv_params;
+/* psf: (2R+1)^2 host floats. stk_timing.finalize_ms is the launches alone; prep_ms and warp_ms are the ratio and the update
+ * launch of the last iteration. */
+stk_status stk_deconvolve(stk_ctx* ctx, const stk_image_f32* in, const float* psf, const stk_deconv_params* params,
+                          const float* mask_or_null, size_t mask_stride_bytes, int32_t mask_location, stk_image_f32* out);
+/* A PSF model from a covariance (host code, f64, no context): with d = (i, j), i, j = -radius .. radius, and
+ * q = d^T S^-1 d, S = [[cxx, cxy], [cxy, cyy]]: STK_PSF_GAUSSIAN exp(-q / 2); STK_PSF_MOFFAT
+ * pow(1 + q (2^(1/beta) - 1) / (2 ln 2), -beta), which has the Gaussian's half-maximum contour. In f64, each operation
+ * rounded on its own: det = cxx cyy - cxy cxy; q = ((cyy i) i - (2 cxy i) j + (cxx j) j) / det; Moffat's
+ * g = (pow(2, 1 / beta) - 1) / (2 log(2)) once, value pow(1 + q g, -beta). Sampled at pixel centres, divided by the f64 sum taken in row-major order,
+ * cast to f32; psf: (2 radius + 1)^2 floats, row j then column i. S not positive definite (cxx > 0, cyy > 0, det > 0,
+ * all finite), beta not finite or <= 1 for Moffat, an unknown kind, radius outside 1 .. 16, null psf: STK_INVALID_PARAMS. */
+stk_status stk_psf_model(int32_t kind, double beta, int32_t radius, double cxx, double cyy, double cxy, float* psf);
+/* The covariance of a frame's stars (host code): over the `count` shapes with flags == 0 and snr >= min_snr the lower
+ * medians (the ((m + 1) / 2)-th smallest of m) of cxx, cyy and cxy, each on its own, each multiplied by scale * scale
+ * (isophotal moments read a few per cent low; 1 = as measured). used: m (may be null). No shape left, a result that is not
+ * finite or not positive definite, count < 0, scale or min_snr not finite, scale <= 0, null arguments: STK_INVALID_PARAMS. */
+stk_status stk_psf_from_shapes(const stk_star_shape* shapes, int32_t count, double min_snr, double scale, double* cxx,
+                               double* cyy, double* cxy, int32_t* used_or_null);
+
 /* One frame's whole ECC preparation as ecc_match runs it per frame: cvt_color(BGR2GRAY) (utils.rs:136-142) followed
  * by findTransformECC's own GaussianBlur of the float image (lib.rs:769-777) in one fused pass. `out` is a tightly
  * packed width x height f32 plane in the frame's location. BGR frames, 8-bit or f32. */

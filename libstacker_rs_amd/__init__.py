@@ -20,7 +20,8 @@ from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_RE
                   star_match_lists,
                   QUALITY_DTYPE, SHAPE_DTYPE, STAR_SCORE_COUNT, STAR_SCORE_FWHM, STAR_SCORE_ROUND, STAR_SCORE_SNR, StarMeasureParameters,
                   StarQualityParameters, star_frame_quality, star_quality_scores, star_quality_weights, star_shape_derive,
-                  BG_CELL_DTYPE, BG_MEAN, BG_MEDIAN, BG_MODE, BackgroundParameters, background_estimate)
+                  BG_CELL_DTYPE, BG_MEAN, BG_MEDIAN, BG_MODE, BackgroundParameters, background_estimate,
+                  PSF_GAUSSIAN, PSF_MOFFAT, DeconvolveParameters, psf_from_shapes, psf_model)
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
@@ -31,4 +32,5 @@ __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchPa
            "StarMeasureParameters", "StarQualityParameters", "SHAPE_DTYPE", "QUALITY_DTYPE", "star_shape_derive", "star_frame_quality",
            "star_quality_scores", "star_quality_weights", "STAR_SCORE_FWHM", "STAR_SCORE_ROUND", "STAR_SCORE_SNR", "STAR_SCORE_COUNT",
            "BackgroundParameters", "background_estimate", "BG_CELL_DTYPE", "BG_MEDIAN", "BG_MEAN", "BG_MODE",
+           "DeconvolveParameters", "psf_model", "psf_from_shapes", "PSF_GAUSSIAN", "PSF_MOFFAT",
            "CFA_RGGB", "CFA_GRBG", "CFA_GBRG", "CFA_BGGR", "DEMOSAIC_BILINEAR", "DEMOSAIC_MHC", "DEMOSAIC_HA", "DEMOSAIC_SUPERPIXEL"]

@@ -154,6 +154,11 @@ class BackgroundParams(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class DeconvParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("radius", C.c_int32), ("floor", C.c_float), ("pedestal", C.c_float),
+                ("lambda", C.c_float), ("tv_eps", C.c_float), ("amount", C.c_float), ("reserved", C.c_int32)]
+
+
 class HgProblem(C.Structure):
     _fields_ = [("src_pts", C.c_void_p), ("dst_pts", C.c_void_p), ("n", C.c_int32), ("inlier_mask_or_null", C.c_void_p)]
 
@@ -449,6 +454,11 @@ SIGNATURES = {
     "stk_background_apply": (c_status, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "stk_background_flatten": (c_status, [C.c_void_p, C.c_void_p, C.POINTER(BackgroundParams), C.c_void_p, C.c_int32, C.c_void_p,
                                           C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(BgCell)]),
+    "stk_deconvolve": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_void_p, C.POINTER(DeconvParams), C.c_void_p, C.c_size_t, C.c_int32,
+                                  C.POINTER(ImageF32)]),
+    "stk_psf_model": (c_status, [C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "stk_psf_from_shapes": (c_status, [C.POINTER(StarShape), C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "stk_grey_blur_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_int32, C.c_void_p]),
     "stk_gaussian_blur_f32": (c_status, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p]),

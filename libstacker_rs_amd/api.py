@@ -678,6 +678,53 @@ def background_estimate(width: int, height: int, channels: int, depth: int, cell
     return res if len(res) > 1 else level
 
 
+PSF_GAUSSIAN, PSF_MOFFAT = range(2)                        # STK_PSF_*: the PSF model of deconvolution
+
+
+@dataclass
+class DeconvolveParameters:       # extension beyond the reference: include/stacker.h, stk_deconv_params
+    """Richardson-Lucy deconvolution of a linear f32 image: `iterations` (1 .. 1000) rounds with a PSF of `radius` (1 .. 16;
+    the PSF has (2 radius + 1)^2 taps). `floor` bounds the blurred estimate from below before the division; `pedestal` is
+    added to the image first (and taken off at the end) so that a sky around 0 stays positive; `lambda_` > 0 turns on the
+    total-variation regulariser with `tv_eps`; `amount` (0 .. 1) blends the result with the input, per pixel times the mask."""
+    iterations: int = 30
+    radius: int = 8
+    floor: float = 1e-6
+    pedestal: float = 0.0
+    lambda_: float = 0.0
+    tv_eps: float = 1e-3
+    amount: float = 1.0
+
+    def _c(self) -> _ffi.DeconvParams:
+        return _ffi.DeconvParams(int(self.iterations), int(self.radius), float(self.floor), float(self.pedestal), float(self.lambda_),
+                                 float(self.tv_eps), float(self.amount), 0)
+
+
+def psf_model(radius: int, cxx: float, cyy: float, cxy: float = 0.0, kind: int = PSF_GAUSSIAN, beta: float = 2.5):
+    """A PSF from a covariance (stk_psf_model; host code, no GPU): a (2 radius + 1)^2 float32 array that sums to 1, a
+    Gaussian exp(-q / 2), q = d^T S^-1 d, or a Moffat profile of exponent `beta` with the same half-maximum contour."""
+    r = int(radius)
+    out = np.zeros((max(2 * r + 1, 1), max(2 * r + 1, 1)), np.float32)
+    st = _ffi.load().stk_psf_model(int(kind), float(beta), r, float(cxx), float(cyy), float(cxy), C.c_void_p(out.ctypes.data))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("psf_model: radius 1 .. 16, a positive definite covariance, beta > 1 for Moffat")
+    return out
+
+
+def psf_from_shapes(shapes, min_snr: float = 0.0, scale: float = 1.0, return_used: bool = False):
+    """The covariance of a frame's stars (stk_psf_from_shapes; host code): (cxx, cyy, cxy), the lower medians over the
+    shapes (SHAPE_DTYPE, Stacker.star_measure) with flags == 0 and snr >= min_snr, times scale^2; return_used adds how many
+    shapes that were."""
+    s = np.ascontiguousarray(np.asarray(shapes, SHAPE_DTYPE).reshape(-1))
+    cxx, cyy, cxy, used = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int32(0)
+    st = _ffi.load().stk_psf_from_shapes(s.ctypes.data_as(C.POINTER(_ffi.StarShape)), s.size, float(min_snr), float(scale), C.byref(cxx),
+                                         C.byref(cyy), C.byref(cxy), C.byref(used))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("psf_from_shapes: no measured star left, or their moments are not positive definite")
+    res = (cxx.value, cyy.value, cxy.value)
+    return res + (used.value,) if return_used else res
+
+
 def _quantile_c(q) -> _ffi.QuantileParams:
     """QuantileParameters, a bare float, or None (the median)."""
     if q is None:
@@ -1788,6 +1835,58 @@ class Stacker:
             raise InvalidParams("flatten_image: an H x W x C float32 image expected")
         res = self.background_flatten([image], params, mask, return_planes=return_plane)
         return (res[0][0], res[1][0]) if return_plane else res[0]
+
+    # -- deconvolution (include/stacker.h, stk_deconv_params) ------------------------------------
+    def deconvolve_image(self, image, psf, params: Optional["DeconvolveParameters"] = None, mask=None, out=None):
+        """Richardson-Lucy deconvolution of a finished stack (stk_deconvolve): an H x W (x C) float32 image, array or device
+        tensor, C = 1, 3 or 4 (alpha is copied through), with `psf`, (2 R + 1)^2 float32 taps that sum to 1 (psf_model).
+        params None: the defaults with the PSF's radius. `mask`: an H x W float32 plane, host or device; the result is blended
+        with the input by amount * mask per pixel. Returns an H x W x C image where the input lives; `out`: the image to
+        write instead, which may be the input itself."""
+        taps = np.ascontiguousarray(np.asarray(psf.cpu().numpy() if _is_torch(psf) else psf, np.float32))
+        side = int(round(taps.size ** 0.5))
+        p = (params or DeconvolveParameters(radius=(side - 1) // 2))._c()
+        if taps.size != (2 * int(p.radius) + 1) ** 2:
+            raise InvalidParams("deconvolve_image: the PSF must have (2 radius + 1)^2 taps")
+        keep = []
+        img = self._image_arg(image, keep)
+        mptr, mstride, mloc = None, 0, HOST
+        if mask is not None:
+            mk = self._image_arg(mask, keep, "mask")
+            if (mk.width, mk.height, mk.channels) != (img.width, img.height, 1):
+                raise InvalidParams("mask: an H x W float32 plane expected")
+            mptr, mstride, mloc = C.c_void_p(mk.data), mk.row_stride_bytes, mk.location
+        if out is None:
+            res, addr = self._alloc(keep[0].device if img.location == DEVICE else None, (img.height, img.width, img.channels), np.float32)
+            o = _ffi.ImageF32(addr, img.width, img.height, img.channels, img.location, 0)
+        else:
+            res = out
+            if _is_torch(out) and not out.is_cuda:
+                out = out.numpy()
+            if str(out.dtype).replace("torch.", "") != "float32" or len(out.shape) not in (2, 3):
+                raise InvalidParams("out: an H x W x C float32 image expected")
+            rs = _image_stride_bytes(out)
+            if _is_torch(out):
+                self._tensor_ready(out)
+            keep.append(out)
+            o = _ffi.ImageF32(out.data_ptr() if _is_torch(out) else out.ctypes.data, int(out.shape[1]), int(out.shape[0]),
+                              int(out.shape[2]) if len(out.shape) == 3 else 1, DEVICE if _is_torch(out) else HOST, rs)
+        self._check(self._lib.stk_deconvolve(self._h, C.byref(img), C.c_void_p(taps.ctypes.data), C.byref(p), mptr, mstride, mloc, C.byref(o)))
+        return res
+
+    def psf_from_image(self, image, radius: int, deep: Optional["StarDeepParameters"] = None, measure: Optional["StarMeasureParameters"] = None,
+                       star: Optional["StarParameters"] = None, kind: int = PSF_GAUSSIAN, beta: float = 2.5, min_snr: float = 0.0,
+                       scale: float = 1.0, return_covariance: bool = False):
+        """The PSF of a finished stack from its own stars: star_detect_deep and star_measure on the image as a one-frame f32
+        stack, then psf_from_shapes and psf_model. Set deep.f32_scale so that sample * f32_scale spans the 16-bit key range.
+        Returns the (2 radius + 1)^2 float32 PSF; return_covariance adds (cxx, cyy, cxy, stars used)."""
+        if str(image.dtype).replace("torch.", "") != "float32" or len(image.shape) not in (2, 3):
+            raise InvalidParams("psf_from_image: an H x W x C float32 image expected")
+        stars = self.star_detect_deep([image], star, deep)
+        shapes = self.star_measure([image], stars, measure, deep)
+        cxx, cyy, cxy, used = psf_from_shapes(shapes[0], min_snr, scale, return_used=True)
+        psf = psf_model(radius, cxx, cyy, cxy, kind, beta)
+        return (psf, (cxx, cyy, cxy, used)) if return_covariance else psf
 
     def _frame_outputs(self, m, out_depth: int, out, keep):
         """The per-frame outputs of a call that writes one image per frame (stk_calibrate, the background calls): a fresh

@@ -403,6 +403,44 @@ struct BgApplyArgs {
     float target[4];
 };
 hipError_t launch_background_apply(const BgApplyArgs& a, int depth, int out_depth, int cn, hipStream_t s);
+// deconvolution (kernels_deconvolve.hip; definition: include/stacker.h, "deconvolution"). The work planes are planar f32,
+// w x h tightly packed, `plane` floats apart, one per colour channel (min(cn, 3) of them); strides of the caller's images
+// in floats. A workgroup owns a DCV_TW x (DCV_TH DCV_NY) tile of one plane; a thread DCV_NY runs of 4 outputs, 16 rows apart.
+#ifndef DCV_NY
+#define DCV_NY 2                             // rows of outputs per thread (1 or 2: measured)
+#endif
+constexpr int DCV_TW = 64, DCV_TH = 16 * DCV_NY;
+constexpr int DCV_PITCH = 128;               // floats per staged row: a multiple of 64 keeps ds_read_b128 conflict-free
+inline int dcv_halo(int radius) { return radius <= 8 ? 8 : 16; }                  // the staged halo along x, by radius class
+inline int dcv_tap_pitch(int radius) { return 2 * dcv_halo(radius) + 8; }         // floats per row of the padded tap table
+inline size_t dcv_tap_floats(int radius) { return (size_t)(2 * radius + 1) * dcv_tap_pitch(radius); }
+// the padded tap table of a PSF: row j + R, column i + halo + 3 holds P[j + R][i + R]; the rest is 0 and is never multiplied
+inline void dcv_pad_taps(const float* psf, int radius, float* table) {
+    const int side = 2 * radius + 1, pitch = dcv_tap_pitch(radius), H = dcv_halo(radius);
+    for (size_t k = 0; k < dcv_tap_floats(radius); k++) table[k] = 0.0f;
+    for (int j = 0; j < side; j++)
+        for (int i = 0; i < side; i++) table[(size_t)j * pitch + (i - radius + H + 3)] = psf[j * side + i];
+}
+// D = in + pedestal, not finite or below 0 -> 0, de-interleaved; cn == 4: the alpha samples go to `out` as they are
+struct DeconvInitArgs {
+    const float* in; float* out; float* D;
+    size_t in_stride, out_stride, plane;
+    int w, h;
+    float pedestal;
+};
+hipError_t launch_deconv_init(const DeconvInitArgs& a, int cn, hipStream_t s);
+// one pass over the colour planes. Ratio: stage u (src), dst = D / fmaxf(P * u, floor). Update: stage r (src), v = u C, the
+// regulariser (lambda > 0), dst = u_{k+1}; last != 0: the output step into `out` (pixel stride cn floats) instead of dst.
+struct DeconvPassArgs {
+    const float* taps;                       // dcv_pad_taps, on the device
+    const float* src; const float* D; const float* u; float* dst;
+    float* out; const float* mask;           // mask: one f32 plane or null
+    size_t out_stride, mask_stride, plane;
+    int w, h, cn, channels, radius, last;    // channels: planes of the launch
+    float floor, lambda, e2, amount, pedestal;
+};
+hipError_t launch_deconv_ratio(const DeconvPassArgs& a, hipStream_t s);
+hipError_t launch_deconv_update(const DeconvPassArgs& a, hipStream_t s);
 // colour-filter mosaics (kernels_demosaic.hip; definition: include/stacker.h, stk_mosaic). One record per frame of the
 // launch; strides in bytes; (w, h): the mosaic's size, at least 3 x 3 (superpixel: 2 x 2).
 constexpr int DEM_TW = 64, DEM_TH = 16;      // output pixels per workgroup tile of demosaic_kernel (32 x 8 cells of 2 x 2)

@@ -255,6 +255,26 @@ inline BgLayout bg_layout(size_t n_frames, size_t mask_bytes, size_t cell_bytes,
     return L;
 }
 
+// ctx->local, deconvolution (deconvolve.cpp): the padded tap table, then per colour channel (`channels` = min(cn, 3)) the
+// planar work images, `plane` bytes apart inside each: D (which is u_0), the two u planes of the ping-pong and r; the
+// copies of a host image and of a host mask (0 bytes for device ones), the staged output of a host image
+struct DeconvLayout { size_t taps, D, u[2], r, plane, image, mask, out, total; };
+inline DeconvLayout deconv_layout(int radius, int w, int h, int channels, size_t image_bytes, size_t mask_bytes, size_t out_bytes) {
+    Carver c;
+    DeconvLayout L{};
+    L.taps = c.take(stk::dcv_tap_floats(radius) * sizeof(float));
+    L.plane = up256((size_t)w * h * sizeof(float));
+    L.D = c.take((size_t)channels * L.plane);
+    L.u[0] = c.take((size_t)channels * L.plane);
+    L.u[1] = c.take((size_t)channels * L.plane);
+    L.r = c.take((size_t)channels * L.plane);
+    L.image = c.take(image_bytes);
+    L.mask = c.take(mask_bytes);
+    L.out = c.take(out_bytes);
+    L.total = c.total;
+    return L;
+}
+
 // ctx->local, colour-filter mosaics (demosaic.cpp): the per-frame records, then the tightly packed outputs of host mosaics
 // (stk_cfa_mask: no records, the plane of a host caller)
 struct DemosaicLayout { size_t records, out, total; };

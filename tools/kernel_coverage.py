@@ -22,6 +22,15 @@ them with the main file and not beside it (tests/test_cpu_star_measure.py pins r
 of the first supplement, which a second supplement counted beside the main file cannot meet). Everything else is the same
 for a part: its own file, same header, every row checked against the tree, `map` writes its rows back into it.
 
+Units named in OWN have a map of their own, tests/kernel_own_<feature>.tsv (same header, same columns), that read_map does
+NOT return and whose units build_kernels leaves out unless asked (own=True): three existing tests pin read_map between them
+(test_cpu_kernel_map.py: read_map = the kernels build_kernels returns; test_cpu_star_measure.py: read_map = the main file with
+its parts + nine rows; test_cpu_background.py: parts = the background file alone), so new rows that read_map counts can go into
+tests/kernel_map.tsv alone, and that is a committed file under tests/, which a feature change leaves byte for byte. (A change
+that may edit it puts its rows there and needs none of this.) Such a unit is held to the same standard by the test that comes
+with it: the kernels build_kernels(own=True) finds in it = the rows of its file, every row naming a qualifying GPU test file.
+`kernels`, `map` and `uncovered` take these units and files along.
+
 Covered: launched by a tests/test_gpu_*.py other than test_gpu_fullsize.py and the test_gpu_00_* bench and multi-rank
 files. Exit status of `uncovered` is 1 if any row has no qualifying file. Only symbol names are read, never instructions."""
 import argparse
@@ -39,6 +48,7 @@ CSRC = os.path.join(ROOT, "libstacker_rs_amd", "csrc")
 MAP = os.path.join(ROOT, "tests", "kernel_map.tsv")
 HEADER = "unit\tmangled\tdemangled\ttest files"
 PARTS = ("background",)                      # tests/kernel_map_<name>.tsv read as a part of tests/kernel_map.tsv (see above)
+OWN = {"kernels_deconvolve": "deconvolve"}   # unit -> feature: its rows are tests/kernel_own_<feature>.tsv (see above)
 MAX_COMPILES = 16
 SYMBOL = re.compile(r"_ZN3stk\w+")
 
@@ -66,9 +76,24 @@ def unit_commands(csrc=CSRC):
     return cmds
 
 
-def build_kernels(csrc=CSRC, workdir=None):
-    """{unit: sorted mangled kernel names} of the tree under `csrc`, compiled as its Makefile compiles it."""
-    cmds = unit_commands(csrc)
+def own_file(unit, path=MAP):
+    """The map file of a unit named in OWN, beside `path`."""
+    return os.path.join(os.path.dirname(path), "kernel_own_" + OWN[unit] + ".tsv")
+
+
+def read_own(path=MAP):
+    """The rows of every own map that exists, units sorted."""
+    rows = []
+    for unit in sorted(OWN):
+        if os.path.isfile(own_file(unit, path)):
+            rows += read_rows(own_file(unit, path))
+    return rows
+
+
+def build_kernels(csrc=CSRC, workdir=None, own=False):
+    """{unit: sorted mangled kernel names} of the tree under `csrc`, compiled as its Makefile compiles it: the units read_map
+    answers for, or (own=True) the units named in OWN."""
+    cmds = {u: c for u, c in unit_commands(csrc).items() if (u in OWN) == own}
     with tempfile.TemporaryDirectory(dir=workdir) as tmp:
         def one(unit):
             out = os.path.join(tmp, unit + ".s")
@@ -160,10 +185,10 @@ def write_map(kernels, seen, path=MAP):
     pretty = demangle(n for names in kernels.values() for n in names)
     others = parts(path) + supplements(path)
     home = {r[1]: extra for extra in others for r in read_rows(extra)}
-    lines = {p: [] for p in [path] + others}
+    lines = {p: [] for p in [path] + others + [own_file(u, path) for u in sorted(kernels) if u in OWN]}
     for unit in sorted(kernels):
         for n in kernels[unit]:
-            lines[home.get(n, path)].append(f"{unit}\t{n}\t{pretty[n]}\t{','.join(sorted(seen.get(n, ())))}\n")
+            lines[own_file(unit, path) if unit in OWN else home.get(n, path)].append(f"{unit}\t{n}\t{pretty[n]}\t{','.join(sorted(seen.get(n, ())))}\n")
     for p, body in lines.items():
         with open(p, "w") as f:
             f.write(HEADER + "\n" + "".join(body))
@@ -185,18 +210,18 @@ def main():
     u.add_argument("--map", default=MAP)
     args = ap.parse_args()
     if args.cmd == "kernels":
-        for unit, names in build_kernels().items():
+        for unit, names in sorted({**build_kernels(), **build_kernels(own=True)}.items()):
             for n in names:
                 print(f"{unit}\t{n}")
         return 0
     if args.cmd == "map":
         seen, traced = launched(args.traces)
         if args.keep:
-            for _, mangled, _, files in read_map(args.out):
+            for _, mangled, _, files in read_map(args.out) + read_own(args.out):
                 for t in files:
                     if t not in traced:
                         seen.setdefault(mangled, set()).add(t)
-        kernels = build_kernels()
+        kernels = {**build_kernels(), **build_kernels(own=True)}
         known = {n for names in kernels.values() for n in names}
         strangers = sorted(set(seen) - known)
         if strangers:
@@ -204,7 +229,8 @@ def main():
             return 2
         write_map(kernels, seen, args.out)
         print(f"{args.out}: {len(known)} kernels, {len(traced)} test files traced")
-    rows = read_map(getattr(args, "map", None) or getattr(args, "out", MAP))
+    which = getattr(args, "map", None) or getattr(args, "out", MAP)
+    rows = read_map(which) + read_own(which)
     bare = uncovered(rows)
     per_unit = {}
     for unit, mangled, demangled, files in bare:
