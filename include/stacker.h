@@ -2069,6 +2069,75 @@ stk_status stk_psf_model(int32_t kind, double beta, int32_t radius, double cxx, 
 stk_status stk_psf_from_shapes(const stk_star_shape* shapes, int32_t count, double min_snr, double scale, double* cxx,
                                double* cyy, double* cxy, int32_t* used_or_null);
 
+/* ---- wavelet layers: the a trous (starlet) decomposition of a finished stack: an EXTENSION beyond the reference ---------
+ * Multiscale denoising (thresholds on the fine layers against the noise those layers carry), sharpening (gains on the fine
+ * layers), separation of structures by scale, and the noise of a finished f32 stack (the first layer's MAD). It runs on
+ * the linear f32 stack beside stk_deconvolve: after the combine and stk_background_flatten, before any stretch.
+ * Everything is f32 and each operation is rounded on its own (no contraction); every fmaf below is one. Channels are
+ * processed independently; with 4 channels the fourth (alpha) is copied through unchanged.
+ * Inputs: an stk_image_f32 d with 1, 3 or 4 channels, host or device, any row stride that is a multiple of 4 bytes;
+ *   levels J, 1 .. 8; optionally a one-channel f32 mask plane M (width x height, its own row stride in bytes, 0 = tightly
+ *   packed; host or device memory), as stk_deconvolve takes it.
+ * 1. D(q) = d(q) if it is finite and fabsf(d) <= 1e30f, else 0. c_0 = D. Every later value is finite.
+ * 2. For j = 0 .. J - 1, s = 2^j, indices outside the image mapped by BORDER_REFLECT_101 (one reflection is enough: see
+ *    the size check):
+ *      hx(x, y): a = 0.0625f c_j(x - 2s, y); a = fmaf(0.25f, c_j(x - s, y), a); a = fmaf(0.375f, c_j(x, y), a);
+ *                a = fmaf(0.25f, c_j(x + s, y), a); a = fmaf(0.0625f, c_j(x + 2s, y), a).
+ *      c_{j+1}(x, y): the same chain over hx(x, y - 2s), hx(x, y - s), hx(x, y), hx(x, y + s), hx(x, y + 2s).
+ *      w_j = c_j - c_{j+1}.
+ * 3. The layer operation, with the f32 values t_j (step 5), keep_j = 1 - layer_amount_j (f32, on the host) and gain_j;
+ *    m = fabsf(w_j):
+ *      STK_WAVELET_HARD: w' = m < t_j ? w_j keep_j : w_j.
+ *      STK_WAVELET_SOFT: z = copysignf(fmaxf(m - t_j, 0), w_j); w' = fmaf(layer_amount_j, z - w_j, w_j).
+ *      acc_0 = gain_0 w'_0; acc_j = acc_{j-1} + gain_j w'_j.
+ * 4. res = fmaf(residual_gain, c_J, acc_{J-1}). mm = amount without a mask, else amount * M(q). mm == 1.0f: o = res; else
+ *    o = fmaf(mm, res - D, D).
+ * 5. t_j = (float)(threshold_j * sigma_c * e_j) in f64 on the host, for channel c. e_j is the standard deviation of layer j
+ *    of unit white noise, derived from the filter (stk_wavelet_noise_table): with a_j the 1-D impulse response of the
+ *    cascade up to c_j (a_0 = the unit impulse), e_j^2 = (sum a_j^2)^2 - 2 (sum a_j a_{j+1})^2 + (sum a_{j+1}^2)^2 in f64.
+ *    sigma_c is the caller's (sigma_given != 0: sigma[c]) or estimated: sigma_c = (float)(1.4826 * (double)med_c / e_0),
+ *    med_c the lower median (the ((N + 1) / 2)-th smallest of N = width * height) of fabsf(w_0) over the channel, exact.
+ *    The estimation pass runs only where it is needed: some threshold_j > 0 (j < levels) with sigma not given, or the caller
+ *    asked for sigma. sigma = 0 gives t = 0 and nothing is below it. A sigma that was neither given nor estimated reads 0.
+ * Checks (anything else is STK_INVALID_PARAMS): levels 1 .. 8; min(width, height) >= 2^levels + 1; gains and residual_gain
+ *   finite; thresholds finite and >= 0; layer_amount and amount 0 .. 1 (all eight entries of each table are checked); given
+ *   sigmas finite and >= 0; a known mode; reserved 0; out has the input's geometry and location.
+ * In place: `out` may be exactly the input (same pointer, same row stride). Any other overlap of an output with the input,
+ *   the mask or another output in the same memory space is refused.
+ * No result depends on scheduling, on the tiling or on what the context held before; a padded or misaligned image gives
+ *   the bits of its tight copy; host and device images give the same bits. Only pixel bytes are written.
+ * Not here: per-layer MAD instead of the table, a multiscale median transform, deringing, per-channel parameters, a
+ *   stretch, shard and files forms. A multi-device context uses its first device. */
+enum { STK_WAVELET_HARD = 0, STK_WAVELET_SOFT = 1 };
+typedef struct {
+    int32_t levels;           /* J, 1 .. 8, default 4 */
+    int32_t mode;             /* STK_WAVELET_HARD (default) or STK_WAVELET_SOFT */
+    int32_t sigma_given;      /* != 0: sigma[] holds the noise per channel; 0 (default): estimated where needed */
+    int32_t reserved;         /* 0 */
+    float   gain[8];          /* finite, default 1 */
+    float   threshold[8];     /* finite, >= 0, in units of the layer's noise; default 0 */
+    float   layer_amount[8];  /* 0 .. 1, default 1 */
+    float   residual_gain;    /* finite, default 1 */
+    float   amount;           /* 0 .. 1, default 1 */
+    float   sigma[4];         /* finite, >= 0; read when sigma_given != 0 */
+} stk_wavelet_params;
+/* Steps 1 - 5. sigma_out_or_null: 4 floats, the sigma of each colour channel as used (given, estimated, or 0 where neither);
+ * entries from min(channels, 3) on are 0. With the defaults the call is the reconstruction: the input to within the f32
+ * rounding of the sums. stk_timing.finalize_ms is the launches alone; prep_ms is the estimation pass (0 where it did not
+ * run), warp_ms the launch of the last level and align_ms that of the level before it (0 with one level). */
+stk_status stk_wavelet_process(stk_ctx* ctx, const stk_image_f32* in, const stk_wavelet_params* params, const float* mask_or_null,
+                               size_t mask_stride_bytes, int32_t mask_location, stk_image_f32* out, float* sigma_out_or_null);
+/* Steps 1 - 2 alone: out is an array of levels + 1 images of the input's geometry and location, w_0 .. w_{J-1} then c_J; bit
+ * for bit the w_j and c_J that stk_wavelet_process uses. With 4 channels every output's fourth channel is the input's.
+ * No output may overlap the input or another output. */
+stk_status stk_wavelet_layers(stk_ctx* ctx, const stk_image_f32* in, int32_t levels, stk_image_f32* out);
+/* The estimate of step 5 alone, the noise of a finished f32 stack: sigma: 4 floats (entries from min(channels, 3) on are
+ * 0); median_or_null: 4 floats, med_c. The image must be at least 3 x 3. */
+stk_status stk_wavelet_sigma(stk_ctx* ctx, const stk_image_f32* in, float* sigma, float* median_or_null);
+/* e_0 .. e_{levels-1} of step 5 (host code, no context): 0.8907963103, 0.2006638510, 0.0855075048, ... levels outside
+ * 1 .. 8 or a null table: STK_INVALID_PARAMS. */
+stk_status stk_wavelet_noise_table(int32_t levels, double* e);
+
 /* One frame's whole ECC preparation as ecc_match runs it per frame: cvt_color(BGR2GRAY) (utils.rs:136-142) followed
  * by findTransformECC's own GaussianBlur of the float image (lib.rs:769-777) in one fused pass. `out` is a tightly
  * packed width x height f32 plane in the frame's location. BGR frames, 8-bit or f32. */

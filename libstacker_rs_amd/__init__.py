@@ -21,7 +21,8 @@ from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_RE
                   QUALITY_DTYPE, SHAPE_DTYPE, STAR_SCORE_COUNT, STAR_SCORE_FWHM, STAR_SCORE_ROUND, STAR_SCORE_SNR, StarMeasureParameters,
                   StarQualityParameters, star_frame_quality, star_quality_scores, star_quality_weights, star_shape_derive,
                   BG_CELL_DTYPE, BG_MEAN, BG_MEDIAN, BG_MODE, BackgroundParameters, background_estimate,
-                  PSF_GAUSSIAN, PSF_MOFFAT, DeconvolveParameters, psf_from_shapes, psf_model)
+                  PSF_GAUSSIAN, PSF_MOFFAT, DeconvolveParameters, psf_from_shapes, psf_model,
+                  WAVELET_HARD, WAVELET_SOFT, WaveletParameters, wavelet_noise_table)
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
@@ -33,4 +34,5 @@ __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchPa
            "star_quality_scores", "star_quality_weights", "STAR_SCORE_FWHM", "STAR_SCORE_ROUND", "STAR_SCORE_SNR", "STAR_SCORE_COUNT",
            "BackgroundParameters", "background_estimate", "BG_CELL_DTYPE", "BG_MEDIAN", "BG_MEAN", "BG_MODE",
            "DeconvolveParameters", "psf_model", "psf_from_shapes", "PSF_GAUSSIAN", "PSF_MOFFAT",
+           "WaveletParameters", "wavelet_noise_table", "WAVELET_HARD", "WAVELET_SOFT",
            "CFA_RGGB", "CFA_GRBG", "CFA_GBRG", "CFA_BGGR", "DEMOSAIC_BILINEAR", "DEMOSAIC_MHC", "DEMOSAIC_HA", "DEMOSAIC_SUPERPIXEL"]

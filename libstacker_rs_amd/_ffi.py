@@ -159,6 +159,12 @@ class DeconvParams(C.Structure):
                 ("lambda", C.c_float), ("tv_eps", C.c_float), ("amount", C.c_float), ("reserved", C.c_int32)]
 
 
+class WaveletParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("mode", C.c_int32), ("sigma_given", C.c_int32), ("reserved", C.c_int32),
+                ("gain", C.c_float * 8), ("threshold", C.c_float * 8), ("layer_amount", C.c_float * 8),
+                ("residual_gain", C.c_float), ("amount", C.c_float), ("sigma", C.c_float * 4)]
+
+
 class HgProblem(C.Structure):
     _fields_ = [("src_pts", C.c_void_p), ("dst_pts", C.c_void_p), ("n", C.c_int32), ("inlier_mask_or_null", C.c_void_p)]
 
@@ -459,6 +465,11 @@ SIGNATURES = {
     "stk_psf_model": (c_status, [C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "stk_psf_from_shapes": (c_status, [C.POINTER(StarShape), C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "stk_wavelet_process": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.POINTER(WaveletParams), C.c_void_p, C.c_size_t, C.c_int32,
+                                       C.POINTER(ImageF32), C.c_void_p]),
+    "stk_wavelet_layers": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_int32, C.POINTER(ImageF32)]),
+    "stk_wavelet_sigma": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_void_p, C.c_void_p]),
+    "stk_wavelet_noise_table": (c_status, [C.c_int32, C.POINTER(C.c_double)]),
     "stk_grey_blur_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_int32, C.c_void_p]),
     "stk_gaussian_blur_f32": (c_status, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p]),

@@ -725,6 +725,60 @@ def psf_from_shapes(shapes, min_snr: float = 0.0, scale: float = 1.0, return_use
     return res + (used.value,) if return_used else res
 
 
+WAVELET_HARD, WAVELET_SOFT = range(2)                      # STK_WAVELET_*: the layer operation of the wavelet layers
+
+
+@dataclass
+class WaveletParameters:          # extension beyond the reference: include/stacker.h, stk_wavelet_params
+    """The a trous wavelet layers of a linear f32 image: `levels` (1 .. 8) layers w_0 .. w_{levels-1} of scale 2^j and the
+    residual. Per layer: `gains` (1 = as it is, > 1 sharpens), `thresholds` in units of the layer's noise (0 = none) below
+    which a coefficient is shrunk (`mode` WAVELET_HARD: multiplied by 1 - layer_amount; WAVELET_SOFT: moved towards 0 by the
+    threshold, blended by layer_amount), `layer_amounts` (0 .. 1). A scalar stands for every level. `residual_gain` scales
+    the residual, `amount` (0 .. 1) blends the result with the input, per pixel times the mask. `sigma`: the noise per
+    channel (a scalar or up to 4 values); None: estimated from the first layer's median where a threshold needs it. The
+    defaults reconstruct the input."""
+    levels: int = 4
+    mode: int = WAVELET_HARD
+    gains: object = 1.0
+    thresholds: object = 0.0
+    layer_amounts: object = 1.0
+    residual_gain: float = 1.0
+    amount: float = 1.0
+    sigma: object = None
+
+    @staticmethod
+    def _table(v, n, what):
+        a = np.asarray(v, np.float64).reshape(-1)
+        if a.size == 1:
+            a = np.repeat(a, n)
+        if a.size > n:
+            raise InvalidParams(f"{what}: at most {n} values")
+        return a
+
+    def _c(self) -> _ffi.WaveletParams:
+        c = _ffi.WaveletParams(int(self.levels), int(self.mode), 0 if self.sigma is None else 1, 0)
+        for name, v, fill in (("gain", self.gains, 1.0), ("threshold", self.thresholds, 0.0), ("layer_amount", self.layer_amounts, 1.0)):
+            a = self._table(v, 8, name)
+            getattr(c, name)[:] = [float(x) for x in a] + [fill] * (8 - a.size)
+        c.residual_gain, c.amount = float(self.residual_gain), float(self.amount)
+        if self.sigma is not None:
+            a = self._table(self.sigma, 4, "sigma")
+            c.sigma[:] = [float(x) for x in a] + [0.0] * (4 - a.size)
+        return c
+
+
+def wavelet_noise_table(levels: int = 8):
+    """e_0 .. e_{levels-1}: the standard deviation of each wavelet layer of unit white noise (stk_wavelet_noise_table; host
+    code, no GPU), float64."""
+    if not 1 <= int(levels) <= 8:
+        raise InvalidParams("wavelet_noise_table: levels 1 .. 8")
+    e = np.zeros(int(levels), np.float64)
+    st = _ffi.load().stk_wavelet_noise_table(int(levels), e.ctypes.data_as(C.POINTER(C.c_double)))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("wavelet_noise_table: levels 1 .. 8")
+    return e
+
+
 def _quantile_c(q) -> _ffi.QuantileParams:
     """QuantileParameters, a bare float, or None (the median)."""
     if q is None:
@@ -1887,6 +1941,72 @@ class Stacker:
         cxx, cyy, cxy, used = psf_from_shapes(shapes[0], min_snr, scale, return_used=True)
         psf = psf_model(radius, cxx, cyy, cxy, kind, beta)
         return (psf, (cxx, cyy, cxy, used)) if return_covariance else psf
+
+    # -- wavelet layers (include/stacker.h, stk_wavelet_params) ---------------------------------
+    def _image_out(self, out, keep):
+        """An H x W x C float32 image the caller holds, to be written: its stk_image_f32."""
+        if _is_torch(out) and not out.is_cuda:
+            out = out.numpy()
+        if str(out.dtype).replace("torch.", "") != "float32" or len(out.shape) not in (2, 3):
+            raise InvalidParams("out: an H x W x C float32 image expected")
+        rs = _image_stride_bytes(out)
+        if _is_torch(out):
+            self._tensor_ready(out)
+        keep.append(out)
+        return _ffi.ImageF32(out.data_ptr() if _is_torch(out) else out.ctypes.data, int(out.shape[1]), int(out.shape[0]),
+                             int(out.shape[2]) if len(out.shape) == 3 else 1, DEVICE if _is_torch(out) else HOST, rs)
+
+    def wavelet_image(self, image, params: Optional["WaveletParameters"] = None, mask=None, out=None, return_sigma: bool = False):
+        """Multiscale denoising and sharpening of a finished stack (stk_wavelet_process): an H x W (x C) float32 image, array or
+        device tensor, C = 1, 3 or 4 (alpha is copied through). `mask`: an H x W float32 plane, host or device; the result is
+        blended with the input by amount * mask per pixel. Returns an H x W x C image where the input lives; `out`: the image
+        to write instead, which may be the input itself. return_sigma adds the noise of each colour channel as used (given,
+        estimated, or 0 where no threshold asked for it; asking estimates it), a float32 array of min(C, 3) values."""
+        p = (params or WaveletParameters())._c()
+        keep = []
+        img = self._image_arg(image, keep)
+        mptr, mstride, mloc = None, 0, HOST
+        if mask is not None:
+            mk = self._image_arg(mask, keep, "mask")
+            if (mk.width, mk.height, mk.channels) != (img.width, img.height, 1):
+                raise InvalidParams("mask: an H x W float32 plane expected")
+            mptr, mstride, mloc = C.c_void_p(mk.data), mk.row_stride_bytes, mk.location
+        if out is None:
+            res, addr = self._alloc(keep[0].device if img.location == DEVICE else None, (img.height, img.width, img.channels), np.float32)
+            o = _ffi.ImageF32(addr, img.width, img.height, img.channels, img.location, 0)
+        else:
+            res, o = out, self._image_out(out, keep)
+        sigma = np.zeros(4, np.float32)
+        self._check(self._lib.stk_wavelet_process(self._h, C.byref(img), C.byref(p), mptr, mstride, mloc, C.byref(o),
+                                                  C.c_void_p(sigma.ctypes.data) if return_sigma else None))
+        return (res, sigma[:min(img.channels, 3)].copy()) if return_sigma else res
+
+    def wavelet_layers(self, image, levels: int = 4):
+        """The wavelet layers of an image (stk_wavelet_layers): a list of levels + 1 H x W x C float32 images where the input
+        lives, w_0 .. w_{levels-1} and the residual c_levels; bit for bit what wavelet_image works on. Their sum is the
+        sanitised input to within rounding. With 4 channels every image's alpha is the input's."""
+        n = int(levels)
+        if not 1 <= n <= 8:
+            raise InvalidParams("wavelet_layers: levels must be 1 .. 8")
+        keep = []
+        img = self._image_arg(image, keep)
+        outs, arr = [], (_ffi.ImageF32 * (n + 1))()
+        for k in range(n + 1):
+            res, addr = self._alloc(keep[0].device if img.location == DEVICE else None, (img.height, img.width, img.channels), np.float32)
+            outs.append(res)
+            arr[k] = _ffi.ImageF32(addr, img.width, img.height, img.channels, img.location, 0)
+        self._check(self._lib.stk_wavelet_layers(self._h, C.byref(img), n, C.cast(arr, C.POINTER(_ffi.ImageF32))))
+        return outs
+
+    def wavelet_sigma(self, image, return_median: bool = False):
+        """The noise of a finished f32 stack (stk_wavelet_sigma): per colour channel 1.4826 / e_0 times the exact lower median
+        of the first wavelet layer's magnitudes; a float32 array of min(C, 3) values. return_median adds those medians."""
+        keep = []
+        img = self._image_arg(image, keep)
+        sigma, med = np.zeros(4, np.float32), np.zeros(4, np.float32)
+        self._check(self._lib.stk_wavelet_sigma(self._h, C.byref(img), C.c_void_p(sigma.ctypes.data), C.c_void_p(med.ctypes.data) if return_median else None))
+        cc = min(img.channels, 3)
+        return (sigma[:cc].copy(), med[:cc].copy()) if return_median else sigma[:cc].copy()
 
     def _frame_outputs(self, m, out_depth: int, out, keep):
         """The per-frame outputs of a call that writes one image per frame (stk_calibrate, the background calls): a fresh

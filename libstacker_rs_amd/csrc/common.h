@@ -441,6 +441,49 @@ struct DeconvPassArgs {
 };
 hipError_t launch_deconv_ratio(const DeconvPassArgs& a, hipStream_t s);
 hipError_t launch_deconv_update(const DeconvPassArgs& a, hipStream_t s);
+// wavelet layers (post/kernels_wavelet.hip; definition: include/stacker.h, "wavelet layers"). The work planes are planar f32,
+// w x h tightly packed, `plane` floats apart, one per colour channel (min(cn, 3) of them); strides of the caller's images
+// in floats. A workgroup owns WV_TW columns and, at tap spacing s, four rows of each of four residue classes modulo s: at
+// s = 1 a WV_TW x WV_TH tile.
+constexpr int WV_TW = 64, WV_TH = 16;
+constexpr int WV_FORM_DIRECT = 0, WV_FORM_STAGED = 1;
+constexpr int WV_STAGED_MAX_S = 32;          // at s = 64 the halo (2 s a side) outgrows the tile
+constexpr int WV_DIGIT_BITS = 8, WV_ROUNDS = 4, WV_BINS = 1 << WV_DIGIT_BITS;     // the radix selection: 4 rounds of 8 bits
+// c_0 = the sanitised image, de-interleaved; cn == 4 and `alpha`: the alpha samples go to every image of `alpha` as they are
+struct WvInitArgs {
+    const float* in; float* c0;
+    float* alpha[9]; size_t alpha_stride[9]; int n_alpha;
+    size_t in_stride, plane;
+    int w, h;
+};
+hipError_t launch_wavelet_init(const WvInitArgs& a, int cn, hipStream_t s);
+// one level over the colour planes: c_{j+1} = the dilated B3 spline of c_j (src -> dst), w_j = c_j - c_{j+1}.
+// layers == 0: the layer operation and acc (first: acc = gain w', else acc += gain w'); last: the output step into `out`
+// instead of dst and acc, D read again from `in`. layers != 0: w_j into `wout`, and on the last level c_J into `cout`.
+struct WvLevelArgs {
+    const float* src; float* dst; float* acc;
+    const float* in; float* out; const float* mask;
+    float* wout; float* cout;
+    size_t in_stride, out_stride, mask_stride, wout_stride, cout_stride, plane;
+    int w, h, cn, channels, s, mode, first, last, layers;
+    int form;                                // WV_FORM_*: the staged form applies up to WV_STAGED_MAX_S, beyond it the direct one runs
+    float t[3];                              // the threshold of this level per colour channel
+    float keep, layer_amount, gain, residual_gain, amount;
+};
+hipError_t launch_wavelet_level(const WvLevelArgs& a, hipStream_t s);
+// the selection of the ((N + 1) / 2)-th smallest key bits(fabsf(w_0)) per colour channel. state: per channel 2 words (the
+// prefix found so far, the rank left inside it), then per channel WV_BINS histogram words. reset: state = (0, rank) and
+// zero counts; hist: one round's counts of the digit below the prefix; pick: the digit, into the prefix, counts zeroed.
+struct WvSelectArgs {
+    const float* c0; uint32_t* state;
+    size_t plane;
+    int w, h, channels, round;
+    uint32_t rank;
+};
+inline size_t wv_state_words(int channels) { return (size_t)channels * (2 + WV_BINS); }
+hipError_t launch_wavelet_select_reset(const WvSelectArgs& a, hipStream_t s);
+hipError_t launch_wavelet_select_hist(const WvSelectArgs& a, hipStream_t s);
+hipError_t launch_wavelet_select_pick(const WvSelectArgs& a, hipStream_t s);
 // colour-filter mosaics (kernels_demosaic.hip; definition: include/stacker.h, stk_mosaic). One record per frame of the
 // launch; strides in bytes; (w, h): the mosaic's size, at least 3 x 3 (superpixel: 2 x 2).
 constexpr int DEM_TW = 64, DEM_TH = 16;      // output pixels per workgroup tile of demosaic_kernel (32 x 8 cells of 2 x 2)

@@ -275,6 +275,26 @@ inline DeconvLayout deconv_layout(int radius, int w, int h, int channels, size_t
     return L;
 }
 
+// ctx->local, the wavelet layers (wavelet.cpp): the selection's state and histogram words, then per colour channel
+// (`channels` = min(cn, 3)) the planar work images, `plane` bytes apart inside each: the two c planes of the ping-pong
+// (c[0] holds c_0) and acc; the copies of a host image and of a host mask (0 bytes for device ones), the staged outputs of
+// a host image (the layers form: levels + 1 of them)
+struct WaveletLayout { size_t state, c[2], acc, plane, image, mask, out, total; };
+inline WaveletLayout wavelet_layout(int w, int h, int channels, size_t image_bytes, size_t mask_bytes, size_t out_bytes) {
+    Carver c;
+    WaveletLayout L{};
+    L.state = c.take(stk::wv_state_words(channels) * sizeof(uint32_t));
+    L.plane = up256((size_t)w * h * sizeof(float));
+    L.c[0] = c.take((size_t)channels * L.plane);
+    L.c[1] = c.take((size_t)channels * L.plane);
+    L.acc = c.take((size_t)channels * L.plane);
+    L.image = c.take(image_bytes);
+    L.mask = c.take(mask_bytes);
+    L.out = c.take(out_bytes);
+    L.total = c.total;
+    return L;
+}
+
 // ctx->local, colour-filter mosaics (demosaic.cpp): the per-frame records, then the tightly packed outputs of host mosaics
 // (stk_cfa_mask: no records, the plane of a host caller)
 struct DemosaicLayout { size_t records, out, total; };

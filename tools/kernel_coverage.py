@@ -31,6 +31,13 @@ that may edit it puts its rows there and needs none of this.) Such a unit is hel
 with it: the kernels build_kernels(own=True) finds in it = the rows of its file, every row naming a qualifying GPU test file.
 `kernels`, `map` and `uncovered` take these units and files along.
 
+Units named in POST live in a subdirectory of csrc (post/: the tools that run on a finished stack) and are held exactly as
+the units of OWN are, for the same reason and one more: tests/test_cpu_deconvolve.py asks that every csrc/*.hip outside OWN
+is in read_map, and pins OWN itself, so a new unit directly in csrc/ can pass with neither table. Their rows are
+tests/kernel_post_<feature>.tsv (read_post), their kernels build_kernels(post=True); the unit's name carries the directory
+(post/kernels_wavelet), as the Makefile's command does. OWN, read_own, read_map, build_kernels() and build_kernels(own=True)
+return what they returned before POST existed.
+
 Covered: launched by a tests/test_gpu_*.py other than test_gpu_fullsize.py and the test_gpu_00_* bench and multi-rank
 files. Exit status of `uncovered` is 1 if any row has no qualifying file. Only symbol names are read, never instructions."""
 import argparse
@@ -49,6 +56,7 @@ MAP = os.path.join(ROOT, "tests", "kernel_map.tsv")
 HEADER = "unit\tmangled\tdemangled\ttest files"
 PARTS = ("background",)                      # tests/kernel_map_<name>.tsv read as a part of tests/kernel_map.tsv (see above)
 OWN = {"kernels_deconvolve": "deconvolve"}   # unit -> feature: its rows are tests/kernel_own_<feature>.tsv (see above)
+POST = {"post/kernels_wavelet": "wavelet"}   # unit (with its directory) -> feature: tests/kernel_post_<feature>.tsv (see above)
 MAX_COMPILES = 16
 SYMBOL = re.compile(r"_ZN3stk\w+")
 
@@ -60,7 +68,8 @@ def qualifies(test_file):
 
 
 def unit_commands(csrc=CSRC):
-    """{unit: argv} — the Makefile's own compile line of every .hip unit, turned into a device-only assembly run."""
+    """{unit: argv} — the Makefile's own compile line of every .hip unit, turned into a device-only assembly run. A unit in a
+    subdirectory of csrc is named with it (post/kernels_wavelet)."""
     dry = subprocess.run(["make", "-C", csrc, "-n", "-B", "--no-print-directory", "OBJDIR=@OBJ@"],
                          check=True, capture_output=True, text=True).stdout
     cmds = {}
@@ -71,8 +80,9 @@ def unit_commands(csrc=CSRC):
         i = argv.index("-c")
         assert argv[i + 1] == "-o" and argv[i + 2].startswith("@OBJ@/"), ln
         cmds[os.path.splitext(argv[-1])[0]] = argv[:i] + ["--cuda-device-only", "-S", "-o", None] + argv[i + 3:]
-    on_disk = {os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(csrc, "*.hip"))}
-    assert set(cmds) == on_disk, ("the Makefile's dry run and csrc/*.hip disagree", sorted(set(cmds) ^ on_disk))
+    on_disk = {os.path.splitext(os.path.relpath(p, csrc))[0].replace(os.sep, "/")
+               for p in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*", "*.hip"))}
+    assert set(cmds) == on_disk, ("the Makefile's dry run and csrc/*.hip, csrc/*/*.hip disagree", sorted(set(cmds) ^ on_disk))
     return cmds
 
 
@@ -90,13 +100,28 @@ def read_own(path=MAP):
     return rows
 
 
-def build_kernels(csrc=CSRC, workdir=None, own=False):
+def post_file(unit, path=MAP):
+    """The map file of a unit named in POST, beside `path`."""
+    return os.path.join(os.path.dirname(path), "kernel_post_" + POST[unit] + ".tsv")
+
+
+def read_post(path=MAP):
+    """The rows of every post map that exists, units sorted."""
+    rows = []
+    for unit in sorted(POST):
+        if os.path.isfile(post_file(unit, path)):
+            rows += read_rows(post_file(unit, path))
+    return rows
+
+
+def build_kernels(csrc=CSRC, workdir=None, own=False, post=False):
     """{unit: sorted mangled kernel names} of the tree under `csrc`, compiled as its Makefile compiles it: the units read_map
-    answers for, or (own=True) the units named in OWN."""
-    cmds = {u: c for u, c in unit_commands(csrc).items() if (u in OWN) == own}
+    answers for, or (own=True) the units named in OWN, or (post=True) the units named in POST."""
+    assert not (own and post)
+    cmds = {u: c for u, c in unit_commands(csrc).items() if (u in OWN) == own and (u in POST) == post}
     with tempfile.TemporaryDirectory(dir=workdir) as tmp:
         def one(unit):
-            out = os.path.join(tmp, unit + ".s")
+            out = os.path.join(tmp, unit.replace("/", "_") + ".s")
             argv = [out if a is None else a for a in cmds[unit]]
             r = subprocess.run(argv, cwd=csrc, capture_output=True, text=True)
             if r.returncode != 0:
@@ -185,10 +210,10 @@ def write_map(kernels, seen, path=MAP):
     pretty = demangle(n for names in kernels.values() for n in names)
     others = parts(path) + supplements(path)
     home = {r[1]: extra for extra in others for r in read_rows(extra)}
-    lines = {p: [] for p in [path] + others + [own_file(u, path) for u in sorted(kernels) if u in OWN]}
+    lines = {p: [] for p in [path] + others + [own_file(u, path) for u in sorted(kernels) if u in OWN] + [post_file(u, path) for u in sorted(kernels) if u in POST]}
     for unit in sorted(kernels):
         for n in kernels[unit]:
-            lines[own_file(unit, path) if unit in OWN else home.get(n, path)].append(f"{unit}\t{n}\t{pretty[n]}\t{','.join(sorted(seen.get(n, ())))}\n")
+            lines[own_file(unit, path) if unit in OWN else post_file(unit, path) if unit in POST else home.get(n, path)].append(f"{unit}\t{n}\t{pretty[n]}\t{','.join(sorted(seen.get(n, ())))}\n")
     for p, body in lines.items():
         with open(p, "w") as f:
             f.write(HEADER + "\n" + "".join(body))
@@ -210,18 +235,18 @@ def main():
     u.add_argument("--map", default=MAP)
     args = ap.parse_args()
     if args.cmd == "kernels":
-        for unit, names in sorted({**build_kernels(), **build_kernels(own=True)}.items()):
+        for unit, names in sorted({**build_kernels(), **build_kernels(own=True), **build_kernels(post=True)}.items()):
             for n in names:
                 print(f"{unit}\t{n}")
         return 0
     if args.cmd == "map":
         seen, traced = launched(args.traces)
         if args.keep:
-            for _, mangled, _, files in read_map(args.out) + read_own(args.out):
+            for _, mangled, _, files in read_map(args.out) + read_own(args.out) + read_post(args.out):
                 for t in files:
                     if t not in traced:
                         seen.setdefault(mangled, set()).add(t)
-        kernels = {**build_kernels(), **build_kernels(own=True)}
+        kernels = {**build_kernels(), **build_kernels(own=True), **build_kernels(post=True)}
         known = {n for names in kernels.values() for n in names}
         strangers = sorted(set(seen) - known)
         if strangers:
@@ -230,7 +255,7 @@ def main():
         write_map(kernels, seen, args.out)
         print(f"{args.out}: {len(known)} kernels, {len(traced)} test files traced")
     which = getattr(args, "map", None) or getattr(args, "out", MAP)
-    rows = read_map(which) + read_own(which)
+    rows = read_map(which) + read_own(which) + read_post(which)
     bare = uncovered(rows)
     per_unit = {}
     for unit, mangled, demangled, files in bare:
