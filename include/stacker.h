@@ -2138,6 +2138,121 @@ stk_status stk_wavelet_sigma(stk_ctx* ctx, const stk_image_f32* in, float* sigma
  * 1 .. 8 or a null table: STK_INVALID_PARAMS. */
 stk_status stk_wavelet_noise_table(int32_t levels, double* e);
 
+/* ---- display stretch: exact image statistics, the auto-stretch rule, the curve and the conversion to 8 or 16 bits: an
+ * EXTENSION beyond the reference ---------------------------------------------------------------------------------------
+ * The last step of every recipe: a finished stack is linear f32 with its sky at 1 - 3 % of full scale, so it is measured
+ * (stk_image_stats), a black point and a midtones balance are set from the sky level and its spread (stk_stretch_auto), and a
+ * non-linear curve and the output conversion are applied in one launch (stk_stretch). stk_auto_stretch is the three in one
+ * call. Everything on the device is f32 and each operation is rounded on its own (no contraction); every fmaf below is one.
+ * The host helpers work in f64, each operation rounded on its own too.
+ * Inputs: an stk_image_f32 d with 1, 3 or 4 channels, host or device, any row stride that is a multiple of 4 bytes;
+ *   cc = min(channels, 3) colour channels. The statistics optionally take a one-channel f32 mask plane M (width x height, its
+ *   own row stride in bytes, 0 = tightly packed; host or device memory), as stk_deconvolve takes it.
+ * 1. Statistics (stk_image_stats), per colour channel c. A sample counts iff it is finite and (there is no mask or
+ *    M(q) > 0). Its value is v, with -0.0f counted as +0.0f (decided on the bits). Of the N samples that count:
+ *      count = N; min; max; median = the lower median, the ((N + 1) / 2)-th smallest;
+ *      mad = the lower median of fabsf(v - median), an f32 subtraction;
+ *      q[i] for up to four quantiles p_i in 0 .. 1: the k-th smallest, k = min(N, max(1, (int64)ceil(p_i * N))) in f64.
+ *    All of them exact: a radix selection on order-preserving 32-bit keys, integer counts, so nothing depends on the order
+ *    of anything. N = 0, the alpha channel and the entries of q that were not asked for: zeros.
+ * 2. The auto rule (stk_stretch_auto; host code, no context, f64), per colour channel from its record, with the constants
+ *    of stk_stretch_auto_params:
+ *      c0 = max(min, median + (shadows_clip * 1.4826) * mad);
+ *      w = white (white_mode 0), max (1) or q[0] (2); if w <= c0 then w = c0 + 1;
+ *      x0 = (median - c0) / (w - c0);
+ *      m = ((target - 1) * x0) / ((2 * target - 1) * x0 - target), clamped to [1e-6, 1 - 1e-6]; x0 == 0: m = 0.5.
+ *    (mtf(m, x) = t iff m = mtf(t, x): the midtone that sends the sky's median to the target.) linked != 0: median, mad, min
+ *    and w are replaced by their means over the colour channels (summed in channel order, divided by cc) before the rule,
+ *    so every colour channel gets the same three values. black = (float)c0, white = (float)w, midtone = (float)m; the
+ *    entries from cc on are 0, 1 and 0.5. The record written is otherwise curve MTF, colour 0, out_depth F32, out_scale 1.
+ * 3. The stretch (stk_stretch), per pixel, for the colour channels c < cc, with r_c = white_c - black_c,
+ *    mm1_c = midtone_c - 1 and k_c = 2 midtone_c - 1 in f32 on the host:
+ *      x_c = fminf(fmaxf((v_c - black_c) / r_c, 0), 1)      (the IEEE fmaxf: a NaN becomes 0; +inf 1; -inf 0)
+ *      the curve f_c(x):
+ *        STK_STRETCH_LINEAR: x.
+ *        STK_STRETCH_MTF:    fminf(fmaxf((mm1_c x) / fmaf(k_c, x, -midtone_c), 0), 1).
+ *        STK_STRETCH_TABLE:  K = knots, T the table of K + 1 floats, one for all channels: t = x (float)K;
+ *                            i = min((int)t, K - 1); fr = t - (float)i; fmaf(T[i+1] - T[i], fr, T[i]).
+ *      colour == 0 or channels == 1: y_c = f_c(x_c).
+ *      colour == 1: L = ((x_0 + x_1) + x_2) / 3.0f; g = f_0(L); s = L > 0 ? g / L : 0; y_c = fminf(x_c s, 1): every channel
+ *        is scaled by what the curve does to the luminance, so hue and saturation survive (what an asinh stretch is for).
+ *      output: STK_DEPTH_F32: y_c out_scale. STK_DEPTH_U8 / U16: rintf(y_c 255.0f) / rintf(y_c 65535.0f), half to even
+ *        (out_scale is not read).
+ *      alpha (channels == 4): y_3 = fminf(fmaxf(v_3, 0), 1) through the same output step: no black point and no curve.
+ * Checks (anything else is STK_INVALID_PARAMS): width * height < 2^31; at most four quantiles, each finite and in 0 .. 1;
+ *   black_c and white_c finite with white_c > black_c (c < cc); midtone_c in (0, 1) under MTF (c < cc); knots 2 .. 65536 and
+ *   every table value finite and in 0 .. 1 under TABLE; out_scale finite; known enums; reserved 0; out has the input's width,
+ *   height, channels and location, and the depth of the parameters; shadows_clip <= 0; target_background in (0, 1); white
+ *   finite; white_quantile in 0 .. 1; linked 0 or 1; white_mode 0 .. 2; the records given to the rule finite.
+ * In place: with STK_DEPTH_F32, `out` may be exactly the input (same pointer, same row stride). Any other overlap of the
+ *   output with the input in the same memory space is refused.
+ * No result depends on scheduling, on the tiling or on what the context held before; a padded or misaligned image gives
+ *   the bits of its tight copy; host and device images give the same bits. Only pixel bytes are written.
+ * Not here: histogram equalisation and CLAHE, the inverted rule for bright backgrounds (median > 0.5), per-channel tables,
+ *   white balance from star colours, star masks, a histogram output, shard and files forms, 8-bit input. A multi-device
+ *   context uses its first device. */
+enum { STK_STRETCH_LINEAR = 0, STK_STRETCH_MTF = 1, STK_STRETCH_TABLE = 2 };
+enum { STK_CURVE_ASINH = 0, STK_CURVE_GAMMA = 1, STK_CURVE_SRGB = 2 };
+typedef struct {
+    int64_t count;            /* N: the samples of the channel that count */
+    float   min, max;
+    float   median, mad;      /* lower medians */
+    float   q[4];             /* the quantiles asked for, in the caller's order */
+} stk_image_stat;
+typedef struct {
+    int32_t curve;            /* STK_STRETCH_* */
+    int32_t colour;           /* 0: per channel; 1: colour-preserving (3 or 4 channels; with 1 channel it is per channel) */
+    int32_t out_depth;        /* STK_DEPTH_U8 / U16 / F32 */
+    int32_t reserved;         /* 0 */
+    float   black[4];         /* finite; the entry of alpha is not read */
+    float   white[4];         /* finite, > black */
+    float   midtone[4];       /* in (0, 1), read under STK_STRETCH_MTF; 0.5 is the identity */
+    float   out_scale;        /* finite; STK_DEPTH_F32 only; default 1 */
+} stk_stretch_params;
+typedef struct {
+    double  shadows_clip;     /* <= 0, in robust sigmas below the median; default -2.8 */
+    double  target_background;/* in (0, 1); default 0.25 */
+    double  white;            /* finite; the white point of white_mode 0; default 1 */
+    double  white_quantile;   /* 0 .. 1; the quantile stk_auto_stretch measures as q[0] under white_mode 2; default 0.999 */
+    int32_t linked;           /* 0 (default): per channel, which neutralises the background; 1: one rule for all */
+    int32_t white_mode;       /* 0 (default): `white`; 1: the channel's max; 2: the channel's q[0] */
+} stk_stretch_auto_params;
+/* The image a stretch writes: as stk_image_f32, with a depth. row_stride_bytes: 0 = tightly packed, else at least
+ * width * channels * (depth / 8) and a multiple of depth / 8; neither it nor data needs any other alignment. */
+typedef struct {
+    void*   data;
+    int32_t width, height, channels;
+    int32_t depth;            /* STK_DEPTH_U8 / U16 / F32 */
+    int32_t location;         /* STK_HOST | STK_DEVICE */
+    size_t  row_stride_bytes;
+} stk_image_out;
+/* Step 1. stats: 4 records, one per channel; those from min(channels, 3) on are zeros. quantiles_or_null: n_quantiles
+ * values (0 .. 4). stk_timing.finalize_ms is the launches alone; prep_ms the first pass (the counts, min and max and the
+ * first digit), warp_ms the second round of the values' selection (one histogram launch and one pick), align_ms the second
+ * round of the MAD's. */
+stk_status stk_image_stats(stk_ctx* ctx, const stk_image_f32* in, const float* mask_or_null, size_t mask_stride_bytes,
+                           int32_t mask_location, const double* quantiles_or_null, int32_t n_quantiles, stk_image_stat* stats);
+/* Step 3. table_or_null: knots + 1 floats in host memory, read under STK_STRETCH_TABLE only. finalize_ms is the launch. */
+stk_status stk_stretch(stk_ctx* ctx, const stk_image_f32* in, const stk_stretch_params* params, const float* table_or_null,
+                       int32_t knots, stk_image_out* out);
+/* Step 2 (host code, no context). stats: 4 records as stk_image_stats writes them; channels 1, 3 or 4; params_or_null:
+ * null = the defaults. */
+stk_status stk_stretch_auto(const stk_image_stat* stats, int32_t channels, const stk_stretch_auto_params* params_or_null,
+                            stk_stretch_params* out);
+/* A table for STK_STRETCH_TABLE (host code, no context, f64): table: knots + 1 floats, T[k] at x = (double)k / knots:
+ * STK_CURVE_ASINH: (float)(asinh(param x) / asinh(param)), param = beta > 0 (10 .. 1000 are usual);
+ * STK_CURVE_GAMMA: (float)pow(x, 1 / param), param = gamma > 0;
+ * STK_CURVE_SRGB:  x <= 0.0031308 ? 12.92 x : 1.055 pow(x, 1 / 2.4) - 0.055 (param is not read).
+ * T[0] = 0 and T[knots] = 1 exactly. knots 2 .. 65536. */
+stk_status stk_stretch_table(int32_t kind, double param, int32_t knots, float* table);
+/* Steps 1 - 3 in one call: the statistics of `in` (with the mask; the quantile white_quantile under white_mode 2, else
+ * none), the rule, then the stretch with the rule's black, white and midtone and this call's curve, colour, out->depth and
+ * out_scale. Bit for bit the three parts. stats_out_or_null: 4 records; params_out_or_null: the parameters as used. */
+stk_status stk_auto_stretch(stk_ctx* ctx, const stk_image_f32* in, const float* mask_or_null, size_t mask_stride_bytes,
+                            int32_t mask_location, const stk_stretch_auto_params* auto_params_or_null, int32_t curve, int32_t colour,
+                            float out_scale, const float* table_or_null, int32_t knots, stk_image_out* out,
+                            stk_image_stat* stats_out_or_null, stk_stretch_params* params_out_or_null);
+
 /* One frame's whole ECC preparation as ecc_match runs it per frame: cvt_color(BGR2GRAY) (utils.rs:136-142) followed
  * by findTransformECC's own GaussianBlur of the float image (lib.rs:769-777) in one fused pass. `out` is a tightly
  * packed width x height f32 plane in the frame's location. BGR frames, 8-bit or f32. */

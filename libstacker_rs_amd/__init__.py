@@ -22,7 +22,9 @@ from .api import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_RE
                   StarQualityParameters, star_frame_quality, star_quality_scores, star_quality_weights, star_shape_derive,
                   BG_CELL_DTYPE, BG_MEAN, BG_MEDIAN, BG_MODE, BackgroundParameters, background_estimate,
                   PSF_GAUSSIAN, PSF_MOFFAT, DeconvolveParameters, psf_from_shapes, psf_model,
-                  WAVELET_HARD, WAVELET_SOFT, WaveletParameters, wavelet_noise_table)
+                  WAVELET_HARD, WAVELET_SOFT, WaveletParameters, wavelet_noise_table,
+                  STRETCH_LINEAR, STRETCH_MTF, STRETCH_TABLE, CURVE_ASINH, CURVE_GAMMA, CURVE_SRGB, DEPTH_U8, DEPTH_U16, DEPTH_F32,
+                  STAT_DTYPE, StretchParameters, AutoStretchParameters, stretch_auto, stretch_table)
 
 __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchParameters", "MotionType",
            "StackerError", "Stacker", "SigmaClipParameters", "RobustClipParameters", "QuantileParameters", "WeightParameters",
@@ -35,4 +37,6 @@ __all__ = ["keypoint_match", "ecc_match", "KeyPointMatchParameters", "EccMatchPa
            "BackgroundParameters", "background_estimate", "BG_CELL_DTYPE", "BG_MEDIAN", "BG_MEAN", "BG_MODE",
            "DeconvolveParameters", "psf_model", "psf_from_shapes", "PSF_GAUSSIAN", "PSF_MOFFAT",
            "WaveletParameters", "wavelet_noise_table", "WAVELET_HARD", "WAVELET_SOFT",
+           "StretchParameters", "AutoStretchParameters", "stretch_auto", "stretch_table", "STAT_DTYPE", "STRETCH_LINEAR", "STRETCH_MTF",
+           "STRETCH_TABLE", "CURVE_ASINH", "CURVE_GAMMA", "CURVE_SRGB", "DEPTH_U8", "DEPTH_U16", "DEPTH_F32",
            "CFA_RGGB", "CFA_GRBG", "CFA_GBRG", "CFA_BGGR", "DEMOSAIC_BILINEAR", "DEMOSAIC_MHC", "DEMOSAIC_HA", "DEMOSAIC_SUPERPIXEL"]

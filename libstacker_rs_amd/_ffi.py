@@ -165,6 +165,26 @@ class WaveletParams(C.Structure):
                 ("residual_gain", C.c_float), ("amount", C.c_float), ("sigma", C.c_float * 4)]
 
 
+class ImageStat(C.Structure):
+    _fields_ = [("count", C.c_int64), ("min", C.c_float), ("max", C.c_float), ("median", C.c_float), ("mad", C.c_float),
+                ("q", C.c_float * 4)]
+
+
+class StretchParams(C.Structure):
+    _fields_ = [("curve", C.c_int32), ("colour", C.c_int32), ("out_depth", C.c_int32), ("reserved", C.c_int32),
+                ("black", C.c_float * 4), ("white", C.c_float * 4), ("midtone", C.c_float * 4), ("out_scale", C.c_float)]
+
+
+class StretchAutoParams(C.Structure):
+    _fields_ = [("shadows_clip", C.c_double), ("target_background", C.c_double), ("white", C.c_double),
+                ("white_quantile", C.c_double), ("linked", C.c_int32), ("white_mode", C.c_int32)]
+
+
+class ImageOut(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32),
+                ("depth", C.c_int32), ("location", C.c_int32), ("row_stride_bytes", C.c_size_t)]
+
+
 class HgProblem(C.Structure):
     _fields_ = [("src_pts", C.c_void_p), ("dst_pts", C.c_void_p), ("n", C.c_int32), ("inlier_mask_or_null", C.c_void_p)]
 
@@ -470,6 +490,14 @@ SIGNATURES = {
     "stk_wavelet_layers": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_int32, C.POINTER(ImageF32)]),
     "stk_wavelet_sigma": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_void_p, C.c_void_p]),
     "stk_wavelet_noise_table": (c_status, [C.c_int32, C.POINTER(C.c_double)]),
+    "stk_image_stats": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_double), C.c_int32,
+                                   C.POINTER(ImageStat)]),
+    "stk_stretch": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.POINTER(StretchParams), C.c_void_p, C.c_int32, C.POINTER(ImageOut)]),
+    "stk_stretch_auto": (c_status, [C.POINTER(ImageStat), C.c_int32, C.POINTER(StretchAutoParams), C.POINTER(StretchParams)]),
+    "stk_stretch_table": (c_status, [C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_float)]),
+    "stk_auto_stretch": (c_status, [C.c_void_p, C.POINTER(ImageF32), C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(StretchAutoParams),
+                                    C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.POINTER(ImageOut), C.POINTER(ImageStat),
+                                    C.POINTER(StretchParams)]),
     "stk_grey_blur_f32": (c_status, [C.c_void_p, C.POINTER(Frames), C.c_int32, C.c_void_p]),
     "stk_gaussian_blur_f32": (c_status, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p]),

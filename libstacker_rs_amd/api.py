@@ -779,6 +779,107 @@ def wavelet_noise_table(levels: int = 8):
     return e
 
 
+STRETCH_LINEAR, STRETCH_MTF, STRETCH_TABLE = range(3)      # STK_STRETCH_*: the curve of the display stretch
+CURVE_ASINH, CURVE_GAMMA, CURVE_SRGB = range(3)            # STK_CURVE_*: the tables stretch_table builds
+DEPTH_U8, DEPTH_U16, DEPTH_F32 = 8, 16, 32                 # STK_DEPTH_*
+STAT_DTYPE = np.dtype([("count", np.int64), ("min", np.float32), ("max", np.float32), ("median", np.float32), ("mad", np.float32),
+                       ("q", np.float32, 4)])                # stk_image_stat
+_DEPTH_DTYPE = {DEPTH_U8: np.uint8, DEPTH_U16: np.uint16, DEPTH_F32: np.float32}
+
+
+def _four(v, what, fill):
+    a = np.asarray(v, np.float64).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, 4)
+    if a.size > 4:
+        raise InvalidParams(f"{what}: at most 4 values")
+    return [float(x) for x in a] + [fill] * (4 - a.size)
+
+
+@dataclass
+class StretchParameters:          # extension beyond the reference: include/stacker.h, stk_stretch_params
+    """The display stretch of a linear f32 image: per colour channel x = clamp((v - black) / (white - black), 0, 1), then the
+    `curve` (STRETCH_LINEAR; STRETCH_MTF: the midtones transfer function with `midtone` in (0, 1), 0.5 = the identity;
+    STRETCH_TABLE: a table of knots + 1 values in 0 .. 1, see stretch_table, linearly interpolated), then the conversion to
+    `out_depth` (DEPTH_U8 / DEPTH_U16: rounded half to even; DEPTH_F32: times out_scale). `colour` 1 applies the curve to
+    the mean of the three x and scales every channel by the same factor, which keeps hue and saturation. black, white and
+    midtone: a scalar or up to 4 values. `table`: read under STRETCH_TABLE."""
+    curve: int = STRETCH_MTF
+    colour: int = 0
+    out_depth: int = DEPTH_F32
+    black: object = 0.0
+    white: object = 1.0
+    midtone: object = 0.5
+    out_scale: float = 1.0
+    table: object = None
+
+    def _c(self) -> _ffi.StretchParams:
+        c = _ffi.StretchParams(int(self.curve), int(self.colour), int(self.out_depth), 0)
+        c.black[:], c.white[:], c.midtone[:] = _four(self.black, "black", 0.0), _four(self.white, "white", 1.0), _four(self.midtone, "midtone", 0.5)
+        c.out_scale = float(self.out_scale)
+        return c
+
+    @staticmethod
+    def _from_c(c, table=None) -> "StretchParameters":
+        return StretchParameters(c.curve, c.colour, c.out_depth, np.array(c.black[:], np.float32), np.array(c.white[:], np.float32),
+                                 np.array(c.midtone[:], np.float32), float(c.out_scale), table)
+
+
+@dataclass
+class AutoStretchParameters:      # extension beyond the reference: include/stacker.h, stk_stretch_auto_params
+    """The screen-transfer-function rule: the black point `shadows_clip` (<= 0) robust sigmas below the median (never below the
+    minimum), the midtone that sends the median to `target_background`; `linked` 0: per channel (a neutral background), 1: one
+    rule from the channels' means. `white_mode` 0: the value `white`; 1: the channel's maximum; 2: its quantile
+    `white_quantile` (q[0] of the statistics)."""
+    shadows_clip: float = -2.8
+    target_background: float = 0.25
+    linked: int = 0
+    white_mode: int = 0
+    white: float = 1.0
+    white_quantile: float = 0.999
+
+    def _c(self) -> _ffi.StretchAutoParams:
+        return _ffi.StretchAutoParams(float(self.shadows_clip), float(self.target_background), float(self.white), float(self.white_quantile),
+                                      int(self.linked), int(self.white_mode))
+
+
+def _stats_c(stats):
+    a = np.zeros(4, STAT_DTYPE)
+    s = np.asarray(stats)
+    if s.dtype != STAT_DTYPE or s.ndim != 1 or not 1 <= s.size <= 4:
+        raise InvalidParams("stats: 1 .. 4 records of STAT_DTYPE expected (Stacker.image_stats)")
+    a[:s.size] = s
+    return a
+
+
+def stretch_auto(stats, params: Optional["AutoStretchParameters"] = None) -> "StretchParameters":
+    """The auto-stretch rule (stk_stretch_auto; host code, no GPU): from the records of Stacker.image_stats (one per colour
+    channel) the StretchParameters with black, white and midtone set, curve STRETCH_MTF, float32 output."""
+    s = np.asarray(stats)
+    a = _stats_c(s)
+    channels = 4 if s.size == 4 else s.size
+    if channels == 2:
+        raise InvalidParams("stats: 1, 3 or 4 records expected")
+    out = _ffi.StretchParams()
+    p = (params or AutoStretchParameters())._c()
+    st = _ffi.load().stk_stretch_auto(a.ctypes.data_as(C.POINTER(_ffi.ImageStat)), channels, C.byref(p), C.byref(out))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("stretch_auto: parameters out of range or records that are not finite")
+    return StretchParameters._from_c(out)
+
+
+def stretch_table(kind: int = CURVE_ASINH, param: float = 100.0, knots: int = 4096):
+    """A table for STRETCH_TABLE (stk_stretch_table; host code, no GPU): knots + 1 float32 values from 0 to 1: CURVE_ASINH:
+    asinh(param x) / asinh(param); CURVE_GAMMA: x^(1 / param); CURVE_SRGB: the sRGB encoding."""
+    if not 2 <= int(knots) <= 65536:
+        raise InvalidParams("stretch_table: knots 2 .. 65536")
+    t = np.zeros(int(knots) + 1, np.float32)
+    st = _ffi.load().stk_stretch_table(int(kind), float(param), int(knots), t.ctypes.data_as(C.POINTER(C.c_float)))
+    if st != 0:
+        raise _STATUS_EXC.get(st, StackerError)("stretch_table: an unknown kind or a parameter that is not positive and finite")
+    return t
+
+
 def _quantile_c(q) -> _ffi.QuantileParams:
     """QuantileParameters, a bare float, or None (the median)."""
     if q is None:
@@ -2007,6 +2108,104 @@ class Stacker:
         self._check(self._lib.stk_wavelet_sigma(self._h, C.byref(img), C.c_void_p(sigma.ctypes.data), C.c_void_p(med.ctypes.data) if return_median else None))
         cc = min(img.channels, 3)
         return (sigma[:cc].copy(), med[:cc].copy()) if return_median else sigma[:cc].copy()
+
+    # -- display stretch (include/stacker.h, "display stretch") ------------------------------------
+    def _image_mask_arg(self, mask, img, keep):
+        """An optional H x W float32 mask plane of an image: (pointer, row stride in bytes, location)."""
+        if mask is None:
+            return None, 0, HOST
+        mk = self._image_arg(mask, keep, "mask")
+        if (mk.width, mk.height, mk.channels) != (img.width, img.height, 1):
+            raise InvalidParams("mask: an H x W float32 plane expected")
+        return C.c_void_p(mk.data), mk.row_stride_bytes, mk.location
+
+    def _stretch_out(self, img, depth, out, keep):
+        """The image a stretch writes: a fresh H x W x C array or tensor of `depth` where the input lives, or the caller's `out`
+        (contiguous, or a view whose only non-contiguity is its row step): (result, stk_image_out)."""
+        if depth not in _DEPTH_DTYPE:
+            raise InvalidParams("out_depth: DEPTH_U8, DEPTH_U16 or DEPTH_F32")
+        if out is None:
+            res, addr = self._alloc(keep[0].device if img.location == DEVICE else None, (img.height, img.width, img.channels), _DEPTH_DTYPE[depth])
+            return res, _ffi.ImageOut(addr, img.width, img.height, img.channels, depth, img.location, 0)
+        o = out.numpy() if _is_torch(out) and not out.is_cuda else out
+        if str(o.dtype).replace("torch.", "") != np.dtype(_DEPTH_DTYPE[depth]).name or len(o.shape) not in (2, 3):
+            raise InvalidParams("out: an H x W x C image of the output depth expected")
+        el = depth // 8
+        if (o.is_contiguous() if _is_torch(o) else o.flags.c_contiguous):
+            rs = 0
+        else:
+            rs = _row_stride_bytes(tuple(o.shape), [s * el for s in o.stride()] if _is_torch(o) else o.strides, el)
+            if not rs:
+                raise InvalidParams("out: contiguous, or a view whose only non-contiguity is its row step")
+        if _is_torch(o):
+            self._tensor_ready(o)
+        keep.append(o)
+        return out, _ffi.ImageOut(o.data_ptr() if _is_torch(o) else o.ctypes.data, int(o.shape[1]), int(o.shape[0]),
+                                  int(o.shape[2]) if len(o.shape) == 3 else 1, depth, DEVICE if _is_torch(o) else HOST, rs)
+
+    @staticmethod
+    def _table_arg(curve, table, keep):
+        if int(curve) != STRETCH_TABLE:
+            return None, 0
+        if table is None:
+            raise InvalidParams("table: STRETCH_TABLE needs a table (stretch_table)")
+        t = np.ascontiguousarray(np.asarray(table, np.float32).reshape(-1))
+        if not 3 <= t.size <= 65537:
+            raise InvalidParams("table: 3 .. 65537 values (knots + 1)")
+        keep.append(t)
+        return C.c_void_p(t.ctypes.data), t.size - 1
+
+    def image_stats(self, image, mask=None, quantiles=()):
+        """Exact statistics of a float32 image per colour channel (stk_image_stats): an H x W (x C) array or device tensor, C =
+        1, 3 or 4 (alpha is not measured). Counted are the finite samples, under a `mask` (H x W float32, host or device)
+        those where it is > 0. Returns min(C, 3) records of STAT_DTYPE: count, min, max, the lower median, the MAD about it
+        and `q`: the k-th smallest for each of up to four `quantiles` in 0 .. 1."""
+        qs = np.ascontiguousarray(np.asarray(quantiles, np.float64).reshape(-1))
+        if qs.size > 4:
+            raise InvalidParams("quantiles: at most 4")
+        keep = []
+        img = self._image_arg(image, keep)
+        mptr, mstride, mloc = self._image_mask_arg(mask, img, keep)
+        stats = np.zeros(4, STAT_DTYPE)
+        self._check(self._lib.stk_image_stats(self._h, C.byref(img), mptr, mstride, mloc, qs.ctypes.data_as(C.POINTER(C.c_double)) if qs.size else None,
+                                              int(qs.size), stats.ctypes.data_as(C.POINTER(_ffi.ImageStat))))
+        return stats[:min(img.channels, 3)].copy()
+
+    def stretch_image(self, image, params: Optional["StretchParameters"] = None, out=None):
+        """The display stretch of a float32 image (stk_stretch): black and white point, curve and conversion to
+        params.out_depth in one launch. Returns an H x W x C image of that depth where the input lives; `out`: the image to
+        write instead, which for float32 output may be the input itself."""
+        sp = params or StretchParameters()
+        p = sp._c()
+        keep = []
+        img = self._image_arg(image, keep)
+        tptr, knots = self._table_arg(sp.curve, sp.table, keep)
+        res, o = self._stretch_out(img, int(sp.out_depth), out, keep)
+        self._check(self._lib.stk_stretch(self._h, C.byref(img), C.byref(p), tptr, knots, C.byref(o)))
+        return res
+
+    def auto_stretch_image(self, image, auto: Optional["AutoStretchParameters"] = None, curve: int = STRETCH_MTF, colour: int = 0,
+                           out_depth: int = DEPTH_F32, out_scale: float = 1.0, table=None, mask=None, out=None, return_stats: bool = False,
+                           return_params: bool = False):
+        """Statistics, the auto rule and the stretch in one call (stk_auto_stretch): bit for bit image_stats (under `mask`),
+        stretch_auto and stretch_image with the rule's black, white and midtone and this call's curve, colour, out_depth and
+        out_scale. return_stats adds the records, return_params the StretchParameters as used."""
+        ap = (auto or AutoStretchParameters())._c()
+        keep = []
+        img = self._image_arg(image, keep)
+        mptr, mstride, mloc = self._image_mask_arg(mask, img, keep)
+        tptr, knots = self._table_arg(curve, table, keep)
+        res, o = self._stretch_out(img, int(out_depth), out, keep)
+        stats, used = np.zeros(4, STAT_DTYPE), _ffi.StretchParams()
+        self._check(self._lib.stk_auto_stretch(self._h, C.byref(img), mptr, mstride, mloc, C.byref(ap), int(curve), int(colour), float(out_scale), tptr, knots,
+                                               C.byref(o), stats.ctypes.data_as(C.POINTER(_ffi.ImageStat)) if return_stats else None,
+                                               C.byref(used) if return_params else None))
+        ret = (res,)
+        if return_stats:
+            ret += (stats[:min(img.channels, 3)].copy(),)
+        if return_params:
+            ret += (StretchParameters._from_c(used, table),)
+        return ret[0] if len(ret) == 1 else ret
 
     def _frame_outputs(self, m, out_depth: int, out, keep):
         """The per-frame outputs of a call that writes one image per frame (stk_calibrate, the background calls): a fresh

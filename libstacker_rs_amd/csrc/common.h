@@ -484,6 +484,42 @@ inline size_t wv_state_words(int channels) { return (size_t)channels * (2 + WV_B
 hipError_t launch_wavelet_select_reset(const WvSelectArgs& a, hipStream_t s);
 hipError_t launch_wavelet_select_hist(const WvSelectArgs& a, hipStream_t s);
 hipError_t launch_wavelet_select_pick(const WvSelectArgs& a, hipStream_t s);
+// display stretch (post/kernels_stretch.hip; definition: include/stacker.h, "display stretch"). Strides of the images in
+// ELEMENTS of their depth. The statistics: an exact radix selection of up to ST_SLOTS ranks per colour channel at once, 4
+// rounds of 8 bits from the top of an order-preserving 32-bit key. A slot is one rank: slot 0 the median, slots 1 .. 4 the
+// quantiles (the values' phase: the key is the sign-flipped value), slot ST_MAD the MAD (its own phase: the key is
+// bits(fabsf(v - median)), the median decoded from slot 0). state, in words: per channel ST_HEAD words (the smallest and the
+// largest key), then per (channel, slot) 2 words (the prefix found so far, the rank left inside it), then per (channel, slot)
+// ST_BINS histogram words. Round 0 of the values' phase has no prefix: one histogram (slot 0's) serves every slot; its sum
+// is N, which the host reads to form the ranks.
+constexpr int ST_DIGIT_BITS = 8, ST_ROUNDS = 4, ST_BINS = 1 << ST_DIGIT_BITS;
+constexpr int ST_SLOTS = 6, ST_MAD = 5, ST_HEAD = 2;
+constexpr int ST_FORM_DIRECT = 0, ST_FORM_MERGED = 1;     // the histogram launch: one LDS atomic per key, or per run of equal digits of a thread
+// the hist launch's workgroups: rows beyond them are strided by the grid. 4 per CU: every workgroup ends by flushing its bins
+// with global atomics on the same few words, and 4096 of them measured 1.54 x slower over the call
+constexpr int ST_TARGET_BLOCKS = 1024;
+__host__ __device__ inline size_t st_sel_at(int channels, int c, int slot) { return (size_t)channels * ST_HEAD + ((size_t)c * ST_SLOTS + slot) * 2; }
+__host__ __device__ inline size_t st_bins_at(int channels, int c, int slot) { return (size_t)channels * (ST_HEAD + 2 * ST_SLOTS) + ((size_t)c * ST_SLOTS + slot) * ST_BINS; }
+__host__ __device__ inline size_t st_state_words(int channels) { return (size_t)channels * (ST_HEAD + ST_SLOTS * (2 + ST_BINS)); }
+struct StStatArgs {
+    const float* in; const float* mask; uint32_t* state;
+    size_t in_stride, mask_stride;
+    int w, h, cn, channels;
+    int form;                                // ST_FORM_*
+    int round, slot0, slots;                 // the slots of this phase: slot0 .. slot0 + slots - 1 (values: 0, 1 + quantiles; MAD: ST_MAD, 1)
+    uint32_t rank[3][ST_SLOTS];              // read by the pick of round 0
+};
+hipError_t launch_stretch_stat_reset(const StStatArgs& a, hipStream_t s);
+hipError_t launch_stretch_stat_hist(const StStatArgs& a, hipStream_t s);
+hipError_t launch_stretch_stat_pick(const StStatArgs& a, hipStream_t s);
+struct StStretchArgs {
+    const float* in; void* out; const float* table;
+    size_t in_stride, out_stride;
+    int w, h, cn, depth, curve, colour, knots;
+    float black[3], r[3], mid[3], mm1[3], k[3];
+    float out_scale;
+};
+hipError_t launch_stretch(const StStretchArgs& a, hipStream_t s);
 // colour-filter mosaics (kernels_demosaic.hip; definition: include/stacker.h, stk_mosaic). One record per frame of the
 // launch; strides in bytes; (w, h): the mosaic's size, at least 3 x 3 (superpixel: 2 x 2).
 constexpr int DEM_TW = 64, DEM_TH = 16;      // output pixels per workgroup tile of demosaic_kernel (32 x 8 cells of 2 x 2)

@@ -295,6 +295,22 @@ inline WaveletLayout wavelet_layout(int w, int h, int channels, size_t image_byt
     return L;
 }
 
+// ctx->local, the display stretch (stretch.cpp): the selection's state and histogram words (`channels` = min(cn, 3); 0: none,
+// the stretch alone), the copies of a host image and of a host mask (0 bytes for device ones), the table of a table curve
+// and the staged output of a host image
+struct StretchLayout { size_t state, image, mask, table, out, total; };
+inline StretchLayout stretch_layout(int channels, size_t image_bytes, size_t mask_bytes, size_t table_bytes, size_t out_bytes) {
+    Carver c;
+    StretchLayout L{};
+    L.state = c.take(channels ? stk::st_state_words(channels) * sizeof(uint32_t) : 0);
+    L.image = c.take(image_bytes);
+    L.mask = c.take(mask_bytes);
+    L.table = c.take(table_bytes);
+    L.out = c.take(out_bytes);
+    L.total = c.total;
+    return L;
+}
+
 // ctx->local, colour-filter mosaics (demosaic.cpp): the per-frame records, then the tightly packed outputs of host mosaics
 // (stk_cfa_mask: no records, the plane of a host caller)
 struct DemosaicLayout { size_t records, out, total; };

@@ -38,6 +38,15 @@ tests/kernel_post_<feature>.tsv (read_post), their kernels build_kernels(post=Tr
 (post/kernels_wavelet), as the Makefile's command does. OWN, read_own, read_map, build_kernels() and build_kernels(own=True)
 return what they returned before POST existed.
 
+Units named in EXTRA are the fourth and LAST table: every later unit goes here, wherever it lives, and no further mechanism
+is needed. The existing tests pin OWN, POST, read_map(), read_own() and read_post() and ask that every unit unit_commands()
+returns is in one of the three, so unit_commands() leaves the units of EXTRA out unless asked (extra=True; its own
+disk-against-Makefile assertion still covers every .hip), and their rows are tests/kernel_extra_<feature>.tsv (read_extra),
+their kernels build_kernels(extra=True). The test that comes with a unit checks THAT UNIT's rows alone (the kernels
+recomputed with the Makefile's command = its rows, every row a qualifying GPU test file, no kernel listed twice anywhere,
+write_map byte for byte) and must not pin the table's contents or any total row count: the next feature adds one entry to
+EXTRA and one file, and nothing else changes. Everything the older functions return stays what it was.
+
 Covered: launched by a tests/test_gpu_*.py other than test_gpu_fullsize.py and the test_gpu_00_* bench and multi-rank
 files. Exit status of `uncovered` is 1 if any row has no qualifying file. Only symbol names are read, never instructions."""
 import argparse
@@ -57,6 +66,7 @@ HEADER = "unit\tmangled\tdemangled\ttest files"
 PARTS = ("background",)                      # tests/kernel_map_<name>.tsv read as a part of tests/kernel_map.tsv (see above)
 OWN = {"kernels_deconvolve": "deconvolve"}   # unit -> feature: its rows are tests/kernel_own_<feature>.tsv (see above)
 POST = {"post/kernels_wavelet": "wavelet"}   # unit (with its directory) -> feature: tests/kernel_post_<feature>.tsv (see above)
+EXTRA = {"post/kernels_stretch": "stretch"}  # unit (with its directory, if any) -> feature: tests/kernel_extra_<feature>.tsv; new units go HERE
 MAX_COMPILES = 16
 SYMBOL = re.compile(r"_ZN3stk\w+")
 
@@ -67,9 +77,10 @@ def qualifies(test_file):
             and test_file != "test_gpu_fullsize.py" and not test_file.startswith("test_gpu_00_"))
 
 
-def unit_commands(csrc=CSRC):
+def unit_commands(csrc=CSRC, extra=False):
     """{unit: argv} — the Makefile's own compile line of every .hip unit, turned into a device-only assembly run. A unit in a
-    subdirectory of csrc is named with it (post/kernels_wavelet)."""
+    subdirectory of csrc is named with it (post/kernels_wavelet). The units named in EXTRA are returned only when asked for
+    (extra=True: all units); the assertion below covers them either way."""
     dry = subprocess.run(["make", "-C", csrc, "-n", "-B", "--no-print-directory", "OBJDIR=@OBJ@"],
                          check=True, capture_output=True, text=True).stdout
     cmds = {}
@@ -83,7 +94,7 @@ def unit_commands(csrc=CSRC):
     on_disk = {os.path.splitext(os.path.relpath(p, csrc))[0].replace(os.sep, "/")
                for p in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*", "*.hip"))}
     assert set(cmds) == on_disk, ("the Makefile's dry run and csrc/*.hip, csrc/*/*.hip disagree", sorted(set(cmds) ^ on_disk))
-    return cmds
+    return cmds if extra else {u: c for u, c in cmds.items() if u not in EXTRA}
 
 
 def own_file(unit, path=MAP):
@@ -114,11 +125,25 @@ def read_post(path=MAP):
     return rows
 
 
-def build_kernels(csrc=CSRC, workdir=None, own=False, post=False):
+def extra_file(unit, path=MAP):
+    """The map file of a unit named in EXTRA, beside `path`."""
+    return os.path.join(os.path.dirname(path), "kernel_extra_" + EXTRA[unit] + ".tsv")
+
+
+def read_extra(path=MAP):
+    """The rows of every extra map that exists, units sorted."""
+    rows = []
+    for unit in sorted(EXTRA):
+        if os.path.isfile(extra_file(unit, path)):
+            rows += read_rows(extra_file(unit, path))
+    return rows
+
+
+def build_kernels(csrc=CSRC, workdir=None, own=False, post=False, extra=False):
     """{unit: sorted mangled kernel names} of the tree under `csrc`, compiled as its Makefile compiles it: the units read_map
-    answers for, or (own=True) the units named in OWN, or (post=True) the units named in POST."""
-    assert not (own and post)
-    cmds = {u: c for u, c in unit_commands(csrc).items() if (u in OWN) == own and (u in POST) == post}
+    answers for, or (own=True) the units named in OWN, or (post=True) the units named in POST, or (extra=True) those in EXTRA."""
+    assert own + post + extra <= 1
+    cmds = {u: c for u, c in unit_commands(csrc, extra=True).items() if (u in OWN) == own and (u in POST) == post and (u in EXTRA) == extra}
     with tempfile.TemporaryDirectory(dir=workdir) as tmp:
         def one(unit):
             out = os.path.join(tmp, unit.replace("/", "_") + ".s")
@@ -210,10 +235,12 @@ def write_map(kernels, seen, path=MAP):
     pretty = demangle(n for names in kernels.values() for n in names)
     others = parts(path) + supplements(path)
     home = {r[1]: extra for extra in others for r in read_rows(extra)}
-    lines = {p: [] for p in [path] + others + [own_file(u, path) for u in sorted(kernels) if u in OWN] + [post_file(u, path) for u in sorted(kernels) if u in POST]}
+    lines = {p: [] for p in [path] + others + [own_file(u, path) for u in sorted(kernels) if u in OWN] + [post_file(u, path) for u in sorted(kernels) if u in POST]
+             + [extra_file(u, path) for u in sorted(kernels) if u in EXTRA]}
     for unit in sorted(kernels):
         for n in kernels[unit]:
-            lines[own_file(unit, path) if unit in OWN else post_file(unit, path) if unit in POST else home.get(n, path)].append(f"{unit}\t{n}\t{pretty[n]}\t{','.join(sorted(seen.get(n, ())))}\n")
+            lines[own_file(unit, path) if unit in OWN else post_file(unit, path) if unit in POST else extra_file(unit, path) if unit in EXTRA
+                  else home.get(n, path)].append(f"{unit}\t{n}\t{pretty[n]}\t{','.join(sorted(seen.get(n, ())))}\n")
     for p, body in lines.items():
         with open(p, "w") as f:
             f.write(HEADER + "\n" + "".join(body))
@@ -235,18 +262,18 @@ def main():
     u.add_argument("--map", default=MAP)
     args = ap.parse_args()
     if args.cmd == "kernels":
-        for unit, names in sorted({**build_kernels(), **build_kernels(own=True), **build_kernels(post=True)}.items()):
+        for unit, names in sorted({**build_kernels(), **build_kernels(own=True), **build_kernels(post=True), **build_kernels(extra=True)}.items()):
             for n in names:
                 print(f"{unit}\t{n}")
         return 0
     if args.cmd == "map":
         seen, traced = launched(args.traces)
         if args.keep:
-            for _, mangled, _, files in read_map(args.out) + read_own(args.out) + read_post(args.out):
+            for _, mangled, _, files in read_map(args.out) + read_own(args.out) + read_post(args.out) + read_extra(args.out):
                 for t in files:
                     if t not in traced:
                         seen.setdefault(mangled, set()).add(t)
-        kernels = {**build_kernels(), **build_kernels(own=True), **build_kernels(post=True)}
+        kernels = {**build_kernels(), **build_kernels(own=True), **build_kernels(post=True), **build_kernels(extra=True)}
         known = {n for names in kernels.values() for n in names}
         strangers = sorted(set(seen) - known)
         if strangers:
@@ -255,7 +282,7 @@ def main():
         write_map(kernels, seen, args.out)
         print(f"{args.out}: {len(known)} kernels, {len(traced)} test files traced")
     which = getattr(args, "map", None) or getattr(args, "out", MAP)
-    rows = read_map(which) + read_own(which) + read_post(which)
+    rows = read_map(which) + read_own(which) + read_post(which) + read_extra(which)
     bare = uncovered(rows)
     per_unit = {}
     for unit, mangled, demangled, files in bare:
