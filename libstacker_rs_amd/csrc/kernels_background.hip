@@ -9,12 +9,11 @@
 //      per wave and 256 pixels for the wave's base). The ORDER of the keys in LDS therefore depends on the order in which
 //      the waves arrive; nothing below depends on the order, only on the multiset. A position outside the frame or the
 //      window forms NO address: x and y are taken from [a, b] of the window, which lies inside the frame.
-//   2. rounds t = 0 .. T over S_t = the keys in [lo_t, hi_t]: the exact median and MAD by kernels_star_deep.hip's two-level
-//      radix selection (a 256-bin histogram of the high byte, one copy per wave, integer LDS atomics, summed and
-//      prefix-summed in registers by wave shuffles (bg_pick), then the low byte of the keys in the chosen bin; the same two
-//      levels on |K - med|). A thread adds a RUN of equal high bytes with one atomic: on sky nearly every key shares its
-//      high byte. |S_t| is the total of the round's first histogram; where it equals |S_{t-1}| the rounds stop, since
-//      every later round would repeat the last one.
+//   2. rounds t = 0 .. T over S_t = the keys in [lo_t, hi_t]: the exact median and MAD by two selections of lds_select.h
+//      at workgroup scope. A thread's share is every 256th key of the compacted window that lies in [lo_t, hi_t]; the
+//      high-byte passes add merged runs (on sky nearly every key shares its high byte). |S_t| is the total that the
+//      round's first pick reports; where it equals |S_{t-1}| the rounds stop there, before the low-byte pass, since every
+//      later round would repeat the last one.
 //   3. kept, and sum and sum2 over S_T as int64 shuffle trees, four wave partials through LDS, added by thread 0.
 // Counts and sums are integers: the record does not depend on the order in which the atomics land.
 // No global atomics, no floating-point atomics, no scratch.
@@ -29,6 +28,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lds_select.h"
 #include "star_key.h"
 
 namespace stk {
@@ -39,36 +39,18 @@ namespace {
 // frames, planes and outputs are global memory by the entry points' contract, and these casts say so.
 #define BG_GLOBAL __attribute__((address_space(1)))
 
-constexpr int BG_HIST_BYTES = 4 * 256 * 4;          // four 256-bin histograms, one per wave
-constexpr int BG_MISC_BYTES = 32 + 64;              // pick[2], wsum[4], count, pad; then 4 + 4 int64 wave partials
+using BgSelect = WorkgroupSelect<true>;             // a round asks for the lower median of a set it has yet to count
+// the dynamic LDS block: the selection's ints (histograms, pick, wsum), count and a pad, sum and sum2 of the four waves, the keys
+constexpr int BG_COUNT_INTS = 2, BG_SUM_BYTES = (4 + 4) * 8;
+constexpr int BG_HIST_BYTES = BgSelect::HIST_INTS * 4, BG_MISC_BYTES = (BgSelect::INTS - BgSelect::HIST_INTS + BG_COUNT_INTS) * 4 + BG_SUM_BYTES;
+constexpr int BG_SUM_OFFSET = BG_HIST_BYTES + BG_MISC_BYTES - BG_SUM_BYTES;
 constexpr int BG_KEY_OFFSET = BG_HIST_BYTES + BG_MISC_BYTES;
+static_assert(BG_SUM_OFFSET % 8 == 0 && BG_KEY_OFFSET % 16 == 0, "the int64 partials and the keys are aligned");
 
 template <typename T>
 __device__ __forceinline__ uint32_t bg_key(T v, float scale) {
     if constexpr (sizeof(T) == 4) return key_f32(v, scale);
     else return v;
-}
-
-// kernels_star_deep.hip's deep_pick with the total: the bin that holds the k-th smallest (k counted from 1; k = 0 on entry:
-// the lower median, k = (total + 1) / 2) of the values counted in hist[4][256], and k's rank inside that bin. Every thread
-// of the 256 calls it; on return hist is zero again, k and total are the same in every thread.
-__device__ __forceinline__ int bg_pick(int* hist, int* pick, int* wsum, int t, int& k, int& total) {
-    __syncthreads();                                                      // the histogram is complete
-    const int v = hist[t] + hist[256 + t] + hist[512 + t] + hist[768 + t];
-    hist[t] = 0; hist[256 + t] = 0; hist[512 + t] = 0; hist[768 + t] = 0;
-    int x = v;                                                            // inclusive prefix sum over the wave's 64 bins
-    const int lane = t & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-    if (lane == 63) wsum[t >> 6] = x;
-    __syncthreads();
-    total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    if (k == 0) k = (total + 1) / 2;
-    for (int i = 0; i < (t >> 6); i++) x += wsum[i];
-    if (x >= k && x - v < k) { pick[0] = t; pick[1] = k - (x - v); }      // exactly one bin (total >= k >= 1)
-    __syncthreads();
-    k = pick[1];
-    return pick[0];
 }
 
 template <typename O>
@@ -86,10 +68,8 @@ __global__ __launch_bounds__(256) void background_cells_kernel(BgCellsArgs a) {
     constexpr int CC = CN < 3 ? CN : 3;
     extern __shared__ __align__(16) unsigned char bg_lds[];
     int* hist = reinterpret_cast<int*>(bg_lds);
-    int* s_pick = hist + 4 * 256;
-    int* s_wsum = s_pick + 2;
-    int* s_count = s_wsum + 4;
-    long long* s_sum = reinterpret_cast<long long*>(bg_lds + BG_HIST_BYTES + 32);
+    int* s_count = hist + BgSelect::INTS;
+    long long* s_sum = reinterpret_cast<long long*>(bg_lds + BG_SUM_OFFSET);
     uint16_t* key = reinterpret_cast<uint16_t*>(bg_lds + BG_KEY_OFFSET);
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -101,8 +81,8 @@ __global__ __launch_bounds__(256) void background_cells_kernel(BgCellsArgs a) {
     const BG_GLOBAL uint8_t* src = (const BG_GLOBAL uint8_t*)a.frames[blockIdx.y];
     const BG_GLOBAL uint8_t* mask = (const BG_GLOBAL uint8_t*)a.mask;
     stk_bg_cell* out = a.cells + ((size_t)blockIdx.y * gridDim.x + node) * CC;
-    int* hw = &hist[wave * 256];
-    for (int i = t; i < 4 * 256; i += 256) hist[i] = 0;
+    const BgSelect sel{hist, hist + BgSelect::PICK_AT, hist + BgSelect::WSUM_AT, t, wave};
+    for (int i = t; i < BgSelect::HIST_INTS; i += 256) hist[i] = 0;
 
     for (int c = 0; c < CC; c++) {
         if (t == 0) *s_count = 0;
@@ -133,45 +113,13 @@ __global__ __launch_bounds__(256) void background_cells_kernel(BgCellsArgs a) {
         // ---- 2. the rounds
         int lo = 0, hi = 65535, med = 0, mad = 0, kept = 0;
         for (int round = 0;; round++) {
-            int kk = 0, tot = 0;
-            {
-                int run = 0, bin = 0;                                     // high byte: runs of equal bins, one atomic each
-                for (int i = t; i < n; i += 256) {
-                    const int g = key[i];
-                    if (g < lo || g > hi) continue;
-                    const int b = g >> 8;
-                    if (run && b != bin) { atomicAdd(&hw[bin], run); run = 0; }
-                    bin = b; run++;
-                }
-                if (run) atomicAdd(&hw[bin], run);
-            }
-            const int hb = bg_pick(hist, s_pick, s_wsum, t, kk, tot);
+            const auto window = select_share(t, n, 256, [=](int i) { return key[i] >= lo && key[i] <= hi; }, [=](int i) { return (int)key[i]; });
+            int kk = 0, tot;                                              // k = 0: the lower median of a set yet to be counted
+            const int hb = select_high<SelectFill::Merged>(sel, window, SelectKey{}, kk, tot);
             if (tot == kept) break;                                       // S_t = S_{t-1}: every later round repeats the last
             kept = tot;
-            for (int i = t; i < n; i += 256) {
-                const int g = key[i];
-                if (g >= lo && g <= hi && (g >> 8) == hb) atomicAdd(&hw[g & 255], 1);
-            }
-            med = (hb << 8) | bg_pick(hist, s_pick, s_wsum, t, kk, tot);
-            {
-                int run = 0, bin = 0;
-                for (int i = t; i < n; i += 256) {
-                    const int g = key[i];
-                    if (g < lo || g > hi) continue;
-                    const int b = abs(g - med) >> 8;
-                    if (run && b != bin) { atomicAdd(&hw[bin], run); run = 0; }
-                    bin = b; run++;
-                }
-                if (run) atomicAdd(&hw[bin], run);
-            }
-            kk = (kept + 1) / 2;
-            const int hd = bg_pick(hist, s_pick, s_wsum, t, kk, tot);
-            for (int i = t; i < n; i += 256) {
-                const int g = key[i];
-                const int d = abs(g - med);
-                if (g >= lo && g <= hi && (d >> 8) == hd) atomicAdd(&hw[d & 255], 1);
-            }
-            mad = (hd << 8) | bg_pick(hist, s_pick, s_wsum, t, kk, tot);
+            med = select_low(sel, window, SelectKey{}, hb, kk);
+            mad = select16<SelectFill::Merged>(sel, window, SelectAbsDev{med}, (kept + 1) / 2);
             if (round >= a.clip_iters) break;
             const int d = max((int)fminf(ceilf(a.ks * (float)mad), 65536.0f), 1);
             lo = max(lo, med - d);

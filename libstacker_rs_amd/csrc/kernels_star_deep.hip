@@ -7,19 +7,16 @@
 //      (u8, u16) or float4s (f32) where the frame's base and row stride are aligned to that unit and the tile is whole in x,
 //      element by element otherwise; both routes compute every key with the same function on the same values, so the LDS
 //      contents are the same. A position outside the frame forms NO address: its key is 0 and is never used.
-//   2. the exact median and MAD of the tile's (up to 4096) keys inside the frame by a two-level radix selection: a 256-bin
-//      histogram of the high byte, one copy per wave (integer LDS atomics), summed, prefix-summed in registers (deep_pick) and
-//      searched for the bin that holds the k-th; then a 256-bin histogram of the low byte of the keys in that bin; then
-//      the same two levels on |K - med|. Four passes over the LDS tile. The counts are integers and the sums are taken in a
-//      fixed order: the result does not depend on the order in which the atomics land. On a sky tile nearly every key
-//      shares its high byte, so a thread adds a RUN of equal bins (its 16 pixels of one column) with one atomic in the
-//      high-byte passes.
+//   2. the exact median and MAD of the tile's (up to 4096) keys inside the frame: two selections of lds_select.h at workgroup
+//      scope, four passes over the LDS tile. A thread's share is its 16 pixels of one column; on a sky tile nearly every key
+//      shares its high byte, so the high-byte passes add merged runs.
 //      thr = med + max((int)fminf(ceilf(ks * (float)mad), 65536.0f), min_contrast).
 //   3. the peak test, the window walk (S <= 225 * 65535, |Sx|, |Sy| <= 840 * 65535: int32), the LDS list,
 //   4. the rank by (S descending, py, px) and the record slots are kernels_star.hip's, to the letter.
 // No global atomics, no floating-point atomics, no scratch.
 #include "common.h"
 #include "grey.h"
+#include "lds_select.h"
 #include "star_key.h"
 
 namespace stk {
@@ -84,32 +81,14 @@ __device__ __forceinline__ void deep_key_x4(const T* p, float scale, uint32_t k[
     }
 }
 
-// The bin that holds the k-th smallest (k counted from 1) of the values counted in hist[4][256] (one histogram per wave),
-// and k's rank inside that bin. Every thread of the 256 calls it; on return hist is zero again and may be filled anew.
-// pick[0 .. 1]: the answer, wsum[0 .. 3]: the waves' totals.
-__device__ __forceinline__ int deep_pick(int* hist, int* pick, int* wsum, int t, int& k) {
-    __syncthreads();                                                      // the histogram is complete
-    const int v = hist[t] + hist[256 + t] + hist[512 + t] + hist[768 + t];
-    hist[t] = 0; hist[256 + t] = 0; hist[512 + t] = 0; hist[768 + t] = 0;
-    int x = v;                                                            // inclusive prefix sum over the wave's 64 bins
-    const int lane = t & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-    if (lane == 63) wsum[t >> 6] = x;
-    __syncthreads();
-    for (int i = 0; i < (t >> 6); i++) x += wsum[i];
-    if (x >= k && x - v < k) { pick[0] = t; pick[1] = k - (x - v); }      // exactly one bin
-    __syncthreads();
-    k = pick[1];
-    return pick[0];
-}
+using DeepSelect = WorkgroupSelect<false>;    // the rank is known: (tile pixels inside the frame + 1) / 2 >= 1
 
 template <typename T, int CN>
 __global__ __launch_bounds__(256) void star_detect_deep_kernel(StarDetectArgs a, float scale) {
     __shared__ __align__(16) uint16_t key[SD_ROWS * SD_GS];
-    __shared__ int hist[4 * 256];
+    __shared__ int hist[DeepSelect::HIST_INTS];
     __shared__ int list[SD_LIST * 7];
-    __shared__ int s_pick[2], s_wsum[4], s_count;
+    __shared__ int s_pick[DeepSelect::PICK_INTS], s_wsum[DeepSelect::WSUM_INTS], s_count;
     const int w = a.w, h = a.h, R = a.radius;
     const int gn = SD + 2 * R;                                            // key rows (= columns) in use
     const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
@@ -120,7 +99,7 @@ __global__ __launch_bounds__(256) void star_detect_deep_kernel(StarDetectArgs a,
 
     // ---- 1. keys of the tile + halo into LDS: row r <-> image row y0 - R + r, column SD_LEFT + lx <-> image column x0 + lx,
     //         lx in [-R, SD + R). Outside the frame: 0, and no address.
-    for (int i = t; i < 4 * 256; i += 256) hist[i] = 0;
+    for (int i = t; i < DeepSelect::HIST_INTS; i += 256) hist[i] = 0;
     if (t == 0) s_count = 0;
     constexpr uintptr_t UNIT = sizeof(T) == 4 ? 15 : 3;                   // x0 * CN * sizeof(T) is a multiple of 16
     const bool wide = x0 + SD <= w && ((reinterpret_cast<uintptr_t>(src) | a.stride) & UNIT) == 0;
@@ -161,35 +140,11 @@ __global__ __launch_bounds__(256) void star_detect_deep_kernel(StarDetectArgs a,
     const int tw = min(SD, w - x0), th = min(SD, h - y0);                  // the tile's pixels inside the frame
     const int rows = lx < tw ? max(min(16, th - ly0), 0) : 0;             // this thread's pixels
     const uint16_t* col = &key[(R + ly0) * SD_GS + SD_LEFT + lx];
-    int* hw = &hist[(t >> 6) * 256];
+    const DeepSelect sel{hist, s_pick, s_wsum, t, t >> 6};
     const int kth = (tw * th + 1) / 2;
-    int med, mad;
-    {
-        int run = 0, bin = 0;                                             // high byte: runs of equal bins, one atomic each
-        for (int i = 0; i < rows; i++) {
-            const int b = col[i * SD_GS] >> 8;
-            if (run && b != bin) { atomicAdd(&hw[bin], run); run = 0; }
-            bin = b; run++;
-        }
-        if (run) atomicAdd(&hw[bin], run);
-        int k = kth;
-        const int hi = deep_pick(hist, s_pick, s_wsum, t, k);
-        for (int i = 0; i < rows; i++) { const int g = col[i * SD_GS]; if ((g >> 8) == hi) atomicAdd(&hw[g & 255], 1); }
-        med = (hi << 8) | deep_pick(hist, s_pick, s_wsum, t, k);
-    }
-    {
-        int run = 0, bin = 0;
-        for (int i = 0; i < rows; i++) {
-            const int b = abs((int)col[i * SD_GS] - med) >> 8;
-            if (run && b != bin) { atomicAdd(&hw[bin], run); run = 0; }
-            bin = b; run++;
-        }
-        if (run) atomicAdd(&hw[bin], run);
-        int k = kth;
-        const int hi = deep_pick(hist, s_pick, s_wsum, t, k);
-        for (int i = 0; i < rows; i++) { const int d = abs((int)col[i * SD_GS] - med); if ((d >> 8) == hi) atomicAdd(&hw[d & 255], 1); }
-        mad = (hi << 8) | deep_pick(hist, s_pick, s_wsum, t, k);
-    }
+    const auto column = select_share(0, rows, 1, [](int) { return true; }, [=](int i) { return (int)col[i * SD_GS]; });
+    const int med = select16<SelectFill::Merged>(sel, column, SelectKey{}, kth);
+    const int mad = select16<SelectFill::Merged>(sel, column, SelectAbsDev{med}, kth);
     const int dT = max((int)fminf(ceilf(a.ks * (float)mad), 65536.0f), a.min_contrast);
     const int thr = med + dT;
 

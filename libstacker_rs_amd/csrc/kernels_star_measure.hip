@@ -8,15 +8,14 @@
 //   1. the (2 Ro + 1)^2 box of keys around the star (at most 33 x 33) goes to the wave's LDS as u16, lane l taking elements
 //      l, l + 64, ... A position outside the frame forms NO address: its key is 0 and is never used. Each lane keeps a bit
 //      per element it loaded: inside the frame and inside the ring.
-//   2. bg and mad by a two-level radix selection, as kernels_star_deep.hip's deep_pick does per workgroup: a 256-bin integer
-//      histogram of the high byte in the wave's LDS (integer LDS atomics), four bins per lane, prefix sums by wave shuffles,
-//      the bin that holds the k-th; then the low byte of the keys of that bin; then the same two levels on |K - bg|. The counts
-//      are integers: the result does not depend on the order in which the atomics land.
+//   2. bg and mad by two selections of lds_select.h at wave scope: a 256-bin histogram in the wave's LDS, four bins per lane.
+//      A lane's share is the ring elements it loaded; every key gets an atomic of its own (the direct fill).
 //   3. the aperture's sums: per lane in int32 (at most 10 pixels of at most 65535 x 144 each), then wave-shuffle trees on
 //      int64; every lane ends with the totals, lane 0 writes the record.
 // No global atomics, no floating-point atomics, no scratch.
 #include "common.h"
 #include "grey.h"
+#include "lds_select.h"
 #include "star_key.h"
 
 namespace stk {
@@ -29,44 +28,11 @@ constexpr int SM_BOX = 2 * SM_RO_MAX + 1;                    // 33
 constexpr int SM_KEYS = (SM_BOX * SM_BOX + 7) & ~7;          // 1096 u16 per wave: the waves' boxes stay 16-byte aligned
 constexpr int SM_ITERS = (SM_BOX * SM_BOX + 63) / 64;        // 18 elements per lane at most
 
-// LDS written by one lane of the wave is read by another: order the accesses for the compiler and the hardware
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 template <typename V>
 __device__ __forceinline__ V wave_sum(V x) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
     return x;
-}
-
-// The bin that holds the k-th smallest (k counted from 1, 1 <= k <= the total) of the values counted in the wave's
-// hist[256], and k's rank inside that bin. Every lane of the wave calls it; on return hist is zero again.
-__device__ __forceinline__ int measure_pick(int* hist, int lane, int& k) {
-    wave_sync();                                                          // the histogram is complete
-    const int4 v = *reinterpret_cast<const int4*>(&hist[4 * lane]);
-    *reinterpret_cast<int4*>(&hist[4 * lane]) = make_int4(0, 0, 0, 0);
-    const int s = v.x + v.y + v.z + v.w;
-    int x = s;                                                            // inclusive prefix sum over the lanes
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-    int bin = -1, rank = 0;
-    if (x >= k && x - s < k) {                                            // exactly one lane
-        int r = k - (x - s);
-        if (r <= v.x) { bin = 0; rank = r; }
-        else if ((r -= v.x) <= v.y) { bin = 1; rank = r; }
-        else if ((r -= v.y) <= v.z) { bin = 2; rank = r; }
-        else { bin = 3; rank = r - v.z; }
-        bin += 4 * lane;
-    }
-    const unsigned long long m = __ballot(bin >= 0);
-    const int src = m ? __ffsll((long long)m) - 1 : 0;
-    k = __shfl(rank, src, 64);
-    bin = __shfl(bin, src, 64);
-    wave_sync();                                                          // the zeroes are in place before the next fill
-    return max(bin, 0);
 }
 
 template <typename T, int CN>
@@ -117,20 +83,11 @@ __global__ __launch_bounds__(256) void star_measure_kernel(StarMeasureArgs a, fl
     int bg = 0, mad = 0;
     if (n_ring > 0) {
         const int kth = (n_ring + 1) / 2;
-        int k = kth;
-        for (int it = 0; it < SM_ITERS; it++)
-            if ((ring >> it) & 1u) atomicAdd(&hist[key[it * 64 + lane] >> 8], 1);
-        int hi = measure_pick(hist, lane, k);
-        for (int it = 0; it < SM_ITERS; it++)
-            if ((ring >> it) & 1u) { const int g = key[it * 64 + lane]; if ((g >> 8) == hi) atomicAdd(&hist[g & 255], 1); }
-        bg = (hi << 8) | measure_pick(hist, lane, k);
-        k = kth;
-        for (int it = 0; it < SM_ITERS; it++)
-            if ((ring >> it) & 1u) atomicAdd(&hist[abs((int)key[it * 64 + lane] - bg) >> 8], 1);
-        hi = measure_pick(hist, lane, k);
-        for (int it = 0; it < SM_ITERS; it++)
-            if ((ring >> it) & 1u) { const int d = abs((int)key[it * 64 + lane] - bg); if ((d >> 8) == hi) atomicAdd(&hist[d & 255], 1); }
-        mad = (hi << 8) | measure_pick(hist, lane, k);
+        const WaveSelect sel{hist, lane};
+        const uint16_t* own = key + lane;                                 // element it * 64 + lane
+        const auto ring_keys = select_share(0, SM_ITERS, 1, [=](int it) { return ((ring >> it) & 1u) != 0; }, [=](int it) { return (int)own[it * 64]; });
+        bg = select16<SelectFill::Direct>(sel, ring_keys, SelectKey{}, kth);
+        mad = select16<SelectFill::Direct>(sel, ring_keys, SelectAbsDev{bg}, kth);
     }
     const int thr = max((int)fminf(ceilf(a.ks * (float)mad), 65536.0f), a.min_contrast);
 

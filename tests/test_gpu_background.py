@@ -11,7 +11,7 @@ import pytest
 import background_restate as br
 from libstacker_rs_amd import BG_MEAN, BG_MODE, BackgroundParameters, InvalidParams, Stacker, StarDeepParameters, StarParameters, background_estimate
 from test_cpu_background import PLANAR, QUALITY_BAR, planar_frame, planar_params, quality_params
-from test_gpu_star_deep import _place
+from test_gpu_star_deep import POPULATIONS, _place, _two_populations
 
 pytestmark = pytest.mark.gpu
 DTYPES = {8: np.uint8, 16: np.uint16, 32: np.float32}
@@ -125,6 +125,46 @@ def test_special_contents(st):
     mask[32, 32] = 0
     c = both(_sky(rng, h, w, 16, 3), mask)
     assert (c["n"][1, 1] == 1).all() and (c["kept"][1, 1] == 1).all() and (c["mad"][1, 1] == 0).all() and c["n"].sum() == 3
+
+
+@pytest.mark.parametrize("below", [0, 1], ids=["k", "k-1"])
+def test_median_rank_on_a_bin_boundary_and_extreme_keys(st, below):
+    """The selection's edge `x >= k && x - v < k` at the smallest step: the 17 x 17 window of node (1, 1) of a 33 x 33 frame
+    holds exactly k = 145, or k - 1, keys in the lower of two high-byte bins. Second population set: the lower keys are all 0
+    and 65535 is present, so that |K - med| reaches bin 255 of both levels."""
+    rng = np.random.default_rng(50 + below)
+    for low, mid, top in POPULATIONS:
+        K = mid + rng.integers(0, 256, (33, 33))
+        K[8:25, 8:25] = _two_populations(rng, 289, 145 - below, low, mid, top).reshape(17, 17)
+        for clip in (0, 2):
+            p = BackgroundParameters(step=16, clip_iters=clip, kappa=2.5)
+            want = br.cells_restate(K.astype(np.uint16), p)
+            assert want.shape == (3, 3, 1) and want["n"][1, 1, 0] == 289
+            if clip == 0:                                                    # the restatement alone: the rank does fall on the boundary
+                assert want["med"][1, 1, 0] >> 8 == (mid if below else low) >> 8 and (K[8:25, 8:25].min() >> 8, K.max()) == (low >> 8, top)
+            for device in (0, 1):
+                _fields_equal(st.background_cells([_place(K.astype(np.uint16), device, device)], p)[0], want, (low, clip, device))
+
+
+def test_one_key_no_key_and_rounds_that_stop_on_their_first_pick(st):
+    """At the smallest step, 33 x 33: a constant frame, whose second round keeps the first round's set and so stops on its
+    first pick (kept = n, lo and hi one key either side); every pixel but one masked: one window of one key; every pixel
+    masked: records of zeros."""
+    p = BackgroundParameters(step=16, clip_iters=2, kappa=2.5)
+    f = np.full((33, 33, 3), 40000, np.uint16)
+    want = br.cells_restate(f, p)
+    assert (want["kept"] == want["n"]).all() and (want["n"] > 0).all() and (want["lo"] == 39999).all() and (want["hi"] == 40001).all()
+    _fields_equal(st.background_cells([f], p)[0], want, "constant")
+    rng = np.random.default_rng(9)
+    f = rng.integers(0, 65536, (33, 33, 3)).astype(np.uint16)
+    mask = np.ones((33, 33), np.uint8)
+    got = st.background_cells([f], p, mask)[0]
+    assert got.tobytes() == np.zeros_like(got).tobytes()
+    _fields_equal(got, br.cells_restate(f, p, mask), "empty")
+    mask[20, 11] = 0                                                         # inside the window of node (1, 1) alone
+    want = br.cells_restate(f, p, mask)
+    assert want["n"].sum() == 3 and (want["n"][1, 1] == 1).all() and (want["med"][1, 1] == f[20, 11]).all() and (want["mad"][1, 1] == 0).all()
+    _fields_equal(st.background_cells([f], p, mask)[0], want, "one key")
 
 
 # ---- 3. apply against the restatement -------------------------------------------------------------------------------

@@ -90,6 +90,25 @@ def _speckle(rng, h, w, depth):
     return g
 
 
+# (low, mid, top) of _two_populations: the populations' high bytes differ; keys 0 and 65535, the ends of both radix levels
+POPULATIONS = [(0x1200, 0x3000, 0x9000), (0, 0x3000, 65535)]
+
+
+def _two_populations(rng, n, c, low, mid, top):
+    """n keys in random order for the boundary cases of the two-level radix selection: exactly c of them in the bin of `low`
+    (high byte low >> 8; all of them 0 where low is 0), the others in the bin of `mid` but for a few, at least one, raised
+    to `top`. With c = k the k-th smallest is the largest of the lower bin (the cumulative count equals the rank), with
+    c = k - 1 the smallest of the upper one (rank 1 inside its bin)."""
+    assert 0 <= c <= n - 2 and low >> 8 != mid >> 8 and top > mid + 255
+    order = rng.permutation(n)
+    v = mid + rng.integers(0, 256, n)
+    v[order[c:][rng.random(n - c) < 0.03]] = top
+    v[order[c]] = top
+    v[order[:c]] = low + (rng.integers(0, 256, c) if low else 0)
+    assert int((v >> 8 == low >> 8).sum()) == c and int((v >> 8 == mid >> 8).sum()) >= 1 and v.max() == top
+    return v
+
+
 def _check_detect(st, frames, p, deep, device, padded):
     lists, peaks = st.star_detect_deep([_place(f, padded, device) for f in frames], p, deep, return_peaks=True)
     total = 0
@@ -154,6 +173,28 @@ def test_keys_over_the_full_range_in_one_tile(st, depth, cn):
         for device, padded in ((1, 0), (0, 1)):
             found = _check_detect(st, frames, p, F32, device, padded)
         assert found >= (0 if p.min_contrast == 65535 else 5)
+
+
+@pytest.mark.parametrize("w,h", [(64, 64), (65, 70)])
+@pytest.mark.parametrize("below", [0, 1], ids=["k", "k-1"])
+def test_median_rank_on_a_bin_boundary_and_extreme_keys(st, w, h, below):
+    """The selection's edge `x >= k && x - v < k`: in every tile (64 x 64; at 65 x 70 also 1 x 64, 64 x 6 and 1 x 6: fewer keys
+    than threads) the keys of the lower high-byte bin number exactly the median's rank k, or k - 1, so the median is the last
+    key of one bin or the first of the next. Second population set: the lower keys are all 0 and 65535 is present, so that
+    |K - med| reaches bin 255 of both levels (the MAD itself cannot: at least k keys lie within min(med - min, max - med) of
+    the median). The raised keys are isolated peaks: S carries med, npix carries thr = med + d(mad)."""
+    rng = np.random.default_rng(1000 * w + below)
+    p = StarParameters(radius=2, kappa=1.0, min_pixels=1, max_stars=1024, min_contrast=1)
+    for low, mid, top in POPULATIONS:
+        K = np.zeros((h, w), np.int64)
+        for y0, x0 in itertools.product(range(0, h, 64), range(0, w, 64)):
+            t = K[y0:y0 + 64, x0:x0 + 64]
+            t[...] = _two_populations(rng, t.size, (t.size + 1) // 2 - below, low, mid, top).reshape(t.shape)
+        med, mad, _ = sd.tile_stats(K, p)                                   # the restatement alone: the rank does fall on the boundary
+        assert (med >> 8 == (mid if below else low) >> 8).all() and (K.min() >> 8, K.max()) == (low >> 8, top)
+        assert (mad == 0).all() if low == 0 and not below else (mad > 0).any()
+        for device, padded in ((1, 0), (0, 1)):
+            assert _check_detect(st, [K.astype(np.uint16)], p, None, device, padded) >= 3
 
 
 @pytest.mark.parametrize("depth", [16, 32])

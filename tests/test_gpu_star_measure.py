@@ -13,7 +13,7 @@ import star_measure_restate as sm
 from libstacker_rs_amd import (STAR_DTYPE, InvalidParams, NotEnoughFiles, Stacker, StarDeepParameters, StarMeasureParameters, StarParameters,
                                StarQualityParameters, synth)
 from test_cpu_star_measure import quality_stack
-from test_gpu_star_deep import F32, _frame, _np, _place, _speckle
+from test_gpu_star_deep import F32, POPULATIONS, _frame, _np, _place, _speckle, _two_populations
 
 pytestmark = pytest.mark.gpu
 RINGS = [(2, 3, 3), (7, 10, 14), (12, 13, 16)]
@@ -120,6 +120,33 @@ def test_edges_of_the_frame(st, depth, cn):
                 assert s.tobytes() == z.tobytes(), p
             else:
                 assert s.tobytes() == got[0][inside.index(p)].tobytes(), p
+
+
+@pytest.mark.parametrize("ring", [RINGS[0], RINGS[2]], ids=["ro3", "ro16"])
+@pytest.mark.parametrize("below", [0, 1], ids=["k", "k-1"])
+def test_ring_median_rank_on_a_bin_boundary_and_extreme_keys(st, ring, below):
+    """The selection's edge `x >= k && x - s < k` in a wave: the ring of the star at the centre of a 48 x 48 frame (the
+    smallest ring, 4 pixels, and the largest radius) holds exactly k, or k - 1, keys in the lower of two high-byte bins, so bg
+    is the last key of one bin or the first of the next. Second population set: the lower keys are all 0 and 65535 is
+    present, so that |K - bg| reaches bin 255 of both levels."""
+    R, Ri, Ro = ring
+    rng = np.random.default_rng(10 * Ro + below)
+    y, x = np.mgrid[0:48, 0:48]
+    d2 = (x - 24) ** 2 + (y - 24) ** 2
+    in_ring = (d2 >= Ri * Ri) & (d2 <= Ro * Ro)
+    n = int(in_ring.sum())
+    k = (n + 1) // 2
+    assert (n == 4) if Ro == 3 else (n > 128)                                   # one key in four lanes; several keys in every lane
+    mp = StarMeasureParameters(radius=R, ring_inner=Ri, ring_outer=Ro, kappa=1.0, min_contrast=1, min_pixels=1)
+    for low, mid, top in POPULATIONS:
+        K = mid + rng.integers(0, 256, (48, 48))
+        K[d2 <= R * R] = np.maximum(mid + 8000 - 60 * d2[d2 <= R * R], mid)   # a star in the aperture
+        K[in_ring] = _two_populations(rng, n, k - below, low, mid, top)
+        f = K.astype(np.uint16)
+        want = sm.measure(f, _stars([(24, 24)]), mp)[0]                     # the restatement alone: the rank does fall on the boundary
+        assert want["n_ring"] == n and want["bg"] >> 8 == (mid if below else low) >> 8 and (K[in_ring].min() >> 8, K[in_ring].max()) == (low >> 8, top)
+        for device, padded in ((1, 0), (0, 1)):
+            _check(st, [f], [_stars([(24, 24)])], mp, None, device, padded)
 
 
 def test_frames_narrower_than_the_ring(st):
